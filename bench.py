@@ -12,7 +12,12 @@ weight-sharing contexts (one group's encoder overlaps the others' decode).  The 
 is reported next to the pipelined throughput.  Everything runs through the C ABI of libwhisper_mi355x.so
 (no torch compute; torch is only used for torch.distributed / RCCL at N > 1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model large-v2] [--batch 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model large-v2] [--batch 8] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure -- the early-stop
+workload, the latency of one batch alone, the event-bracketed roofline pass (+ its in-situ twin), the other BASELINE.json
+configurations and the CPU baseline -- runs only with --full (each still switchable off by its --no-* flag).
+--dump-outputs DIR writes the last timed step's tokens and lengths as DIR/tokens.npy and DIR/lengths.npy (float64).
 
 N > 1: one rank per GPU -- started by torch.distributed.run (the driver), or by bench.py itself when `--gpus N` is given
 without a launcher (it re-executes under torch.distributed.run); a launcher whose WORLD_SIZE differs from --gpus is an
@@ -20,6 +25,7 @@ error.  Each rank owns its own chunks (weak scaling, no data-path collective) an
 RCCL inside the timed region.  Prints ONE JSON line on rank 0.
 """
 import argparse
+import concurrent.futures
 import ctypes
 import json
 import os
@@ -532,7 +538,15 @@ def main():
     ap.add_argument("--no-single-batch", action="store_true",
                     help="skip the one-batch-in-flight latency measurement (profiling runs: keeps every decode launch of the "
                          "process at the timed group size)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the early-stop workload, the one-batch latency, the roofline pass, "
+                         "the other configurations and the CPU baseline (off by default: a plain run is the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for its LAST step (one batch: token ids [batch][new tokens] and "
+                         "generated lengths [batch], rank 0's) as DIR/tokens.npy and DIR/lengths.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (ms_per_step is the timed region over the steps)")
 
     # --gpus N decides the world size (it used to be parsed and never used).  Under a launcher
     # (torch.distributed.run sets WORLD_SIZE) an EXPLICIT --gpus must agree with it; when --gpus is not given the launcher's
@@ -619,7 +633,12 @@ def main():
     # EVERY chunk of the run is a different recording (seeded noise; chunk 0 of rank 0 the structured KAT-3 chunk): decode
     # group g reads its own slice of the resident PCM, so a crossed row, cache or lane shows up in the token checks below
     n_res = nb * max(F, args.steps, args.warmup if args.warmup > 0 else 0)
-    pcm = np.stack([structured_pcm16() if (i == 0 and rank == 0) else synth_pcm16(rank * n_res + i) for i in range(n_res)])
+    pcm = np.empty((n_res, 480000), np.int16)
+
+    def synth_into(i):   # one seeded generator per chunk: the same arrays whatever thread fills them
+        pcm[i] = structured_pcm16() if (i == 0 and rank == 0) else synth_pcm16(rank * n_res + i)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, effective_cores())) as ex:
+        list(ex.map(synth_into, range(n_res)))
     d_pcm = ctx.to_device(pcm)
     chunk_bytes = 480000 * 2
 
@@ -653,6 +672,7 @@ def main():
         c.set_lanes(1)   # this harness supplies the concurrency itself (S host threads x one decode group each)
     gathered = None
     seen = {}   # pass tag -> {group index: tokens}: compared after the timed region
+    seen_lens = {}   # pass tag -> {group index: generated lengths}: --dump-outputs
     pass_tag = ["warmup"]
     es_tokens = [0]
 
@@ -688,6 +708,7 @@ def main():
             with lock:
                 stage_sum[:] += c.last_stage_ms()
                 seen.setdefault(pass_tag[0], {})[g] = toks
+                seen_lens.setdefault(pass_tag[0], {})[g] = lens
             return toks, lens
 
         _, g = sharding.run_grouped(plan, S, run_group, nb, max_new, dist=dist if (use_dist and collective) else None,
@@ -738,12 +759,19 @@ def main():
     all_rows = np.concatenate([timed_tokens[g] for g in sorted(timed_tokens)], axis=0) if timed_tokens else np.zeros((0, max_new), np.int32)
     distinct_rows = len({r.tobytes() for r in all_rows})
     per_row = [len(set(r.tolist())) for r in all_rows]
+    if args.dump_outputs and rank == 0:
+        # the last timed step = the last nb rows of the last decode group (a group's rows are its batches in order)
+        g_last = max(timed_tokens)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), timed_tokens[g_last][-nb:].astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "lengths.npy"),
+                np.asarray(seen_lens["timed"][g_last], np.float64).reshape(-1)[-nb:])
 
     # Early stop: the same plan, but every chunk stops after a synthetic budget of uniform(40..200)
     # tokens instead of the forced 224 -- finished rows leave the attention walk, finished groups are not decoded further.
     # Reported beside the headline (which stays the fixed-length decode); every rank runs it (the collective is symmetric).
     early = None
-    if args.steps > 0 and not args.no_early_stop:
+    if args.full and not args.no_early_stop:
         run_steps(args.steps, early_stop=True)      # graphs of the stop variant captured outside the timed pass
         sync_all()
         es_tokens[0] = 0
@@ -765,7 +793,7 @@ def main():
 
     # for transparency: the same workload with ONE batch in flight (latency of a single batch of nb chunks)
     single_ms = None
-    if (S > 1 or F > 1) and not args.no_single_batch:
+    if args.full and (S > 1 or F > 1) and not args.no_single_batch:
         sync_all()
         t1 = time.perf_counter()
         for _ in range(2):
@@ -783,7 +811,8 @@ def main():
     grp_steps = max(sharding.plan_groups(args.steps, F, S)) if args.steps > 0 else 1
     mean_grp_steps = args.steps / max(1, len(sharding.plan_groups(args.steps, F, S)))   # weights stream once per group
     grp_chunks = nb * grp_steps
-    if rank == 0:
+    prof_steps, prof_wall_ms = 0, 0.0
+    if rank == 0 and args.full:
         ctx.profile_reset()
         ctx.profile_enable(True)
         n_prof = 1 if grp_chunks > 16 else min(args.steps, 3)
@@ -869,11 +898,11 @@ def main():
                             frac=ach / MFMA_BF16_PEAK_TF, alg_flops_per_launch=work)
 
     others = None
-    if rank == 0 and world == 1 and not args.no_other_configs and args.model == "large-v2" and args.steps > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and args.model == "large-v2":
         others = other_configs(B, args.model, pcm, max_new)
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:   # at N > 1 too: CPU-only, after the timed region; the other ranks wait at the closing barrier
+    if args.full and rank == 0 and not args.no_cpu_baseline:   # at N > 1 too: CPU-only, after the timed region; the other ranks wait at the closing barrier
         try:
             cpu = cpu_baseline(ctx, dims, pcm[1], prompt)
         except Exception as e:  # the baseline leg must never take the GPU number down with it
@@ -946,7 +975,7 @@ def main():
             # steps): sum(ms_per_step) <= kernel_families_pass.wall_ms_per_step, the pass's own wall time per step
             "kernel_families_pass": {"steps": prof_steps, "group_chunks": grp_chunks, "lanes": 1,
                                      "wall_ms_per_step": prof_wall_ms / max(prof_steps, 1),
-                                     "sum_family_ms_per_step": fam_sum},
+                                     "sum_family_ms_per_step": fam_sum} if prof_steps else None,
             "kernel_families": fams,
         }
         line["summary"] = build_summary(line)   # LAST key: inside the 2 000-character tail the driver keeps

@@ -53,6 +53,13 @@ def test_gpus_flag_and_launcher_rule():
     assert '"--gpus", type=int, default=None' in src and "--standalone" in src and "bind((" not in src
 
 
+def test_steps_must_be_positive():
+    """ms_per_step is the timed region over --steps: zero timed steps is refused before any GPU work."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr[-500:]
+
+
 def _fake_sysfs(tmp_path, gpus, nodes):
     """gpus: {bdf: numa_node}; nodes: {node: cpulist}"""
     for bdf, n in gpus.items():

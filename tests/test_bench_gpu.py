@@ -27,7 +27,7 @@ def test_bench_distributed_branch_runs_at_world_size_one():
     env = dict(os.environ, WM_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0",
                WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1",
-                        "--new-tokens", "24", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env,
+                        "--new-tokens", "24", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -169,7 +169,7 @@ def test_config5_job_on_one_rank_and_on_two_gloo_ranks():
     (b) two REAL ranks sharing device 0 over gloo at --total-chunks 30: 15 chunks per rank = exactly the per-GPU shard of the
         8-GPU job, block partition + the fixed-stride all-gather, `cpu_baseline` present on a line with n_gpus > 1, the
         compact `summary` last."""
-    common = ["--model", "large-v3", "--steps", "1", "--warmup", "1", "--no-early-stop", "--no-other-configs"]
+    common = ["--model", "large-v3", "--steps", "1", "--warmup", "1", "--no-early-stop", "--no-other-configs", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--total-chunks", "120", "--no-cpu-baseline"]
                        + common, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
@@ -195,3 +195,43 @@ def test_config5_job_on_one_rank_and_on_two_gloo_ranks():
     cb = two["cpu_baseline"]                         # the CPU leg now also runs at N > 1 (rank 0, after the timed region)
     assert cb is not None and cb["kind"] == "port" and (cb["value"] is None or cb["value"] > 0), cb
     assert list(two)[-1] == "summary" and two["summary"]["n_gpus"] == 2
+
+
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path, pkg):
+    """A plain run sets up, warms up, times the steps and prints the line: the early-stop workload, the one-batch latency,
+    the roofline pass and the CPU baseline belong to --full.  --dump-outputs writes the last timed step's tokens and
+    lengths; they are the rows the product returns for that batch alone, and --full (whose passes follow the timed
+    region) dumps the same arrays."""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    common = ["--gpus", "1", "--model", "base", "--steps", "3", "--warmup", "1", "--new-tokens", "16"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra
+                           + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    p, f = lines["plain"], lines["full"]
+    assert p["steps"] == 3 and p["config"]["decode_groups"] == [1, 1, 1]
+    assert abs(p["value"] - 30.0 * 8 * 3 / (p["ms_per_step"] * 3e-3)) < 1e-6 * p["value"]
+    assert p["early_stop"] is None and p["single_batch_latency_ms"] is None and p["roofline"] is None
+    assert p["cpu_baseline"] is None and p["kernel_families_pass"] is None and p["other_configs"] is None
+    assert p["token_checks"] == {"warmup_pass_equals_timed_pass": True}
+    assert f["early_stop"] is not None and f["roofline"] is not None and len(f["token_checks"]) == 3, f["token_checks"]
+    toks = [np.load(str(tmp_path / n / "tokens.npy")) for n in ("plain", "full")]
+    lens = [np.load(str(tmp_path / n / "lengths.npy")) for n in ("plain", "full")]
+    assert toks[0].dtype == np.float64 and toks[0].shape == (8, 16) and np.array_equal(toks[0], toks[1])
+    assert lens[0].dtype == np.float64 and np.array_equal(lens[0], lens[1]) and np.all(lens[0] == 16)
+    # the last step is batch 2 = chunks 16..23 of the run, decoded here alone through the C ABI
+    dims = pkg.binding.MODEL_DIMS["base"]
+    ctx = pkg.binding.Context(dims)
+    try:
+        ctx.init_synthetic(20240928, matrix_gain=importlib.import_module("openai_whisper_coreml_amd.weights").lively_gain(dims))
+        ctx.finalize()
+        pcm = np.stack([bench.synth_pcm16(i) for i in range(16, 24)])
+        want, want_lens = ctx.transcribe_greedy(pcm, [50258, 50259, 50359, 50363], 16, eot=-1)
+    finally:
+        ctx.close()
+    assert np.array_equal(toks[0], want) and np.array_equal(lens[0], want_lens)

@@ -14,8 +14,8 @@ bash tools/profile_round.sh $R > $O/${R}_profile_round.log 2>&1; tail -3 $O/${R}
 python tools/pmc_traffic_update.py $O/${R}_pmc_fetch_size_group56.txt large-v2 56 "profiles/${R}_pmc_fetch_size_group56.txt"
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
 bash tools/profile_tiny_en.sh $R > $O/${R}_kernel_trace_tiny_en_b1_summary.txt 2>&1
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/${R}_bench_n1_driver_cmd.json 2> $O/${R}_bench_n1_driver_cmd.err; echo "bench driver rc=$?"
-timeout 900 python bench.py > $O/${R}_bench_n1_default.json 2> $O/${R}_bench_n1_default.err; echo "bench default rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_n1_driver_cmd.json 2> $O/${R}_bench_n1_driver_cmd.err; echo "bench driver rc=$?"
+timeout 900 python bench.py --full > $O/${R}_bench_n1_default.json 2> $O/${R}_bench_n1_default.err; echo "bench default rc=$?"
 python - "$R" <<'PY'
 import json, sys
 R = sys.argv[1]

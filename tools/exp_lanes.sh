@@ -1,5 +1,5 @@
 # A/B runs of bench.py's timed configuration under launch-shape knobs (debug library): one line per run
-run() { python bench.py --warmup 5 --no-cpu-baseline --no-early-stop --no-other-configs $1 2>/dev/null | python -c "
+run() { python bench.py --full --warmup 5 --no-cpu-baseline --no-early-stop --no-other-configs $1 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=l['roofline']
