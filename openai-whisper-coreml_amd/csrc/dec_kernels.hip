@@ -17,7 +17,9 @@
 //     128-byte row, fp32 online softmax per stream, one ordered merge -- the same arithmetic whatever the launch shape.
 //     With early stop on they walk the compact list of LIVE rows.
 //   * dec_xattn_fq_kernel: cross_attn_ln + query projection INSIDE the cross-attention launch for 96 .. 256 pairs alone on
-//     the device (7 launches per layer), bit-identical to the two launches.
+//     the device (7 launches per layer), bit-identical to the two launches.  The three attention kernels have their own
+//     prologue, loop driver and query load; a stream's block loads, block arithmetic and row-group reduction are written
+//     once (attn_load_block, attn_block, attn_stream_reduce), and so is the merge (attn_merge_core).
 //   * argmax_embed_kernel: closes a position (arg-max reduce, timestamp decision, early-stop flags + live list, next
 //     token, next embedding + statistics) and advances the decode position, which lives in HBM (*pos_ptr) -- so ONE
 //     captured hipGraph of the whole position (and one of WM_BURST positions) replays for every position.
@@ -649,6 +651,106 @@ __device__ __forceinline__ float attn_merge(const float *m, const float *l, cons
     return attn_merge_core<NS>(mm, ll, oo);
 }
 
+// ---- the per-stream arithmetic of the three attention kernels (dec_rows_attn_kernel, dec_xrows_attn_kernel,
+// dec_xattn_fq_kernel), written ONCE so that every launch shape gives the same bits.  Each kernel keeps its own prologue,
+// loop driver, query load and tail (the stores of the reduced stream and the merge).  Lane geometry: row i of a pair
+// belongs to stream (i / 8) % NS; lane 8 rg + e8 of the stream's wave holds 16 bytes (columns e8 * 8 .. e8 * 8 + 7) of the
+// block's rows with i % 8 == rg.
+// Machine code: a kernel calls attn_load_block / attn_block from its own load_block / process_block lambdas, and
+// attn_load_block reads `stream` and `rg` through references.  Both keep the compiler's schedule of the loops exactly as
+// it was when each kernel carried its own copy (instruction for instruction, checked on the disassembly); direct calls, or
+// the tail as a function, move instructions and registers in the streaming loop of dec_xrows_attn_kernel.
+
+// the U K/V loads of one block of a stream (rows r0 + u * NS * 8 + stream * 8 + rg); a row index i >= lim is replaced by
+// `clamp` so the loads are unconditional
+template <int NS, int U, bool NT>
+__device__ __forceinline__ void attn_load_block(const bf16_t *kb, const bf16_t *vb, int r0, const int &stream, const int &rg,
+                                                int lim, int clamp, u32x4 (&kv)[U], u32x4 (&vv)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        int i = r0 + u * (NS * 8) + stream * 8 + rg;
+        i = i < lim ? i : clamp;
+        if (NT) {
+            kv[u] = __builtin_nontemporal_load((const u32x4 *)(kb + (long)i * 64));
+            vv[u] = __builtin_nontemporal_load((const u32x4 *)(vb + (long)i * 64));
+        } else {
+            kv[u] = *(const u32x4 *)(kb + (long)i * 64);
+            vv[u] = *(const u32x4 *)(vb + (long)i * 64);
+        }
+    }
+}
+
+// every load of a block is IN FLIGHT before its first score is computed: the 2 U values pass through one empty asm, so
+// nothing of the block can be consumed before all of it was requested (round 5: a re-ordered argument list was enough
+// for the compiler to issue 6 of the 8 loads, start on the scores, and issue the last two afterwards -- 13.7 -> 16.5 us
+// at 8 sequences: the stream is bound by bytes in flight per CU).  Not used by dec_xrows_attn_kernel: its fenced loop
+// measured 1-3 % slower.
+template <int U>
+__device__ __forceinline__ void attn_block_fence(u32x4 (&kv)[U], u32x4 (&vv)[U]) {
+    static_assert(U == 4, "attn_block_fence is written for 4 loads per block");
+    asm volatile("" : "+v"(kv[0]), "+v"(kv[1]), "+v"(kv[2]), "+v"(kv[3]), "+v"(vv[0]), "+v"(vv[1]), "+v"(vv[2]), "+v"(vv[3]));
+}
+
+// one block of U x 8 rows of a stream: scores, block maximum, rescale, accumulate into the stream's running (m_run, l_run,
+// oa).  qe: the query columns of this lane, pre-scaled.  Rows i >= n_keys score -1e30 and weigh 0.  MASK_V (the
+// self-attention, whose loads are clamped to the cache's last row, not to the position): the V words of such a row are
+// zeroed too -- they may hold anything, and 0 x NaN must not reach the sum.
+template <int NS, int U, bool MASK_V>
+__device__ __forceinline__ void attn_block(const float (&qe)[8], int r0, int stream, int rg, int n_keys, const u32x4 (&kv)[U],
+                                           const u32x4 (&vv)[U], float &m_run, float &l_run, float (&oa)[8]) {
+    float sc[U];
+    float mb = -1e30f;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = r0 + u * (NS * 8) + stream * 8 + rg;
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            a = __fmaf_rn(qe[2 * j], __uint_as_float(kv[u][j] << 16), a);
+            a = __fmaf_rn(qe[2 * j + 1], __uint_as_float(kv[u][j] & 0xffff0000u), a);
+        }
+        a += __shfl_xor(a, 1);
+        a += __shfl_xor(a, 2);
+        a += __shfl_xor(a, 4);
+        sc[u] = i < n_keys ? a : -1e30f;
+        mb = fmaxf(mb, sc[u]);
+    }
+    mb = fmaxf(mb, __shfl_xor(mb, 8));
+    mb = fmaxf(mb, __shfl_xor(mb, 16));
+    mb = fmaxf(mb, __shfl_xor(mb, 32));
+    const float m_new = fmaxf(m_run, mb);
+    const float resc = __expf(m_run - m_new);  // 0 on the first block (m_run = -1e30), 1 when the max is unchanged
+    l_run *= resc;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) oa[j] *= resc;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const bool live_row = sc[u] > -1e29f;
+        const float pv = live_row ? __expf(sc[u] - m_new) : 0.f;
+        l_run += pv;  // the 8 lanes of a row hold the same pv: only the row groups are summed (attn_stream_reduce)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned vw = (MASK_V && !live_row) ? 0u : vv[u][j];
+            oa[2 * j] = __fmaf_rn(pv, __uint_as_float(vw << 16), oa[2 * j]);
+            oa[2 * j + 1] = __fmaf_rn(pv, __uint_as_float(vw & 0xffff0000u), oa[2 * j + 1]);
+        }
+    }
+    m_run = m_new;
+}
+
+// a stream's partials summed over its 8 row groups: every lane then holds the stream's l_run and its 8 output columns
+__device__ __forceinline__ void attn_stream_reduce(float &l_run, float (&oa)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        oa[i] += __shfl_xor(oa[i], 8);
+        oa[i] += __shfl_xor(oa[i], 16);
+        oa[i] += __shfl_xor(oa[i], 32);
+    }
+    l_run += __shfl_xor(l_run, 8);
+    l_run += __shfl_xor(l_run, 16);
+    l_run += __shfl_xor(l_run, 32);
+}
+
 // KERNEL ARGUMENTS / FIRST LOADS (round 5).  The round-4 kernel reached its first K/V load after six to seven DEPENDENT
 // memory round trips (three lazy kernarg bursts, *n_live_ptr, *pos_ptr, live_rows[..], the query), each a cache miss on
 // a fresh dispatch: 5.0 us for the ~1 MB self-attention of a batch of 8.  Now (a) the first 15 dwords of the argument
@@ -707,26 +809,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     // pairs stay balanced over the chip.  (null: every row is live -- the fixed-length benchmark decode.)
     const int n_clamp = SELF ? T_stride - 1 : n_keys_const - 1;  // known without a load: the first block's row clamp
     auto load_block = [&](const bf16_t *kb, const bf16_t *vb, int r0, int clamp, u32x4 (&kv)[U], u32x4 (&vv)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            int i = r0 + u * (NS * 8) + stream * 8 + rg;
-            i = i < clamp ? i : clamp;  // clamped: unconditional loads
-            if (NT) {
-                kv[u] = __builtin_nontemporal_load((const u32x4 *)(kb + (long)i * 64));
-                vv[u] = __builtin_nontemporal_load((const u32x4 *)(vb + (long)i * 64));
-            } else {
-                kv[u] = *(const u32x4 *)(kb + (long)i * 64);
-                vv[u] = *(const u32x4 *)(vb + (long)i * 64);
-            }
-        }
-    };
-    // every load of a block is IN FLIGHT before its first score is computed: the 2 U values pass through one empty asm, so
-    // nothing of the block can be consumed before all of it was requested (round 5: a re-ordered argument list was enough
-    // for the compiler to issue 6 of the 8 loads, start on the scores, and issue the last two afterwards -- 13.7 -> 16.5 us
-    // at 8 sequences: the stream is bound by bytes in flight per CU)
-    auto block_fence = [](u32x4 (&kv)[U], u32x4 (&vv)[U]) {
-        static_assert(U == 4, "block_fence is written for 4 loads per block");
-        asm volatile("" : "+v"(kv[0]), "+v"(kv[1]), "+v"(kv[2]), "+v"(kv[3]), "+v"(vv[0]), "+v"(vv[1]), "+v"(vv[2]), "+v"(vv[3]));
+        attn_load_block<NS, U, NT>(kb, vb, r0, stream, rg, clamp, clamp, kv, vv);
     };
     bool first = true;
     int n_bh = n_bh_full, n_keys = n_keys_const;
@@ -770,47 +853,8 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         }
         float m_run = -1e30f, l_run = 0.f;
         float oa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        // one block of U x 8 rows of this stream: scores, block maximum, rescale, accumulate -- the stream's arithmetic
         auto process_block = [&](int r0, const u32x4 (&kv)[U], const u32x4 (&vv)[U]) {
-            float sc[U];
-            float mb = -1e30f;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = r0 + u * (NS * 8) + stream * 8 + rg;
-                float a = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    a = __fmaf_rn(qe[2 * j], __uint_as_float(kv[u][j] << 16), a);
-                    a = __fmaf_rn(qe[2 * j + 1], __uint_as_float(kv[u][j] & 0xffff0000u), a);
-                }
-                a += __shfl_xor(a, 1);
-                a += __shfl_xor(a, 2);
-                a += __shfl_xor(a, 4);
-                sc[u] = i < n_keys ? a : -1e30f;
-                mb = fmaxf(mb, sc[u]);
-            }
-            mb = fmaxf(mb, __shfl_xor(mb, 8));
-            mb = fmaxf(mb, __shfl_xor(mb, 16));
-            mb = fmaxf(mb, __shfl_xor(mb, 32));
-            const float m_new = fmaxf(m_run, mb);
-            const float resc = __expf(m_run - m_new);  // 0 on the first block (m_run = -1e30), 1 when the max is unchanged
-            l_run *= resc;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) oa[j] *= resc;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const bool live_row = sc[u] > -1e29f;
-                const float pv = live_row ? __expf(sc[u] - m_new) : 0.f;
-                l_run += pv;  // the 8 lanes of a row hold the same pv: only the row groups are summed below
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    // SELF: a row past the position was read from wherever the clamp pointed -- never let its bits in
-                    const unsigned vw = (SELF && !live_row) ? 0u : vv[u][j];
-                    oa[2 * j] = __fmaf_rn(pv, __uint_as_float(vw << 16), oa[2 * j]);
-                    oa[2 * j + 1] = __fmaf_rn(pv, __uint_as_float(vw & 0xffff0000u), oa[2 * j + 1]);
-                }
-            }
-            m_run = m_new;
+            attn_block<NS, U, SELF>(qe, r0, stream, rg, n_keys, kv, vv, m_run, l_run, oa);
         };
         if (DEEP) {
             // LATENCY shape (a handful of pairs: tiny.en single chunk = 48 waves on the whole chip): a stream's rows are
@@ -821,25 +865,17 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
                 if (blk * (NS * 8 * U) < n_keys) process_block(blk * (NS * 8 * U), kall[blk], vall[blk]);  // workgroup-uniform
         } else {
             if (SPEC) {
-                block_fence(kall[0], vall[0]);
+                attn_block_fence<U>(kall[0], vall[0]);
                 process_block(0, kall[0], vall[0]);
             }
             for (int r0 = SPEC ? NS * 8 * U : 0; r0 < n_keys; r0 += NS * 8 * U) {  // workgroup-uniform trip count
                 u32x4 kv[U], vv[U];
                 load_block(kb, vb, r0, n_keys - 1, kv, vv);
-                block_fence(kv, vv);
+                attn_block_fence<U>(kv, vv);
                 process_block(r0, kv, vv);
             }
         }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            oa[i] += __shfl_xor(oa[i], 8);
-            oa[i] += __shfl_xor(oa[i], 16);
-            oa[i] += __shfl_xor(oa[i], 32);
-        }
-        l_run += __shfl_xor(l_run, 8);
-        l_run += __shfl_xor(l_run, 16);
-        l_run += __shfl_xor(l_run, 32);
+        attn_stream_reduce(l_run, oa);
         if (nsplit > 1) {  // workgroup-uniform: the stream partials go to HBM, dec_attn_combine_kernel merges them
             if (rg == 0) {
                 float *po = cold.part + ((long)bh * NS + stream) * 66;
@@ -866,12 +902,13 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     }
 }
 
-// The CROSS-attention family (NS = 8: streaming shape, flat deal, deep flat deal) keeps the round-4 body verbatim: its
-// block loop is the kernel that carries the roofline (66.8 us for 430 MB at 56 sequences), and every restructuring of it
-// tried in round 5 -- peeled first block, fenced loads, asm-issued loads with counted waits -- left it 1-3 % slower
-// (68.0 - 68.8 us) although the loads were in flight earlier: the compiler's schedule of THIS source (packed FMAs across
-// row groups, 196 instructions per block) is the one measured.  Only the argument list is the new one (hot scalars first,
-// packed, preloaded); the key count of a cross-attention is an argument, so nothing here waits for the position.
+// The CROSS-attention family (NS = 8: streaming shape, flat deal, deep flat deal) keeps the round-4 loop: one unfenced
+// block at a time, loads clamped to n_keys - 1.  Its block loop is the kernel that carries the roofline (66.8 us for 430 MB
+// at 56 sequences), and every restructuring of it tried in round 5 -- peeled first block, fenced loads, asm-issued loads
+// with counted waits -- left it 1-3 % slower (68.0 - 68.8 us) although the loads were in flight earlier: the compiler's
+// schedule of THIS loop (packed FMAs across row groups, 196 instructions per block) is the one measured, and the shared
+// block helpers above reproduce it instruction for instruction.  Only the argument list is the new one (hot scalars
+// first, packed, preloaded); the key count of a cross-attention is an argument, so nothing here waits for the position.
 template <int NS, int U, bool NT, bool DEEP = false>
 __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
@@ -932,57 +969,10 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
         float m_run = -1e30f, l_run = 0.f;
         float oa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         auto load_block = [&](int r0, u32x4 (&kv)[U], u32x4 (&vv)[U]) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                int i = r0 + u * (NS * 8) + stream * 8 + rg;
-                i = i < n_keys ? i : last;  // clamped: unconditional loads
-                if (NT) {
-                    kv[u] = __builtin_nontemporal_load((const u32x4 *)(kb + (long)i * 64));
-                    vv[u] = __builtin_nontemporal_load((const u32x4 *)(vb + (long)i * 64));
-                } else {
-                    kv[u] = *(const u32x4 *)(kb + (long)i * 64);
-                    vv[u] = *(const u32x4 *)(vb + (long)i * 64);
-                }
-            }
+            attn_load_block<NS, U, NT>(kb, vb, r0, stream, rg, n_keys, last, kv, vv);
         };
-        // one block of U x 8 rows of this stream: scores, block maximum, rescale, accumulate -- the stream's arithmetic
         auto process_block = [&](int r0, const u32x4 (&kv)[U], const u32x4 (&vv)[U]) {
-            float sc[U];
-            float mb = -1e30f;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = r0 + u * (NS * 8) + stream * 8 + rg;
-                float a = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    a = __fmaf_rn(qe[2 * j], __uint_as_float(kv[u][j] << 16), a);
-                    a = __fmaf_rn(qe[2 * j + 1], __uint_as_float(kv[u][j] & 0xffff0000u), a);
-                }
-                a += __shfl_xor(a, 1);
-                a += __shfl_xor(a, 2);
-                a += __shfl_xor(a, 4);
-                sc[u] = i < n_keys ? a : -1e30f;
-                mb = fmaxf(mb, sc[u]);
-            }
-            mb = fmaxf(mb, __shfl_xor(mb, 8));
-            mb = fmaxf(mb, __shfl_xor(mb, 16));
-            mb = fmaxf(mb, __shfl_xor(mb, 32));
-            const float m_new = fmaxf(m_run, mb);
-            const float resc = __expf(m_run - m_new);  // 0 on the first block (m_run = -1e30), 1 when the max is unchanged
-            l_run *= resc;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) oa[j] *= resc;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float pv = sc[u] > -1e29f ? __expf(sc[u] - m_new) : 0.f;
-                l_run += pv;  // the 8 lanes of a row hold the same pv: only the row groups are summed below
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    oa[2 * j] = __fmaf_rn(pv, __uint_as_float(vv[u][j] << 16), oa[2 * j]);
-                    oa[2 * j + 1] = __fmaf_rn(pv, __uint_as_float(vv[u][j] & 0xffff0000u), oa[2 * j + 1]);
-                }
-            }
-            m_run = m_new;
+            attn_block<NS, U, false>(qe, r0, stream, rg, n_keys, kv, vv, m_run, l_run, oa);
         };
         if (DEEP) {
             // LATENCY shape (a handful of pairs: tiny.en single chunk = 48 waves on the whole chip): a stream's rows are
@@ -1002,15 +992,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
                 process_block(r0, kv, vv);
             }
         }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            oa[i] += __shfl_xor(oa[i], 8);
-            oa[i] += __shfl_xor(oa[i], 16);
-            oa[i] += __shfl_xor(oa[i], 32);
-        }
-        l_run += __shfl_xor(l_run, 8);
-        l_run += __shfl_xor(l_run, 16);
-        l_run += __shfl_xor(l_run, 32);
+        attn_stream_reduce(l_run, oa);
         if (nsplit > 1) {  // workgroup-uniform: the stream partials go to HBM, dec_attn_combine_kernel merges them
             if (rg == 0) {
                 float *po = part + ((long)bh * NS + stream) * 66;
@@ -1046,7 +1028,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
 // 16 residual rows that holds b, K split over the waves exactly as dec_gemv_kernel splits it, partials summed through LDS
 // in part order, LayerNorm fold applied by the very functions the GEMV uses (gemv_unit_load / gemv_unit_stats): the 64
 // values are bit for bit what the GEMV would have left in HBM -- while the first block of its K/V rows is already on its
-// way, then walks its six blocks like the streaming kernel (stream_block / process_block arithmetic, same order: same
+// way, then walks its six blocks like the streaming kernel (attn_block / attn_stream_reduce, same order: same
 // bits).  One launch and one kernel boundary less per layer.  Workgroup -> pair: the head-major pair list is cut into 8
 // equal ranges, one per XCD (workgroup id % 8, observed placement), so every XCD streams the same number of caches and a
 // head's 164 KB weight slice crosses the fabric once or twice and is an L2 hit for the other sequences of the head; the
@@ -1126,18 +1108,7 @@ __global__ __launch_bounds__(512) void dec_xattn_fq_kernel(const bf16_t *__restr
     const bf16_t *kb = kc + (long)bh * T_stride * 64 + e8 * 8;
     const bf16_t *vb = vc + (long)bh * T_stride * 64 + e8 * 8;
     auto load_block = [&](int r0, u32x4 (&kv)[U], u32x4 (&vv)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            int i = r0 + u * (NS * 8) + stream * 8 + rg;
-            i = i < n_keys - 1 ? i : n_keys - 1;  // clamped: unconditional loads
-            if (NT) {
-                kv[u] = __builtin_nontemporal_load((const u32x4 *)(kb + (long)i * 64));
-                vv[u] = __builtin_nontemporal_load((const u32x4 *)(vb + (long)i * 64));
-            } else {
-                kv[u] = *(const u32x4 *)(kb + (long)i * 64);
-                vv[u] = *(const u32x4 *)(vb + (long)i * 64);
-            }
-        }
+        attn_load_block<NS, U, NT>(kb, vb, r0, stream, rg, n_keys - 1, n_keys - 1, kv, vv);
     };
     u32x4 kv0[U], vv0[U];
     load_block(0, kv0, vv0);
@@ -1170,63 +1141,20 @@ __global__ __launch_bounds__(512) void dec_xattn_fq_kernel(const bf16_t *__restr
     float qe[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) qe[i] = q_lds[e8 * 8 + i] * 0.125f;  // hd^-0.5 (== hd^-0.25 on q and on k)
-    // ---- the stream: the block arithmetic of dec_rows_attn_kernel, block by block
+    // ---- the stream, block by block: the shared block arithmetic (attn_block)
     float m_run = -1e30f, l_run = 0.f;
     float oa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto process_block = [&](int r0, const u32x4 (&kv)[U], const u32x4 (&vv)[U]) {
-        float sc[U];
-        float mb = -1e30f;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = r0 + u * (NS * 8) + stream * 8 + rg;
-            float a = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                a = __fmaf_rn(qe[2 * j], __uint_as_float(kv[u][j] << 16), a);
-                a = __fmaf_rn(qe[2 * j + 1], __uint_as_float(kv[u][j] & 0xffff0000u), a);
-            }
-            a += __shfl_xor(a, 1);
-            a += __shfl_xor(a, 2);
-            a += __shfl_xor(a, 4);
-            sc[u] = i < n_keys ? a : -1e30f;
-            mb = fmaxf(mb, sc[u]);
-        }
-        mb = fmaxf(mb, __shfl_xor(mb, 8));
-        mb = fmaxf(mb, __shfl_xor(mb, 16));
-        mb = fmaxf(mb, __shfl_xor(mb, 32));
-        const float m_new = fmaxf(m_run, mb);
-        const float resc = __expf(m_run - m_new);
-        l_run *= resc;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) oa[j] *= resc;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float pv = sc[u] > -1e29f ? __expf(sc[u] - m_new) : 0.f;
-            l_run += pv;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                oa[2 * j] = __fmaf_rn(pv, __uint_as_float(vv[u][j] << 16), oa[2 * j]);
-                oa[2 * j + 1] = __fmaf_rn(pv, __uint_as_float(vv[u][j] & 0xffff0000u), oa[2 * j + 1]);
-            }
-        }
-        m_run = m_new;
+        attn_block<NS, U, false>(qe, r0, stream, rg, n_keys, kv, vv, m_run, l_run, oa);
     };
     process_block(0, kv0, vv0);
     for (int r0 = NS * 8 * U; r0 < n_keys; r0 += NS * 8 * U) {  // workgroup-uniform trip count
         u32x4 kv[U], vv[U];
         load_block(r0, kv, vv);
-        asm volatile("" : "+v"(kv[0]), "+v"(kv[1]), "+v"(kv[2]), "+v"(kv[3]), "+v"(vv[0]), "+v"(vv[1]), "+v"(vv[2]), "+v"(vv[3]));
+        attn_block_fence<U>(kv, vv);
         process_block(r0, kv, vv);
     }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        oa[i] += __shfl_xor(oa[i], 8);
-        oa[i] += __shfl_xor(oa[i], 16);
-        oa[i] += __shfl_xor(oa[i], 32);
-    }
-    l_run += __shfl_xor(l_run, 8);
-    l_run += __shfl_xor(l_run, 16);
-    l_run += __shfl_xor(l_run, 32);
+    attn_stream_reduce(l_run, oa);
     float *wm_ = red, *wl_ = red + NS, *wo_ = red + 2 * NS;  // (the split-K partials are dead: both barriers passed)
     __syncthreads();
     if (rg == 0) {
@@ -1824,14 +1752,9 @@ int wm_dec_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t
         // walk the pairs, balanced (56 chunks x 20 heads = 224 workgroups x 5 pairs).  Measured alone at B = 8 / 56 / 128:
         // 12.8 / 67 / 144 us (4.8 / 6.4 / 6.8 TB/s: ~6.4 is what HBM reads deliver).
         // short_lived (the chip is shared with other decode groups): one workgroup per pair, see WmModel::xattn_shared
-        // EXPERIMENT, off in the product (xattn_pair_wg_max_pairs = 0): alone on the device and at most two pairs per CU (a
-        // group of 13 .. 25 sequences at 20 heads): one workgroup per pair, TWO per CU (no LDS reservation) instead of the
-        // persistent shape's 150 workgroups of two pairs each.  Measured: SLOWER (large-v3 x 15: 2.123 vs 2.042 ms per
-        // position; large-v2 x 16: 2.097 vs 2.022): sixteen streaming waves per CU do worse than eight
-        const bool two_per_cu = !short_lived && B * H > 256 && B * H <= g_wm_tuning.xattn_pair_wg_max_pairs;
         // (a sub-chip lane: one persistent workgroup per CU of ITS part of the chip)
         const int cap_cus = g_wm_tuning.xattn_wgs > 0 && g_wm_tuning.xattn_wgs < ctx->n_cus ? g_wm_tuning.xattn_wgs : ctx->n_cus;
-        const int cap = (short_lived || two_per_cu) ? (1 << 30) : cap_cus;
+        const int cap = short_lived ? (1 << 30) : cap_cus;
         int n_wg = B * H;
         if (n_wg > cap) {
             const int rounds = (n_wg + cap - 1) / cap;
@@ -1885,7 +1808,7 @@ int wm_dec_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t
             const AttnCold cold = {att, part, (const char *)pf_ptr, tile_bytes};
             const unsigned pA = (unsigned)H | ((unsigned)nsplit << 8), pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
             const unsigned pC = (unsigned)(B * H) | ((unsigned)n_wg << 16);
-            dec_xrows_attn_kernel<8, 4, WM_XATTN_NT><<<grid, (8 / nsplit) * 64, (nsplit == 1 && !two_per_cu) ? lds_pad : 0, ctx->stream>>>(
+            dec_xrows_attn_kernel<8, 4, WM_XATTN_NT><<<grid, (8 / nsplit) * 64, nsplit == 1 ? lds_pad : 0, ctx->stream>>>(
                 q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
         }
         WM_HIP(hipGetLastError());
