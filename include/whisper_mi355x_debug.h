@@ -65,13 +65,14 @@ WM_API int wmdbg_bench_graph_branches(wm_ctx *ctx, int iters, int grid, int us_e
  * (A ~ N(0,1), W ~ N(0,0.02^2)); launches rotate over n_w copies of W (n_w large: W streams from HBM as in the model). */
 WM_API int wmdbg_bench_gemm(wm_ctx *ctx, int M, int N, int K, int epi, int iters, int n_w, float *us);
 
-/* Force the encoder GEMM tile: 128 (128 x 128, 4 waves), 256 (256 x 256, 8 waves, staggered phases) or 0 = automatic.
- * Process-wide; used by the parity tests and A/B probes to run every shape through both kernels. */
+/* Force the encoder GEMM tile: 64 (64 x 64, 4 waves), 128 (128 x 128, 4 waves), 256 (256 x 256, 8 waves, staggered phases)
+ * or 0 = automatic.  Process-wide; used by the parity tests and A/B probes to run every shape through every tile kernel. */
+WM_API int wmdbg_set_gemm_tile(int tile);
+
 /* sub-chip lanes (round 6): CU-masked decode groups of a wm_transcribe_greedy call (0: none, 2: two half-chip groups) for a
  * call of B chunks on a model of decoder width n_text_state; the 256-bit CU mask of the CUs [cu_lo, cu_hi) of every XCD */
 WM_API int wmdbg_lane_parts(int B, int lanes, int explicit_lanes, int n_text_state);
 WM_API int wmdbg_cu_mask(int cu_lo, int cu_hi, uint32_t *mask8);
-WM_API int wmdbg_set_gemm_tile(int tile);
 
 /* The ALL-FP32 debug model path (BASELINE.md parity gate: "fp32 debug path must match to <= 1e-4 rel-L2"; csrc/f32_path.hip).
  * precision = WM_F32: wm_encode and wm_decode_logits of THIS context run with f32 activations, f32 K/V and f32 accumulation on

@@ -1,10 +1,13 @@
 // gemm.hip -- bf16 MFMA GEMM for gfx950:  C[M][N] (epilogue) = A[M][K] . W[N][K]^T
 //
-// Every encoder-side matrix product goes through this kernel (conv1/conv2 as implicit
+// Every encoder-side matrix product goes through these kernels (conv1/conv2 as implicit
 // GEMMs via row-address mapping, Q/K/V, attention out-proj, MLP fc1/fc2, cross-attention
-// K/V projection): SURVEY.md section 2 rows K4, K5, K7, K9.
+// K/V projection): SURVEY.md section 2 rows K4, K5, K7, K9.  Four tile kernels, chosen per
+// product by wm_gemm: gemm_bf16_kernel (128 x 128, double buffer), gemm64_bf16_kernel and
+// gemm128p_bf16_kernel (64 x 64 and 128 x 128 on an LDS-DMA ring) and gemm256_bf16_kernel
+// (256 x 256, staggered phases); they accumulate in the same order (bitwise equal: tests).
 //
-// Structure (CDNA4-first, not a warp-tiling port):
+// Structure (CDNA4-first, not a warp-tiling port), described for gemm_bf16_kernel:
 //   * 128 x 128 x 64 block tile, 256 threads = 4 wave64 as 2(M) x 2(N); each wave owns a
 //     64 x 64 output sub-tile = 4 x 4 fragments of v_mfma_f32_16x16x32_bf16 (f32 accumulate).
 //   * both operands are K-contiguous in HBM, so a tile row is one 128-byte line; tiles are
@@ -26,7 +29,7 @@
 
 #include "model.h"
 
-// No implicit FMA contraction in this file: the two tile shapes (and their different epilogue code paths) must round
+// No implicit FMA contraction in this file: the tile shapes (and their different epilogue code paths) must round
 // every output identically -- whether `gelu(v) + pos` or `c + (acc + bias)` became an FMA used to depend on the
 // surrounding code (tests: the 256 tile is bitwise equal to the 128 tile, kernel by kernel and on a whole model).
 // Every FMA that is wanted is written as fmaf().
@@ -335,6 +338,25 @@ __device__ __forceinline__ void tile_of_workgroup(const GemmDev &p, int &tm, int
     tn = in_grp / gsz;
 }
 
+// ---- operand staging sources, shared by every tile kernel --------------------------------------------------------
+// A thread stages 16 B of one tile row per pass: source row m (A) or n (W), logical chunk lch8 / 8 (the chunk is XOR-
+// swizzled by the caller so that the lane-linear LDS image is the swizzled one).  Rows past the end of the problem are
+// clamped to the last row: tail rows are masked in the epilogue.
+__device__ __forceinline__ unsigned a_rpb32(const GemmDev &p) {   // rows per batch for the 32-bit division (M < 2^30)
+    return p.a_rpb > 0x7fffffffL ? 0x7fffffffu : (unsigned)p.a_rpb;
+}
+__device__ __forceinline__ const bf16_t *a_row_src(const GemmDev &p, unsigned arpb, unsigned m, int lch8) {
+    if (m > (unsigned)(p.M - 1)) m = (unsigned)(p.M - 1);
+    // 32-bit row -> (batch, row) division: the 64-bit one is ~300 VALU instructions, and four of them per thread were 1.4 us
+    // of a 28-us K = 1280 tile of the 256 kernel (measured with in-kernel timestamps)
+    const unsigned aq = m / arpb, ar = m - aq * arpb;
+    return p.A + (long)aq * p.a_bstride + (long)ar * p.a_rstride + lch8;
+}
+__device__ __forceinline__ const bf16_t *w_row_src(const GemmDev &p, long n, int lch8) {
+    if (n > p.N - 1) n = p.N - 1;
+    return p.W + n * (long)p.K + lch8;
+}
+
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmDev p) {
     __shared__ __attribute__((aligned(16))) char lds[2][2][TILE_BYTES];  // [buf][A|B]
@@ -352,18 +374,13 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmDev p) {
     const int srow = tid >> 3, pch = tid & 7;
     const bf16_t *a_src[4];
     const bf16_t *w_src[4];
-    const unsigned arpb = p.a_rpb > 0x7fffffffL ? 0x7fffffffu : (unsigned)p.a_rpb;
+    const unsigned arpb = a_rpb32(p);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = i * 32 + srow;
-        const int lch = pch ^ (row & 7);
-        unsigned m = (unsigned)(m0 + row);
-        if (m > (unsigned)(p.M - 1)) m = (unsigned)(p.M - 1);  // clamp: tail rows are masked in the epilogue
-        const unsigned aq = m / arpb, ar = m - aq * arpb;  // 32-bit: see the 256 kernel
-        a_src[i] = p.A + (long)aq * p.a_bstride + (long)ar * p.a_rstride + lch * 8;
-        long n = n0 + row;
-        if (n > p.N - 1) n = p.N - 1;
-        w_src[i] = p.W + n * (long)p.K + lch * 8;
+        const int lch8 = (pch ^ (row & 7)) * 8;
+        a_src[i] = a_row_src(p, arpb, (unsigned)(m0 + row), lch8);
+        w_src[i] = w_row_src(p, n0 + row, lch8);
     }
     auto stage = [&](int buf, int kt) {
         const long ko = (long)kt * BK;
@@ -441,15 +458,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmDev p) {
 // 64 x 64 x 64 tile for products that cannot fill the chip with 128 x 128 tiles (round 6): ONE 30 s chunk (M = 1500) -- the
 // reference's own flow (Whisper.swift:23-31, one chunk of Whisper-small) -- has 72 tiles of 128 x 128 for its N = 768 products
 // (out-projection, fc2 with K = 3072, conv2) on 256 CUs; as 64 x 64 tiles they are 288 workgroups.  Same structure as the
-// 128 tile (4 waves as 2 x 2, LDS-DMA double buffer, XOR swizzle), each wave owns 32 x 32 = 2 x 2 fragments; 2 x 16 KiB of LDS,
-// so several workgroups share a CU.  Every output element is accumulated over K in the same order by the same MFMA and
+// 128 tile (4 waves as 2 x 2, LDS-DMA, XOR swizzle), each wave owns 32 x 32 = 2 x 2 fragments; a 4 x 16 KiB LDS ring (64 KiB),
+// so at most two workgroups share a CU.  Every output element is accumulated over K in the same order by the same MFMA and
 // finished by the same epilogue arithmetic: bitwise equal to the other tiles (test).
 constexpr int BM3 = 64, BN3 = 64;
 constexpr int TILE3_BYTES = BM3 * BK * 2;   // 8 KiB per operand tile
 constexpr int STAGE3_BYTES = 2 * TILE3_BYTES;  // A + W of one K-tile
 constexpr int NST3 = 4;                      // K-tiles in flight (ring of 4 x 16 KiB)
 
-#define WM_DSR3(dst, addr, off) \
+#define WM_DSR(dst, addr, off) \
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
 
 // A single-chunk product is LATENCY-bound per K-tile (4 MFMAs per wave against one HBM / L2 round trip), and with ~1
@@ -470,18 +487,13 @@ __global__ __launch_bounds__(256, 2) void gemm64_bf16_kernel(GemmDev p) {
     const int srow = tid >> 3, pch = tid & 7;
     const bf16_t *a_src[2];
     const bf16_t *w_src[2];
-    const unsigned arpb = p.a_rpb > 0x7fffffffL ? 0x7fffffffu : (unsigned)p.a_rpb;
+    const unsigned arpb = a_rpb32(p);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = i * 32 + srow;
-        const int lch = pch ^ (row & 7);
-        unsigned m = (unsigned)(m0 + row);
-        if (m > (unsigned)(p.M - 1)) m = (unsigned)(p.M - 1);  // clamp: tail rows are masked in the epilogue
-        const unsigned aq = m / arpb, ar = m - aq * arpb;
-        a_src[i] = p.A + (long)aq * p.a_bstride + (long)ar * p.a_rstride + lch * 8;
-        long n = n0 + row;
-        if (n > p.N - 1) n = p.N - 1;
-        w_src[i] = p.W + n * (long)p.K + lch * 8;
+        const int lch8 = (pch ^ (row & 7)) * 8;
+        a_src[i] = a_row_src(p, arpb, (unsigned)(m0 + row), lch8);
+        w_src[i] = w_row_src(p, n0 + row, lch8);
     }
     const int nk = p.K / BK;
     auto stage = [&](int slot, int kt) {   // 4 LDS-DMA instructions per wave
@@ -522,10 +534,10 @@ __global__ __launch_bounds__(256, 2) void gemm64_bf16_kernel(GemmDev p) {
         __builtin_amdgcn_s_barrier();                        // ... everybody's; and everybody is done reading K-tile kt - 1
         stage((SLOT + 3) % NST3, kt + 3);                    // into the slot K-tile kt - 1 lived in
         bf16x8 af[2][2], bfr[2][2];
-        WM_DSR3(af[0][0], aa[0][0], SO); WM_DSR3(af[1][0], aa[1][0], SO);
-        WM_DSR3(bfr[0][0], wa[0][0], SO + TILE3_BYTES); WM_DSR3(bfr[1][0], wa[1][0], SO + TILE3_BYTES);
-        WM_DSR3(af[0][1], aa[0][1], SO); WM_DSR3(af[1][1], aa[1][1], SO);
-        WM_DSR3(bfr[0][1], wa[0][1], SO + TILE3_BYTES); WM_DSR3(bfr[1][1], wa[1][1], SO + TILE3_BYTES);
+        WM_DSR(af[0][0], aa[0][0], SO); WM_DSR(af[1][0], aa[1][0], SO);
+        WM_DSR(bfr[0][0], wa[0][0], SO + TILE3_BYTES); WM_DSR(bfr[1][0], wa[1][0], SO + TILE3_BYTES);
+        WM_DSR(af[0][1], aa[0][1], SO); WM_DSR(af[1][1], aa[1][1], SO);
+        WM_DSR(bfr[0][1], wa[0][1], SO + TILE3_BYTES); WM_DSR(bfr[1][1], wa[1][1], SO + TILE3_BYTES);
         asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(af[0][0]), "+v"(af[1][0]), "+v"(bfr[0][0]), "+v"(bfr[1][0]), "+v"(af[0][1]), "+v"(af[1][1]),
                        "+v"(bfr[0][1]), "+v"(bfr[1][1])::"memory");
@@ -574,18 +586,13 @@ __global__ __launch_bounds__(256, 1) void gemm128p_bf16_kernel(GemmDev p) {
     const int srow = tid >> 3, pch = tid & 7;
     const bf16_t *a_src[4];
     const bf16_t *w_src[4];
-    const unsigned arpb = p.a_rpb > 0x7fffffffL ? 0x7fffffffu : (unsigned)p.a_rpb;
+    const unsigned arpb = a_rpb32(p);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = i * 32 + srow;
-        const int lch = pch ^ (row & 7);
-        unsigned m = (unsigned)(m0 + row);
-        if (m > (unsigned)(p.M - 1)) m = (unsigned)(p.M - 1);  // clamp: tail rows are masked in the epilogue
-        const unsigned aq = m / arpb, ar = m - aq * arpb;
-        a_src[i] = p.A + (long)aq * p.a_bstride + (long)ar * p.a_rstride + lch * 8;
-        long n = n0 + row;
-        if (n > p.N - 1) n = p.N - 1;
-        w_src[i] = p.W + n * (long)p.K + lch * 8;
+        const int lch8 = (pch ^ (row & 7)) * 8;
+        a_src[i] = a_row_src(p, arpb, (unsigned)(m0 + row), lch8);
+        w_src[i] = w_row_src(p, n0 + row, lch8);
     }
     const int nk = p.K / BK;
     auto stage = [&](int slot, int kt) {   // 8 LDS-DMA instructions per wave
@@ -632,9 +639,9 @@ __global__ __launch_bounds__(256, 1) void gemm128p_bf16_kernel(GemmDev p) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 af[4], bfr[4];
-            WM_DSR3(af[0], A_[0][ks], SO); WM_DSR3(af[1], A_[1][ks], SO); WM_DSR3(af[2], A_[2][ks], SO); WM_DSR3(af[3], A_[3][ks], SO);
-            WM_DSR3(bfr[0], W_[0][ks], SO + TILE_BYTES); WM_DSR3(bfr[1], W_[1][ks], SO + TILE_BYTES);
-            WM_DSR3(bfr[2], W_[2][ks], SO + TILE_BYTES); WM_DSR3(bfr[3], W_[3][ks], SO + TILE_BYTES);
+            WM_DSR(af[0], A_[0][ks], SO); WM_DSR(af[1], A_[1][ks], SO); WM_DSR(af[2], A_[2][ks], SO); WM_DSR(af[3], A_[3][ks], SO);
+            WM_DSR(bfr[0], W_[0][ks], SO + TILE_BYTES); WM_DSR(bfr[1], W_[1][ks], SO + TILE_BYTES);
+            WM_DSR(bfr[2], W_[2][ks], SO + TILE_BYTES); WM_DSR(bfr[3], W_[3][ks], SO + TILE_BYTES);
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(bfr[0]), "+v"(bfr[1]), "+v"(bfr[2]), "+v"(bfr[3])::"memory");
 #pragma unroll
@@ -693,8 +700,6 @@ constexpr int BM2 = 256, BN2 = 256;
 constexpr int UNIT_BYTES = 128 * BK * 2;   // 16 KiB
 constexpr int BUF_BYTES = 4 * UNIT_BYTES;  // 64 KiB per K-tile
 
-#define WM_DSR(dst, addr, off) \
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
 #define WM_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
 template <int EPI>
@@ -716,20 +721,14 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
     const int lch8 = (pch ^ (srow & 7)) * 8;
     const bf16_t *a_src[2][2];  // [sub][pass]
     const bf16_t *w_src[2][2];
-    const unsigned arpb = p.a_rpb > 0x7fffffffL ? 0x7fffffffu : (unsigned)p.a_rpb;
+    const unsigned arpb = a_rpb32(p);
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            unsigned m = (unsigned)(m0 + i * 128 + sub * 64 + srow);  // pass i = wave row i
-            if (m > (unsigned)(p.M - 1)) m = (unsigned)(p.M - 1);     // clamp: tail rows are masked in the epilogue
-            // 32-bit row -> (batch, row) division: the 64-bit one is ~300 VALU instructions, and four of them per thread
-            // were 1.4 us of a 28-us K = 1280 tile (measured with in-kernel timestamps)
-            const unsigned aq = m / arpb, ar = m - aq * arpb;
-            a_src[sub][i] = p.A + (long)aq * p.a_bstride + (long)ar * p.a_rstride + lch8;
-            long n = n0 + (2 * i + (srow >> 5)) * 64 + sub * 32 + (srow & 31);  // unit-row -> (wave col, row)
-            if (n > p.N - 1) n = p.N - 1;
-            w_src[sub][i] = p.W + n * (long)p.K + lch8;
+            a_src[sub][i] = a_row_src(p, arpb, (unsigned)(m0 + i * 128 + sub * 64 + srow), lch8);  // pass i = wave row i
+            w_src[sub][i] = w_row_src(p, n0 + (2 * i + (srow >> 5)) * 64 + sub * 32 + (srow & 31),  // unit-row -> (wave col, row)
+                                      lch8);
         }
     auto issue = [&](const bf16_t *s0, const bf16_t *s1, int lds_off, long ko) {
         char *d0 = lds + lds_off + wave * 1024;  // wave-uniform base; the hardware adds lane * 16
@@ -869,7 +868,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
 
 }  // namespace
 
-// A/B and parity probes force one of the two tile shapes (the wmdbg_set_gemm_tile hook lives in debug_hooks.cpp)
+// A/B and parity probes force one tile shape: 64, 128 or 256 (the wmdbg_set_gemm_tile hook lives in debug_hooks.cpp)
 int wm_gemm_set_tile_override(int tile) {
     if (tile != 0 && tile != 64 && tile != 128 && tile != 256) return WM_ERR_INVALID;
     g_wm_tuning.gemm_tile = tile;
