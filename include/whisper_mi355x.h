@@ -170,6 +170,37 @@ WM_API int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype
                          const int32_t *prompt, int n_prompt, int max_new, int32_t eot,
                          int32_t *tokens_out, int32_t *lens_out, wm_mem mem);
 
+/* Options of wm_transcribe (openai-whisper's DecodingOptions subset that temperature fallback needs). */
+typedef struct wm_decode_opts {
+    float temperature;         /* 0: arg-max (tokens bit-identical to wm_transcribe_greedy); > 0: sample from
+                                  softmax(filtered logits / temperature) */
+    uint64_t seed;             /* sampling stream; ignored at temperature 0 */
+    int32_t no_speech_token;   /* id of <|nospeech|> (50362 multilingual, 50363 large-v3); -1: not computed */
+    int32_t sot_index;         /* index in prompt[] of <|startoftranscript|> (0 unless a previous-text prompt precedes it) */
+} wm_decode_opts;
+
+/* wm_transcribe_greedy with decoding options and two optional outputs; the same arguments, policies, grouping, filters
+ * (wm_set_suppress, wm_set_timestamp_rules) and token budgets.  opts == NULL is temperature 0, no no-speech token.
+ *   token_logprobs_out : f32 [B][max_new] (host, nullable): log-probability of every generated token under the FILTERED
+ *                        distribution at temperature 1 -- logit[tok] - logsumexp(allowed logits), "allowed" being what the
+ *                        suppress lists (the first-token list at the first generated token), the timestamp rules and, when
+ *                        the rules force a timestamp, the admissible timestamps only leave (openai-whisper applies its
+ *                        filters before log_softmax and does not divide by T there).  The token that stops a chunk (eot or
+ *                        the last one its budget allows) has its value; 0 after it.  -INFINITY when nothing is admissible;
+ *   no_speech_prob_out : f32 [B] (host, nullable; needs opts->no_speech_token >= 0): softmax probability of <|nospeech|>
+ *                        in the RAW logits at the position of prompt[opts->sot_index] (openai-whisper DecodingTask).
+ * Sampling (temperature T > 0) is Gumbel-max inside the fused logits kernel: token = arg-max over the allowed ids of
+ * logit(n) * (float)(1 / T) + g(n), g = -log(-log u), u from Philox-4x32-10 with key {seed low, seed high word} and counter
+ * {n >> 2, generated index, chunk index within THIS call, 0}, word n & 3 -> u = ((x >> 9) * 2 + 1) * 2^-24.  The
+ * timestamp sum rule compares the unperturbed logits.  Results do not depend on the lanes, the grouping or the other
+ * chunks of the call.  Invalid: temperature < 0, not finite or so small that
+ * (float)(1 / temperature) overflows, sot_index outside [0, n_prompt), no_speech_token outside
+ * the vocabulary, no_speech_prob_out without a token. */
+WM_API int wm_transcribe(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
+                  const int32_t *prompt, int n_prompt, int max_new, int32_t eot, const wm_decode_opts *opts,
+                  int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
+                  wm_mem mem);
+
 /* Decode groups a wm_transcribe_greedy call on this context keeps in flight.
  *   0 (default): the library's own measured policy -- one group below 32 chunks, two groups (two weight-sharing lanes)
  *                up to 143, three from 144 chunks, never more than $WM_LANES (default 3) at once; for the NARROW models

@@ -89,6 +89,10 @@ WM_API int wmdbg_set_tuning(const char *key, int value);
  * available; explicit_lanes != 0: the host set the lane count with wm_set_lanes (host only, no GPU). */
 WM_API int wmdbg_group_count(int B, int lanes, int explicit_lanes);
 
+/* The Gumbel noise wm_transcribe's sampling adds at temperature > 0, computed by the DEVICE code (csrc/philox.h): g(n) of
+ * ids n0 .. n0 + count - 1 for chunk `chunk` of a call and generated index gi, into host g[count]. */
+WM_API int wmdbg_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int n0, int count, float *g);
+
 #ifdef __cplusplus
 }
 #endif

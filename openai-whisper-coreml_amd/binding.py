@@ -14,7 +14,9 @@ Everything goes through libwhisper_mi355x.so (include/whisper_mi355x.h).  There 
 CPU fallback: if the library is missing, or no gfx950 device is usable, calls raise.
 """
 import ctypes
+import math
 import os
+import zlib
 
 import numpy as np
 
@@ -109,6 +111,7 @@ def load_library(path=None):
         "wm_decode_logits": [vp, vp, ip, ip, vp, vp, ip],
         "wm_detect_language": [vp, vp, ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ip],
         "wm_transcribe_greedy": [vp, vp, ip, ip, vp, ip, ip, ctypes.c_int32, vp, vp, ip],
+        "wm_transcribe": [vp, vp, ip, ip, vp, ip, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
         "wm_set_token_budgets": [vp, vp, ip],
         "wm_set_lanes": [vp, ip],
         "wm_dev_malloc": [vp, sz, pp],
@@ -179,6 +182,121 @@ def generateSpectrogram(audio):
     result = np.zeros(80 * N_FRAMES, dtype=np.float64)
     lib.generate_spectrogram(_ptr(buf), _ptr(result))
     return result
+
+
+class wm_decode_opts(ctypes.Structure):
+    _fields_ = [("temperature", ctypes.c_float), ("seed", ctypes.c_uint64), ("no_speech_token", ctypes.c_int32),
+                ("sot_index", ctypes.c_int32)]
+
+
+class TranscribeResult:
+    """What Context.transcribe returns.  tokens i32 [B][max_new] (padded with eot), lens i32 [B], logprobs f32 [B][max_new]
+    (0 past lens), sum_logprob / avg_logprob f64 [B], no_speech_prob f32 [B] (None without a no-speech token).
+    sum_logprob adds the log-probs of all lens[b] tokens (the stopping eot included) and avg_logprob = sum / (n_text + 1),
+    n_text = tokens before eot -- openai-whisper's DecodingTask.run (its finalize pads with eot)."""
+
+    def __init__(self, tokens, lens, logprobs, no_speech_prob, eot):
+        self.tokens, self.lens, self.logprobs, self.no_speech_prob = tokens, lens, logprobs, no_speech_prob
+        B = tokens.shape[0]
+        self.sum_logprob = np.array([float(np.sum(logprobs[b, :lens[b]], dtype=np.float64)) for b in range(B)])
+        self.n_text = np.array([n_text_tokens(tokens[b, :lens[b]], eot) for b in range(B)], dtype=np.int64)
+        self.avg_logprob = self.sum_logprob / (self.n_text + 1)
+
+
+def n_text_tokens(toks, eot):
+    """generated tokens before the first eot"""
+    toks = np.asarray(toks)
+    hit = np.flatnonzero(toks == eot) if eot >= 0 else np.array([], dtype=np.int64)
+    return int(hit[0]) if hit.size else int(toks.size)
+
+
+def compression_ratio_text(text):
+    """openai-whisper's rule (whisper/utils.py compression_ratio): UTF-8 bytes over their zlib-compressed size."""
+    b = text.encode("utf-8")
+    return len(b) / len(zlib.compress(b))
+
+
+def compression_ratio_tokens(tokens, vocab_size):
+    """transformers' rule for token ids without a tokenizer (generation_whisper.py _retrieve_compression_ratio): every id as
+    int(log2(vocab_size) / 8) + 1 little-endian bytes, over their zlib-compressed size."""
+    length = int(math.log2(vocab_size) / 8) + 1
+    b = b"".join(int(t).to_bytes(length, "little") for t in np.asarray(tokens).tolist())
+    return len(b) / len(zlib.compress(b))
+
+
+FALLBACK_TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)
+
+
+def fallback_seed(seed, k):
+    """Sampling seed of temperature step k of transcribe_with_fallback."""
+    return (int(seed) + int(k)) & 0xFFFFFFFFFFFFFFFF
+
+
+def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
+                             compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
+                             vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None):
+    """openai-whisper's decode_with_fallback, per chunk, over ctx.transcribe.
+
+    Temperature step k decodes, as ONE batched call, the chunks that still need fallback (step 0: all of them) at
+    temperatures[k] with seed fallback_seed(seed, k).  A chunk needs fallback when its compression ratio exceeds
+    compression_ratio_threshold or its avg_logprob is below logprob_threshold; it does NOT need it when its
+    no_speech_prob exceeds no_speech_threshold (checked last; needs no_speech_token >= 0).  A threshold of None is not
+    checked.  A chunk keeps the result of the last call that decoded it.  Compression ratio: with a Vocab,
+    openai-whisper's rule on the detokenized text; without one, transformers' token-byte rule.  The default
+    compression_ratio_threshold "auto" is each rule's documented threshold: 2.4 with a Vocab, 1.35 without.
+
+    Returns a dict of per-chunk arrays (tokens, lens, logprobs, sum_logprob, avg_logprob, no_speech_prob,
+    compression_ratio, temperature, seed, needs_fallback) and `steps`: [(temperature, seed, chunk indices)] per call."""
+    pcm = np.asarray(pcm)
+    B = pcm.shape[0]
+    if isinstance(compression_ratio_threshold, str):
+        if compression_ratio_threshold != "auto":
+            raise ValueError("compression_ratio_threshold: a number, None (not checked) or 'auto'")
+        compression_ratio_threshold = 2.4 if vocab is not None else 1.35
+    if vocab_size is None:
+        vocab_size = int(ctx.dims["n_vocab"])
+    out = dict(tokens=np.full((B, max_new), eot, dtype=np.int32), lens=np.zeros(B, dtype=np.int32),
+               logprobs=np.zeros((B, max_new), dtype=np.float32), sum_logprob=np.zeros(B), avg_logprob=np.zeros(B),
+               no_speech_prob=np.full(B, np.nan, dtype=np.float32), compression_ratio=np.zeros(B),
+               temperature=np.zeros(B), seed=np.zeros(B, dtype=np.uint64), needs_fallback=np.zeros(B, dtype=bool))
+    steps = []
+    todo = np.arange(B)
+    for k, t in enumerate(temperatures):
+        if todo.size == 0:
+            break
+        sd = fallback_seed(seed, k)
+        r = ctx.transcribe(pcm[todo], prompt, max_new, eot=eot, temperature=float(t), seed=sd,
+                           no_speech_token=no_speech_token, sot_index=sot_index)
+        steps.append((float(t), sd, todo.copy()))
+        need = np.zeros(todo.size, dtype=bool)
+        for i, b in enumerate(todo):
+            n_text = int(r.n_text[i])
+            text_toks = r.tokens[i, :n_text]
+            cr = (compression_ratio_text(vocab.decode(text_toks)) if vocab is not None
+                  else compression_ratio_tokens(text_toks, vocab_size))
+            nf = False
+            if compression_ratio_threshold is not None and cr > compression_ratio_threshold:
+                nf = True
+            if logprob_threshold is not None and r.avg_logprob[i] < logprob_threshold:
+                nf = True
+            if (no_speech_threshold is not None and r.no_speech_prob is not None
+                    and r.no_speech_prob[i] > no_speech_threshold):
+                nf = False
+            need[i] = nf
+            out["tokens"][b] = r.tokens[i]
+            out["lens"][b] = r.lens[i]
+            out["logprobs"][b] = r.logprobs[i]
+            out["sum_logprob"][b] = r.sum_logprob[i]
+            out["avg_logprob"][b] = r.avg_logprob[i]
+            if r.no_speech_prob is not None:
+                out["no_speech_prob"][b] = r.no_speech_prob[i]
+            out["compression_ratio"][b] = cr
+            out["temperature"][b] = t
+            out["seed"][b] = sd
+            out["needs_fallback"][b] = nf
+        todo = todo[need]
+    out["steps"] = steps
+    return out
 
 
 class Context:
@@ -408,6 +526,52 @@ class Context:
                                                        len(prompt), max_new, eot, _ptr(toks),
                                                        _ptr(lens), mem))
         return toks, lens
+
+    def transcribe_raw(self, pcm, prompt, max_new, eot=-1, opts=None, logprobs=True, no_speech=False, budgets=None):
+        """wm_transcribe on host arrays: opts a wm_decode_opts or None (NULL); logprobs / no_speech request the two
+        optional outputs.  Returns (tokens, lens, logprobs or None, no_speech_prob or None)."""
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        pcm = np.ascontiguousarray(pcm)
+        B = pcm.shape[0]
+        toks = np.empty((B, max_new), dtype=np.int32)
+        lens = np.empty(B, dtype=np.int32)
+        lp = np.empty((B, max_new), dtype=np.float32) if logprobs else None
+        ns = np.empty(B, dtype=np.float32) if no_speech else None
+        _check(self.lib, self.lib.wm_transcribe(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], B, _ptr(prompt), len(prompt),
+                                                max_new, eot, ctypes.byref(opts) if opts is not None else None,
+                                                _ptr(toks), _ptr(lens), _ptr(lp) if lp is not None else None,
+                                                _ptr(ns) if ns is not None else None, WM_MEM_HOST))
+        return toks, lens, lp, ns
+
+    def transcribe(self, pcm, prompt, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1, sot_index=0,
+                   budgets=None):
+        """wm_transcribe: greedy (temperature 0) or sampled decode with per-token log-probs and, with no_speech_token >= 0,
+        openai-whisper's no_speech_prob.  Returns a TranscribeResult."""
+        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
+        toks, lens, lp, ns = self.transcribe_raw(pcm, prompt, max_new, eot, opts, logprobs=True,
+                                                 no_speech=no_speech_token >= 0, budgets=budgets)
+        return TranscribeResult(toks, lens, lp, ns, eot)
+
+    def transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
+                                 compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
+                                 vocab=None, seed=0, no_speech_token=-1, sot_index=0):
+        """openai-whisper's temperature fallback (module function transcribe_with_fallback) on this context."""
+        return transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures, compression_ratio_threshold,
+                                        logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index)
+
+    def sample_noise(self, seed, chunk, gi, n0, count):
+        """Debug library only: the Gumbel noise g(n0 .. n0 + count - 1) wm_transcribe's sampling adds, from the device."""
+        if not hasattr(self.lib, "wmdbg_sample_noise"):
+            raise WhisperError(-1, "sample_noise needs the debug library: Context(dims, debug=True)")
+        fn = self.lib.wmdbg_sample_noise
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        g = np.empty(count, dtype=np.float32)
+        _check(self.lib, fn(self.handle, int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk), int(gi), int(n0), int(count), _ptr(g)))
+        return g
 
 
 class Vocab:

@@ -136,6 +136,23 @@ extern "C" int wmdbg_layernorm(wm_ctx *ctx, const float *x, const float *g, cons
     return rc;
 }
 
+// The sampling noise of wm_transcribe as the device computes it (the DE_LOGITS_X epilogue's philox.h functions).
+extern "C" int wmdbg_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int n0, int count, float *g) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(g && count >= 0, WM_ERR_INVALID, "bad args");
+    if (count == 0) return WM_OK;
+    void *dg;
+    hipStream_t s = ctx->stream;
+    WM_TRY(up(&dg, nullptr, (size_t)count * 4, s));
+    int rc = wm_sample_noise(ctx, seed, chunk, gi, n0, count, (float *)dg);
+    if (rc == WM_OK) {
+        WM_HIP(hipMemcpyAsync(g, dg, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    }
+    (void)hipFree(dg);
+    return rc;
+}
+
 // Encoder attention on host q, k, v given as f32 [B][S][H*64] each (rounded to bf16 inside).
 extern "C" int wmdbg_enc_attention(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int S,
                                    float *out) {

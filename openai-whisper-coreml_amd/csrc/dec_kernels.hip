@@ -29,6 +29,7 @@
 #include <string.h>
 
 #include "model.h"
+#include "philox.h"
 
 namespace {
 
@@ -89,6 +90,7 @@ struct DecGemvDev {
     const unsigned *mask;  // DE_LOGITS: suppressed-token bitmaps [2][mask_words] or null
     int mask_words, mask_first_pos;
     WmTsDev ts;            // DE_LOGITS: timestamp rules (ts.rng == null: off)
+    WmXDev x;              // DE_LOGITS_X: extended decode (read in the epilogue only)
     const char *pf_ptr;    // next GEMV's weights: extra workgroups pull them into this XCD's L2
     long pf_tile_bytes;    // bytes of one 16-row weight tile of that matrix
     int pf_tiles;
@@ -190,7 +192,7 @@ __device__ __forceinline__ void gemv_unit_load(const DecGemvDev &p, GemvUnitOps<
         }
     }
     if (LN && p.mean_in && want_stats) o.offrow = p.mean_in[b0 + (nrow < nb ? nrow : nb - 1)];
-    if (EPI == DE_LOGITS && p.ts.rng) {
+    if ((EPI == DE_LOGITS || EPI == DE_LOGITS_X) && p.ts.rng) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (r < r0 || r >= r1) continue;
@@ -237,6 +239,17 @@ __device__ __forceinline__ void gemv_unit_stats(const DecGemvDev &p, const GemvU
     }
 }
 
+// word k of quad lane R's Philox output, for the lane whose index in the quad is k (= its id n & 3): four DPP broadcasts
+template <int R>
+__device__ __forceinline__ void quad_words(const wm_philox4 &w, int k, unsigned &out) {
+    const unsigned w0 = (unsigned)__builtin_amdgcn_mov_dpp((int)w.v[0], R * 0x55, 0xf, 0xf, false);
+    const unsigned w1 = (unsigned)__builtin_amdgcn_mov_dpp((int)w.v[1], R * 0x55, 0xf, 0xf, false);
+    const unsigned w2 = (unsigned)__builtin_amdgcn_mov_dpp((int)w.v[2], R * 0x55, 0xf, 0xf, false);
+    const unsigned w3 = (unsigned)__builtin_amdgcn_mov_dpp((int)w.v[3], R * 0x55, 0xf, 0xf, false);
+    const unsigned lo = (k & 1) ? w1 : w0, hi = (k & 1) ? w3 : w2;
+    out = (k & 2) ? hi : lo;
+}
+
 // epilogue of one (tile, block) unit by one wave: D col n = lane & 15, rows b = b0 + kq*4 + r
 template <int EPI, bool LN>
 __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const GemvUnitOps<EPI, LN> &o, const f32x4 acc,
@@ -246,6 +259,23 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
     const int n0 = tile * 16, n = n0 + nrow;
     const bool nvalid = n < p.N;
     const int nb = p.B - b0 < 16 ? p.B - b0 : 16;
+    unsigned draw[4] = {0u, 0u, 0u, 0u};   // DE_LOGITS_X under sampling: the 32-bit draw of (row kq * 4 + r, id n)
+    if (EPI == DE_LOGITS_X) {
+        const WmXPar xp = *p.x.par;
+        const int gi = pos + 1 - xp.n_prompt;
+        if (xp.sample && gi >= 0) {   // wave-uniform (every lane active)
+            // ONE Philox call serves the four ids of a quad (lanes 4q .. 4q + 3 = ids 4 (n >> 2) .. + 3) for one row: lane j
+            // of the quad runs the call of row kq * 4 + j, and DPP broadcasts hand every lane its word (n & 3) of each row's call
+            const int j = nrow & 3;
+            wm_philox4 c;
+            c.v[0] = (unsigned)n >> 2; c.v[1] = (unsigned)gi; c.v[2] = (unsigned)(xp.chunk0 + b0 + kq * 4 + j); c.v[3] = 0u;
+            const wm_philox4 w = wm_philox4x32_10(c, xp.key0, xp.key1);
+            quad_words<0>(w, j, draw[0]);
+            quad_words<1>(w, j, draw[1]);
+            quad_words<2>(w, j, draw[2]);
+            quad_words<3>(w, j, draw[3]);
+        }
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         if (r < r0 || r >= r1) continue;  // wave-uniform: this wave's share of the unit's rows
@@ -258,6 +288,67 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             v = __fmaf_rn(ms.x, acc[r], __fmaf_rn(ms.y, o.c1v, o.c2v));  // rstd (acc - mean c1) + c2
         } else {
             v = acc[r] + o.c2v;
+        }
+        if (EPI == DE_LOGITS_X) {
+            // extended decode: the DE_LOGITS keys (timestamp rules or the plain [arg_first, arg_last] range), over
+            // Gumbel-perturbed scores when sampling, with the winners' RAW logits beside them (their log-probs; score - g
+            // would lose bits), plus the (max, sum exp) partial of the allowed text ids and, at the <|startoftranscript|>
+            // position only, the unfiltered one over the whole vocabulary (no_speech_prob).  Wave-uniform branches.
+            const WmXPar xp = *p.x.par;
+            const unsigned mw = (pos == p.mask_first_pos) ? mword1 : mword0;
+            const bool ok = bvalid && nvalid && !((mw >> (n & 31)) & 1u);
+            const bool ts_on = p.ts.rng != nullptr;
+            const bool in_text = ts_on ? (ok && n >= o.trng[r].x && n < o.trng[r].y) : (ok && n >= p.arg_first && n <= p.arg_last);
+            const bool in_ts = ts_on && ok && n >= o.trng[r].z && n < o.trng[r].w;
+            const int gi = pos + 1 - xp.n_prompt;
+            float sc = v;
+            if (xp.sample && gi >= 0) sc = __fmaf_rn(v, xp.inv_T, wm_gumbel_from_bits(draw[r]));
+            unsigned long long kt = in_text ? argmax_key(sc, n) : 0ull, ks = in_ts ? argmax_key(sc, n) : 0ull;
+            float vt = v, vs = v;
+#pragma unroll
+            for (int q = 1; q < 16; q <<= 1) {
+                const unsigned long long a = __shfl_xor(kt, q), c = __shfl_xor(ks, q);
+                const float av = __shfl_xor(vt, q), cv = __shfl_xor(vs, q);
+                if (a > kt) { kt = a; vt = av; }
+                if (c > ks) { ks = c; vs = cv; }
+            }
+            float mx = in_text ? v : -1e30f;
+#pragma unroll
+            for (int q = 1; q < 16; q <<= 1) mx = fmaxf(mx, __shfl_xor(mx, q));
+            float se = in_text ? __expf(v - mx) : 0.f;
+#pragma unroll
+            for (int q = 1; q < 16; q <<= 1) se += __shfl_xor(se, q);
+            const long ti = (long)b * p.n_tiles + tile;
+            if (bvalid && nrow == 0) {
+                p.tilemax[ti] = kt;
+                *(float2 *)(p.x.txt + ti * 2) = make_float2(mx, se);
+                *(float2 *)(p.x.win + ti * 2) = make_float2(vt, vs);
+            }
+            if (ts_on && n0 + 16 > p.ts.ts_begin) {  // wave-uniform: the DE_LOGITS timestamp partial (raw logits)
+                float mt = in_ts ? v : -1e30f;
+#pragma unroll
+                for (int q = 1; q < 16; q <<= 1) mt = fmaxf(mt, __shfl_xor(mt, q));
+                float st2 = in_ts ? __expf(v - mt) : 0.f;
+#pragma unroll
+                for (int q = 1; q < 16; q <<= 1) st2 += __shfl_xor(st2, q);
+                if (bvalid && nrow == 0) {
+                    p.ts.key_ts[ti] = ks;
+                    *(float2 *)(p.ts.lse + ti * 2) = make_float2(mt, st2);
+                }
+            }
+            if (pos == xp.sot_pos) {  // wave-uniform: openai-whisper reads no_speech_prob before any filter
+                const bool any = bvalid && nvalid;
+                float ma = any ? v : -1e30f;
+#pragma unroll
+                for (int q = 1; q < 16; q <<= 1) ma = fmaxf(ma, __shfl_xor(ma, q));
+                float sa = any ? __expf(v - ma) : 0.f;
+#pragma unroll
+                for (int q = 1; q < 16; q <<= 1) sa += __shfl_xor(sa, q);
+                if (bvalid && nrow == 0) *(float2 *)(p.x.all + ti * 2) = make_float2(ma, sa);
+                if (bvalid && n == xp.ns_tok) p.x.ns_v[b] = v;
+            }
+            if (bvalid && nvalid && p.out_f32) p.out_f32[(long)b * p.ldo + n] = v;
+            continue;
         }
         if (EPI == DE_LOGITS && p.ts.rng) {
             // timestamp rules: best allowed text token, best allowed timestamp, and the (max, sum exp) partial of the
@@ -438,7 +529,7 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
     if (EPI == DE_RESID) { GEMV_PIN(p.out_bf16); GEMV_PIN(p.stats_out); GEMV_PIN(p.stats_stride); GEMV_PIN(p.mean_in); }
     if (EPI == DE_QKV) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); }
     if (EPI == DE_GELU) GEMV_PIN(p.out_bf16);
-    if (EPI == DE_LOGITS) {
+    if (EPI == DE_LOGITS || EPI == DE_LOGITS_X) {
         GEMV_PIN(p.tilemax); GEMV_PIN(p.arg_first); GEMV_PIN(p.arg_last); GEMV_PIN(p.mask); GEMV_PIN(p.mask_words);
         GEMV_PIN(p.mask_first_pos); GEMV_PIN(p.ts.rng); GEMV_PIN(p.ts.key_ts); GEMV_PIN(p.ts.lse); GEMV_PIN(p.ts.ts_begin);
     }
@@ -471,7 +562,7 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
         gemv_unit_load<EPI, LN>(p, ops, utile, ub0, lane, my_r0, my_r1, my_stats);
     }
     if (p.pos_ptr) pos = *p.pos_ptr;
-    if (EPI == DE_LOGITS && p.mask && has_unit) {
+    if ((EPI == DE_LOGITS || EPI == DE_LOGITS_X) && p.mask && has_unit) {
         const int n = utile * 16 + nrow;
         const int nc = n < p.N ? n : p.N - 1;
         mword0 = p.mask[nc >> 5];
@@ -521,7 +612,7 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
         if (tk != wave) {  // more units than waves (small models; RS == 1): operands fetched late
             gemv_unit_load<EPI, LN>(p, ops, tile, b0, lane);
             gemv_unit_stats<EPI, LN>(p, ops, st, lane, tile, b0);
-            if (EPI == DE_LOGITS && p.mask) {
+            if ((EPI == DE_LOGITS || EPI == DE_LOGITS_X) && p.mask) {
                 const int n = tile * 16 + nrow;
                 const int nc = n < p.N ? n : p.N - 1;
                 mword0 = p.mask[nc >> 5];
@@ -1201,16 +1292,38 @@ __global__ __launch_bounds__(64) void dec_attn_combine_kernel(const float *__res
 // tokens of position pos+1 (token + positional embedding, plus the LayerNorm partial statistics
 // the next layer-0 GEMV expects) and advances the device-side position -- so a step has no
 // separate embedding launch and *pos_ptr has exactly one writer.
-__global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long long *__restrict__ tilemax,
-                                                             int n_tiles, int B, int *__restrict__ seq,
-                                                             int *__restrict__ pos_ptr, int n_prompt,
-                                                             int *__restrict__ result, int arg_first,
-                                                             const bf16_t *__restrict__ emb,
-                                                             const float *__restrict__ pemb, int d, int n_ctx,
-                                                             float *__restrict__ x, bf16_t *__restrict__ xb,
-                                                             float *__restrict__ stats_out, WmTsDev ts,
-                                                             int *__restrict__ arrive, int fallback_tok,
-                                                             float *__restrict__ mean_buf, WmStopDev stop, int rpw) {
+// (max, sum exp) partials merged: commutative (no contraction), so a butterfly gives every lane the same bits
+// (a plain two-float struct, selected field by field: HIP's float2 through selects and shuffles left the kernel a scratch copy)
+struct Lse {
+    float m, s;
+};
+__device__ __forceinline__ Lse lse_merge(Lse a, Lse b) {
+    const float M = fmaxf(a.m, b.m);
+    return Lse{M, __fadd_rn(__fmul_rn(a.s, __expf(a.m - M)), __fmul_rn(b.s, __expf(b.m - M)))};
+}
+__device__ __forceinline__ Lse lse_shfl_xor(Lse v, int o) { return Lse{__shfl_xor(v.m, o), __shfl_xor(v.s, o)}; }
+__device__ __forceinline__ Lse lse_load(const float *p) {
+    const float2 v = *(const float2 *)p;
+    return Lse{v.x, v.y};
+}
+
+// X (wm_transcribe's extended decode, WmXDev): the same close, plus the log-prob of the chosen token under the filtered
+// distribution, no_speech_prob at the <|startoftranscript|> position, and -- under sampling -- the sum rule decided on
+// the raw text maximum.  The (max, sum exp) partials of a row are merged over 16 FIXED tile segments (any participant
+// count P scans whole segments; each segment and the final merge have one summation order): the bits do not depend on
+// the rows per workgroup, i.e. on the decode group.
+template <bool X>
+__device__ __forceinline__ void argmax_embed_body(const unsigned long long *__restrict__ tilemax,
+                                                  int n_tiles, int B, int *__restrict__ seq,
+                                                  int *__restrict__ pos_ptr, int n_prompt,
+                                                  int *__restrict__ result, int arg_first,
+                                                  const bf16_t *__restrict__ emb,
+                                                  const float *__restrict__ pemb, int d, int n_ctx,
+                                                  float *__restrict__ x, bf16_t *__restrict__ xb,
+                                                  float *__restrict__ stats_out, const WmTsDev &ts,
+                                                  int *__restrict__ arrive, int fallback_tok,
+                                                  float *__restrict__ mean_buf, const WmStopDev &stop, int rpw,
+                                                  const WmXDev &xd) {
     __shared__ int tok_s[16];
     __shared__ int is_last_s;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1251,6 +1364,41 @@ __global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long 
         }
         if (lane == 0) part_s[my_row][my_pi] = key;
     }
+    __shared__ float seg_s[X ? 16 : 1][X ? 16 : 1][4];   // [row][segment]: allowed text (m, s), unfiltered (m, s)
+    if (X && my_row >= 0) {  // wave-uniform
+        const long rb = (long)(bw + my_row) * n_tiles;
+        const bool sot = pos_raw == xd.par->sot_pos;
+        const int cs = (n_tiles + 15) / 16;
+        for (int sg = my_pi; sg < 16; sg += P) {
+            const int lo = sg * cs, hi = lo + cs < n_tiles ? lo + cs : n_tiles;
+            const Lse none{-1e30f, 0.f};
+            Lse a = none, c = none;
+            for (int t0 = lo + lane; t0 < hi; t0 += 64 * 4) {
+                Lse va0 = none, va1 = none, va2 = none, va3 = none, vc0 = none, vc1 = none, vc2 = none, vc3 = none;
+                if (t0 < hi) va0 = lse_load(xd.txt + (rb + t0) * 2);
+                if (t0 + 64 < hi) va1 = lse_load(xd.txt + (rb + t0 + 64) * 2);
+                if (t0 + 128 < hi) va2 = lse_load(xd.txt + (rb + t0 + 128) * 2);
+                if (t0 + 192 < hi) va3 = lse_load(xd.txt + (rb + t0 + 192) * 2);
+                if (sot) {   // wave-uniform
+                    if (t0 < hi) vc0 = lse_load(xd.all + (rb + t0) * 2);
+                    if (t0 + 64 < hi) vc1 = lse_load(xd.all + (rb + t0 + 64) * 2);
+                    if (t0 + 128 < hi) vc2 = lse_load(xd.all + (rb + t0 + 128) * 2);
+                    if (t0 + 192 < hi) vc3 = lse_load(xd.all + (rb + t0 + 192) * 2);
+                }
+                a = lse_merge(lse_merge(lse_merge(lse_merge(a, va0), va1), va2), va3);
+                c = lse_merge(lse_merge(lse_merge(lse_merge(c, vc0), vc1), vc2), vc3);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                a = lse_merge(a, lse_shfl_xor(a, o));
+                c = lse_merge(c, lse_shfl_xor(c, o));
+            }
+            if (lane == 0) {
+                seg_s[my_row][sg][0] = a.m; seg_s[my_row][sg][1] = a.s;
+                seg_s[my_row][sg][2] = c.m; seg_s[my_row][sg][3] = c.s;
+            }
+        }
+    }
     __syncthreads();
     for (int b = bw + wave; b < B && b < bw + nrows; b += 16) {  // wave-uniform, at most one trip: the owners
         unsigned long long key = lane < P ? part_s[wave][lane] : 0ull;
@@ -1265,6 +1413,21 @@ __global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long 
             key = ok > key ? ok : key;
         }
         key = __shfl(key, 0);               // (every lane of the owner carries the row's key, as before)
+        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f}, lts{-1e30f, 0.f};
+        bool forced = false;
+        if (X) {   // the row's 16 segments, in a fixed order
+            if (lane < 16) {
+                lt.m = seg_s[wave][lane][0]; lt.s = seg_s[wave][lane][1];
+                la.m = seg_s[wave][lane][2]; la.s = seg_s[wave][lane][3];
+            }
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                lt = lse_merge(lt, lse_shfl_xor(lt, o));
+                la = lse_merge(la, lse_shfl_xor(la, o));
+            }
+            lt = Lse{__shfl(lt.m, 0), __shfl(lt.s, 0)};
+            la = Lse{__shfl(la.m, 0), __shfl(la.s, 0)};
+        }
         if (ts.rng) {
             // `key` is the best allowed TEXT token.  Merge the timestamp tiles: best allowed timestamp and
             // log-sum-exp of the allowed timestamps; a timestamp is forced when that exceeds the best text logit
@@ -1292,14 +1455,32 @@ __global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long 
             for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
             unsigned u = (unsigned)(key >> 32);
             u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;  // inverse of argmax_key's order-preserving map
-            const float text_best = key ? __uint_as_float(u) : -1e30f;
+            // (X: the key may be a perturbed score; the rule compares RAW logits, as openai-whisper does)
+            const float text_best = key ? (X ? lt.m : __uint_as_float(u)) : -1e30f;
             const float lse = S > 0.f ? M + __logf(S) : -1e30f;
-            if (kts != 0ull && (key == 0ull || lse > text_best)) key = kts;   // timestamps only
-            else key = kts > key ? kts : key;                                  // arg-max over everything allowed
+            lts = Lse{M, S};
+            forced = kts != 0ull && (key == 0ull || lse > text_best);
+            if (forced) key = kts;                    // timestamps only
+            else key = kts > key ? kts : key;         // arg-max over everything allowed
         }
         if (lane == 0) {
             // key == 0: nothing admissible (every allowed id suppressed, or NaN logits): never index with -1
             int tok = key ? (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)) : fallback_tok;
+            if (X && pos + 1 >= n_prompt) {
+                // log-prob of the chosen token under the filtered distribution (temperature 1): the allowed set is the
+                // admissible timestamps when the sum rule forced one, else text and timestamps; nothing admissible: -inf
+                Lse al = lt;
+                if (forced) al = lts;
+                else if (ts.rng) al = lse_merge(lt, lts);
+                float lp = -INFINITY;
+                if (key) {
+                    const int side = (ts.rng && tok >= ts.ts_begin) ? 1 : 0;
+                    lp = xd.win[((long)b * n_tiles + (tok >> 4)) * 2 + side] - (al.m + __logf(al.s));
+                }
+                if (stop.done && stop.done[b]) lp = 0.f;   // finished earlier: nothing is generated here
+                xd.logprob[(long)(pos + 1 - n_prompt) * B + b] = lp;
+            }
+            if (X && pos == xd.par->sot_pos) xd.nospeech[b] = __expf(xd.ns_v[b] - la.m) / la.s;
             if (stop.done && pos + 1 >= n_prompt) {
                 // the token at index pos + 1 is generated token number gi (0-based)
                 const int gi = pos + 1 - n_prompt;
@@ -1436,6 +1617,41 @@ __global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long 
     }
 }
 
+__global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long long *__restrict__ tilemax,
+                                                             int n_tiles, int B, int *__restrict__ seq,
+                                                             int *__restrict__ pos_ptr, int n_prompt,
+                                                             int *__restrict__ result, int arg_first,
+                                                             const bf16_t *__restrict__ emb,
+                                                             const float *__restrict__ pemb, int d, int n_ctx,
+                                                             float *__restrict__ x, bf16_t *__restrict__ xb,
+                                                             float *__restrict__ stats_out, WmTsDev ts,
+                                                             int *__restrict__ arrive, int fallback_tok,
+                                                             float *__restrict__ mean_buf, WmStopDev stop, int rpw) {
+    const WmXDev none = {};
+    argmax_embed_body<false>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first, emb, pemb, d, n_ctx, x, xb,
+                             stats_out, ts, arrive, fallback_tok, mean_buf, stop, rpw, none);
+}
+__global__ __launch_bounds__(1024) void argmax_embed_x_kernel(const unsigned long long *__restrict__ tilemax,
+                                                               int n_tiles, int B, int *__restrict__ seq,
+                                                               int *__restrict__ pos_ptr, int n_prompt,
+                                                               int *__restrict__ result, int arg_first,
+                                                               const bf16_t *__restrict__ emb,
+                                                               const float *__restrict__ pemb, int d, int n_ctx,
+                                                               float *__restrict__ x, bf16_t *__restrict__ xb,
+                                                               float *__restrict__ stats_out, WmTsDev ts,
+                                                               int *__restrict__ arrive, int fallback_tok,
+                                                               float *__restrict__ mean_buf, WmStopDev stop, int rpw,
+                                                               WmXDev xd) {
+    argmax_embed_body<true>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first, emb, pemb, d, n_ctx, x, xb,
+                            stats_out, ts, arrive, fallback_tok, mean_buf, stop, rpw, xd);
+}
+
+// the DE_LOGITS_X epilogue's Gumbel noise for a range of ids (test hook)
+__global__ void sample_noise_kernel(unsigned long long seed, int chunk, int gi, int n0, int count, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = wm_gumbel_from_bits(wm_sample_bits(seed, (unsigned)chunk, (unsigned)gi, (unsigned)(n0 + i)));
+}
+
 // start of a decode: nobody is done, every row is live
 __global__ void dec_live_init_kernel(WmStopDev stop, int B) {
     const int b = threadIdx.x;
@@ -1522,11 +1738,12 @@ int launch_gemv_shape(wm_ctx *ctx, const DecGemvDev &p, int tn, int nblk, int nw
     }
     const size_t lds = (size_t)nw * tn * nblk * 1024 + (size_t)nw * 32 * 4;
     const int th = nw * 64;
-    constexpr bool WIDE = LN && (EPI == DE_QKV || EPI == DE_GELU || EPI == DE_LOGITS) && SPW <= 6;
+    constexpr bool LOGITS = EPI == DE_LOGITS || EPI == DE_LOGITS_X;
+    constexpr bool WIDE = LN && (EPI == DE_QKV || EPI == DE_GELU || LOGITS) && SPW <= 6;
     if (tn == 1 && nblk == 1) dec_gemv_kernel<SPW, 1, 1, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 1 && nblk == 2 && SPW <= 8) dec_gemv_kernel<SPW <= 8 ? SPW : 2, 1, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
-    else if (tn == 2 && nblk == 1 && WIDE && EPI == DE_LOGITS) dec_gemv_kernel<WIDE ? SPW : 2, 2, 1, WIDE ? EPI : DE_LOGITS, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
-    else if (tn == 4 && nblk == 1 && WIDE && EPI == DE_LOGITS) dec_gemv_kernel<WIDE ? SPW : 2, 4, 1, WIDE ? EPI : DE_LOGITS, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+    else if (tn == 2 && nblk == 1 && WIDE && LOGITS) dec_gemv_kernel<WIDE ? SPW : 2, 2, 1, WIDE ? EPI : DE_LOGITS, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+    else if (tn == 4 && nblk == 1 && WIDE && LOGITS) dec_gemv_kernel<WIDE ? SPW : 2, 4, 1, WIDE ? EPI : DE_LOGITS, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 2 && nblk == 2 && WIDE) dec_gemv_kernel<WIDE ? SPW : 2, 2, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 4 && nblk == 2 && WIDE) dec_gemv_kernel<WIDE ? SPW : 2, 4, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else { wm_set_error("dec_gemv: unsupported launch shape (tn %d, nblk %d, spw %d)", tn, nblk, SPW); return WM_ERR_INVALID; }
@@ -1586,7 +1803,7 @@ static void pick_shape(int epi, bool ln, int spw, int nw, int B, int n_tiles, in
     // 512, register budget) or more than 8 k-steps per wave (K = 4d at d = 576 / 640: spw 12 / 10 on <= 8 waves -- the
     // two-block kernel holds 2 x SPW activation fragments and exists for SPW <= 8 only): one unit per workgroup, more
     // workgroups along the batch
-    if (blocks < 2 && epi == DE_LOGITS && ln && spw <= 6) {
+    if (blocks < 2 && (epi == DE_LOGITS || epi == DE_LOGITS_X) && ln && spw <= 6) {
         // the vocabulary product of a one-block group: 4 tiles per workgroup (810 workgroups instead of 3 242 two-wave
         // ones; -1.4 % per position at tiny.en / base / small, neutral at large-v2: profiles/r04_latency_probe.txt)
         *tn = (g_wm_tuning.logits_tn == 1 || g_wm_tuning.logits_tn == 2) ? g_wm_tuning.logits_tn : 4;
@@ -1594,7 +1811,7 @@ static void pick_shape(int epi, bool ln, int spw, int nw, int B, int n_tiles, in
     }
     if (blocks < 2 || nw > 8 || spw > 8) return;
     *nblk = env_nb == 1 ? 1 : 2;
-    const bool wide = ln && (epi == DE_QKV || epi == DE_GELU || epi == DE_LOGITS) && *nblk == 2 && spw <= 6;
+    const bool wide = ln && (epi == DE_QKV || epi == DE_GELU || epi == DE_LOGITS || epi == DE_LOGITS_X) && *nblk == 2 && spw <= 6;
     if (!wide) return;
     // Tile-group width by RESIDENCY ROUNDS: an 8-wave workgroup of the (1, 2) shape needs <= 128 VGPRs and sits two per
     // CU, the wide shapes (136-190 VGPRs) one per CU; a grid that needs a second round of the chip costs a whole kernel
@@ -1638,6 +1855,8 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
     p.ldo = a.ldo; p.tilemax = a.argmax; p.arg_first = a.arg_first; p.arg_last = a.arg_last;
     p.mask = a.mask; p.mask_words = a.mask_words; p.mask_first_pos = a.mask_first_pos;
     p.ts = a.ts;
+    p.x = a.x;
+    WM_REQUIRE(a.epi != DE_LOGITS_X || (a.x.par && a.pos_ptr), WM_ERR_INVALID, "dec_gemv: DE_LOGITS_X needs its state and the device position");
     p.n_tiles = (a.N + 15) / 16;
     int tn = 1, nblk = 1;
     pick_shape(a.epi, ln, spw, nw, a.B, p.n_tiles, ctx->n_cus, &tn, &nblk);
@@ -1689,6 +1908,10 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
         case DE_LOGITS * 2 + 1: {
             WmProfScope ps(&ctx->prof, "dec_gemv_ln_logits", ctx->stream);
             return launch_gemv<DE_LOGITS, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
+        }
+        case DE_LOGITS_X * 2 + 1: {
+            WmProfScope ps(&ctx->prof, "dec_gemv_ln_logits_x", ctx->stream);
+            return launch_gemv<DE_LOGITS_X, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
         }
         case DE_RESID * 2: {
             WmProfScope ps(&ctx->prof, a.K > a.N ? "dec_gemv_fc2" : "dec_gemv_attn_out", ctx->stream);
@@ -1893,7 +2116,7 @@ int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const b
 int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, int B, int *seq, int *pos_ptr,
                     int n_prompt, int *result, int arg_first, const bf16_t *emb, const float *pemb, int d, int n_ctx,
                     float *x, bf16_t *xb, float *stats_out, const WmTsDev *ts, int *arrive, int fallback_tok,
-                    float *mean_buf, const WmStopDev *stop) {
+                    float *mean_buf, const WmStopDev *stop, const WmXDev *xd) {
     WmProfScope ps(&ctx->prof, "argmax_embed", ctx->stream);
     WmTsDev t;
     memset(&t, 0, sizeof(t));
@@ -1910,9 +2133,24 @@ int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles,
     const int grid = arrive ? (B + rpw - 1) / rpw : 1;
     WM_REQUIRE(grid == 1 || B <= rpw * grid, WM_ERR_INVALID, "argmax_embed: bad grid");
     WM_REQUIRE(arrive || B <= 16, WM_ERR_INVALID, "argmax_embed: more than 16 rows need the arrival counter");
-    argmax_embed_kernel<<<grid, 1024, 0, ctx->stream>>>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first,
-                                                        emb, pemb, d, n_ctx, x, xb, stats_out, t, arrive, fallback_tok,
-                                                        mean_buf, sp, rpw);
+    if (xd && xd->par) {
+        WM_REQUIRE(pos_ptr != nullptr, WM_ERR_INVALID, "argmax_embed: the extended decode needs the device position");
+        argmax_embed_x_kernel<<<grid, 1024, 0, ctx->stream>>>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first,
+                                                              emb, pemb, d, n_ctx, x, xb, stats_out, t, arrive, fallback_tok,
+                                                              mean_buf, sp, rpw, *xd);
+    } else {
+        argmax_embed_kernel<<<grid, 1024, 0, ctx->stream>>>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first,
+                                                            emb, pemb, d, n_ctx, x, xb, stats_out, t, arrive, fallback_tok,
+                                                            mean_buf, sp, rpw);
+    }
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+int wm_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int n0, int count, float *out) {
+    WM_REQUIRE(count >= 0 && n0 >= 0 && chunk >= 0 && gi >= 0 && out, WM_ERR_INVALID, "sample_noise: bad arguments");
+    if (count == 0) return WM_OK;
+    sample_noise_kernel<<<(count + 255) / 256, 256, 0, ctx->stream>>>((unsigned long long)seed, chunk, gi, n0, count, out);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

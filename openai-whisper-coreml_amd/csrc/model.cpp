@@ -68,6 +68,14 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc_t(m, &m->dts_hist, (size_t)WM_DEC_MAXB * 4, s));
     WM_TRY(dalloc_t(m, &m->dts_key, (size_t)WM_DEC_MAXB * (m->vpad / 16), s));
     WM_TRY(dalloc_t(m, &m->dts_lse, (size_t)WM_DEC_MAXB * (m->vpad / 16) * 2, s));
+    const size_t tiles = (size_t)WM_DEC_MAXB * (m->vpad / 16);
+    WM_TRY(dalloc_t(m, &m->dx_txt, tiles * 2, s));
+    WM_TRY(dalloc_t(m, &m->dx_win, tiles * 2, s));
+    WM_TRY(dalloc_t(m, &m->dx_all, tiles * 2, s));
+    WM_TRY(dalloc_t(m, &m->dx_nsv, WM_DEC_MAXB, s));
+    WM_TRY(dalloc_t(m, &m->dx_logprob, (size_t)D.n_text_ctx * WM_DEC_MAXB, s));
+    WM_TRY(dalloc_t(m, &m->dx_nospeech, WM_DEC_MAXB, s));
+    WM_TRY(dalloc(m, (void **)&m->dx_par, sizeof(WmXPar), s));
     WM_TRY(dalloc_t(m, &m->dmask, (size_t)2 * (m->vpad / 32), s));
     WM_HIP(hipMemsetAsync(m->dmask, 0, (size_t)2 * (m->vpad / 32) * 4, s));
     return WM_OK;
@@ -80,6 +88,15 @@ WmStopDev wm_model_stop_dev(const WmModel *m) {
     t.done = m->ddone; t.budget = m->budget_on ? m->dbudget : nullptr; t.live_rows = m->dlive; t.n_live = m->dnlive;
     t.eot = m->stop_eot;
     t.pad_tok = m->stop_eot >= 0 ? m->stop_eot : 0;   // what a finished row keeps embedding: any valid id
+    return t;
+}
+
+WmXDev wm_model_x_dev(const WmModel *m) {
+    WmXDev t;
+    memset(&t, 0, sizeof(t));
+    if (!m->x_on) return t;
+    t.par = m->dx_par; t.txt = m->dx_txt; t.win = m->dx_win; t.all = m->dx_all; t.ns_v = m->dx_nsv;
+    t.logprob = m->dx_logprob; t.nospeech = m->dx_nospeech;
     return t;
 }
 
@@ -552,6 +569,7 @@ int wm_model_decode_begin(wm_ctx *ctx, int B) {
     // (an error in the middle of a step) must not leave the next one with a stale count
     WM_HIP(hipMemsetAsync(m->darrive, 0, sizeof(int), ctx->stream));
     m->stop_on = false;   // wm_transcribe_greedy switches it on for its own decode (lane_prefill)
+    m->x_on = false;      // ... and wm_transcribe its extended decode
     m->xattn_shared = false;   // ... and decides whether the group shares the chip
     return WM_OK;
 }
@@ -567,7 +585,8 @@ int wm_model_set_pos(wm_ctx *ctx, int pos) {
     return WM_OK;
 }
 
-int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, int mask_first_pos, bool use_ts) {
+int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, int mask_first_pos, bool use_ts,
+                         bool x) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head, T = D.n_text_ctx, S = 1500;
@@ -655,6 +674,10 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
             a.mask = m->dmask; a.mask_words = m->vpad / 32; a.mask_first_pos = mask_first_pos; a.pos_ptr = m->dpos;
         }
         if (use_ts) a.ts = wm_model_ts_dev(m);
+        if (x) {   // extended decode: its own epilogue instantiation, the position always from the device
+            WM_REQUIRE(m->x_on, WM_ERR_STATE, "extended decode step without its state");
+            a.epi = DE_LOGITS_X; a.x = wm_model_x_dev(m); a.pos_ptr = m->dpos;
+        }
         WM_TRY(wm_dec_gemv(ctx, a));
     }
     return WM_OK;
@@ -665,12 +688,13 @@ int wm_model_embed_first(wm_ctx *ctx, int B) {
     return wm_dec_embed(ctx, m->dseq, m->dpos, B, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dx, m->dxb, m->dstats, m->dmean);
 }
 
-int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, bool use_ts) {
+int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, bool use_ts, bool x) {
     WmModel *m = ctx->model;
     const WmTsDev t = wm_model_ts_dev(m);
     const WmStopDev sp = wm_model_stop_dev(m);
+    const WmXDev xd = wm_model_x_dev(m);
     return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, write_seq ? m->dseq : nullptr, m->dpos, n_prompt, result,
                            arg_first, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dims.n_text_ctx, m->dx, m->dxb,
                            m->dstats, use_ts ? &t : nullptr, m->darrive, use_ts ? m->ts_eot : arg_first, m->dmean,
-                           m->stop_on ? &sp : nullptr);
+                           m->stop_on ? &sp : nullptr, x ? &xd : nullptr);
 }

@@ -78,6 +78,28 @@ struct WmTsDev {
     int ts_begin, eot, n_vocab, max_initial;  // max_initial: index of the largest first timestamp, < 0 = unlimited
 };
 
+// wm_transcribe's extended decode (DE_LOGITS_X + the arg-max kernel's X mode): per-token log-probabilities of the filtered
+// distribution, openai-whisper's no_speech_prob and Gumbel-max sampling at temperature T > 0.  Everything that changes from
+// call to call lives in device memory (WmXPar, written at prefill), so the captured position graphs stay valid.
+struct WmXPar {
+    unsigned key0, key1;  // the sampling seed (Philox key: low, high word)
+    float inv_T;          // (float)(1 / T); sampling on when > 0
+    int sample;           // 0: arg-max, 1: Gumbel-max
+    int sot_pos;          // decode position of <|startoftranscript|> (no_speech_prob); -1: not computed
+    int ns_tok;           // <|nospeech|> id (with sot_pos >= 0)
+    int chunk0;           // index within the call of the group's row 0 (Philox counter: call index, not group row)
+    int n_prompt;         // generated index gi = pos + 1 - n_prompt
+};
+struct WmXDev {
+    const WmXPar *par;    // null: X mode off
+    float *txt;           // [B][n_tiles][2] (max, sum exp) over the tile's allowed TEXT ids (raw logits)
+    float *win;           // [B][n_tiles][2] raw logit of the tile's winner: text, timestamp
+    float *all;           // [B][n_tiles][2] (max, sum exp) over every id -- at pos == sot_pos only
+    float *ns_v;          // [B] raw logit of <|nospeech|> at pos == sot_pos
+    float *logprob;       // [n_ctx][B] log-prob of generated token gi of row b at [gi * B + b]
+    float *nospeech;      // [B]
+};
+
 // Early-stop state of a decode group (device view; done == null: off).  A row is DONE once it has emitted `eot`
 // (eot >= 0) or produced budget[b] tokens (budget != null); from then on its tokens are `pad_tok`, it is dropped from
 // the compact live list the attention kernels walk, and when the list is empty the host stops launching positions.
@@ -158,7 +180,7 @@ struct WmModel {
     // pass to the next) instead of re-capturing ~2300 launches every time the shape changes (measured: the capture is
     // host work of a few ms that hides behind the lane's own encoder, so this is tidiness, not throughput).
     struct GraphSet {
-        int B = 0, n_prompt = 0, cap_b = 0, mask = 0, stop_key = 0;
+        int B = 0, n_prompt = 0, cap_b = 0, mask = 0, stop_key = 0;  // mask: bit 0 suppress, 1 timestamps, 2 X mode
         // [mode]: 0 = the group has the chip to itself, 1 = it shares it (xattn_shared: short-lived cross-attention
         // workgroups); chosen burst by burst from the number of decodes in flight on the device, captured on first use
         int burst[2] = {0, 0};
@@ -203,6 +225,12 @@ struct WmModel {
     int *dts_rng = nullptr, *dts_hist = nullptr;
     unsigned long long *dts_key = nullptr;
     float *dts_lse = nullptr;
+    // wm_transcribe's extended decode (WmXDev): per-tile partials, outputs and the group's parameters
+    bool x_on = false;          // the decode being enqueued runs the X-mode kernels (a key of the captured graphs)
+    float *dx_txt = nullptr, *dx_win = nullptr, *dx_all = nullptr, *dx_nsv = nullptr;
+    float *dx_logprob = nullptr;   // [n_text_ctx][WM_DEC_MAXB]
+    float *dx_nospeech = nullptr;  // [WM_DEC_MAXB]
+    WmXPar *dx_par = nullptr;
     void *pcm_stage = nullptr;  // host-pointer staging for wm_transcribe_greedy
     size_t pcm_stage_bytes = 0;
     float *io_stage = nullptr;  // staging for host-pointer model calls
@@ -227,8 +255,11 @@ int wm_model_decode_begin(wm_ctx *ctx, int B);
 // embedded input of that position in m->dx (+ m->dstats): wm_model_embed_first for the first
 // position, afterwards produced by wm_model_close_step.  Ends with logits -> per-tile arg-max over
 // [arg_first, arg_last] (m->dargmax); want_logits additionally stores f32 logits in m->dlogits.
+// x: X mode (log-probs, no-speech, sampling; m->x_on's WmXDev) -- DE_LOGITS_X and the arg-max kernel's X variant
 int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, int mask_first_pos = -1,
-                         bool use_ts = false);
+                         bool use_ts = false, bool x = false);
+// the device view of the extended-decode state (par == null when m->x_on is false)
+WmXDev wm_model_x_dev(const WmModel *m);
 // the device view of the context's timestamp-rule state (rng == null when the rules are off)
 WmTsDev wm_model_ts_dev(const WmModel *m);
 int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int32_t eot, int32_t max_initial);
@@ -236,7 +267,8 @@ int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int3
 int wm_model_set_suppress(wm_ctx *ctx, const int32_t *ids, int n, const int32_t *first_ids, int n_first);
 int wm_model_embed_first(wm_ctx *ctx, int B);
 // arg-max reduce + write next token (positions >= n_prompt) + embed next position + advance *dpos
-int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, bool use_ts = false);
+int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, bool use_ts = false,
+                        bool x = false);
 // the device view of the early-stop state (done == null when m->stop_on is false)
 WmStopDev wm_model_stop_dev(const WmModel *m);
 void wm_model_drop_graphs(WmModel *m);
@@ -288,7 +320,10 @@ int wm_enc_attention(wm_ctx *ctx, const bf16_t *qk, const bf16_t *vt, bf16_t *at
 constexpr int WM_DEC_MAXB = 128;  // decode group: up to eight batch blocks of 16 rows (the MFMA M dimension)
 constexpr int WM_NLIVE_RING = 16;  // pinned host slots for the per-burst live-row counts (early stop)
 constexpr int WM_MAXSPLIT = 8;  // stream partials of a (sequence, head) pair of the cross-attention (small batches)
-enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4 };
+// DE_LOGITS_X: DE_LOGITS plus the WmXDev partials (text (max, sum exp), winners' raw logits, the unfiltered partial at
+// the <|startoftranscript|> position) and Gumbel-perturbed keys when sampling -- its own instantiations, so the plain
+// greedy logits kernel does none of it
+enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5 };
 struct DecGemvArgs {
     int epi;
     int B, N, K;
@@ -318,6 +353,7 @@ struct DecGemvArgs {
     const unsigned *mask;
     int mask_words, mask_first_pos;
     WmTsDev ts;  // DE_LOGITS: timestamp rules (ts.rng == null: off)
+    WmXDev x;    // DE_LOGITS_X: extended decode (x.par non-null)
     // optional L2 warm-up of the NEXT skinny GEMV's weights ([pf_rows][pf_k] bf16, WL_TILED)
     const bf16_t *pf_ptr;
     int pf_rows, pf_k;
@@ -358,7 +394,10 @@ int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const b
 int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, int B, int *seq, int *pos_ptr,
                     int n_prompt, int *result, int arg_first, const bf16_t *emb, const float *pemb, int d, int n_ctx,
                     float *x, bf16_t *xb, float *stats_out, const WmTsDev *ts = nullptr, int *arrive = nullptr,
-                    int fallback_tok = 0, float *mean_buf = nullptr, const WmStopDev *stop = nullptr);
+                    int fallback_tok = 0, float *mean_buf = nullptr, const WmStopDev *stop = nullptr,
+                    const WmXDev *xd = nullptr);
+// Gumbel noise g(n) of ids n0 .. n0 + count - 1 as the DE_LOGITS_X epilogue computes it (philox.h), into device memory
+int wm_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int n0, int count, float *out);
 // start of a decode with early stop: no row done, every row live
 int wm_stop_init(wm_ctx *ctx, const WmStopDev &stop, int B);
 // initial timestamp-rule state of B sequences (before the first sampled token)

@@ -8,6 +8,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <vector>
 
 #include "model.h"
@@ -394,6 +395,8 @@ struct LaneJob {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t burst_ev[WM_NLIVE_RING] = {};
     std::vector<int32_t> pr, gen, bud;
+    WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
+    std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
     float stage_sum[3] = {0.f, 0.f, 0.f};
     ~LaneJob() {
         if (c) (void)hipStreamSynchronize(c->stream);  // error paths: nothing may outlive pr / gen / bud
@@ -410,9 +413,18 @@ struct StopCfg {
     const int32_t *budgets = nullptr;  // [B] of the call, already clamped to max_new (null: none)
 };
 
+// wm_transcribe's extended decode: off for wm_transcribe_greedy and for a wm_transcribe call that wants neither outputs nor
+// sampling (then it IS the greedy decode: same graphs, same kernels)
+struct XCfg {
+    bool on = false;
+    WmXPar par = {};               // chunk0 / n_prompt filled per group
+    float *logprobs = nullptr;     // [B][max_new] host, nullable
+    float *no_speech = nullptr;    // [B] host, nullable
+};
+
 // front end -> encoder -> cross K/V -> prompt upload -> first embedding, all enqueued on the lane's stream
 int lane_prefill(LaneJob &j, const void *pcm, wm_dtype pcm_dtype, const int32_t *prompt, int n_prompt, wm_mem mem,
-                 const StopCfg &stop) {
+                 const StopCfg &stop, const XCfg &xc) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
     const wm_dims &D = m->dims;
@@ -450,6 +462,15 @@ int lane_prefill(LaneJob &j, const void *pcm, wm_dtype pcm_dtype, const int32_t 
         }
         WM_TRY(wm_stop_init(c, wm_model_stop_dev(m), Bg));
     }
+    // extended decode: seed, 1/T, the sot position and the group's first call index live in device memory, so the
+    // captured graphs replay for any of them
+    m->x_on = xc.on;
+    if (xc.on) {
+        j.xpar = xc.par;
+        j.xpar.chunk0 = j.b0;
+        j.xpar.n_prompt = n_prompt;
+        WM_HIP(hipMemcpyAsync(m->dx_par, &j.xpar, sizeof(WmXPar), hipMemcpyHostToDevice, c->stream));
+    }
     WM_TRY(wm_model_reserve(c, Bg));
     WM_HIP(hipEventRecord(j.ev[0], c->stream));
     // 1. log-mel front end (f32 fast path), output stays in HBM
@@ -474,8 +495,8 @@ int capture_positions(LaneJob &j, int n_prompt, int n_pos, hipGraph_t *g, hipGra
     WM_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     int crc = WM_OK;
     for (int i = 0; i < n_pos && crc == WM_OK; ++i) {
-        crc = wm_model_decode_step(c, j.Bg, false, 0, m->dims.n_vocab - 1, m->mask_on ? n_prompt - 1 : -1, m->ts_on);
-        if (crc == WM_OK) crc = wm_model_close_step(c, j.Bg, n_prompt, true, nullptr, 0, m->ts_on);
+        crc = wm_model_decode_step(c, j.Bg, false, 0, m->dims.n_vocab - 1, m->mask_on ? n_prompt - 1 : -1, m->ts_on, m->x_on);
+        if (crc == WM_OK) crc = wm_model_close_step(c, j.Bg, n_prompt, true, nullptr, 0, m->ts_on, m->x_on);
     }
     hipError_t ce = hipStreamEndCapture(c->stream, g);
     if (crc != WM_OK || ce != hipSuccess) {   // a half-captured graph is of no use: do not leave it behind
@@ -499,7 +520,7 @@ int capture_positions(LaneJob &j, int n_prompt, int n_pos, hipGraph_t *g, hipGra
 int lane_graph(LaneJob &j, int n_prompt) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
-    const int mk = (m->mask_on ? 1 : 0) | (m->ts_on ? 2 : 0);
+    const int mk = (m->mask_on ? 1 : 0) | (m->ts_on ? 2 : 0) | (m->x_on ? 4 : 0);
     const int sk = m->stop_on ? (1 | (m->budget_on ? 2 : 0) | ((m->stop_eot + 2) << 2)) : 0;
     int cur = -1;
     for (size_t i = 0; i < m->graph_sets.size(); ++i) {
@@ -552,8 +573,9 @@ int lane_burst(LaneJob &j, int n_prompt, int n_steps, bool use_graph, bool stop_
             if (use_graph) {
                 WM_HIP(hipGraphLaunch(g->e1[mode], c->stream));
             } else {
-                WM_TRY(wm_model_decode_step(c, j.Bg, false, 0, m->dims.n_vocab - 1, m->mask_on ? n_prompt - 1 : -1, m->ts_on));
-                WM_TRY(wm_model_close_step(c, j.Bg, n_prompt, true, nullptr, 0, m->ts_on));
+                WM_TRY(wm_model_decode_step(c, j.Bg, false, 0, m->dims.n_vocab - 1, m->mask_on ? n_prompt - 1 : -1, m->ts_on,
+                                            m->x_on));
+                WM_TRY(wm_model_close_step(c, j.Bg, n_prompt, true, nullptr, 0, m->ts_on, m->x_on));
             }
         }
     }
@@ -611,9 +633,28 @@ int wm_lane_parts(int B, int L, bool explicit_lanes, int n_text_state, int n_tex
     return 0;                                    // d >= 768: the chain needs the whole chip
 }
 
+static int transcribe_impl(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
+                           int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
+                           float *logprobs_out, float *no_speech_out, wm_mem mem);
+
 extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
                                     const int32_t *prompt, int n_prompt, int max_new, int32_t eot,
                                     int32_t *tokens_out, int32_t *lens_out, wm_mem mem) try {
+    return transcribe_impl(ctx, pcm, pcm_dtype, B, prompt, n_prompt, max_new, eot, nullptr, tokens_out, lens_out, nullptr,
+                           nullptr, mem);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
+                             int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
+                             float *token_logprobs_out, float *no_speech_prob_out, wm_mem mem) try {
+    return transcribe_impl(ctx, pcm, pcm_dtype, B, prompt, n_prompt, max_new, eot, opts, tokens_out, lens_out,
+                           token_logprobs_out, no_speech_prob_out, mem);
+} WM_API_CATCH
+
+// wm_transcribe_greedy and wm_transcribe: opts == null with both extra outputs null is the greedy decode exactly
+static int transcribe_impl(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
+                           int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
+                           float *logprobs_out, float *no_speech_out, wm_mem mem) {
     WM_MODEL(ctx);
     // per-chunk token budgets set for THIS call (wm_set_token_budgets) are consumed by it whatever happens next: a call
     // that fails validation must not leave them armed for a later, unrelated call with the same B
@@ -632,6 +673,30 @@ extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_d
     WM_REQUIRE(budgets.empty() || (int)budgets.size() == B, WM_ERR_INVALID,
                "token budgets were set for %d chunks, the call has %d", (int)budgets.size(), B);
     for (auto &b : budgets) b = b > max_new ? max_new : b;
+    XCfg xc;
+    {
+        const float T = opts ? opts->temperature : 0.f;
+        const int32_t ns_tok = opts ? opts->no_speech_token : -1;
+        const int32_t sot_index = opts ? opts->sot_index : 0;
+        WM_REQUIRE(std::isfinite(T) && T >= 0.f, WM_ERR_INVALID, "temperature must be finite and >= 0");
+        // (1 / T must be a finite f32 too: an infinite scale turns a zero logit's score into NaN)
+        WM_REQUIRE(T == 0.f || std::isfinite((float)(1.0 / (double)T)), WM_ERR_INVALID,
+                   "temperature %g is too small: 1 / T overflows", (double)T);
+        WM_REQUIRE(sot_index >= 0 && sot_index < n_prompt, WM_ERR_INVALID, "sot_index %d outside the prompt [0, %d)",
+                   sot_index, n_prompt);
+        WM_REQUIRE(ns_tok >= -1 && ns_tok < D.n_vocab, WM_ERR_INVALID, "no_speech_token %d outside the vocabulary", ns_tok);
+        WM_REQUIRE(!no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
+        xc.on = T > 0.f || logprobs_out || no_speech_out;
+        xc.logprobs = logprobs_out;
+        xc.no_speech = no_speech_out;
+        const uint64_t seed = opts ? opts->seed : 0;
+        xc.par.key0 = (unsigned)seed;
+        xc.par.key1 = (unsigned)(seed >> 32);
+        xc.par.sample = T > 0.f ? 1 : 0;
+        xc.par.inv_T = T > 0.f ? (float)(1.0 / (double)T) : 0.f;
+        xc.par.sot_pos = no_speech_out ? sot_index : -1;
+        xc.par.ns_tok = ns_tok;
+    }
     static const bool no_graph = getenv("WM_NO_GRAPH") != nullptr;
     const bool no_stop = g_wm_tuning.no_early_stop != 0;   // probes only: decode every position, truncate on the host
     const bool use_graph = !no_graph && !ctx->prof.on;
@@ -712,7 +777,7 @@ extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_d
                 j.Bg = base + (g < rem ? 1 : 0);
                 j.b0 = g * base + (g < rem ? g : rem);
                 j.t = 0; j.bursts = 0; j.stopped = false;
-                WM_TRY(lane_prefill(j, pcm, pcm_dtype, prompt, n_prompt, mem, stop));
+                WM_TRY(lane_prefill(j, pcm, pcm_dtype, prompt, n_prompt, mem, stop, xc));
                 if (use_graph) WM_TRY(lane_graph(j, n_prompt));
                 j.state = LaneJob::DECODING;
                 progress = true;
@@ -743,6 +808,16 @@ extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_d
                 j.gen.resize((size_t)max_new * j.Bg);  // dseq[n_prompt + i][b]
                 WM_HIP(hipMemcpyAsync(j.gen.data(), j.c->model->dseq + (size_t)n_prompt * j.Bg, j.gen.size() * 4,
                                       hipMemcpyDeviceToHost, j.c->stream));
+                if (xc.logprobs) {   // [gi][b], laid out like dseq
+                    j.lp.resize((size_t)max_new * j.Bg);
+                    WM_HIP(hipMemcpyAsync(j.lp.data(), j.c->model->dx_logprob, j.lp.size() * 4, hipMemcpyDeviceToHost,
+                                          j.c->stream));
+                }
+                if (xc.no_speech) {
+                    j.ns.resize(j.Bg);
+                    WM_HIP(hipMemcpyAsync(j.ns.data(), j.c->model->dx_nospeech, j.ns.size() * 4, hipMemcpyDeviceToHost,
+                                          j.c->stream));
+                }
                 j.state = LaneJob::DRAINING;
                 progress = true;
                 continue;
@@ -761,6 +836,10 @@ extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_d
                 for (int i = 0; i < max_new; ++i)
                     tokens_out[(size_t)(j.b0 + b) * max_new + i] = i < len ? j.gen[(size_t)i * j.Bg + b] : eot;
                 lens_out[j.b0 + b] = len;
+                if (xc.logprobs)   // the token that stops a chunk has its log-prob; nothing after it
+                    for (int i = 0; i < max_new; ++i)
+                        xc.logprobs[(size_t)(j.b0 + b) * max_new + i] = i < len ? j.lp[(size_t)i * j.Bg + b] : 0.f;
+                if (xc.no_speech) xc.no_speech[j.b0 + b] = j.ns[b];
             }
             float ms;
             for (int i = 0; i < 3; ++i)
@@ -775,4 +854,4 @@ extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_d
         for (int i = 0; i < 3; ++i)
             if (jobs[l].stage_sum[i] > ctx->stage_ms[i]) ctx->stage_ms[i] = jobs[l].stage_sum[i];
     return WM_OK;
-} WM_API_CATCH
+}
