@@ -201,6 +201,38 @@ WM_API int wm_transcribe(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B
                   int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
                   wm_mem mem);
 
+/* ------------------------------------------------------------- word-level timestamps --- */
+/* openai-whisper's find_alignment (whisper/timing.py) on the GPU, for the text tokens a transcription produced (e.g. each
+ * chunk's tokens from the temperature step of wm_transcribe that it kept).  Per chunk with text tokens t[0 .. n), all < eot:
+ *   1. teacher-forced decoder pass over [*sot_seq, no_timestamps, *t, eot] (T = n_sot + n + 2 rows);
+ *   2. per alignment head (layer, head), ascending: softmax over the audio frames [0, M), M = n_frames / 2, of the
+ *      cross-attention scores q.k / 8 * qk_scale;  3. z-score per head and frame over the T rows (std with 1 / T);
+ *   4. median filter of width medfilt_width along the frames, reflect padding (none when M <= medfilt_width / 2);
+ *   5. mean over the heads, rows n_sot .. n_sot + n, negated: the cost matrix x[n + 1][M];
+ *   6. dynamic time warping of x in f32 with openai-whisper's CPU cell rule (dtw_cpu; its CUDA path uses another tie order);
+ *   7. start_frame_out[b][i], i = 0 .. n: the first audio frame (20 ms each) of row i on the path -- token i spans
+ *      [start_frame[i], start_frame[i + 1]), a word of tokens [a, b) spans [start_frame[a], start_frame[b]);
+ *   8. token_prob_out[b][i] = softmax(logits[n_sot + i][0 : eot])[t[i]] (raw logits; the word-probability input).
+ *   pcm           : [B][480000] samples, host or device memory (mem); everything else is host memory;
+ *   text_tokens   : i32 [B][max_text], n_text i32 [B] (0 .. max_text); n_frames i32 [B] mel frames (2 .. 3000), NULL = 3000;
+ *   medfilt_width : odd, 1 .. 31 (openai-whisper: 7);  qk_scale finite (openai-whisper: 1.0);
+ *   start_frame_out i32 [B][max_text + 1] (-1 past n; a chunk with n = 0 gets only -1), token_prob_out f32 [B][max_text]
+ *   (nullable; 0 past n).
+ * Every chunk runs its whole path (front end, encoder, cross K/V, teacher-forced pass) on this context's stream, in decode
+ * groups of at most 128 chunks.  Results depend only on the chunk's own inputs (bit level).  Invalid: a text token < 0 or
+ * >= eot, n_sot + max_text + 2 > n_text_ctx, n_frames outside [2, 3000], an even, non-positive or wider medfilt_width, a
+ * qk_scale that is not finite. */
+WM_API int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *sot_seq, int n_sot,
+             int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
+             const int32_t *n_frames, int medfilt_width, float qk_scale, int32_t *start_frame_out, float *token_prob_out,
+             wm_mem mem);
+
+/* The alignment heads wm_align reads: n (layer, head) pairs, any order (used ascending).  n = 0 restores the default, every
+ * head of the decoder layers n_text_layer / 2 .. n_text_layer - 1 (openai-whisper's default when a checkpoint has no list);
+ * a checkpoint's own list (openai-whisper _ALIGNMENT_HEADS, Hugging Face generation_config.alignment_heads) comes from the
+ * host.  Out-of-range pairs and duplicates are invalid.  Same inheritance as wm_set_suppress. */
+WM_API int wm_set_alignment_heads(wm_ctx *ctx, const int32_t *layers, const int32_t *heads, int n);
+
 /* Decode groups a wm_transcribe_greedy call on this context keeps in flight.
  *   0 (default): the library's own measured policy -- one group below 32 chunks, two groups (two weight-sharing lanes)
  *                up to 143, three from 144 chunks, never more than $WM_LANES (default 3) at once; for the NARROW models
@@ -317,7 +349,8 @@ WM_API int wm_profile_overhead_us(wm_ctx *ctx, float *us);
 /* Writes a JSON object {"family": {"ms": total_ms, "n": launches}, ...} into buf. */
 WM_API int wm_profile_json(wm_ctx *ctx, char *buf, size_t buf_bytes);
 /* Wall-clock stage split of the last wm_transcribe_greedy call, in ms (HIP events):
- * [0] front end, [1] encoder + cross-KV projection, [2] decode loop. */
+ * [0] front end, [1] encoder + cross-KV projection, [2] decode loop.  After wm_align: [0] front end + encoder + cross-KV
+ * projection, [1] teacher-forced pass, [2] alignment kernels + DTW. */
 WM_API int wm_last_stage_ms(wm_ctx *ctx, float out3[3]);
 
 #ifdef __cplusplus

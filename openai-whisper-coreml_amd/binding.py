@@ -113,6 +113,8 @@ def load_library(path=None):
         "wm_transcribe_greedy": [vp, vp, ip, ip, vp, ip, ip, ctypes.c_int32, vp, vp, ip],
         "wm_transcribe": [vp, vp, ip, ip, vp, ip, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
         "wm_set_token_budgets": [vp, vp, ip],
+        "wm_set_alignment_heads": [vp, vp, vp, ip],
+        "wm_align": [vp, vp, ip, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, vp, ip, ctypes.c_float, vp, vp, ip],
         "wm_set_lanes": [vp, ip],
         "wm_dev_malloc": [vp, sz, pp],
         "wm_dev_free": [vp, vp],
@@ -561,6 +563,68 @@ class Context:
         return transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures, compression_ratio_threshold,
                                         logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index)
 
+    def set_alignment_heads(self, pairs):
+        """wm_set_alignment_heads: the (layer, head) pairs Context.align reads; empty = every head of the last half of the
+        decoder layers (openai-whisper's default)."""
+        pairs = [(int(l), int(h)) for l, h in pairs]
+        ls = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32)
+        hs = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
+        _check(self.lib, self.lib.wm_set_alignment_heads(self.handle, _ptr(ls) if ls.size else None,
+                                                         _ptr(hs) if hs.size else None, len(pairs)))
+
+    def align(self, pcm, text_tokens, sot_seq, no_timestamps, eot, n_frames=None, medfilt_width=7, qk_scale=1.0,
+              capture_matrix=False):
+        """wm_align: word-level timing inputs of every chunk.  pcm [B][480000]; text_tokens: a list of B token lists (or an
+        int array [B][n]).  Returns (start_frames i32 [B][max_text + 1], token_probs f32 [B][max_text]), -1 / 0 past each
+        chunk's tokens; capture_matrix=True (debug library) also returns the cost matrix f32 [B][max_text + 1][1500]."""
+        pcm = np.ascontiguousarray(pcm)
+        B = pcm.shape[0]
+        rows = [list(np.asarray(t).reshape(-1)) for t in text_tokens]
+        if len(rows) != B:
+            raise ValueError("text_tokens: %d lists for %d chunks" % (len(rows), B))
+        max_text = max([len(r) for r in rows] + [0])
+        tt = np.zeros((B, max(max_text, 1)), dtype=np.int32)
+        for b, r in enumerate(rows):
+            tt[b, :len(r)] = r
+        nt = np.ascontiguousarray([len(r) for r in rows], dtype=np.int32)
+        sot = np.ascontiguousarray(sot_seq, dtype=np.int32)
+        nf = None if n_frames is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
+        start = np.empty((B, max_text + 1), dtype=np.int32)
+        probs = np.empty((B, max_text), dtype=np.float32)
+        matrix = None
+        if capture_matrix:
+            if not hasattr(self.lib, "wmdbg_align_capture"):
+                raise WhisperError(-1, "capture_matrix needs the debug library: Context(dims, debug=True)")
+            matrix = np.empty((B, max_text + 1, 1500), dtype=np.float32)
+            self.lib.wmdbg_align_capture.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            self.lib.wmdbg_align_capture.restype = ctypes.c_int
+            _check(self.lib, self.lib.wmdbg_align_capture(self.handle, _ptr(matrix)))
+        _check(self.lib, self.lib.wm_align(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], B, _ptr(sot), len(sot),
+                                           int(no_timestamps), int(eot), _ptr(tt), _ptr(nt), max_text,
+                                           _ptr(nf) if nf is not None else None, int(medfilt_width), float(qk_scale),
+                                           _ptr(start), _ptr(probs), WM_MEM_HOST))
+        return (start, probs, matrix) if capture_matrix else (start, probs)
+
+    def dtw(self, mats):
+        """Debug library only: the DTW kernel of wm_align alone on a list of f32 cost matrices [N][M] (N <= 448,
+        M <= 1500).  Returns the start frame of every row of each (wmdbg_dtw)."""
+        if not hasattr(self.lib, "wmdbg_dtw"):
+            raise WhisperError(-1, "dtw needs the debug library: Context(dims, debug=True)")
+        B = len(mats)
+        N = np.ascontiguousarray([m.shape[0] for m in mats], dtype=np.int32)
+        M = np.ascontiguousarray([m.shape[1] for m in mats], dtype=np.int32)
+        nmax, ld = max(int(N.max()), 1), max(int(M.max()), 1)
+        x = np.zeros((B, nmax, ld), dtype=np.float32)
+        for b, m in enumerate(mats):
+            x[b, :m.shape[0], :m.shape[1]] = m
+        out = np.empty((B, nmax), dtype=np.int32)
+        fn = self.lib.wmdbg_dtw
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                       ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        _check(self.lib, fn(self.handle, _ptr(x), B, _ptr(N), _ptr(M), ld, _ptr(out)))
+        return [out[b, :N[b]] for b in range(B)]
+
     def sample_noise(self, seed, chunk, gi, n0, count):
         """Debug library only: the Gumbel noise g(n0 .. n0 + count - 1) wm_transcribe's sampling adds, from the device."""
         if not hasattr(self.lib, "wmdbg_sample_noise"):
@@ -572,6 +636,107 @@ class Context:
         g = np.empty(count, dtype=np.float32)
         _check(self.lib, fn(self.handle, int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk), int(gi), int(n0), int(count), _ptr(g)))
         return g
+
+
+# openai-whisper's defaults (whisper/transcribe.py): punctuation merged into the following / preceding word
+PREPEND_PUNCTUATIONS = "\"'“¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+NO_SPACE_LANGUAGES = {"zh", "ja", "th", "lo", "my", "yue"}
+FRAMES_PER_SECOND = 50   # audio frames of the encoder output (openai-whisper TOKENS_PER_SECOND)
+_EOT = object()          # the <|endoftext|> find_alignment appends to the text tokens
+
+
+def _split_tokens_on_unicode(decode, tokens):
+    """openai-whisper Tokenizer.split_tokens_on_unicode: cut wherever the tokens so far decode to whole characters."""
+    decoded_full = decode(tokens)
+    words, word_tokens, current, offset = [], [], [], 0
+    for t in tokens:
+        current.append(t)
+        decoded = decode(current)
+        if "\ufffd" not in decoded or decoded_full[offset + decoded.index("\ufffd")] == "\ufffd":
+            words.append(decoded)
+            word_tokens.append(current)
+            current = []
+            offset += len(decoded)
+    return words, word_tokens
+
+
+def _split_tokens_on_spaces(decode, tokens):
+    """openai-whisper Tokenizer.split_tokens_on_spaces: subwords joined until a space, a punctuation mark or a special."""
+    import string
+    subwords, subword_tokens = _split_tokens_on_unicode(decode, tokens)
+    words, word_tokens = [], []
+    for sw, st in zip(subwords, subword_tokens):
+        if st[0] is _EOT or sw.startswith(" ") or sw.strip() in string.punctuation or not words:
+            words.append(sw)
+            word_tokens.append(list(st))
+        else:
+            words[-1] = words[-1] + sw
+            word_tokens[-1].extend(st)
+    return words, word_tokens
+
+
+def _merge_punctuations(alignment, prepended, appended):
+    """openai-whisper merge_punctuations (whisper/timing.py), in place on dicts with `word` and `tokens`."""
+    i, j = len(alignment) - 2, len(alignment) - 1
+    while i >= 0:
+        prev, foll = alignment[i], alignment[j]
+        if prev["word"].startswith(" ") and prev["word"].strip() in prepended:
+            foll["word"] = prev["word"] + foll["word"]
+            foll["tokens"] = prev["tokens"] + foll["tokens"]
+            prev["word"] = ""
+            prev["tokens"] = []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(alignment):
+        prev, foll = alignment[i], alignment[j]
+        if not prev["word"].endswith(" ") and foll["word"] in appended:
+            prev["word"] = prev["word"] + foll["word"]
+            prev["tokens"] = prev["tokens"] + foll["tokens"]
+            foll["word"] = ""
+            foll["tokens"] = []
+        else:
+            i = j
+        j += 1
+
+
+def word_timestamps(vocab, text_tokens, start_frames, token_probs, language=None,
+                    prepend_punctuations=PREPEND_PUNCTUATIONS, append_punctuations=APPEND_PUNCTUATIONS):
+    """Words of ONE chunk from Context.align's outputs, as openai-whisper's find_alignment + merge_punctuations build them:
+    [{word, tokens, start, end, probability}], times in seconds (frame / 50) from the chunk's start.
+
+    The text tokens (plus the <|endoftext|> find_alignment appends) are split into words by split_tokens_on_unicode for
+    zh / ja / th / lo / my / yue and by split_tokens_on_spaces otherwise (Vocab.decode gives U+FFFD for a partial UTF-8
+    piece).  A word of tokens [a, b) spans [start_frames[a], start_frames[b]) and its probability is the mean of
+    token_probs[a:b].  Punctuation is then merged into the neighbouring words (which keep their own times); words left
+    empty are dropped.  add_word_timestamps' segment heuristics are not applied."""
+    toks = [int(t) for t in np.asarray(text_tokens).reshape(-1)]
+    n = len(toks)
+    if n == 0:
+        return []
+    start_frames = np.asarray(start_frames)
+    token_probs = np.asarray(token_probs, dtype=np.float64)
+
+    def decode(ts):
+        ids = [t for t in ts if t is not _EOT]
+        text = vocab.decode(ids, skip_special=False) if ids else ""
+        return text + ("<|endoftext|>" if ts and ts[-1] is _EOT else "")
+
+    split = _split_tokens_on_unicode if language in NO_SPACE_LANGUAGES else _split_tokens_on_spaces
+    words, word_tokens = split(decode, toks + [_EOT])
+    if len(word_tokens) <= 1:
+        return []
+    bounds = np.concatenate([[0], np.cumsum([len(t) for t in word_tokens[:-1]])]).astype(np.int64)
+    out = []
+    for k in range(len(bounds) - 1):   # the last word is <|endoftext|> (or ends with it): dropped, as by find_alignment
+        a, b = int(bounds[k]), int(bounds[k + 1])
+        out.append(dict(word=words[k], tokens=[t for t in word_tokens[k] if t is not _EOT],
+                        start=float(start_frames[a]) / FRAMES_PER_SECOND, end=float(start_frames[b]) / FRAMES_PER_SECOND,
+                        probability=float(np.mean(token_probs[a:b]))))
+    _merge_punctuations(out, prepend_punctuations, append_punctuations)
+    return [w for w in out if w["word"]]
 
 
 class Vocab:

@@ -571,3 +571,37 @@ extern "C" int wmdbg_bench_graph_branches(wm_ctx *ctx, int iters, int grid, int 
     (void)hipStreamDestroy(s2); (void)hipFree(d);
     return WM_OK;
 }
+
+extern "C" int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, const int32_t *M, int ld, int32_t *start) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(x && N && M && start && B >= 1 && ld >= 1, WM_ERR_INVALID, "bad args");
+    int nmax = 0, mmax = 0;
+    for (int b = 0; b < B; ++b) {
+        WM_REQUIRE(N[b] >= 0 && N[b] <= 448 && M[b] >= 0 && M[b] <= 1500 && M[b] <= ld, WM_ERR_INVALID, "dtw: bad shape");
+        nmax = N[b] > nmax ? N[b] : nmax;
+        mmax = M[b] > mmax ? M[b] : mmax;
+    }
+    if (nmax == 0) return WM_OK;
+    hipStream_t s = ctx->stream;
+    void *dx, *dn, *dm, *dt, *ds;
+    WM_TRY(up(&dx, x, (size_t)B * nmax * ld * 4, s));
+    WM_TRY(up(&dn, N, (size_t)B * 4, s));
+    WM_TRY(up(&dm, M, (size_t)B * 4, s));
+    WM_TRY(up(&dt, nullptr, (size_t)B * wm_dtw_trace_words(nmax) * 4, s));
+    WM_TRY(up(&ds, nullptr, (size_t)B * nmax * 4, s));
+    int rc = wm_dtw(ctx, (const float *)dx, (long)nmax * ld, ld, (const int *)dn, (const int *)dm, B, nmax, mmax,
+                    (unsigned *)dt, (int *)ds, nmax);
+    if (rc == WM_OK) {
+        WM_HIP(hipMemcpyAsync(start, ds, (size_t)B * nmax * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    }
+    for (void *p : {dx, dn, dm, dt, ds}) (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(ctx->model && matrix_out, WM_ERR_INVALID, "bad args");
+    ctx->model->align_dbg_matrix = matrix_out;
+    return WM_OK;
+}

@@ -309,6 +309,7 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     WM_HIP(hipMemcpyAsync(m->dmask, pm->dmask, (size_t)2 * (m->vpad / 32) * 4, hipMemcpyDeviceToDevice, child->stream));
     m->mask_on = pm->mask_on; m->mask_host = pm->mask_host;
     m->ts_on = pm->ts_on; m->ts_begin = pm->ts_begin; m->ts_eot = pm->ts_eot; m->ts_max_initial = pm->ts_max_initial;
+    m->align_l = pm->align_l; m->align_h = pm->align_h;
     WM_HIP(hipStreamSynchronize(child->stream));
     return WM_OK;
 }
@@ -321,6 +322,7 @@ void wm_model_destroy(wm_ctx *ctx) {
     for (void *p : m->allocs) (void)hipFree(p);
     if (m->pcm_stage) (void)hipFree(m->pcm_stage);
     if (m->io_stage) (void)hipFree(m->io_stage);
+    if (m->align_ws) (void)hipFree(m->align_ws);
     delete m;
     ctx->model = nullptr;
 }
@@ -586,7 +588,7 @@ int wm_model_set_pos(wm_ctx *ctx, int pos) {
 }
 
 int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, int mask_first_pos, bool use_ts,
-                         bool x) {
+                         bool x, const WmAlignCap *cap) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head, T = D.n_text_ctx, S = 1500;
@@ -621,7 +623,9 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         a.mean_in = mean_buf(cur);
         a.pf_ptr = L.wxq_f; a.pf_rows = d; a.pf_k = d;
         const bool xshort = m->xattn_shared && !g_wm_tuning.xattn_never_short;
-        const bool fuse_q = xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
+        // wm_align: a layer with alignment heads leaves its f32 query in m->dq (the two launches: same bits as the fused one)
+        const bool cap_l = cap && cap->layer[l].n > 0;
+        const bool fuse_q = !cap_l && xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
         a.pf_head_major = fuse_q ? (H * B + 7) / 8 : 0;   // pairs per XCD of the fused consumer
         WM_TRY(wm_dec_gemv(ctx, a));
         // 4. cross_attn_ln (folded) + query projection
@@ -636,6 +640,7 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
             WM_TRY(wm_dec_xattn_fq(ctx, a, xk, xv, B, H, S, S, m->datt, live, nlive, L.wxo, d, d));
         } else {
             WM_TRY(wm_dec_gemv(ctx, a));
+            if (cap_l) WM_TRY(wm_align_capture_q(ctx, m->dq, d, B, cap->layer[l], cap->q, cap->Tq, cap->J, m->dpos));
             // 5. cross-attention over the 1500 cached encoder frames
             WM_TRY(wm_dec_attention(ctx, m->dq, xk, xv, B, H, S, S, nullptr, xns, m->dpart, m->datt, true, L.wxo, d, d, live, nlive, xshort));
         }

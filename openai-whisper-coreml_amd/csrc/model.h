@@ -111,6 +111,33 @@ struct WmStopDev {
     int eot, pad_tok;
 };
 
+// Word-level timestamps (wm_align, align.hip).  The alignment heads of one decoder layer: n heads (ascending) whose
+// captured queries go to slots slot0 .. slot0 + n - 1 of the capture buffer.
+struct WmAlignLayer {
+    int n = 0, slot0 = 0;
+    int head[32] = {};
+};
+// what the teacher-forced pass of wm_align captures: the layers' alignment-head queries, [B][Tq][J][64] f32
+struct WmAlignCap {
+    const WmAlignLayer *layer;  // [n_text_layer] (host)
+    float *q;
+    int Tq, J;
+};
+// the alignment kernels' view of one decode group (device pointers)
+struct WmAlignDev {
+    const float *q;          // [B][Tq][J][64] captured cross-attention queries (f32)
+    const bf16_t *xkv;       // the group's cross-attention K/V cache [L][2][B][H][1500][64]
+    const int *hl, *hh;      // [J] alignment heads (layer, head), ascending
+    const int *n_text;       // [B] text tokens n of each chunk: decoder rows S + n + 2, cost-matrix rows n + 1; 0 = none
+    const int *n_frames;     // [B] mel frames; the alignment uses audio frames [0, n_frames / 2)
+    float *rowst;            // [B][J][Tq][2] per decoder row: softmax max and 1 / sum (scores in log2 units)
+    float *colst;            // [B][J][1500][2] per frame: mean and std of the probabilities over the chunk's rows
+    float *x;                // [B][n_ld][1500] cost matrix -mean over heads of the filtered z-scores
+    int B, H, Tq, J, S, n_ld;
+    float sc;                // 0.125 * qk_scale * log2(e)
+    int half;                // medfilt_width / 2
+};
+
 struct WmModel {
     wm_dims dims;
     bool finalized = false;
@@ -231,6 +258,12 @@ struct WmModel {
     float *dx_logprob = nullptr;   // [n_text_ctx][WM_DEC_MAXB]
     float *dx_nospeech = nullptr;  // [WM_DEC_MAXB]
     WmXPar *dx_par = nullptr;
+    // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..), the
+    // workspace of a call (grown on demand) and the debug library's one-shot cost-matrix capture (host, null in the product)
+    std::vector<int32_t> align_l, align_h;
+    void *align_ws = nullptr;
+    size_t align_ws_bytes = 0;
+    float *align_dbg_matrix = nullptr;
     void *pcm_stage = nullptr;  // host-pointer staging for wm_transcribe_greedy
     size_t pcm_stage_bytes = 0;
     float *io_stage = nullptr;  // staging for host-pointer model calls
@@ -256,8 +289,9 @@ int wm_model_decode_begin(wm_ctx *ctx, int B);
 // position, afterwards produced by wm_model_close_step.  Ends with logits -> per-tile arg-max over
 // [arg_first, arg_last] (m->dargmax); want_logits additionally stores f32 logits in m->dlogits.
 // x: X mode (log-probs, no-speech, sampling; m->x_on's WmXDev) -- DE_LOGITS_X and the arg-max kernel's X variant
+// cap (wm_align): the layers with alignment heads take the unfused cross_attn_ln + query path and copy those heads' queries
 int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, int mask_first_pos = -1,
-                         bool use_ts = false, bool x = false);
+                         bool use_ts = false, bool x = false, const WmAlignCap *cap = nullptr);
 // the device view of the extended-decode state (par == null when m->x_on is false)
 WmXDev wm_model_x_dev(const WmModel *m);
 // the device view of the context's timestamp-rule state (rng == null when the rules are off)
@@ -404,3 +438,19 @@ int wm_stop_init(wm_ctx *ctx, const WmStopDev &stop, int B);
 int wm_ts_init(wm_ctx *ctx, const WmTsDev &ts, int B);
 int wm_range_softmax(wm_ctx *ctx, const float *logits, long ldo, int B, int first, int n, float *probs);
 int wm_fill_synthetic(wm_ctx *ctx, const WmTensor &t, uint32_t seed, int tensor_id, float gain);
+
+// align.hip (word-level timestamps)
+// the alignment heads' queries of decode position *pos_ptr: dq [B][d] -> cap[b][*pos_ptr][L.slot0 + k][64]
+int wm_align_capture_q(wm_ctx *ctx, const float *dq, int d, int B, const WmAlignLayer &L, float *cap, int Tq, int J,
+                       const int *pos_ptr);
+// position pos = *pos_ptr, i = pos - S in [0, n_text[b]): prob[b][i] = softmax(logits[b][0 : eot])[seq[pos + 1][b]]
+int wm_align_token_prob(wm_ctx *ctx, const float *logits, long ldo, const int *seq, const int *pos_ptr, int B, int S, int eot,
+                        const int *n_text, float *prob, int max_text);
+// scores -> softmax -> z-score -> median filter -> head mean -> a.x (max_n: largest n_text, max_m: largest n_frames / 2)
+int wm_align_matrix(wm_ctx *ctx, const WmAlignDev &a, int max_n, int max_m);
+// trace words a chunk of max_rows rows needs in HBM (when its trace does not fit the DTW kernel's LDS)
+size_t wm_dtw_trace_words(int max_rows);
+// DTW of x[b] (N[b] x M[b], row stride ld, chunk stride x_bstride) -> start[b][0 .. n_out): the first frame of every row on
+// the path, -1 past N[b] (dtw.h).  trace: B * wm_dtw_trace_words(max_rows) words of HBM (used when the LDS is too small).
+int wm_dtw(wm_ctx *ctx, const float *x, long x_bstride, int ld, const int *N, const int *M, int B, int max_rows, int max_m,
+           unsigned *trace, int *start, int n_out);

@@ -8,6 +8,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -855,3 +856,235 @@ static int transcribe_impl(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int
             if (jobs[l].stage_sum[i] > ctx->stage_ms[i]) ctx->stage_ms[i] = jobs[l].stage_sum[i];
     return WM_OK;
 }
+
+// ---------------------------------------------------------------- word-level timestamps
+// openai-whisper's find_alignment (whisper/timing.py): a teacher-forced decoder pass that captures the alignment heads'
+// cross-attention queries, then the alignment kernels and DTW of align.hip.
+extern "C" int wm_set_alignment_heads(wm_ctx *ctx, const int32_t *layers, const int32_t *heads, int n) try {
+    WM_MODEL(ctx);
+    WM_REQUIRE(n >= 0 && (n == 0 || (layers && heads)), WM_ERR_INVALID, "set_alignment_heads: bad list");
+    const int L = m->dims.n_text_layer, H = m->dims.n_text_head;
+    std::vector<std::pair<int32_t, int32_t>> v;
+    for (int i = 0; i < n; ++i) {
+        WM_REQUIRE(layers[i] >= 0 && layers[i] < L && heads[i] >= 0 && heads[i] < H, WM_ERR_INVALID,
+                   "set_alignment_heads: (%d, %d) outside %d layers x %d heads", layers[i], heads[i], L, H);
+        v.emplace_back(layers[i], heads[i]);
+    }
+    std::sort(v.begin(), v.end());
+    for (size_t i = 1; i < v.size(); ++i)
+        WM_REQUIRE(v[i] != v[i - 1], WM_ERR_INVALID, "set_alignment_heads: (%d, %d) listed twice", v[i].first, v[i].second);
+    std::vector<int32_t> hl, hh;
+    for (auto &p : v) { hl.push_back(p.first); hh.push_back(p.second); }
+    auto set = [&](wm_ctx *c) { c->model->align_l = hl; c->model->align_h = hh; };
+    set(ctx);
+    for (wm_ctx *lane : ctx->lanes) set(lane);
+    for (auto &pl : ctx->part_lanes)
+        for (wm_ctx *lane : pl) set(lane);
+    for (auto &kv : ctx->solo_lanes) set(kv.second);
+    return WM_OK;
+} WM_API_CATCH
+
+namespace {
+constexpr size_t kAlignCaptureBudget = (size_t)2 << 30;   // bytes of captured queries + statistics per decode group
+
+size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct AlignCall {
+    const void *pcm;
+    wm_dtype pcm_dtype;
+    wm_mem mem;
+    const int32_t *sot_seq, *text_tokens, *n_text, *n_frames;
+    int n_sot, max_text;
+    int32_t no_timestamps, eot;
+    int half;
+    float qk_scale;
+    int32_t *start_out;
+    float *prob_out, *dbg_matrix;
+    std::vector<int32_t> hl, hh;
+};
+
+// one decode group: chunks [b0, b0 + Bg) of the call
+int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4]) {
+    WmModel *m = ctx->model;
+    const wm_dims &D = m->dims;
+    const int S = c.n_sot, J = (int)c.hl.size(), n_ld = c.max_text + 1, V = D.n_vocab;
+    int nmax = 0, mmax = 0;
+    for (int b = 0; b < Bg; ++b) {
+        nmax = std::max(nmax, (int)c.n_text[b0 + b]);
+        mmax = std::max(mmax, (c.n_frames ? (int)c.n_frames[b0 + b] : WM_N_FRAMES) / 2);
+    }
+    if (nmax == 0) return WM_OK;   // outputs stay -1 / 0
+    const int T = S + nmax + 2;
+    // workspace
+    const size_t o_q = 0, o_row = o_q + align_up((size_t)Bg * T * J * 64 * 4), o_col = o_row + align_up((size_t)Bg * J * T * 8);
+    const size_t o_x = o_col + align_up((size_t)Bg * J * 1500 * 8), o_tr = o_x + align_up((size_t)Bg * n_ld * 1500 * 4);
+    const size_t o_prob = o_tr + align_up((size_t)Bg * wm_dtw_trace_words(n_ld) * 4);
+    const size_t o_start = o_prob + align_up((size_t)Bg * std::max(c.max_text, 1) * 4);
+    const size_t o_int = o_start + align_up((size_t)Bg * n_ld * 4), n_int = (size_t)4 * Bg + 2 * J;
+    const size_t bytes = o_int + align_up(n_int * 4);
+    if (m->align_ws_bytes < bytes) {
+        WM_HIP(hipStreamSynchronize(ctx->stream));
+        if (m->align_ws) WM_HIP(hipFree(m->align_ws));
+        m->align_ws = nullptr;
+        m->align_ws_bytes = 0;
+        WM_HIP(hipMalloc(&m->align_ws, bytes));
+        m->align_ws_bytes = bytes;
+    }
+    char *ws = (char *)m->align_ws;
+    float *q = (float *)(ws + o_q), *x = (float *)(ws + o_x), *prob = (float *)(ws + o_prob);
+    int *start = (int *)(ws + o_start), *ints = (int *)(ws + o_int);
+    // host staging (fenced by the synchronisation at the end of the group): n_text, n_frames, DTW rows, DTW frames, heads
+    std::vector<int32_t> hint(n_int), seq((size_t)T * Bg);
+    for (int b = 0; b < Bg; ++b) {
+        const int n = c.n_text[b0 + b], nf = c.n_frames ? c.n_frames[b0 + b] : WM_N_FRAMES;
+        hint[b] = n;
+        hint[Bg + b] = nf;
+        hint[2 * Bg + b] = n > 0 ? n + 1 : 0;
+        hint[3 * Bg + b] = nf / 2;
+        const int32_t *t = c.text_tokens + (size_t)(b0 + b) * c.max_text;
+        for (int p = 0; p < T; ++p) {   // [*sot_seq, no_timestamps, *t, eot, eot ...] (padding after eot: causal, unread)
+            const int32_t tok = p < S ? c.sot_seq[p] : p == S ? c.no_timestamps : p <= S + n ? t[p - S - 1] : c.eot;
+            seq[(size_t)p * Bg + b] = tok;
+        }
+    }
+    for (int j = 0; j < J; ++j) { hint[4 * Bg + j] = c.hl[j]; hint[4 * Bg + J + j] = c.hh[j]; }
+    struct StreamFence {   // error paths: no copy from seq / hint may outlive them
+        hipStream_t s;
+        ~StreamFence() { (void)hipStreamSynchronize(s); }
+    } fence{ctx->stream};
+    // decode state, then the front end -> encoder -> cross K/V of the group
+    WM_TRY(wm_model_decode_begin(ctx, Bg));
+    WM_HIP(hipMemcpyAsync(m->dseq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipMemcpyAsync(ints, hint.data(), hint.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipMemsetAsync(prob, 0, (size_t)Bg * std::max(c.max_text, 1) * 4, ctx->stream));
+    WM_HIP(hipMemsetAsync(x, 0, (size_t)Bg * n_ld * 1500 * 4, ctx->stream));
+    WM_TRY(wm_model_set_pos(ctx, 0));
+    WM_TRY(wm_model_reserve(ctx, Bg));
+    const size_t pbytes = (size_t)Bg * WM_N_SAMPLES * pcm_elem(c.pcm_dtype);
+    const void *d_pcm = (const char *)c.pcm + (size_t)b0 * WM_N_SAMPLES * pcm_elem(c.pcm_dtype);
+    if (c.mem == WM_MEM_HOST) {
+        if (m->pcm_stage_bytes < pbytes) {
+            WM_HIP(hipStreamSynchronize(ctx->stream));
+            if (m->pcm_stage) WM_HIP(hipFree(m->pcm_stage));
+            m->pcm_stage = nullptr;
+            m->pcm_stage_bytes = 0;
+            WM_HIP(hipMalloc(&m->pcm_stage, pbytes));
+            m->pcm_stage_bytes = pbytes;
+        }
+        WM_HIP(hipMemcpyAsync(m->pcm_stage, d_pcm, pbytes, hipMemcpyHostToDevice, ctx->stream));
+        d_pcm = m->pcm_stage;
+    }
+    WM_HIP(hipEventRecord(ev[0], ctx->stream));
+    WM_TRY(wm_frontend_run(&ctx->fe, &ctx->prof, ctx->stream, d_pcm, c.pcm_dtype, Bg, D.n_mels, m->mel_f32, WM_F32));
+    WM_TRY(wm_model_encode_dev(ctx, m->mel_f32, Bg, nullptr));
+    WM_TRY(wm_model_cross_kv(ctx, Bg));
+    WM_HIP(hipEventRecord(ev[1], ctx->stream));
+    // teacher-forced pass: every position is prompt, the alignment layers leave their queries in the capture buffer
+    std::vector<WmAlignLayer> layers(D.n_text_layer);
+    for (int j = 0; j < J; ++j) {
+        WmAlignLayer &Ly = layers[c.hl[j]];
+        if (Ly.n == 0) Ly.slot0 = j;
+        Ly.head[Ly.n++] = c.hh[j];
+    }
+    const WmAlignCap cap = {layers.data(), q, T, J};
+    WM_TRY(wm_model_embed_first(ctx, Bg));
+    for (int p = 0; p < T; ++p) {
+        const bool want = p >= S && p < S + nmax;   // rows whose logits give a token probability
+        WM_TRY(wm_model_decode_step(ctx, Bg, want, 0, V - 1, -1, false, false, &cap));
+        if (want) WM_TRY(wm_align_token_prob(ctx, m->dlogits, m->vpad, m->dseq, m->dpos, Bg, S, c.eot, ints, prob, std::max(c.max_text, 1)));
+        if (p + 1 < T) WM_TRY(wm_model_close_step(ctx, Bg, T, true, nullptr, 0));
+    }
+    WM_HIP(hipEventRecord(ev[2], ctx->stream));
+    // alignment kernels and DTW
+    WmAlignDev a;
+    a.q = q; a.xkv = m->xkv; a.hl = ints + 4 * Bg; a.hh = ints + 4 * Bg + J; a.n_text = ints; a.n_frames = ints + Bg;
+    a.rowst = (float *)(ws + o_row); a.colst = (float *)(ws + o_col); a.x = x;
+    a.B = Bg; a.H = D.n_text_head; a.Tq = T; a.J = J; a.S = S; a.n_ld = n_ld;
+    a.sc = 0.125f * c.qk_scale * 1.44269504088896340736f;
+    a.half = c.half;
+    WM_TRY(wm_align_matrix(ctx, a, nmax, mmax));
+    WM_TRY(wm_dtw(ctx, x, (long)n_ld * 1500, 1500, ints + 2 * Bg, ints + 3 * Bg, Bg, nmax + 1, mmax, (unsigned *)(ws + o_tr),
+                  start, n_ld));
+    WM_HIP(hipEventRecord(ev[3], ctx->stream));
+    WM_HIP(hipMemcpyAsync(c.start_out + (size_t)b0 * n_ld, start, (size_t)Bg * n_ld * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c.prob_out && c.max_text > 0)
+        WM_HIP(hipMemcpyAsync(c.prob_out + (size_t)b0 * c.max_text, prob, (size_t)Bg * c.max_text * 4, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    if (c.dbg_matrix)
+        WM_HIP(hipMemcpyAsync(c.dbg_matrix + (size_t)b0 * n_ld * 1500, x, (size_t)Bg * n_ld * 1500 * 4, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    float ms;
+    for (int i = 0; i < 3; ++i)
+        if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) ctx->stage_ms[i] += ms;
+    return WM_OK;
+}
+}  // namespace
+
+extern "C" int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *sot_seq, int n_sot,
+                        int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
+                        const int32_t *n_frames, int medfilt_width, float qk_scale, int32_t *start_frame_out,
+                        float *token_prob_out, wm_mem mem) try {
+    WM_MODEL(ctx);
+    AlignCall c;
+    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
+    m->align_dbg_matrix = nullptr;
+    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
+    WM_REQUIRE(pcm && sot_seq && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID, "bad pcm dtype");
+    WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
+    const wm_dims &D = m->dims;
+    const int V = D.n_vocab;
+    WM_REQUIRE(n_sot >= 1 && max_text >= 0 && n_sot + max_text + 2 <= D.n_text_ctx, WM_ERR_INVALID,
+               "align: sot_seq (%d) + max_text (%d) + 2 must fit the %d-token context", n_sot, max_text, D.n_text_ctx);
+    for (int i = 0; i < n_sot; ++i)
+        WM_REQUIRE(sot_seq[i] >= 0 && sot_seq[i] < V, WM_ERR_INVALID, "align: sot_seq token %d out of range", sot_seq[i]);
+    WM_REQUIRE(no_timestamps >= 0 && no_timestamps < V && eot >= 0 && eot < V, WM_ERR_INVALID,
+               "align: no_timestamps / eot outside the vocabulary");
+    WM_REQUIRE(medfilt_width >= 1 && medfilt_width <= 31 && medfilt_width % 2 == 1, WM_ERR_INVALID,
+               "align: medfilt_width %d must be odd, 1 .. 31", medfilt_width);
+    WM_REQUIRE(std::isfinite(qk_scale), WM_ERR_INVALID, "align: qk_scale must be finite");
+    for (int b = 0; b < B; ++b) {
+        WM_REQUIRE(n_text[b] >= 0 && n_text[b] <= max_text, WM_ERR_INVALID, "align: n_text[%d] = %d outside [0, %d]", b,
+                   n_text[b], max_text);
+        for (int i = 0; i < n_text[b]; ++i) {
+            const int32_t t = text_tokens[(size_t)b * max_text + i];
+            WM_REQUIRE(t >= 0 && t < eot, WM_ERR_INVALID, "align: text token %d of chunk %d is not a text token (< eot %d)", t,
+                       b, eot);
+        }
+        if (n_frames)
+            WM_REQUIRE(n_frames[b] >= 2 && n_frames[b] <= WM_N_FRAMES, WM_ERR_INVALID, "align: n_frames[%d] = %d outside [2, %d]",
+                       b, n_frames[b], WM_N_FRAMES);
+    }
+    if (m->align_l.empty()) {   // openai-whisper's default: every head of the last half of the decoder layers
+        for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)
+            for (int h = 0; h < D.n_text_head; ++h) { c.hl.push_back(l); c.hh.push_back(h); }
+    } else {
+        c.hl = m->align_l;
+        c.hh = m->align_h;
+    }
+    c.pcm = pcm; c.pcm_dtype = pcm_dtype; c.mem = mem;
+    c.sot_seq = sot_seq; c.text_tokens = text_tokens; c.n_text = n_text; c.n_frames = n_frames;
+    c.n_sot = n_sot; c.max_text = max_text; c.no_timestamps = no_timestamps; c.eot = eot;
+    c.half = medfilt_width / 2; c.qk_scale = qk_scale;
+    c.start_out = start_frame_out; c.prob_out = token_prob_out;
+    const int n_ld = max_text + 1;
+    for (size_t i = 0; i < (size_t)B * n_ld; ++i) start_frame_out[i] = -1;
+    if (token_prob_out)
+        for (size_t i = 0; i < (size_t)B * max_text; ++i) token_prob_out[i] = 0.f;
+    if (c.dbg_matrix) memset(c.dbg_matrix, 0, (size_t)B * n_ld * 1500 * 4);
+    // decode groups of at most WM_DEC_MAXB chunks, fewer when the captured queries would outgrow the budget
+    const size_t J = c.hl.size(), T = (size_t)n_sot + max_text + 2;
+    const size_t per_chunk = T * J * (64 * 4 + 8) + J * 1500 * 8 + (size_t)n_ld * 1500 * 4;
+    const int G = (int)std::max<size_t>(1, std::min<size_t>(WM_DEC_MAXB, kAlignCaptureBudget / per_chunk));
+    ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = WM_OK;
+    for (auto &e : ev)
+        if (rc == WM_OK && hipEventCreate(&e) != hipSuccess) { wm_set_error("hipEventCreate failed"); rc = WM_ERR_HIP; }
+    for (int b0 = 0; b0 < B && rc == WM_OK; b0 += G) rc = align_group(ctx, c, b0, std::min(G, B - b0), ev);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (auto &e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+} WM_API_CATCH

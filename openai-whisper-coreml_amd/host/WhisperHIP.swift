@@ -165,6 +165,40 @@ struct Whisper {
         return (0..<chunks).map { c in Array(tokens[c * Int(maxNew)..<c * Int(maxNew) + Int(lens[c])]) }
     }
 
+    /// Word-level timing inputs (wm_align; openai-whisper find_alignment): for each 30 s window of `audio` and the text
+    /// tokens a transcription produced for it (all < eot), the first audio frame (20 ms) of every token plus the end row, and
+    /// every token's probability.  Word grouping (split_to_word_tokens, merge_punctuations) is host work: binding.py
+    /// word_timestamps.  `alignmentHeads`: a checkpoint's (layer, head) list; nil = the last half of the decoder layers.
+    /// Not compiled in this repository (see the top of the file).
+    func align(audio: [Float], text: [[Int32]], sotSequence: [Int32] = [50258, 50259, 50359], noTimestamps: Int32 = 50363,
+               eot: Int32 = 50257, alignmentHeads: [(Int32, Int32)]? = nil,
+               medfiltWidth: Int32 = 7) throws -> (startFrames: [[Int32]], tokenProbs: [[Float]]) {
+        typealias HeadsFn = @convention(c) (OpaquePointer, UnsafePointer<Int32>?, UnsafePointer<Int32>?, Int32) -> Int32
+        typealias AlignFn = @convention(c) (OpaquePointer, UnsafeRawPointer, Int32, Int32, UnsafePointer<Int32>, Int32, Int32,
+                                            Int32, UnsafePointer<Int32>, UnsafePointer<Int32>, Int32, UnsafePointer<Int32>?,
+                                            Int32, Float, UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Float>?, Int32) -> Int32
+        let n = 480_000
+        let chunks = text.count
+        var pcm = [Float](repeating: 0, count: chunks * n)
+        pcm.replaceSubrange(0..<min(audio.count, chunks * n), with: audio.prefix(chunks * n))
+        let maxText = text.map { $0.count }.max() ?? 0
+        var flat = [Int32](repeating: 0, count: max(1, chunks * maxText))
+        for (c, t) in text.enumerated() { flat.replaceSubrange(c * maxText..<c * maxText + t.count, with: t) }
+        let nText = text.map { Int32($0.count) }
+        let heads: HeadsFn = try sym("wm_set_alignment_heads")
+        let h = alignmentHeads ?? []
+        try check(heads(ctx, h.map { $0.0 }, h.map { $0.1 }, Int32(h.count)))
+        var start = [Int32](repeating: -1, count: chunks * (maxText + 1))
+        var probs = [Float](repeating: 0, count: max(1, chunks * maxText))
+        let f: AlignFn = try sym("wm_align")
+        try pcm.withUnsafeBytes { p in
+            try check(f(ctx, p.baseAddress!, 1 /* WM_F32 */, Int32(chunks), sotSequence, Int32(sotSequence.count),
+                        noTimestamps, eot, flat, nText, Int32(maxText), nil, medfiltWidth, 1.0, &start, &probs, 0))
+        }
+        return ((0..<chunks).map { c in Array(start[c * (maxText + 1)...c * (maxText + 1) + text[c].count]) },
+                (0..<chunks).map { c in Array(probs[c * maxText..<c * maxText + text[c].count]) })
+    }
+
     /// ids -> text with the tokenizer's vocab.json (wm_vocab_load / wm_detokenize; no vocabulary ships with the library).
     func text(of ids: [Int32], vocabJSON: String) throws -> String {
         let load: VocabLoadFn = try sym("wm_vocab_load")

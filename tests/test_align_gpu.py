@@ -1,0 +1,278 @@
+"""GPU tests of word-level timestamps: wm_align (teacher-forced pass with the alignment heads' queries captured, the
+alignment kernels and the DTW kernel of csrc/align.hip), wm_set_alignment_heads and binding.word_timestamps on top.
+Oracle: oracle/whisper_ref.py's helpers plus a decoder forward that records the cross-attention scores (below), and the
+numpy restatement of find_alignment's post-processing in tests/test_align_cpu.py."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import whisper_ref as R
+from test_align_cpu import _bytes_to_unicode, alignment_matrix, start_frames
+from test_model_gpu import _lively_on_device, _oracle_weights, lively, tones  # noqa: F401  (lively: module fixture)
+
+pytestmark = pytest.mark.gpu
+
+EOT, NO_TS = 890, 889               # the lively model's tiny vocabulary (1024)
+SOT_SEQ = [10, 21, 5]
+MEASURED = {}
+
+# rel-L2 of the cost matrix against the fp32 restatement, gates >= 3x the largest value measured on an MI355X: tiny 0.0178,
+# production width 0.0208 (every case of the two tests; with $WM_MEASURED_DIR set, the tests write what they measure to
+# align_measured.json there)
+GATE_TINY = 0.06
+GATE_WIDE = 0.07
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_measured():
+    yield
+    out = os.environ.get("WM_MEASURED_DIR")
+    if out:
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, "align_measured.json"), "w") as f:
+            json.dump(MEASURED, f, indent=1, sort_keys=True)
+
+
+def _note(key, v):
+    MEASURED[key] = max(MEASURED.get(key, 0.0), float(v))
+
+
+def oracle_forward(sd, dims, tokens, xa):
+    """R.decode_logits for one sequence with the cross-attention scores q.k / 8 of every (layer, head) recorded:
+    (logits [T][V], qk [L][H][T][1500])."""
+    tokens = torch.as_tensor(np.asarray(tokens, dtype=np.int64)[None])
+    xa = torch.as_tensor(np.asarray(xa, dtype=np.float32)[None])
+    T, H = tokens.shape[1], dims["n_text_head"]
+    x = sd["decoder.token_embedding.weight"][tokens] + sd["decoder.positional_embedding"][:T]
+    mask = torch.full((dims["n_text_ctx"], dims["n_text_ctx"]), float("-inf")).triu_(1)
+    qks = []
+    with torch.no_grad():
+        for i in range(dims["n_text_layer"]):
+            p = "decoder.blocks.%d" % i
+            x = x + R._mha(R._ln(x, sd, p + ".attn_ln"), sd, p + ".attn", H, mask=mask)
+            h = R._ln(x, sd, p + ".cross_attn_ln")
+            q = R._linear(h, sd, p + ".cross_attn.query")
+            k = R._linear(xa, sd, p + ".cross_attn.key", bias=False)
+            sc = (q.shape[-1] // H) ** -0.25
+            qh = q.view(1, T, H, -1).permute(0, 2, 1, 3) * sc
+            kh = k.view(1, k.shape[1], H, -1).permute(0, 2, 3, 1) * sc
+            qks.append((qh @ kh).float()[0])
+            x = x + R._mha(h, sd, p + ".cross_attn", H, xa=xa)
+            x = x + R._linear(F.gelu(R._linear(R._ln(x, sd, p + ".mlp_ln"), sd, p + ".mlp.0")), sd, p + ".mlp.2")
+        x = R._ln(x, sd, "decoder.ln")
+        logits = (x @ sd["decoder.token_embedding.weight"].T).float()[0]
+    return logits.numpy(), torch.stack(qks).numpy()
+
+
+def default_heads(dims):
+    L, H = dims["n_text_layer"], dims["n_text_head"]
+    return [(l, h) for l in range(L // 2, L) for h in range(H)]
+
+
+def _text(rng, n, eot=EOT):
+    return [int(t) for t in rng.integers(0, eot, size=n)]
+
+
+def _check_against_oracle(ctx, sd, dims, pcm, texts, heads, n_frames, width, key, gate, eot=EOT, no_ts=NO_TS):
+    """cost matrix vs the fp32 restatement (rel-L2), DTW of the GPU's own matrix (exact), the oracle matrix's path (loose),
+    token probabilities vs the GPU's own logits (tight) and the oracle's (loose)."""
+    mel = ctx.logmel(pcm, out_dtype=np.float32)
+    xa = ctx.encode_mel(mel)
+    sf, pr, mat = ctx.align(pcm, texts, SOT_SEQ, no_ts, eot, n_frames=n_frames, medfilt_width=width, capture_matrix=True)
+    S = len(SOT_SEQ)
+    for b, t in enumerate(texts):
+        n, M = len(t), n_frames // 2
+        seq = SOT_SEQ + [no_ts] + t + [eot]
+        logits, qk = oracle_forward(sd, dims, seq, xa[b])
+        want = alignment_matrix(np.stack([qk[l, h] for l, h in heads]), S, n_frames, width)
+        got = mat[b, :n + 1, :M]
+        assert np.all(mat[b, n + 1:] == 0) and np.all(mat[b, :, M:] == 0)
+        e = R.rel_l2(got, want)
+        _note(key, e)
+        assert e <= gate, (key, b, e)
+        # DTW: bit-exact against numpy f32 on the GPU's own matrix
+        own = start_frames(got)
+        assert sf[b, :n + 1].tolist() == own.tolist(), (key, b)
+        assert np.all(sf[b, n + 1:] == -1)
+        d = np.abs(start_frames(want) - own)
+        _note(key + "_frame_median", np.median(d))
+        _note(key + "_frame_max", d.max())
+        assert np.median(d) <= 1, (key, b, d)
+        # token probabilities: softmax(logits[S + i][:eot])[t[i]]
+        own_l = ctx.decode_logits(np.asarray([seq[:-1]], dtype=np.int32), xa[b:b + 1])[0]
+        p_own = torch.softmax(torch.as_tensor(own_l[S:S + n, :eot]).double(), -1).numpy()[np.arange(n), t]
+        p_ref = torch.softmax(torch.as_tensor(logits[S:S + n, :eot]).double(), -1).numpy()[np.arange(n), t]
+        d_own = np.abs(pr[b, :n] - p_own).max()
+        _note(key + "_prob_own", d_own)
+        assert d_own <= 1e-5 + 1e-4 * p_own.max(), (key, b, d_own)
+        d_ref = np.abs(pr[b, :n] - p_ref).max()
+        _note(key + "_prob_oracle", d_ref)
+        assert d_ref <= 2e-3, (key, b, d_ref)      # measured 2.4e-5
+        assert np.all(pr[b, n:] == 0)
+    return sf, pr
+
+
+@pytest.fixture(scope="module")
+def dbg(pkg, lively):
+    """the lively model in a context of the debug library (cost-matrix capture, the DTW hook)"""
+    dims, sd_np, sd, _ = lively
+    ctx = pkg.binding.Context(dims, debug=True)
+    ctx.load_state_dict(sd_np)
+    ctx.finalize()
+    yield dims, sd, ctx
+    ctx.close()
+
+
+def test_dtw_kernel_matches_numpy(dbg):
+    _, _, ctx = dbg
+    rng = np.random.default_rng(3)
+    for kind in ("random", "ties"):
+        for n in (1, 2, 225, 446):
+            mats = []
+            for m in (1, 3, 4, 750, 1500):
+                mats.append(rng.standard_normal((n, m)).astype(np.float32) if kind == "random"
+                            else rng.integers(-1, 2, size=(n, m)).astype(np.float32))
+            # whole batch (the 1500-frame matrix decides: trace in LDS up to 225 rows, in HBM at 446), then each alone
+            for got, x in zip(ctx.dtw(mats), mats):
+                assert got.tolist() == start_frames(x).tolist(), (kind, n, x.shape)
+            if n == 446:
+                x = mats[3]     # 446 x 750: the trace fits the LDS when alone
+                assert ctx.dtw([x])[0].tolist() == start_frames(x).tolist()
+
+
+@pytest.mark.parametrize("heads, n_frames, width", [("default", 3000, 7), ("explicit", 1234, 7), ("default", 1234, 1),
+                                                    ("explicit", 3000, 1)])
+def test_cost_matrix_tiny_against_the_oracle(dbg, heads, n_frames, width):
+    dims, sd, ctx = dbg
+    rng = np.random.default_rng(n_frames + width)
+    hl = default_heads(dims) if heads == "default" else [(0, 1), (1, 0)]
+    ctx.set_alignment_heads([] if heads == "default" else hl)
+    try:
+        texts = [_text(rng, 23), _text(rng, 5), _text(rng, 1)]
+        _check_against_oracle(ctx, sd, dims, tones(3), texts, hl, n_frames, width, "tiny_rel_l2", GATE_TINY)
+    finally:
+        ctx.set_alignment_heads([])
+
+
+def test_cost_matrix_production_width_against_the_oracle(pkg):
+    dims = dict(n_mels=80, n_audio_ctx=1500, n_audio_state=1280, n_audio_head=20, n_audio_layer=2, n_vocab=51865,
+                n_text_ctx=448, n_text_state=1280, n_text_head=20, n_text_layer=2)
+    ctx = pkg.binding.Context(dims, debug=True)
+    try:
+        ctx.init_synthetic(5)
+        _lively_on_device(ctx, dims)
+        ctx.finalize()
+        sd = _oracle_weights(ctx, dims)
+        rng = np.random.default_rng(9)
+        eot, no_ts = 50257, 50363
+        for heads, n_frames, width in (("default", 3000, 7), ("explicit", 1234, 1)):
+            hl = default_heads(dims) if heads == "default" else [(0, 3), (1, 7), (1, 19)]
+            ctx.set_alignment_heads([] if heads == "default" else hl)
+            texts = [_text(rng, 40, eot), _text(rng, 9, eot)]
+            _check_against_oracle(ctx, sd, dims, tones(2, 5), texts, hl, n_frames, width, "wide_rel_l2", GATE_WIDE,
+                                  eot=eot, no_ts=no_ts)
+    finally:
+        ctx.close()
+
+
+def test_batch_invariance_across_groups(lively):
+    """a chunk alone, inside 9 chunks and inside 130 (two decode groups), with mixed n_text including 0: same bits"""
+    dims, _, _, ctx = lively
+    rng = np.random.default_rng(11)
+    pcm = np.concatenate([tones(13)] * 10)
+    lens = [int(v) for v in rng.integers(0, 13, size=130)]
+    lens[0], lens[4], lens[129] = 12, 0, 7
+    texts = [_text(rng, n) for n in lens]
+    nf = [int(v) for v in rng.integers(2, 3001, size=130)]
+    sf_all, pr_all = ctx.align(pcm, texts, SOT_SEQ, NO_TS, EOT, n_frames=nf)
+    assert np.all(sf_all[4] == -1) and np.all(pr_all[4] == 0)
+    sf_9, pr_9 = ctx.align(pcm[121:130], texts[121:130], SOT_SEQ, NO_TS, EOT, n_frames=nf[121:130])
+    w = sf_9.shape[1]
+    assert np.array_equal(sf_9, sf_all[121:130, :w]) and np.array_equal(pr_9, pr_all[121:130, :w - 1])
+    for b in (0, 4, 128, 129):
+        sf1, pr1 = ctx.align(pcm[b:b + 1], texts[b:b + 1], SOT_SEQ, NO_TS, EOT, n_frames=nf[b])
+        n = lens[b]
+        assert np.array_equal(sf1[0, :n + 1], sf_all[b, :n + 1]) and np.array_equal(pr1[0, :n], pr_all[b, :n]), b
+
+
+def test_alignment_heads_default_invalid_and_inherited(lively, pkg):
+    dims, _, _, ctx = lively
+    WhisperError = pkg.binding.WhisperError
+    pcm, texts = tones(2), [[5, 100, 7, 300], [9, 9]]
+    base = ctx.align(pcm, texts, SOT_SEQ, NO_TS, EOT)
+    ctx.set_alignment_heads(default_heads(dims))
+    try:
+        same = ctx.align(pcm, texts, SOT_SEQ, NO_TS, EOT)
+        assert all(np.array_equal(a, b) for a, b in zip(base, same))
+        for bad in ([(2, 0)], [(0, 2)], [(-1, 0)], [(1, 1), (0, 0), (1, 1)]):
+            with pytest.raises(WhisperError) as e:
+                ctx.set_alignment_heads(bad)
+            assert e.value.status == 1
+        ctx.set_alignment_heads([(1, 1), (0, 0)])     # any order: used ascending
+        mine = ctx.align(pcm, texts, SOT_SEQ, NO_TS, EOT)
+        clone = ctx.clone()
+        try:
+            got = clone.align(pcm, texts, SOT_SEQ, NO_TS, EOT)
+            assert all(np.array_equal(a, b) for a, b in zip(mine, got))
+        finally:
+            clone.close()
+    finally:
+        ctx.set_alignment_heads([])
+    again = ctx.align(pcm, texts, SOT_SEQ, NO_TS, EOT)
+    assert all(np.array_equal(a, b) for a, b in zip(base, again))
+
+
+def test_invalid_align_arguments(lively, pkg):
+    dims, _, _, ctx = lively
+    WhisperError = pkg.binding.WhisperError
+    pcm = tones(1)
+    bad = [dict(texts=[[EOT]]), dict(texts=[[-1]]), dict(texts=[[1] * 444]), dict(n_frames=1), dict(n_frames=3001),
+           dict(medfilt_width=6), dict(medfilt_width=0), dict(medfilt_width=-3), dict(qk_scale=float("nan")),
+           dict(qk_scale=float("inf"))]
+    for kw in bad:
+        texts = kw.pop("texts", [[1, 2, 3]])
+        with pytest.raises(WhisperError) as e:
+            ctx.align(pcm, texts, SOT_SEQ, NO_TS, EOT, **kw)
+        assert e.value.status == 1, kw
+    sf, pr = ctx.align(pcm, [[1] * 443], SOT_SEQ, NO_TS, EOT)     # 3 + 443 + 2 = 448: the longest allowed
+    assert sf.shape == (1, 444) and np.all(sf[0] >= 0) and np.all(np.diff(sf[0]) >= 0)
+
+
+def test_greedy_is_unchanged_around_align(lively):
+    dims, _, _, ctx = lively
+    pcm = tones(3)
+    t0, l0 = ctx.transcribe_greedy(pcm, SOT_SEQ, 20, eot=EOT)
+    ctx.align(pcm, [list(t0[b, :max(int(l0[b]) - 1, 0)]) for b in range(3)], SOT_SEQ, NO_TS, EOT)
+    t1, l1 = ctx.transcribe_greedy(pcm, SOT_SEQ, 20, eot=EOT)
+    assert np.array_equal(t0, t1) and np.array_equal(l0, l1)
+
+
+def test_end_to_end_transcribe_align_words(lively, pkg, tmp_path):
+    dims, _, _, ctx = lively
+    B = pkg.binding
+    b2u = _bytes_to_unicode()
+    pieces = {"".join(b2u[c] for c in ((" w%d" % i) if i % 3 else ("x%d" % i)).encode()): i for i in range(EOT)}
+    path = tmp_path / "vocab.json"
+    path.write_text(json.dumps(pieces))
+    vocab = B.Vocab(str(path))
+    pcm = tones(4)
+    r = ctx.transcribe(pcm, SOT_SEQ + [NO_TS], 30, eot=EOT)
+    texts = [[int(t) for t in r.tokens[b, :r.n_text[b]] if t < EOT] for b in range(4)]
+    n_frames = [3000, 1234, 2000, 600]
+    sf, pr = ctx.align(pcm, texts, SOT_SEQ, NO_TS, EOT, n_frames=n_frames)
+    n_words = 0
+    for b in range(4):
+        words = B.word_timestamps(vocab, texts[b], sf[b], pr[b])
+        n_words += len(words)
+        prev = 0.0
+        for w in words:
+            assert 0.0 <= w["start"] <= w["end"] <= n_frames[b] / 100, (b, w)
+            assert w["start"] >= prev
+            assert 0.0 <= w["probability"] <= 1.0
+            prev = w["start"]
+    assert n_words > 0
+    vocab.close()
