@@ -83,6 +83,24 @@ WM_API void generate_spectrogram(double *audio, double *output);
 WM_API int wm_logmel(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int n_chunks, int n_mels,
               void *out, wm_dtype out_dtype, wm_mem mem);
 
+/* openai-whisper's log_mel_spectrogram(audio, padding=480000) for R recordings of any length: the front end of its
+ * long-form transcribe(), one log-mel over the whole recording.  Recording r's signal is its samples followed by 480000
+ * zeros, reflect-padded by 200 samples at both ends (torch.stft center=True, pad_mode="reflect"); then the f32 fast path of
+ * wm_logmel frame by frame (periodic Hann 400, hop 160, power, mel, log10(max(., 1e-10))), the same kernel arithmetic;
+ * then max(x, gmax_r - 8) with gmax_r over ALL T_r frames of the recording, and (x + 4) / 4.
+ *   pcm            : the samples of all recordings back to back, WM_I16 (x = s/32768) / WM_F32 / WM_F64, mem-space
+ *                    selectable (with WM_MEM_HOST only pcm[sample_offsets[0] .. sample_offsets[R]) is copied);
+ *   sample_offsets : i64 [R + 1] (host), non-decreasing: recording r = pcm[sample_offsets[r] .. sample_offsets[r + 1]),
+ *                    0 .. 2^30 samples;  R : 0 .. 65535;
+ *   n_mels         : 80 / 128, as wm_logmel;
+ *   out            : f32, recording r's [n_mels][T_r] block after those of recordings 0 .. r - 1,
+ *                    T_r = (len_r + 480000) / 160 (integer division: torch.stft's center=True frames minus the last, as
+ *                    openai-whisper drops it); same `mem` as pcm.
+ * Frames [0, 2999) of a 30 s recording see the same samples as wm_logmel's chunk; when the recording's maximum lies
+ * there, they are bit-identical to wm_logmel(..., WM_F32). */
+WM_API int wm_logmel_long(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *sample_offsets, int R,
+                          int n_mels, float *out, wm_mem mem);
+
 /* --------------------------------------------------------- context / weight loading --- */
 
 /* Front-end-only context (no model): enough for wm_logmel. */
@@ -200,6 +218,29 @@ WM_API int wm_transcribe(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B
                   const int32_t *prompt, int n_prompt, int max_new, int32_t eot, const wm_decode_opts *opts,
                   int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
                   wm_mem mem);
+
+/* wm_transcribe with log-mel windows instead of PCM chunks, and one prompt per row: the decode step of openai-whisper's
+ * long-form transcribe(), whose windows start at any frame (`seek`).
+ *   mel        : f32, mem-space selectable -- typically wm_logmel_long's output, kept on the device;
+ *   mel_base   : i64 [B] (host) element offset in mel of row b's recording block [n_mels][mel_len[b]];
+ *   mel_len    : i32 [B] (host) frames T of that block;  seek : i32 [B] (host) first frame, >= 0;
+ *   n_frames   : i32 [B] (host) 1 .. 3000 frames, seek + n_frames <= mel_len.  Row b's encoder input is
+ *                mel[:, seek : seek + n_frames] zero-padded to 3000 frames (openai-whisper pad_or_trim); the gather is
+ *                fused into the encoder's first step.  With WM_MEM_HOST only the B windows are copied;
+ *   prompts    : i32 [B][n_prompt] (host), every row its own prompt, all of one length; opts->sot_index applies to all;
+ *   sample_ids : u32 [B] (host, nullable): the Philox counter word that wm_transcribe fills with the chunk index within
+ *                THIS call is sample_ids[b] instead, so a row's sampling noise depends on its id, not on the other rows
+ *                of the call; NULL: the index within the call, exactly as wm_transcribe;
+ *   everything else (max_new, eot, opts, outputs, suppress / timestamp rules, token budgets, lanes, grouping, early stop)
+ *   exactly as wm_transcribe.  Windows cut at seek 0 with 3000 frames from wm_logmel's output, with every prompt equal and
+ *   sample_ids NULL, give wm_transcribe's results bit for bit.  Invalid: n_mels of the model other than the mel's (not
+ *   checkable: the caller's duty), mel_len < 1, seek < 0, n_frames outside [1, 3000], seek + n_frames > mel_len,
+ *   mel_base < 0, a prompt token outside the vocabulary, and everything wm_transcribe rejects. */
+WM_API int wm_transcribe_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                             const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts, int n_prompt,
+                             const uint32_t *sample_ids, int max_new, int32_t eot, const wm_decode_opts *opts,
+                             int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
+                             wm_mem mem);
 
 /* ------------------------------------------------------------- word-level timestamps --- */
 /* openai-whisper's find_alignment (whisper/timing.py) on the GPU, for the text tokens a transcription produced (e.g. each

@@ -112,6 +112,8 @@ def load_library(path=None):
         "wm_detect_language": [vp, vp, ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ip],
         "wm_transcribe_greedy": [vp, vp, ip, ip, vp, ip, ip, ctypes.c_int32, vp, vp, ip],
         "wm_transcribe": [vp, vp, ip, ip, vp, ip, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
+        "wm_logmel_long": [vp, vp, ip, vp, ip, ip, vp, ip],
+        "wm_transcribe_mel": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
         "wm_set_token_budgets": [vp, vp, ip],
         "wm_set_alignment_heads": [vp, vp, vp, ip],
         "wm_align": [vp, vp, ip, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, vp, ip, ctypes.c_float, vp, vp, ip],
@@ -250,13 +252,24 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     Returns a dict of per-chunk arrays (tokens, lens, logprobs, sum_logprob, avg_logprob, no_speech_prob,
     compression_ratio, temperature, seed, needs_fallback) and `steps`: [(temperature, seed, chunk indices)] per call."""
     pcm = np.asarray(pcm)
-    B = pcm.shape[0]
+
+    def decode(todo, t, sd):
+        return ctx.transcribe(pcm[todo], prompt, max_new, eot=eot, temperature=t, seed=sd,
+                              no_speech_token=no_speech_token, sot_index=sot_index)
+    return fallback_decode(decode, pcm.shape[0], int(ctx.dims["n_vocab"]) if vocab_size is None else vocab_size, max_new,
+                           eot, temperatures, compression_ratio_threshold, logprob_threshold, no_speech_threshold, vocab,
+                           seed)
+
+
+def fallback_decode(decode, B, vocab_size, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
+                    compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6, vocab=None,
+                    seed=0):
+    """The decision rule of transcribe_with_fallback over any decode: decode(indices, temperature, seed) returns the
+    TranscribeResult of rows `indices` (an int array into 0 .. B - 1).  Same result dict."""
     if isinstance(compression_ratio_threshold, str):
         if compression_ratio_threshold != "auto":
             raise ValueError("compression_ratio_threshold: a number, None (not checked) or 'auto'")
         compression_ratio_threshold = 2.4 if vocab is not None else 1.35
-    if vocab_size is None:
-        vocab_size = int(ctx.dims["n_vocab"])
     out = dict(tokens=np.full((B, max_new), eot, dtype=np.int32), lens=np.zeros(B, dtype=np.int32),
                logprobs=np.zeros((B, max_new), dtype=np.float32), sum_logprob=np.zeros(B), avg_logprob=np.zeros(B),
                no_speech_prob=np.full(B, np.nan, dtype=np.float32), compression_ratio=np.zeros(B),
@@ -267,8 +280,7 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
         if todo.size == 0:
             break
         sd = fallback_seed(seed, k)
-        r = ctx.transcribe(pcm[todo], prompt, max_new, eot=eot, temperature=float(t), seed=sd,
-                           no_speech_token=no_speech_token, sot_index=sot_index)
+        r = decode(todo, float(t), sd)
         steps.append((float(t), sd, todo.copy()))
         need = np.zeros(todo.size, dtype=bool)
         for i, b in enumerate(todo):
@@ -298,6 +310,201 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
             out["needs_fallback"][b] = nf
         todo = todo[need]
     out["steps"] = steps
+    return out
+
+
+def _pack_recordings(recordings):
+    """Recordings (1-D sample arrays) back to back in one array of a supported dtype, plus i64 offsets [R + 1].  All
+    int16: int16; otherwise int16 recordings become float32 s / 32768 (exact) and the rest float32 or float64."""
+    recs = [np.asarray(r).reshape(-1) for r in recordings]
+    for r in recs:
+        if r.dtype not in _DTYPES:
+            raise ValueError("recording dtype must be int16/float32/float64, got %s" % r.dtype)
+    if recs and all(r.dtype == np.int16 for r in recs):
+        dt = np.dtype(np.int16)
+    else:
+        dt = np.dtype(np.float64) if any(r.dtype == np.float64 for r in recs) else np.dtype(np.float32)
+        recs = [(r.astype(dt) / dt.type(32768.0)) if r.dtype == np.int16 else r.astype(dt, copy=False) for r in recs]
+    offs = np.zeros(len(recs) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum([r.size for r in recs])
+    pcm = np.ascontiguousarray(np.concatenate(recs) if recs else np.zeros(0, dt), dtype=dt)
+    return pcm, offs
+
+
+# ---- long-form transcription: openai-whisper transcribe()'s seek loop ---------------------------------------------------
+HOP_SECONDS = 160 / 16000     # one mel frame
+INPUT_STRIDE = 2              # mel frames per encoder output frame (N_FRAMES // n_audio_ctx)
+TIME_PRECISION = 0.02         # seconds per timestamp token (INPUT_STRIDE * HOP_LENGTH / SAMPLE_RATE)
+
+
+def should_skip_window(no_speech_prob, avg_logprob, no_speech_threshold=0.6, logprob_threshold=-1.0):
+    """openai-whisper's silence skip: no_speech_prob > no_speech_threshold, unless avg_logprob > logprob_threshold."""
+    if no_speech_threshold is None or no_speech_prob is None:
+        return False
+    skip = no_speech_prob > no_speech_threshold
+    if logprob_threshold is not None and avg_logprob > logprob_threshold:
+        skip = False
+    return bool(skip)
+
+
+def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vocab=None):
+    """openai-whisper transcribe()'s handling of one decoded window (word_timestamps=False): slicing at consecutive
+    timestamps, single_timestamp_ending, the seek update and the clearing of instantaneous / text-less segments.
+      tokens : the window's generated tokens without the final eot (openai-whisper DecodingResult.tokens);
+      seek, segment_size : the window's first frame and frame count;
+      result : dict with temperature, avg_logprob, compression_ratio, no_speech_prob (copied into every segment).
+    Returns (segments, next_seek).  A segment is text-less when, with a Vocab, its decoded text is blank, and without one
+    when it has no token below eot."""
+    tokens = [int(t) for t in tokens]
+    time_offset = float(seek * HOP_SECONDS)
+    segment_duration = segment_size * HOP_SECONDS
+
+    def new_segment(start, end, toks):
+        seg = dict(seek=seek, start=start, end=end, tokens=list(toks), temperature=result["temperature"],
+                   avg_logprob=result["avg_logprob"], compression_ratio=result["compression_ratio"],
+                   no_speech_prob=result["no_speech_prob"])
+        if vocab is not None:
+            seg["text"] = vocab.decode([t for t in toks if t < eot])
+        return seg
+
+    is_ts = [t >= timestamp_begin for t in tokens]
+    single_timestamp_ending = is_ts[-2:] == [False, True]
+    consecutive = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
+    segments = []
+    if consecutive:
+        slices = list(consecutive)
+        if single_timestamp_ending:
+            slices.append(len(tokens))
+        last_slice = 0
+        for cur in slices:
+            sl = tokens[last_slice:cur]
+            segments.append(new_segment(time_offset + (sl[0] - timestamp_begin) * TIME_PRECISION,
+                                        time_offset + (sl[-1] - timestamp_begin) * TIME_PRECISION, sl))
+            last_slice = cur
+        if single_timestamp_ending:
+            next_seek = seek + segment_size
+        else:
+            next_seek = seek + (tokens[last_slice - 1] - timestamp_begin) * INPUT_STRIDE
+    else:
+        duration = segment_duration
+        ts = [t for t in tokens if t >= timestamp_begin]
+        if ts and ts[-1] != timestamp_begin:
+            duration = (ts[-1] - timestamp_begin) * TIME_PRECISION
+        segments.append(new_segment(time_offset, time_offset + duration, tokens))
+        next_seek = seek + segment_size
+    for seg in segments:
+        blank = (seg["text"].strip() == "") if vocab is not None else not any(t < eot for t in seg["tokens"])
+        if seg["start"] == seg["end"] or blank:
+            seg["tokens"] = []
+            if vocab is not None:
+                seg["text"] = ""
+    return segments, next_seek
+
+
+def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_speech_token, lang_first=None,
+                    lang_last=None, language=None, sot_prev=None, initial_prompt_tokens=None, recording_ids=None,
+                    temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
+                    no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None):
+    """openai-whisper transcribe() for recordings of any length, with condition_on_previous_text=False,
+    word_timestamps=False, no clip timestamps and no hallucination-silence threshold, batched across the recordings.
+
+    1. One wm_logmel_long call for all recordings, kept on the device; content_frames = T_r - 3000.
+    2. language None: per recording, openai-whisper's detect_language on mel[:, :3000] (wm_encode + the language-token
+       softmax, ids lang_first .. lang_last); otherwise a token id for all recordings or a list of one per recording.
+    3. Rounds: every unfinished recording decodes its window mel[:, seek : seek + segment_size], segment_size =
+       min(3000, content_frames - seek), prompt [sot_prev, *initial_prompt_tokens[-(n_text_ctx // 2 - 1):]] (when
+       given) + [sot, language, task], max_new = n_text_ctx // 2, in ONE wm_transcribe_mel call per fallback step
+       (fallback_decode: transcribe_with_fallback's rule and seeds).  Row sample id = (window ordinal << 16) |
+       recording id, so a recording's samples depend on itself only; recording ids default to 0 .. R - 1, < 65536.
+    4. Per window: should_skip_window, else window_segments.
+    Sets the context's timestamp rules (wm_set_timestamp_rules: timestamp_begin, eot, max initial timestamp 1.0 s);
+    suppress lists are the caller's (Context.set_suppress).  Returns per recording a dict: language (token id),
+    segments (openai-whisper's keys id seek start end tokens temperature avg_logprob compression_ratio no_speech_prob, plus
+    text with a Vocab), text (with a Vocab), seeks (the first frame of every decoded window) and windows (per window:
+    seek, segment_size, the fallback steps' temperatures, skipped)."""
+    R = len(recordings)
+    rec_ids = list(range(R)) if recording_ids is None else [int(i) for i in recording_ids]
+    if len(rec_ids) != R or any(i < 0 or i >= 65536 for i in rec_ids):
+        raise ValueError("recording_ids: one per recording, each 0 .. 65535")
+    n_ctx = int(ctx.dims["n_text_ctx"])
+    n_mels = int(ctx.dims["n_mels"])
+    max_new = n_ctx // 2
+    if vocab_size is None:
+        vocab_size = int(ctx.dims["n_vocab"])
+    ctx.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
+    out = [dict(language=None, segments=[], seeks=[], windows=[]) for _ in range(R)]
+    if R == 0:
+        return out
+    d_mel, mel_offs, T = ctx.logmel_long(recordings, n_mels=n_mels, device=True)
+    try:
+        content = [int(t) - N_FRAMES for t in T]
+        # 2. language
+        if language is None:
+            if lang_first is None or lang_last is None:
+                raise ValueError("language detection needs lang_first / lang_last")
+            win = np.empty((R, n_mels, N_FRAMES), dtype=np.float32)
+            for r in range(R):
+                for c in range(n_mels):
+                    src = ctypes.c_void_p(d_mel.value + 4 * (int(mel_offs[r]) + c * int(T[r])))
+                    _check(ctx.lib, ctx.lib.wm_dev_download(ctx.handle, _ptr(win[r, c]), src, 4 * N_FRAMES))
+            idx, _ = ctx.detect_language_probs(ctx.encode_mel(win), sot, lang_first, lang_last)
+            langs = [int(lang_first + i) for i in idx]
+        elif np.ndim(language) == 0:
+            langs = [int(language)] * R
+        else:
+            langs = [int(x) for x in language]
+            if len(langs) != R:
+                raise ValueError("language: one token id per recording")
+        head = []
+        if initial_prompt_tokens is not None:
+            if sot_prev is None:
+                raise ValueError("initial_prompt_tokens need sot_prev")
+            head = [int(sot_prev)] + [int(t) for t in initial_prompt_tokens][-(n_ctx // 2 - 1):]
+        sot_index = len(head)
+        seek = [0] * R
+        for r in range(R):
+            out[r]["language"] = langs[r]
+        # 3. rounds in lockstep
+        while True:
+            live = [r for r in range(R) if seek[r] < content[r]]
+            if not live:
+                break
+            size = [min(N_FRAMES, content[r] - seek[r]) for r in live]
+            ids = [((len(out[r]["windows"]) & 0xFFFF) << 16) | rec_ids[r] for r in live]
+            prompts = np.array([head + [int(sot), langs[r], int(task)] for r in live], dtype=np.int32)
+
+            def decode(todo, t, sd):
+                rows = [live[i] for i in todo]
+                return ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
+                                          [size[i] for i in todo], prompts[todo], max_new, eot=eot, temperature=t,
+                                          seed=sd, no_speech_token=no_speech_token, sot_index=sot_index,
+                                          sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE)
+            res = fallback_decode(decode, len(live), vocab_size, max_new, eot, temperatures, compression_ratio_threshold,
+                                  logprob_threshold, no_speech_threshold, vocab, seed)
+            for i, r in enumerate(live):
+                temps = [st[0] for st in res["steps"] if i in st[2]]
+                n_text = n_text_tokens(res["tokens"][i, :res["lens"][i]], eot)
+                result = dict(temperature=float(res["temperature"][i]), avg_logprob=float(res["avg_logprob"][i]),
+                              compression_ratio=float(res["compression_ratio"][i]),
+                              no_speech_prob=float(res["no_speech_prob"][i]))
+                skip = should_skip_window(result["no_speech_prob"], result["avg_logprob"], no_speech_threshold,
+                                          logprob_threshold)
+                out[r]["seeks"].append(seek[r])
+                out[r]["windows"].append(dict(seek=seek[r], segment_size=size[i], temperatures=temps, skipped=skip,
+                                              tokens=[int(t) for t in res["tokens"][i, :n_text]]))
+                if skip:
+                    seek[r] += size[i]
+                    continue
+                segs, seek[r] = window_segments(res["tokens"][i, :n_text], seek[r], size[i], timestamp_begin, eot,
+                                                result, vocab)
+                for sg in segs:
+                    sg["id"] = len(out[r]["segments"])
+                    out[r]["segments"].append(sg)
+    finally:
+        ctx.dev_free(d_mel)
+    if vocab is not None:
+        for o in out:
+            o["text"] = vocab.decode([t for sg in o["segments"] for t in sg["tokens"] if t < eot])
     return out
 
 
@@ -358,6 +565,34 @@ class Context:
         _check(self.lib, self.lib.wm_logmel(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], n, n_mels,
                                             _ptr(out), _DTYPES[np.dtype(out_dtype)], WM_MEM_HOST))
         return out
+
+    def logmel_long(self, recordings, n_mels=80, device=False):
+        """wm_logmel_long: openai-whisper's log_mel_spectrogram(audio, padding=480000) of each recording (1-D int16 /
+        float32 / float64 arrays of any length).  Returns a list of f32 [n_mels][T_r] arrays, T_r = (len_r + 480000) //
+        160; device=True keeps the result on the device and returns (pointer, element offsets i64 [R + 1], T i32 [R])
+        -- free the pointer with dev_free."""
+        pcm, offs = _pack_recordings(recordings)
+        R = len(offs) - 1
+        T = ((np.diff(offs) + N_SAMPLES) // 160).astype(np.int32)
+        mel_offs = np.concatenate([[0], np.cumsum(T.astype(np.int64) * n_mels)]).astype(np.int64)
+        if not device:
+            out = np.empty(max(int(mel_offs[-1]), 1), dtype=np.float32)
+            _check(self.lib, self.lib.wm_logmel_long(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], _ptr(offs), R, n_mels,
+                                                     _ptr(out), WM_MEM_HOST))
+            return [out[mel_offs[r]:mel_offs[r + 1]].reshape(n_mels, T[r]) for r in range(R)]
+        d_pcm = self.to_device(pcm) if pcm.nbytes else None
+        d_out = self.dev_malloc(max(int(mel_offs[-1]), 1) * 4)
+        try:
+            _check(self.lib, self.lib.wm_logmel_long(self.handle, d_pcm, _DTYPES[pcm.dtype], _ptr(offs), R, n_mels, d_out,
+                                                     WM_MEM_DEVICE))
+            self.sync()
+        except Exception:
+            self.dev_free(d_out)
+            raise
+        finally:
+            if d_pcm is not None:
+                self.dev_free(d_pcm)
+        return d_out, mel_offs, T
 
     # ---- device memory --------------------------------------------------------------
     def dev_malloc(self, nbytes):
@@ -562,6 +797,51 @@ class Context:
         """openai-whisper's temperature fallback (module function transcribe_with_fallback) on this context."""
         return transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures, compression_ratio_threshold,
                                         logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index)
+
+    def transcribe_mel_raw(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, opts=None,
+                           sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None):
+        """wm_transcribe_mel: mel is a host f32 array (mem WM_MEM_HOST) or a device pointer (WM_MEM_DEVICE); mel_base i64,
+        mel_len / seek / n_frames i32 [B]; prompts [B][n_prompt]; sample_ids u32 [B] or None.  Returns (tokens, lens,
+        logprobs or None, no_speech_prob or None)."""
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        base = np.ascontiguousarray(mel_base, dtype=np.int64)
+        B = base.size
+        mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (B,)))
+        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (B,)))
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
+        pr = np.ascontiguousarray(prompts, dtype=np.int32)
+        if pr.ndim == 1:
+            pr = np.ascontiguousarray(np.broadcast_to(pr, (B, pr.size)))
+        ids = None if sample_ids is None else np.ascontiguousarray(sample_ids, dtype=np.uint32)
+        if mem == WM_MEM_HOST:
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            mp = _ptr(mel)
+        else:
+            mp = mel
+        toks = np.empty((B, max_new), dtype=np.int32)
+        lens = np.empty(B, dtype=np.int32)
+        lp = np.empty((B, max_new), dtype=np.float32) if logprobs else None
+        ns = np.empty(B, dtype=np.float32) if no_speech else None
+        _check(self.lib, self.lib.wm_transcribe_mel(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr),
+                                                    pr.shape[1], _ptr(ids) if ids is not None else None, max_new, eot,
+                                                    ctypes.byref(opts) if opts is not None else None, _ptr(toks),
+                                                    _ptr(lens), _ptr(lp) if lp is not None else None,
+                                                    _ptr(ns) if ns is not None else None, mem))
+        return toks, lens, lp, ns
+
+    def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
+                       no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None):
+        """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult."""
+        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
+        toks, lens, lp, ns = self.transcribe_mel_raw(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot, opts,
+                                                     sample_ids, logprobs=True, no_speech=no_speech_token >= 0, mem=mem,
+                                                     budgets=budgets)
+        return TranscribeResult(toks, lens, lp, ns, eot)
+
+    def transcribe_long(self, recordings, **kw):
+        """openai-whisper's long-form transcribe() (module function transcribe_long) on this context."""
+        return transcribe_long(self, recordings, **kw)
 
     def set_alignment_heads(self, pairs):
         """wm_set_alignment_heads: the (layer, head) pairs Context.align reads; empty = every head of the last half of the

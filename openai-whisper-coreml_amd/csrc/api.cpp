@@ -348,6 +348,41 @@ extern "C" int wm_logmel(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int n
     return WM_OK;
 } WM_API_CATCH
 
+extern "C" int wm_logmel_long(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *sample_offsets, int R,
+                              int n_mels, float *out, wm_mem mem) try {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(R >= 0 && R <= 65535, WM_ERR_INVALID, "R must be 0 .. 65535, got %d", R);
+    WM_REQUIRE(n_mels == 80 || n_mels == 128, WM_ERR_INVALID, "n_mels must be 80 or 128, got %d", n_mels);
+    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID,
+               "pcm dtype must be WM_I16 / WM_F32 / WM_F64");
+    if (R == 0) return WM_OK;
+    WM_REQUIRE(sample_offsets && out, WM_ERR_INVALID, "null sample_offsets / out");
+    int64_t n_out = 0;
+    for (int r = 0; r < R; ++r) {
+        WM_REQUIRE(sample_offsets[r] >= 0 && sample_offsets[r + 1] >= sample_offsets[r], WM_ERR_INVALID,
+                   "sample_offsets must be >= 0 and non-decreasing (recording %d)", r);
+        n_out += (int64_t)n_mels * wm_long_frames(sample_offsets[r + 1] - sample_offsets[r]);
+    }
+    WM_REQUIRE(sample_offsets[R] == 0 || pcm, WM_ERR_INVALID, "null pcm");
+    if (mem == WM_MEM_DEVICE)
+        return wm_frontend_run_long(&ctx->fe, &ctx->prof, ctx->stream, pcm, pcm_dtype, sample_offsets, R, n_mels, out);
+    // host memory: only the samples the recordings span cross PCIe (offsets rebased to the first one)
+    std::vector<int64_t> offs(sample_offsets, sample_offsets + R + 1);
+    for (auto &o : offs) o -= sample_offsets[0];
+    const size_t in_b = (size_t)offs[R] * dtype_size(pcm_dtype);
+    const size_t out_b = (size_t)n_out * sizeof(float);
+    const size_t in_al = (in_b + 255) & ~(size_t)255;
+    WM_TRY(ensure_scratch(ctx, in_al + out_b));
+    char *d_in = (char *)ctx->fe.scratch, *d_out = d_in + in_al;
+    if (in_b)
+        WM_HIP(hipMemcpyAsync(d_in, (const char *)pcm + (size_t)sample_offsets[0] * dtype_size(pcm_dtype), in_b,
+                              hipMemcpyHostToDevice, ctx->stream));
+    WM_TRY(wm_frontend_run_long(&ctx->fe, &ctx->prof, ctx->stream, d_in, pcm_dtype, offs.data(), R, n_mels, (float *)d_out));
+    WM_HIP(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    return WM_OK;
+} WM_API_CATCH
+
 // The reference's symbol (bridge.h:11 / lib.rs:110-122).  The Rust crate's entry is re-entrant (immutable lazily
 // initialised state, lib.rs:11-14), so concurrent callers must not queue behind one another here either: a small pool of
 // lazily created front-end contexts (own stream, tables and staging each), handed out under a mutex and used outside it.

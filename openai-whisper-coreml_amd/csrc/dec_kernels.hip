@@ -268,7 +268,9 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             // of the quad runs the call of row kq * 4 + j, and DPP broadcasts hand every lane its word (n & 3) of each row's call
             const int j = nrow & 3;
             wm_philox4 c;
-            c.v[0] = (unsigned)n >> 2; c.v[1] = (unsigned)gi; c.v[2] = (unsigned)(xp.chunk0 + b0 + kq * 4 + j); c.v[3] = 0u;
+            const int row = b0 + kq * 4 + j;   // (rows past the group's: their draws are never used)
+            c.v[0] = (unsigned)n >> 2; c.v[1] = (unsigned)gi; c.v[2] = xp.ids_on ? p.x.ids[row] : (unsigned)(xp.chunk0 + row);
+            c.v[3] = 0u;
             const wm_philox4 w = wm_philox4x32_10(c, xp.key0, xp.key1);
             quad_words<0>(w, j, draw[0]);
             quad_words<1>(w, j, draw[1]);

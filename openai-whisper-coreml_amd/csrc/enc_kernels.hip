@@ -78,13 +78,24 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
 // mel f32 [B][C][3000] (the reference's encoder input layout, Whisper.swift:25) ->
 // bf16 [B][3002][C] time-major with zero rows 0 and 3001 (zeroed once at allocation), so
 // conv1's 3-tap window of frame t is the contiguous run mel_t[b][t .. t+2][:].
+// WIN (wm_transcribe_mel): row b reads the window win[b] of a [C][T] block instead -- frames seek .. seek + n - 1, zeros
+// from n to 3000 (openai-whisper pad_or_trim in mel space); the gather costs no pass of its own.
+template <bool WIN>
 __global__ __launch_bounds__(256) void mel_time_major_kernel(const float *__restrict__ mel, int C,
-                                                             bf16_t *__restrict__ out) {
+                                                             bf16_t *__restrict__ out, const WmMelWin *__restrict__ win) {
     __shared__ float tile[128][65];
     const int b = blockIdx.y, t0 = blockIdx.x * 64;
+    size_t base = (size_t)b * C * WM_N_FRAMES;
+    int T = WM_N_FRAMES, n = WM_N_FRAMES;
+    if (WIN) {
+        const WmMelWin w = win[b];
+        base = (size_t)w.base + (size_t)w.seek;
+        T = w.T;
+        n = w.n;
+    }
     for (int i = threadIdx.x; i < C * 64; i += 256) {
         const int c = i >> 6, t = i & 63;
-        tile[c][t] = (t0 + t < WM_N_FRAMES) ? mel[((size_t)b * C + c) * WM_N_FRAMES + t0 + t] : 0.f;
+        tile[c][t] = (t0 + t < n) ? mel[base + (size_t)c * T + t0 + t] : 0.f;
     }
     __syncthreads();
     for (int i = threadIdx.x; i < C * 64; i += 256) {
@@ -385,11 +396,14 @@ int wm_layernorm(wm_ctx *ctx, const float *x, const float *g, const float *b, in
     return WM_OK;
 }
 
-int wm_mel_to_time_major(wm_ctx *ctx, const float *mel, int B, int n_mels, bf16_t *mel_t) {
+int wm_mel_to_time_major(wm_ctx *ctx, const float *mel, int B, int n_mels, bf16_t *mel_t, const WmMelWin *d_win) {
     WM_REQUIRE(n_mels <= 128, WM_ERR_INVALID, "n_mels > 128");
     WmProfScope ps(&ctx->prof, "mel_time_major", ctx->stream);
     dim3 grid((WM_N_FRAMES + 63) / 64, B);
-    mel_time_major_kernel<<<grid, 256, 0, ctx->stream>>>(mel, n_mels, mel_t);
+    if (d_win)
+        mel_time_major_kernel<true><<<grid, 256, 0, ctx->stream>>>(mel, n_mels, mel_t, d_win);
+    else
+        mel_time_major_kernel<false><<<grid, 256, 0, ctx->stream>>>(mel, n_mels, mel_t, nullptr);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

@@ -254,10 +254,16 @@ constexpr int BAND8 = 128 * (BW8 + 2);                  // band start / length /
 constexpr int LDS8_WORDS = MAIN8 + 2 * SLICE8 + 404 + W8 * 16 + BAND8;
 constexpr int LDS8_BYTES = LDS8_WORDS * 4;              // 76.5 KiB: two workgroups per CU
 
+// The staging rule is the template argument; the DFT, power, mel and log arithmetic below it is one code for both:
+//   LONG = false: chunk c = pcm[c * 480000, +480000), reflect-padded at both ends, 3000 frames, out [c][n_mels][3000];
+//   LONG = true : openai-whisper's log_mel_spectrogram(audio, padding=480000) -- recording r = its len_r samples followed by
+//                 480000 zeros, reflect-padded by 200 at both ends (torch.stft center=True), T_r frames; workgroup ->
+//                 (recording, first frame) from lt.blk, out = recording r's [n_mels][T_r] block at lt.rec[r].out.
+template <bool LONG>
 __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     const void *__restrict__ pcm, int pcm_dtype, int n_mels, const float *__restrict__ tw, const float *__restrict__ win,
     const int *__restrict__ band_start, const int *__restrict__ band_len, const float *__restrict__ band_w,
-    float *__restrict__ out, unsigned long long *__restrict__ gmax, int blocks_per_chunk) {
+    float *__restrict__ out, unsigned long long *__restrict__ gmax, int blocks_per_chunk, WmLongTab lt) {
     extern __shared__ __attribute__((aligned(16))) float smem8[];
     float *xs = smem8;
     float(*pw)[16][PW8_STRIDE] = (float(*)[16][PW8_STRIDE])smem8;
@@ -266,8 +272,21 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     int(*bad)[16] = (int(*)[16])(wl + 404);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < W8 * 16) bad[tid >> 4][tid & 15] = 0;
-    const int chunk = blockIdx.x / blocks_per_chunk;
-    const int f0 = (blockIdx.x % blocks_per_chunk) * FPB8;
+    // this workgroup's signal: samples pcm[base + n] for 0 <= n < len, zeros for len <= n < nsig, reflected outside
+    // [0, nsig); frames f0 .. f0 + 63 of nT, written to out[out0 + m * nT + frame]; its maximum goes to gmax[chunk]
+    int chunk, f0, len, nsig, nT;
+    size_t base, out0;
+    if (LONG) {
+        const int2 bk = lt.blk[blockIdx.x];
+        const WmLongRec r = lt.rec[bk.x];
+        chunk = bk.x; f0 = bk.y;
+        base = (size_t)r.base; out0 = (size_t)r.out; len = r.len; nsig = r.len + WM_N_SAMPLES; nT = r.T;
+    } else {
+        chunk = blockIdx.x / blocks_per_chunk;
+        f0 = (blockIdx.x % blocks_per_chunk) * FPB8;
+        base = (size_t)chunk * WM_N_SAMPLES; out0 = (size_t)chunk * n_mels * WM_N_FRAMES;
+        len = nsig = WM_N_SAMPLES; nT = WM_N_FRAMES;
+    }
     // slice 0 requested first: 448 x 16 bytes (element e: table t = e / 112, float4 e % 112 of rows 4 kk .. + 3), thread tid
     // fetches elements tid and tid + 256
     const bool loader2 = tid + 256 < 448;
@@ -281,13 +300,14 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     for (int i = tid; i < n_mels; i += W8 * 64) { bnd_i[i] = band_start[i]; bnd_i[128 + i] = band_len[i]; }
     for (int i = tid; i < n_mels * BW8; i += W8 * 64) bnd[256 + i] = band_w[(i / BW8) * WM_MEL_MAXW + (i % BW8)];
     // ---- stage the PCM span (reflect pad by index; lib.rs:34-40): all loads of a thread first, then its stores ----------
-    const size_t chunk_base = (size_t)chunk * WM_N_SAMPLES;
+    const size_t chunk_base = base;
     constexpr int PER = 8, NPASS = (SPAN8 / PER + W8 * 64 - 1) / (W8 * 64);   // 1310 groups of 8 samples, 6 passes of 256 threads
     static_assert(SPAN8 % PER == 0, "the span is a whole number of 8-sample groups");
     const int first = f0 * WM_HOP - 200;        // unpadded-chunk index of span sample 0
-    // (workgroup-uniform) no reflect, no masked frames -- and a caller's buffer that is 16-byte aligned (chunk offsets and
-    // `first` are multiples of 16 bytes for int16 and f32; an odd base pointer takes the gather path)
-    const bool interior = first >= 0 && first + SPAN8 <= WM_N_SAMPLES && ((size_t)pcm & 15) == 0;
+    // (workgroup-uniform) no reflect, no masked frames, no zero tail -- and a span that starts 16-byte aligned (chunk offsets
+    // and `first` are multiples of 16 bytes for int16 and f32; an odd base pointer or recording offset takes the gather path)
+    const size_t esz = pcm_dtype == WM_I16 ? 2 : (pcm_dtype == WM_F32 ? 4 : 8);
+    const bool interior = first >= 0 && first + SPAN8 <= len && (((size_t)pcm + (chunk_base + first) * esz) & 15) == 0;
     float v[NPASS][PER];
     if (interior && pcm_dtype == WM_I16) {      // 16 bytes = 8 samples per load; first * 2 and chunk_base * 2 are multiples of 16
         const short *src = (const short *)pcm + chunk_base + first;
@@ -321,10 +341,10 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
             for (int u = 0; u < PER; ++u) {
                 int n = first + g * PER + u;
                 if (n < 0) n = -n;                                 // a[i] = a[400 - i]
-                if (n >= WM_N_SAMPLES) n = 2 * (WM_N_SAMPLES - 1) - n;  // a[j] = a[200 + (N-2) - i]
-                if (n < 0) n = 0;                                  // only for masked frames >= 3000
-                if (n >= WM_N_SAMPLES) n = WM_N_SAMPLES - 1;       // (groups past the span: never stored)
-                v[ps][u] = load_sample<float>(pcm, pcm_dtype, chunk_base + n);
+                if (n >= nsig) n = 2 * (nsig - 1) - n;             // a[j] = a[200 + (N-2) - i]
+                if (n < 0) n = 0;                                  // only for masked frames >= nT
+                if (n >= nsig) n = nsig - 1;                       // (groups past the span: never stored)
+                v[ps][u] = n < len ? load_sample<float>(pcm, pcm_dtype, chunk_base + n) : 0.f;   // (LONG: the zero tail)
             }
         }
     }
@@ -404,7 +424,7 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     }
     __syncthreads();
     const int frame = f0 + wave * 16 + (lane & 15);
-    const bool live = frame < WM_N_FRAMES;
+    const bool live = frame < nT;
     float vmax = -1e30f;
     for (int m = lane >> 4; m < n_mels; m += 4) {
         const int ks = bnd_i[m], kl = bnd_i[128 + m];
@@ -420,7 +440,7 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
         s = (s > 1e-10f) ? s : 1e-10f;
         const float v = log10_t(s);
         if (live) {
-            out[((size_t)chunk * n_mels + m) * WM_N_FRAMES + frame] = v;
+            out[out0 + (size_t)m * nT + frame] = v;
             vmax = (v > vmax) ? v : vmax;
         }
     }
@@ -432,19 +452,35 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     if (lane == 0 && vmax > -1e29f) atomicMax(gmax + chunk, enc_max(vmax));
 }
 
+// the dynamic-range clamp and affine of one value (both stage-2 layouts)
+template <typename T>
+__device__ __forceinline__ T clamp_affine(T x, unsigned long long gm) {
+    T g;
+    dec_max(gm, &g);
+    const T fl = g - (T)8.0;
+    x = (x > fl) ? x : fl;         // x.max(gmax - 8.0)   lib.rs:96
+    return (x + (T)4.0) / (T)4.0;  // (.. + 4.0) / 4.0
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void logmel_stage2(T *__restrict__ io,
                                                      const unsigned long long *__restrict__ gmax,
                                                      int per_chunk, size_t total) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * blockDim.x) {
-        T g;
-        dec_max(gmax[i / per_chunk], &g);
-        const T fl = g - (T)8.0;
-        T x = io[i];
-        x = (x > fl) ? x : fl;         // x.max(gmax - 8.0)   lib.rs:96
-        io[i] = (x + (T)4.0) / (T)4.0; // (.. + 4.0) / 4.0
-    }
+         i += (size_t)gridDim.x * blockDim.x)
+        io[i] = clamp_affine(io[i], gmax[i / per_chunk]);
+}
+
+// the same over the whole-recording layout: blockIdx.y = recording, its [n_mels][T_r] block at rec[r].out
+__global__ __launch_bounds__(256) void logmel_stage2_long(float *__restrict__ io, const unsigned long long *__restrict__ gmax,
+                                                          const WmLongRec *__restrict__ rec, int n_mels) {
+    const int r = blockIdx.y;
+    const WmLongRec rr = rec[r];
+    const unsigned long long gm = gmax[r];
+    float *p = io + rr.out;
+    const size_t total = (size_t)n_mels * rr.T;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        p[i] = clamp_affine(p[i], gm);
 }
 
 template <typename T>
@@ -567,7 +603,7 @@ int wm_frontend_init(WmFrontend *fe, hipStream_t stream) {
 void wm_frontend_destroy(WmFrontend *fe) {
     void *ptrs[] = {fe->cos32, fe->sin32, fe->win32, fe->cos64, fe->sin64, fe->win64,
                     fe->band_start[0], fe->band_start[1], fe->band_len[0], fe->band_len[1],
-                    fe->band_w[0], fe->band_w[1], fe->gmax, fe->scratch};
+                    fe->band_w[0], fe->band_w[1], fe->gmax, fe->scratch, fe->long_tab};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     *fe = WmFrontend();
@@ -606,14 +642,14 @@ int wm_frontend_run(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const 
             int dev = 0;
             WM_HIP(hipGetDevice(&dev));
             if (!attr_set[dev & 63].load(std::memory_order_acquire)) {
-                WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
+                WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
                 attr_set[dev & 63].store(1, std::memory_order_release);
             }
             const int bpc = (WM_N_FRAMES + FPB8 - 1) / FPB8;
             WmProfScope ps(prof, "logmel_stage1_f32", stream);
-            logmel_stage1_f32_lds<<<n_chunks * bpc, W8 * 64, LDS8_BYTES, stream>>>(
+            logmel_stage1_f32_lds<false><<<n_chunks * bpc, W8 * 64, LDS8_BYTES, stream>>>(
                 d_pcm, (int)pcm_dtype, n_mels, fe->cos32, fe->win32, fe->band_start[fi], fe->band_len[fi],
-                fe->band_w[fi], (float *)d_out, (unsigned long long *)fe->gmax, bpc);
+                fe->band_w[fi], (float *)d_out, (unsigned long long *)fe->gmax, bpc, WmLongTab{});
         }
         {
             WmProfScope ps(prof, "logmel_stage2_f32", stream);
@@ -638,5 +674,80 @@ int wm_frontend_run(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const 
         }
     }
     WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+int wm_frontend_run_long(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
+                         const int64_t *offs, int R, int n_mels, float *d_out) {
+    WM_REQUIRE(fe->ready, WM_ERR_STATE, "front end not initialised");
+    WM_REQUIRE(n_mels == 80 || n_mels == 128, WM_ERR_INVALID, "n_mels must be 80 or 128, got %d", n_mels);
+    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID,
+               "pcm dtype must be i16/f32/f64");
+    WM_REQUIRE(R >= 0 && R <= 65535 && offs, WM_ERR_INVALID, "bad recording count (0 .. 65535) / null offsets");
+    if (R == 0) return WM_OK;
+    WM_REQUIRE(d_out, WM_ERR_INVALID, "null output");
+    const int fi = (n_mels == 80) ? 0 : 1;
+    WM_REQUIRE(fe->band_maxw[fi] <= BW8, WM_ERR_INVALID, "filterbank bands wider than %d bins", BW8);
+    // the tables: R recordings, then one (recording, first frame) pair per workgroup of 64 frames
+    std::vector<WmLongRec> rec(R);
+    std::vector<int2> blk;
+    long long out = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t len = offs[r + 1] - offs[r];
+        // (sample indices are int in the kernel: the padded signal must stay below 2^31)
+        WM_REQUIRE(offs[r] >= 0 && len >= 0 && len <= (int64_t)1 << 30, WM_ERR_INVALID,
+                   "recording %d: offsets [%lld, %lld) invalid (length 0 .. 2^30 samples)", r, (long long)offs[r],
+                   (long long)offs[r + 1]);
+        rec[r].base = offs[r];
+        rec[r].out = out;
+        rec[r].len = (int)len;
+        rec[r].T = (int)wm_long_frames(len);
+        out += (long long)n_mels * rec[r].T;
+        for (int f = 0; f < rec[r].T; f += FPB8) blk.push_back(make_int2(r, f));
+    }
+    const size_t rec_b = (sizeof(WmLongRec) * R + 255) & ~(size_t)255, bytes = rec_b + sizeof(int2) * blk.size();
+    if (fe->long_tab_bytes < bytes) {
+        WM_HIP(hipStreamSynchronize(stream));
+        if (fe->long_tab) WM_HIP(hipFree(fe->long_tab));
+        fe->long_tab = nullptr;
+        fe->long_tab_bytes = 0;
+        WM_HIP(hipMalloc(&fe->long_tab, bytes));
+        fe->long_tab_bytes = bytes;
+    }
+    if (fe->gmax_cap < R) {
+        WM_HIP(hipStreamSynchronize(stream));
+        if (fe->gmax) WM_HIP(hipFree(fe->gmax));
+        fe->gmax = nullptr;
+        WM_HIP(hipMalloc(&fe->gmax, sizeof(unsigned long long) * R));
+        fe->gmax_cap = R;
+    }
+    WmLongTab lt;
+    lt.rec = (const WmLongRec *)fe->long_tab;
+    lt.blk = (const int2 *)((char *)fe->long_tab + rec_b);
+    WM_HIP(hipMemcpyAsync(fe->long_tab, rec.data(), sizeof(WmLongRec) * R, hipMemcpyHostToDevice, stream));
+    WM_HIP(hipMemcpyAsync((void *)lt.blk, blk.data(), sizeof(int2) * blk.size(), hipMemcpyHostToDevice, stream));
+    WM_HIP(hipMemsetAsync(fe->gmax, 0, sizeof(unsigned long long) * R, stream));
+    static std::atomic<int> attr_set[64];
+    int dev = 0;
+    WM_HIP(hipGetDevice(&dev));
+    if (!attr_set[dev & 63].load(std::memory_order_acquire)) {
+        WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
+        attr_set[dev & 63].store(1, std::memory_order_release);
+    }
+    {
+        WmProfScope ps(prof, "logmel_long_stage1", stream);
+        logmel_stage1_f32_lds<true><<<(int)blk.size(), W8 * 64, LDS8_BYTES, stream>>>(
+            d_pcm, (int)pcm_dtype, n_mels, fe->cos32, fe->win32, fe->band_start[fi], fe->band_len[fi], fe->band_w[fi],
+            d_out, (unsigned long long *)fe->gmax, 0, lt);
+    }
+    {
+        WmProfScope ps(prof, "logmel_long_stage2", stream);
+        const int per = (int)(blk.size() / R) + 1;   // ~ the recordings' mean size in workgroups of 64 frames
+        logmel_stage2_long<<<dim3(per < 256 ? per : 256, R), 256, 0, stream>>>(d_out, (const unsigned long long *)fe->gmax,
+                                                                               lt.rec, n_mels);
+    }
+    WM_HIP(hipGetLastError());
+    // the tables are pageable host memory: the copies must have read them before they go out of scope
+    WM_HIP(hipStreamSynchronize(stream));
     return WM_OK;
 }

@@ -76,6 +76,8 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc_t(m, &m->dx_logprob, (size_t)D.n_text_ctx * WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dx_nospeech, WM_DEC_MAXB, s));
     WM_TRY(dalloc(m, (void **)&m->dx_par, sizeof(WmXPar), s));
+    WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)WM_DEC_MAXB + 16, s));   // (+16: the epilogue's padded 16-row blocks)
+    WM_TRY(dalloc_t(m, &m->dmel_win, (size_t)WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dmask, (size_t)2 * (m->vpad / 32), s));
     WM_HIP(hipMemsetAsync(m->dmask, 0, (size_t)2 * (m->vpad / 32) * 4, s));
     return WM_OK;
@@ -96,7 +98,7 @@ WmXDev wm_model_x_dev(const WmModel *m) {
     memset(&t, 0, sizeof(t));
     if (!m->x_on) return t;
     t.par = m->dx_par; t.txt = m->dx_txt; t.win = m->dx_win; t.all = m->dx_all; t.ns_v = m->dx_nsv;
-    t.logprob = m->dx_logprob; t.nospeech = m->dx_nospeech;
+    t.logprob = m->dx_logprob; t.nospeech = m->dx_nospeech; t.ids = m->dx_ids;
     return t;
 }
 
@@ -496,6 +498,10 @@ static GemmArgs plain_gemm(const bf16_t *A, int lda, const bf16_t *W, const floa
 }
 
 int wm_model_encode_dev(wm_ctx *ctx, const float *d_mel, int B, float *d_xa_out) {
+    return wm_model_encode_win(ctx, d_mel, nullptr, B, d_xa_out);
+}
+
+int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out) {
     WmModel *m = ctx->model;
     WM_REQUIRE(m && m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
     WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B must be >= 1");
@@ -503,8 +509,8 @@ int wm_model_encode_dev(wm_ctx *ctx, const float *d_mel, int B, float *d_xa_out)
     const wm_dims &D = m->dims;
     const int d = D.n_audio_state, H = D.n_audio_head, S = 1500, C = D.n_mels;
     const int M = B * S;
-    // mel [B][C][3000] f32 -> time-major bf16 with zero edge rows (conv padding = 1)
-    WM_TRY(wm_mel_to_time_major(ctx, d_mel, B, C, m->mel_t));
+    // mel [B][C][3000] f32 (or the windows d_win) -> time-major bf16 with zero edge rows (conv padding = 1)
+    WM_TRY(wm_mel_to_time_major(ctx, d_mel, B, C, m->mel_t, d_win));
     {   // conv1 (k3, p1) + GELU as an implicit GEMM: window of frame t = mel_t[b][t..t+2][:]
         GemmArgs g;
         memset(&g, 0, sizeof(g));

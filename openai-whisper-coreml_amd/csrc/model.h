@@ -89,9 +89,17 @@ struct WmXPar {
     int ns_tok;           // <|nospeech|> id (with sot_pos >= 0)
     int chunk0;           // index within the call of the group's row 0 (Philox counter: call index, not group row)
     int n_prompt;         // generated index gi = pos + 1 - n_prompt
+    int ids_on;           // 1: row b's counter word is WmXDev::ids[b] (caller-given sample ids), not chunk0 + b
+};
+
+// wm_transcribe_mel: row b's encoder input = frames seek .. seek + n - 1 of the [n_mels][T] block at mel + base, zeros after
+struct WmMelWin {
+    long long base;
+    int T, seek, n, pad;
 };
 struct WmXDev {
     const WmXPar *par;    // null: X mode off
+    const unsigned *ids;  // [>= WM_DEC_MAXB] per-row Philox counter words, read when par->ids_on (wm_transcribe_mel sample_ids)
     float *txt;           // [B][n_tiles][2] (max, sum exp) over the tile's allowed TEXT ids (raw logits)
     float *win;           // [B][n_tiles][2] raw logit of the tile's winner: text, timestamp
     float *all;           // [B][n_tiles][2] (max, sum exp) over every id -- at pos == sot_pos only
@@ -258,6 +266,8 @@ struct WmModel {
     float *dx_logprob = nullptr;   // [n_text_ctx][WM_DEC_MAXB]
     float *dx_nospeech = nullptr;  // [WM_DEC_MAXB]
     WmXPar *dx_par = nullptr;
+    unsigned *dx_ids = nullptr;    // [WM_DEC_MAXB + 16] per-row sample ids of the group (WmXPar::ids_on)
+    WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..), the
     // workspace of a call (grown on demand) and the debug library's one-shot cost-matrix capture (host, null in the product)
     std::vector<int32_t> align_l, align_h;
@@ -281,6 +291,8 @@ int wm_model_init_synthetic(wm_ctx *ctx, uint64_t seed, float matrix_gain);
 int wm_model_finalize(wm_ctx *ctx);
 // device-pointer cores
 int wm_model_encode_dev(wm_ctx *ctx, const float *d_mel, int B, float *d_xa_out /*nullable*/);
+// the same with row b's input the mel window d_win[b] (device, nullable: wm_model_encode_dev)
+int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out /*nullable*/);
 int wm_model_cross_kv(wm_ctx *ctx, int B);                 // from m->xn (bf16 encoder output)
 int wm_model_set_xa(wm_ctx *ctx, const float *d_xa, int B);  // f32 xa -> m->xn (bf16)
 int wm_model_decode_begin(wm_ctx *ctx, int B);
@@ -345,7 +357,8 @@ int wm_gemm(wm_ctx *ctx, const GemmArgs &g);
 // enc_kernels.hip
 int wm_layernorm(wm_ctx *ctx, const float *x, const float *g, const float *b, int rows, int d,
                  bf16_t *out_bf16 /*nullable*/, float *out_f32 /*nullable*/);
-int wm_mel_to_time_major(wm_ctx *ctx, const float *mel, int B, int n_mels, bf16_t *mel_t);
+// d_win (nullable, device [B]): row b = window d_win[b] of a [n_mels][T] block (wm_transcribe_mel); null: mel [B][n_mels][3000]
+int wm_mel_to_time_major(wm_ctx *ctx, const float *mel, int B, int n_mels, bf16_t *mel_t, const WmMelWin *d_win = nullptr);
 int wm_f32_to_bf16(wm_ctx *ctx, const float *in, bf16_t *out, size_t n);
 int wm_enc_attention(wm_ctx *ctx, const bf16_t *qk, const bf16_t *vt, bf16_t *att, int B, int H,
                      int S, int S_pad, int d);

@@ -398,6 +398,8 @@ struct LaneJob {
     std::vector<int32_t> pr, gen, bud;
     WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
+    std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
+    std::vector<unsigned> ids;     // its sample ids (wm_transcribe_mel)
     float stage_sum[3] = {0.f, 0.f, 0.f};
     ~LaneJob() {
         if (c) (void)hipStreamSynchronize(c->stream);  // error paths: nothing may outlive pr / gen / bud
@@ -406,6 +408,18 @@ struct LaneJob {
         for (auto &e : burst_ev)
             if (e) (void)hipEventDestroy(e);
     }
+};
+
+// where a call's rows come from: PCM chunks (wm_transcribe) or mel windows (wm_transcribe_mel), and their prompts
+struct TxSrc {
+    const void *pcm = nullptr;
+    wm_dtype pcm_dtype = WM_F32;
+    const float *mel = nullptr;        // non-null: mel windows
+    const int64_t *mel_base = nullptr;
+    const int32_t *mel_len = nullptr, *seek = nullptr, *n_frames = nullptr;
+    const int32_t *prompt = nullptr;   // row b's prompt: prompt + b * prompt_stride (0: one prompt for all)
+    int prompt_stride = 0;
+    const uint32_t *sample_ids = nullptr;
 };
 
 struct StopCfg {
@@ -424,15 +438,15 @@ struct XCfg {
 };
 
 // front end -> encoder -> cross K/V -> prompt upload -> first embedding, all enqueued on the lane's stream
-int lane_prefill(LaneJob &j, const void *pcm, wm_dtype pcm_dtype, const int32_t *prompt, int n_prompt, wm_mem mem,
-                 const StopCfg &stop, const XCfg &xc) {
+int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const StopCfg &stop, const XCfg &xc) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
     const wm_dims &D = m->dims;
     const int Bg = j.Bg;
-    const size_t bytes = (size_t)Bg * WM_N_SAMPLES * pcm_elem(pcm_dtype);
-    const void *d_pcm = (const char *)pcm + (size_t)j.b0 * WM_N_SAMPLES * pcm_elem(pcm_dtype);
-    if (mem == WM_MEM_HOST) {
+    const wm_dtype pcm_dtype = src.pcm_dtype;
+    const size_t bytes = src.mel ? 0 : (size_t)Bg * WM_N_SAMPLES * pcm_elem(pcm_dtype);
+    const void *d_pcm = src.mel ? nullptr : (const char *)src.pcm + (size_t)j.b0 * WM_N_SAMPLES * pcm_elem(pcm_dtype);
+    if (mem == WM_MEM_HOST && !src.mel) {
         if (m->pcm_stage_bytes < bytes) {
             WM_HIP(hipStreamSynchronize(c->stream));
             if (m->pcm_stage) WM_HIP(hipFree(m->pcm_stage));
@@ -449,7 +463,7 @@ int lane_prefill(LaneJob &j, const void *pcm, wm_dtype pcm_dtype, const int32_t 
     WM_TRY(wm_model_decode_begin(c, Bg));
     j.pr.resize((size_t)n_prompt * Bg);
     for (int t = 0; t < n_prompt; ++t)
-        for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = prompt[t];
+        for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = src.prompt[(size_t)(j.b0 + b) * src.prompt_stride + t];
     WM_HIP(hipMemcpyAsync(m->dseq, j.pr.data(), j.pr.size() * 4, hipMemcpyHostToDevice, c->stream));
     WM_TRY(wm_model_set_pos(c, 0));
     // early-stop state of this group: done flags, live list, per-row budgets (kernel arguments of the decode graphs)
@@ -470,15 +484,43 @@ int lane_prefill(LaneJob &j, const void *pcm, wm_dtype pcm_dtype, const int32_t 
         j.xpar = xc.par;
         j.xpar.chunk0 = j.b0;
         j.xpar.n_prompt = n_prompt;
+        j.xpar.ids_on = src.sample_ids ? 1 : 0;
+        if (src.sample_ids) {   // caller-given Philox counter words (wm_transcribe_mel): a row's noise follows its id
+            j.ids.assign(src.sample_ids + j.b0, src.sample_ids + j.b0 + Bg);
+            WM_HIP(hipMemcpyAsync(m->dx_ids, j.ids.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
+        }
         WM_HIP(hipMemcpyAsync(m->dx_par, &j.xpar, sizeof(WmXPar), hipMemcpyHostToDevice, c->stream));
     }
     WM_TRY(wm_model_reserve(c, Bg));
     WM_HIP(hipEventRecord(j.ev[0], c->stream));
-    // 1. log-mel front end (f32 fast path), output stays in HBM
-    WM_TRY(wm_frontend_run(&c->fe, &c->prof, c->stream, d_pcm, pcm_dtype, Bg, D.n_mels, m->mel_f32, WM_F32));
+    // 1. log-mel front end (f32 fast path), output stays in HBM -- or the caller's mel windows, gathered by the encoder's
+    //    first step (with host memory only the windows are copied, into the front end's buffer)
+    const float *enc_mel = m->mel_f32;
+    const WmMelWin *enc_win = nullptr;
+    if (src.mel) {
+        const int C = D.n_mels;
+        j.win.resize(Bg);
+        for (int b = 0; b < Bg; ++b) {
+            const int r = j.b0 + b;
+            WmMelWin &w = j.win[b];
+            w.T = src.mel_len[r]; w.seek = src.seek[r]; w.n = src.n_frames[r]; w.pad = 0;
+            w.base = src.mel_base[r];
+            if (mem == WM_MEM_HOST) {
+                WM_HIP(hipMemcpy2DAsync(m->mel_f32 + (size_t)b * C * WM_N_FRAMES, WM_N_FRAMES * sizeof(float),
+                                        src.mel + w.base + w.seek, (size_t)w.T * sizeof(float), (size_t)w.n * sizeof(float),
+                                        C, hipMemcpyHostToDevice, c->stream));
+                w.base = (long long)b * C * WM_N_FRAMES; w.T = WM_N_FRAMES; w.seek = 0;
+            }
+        }
+        WM_HIP(hipMemcpyAsync(m->dmel_win, j.win.data(), (size_t)Bg * sizeof(WmMelWin), hipMemcpyHostToDevice, c->stream));
+        if (mem != WM_MEM_HOST) enc_mel = src.mel;
+        enc_win = m->dmel_win;
+    } else {
+        WM_TRY(wm_frontend_run(&c->fe, &c->prof, c->stream, d_pcm, pcm_dtype, Bg, D.n_mels, m->mel_f32, WM_F32));
+    }
     WM_HIP(hipEventRecord(j.ev[1], c->stream));
     // 2. encoder + cross-attention K/V
-    WM_TRY(wm_model_encode_dev(c, m->mel_f32, Bg, nullptr));
+    WM_TRY(wm_model_encode_win(c, enc_mel, enc_win, Bg, nullptr));
     WM_TRY(wm_model_cross_kv(c, Bg));
     WM_HIP(hipEventRecord(j.ev[2], c->stream));
     // 3. embedding of the first prompt token (+ the initial timestamp-rule state)
@@ -634,42 +676,69 @@ int wm_lane_parts(int B, int L, bool explicit_lanes, int n_text_state, int n_tex
     return 0;                                    // d >= 768: the chain needs the whole chip
 }
 
-static int transcribe_impl(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
-                           int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
-                           float *logprobs_out, float *no_speech_out, wm_mem mem);
+static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, int max_new, int32_t eot,
+                           const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, float *logprobs_out,
+                           float *no_speech_out, wm_mem mem);
 
 extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
                                     const int32_t *prompt, int n_prompt, int max_new, int32_t eot,
                                     int32_t *tokens_out, int32_t *lens_out, wm_mem mem) try {
-    return transcribe_impl(ctx, pcm, pcm_dtype, B, prompt, n_prompt, max_new, eot, nullptr, tokens_out, lens_out, nullptr,
-                           nullptr, mem);
+    TxSrc src;
+    src.pcm = pcm; src.pcm_dtype = pcm_dtype; src.prompt = prompt;
+    return transcribe_impl(ctx, src, B, n_prompt, max_new, eot, nullptr, tokens_out, lens_out, nullptr, nullptr, mem);
 } WM_API_CATCH
 
 extern "C" int wm_transcribe(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
                              int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
                              float *token_logprobs_out, float *no_speech_prob_out, wm_mem mem) try {
-    return transcribe_impl(ctx, pcm, pcm_dtype, B, prompt, n_prompt, max_new, eot, opts, tokens_out, lens_out,
-                           token_logprobs_out, no_speech_prob_out, mem);
+    TxSrc src;
+    src.pcm = pcm; src.pcm_dtype = pcm_dtype; src.prompt = prompt;
+    return transcribe_impl(ctx, src, B, n_prompt, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
+                           no_speech_prob_out, mem);
 } WM_API_CATCH
 
-// wm_transcribe_greedy and wm_transcribe: opts == null with both extra outputs null is the greedy decode exactly
-static int transcribe_impl(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
-                           int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
-                           float *logprobs_out, float *no_speech_out, wm_mem mem) {
+extern "C" int wm_transcribe_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                 const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts, int n_prompt,
+                                 const uint32_t *sample_ids, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                 int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                 wm_mem mem) try {
+    WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
+    TxSrc src;
+    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
+    src.prompt = prompts; src.prompt_stride = n_prompt; src.sample_ids = sample_ids;
+    return transcribe_impl(ctx, src, B, n_prompt, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
+                           no_speech_prob_out, mem);
+} WM_API_CATCH
+
+// wm_transcribe_greedy, wm_transcribe and wm_transcribe_mel: opts == null with both extra outputs null is the greedy
+// decode exactly
+static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, int max_new, int32_t eot,
+                           const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, float *logprobs_out,
+                           float *no_speech_out, wm_mem mem) {
     WM_MODEL(ctx);
     // per-chunk token budgets set for THIS call (wm_set_token_budgets) are consumed by it whatever happens next: a call
     // that fails validation must not leave them armed for a later, unrelated call with the same B
     std::vector<int32_t> budgets;
     budgets.swap(m->budget_host);
     WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
-    WM_REQUIRE(pcm && prompt && tokens_out && lens_out, WM_ERR_INVALID, "null pointer");
-    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID, "bad pcm dtype");
+    WM_REQUIRE((src.pcm || src.mel) && src.prompt && tokens_out && lens_out, WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE(src.mel || src.pcm_dtype == WM_I16 || src.pcm_dtype == WM_F32 || src.pcm_dtype == WM_F64, WM_ERR_INVALID,
+               "bad pcm dtype");
     WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
+    if (src.mel)
+        for (int b = 0; b < B; ++b)
+            WM_REQUIRE(src.mel_base[b] >= 0 && src.mel_len[b] >= 1 && src.seek[b] >= 0 && src.n_frames[b] >= 1 &&
+                           src.n_frames[b] <= WM_N_FRAMES && (int64_t)src.seek[b] + src.n_frames[b] <= src.mel_len[b],
+                       WM_ERR_INVALID, "row %d: window (base %lld, T %d, seek %d, n_frames %d) invalid", b,
+                       (long long)src.mel_base[b], src.mel_len[b], src.seek[b], src.n_frames[b]);
     const wm_dims &D = m->dims;
     WM_REQUIRE(n_prompt >= 1 && max_new >= 1 && n_prompt + max_new <= D.n_text_ctx, WM_ERR_INVALID,
                "prompt (%d) + new tokens (%d) must fit the %d-token context", n_prompt, max_new, D.n_text_ctx);
-    for (int i = 0; i < n_prompt; ++i)
-        WM_REQUIRE(prompt[i] >= 0 && prompt[i] < D.n_vocab, WM_ERR_INVALID, "prompt token %d out of range", prompt[i]);
+    for (int b = 0; b < (src.prompt_stride ? B : 1); ++b)
+        for (int i = 0; i < n_prompt; ++i) {
+            const int32_t t = src.prompt[(size_t)b * src.prompt_stride + i];
+            WM_REQUIRE(t >= 0 && t < D.n_vocab, WM_ERR_INVALID, "prompt token %d out of range", t);
+        }
     WM_REQUIRE(eot < D.n_vocab, WM_ERR_INVALID, "eot %d outside the vocabulary", eot);
     WM_REQUIRE(budgets.empty() || (int)budgets.size() == B, WM_ERR_INVALID,
                "token budgets were set for %d chunks, the call has %d", (int)budgets.size(), B);
@@ -778,7 +847,7 @@ static int transcribe_impl(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int
                 j.Bg = base + (g < rem ? 1 : 0);
                 j.b0 = g * base + (g < rem ? g : rem);
                 j.t = 0; j.bursts = 0; j.stopped = false;
-                WM_TRY(lane_prefill(j, pcm, pcm_dtype, prompt, n_prompt, mem, stop, xc));
+                WM_TRY(lane_prefill(j, src, n_prompt, mem, stop, xc));
                 if (use_graph) WM_TRY(lane_graph(j, n_prompt));
                 j.state = LaneJob::DECODING;
                 progress = true;

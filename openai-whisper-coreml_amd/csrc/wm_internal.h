@@ -111,7 +111,21 @@ struct WmFrontend {
     int gmax_cap = 0;
     void *scratch = nullptr;                // staging for host-pointer calls
     size_t scratch_bytes = 0;
+    void *long_tab = nullptr;               // wm_logmel_long: recording and workgroup tables (WmLongRec, int2)
+    size_t long_tab_bytes = 0;
     bool ready = false;
+};
+
+// wm_logmel_long's geometry (frontend.hip): one record per recording, one (recording, first frame) pair per workgroup
+struct WmLongRec {
+    long long base;  // first sample of the recording in pcm
+    long long out;   // element offset of its [n_mels][T] block in the output
+    int len;         // samples (>= 0)
+    int T;           // frames: (len + 480000) / 160
+};
+struct WmLongTab {
+    const WmLongRec *rec;
+    const int2 *blk;
 };
 
 int wm_frontend_init(WmFrontend *fe, hipStream_t stream);
@@ -120,6 +134,12 @@ void wm_frontend_destroy(WmFrontend *fe);
 int wm_frontend_run(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const void *d_pcm,
                     wm_dtype pcm_dtype, int n_chunks, int n_mels, void *d_out,
                     wm_dtype out_dtype);
+// openai-whisper log_mel_spectrogram(audio, padding=480000), f32, of R recordings back to back in d_pcm: recording r =
+// d_pcm[offs[r] .. offs[r + 1]) (offs: host) -> d_out, recording r's [n_mels][(len_r + 480000) / 160] after the previous ones.
+int wm_frontend_run_long(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
+                         const int64_t *offs, int R, int n_mels, float *d_out);
+// frames of a recording of len samples in that layout
+inline int64_t wm_long_frames(int64_t len) { return (len + WM_N_SAMPLES) / WM_HOP; }
 // Host-side slaney mel filterbank generator (librosa.filters.mel semantics; used for
 // n_mels = 128 and validated against the reference's m80.npy at n_mels = 80).
 void wm_mel_filterbank(int n_mels, std::vector<float> &out /* [n_mels][201] */);

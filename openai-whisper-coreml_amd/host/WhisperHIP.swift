@@ -199,6 +199,51 @@ struct Whisper {
                 (0..<chunks).map { c in Array(probs[c * maxText..<c * maxText + text[c].count]) })
     }
 
+    /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
+    /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
+    /// Not compiled in this repository (see the top of the file).
+    func logMelLong(recordings: [[Float]], nMels: Int32 = 80) throws -> [[Float]] {
+        typealias LongFn = @convention(c) (OpaquePointer, UnsafeRawPointer?, Int32, UnsafePointer<Int64>, Int32, Int32,
+                                           UnsafeMutablePointer<Float>, Int32) -> Int32
+        var offsets: [Int64] = [0]
+        for r in recordings { offsets.append(offsets.last! + Int64(r.count)) }
+        let frames = recordings.map { ($0.count + 480_000) / 160 }
+        let pcm = recordings.flatMap { $0 }
+        var out = [Float](repeating: 0, count: max(1, frames.reduce(0, +) * Int(nMels)))
+        let f: LongFn = try sym("wm_logmel_long")
+        try pcm.withUnsafeBytes { p in
+            try check(f(ctx, p.baseAddress, 1 /* WM_F32 */, offsets, Int32(recordings.count), nMels, &out, 0))
+        }
+        var result: [[Float]] = []
+        var at = 0
+        for t in frames {
+            result.append(Array(out[at..<at + t * Int(nMels)]))
+            at += t * Int(nMels)
+        }
+        return result
+    }
+
+    /// One decode step of the long-form loop (wm_transcribe_mel): row b decodes mel[:, seek[b] ..< seek[b] + nFrames[b]] of
+    /// the recording block at element melBase[b] (melLen[b] frames) with its own prompt; temperature 0, host memory.
+    /// Returns each row's generated tokens.  Not compiled in this repository (see the top of the file).
+    func transcribeMel(mel: [Float], melBase: [Int64], melLen: [Int32], seek: [Int32], nFrames: [Int32],
+                       prompts: [[Int32]], maxNew: Int32, eot: Int32) throws -> [[Int32]] {
+        typealias MelFn = @convention(c) (OpaquePointer, UnsafePointer<Float>, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                          UnsafePointer<Int32>, UnsafePointer<Int32>, Int32, UnsafePointer<Int32>, Int32,
+                                          UnsafePointer<UInt32>?, Int32, Int32, UnsafeRawPointer?,
+                                          UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Int32>,
+                                          UnsafeMutablePointer<Float>?, UnsafeMutablePointer<Float>?, Int32) -> Int32
+        let rows = melBase.count
+        let nPrompt = prompts.first?.count ?? 0
+        let flat = prompts.flatMap { $0 }
+        var tokens = [Int32](repeating: 0, count: rows * Int(maxNew))
+        var lens = [Int32](repeating: 0, count: rows)
+        let f: MelFn = try sym("wm_transcribe_mel")
+        try check(f(ctx, mel, melBase, melLen, seek, nFrames, Int32(rows), flat, Int32(nPrompt), nil, maxNew, eot, nil,
+                    &tokens, &lens, nil, nil, 0))
+        return (0..<rows).map { r in Array(tokens[r * Int(maxNew)..<r * Int(maxNew) + Int(lens[r])]) }
+    }
+
     /// ids -> text with the tokenizer's vocab.json (wm_vocab_load / wm_detokenize; no vocabulary ships with the library).
     func text(of ids: [Int32], vocabJSON: String) throws -> String {
         let load: VocabLoadFn = try sym("wm_vocab_load")
