@@ -99,6 +99,21 @@ WM_API int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, const
 /* Makes the NEXT wm_align call on ctx also return its cost matrix -- AFTER negation, i.e. x = -mean over heads, the matrix
  * the DTW runs on -- into matrix_out f32 [B][max_text + 1][1500] (0 outside each chunk's n + 1 rows x n_frames / 2 frames). */
 WM_API int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out);
+/* The alignment kernels of wm_align alone (column statistics, then the cost matrix) on host data.  q f32 [B][Tq][J][64] (the
+ * capture buffer: chunk b's decoder rows 0 .. S + n_text[b] + 1), keys f32 [L][B][H][1500][64] (the cross-attention keys of
+ * every decoder layer, chunk and head), alignment heads (hl[j], hh[j]), j < J, in the order the mean adds them.  Row counts as
+ * wm_align: n_text[b] in [0, Tq - S - 2] (0: chunk untouched), Tq <= n_text_ctx (448 without a model), n_frames[b] in
+ * [2, 3000], medfilt_width odd 1 .. 31.  The keys are rounded to bf16 into a cross-K/V cache [L][2][B][H][1500][64] whose V
+ * halves are NaN and whose key frames >= n_frames[b] / 2 hold 32768.  Out: x f32 [B][Tq - S - 1][1500], pre-filled with the
+ * NaN bits 0x7fc0dead, of which the kernels overwrite rows [0, n_text[b] + 1) x frames [0, n_frames[b] / 2) of each chunk;
+ * optional col_stats f32 [B][J][1500][2] (per frame: mean and std of the probabilities over the S + n + 2 rows). */
+WM_API int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
+                              const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
+                              int medfilt_width, float qk_scale, float *x, float *col_stats);
+/* The token-probability kernel of wm_align alone: prob[b] = softmax(logits[b][0 : eot])[tok[b]] for B host rows of row stride
+ * ldo >= V (entries eot .. ldo - 1 are never read), 1 <= eot <= V, 0 <= tok[b] < eot. */
+WM_API int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, int V, int ldo, const int32_t *tok, int eot,
+                                  float *prob);
 
 #ifdef __cplusplus
 }

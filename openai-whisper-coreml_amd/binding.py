@@ -905,6 +905,49 @@ class Context:
         _check(self.lib, fn(self.handle, _ptr(x), B, _ptr(N), _ptr(M), ld, _ptr(out)))
         return [out[b, :N[b]] for b in range(B)]
 
+    def align_matrix(self, q, keys, heads, S, n_text, n_frames, medfilt_width=7, qk_scale=1.0, col_stats=False):
+        """Debug library only: the alignment kernels of wm_align alone (wmdbg_align_matrix).  q f32 [B][Tq][J][64], keys f32
+        [L][B][H][1500][64], heads: J (layer, head) pairs.  Returns the cost matrix x f32 [B][Tq - S - 1][1500] (the NaN bits
+        0x7fc0dead off each chunk's n + 1 rows x n_frames // 2 frames), with col_stats=True also the column statistics
+        f32 [B][J][1500][2] (mean, std)."""
+        if not hasattr(self.lib, "wmdbg_align_matrix"):
+            raise WhisperError(-1, "align_matrix needs the debug library: Context(dims, debug=True)")
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        keys = np.ascontiguousarray(keys, dtype=np.float32)
+        B, Tq, J = q.shape[:3]
+        L, H = keys.shape[0], keys.shape[2]
+        if q.shape[3] != 64 or keys.shape[1:] != (B, H, 1500, 64) or len(heads) != J:
+            raise ValueError("align_matrix: q %s, keys %s, %d heads" % (q.shape, keys.shape, len(heads)))
+        hl = np.ascontiguousarray([p[0] for p in heads], dtype=np.int32)
+        hh = np.ascontiguousarray([p[1] for p in heads], dtype=np.int32)
+        nt = np.ascontiguousarray(np.broadcast_to(np.asarray(n_text, dtype=np.int32), (B,)))
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
+        x = np.empty((B, Tq - S - 1, 1500), dtype=np.float32)
+        cs = np.empty((B, J, 1500, 2), dtype=np.float32) if col_stats else None
+        fn = self.lib.wmdbg_align_matrix
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        fn.argtypes = [vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, ctypes.c_float, vp, vp]
+        fn.restype = ctypes.c_int
+        _check(self.lib, fn(self.handle, _ptr(q), _ptr(keys), L, H, B, Tq, J, _ptr(hl), _ptr(hh), int(S), _ptr(nt), _ptr(nf),
+                            int(medfilt_width), float(qk_scale), _ptr(x), _ptr(cs) if col_stats else None))
+        return (x, cs) if col_stats else x
+
+    def align_token_prob(self, logits, tok, eot, V=None):
+        """Debug library only: the token-probability kernel of wm_align alone (wmdbg_align_token_prob) on logits rows f32
+        [B][ldo] (V <= ldo columns, default ldo): softmax(logits[b][:eot])[tok[b]] f32 [B]."""
+        if not hasattr(self.lib, "wmdbg_align_token_prob"):
+            raise WhisperError(-1, "align_token_prob needs the debug library: Context(dims, debug=True)")
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        B, ldo = logits.shape
+        tok = np.ascontiguousarray(np.broadcast_to(np.asarray(tok, dtype=np.int32), (B,)))
+        out = np.empty(B, dtype=np.float32)
+        fn = self.lib.wmdbg_align_token_prob
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        fn.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp]
+        fn.restype = ctypes.c_int
+        _check(self.lib, fn(self.handle, _ptr(logits), B, int(ldo if V is None else V), ldo, _ptr(tok), int(eot), _ptr(out)))
+        return out
+
     def sample_noise(self, seed, chunk, gi, n0, count):
         """Debug library only: the Gumbel noise g(n0 .. n0 + count - 1) wm_transcribe's sampling adds, from the device."""
         if not hasattr(self.lib, "wmdbg_sample_noise"):

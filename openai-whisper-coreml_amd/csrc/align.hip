@@ -7,7 +7,9 @@
 //   * align_stats_kernel (pass 1, one workgroup per (chunk, head)): the scores q.k / 8 * qk_scale over frames [0, M) are
 //     recomputed from the bf16 cross-K cache with the exact-f32 MFMA (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain),
 //     16 decoder rows x 16 frames per tile.  Sweep 1 gives every row its softmax (max, 1 / sum); sweep 2 the per-frame sums
-//     of p and p^2 over the chunk's rows (each wave owns its LDS column partials, summed in wave order: no float atomics).
+//     of p over the chunk's rows, hence the column means; sweep 3 the per-frame sums of (p - mean)^2, hence the stds (two
+//     passes: the one-pass E[p^2] - mean^2 cancels to nothing in f32 once std / mean falls to ~1e-3).  Each wave owns its LDS
+//     column partials, summed in wave order: no float atomics.
 //     Out: row statistics [B][J][T][2] and column (mean, std) [B][J][1500][2] -- never the [J][T][1500] probabilities.
 //   * align_matrix_kernel (pass 2, one workgroup per (chunk, 16 text rows, 64 frames)): for every head in ascending
 //     (layer, head) order it recomputes the scores of its rows over its frames plus the filter's halo, normalises them
@@ -26,7 +28,8 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 constexpr int AL_OUT = 64;        // output frames per workgroup of the matrix kernel
 constexpr int AL_MAXHALF = 15;    // medfilt_width <= 31
 constexpr int AL_ZW = AL_OUT + 2 * AL_MAXHALF + 2;   // LDS row of one head's normalised scores (frames + halo)
-constexpr int DTW_ROWS_PER_LANE = (448 + 63) / 64;   // text rows <= n_text_ctx
+constexpr int AL_MAXT = 448;      // decoder rows S + n + 2 <= n_text_ctx <= 448
+constexpr int DTW_ROWS_PER_LANE = (AL_MAXT + 63) / 64;   // text rows <= n_text_ctx
 
 __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
@@ -102,12 +105,14 @@ __global__ __launch_bounds__(256) void align_token_prob_kernel(const float *__re
 }
 
 __global__ __launch_bounds__(256) void align_stats_kernel(WmAlignDev a) {
-    __shared__ float part[4][1500][2];   // per-wave column sums of p and p^2
+    __shared__ float part[4][1500];      // per-wave column sums: of p (sweep 2), then of (p - mean)^2 (sweep 3)
+    __shared__ float mean[1500];
+    __shared__ float rowl[AL_MAXT][2];   // the rows' (max, 1 / sum) for sweep 3
     const int j = blockIdx.x, b = blockIdx.y, n = a.n_text[b];
     if (n <= 0) return;
     const int T = a.S + n + 2, M = a.n_frames[b] / 2;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
-    for (int i = threadIdx.x; i < 4 * 1500 * 2; i += 256) (&part[0][0][0])[i] = 0.f;
+    for (int i = threadIdx.x; i < 4 * 1500; i += 256) (&part[0][0])[i] = 0.f;
     __syncthreads();
     const bf16_t *K = head_keys(a, b, j);
     const int nft = (M + 15) / 16;
@@ -140,35 +145,63 @@ __global__ __launch_bounds__(256) void align_stats_kernel(WmAlignDev a) {
             const int t = t0 + 4 * g + r;
             if (c == 0 && t < T) {
                 float *rs = a.rowst + (((size_t)b * a.J + j) * a.Tq + t) * 2;
-                rs[0] = m[r];
-                rs[1] = inv[r];
+                rs[0] = rowl[t][0] = m[r];
+                rs[1] = rowl[t][1] = inv[r];
             }
         }
         for (int ft = 0; ft < nft; ++ft) {
             const int f = ft * 16 + c;
             const f32x4 acc = score_tile(qf, K + (size_t)min(f, M - 1) * 64 + 16 * g);
-            float p1 = 0.f, p2 = 0.f;
+            float p1 = 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (f < M && t0 + 4 * g + r < T) {
-                    const float p = exp2f(acc[r] * a.sc - m[r]) * inv[r];
-                    p1 += p;
-                    p2 += p * p;
-                }
-            p1 += __shfl_xor(p1, 16); p2 += __shfl_xor(p2, 16);
-            p1 += __shfl_xor(p1, 32); p2 += __shfl_xor(p2, 32);
-            if (g == 0 && f < M) { part[w][f][0] += p1; part[w][f][1] += p2; }
+                if (f < M && t0 + 4 * g + r < T) p1 += exp2f(acc[r] * a.sc - m[r]) * inv[r];
+            p1 += __shfl_xor(p1, 16);
+            p1 += __shfl_xor(p1, 32);
+            if (g == 0 && f < M) part[w][f] += p1;
         }
     }
     __syncthreads();
     const float inv_T = 1.f / (float)T;
+    for (int f = threadIdx.x; f < M; f += 256) {   // one thread per frame: reads its partials, then clears them
+        mean[f] = (((part[0][f] + part[1][f]) + part[2][f]) + part[3][f]) * inv_T;
+        part[0][f] = part[1][f] = part[2][f] = part[3][f] = 0.f;
+    }
+    __syncthreads();
+    for (int t0 = w * 16; t0 < T; t0 += 64) {   // sweep 3: the same p once more, its squared deviation from the column mean
+        float qf[16];
+        load_q(head_query(a, b, min(t0 + c, T - 1), j) + 16 * g, qf);
+        float m[4], inv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int t = min(t0 + 4 * g + r, T - 1);
+            m[r] = rowl[t][0];
+            inv[r] = rowl[t][1];
+        }
+        for (int ft = 0; ft < nft; ++ft) {
+            const int f = ft * 16 + c;
+            const f32x4 acc = score_tile(qf, K + (size_t)min(f, M - 1) * 64 + 16 * g);
+            float d2 = 0.f;
+            if (f < M) {
+                const float mu = mean[f];
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (t0 + 4 * g + r < T) {
+                        const float d = exp2f(acc[r] * a.sc - m[r]) * inv[r] - mu;
+                        d2 += d * d;
+                    }
+            }
+            d2 += __shfl_xor(d2, 16);
+            d2 += __shfl_xor(d2, 32);
+            if (g == 0 && f < M) part[w][f] += d2;
+        }
+    }
+    __syncthreads();
     for (int f = threadIdx.x; f < M; f += 256) {
-        const float s1 = ((part[0][f][0] + part[1][f][0]) + part[2][f][0]) + part[3][f][0];
-        const float s2 = ((part[0][f][1] + part[1][f][1]) + part[2][f][1]) + part[3][f][1];
-        const float mean = s1 * inv_T;
+        const float s2 = ((part[0][f] + part[1][f]) + part[2][f]) + part[3][f];
         float *cs = a.colst + (((size_t)b * a.J + j) * 1500 + f) * 2;
-        cs[0] = mean;
-        cs[1] = sqrtf(fmaxf(s2 * inv_T - mean * mean, 0.f));
+        cs[0] = mean[f];
+        cs[1] = sqrtf(s2 * inv_T);
     }
 }
 
@@ -361,6 +394,7 @@ int wm_align_token_prob(wm_ctx *ctx, const float *logits, long ldo, const int *s
 int wm_align_matrix(wm_ctx *ctx, const WmAlignDev &a, int max_n, int max_m) {
     WM_REQUIRE(a.half >= 0 && a.half <= AL_MAXHALF, WM_ERR_INVALID, "align: median filter half-width %d > %d", a.half,
                AL_MAXHALF);
+    WM_REQUIRE(a.Tq <= AL_MAXT, WM_ERR_INVALID, "align: %d decoder rows > %d", a.Tq, AL_MAXT);
     if (max_n <= 0 || max_m <= 0) return WM_OK;
     {
         WmProfScope ps(&ctx->prof, "align_stats", ctx->stream);

@@ -605,3 +605,96 @@ extern "C" int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out) {
     ctx->model->align_dbg_matrix = matrix_out;
     return WM_OK;
 }
+
+extern "C" int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
+                                  const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
+                                  int medfilt_width, float qk_scale, float *x, float *col_stats) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(q && keys && hl && hh && n_text && n_frames && x && L >= 1 && H >= 1 && B >= 1 && J >= 1 && S >= 1,
+               WM_ERR_INVALID, "bad args");
+    const int n_ctx = ctx->model ? ctx->model->dims.n_text_ctx : 448;
+    WM_REQUIRE(Tq >= S + 2 && Tq <= n_ctx, WM_ERR_INVALID, "align: Tq = %d outside [S + 2, %d]", Tq, n_ctx);
+    WM_REQUIRE(medfilt_width >= 1 && medfilt_width <= 31 && medfilt_width % 2 == 1, WM_ERR_INVALID,
+               "align: medfilt_width %d must be odd, 1 .. 31", medfilt_width);
+    WM_REQUIRE(isfinite(qk_scale), WM_ERR_INVALID, "align: qk_scale must be finite");
+    for (int j = 0; j < J; ++j)
+        WM_REQUIRE(hl[j] >= 0 && hl[j] < L && hh[j] >= 0 && hh[j] < H, WM_ERR_INVALID, "align: head %d outside the model", j);
+    int nmax = 0, mmax = 0;
+    for (int b = 0; b < B; ++b) {
+        WM_REQUIRE(n_text[b] >= 0 && n_text[b] <= Tq - S - 2, WM_ERR_INVALID, "align: n_text[%d] = %d outside [0, %d]", b,
+                   n_text[b], Tq - S - 2);
+        WM_REQUIRE(n_frames[b] >= 2 && n_frames[b] <= WM_N_FRAMES, WM_ERR_INVALID, "align: n_frames[%d] = %d outside [2, %d]",
+                   b, n_frames[b], WM_N_FRAMES);
+        nmax = n_text[b] > nmax ? n_text[b] : nmax;
+        mmax = n_frames[b] / 2 > mmax ? n_frames[b] / 2 : mmax;
+    }
+    const int n_ld = Tq - S - 1;
+    const size_t head = (size_t)1500 * 64;
+    // the cross-K/V cache [L][2][B][H][1500][64]: keys rounded as to_bf16 rounds, V halves NaN, frames >= M a large key
+    std::vector<bf16_t> kv((size_t)L * 2 * B * H * head, (bf16_t)0x7fc0);
+    for (int l = 0; l < L; ++l)
+        for (int b = 0; b < B; ++b)
+            for (int h = 0; h < H; ++h) {
+                const float *src = keys + (((size_t)l * B + b) * H + h) * head;
+                bf16_t *dst = kv.data() + (((size_t)l * 2 * B + b) * H + h) * head;
+                const size_t live = (size_t)(n_frames[b] / 2) * 64;
+                for (size_t i = 0; i < head; ++i) {
+                    uint32_t u;
+                    memcpy(&u, &src[i], 4);
+                    u += 0x7fffu + ((u >> 16) & 1u);
+                    dst[i] = i < live ? (bf16_t)(u >> 16) : (bf16_t)0x4700;   // 32768
+                }
+            }
+    std::vector<int32_t> ints((size_t)2 * B + 2 * J);
+    for (int b = 0; b < B; ++b) { ints[b] = n_text[b]; ints[B + b] = n_frames[b]; }
+    for (int j = 0; j < J; ++j) { ints[2 * B + j] = hl[j]; ints[2 * B + J + j] = hh[j]; }
+    const uint32_t sentinel = 0x7fc0deadu;
+    std::vector<uint32_t> x0((size_t)B * n_ld * 1500, sentinel);
+    hipStream_t s = ctx->stream;
+    void *dq, *dkv, *di, *drow, *dcol, *dx;
+    WM_TRY(up(&dq, q, (size_t)B * Tq * J * 64 * 4, s));
+    WM_TRY(up(&dkv, kv.data(), kv.size() * 2, s));
+    WM_TRY(up(&di, ints.data(), ints.size() * 4, s));
+    WM_TRY(up(&drow, nullptr, (size_t)B * J * Tq * 2 * 4, s));
+    WM_TRY(up(&dcol, nullptr, (size_t)B * J * 1500 * 2 * 4, s));
+    WM_TRY(up(&dx, x0.data(), x0.size() * 4, s));
+    WmAlignDev a;
+    a.q = (const float *)dq; a.xkv = (const bf16_t *)dkv;
+    a.n_text = (const int *)di; a.n_frames = (const int *)di + B; a.hl = (const int *)di + 2 * B; a.hh = (const int *)di + 2 * B + J;
+    a.rowst = (float *)drow; a.colst = (float *)dcol; a.x = (float *)dx;
+    a.B = B; a.H = H; a.Tq = Tq; a.J = J; a.S = S; a.n_ld = n_ld;
+    a.sc = 0.125f * qk_scale * 1.44269504088896340736f;   // as wm_align
+    a.half = medfilt_width / 2;
+    int rc = wm_align_matrix(ctx, a, nmax, mmax);
+    if (rc == WM_OK) {
+        WM_HIP(hipMemcpyAsync(x, dx, x0.size() * 4, hipMemcpyDeviceToHost, s));
+        if (col_stats) WM_HIP(hipMemcpyAsync(col_stats, dcol, (size_t)B * J * 1500 * 2 * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    }
+    for (void *p : {dq, dkv, di, drow, dcol, dx}) (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, int V, int ldo, const int32_t *tok, int eot,
+                                      float *prob) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(logits && tok && prob && B >= 1 && V >= 1 && ldo >= V && eot >= 1 && eot <= V, WM_ERR_INVALID, "bad args");
+    for (int b = 0; b < B; ++b)
+        WM_REQUIRE(tok[b] >= 0 && tok[b] < eot, WM_ERR_INVALID, "align: token %d of row %d is not below eot %d", tok[b], b, eot);
+    // one decode position (pos 0, S = 0) with one text token per row: the token is seq[pos + 1][b]
+    std::vector<int32_t> ints((size_t)3 * B + 1, 0);
+    for (int b = 0; b < B; ++b) { ints[B + b] = tok[b]; ints[2 * B + b] = 1; }
+    hipStream_t s = ctx->stream;
+    void *dl, *di, *dp;
+    WM_TRY(up(&dl, logits, (size_t)B * ldo * 4, s));
+    WM_TRY(up(&di, ints.data(), ints.size() * 4, s));
+    WM_TRY(up(&dp, nullptr, (size_t)B * 4, s));
+    const int *seq = (const int *)di, *n_text = seq + 2 * B, *pos = seq + 3 * B;
+    int rc = wm_align_token_prob(ctx, (const float *)dl, ldo, seq, pos, B, 0, eot, n_text, (float *)dp, 1);
+    if (rc == WM_OK) {
+        WM_HIP(hipMemcpyAsync(prob, dp, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    }
+    for (void *p : {dl, di, dp}) (void)hipFree(p);
+    return rc;
+}

@@ -20,9 +20,9 @@ B = importlib.import_module("openai_whisper_coreml_amd.binding")
 
 
 # ---------------------------------------------------------------- numpy / torch restatement
-def median_filter(x, width):
+def median_filter(x, width, dtype=np.float32):
     """openai-whisper median_filter: along the last axis, reflect padding of width // 2, none when it would not fit."""
-    x = torch.as_tensor(np.asarray(x, dtype=np.float32))
+    x = torch.as_tensor(np.asarray(x, dtype=dtype))
     pad = width // 2
     if x.shape[-1] <= pad:
         return x.numpy()
@@ -33,9 +33,9 @@ def median_filter(x, width):
     return (r[0, 0] if nd <= 2 else r).numpy()
 
 
-def zscore(w):
+def zscore(w, dtype=np.float32):
     """per head and frame over the rows (torch.std_mean(dim=-2, unbiased=False))"""
-    w = torch.as_tensor(np.asarray(w, dtype=np.float32))
+    w = torch.as_tensor(np.asarray(w, dtype=dtype))
     std, mean = torch.std_mean(w, dim=-2, keepdim=True, unbiased=False)
     return ((w - mean) / std).numpy()
 
@@ -88,14 +88,29 @@ def start_frames(x):
     return time_idx[jumps].astype(np.int64)
 
 
-def alignment_matrix(qk, n_sot, n_frames, medfilt_width=7, qk_scale=1.0):
-    """find_alignment steps 2-5 on the recorded scores of the alignment heads, qk f32 [J][T][1500] (= q.k / 8):
-    the cost matrix -matrix [n + 1][n_frames // 2]."""
-    w = torch.as_tensor(np.asarray(qk, dtype=np.float32))[:, :, : n_frames // 2]
+def alignment_matrix(qk, n_sot, n_frames, medfilt_width=7, qk_scale=1.0, dtype=np.float32):
+    """find_alignment steps 2-5 on the recorded scores of the alignment heads, qk [J][T][>= n_frames // 2] (= q.k / 8), in
+    `dtype` throughout (openai-whisper: f32): the cost matrix -matrix [n + 1][n_frames // 2]."""
+    w = torch.as_tensor(np.asarray(qk, dtype=dtype))[:, :, : n_frames // 2]
     w = (w * qk_scale).softmax(dim=-1).numpy()
-    w = median_filter(zscore(w), medfilt_width)
+    w = median_filter(zscore(w, dtype), medfilt_width, dtype)
     matrix = np.asarray(w).mean(axis=0)
     return -matrix[n_sot:-1]
+
+
+def _variant_matrix(qk, n_sot, n_frames, medfilt_width, qk_scale, variant):
+    """alignment_matrix in f64 for one head with one deliberate mistake ("none": without): "unbiased" std (ddof 1), "shifted" median window
+    (frames fo - h + 1 .. fo + h + 1), "replicate" padding, "text-rows" (the column statistics over the n + 1 text rows
+    only, not all S + n + 2 rows)."""
+    w = (torch.as_tensor(np.asarray(qk, dtype=np.float64))[:, :, : n_frames // 2] * qk_scale).softmax(dim=-1)
+    rows = w[:, n_sot:-1] if variant == "text-rows" else w
+    std, mean = torch.std_mean(rows, dim=-2, keepdim=True, unbiased=variant == "unbiased")
+    z = (w - mean) / std
+    h, M = medfilt_width // 2, w.shape[-1]
+    if M > h + (variant == "shifted"):
+        y = F.pad(z, (h, h + (variant == "shifted"), 0, 0), mode="replicate" if variant == "replicate" else "reflect")
+        z = y.unfold(-1, medfilt_width, 1).sort()[0][..., h][..., variant == "shifted":][..., :M]
+    return -z.mean(dim=0).numpy()[n_sot:-1]
 
 
 # ---------------------------------------------------------------- hand-worked cases
@@ -264,3 +279,43 @@ def test_words_edge_cases(vocab):
     assert B.word_timestamps(vocab, [], np.array([-1]), np.zeros(0)) == []
     w = B.word_timestamps(vocab, [0], np.array([2, 7]), np.array([0.5]))
     assert w == [dict(word=" hello", tokens=[0], start=2 / 50, end=7 / 50, probability=0.5)]
+
+
+# ---------------------------------------------------------------- the fp64 reference of tests/test_align_kernels_gpu.py
+def test_fp64_restatement_matches_the_f32_one():
+    """well-conditioned scores (q, k ~ N(0, 1)): the fp64 restatement the kernel tests use and the f32 one agree to within
+    the kernel tests' gate for such inputs"""
+    K = importlib.import_module("test_align_kernels_gpu")
+    rng = np.random.default_rng(1)
+    for T, M, width in ((5, 2, 3), (20, 64, 7), (60, 617, 15), (448, 1500, 31)):
+        qk = rng.standard_normal((3, T, 64)) @ rng.standard_normal((M, 64)).T / 8
+        x64 = alignment_matrix(qk, 3, 2 * M, width, 0.37, dtype=np.float64)
+        x32 = alignment_matrix(qk, 3, 2 * M, width, 0.37)
+        assert x64.dtype == np.float64 and x32.dtype == np.float32 and x64.shape == (T - 4, M)
+        assert np.abs(x64 - x32).max() <= K.GATES["normal"], (T, M, width, np.abs(x64 - x32).max())
+
+
+def test_kernel_gates_catch_known_wrong_variants():
+    """On the kernel tests' own inputs (chunks of up to 64 text tokens), each known-wrong variant moves x by more than 10x the
+    regime's gate in some case of every regime: the gates would catch a kernel that made that mistake."""
+    K = importlib.import_module("test_align_kernels_gpu")
+    worst = {}
+    for i, case in enumerate(K.CASES):
+        regime, hk, S, width, qk_scale, chunks = case
+        heads = K.HEADS[hk][2]
+        q, keys = K.inputs(case, i)
+        for b, (n, nf) in enumerate(chunks):
+            if n > 64 or nf // 2 < 2:
+                continue
+            qk = K.head_scores(q, keys, heads, b, S + n + 2, nf // 2)
+            want = K.reference(case, q, keys, b)
+            for variant in ("none", "unbiased", "shifted", "replicate", "text-rows"):
+                got = np.mean([_variant_matrix(qk[j:j + 1], S, nf, width, qk_scale, variant) for j in range(len(heads))], 0)
+                d = np.abs(got - want).max() / K.GATES[regime]
+                if variant == "none":
+                    assert d <= 1e-6, (K.case_id(case), b)    # without a mistake: the reference itself
+                    continue
+                worst[variant, regime] = max(worst.get((variant, regime), 0.0), d)
+    assert len(worst) == 4 * len(K.GATES)
+    weak = {k: v for k, v in worst.items() if not v > 10}
+    assert not weak, weak
