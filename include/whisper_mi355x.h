@@ -242,6 +242,26 @@ WM_API int wm_transcribe_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_b
                              int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
                              wm_mem mem);
 
+/* wm_transcribe_mel with prompts of DIFFERENT lengths in one call -- what openai-whisper's condition_on_previous_text needs:
+ * every window's prompt carries the text its own recording produced so far.
+ *   prompts    : i32 [B][prompt_stride] (host): row b's prompt is its first prompt_len[b] entries, the rest is not read;
+ *   prompt_len : i32 [B] (host), each 1 .. prompt_stride;
+ *   sot_tail   : <|startoftranscript|> is prompts[b][prompt_len[b] - sot_tail] in every row (the same distance from the END
+ *                of every prompt: 3 for [..., sot, language, task]); read only when no_speech_prob_out is given.
+ *                opts->sot_index is NOT read by this call;
+ *   everything else exactly as wm_transcribe_mel.
+ * Row b's tokens, length, log-probs and no-speech probability are those of wm_transcribe_mel on row b alone with its own
+ * prompt (and sot_index = prompt_len[b] - sot_tail), bit for bit, whatever the other rows, the grouping and the lanes; with
+ * all lengths equal the call IS wm_transcribe_mel.  Inside, each decode group right-aligns its rows to its own longest
+ * prompt and steps through that many prompt positions.  Invalid: a prompt_len outside
+ * [1, prompt_stride], sot_tail outside [1, min prompt_len] when no_speech_prob_out is given, max prompt_len + max_new >
+ * n_text_ctx, a token outside the vocabulary among a row's first prompt_len[b], and everything wm_transcribe_mel rejects. */
+WM_API int wm_transcribe_mel_ragged(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                    const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                    int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                    int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out,
+                                    int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out, wm_mem mem);
+
 /* ------------------------------------------------------------- word-level timestamps --- */
 /* openai-whisper's find_alignment (whisper/timing.py) on the GPU, for the text tokens a transcription produced (e.g. each
  * chunk's tokens from the temperature step of wm_transcribe that it kept).  Per chunk with text tokens t[0 .. n), all < eot:

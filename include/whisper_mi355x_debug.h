@@ -46,6 +46,11 @@ WM_API int wmdbg_dec_gemv_resid(wm_ctx *ctx, const float *x, const float *W, con
  * out = the bf16 head outputs widened to f32.  nsplit in 1..8. */
 WM_API int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int T,
                         int n_keys, int nsplit, float *out);
+/* The decoder's causal self-attention launch at position pos with per-row offsets (ragged decode groups): sequence b
+ * attends to the cache rows [min(off[b], pos), pos] of k/v [B][H][T][64]; off i32 [B], each in [0, T).  The cache is used
+ * as given (rounded to bf16): rows outside that range may hold anything, NaN included. */
+WM_API int wmdbg_dec_self_attention_off(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int T,
+                                        int pos, const int32_t *off, float *out);
 
 /* ---- micro-benchmarks: average microseconds per launch over `iters` back-to-back launches
  * that cycle over n_mats weight matrices / n_slices cache slices (defeats L2 / MALL reuse). */
@@ -88,6 +93,11 @@ WM_API int wmdbg_set_tuning(const char *key, int value);
 /* The product's group policy as a pure function: decode groups of a wm_transcribe_greedy call of B chunks with `lanes` lanes
  * available; explicit_lanes != 0: the host set the lane count with wm_set_lanes (host only, no GPU). */
 WM_API int wmdbg_group_count(int B, int lanes, int explicit_lanes);
+/* The prompt table of one decode group of a wm_transcribe_mel_ragged call as a pure function (host only): rows
+ * [b0, b0 + Bg) of prompts [.][stride] with lengths prompt_len, right-aligned to the group's own longest prompt P (returned).
+ * table_out i32 [P][Bg] (room for stride * Bg), position-major like the device's token buffer; off_out i32 [Bg] = P - len. */
+WM_API int wmdbg_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, int32_t *table_out,
+                             int32_t *off_out);
 
 /* The Gumbel noise wm_transcribe's sampling adds at temperature > 0, computed by the DEVICE code (csrc/philox.h): g(n) of
  * ids n0 .. n0 + count - 1 for chunk `chunk` of a call and generated index gi, into host g[count]. */

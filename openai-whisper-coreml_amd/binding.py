@@ -114,6 +114,7 @@ def load_library(path=None):
         "wm_transcribe": [vp, vp, ip, ip, vp, ip, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
         "wm_logmel_long": [vp, vp, ip, vp, ip, ip, vp, ip],
         "wm_transcribe_mel": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
+        "wm_transcribe_mel_ragged": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
         "wm_set_token_budgets": [vp, vp, ip],
         "wm_set_alignment_heads": [vp, vp, vp, ip],
         "wm_align": [vp, vp, ip, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, vp, ip, ctypes.c_float, vp, vp, ip],
@@ -401,12 +402,38 @@ def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vo
     return segments, next_seek
 
 
+def conditioned_prompt(all_tokens, prompt_reset_since, sot_sequence, sot_prev, n_text_ctx):
+    """The prompt of a window under condition_on_previous_text (openai-whisper transcribe(): prompt =
+    all_tokens[prompt_reset_since:], and DecodingTask._get_initial_tokens): [sot_prev] + the last n_text_ctx // 2 - 1
+    tokens of that history + sot_sequence, or sot_sequence alone while the history is empty."""
+    prev = [int(t) for t in all_tokens[prompt_reset_since:]]
+    seq = [int(t) for t in sot_sequence]
+    if not prev:
+        return seq
+    return [int(sot_prev)] + prev[-(n_text_ctx // 2 - 1):] + seq
+
+
+def conditioned_history(all_tokens, prompt_reset_since, segments, temperature, skipped, prompt_reset_on_temperature=0.5):
+    """The history after a window (openai-whisper transcribe()): all_tokens grows by the tokens of the window's segments
+    (timestamps included; a cleared segment has none), then the prompt restarts behind them when the window's final
+    temperature exceeds prompt_reset_on_temperature.  A skipped window changes nothing.  Returns (all_tokens,
+    prompt_reset_since); the list passed in is not modified."""
+    if skipped:
+        return list(all_tokens), prompt_reset_since
+    grown = list(all_tokens) + [int(t) for sg in segments for t in sg["tokens"]]
+    if temperature > prompt_reset_on_temperature:
+        prompt_reset_since = len(grown)
+    return grown, prompt_reset_since
+
+
 def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_speech_token, lang_first=None,
                     lang_last=None, language=None, sot_prev=None, initial_prompt_tokens=None, recording_ids=None,
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
-                    no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None):
-    """openai-whisper transcribe() for recordings of any length, with condition_on_previous_text=False,
-    word_timestamps=False, no clip timestamps and no hallucination-silence threshold, batched across the recordings.
+                    no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None, condition_on_previous_text=False,
+                    prompt_reset_on_temperature=0.5):
+    """openai-whisper transcribe() for recordings of any length, with word_timestamps=False, no clip timestamps and no
+    hallucination-silence threshold, batched across the recordings.  condition_on_previous_text defaults to False here
+    (openai-whisper: True); see 5.
 
     1. One wm_logmel_long call for all recordings, kept on the device; content_frames = T_r - 3000.
     2. language None: per recording, openai-whisper's detect_language on mel[:, :3000] (wm_encode + the language-token
@@ -417,11 +444,20 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        (fallback_decode: transcribe_with_fallback's rule and seeds).  Row sample id = (window ordinal << 16) |
        recording id, so a recording's samples depend on itself only; recording ids default to 0 .. R - 1, < 65536.
     4. Per window: should_skip_window, else window_segments.
+    5. condition_on_previous_text=True (needs sot_prev): per recording, a window's prompt is conditioned_prompt() of the
+       recording's history -- initial_prompt_tokens, then the tokens of every kept window's segments, restarted behind a
+       window whose final temperature exceeds prompt_reset_on_temperature (conditioned_history()).  The rows of a round
+       then have prompts of different lengths and go out in ONE wm_transcribe_mel_ragged call per fallback step.  max_new
+       is min(n_text_ctx // 2, n_text_ctx - (n_text_ctx // 2 + 3)) for every window of such a run (221 at 448): a row's
+       budget depends neither on its own prompt nor on the other rows, so batched equals alone.  openai-whisper allows 224
+       tokens after a short prompt and 222 after a full one; only a window that fills its whole budget can tell.
+    initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
+    no prompt).  Without conditioning a recording's list heads every one of its windows; with it, it seeds the history.
     Sets the context's timestamp rules (wm_set_timestamp_rules: timestamp_begin, eot, max initial timestamp 1.0 s);
     suppress lists are the caller's (Context.set_suppress).  Returns per recording a dict: language (token id),
     segments (openai-whisper's keys id seek start end tokens temperature avg_logprob compression_ratio no_speech_prob, plus
     text with a Vocab), text (with a Vocab), seeks (the first frame of every decoded window) and windows (per window:
-    seek, segment_size, the fallback steps' temperatures, skipped)."""
+    seek, segment_size, the fallback steps' temperatures, skipped, prompt_len, prompt)."""
     R = len(recordings)
     rec_ids = list(range(R)) if recording_ids is None else [int(i) for i in recording_ids]
     if len(rec_ids) != R or any(i < 0 or i >= 65536 for i in rec_ids):
@@ -429,6 +465,15 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     n_ctx = int(ctx.dims["n_text_ctx"])
     n_mels = int(ctx.dims["n_mels"])
     max_new = n_ctx // 2
+    cond = bool(condition_on_previous_text)
+    if cond:
+        if sot_prev is None:
+            raise ValueError("condition_on_previous_text needs sot_prev")
+        max_new = min(n_ctx // 2, n_ctx - (n_ctx // 2 + 3))
+    per_rec = (initial_prompt_tokens is not None and len(initial_prompt_tokens) > 0
+               and all(isinstance(x, (list, tuple, np.ndarray)) for x in initial_prompt_tokens))
+    if per_rec and len(initial_prompt_tokens) != R:
+        raise ValueError("initial_prompt_tokens: one list per recording")
     if vocab_size is None:
         vocab_size = int(ctx.dims["n_vocab"])
     ctx.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
@@ -459,8 +504,17 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         if initial_prompt_tokens is not None:
             if sot_prev is None:
                 raise ValueError("initial_prompt_tokens need sot_prev")
-            head = [int(sot_prev)] + [int(t) for t in initial_prompt_tokens][-(n_ctx // 2 - 1):]
+            if not per_rec:
+                head = [int(sot_prev)] + [int(t) for t in initial_prompt_tokens][-(n_ctx // 2 - 1):]
         sot_index = len(head)
+        # per recording: the history of a conditioned run, or the fixed prompt tokens of its windows
+        if per_rec:
+            seeds = [[int(t) for t in x] for x in initial_prompt_tokens]
+        else:
+            seeds = [[int(t) for t in (initial_prompt_tokens if initial_prompt_tokens is not None else [])] for _ in range(R)]
+        all_tokens = [list(x) for x in seeds]
+        reset_since = [0] * R
+        ragged = cond or per_rec   # rows may differ in prompt length: wm_transcribe_mel_ragged, <|startoftranscript|> third from the end
         seek = [0] * R
         for r in range(R):
             out[r]["language"] = langs[r]
@@ -471,10 +525,20 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 break
             size = [min(N_FRAMES, content[r] - seek[r]) for r in live]
             ids = [((len(out[r]["windows"]) & 0xFFFF) << 16) | rec_ids[r] for r in live]
-            prompts = np.array([head + [int(sot), langs[r], int(task)] for r in live], dtype=np.int32)
+            if ragged:
+                plist = [conditioned_prompt(all_tokens[r], reset_since[r] if cond else 0, [int(sot), langs[r], int(task)],
+                                            sot_prev, n_ctx) for r in live]
+            else:
+                plist = [head + [int(sot), langs[r], int(task)] for r in live]
+                prompts = np.array(plist, dtype=np.int32)
 
             def decode(todo, t, sd):
                 rows = [live[i] for i in todo]
+                if ragged:
+                    return ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
+                                              [size[i] for i in todo], [plist[i] for i in todo], max_new, eot=eot,
+                                              temperature=t, seed=sd, no_speech_token=no_speech_token, sot_tail=3,
+                                              sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE)
                 return ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
                                           [size[i] for i in todo], prompts[todo], max_new, eot=eot, temperature=t,
                                           seed=sd, no_speech_token=no_speech_token, sot_index=sot_index,
@@ -491,12 +555,17 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                           logprob_threshold)
                 out[r]["seeks"].append(seek[r])
                 out[r]["windows"].append(dict(seek=seek[r], segment_size=size[i], temperatures=temps, skipped=skip,
-                                              tokens=[int(t) for t in res["tokens"][i, :n_text]]))
+                                              tokens=[int(t) for t in res["tokens"][i, :n_text]],
+                                              prompt_len=len(plist[i]), prompt=[int(t) for t in plist[i]]))
                 if skip:
                     seek[r] += size[i]
                     continue
                 segs, seek[r] = window_segments(res["tokens"][i, :n_text], seek[r], size[i], timestamp_begin, eot,
                                                 result, vocab)
+                if cond:
+                    all_tokens[r], reset_since[r] = conditioned_history(all_tokens[r], reset_since[r], segs,
+                                                                        result["temperature"], False,
+                                                                        prompt_reset_on_temperature)
                 for sg in segs:
                     sg["id"] = len(out[r]["segments"])
                     out[r]["segments"].append(sg)
@@ -799,10 +868,15 @@ class Context:
                                         logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index)
 
     def transcribe_mel_raw(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, opts=None,
-                           sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None):
+                           sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
+                           sot_tail=None):
         """wm_transcribe_mel: mel is a host f32 array (mem WM_MEM_HOST) or a device pointer (WM_MEM_DEVICE); mel_base i64,
         mel_len / seek / n_frames i32 [B]; prompts [B][n_prompt]; sample_ids u32 [B] or None.  Returns (tokens, lens,
-        logprobs or None, no_speech_prob or None)."""
+        logprobs or None, no_speech_prob or None).
+        Prompts of different lengths -- a list of B lists, or prompts [B][stride] with prompt_len i32 [B] -- go to
+        wm_transcribe_mel_ragged with sot_tail (<|startoftranscript|> is the sot_tail-th token from the end of every
+        prompt; default 1, opts.sot_index is not read).  A list of lists of ONE length without prompt_len stays
+        wm_transcribe_mel; there a sot_tail, when given, replaces opts.sot_index by n_prompt - sot_tail."""
         if budgets is not None:
             self.set_token_budgets(budgets)
         base = np.ascontiguousarray(mel_base, dtype=np.int64)
@@ -810,9 +884,21 @@ class Context:
         mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (B,)))
         sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (B,)))
         nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
+        plen = None
+        if prompt_len is not None:
+            plen = np.ascontiguousarray(prompt_len, dtype=np.int32)
+        elif not isinstance(prompts, np.ndarray) and len(prompts) > 0 and np.ndim(prompts[0]) == 1 \
+                and len({len(p) for p in prompts}) > 1:
+            plen = np.array([len(p) for p in prompts], dtype=np.int32)
+            padded = np.zeros((len(prompts), int(plen.max())), dtype=np.int32)
+            for i, p in enumerate(prompts):
+                padded[i, :len(p)] = np.asarray(p, dtype=np.int32)
+            prompts = padded
         pr = np.ascontiguousarray(prompts, dtype=np.int32)
         if pr.ndim == 1:
             pr = np.ascontiguousarray(np.broadcast_to(pr, (B, pr.size)))
+        if plen is None and sot_tail is not None and opts is not None:
+            opts = wm_decode_opts(opts.temperature, opts.seed, opts.no_speech_token, pr.shape[1] - int(sot_tail))
         ids = None if sample_ids is None else np.ascontiguousarray(sample_ids, dtype=np.uint32)
         if mem == WM_MEM_HOST:
             mel = np.ascontiguousarray(mel, dtype=np.float32)
@@ -823,6 +909,15 @@ class Context:
         lens = np.empty(B, dtype=np.int32)
         lp = np.empty((B, max_new), dtype=np.float32) if logprobs else None
         ns = np.empty(B, dtype=np.float32) if no_speech else None
+        if plen is not None:
+            if plen.shape != (B,):
+                raise ValueError("prompt_len: one length per row")
+            _check(self.lib, self.lib.wm_transcribe_mel_ragged(
+                self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr), pr.shape[1], _ptr(plen),
+                1 if sot_tail is None else int(sot_tail), _ptr(ids) if ids is not None else None, max_new, eot,
+                ctypes.byref(opts) if opts is not None else None, _ptr(toks), _ptr(lens),
+                _ptr(lp) if lp is not None else None, _ptr(ns) if ns is not None else None, mem))
+            return toks, lens, lp, ns
         _check(self.lib, self.lib.wm_transcribe_mel(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr),
                                                     pr.shape[1], _ptr(ids) if ids is not None else None, max_new, eot,
                                                     ctypes.byref(opts) if opts is not None else None, _ptr(toks),
@@ -831,12 +926,14 @@ class Context:
         return toks, lens, lp, ns
 
     def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
-                       no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None):
-        """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult."""
+                       no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
+                       sot_tail=None):
+        """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
+        Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw."""
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         toks, lens, lp, ns = self.transcribe_mel_raw(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot, opts,
                                                      sample_ids, logprobs=True, no_speech=no_speech_token >= 0, mem=mem,
-                                                     budgets=budgets)
+                                                     budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail)
         return TranscribeResult(toks, lens, lp, ns, eot)
 
     def transcribe_long(self, recordings, **kw):

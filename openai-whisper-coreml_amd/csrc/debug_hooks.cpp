@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/whisper_mi355x_debug.h"
@@ -36,6 +37,14 @@ extern "C" int wmdbg_set_tuning(const char *key, int value) {
 }
 
 extern "C" int wmdbg_group_count(int B, int lanes, int explicit_lanes) { return wm_group_count(B, lanes, explicit_lanes != 0, 0); }
+extern "C" int wmdbg_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg,
+                                 int32_t *table_out, int32_t *off_out) {
+    std::vector<int32_t> table, off;
+    const int P = wm_right_align(prompts, stride, prompt_len, b0, Bg, table, off);
+    std::copy(table.begin(), table.end(), table_out);
+    std::copy(off.begin(), off.end(), off_out);
+    return P;
+}
 extern "C" int wmdbg_lane_parts(int B, int lanes, int explicit_lanes, int n_text_state) {
     return wm_lane_parts(B, lanes, explicit_lanes != 0, n_text_state, 0);
 }
@@ -343,6 +352,42 @@ extern "C" int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, 
     }
     (void)hipFree(datt);
     (void)hipFree(dq); (void)hipFree(dk); (void)hipFree(dv); (void)hipFree(dp);
+    return rc;
+}
+
+// The production self-attention launch of a ragged decode group: position `pos`, sequence b's keys [min(off[b], pos), pos].
+extern "C" int wmdbg_dec_self_attention_off(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int T,
+                                            int pos, const int32_t *off, float *out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(q && k && v && off && out, WM_ERR_INVALID, "dec_self_attention_off: null pointer");
+    WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && T >= 1 && pos >= 0 && pos < T, WM_ERR_INVALID, "dec_self_attention_off: bad geometry");
+    for (int b = 0; b < B; ++b)
+        WM_REQUIRE(off[b] >= 0 && off[b] < T, WM_ERR_INVALID, "dec_self_attention_off: off[%d] = %d outside [0, %d)", b, off[b], T);
+    std::vector<bf16_t> k16, v16;
+    to_bf16(k, k16, (size_t)B * H * T * 64);
+    to_bf16(v, v16, (size_t)B * H * T * 64);
+    void *dq, *dk, *dv, *doff, *dpos, *datt;
+    hipStream_t s = ctx->stream;
+    WM_TRY(up(&dq, q, (size_t)B * H * 64 * 4, s));
+    WM_TRY(up(&dk, k16.data(), k16.size() * 2, s));
+    WM_TRY(up(&dv, v16.data(), v16.size() * 2, s));
+    WM_TRY(up(&doff, off, (size_t)B * 4, s));
+    WM_TRY(up(&dpos, &pos, 4, s));
+    WM_TRY(up(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
+    int rc = wm_dec_self_attention(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, B, H, T, 0, (const int *)dpos,
+                                   (bf16_t *)datt, nullptr, 0, 0, nullptr, nullptr, (const int *)doff);
+    if (rc == WM_OK) {
+        const size_t Bpad = ((size_t)B + 15) / 16 * 16, dd = (size_t)H * 64;
+        std::vector<bf16_t> o16(Bpad * dd), lin((size_t)B * dd);
+        WM_HIP(hipMemcpyAsync(o16.data(), datt, o16.size() * 2, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+        for (size_t b = 0; b < (size_t)B; ++b)
+            for (size_t j = 0; j < dd; ++j) lin[b * dd + j] = o16[wm_tiled_offset(b, j, dd)];
+        from_bf16(lin, out);
+    }
+    void *fr[] = {dq, dk, dv, doff, dpos, datt};
+    for (void *p : fr)
+        if (p) (void)hipFree(p);
     return rc;
 }
 

@@ -672,18 +672,22 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const bf16_t *__restrict__
 
 // ------------------------------------------------------------------ token embedding ------
 // x[b] = token_embedding[seq[pos][b]] + positional_embedding[pos]  (+ LayerNorm partial statistics)
+// off (nullable, [B]): a ragged decode group -- row b's prompt starts at position off[b] of the group, so its positional
+// row is pos - off[b] (0 while the row has not started)
 __global__ __launch_bounds__(256) void dec_embed_kernel(const int *__restrict__ seq, const int *__restrict__ pos_ptr,
                                                         int B, const bf16_t *__restrict__ emb,
                                                         const float *__restrict__ pemb, int d,
                                                         float *__restrict__ x, bf16_t *__restrict__ xb,
-                                                        float *__restrict__ stats_out, float *__restrict__ mean_buf) {
+                                                        float *__restrict__ stats_out, float *__restrict__ mean_buf,
+                                                        const int *__restrict__ off) {
     __shared__ float r1[4], r2[4];
     const int b = blockIdx.x;
     const int pos = *pos_ptr;
     const long tok = seq[pos * B + b];
+    const int prow = off ? max(pos - off[b], 0) : pos;
     float s1 = 0.f, s2 = 0.f;
     for (int j = threadIdx.x; j < d; j += 256) {
-        const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)pos * d + j];
+        const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
         x[(long)b * d + j] = v;
         s1 += v;
         s2 += v * v;
@@ -860,12 +864,31 @@ struct AttnCold {
     const char *pf_ptr;
     long pf_tile_bytes;
 };
-template <int NS, int U, bool NT, bool DEEP = false>
+// RAGGED DECODE GROUPS (OFF, the self-attention only).  The rows of a group whose prompts differ in length are right-aligned:
+// sequence b's first token sits at position off[b] of the group, so its keys are the cache rows [min(off[b], pos), pos].  The
+// pair's K/V base pointers are advanced by that many rows and every row index below -- stream and block assignment, masks,
+// merge order -- is RELATIVE to it: a row's bits are those of the same keys at the front of a cache with offset 0.  A
+// sequence that has not started (pos < off[b]) attends to its one current row, which keeps it finite; nothing of it is kept.
+// The offset is a load in FRONT of the speculative first block, which is why this is an instantiation of its own: uniform
+// groups run the kernel they always ran.  Its pointer takes the place of `att` in the last preloaded dwords (14-15), and the
+// first pair's offset is requested in the scalar burst for the row that pair has while every row is live (a group's whole
+// prompt phase); only once the live list has been compacted does it cost a dependent load.
+struct AttnColdOff {
+    const int *off;   // [>= rows of the group]
+    bf16_t *att;
+    float *part;
+    const char *pf_ptr;
+    long pf_tile_bytes;
+};
+template <bool OFF> struct AttnColdSel { typedef AttnCold type; };
+template <> struct AttnColdSel<true> { typedef AttnColdOff type; };
+template <int NS, int U, bool NT, bool DEEP = false, bool OFF = false>
 __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
     const int *__restrict__ pos_ptr, const int *__restrict__ live_rows /* [WM_DEC_MAXB] rows | [1] count, or null */,
     unsigned packA /* H | nsplit << 8 | flat_wpw << 16 */, unsigned packB /* T_stride | n_keys_const << 16 */,
-    unsigned packC /* n_bh | n_wg << 16 */, AttnCold cold) {
+    unsigned packC /* n_bh | n_wg << 16 */, typename AttnColdSel<OFF>::type cold) {
+    static_assert(!OFF || (NS == 4 && !DEEP), "row offsets: the causal self-attention only");
     const int H = (int)(packA & 0xffu), nsplit = (int)((packA >> 8) & 0xffu), flat_wpw = (int)(packA >> 16);
     const int T_stride = (int)(packB & 0xffffu), n_keys_const = (int)(packB >> 16);
     const int n_bh_full = (int)(packC & 0xffffu), n_wg = (int)(packC >> 16);
@@ -896,6 +919,8 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     const int *dummy = (const int *)q;
     const int pos_raw = *(pos_ptr ? pos_ptr : dummy);
     const int nl_raw = *(n_live_ptr ? n_live_ptr : dummy);
+    int off_raw = 0;
+    if constexpr (OFF) off_raw = cold.off[bh0 / H];
     // Early stop: sequences that have emitted <|endoftext|> (or used up their token budget) leave the decode group.
     // The arg-max kernel keeps a COMPACT list of the live rows; the pairs walked here are (live row, head), dealt to the
     // workgroups exactly like the full set, so the cache of a finished sequence is never read again and the remaining
@@ -906,6 +931,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     };
     bool first = true;
     int n_bh = n_bh_full, n_keys = n_keys_const;
+    int pos_k = 0;  // OFF: the position, once known
     // n_wg <= n_bh workgroups (per split) walk the (sequence, head) pairs
     for (int pi = bh0; pi < n_bh; pi += bh_step) {
         if (flat_wpw == 0 && !first) __syncthreads();  // the previous pair's merge has been read
@@ -917,6 +943,20 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         const bf16_t *vb = vc + (long)bh * T_stride * 64 + e8 * 8;
         const f32x4 *qp = (const f32x4 *)(q + (long)b * d + h * 64 + e8 * 8);
         const f32x4 q0 = qp[0], q1 = qp[1];
+        int ob = 0;       // OFF: first cache row of this pair; row indices from here on are relative to it
+        int clamp0 = first ? n_clamp : n_keys - 1;
+        if constexpr (OFF) {
+            if (first) {
+                ob = b == bh0 / H ? off_raw : cold.off[b];   // (the position is not known yet: see below)
+                clamp0 = n_clamp - ob;
+            } else {
+                ob = cold.off[b];
+                ob = ob < pos_k ? ob : pos_k;
+                clamp0 = pos_k - ob;
+            }
+            kb += (long)ob * 64;
+            vb += (long)ob * 64;
+        }
         // SPEC: the first block (DEEP: every block) of this stream is requested BEFORE the position / live count / query is
         // looked at.  (This kernel serves the self-attention and the flat, deep cross-attention of a few pairs -- the latency
         // shapes; the streaming cross-attention is dec_xrows_attn_kernel, the round-4 loop.)
@@ -926,7 +966,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         if (SPEC) {
 #pragma unroll
             for (int blk = 0; blk < NB; ++blk)
-                load_block(kb, vb, blk * (NS * 8 * U), first ? n_clamp : n_keys - 1, kall[blk], vall[blk]);
+                load_block(kb, vb, blk * (NS * 8 * U), clamp0, kall[blk], vall[blk]);
         }
         if (first) {
             // (the empty asm ties the first USE of the two scalar loads to the arrival of the query: without it the
@@ -937,7 +977,18 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
             if (pos_ptr) n_keys = pos_v + 1;
             first = false;
             if (pi >= n_bh) break;  // (workgroup- / wave-uniform) the speculative pair is not live
+            if constexpr (OFF) {
+                pos_k = n_keys - 1;
+                if (pos_k < ob) {   // (workgroup-uniform) a sequence that has not started: its one key is the current row
+                    kb -= (long)(ob - pos_k) * 64;
+                    vb -= (long)(ob - pos_k) * 64;
+                    ob = pos_k;
+                    load_block(kb, vb, 0, 0, kall[0], vall[0]);
+                }
+            }
         }
+        int nk = n_keys;  // keys of this pair
+        if constexpr (OFF) nk = pos_k + 1 - ob;
         float qe[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -947,7 +998,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         float m_run = -1e30f, l_run = 0.f;
         float oa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         auto process_block = [&](int r0, const u32x4 (&kv)[U], const u32x4 (&vv)[U]) {
-            attn_block<NS, U, SELF>(qe, r0, stream, rg, n_keys, kv, vv, m_run, l_run, oa);
+            attn_block<NS, U, SELF>(qe, r0, stream, rg, nk, kv, vv, m_run, l_run, oa);
         };
         if (DEEP) {
             // LATENCY shape (a handful of pairs: tiny.en single chunk = 48 waves on the whole chip): a stream's rows are
@@ -955,15 +1006,15 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
             // was requested above (48 x 16 B per lane); the same block arithmetic in the same order: same bits.
 #pragma unroll
             for (int blk = 0; blk < NB; ++blk)
-                if (blk * (NS * 8 * U) < n_keys) process_block(blk * (NS * 8 * U), kall[blk], vall[blk]);  // workgroup-uniform
+                if (blk * (NS * 8 * U) < nk) process_block(blk * (NS * 8 * U), kall[blk], vall[blk]);  // workgroup-uniform
         } else {
             if (SPEC) {
                 attn_block_fence<U>(kall[0], vall[0]);
                 process_block(0, kall[0], vall[0]);
             }
-            for (int r0 = SPEC ? NS * 8 * U : 0; r0 < n_keys; r0 += NS * 8 * U) {  // workgroup-uniform trip count
+            for (int r0 = SPEC ? NS * 8 * U : 0; r0 < nk; r0 += NS * 8 * U) {  // workgroup-uniform trip count
                 u32x4 kv[U], vv[U];
-                load_block(kb, vb, r0, n_keys - 1, kv, vv);
+                load_block(kb, vb, r0, nk - 1, kv, vv);
                 attn_block_fence<U>(kv, vv);
                 process_block(r0, kv, vv);
             }
@@ -1325,7 +1376,7 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
                                                   float *__restrict__ stats_out, const WmTsDev &ts,
                                                   int *__restrict__ arrive, int fallback_tok,
                                                   float *__restrict__ mean_buf, const WmStopDev &stop, int rpw,
-                                                  const WmXDev &xd) {
+                                                  const WmXDev &xd, const int *__restrict__ off) {
     __shared__ int tok_s[16];
     __shared__ int is_last_s;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1529,6 +1580,8 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
     if (x && pos + 1 < n_ctx) {
         for (int b = bw + wave; b < B && b < bw + nrows; b += 16) {
             const long tok = tok_s[b - bw];
+            // a ragged group (off != null): row b's prompt starts at position off[b], its positional row counts from there
+            const int prow = off ? max(pos + 1 - off[b], 0) : pos + 1;
             float s1 = 0.f, s2 = 0.f;
             // the row stays in registers between the sums and the mean-centred bf16 copy (the first 512 columns: 8 values per lane; the
             // round-4 kernel re-read what it had just stored: a store -> load round trip through L2 on the step's tail)
@@ -1539,7 +1592,7 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
                 const int j = lane + 64 * i;
                 ev[i] = 0.f;
                 if (j < d) {
-                    const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)(pos + 1) * d + j];
+                    const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
                     x[(long)b * d + j] = v;
                     ev[i] = v;
                     s1 += v;
@@ -1547,7 +1600,7 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
                 }
             }
             for (int j = lane + 64 * EV; j < d; j += 64) {  // (wider models than any Whisper: the re-reading path)
-                const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)(pos + 1) * d + j];
+                const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
                 x[(long)b * d + j] = v;
                 s1 += v;
                 s2 += v * v;
@@ -1628,10 +1681,11 @@ __global__ __launch_bounds__(1024) void argmax_embed_kernel(const unsigned long 
                                                              float *__restrict__ x, bf16_t *__restrict__ xb,
                                                              float *__restrict__ stats_out, WmTsDev ts,
                                                              int *__restrict__ arrive, int fallback_tok,
-                                                             float *__restrict__ mean_buf, WmStopDev stop, int rpw) {
+                                                             float *__restrict__ mean_buf, WmStopDev stop, int rpw,
+                                                             const int *__restrict__ off) {
     const WmXDev none = {};
     argmax_embed_body<false>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first, emb, pemb, d, n_ctx, x, xb,
-                             stats_out, ts, arrive, fallback_tok, mean_buf, stop, rpw, none);
+                             stats_out, ts, arrive, fallback_tok, mean_buf, stop, rpw, none, off);
 }
 __global__ __launch_bounds__(1024) void argmax_embed_x_kernel(const unsigned long long *__restrict__ tilemax,
                                                                int n_tiles, int B, int *__restrict__ seq,
@@ -1643,9 +1697,9 @@ __global__ __launch_bounds__(1024) void argmax_embed_x_kernel(const unsigned lon
                                                                float *__restrict__ stats_out, WmTsDev ts,
                                                                int *__restrict__ arrive, int fallback_tok,
                                                                float *__restrict__ mean_buf, WmStopDev stop, int rpw,
-                                                               WmXDev xd) {
+                                                               WmXDev xd, const int *__restrict__ off) {
     argmax_embed_body<true>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first, emb, pemb, d, n_ctx, x, xb,
-                            stats_out, ts, arrive, fallback_tok, mean_buf, stop, rpw, xd);
+                            stats_out, ts, arrive, fallback_tok, mean_buf, stop, rpw, xd, off);
 }
 
 // the DE_LOGITS_X epilogue's Gumbel noise for a range of ids (test hook)
@@ -1938,9 +1992,9 @@ int wm_ln_fold(wm_ctx *ctx, const bf16_t *W, const float *g, const float *beta, 
 }
 
 int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const bf16_t *emb, const float *pemb,
-                 int d, float *x, bf16_t *xb, float *stats_out, float *mean_buf) {
+                 int d, float *x, bf16_t *xb, float *stats_out, float *mean_buf, const int *off) {
     WmProfScope ps(&ctx->prof, "dec_embed", ctx->stream);
-    dec_embed_kernel<<<B, 256, 0, ctx->stream>>>(seq, pos_ptr, B, emb, pemb, d, x, xb, stats_out, mean_buf);
+    dec_embed_kernel<<<B, 256, 0, ctx->stream>>>(seq, pos_ptr, B, emb, pemb, d, x, xb, stats_out, mean_buf, off);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
@@ -2094,7 +2148,7 @@ int wm_dec_xattn_fq(wm_ctx *ctx, const DecGemvArgs &qa, const bf16_t *kc, const 
 
 int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int B, int H, int T_stride,
                           int n_keys, const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k,
-                          const int *live_rows, const int *n_live) {
+                          const int *live_rows, const int *n_live, const int *off) {
     WM_REQUIRE(T_stride <= ATT_MAXK && n_keys <= ATT_MAXK && (pos_ptr || n_keys >= 1), WM_ERR_INVALID,
                "dec_self_attention: 1..%d keys", ATT_MAXK);
     WM_REQUIRE(H >= 1 && H <= 255 && B * H < 65536, WM_ERR_INVALID, "dec_self_attention: %d heads x %d rows do not fit the packed arguments", H, B);
@@ -2110,7 +2164,13 @@ int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const b
     const AttnCold cold = {att, nullptr, (const char *)pf_ptr, tile_bytes};
     const unsigned pA = (unsigned)H | (1u << 8), pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
     const unsigned pC = (unsigned)(B * H) | ((unsigned)(B * H) << 16);
-    dec_rows_attn_kernel<4, 4, false><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
+    if (off) {   // a ragged decode group: the instantiation that places every pair at its row offset
+        const AttnColdOff cold_off = {off, att, nullptr, (const char *)pf_ptr, tile_bytes};
+        dec_rows_attn_kernel<4, 4, false, false, true><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, live_rows, pA, pB, pC,
+                                                                                    cold_off);
+    } else {
+        dec_rows_attn_kernel<4, 4, false><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
+    }
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
@@ -2118,7 +2178,7 @@ int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const b
 int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, int B, int *seq, int *pos_ptr,
                     int n_prompt, int *result, int arg_first, const bf16_t *emb, const float *pemb, int d, int n_ctx,
                     float *x, bf16_t *xb, float *stats_out, const WmTsDev *ts, int *arrive, int fallback_tok,
-                    float *mean_buf, const WmStopDev *stop, const WmXDev *xd) {
+                    float *mean_buf, const WmStopDev *stop, const WmXDev *xd, const int *off) {
     WmProfScope ps(&ctx->prof, "argmax_embed", ctx->stream);
     WmTsDev t;
     memset(&t, 0, sizeof(t));
@@ -2139,11 +2199,11 @@ int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles,
         WM_REQUIRE(pos_ptr != nullptr, WM_ERR_INVALID, "argmax_embed: the extended decode needs the device position");
         argmax_embed_x_kernel<<<grid, 1024, 0, ctx->stream>>>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first,
                                                               emb, pemb, d, n_ctx, x, xb, stats_out, t, arrive, fallback_tok,
-                                                              mean_buf, sp, rpw, *xd);
+                                                              mean_buf, sp, rpw, *xd, off);
     } else {
         argmax_embed_kernel<<<grid, 1024, 0, ctx->stream>>>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first,
                                                             emb, pemb, d, n_ctx, x, xb, stats_out, t, arrive, fallback_tok,
-                                                            mean_buf, sp, rpw);
+                                                            mean_buf, sp, rpw, off);
     }
     WM_HIP(hipGetLastError());
     return WM_OK;

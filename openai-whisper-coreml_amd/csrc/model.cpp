@@ -58,6 +58,7 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc_t(m, &m->dresult, WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dseq, (size_t)WM_DEC_MAXB * (D.n_text_ctx + 1), s));
     WM_TRY(dalloc_t(m, &m->dpos, 4, s));
+    WM_TRY(dalloc_t(m, &m->doff, WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->darrive, 4, s));
     WM_TRY(dalloc_t(m, &m->ddone, WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dbudget, WM_DEC_MAXB, s));
@@ -578,6 +579,7 @@ int wm_model_decode_begin(wm_ctx *ctx, int B) {
     WM_HIP(hipMemsetAsync(m->darrive, 0, sizeof(int), ctx->stream));
     m->stop_on = false;   // wm_transcribe_greedy switches it on for its own decode (lane_prefill)
     m->x_on = false;      // ... and wm_transcribe its extended decode
+    m->off_on = false;    // ... and wm_transcribe_mel_ragged the row offsets of a ragged group
     m->xattn_shared = false;   // ... and decides whether the group shares the chip
     return WM_OK;
 }
@@ -621,7 +623,8 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         a.pos_ptr = m->dpos; a.n_ctx = T; a.n_head = H;
         WM_TRY(wm_dec_gemv(ctx, a));
         // 2. causal self-attention over positions 0..pos
-        WM_TRY(wm_dec_self_attention(ctx, m->dq, kc, vc, B, H, T, 0, m->dpos, m->datt, L.wo, d, d, live, nlive));
+        WM_TRY(wm_dec_self_attention(ctx, m->dq, kc, vc, B, H, T, 0, m->dpos, m->datt, L.wo, d, d, live, nlive,
+                                     m->off_on ? m->doff : nullptr));
         // 3. out-projection + residual (f32 stream, its bf16 copy, partial statistics)
         memset(&a, 0, sizeof(a));
         a.epi = DE_RESID; a.B = B; a.N = d; a.K = d; a.W = L.wo; a.c2 = L.bo;
@@ -696,7 +699,8 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
 
 int wm_model_embed_first(wm_ctx *ctx, int B) {
     WmModel *m = ctx->model;
-    return wm_dec_embed(ctx, m->dseq, m->dpos, B, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dx, m->dxb, m->dstats, m->dmean);
+    return wm_dec_embed(ctx, m->dseq, m->dpos, B, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dx, m->dxb, m->dstats, m->dmean,
+                        m->off_on ? m->doff : nullptr);
 }
 
 int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, bool use_ts, bool x) {
@@ -707,5 +711,5 @@ int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *r
     return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, write_seq ? m->dseq : nullptr, m->dpos, n_prompt, result,
                            arg_first, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dims.n_text_ctx, m->dx, m->dxb,
                            m->dstats, use_ts ? &t : nullptr, m->darrive, use_ts ? m->ts_eot : arg_first, m->dmean,
-                           m->stop_on ? &sp : nullptr, x ? &xd : nullptr);
+                           m->stop_on ? &sp : nullptr, x ? &xd : nullptr, m->off_on ? m->doff : nullptr);
 }

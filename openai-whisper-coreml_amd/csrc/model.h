@@ -194,6 +194,12 @@ struct WmModel {
     int *dresult = nullptr;     // [16] arg-max result relative to arg_first
     int *dseq = nullptr;        // [n_text_ctx][16->B] token sequence (prompt, then generated), position-major
     int *dpos = nullptr;        // [1] current decode position (read by every decode kernel)
+    // A RAGGED decode group (wm_transcribe_mel_ragged): prompts of different lengths, right-aligned to the longest (P), so
+    // that every row generates its first token at position P - 1 and everything about "prompt or generated" stays one
+    // scalar per group.  Row b's prompt starts at position doff[b] = P - len_b: its positional embedding and the first key
+    // of its causal self-attention count from there (dec_kernels.hip).  Uploaded at prefill like dx_ids.
+    int *doff = nullptr;        // [WM_DEC_MAXB]
+    bool off_on = false;        // the decode being enqueued is ragged (kernel arguments of the captured graphs)
     int *darrive = nullptr;     // [1] arrival counter of the arg-max workgroups (zero between launches)
     // early stop (wm_transcribe_greedy with eot >= 0 or per-chunk token budgets): see WmStopDev
     int *ddone = nullptr, *dbudget = nullptr, *dlive = nullptr, *dnlive = nullptr;
@@ -215,7 +221,7 @@ struct WmModel {
     // pass to the next) instead of re-capturing ~2300 launches every time the shape changes (measured: the capture is
     // host work of a few ms that hides behind the lane's own encoder, so this is tidiness, not throughput).
     struct GraphSet {
-        int B = 0, n_prompt = 0, cap_b = 0, mask = 0, stop_key = 0;  // mask: bit 0 suppress, 1 timestamps, 2 X mode
+        int B = 0, n_prompt = 0, cap_b = 0, mask = 0, stop_key = 0;  // mask: bit 0 suppress, 1 timestamps, 2 X mode, 3 ragged
         // [mode]: 0 = the group has the chip to itself, 1 = it shares it (xattn_shared: short-lived cross-attention
         // workgroups); chosen burst by burst from the number of decodes in flight on the device, captured on first use
         int burst[2] = {0, 0};
@@ -419,8 +425,10 @@ int wm_dec_gemv_split(int K, int *spw);
 int wm_ln_fold(wm_ctx *ctx, const bf16_t *W, const float *g, const float *beta, const float *bias /*nullable*/, int N,
                int K, bf16_t *Wf, float *c1, float *c2);
 // x[b] = token_embedding[seq[*pos_ptr][b]] + positional_embedding[*pos_ptr]
+// off (device [B], nullable: all 0): the row offsets of a ragged decode group -- row b's positional row is
+// max(*pos_ptr - off[b], 0); the same argument of wm_argmax_embed, and of wm_dec_self_attention (keys [min(off[b], pos), pos])
 int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const bf16_t *emb, const float *pemb,
-                 int d, float *x, bf16_t *xb, float *stats_out, float *mean_buf /*nullable*/);
+                 int d, float *x, bf16_t *xb, float *stats_out, float *mean_buf /*nullable*/, const int *off = nullptr);
 // Single-query attention over a K/V cache [B][H][T_stride][64] -> bf16 head outputs att[B][H*64] in WL_TILED order.
 // Keys 0 .. n-1 with n = *pos_ptr + 1 when pos_ptr != null, else n_keys.
 int wm_dec_attn_splits(int B, int H);
@@ -431,7 +439,8 @@ int wm_dec_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t
 // The decoder's causal self-attention (<= 448 cached rows per pair): one 4-wave workgroup per (sequence, head).
 int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int B, int H, int T_stride,
                           int n_keys, const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0,
-                          int pf_k = 0, const int *live_rows = nullptr, const int *n_live = nullptr);
+                          int pf_k = 0, const int *live_rows = nullptr, const int *n_live = nullptr,
+                          const int *off = nullptr);
 // Close a decode step (one workgroup): reduce the per-tile packed maxima of a DE_LOGITS launch;
 // chosen token of row b -> seq[(*pos_ptr + 1) * B + b] when that position is >= n_prompt;
 // (token - arg_first) -> result[b]; embed the tokens of position *pos_ptr + 1 into x (+ LayerNorm
@@ -442,7 +451,7 @@ int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles,
                     int n_prompt, int *result, int arg_first, const bf16_t *emb, const float *pemb, int d, int n_ctx,
                     float *x, bf16_t *xb, float *stats_out, const WmTsDev *ts = nullptr, int *arrive = nullptr,
                     int fallback_tok = 0, float *mean_buf = nullptr, const WmStopDev *stop = nullptr,
-                    const WmXDev *xd = nullptr);
+                    const WmXDev *xd = nullptr, const int *off = nullptr);
 // Gumbel noise g(n) of ids n0 .. n0 + count - 1 as the DE_LOGITS_X epilogue computes it (philox.h), into device memory
 int wm_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int n0, int count, float *out);
 // start of a decode with early stop: no row done, every row live

@@ -389,6 +389,7 @@ struct LaneJob {
     enum State { IDLE, DECODING, DRAINING };
     wm_ctx *c = nullptr;
     int b0 = 0, Bg = 0;
+    int P = 0;          // prompt positions of the group (a ragged call: the longest prompt among ITS rows)
     State state = IDLE;
     int t = 0;          // decoder positions enqueued so far
     int bursts = 0;     // bursts enqueued so far
@@ -400,6 +401,7 @@ struct LaneJob {
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
     std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
     std::vector<unsigned> ids;     // its sample ids (wm_transcribe_mel)
+    std::vector<int32_t> off;      // its row offsets (wm_transcribe_mel_ragged)
     float stage_sum[3] = {0.f, 0.f, 0.f};
     ~LaneJob() {
         if (c) (void)hipStreamSynchronize(c->stream);  // error paths: nothing may outlive pr / gen / bud
@@ -419,6 +421,8 @@ struct TxSrc {
     const int32_t *mel_len = nullptr, *seek = nullptr, *n_frames = nullptr;
     const int32_t *prompt = nullptr;   // row b's prompt: prompt + b * prompt_stride (0: one prompt for all)
     int prompt_stride = 0;
+    const int32_t *prompt_len = nullptr;   // non-null: a ragged call, row b's prompt is its first prompt_len[b] entries
+    int sot_tail = 0;                      // ... whose <|startoftranscript|> is entry prompt_len[b] - sot_tail
     const uint32_t *sample_ids = nullptr;
 };
 
@@ -437,6 +441,28 @@ struct XCfg {
     float *no_speech = nullptr;    // [B] host, nullable
 };
 
+}  // namespace
+
+// The prompt table of ONE decode group of a ragged call (pure: tests pin it through the debug library): rows
+// [b0, b0 + Bg) of prompts [.][stride], right-aligned to the group's own longest prompt P.  table [P][Bg] position-major
+// like dseq, off [Bg] = P - len.  The positions in front of a row's prompt repeat its first token: any valid id would
+// do, nothing decoded there is kept.
+int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, std::vector<int32_t> &table,
+                   std::vector<int32_t> &off) {
+    int P = 0;
+    for (int b = 0; b < Bg; ++b) P = std::max(P, (int)prompt_len[b0 + b]);
+    table.resize((size_t)P * Bg);
+    off.resize(Bg);
+    for (int b = 0; b < Bg; ++b) {
+        const int32_t *row = prompts + (size_t)(b0 + b) * stride;
+        const int o = P - prompt_len[b0 + b];
+        off[b] = o;
+        for (int t = 0; t < P; ++t) table[(size_t)t * Bg + b] = row[t < o ? 0 : t - o];
+    }
+    return P;
+}
+
+namespace {
 // front end -> encoder -> cross K/V -> prompt upload -> first embedding, all enqueued on the lane's stream
 int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const StopCfg &stop, const XCfg &xc) {
     wm_ctx *c = j.c;
@@ -461,9 +487,15 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
     // decode state first (prompt tokens [n_prompt][Bg], position 0): a pageable H2D copy may wait for the
     // stream to drain, so it is issued while the lane is still idle
     WM_TRY(wm_model_decode_begin(c, Bg));
-    j.pr.resize((size_t)n_prompt * Bg);
-    for (int t = 0; t < n_prompt; ++t)
-        for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = src.prompt[(size_t)(j.b0 + b) * src.prompt_stride + t];
+    if (src.prompt_len) {   // ragged: right-aligned to the group's longest prompt (n_prompt = j.P), offsets next to it
+        wm_right_align(src.prompt, src.prompt_stride, src.prompt_len, j.b0, Bg, j.pr, j.off);
+        WM_HIP(hipMemcpyAsync(m->doff, j.off.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
+    } else {
+        j.pr.resize((size_t)n_prompt * Bg);
+        for (int t = 0; t < n_prompt; ++t)
+            for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = src.prompt[(size_t)(j.b0 + b) * src.prompt_stride + t];
+    }
+    m->off_on = src.prompt_len != nullptr;
     WM_HIP(hipMemcpyAsync(m->dseq, j.pr.data(), j.pr.size() * 4, hipMemcpyHostToDevice, c->stream));
     WM_TRY(wm_model_set_pos(c, 0));
     // early-stop state of this group: done flags, live list, per-row budgets (kernel arguments of the decode graphs)
@@ -484,6 +516,7 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
         j.xpar = xc.par;
         j.xpar.chunk0 = j.b0;
         j.xpar.n_prompt = n_prompt;
+        if (src.prompt_len && xc.no_speech) j.xpar.sot_pos = n_prompt - src.sot_tail;   // the same distance from every row's end
         j.xpar.ids_on = src.sample_ids ? 1 : 0;
         if (src.sample_ids) {   // caller-given Philox counter words (wm_transcribe_mel): a row's noise follows its id
             j.ids.assign(src.sample_ids + j.b0, src.sample_ids + j.b0 + Bg);
@@ -563,7 +596,7 @@ int capture_positions(LaneJob &j, int n_prompt, int n_pos, hipGraph_t *g, hipGra
 int lane_graph(LaneJob &j, int n_prompt) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
-    const int mk = (m->mask_on ? 1 : 0) | (m->ts_on ? 2 : 0) | (m->x_on ? 4 : 0);
+    const int mk = (m->mask_on ? 1 : 0) | (m->ts_on ? 2 : 0) | (m->x_on ? 4 : 0) | (m->off_on ? 8 : 0);
     const int sk = m->stop_on ? (1 | (m->budget_on ? 2 : 0) | ((m->stop_eot + 2) << 2)) : 0;
     int cur = -1;
     for (size_t i = 0; i < m->graph_sets.size(); ++i) {
@@ -710,8 +743,27 @@ extern "C" int wm_transcribe_mel(wm_ctx *ctx, const float *mel, const int64_t *m
                            no_speech_prob_out, mem);
 } WM_API_CATCH
 
-// wm_transcribe_greedy, wm_transcribe and wm_transcribe_mel: opts == null with both extra outputs null is the greedy
-// decode exactly
+// wm_transcribe_mel with prompts of different lengths: every decode group right-aligns its rows to its own longest prompt
+// (wm_right_align, WmModel::doff); a row's results are those of wm_transcribe_mel on that row alone with its own prompt
+extern "C" int wm_transcribe_mel_ragged(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                        const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                        int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                        int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out,
+                                        int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                        wm_mem mem) try {
+    WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
+    WM_REQUIRE(prompt_len, WM_ERR_INVALID, "null prompt_len");
+    WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
+    TxSrc src;
+    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
+    src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
+    src.sample_ids = sample_ids;
+    return transcribe_impl(ctx, src, B, prompt_stride, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
+                           no_speech_prob_out, mem);
+} WM_API_CATCH
+
+// wm_transcribe_greedy, wm_transcribe, wm_transcribe_mel and wm_transcribe_mel_ragged: opts == null with both extra outputs
+// null is the greedy decode exactly
 static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, int max_new, int32_t eot,
                            const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, float *logprobs_out,
                            float *no_speech_out, wm_mem mem) {
@@ -732,10 +784,19 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                        WM_ERR_INVALID, "row %d: window (base %lld, T %d, seek %d, n_frames %d) invalid", b,
                        (long long)src.mel_base[b], src.mel_len[b], src.seek[b], src.n_frames[b]);
     const wm_dims &D = m->dims;
+    if (src.prompt_len) {   // ragged: n_prompt arrives as the row stride and becomes the call's longest prompt
+        int longest = 0;
+        for (int b = 0; b < B; ++b) {
+            WM_REQUIRE(src.prompt_len[b] >= 1 && src.prompt_len[b] <= src.prompt_stride, WM_ERR_INVALID,
+                       "row %d: prompt_len %d outside [1, %d]", b, src.prompt_len[b], src.prompt_stride);
+            longest = std::max(longest, (int)src.prompt_len[b]);
+        }
+        n_prompt = longest;
+    }
     WM_REQUIRE(n_prompt >= 1 && max_new >= 1 && n_prompt + max_new <= D.n_text_ctx, WM_ERR_INVALID,
                "prompt (%d) + new tokens (%d) must fit the %d-token context", n_prompt, max_new, D.n_text_ctx);
     for (int b = 0; b < (src.prompt_stride ? B : 1); ++b)
-        for (int i = 0; i < n_prompt; ++i) {
+        for (int i = 0; i < (src.prompt_len ? src.prompt_len[b] : n_prompt); ++i) {
             const int32_t t = src.prompt[(size_t)b * src.prompt_stride + i];
             WM_REQUIRE(t >= 0 && t < D.n_vocab, WM_ERR_INVALID, "prompt token %d out of range", t);
         }
@@ -747,7 +808,13 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
     {
         const float T = opts ? opts->temperature : 0.f;
         const int32_t ns_tok = opts ? opts->no_speech_token : -1;
-        const int32_t sot_index = opts ? opts->sot_index : 0;
+        // (a ragged call places <|startoftranscript|> by sot_tail; opts->sot_index is not read)
+        const int32_t sot_index = (opts && !src.prompt_len) ? opts->sot_index : 0;
+        if (src.prompt_len && no_speech_out) {
+            const int shortest = *std::min_element(src.prompt_len, src.prompt_len + B);
+            WM_REQUIRE(src.sot_tail >= 1 && src.sot_tail <= shortest, WM_ERR_INVALID,
+                       "sot_tail %d outside [1, %d] (the shortest prompt)", src.sot_tail, shortest);
+        }
         WM_REQUIRE(std::isfinite(T) && T >= 0.f, WM_ERR_INVALID, "temperature must be finite and >= 0");
         // (1 / T must be a finite f32 too: an infinite scale turns a zero logit's score into NaN)
         WM_REQUIRE(T == 0.f || std::isfinite((float)(1.0 / (double)T)), WM_ERR_INVALID,
@@ -827,7 +894,8 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
             for (auto &e : jobs[l].burst_ev) WM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
-    const int n_steps = n_prompt + max_new - 1;
+    // (a ragged call: a group's prompt positions are its own longest prompt, LaneJob::P; n_prompt is the call's longest)
+    auto n_steps = [&](const LaneJob &j) { return j.P + max_new - 1; };
     // decodes in flight on this device (this call included): other lanes of this call, other contexts' calls
     struct ActiveGuard {
         std::atomic<int> &n;
@@ -847,8 +915,10 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                 j.Bg = base + (g < rem ? 1 : 0);
                 j.b0 = g * base + (g < rem ? g : rem);
                 j.t = 0; j.bursts = 0; j.stopped = false;
-                WM_TRY(lane_prefill(j, src, n_prompt, mem, stop, xc));
-                if (use_graph) WM_TRY(lane_graph(j, n_prompt));
+                j.P = n_prompt;
+                if (src.prompt_len) j.P = *std::max_element(src.prompt_len + j.b0, src.prompt_len + j.b0 + j.Bg);
+                WM_TRY(lane_prefill(j, src, j.P, mem, stop, xc));
+                if (use_graph) WM_TRY(lane_graph(j, j.P));
                 j.state = LaneJob::DECODING;
                 progress = true;
                 continue;   // the other lanes get their prefill before anyone's first burst
@@ -863,20 +933,20 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                     WM_HIP(q);
                     if (j.c->model->h_nlive[slot] == 0) j.stopped = true;
                 }
-                if (j.t < n_steps && !j.stopped) {
+                if (j.t < n_steps(j) && !j.stopped) {
                     // does this burst share the chip?  other lanes of this call still decoding, or other calls in flight
                     int busy = 0;
-                    for (int o = 0; o < n_lanes; ++o) busy += jobs[o].state == LaneJob::DECODING && jobs[o].t < n_steps && !jobs[o].stopped;
+                    for (int o = 0; o < n_lanes; ++o) busy += jobs[o].state == LaneJob::DECODING && jobs[o].t < n_steps(jobs[o]) && !jobs[o].stopped;
                     // (sub-chip lanes own their CUs: the other lanes of THIS call do not make the chip "shared")
                     const bool shared = (busy > 1 && !parts) || g_wm_active_decodes[ctx->device & 63].load(std::memory_order_relaxed) > 1;
-                    WM_TRY(lane_burst(j, n_prompt, n_steps, use_graph, stop.on, shared));
+                    WM_TRY(lane_burst(j, j.P, n_steps(j), use_graph, stop.on, shared));
                     progress = true;
                     continue;
                 }
                 // everything enqueued (or nothing left to decode): fetch the token streams
                 WM_HIP(hipEventRecord(j.ev[3], j.c->stream));
-                j.gen.resize((size_t)max_new * j.Bg);  // dseq[n_prompt + i][b]
-                WM_HIP(hipMemcpyAsync(j.gen.data(), j.c->model->dseq + (size_t)n_prompt * j.Bg, j.gen.size() * 4,
+                j.gen.resize((size_t)max_new * j.Bg);  // dseq[P + i][b]
+                WM_HIP(hipMemcpyAsync(j.gen.data(), j.c->model->dseq + (size_t)j.P * j.Bg, j.gen.size() * 4,
                                       hipMemcpyDeviceToHost, j.c->stream));
                 if (xc.logprobs) {   // [gi][b], laid out like dseq
                     j.lp.resize((size_t)max_new * j.Bg);

@@ -183,6 +183,9 @@ int wm_cu_mask(int cu_lo, int cu_hi, uint32_t mask[8]);
 
 int wm_ctx_make_current(const wm_ctx *ctx);
 int wm_group_count(int B, int L, bool explicit_lanes, int gc_probe);   // model_api.cpp: decode groups of a wm_transcribe_greedy call
+// the right-aligned prompt table [P][Bg] and the row offsets [Bg] of rows [b0, b0 + Bg) of a ragged call; returns P (model_api.cpp)
+int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, std::vector<int32_t> &table,
+                   std::vector<int32_t> &off);
 // CU-masked groups of a call (0: none -- unmasked lanes as wm_group_count says; 2 / 3: that many groups, one per part of the chip)
 int wm_lane_parts(int B, int L, bool explicit_lanes, int n_text_state, int n_text_layer);
 

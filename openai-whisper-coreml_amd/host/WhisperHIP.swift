@@ -244,6 +244,28 @@ struct Whisper {
         return (0..<rows).map { r in Array(tokens[r * Int(maxNew)..<r * Int(maxNew) + Int(lens[r])]) }
     }
 
+    /// The same step with prompts of different lengths (wm_transcribe_mel_ragged): what condition_on_previous_text needs,
+    /// every row's prompt being [sot_prev, *its recording's previous text, sot, language, task] (sotTail 3) or
+    /// [sot, language, task].  Returns each row's generated tokens.  Not compiled in this repository.
+    func transcribeMelRagged(mel: [Float], melBase: [Int64], melLen: [Int32], seek: [Int32], nFrames: [Int32],
+                             prompts: [[Int32]], sotTail: Int32, maxNew: Int32, eot: Int32) throws -> [[Int32]] {
+        typealias RaggedFn = @convention(c) (OpaquePointer, UnsafePointer<Float>, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                             UnsafePointer<Int32>, UnsafePointer<Int32>, Int32, UnsafePointer<Int32>, Int32,
+                                             UnsafePointer<Int32>, Int32, UnsafePointer<UInt32>?, Int32, Int32,
+                                             UnsafeRawPointer?, UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Int32>,
+                                             UnsafeMutablePointer<Float>?, UnsafeMutablePointer<Float>?, Int32) -> Int32
+        let rows = melBase.count
+        let stride = prompts.map { $0.count }.max() ?? 0
+        let lens = prompts.map { Int32($0.count) }
+        let flat = prompts.flatMap { $0 + [Int32](repeating: 0, count: stride - $0.count) }
+        var tokens = [Int32](repeating: 0, count: rows * Int(maxNew))
+        var outLens = [Int32](repeating: 0, count: rows)
+        let f: RaggedFn = try sym("wm_transcribe_mel_ragged")
+        try check(f(ctx, mel, melBase, melLen, seek, nFrames, Int32(rows), flat, Int32(stride), lens, sotTail, nil, maxNew,
+                    eot, nil, &tokens, &outLens, nil, nil, 0))
+        return (0..<rows).map { r in Array(tokens[r * Int(maxNew)..<r * Int(maxNew) + Int(outLens[r])]) }
+    }
+
     /// ids -> text with the tokenizer's vocab.json (wm_vocab_load / wm_detokenize; no vocabulary ships with the library).
     func text(of ids: [Int32], vocabJSON: String) throws -> String {
         let load: VocabLoadFn = try sym("wm_vocab_load")

@@ -3,7 +3,17 @@ lockstep across recordings, temperature fallback) against the fixed 30 s windows
 (every recording cut at multiples of 480000 samples, the last piece zero-padded).  Synthetic weights of the multilingual model
 given as argv[1] (default base), every matrix scaled by weights.lively_gain so that the decode depends on the audio, N recordings of mixed
 length (argv[2], default 8: 10 .. 150 s), the production vocabulary's token ids, text context n_text_ctx.  Prints one JSON
-line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form."""
+line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form.
+
+    python tools/gpu_longform_probe.py [model] [recordings] [--condition]
+
+--condition: the cost of condition_on_previous_text instead.  One more JSON line: wall seconds of the long form with
+conditioning off and on (the same recordings, after a warm-up of each; with the default fallback thresholds and with the
+log-prob and compression-ratio thresholds off, where no window falls back and the prompts accumulate), the prompt positions and generated positions each
+run decoded (per wm_transcribe_mel[_ragged] call: rows x the longest prompt of the call, rows x the longest generated
+length), the position graphs captured (distinct (rows, prompt positions) pairs among the calls, against the 4 graph sets a
+lane keeps), and the per-position time of ONE ragged decode group against a uniform group of the same size and the same
+number of prompt positions (what the row-offset load in the self-attention launch costs)."""
 import json
 import os
 import sys
@@ -16,8 +26,10 @@ import openai_whisper_coreml_amd as pkg  # noqa: E402
 from openai_whisper_coreml_amd import weights as W  # noqa: E402
 
 b = pkg.binding
-name = sys.argv[1] if len(sys.argv) > 1 else "base"
-N = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+CONDITION = "--condition" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--condition"]
+name = argv[0] if len(argv) > 0 else "base"
+N = int(argv[1]) if len(argv) > 1 else 8
 dims = dict(b.MODEL_DIMS[name])
 SOT, TASK, NS, TSB, EOT = 50258, 50359, 50362, 50364, 50257
 ctx = b.Context(dims)
@@ -36,6 +48,81 @@ for i in range(N):
     recs.append((0.3 * np.sin(2 * np.pi * (180 + 60 * i) * t) * (0.6 + 0.4 * np.sin(2 * np.pi * 0.2 * t))).astype(np.float32))
 audio_s = sum(r.size for r in recs) / 16000.0
 kw = dict(sot=SOT, task=TASK, eot=EOT, timestamp_begin=TSB, no_speech_token=NS, language=50259)
+
+
+def condition_probe():
+    SOT_PREV = 50361
+    calls = []
+    inner = ctx.transcribe_mel
+
+    def counted(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, **k):
+        t0 = time.perf_counter()
+        r = inner(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, **k)
+        calls.append(dict(rows=len(prompts), P=max(len(p) for p in prompts), gen=int(r.lens.max()),
+                          wall=time.perf_counter() - t0))
+        return r
+    ctx.transcribe_mel = counted
+    res = {}
+    # the synthetic model fails the log-prob test on every window, so with the default thresholds every window ends at
+    # temperature 1.0 and resets its recording's prompt: the runs without thresholds are the ones whose prompts accumulate
+    cond = dict(condition_on_previous_text=True, sot_prev=SOT_PREV)
+    nofb = dict(logprob_threshold=None, compression_ratio_threshold=None)
+    for label, extra in (("off", {}), ("on", cond), ("off_no_fallback", nofb), ("on_no_fallback", dict(cond, **nofb))):
+        ctx.transcribe_long(recs, **kw, **extra)     # warm-up: buffers, and whatever graphs survive
+        del calls[:]
+        t0 = time.perf_counter()
+        out = ctx.transcribe_long(recs, **kw, **extra)
+        wall = time.perf_counter() - t0
+        shapes = [(c["rows"], c["P"]) for c in calls]
+        recaptured, held = 0, []
+        for sh in shapes:   # the LRU of 4 graph sets a lane keeps, replayed over the run's calls
+            if sh in held:
+                held.remove(sh)
+            else:
+                recaptured += 1
+                if len(held) == 4:
+                    held.pop(0)
+            held.append(sh)
+        res[label] = dict(wall_s=wall, audio_s_per_s=audio_s / wall, calls=len(calls),
+                          windows=sum(len(o["windows"]) for o in out),
+                          prompt_positions=sum(c["rows"] * c["P"] for c in calls),
+                          generated_positions=sum(c["rows"] * c["gen"] for c in calls),
+                          prompt_steps=sum(c["P"] for c in calls), generated_steps=sum(c["gen"] for c in calls),
+                          distinct_graph_shapes=len(set(shapes)), graph_captures=recaptured,
+                          first_call_of_a_shape_mean_s=float(np.mean([c["wall"] for i, c in enumerate(calls)
+                                                                      if shapes.index(shapes[i]) == i])),
+                          repeated_shape_mean_s=float(np.mean([c["wall"] for i, c in enumerate(calls)
+                                                               if shapes.index(shapes[i]) != i] or [0.0])))
+    ctx.transcribe_mel = inner
+    # one ragged group against one uniform group: same rows, same prompt positions, fixed length (eot off)
+    n_ctx = dims["n_text_ctx"]
+    P, new = n_ctx // 2 + 3, 64
+    d_mel, offs, T = ctx.logmel_long(recs, n_mels=dims["n_mels"], device=True)
+    rows = list(range(N))
+    prng = np.random.default_rng(5)
+    uniform = [[int(t) for t in prng.integers(0, 50000, size=P - 3)] + [SOT, 50259, TASK] for _ in rows]
+    lens = [P] + [3 + (P - 3) * i // N for i in range(1, N)]     # the longest first, then 3 + ... spread up to P
+    ragged = [p[P - n:] for p, n in zip(uniform, lens)]
+    per_pos = {}
+    try:
+        for label, prompts in (("uniform", uniform), ("ragged", ragged)):
+            best = None
+            for _ in range(4):
+                ctx.transcribe_mel(d_mel, offs[rows], T[rows], 0, [min(3000, int(t) - 3000) for t in T[rows]], prompts, new,
+                                   eot=-1, no_speech_token=NS, sot_tail=3, mem=b.WM_MEM_DEVICE)
+                ms = float(ctx.last_stage_ms()[2]) / (P + new - 1)
+                best = ms if best is None else min(best, ms)
+            per_pos[label] = best
+    finally:
+        ctx.dev_free(d_mel)
+    print(json.dumps(dict(model=name, recordings=N, audio_s=audio_s, conditioning=res, group_rows=N, group_P=P,
+                          ragged_prompt_lengths=[len(p) for p in ragged], decode_ms_per_position=per_pos,
+                          ragged_over_uniform=per_pos["ragged"] / per_pos["uniform"])))
+
+
+if CONDITION:
+    condition_probe()
+    sys.exit(0)
 ctx.transcribe_long(recs[:1], **kw)    # warm-up: graphs, buffers
 t0 = time.perf_counter()
 out = ctx.transcribe_long(recs, **kw)
