@@ -288,7 +288,27 @@ WM_API int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, con
              const int32_t *n_frames, int medfilt_width, float qk_scale, int32_t *start_frame_out, float *token_prob_out,
              wm_mem mem);
 
-/* The alignment heads wm_align reads: n (layer, head) pairs, any order (used ascending).  n = 0 restores the default, every
+/* wm_align on log-mel windows, one start sequence per row: word-level timing inside openai-whisper's long-form seek loop,
+ * where a round holds one window of every live recording (each with its own language token) and the text was decoded from
+ * the whole-recording log-mel, not from a 30 s chunk's.
+ *   mel, mel_base, mel_len, seek, n_frames, mem : the window description of wm_transcribe_mel (typically wm_logmel_long's
+ *              output kept on the device; with WM_MEM_HOST only the B windows are copied).  Row b's encoder input is
+ *              mel[:, seek : seek + n_frames] zero-padded to 3000 frames, and n_frames[b] is ALSO find_alignment's
+ *              num_frames: the cost matrix has M = n_frames[b] / 2 audio frames.  n_frames 2 .. 3000, never NULL;
+ *   sot_seqs : i32 [B][n_sot] (host): row b's teacher-forced sequence is [*sot_seqs[b], no_timestamps, *t_b, eot];
+ *   everything else (text tokens, alignment heads, median filter, qk_scale, outputs and their -1 / 0 padding, groups of at
+ *   most 128 rows, wm_last_stage_ms) exactly as wm_align.
+ * Rows cut at seek 0 with 3000 frames from wm_logmel(..., WM_F32)'s output, every row carrying the same start sequence,
+ * give wm_align's start_frame_out and token_prob_out bit for bit.  A row's results depend only on its own window, start
+ * sequence and text: the same bits alone, among other rows, across decode groups, and for the same frames presented as
+ * their own block at seek 0.  Invalid: everything wm_align rejects (n_frames non-null here), mel_len < 1, seek < 0,
+ * seek + n_frames > mel_len, mel_base < 0, a null window pointer, a sot_seqs token outside the vocabulary. */
+WM_API int wm_align_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                        const int32_t *seek, const int32_t *n_frames, int B, const int32_t *sot_seqs, int n_sot,
+                        int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
+                        int medfilt_width, float qk_scale, int32_t *start_frame_out, float *token_prob_out, wm_mem mem);
+
+/* The alignment heads wm_align and wm_align_mel read: n (layer, head) pairs, any order (used ascending).  n = 0 restores the default, every
  * head of the decoder layers n_text_layer / 2 .. n_text_layer - 1 (openai-whisper's default when a checkpoint has no list);
  * a checkpoint's own list (openai-whisper _ALIGNMENT_HEADS, Hugging Face generation_config.alignment_heads) comes from the
  * host.  Out-of-range pairs and duplicates are invalid.  Same inheritance as wm_set_suppress. */
@@ -410,8 +430,9 @@ WM_API int wm_profile_overhead_us(wm_ctx *ctx, float *us);
 /* Writes a JSON object {"family": {"ms": total_ms, "n": launches}, ...} into buf. */
 WM_API int wm_profile_json(wm_ctx *ctx, char *buf, size_t buf_bytes);
 /* Wall-clock stage split of the last wm_transcribe_greedy call, in ms (HIP events):
- * [0] front end, [1] encoder + cross-KV projection, [2] decode loop.  After wm_align: [0] front end + encoder + cross-KV
- * projection, [1] teacher-forced pass, [2] alignment kernels + DTW. */
+ * [0] front end, [1] encoder + cross-KV projection, [2] decode loop.  After wm_align / wm_align_mel: [0] front end (the
+ * window copies of a WM_MEM_HOST wm_align_mel call) + encoder + cross-KV projection, [1] teacher-forced pass, [2] alignment
+ * kernels + DTW. */
 WM_API int wm_last_stage_ms(wm_ctx *ctx, float out3[3]);
 
 #ifdef __cplusplus

@@ -106,7 +106,7 @@ WM_API int wmdbg_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int
 /* The DTW kernel of wm_align alone, on host matrices: chunk b is x + b * max(N) * ld, N[b] rows (<= 448) x M[b] frames
  * (<= 1500, <= ld), row stride ld.  start_frame_out i32 [B][max(N)]: the first frame of every row on the path, -1 past N[b]. */
 WM_API int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, const int32_t *M, int ld, int32_t *start_frame_out);
-/* Makes the NEXT wm_align call on ctx also return its cost matrix -- AFTER negation, i.e. x = -mean over heads, the matrix
+/* Makes the NEXT wm_align or wm_align_mel call on ctx also return its cost matrix -- AFTER negation, i.e. x = -mean over heads, the matrix
  * the DTW runs on -- into matrix_out f32 [B][max_text + 1][1500] (0 outside each chunk's n + 1 rows x n_frames / 2 frames). */
 WM_API int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out);
 /* The alignment kernels of wm_align alone (column statistics, then the cost matrix) on host data.  q f32 [B][Tq][J][64] (the

@@ -118,6 +118,8 @@ def load_library(path=None):
         "wm_set_token_budgets": [vp, vp, ip],
         "wm_set_alignment_heads": [vp, vp, vp, ip],
         "wm_align": [vp, vp, ip, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, vp, ip, ctypes.c_float, vp, vp, ip],
+        "wm_align_mel": [vp, vp, vp, vp, vp, vp, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, ip, ctypes.c_float, vp, vp,
+                         ip],
         "wm_set_lanes": [vp, ip],
         "wm_dev_malloc": [vp, sz, pp],
         "wm_dev_free": [vp, vp],
@@ -348,14 +350,15 @@ def should_skip_window(no_speech_prob, avg_logprob, no_speech_threshold=0.6, log
     return bool(skip)
 
 
-def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vocab=None):
+def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vocab=None, cleanup=True):
     """openai-whisper transcribe()'s handling of one decoded window (word_timestamps=False): slicing at consecutive
     timestamps, single_timestamp_ending, the seek update and the clearing of instantaneous / text-less segments.
       tokens : the window's generated tokens without the final eot (openai-whisper DecodingResult.tokens);
       seek, segment_size : the window's first frame and frame count;
       result : dict with temperature, avg_logprob, compression_ratio, no_speech_prob (copied into every segment).
     Returns (segments, next_seek).  A segment is text-less when, with a Vocab, its decoded text is blank, and without one
-    when it has no token below eot."""
+    when it has no token below eot.  cleanup=False (the word-timestamp path, where openai-whisper clears AFTER the word
+    step: clear_empty_segments) leaves the segments as sliced and returns (segments, next_seek, single_timestamp_ending)."""
     tokens = [int(t) for t in tokens]
     time_offset = float(seek * HOP_SECONDS)
     segment_duration = segment_size * HOP_SECONDS
@@ -393,13 +396,23 @@ def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vo
             duration = (ts[-1] - timestamp_begin) * TIME_PRECISION
         segments.append(new_segment(time_offset, time_offset + duration, tokens))
         next_seek = seek + segment_size
+    if not cleanup:
+        return segments, next_seek, single_timestamp_ending
+    clear_empty_segments(segments, eot, vocab)
+    return segments, next_seek
+
+
+def clear_empty_segments(segments, eot, vocab=None, words=False):
+    """The last loop of openai-whisper transcribe() over a window's segments: one with start == end or without text loses
+    its tokens and text (and, with words=True, its words)."""
     for seg in segments:
         blank = (seg["text"].strip() == "") if vocab is not None else not any(t < eot for t in seg["tokens"])
         if seg["start"] == seg["end"] or blank:
             seg["tokens"] = []
             if vocab is not None:
                 seg["text"] = ""
-    return segments, next_seek
+            if words:
+                seg["words"] = []
 
 
 def conditioned_prompt(all_tokens, prompt_reset_since, sot_sequence, sot_prev, n_text_ctx):
@@ -430,10 +443,11 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     lang_last=None, language=None, sot_prev=None, initial_prompt_tokens=None, recording_ids=None,
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
                     no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None, condition_on_previous_text=False,
-                    prompt_reset_on_temperature=0.5):
-    """openai-whisper transcribe() for recordings of any length, with word_timestamps=False, no clip timestamps and no
-    hallucination-silence threshold, batched across the recordings.  condition_on_previous_text defaults to False here
-    (openai-whisper: True); see 5.
+                    prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
+                    prepend_punctuations=None, append_punctuations=None):
+    """openai-whisper transcribe() for recordings of any length, batched across the recordings; hallucination_silence_threshold
+    and clip_timestamps are not implemented.  condition_on_previous_text defaults to False here (openai-whisper: True);
+    see 5.  word_timestamps: see 6.
 
     1. One wm_logmel_long call for all recordings, kept on the device; content_frames = T_r - 3000.
     2. language None: per recording, openai-whisper's detect_language on mel[:, :3000] (wm_encode + the language-token
@@ -451,12 +465,23 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        is min(n_text_ctx // 2, n_text_ctx - (n_text_ctx // 2 + 3)) for every window of such a run (221 at 448): a row's
        budget depends neither on its own prompt nor on the other rows, so batched equals alone.  openai-whisper allows 224
        tokens after a short prompt and 222 after a full one; only a window that fills its whole budget can tell.
+    6. word_timestamps=True (needs vocab and no_timestamps, the id of <|notimestamps|>): per round, after the decode, the
+       kept windows that have a text token and at least 2 frames go out in ONE wm_align_mel call -- the decode's own mel,
+       seek and segment_size, start sequence [sot, language_r, task], median filter 7 -- and window_word_timestamps gives
+       every segment its `words` and adjusts its start / end, each recording with its own running last speech timestamp.
+       As in openai-whisper, the clearing of instantaneous / text-less segments then runs AFTER the word step, and a
+       window that did not end in a single timestamp moves the seek to the end of its last word when that lies behind
+       the window's start.  Words are split by spaces unless the language token, counted from sot + 1 in
+       Whisper.LANGUAGES, is one of zh / ja / th / lo / my.  This project's rule where openai-whisper defines nothing:
+       a window of fewer than 2 frames (no audio frame to align to), like a skipped window or one without a text token,
+       gets `words` [] on its segments and the seek of word_timestamps=False.
+       prepend_punctuations / append_punctuations: None = openai-whisper's defaults (PREPEND_ / APPEND_PUNCTUATIONS).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
     no prompt).  Without conditioning a recording's list heads every one of its windows; with it, it seeds the history.
     Sets the context's timestamp rules (wm_set_timestamp_rules: timestamp_begin, eot, max initial timestamp 1.0 s);
     suppress lists are the caller's (Context.set_suppress).  Returns per recording a dict: language (token id),
     segments (openai-whisper's keys id seek start end tokens temperature avg_logprob compression_ratio no_speech_prob, plus
-    text with a Vocab), text (with a Vocab), seeks (the first frame of every decoded window) and windows (per window:
+    text with a Vocab and words [{word, start, end, probability}] with word_timestamps), text (with a Vocab), seeks (the first frame of every decoded window) and windows (per window:
     seek, segment_size, the fallback steps' temperatures, skipped, prompt_len, prompt)."""
     R = len(recordings)
     rec_ids = list(range(R)) if recording_ids is None else [int(i) for i in recording_ids]
@@ -476,6 +501,13 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         raise ValueError("initial_prompt_tokens: one list per recording")
     if vocab_size is None:
         vocab_size = int(ctx.dims["n_vocab"])
+    words_on = bool(word_timestamps)
+    if words_on and (vocab is None or no_timestamps is None):
+        raise ValueError("word_timestamps needs vocab and no_timestamps")
+    if prepend_punctuations is None:
+        prepend_punctuations = PREPEND_PUNCTUATIONS
+    if append_punctuations is None:
+        append_punctuations = APPEND_PUNCTUATIONS
     ctx.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
     out = [dict(language=None, segments=[], seeks=[], windows=[]) for _ in range(R)]
     if R == 0:
@@ -516,6 +548,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         reset_since = [0] * R
         ragged = cond or per_rec   # rows may differ in prompt length: wm_transcribe_mel_ragged, <|startoftranscript|> third from the end
         seek = [0] * R
+        last_speech = [0.0] * R
         for r in range(R):
             out[r]["language"] = langs[r]
         # 3. rounds in lockstep
@@ -545,6 +578,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                           sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE)
             res = fallback_decode(decode, len(live), vocab_size, max_new, eot, temperatures, compression_ratio_threshold,
                                   logprob_threshold, no_speech_threshold, vocab, seed)
+            kept = []   # word_timestamps: (row of the round, segments, next seek, single_timestamp_ending) of every kept window
             for i, r in enumerate(live):
                 temps = [st[0] for st in res["steps"] if i in st[2]]
                 n_text = n_text_tokens(res["tokens"][i, :res["lens"][i]], eot)
@@ -560,11 +594,51 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 if skip:
                     seek[r] += size[i]
                     continue
+                if words_on:
+                    kept.append((i,) + window_segments(res["tokens"][i, :n_text], seek[r], size[i], timestamp_begin, eot,
+                                                       result, vocab, cleanup=False))
+                    continue
                 segs, seek[r] = window_segments(res["tokens"][i, :n_text], seek[r], size[i], timestamp_begin, eot,
                                                 result, vocab)
                 if cond:
                     all_tokens[r], reset_since[r] = conditioned_history(all_tokens[r], reset_since[r], segs,
                                                                         result["temperature"], False,
+                                                                        prompt_reset_on_temperature)
+                for sg in segs:
+                    sg["id"] = len(out[r]["segments"])
+                    out[r]["segments"].append(sg)
+            if not kept:
+                continue
+            # 6. the word step of the round: one alignment call, then per recording the word rules and the word-driven seek
+            texts = [[t for sg in k[1] for t in sg["tokens"] if t < eot] for k in kept]
+            go = [n for n, k in enumerate(kept) if texts[n] and size[k[0]] >= 2]
+            if go:
+                rows = [live[kept[n][0]] for n in go]
+                sf, pr = ctx.align_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
+                                       [size[kept[n][0]] for n in go], [texts[n] for n in go],
+                                       [[int(sot), langs[r], int(task)] for r in rows], no_timestamps, eot,
+                                       medfilt_width=7, qk_scale=1.0, mem=WM_MEM_DEVICE)
+            for n, (i, segs, next_seek, single_ending) in enumerate(kept):
+                r = live[i]
+                if n in go:
+                    g = go.index(n)
+                    code = langs[r] - int(sot) - 1
+                    code = Whisper.LANGUAGES[code] if 0 <= code < len(Whisper.LANGUAGES) else None
+                    last_speech[r] = window_word_timestamps(vocab, segs, sf[g], pr[g], seek[r], eot, last_speech[r], code,
+                                                            prepend_punctuations, append_punctuations)
+                    ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
+                    if ends:
+                        if not single_ending and ends[-1] > seek[r] * HOP_SECONDS:
+                            next_seek = int(round(ends[-1] * 100))
+                        last_speech[r] = ends[-1]
+                else:
+                    for sg in segs:
+                        sg["words"] = []
+                clear_empty_segments(segs, eot, vocab, words=True)
+                seek[r] = next_seek
+                if cond:
+                    all_tokens[r], reset_since[r] = conditioned_history(all_tokens[r], reset_since[r], segs,
+                                                                        float(res["temperature"][i]), False,
                                                                         prompt_reset_on_temperature)
                 for sg in segs:
                     sg["id"] = len(out[r]["segments"])
@@ -982,6 +1056,50 @@ class Context:
                                            _ptr(start), _ptr(probs), WM_MEM_HOST))
         return (start, probs, matrix) if capture_matrix else (start, probs)
 
+    def align_mel(self, mel, mel_base, mel_len, seek, n_frames, text_tokens, sot_seqs, no_timestamps, eot, medfilt_width=7,
+                  qk_scale=1.0, capture_matrix=False, mem=WM_MEM_HOST):
+        """wm_align_mel: Context.align on mel windows.  mel, mel_base, mel_len, seek, n_frames, mem: the window description
+        of transcribe_mel_raw (n_frames 2 .. 3000: also the audio frames the alignment covers); sot_seqs: one start
+        sequence for every row, or B of one length (one per row).  Returns what align returns."""
+        base = np.ascontiguousarray(mel_base, dtype=np.int64)
+        B = base.size
+        mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (B,)))
+        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (B,)))
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
+        rows = [list(np.asarray(t).reshape(-1)) for t in text_tokens]
+        if len(rows) != B:
+            raise ValueError("text_tokens: %d lists for %d windows" % (len(rows), B))
+        max_text = max([len(r) for r in rows] + [0])
+        tt = np.zeros((B, max(max_text, 1)), dtype=np.int32)
+        for b, r in enumerate(rows):
+            tt[b, :len(r)] = r
+        nt = np.ascontiguousarray([len(r) for r in rows], dtype=np.int32)
+        sot = np.asarray(sot_seqs, dtype=np.int32)
+        if sot.ndim == 1:
+            sot = np.broadcast_to(sot, (B, sot.size))
+        if sot.ndim != 2 or sot.shape[0] != B:
+            raise ValueError("sot_seqs: one start sequence, or one per window")
+        sot = np.ascontiguousarray(sot)
+        if mem == WM_MEM_HOST:
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            mp = _ptr(mel)
+        else:
+            mp = mel
+        start = np.empty((B, max_text + 1), dtype=np.int32)
+        probs = np.empty((B, max_text), dtype=np.float32)
+        matrix = None
+        if capture_matrix:
+            if not hasattr(self.lib, "wmdbg_align_capture"):
+                raise WhisperError(-1, "capture_matrix needs the debug library: Context(dims, debug=True)")
+            matrix = np.empty((B, max_text + 1, 1500), dtype=np.float32)
+            self.lib.wmdbg_align_capture.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            self.lib.wmdbg_align_capture.restype = ctypes.c_int
+            _check(self.lib, self.lib.wmdbg_align_capture(self.handle, _ptr(matrix)))
+        _check(self.lib, self.lib.wm_align_mel(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(sot),
+                                               sot.shape[1], int(no_timestamps), int(eot), _ptr(tt), _ptr(nt), max_text,
+                                               int(medfilt_width), float(qk_scale), _ptr(start), _ptr(probs), mem))
+        return (start, probs, matrix) if capture_matrix else (start, probs)
+
     def dtw(self, mats):
         """Debug library only: the DTW kernel of wm_align alone on a list of f32 cost matrices [N][M] (N <= 448,
         M <= 1500).  Returns the start frame of every row of each (wmdbg_dtw)."""
@@ -1131,7 +1249,15 @@ def word_timestamps(vocab, text_tokens, start_frames, token_probs, language=None
     zh / ja / th / lo / my / yue and by split_tokens_on_spaces otherwise (Vocab.decode gives U+FFFD for a partial UTF-8
     piece).  A word of tokens [a, b) spans [start_frames[a], start_frames[b]) and its probability is the mean of
     token_probs[a:b].  Punctuation is then merged into the neighbouring words (which keep their own times); words left
-    empty are dropped.  add_word_timestamps' segment heuristics are not applied."""
+    empty are dropped.  add_word_timestamps' segment heuristics are not applied here: window_word_timestamps applies them
+    to the segments of a long-form window."""
+    out = _alignment_words(vocab, text_tokens, start_frames, token_probs, language)
+    _merge_punctuations(out, prepend_punctuations, append_punctuations)
+    return [w for w in out if w["word"]]
+
+
+def _alignment_words(vocab, text_tokens, start_frames, token_probs, language):
+    """find_alignment's words before punctuation merging (word_timestamps' docstring), zero-length and empty ones kept."""
     toks = [int(t) for t in np.asarray(text_tokens).reshape(-1)]
     n = len(toks)
     if n == 0:
@@ -1155,8 +1281,75 @@ def word_timestamps(vocab, text_tokens, start_frames, token_probs, language=None
         out.append(dict(word=words[k], tokens=[t for t in word_tokens[k] if t is not _EOT],
                         start=float(start_frames[a]) / FRAMES_PER_SECOND, end=float(start_frames[b]) / FRAMES_PER_SECOND,
                         probability=float(np.mean(token_probs[a:b]))))
-    _merge_punctuations(out, prepend_punctuations, append_punctuations)
-    return [w for w in out if w["word"]]
+    return out
+
+
+SENTENCE_END_MARKS = ".。!！?？"
+
+
+def window_word_timestamps(vocab, segments, start_frames, token_probs, seek, eot, last_speech_timestamp, language=None,
+                           prepend_punctuations=PREPEND_PUNCTUATIONS, append_punctuations=APPEND_PUNCTUATIONS):
+    """openai-whisper's add_word_timestamps (whisper/timing.py) for ONE long-form window with at least one segment: the
+    words of Context.align_mel's outputs for the window's text tokens -- the tokens < eot of its segments, concatenated --
+    dealt out to the segments as `words` [{word, start, end, probability}] in seconds of the recording, with its
+    heuristics: word durations capped at twice the window's median (at most 0.7 s) around sentence ends, a long first
+    word after a pause pulled to its end, a segment's start / end and its first / last word reconciled.  Edits the
+    segments (as window_segments(..., cleanup=False) returns them) in place: words, start, end.  Returns the new
+    last_speech_timestamp (the end of the last segment that has words)."""
+    per_segment = [[int(t) for t in sg["tokens"] if t < eot] for sg in segments]
+    text_tokens = [t for ts in per_segment for t in ts]
+    alignment = _alignment_words(vocab, text_tokens, start_frames, token_probs, language)
+    durations = np.array([w["end"] - w["start"] for w in alignment], dtype=np.float64)
+    durations = durations[durations.nonzero()]
+    median = min(0.7, float(np.median(durations))) if len(durations) > 0 else 0.0
+    max_duration = median * 2
+    if len(durations) > 0:   # a long word at a sentence end is cut at its start side, one behind a sentence end at its end side
+        for i in range(1, len(alignment)):
+            w = alignment[i]
+            if w["end"] - w["start"] > max_duration:
+                if _is_sentence_end(w["word"]):
+                    w["end"] = w["start"] + max_duration
+                elif _is_sentence_end(alignment[i - 1]["word"]):
+                    w["start"] = w["end"] - max_duration
+    _merge_punctuations(alignment, prepend_punctuations, append_punctuations)
+    time_offset = seek * HOP_SECONDS
+    word_index = 0
+    for sg, toks in zip(segments, per_segment):
+        saved = 0
+        words = []
+        while word_index < len(alignment) and saved < len(toks):
+            t = alignment[word_index]
+            if t["word"]:
+                words.append(dict(word=t["word"], start=round(time_offset + t["start"], 2),
+                                  end=round(time_offset + t["end"], 2), probability=t["probability"]))
+            saved += len(t["tokens"])
+            word_index += 1
+        if words:
+            # a first word that ends long after the last speech and is itself (or with its follower) too long: a pause
+            if words[0]["end"] - last_speech_timestamp > median * 4 and (
+                    words[0]["end"] - words[0]["start"] > max_duration
+                    or (len(words) > 1 and words[1]["end"] - words[0]["start"] > max_duration * 2)):
+                if len(words) > 1 and words[1]["end"] - words[1]["start"] > max_duration:
+                    boundary = max(words[1]["end"] / 2, words[1]["end"] - max_duration)
+                    words[0]["end"] = words[1]["start"] = boundary
+                words[0]["start"] = max(0, words[0]["end"] - max_duration)
+            # prefer the segment-level start timestamp if the first word is too long
+            if sg["start"] < words[0]["end"] and sg["start"] - 0.5 > words[0]["start"]:
+                words[0]["start"] = max(0, min(words[0]["end"] - median, sg["start"]))
+            else:
+                sg["start"] = words[0]["start"]
+            # prefer the segment-level end timestamp if the last word is too long
+            if sg["end"] > words[-1]["start"] and sg["end"] + 0.5 < words[-1]["end"]:
+                words[-1]["end"] = max(words[-1]["start"] + median, sg["end"])
+            else:
+                sg["end"] = words[-1]["end"]
+            last_speech_timestamp = sg["end"]
+        sg["words"] = words
+    return last_speech_timestamp
+
+
+def _is_sentence_end(word):
+    return len(word) == 1 and word in SENTENCE_END_MARKS
 
 
 class Vocab:

@@ -1028,11 +1028,17 @@ constexpr size_t kAlignCaptureBudget = (size_t)2 << 30;   // bytes of captured q
 
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// where a call's encoder input comes from -- PCM chunks (wm_align) or mel windows (wm_align_mel, mel non-null) -- and its
+// start sequences: row b's is sot_seq + b * sot_stride (0: one for all)
 struct AlignCall {
-    const void *pcm;
-    wm_dtype pcm_dtype;
+    const void *pcm = nullptr;
+    wm_dtype pcm_dtype = WM_F32;
+    const float *mel = nullptr;
+    const int64_t *mel_base = nullptr;
+    const int32_t *mel_len = nullptr, *seek = nullptr;
     wm_mem mem;
     const int32_t *sot_seq, *text_tokens, *n_text, *n_frames;
+    int sot_stride = 0;
     int n_sot, max_text;
     int32_t no_timestamps, eot;
     int half;
@@ -1074,6 +1080,7 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     int *start = (int *)(ws + o_start), *ints = (int *)(ws + o_int);
     // host staging (fenced by the synchronisation at the end of the group): n_text, n_frames, DTW rows, DTW frames, heads
     std::vector<int32_t> hint(n_int), seq((size_t)T * Bg);
+    std::vector<WmMelWin> win;
     for (int b = 0; b < Bg; ++b) {
         const int n = c.n_text[b0 + b], nf = c.n_frames ? c.n_frames[b0 + b] : WM_N_FRAMES;
         hint[b] = n;
@@ -1081,8 +1088,9 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
         hint[2 * Bg + b] = n > 0 ? n + 1 : 0;
         hint[3 * Bg + b] = nf / 2;
         const int32_t *t = c.text_tokens + (size_t)(b0 + b) * c.max_text;
+        const int32_t *sot = c.sot_seq + (size_t)(b0 + b) * c.sot_stride;
         for (int p = 0; p < T; ++p) {   // [*sot_seq, no_timestamps, *t, eot, eot ...] (padding after eot: causal, unread)
-            const int32_t tok = p < S ? c.sot_seq[p] : p == S ? c.no_timestamps : p <= S + n ? t[p - S - 1] : c.eot;
+            const int32_t tok = p < S ? sot[p] : p == S ? c.no_timestamps : p <= S + n ? t[p - S - 1] : c.eot;
             seq[(size_t)p * Bg + b] = tok;
         }
     }
@@ -1101,7 +1109,7 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     WM_TRY(wm_model_reserve(ctx, Bg));
     const size_t pbytes = (size_t)Bg * WM_N_SAMPLES * pcm_elem(c.pcm_dtype);
     const void *d_pcm = (const char *)c.pcm + (size_t)b0 * WM_N_SAMPLES * pcm_elem(c.pcm_dtype);
-    if (c.mem == WM_MEM_HOST) {
+    if (c.mem == WM_MEM_HOST && !c.mel) {
         if (m->pcm_stage_bytes < pbytes) {
             WM_HIP(hipStreamSynchronize(ctx->stream));
             if (m->pcm_stage) WM_HIP(hipFree(m->pcm_stage));
@@ -1114,8 +1122,28 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
         d_pcm = m->pcm_stage;
     }
     WM_HIP(hipEventRecord(ev[0], ctx->stream));
-    WM_TRY(wm_frontend_run(&ctx->fe, &ctx->prof, ctx->stream, d_pcm, c.pcm_dtype, Bg, D.n_mels, m->mel_f32, WM_F32));
-    WM_TRY(wm_model_encode_dev(ctx, m->mel_f32, Bg, nullptr));
+    if (c.mel) {   // the window table of the wm_transcribe_mel prefill: gathered by the encoder's first step
+        const float *enc_mel = c.mel;
+        win.resize(Bg);
+        for (int b = 0; b < Bg; ++b) {
+            const int r = b0 + b;
+            WmMelWin &w = win[b];
+            w.T = c.mel_len[r]; w.seek = c.seek[r]; w.n = c.n_frames[r]; w.pad = 0;
+            w.base = c.mel_base[r];
+            if (c.mem == WM_MEM_HOST) {   // only the windows are copied, into the front end's buffer
+                WM_HIP(hipMemcpy2DAsync(m->mel_f32 + (size_t)b * D.n_mels * WM_N_FRAMES, WM_N_FRAMES * sizeof(float),
+                                        c.mel + w.base + w.seek, (size_t)w.T * sizeof(float), (size_t)w.n * sizeof(float),
+                                        D.n_mels, hipMemcpyHostToDevice, ctx->stream));
+                w.base = (long long)b * D.n_mels * WM_N_FRAMES; w.T = WM_N_FRAMES; w.seek = 0;
+            }
+        }
+        if (c.mem == WM_MEM_HOST) enc_mel = m->mel_f32;
+        WM_HIP(hipMemcpyAsync(m->dmel_win, win.data(), (size_t)Bg * sizeof(WmMelWin), hipMemcpyHostToDevice, ctx->stream));
+        WM_TRY(wm_model_encode_win(ctx, enc_mel, m->dmel_win, Bg, nullptr));
+    } else {
+        WM_TRY(wm_frontend_run(&ctx->fe, &ctx->prof, ctx->stream, d_pcm, c.pcm_dtype, Bg, D.n_mels, m->mel_f32, WM_F32));
+        WM_TRY(wm_model_encode_dev(ctx, m->mel_f32, Bg, nullptr));
+    }
     WM_TRY(wm_model_cross_kv(ctx, Bg));
     WM_HIP(hipEventRecord(ev[1], ctx->stream));
     // teacher-forced pass: every position is prompt, the alignment layers leave their queries in the capture buffer
@@ -1160,24 +1188,19 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
 }
 }  // namespace
 
-extern "C" int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *sot_seq, int n_sot,
-                        int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
-                        const int32_t *n_frames, int medfilt_width, float qk_scale, int32_t *start_frame_out,
-                        float *token_prob_out, wm_mem mem) try {
-    WM_MODEL(ctx);
-    AlignCall c;
-    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
-    m->align_dbg_matrix = nullptr;
-    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
-    WM_REQUIRE(pcm && sot_seq && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
-    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID, "bad pcm dtype");
-    WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
+// wm_align and wm_align_mel behind their own checks of the input source: c carries the source, the start sequences,
+// text_tokens, n_text and n_frames
+static int align_impl(wm_ctx *ctx, AlignCall &c, int B, int32_t no_timestamps, int32_t eot, int medfilt_width, float qk_scale,
+                      int32_t *start_frame_out, float *token_prob_out) {
+    WmModel *m = ctx->model;
+    const int n_sot = c.n_sot, max_text = c.max_text;
+    const int32_t *text_tokens = c.text_tokens, *n_text = c.n_text, *n_frames = c.n_frames;
     const wm_dims &D = m->dims;
     const int V = D.n_vocab;
     WM_REQUIRE(n_sot >= 1 && max_text >= 0 && n_sot + max_text + 2 <= D.n_text_ctx, WM_ERR_INVALID,
                "align: sot_seq (%d) + max_text (%d) + 2 must fit the %d-token context", n_sot, max_text, D.n_text_ctx);
-    for (int i = 0; i < n_sot; ++i)
-        WM_REQUIRE(sot_seq[i] >= 0 && sot_seq[i] < V, WM_ERR_INVALID, "align: sot_seq token %d out of range", sot_seq[i]);
+    for (size_t i = 0; i < (size_t)n_sot * (c.sot_stride ? B : 1); ++i)
+        WM_REQUIRE(c.sot_seq[i] >= 0 && c.sot_seq[i] < V, WM_ERR_INVALID, "align: sot_seq token %d out of range", c.sot_seq[i]);
     WM_REQUIRE(no_timestamps >= 0 && no_timestamps < V && eot >= 0 && eot < V, WM_ERR_INVALID,
                "align: no_timestamps / eot outside the vocabulary");
     WM_REQUIRE(medfilt_width >= 1 && medfilt_width <= 31 && medfilt_width % 2 == 1, WM_ERR_INVALID,
@@ -1194,6 +1217,11 @@ extern "C" int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
         if (n_frames)
             WM_REQUIRE(n_frames[b] >= 2 && n_frames[b] <= WM_N_FRAMES, WM_ERR_INVALID, "align: n_frames[%d] = %d outside [2, %d]",
                        b, n_frames[b], WM_N_FRAMES);
+        if (c.mel)
+            WM_REQUIRE(c.mel_base[b] >= 0 && c.mel_len[b] >= 1 && c.seek[b] >= 0 &&
+                           (int64_t)c.seek[b] + n_frames[b] <= c.mel_len[b],
+                       WM_ERR_INVALID, "align: row %d: window (base %lld, T %d, seek %d, n_frames %d) invalid", b,
+                       (long long)c.mel_base[b], c.mel_len[b], c.seek[b], n_frames[b]);
     }
     if (m->align_l.empty()) {   // openai-whisper's default: every head of the last half of the decoder layers
         for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)
@@ -1202,9 +1230,7 @@ extern "C" int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
         c.hl = m->align_l;
         c.hh = m->align_h;
     }
-    c.pcm = pcm; c.pcm_dtype = pcm_dtype; c.mem = mem;
-    c.sot_seq = sot_seq; c.text_tokens = text_tokens; c.n_text = n_text; c.n_frames = n_frames;
-    c.n_sot = n_sot; c.max_text = max_text; c.no_timestamps = no_timestamps; c.eot = eot;
+    c.no_timestamps = no_timestamps; c.eot = eot;
     c.half = medfilt_width / 2; c.qk_scale = qk_scale;
     c.start_out = start_frame_out; c.prob_out = token_prob_out;
     const int n_ld = max_text + 1;
@@ -1226,4 +1252,42 @@ extern "C" int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
     for (auto &e : ev)
         if (e) (void)hipEventDestroy(e);
     return rc;
+}
+
+extern "C" int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *sot_seq, int n_sot,
+                        int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
+                        const int32_t *n_frames, int medfilt_width, float qk_scale, int32_t *start_frame_out,
+                        float *token_prob_out, wm_mem mem) try {
+    WM_MODEL(ctx);
+    AlignCall c;
+    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
+    m->align_dbg_matrix = nullptr;
+    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
+    WM_REQUIRE(pcm && sot_seq && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID, "bad pcm dtype");
+    WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
+    c.pcm = pcm; c.pcm_dtype = pcm_dtype; c.mem = mem;
+    c.sot_seq = sot_seq; c.text_tokens = text_tokens; c.n_text = n_text; c.n_frames = n_frames;
+    c.n_sot = n_sot; c.max_text = max_text;
+    return align_impl(ctx, c, B, no_timestamps, eot, medfilt_width, qk_scale, start_frame_out, token_prob_out);
+} WM_API_CATCH
+
+// wm_align on mel windows (the window description of wm_transcribe_mel) with one start sequence per row
+extern "C" int wm_align_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                            const int32_t *seek, const int32_t *n_frames, int B, const int32_t *sot_seqs, int n_sot,
+                            int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
+                            int medfilt_width, float qk_scale, int32_t *start_frame_out, float *token_prob_out,
+                            wm_mem mem) try {
+    WM_MODEL(ctx);
+    AlignCall c;
+    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
+    m->align_dbg_matrix = nullptr;
+    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
+    WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
+    WM_REQUIRE(sot_seqs && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
+    c.mel = mel; c.mel_base = mel_base; c.mel_len = mel_len; c.seek = seek; c.mem = mem;
+    c.sot_seq = sot_seqs; c.sot_stride = n_sot; c.text_tokens = text_tokens; c.n_text = n_text; c.n_frames = n_frames;
+    c.n_sot = n_sot; c.max_text = max_text;
+    return align_impl(ctx, c, B, no_timestamps, eot, medfilt_width, qk_scale, start_frame_out, token_prob_out);
 } WM_API_CATCH

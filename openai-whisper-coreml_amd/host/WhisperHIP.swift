@@ -266,6 +266,33 @@ struct Whisper {
         return (0..<rows).map { r in Array(tokens[r * Int(maxNew)..<r * Int(maxNew) + Int(outLens[r])]) }
     }
 
+    /// Word-level timing inputs of the windows of a long-form round (wm_align_mel): the window description of
+    /// transcribeMel, one start sequence per row ([sot, language, task] with the row's own language) and the text tokens the
+    /// round decoded for each window (all < eot).  Same outputs as align.  The word rules (add_word_timestamps) and the
+    /// word-driven seek are host work: binding.py window_word_timestamps / transcribe_long.  Not compiled in this repository.
+    func alignMel(mel: [Float], melBase: [Int64], melLen: [Int32], seek: [Int32], nFrames: [Int32],
+                  sotSequences: [[Int32]], text: [[Int32]], noTimestamps: Int32 = 50363, eot: Int32 = 50257,
+                  medfiltWidth: Int32 = 7) throws -> (startFrames: [[Int32]], tokenProbs: [[Float]]) {
+        typealias AlignMelFn = @convention(c) (OpaquePointer, UnsafePointer<Float>, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                               UnsafePointer<Int32>, UnsafePointer<Int32>, Int32, UnsafePointer<Int32>, Int32,
+                                               Int32, Int32, UnsafePointer<Int32>, UnsafePointer<Int32>, Int32, Int32, Float,
+                                               UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Float>?, Int32) -> Int32
+        let rows = melBase.count
+        let nSot = sotSequences.first?.count ?? 0
+        let sot = sotSequences.flatMap { $0 }
+        let maxText = text.map { $0.count }.max() ?? 0
+        var flat = [Int32](repeating: 0, count: max(1, rows * maxText))
+        for (r, t) in text.enumerated() { flat.replaceSubrange(r * maxText..<r * maxText + t.count, with: t) }
+        let nText = text.map { Int32($0.count) }
+        var start = [Int32](repeating: -1, count: rows * (maxText + 1))
+        var probs = [Float](repeating: 0, count: max(1, rows * maxText))
+        let f: AlignMelFn = try sym("wm_align_mel")
+        try check(f(ctx, mel, melBase, melLen, seek, nFrames, Int32(rows), sot, Int32(nSot), noTimestamps, eot, flat, nText,
+                    Int32(maxText), medfiltWidth, 1.0, &start, &probs, 0))
+        return ((0..<rows).map { r in Array(start[r * (maxText + 1)...r * (maxText + 1) + text[r].count]) },
+                (0..<rows).map { r in Array(probs[r * maxText..<r * maxText + text[r].count]) })
+    }
+
     /// ids -> text with the tokenizer's vocab.json (wm_vocab_load / wm_detokenize; no vocabulary ships with the library).
     func text(of ids: [Int32], vocabJSON: String) throws -> String {
         let load: VocabLoadFn = try sym("wm_vocab_load")

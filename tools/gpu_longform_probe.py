@@ -5,7 +5,7 @@ given as argv[1] (default base), every matrix scaled by weights.lively_gain so t
 length (argv[2], default 8: 10 .. 150 s), the production vocabulary's token ids, text context n_text_ctx.  Prints one JSON
 line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form.
 
-    python tools/gpu_longform_probe.py [model] [recordings] [--condition]
+    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words]
 
 --condition: the cost of condition_on_previous_text instead.  One more JSON line: wall seconds of the long form with
 conditioning off and on (the same recordings, after a warm-up of each; with the default fallback thresholds and with the
@@ -13,7 +13,13 @@ log-prob and compression-ratio thresholds off, where no window falls back and th
 run decoded (per wm_transcribe_mel[_ragged] call: rows x the longest prompt of the call, rows x the longest generated
 length), the position graphs captured (distinct (rows, prompt positions) pairs among the calls, against the 4 graph sets a
 lane keeps), and the per-position time of ONE ragged decode group against a uniform group of the same size and the same
-number of prompt positions (what the row-offset load in the self-attention launch costs)."""
+number of prompt positions (what the row-offset load in the self-attention launch costs).
+
+--words: the cost of word_timestamps instead.  Fallback and the silence skip are off, so every window is kept and goes
+through the alignment; a synthetic vocabulary (one piece per text token) is written to a temporary file.  One more JSON
+line: wall seconds of the long form with word_timestamps off and on, interleaved, three runs each after a warm-up of
+each, the windows and words of a run, and over the wm_align_mel calls of one run their number, rows, wall time and the
+wm_last_stage_ms split (window gather + encoder + cross K/V, teacher-forced pass, alignment kernels + DTW)."""
 import json
 import os
 import sys
@@ -27,7 +33,8 @@ from openai_whisper_coreml_amd import weights as W  # noqa: E402
 
 b = pkg.binding
 CONDITION = "--condition" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--condition"]
+WORDS = "--words" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words")]
 name = argv[0] if len(argv) > 0 else "base"
 N = int(argv[1]) if len(argv) > 1 else 8
 dims = dict(b.MODEL_DIMS[name])
@@ -120,8 +127,58 @@ def condition_probe():
                           ragged_over_uniform=per_pos["ragged"] / per_pos["uniform"])))
 
 
+def words_probe():
+    import tempfile
+    # GPT-2's byte alphabet: printable bytes stand for themselves, the others for U+0100 ...
+    bs = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
+    b2u = {c: chr(c) for c in bs}
+    b2u.update({c: chr(256 + i) for i, c in enumerate(c for c in range(256) if c not in bs)})
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "vocab.json")
+        with open(path, "w") as f:
+            json.dump({"".join(b2u[c] for c in ((" w%d" % i) if i % 3 else ("x%d" % i)).encode()): i for i in range(EOT)}, f)
+        vocab = b.Vocab(path)
+    calls = []
+    inner = ctx.align_mel
+
+    def counted(mel, mel_base, *a, **k):
+        t0 = time.perf_counter()
+        r = inner(mel, mel_base, *a, **k)
+        calls.append(dict(rows=len(mel_base), wall=time.perf_counter() - t0, stage_ms=[float(v) for v in ctx.last_stage_ms()],
+                          text_tokens=int((r[0] >= 0).sum()) - len(mel_base)))
+        return r
+    ctx.align_mel = counted
+    keep = dict(logprob_threshold=None, compression_ratio_threshold=None, no_speech_threshold=None, vocab=vocab)
+    on = dict(keep, word_timestamps=True, no_timestamps=50363)
+    ctx.transcribe_long(recs, **kw, **keep)
+    ctx.transcribe_long(recs, **kw, **on)
+    walls = dict(off=[], on=[])
+    for _ in range(3):
+        for label, extra in (("off", keep), ("on", on)):
+            del calls[:]
+            t0 = time.perf_counter()
+            out = ctx.transcribe_long(recs, **kw, **extra)
+            walls[label].append(time.perf_counter() - t0)
+            if label == "off":
+                windows_off = sum(len(o["windows"]) for o in out)
+    ctx.align_mel = inner
+    stage = [sum(c["stage_ms"][i] for c in calls) for i in range(3)]
+    print(json.dumps(dict(model=name, recordings=N, audio_s=audio_s, wall_s=walls,
+                          median_wall_s={k: float(np.median(v)) for k, v in walls.items()},
+                          on_over_off=float(np.median(walls["on"]) / np.median(walls["off"])),
+                          windows_off=windows_off, windows_on=sum(len(o["windows"]) for o in out),
+                          words=sum(len(s["words"]) for o in out for s in o["segments"]),
+                          align_calls=len(calls), align_rows=sum(c["rows"] for c in calls),
+                          align_text_tokens=sum(c["text_tokens"] for c in calls),
+                          align_wall_s=sum(c["wall"] for c in calls),
+                          align_stage_ms=dict(encoder_cross_kv=stage[0], teacher_forced=stage[1], alignment_dtw=stage[2]))))
+
+
 if CONDITION:
     condition_probe()
+    sys.exit(0)
+if WORDS:
+    words_probe()
     sys.exit(0)
 ctx.transcribe_long(recs[:1], **kw)    # warm-up: graphs, buffers
 t0 = time.perf_counter()
