@@ -183,14 +183,8 @@ int wm_clone_cus(wm_ctx *parent, int cu_lo, int cu_hi, wm_ctx **out) {
 
 extern "C" void wm_destroy(wm_ctx *ctx) {
     if (!ctx) return;
-    for (wm_ctx *lane : ctx->lanes) wm_destroy(lane);  // clones go before the weights they alias
-    ctx->lanes.clear();
-    for (auto &v : ctx->part_lanes) {
-        for (wm_ctx *lane : v) wm_destroy(lane);
-        v.clear();
-    }
-    for (auto &kv : ctx->solo_lanes) wm_destroy(kv.second);
-    ctx->solo_lanes.clear();
+    // clones go before the weights they alias
+    (void)wm_for_each_lane(ctx, false, [](wm_ctx *lane) { wm_destroy(lane); return (int)WM_OK; });
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     wm_model_destroy(ctx);

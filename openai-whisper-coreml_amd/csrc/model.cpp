@@ -84,20 +84,20 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     return WM_OK;
 }
 
-WmStopDev wm_model_stop_dev(const WmModel *m) {
+WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode) {
     WmStopDev t;
     memset(&t, 0, sizeof(t));
-    if (!m->stop_on) return t;
-    t.done = m->ddone; t.budget = m->budget_on ? m->dbudget : nullptr; t.live_rows = m->dlive; t.n_live = m->dnlive;
-    t.eot = m->stop_eot;
-    t.pad_tok = m->stop_eot >= 0 ? m->stop_eot : 0;   // what a finished row keeps embedding: any valid id
+    if (!mode.stop) return t;
+    t.done = m->ddone; t.budget = mode.budget ? m->dbudget : nullptr; t.live_rows = m->dlive; t.n_live = m->dnlive;
+    t.eot = mode.stop_eot;
+    t.pad_tok = mode.stop_eot >= 0 ? mode.stop_eot : 0;   // what a finished row keeps embedding: any valid id
     return t;
 }
 
-WmXDev wm_model_x_dev(const WmModel *m) {
+WmXDev wm_model_x_dev(const WmModel *m, const WmDecodeMode &mode) {
     WmXDev t;
     memset(&t, 0, sizeof(t));
-    if (!m->x_on) return t;
+    if (!mode.x) return t;
     t.par = m->dx_par; t.txt = m->dx_txt; t.win = m->dx_win; t.all = m->dx_all; t.ns_v = m->dx_nsv;
     t.logprob = m->dx_logprob; t.nospeech = m->dx_nospeech; t.ids = m->dx_ids;
     return t;
@@ -106,7 +106,6 @@ WmXDev wm_model_x_dev(const WmModel *m) {
 void wm_model_drop_graphs(WmModel *m) {
     for (WmModel::GraphSet &g : m->graph_sets) g.destroy();
     m->graph_sets.clear();
-    m->graph_cur = -1;
     m->lid_graph.destroy();
 }
 
@@ -323,9 +322,7 @@ void wm_model_destroy(wm_ctx *ctx) {
     wm_model_drop_graphs(m);
     if (m->h_nlive) (void)hipHostFree(m->h_nlive);
     for (void *p : m->allocs) (void)hipFree(p);
-    if (m->pcm_stage) (void)hipFree(m->pcm_stage);
-    if (m->io_stage) (void)hipFree(m->io_stage);
-    if (m->align_ws) (void)hipFree(m->align_ws);
+    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws}) b->release();
     delete m;
     ctx->model = nullptr;
 }
@@ -452,6 +449,16 @@ int wm_model_finalize(wm_ctx *ctx) {
 }
 
 // ------------------------------------------------------------------ activations --------
+int WmDevBuf::reserve(hipStream_t stream, size_t need) {
+    if (bytes >= need) return WM_OK;
+    WM_HIP(hipStreamSynchronize(stream));
+    if (p) WM_HIP(hipFree(p));
+    p = nullptr; bytes = 0;
+    WM_HIP(hipMalloc(&p, need));
+    bytes = need;
+    return WM_OK;
+}
+
 int wm_model_reserve(wm_ctx *ctx, int B) {
     WmModel *m = ctx->model;
     WM_REQUIRE(m, WM_ERR_STATE, "context has no model");
@@ -577,10 +584,6 @@ int wm_model_decode_begin(wm_ctx *ctx, int B) {
     // the arrival counter of the arg-max workgroups is zero between launches; a decode that was abandoned half way
     // (an error in the middle of a step) must not leave the next one with a stale count
     WM_HIP(hipMemsetAsync(m->darrive, 0, sizeof(int), ctx->stream));
-    m->stop_on = false;   // wm_transcribe_greedy switches it on for its own decode (lane_prefill)
-    m->x_on = false;      // ... and wm_transcribe its extended decode
-    m->off_on = false;    // ... and wm_transcribe_mel_ragged the row offsets of a ragged group
-    m->xattn_shared = false;   // ... and decides whether the group shares the chip
     return WM_OK;
 }
 
@@ -595,14 +598,15 @@ int wm_model_set_pos(wm_ctx *ctx, int pos) {
     return WM_OK;
 }
 
-int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, int mask_first_pos, bool use_ts,
-                         bool x, const WmAlignCap *cap) {
+int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, const WmAlignCap *cap,
+                         const WmDecodeMode &mode, int n_prompt) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head, T = D.n_text_ctx, S = 1500;
     const int ns = wm_dec_attn_splits(B, H);
     const int xns = g_wm_tuning.xattn_splits > 0 ? g_wm_tuning.xattn_splits : ns;   // 0 in the product
-    const int *live = m->stop_on ? m->dlive : nullptr, *nlive = m->stop_on ? m->dnlive : nullptr;
+    const int *live = mode.stop ? m->dlive : nullptr, *nlive = mode.stop ? m->dnlive : nullptr;
+    const int *off = mode.off ? m->doff : nullptr;
     // mean-centring offsets of the bf16 residual copy: the embedding wrote buffer 0; every LayerNorm-folded GEMV reads
     // the current buffer and leaves the new means in the other one
     int cur = 0;
@@ -623,15 +627,14 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         a.pos_ptr = m->dpos; a.n_ctx = T; a.n_head = H;
         WM_TRY(wm_dec_gemv(ctx, a));
         // 2. causal self-attention over positions 0..pos
-        WM_TRY(wm_dec_self_attention(ctx, m->dq, kc, vc, B, H, T, 0, m->dpos, m->datt, L.wo, d, d, live, nlive,
-                                     m->off_on ? m->doff : nullptr));
+        WM_TRY(wm_dec_self_attention(ctx, m->dq, kc, vc, B, H, T, 0, m->dpos, m->datt, L.wo, d, d, live, nlive, off));
         // 3. out-projection + residual (f32 stream, its bf16 copy, partial statistics)
         memset(&a, 0, sizeof(a));
         a.epi = DE_RESID; a.B = B; a.N = d; a.K = d; a.W = L.wo; a.c2 = L.bo;
         a.a = m->datt; a.out_f32 = m->dx; a.out_bf16 = m->dxb; a.ldo = d; a.stats_out = m->dstats;
         a.mean_in = mean_buf(cur);
         a.pf_ptr = L.wxq_f; a.pf_rows = d; a.pf_k = d;
-        const bool xshort = m->xattn_shared && !g_wm_tuning.xattn_never_short;
+        const bool xshort = mode.xattn_shared && !g_wm_tuning.xattn_never_short;
         // wm_align: a layer with alignment heads leaves its f32 query in m->dq (the two launches: same bits as the fused one)
         const bool cap_l = cap && cap->layer[l].n > 0;
         const bool fuse_q = !cap_l && xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
@@ -684,32 +687,31 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         a.mean_in = mean_buf(cur); a.mean_out = mean_buf(cur ^ 1);
         a.out_f32 = want_logits ? m->dlogits : nullptr; a.ldo = m->vpad;
         a.argmax = m->dargmax; a.arg_first = arg_first; a.arg_last = arg_last;
-        if (mask_first_pos >= 0) {
-            a.mask = m->dmask; a.mask_words = m->vpad / 32; a.mask_first_pos = mask_first_pos; a.pos_ptr = m->dpos;
+        if (mode.mask) {
+            a.mask = m->dmask; a.mask_words = m->vpad / 32; a.mask_first_pos = n_prompt - 1; a.pos_ptr = m->dpos;
         }
-        if (use_ts) a.ts = wm_model_ts_dev(m);
-        if (x) {   // extended decode: its own epilogue instantiation, the position always from the device
-            WM_REQUIRE(m->x_on, WM_ERR_STATE, "extended decode step without its state");
-            a.epi = DE_LOGITS_X; a.x = wm_model_x_dev(m); a.pos_ptr = m->dpos;
+        if (mode.ts) a.ts = wm_model_ts_dev(m);
+        if (mode.x) {   // extended decode: its own epilogue instantiation, the position always from the device
+            a.epi = DE_LOGITS_X; a.x = wm_model_x_dev(m, mode); a.pos_ptr = m->dpos;
         }
         WM_TRY(wm_dec_gemv(ctx, a));
     }
     return WM_OK;
 }
 
-int wm_model_embed_first(wm_ctx *ctx, int B) {
+int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
     return wm_dec_embed(ctx, m->dseq, m->dpos, B, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dx, m->dxb, m->dstats, m->dmean,
-                        m->off_on ? m->doff : nullptr);
+                        mode.off ? m->doff : nullptr);
 }
 
-int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, bool use_ts, bool x) {
+int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
     const WmTsDev t = wm_model_ts_dev(m);
-    const WmStopDev sp = wm_model_stop_dev(m);
-    const WmXDev xd = wm_model_x_dev(m);
+    const WmStopDev sp = wm_model_stop_dev(m, mode);
+    const WmXDev xd = wm_model_x_dev(m, mode);
     return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, write_seq ? m->dseq : nullptr, m->dpos, n_prompt, result,
                            arg_first, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dims.n_text_ctx, m->dx, m->dxb,
-                           m->dstats, use_ts ? &t : nullptr, m->darrive, use_ts ? m->ts_eot : arg_first, m->dmean,
-                           m->stop_on ? &sp : nullptr, x ? &xd : nullptr, m->off_on ? m->doff : nullptr);
+                           m->dstats, mode.ts ? &t : nullptr, m->darrive, mode.ts ? m->ts_eot : arg_first, m->dmean,
+                           mode.stop ? &sp : nullptr, mode.x ? &xd : nullptr, mode.off ? m->doff : nullptr);
 }

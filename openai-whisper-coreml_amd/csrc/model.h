@@ -146,6 +146,54 @@ struct WmAlignDev {
     int half;                // medfilt_width / 2
 };
 
+// The mode of ONE decode: everything a captured position bakes into its kernel arguments that the context's weights and
+// shapes do not fix.  A default-constructed value is the plain teacher-forced step (wm_decode_logits, language
+// identification, wm_align); a transcribe call fills its groups' mode once (model_api.cpp lane_prefill) and every step,
+// eager or captured, is handed that value -- it is also, member by member, the key of the captured graphs (GraphSet).
+struct WmDecodeMode {
+    bool mask = false;      // the suppress bitmaps apply (wm_set_suppress), the first-token one at position n_prompt - 1
+    bool ts = false;        // the timestamp rules apply (wm_set_timestamp_rules, WmTsDev)
+    bool x = false;         // extended decode: the X-mode kernels and their WmXDev state
+    bool off = false;       // a ragged group: the row offsets WmModel::doff
+    bool stop = false;      // early stop: the WmStopDev state ...
+    bool budget = false;    // ... with per-row token budgets
+    int stop_eot = -1;      // ... and this end-of-text id (< 0: budgets only)
+    // The group SHARES the chip with other groups (other lanes of the call, other contexts' calls): its cross-attention
+    // is launched as one short-lived workgroup per (sequence, head) pair instead of <= 256 persistent ones.  Alone, the
+    // persistent shape streams faster (56 rows: 66.8 vs 70.5 us); next to other groups' kernels the short-lived one lets
+    // their workgroups in every ~13 us instead of once per launch: driver command 2076 -> 2100-2134 audio-s/s, default
+    // run 2190 -> 2250 (profiles/r04_xattn_short_lived.txt).  A launch shape: same bits.
+    bool xattn_shared = false;
+    bool operator==(const WmDecodeMode &o) const {
+        return mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+               stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
+    }
+};
+
+// A grow-only device buffer: reserve() keeps what it has when that is enough, otherwise waits for the stream, frees and
+// reallocates (contents are not kept); a failed allocation leaves {nullptr, 0}.
+struct WmDevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int reserve(hipStream_t stream, size_t need);   // model.cpp
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+    }
+};
+
+// A captured graph and its executable instance.  Not a destructor-owning type: GraphSet lives in a std::vector that is
+// erased from and pushed to, so the owner calls destroy() (wm_model_drop_graphs, the LRU eviction).
+struct WmGraph {
+    hipGraph_t g = nullptr;
+    hipGraphExec_t e = nullptr;
+    void destroy() {
+        if (e) (void)hipGraphExecDestroy(e);
+        if (g) (void)hipGraphDestroy(g);
+        e = nullptr; g = nullptr;
+    }
+};
+
 struct WmModel {
     wm_dims dims;
     bool finalized = false;
@@ -199,43 +247,27 @@ struct WmModel {
     // scalar per group.  Row b's prompt starts at position doff[b] = P - len_b: its positional embedding and the first key
     // of its causal self-attention count from there (dec_kernels.hip).  Uploaded at prefill like dx_ids.
     int *doff = nullptr;        // [WM_DEC_MAXB]
-    bool off_on = false;        // the decode being enqueued is ragged (kernel arguments of the captured graphs)
     int *darrive = nullptr;     // [1] arrival counter of the arg-max workgroups (zero between launches)
     // early stop (wm_transcribe_greedy with eot >= 0 or per-chunk token budgets): see WmStopDev
     int *ddone = nullptr, *dbudget = nullptr, *dlive = nullptr, *dnlive = nullptr;
     int *h_nlive = nullptr;     // pinned host ring: n_live after each burst of positions (the host polls it)
-    // The decode group being enqueued SHARES the chip with other groups (other lanes of the call, other contexts' calls):
-    // its cross-attention is launched as one short-lived workgroup per (sequence, head) pair instead of <= 256 persistent
-    // ones.  Alone, the persistent shape streams faster (56 rows: 66.8 vs 70.5 us); next to other groups' kernels the
-    // short-lived one lets their workgroups in every ~13 us instead of once per launch: driver command 2076 -> 2100-2134
-    // audio-s/s, default run 2190 -> 2250 (profiles/r04_xattn_short_lived.txt).  A launch shape: same bits.
-    bool xattn_shared = false;
-    bool stop_on = false;       // the decode being enqueued uses the stop state (kernel arguments of the captured graph)
-    bool budget_on = false;
-    int stop_eot = -1;
     std::vector<int32_t> budget_host;  // wm_set_token_budgets: per-chunk budgets of the NEXT call (empty: none)
     // Captured decode steps: one hipGraph of ONE position, and one of WM_BURST consecutive positions (the arg-max kernel
     // advances the device-side position, so consecutive positions do not depend on the host: 1/8 of the graph launches).
-    // Everything a capture bakes into its kernel arguments is in the key; a lane keeps the last few shapes it ran
+    // Everything a capture bakes into its kernel arguments is in the key (the shape and the WmDecodeMode it was captured
+    // for, compared member by member); a lane keeps the last few shapes it ran
     // (a server alternating between batch sizes, bench.py's groups of 56 / 48 chunks landing on different lanes from one
     // pass to the next) instead of re-capturing ~2300 launches every time the shape changes (measured: the capture is
     // host work of a few ms that hides behind the lane's own encoder, so this is tidiness, not throughput).
     struct GraphSet {
-        int B = 0, n_prompt = 0, cap_b = 0, mask = 0, stop_key = 0;  // mask: bit 0 suppress, 1 timestamps, 2 X mode, 3 ragged
-        // [mode]: 0 = the group has the chip to itself, 1 = it shares it (xattn_shared: short-lived cross-attention
+        int B = 0, n_prompt = 0, cap_b = 0;
+        WmDecodeMode mode;   // with xattn_shared false: sharing is the index below
+        // [shared]: 0 = the group has the chip to itself, 1 = it shares it (xattn_shared: short-lived cross-attention
         // workgroups); chosen burst by burst from the number of decodes in flight on the device, captured on first use
         int burst[2] = {0, 0};
-        hipGraph_t g1[2] = {nullptr, nullptr}, gk[2] = {nullptr, nullptr};
-        hipGraphExec_t e1[2] = {nullptr, nullptr}, ek[2] = {nullptr, nullptr};
+        WmGraph g1[2], gk[2];   // one position, burst[.] positions
         void destroy() {
-            for (int i = 0; i < 2; ++i) {
-                if (e1[i]) (void)hipGraphExecDestroy(e1[i]);
-                if (g1[i]) (void)hipGraphDestroy(g1[i]);
-                if (ek[i]) (void)hipGraphExecDestroy(ek[i]);
-                if (gk[i]) (void)hipGraphDestroy(gk[i]);
-                e1[i] = ek[i] = nullptr;
-                g1[i] = gk[i] = nullptr;
-            }
+            for (int i = 0; i < 2; ++i) { g1[i].destroy(); gk[i].destroy(); }
         }
         unsigned long stamp = 0;   // last use (LRU eviction)
     };
@@ -244,18 +276,12 @@ struct WmModel {
     // captured once per shape and replayed (round 6: the reference's own flow, device-resident, 2.23 -> see profiles/).
     struct LidGraph {
         int B = 0, cap_b = 0, first = 0, last = 0, logits = 0;
-        hipGraph_t g = nullptr;
-        hipGraphExec_t e = nullptr;
-        void destroy() {
-            if (e) (void)hipGraphExecDestroy(e);
-            if (g) (void)hipGraphDestroy(g);
-            e = nullptr; g = nullptr; B = 0;
-        }
+        WmGraph graph;
+        void destroy() { graph.destroy(); B = 0; }
     } lid_graph;
     std::vector<int32_t> lid_host;   // host staging of the call's <|startoftranscript|> row (outlives the async upload)
     static constexpr int kMaxGraphSets = 4;
     std::vector<GraphSet> graph_sets;
-    int graph_cur = -1;            // the set of the decode being enqueued
     unsigned long graph_clock = 0;
     unsigned *dmask = nullptr;   // [2][vpad/32] suppressed-token bitmaps (wm_set_suppress); [1] = first generated token
     bool mask_on = false;
@@ -267,7 +293,6 @@ struct WmModel {
     unsigned long long *dts_key = nullptr;
     float *dts_lse = nullptr;
     // wm_transcribe's extended decode (WmXDev): per-tile partials, outputs and the group's parameters
-    bool x_on = false;          // the decode being enqueued runs the X-mode kernels (a key of the captured graphs)
     float *dx_txt = nullptr, *dx_win = nullptr, *dx_all = nullptr, *dx_nsv = nullptr;
     float *dx_logprob = nullptr;   // [n_text_ctx][WM_DEC_MAXB]
     float *dx_nospeech = nullptr;  // [WM_DEC_MAXB]
@@ -277,13 +302,10 @@ struct WmModel {
     // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..), the
     // workspace of a call (grown on demand) and the debug library's one-shot cost-matrix capture (host, null in the product)
     std::vector<int32_t> align_l, align_h;
-    void *align_ws = nullptr;
-    size_t align_ws_bytes = 0;
+    WmDevBuf align_ws;
     float *align_dbg_matrix = nullptr;
-    void *pcm_stage = nullptr;  // host-pointer staging for wm_transcribe_greedy
-    size_t pcm_stage_bytes = 0;
-    float *io_stage = nullptr;  // staging for host-pointer model calls
-    size_t io_stage_bytes = 0;
+    WmDevBuf pcm_stage;   // host-pointer staging of a decode group's PCM (wm_transcribe*, wm_align)
+    WmDevBuf io_stage;    // staging for host-pointer model calls
 };
 
 // model.cpp
@@ -306,23 +328,23 @@ int wm_model_decode_begin(wm_ctx *ctx, int B);
 // embedded input of that position in m->dx (+ m->dstats): wm_model_embed_first for the first
 // position, afterwards produced by wm_model_close_step.  Ends with logits -> per-tile arg-max over
 // [arg_first, arg_last] (m->dargmax); want_logits additionally stores f32 logits in m->dlogits.
-// x: X mode (log-probs, no-speech, sampling; m->x_on's WmXDev) -- DE_LOGITS_X and the arg-max kernel's X variant
 // cap (wm_align): the layers with alignment heads take the unfused cross_attn_ln + query path and copy those heads' queries
-int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, int mask_first_pos = -1,
-                         bool use_ts = false, bool x = false, const WmAlignCap *cap = nullptr);
-// the device view of the extended-decode state (par == null when m->x_on is false)
-WmXDev wm_model_x_dev(const WmModel *m);
+// mode: see WmDecodeMode (mode.x: log-probs, no-speech, sampling -- DE_LOGITS_X and the arg-max kernel's X variant);
+// n_prompt is read with mode.mask only: the first-token suppress bitmap applies at decode position n_prompt - 1
+int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, const WmAlignCap *cap = nullptr,
+                         const WmDecodeMode &mode = WmDecodeMode(), int n_prompt = 0);
+// the device view of the extended-decode state (par == null when mode.x is false)
+WmXDev wm_model_x_dev(const WmModel *m, const WmDecodeMode &mode);
 // the device view of the context's timestamp-rule state (rng == null when the rules are off)
 WmTsDev wm_model_ts_dev(const WmModel *m);
 int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int32_t eot, int32_t max_initial);
-// mask_first_pos >= 0: apply the suppress bitmaps, the first-token one at decode position mask_first_pos
 int wm_model_set_suppress(wm_ctx *ctx, const int32_t *ids, int n, const int32_t *first_ids, int n_first);
-int wm_model_embed_first(wm_ctx *ctx, int B);
+int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode = WmDecodeMode());
 // arg-max reduce + write next token (positions >= n_prompt) + embed next position + advance *dpos
-int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, bool use_ts = false,
-                        bool x = false);
-// the device view of the early-stop state (done == null when m->stop_on is false)
-WmStopDev wm_model_stop_dev(const WmModel *m);
+int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first,
+                        const WmDecodeMode &mode = WmDecodeMode());
+// the device view of the early-stop state (done == null when mode.stop is false)
+WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode);
 void wm_model_drop_graphs(WmModel *m);
 int wm_model_set_pos(wm_ctx *ctx, int pos);
 

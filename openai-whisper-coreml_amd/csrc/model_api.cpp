@@ -20,18 +20,58 @@
     WM_REQUIRE(m != nullptr, WM_ERR_STATE, "context was created without a model (use wm_create)")
 
 static int io_stage(wm_ctx *ctx, size_t bytes, char **out) {
-    WmModel *m = ctx->model;
-    if (m->io_stage_bytes < bytes) {
-        WM_HIP(hipStreamSynchronize(ctx->stream));
-        if (m->io_stage) WM_HIP(hipFree(m->io_stage));
-        m->io_stage = nullptr;
-        m->io_stage_bytes = 0;
-        WM_HIP(hipMalloc((void **)&m->io_stage, bytes));
-        m->io_stage_bytes = bytes;
-    }
-    *out = (char *)m->io_stage;
+    WM_TRY(ctx->model->io_stage.reserve(ctx->stream, bytes));
+    *out = (char *)ctx->model->io_stage.p;
     return WM_OK;
 }
+
+namespace {
+int lane_limit() {
+    static const int n = [] {
+        const char *e = getenv("WM_LANES");
+        const int v = e ? atoi(e) : 3;
+        return v < 1 ? 1 : (v > 8 ? 8 : v);
+    }();
+    return n;
+}
+
+int burst_len() {
+    static const int n = [] {
+        const char *e = getenv("WM_BURST");
+        const int v = e ? atoi(e) : 8;
+        return v < 1 ? 1 : (v > 32 ? 32 : v);
+    }();
+    return n;
+}
+
+bool graphs_off() {   // every decode step is launched eagerly
+    static const bool off = getenv("WM_NO_GRAPH") != nullptr;
+    return off;
+}
+
+// Capture what `enqueue` launches on the stream into *out (whatever it held is destroyed first) and instantiate it.  A
+// half-captured graph is of no use: on any failure *out is left empty; `what` names the graph in the error.
+template <typename F>
+int capture_graph(hipStream_t stream, WmGraph *out, const char *what, F &&enqueue) {
+    out->destroy();
+    WM_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    const int crc = enqueue();
+    const hipError_t ce = hipStreamEndCapture(stream, &out->g);
+    if (crc != WM_OK || ce != hipSuccess) {
+        if (ce != hipSuccess) out->g = nullptr;
+        out->destroy();
+        if (crc != WM_OK) return crc;
+        WM_HIP(ce);
+    }
+    if (hipGraphInstantiate(&out->e, out->g, nullptr, nullptr, 0) != hipSuccess) {
+        out->e = nullptr;
+        out->destroy();
+        wm_set_error("hipGraphInstantiate failed for %s", what);
+        return WM_ERR_HIP;
+    }
+    return WM_OK;
+}
+}  // namespace
 
 extern "C" int wm_set_tensor(wm_ctx *ctx, const char *name, const float *data, size_t n) try {
     WM_MODEL(ctx);
@@ -62,26 +102,15 @@ extern "C" int wm_finalize(wm_ctx *ctx) try {
 extern "C" int wm_set_suppress(wm_ctx *ctx, const int32_t *suppress, int n, const int32_t *suppress_first, int n_first) try {
     WM_MODEL(ctx);
     (void)m;
-    WM_TRY(wm_model_set_suppress(ctx, suppress, n, suppress_first, n_first));
-    for (wm_ctx *lane : ctx->lanes) WM_TRY(wm_model_set_suppress(lane, suppress, n, suppress_first, n_first));
-    for (auto &v : ctx->part_lanes)
-        for (wm_ctx *lane : v) WM_TRY(wm_model_set_suppress(lane, suppress, n, suppress_first, n_first));
-    for (auto &kv : ctx->solo_lanes) WM_TRY(wm_model_set_suppress(kv.second, suppress, n, suppress_first, n_first));
-    return WM_OK;
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { return wm_model_set_suppress(c, suppress, n, suppress_first, n_first); });
 } WM_API_CATCH
 extern "C" int wm_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t timestamp_begin, int32_t eot,
                                       int32_t max_initial_timestamp_index) try {
     WM_MODEL(ctx);
     (void)m;
-    WM_TRY(wm_model_set_timestamp_rules(ctx, enable, timestamp_begin, eot, max_initial_timestamp_index));
-    for (wm_ctx *lane : ctx->lanes)
-        WM_TRY(wm_model_set_timestamp_rules(lane, enable, timestamp_begin, eot, max_initial_timestamp_index));
-    for (auto &v : ctx->part_lanes)
-        for (wm_ctx *lane : v)
-            WM_TRY(wm_model_set_timestamp_rules(lane, enable, timestamp_begin, eot, max_initial_timestamp_index));
-    for (auto &kv : ctx->solo_lanes)
-        WM_TRY(wm_model_set_timestamp_rules(kv.second, enable, timestamp_begin, eot, max_initial_timestamp_index));
-    return WM_OK;
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) {
+        return wm_model_set_timestamp_rules(c, enable, timestamp_begin, eot, max_initial_timestamp_index);
+    });
 } WM_API_CATCH
 extern "C" int wm_set_lanes(wm_ctx *ctx, int n_lanes) try {
     WM_REQUIRE(ctx, WM_ERR_INVALID, "null context");
@@ -290,36 +319,22 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
     WM_TRY(load_xa(ctx, xa, B, mem));
     WM_TRY(wm_model_set_pos(ctx, 0));
     WM_TRY(wm_model_embed_first(ctx, B));
-    static const bool no_graph = getenv("WM_NO_GRAPH") != nullptr;
     auto step = [&]() -> int {
         WM_TRY(wm_model_decode_step(ctx, B, probs != nullptr, lang_first, lang_last));     // :36-37
         return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, nullptr, nullptr, 0, m->dresult, lang_first, nullptr,
                                nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, m->darrive, lang_first);  // :38
     };
-    if (no_graph || ctx->prof.on) {
+    if (graphs_off() || ctx->prof.on) {
         WM_TRY(step());
     } else {
         WmModel::LidGraph &lg = m->lid_graph;
         const int want = probs != nullptr ? 1 : 0;
-        if (!lg.e || lg.B != B || lg.cap_b != m->cap_b || lg.first != lang_first || lg.last != lang_last || lg.logits != want) {
+        if (!lg.graph.e || lg.B != B || lg.cap_b != m->cap_b || lg.first != lang_first || lg.last != lang_last || lg.logits != want) {
             lg.destroy();
-            WM_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            const int crc = step();
-            const hipError_t ce = hipStreamEndCapture(ctx->stream, &lg.g);
-            if (crc != WM_OK || ce != hipSuccess) {
-                if (ce == hipSuccess && lg.g) (void)hipGraphDestroy(lg.g);
-                lg.g = nullptr;
-                if (crc != WM_OK) return crc;
-                WM_HIP(ce);
-            }
-            if (hipGraphInstantiate(&lg.e, lg.g, nullptr, nullptr, 0) != hipSuccess) {
-                lg.destroy();
-                wm_set_error("hipGraphInstantiate failed for the language-identification step");
-                return WM_ERR_HIP;
-            }
+            WM_TRY(capture_graph(ctx->stream, &lg.graph, "the language-identification step", step));
             lg.B = B; lg.cap_b = m->cap_b; lg.first = lang_first; lg.last = lang_last; lg.logits = want;
         }
-        WM_HIP(hipGraphLaunch(lg.e, ctx->stream));
+        WM_HIP(hipGraphLaunch(lg.graph.e, ctx->stream));
     }
     if (probs) {  // openai-whisper detect_language(): softmax over the language-token logits only
         const int n_lang = lang_last - lang_first + 1;
@@ -333,13 +348,10 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
         if (mem == WM_MEM_HOST)
             WM_HIP(hipMemcpyAsync(probs, d_probs, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (mem == WM_MEM_DEVICE) {   // the caller's buffer is device memory: one device-to-device copy behind the step
-        WM_HIP(hipMemcpyAsync(lang_idx, m->dresult, (size_t)B * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        WM_HIP(hipStreamSynchronize(ctx->stream));
-    } else {
-        WM_HIP(hipMemcpyAsync(lang_idx, m->dresult, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
-        WM_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    // (the caller's buffer in device memory: one device-to-device copy behind the step)
+    WM_HIP(hipMemcpyAsync(lang_idx, m->dresult, (size_t)B * 4, mem == WM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                          ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
     return WM_OK;
 }
 
@@ -367,29 +379,13 @@ extern "C" int wm_set_token_budgets(wm_ctx *ctx, const int32_t *budgets, int n) 
 namespace {
 constexpr int kGroupChunks = 8;   // smallest decode group worth a lane (BASELINE.json configs[3]); up to WM_DEC_MAXB
 
-int lane_limit() {
-    static const int n = [] {
-        const char *e = getenv("WM_LANES");
-        const int v = e ? atoi(e) : 3;
-        return v < 1 ? 1 : (v > 8 ? 8 : v);
-    }();
-    return n;
-}
-
-int burst_len() {
-    static const int n = [] {
-        const char *e = getenv("WM_BURST");
-        const int v = e ? atoi(e) : 8;
-        return v < 1 ? 1 : (v > 32 ? 32 : v);
-    }();
-    return n;
-}
-
 struct LaneJob {
     enum State { IDLE, DECODING, DRAINING };
     wm_ctx *c = nullptr;
     int b0 = 0, Bg = 0;
     int P = 0;          // prompt positions of the group (a ragged call: the longest prompt among ITS rows)
+    WmDecodeMode mode;  // of the group's decode (xattn_shared: decided burst by burst), filled by lane_prefill
+    int gset = -1;      // its graph set in the lane's WmModel::graph_sets (lane_graph)
     State state = IDLE;
     int t = 0;          // decoder positions enqueued so far
     int bursts = 0;     // bursts enqueued so far
@@ -412,13 +408,18 @@ struct LaneJob {
     }
 };
 
-// where a call's rows come from: PCM chunks (wm_transcribe) or mel windows (wm_transcribe_mel), and their prompts
-struct TxSrc {
+// where a call's encoder input comes from: PCM chunks [.][480000], or (mel non-null) mel windows -- row b is frames
+// seek[b] .. seek[b] + n_frames[b] - 1 of the [n_mels][mel_len[b]] block at mel + mel_base[b]
+struct WmAudioSrc {
     const void *pcm = nullptr;
     wm_dtype pcm_dtype = WM_F32;
-    const float *mel = nullptr;        // non-null: mel windows
+    const float *mel = nullptr;
     const int64_t *mel_base = nullptr;
     const int32_t *mel_len = nullptr, *seek = nullptr, *n_frames = nullptr;
+};
+
+// a transcribe call's rows (wm_transcribe: PCM, wm_transcribe_mel: windows) and their prompts
+struct TxSrc : WmAudioSrc {
     const int32_t *prompt = nullptr;   // row b's prompt: prompt + b * prompt_stride (0: one prompt for all)
     int prompt_stride = 0;
     const int32_t *prompt_len = nullptr;   // non-null: a ragged call, row b's prompt is its first prompt_len[b] entries
@@ -463,27 +464,71 @@ int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len
 }
 
 namespace {
+// row b of a mel source: its window lies inside its block (`who` prefixes the message; align bounds n_frames tighter itself)
+int check_window(const WmAudioSrc &a, int b, const char *who) {
+    WM_REQUIRE(a.mel_base[b] >= 0 && a.mel_len[b] >= 1 && a.seek[b] >= 0 && a.n_frames[b] >= 1 &&
+                   a.n_frames[b] <= WM_N_FRAMES && (int64_t)a.seek[b] + a.n_frames[b] <= a.mel_len[b],
+               WM_ERR_INVALID, "%srow %d: window (base %lld, T %d, seek %d, n_frames %d) invalid", who, b,
+               (long long)a.mel_base[b], a.mel_len[b], a.seek[b], a.n_frames[b]);
+    return WM_OK;
+}
+
+// *d_pcm = the PCM of rows [b0, b0 + Bg) in device memory: the caller's, or (host memory) uploaded into m->pcm_stage.
+// Null for a mel source.
+int stage_pcm(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const void **d_pcm) {
+    WmModel *m = c->model;
+    *d_pcm = nullptr;
+    if (a.mel) return WM_OK;
+    const size_t row = WM_N_SAMPLES * pcm_elem(a.pcm_dtype);
+    *d_pcm = (const char *)a.pcm + (size_t)b0 * row;
+    if (mem != WM_MEM_HOST) return WM_OK;
+    WM_TRY(m->pcm_stage.reserve(c->stream, (size_t)Bg * row));
+    WM_HIP(hipMemcpyAsync(m->pcm_stage.p, *d_pcm, (size_t)Bg * row, hipMemcpyHostToDevice, c->stream));
+    *d_pcm = m->pcm_stage.p;
+    return WM_OK;
+}
+
+// The encoder input (enc_mel, enc_win) of rows [b0, b0 + Bg), to be called after wm_model_reserve.  PCM: the log-mel front
+// end (f32 fast path) of d_pcm into m->mel_f32, output stays in HBM, no windows.  Mel windows: the table `win` -- the
+// CALLER's, it is the source of an asynchronous upload -- in m->dmel_win, gathered by the encoder's first step from the
+// caller's device memory; with host memory only the windows are copied, into the front end's buffer.
+int stage_mel(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const void *d_pcm, std::vector<WmMelWin> &win,
+              const float **enc_mel, const WmMelWin **enc_win) {
+    WmModel *m = c->model;
+    const int C = m->dims.n_mels;
+    *enc_mel = m->mel_f32;
+    *enc_win = nullptr;
+    if (!a.mel) return wm_frontend_run(&c->fe, &c->prof, c->stream, d_pcm, a.pcm_dtype, Bg, C, m->mel_f32, WM_F32);
+    win.resize(Bg);
+    for (int b = 0; b < Bg; ++b) {
+        const int r = b0 + b;
+        WmMelWin &w = win[b];
+        w.T = a.mel_len[r]; w.seek = a.seek[r]; w.n = a.n_frames[r]; w.pad = 0;
+        w.base = a.mel_base[r];
+        if (mem == WM_MEM_HOST) {
+            WM_HIP(hipMemcpy2DAsync(m->mel_f32 + (size_t)b * C * WM_N_FRAMES, WM_N_FRAMES * sizeof(float),
+                                    a.mel + w.base + w.seek, (size_t)w.T * sizeof(float), (size_t)w.n * sizeof(float),
+                                    C, hipMemcpyHostToDevice, c->stream));
+            w.base = (long long)b * C * WM_N_FRAMES; w.T = WM_N_FRAMES; w.seek = 0;
+        }
+    }
+    WM_HIP(hipMemcpyAsync(m->dmel_win, win.data(), (size_t)Bg * sizeof(WmMelWin), hipMemcpyHostToDevice, c->stream));
+    if (mem != WM_MEM_HOST) *enc_mel = a.mel;
+    *enc_win = m->dmel_win;
+    return WM_OK;
+}
+
 // front end -> encoder -> cross K/V -> prompt upload -> first embedding, all enqueued on the lane's stream
 int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const StopCfg &stop, const XCfg &xc) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
-    const wm_dims &D = m->dims;
     const int Bg = j.Bg;
-    const wm_dtype pcm_dtype = src.pcm_dtype;
-    const size_t bytes = src.mel ? 0 : (size_t)Bg * WM_N_SAMPLES * pcm_elem(pcm_dtype);
-    const void *d_pcm = src.mel ? nullptr : (const char *)src.pcm + (size_t)j.b0 * WM_N_SAMPLES * pcm_elem(pcm_dtype);
-    if (mem == WM_MEM_HOST && !src.mel) {
-        if (m->pcm_stage_bytes < bytes) {
-            WM_HIP(hipStreamSynchronize(c->stream));
-            if (m->pcm_stage) WM_HIP(hipFree(m->pcm_stage));
-            m->pcm_stage = nullptr;
-            m->pcm_stage_bytes = 0;
-            WM_HIP(hipMalloc(&m->pcm_stage, bytes));
-            m->pcm_stage_bytes = bytes;
-        }
-        WM_HIP(hipMemcpyAsync(m->pcm_stage, d_pcm, bytes, hipMemcpyHostToDevice, c->stream));
-        d_pcm = m->pcm_stage;
-    }
+    // the mode of this group's decode: the lane's own context settings and the call's options, in this one place
+    j.mode = WmDecodeMode();
+    j.mode.mask = m->mask_on; j.mode.ts = m->ts_on; j.mode.x = xc.on; j.mode.off = src.prompt_len != nullptr;
+    j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
+    const void *d_pcm;
+    WM_TRY(stage_pcm(c, src, j.b0, Bg, mem, &d_pcm));
     // decode state first (prompt tokens [n_prompt][Bg], position 0): a pageable H2D copy may wait for the
     // stream to drain, so it is issued while the lane is still idle
     WM_TRY(wm_model_decode_begin(c, Bg));
@@ -495,23 +540,18 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
         for (int t = 0; t < n_prompt; ++t)
             for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = src.prompt[(size_t)(j.b0 + b) * src.prompt_stride + t];
     }
-    m->off_on = src.prompt_len != nullptr;
     WM_HIP(hipMemcpyAsync(m->dseq, j.pr.data(), j.pr.size() * 4, hipMemcpyHostToDevice, c->stream));
     WM_TRY(wm_model_set_pos(c, 0));
     // early-stop state of this group: done flags, live list, per-row budgets (kernel arguments of the decode graphs)
-    m->stop_on = stop.on;
-    m->stop_eot = stop.eot;
-    m->budget_on = stop.on && stop.budgets != nullptr;
     if (stop.on) {
-        if (m->budget_on) {
+        if (j.mode.budget) {
             j.bud.assign(stop.budgets + j.b0, stop.budgets + j.b0 + Bg);
             WM_HIP(hipMemcpyAsync(m->dbudget, j.bud.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
         }
-        WM_TRY(wm_stop_init(c, wm_model_stop_dev(m), Bg));
+        WM_TRY(wm_stop_init(c, wm_model_stop_dev(m, j.mode), Bg));
     }
     // extended decode: seed, 1/T, the sot position and the group's first call index live in device memory, so the
     // captured graphs replay for any of them
-    m->x_on = xc.on;
     if (xc.on) {
         j.xpar = xc.par;
         j.xpar.chunk0 = j.b0;
@@ -526,82 +566,46 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
     }
     WM_TRY(wm_model_reserve(c, Bg));
     WM_HIP(hipEventRecord(j.ev[0], c->stream));
-    // 1. log-mel front end (f32 fast path), output stays in HBM -- or the caller's mel windows, gathered by the encoder's
-    //    first step (with host memory only the windows are copied, into the front end's buffer)
-    const float *enc_mel = m->mel_f32;
-    const WmMelWin *enc_win = nullptr;
-    if (src.mel) {
-        const int C = D.n_mels;
-        j.win.resize(Bg);
-        for (int b = 0; b < Bg; ++b) {
-            const int r = j.b0 + b;
-            WmMelWin &w = j.win[b];
-            w.T = src.mel_len[r]; w.seek = src.seek[r]; w.n = src.n_frames[r]; w.pad = 0;
-            w.base = src.mel_base[r];
-            if (mem == WM_MEM_HOST) {
-                WM_HIP(hipMemcpy2DAsync(m->mel_f32 + (size_t)b * C * WM_N_FRAMES, WM_N_FRAMES * sizeof(float),
-                                        src.mel + w.base + w.seek, (size_t)w.T * sizeof(float), (size_t)w.n * sizeof(float),
-                                        C, hipMemcpyHostToDevice, c->stream));
-                w.base = (long long)b * C * WM_N_FRAMES; w.T = WM_N_FRAMES; w.seek = 0;
-            }
-        }
-        WM_HIP(hipMemcpyAsync(m->dmel_win, j.win.data(), (size_t)Bg * sizeof(WmMelWin), hipMemcpyHostToDevice, c->stream));
-        if (mem != WM_MEM_HOST) enc_mel = src.mel;
-        enc_win = m->dmel_win;
-    } else {
-        WM_TRY(wm_frontend_run(&c->fe, &c->prof, c->stream, d_pcm, pcm_dtype, Bg, D.n_mels, m->mel_f32, WM_F32));
-    }
+    // 1. log-mel front end, or the caller's mel windows
+    const float *enc_mel;
+    const WmMelWin *enc_win;
+    WM_TRY(stage_mel(c, src, j.b0, Bg, mem, d_pcm, j.win, &enc_mel, &enc_win));
     WM_HIP(hipEventRecord(j.ev[1], c->stream));
     // 2. encoder + cross-attention K/V
     WM_TRY(wm_model_encode_win(c, enc_mel, enc_win, Bg, nullptr));
     WM_TRY(wm_model_cross_kv(c, Bg));
     WM_HIP(hipEventRecord(j.ev[2], c->stream));
     // 3. embedding of the first prompt token (+ the initial timestamp-rule state)
-    WM_TRY(wm_model_embed_first(c, Bg));
-    if (m->ts_on) WM_TRY(wm_ts_init(c, wm_model_ts_dev(m), Bg));
+    WM_TRY(wm_model_embed_first(c, Bg, j.mode));
+    if (j.mode.ts) WM_TRY(wm_ts_init(c, wm_model_ts_dev(m), Bg));
     return WM_OK;
 }
 
 // One decoder position = 8 launches per layer + logits + arg-max/embed (which writes the next token, embeds the
 // next position and advances *dpos).  Nothing in it depends on host state, so it is captured ONCE into a
 // hipGraph per lane and replayed for every position -- and `burst` consecutive positions are captured as one more graph.
-int capture_positions(LaneJob &j, int n_prompt, int n_pos, hipGraph_t *g, hipGraphExec_t *ge) {
-    wm_ctx *c = j.c;
-    WmModel *m = c->model;
-    WM_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int crc = WM_OK;
-    for (int i = 0; i < n_pos && crc == WM_OK; ++i) {
-        crc = wm_model_decode_step(c, j.Bg, false, 0, m->dims.n_vocab - 1, m->mask_on ? n_prompt - 1 : -1, m->ts_on, m->x_on);
-        if (crc == WM_OK) crc = wm_model_close_step(c, j.Bg, n_prompt, true, nullptr, 0, m->ts_on, m->x_on);
-    }
-    hipError_t ce = hipStreamEndCapture(c->stream, g);
-    if (crc != WM_OK || ce != hipSuccess) {   // a half-captured graph is of no use: do not leave it behind
-        if (ce == hipSuccess && *g) (void)hipGraphDestroy(*g);
-        *g = nullptr;
-        if (crc != WM_OK) return crc;
-        WM_HIP(ce);
-    }
-    if (hipGraphInstantiate(ge, *g, nullptr, nullptr, 0) != hipSuccess) {
-        (void)hipGraphDestroy(*g);
-        *g = nullptr;
-        *ge = nullptr;
-        wm_set_error("hipGraphInstantiate failed for the %d-position decode graph", n_pos);
-        return WM_ERR_HIP;
-    }
-    return WM_OK;
+int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt) {
+    WM_TRY(wm_model_decode_step(j.c, j.Bg, false, 0, j.c->model->dims.n_vocab - 1, nullptr, mode, n_prompt));
+    return wm_model_close_step(j.c, j.Bg, n_prompt, true, nullptr, 0, mode);
 }
 
-// Select (creating it if needed) the graph set of the lane's current decode shape.  The graphs themselves are captured
+int capture_positions(LaneJob &j, const WmDecodeMode &mode, int n_prompt, int n_pos, WmGraph *out) {
+    char what[48];
+    snprintf(what, sizeof(what), "the %d-position decode graph", n_pos);
+    return capture_graph(j.c->stream, out, what, [&]() -> int {
+        for (int i = 0; i < n_pos; ++i) WM_TRY(lane_position(j, mode, n_prompt));
+        return WM_OK;
+    });
+}
+
+// Select (creating it if needed) the graph set of the group's decode shape and mode.  The graphs themselves are captured
 // on first use, per sharing mode, by lane_burst.
 int lane_graph(LaneJob &j, int n_prompt) {
-    wm_ctx *c = j.c;
-    WmModel *m = c->model;
-    const int mk = (m->mask_on ? 1 : 0) | (m->ts_on ? 2 : 0) | (m->x_on ? 4 : 0) | (m->off_on ? 8 : 0);
-    const int sk = m->stop_on ? (1 | (m->budget_on ? 2 : 0) | ((m->stop_eot + 2) << 2)) : 0;
+    WmModel *m = j.c->model;
     int cur = -1;
     for (size_t i = 0; i < m->graph_sets.size(); ++i) {
         const WmModel::GraphSet &g = m->graph_sets[i];
-        if (g.B == j.Bg && g.n_prompt == n_prompt && g.cap_b == m->cap_b && g.mask == mk && g.stop_key == sk) cur = (int)i;
+        if (g.B == j.Bg && g.n_prompt == n_prompt && g.cap_b == m->cap_b && g.mode == j.mode) cur = (int)i;
     }
     if (cur < 0) {
         if ((int)m->graph_sets.size() >= WmModel::kMaxGraphSets) {   // evict the least recently used shape
@@ -612,51 +616,44 @@ int lane_graph(LaneJob &j, int n_prompt) {
             m->graph_sets.erase(m->graph_sets.begin() + (long)old);
         }
         WmModel::GraphSet g;
-        g.B = j.Bg; g.n_prompt = n_prompt; g.cap_b = m->cap_b; g.mask = mk; g.stop_key = sk;
+        g.B = j.Bg; g.n_prompt = n_prompt; g.cap_b = m->cap_b; g.mode = j.mode;
         m->graph_sets.push_back(g);
         cur = (int)m->graph_sets.size() - 1;
     }
-    m->graph_cur = cur;
+    j.gset = cur;
     m->graph_sets[cur].stamp = ++m->graph_clock;
     return WM_OK;
 }
 
 // enqueue the next burst of positions of a lane (<= burst_len(), up to the end of the sequence).  `shared`: other decode
 // groups are in flight on the device right now -- this burst's cross-attention launches are the short-lived shape.
-int lane_burst(LaneJob &j, int n_prompt, int n_steps, bool use_graph, bool stop_on, bool shared) {
+int lane_burst(LaneJob &j, int n_prompt, int n_steps, bool use_graph, bool shared) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
     const int K = burst_len();
     const int k = n_steps - j.t < K ? n_steps - j.t : K;
-    const int mode = shared ? 1 : 0;
-    m->xattn_shared = shared;   // read by wm_model_decode_step (eager launches and captures alike)
-    WmModel::GraphSet *g = use_graph ? &m->graph_sets[m->graph_cur] : nullptr;
+    const int sh = shared ? 1 : 0;
+    WmDecodeMode mode = j.mode;   // what every step of this burst, launched or captured, is handed
+    mode.xattn_shared = shared;
+    WmModel::GraphSet *g = use_graph ? &m->graph_sets[j.gset] : nullptr;
     if (use_graph && k == K && K > 1) {
-        if (!g->ek[mode] || g->burst[mode] != K) {
-            if (g->ek[mode]) { (void)hipGraphExecDestroy(g->ek[mode]); g->ek[mode] = nullptr; }
-            if (g->gk[mode]) { (void)hipGraphDestroy(g->gk[mode]); g->gk[mode] = nullptr; }
-            const int rc = capture_positions(j, n_prompt, K, &g->gk[mode], &g->ek[mode]);
-            if (rc != WM_OK) { g->gk[mode] = nullptr; g->ek[mode] = nullptr; return rc; }
-            g->burst[mode] = K;
+        if (!g->gk[sh].e || g->burst[sh] != K) {
+            WM_TRY(capture_positions(j, mode, n_prompt, K, &g->gk[sh]));
+            g->burst[sh] = K;
         }
-        WM_HIP(hipGraphLaunch(g->ek[mode], c->stream));
+        WM_HIP(hipGraphLaunch(g->gk[sh].e, c->stream));
     } else {
-        if (use_graph && !g->e1[mode]) {
-            const int rc = capture_positions(j, n_prompt, 1, &g->g1[mode], &g->e1[mode]);
-            if (rc != WM_OK) { g->g1[mode] = nullptr; g->e1[mode] = nullptr; return rc; }
-        }
+        if (use_graph && !g->g1[sh].e) WM_TRY(capture_positions(j, mode, n_prompt, 1, &g->g1[sh]));
         for (int i = 0; i < k; ++i) {
             if (use_graph) {
-                WM_HIP(hipGraphLaunch(g->e1[mode], c->stream));
+                WM_HIP(hipGraphLaunch(g->g1[sh].e, c->stream));
             } else {
-                WM_TRY(wm_model_decode_step(c, j.Bg, false, 0, m->dims.n_vocab - 1, m->mask_on ? n_prompt - 1 : -1, m->ts_on,
-                                            m->x_on));
-                WM_TRY(wm_model_close_step(c, j.Bg, n_prompt, true, nullptr, 0, m->ts_on, m->x_on));
+                WM_TRY(lane_position(j, mode, n_prompt));
             }
         }
     }
     j.t += k;
-    if (stop_on) {  // the live-row count after this burst, where the host can read it without touching the stream
+    if (j.mode.stop) {  // the live-row count after this burst, where the host can read it without touching the stream
         const int slot = j.bursts % WM_NLIVE_RING;
         WM_HIP(hipMemcpyAsync(m->h_nlive + slot, m->dnlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         WM_HIP(hipEventRecord(j.burst_ev[slot], c->stream));
@@ -778,11 +775,7 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                "bad pcm dtype");
     WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
     if (src.mel)
-        for (int b = 0; b < B; ++b)
-            WM_REQUIRE(src.mel_base[b] >= 0 && src.mel_len[b] >= 1 && src.seek[b] >= 0 && src.n_frames[b] >= 1 &&
-                           src.n_frames[b] <= WM_N_FRAMES && (int64_t)src.seek[b] + src.n_frames[b] <= src.mel_len[b],
-                       WM_ERR_INVALID, "row %d: window (base %lld, T %d, seek %d, n_frames %d) invalid", b,
-                       (long long)src.mel_base[b], src.mel_len[b], src.seek[b], src.n_frames[b]);
+        for (int b = 0; b < B; ++b) WM_TRY(check_window(src, b, ""));
     const wm_dims &D = m->dims;
     if (src.prompt_len) {   // ragged: n_prompt arrives as the row stride and becomes the call's longest prompt
         int longest = 0;
@@ -834,9 +827,8 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
         xc.par.sot_pos = no_speech_out ? sot_index : -1;
         xc.par.ns_tok = ns_tok;
     }
-    static const bool no_graph = getenv("WM_NO_GRAPH") != nullptr;
     const bool no_stop = g_wm_tuning.no_early_stop != 0;   // probes only: decode every position, truncate on the host
-    const bool use_graph = !no_graph && !ctx->prof.on;
+    const bool use_graph = !graphs_off() && !ctx->prof.on;
     StopCfg stop;
     stop.on = !no_stop && (eot >= 0 || !budgets.empty());
     stop.eot = eot;
@@ -939,7 +931,7 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                     for (int o = 0; o < n_lanes; ++o) busy += jobs[o].state == LaneJob::DECODING && jobs[o].t < n_steps(jobs[o]) && !jobs[o].stopped;
                     // (sub-chip lanes own their CUs: the other lanes of THIS call do not make the chip "shared")
                     const bool shared = (busy > 1 && !parts) || g_wm_active_decodes[ctx->device & 63].load(std::memory_order_relaxed) > 1;
-                    WM_TRY(lane_burst(j, j.P, n_steps(j), use_graph, stop.on, shared));
+                    WM_TRY(lane_burst(j, j.P, n_steps(j), use_graph, shared));
                     progress = true;
                     continue;
                 }
@@ -1014,13 +1006,7 @@ extern "C" int wm_set_alignment_heads(wm_ctx *ctx, const int32_t *layers, const 
         WM_REQUIRE(v[i] != v[i - 1], WM_ERR_INVALID, "set_alignment_heads: (%d, %d) listed twice", v[i].first, v[i].second);
     std::vector<int32_t> hl, hh;
     for (auto &p : v) { hl.push_back(p.first); hh.push_back(p.second); }
-    auto set = [&](wm_ctx *c) { c->model->align_l = hl; c->model->align_h = hh; };
-    set(ctx);
-    for (wm_ctx *lane : ctx->lanes) set(lane);
-    for (auto &pl : ctx->part_lanes)
-        for (wm_ctx *lane : pl) set(lane);
-    for (auto &kv : ctx->solo_lanes) set(kv.second);
-    return WM_OK;
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { c->model->align_l = hl; c->model->align_h = hh; return (int)WM_OK; });
 } WM_API_CATCH
 
 namespace {
@@ -1028,16 +1014,11 @@ constexpr size_t kAlignCaptureBudget = (size_t)2 << 30;   // bytes of captured q
 
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// where a call's encoder input comes from -- PCM chunks (wm_align) or mel windows (wm_align_mel, mel non-null) -- and its
-// start sequences: row b's is sot_seq + b * sot_stride (0: one for all)
-struct AlignCall {
-    const void *pcm = nullptr;
-    wm_dtype pcm_dtype = WM_F32;
-    const float *mel = nullptr;
-    const int64_t *mel_base = nullptr;
-    const int32_t *mel_len = nullptr, *seek = nullptr;
+// an align call's encoder input -- PCM chunks (wm_align; n_frames nullable: whole chunks) or mel windows (wm_align_mel) --
+// and its start sequences: row b's is sot_seq + b * sot_stride (0: one for all)
+struct AlignCall : WmAudioSrc {
     wm_mem mem;
-    const int32_t *sot_seq, *text_tokens, *n_text, *n_frames;
+    const int32_t *sot_seq, *text_tokens, *n_text;
     int sot_stride = 0;
     int n_sot, max_text;
     int32_t no_timestamps, eot;
@@ -1067,15 +1048,8 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     const size_t o_start = o_prob + align_up((size_t)Bg * std::max(c.max_text, 1) * 4);
     const size_t o_int = o_start + align_up((size_t)Bg * n_ld * 4), n_int = (size_t)4 * Bg + 2 * J;
     const size_t bytes = o_int + align_up(n_int * 4);
-    if (m->align_ws_bytes < bytes) {
-        WM_HIP(hipStreamSynchronize(ctx->stream));
-        if (m->align_ws) WM_HIP(hipFree(m->align_ws));
-        m->align_ws = nullptr;
-        m->align_ws_bytes = 0;
-        WM_HIP(hipMalloc(&m->align_ws, bytes));
-        m->align_ws_bytes = bytes;
-    }
-    char *ws = (char *)m->align_ws;
+    WM_TRY(m->align_ws.reserve(ctx->stream, bytes));
+    char *ws = (char *)m->align_ws.p;
     float *q = (float *)(ws + o_q), *x = (float *)(ws + o_x), *prob = (float *)(ws + o_prob);
     int *start = (int *)(ws + o_start), *ints = (int *)(ws + o_int);
     // host staging (fenced by the synchronisation at the end of the group): n_text, n_frames, DTW rows, DTW frames, heads
@@ -1107,43 +1081,13 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     WM_HIP(hipMemsetAsync(x, 0, (size_t)Bg * n_ld * 1500 * 4, ctx->stream));
     WM_TRY(wm_model_set_pos(ctx, 0));
     WM_TRY(wm_model_reserve(ctx, Bg));
-    const size_t pbytes = (size_t)Bg * WM_N_SAMPLES * pcm_elem(c.pcm_dtype);
-    const void *d_pcm = (const char *)c.pcm + (size_t)b0 * WM_N_SAMPLES * pcm_elem(c.pcm_dtype);
-    if (c.mem == WM_MEM_HOST && !c.mel) {
-        if (m->pcm_stage_bytes < pbytes) {
-            WM_HIP(hipStreamSynchronize(ctx->stream));
-            if (m->pcm_stage) WM_HIP(hipFree(m->pcm_stage));
-            m->pcm_stage = nullptr;
-            m->pcm_stage_bytes = 0;
-            WM_HIP(hipMalloc(&m->pcm_stage, pbytes));
-            m->pcm_stage_bytes = pbytes;
-        }
-        WM_HIP(hipMemcpyAsync(m->pcm_stage, d_pcm, pbytes, hipMemcpyHostToDevice, ctx->stream));
-        d_pcm = m->pcm_stage;
-    }
+    const void *d_pcm;
+    WM_TRY(stage_pcm(ctx, c, b0, Bg, c.mem, &d_pcm));
     WM_HIP(hipEventRecord(ev[0], ctx->stream));
-    if (c.mel) {   // the window table of the wm_transcribe_mel prefill: gathered by the encoder's first step
-        const float *enc_mel = c.mel;
-        win.resize(Bg);
-        for (int b = 0; b < Bg; ++b) {
-            const int r = b0 + b;
-            WmMelWin &w = win[b];
-            w.T = c.mel_len[r]; w.seek = c.seek[r]; w.n = c.n_frames[r]; w.pad = 0;
-            w.base = c.mel_base[r];
-            if (c.mem == WM_MEM_HOST) {   // only the windows are copied, into the front end's buffer
-                WM_HIP(hipMemcpy2DAsync(m->mel_f32 + (size_t)b * D.n_mels * WM_N_FRAMES, WM_N_FRAMES * sizeof(float),
-                                        c.mel + w.base + w.seek, (size_t)w.T * sizeof(float), (size_t)w.n * sizeof(float),
-                                        D.n_mels, hipMemcpyHostToDevice, ctx->stream));
-                w.base = (long long)b * D.n_mels * WM_N_FRAMES; w.T = WM_N_FRAMES; w.seek = 0;
-            }
-        }
-        if (c.mem == WM_MEM_HOST) enc_mel = m->mel_f32;
-        WM_HIP(hipMemcpyAsync(m->dmel_win, win.data(), (size_t)Bg * sizeof(WmMelWin), hipMemcpyHostToDevice, ctx->stream));
-        WM_TRY(wm_model_encode_win(ctx, enc_mel, m->dmel_win, Bg, nullptr));
-    } else {
-        WM_TRY(wm_frontend_run(&ctx->fe, &ctx->prof, ctx->stream, d_pcm, c.pcm_dtype, Bg, D.n_mels, m->mel_f32, WM_F32));
-        WM_TRY(wm_model_encode_dev(ctx, m->mel_f32, Bg, nullptr));
-    }
+    const float *enc_mel;
+    const WmMelWin *enc_win;
+    WM_TRY(stage_mel(ctx, c, b0, Bg, c.mem, d_pcm, win, &enc_mel, &enc_win));
+    WM_TRY(wm_model_encode_win(ctx, enc_mel, enc_win, Bg, nullptr));
     WM_TRY(wm_model_cross_kv(ctx, Bg));
     WM_HIP(hipEventRecord(ev[1], ctx->stream));
     // teacher-forced pass: every position is prompt, the alignment layers leave their queries in the capture buffer
@@ -1157,7 +1101,7 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     WM_TRY(wm_model_embed_first(ctx, Bg));
     for (int p = 0; p < T; ++p) {
         const bool want = p >= S && p < S + nmax;   // rows whose logits give a token probability
-        WM_TRY(wm_model_decode_step(ctx, Bg, want, 0, V - 1, -1, false, false, &cap));
+        WM_TRY(wm_model_decode_step(ctx, Bg, want, 0, V - 1, &cap));
         if (want) WM_TRY(wm_align_token_prob(ctx, m->dlogits, m->vpad, m->dseq, m->dpos, Bg, S, c.eot, ints, prob, std::max(c.max_text, 1)));
         if (p + 1 < T) WM_TRY(wm_model_close_step(ctx, Bg, T, true, nullptr, 0));
     }
@@ -1217,11 +1161,7 @@ static int align_impl(wm_ctx *ctx, AlignCall &c, int B, int32_t no_timestamps, i
         if (n_frames)
             WM_REQUIRE(n_frames[b] >= 2 && n_frames[b] <= WM_N_FRAMES, WM_ERR_INVALID, "align: n_frames[%d] = %d outside [2, %d]",
                        b, n_frames[b], WM_N_FRAMES);
-        if (c.mel)
-            WM_REQUIRE(c.mel_base[b] >= 0 && c.mel_len[b] >= 1 && c.seek[b] >= 0 &&
-                           (int64_t)c.seek[b] + n_frames[b] <= c.mel_len[b],
-                       WM_ERR_INVALID, "align: row %d: window (base %lld, T %d, seek %d, n_frames %d) invalid", b,
-                       (long long)c.mel_base[b], c.mel_len[b], c.seek[b], n_frames[b]);
+        if (c.mel) WM_TRY(check_window(c, b, "align: "));
     }
     if (m->align_l.empty()) {   // openai-whisper's default: every head of the last half of the decoder layers
         for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)

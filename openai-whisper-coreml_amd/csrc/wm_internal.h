@@ -176,6 +176,17 @@ struct wm_ctx {
     bool no_cu_masks = false;              // a CU-masked stream could not be created on this device: the policy stays unmasked
     std::map<int, wm_ctx *> solo_lanes;    // probes (debug knob lane_solo_cus): a clone confined to the first n CUs of every XCD
 };
+// fn(c) -> status for the context itself (with_self) and every lane it owns; the first status that is not WM_OK ends the
+// walk and is returned
+template <typename F>
+int wm_for_each_lane(wm_ctx *ctx, bool with_self, F &&fn) {
+    if (with_self) WM_TRY(fn(ctx));
+    for (wm_ctx *lane : ctx->lanes) WM_TRY(fn(lane));
+    for (auto &v : ctx->part_lanes)
+        for (wm_ctx *lane : v) WM_TRY(fn(lane));
+    for (auto &kv : ctx->solo_lanes) WM_TRY(fn(kv.second));
+    return WM_OK;
+}
 // weight-sharing clone of `parent` whose stream is confined to the CUs [cu_lo, cu_hi) of every XCD (api.cpp)
 int wm_clone_cus(wm_ctx *parent, int cu_lo, int cu_hi, wm_ctx **out);
 // CU mask (256 bits) of the CUs [cu_lo, cu_hi) of every XCD; returns the CU count
@@ -224,6 +235,6 @@ struct WmTuning {
 extern WmTuning g_wm_tuning;   // api.cpp
 
 // wm_transcribe_greedy calls in flight per device (any context, any host thread): a decode group that shares the chip
-// with others launches its cross-attention as short-lived workgroups (model.h WmModel::xattn_shared).
+// with others launches its cross-attention as short-lived workgroups (model.h WmDecodeMode::xattn_shared).
 #include <atomic>
 extern std::atomic<int> g_wm_active_decodes[64];   // api.cpp
