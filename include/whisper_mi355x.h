@@ -262,6 +262,43 @@ WM_API int wm_transcribe_mel_ragged(wm_ctx *ctx, const float *mel, const int64_t
                                     int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out,
                                     int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out, wm_mem mem);
 
+/* openai-whisper's best_of: wm_transcribe_mel_ragged (prompt_len given) or wm_transcribe_mel (prompt_len NULL: every prompt is
+ * prompt_stride long and opts->sot_index applies) with best_of independently sampled CANDIDATES per window.  The candidates
+ * of a window share its encoder pass, its cross-attention K/V cache and every read of that cache.
+ *   best_of        : 1 .. WM_MAX_BEST_OF candidates per window;
+ *   candidate noise: candidate s of row b is sampled with Philox counter {n >> 2, generated index, id_b, s} -- the fourth word
+ *                    is 0 in every other call -- id_b = sample_ids[b], or b when sample_ids is NULL;
+ *   length_penalty : NaN (openai-whisper's None) or in [0, 1]: how best_out ranks (wm_rank_candidates);
+ *   tokens_out     : i32 [B][best_of][max_new];  lens_out : i32 [B][best_of];
+ *   token_logprobs_out : f32 [B][best_of][max_new], nullable (best_out is computed either way);
+ *   no_speech_prob_out : f32 [B], nullable: candidate 0's (the raw logits at <|startoftranscript|> do not see the noise);
+ *   best_out       : i32 [B], nullable: wm_rank_candidates over each row's candidates.
+ * Bit for bit: best_of = 1 is wm_transcribe_mel_ragged / wm_transcribe_mel; candidate 0 of any call is that result; candidate
+ * (b, s) depends on row b's window, prompt, id, s, the seed and the temperature only -- not on best_of, the other rows, the
+ * grouping or the lanes.  Temperature 0 is allowed (all candidates equal, best_out 0).  Suppress lists and timestamp rules
+ * apply per candidate; a token budget (wm_set_token_budgets, B entries) applies to every candidate of its row; early stop is
+ * per candidate, and a window whose candidates have all stopped has its cross-K/V cache not read again.
+ * Invalid: best_of outside its range, length_penalty neither NaN nor in [0, 1], and
+ * everything the ragged / uniform call rejects. */
+#define WM_MAX_BEST_OF 8
+WM_API int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                     const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                     int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                     int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                     int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                     float *no_speech_prob_out, int32_t *best_out, wm_mem mem);
+
+/* openai-whisper's MaximumLikelihoodRanker on the host (no GPU, no context): per row the candidate with the highest score.
+ *   tokens [B][n_cand][max_new], lens [B][n_cand], token_logprobs [B][n_cand][max_new] as wm_transcribe_mel_best_of returns them;
+ *   sum     = f64 sum of token_logprobs[0 .. lens) in index order (the stopping eot included);
+ *   n_text  = tokens before the first eot;  penalty = n_text when length_penalty is NaN (1 when n_text is 0: the library's
+ *             own rule where openai-whisper divides by zero), else ((5 + n_text) / 6) ** length_penalty;
+ *   score   = sum / penalty; the FIRST maximal score wins; -inf is a legal score, all -inf: candidate 0;
+ *   best_out [B];  score_out f64 [B][n_cand], nullable.
+ * Invalid: null pointers, B or n_cand or max_new < 1, a length outside [0, max_new], length_penalty neither NaN nor in [0, 1]. */
+WM_API int wm_rank_candidates(const int32_t *tokens, const int32_t *lens, const float *token_logprobs, int B, int n_cand,
+                              int max_new, int32_t eot, float length_penalty, int32_t *best_out, double *score_out);
+
 /* ------------------------------------------------------------- word-level timestamps --- */
 /* openai-whisper's find_alignment (whisper/timing.py) on the GPU, for the text tokens a transcription produced (e.g. each
  * chunk's tokens from the temperature step of wm_transcribe that it kept).  Per chunk with text tokens t[0 .. n), all < eot:

@@ -99,6 +99,21 @@ WM_API int wmdbg_group_count(int B, int lanes, int explicit_lanes);
 WM_API int wmdbg_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, int32_t *table_out,
                              int32_t *off_out);
 
+/* The decode groups of a wm_transcribe_mel_best_of call of B windows x N candidates as a pure function (host only): group g
+ * holds windows [b0_out[g], b0_out[g] + cg_out[g]) = cg_out[g] * N decoder rows.  Returns the number of groups (room for B
+ * entries in both arrays), or -1 on bad arguments. */
+WM_API int wmdbg_cand_groups(int B, int N, int lanes, int explicit_lanes, int32_t *b0_out, int32_t *cg_out);
+/* The cross-attention launch of a candidate group exactly as the decode step makes it (wm_dec_attention_cand): C windows x N
+ * candidates, q f32 [C * N][H * 64] (row c * N + s = candidate s of window c), k / v f32 [C][H][T][64] (rounded to bf16), the
+ * first n_keys positions; live_rows: the compact ascending list of the n_live live rows (NULL: every row is live);
+ * out f32 [C * N][H * 64] -- rows that are not live are not written by the kernel. */
+WM_API int wmdbg_dec_attention_cand(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int N, int H, int T,
+                                    int n_keys, const int32_t *live_rows, int n_live, float *out);
+/* The same launch in the shape of a burst that shares the chip with other decode groups (one short-lived 8-wave workgroup per
+ * (window, head) pair, merge in LDS, whatever the pair count): same bits. */
+WM_API int wmdbg_dec_attention_cand_shared(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int N, int H,
+                                           int T, int n_keys, const int32_t *live_rows, int n_live, float *out);
+
 /* The Gumbel noise wm_transcribe's sampling adds at temperature > 0, computed by the DEVICE code (csrc/philox.h): g(n) of
  * ids n0 .. n0 + count - 1 for chunk `chunk` of a call and generated index gi, into host g[count]. */
 WM_API int wmdbg_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int n0, int count, float *g);

@@ -115,6 +115,9 @@ def load_library(path=None):
         "wm_logmel_long": [vp, vp, ip, vp, ip, ip, vp, ip],
         "wm_transcribe_mel": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
         "wm_transcribe_mel_ragged": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
+        "wm_transcribe_mel_best_of": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_float, ip, ctypes.c_int32, vp,
+                                      vp, vp, vp, vp, vp, ip],
+        "wm_rank_candidates": [vp, vp, vp, ip, ip, ip, ctypes.c_int32, ctypes.c_float, vp, vp],
         "wm_set_token_budgets": [vp, vp, ip],
         "wm_set_alignment_heads": [vp, vp, vp, ip],
         "wm_align": [vp, vp, ip, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, vp, ip, ctypes.c_float, vp, vp, ip],
@@ -210,6 +213,37 @@ class TranscribeResult:
         self.avg_logprob = self.sum_logprob / (self.n_text + 1)
 
 
+class BestOfResult:
+    """What Context.transcribe_mel_best_of returns.  tokens i32 [B][N][max_new], lens i32 [B][N], logprobs f32 [B][N][max_new],
+    no_speech_prob f32 [B] (candidate 0's; None without a no-speech token), best i32 [B] (wm_rank_candidates) and
+    selected: the TranscribeResult of candidate best[b] of every row, with the same indices as its attribute `candidate`."""
+
+    def __init__(self, tokens, lens, logprobs, no_speech_prob, best, eot):
+        self.tokens, self.lens, self.logprobs, self.no_speech_prob, self.best = tokens, lens, logprobs, no_speech_prob, best
+        rows = np.arange(tokens.shape[0])
+        self.selected = TranscribeResult(np.ascontiguousarray(tokens[rows, best]), np.ascontiguousarray(lens[rows, best]),
+                                         np.ascontiguousarray(logprobs[rows, best]), no_speech_prob, eot)
+        self.selected.candidate = best
+
+
+def rank_candidates(tokens, lens, logprobs, eot, length_penalty=None):
+    """wm_rank_candidates (openai-whisper's MaximumLikelihoodRanker; host only): tokens [B][N][max_new], lens [B][N],
+    logprobs [B][N][max_new]; length_penalty None is openai-whisper's None.  Returns (best i32 [B], scores f64 [B][N])."""
+    lib = load_library()
+    tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    logprobs = np.ascontiguousarray(logprobs, dtype=np.float32)
+    if tokens.ndim != 3 or lens.shape != tokens.shape[:2] or logprobs.shape != tokens.shape:
+        raise ValueError("rank_candidates: tokens / logprobs [B][N][max_new], lens [B][N]")
+    B, N, max_new = tokens.shape
+    best = np.empty(B, dtype=np.int32)
+    scores = np.empty((B, N), dtype=np.float64)
+    _check(lib, lib.wm_rank_candidates(_ptr(tokens), _ptr(lens), _ptr(logprobs), B, N, max_new, eot,
+                                       float("nan") if length_penalty is None else float(length_penalty), _ptr(best),
+                                       _ptr(scores)))
+    return best, scores
+
+
 def n_text_tokens(toks, eot):
     """generated tokens before the first eot"""
     toks = np.asarray(toks)
@@ -241,7 +275,8 @@ def fallback_seed(seed, k):
 
 def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                              compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
-                             vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None):
+                             vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None, best_of=None,
+                             length_penalty=None):
     """openai-whisper's decode_with_fallback, per chunk, over ctx.transcribe.
 
     Temperature step k decodes, as ONE batched call, the chunks that still need fallback (step 0: all of them) at
@@ -252,11 +287,22 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     openai-whisper's rule on the detokenized text; without one, transformers' token-byte rule.  The default
     compression_ratio_threshold "auto" is each rule's documented threshold: 2.4 with a Vocab, 1.35 without.
 
+    best_of (openai-whisper's best_of; None: one sample): a step with temperature > 0 decodes best_of candidates per chunk
+    in ONE wm_transcribe_mel_best_of call -- the chunks' Context.logmel windows at seek 0, the same seed and the same sample
+    ids (the index within the call) -- and keeps each chunk's best one under length_penalty (rank_candidates).  The
+    temperature-0 step is unchanged.
+
     Returns a dict of per-chunk arrays (tokens, lens, logprobs, sum_logprob, avg_logprob, no_speech_prob,
     compression_ratio, temperature, seed, needs_fallback) and `steps`: [(temperature, seed, chunk indices)] per call."""
     pcm = np.asarray(pcm)
 
     def decode(todo, t, sd):
+        if best_of is not None and t > 0:
+            n_mels = int(ctx.dims["n_mels"])
+            mel = ctx.logmel(pcm[todo], n_mels=n_mels)
+            return ctx.transcribe_mel(mel, np.arange(len(todo), dtype=np.int64) * (n_mels * N_FRAMES), N_FRAMES, 0, N_FRAMES,
+                                      prompt, max_new, eot=eot, temperature=t, seed=sd, no_speech_token=no_speech_token,
+                                      sot_index=sot_index, best_of=best_of, length_penalty=length_penalty)
         return ctx.transcribe(pcm[todo], prompt, max_new, eot=eot, temperature=t, seed=sd,
                               no_speech_token=no_speech_token, sot_index=sot_index)
     return fallback_decode(decode, pcm.shape[0], int(ctx.dims["n_vocab"]) if vocab_size is None else vocab_size, max_new,
@@ -444,7 +490,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
                     no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None, condition_on_previous_text=False,
                     prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
-                    prepend_punctuations=None, append_punctuations=None):
+                    prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings; hallucination_silence_threshold
     and clip_timestamps are not implemented.  condition_on_previous_text defaults to False here (openai-whisper: True);
     see 5.  word_timestamps: see 6.
@@ -476,6 +522,10 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        a window of fewer than 2 frames (no audio frame to align to), like a skipped window or one without a text token,
        gets `words` [] on its segments and the seek of word_timestamps=False.
        prepend_punctuations / append_punctuations: None = openai-whisper's defaults (PREPEND_ / APPEND_PUNCTUATIONS).
+    7. best_of (openai-whisper's best_of; None: one sample per window): a fallback step with temperature > 0 decodes best_of
+       candidates per window in ONE wm_transcribe_mel_best_of call -- same seeds, same sample ids -- and hands
+       fallback_decode each window's best candidate under length_penalty (rank_candidates; None = openai-whisper's None).
+       The temperature-0 step is unchanged.  Every window record then has `candidate`, the index its last step kept.
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
     no prompt).  Without conditioning a recording's list heads every one of its windows; with it, it seeds the history.
     Sets the context's timestamp rules (wm_set_timestamp_rules: timestamp_begin, eot, max initial timestamp 1.0 s);
@@ -565,17 +615,26 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 plist = [head + [int(sot), langs[r], int(task)] for r in live]
                 prompts = np.array(plist, dtype=np.int32)
 
+            cand = {}   # best_of: row of the round -> candidate kept by its last step
+
             def decode(todo, t, sd):
                 rows = [live[i] for i in todo]
+                # (best_of None, or the temperature-0 step: exactly the call without candidates)
+                extra = dict(best_of=best_of, length_penalty=length_penalty) if best_of is not None and t > 0 else {}
                 if ragged:
-                    return ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
-                                              [size[i] for i in todo], [plist[i] for i in todo], max_new, eot=eot,
-                                              temperature=t, seed=sd, no_speech_token=no_speech_token, sot_tail=3,
-                                              sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE)
-                return ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
-                                          [size[i] for i in todo], prompts[todo], max_new, eot=eot, temperature=t,
-                                          seed=sd, no_speech_token=no_speech_token, sot_index=sot_index,
-                                          sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE)
+                    r_ = ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
+                                            [size[i] for i in todo], [plist[i] for i in todo], max_new, eot=eot,
+                                            temperature=t, seed=sd, no_speech_token=no_speech_token, sot_tail=3,
+                                            sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE, **extra)
+                else:
+                    r_ = ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
+                                            [size[i] for i in todo], prompts[todo], max_new, eot=eot, temperature=t,
+                                            seed=sd, no_speech_token=no_speech_token, sot_index=sot_index,
+                                            sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE, **extra)
+                if best_of is not None:
+                    for k, i in enumerate(todo):
+                        cand[int(i)] = int(r_.candidate[k]) if extra else 0
+                return r_
             res = fallback_decode(decode, len(live), vocab_size, max_new, eot, temperatures, compression_ratio_threshold,
                                   logprob_threshold, no_speech_threshold, vocab, seed)
             kept = []   # word_timestamps: (row of the round, segments, next seek, single_timestamp_ending) of every kept window
@@ -591,6 +650,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 out[r]["windows"].append(dict(seek=seek[r], segment_size=size[i], temperatures=temps, skipped=skip,
                                               tokens=[int(t) for t in res["tokens"][i, :n_text]],
                                               prompt_len=len(plist[i]), prompt=[int(t) for t in plist[i]]))
+                if best_of is not None:
+                    out[r]["windows"][-1]["candidate"] = cand[i]
                 if skip:
                     seek[r] += size[i]
                     continue
@@ -936,23 +997,15 @@ class Context:
 
     def transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                                  compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
-                                 vocab=None, seed=0, no_speech_token=-1, sot_index=0):
+                                 vocab=None, seed=0, no_speech_token=-1, sot_index=0, best_of=None, length_penalty=None):
         """openai-whisper's temperature fallback (module function transcribe_with_fallback) on this context."""
         return transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures, compression_ratio_threshold,
-                                        logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index)
+                                        logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index,
+                                        best_of=best_of, length_penalty=length_penalty)
 
-    def transcribe_mel_raw(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, opts=None,
-                           sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                           sot_tail=None):
-        """wm_transcribe_mel: mel is a host f32 array (mem WM_MEM_HOST) or a device pointer (WM_MEM_DEVICE); mel_base i64,
-        mel_len / seek / n_frames i32 [B]; prompts [B][n_prompt]; sample_ids u32 [B] or None.  Returns (tokens, lens,
-        logprobs or None, no_speech_prob or None).
-        Prompts of different lengths -- a list of B lists, or prompts [B][stride] with prompt_len i32 [B] -- go to
-        wm_transcribe_mel_ragged with sot_tail (<|startoftranscript|> is the sot_tail-th token from the end of every
-        prompt; default 1, opts.sot_index is not read).  A list of lists of ONE length without prompt_len stays
-        wm_transcribe_mel; there a sot_tail, when given, replaces opts.sot_index by n_prompt - sot_tail."""
-        if budgets is not None:
-            self.set_token_budgets(budgets)
+    def _mel_call_args(self, mel, mel_base, mel_len, seek, n_frames, prompts, opts, sample_ids, mem, prompt_len, sot_tail):
+        """The arrays of a wm_transcribe_mel* call (the conventions of transcribe_mel_raw): (mel kept alive, its pointer,
+        mel_base, mel_len, seek, n_frames, B, prompts [B][stride], prompt_len or None, opts, sample_ids or None)."""
         base = np.ascontiguousarray(mel_base, dtype=np.int64)
         B = base.size
         mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (B,)))
@@ -979,13 +1032,29 @@ class Context:
             mp = _ptr(mel)
         else:
             mp = mel
+        if plen is not None and plen.shape != (B,):
+            raise ValueError("prompt_len: one length per row")
+        return mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids
+
+    def transcribe_mel_raw(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, opts=None,
+                           sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
+                           sot_tail=None):
+        """wm_transcribe_mel: mel is a host f32 array (mem WM_MEM_HOST) or a device pointer (WM_MEM_DEVICE); mel_base i64,
+        mel_len / seek / n_frames i32 [B]; prompts [B][n_prompt]; sample_ids u32 [B] or None.  Returns (tokens, lens,
+        logprobs or None, no_speech_prob or None).
+        Prompts of different lengths -- a list of B lists, or prompts [B][stride] with prompt_len i32 [B] -- go to
+        wm_transcribe_mel_ragged with sot_tail (<|startoftranscript|> is the sot_tail-th token from the end of every
+        prompt; default 1, opts.sot_index is not read).  A list of lists of ONE length without prompt_len stays
+        wm_transcribe_mel; there a sot_tail, when given, replaces opts.sot_index by n_prompt - sot_tail."""
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids = self._mel_call_args(mel, mel_base, mel_len, seek, n_frames, prompts,
+                                                                                  opts, sample_ids, mem, prompt_len, sot_tail)
         toks = np.empty((B, max_new), dtype=np.int32)
         lens = np.empty(B, dtype=np.int32)
         lp = np.empty((B, max_new), dtype=np.float32) if logprobs else None
         ns = np.empty(B, dtype=np.float32) if no_speech else None
         if plen is not None:
-            if plen.shape != (B,):
-                raise ValueError("prompt_len: one length per row")
             _check(self.lib, self.lib.wm_transcribe_mel_ragged(
                 self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr), pr.shape[1], _ptr(plen),
                 1 if sot_tail is None else int(sot_tail), _ptr(ids) if ids is not None else None, max_new, eot,
@@ -999,11 +1068,43 @@ class Context:
                                                     _ptr(ns) if ns is not None else None, mem))
         return toks, lens, lp, ns
 
+    def transcribe_mel_best_of(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1, temperature=0.0,
+                               seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None,
+                               prompt_len=None, sot_tail=None, length_penalty=None):
+        """wm_transcribe_mel_best_of: transcribe_mel's arguments (uniform or ragged prompts as in transcribe_mel_raw) with
+        best_of sampled candidates per row that share the row's encoder pass and cross-attention cache; length_penalty None
+        is openai-whisper's None.  Returns a BestOfResult."""
+        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids = self._mel_call_args(mel, mel_base, mel_len, seek, n_frames, prompts,
+                                                                                  opts, sample_ids, mem, prompt_len, sot_tail)
+        N = int(best_of)
+        shape = (B, max(N, 1), max_new)
+        toks = np.empty(shape, dtype=np.int32)
+        lens = np.empty(shape[:2], dtype=np.int32)
+        lp = np.empty(shape, dtype=np.float32)
+        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
+        best = np.empty(B, dtype=np.int32)
+        _check(self.lib, self.lib.wm_transcribe_mel_best_of(
+            self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr), pr.shape[1],
+            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail),
+            _ptr(ids) if ids is not None else None, N, float("nan") if length_penalty is None else float(length_penalty),
+            max_new, eot, ctypes.byref(opts), _ptr(toks), _ptr(lens), _ptr(lp), _ptr(ns) if ns is not None else None,
+            _ptr(best), mem))
+        return BestOfResult(toks, lens, lp, ns, best, eot)
+
     def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                        no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                       sot_tail=None):
+                       sot_tail=None, best_of=None, length_penalty=None):
         """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
-        Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw."""
+        Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw.
+        best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`)."""
+        if best_of is not None:
+            return self.transcribe_mel_best_of(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=eot,
+                                               temperature=temperature, seed=seed, no_speech_token=no_speech_token,
+                                               sot_index=sot_index, sample_ids=sample_ids, mem=mem, budgets=budgets,
+                                               prompt_len=prompt_len, sot_tail=sot_tail, length_penalty=length_penalty).selected
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         toks, lens, lp, ns = self.transcribe_mel_raw(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot, opts,
                                                      sample_ids, logprobs=True, no_speech=no_speech_token >= 0, mem=mem,

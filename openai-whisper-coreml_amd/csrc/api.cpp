@@ -2,11 +2,13 @@
 // context life cycle, error reporting, the front-end entry points (boundary #1), device
 // memory helpers and the HIP-event profiler.  The model entry points (boundary #2) are in
 // model_api.cpp.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -314,6 +316,39 @@ static size_t dtype_size(wm_dtype t) {
     }
     return 0;
 }
+
+// openai-whisper's MaximumLikelihoodRanker (whisper/decoding.py): host only, no context, no GPU
+extern "C" int wm_rank_candidates(const int32_t *tokens, const int32_t *lens, const float *token_logprobs, int B, int n_cand,
+                                  int max_new, int32_t eot, float length_penalty, int32_t *best_out, double *score_out) try {
+    WM_REQUIRE(tokens && lens && token_logprobs && best_out, WM_ERR_INVALID, "rank_candidates: null pointer");
+    WM_REQUIRE(B >= 1 && n_cand >= 1 && max_new >= 1, WM_ERR_INVALID, "rank_candidates: B, n_cand and max_new must be >= 1");
+    WM_REQUIRE(std::isnan(length_penalty) || (length_penalty >= 0.f && length_penalty <= 1.f), WM_ERR_INVALID,
+               "rank_candidates: length_penalty must be NaN (none) or in [0, 1]");
+    for (size_t i = 0; i < (size_t)B * n_cand; ++i)
+        WM_REQUIRE(lens[i] >= 0 && lens[i] <= max_new, WM_ERR_INVALID, "rank_candidates: length %d of candidate %zu outside [0, %d]",
+                   lens[i], i, max_new);
+    for (int b = 0; b < B; ++b) {
+        int best = 0;
+        double best_score = -INFINITY;
+        for (int s = 0; s < n_cand; ++s) {
+            const size_t r = (size_t)b * n_cand + s;
+            const int32_t *t = tokens + r * max_new;
+            const float *lp = token_logprobs + r * max_new;
+            double sum = 0.0;
+            for (int i = 0; i < lens[r]; ++i) sum += (double)lp[i];
+            int n_text = 0;
+            while (n_text < lens[r] && t[n_text] != eot) ++n_text;
+            double penalty;
+            if (std::isnan(length_penalty)) penalty = n_text > 0 ? (double)n_text : 1.0;
+            else penalty = pow((5.0 + (double)n_text) / 6.0, (double)length_penalty);
+            const double score = sum / penalty;
+            if (score_out) score_out[r] = score;
+            if (score > best_score) { best_score = score; best = s; }   // the first maximal score; all -inf: candidate 0
+        }
+        best_out[b] = best;
+    }
+    return WM_OK;
+} WM_API_CATCH
 
 extern "C" int wm_logmel(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int n_chunks,
                          int n_mels, void *out, wm_dtype out_dtype, wm_mem mem) try {

@@ -37,6 +37,13 @@ extern "C" int wmdbg_set_tuning(const char *key, int value) {
 }
 
 extern "C" int wmdbg_group_count(int B, int lanes, int explicit_lanes) { return wm_group_count(B, lanes, explicit_lanes != 0, 0); }
+extern "C" int wmdbg_cand_groups(int B, int N, int lanes, int explicit_lanes, int32_t *b0_out, int32_t *cg_out) {
+    if (B < 1 || N < 1 || N > WM_MAX_BEST_OF || !b0_out || !cg_out) return -1;
+    std::vector<int> b0, cg;
+    const int G = wm_cand_groups(B, N, lanes, explicit_lanes != 0, b0, cg);
+    for (int g = 0; g < G; ++g) { b0_out[g] = b0[g]; cg_out[g] = cg[g]; }
+    return G;
+}
 extern "C" int wmdbg_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg,
                                  int32_t *table_out, int32_t *off_out) {
     std::vector<int32_t> table, off;
@@ -353,6 +360,66 @@ extern "C" int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, 
     (void)hipFree(datt);
     (void)hipFree(dq); (void)hipFree(dk); (void)hipFree(dv); (void)hipFree(dp);
     return rc;
+}
+
+// The cross-attention launch of a candidate group (wm_transcribe_mel_best_of), as wm_model_decode_step makes it; short_lived:
+// the shape of a burst that shares the chip (WmDecodeMode::xattn_shared)
+static int dec_attention_cand(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int N, int H, int T, int n_keys,
+                              const int32_t *live_rows, int n_live, float *out, bool short_lived) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(q && k && v && out, WM_ERR_INVALID, "dec_attention_cand: null pointer");
+    WM_REQUIRE(N >= 1 && N <= WM_MAX_BEST_OF && C >= 1 && C * N <= WM_DEC_MAXB && H >= 1 && H <= 255 && T >= 1 && n_keys >= 1 &&
+                   n_keys <= T,
+               WM_ERR_INVALID, "dec_attention_cand: bad geometry");
+    const int B = C * N;
+    std::vector<int32_t> live((size_t)WM_DEC_MAXB + 4, 0);
+    if (live_rows) {
+        WM_REQUIRE(n_live >= 0 && n_live <= B, WM_ERR_INVALID, "dec_attention_cand: n_live %d outside [0, %d]", n_live, B);
+        for (int i = 0; i < n_live; ++i) {
+            WM_REQUIRE(live_rows[i] >= 0 && live_rows[i] < B && (i == 0 || live_rows[i] > live_rows[i - 1]), WM_ERR_INVALID,
+                       "dec_attention_cand: the live list must be ascending rows of the group");
+            live[i] = live_rows[i];
+        }
+        live[WM_DEC_MAXB] = n_live;
+    }
+    std::vector<bf16_t> k16, v16;
+    to_bf16(k, k16, (size_t)C * H * T * 64);
+    to_bf16(v, v16, (size_t)C * H * T * 64);
+    void *dq, *dk, *dv, *dp, *dl, *datt;
+    hipStream_t s = ctx->stream;
+    const size_t att_b = ((size_t)B + 15) / 16 * 16 * H * 64 * 2;
+    WM_TRY(up(&dq, q, (size_t)B * H * 64 * 4, s));
+    WM_TRY(up(&dk, k16.data(), k16.size() * 2, s));
+    WM_TRY(up(&dv, v16.data(), v16.size() * 2, s));
+    WM_TRY(up(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
+    WM_TRY(up(&dl, live.data(), live.size() * 4, s));
+    WM_TRY(up(&datt, nullptr, att_b, s));
+    WM_HIP(hipMemsetAsync(dp, 0, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
+    WM_HIP(hipMemsetAsync(datt, 0, att_b, s));
+    const int *lr = live_rows ? (const int *)dl : nullptr;
+    int rc = wm_dec_attention_cand(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, C, N, H, T, n_keys, (float *)dp,
+                                   (bf16_t *)datt, nullptr, 0, 0, lr, lr ? lr + WM_DEC_MAXB : nullptr, short_lived);
+    if (rc == WM_OK) {
+        const size_t Bpad = ((size_t)B + 15) / 16 * 16, dd = (size_t)H * 64;
+        std::vector<bf16_t> o16(Bpad * dd), lin((size_t)B * dd);
+        WM_HIP(hipMemcpyAsync(o16.data(), datt, o16.size() * 2, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+        for (size_t b = 0; b < (size_t)B; ++b)   // head outputs are stored in the out-projection's tiled A-operand order
+            for (size_t kk = 0; kk < dd; ++kk) lin[b * dd + kk] = o16[wm_tiled_offset(b, kk, dd)];
+        from_bf16(lin, out);
+    }
+    void *fr[] = {dq, dk, dv, dp, dl, datt};
+    for (void *p : fr) (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int wmdbg_dec_attention_cand(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int N, int H, int T,
+                                        int n_keys, const int32_t *live_rows, int n_live, float *out) {
+    return dec_attention_cand(ctx, q, k, v, C, N, H, T, n_keys, live_rows, n_live, out, false);
+}
+extern "C" int wmdbg_dec_attention_cand_shared(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int N, int H,
+                                               int T, int n_keys, const int32_t *live_rows, int n_live, float *out) {
+    return dec_attention_cand(ctx, q, k, v, C, N, H, T, n_keys, live_rows, n_live, out, true);
 }
 
 // The production self-attention launch of a ragged decode group: position `pos`, sequence b's keys [min(off[b], pos), pos].

@@ -270,7 +270,7 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             wm_philox4 c;
             const int row = b0 + kq * 4 + j;   // (rows past the group's: their draws are never used)
             c.v[0] = (unsigned)n >> 2; c.v[1] = (unsigned)gi; c.v[2] = xp.ids_on ? p.x.ids[row] : (unsigned)(xp.chunk0 + row);
-            c.v[3] = 0u;
+            c.v[3] = xp.n_cand > 1 ? p.x.ids[WM_XIDS_CAND + row] : 0u;   // the candidate word (best-of-N; 0 in every other call)
             const wm_philox4 w = wm_philox4x32_10(c, xp.key0, xp.key1);
             quad_words<0>(w, j, draw[0]);
             quad_words<1>(w, j, draw[1]);
@@ -1160,6 +1160,168 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
         __syncthreads();
         if (tid < 64)  // head outputs feed the out-projection GEMV: stored in its fragment-tiled A-operand order
             att[wm_tiled_offset((size_t)b, (size_t)(h * 64 + tid), (size_t)d)] = f2bf(attn_merge<NS>(wm_, wl_, &wo_[0][0], 64, tid));
+    }
+}
+
+// ------------------------------------------------------------------ cross-attention of CANDIDATE groups (best-of-N)
+// A decode group of wm_transcribe_mel_best_of holds C windows x N candidates: row c * N + s is candidate s of window c, and
+// the N rows of a window attend to ONE cross-K/V cache [C][H][T][64].  A stream of pair (window c, head h) requests every
+// block of c's K/V once and runs attn_block on it for each LIVE candidate of c, each with its own (qe, m_run, l_run, oa):
+// the stream geometry (NS = 8, U = 4, the block order), attn_stream_reduce and the merge (in LDS, or through `part` and
+// dec_attn_combine_kernel) are those of dec_xrows_attn_kernel, so row c * N + s gets the bits the single-query kernel gives
+// it over a copy of c's cache -- whatever N, the other rows and the launch shape.
+// LIVE ROWS come from the compact ascending list the arg-max kernel maintains (rows of a window are adjacent in it).  Every
+// wave reads the whole list with two vector loads per lane (<= 128 entries) and derives, by ballots alone, the number of live
+// windows, the j-th live window (the pairs walked are (live window, head), dealt like dec_xrows_attn_kernel deals its pairs)
+// and the N-bit mask of its live candidates: no LDS, no atomics and no scalar load beyond the live count in front of the
+// first K/V load.  A window whose candidates have all finished is no pair any more: its cache is not read again.
+// N is a template argument: the candidates' state lives in registers and the candidate loop is unrolled around wave-uniform
+// branches (measured by the compiler: ~26 VGPRs per candidate, 114 / 162 / 188 / 214 / 240 for N = 1 .. 5).
+// Shapes (wm_dec_attention_cand): one 8-wave workgroup per pair, <= one per CU, persistent (flat_wpw == 0, merge in LDS);
+// or, below 256 pairs, the FLAT deal of the (pair, stream) units over ~256 workgroups (partials to `part`).
+struct CandLive {
+    int r_lo, r_hi;                      // this lane's list entries (lane, 64 + lane): row ids, -1 past the live count
+    unsigned long long head_lo, head_hi; // entries that open a window
+};
+template <int N>
+__device__ __forceinline__ void cand_window(const CandLive &L, int wj, int lane, int &c, unsigned &lm) {
+    const int rank_lo = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(L.head_lo >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)L.head_lo, 0u));
+    const int rank_hi = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(L.head_hi >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)L.head_hi, 0u)) +
+                        __popcll(L.head_lo);
+    const unsigned long long sel_lo = __ballot(((L.head_lo >> lane) & 1ull) && rank_lo == wj);
+    const unsigned long long sel_hi = __ballot(((L.head_hi >> lane) & 1ull) && rank_hi == wj);
+    int row;
+    if (sel_lo) row = __builtin_amdgcn_readlane(L.r_lo, __builtin_ctzll(sel_lo));
+    else row = __builtin_amdgcn_readlane(L.r_hi, sel_hi ? __builtin_ctzll(sel_hi) : 0);
+    c = row / N;
+    lm = 0u;
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        const int r = c * N + s;
+        if ((__ballot(L.r_lo == r) | __ballot(L.r_hi == r)) != 0ull) lm |= 1u << s;
+    }
+}
+
+template <int N, bool NT>
+__global__ __launch_bounds__(512) void dec_xcand_attn_kernel(
+    const float *__restrict__ q, const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
+    const int *__restrict__ live_rows /* [WM_DEC_MAXB] rows | [1] count, or null */, bf16_t *__restrict__ att,
+    float *__restrict__ part, unsigned packA /* H | flat_wpw << 16 */, unsigned packB /* T_stride | n_keys << 16 */,
+    unsigned packC /* C | n_wg << 16 */, const char *pf_ptr, long pf_tile_bytes) {
+    // (the 15 dwords up to packC are everything the compute path reads: all of them arrive preloaded in SGPRs, and the only
+    // scalar load in front of the first K/V load is the live count; pf_* are read by the warm-up workgroups alone)
+    constexpr int NS = 8, U = 4;
+    static_assert(N >= 1 && N <= 8, "1 .. 8 candidates per window");
+    // Candidates held in registers at a time.  Five fit the 256 VGPRs two waves per SIMD leave a wave (240, no scratch);
+    // six spill.  N = 6 .. 8 walk the window in TWO passes of (N + 1) / 2 candidates and request every block once per pass.
+    constexpr int NP = N <= 5 ? N : (N + 1) / 2;
+    const int H = (int)(packA & 0xffu), flat_wpw = (int)(packA >> 16);
+    const int T_stride = (int)(packB & 0xffffu), n_keys = (int)(packB >> 16);
+    const int C = (int)(packC & 0xffffu), n_wg = (int)(packC >> 16);
+    const int d = H * 64;
+    if ((int)blockIdx.x >= n_wg) {  // L2 warm-up workgroup for the next GEMV's weights
+        l2_warm_tile(pf_ptr, pf_tile_bytes, (int)blockIdx.x - n_wg, blockDim.x);
+        return;
+    }
+    __shared__ float wm_[N][NS], wl_[N][NS];
+    __shared__ float wo_[N][NS][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rg = lane >> 3, e8 = lane & 7;
+    const int last = n_keys - 1;
+    // ---- the live list -> windows (every wave for itself; null: every row of the C windows is live)
+    CandLive L;
+    {
+        int n_live = C * N, p_lo = lane - 1, p_hi = lane + 63;
+        L.r_lo = lane;
+        L.r_hi = lane + 64;
+        if (live_rows) {
+            n_live = live_rows[WM_DEC_MAXB];
+            L.r_lo = live_rows[lane];
+            L.r_hi = live_rows[lane + 64];
+            p_lo = live_rows[lane > 0 ? lane - 1 : 0];
+            p_hi = live_rows[lane + 63];
+        }
+        const bool v_lo = lane < n_live, v_hi = lane + 64 < n_live;
+        L.r_lo = v_lo ? L.r_lo : -1;
+        L.r_hi = v_hi ? L.r_hi : -1;
+        L.head_lo = __ballot(v_lo && (lane == 0 || p_lo / N != L.r_lo / N));
+        L.head_hi = __ballot(v_hi && p_hi / N != L.r_hi / N);
+    }
+    const int n_pairs = (__popcll(L.head_lo) + __popcll(L.head_hi)) * H;   // (live window, head)
+    int stream = wave;  // flat_wpw == 0: blockDim.x == NS * 64
+    int p0 = blockIdx.x, p_step = n_wg;
+    if (flat_wpw > 0) {   // FLAT launch: the n_pairs * NS (pair, stream) units dealt to the waves of the grid one to one
+        const int unit = (int)blockIdx.x * flat_wpw + wave;
+        if (unit >= n_pairs * NS) return;  // wave-uniform
+        p0 = unit / NS;
+        stream = unit % NS;
+        p_step = n_pairs;  // one pair per wave
+    }
+    for (int pi = p0; pi < n_pairs; pi += p_step) {
+        if (flat_wpw == 0 && pi != (int)blockIdx.x) __syncthreads();  // the previous pair's merge has been read
+        const int h = pi % H;
+        int c;
+        unsigned lm;   // bit s: candidate s of window c is live (wave-uniform)
+        cand_window<N>(L, pi / H, lane, c, lm);
+        const int ch = c * H + h;
+        const bf16_t *kb = kc + (long)ch * T_stride * 64 + e8 * 8;
+        const bf16_t *vb = vc + (long)ch * T_stride * 64 + e8 * 8;
+        // the candidates of the window, NP at a time in registers (N <= 5: one pass)
+        for (int s0 = 0; s0 < N; s0 += NP) {
+            const unsigned pm = (lm >> s0) & ((1u << NP) - 1u);   // live candidates of this pass (wave-uniform)
+            if (NP < N && pm == 0u) continue;
+            float qe[NP][8], m_run[NP], l_run[NP], oa[NP][8];
+#pragma unroll
+            for (int s = 0; s < NP; ++s) {
+                m_run[s] = -1e30f;
+                l_run[s] = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    qe[s][i] = 0.f;
+                    oa[s][i] = 0.f;
+                }
+                if ((pm >> s) & 1u) {
+                    const float *qp = q + (long)(c * N + s0 + s) * d + h * 64 + e8 * 8;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) qe[s][i] = qp[i] * 0.125f;  // hd^-0.5 (== hd^-0.25 on q and on k)
+                }
+            }
+            for (int r0 = 0; r0 < n_keys; r0 += NS * 8 * U) {  // workgroup-uniform trip count
+                u32x4 kv[U], vv[U];
+                attn_load_block<NS, U, NT>(kb, vb, r0, stream, rg, n_keys, last, kv, vv);
+#pragma unroll
+                for (int s = 0; s < NP; ++s)
+                    if ((pm >> s) & 1u) attn_block<NS, U, false>(qe[s], r0, stream, rg, n_keys, kv, vv, m_run[s], l_run[s], oa[s]);
+            }
+#pragma unroll
+            for (int s = 0; s < NP; ++s) {
+                if (!((pm >> s) & 1u)) continue;   // wave-uniform
+                attn_stream_reduce(l_run[s], oa[s]);
+                if (rg != 0) continue;
+                if (flat_wpw > 0) {  // the stream partials go to HBM, dec_attn_combine_kernel merges them
+                    float *po = part + ((long)((c * N + s0 + s) * H + h) * NS + stream) * 66;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) po[2 + e8 * 8 + i] = oa[s][i];
+                    if (e8 == 0) {
+                        po[0] = m_run[s];
+                        po[1] = l_run[s];
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) wo_[s0 + s][wave][e8 * 8 + i] = oa[s][i];
+                    if (e8 == 0) {
+                        wm_[s0 + s][wave] = m_run[s];
+                        wl_[s0 + s][wave] = l_run[s];
+                    }
+                }
+            }
+        }
+        if (flat_wpw > 0) continue;
+        __syncthreads();
+        // wave s merges candidate s: head outputs in the out-projection GEMV's fragment-tiled A-operand order
+        if (wave < N && ((lm >> wave) & 1u))
+            att[wm_tiled_offset((size_t)(c * N + wave), (size_t)(h * 64 + lane), (size_t)d)] =
+                f2bf(attn_merge<NS>(wm_[wave], wl_[wave], &wo_[wave][0][0], 64, lane));
     }
 }
 
@@ -2095,6 +2257,89 @@ int wm_dec_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t
     if (nsplit > 1) {
         WmProfScope ps(&ctx->prof, "dec_attn_combine", ctx->stream);
         dec_attn_combine_kernel<8><<<B * H, 64, 0, ctx->stream>>>(part, H, H * 64, att);
+        WM_HIP(hipGetLastError());
+    }
+    return WM_OK;
+}
+
+// Cross-attention of a candidate group (dec_xcand_attn_kernel): C windows x N candidates, q / att rows c * N + s, K/V
+// [C][H][T_stride][64].  part: [C * N][H][8][66] floats, needed below 256 (window, head) pairs (the flat deal).
+namespace {
+template <int N>
+int launch_xcand(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int H, int T_stride, int n_keys,
+                 float *part, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k, const int *live_rows, bool short_lived,
+                 bool *flat) {
+    const int pairs = C * H;
+    *flat = pairs < 256 && !short_lived;
+    const unsigned pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
+    long tile_bytes = 0;
+    int warm = 0;
+    if (pf_enabled(C * N) && pf_ptr && pf_rows >= 16) {
+        tile_bytes = 16L * pf_k * 2;
+        warm = pf_rows / 16;
+    }
+    if (*flat) {
+        // few pairs (8 windows x 20 heads = 160): every CU streams an equal share of the (pair, stream) units
+        const int units = pairs * 8;
+        int wpw = (units + 255) / 256;
+        wpw = wpw < 1 ? 1 : (wpw > 8 ? 8 : wpw);
+        const int g = (units + wpw - 1) / wpw;
+        if (g % 8 != 0) warm = 0;   // (the warm-up tiles follow the compute workgroups: keep their XCD placement)
+        const unsigned pA = (unsigned)H | ((unsigned)wpw << 16), pC = (unsigned)C | ((unsigned)g << 16);
+        dec_xcand_attn_kernel<N, WM_XATTN_NT><<<g + warm, wpw * 64, 0, ctx->stream>>>(
+            q, kc, vc, live_rows, att, part, pA, pB, pC, warm ? (const char *)pf_ptr : nullptr, warm ? tile_bytes : 0);
+        WM_HIP(hipGetLastError());
+        return WM_OK;   // (the caller launches the combine)
+    }
+    // one 8-wave workgroup per pair, at most one per CU (persistent, balanced), or one per pair when the chip is shared
+    const int cap_cus = g_wm_tuning.xattn_wgs > 0 && g_wm_tuning.xattn_wgs < ctx->n_cus ? g_wm_tuning.xattn_wgs : ctx->n_cus;
+    const int cap = short_lived ? (1 << 30) : cap_cus;
+    int n_wg = pairs;
+    if (n_wg > cap) {
+        const int rounds = (n_wg + cap - 1) / cap;
+        n_wg = (n_wg + rounds - 1) / rounds;
+    }
+    if (n_wg % 8 != 0) warm = 0;
+    WM_REQUIRE(n_wg < 65536, WM_ERR_INVALID, "dec_attention_cand: grid too large");
+    const unsigned pA = (unsigned)H, pC = (unsigned)C | ((unsigned)n_wg << 16);
+    dec_xcand_attn_kernel<N, WM_XATTN_NT><<<n_wg + warm, 512, 0, ctx->stream>>>(
+        q, kc, vc, live_rows, att, part, pA, pB, pC, warm ? (const char *)pf_ptr : nullptr, warm ? tile_bytes : 0);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+}  // namespace
+
+int wm_dec_attention_cand(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int N, int H, int T_stride,
+                          int n_keys, float *part, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k,
+                          const int *live_rows, const int *n_live, bool short_lived) {
+    WM_REQUIRE(N >= 1 && N <= WM_MAX_BEST_OF && C >= 1 && C * N <= WM_DEC_MAXB, WM_ERR_INVALID,
+               "dec_attention_cand: %d windows x %d candidates outside 1 .. %d rows of 1 .. %d candidates", C, N, WM_DEC_MAXB,
+               WM_MAX_BEST_OF);
+    WM_REQUIRE(T_stride >= 1 && T_stride <= ATT_MAXK && n_keys >= 1 && n_keys <= T_stride, WM_ERR_INVALID,
+               "dec_attention_cand: 1 .. %d keys", ATT_MAXK);
+    WM_REQUIRE(H >= 1 && H <= 255, WM_ERR_INVALID, "dec_attention_cand: %d heads do not fit the packed arguments", H);
+    WM_REQUIRE((!live_rows && !n_live) || n_live == live_rows + WM_DEC_MAXB, WM_ERR_INVALID,
+               "dec_attention_cand: the live count must follow the live rows");
+    WM_REQUIRE(part || C * H >= 256 || short_lived, WM_ERR_INVALID, "dec_attention_cand: flat launch without a partials buffer");
+    bool flat = false;
+    {
+        WmProfScope ps(&ctx->prof, "dec_attn_cross_cand", ctx->stream);
+        int rc = WM_ERR_INVALID;
+        switch (N) {
+#define WM_XCAND_CASE(n)                                                                                                   \
+    case n:                                                                                                                \
+        rc = launch_xcand<n>(ctx, q, kc, vc, C, H, T_stride, n_keys, part, att, pf_ptr, pf_rows, pf_k, live_rows, short_lived, \
+                             &flat);                                                                                       \
+        break
+            WM_XCAND_CASE(1); WM_XCAND_CASE(2); WM_XCAND_CASE(3); WM_XCAND_CASE(4);
+            WM_XCAND_CASE(5); WM_XCAND_CASE(6); WM_XCAND_CASE(7); WM_XCAND_CASE(8);
+#undef WM_XCAND_CASE
+        }
+        WM_TRY(rc);
+    }
+    if (flat) {
+        WmProfScope ps(&ctx->prof, "dec_attn_combine", ctx->stream);
+        dec_attn_combine_kernel<8><<<C * N * H, 64, 0, ctx->stream>>>(part, H, H * 64, att);
         WM_HIP(hipGetLastError());
     }
     return WM_OK;

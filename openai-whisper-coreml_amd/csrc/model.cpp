@@ -77,7 +77,8 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc_t(m, &m->dx_logprob, (size_t)D.n_text_ctx * WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dx_nospeech, WM_DEC_MAXB, s));
     WM_TRY(dalloc(m, (void **)&m->dx_par, sizeof(WmXPar), s));
-    WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)WM_DEC_MAXB + 16, s));   // (+16: the epilogue's padded 16-row blocks)
+    // (+16: the epilogue's padded 16-row blocks; second half: the rows' candidate words, WM_XIDS_CAND)
+    WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)2 * WM_XIDS_CAND, s));
     WM_TRY(dalloc_t(m, &m->dmel_win, (size_t)WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dmask, (size_t)2 * (m->vpad / 32), s));
     WM_HIP(hipMemsetAsync(m->dmask, 0, (size_t)2 * (m->vpad / 32) * 4, s));
@@ -486,10 +487,33 @@ int wm_model_reserve(wm_ctx *ctx, int B) {
     WM_TRY(dalloc_t(m, &m->xa_f32, M * d, s));
     WM_TRY(dalloc_t(m, &m->mel_f32, (size_t)B * D.n_mels * WM_N_FRAMES, s));
     WM_TRY(dalloc_t(m, &m->xkv, (size_t)D.n_text_layer * 2 * B * H * 1500 * 64, s));
-    const int Bd = B < WM_DEC_MAXB ? B : WM_DEC_MAXB;
+    const int Bd = std::max(B < WM_DEC_MAXB ? B : WM_DEC_MAXB, m->cap_rows);   // (cap_rows: wm_model_reserve_rows)
     WM_TRY(dalloc_t(m, &m->skv, (size_t)D.n_text_layer * 2 * Bd * H * D.n_text_ctx * 64, s));
     m->cap_b = B;
+    m->cap_rows = Bd;
     WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
+// A candidate group decodes more rows than it encodes windows: the self-attention K/V cache alone grows to `rows` decoder
+// rows.  The captured graphs hold its address, so they are dropped with it.
+int wm_model_reserve_rows(wm_ctx *ctx, int rows) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m && rows >= 1 && rows <= WM_DEC_MAXB, WM_ERR_INVALID, "decode rows must be 1..%d", WM_DEC_MAXB);
+    if (rows <= m->cap_rows) return WM_OK;
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    wm_model_drop_graphs(m);
+    if (m->skv) {
+        (void)hipFree(m->skv);
+        for (auto &a : m->allocs)
+            if (a == m->skv) a = nullptr;
+        m->skv = nullptr;
+    }
+    const wm_dims &D = m->dims;
+    m->cap_rows = 0;
+    WM_TRY(dalloc_t(m, &m->skv, (size_t)D.n_text_layer * 2 * rows * D.n_audio_head * D.n_text_ctx * 64, ctx->stream));
+    m->cap_rows = rows;
+    WM_HIP(hipStreamSynchronize(ctx->stream));
     return WM_OK;
 }
 
@@ -603,6 +627,8 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head, T = D.n_text_ctx, S = 1500;
+    const int NC = mode.n_cand > 1 ? mode.n_cand : 1;   // candidate group: B = Bx windows x NC rows, one cross cache per window
+    const int Bx = B / NC;
     const int ns = wm_dec_attn_splits(B, H);
     const int xns = g_wm_tuning.xattn_splits > 0 ? g_wm_tuning.xattn_splits : ns;   // 0 in the product
     const int *live = mode.stop ? m->dlive : nullptr, *nlive = mode.stop ? m->dnlive : nullptr;
@@ -615,8 +641,8 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         const DecLayerW &L = m->dec[l];
         bf16_t *kc = m->skv + (size_t)(l * 2 + 0) * B * H * T * 64;
         bf16_t *vc = m->skv + (size_t)(l * 2 + 1) * B * H * T * 64;
-        const bf16_t *xk = m->xkv + (size_t)(l * 2 + 0) * B * H * S * 64;
-        const bf16_t *xv = m->xkv + (size_t)(l * 2 + 1) * B * H * S * 64;
+        const bf16_t *xk = m->xkv + (size_t)(l * 2 + 0) * Bx * H * S * 64;
+        const bf16_t *xv = m->xkv + (size_t)(l * 2 + 1) * Bx * H * S * 64;
         DecGemvArgs a;
         // 1. attn_ln (folded) + fused q|k|v projection; k, v appended to the self-attention cache
         memset(&a, 0, sizeof(a));
@@ -637,7 +663,7 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         const bool xshort = mode.xattn_shared && !g_wm_tuning.xattn_never_short;
         // wm_align: a layer with alignment heads leaves its f32 query in m->dq (the two launches: same bits as the fused one)
         const bool cap_l = cap && cap->layer[l].n > 0;
-        const bool fuse_q = !cap_l && xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
+        const bool fuse_q = NC == 1 && !cap_l && xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
         a.pf_head_major = fuse_q ? (H * B + 7) / 8 : 0;   // pairs per XCD of the fused consumer
         WM_TRY(wm_dec_gemv(ctx, a));
         // 4. cross_attn_ln (folded) + query projection
@@ -653,8 +679,12 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         } else {
             WM_TRY(wm_dec_gemv(ctx, a));
             if (cap_l) WM_TRY(wm_align_capture_q(ctx, m->dq, d, B, cap->layer[l], cap->q, cap->Tq, cap->J, m->dpos));
-            // 5. cross-attention over the 1500 cached encoder frames
-            WM_TRY(wm_dec_attention(ctx, m->dq, xk, xv, B, H, S, S, nullptr, xns, m->dpart, m->datt, true, L.wxo, d, d, live, nlive, xshort));
+            // 5. cross-attention over the 1500 cached encoder frames (a candidate group: one K/V read per window)
+            if (NC > 1) {
+                WM_TRY(wm_dec_attention_cand(ctx, m->dq, xk, xv, Bx, NC, H, S, S, m->dpart, m->datt, L.wxo, d, d, live, nlive, xshort));
+            } else {
+                WM_TRY(wm_dec_attention(ctx, m->dq, xk, xv, B, H, S, S, nullptr, xns, m->dpart, m->datt, true, L.wxo, d, d, live, nlive, xshort));
+            }
         }
         // 6. out-projection + residual
         memset(&a, 0, sizeof(a));

@@ -90,7 +90,9 @@ struct WmXPar {
     int chunk0;           // index within the call of the group's row 0 (Philox counter: call index, not group row)
     int n_prompt;         // generated index gi = pos + 1 - n_prompt
     int ids_on;           // 1: row b's counter word is WmXDev::ids[b] (caller-given sample ids), not chunk0 + b
+    int n_cand;           // > 1: a candidate group -- row b's FOURTH counter word is WmXDev::ids[WM_XIDS_CAND + b] (else 0)
 };
+constexpr int WM_XIDS_CAND = 128 + 16;   // WmXDev::ids: [WM_DEC_MAXB + 16] sample ids | [WM_DEC_MAXB + 16] candidate words
 
 // wm_transcribe_mel: row b's encoder input = frames seek .. seek + n - 1 of the [n_mels][T] block at mel + base, zeros after
 struct WmMelWin {
@@ -164,8 +166,12 @@ struct WmDecodeMode {
     // their workgroups in every ~13 us instead of once per launch: driver command 2076 -> 2100-2134 audio-s/s, default
     // run 2190 -> 2250 (profiles/r04_xattn_short_lived.txt).  A launch shape: same bits.
     bool xattn_shared = false;
+    // Candidates per window (wm_transcribe_mel_best_of; 1: none): the group's rows are windows x n_cand, row c * n_cand + s is
+    // candidate s of window c, the cross-attention K/V cache holds one entry per WINDOW and is read by
+    // wm_dec_attention_cand, once for all live candidates of a window.
+    int n_cand = 1;
     bool operator==(const WmDecodeMode &o) const {
-        return mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return n_cand == o.n_cand && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -216,6 +222,7 @@ struct WmModel {
     std::map<std::string, int> index;
     // activations (sized for `cap_b` chunks)
     int cap_b = 0;
+    int cap_rows = 0;         // decoder rows skv holds: min(cap_b, WM_DEC_MAXB), or more for a candidate group (wm_model_reserve_rows)
     bf16_t *mel_t = nullptr;  // [B][3002][n_mels]  time-major, zero rows 0 and 3001
     bf16_t *h1p = nullptr;    // [B][3001][d]       conv1 output, zero row 0
     float *x = nullptr;       // [B*1500][d]        encoder residual stream (f32)
@@ -297,7 +304,7 @@ struct WmModel {
     float *dx_logprob = nullptr;   // [n_text_ctx][WM_DEC_MAXB]
     float *dx_nospeech = nullptr;  // [WM_DEC_MAXB]
     WmXPar *dx_par = nullptr;
-    unsigned *dx_ids = nullptr;    // [WM_DEC_MAXB + 16] per-row sample ids of the group (WmXPar::ids_on)
+    unsigned *dx_ids = nullptr;    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..), the
     // workspace of a call (grown on demand) and the debug library's one-shot cost-matrix capture (host, null in the product)
@@ -313,6 +320,7 @@ int wm_model_create(wm_ctx *ctx, const wm_dims *dims);
 void wm_model_destroy(wm_ctx *ctx);
 int wm_model_clone(wm_ctx *child, const wm_ctx *parent);
 int wm_model_reserve(wm_ctx *ctx, int B);
+int wm_model_reserve_rows(wm_ctx *ctx, int rows);   // the self-attention K/V cache alone, for `rows` decoder rows
 int wm_model_set_tensor(wm_ctx *ctx, const char *name, const float *data, size_t n);
 int wm_model_get_tensor(wm_ctx *ctx, const char *name, float *data, size_t n);
 int wm_model_init_synthetic(wm_ctx *ctx, uint64_t seed, float matrix_gain);
@@ -393,6 +401,7 @@ int wm_enc_attention(wm_ctx *ctx, const bf16_t *qk, const bf16_t *vt, bf16_t *at
 
 // dec_kernels.hip
 constexpr int WM_DEC_MAXB = 128;  // decode group: up to eight batch blocks of 16 rows (the MFMA M dimension)
+static_assert(WM_XIDS_CAND == WM_DEC_MAXB + 16, "WmXDev::ids: the candidate words follow the padded sample ids");
 constexpr int WM_NLIVE_RING = 16;  // pinned host slots for the per-burst live-row counts (early stop)
 constexpr int WM_MAXSPLIT = 8;  // stream partials of a (sequence, head) pair of the cross-attention (small batches)
 // DE_LOGITS_X: DE_LOGITS plus the WmXDev partials (text (max, sum exp), winners' raw logits, the unfiltered partial at
@@ -458,6 +467,12 @@ int wm_dec_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t
                      int T_stride, int n_keys, const int *pos_ptr, int nsplit, float *part, bf16_t *att,
                      bool cross, const bf16_t *pf_ptr = nullptr, int pf_rows = 0, int pf_k = 0,
                      const int *live_rows = nullptr, const int *n_live = nullptr, bool short_lived = false);
+// Cross-attention of a candidate group: C windows x N candidates (rows c * N + s of q / att), K/V [C][H][T_stride][64], every
+// block of a window's K/V requested once for all its live candidates.  Row bits = wm_dec_attention's over a copy of the cache.
+// part: [C * N][H][8][66] floats (the flat deal below 256 pairs).
+int wm_dec_attention_cand(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int N, int H, int T_stride,
+                          int n_keys, float *part, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0, int pf_k = 0,
+                          const int *live_rows = nullptr, const int *n_live = nullptr, bool short_lived = false);
 // The decoder's causal self-attention (<= 448 cached rows per pair): one 4-wave workgroup per (sequence, head).
 int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int B, int H, int T_stride,
                           int n_keys, const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0,

@@ -382,7 +382,8 @@ constexpr int kGroupChunks = 8;   // smallest decode group worth a lane (BASELIN
 struct LaneJob {
     enum State { IDLE, DECODING, DRAINING };
     wm_ctx *c = nullptr;
-    int b0 = 0, Bg = 0;
+    int b0 = 0, Bg = 0;   // first row of the call (a candidate call: first WINDOW) and decoder rows of the group
+    int Cg = 0;           // its encoder rows: Bg, or (candidates) Bg / n_cand windows -- row c * n_cand + s is candidate s of window c
     int P = 0;          // prompt positions of the group (a ragged call: the longest prompt among ITS rows)
     WmDecodeMode mode;  // of the group's decode (xattn_shared: decided burst by burst), filled by lane_prefill
     int gset = -1;      // its graph set in the lane's WmModel::graph_sets (lane_graph)
@@ -425,6 +426,7 @@ struct TxSrc : WmAudioSrc {
     const int32_t *prompt_len = nullptr;   // non-null: a ragged call, row b's prompt is its first prompt_len[b] entries
     int sot_tail = 0;                      // ... whose <|startoftranscript|> is entry prompt_len[b] - sot_tail
     const uint32_t *sample_ids = nullptr;
+    int n_cand = 1;   // candidates per row (wm_transcribe_mel_best_of): every row decodes n_cand times over ONE encoder pass
 };
 
 struct StopCfg {
@@ -522,30 +524,40 @@ int stage_mel(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const 
 int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const StopCfg &stop, const XCfg &xc) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
-    const int Bg = j.Bg;
+    const int Bg = j.Bg, Cg = j.Cg, N = src.n_cand;   // decoder rows, encoder rows (windows), candidates per window
     // the mode of this group's decode: the lane's own context settings and the call's options, in this one place
     j.mode = WmDecodeMode();
     j.mode.mask = m->mask_on; j.mode.ts = m->ts_on; j.mode.x = xc.on; j.mode.off = src.prompt_len != nullptr;
     j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
+    j.mode.n_cand = N;
     const void *d_pcm;
-    WM_TRY(stage_pcm(c, src, j.b0, Bg, mem, &d_pcm));
+    WM_TRY(stage_pcm(c, src, j.b0, Cg, mem, &d_pcm));
     // decode state first (prompt tokens [n_prompt][Bg], position 0): a pageable H2D copy may wait for the
     // stream to drain, so it is issued while the lane is still idle
     WM_TRY(wm_model_decode_begin(c, Bg));
     if (src.prompt_len) {   // ragged: right-aligned to the group's longest prompt (n_prompt = j.P), offsets next to it
-        wm_right_align(src.prompt, src.prompt_stride, src.prompt_len, j.b0, Bg, j.pr, j.off);
+        wm_right_align(src.prompt, src.prompt_stride, src.prompt_len, j.b0, Cg, j.pr, j.off);
+        if (N > 1) {   // every candidate of a window steps through the window's prompt
+            std::vector<int32_t> pr((size_t)n_prompt * Bg), off(Bg);
+            for (int b = 0; b < Bg; ++b) off[b] = j.off[b / N];
+            for (int t = 0; t < n_prompt; ++t)
+                for (int b = 0; b < Bg; ++b) pr[(size_t)t * Bg + b] = j.pr[(size_t)t * Cg + b / N];
+            j.pr.swap(pr);
+            j.off.swap(off);
+        }
         WM_HIP(hipMemcpyAsync(m->doff, j.off.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
     } else {
         j.pr.resize((size_t)n_prompt * Bg);
         for (int t = 0; t < n_prompt; ++t)
-            for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = src.prompt[(size_t)(j.b0 + b) * src.prompt_stride + t];
+            for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = src.prompt[(size_t)(j.b0 + b / N) * src.prompt_stride + t];
     }
     WM_HIP(hipMemcpyAsync(m->dseq, j.pr.data(), j.pr.size() * 4, hipMemcpyHostToDevice, c->stream));
     WM_TRY(wm_model_set_pos(c, 0));
     // early-stop state of this group: done flags, live list, per-row budgets (kernel arguments of the decode graphs)
     if (stop.on) {
         if (j.mode.budget) {
-            j.bud.assign(stop.budgets + j.b0, stop.budgets + j.b0 + Bg);
+            j.bud.resize(Bg);
+            for (int b = 0; b < Bg; ++b) j.bud[b] = stop.budgets[j.b0 + b / N];
             WM_HIP(hipMemcpyAsync(m->dbudget, j.bud.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
         }
         WM_TRY(wm_stop_init(c, wm_model_stop_dev(m, j.mode), Bg));
@@ -557,23 +569,32 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
         j.xpar.chunk0 = j.b0;
         j.xpar.n_prompt = n_prompt;
         if (src.prompt_len && xc.no_speech) j.xpar.sot_pos = n_prompt - src.sot_tail;   // the same distance from every row's end
-        j.xpar.ids_on = src.sample_ids ? 1 : 0;
-        if (src.sample_ids) {   // caller-given Philox counter words (wm_transcribe_mel): a row's noise follows its id
+        j.xpar.ids_on = (src.sample_ids || N > 1) ? 1 : 0;
+        j.xpar.n_cand = N;
+        if (N > 1) {   // a candidate group: per row the window's id (given, or its index in the call) and the candidate word
+            j.ids.assign((size_t)2 * WM_XIDS_CAND, 0u);
+            for (int b = 0; b < Bg; ++b) {
+                j.ids[b] = src.sample_ids ? src.sample_ids[j.b0 + b / N] : (unsigned)(j.b0 + b / N);
+                j.ids[WM_XIDS_CAND + b] = (unsigned)(b % N);
+            }
+            WM_HIP(hipMemcpyAsync(m->dx_ids, j.ids.data(), j.ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+        } else if (src.sample_ids) {   // caller-given Philox counter words (wm_transcribe_mel): a row's noise follows its id
             j.ids.assign(src.sample_ids + j.b0, src.sample_ids + j.b0 + Bg);
             WM_HIP(hipMemcpyAsync(m->dx_ids, j.ids.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
         }
         WM_HIP(hipMemcpyAsync(m->dx_par, &j.xpar, sizeof(WmXPar), hipMemcpyHostToDevice, c->stream));
     }
-    WM_TRY(wm_model_reserve(c, Bg));
+    WM_TRY(wm_model_reserve(c, Cg));
+    if (N > 1) WM_TRY(wm_model_reserve_rows(c, Bg));
     WM_HIP(hipEventRecord(j.ev[0], c->stream));
     // 1. log-mel front end, or the caller's mel windows
     const float *enc_mel;
     const WmMelWin *enc_win;
-    WM_TRY(stage_mel(c, src, j.b0, Bg, mem, d_pcm, j.win, &enc_mel, &enc_win));
+    WM_TRY(stage_mel(c, src, j.b0, Cg, mem, d_pcm, j.win, &enc_mel, &enc_win));
     WM_HIP(hipEventRecord(j.ev[1], c->stream));
     // 2. encoder + cross-attention K/V
-    WM_TRY(wm_model_encode_win(c, enc_mel, enc_win, Bg, nullptr));
-    WM_TRY(wm_model_cross_kv(c, Bg));
+    WM_TRY(wm_model_encode_win(c, enc_mel, enc_win, Cg, nullptr));
+    WM_TRY(wm_model_cross_kv(c, Cg));
     WM_HIP(hipEventRecord(j.ev[2], c->stream));
     // 3. embedding of the first prompt token (+ the initial timestamp-rule state)
     WM_TRY(wm_model_embed_first(c, Bg, j.mode));
@@ -684,6 +705,31 @@ int wm_group_count(int B, int L, bool explicit_lanes, int gc_probe) {
     return G < g_min ? g_min : (G < 1 ? 1 : G);
 }
 
+// B rows in G balanced runs (sizes differ by at most one, the larger ones first): run g is rows [b0[g], b0[g] + cg[g]).  The cut
+// of every transcribe call, with or without candidates.
+void wm_balanced_cut(int B, int G, std::vector<int> &b0, std::vector<int> &cg) {
+    b0.resize(G);
+    cg.resize(G);
+    const int base = B / G, rem = B % G;
+    for (int g = 0; g < G; ++g) {
+        cg[g] = base + (g < rem ? 1 : 0);
+        b0[g] = g * base + (g < rem ? g : rem);
+    }
+}
+
+// Decode groups of a CANDIDATE call (wm_transcribe_mel_best_of) of B windows x N candidates: a group holds whole windows,
+// cg[g] of them from window b0[g], cg[g] * N <= WM_DEC_MAXB rows.  The number of groups is wm_group_count's for the B * N
+// decoder rows (what the GEMVs and the self-attention see), at least what the row cap asks for and at most one per window;
+// the windows are dealt in balanced runs.  Pure: tests pin it through the debug library.  Returns the number of groups.
+int wm_cand_groups(int B, int N, int L, bool explicit_lanes, std::vector<int> &b0, std::vector<int> &cg) {
+    const int c_max = WM_DEC_MAXB / N;
+    int G = wm_group_count(B * N, L, explicit_lanes, 0);
+    G = std::max(G, (B + c_max - 1) / c_max);
+    G = std::min(G, B);
+    wm_balanced_cut(B, G, b0, cg);
+    return G;
+}
+
 // SUB-CHIP LANES (round 6): P = 2 (or 3) decode groups of a call, each on its OWN part of the chip -- weight-sharing clones
 // whose streams carry complementary CU masks (wm_clone_cus: a slice of the CUs of every XCD) -- instead of one
 // latency-bound chain, or unmasked chains whose every launch floods all 256 CUs.  Returns 0 when the call is served better
@@ -757,6 +803,45 @@ extern "C" int wm_transcribe_mel_ragged(wm_ctx *ctx, const float *mel, const int
     src.sample_ids = sample_ids;
     return transcribe_impl(ctx, src, B, prompt_stride, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
                            no_speech_prob_out, mem);
+} WM_API_CATCH
+
+// wm_transcribe_mel_ragged / wm_transcribe_mel with best_of candidates per row (TxSrc::n_cand): one encoder pass, one
+// cross-K/V cache and one read of it per window, best_of decoder rows (lane_prefill, wm_dec_attention_cand)
+extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                         const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                         int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                         int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                         int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                         float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+    // the checks of this entry point's own arguments; a call that fails them consumes the token budgets set for it, as a
+    // call that fails transcribe_impl's checks does
+    const int rc = [&]() -> int {
+        WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
+        WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
+        WM_REQUIRE(best_of >= 1 && best_of <= WM_MAX_BEST_OF, WM_ERR_INVALID, "best_of %d outside [1, %d]", best_of, WM_MAX_BEST_OF);
+        WM_REQUIRE(std::isnan(length_penalty) || (length_penalty >= 0.f && length_penalty <= 1.f), WM_ERR_INVALID,
+                   "length_penalty must be NaN (none) or in [0, 1]");
+        WM_REQUIRE(B >= 1 && max_new >= 1, WM_ERR_INVALID, "B < 1 or max_new < 1");
+        return WM_OK;
+    }();
+    if (rc != WM_OK) {
+        if (ctx && ctx->model) ctx->model->budget_host.clear();
+        return rc;
+    }
+    TxSrc src;
+    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
+    src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
+    src.sample_ids = sample_ids; src.n_cand = best_of;
+    std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
+    float *lp = token_logprobs_out;
+    if (best_out && !lp) {
+        lp_own.resize((size_t)B * best_of * max_new);
+        lp = lp_own.data();
+    }
+    WM_TRY(transcribe_impl(ctx, src, B, prompt_stride, max_new, eot, opts, tokens_out, lens_out, lp, no_speech_prob_out, mem));
+    if (best_out)
+        WM_TRY(wm_rank_candidates(tokens_out, lens_out, lp, B, best_of, max_new, eot, length_penalty, best_out, nullptr));
+    return WM_OK;
 } WM_API_CATCH
 
 // wm_transcribe_greedy, wm_transcribe, wm_transcribe_mel and wm_transcribe_mel_ragged: opts == null with both extra outputs
@@ -846,7 +931,8 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
     const bool explicit_lanes = ctx->max_lanes > 0;
     const int L = ctx->prof.on ? 1 : (explicit_lanes ? ctx->max_lanes : lane_limit());
     const int solo = g_wm_tuning.lane_solo_cus;   // probes only (0 in the product)
-    int parts = (ctx->prof.on || solo || ctx->no_cu_masks) ? 0 : wm_lane_parts(B, L, explicit_lanes, D.n_text_state, D.n_text_layer);
+    const int N = src.n_cand;   // candidates per row: tokens_out [B][N][max_new], a decode group holds whole rows
+    int parts = (ctx->prof.on || solo || ctx->no_cu_masks || N > 1) ? 0 : wm_lane_parts(B, L, explicit_lanes, D.n_text_state, D.n_text_layer);
     if (parts) {
         // the sub-chip lanes of this partition, created on first use.  A device / driver that refuses CU-masked streams (a
         // partitioned GPU, an older KFD) is not an error: the call falls back to the unmasked policy, once and for all
@@ -863,7 +949,16 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
         }
         WM_TRY(wm_ctx_make_current(ctx));
     }
-    const int G = parts ? parts : wm_group_count(B, L, explicit_lanes, g_wm_tuning.group_chunks);
+    // group g: rows (a candidate call: windows) [grp_b0[g], grp_b0[g] + grp_cg[g]) of the call.  (Sub-chip parts stay off for
+    // candidate calls: not measured.)
+    std::vector<int> grp_b0, grp_cg;
+    int G;
+    if (N > 1) {
+        G = wm_cand_groups(B, N, L, explicit_lanes, grp_b0, grp_cg);
+    } else {
+        G = parts ? parts : wm_group_count(B, L, explicit_lanes, g_wm_tuning.group_chunks);
+        wm_balanced_cut(B, G, grp_b0, grp_cg);
+    }
     const int n_lanes = solo ? 1 : (parts ? parts : (G < L ? G : L));
     wm_ctx *solo_ctx = nullptr;
     if (solo) {
@@ -894,7 +989,6 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
         explicit ActiveGuard(std::atomic<int> &a) : n(a) { n.fetch_add(1, std::memory_order_relaxed); }
         ~ActiveGuard() { n.fetch_sub(1, std::memory_order_relaxed); }
     } active_guard(g_wm_active_decodes[ctx->device & 63]);
-    const int base = B / G, rem = B % G;
     int next_group = 0, groups_done = 0;
     while (groups_done < G) {
         bool progress = false;
@@ -904,11 +998,12 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
             if (j.state == LaneJob::IDLE) {
                 if (next_group >= G) continue;
                 const int g = next_group++;
-                j.Bg = base + (g < rem ? 1 : 0);
-                j.b0 = g * base + (g < rem ? g : rem);
+                j.Cg = grp_cg[g];
+                j.b0 = grp_b0[g];
+                j.Bg = j.Cg * N;
                 j.t = 0; j.bursts = 0; j.stopped = false;
                 j.P = n_prompt;
-                if (src.prompt_len) j.P = *std::max_element(src.prompt_len + j.b0, src.prompt_len + j.b0 + j.Bg);
+                if (src.prompt_len) j.P = *std::max_element(src.prompt_len + j.b0, src.prompt_len + j.b0 + j.Cg);
                 WM_TRY(lane_prefill(j, src, j.P, mem, stop, xc));
                 if (use_graph) WM_TRY(lane_graph(j, j.P));
                 j.state = LaneJob::DECODING;
@@ -960,18 +1055,20 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
             if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
             WM_HIP(q);
             WM_HIP(hipStreamSynchronize(j.c->stream));
-            for (int b = 0; b < j.Bg; ++b) {
+            for (int b = 0; b < j.Bg; ++b) {   // [gi][row] -> [row of the call][candidate][gi]
+                const int w = j.b0 + b / N;            // row of the call
+                const size_t o = (size_t)j.b0 * N + b; // its candidate's output row
                 int len = max_new;
-                if (stop.budgets && stop.budgets[j.b0 + b] < len) len = stop.budgets[j.b0 + b];
+                if (stop.budgets && stop.budgets[w] < len) len = stop.budgets[w];
                 for (int i = 0; i < len; ++i)
                     if (eot >= 0 && j.gen[(size_t)i * j.Bg + b] == eot) { len = i + 1; break; }
                 for (int i = 0; i < max_new; ++i)
-                    tokens_out[(size_t)(j.b0 + b) * max_new + i] = i < len ? j.gen[(size_t)i * j.Bg + b] : eot;
-                lens_out[j.b0 + b] = len;
+                    tokens_out[o * max_new + i] = i < len ? j.gen[(size_t)i * j.Bg + b] : eot;
+                lens_out[o] = len;
                 if (xc.logprobs)   // the token that stops a chunk has its log-prob; nothing after it
                     for (int i = 0; i < max_new; ++i)
-                        xc.logprobs[(size_t)(j.b0 + b) * max_new + i] = i < len ? j.lp[(size_t)i * j.Bg + b] : 0.f;
-                if (xc.no_speech) xc.no_speech[j.b0 + b] = j.ns[b];
+                        xc.logprobs[o * max_new + i] = i < len ? j.lp[(size_t)i * j.Bg + b] : 0.f;
+                if (xc.no_speech && b % N == 0) xc.no_speech[w] = j.ns[b];   // (candidates: candidate 0's)
             }
             float ms;
             for (int i = 0; i < 3; ++i)

@@ -5,7 +5,8 @@
 // Sampling at temperature T draws token n with probability softmax(logits / T) by the Gumbel-max trick: the arg-max of
 // score(n) = logit(n) / T + g(n), g(n) = -log(-log u(n)), u(n) uniform in (0, 1).  The uniform of token n at generated
 // index gi of chunk c (the chunk's index within the call) under a 64-bit seed is word (n & 3) of
-//     philox4x32_10(counter = {n >> 2, gi, c, 0}, key = {seed & 0xffffffff, seed >> 32})
+//     philox4x32_10(counter = {n >> 2, gi, c, s}, key = {seed & 0xffffffff, seed >> 32})
+// with s the candidate index of a best-of-N call and 0 in every other call,
 // mapped to u = ((x >> 9) * 2 + 1) * 2^-24: exact in f32, strictly inside (0, 1).  One Philox call serves four ids.
 #pragma once
 #include <stdint.h>
@@ -56,6 +57,15 @@ WM_PHILOX_FN uint32_t wm_philox_word(const wm_philox4 &r, uint32_t n) {
 WM_PHILOX_FN uint32_t wm_sample_bits(uint64_t seed, uint32_t chunk, uint32_t gi, uint32_t n) {
     wm_philox4 c;
     c.v[0] = n >> 2; c.v[1] = gi; c.v[2] = chunk; c.v[3] = 0u;
+    const wm_philox4 r = wm_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return wm_philox_word(r, n);
+}
+
+// the same draw for CANDIDATE `cand` of the chunk (wm_transcribe_mel_best_of): the fourth counter word, 0 everywhere else --
+// wm_sample_bits_cand(seed, chunk, 0, gi, n) == wm_sample_bits(seed, chunk, gi, n)
+WM_PHILOX_FN uint32_t wm_sample_bits_cand(uint64_t seed, uint32_t chunk, uint32_t cand, uint32_t gi, uint32_t n) {
+    wm_philox4 c;
+    c.v[0] = n >> 2; c.v[1] = gi; c.v[2] = chunk; c.v[3] = cand;
     const wm_philox4 r = wm_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     return wm_philox_word(r, n);
 }

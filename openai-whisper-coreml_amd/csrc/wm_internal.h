@@ -194,6 +194,9 @@ int wm_cu_mask(int cu_lo, int cu_hi, uint32_t mask[8]);
 
 int wm_ctx_make_current(const wm_ctx *ctx);
 int wm_group_count(int B, int L, bool explicit_lanes, int gc_probe);   // model_api.cpp: decode groups of a wm_transcribe_greedy call
+// ... and of a wm_transcribe_mel_best_of call of B windows x N candidates: groups of whole windows (first window, windows)
+int wm_cand_groups(int B, int N, int L, bool explicit_lanes, std::vector<int> &b0, std::vector<int> &cg);
+void wm_balanced_cut(int B, int G, std::vector<int> &b0, std::vector<int> &cg);   // B rows in G balanced runs
 // the right-aligned prompt table [P][Bg] and the row offsets [Bg] of rows [b0, b0 + Bg) of a ragged call; returns P (model_api.cpp)
 int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, std::vector<int32_t> &table,
                    std::vector<int32_t> &off);

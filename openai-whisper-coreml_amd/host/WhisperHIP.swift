@@ -266,6 +266,39 @@ struct Whisper {
         return (0..<rows).map { r in Array(tokens[r * Int(maxNew)..<r * Int(maxNew) + Int(outLens[r])]) }
     }
 
+    /// openai-whisper's best_of on the same step (wm_transcribe_mel_best_of): bestOf sampled candidates per window that share
+    /// the window's encoder pass and cross-attention cache, ranked by the library (lengthPenalty nil = openai-whisper's None).
+    /// Uniform prompts of one length (sotTail nil) or ragged ones.  Returns, per window, the generated tokens of every
+    /// candidate and the index of the best one.  Not compiled in this repository.
+    func transcribeMelBestOf(mel: [Float], melBase: [Int64], melLen: [Int32], seek: [Int32], nFrames: [Int32],
+                             prompts: [[Int32]], sotTail: Int32?, bestOf: Int32, lengthPenalty: Float?, temperature: Float,
+                             seed: UInt64, maxNew: Int32, eot: Int32) throws -> (candidates: [[[Int32]]], best: [Int32]) {
+        typealias BestOfFn = @convention(c) (OpaquePointer, UnsafePointer<Float>, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                             UnsafePointer<Int32>, UnsafePointer<Int32>, Int32, UnsafePointer<Int32>, Int32,
+                                             UnsafePointer<Int32>?, Int32, UnsafePointer<UInt32>?, Int32, Float, Int32, Int32,
+                                             UnsafeRawPointer?, UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Int32>,
+                                             UnsafeMutablePointer<Float>?, UnsafeMutablePointer<Float>?,
+                                             UnsafeMutablePointer<Int32>?, Int32) -> Int32
+        struct DecodeOpts { var temperature: Float; var seed: UInt64; var noSpeechToken: Int32; var sotIndex: Int32 }   // wm_decode_opts
+        let rows = melBase.count, n = Int(bestOf), m = Int(maxNew)
+        let stride = prompts.map { $0.count }.max() ?? 0
+        let lens = prompts.map { Int32($0.count) }
+        let flat = prompts.flatMap { $0 + [Int32](repeating: 0, count: stride - $0.count) }
+        var opts = DecodeOpts(temperature: temperature, seed: seed, noSpeechToken: -1, sotIndex: 0)
+        var tokens = [Int32](repeating: 0, count: rows * n * m)
+        var outLens = [Int32](repeating: 0, count: rows * n)
+        var best = [Int32](repeating: 0, count: rows)
+        let f: BestOfFn = try sym("wm_transcribe_mel_best_of")
+        let st = withUnsafePointer(to: &opts) { o in
+            f(ctx, mel, melBase, melLen, seek, nFrames, Int32(rows), flat, Int32(stride), sotTail == nil ? nil : lens,
+              sotTail ?? 0, nil, bestOf, lengthPenalty ?? Float.nan, maxNew, eot, UnsafeRawPointer(o), &tokens, &outLens, nil, nil,
+              &best, 0)
+        }
+        try check(st)
+        let cands = (0..<rows).map { r in (0..<n).map { s in Array(tokens[(r * n + s) * m..<(r * n + s) * m + Int(outLens[r * n + s])]) } }
+        return (cands, best)
+    }
+
     /// Word-level timing inputs of the windows of a long-form round (wm_align_mel): the window description of
     /// transcribeMel, one start sequence per row ([sot, language, task] with the row's own language) and the text tokens the
     /// round decoded for each window (all < eot).  Same outputs as align.  The word rules (add_word_timestamps) and the
