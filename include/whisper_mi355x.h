@@ -299,6 +299,43 @@ WM_API int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const int64_
 WM_API int wm_rank_candidates(const int32_t *tokens, const int32_t *lens, const float *token_logprobs, int B, int n_cand,
                               int max_new, int32_t eot, float length_penalty, int32_t *best_out, double *score_out);
 
+/* openai-whisper's beam search (BeamSearchDecoder, beam_size / patience): wm_transcribe_mel_ragged (prompt_len given) or
+ * wm_transcribe_mel (prompt_len NULL) with beam_size BEAMS per window.  The beams of a window share its encoder pass, its
+ * cross-attention K/V cache and every read of that cache, exactly as the candidates of wm_transcribe_mel_best_of do; after
+ * every generated token the beams are re-parented on the device.  Per window and generated index:
+ *   list      : every live beam's beam_size + 1 most probable tokens under the filtered distribution (suppress lists, timestamp
+ *               rules incl. the sum rule -- the filters of the greedy decode), lp = logit - logsumexp(allowed) in f32, best
+ *               first (by logit, equal logits: the lower id; -inf is never listed; fewer admissible ids: a shorter list);
+ *   candidates: score = f32(sum_of_beam + lp); at the first generated token beam 0 alone contributes (all beams are equal);
+ *               walked by descending score (ties: the lower beam, then the earlier list entry).  A candidate ending in eot is
+ *               a finished hypothesis, kept while the window has fewer than max_candidates; any other becomes the next beam
+ *               0, 1, ... until beam_size are taken.  Slots left empty are DEAD beams (sum -inf, eot padding, no candidates);
+ *   a window with max_candidates finished hypotheses leaves the decode: its rows stop, its cross-K/V cache is not read again;
+ *   finalize  : when max_new -- or the window's token budget (wm_set_token_budgets, B entries: the window's own max_new) -- is
+ *               used up; with fewer than beam_size hypotheses finished, the live beams follow in descending-sum order until
+ *               there are beam_size.  Hypothesis order: the finished ones as they finished, then those.
+ *   beam_size      : 1 .. WM_MAX_BEAM;  max_candidates : 1 .. WM_MAX_BEAM_HYPS (openai-whisper: round(beam_size * patience));
+ *   length_penalty : as wm_rank_candidates;  opts->temperature must be 0 (it plays no part);  eot < 0: nothing ever finishes;
+ *   outputs, with S = max(beam_size, max_candidates):
+ *   tokens_out i32 [B][S][max_new];  lens_out i32 [B][S] (a finished hypothesis counts its eot);  n_hyp_out i32 [B];
+ *   sum_logprobs_out f32 [B][S]: the running f32 sum the search itself used;  token_logprobs_out f32 [B][S][max_new], nullable;
+ *   slots past n_hyp: tokens eot, length 0, sum -inf;  no_speech_prob_out f32 [B], nullable: beam 0's;
+ *   best_out i32 [B], nullable: the MaximumLikelihoodRanker over sum_logprobs and the tokens before eot, with the penalty
+ *   rules of wm_rank_candidates (n_text == 0 counts as 1, the first maximal score wins).
+ * Bit for bit: beam_size = 1 with max_candidates = 1 is wm_transcribe_mel / wm_transcribe_mel_ragged at temperature 0 -- tokens,
+ * length and log-probs, and the sum is the in-order f32 sum of those log-probs; a window's result depends on its own window,
+ * prompt and the beam parameters only, not on the other rows, the grouping or the lanes.
+ * Invalid: beam_size or max_candidates outside their ranges, opts->temperature != 0, eot >= n_vocab, a null n_hyp_out or
+ * sum_logprobs_out, and everything wm_transcribe_mel_best_of rejects. */
+#define WM_MAX_BEAM 8
+#define WM_MAX_BEAM_HYPS 16
+WM_API int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                  const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts, int prompt_stride,
+                                  const int32_t *prompt_len, int sot_tail, int beam_size, int max_candidates,
+                                  float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                  int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
+                                  float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem);
+
 /* ------------------------------------------------------------- word-level timestamps --- */
 /* openai-whisper's find_alignment (whisper/timing.py) on the GPU, for the text tokens a transcription produced (e.g. each
  * chunk's tokens from the temperature step of wm_transcribe that it kept).  Per chunk with text tokens t[0 .. n), all < eot:

@@ -140,6 +140,40 @@ WM_API int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys, in
 WM_API int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, int V, int ldo, const int32_t *tok, int eot,
                                   float *prob);
 
+/* Beam search (wm_transcribe_mel_beam).  One selection step of ONE window on host data, by the function the select kernel runs
+ * (csrc/beam.h): N beams of which the first n_from contribute (1 at the first generated token), sum f32 [N] (-inf: a dead beam),
+ * lists list_n i32 [N] (0 .. WM_MAX_BEAM + 1 entries, best first), list_tok i32 / list_lp f32 [N][WM_MAX_BEAM + 1]; eot < 0:
+ * nothing finishes; pad: the token of a dead beam; room: finished hypotheses the window still takes.  Out: *n_next beams taken,
+ * src / tok / lp / new_sum [N] (slots >= *n_next: dead -- src = slot, tok = pad, lp 0, sum -inf), *n_fin kept newly finished
+ * hypotheses with fin_src / fin_lp / fin_sum [N]. */
+WM_API int wmdbg_beam_select(int N, int n_from, int32_t eot, int32_t pad, int room, const float *sum, const int32_t *list_n,
+                             const int32_t *list_tok, const float *list_lp, int32_t *n_next, int32_t *src, int32_t *tok,
+                             float *lp, float *new_sum, int32_t *n_fin, int32_t *fin_src, float *fin_lp, float *fin_sum);
+/* The MaximumLikelihoodRanker's score of one hypothesis, the function behind wm_rank_candidates and
+ * wm_transcribe_mel_beam's best_out: sum / n_text (n_text 0 counts as 1) with length_penalty NaN, else
+ * sum / ((5 + n_text) / 6) ** length_penalty.  Host only. */
+WM_API double wmdbg_rank_score(double sum, int n_text, float length_penalty);
+/* Finalize: the live beams (sum > -inf) by descending sum, ties to the lower beam, into order_out [N]; returns their count
+ * (-1: bad arguments).  Host only. */
+WM_API int wmdbg_beam_fill_order(int N, const float *sum, int32_t *order_out);
+/* Makes the NEXT wm_transcribe_mel_beam call on ctx also return, per window, generated index and beam, the beam's list and
+ * its running sum BEFORE that step: trace_out f32 [B][max_new][beam_size][2 + 2 * (WM_MAX_BEAM + 1)], each record = entries
+ * (i32 bits), sum, WM_MAX_BEAM + 1 token ids (i32 bits), WM_MAX_BEAM + 1 log-probs; zeros where no step ran.  That call
+ * launches its positions eagerly. */
+WM_API int wmdbg_beam_trace(wm_ctx *ctx, float *trace_out);
+/* The per-row list kernel alone.  logits f32 [rows][V] (host), N beams per window (the lists hold N + 1 entries), suppressed
+ * ids, rng i32 [rows][4] = (text_lo, text_hi, ts_lo, ts_hi) or NULL (timestamp rules off) with ts_begin.  The per-tile
+ * partials the decode step's logits launch would leave are restated on the host (f32, libm expf).  Out: list_n i32 [rows],
+ * list_tok i32 / list_lp f32 [rows][WM_MAX_BEAM + 1]. */
+WM_API int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V, int N, const int32_t *suppress, int n_suppress,
+                           const int32_t *rng, int32_t ts_begin, int32_t *list_n, int32_t *list_tok, float *list_lp);
+/* The re-parenting kernel alone, in place on host data: cache u16 [L2][rows][H][T][64] (bf16 bits), seq i32 [T][rows] and
+ * logprob f32 [T][rows] (position-major), for the close of position pos (rows 0 .. pos of the cache, generated indices
+ * 0 .. pos - n_prompt of the histories); src i32 [rows]: the beam (0 .. N - 1) of its window each row continues; wdone i32
+ * [rows / N]: 1 = the window has just left the decode (its histories move, its cache does not). */
+WM_API int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows, int H, int T, int N, int pos, int n_prompt,
+                              const int32_t *src, const int32_t *wdone, int32_t *seq, float *logprob);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,8 @@ def load_library(path=None):
         "wm_transcribe_mel_ragged": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, vp, vp, vp, vp, ip],
         "wm_transcribe_mel_best_of": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_float, ip, ctypes.c_int32, vp,
                                       vp, vp, vp, vp, vp, ip],
+        "wm_transcribe_mel_beam": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, ip, ip, ctypes.c_float, ip, ctypes.c_int32, vp,
+                                   vp, vp, vp, vp, vp, vp, vp, ip],
         "wm_rank_candidates": [vp, vp, vp, ip, ip, ip, ctypes.c_int32, ctypes.c_float, vp, vp],
         "wm_set_token_budgets": [vp, vp, ip],
         "wm_set_alignment_heads": [vp, vp, vp, ip],
@@ -226,6 +228,45 @@ class BestOfResult:
         self.selected.candidate = best
 
 
+MAX_BEAM, MAX_BEAM_HYPS = 8, 16   # WM_MAX_BEAM, WM_MAX_BEAM_HYPS
+
+
+def beam_max_candidates(beam_size, patience=None):
+    """openai-whisper's BeamSearchDecoder: max_candidates = round(beam_size * patience), patience None = 1.0.  Raises
+    ValueError where wm_transcribe_mel_beam would reject the pair."""
+    if beam_size is None:
+        if patience is not None:
+            raise ValueError("patience requires beam_size to be given")
+        return None
+    if int(beam_size) != beam_size or not 1 <= int(beam_size) <= MAX_BEAM:
+        raise ValueError("beam_size must be an integer in 1 .. %d" % MAX_BEAM)
+    pat = 1.0 if patience is None else float(patience)
+    if not pat > 0.0:
+        raise ValueError("patience must be positive")
+    n = round(int(beam_size) * pat)
+    if not 1 <= n <= MAX_BEAM_HYPS:
+        raise ValueError("round(beam_size * patience) = %d outside 1 .. %d" % (n, MAX_BEAM_HYPS))
+    return int(n)
+
+
+class BeamResult:
+    """What Context.transcribe_mel_beam returns, with S = max(beam_size, max_candidates): tokens i32 [B][S][max_new], lens i32
+    [B][S] (a finished hypothesis counts its eot), n_hyp i32 [B], sum_logprob f32 [B][S] (the search's own running sums; -inf
+    past n_hyp), logprobs f32 [B][S][max_new], no_speech_prob f32 [B] (beam 0's; None without a no-speech token), best i32 [B]
+    and selected: the TranscribeResult of hypothesis best[b] of every row, whose sum_logprob is the search's f32 sum and
+    avg_logprob = sum / (n_text + 1), with the same indices as its attribute `hypothesis`."""
+
+    def __init__(self, tokens, lens, n_hyp, sum_logprob, logprobs, no_speech_prob, best, eot):
+        self.tokens, self.lens, self.n_hyp, self.sum_logprob = tokens, lens, n_hyp, sum_logprob
+        self.logprobs, self.no_speech_prob, self.best = logprobs, no_speech_prob, best
+        rows = np.arange(tokens.shape[0])
+        self.selected = TranscribeResult(np.ascontiguousarray(tokens[rows, best]), np.ascontiguousarray(lens[rows, best]),
+                                         np.ascontiguousarray(logprobs[rows, best]), no_speech_prob, eot)
+        self.selected.sum_logprob = sum_logprob[rows, best].astype(np.float64)
+        self.selected.avg_logprob = self.selected.sum_logprob / (self.selected.n_text + 1)
+        self.selected.hypothesis = best
+
+
 def rank_candidates(tokens, lens, logprobs, eot, length_penalty=None):
     """wm_rank_candidates (openai-whisper's MaximumLikelihoodRanker; host only): tokens [B][N][max_new], lens [B][N],
     logprobs [B][N][max_new]; length_penalty None is openai-whisper's None.  Returns (best i32 [B], scores f64 [B][N])."""
@@ -276,7 +317,7 @@ def fallback_seed(seed, k):
 def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                              compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
                              vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None, best_of=None,
-                             length_penalty=None):
+                             length_penalty=None, beam_size=None, patience=None):
     """openai-whisper's decode_with_fallback, per chunk, over ctx.transcribe.
 
     Temperature step k decodes, as ONE batched call, the chunks that still need fallback (step 0: all of them) at
@@ -292,17 +333,27 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     ids (the index within the call) -- and keeps each chunk's best one under length_penalty (rank_candidates).  The
     temperature-0 step is unchanged.
 
+    beam_size (openai-whisper's beam_size, with patience; None: greedy): the temperature-0 step is ONE wm_transcribe_mel_beam
+    call over the chunks' Context.logmel windows and keeps each chunk's best hypothesis under length_penalty; the steps
+    above temperature 0 are unchanged.  patience without beam_size is a ValueError.
+
     Returns a dict of per-chunk arrays (tokens, lens, logprobs, sum_logprob, avg_logprob, no_speech_prob,
     compression_ratio, temperature, seed, needs_fallback) and `steps`: [(temperature, seed, chunk indices)] per call."""
     pcm = np.asarray(pcm)
+    beam_max_candidates(beam_size, patience)
 
     def decode(todo, t, sd):
-        if best_of is not None and t > 0:
+        extra = None
+        if beam_size is not None and t == 0:
+            extra = dict(beam_size=beam_size, patience=patience, length_penalty=length_penalty)
+        elif best_of is not None and t > 0:
+            extra = dict(best_of=best_of, length_penalty=length_penalty)
+        if extra is not None:
             n_mels = int(ctx.dims["n_mels"])
             mel = ctx.logmel(pcm[todo], n_mels=n_mels)
             return ctx.transcribe_mel(mel, np.arange(len(todo), dtype=np.int64) * (n_mels * N_FRAMES), N_FRAMES, 0, N_FRAMES,
                                       prompt, max_new, eot=eot, temperature=t, seed=sd, no_speech_token=no_speech_token,
-                                      sot_index=sot_index, best_of=best_of, length_penalty=length_penalty)
+                                      sot_index=sot_index, **extra)
         return ctx.transcribe(pcm[todo], prompt, max_new, eot=eot, temperature=t, seed=sd,
                               no_speech_token=no_speech_token, sot_index=sot_index)
     return fallback_decode(decode, pcm.shape[0], int(ctx.dims["n_vocab"]) if vocab_size is None else vocab_size, max_new,
@@ -490,7 +541,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
                     no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None, condition_on_previous_text=False,
                     prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
-                    prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None):
+                    prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
+                    patience=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings; hallucination_silence_threshold
     and clip_timestamps are not implemented.  condition_on_previous_text defaults to False here (openai-whisper: True);
     see 5.  word_timestamps: see 6.
@@ -526,6 +578,12 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        candidates per window in ONE wm_transcribe_mel_best_of call -- same seeds, same sample ids -- and hands
        fallback_decode each window's best candidate under length_penalty (rank_candidates; None = openai-whisper's None).
        The temperature-0 step is unchanged.  Every window record then has `candidate`, the index its last step kept.
+    8. beam_size (openai-whisper's beam_size, with patience; None: greedy): the temperature-0 step of every round is ONE
+       wm_transcribe_mel_beam call -- max_candidates = round(beam_size * patience), ranked under length_penalty -- and
+       hands fallback_decode each window's best hypothesis (sum_logprob: the search's own f32 sum); the steps above
+       temperature 0 are unchanged (openai-whisper uses beam_size at temperature 0 and best_of above it).  Every window
+       record then has `hypothesis`, the index that was kept (0 when a later step replaced the beam result).  patience
+       without beam_size is a ValueError; with beam_size None the calls made are exactly those without the argument.
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
     no prompt).  Without conditioning a recording's list heads every one of its windows; with it, it seeds the history.
     Sets the context's timestamp rules (wm_set_timestamp_rules: timestamp_begin, eot, max initial timestamp 1.0 s);
@@ -534,6 +592,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     text with a Vocab and words [{word, start, end, probability}] with word_timestamps), text (with a Vocab), seeks (the first frame of every decoded window) and windows (per window:
     seek, segment_size, the fallback steps' temperatures, skipped, prompt_len, prompt)."""
     R = len(recordings)
+    beam_max_candidates(beam_size, patience)
     rec_ids = list(range(R)) if recording_ids is None else [int(i) for i in recording_ids]
     if len(rec_ids) != R or any(i < 0 or i >= 65536 for i in rec_ids):
         raise ValueError("recording_ids: one per recording, each 0 .. 65535")
@@ -616,11 +675,15 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 prompts = np.array(plist, dtype=np.int32)
 
             cand = {}   # best_of: row of the round -> candidate kept by its last step
+            hyp = {}    # beam_size: row of the round -> hypothesis kept by its last step
 
             def decode(todo, t, sd):
                 rows = [live[i] for i in todo]
                 # (best_of None, or the temperature-0 step: exactly the call without candidates)
                 extra = dict(best_of=best_of, length_penalty=length_penalty) if best_of is not None and t > 0 else {}
+                beam = beam_size is not None and t == 0
+                if beam:
+                    extra = dict(beam_size=beam_size, patience=patience, length_penalty=length_penalty)
                 if ragged:
                     r_ = ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
                                             [size[i] for i in todo], [plist[i] for i in todo], max_new, eot=eot,
@@ -633,7 +696,10 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                             sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE, **extra)
                 if best_of is not None:
                     for k, i in enumerate(todo):
-                        cand[int(i)] = int(r_.candidate[k]) if extra else 0
+                        cand[int(i)] = int(r_.candidate[k]) if extra and not beam else 0
+                if beam_size is not None:
+                    for k, i in enumerate(todo):
+                        hyp[int(i)] = int(r_.hypothesis[k]) if beam else 0
                 return r_
             res = fallback_decode(decode, len(live), vocab_size, max_new, eot, temperatures, compression_ratio_threshold,
                                   logprob_threshold, no_speech_threshold, vocab, seed)
@@ -652,6 +718,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                               prompt_len=len(plist[i]), prompt=[int(t) for t in plist[i]]))
                 if best_of is not None:
                     out[r]["windows"][-1]["candidate"] = cand[i]
+                if beam_size is not None:
+                    out[r]["windows"][-1]["hypothesis"] = hyp[i]
                 if skip:
                     seek[r] += size[i]
                     continue
@@ -997,11 +1065,12 @@ class Context:
 
     def transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                                  compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
-                                 vocab=None, seed=0, no_speech_token=-1, sot_index=0, best_of=None, length_penalty=None):
+                                 vocab=None, seed=0, no_speech_token=-1, sot_index=0, best_of=None, length_penalty=None,
+                                 beam_size=None, patience=None):
         """openai-whisper's temperature fallback (module function transcribe_with_fallback) on this context."""
         return transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures, compression_ratio_threshold,
                                         logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index,
-                                        best_of=best_of, length_penalty=length_penalty)
+                                        best_of=best_of, length_penalty=length_penalty, beam_size=beam_size, patience=patience)
 
     def _mel_call_args(self, mel, mel_base, mel_len, seek, n_frames, prompts, opts, sample_ids, mem, prompt_len, sot_tail):
         """The arrays of a wm_transcribe_mel* call (the conventions of transcribe_mel_raw): (mel kept alive, its pointer,
@@ -1094,12 +1163,56 @@ class Context:
             _ptr(best), mem))
         return BestOfResult(toks, lens, lp, ns, best, eot)
 
+    def transcribe_mel_beam(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, beam_size, eot=-1, patience=None,
+                            no_speech_token=-1, sot_index=0, mem=WM_MEM_HOST, budgets=None, prompt_len=None, sot_tail=None,
+                            length_penalty=None, max_candidates=None):
+        """wm_transcribe_mel_beam: transcribe_mel's arguments (uniform or ragged prompts as in transcribe_mel_raw) decoded by
+        beam search with beam_size beams per row that share the row's encoder pass and cross-attention cache; max_candidates
+        defaults to openai-whisper's round(beam_size * patience) (patience None = 1.0); length_penalty None is
+        openai-whisper's None.  Returns a BeamResult."""
+        if max_candidates is None:
+            max_candidates = beam_max_candidates(beam_size, patience)
+        elif patience is not None:
+            raise ValueError("give patience or max_candidates, not both")
+        opts = wm_decode_opts(0.0, 0, int(no_speech_token), int(sot_index))
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        mel, mp, base, mlen, sk, nf, B, pr, plen, opts, _ = self._mel_call_args(mel, mel_base, mel_len, seek, n_frames, prompts,
+                                                                                opts, None, mem, prompt_len, sot_tail)
+        N, C = int(beam_size), int(max_candidates)
+        shape = (B, max(N, C, 1), max_new)
+        toks = np.empty(shape, dtype=np.int32)
+        lens = np.empty(shape[:2], dtype=np.int32)
+        n_hyp = np.empty(B, dtype=np.int32)
+        sums = np.empty(shape[:2], dtype=np.float32)
+        lp = np.empty(shape, dtype=np.float32)
+        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
+        best = np.empty(B, dtype=np.int32)
+        _check(self.lib, self.lib.wm_transcribe_mel_beam(
+            self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr), pr.shape[1],
+            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail), N, C,
+            float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts), _ptr(toks),
+            _ptr(lens), _ptr(n_hyp), _ptr(sums), _ptr(lp), _ptr(ns) if ns is not None else None, _ptr(best), mem))
+        return BeamResult(toks, lens, n_hyp, sums, lp, ns, best, eot)
+
     def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                        no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                       sot_tail=None, best_of=None, length_penalty=None):
+                       sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None):
         """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
         Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw.
-        best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`)."""
+        best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`).
+        beam_size (None: no beam search; with patience): transcribe_mel_beam at temperature 0 -- sample_ids and the seed play
+        no part -- and the result is its `selected` (with `hypothesis`)."""
+        if beam_size is not None or patience is not None:
+            if best_of is not None:
+                raise ValueError("beam_size and best_of exclude each other (openai-whisper)")
+            if temperature != 0:
+                raise ValueError("beam search decodes at temperature 0")
+            beam_max_candidates(beam_size, patience)
+            return self.transcribe_mel_beam(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, beam_size, eot=eot,
+                                            patience=patience, no_speech_token=no_speech_token, sot_index=sot_index, mem=mem,
+                                            budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail,
+                                            length_penalty=length_penalty).selected
         if best_of is not None:
             return self.transcribe_mel_best_of(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=eot,
                                                temperature=temperature, seed=seed, no_speech_token=no_speech_token,

@@ -317,6 +317,16 @@ static size_t dtype_size(wm_dtype t) {
     return 0;
 }
 
+// The MaximumLikelihoodRanker's score of one hypothesis: sum / n_text (an empty text counts as 1: the library's own rule
+// where openai-whisper divides by zero), or sum / ((5 + n_text) / 6) ** length_penalty.  wm_rank_candidates and
+// wm_transcribe_mel_beam's best_out.
+double wm_rank_score(double sum, int n_text, float length_penalty) {
+    double penalty;
+    if (std::isnan(length_penalty)) penalty = n_text > 0 ? (double)n_text : 1.0;
+    else penalty = pow((5.0 + (double)n_text) / 6.0, (double)length_penalty);
+    return sum / penalty;
+}
+
 // openai-whisper's MaximumLikelihoodRanker (whisper/decoding.py): host only, no context, no GPU
 extern "C" int wm_rank_candidates(const int32_t *tokens, const int32_t *lens, const float *token_logprobs, int B, int n_cand,
                                   int max_new, int32_t eot, float length_penalty, int32_t *best_out, double *score_out) try {
@@ -338,10 +348,7 @@ extern "C" int wm_rank_candidates(const int32_t *tokens, const int32_t *lens, co
             for (int i = 0; i < lens[r]; ++i) sum += (double)lp[i];
             int n_text = 0;
             while (n_text < lens[r] && t[n_text] != eot) ++n_text;
-            double penalty;
-            if (std::isnan(length_penalty)) penalty = n_text > 0 ? (double)n_text : 1.0;
-            else penalty = pow((5.0 + (double)n_text) / 6.0, (double)length_penalty);
-            const double score = sum / penalty;
+            const double score = wm_rank_score(sum, n_text, length_penalty);
             if (score_out) score_out[r] = score;
             if (score > best_score) { best_score = score; best = s; }   // the first maximal score; all -inf: candidate 0
         }

@@ -1,0 +1,506 @@
+// beam.hip -- the close of a generating position of a beam group (wm_transcribe_mel_beam): three
+// launches behind the decode step's DE_LOGITS_X product (which leaves the f32 logits and the filtered per-tile partials):
+//   * beam_topk_kernel   : per row, the log-sum-exp of the admissible ids and its N + 1 best tokens;
+//   * beam_select_kernel : per window, the selection rule of beam.h, the finished records, the rows' new state, the
+//                          embedding of the next position, the live list and the position advance;
+//   * beam_reorder_kernel: the self-attention K/V cache and the rows' histories gathered by source beam, in place.
+// A beam of width 1 must reproduce the greedy decode BIT FOR BIT (tokens, log-probs), so a row's close here is the
+// arithmetic of dec_kernels.hip's argmax_embed_body in its summation orders: the functions of the first block below restate
+// that kernel's inline code (16 fixed tile segments, one wave per row for the merges and the embedding).  They are restated,
+// not shared: moving any of them out of argmax_embed_body into a common function changed that kernel's machine code
+// (instruction counts of both instantiations), which this project pins; tests/test_beam_gpu.py holds the two to equal bits.
+#include "beam.h"
+#include "dec_close.h"
+#include "model.h"
+
+namespace {
+
+// ------------------------------------------------------------------ a row's close, as argmax_embed_body computes it ----
+// One wave's share of a row's 16 FIXED tile segments of the WmXDev partials: segments pi, pi + P, ... of the row whose
+// partials start at tile index rb; seg[sg] = allowed text (m, s), unfiltered (m, s) -- the latter merged when `sot` only.
+// Each segment has one summation order whatever P is.
+__device__ __forceinline__ void lse_row_segments(const WmXDev &xd, long rb, int n_tiles, bool sot, int pi, int P, int lane,
+                                                 float (*seg)[4]) {
+    const int cs = (n_tiles + 15) / 16;
+    for (int sg = pi; sg < 16; sg += P) {
+        const int lo = sg * cs, hi = lo + cs < n_tiles ? lo + cs : n_tiles;
+        const Lse none{-1e30f, 0.f};
+        Lse a = none, c = none;
+        for (int t0 = lo + lane; t0 < hi; t0 += 64 * 4) {
+            Lse va0 = none, va1 = none, va2 = none, va3 = none, vc0 = none, vc1 = none, vc2 = none, vc3 = none;
+            if (t0 < hi) va0 = lse_load(xd.txt + (rb + t0) * 2);
+            if (t0 + 64 < hi) va1 = lse_load(xd.txt + (rb + t0 + 64) * 2);
+            if (t0 + 128 < hi) va2 = lse_load(xd.txt + (rb + t0 + 128) * 2);
+            if (t0 + 192 < hi) va3 = lse_load(xd.txt + (rb + t0 + 192) * 2);
+            if (sot) {   // wave-uniform
+                if (t0 < hi) vc0 = lse_load(xd.all + (rb + t0) * 2);
+                if (t0 + 64 < hi) vc1 = lse_load(xd.all + (rb + t0 + 64) * 2);
+                if (t0 + 128 < hi) vc2 = lse_load(xd.all + (rb + t0 + 128) * 2);
+                if (t0 + 192 < hi) vc3 = lse_load(xd.all + (rb + t0 + 192) * 2);
+            }
+            a = lse_merge(lse_merge(lse_merge(lse_merge(a, va0), va1), va2), va3);
+            c = lse_merge(lse_merge(lse_merge(lse_merge(c, vc0), vc1), vc2), vc3);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            a = lse_merge(a, lse_shfl_xor(a, o));
+            c = lse_merge(c, lse_shfl_xor(c, o));
+        }
+        if (lane == 0) {
+            seg[sg][0] = a.m; seg[sg][1] = a.s;
+            seg[sg][2] = c.m; seg[sg][3] = c.s;
+        }
+    }
+}
+
+// The row's 16 segments merged in a fixed order (one wave): lt = allowed text, la = unfiltered; every lane gets both.
+__device__ __forceinline__ void lse_row_total(const float (*seg)[4], int lane, Lse &lt, Lse &la) {
+    if (lane < 16) {
+        lt.m = seg[lane][0]; lt.s = seg[lane][1];
+        la.m = seg[lane][2]; la.s = seg[lane][3];
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+        lt = lse_merge(lt, lse_shfl_xor(lt, o));
+        la = lse_merge(la, lse_shfl_xor(la, o));
+    }
+    lt = Lse{__shfl(lt.m, 0), __shfl(lt.s, 0)};
+    la = Lse{__shfl(la.m, 0), __shfl(la.s, 0)};
+}
+
+// Row b's timestamp tiles merged by one wave: the best allowed timestamp key and (M, S) = (max, sum exp(v - M)) over the
+// allowed timestamps; every lane gets all three.
+__device__ __forceinline__ void ts_row_merge(const WmTsDev &ts, int b, int n_tiles, int lane, unsigned long long &kts, float &M,
+                                             float &S) {
+    const int t_first = ts.ts_begin >> 4;
+    kts = 0ull;
+    M = -1e30f;
+    for (int t = t_first + lane; t < n_tiles; t += 64) {
+        const unsigned long long k2 = ts.key_ts[(long)b * n_tiles + t];
+        kts = k2 > kts ? k2 : kts;
+        M = fmaxf(M, ts.lse[((long)b * n_tiles + t) * 2]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long ok = __shfl_xor(kts, o);
+        kts = ok > kts ? ok : kts;
+        M = fmaxf(M, __shfl_xor(M, o));
+    }
+    S = 0.f;
+    for (int t = t_first + lane; t < n_tiles; t += 64) {
+        const float2 ms = *(const float2 *)(ts.lse + ((long)b * n_tiles + t) * 2);
+        S += ms.y * __expf(ms.x - M);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
+}
+
+// `tok` was sampled for a row whose timestamp-rule history is hs[4] (n_sampled, last_is_ts, prev_is_ts, last_ts): advance
+// the history in place and return the ranges (text_lo, text_hi, ts_lo, ts_hi) of the next position.
+__device__ __forceinline__ int4 ts_advance(const WmTsDev &ts, int *hs, int tok) {
+    const int n_s = hs[0] + 1;
+    const bool prev_ts = hs[0] < 1 || hs[1] != 0;  // penultimate_was_timestamp = len(seq) < 2 or seq[-2] >= begin
+    const bool last_ts = tok >= ts.ts_begin;
+    const int last_val = last_ts ? tok : hs[3];
+    hs[0] = n_s; hs[2] = hs[1]; hs[1] = last_ts ? 1 : 0; hs[3] = last_val;
+    int text_lo = 0, text_hi = ts.ts_begin, ts_lo = ts.ts_begin, ts_hi = ts.n_vocab;
+    if (last_ts) {
+        if (prev_ts) ts_hi = ts_lo;        // a pair was just closed: the next token is not a timestamp
+        else text_lo = ts.eot;             // an opening timestamp needs its partner (or <|endoftext|>)
+    }
+    if (last_val >= 0) {                   // timestamps never decrease (and advance unless closing a pair)
+        const int floor_ts = (last_ts && !prev_ts) ? last_val : last_val + 1;
+        ts_lo = floor_ts > ts_lo ? floor_ts : ts_lo;
+    }
+    return make_int4(text_lo, text_hi, ts_lo, ts_hi);
+}
+
+// One wave embeds token `tok` at positional row `prow` into row b of the residual stream: x (f32), its mean-centred bf16
+// copy xb (WL_TILED order), the row mean and the LayerNorm partial statistics the next layer-0 GEMV expects.
+__device__ __forceinline__ void embed_row(long tok, int prow, int b, int lane, const bf16_t *__restrict__ emb,
+                                          const float *__restrict__ pemb, int d, float *__restrict__ x, bf16_t *__restrict__ xb,
+                                          float *__restrict__ stats_out, float *__restrict__ mean_buf) {
+    float s1 = 0.f, s2 = 0.f;
+    // the row stays in registers between the sums and the mean-centred bf16 copy (the first 512 columns: 8 values per lane; the
+    // round-4 kernel re-read what it had just stored: a store -> load round trip through L2 on the step's tail)
+    constexpr int EV = 8;   // (d <= 512 entirely: tiny, base -- where a step is 35 launches and this trip is 0.5 % of it)
+    float ev[EV];
+#pragma unroll
+    for (int i = 0; i < EV; ++i) {
+        const int j = lane + 64 * i;
+        ev[i] = 0.f;
+        if (j < d) {
+            const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
+            x[(long)b * d + j] = v;
+            ev[i] = v;
+            s1 += v;
+            s2 += v * v;
+        }
+    }
+    for (int j = lane + 64 * EV; j < d; j += 64) {  // (wider models than any Whisper: the re-reading path)
+        const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
+        x[(long)b * d + j] = v;
+        s1 += v;
+        s2 += v * v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o);
+        s2 += __shfl_xor(s2, o);
+    }
+    {   // bf16 copy, mean-centred (see DecGemvDev::mean_in)
+        const float mean = s1 / (float)d;
+#pragma unroll
+        for (int i = 0; i < EV; ++i) {
+            const int j = lane + 64 * i;
+            if (j < d) xb[wm_tiled_offset((size_t)b, (size_t)j, (size_t)d)] = f2bf(ev[i] - mean);
+        }
+        for (int j = lane + 64 * EV; j < d; j += 64)
+            xb[wm_tiled_offset((size_t)b, (size_t)j, (size_t)d)] = f2bf(x[(long)b * d + j] - mean);
+        if (lane == 0 && mean_buf) mean_buf[b] = mean;
+    }
+    if (stats_out) {  // one part (index 0) carries the row; the other d/16 - 1 parts the consumers sum are zero
+        float *blk = stats_out + (long)(b >> 4) * (2 * d) + (b & 15) * 2;
+        for (int pt = 1 + lane; pt < d / 16; pt += 64) *(float2 *)(blk + pt * 32) = make_float2(0.f, 0.f);
+        if (lane == 0) *(float2 *)blk = make_float2(s1, s2);
+    }
+}
+
+// ------------------------------------------------------------------ per-row list ------------------------------------
+// One 16-wave workgroup per row.  The reductions are maxima (any order, same bits) except the log-sum-exp, which follows
+// the fixed orders above: a row's list does not depend on the group's shape.
+__global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict__ logits, long ldo, int V, int n_tiles,
+                                                         const unsigned long long *__restrict__ tilemax, WmTsDev ts, WmXDev xd,
+                                                         const unsigned *__restrict__ mask, int mask_words, int n_prompt,
+                                                         const int *__restrict__ pos_ptr, WmBeamDev bm) {
+    __shared__ float seg_s[16][4];
+    __shared__ unsigned long long red_s[2][16];
+    __shared__ float norm_s;
+    __shared__ int forced_s;
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pos = *pos_ptr, gi = pos + 1 - n_prompt;
+    const int K = bm.N + 1;
+    const float my_sum = bm.sum[b];
+    float *tr = bm.trace ? bm.trace + ((long)gi * gridDim.x + b) * WM_BEAM_TRACE : nullptr;
+    if (bm.wdone[b / bm.N] || my_sum == -INFINITY) {   // workgroup-uniform: the window has left, or a dead beam
+        if (threadIdx.x == 0) {
+            bm.list_n[b] = 0;
+            if (tr) { tr[0] = __int_as_float(0); tr[1] = my_sum; }
+        }
+        return;
+    }
+    const long rb = (long)b * n_tiles;
+    const bool sot = pos == xd.par->sot_pos;
+    lse_row_segments(xd, rb, n_tiles, sot, wave, 16, lane, seg_s);
+    {   // the best allowed text key of the row (decides the sum rule with the timestamps' log-sum-exp)
+        unsigned long long key = 0ull;
+        for (int t = threadIdx.x; t < n_tiles; t += 1024) {
+            const unsigned long long k = tilemax[rb + t];
+            key = k > key ? k : key;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ok = __shfl_xor(key, o);
+            key = ok > key ? ok : key;
+        }
+        if (lane == 0) red_s[0][wave] = key;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f}, lts{-1e30f, 0.f};
+        lse_row_total(seg_s, lane, lt, la);
+        unsigned long long key = lane < 16 ? red_s[0][lane] : 0ull;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+            const unsigned long long ok = __shfl_xor(key, o);
+            key = ok > key ? ok : key;
+        }
+        key = __shfl(key, 0);
+        bool forced = false;
+        if (ts.rng) {   // "if sum of probability over timestamps is above any other token, sample timestamp", on raw logits
+            unsigned long long kts;
+            float M, S;
+            ts_row_merge(ts, b, n_tiles, lane, kts, M, S);
+            const float text_best = key ? lt.m : -1e30f;
+            const float lse = S > 0.f ? M + __logf(S) : -1e30f;
+            lts = Lse{M, S};
+            forced = kts != 0ull && (key == 0ull || lse > text_best);
+        }
+        Lse al = lt;
+        if (forced) al = lts;
+        else if (ts.rng) al = lse_merge(lt, lts);
+        if (lane == 0) {
+            norm_s = al.m + __logf(al.s);
+            forced_s = forced ? 1 : 0;
+            if (sot) xd.nospeech[b] = __expf(xd.ns_v[b] - la.m) / la.s;
+        }
+    }
+    __syncthreads();
+    const float norm = norm_s;
+    const bool forced = forced_s != 0;
+    // a thread's ids are n = tid + 1024 i; its best admissible key below `bound` (the keys at and above the last listed one are
+    // taken: the list is built in descending key order).  Every thread scans once; afterwards only a round's winner rescans.
+    int4 rng = make_int4(0, V, 0, 0);
+    if (ts.rng) rng = *(const int4 *)(ts.rng + b * 4);
+    const unsigned *mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
+    auto local_best = [&](unsigned long long bound) {
+        unsigned long long best = 0ull;
+        for (int n = threadIdx.x; n < V; n += 1024) {
+            const bool in_text = !forced && n >= rng.x && n < rng.y, in_ts = n >= rng.z && n < rng.w;
+            if (!(in_text || in_ts) || (mrow && ((mrow[n >> 5] >> (n & 31)) & 1u))) continue;
+            const unsigned long long k = argmax_key(logits[(long)b * ldo + n], n);
+            if (k < bound && k > best) best = k;
+        }
+        return best;
+    };
+    unsigned long long mine = local_best(~0ull);
+    int count = 0;
+    for (int r = 0; r < K; ++r) {   // K rounds of a workgroup-wide maximum; the winner's thread retires it
+        unsigned long long key = mine;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ok = __shfl_xor(key, o);
+            key = ok > key ? ok : key;
+        }
+        if (lane == 0) red_s[(r + 1) & 1][wave] = key;
+        __syncthreads();
+        key = lane < 16 ? red_s[(r + 1) & 1][lane] : 0ull;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+            const unsigned long long ok = __shfl_xor(key, o);
+            key = ok > key ? ok : key;
+        }
+        key = __shfl(key, 0);
+        if (key == 0ull) break;                       // nothing admissible is left (uniform)
+        const float lp = argmax_key_value(key) - norm;
+        if (!(lp > -INFINITY)) break;                 // -inf (and NaN) is never listed (uniform)
+        if (threadIdx.x == 0) {
+            bm.list_tok[b * WM_BEAM_LIST + r] = argmax_key_index(key);
+            bm.list_lp[b * WM_BEAM_LIST + r] = lp;
+            if (tr) { tr[2 + r] = __int_as_float(argmax_key_index(key)); tr[2 + WM_BEAM_LIST + r] = lp; }
+        }
+        ++count;
+        if (mine == key) mine = local_best(key);
+    }
+    if (threadIdx.x == 0) {
+        bm.list_n[b] = count;
+        if (tr) { tr[0] = __int_as_float(count); tr[1] = my_sum; }
+    }
+}
+
+// ------------------------------------------------------------------ per-window step ---------------------------------
+// ONE workgroup: wave v takes windows v, v + 16, ...; nothing is handed between workgroups.
+__global__ __launch_bounds__(1024) void beam_select_kernel(int B, int *__restrict__ seq, int *__restrict__ pos_ptr, int n_prompt,
+                                                           const bf16_t *__restrict__ emb, const float *__restrict__ pemb, int d,
+                                                           float *__restrict__ x, bf16_t *__restrict__ xb,
+                                                           float *__restrict__ stats_out, float *__restrict__ mean_buf, WmTsDev ts,
+                                                           WmStopDev stop, WmXDev xd, const int *__restrict__ off, WmBeamDev bm) {
+    __shared__ WmBeamStep step_s[16];
+    __shared__ float sum_s[16][WM_MAX_BEAM], lp_s[16][WM_MAX_BEAM * WM_BEAM_LIST];
+    __shared__ int ln_s[16][WM_MAX_BEAM], tok_s[16][WM_MAX_BEAM * WM_BEAM_LIST];
+    __shared__ __align__(16) int hist_s[16][WM_MAX_BEAM][4];
+    __shared__ int done_s[WM_DEC_MAXB];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pos = *pos_ptr, gi = pos + 1 - n_prompt, N = bm.N, C = B / N;
+    const WmBeamPar par = *bm.par;
+    for (int w = wave; w < C; w += 16) {   // wave-uniform
+        const int row0 = w * N;
+        const bool was_done = bm.wdone[w] != 0;
+        WmBeamStep &st = step_s[wave];
+        if (was_done) {   // the window has left: padding, nothing moves
+            if (lane < N) {
+                seq[(pos + 1) * B + row0 + lane] = par.pad;
+                xd.logprob[(long)gi * B + row0 + lane] = 0.f;
+                bm.src[row0 + lane] = lane;
+                done_s[row0 + lane] = 1;
+                st.tok[lane] = par.pad;
+            }
+        } else {
+            if (lane < N) {
+                sum_s[wave][lane] = bm.sum[row0 + lane];
+                ln_s[wave][lane] = bm.list_n[row0 + lane];
+                if (ts.rng) *(int4 *)hist_s[wave][lane] = *(const int4 *)(ts.hist + (row0 + lane) * 4);
+            }
+            for (int e = lane; e < N * WM_BEAM_LIST; e += 64) {
+                tok_s[wave][e] = bm.list_tok[row0 * WM_BEAM_LIST + e];
+                lp_s[wave][e] = bm.list_lp[row0 * WM_BEAM_LIST + e];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int nfin0 = bm.fin_n[w];
+            if (lane == 0)
+                wm_beam_select(N, gi == 0 ? 1 : N, par.eot, par.pad, par.max_cand - nfin0, sum_s[wave], ln_s[wave], tok_s[wave],
+                               lp_s[wave], &st);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // newly finished hypotheses: the source beam's history, then eot
+            for (int f = 0; f < st.n_fin; ++f) {
+                const int slot = nfin0 + f, srow = row0 + st.fin_src[f];
+                const long base = ((long)w * WM_MAX_BEAM_HYPS + slot) * bm.n_ctx;
+                for (int i = lane; i < gi; i += 64) {
+                    bm.fin_tok[base + i] = seq[(n_prompt + i) * B + srow];
+                    bm.fin_lp[base + i] = xd.logprob[(long)i * B + srow];
+                }
+                if (lane == 0) {
+                    bm.fin_tok[base + gi] = par.eot;
+                    bm.fin_lp[base + gi] = st.fin_lp[f];
+                    bm.fin_len[w * WM_MAX_BEAM_HYPS + slot] = gi + 1;
+                    bm.fin_sum[w * WM_MAX_BEAM_HYPS + slot] = st.fin_sum[f];
+                }
+            }
+            const int nfin = nfin0 + st.n_fin;
+            const bool leaves = nfin >= par.max_cand || gi + 1 >= bm.budget[w];
+            if (lane < N) {
+                const int row = row0 + lane, tok = st.tok[lane];
+                seq[(pos + 1) * B + row] = tok;
+                xd.logprob[(long)gi * B + row] = st.lp[lane];
+                bm.sum[row] = st.sum[lane];
+                bm.src[row] = st.src[lane];
+                if (ts.rng) {   // the timestamp-rule state follows the source beam
+                    __align__(16) int hs[4];
+                    *(int4 *)hs = *(const int4 *)hist_s[wave][st.src[lane]];
+                    const int4 rng = ts_advance(ts, hs, tok);
+                    *(int4 *)(ts.hist + row * 4) = *(const int4 *)hs;
+                    *(int4 *)(ts.rng + row * 4) = rng;
+                }
+                done_s[row] = (leaves || st.sum[lane] == -INFINITY) ? 1 : 0;
+            }
+            if (lane == 0) {
+                bm.fin_n[w] = nfin;
+                bm.wdone[w] = leaves ? 1 : 0;
+                bm.wsteps[w] = gi + 1;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // st.tok: written by the lanes above, read by every lane
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (pos + 1 < bm.n_ctx) {
+            for (int k = 0; k < N; ++k) {
+                const int row = row0 + k;
+                // a ragged group (off != null): the row's prompt starts at position off[row], its positional row counts from there
+                const int prow = off ? max(pos + 1 - off[row], 0) : pos + 1;
+                embed_row((long)st.tok[k], prow, row, lane, emb, pemb, d, x, xb, stats_out, mean_buf);
+            }
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        if (stop.done) {   // early stop: the flags and the compact list of live rows the attention kernels walk
+            int n = 0;
+            for (int b0 = 0; b0 < B; b0 += 64) {
+                const int b = b0 + lane;
+                const bool live = b < B && done_s[b < B ? b : 0] == 0;
+                if (b < B) stop.done[b] = live ? 0 : 1;
+                const unsigned long long m = __ballot(live);
+                if (live) stop.live_rows[n + __popcll(m & ((1ull << lane) - 1ull))] = b;
+                n += __popcll(m);
+            }
+            if (lane == 0) *stop.n_live = n;
+        }
+        if (lane == 0) *pos_ptr = pos + 1;
+    }
+}
+
+// ------------------------------------------------------------------ re-parenting ------------------------------------
+// grid (H, L2 + 1, windows).  y < L2: the 128-byte rows [0, p] of one (layer, K or V, head) of a window's N beams, 16 bytes per
+// thread: a thread reads its unit of every source row before it writes it to any row, and no other thread touches that
+// unit, so the gather is safe in place.  y == L2 (x == 0): the token and log-prob histories, one position per thread.
+// p = *pos_ptr - 1, the position wm_beam_select_step has just closed.
+template <int N>
+__global__ __launch_bounds__(256) void beam_reorder_kernel(bf16_t *__restrict__ skv, int L2, int rows, int H, int T,
+                                                           const int *__restrict__ pos_ptr, int n_prompt, int *__restrict__ seq,
+                                                           float *__restrict__ logprob, WmBeamDev bm) {
+    const int w = blockIdx.z, row0 = w * N;
+    int s[N];
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        s[k] = bm.src[row0 + k];
+        same = same && s[k] == k;
+    }
+    if (same) return;   // (a window that left earlier, a step that kept every beam in place: nothing moves)
+    const int p = *pos_ptr - 1, gi = p + 1 - n_prompt;
+    if ((int)blockIdx.y == L2) {
+        if (blockIdx.x != 0) return;
+        for (int i = threadIdx.x; i < gi; i += 256) {   // (index gi is the new token, written in the new order already)
+            int tk[N];
+            float lp[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                tk[k] = seq[(n_prompt + i) * rows + row0 + s[k]];
+                lp[k] = logprob[(long)i * rows + row0 + s[k]];
+            }
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                if (s[k] == k) continue;
+                seq[(n_prompt + i) * rows + row0 + k] = tk[k];
+                logprob[(long)i * rows + row0 + k] = lp[k];
+            }
+        }
+        return;
+    }
+    if (bm.wdone[w]) return;   // the window has just left: its caches are not read again
+    const size_t slice = (size_t)T * 64;   // elements of one (row, head)
+    uint4 *base = (uint4 *)(skv + (((size_t)blockIdx.y * rows + row0) * H + blockIdx.x) * slice);
+    const size_t row_u = (size_t)H * slice / 8;   // 16-byte units between consecutive rows
+    const int n_u = (p + 1) * 8;
+    for (int q = threadIdx.x; q < n_u; q += 256) {
+        uint4 v[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            v[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (s[k] != k) v[k] = base[(size_t)s[k] * row_u + q];
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if (s[k] != k) base[(size_t)k * row_u + q] = v[k];
+    }
+}
+
+}  // namespace
+
+int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
+                 const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
+                 const WmBeamDev &bm) {
+    WmProfScope ps(&ctx->prof, "beam_topk", ctx->stream);
+    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && bm.N >= 1 && bm.N <= WM_MAX_BEAM && rows % bm.N == 0 && xd.par, WM_ERR_INVALID,
+               "beam_topk: bad group");
+    beam_topk_kernel<<<rows, 1024, 0, ctx->stream>>>(logits, ldo, n_vocab, (n_vocab + 15) / 16, tilemax, ts, xd, mask, mask_words,
+                                                     n_prompt, pos_ptr, bm);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const bf16_t *emb, const float *pemb, int d,
+                        float *x, bf16_t *xb, float *stats_out, float *mean_buf, const WmTsDev &ts, const WmStopDev &stop,
+                        const WmXDev &xd, const int *off, const WmBeamDev &bm) {
+    WmProfScope ps(&ctx->prof, "beam_select", ctx->stream);
+    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && bm.N >= 1 && bm.N <= WM_MAX_BEAM && rows % bm.N == 0 && xd.par, WM_ERR_INVALID,
+               "beam_select: bad group");
+    beam_select_kernel<<<1, 1024, 0, ctx->stream>>>(rows, seq, pos_ptr, n_prompt, emb, pemb, d, x, xb, stats_out, mean_buf, ts, stop,
+                                                    xd, off, bm);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, const int *pos_ptr, int n_prompt, int *seq,
+                    float *logprob, const WmBeamDev &bm) {
+    WmProfScope ps(&ctx->prof, "beam_reorder", ctx->stream);
+    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && bm.N >= 1 && bm.N <= WM_MAX_BEAM && rows % bm.N == 0, WM_ERR_INVALID,
+               "beam_reorder: bad group");
+    if (bm.N == 1) return WM_OK;   // one beam per window: its source is itself
+    const dim3 grid(H, L2 + 1, rows / bm.N);
+#define WM_BEAM_REORDER_CASE(n)                                                                                            \
+    case n:                                                                                                                \
+        beam_reorder_kernel<n><<<grid, 256, 0, ctx->stream>>>(skv, L2, rows, H, T, pos_ptr, n_prompt, seq, logprob, bm);   \
+        break;
+    switch (bm.N) {
+        WM_BEAM_REORDER_CASE(2) WM_BEAM_REORDER_CASE(3) WM_BEAM_REORDER_CASE(4) WM_BEAM_REORDER_CASE(5)
+        WM_BEAM_REORDER_CASE(6) WM_BEAM_REORDER_CASE(7) WM_BEAM_REORDER_CASE(8)
+    }
+#undef WM_BEAM_REORDER_CASE
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}

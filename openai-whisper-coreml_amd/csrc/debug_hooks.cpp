@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/whisper_mi355x_debug.h"
+#include "beam.h"
 #include "model.h"
 
 // ---------------------------------------------------------------- host-only test hooks
@@ -808,5 +809,162 @@ extern "C" int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, i
         WM_HIP(hipStreamSynchronize(s));
     }
     for (void *p : {dl, di, dp}) (void)hipFree(p);
+    return rc;
+}
+
+// ------------------------------------------------------------------ beam search ----
+extern "C" int wmdbg_beam_select(int N, int n_from, int32_t eot, int32_t pad, int room, const float *sum, const int32_t *list_n,
+                                 const int32_t *list_tok, const float *list_lp, int32_t *n_next, int32_t *src, int32_t *tok,
+                                 float *lp, float *new_sum, int32_t *n_fin, int32_t *fin_src, float *fin_lp, float *fin_sum) {
+    WM_REQUIRE(N >= 1 && N <= WM_MAX_BEAM && n_from >= 1 && n_from <= N, WM_ERR_INVALID, "beam_select: N 1..%d, n_from 1..N", WM_MAX_BEAM);
+    WM_REQUIRE(sum && list_n && list_tok && list_lp && n_next && src && tok && lp && new_sum && n_fin && fin_src && fin_lp && fin_sum,
+               WM_ERR_INVALID, "beam_select: null pointer");
+    for (int j = 0; j < N; ++j)
+        WM_REQUIRE(list_n[j] >= 0 && list_n[j] <= WM_BEAM_LIST, WM_ERR_INVALID, "beam_select: list_n[%d] = %d", j, list_n[j]);
+    WmBeamStep st;
+    wm_beam_select(N, n_from, eot, pad, room, sum, list_n, list_tok, list_lp, &st);
+    *n_next = st.n_next;
+    *n_fin = st.n_fin;
+    for (int k = 0; k < N; ++k) { src[k] = st.src[k]; tok[k] = st.tok[k]; lp[k] = st.lp[k]; new_sum[k] = st.sum[k]; }
+    for (int f = 0; f < st.n_fin; ++f) { fin_src[f] = st.fin_src[f]; fin_lp[f] = st.fin_lp[f]; fin_sum[f] = st.fin_sum[f]; }
+    return WM_OK;
+}
+
+extern "C" double wmdbg_rank_score(double sum, int n_text, float length_penalty) { return wm_rank_score(sum, n_text, length_penalty); }
+
+extern "C" int wmdbg_beam_fill_order(int N, const float *sum, int32_t *order_out) {
+    if (N < 1 || N > WM_MAX_BEAM || !sum || !order_out) return -1;
+    return wm_beam_fill_order(N, sum, order_out);
+}
+
+extern "C" int wmdbg_beam_trace(wm_ctx *ctx, float *trace_out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(ctx->model && trace_out, WM_ERR_INVALID, "bad args");
+    ctx->model->beam_dbg_trace = trace_out;
+    return WM_OK;
+}
+
+// The partials a DE_LOGITS_X launch leaves for a row, restated on the host: per 16-id tile the best allowed text / timestamp
+// key and the (max, sum exp) of the allowed text ids / timestamps.
+static unsigned long long host_key(float v, int n) {
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
+}
+
+extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V, int N, const int32_t *suppress, int n_suppress,
+                               const int32_t *rng, int32_t ts_begin, int32_t *list_n, int32_t *list_tok, float *list_lp) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(logits && list_n && list_tok && list_lp && rows >= 1 && rows <= WM_DEC_MAXB && V >= 16 && N >= 1 && N <= WM_MAX_BEAM &&
+                   rows % N == 0 && n_suppress >= 0 && (n_suppress == 0 || suppress) && (!rng || (ts_begin >= 0 && ts_begin <= V)),
+               WM_ERR_INVALID, "beam_topk: bad args");
+    const int vpad = (V + 15) / 16 * 16, nt = vpad / 16, mw = (vpad + 31) / 32;
+    std::vector<unsigned> mask((size_t)2 * mw, 0u);
+    for (int i = 0; i < n_suppress; ++i) {
+        WM_REQUIRE(suppress[i] >= 0 && suppress[i] < V, WM_ERR_INVALID, "beam_topk: suppressed id %d", suppress[i]);
+        mask[suppress[i] >> 5] |= 1u << (suppress[i] & 31);
+    }
+    std::vector<float> lg((size_t)rows * vpad, 0.f), txt((size_t)rows * nt * 2), tsl((size_t)rows * nt * 2);
+    std::vector<unsigned long long> kt((size_t)rows * nt, 0ull), ks((size_t)rows * nt, 0ull);
+    for (int b = 0; b < rows; ++b) {
+        memcpy(&lg[(size_t)b * vpad], logits + (size_t)b * V, (size_t)V * 4);
+        const int32_t *r = rng ? rng + b * 4 : nullptr;
+        for (int t = 0; t < nt; ++t) {
+            float mx = -1e30f, mt = -1e30f;
+            for (int pass = 0; pass < 2; ++pass) {
+                float se = 0.f, st = 0.f;
+                for (int n = t * 16; n < t * 16 + 16 && n < V; ++n) {
+                    if ((mask[n >> 5] >> (n & 31)) & 1u) continue;
+                    const float v = logits[(size_t)b * V + n];
+                    const bool in_text = r ? (n >= r[0] && n < r[1]) : true, in_ts = r && n >= r[2] && n < r[3];
+                    if (pass == 0) {
+                        if (in_text) { mx = std::max(mx, v); kt[(size_t)b * nt + t] = std::max(kt[(size_t)b * nt + t], host_key(v, n)); }
+                        if (in_ts) { mt = std::max(mt, v); ks[(size_t)b * nt + t] = std::max(ks[(size_t)b * nt + t], host_key(v, n)); }
+                    } else {
+                        if (in_text) se += expf(v - mx);
+                        if (in_ts) st += expf(v - mt);
+                    }
+                }
+                if (pass == 1) {
+                    txt[((size_t)b * nt + t) * 2] = mx; txt[((size_t)b * nt + t) * 2 + 1] = se;
+                    tsl[((size_t)b * nt + t) * 2] = mt; tsl[((size_t)b * nt + t) * 2 + 1] = st;
+                }
+            }
+        }
+    }
+    hipStream_t s = ctx->stream;
+    const int L = WM_MAX_BEAM + 1;
+    std::vector<int32_t> ints(2);   // pos, then the beam parameters are not read by this kernel
+    ints[0] = 0; ints[1] = 0;
+    WmXPar xp;
+    memset(&xp, 0, sizeof(xp));
+    xp.sot_pos = -1;
+    void *dlg, *dtxt, *dtsl, *dkt, *dks, *dmask, *drng = nullptr, *dpos, *dxp, *dsum, *dwd, *dln, *dlt, *dlp;
+    WM_TRY(up(&dlg, lg.data(), lg.size() * 4, s));
+    WM_TRY(up(&dtxt, txt.data(), txt.size() * 4, s));
+    WM_TRY(up(&dtsl, tsl.data(), tsl.size() * 4, s));
+    WM_TRY(up(&dkt, kt.data(), kt.size() * 8, s));
+    WM_TRY(up(&dks, ks.data(), ks.size() * 8, s));
+    WM_TRY(up(&dmask, mask.data(), mask.size() * 4, s));
+    if (rng) WM_TRY(up(&drng, rng, (size_t)rows * 16, s));
+    WM_TRY(up(&dpos, ints.data(), 8, s));
+    WM_TRY(up(&dxp, &xp, sizeof(xp), s));
+    WM_TRY(up(&dsum, nullptr, (size_t)rows * 4, s));
+    WM_TRY(up(&dwd, nullptr, (size_t)rows * 4, s));
+    WM_TRY(up(&dln, nullptr, (size_t)rows * 4, s));
+    WM_TRY(up(&dlt, nullptr, (size_t)rows * L * 4, s));
+    WM_TRY(up(&dlp, nullptr, (size_t)rows * L * 4, s));
+    WmTsDev ts;
+    memset(&ts, 0, sizeof(ts));
+    if (rng) { ts.rng = (int *)drng; ts.key_ts = (unsigned long long *)dks; ts.lse = (float *)dtsl; ts.ts_begin = ts_begin; ts.n_vocab = V; }
+    WmXDev xd;
+    memset(&xd, 0, sizeof(xd));
+    xd.par = (const WmXPar *)dxp; xd.txt = (float *)dtxt;
+    WmBeamDev bm;
+    memset(&bm, 0, sizeof(bm));
+    bm.N = N; bm.sum = (float *)dsum; bm.wdone = (int *)dwd; bm.list_n = (int *)dln; bm.list_tok = (int *)dlt; bm.list_lp = (float *)dlp;
+    // n_prompt 2 at position 0: not the first generated token, so the every-position bitmap applies
+    int rc = wm_beam_topk(ctx, (const float *)dlg, vpad, V, (const unsigned long long *)dkt, rows, ts, xd, (const unsigned *)dmask, mw, 2,
+                          (const int *)dpos, bm);
+    if (rc == WM_OK) {
+        WM_HIP(hipMemcpyAsync(list_n, dln, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(list_tok, dlt, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(list_lp, dlp, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    }
+    for (void *p : {dlg, dtxt, dtsl, dkt, dks, dmask, drng, dpos, dxp, dsum, dwd, dln, dlt, dlp})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows, int H, int T, int N, int pos, int n_prompt,
+                                  const int32_t *src, const int32_t *wdone, int32_t *seq, float *logprob) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(cache && src && wdone && seq && logprob && L2 >= 1 && H >= 1 && T >= 1 && N >= 1 && N <= WM_MAX_BEAM && rows >= 1 &&
+                   rows <= WM_DEC_MAXB && rows % N == 0 && pos >= 0 && pos < T && n_prompt >= 1 && n_prompt <= pos + 1,
+               WM_ERR_INVALID, "beam_reorder: bad args");
+    for (int b = 0; b < rows; ++b) WM_REQUIRE(src[b] >= 0 && src[b] < N, WM_ERR_INVALID, "beam_reorder: src[%d] = %d", b, src[b]);
+    hipStream_t s = ctx->stream;
+    const size_t nc = (size_t)L2 * rows * H * T * 64;
+    const int after = pos + 1;   // the kernel runs behind the position advance
+    void *dc, *dsrc, *dwd, *dseq, *dlp, *dpos;
+    WM_TRY(up(&dc, cache, nc * 2, s));
+    WM_TRY(up(&dsrc, src, (size_t)rows * 4, s));
+    WM_TRY(up(&dwd, wdone, (size_t)(rows / N) * 4, s));
+    WM_TRY(up(&dseq, seq, (size_t)T * rows * 4, s));
+    WM_TRY(up(&dlp, logprob, (size_t)T * rows * 4, s));
+    WM_TRY(up(&dpos, &after, 4, s));
+    WmBeamDev bm;
+    memset(&bm, 0, sizeof(bm));
+    bm.N = N; bm.src = (int *)dsrc; bm.wdone = (int *)dwd;
+    int rc = wm_beam_reorder(ctx, (bf16_t *)dc, L2, rows, H, T, (const int *)dpos, n_prompt, (int *)dseq, (float *)dlp, bm);
+    if (rc == WM_OK) {
+        WM_HIP(hipMemcpyAsync(cache, dc, nc * 2, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(seq, dseq, (size_t)T * rows * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(logprob, dlp, (size_t)T * rows * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    }
+    for (void *p : {dc, dsrc, dwd, dseq, dlp, dpos}) (void)hipFree(p);
     return rc;
 }

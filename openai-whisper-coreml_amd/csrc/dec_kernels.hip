@@ -28,6 +28,7 @@
 #include <atomic>
 #include <string.h>
 
+#include "dec_close.h"
 #include "model.h"
 #include "philox.h"
 
@@ -40,12 +41,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
-// f32 -> bf16 round-to-nearest-even: v_cvt_pk_bf16_f32 on gfx950
-__device__ __forceinline__ bf16_t f2bf(float f) {
-    const __bf16 h = (__bf16)f;
-    return __builtin_bit_cast(bf16_t, h);
-}
-__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
 __device__ __forceinline__ unsigned pack2(float a, float b) {
     const f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
@@ -53,12 +48,6 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {
 __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
-__device__ __forceinline__ unsigned long long argmax_key(float v, int n) {
-    unsigned u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
-}
-
 struct DecGemvDev {
     int B, N, K;
     const bf16_t *W;        // WL_TILED [N padded to 16][K]; LayerNorm modes: gamma folded in (W_nk * g_k, rounded to bf16)
@@ -1507,21 +1496,6 @@ __global__ __launch_bounds__(64) void dec_attn_combine_kernel(const float *__res
 // tokens of position pos+1 (token + positional embedding, plus the LayerNorm partial statistics
 // the next layer-0 GEMV expects) and advances the device-side position -- so a step has no
 // separate embedding launch and *pos_ptr has exactly one writer.
-// (max, sum exp) partials merged: commutative (no contraction), so a butterfly gives every lane the same bits
-// (a plain two-float struct, selected field by field: HIP's float2 through selects and shuffles left the kernel a scratch copy)
-struct Lse {
-    float m, s;
-};
-__device__ __forceinline__ Lse lse_merge(Lse a, Lse b) {
-    const float M = fmaxf(a.m, b.m);
-    return Lse{M, __fadd_rn(__fmul_rn(a.s, __expf(a.m - M)), __fmul_rn(b.s, __expf(b.m - M)))};
-}
-__device__ __forceinline__ Lse lse_shfl_xor(Lse v, int o) { return Lse{__shfl_xor(v.m, o), __shfl_xor(v.s, o)}; }
-__device__ __forceinline__ Lse lse_load(const float *p) {
-    const float2 v = *(const float2 *)p;
-    return Lse{v.x, v.y};
-}
-
 // X (wm_transcribe's extended decode, WmXDev): the same close, plus the log-prob of the chosen token under the filtered
 // distribution, no_speech_prob at the <|startoftranscript|> position, and -- under sampling -- the sum rule decided on
 // the raw text maximum.  The (max, sum exp) partials of a row are merged over 16 FIXED tile segments (any participant

@@ -104,6 +104,79 @@ WmXDev wm_model_x_dev(const WmModel *m, const WmDecodeMode &mode) {
     return t;
 }
 
+// ------------------------------------------------------------------ beam search state ----
+namespace {
+// beam_ws: [WmBeamPar | per-row and per-window state | fin_tok | fin_lp], sized for WM_DEC_MAXB rows and as many windows
+struct BeamLayout {
+    size_t par, budget, sum, src, list_n, list_tok, list_lp, wdone, wsteps, fin_n, fin_len, fin_sum, fin_tok, fin_lp, end;
+    explicit BeamLayout(int n_ctx) {
+        size_t o = 0;
+        auto take = [&](size_t words) { const size_t at = o; o += (words * 4 + 255) & ~(size_t)255; return at; };
+        const size_t R = WM_DEC_MAXB;
+        par = take(sizeof(WmBeamPar) / 4); budget = take(R); sum = take(R); src = take(R); list_n = take(R);
+        list_tok = take(R * (WM_MAX_BEAM + 1)); list_lp = take(R * (WM_MAX_BEAM + 1));
+        wdone = take(R); wsteps = take(R); fin_n = take(R); fin_len = take(R * WM_MAX_BEAM_HYPS); fin_sum = take(R * WM_MAX_BEAM_HYPS);
+        fin_tok = take(R * WM_MAX_BEAM_HYPS * n_ctx); fin_lp = take(R * WM_MAX_BEAM_HYPS * n_ctx);
+        end = o;
+    }
+};
+}  // namespace
+
+size_t wm_model_beam_state_bytes(const WmModel *m) { return BeamLayout(m->dims.n_text_ctx).fin_tok; }
+
+int wm_model_beam_dev(wm_ctx *ctx, const WmDecodeMode &mode, WmBeamDev *out) {
+    WmModel *m = ctx->model;
+    const BeamLayout L(m->dims.n_text_ctx);
+    if (!m->beam_ws.p) {   // (allocated once: the captured graphs hold these addresses)
+        WM_TRY(m->beam_ws.reserve(ctx->stream, L.end));
+        WM_HIP(hipMemsetAsync(m->beam_ws.p, 0, L.end, ctx->stream));
+    }
+    char *p = (char *)m->beam_ws.p;
+    WmBeamDev d;
+    memset(&d, 0, sizeof(d));
+    d.par = (const WmBeamPar *)(p + L.par); d.N = mode.beam; d.n_ctx = m->dims.n_text_ctx;
+    d.budget = (const int *)(p + L.budget); d.sum = (float *)(p + L.sum); d.src = (int *)(p + L.src);
+    d.list_n = (int *)(p + L.list_n); d.list_tok = (int *)(p + L.list_tok); d.list_lp = (float *)(p + L.list_lp);
+    d.wdone = (int *)(p + L.wdone); d.wsteps = (int *)(p + L.wsteps); d.fin_n = (int *)(p + L.fin_n);
+    d.fin_len = (int *)(p + L.fin_len); d.fin_sum = (float *)(p + L.fin_sum);
+    d.fin_tok = (int *)(p + L.fin_tok); d.fin_lp = (float *)(p + L.fin_lp);
+    d.trace = m->beam_trace_on ? (float *)m->beam_trace.p : nullptr;   // (the debug library asked for this call's trace)
+    *out = d;
+    return WM_OK;
+}
+
+int wm_model_beam_begin(wm_ctx *ctx, const WmDecodeMode &mode, int rows, int windows, const WmBeamPar *par, const int32_t *budgets) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(mode.beam >= 1 && mode.beam <= WM_MAX_BEAM && rows == windows * mode.beam && rows <= WM_DEC_MAXB, WM_ERR_INVALID,
+               "beam group: %d rows are not %d windows x %d beams", rows, windows, mode.beam);
+    WmBeamDev d;
+    WM_TRY(wm_model_beam_dev(ctx, mode, &d));
+    const BeamLayout L(m->dims.n_text_ctx);
+    char *p = (char *)m->beam_ws.p;
+    // sums 0, sources / lists / flags / counts 0: everything between the budgets and the finished records
+    WM_HIP(hipMemsetAsync(p + L.sum, 0, L.fin_len - L.sum, ctx->stream));
+    WM_HIP(hipMemcpyAsync(p + L.par, par, sizeof(WmBeamPar), hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipMemcpyAsync(p + L.budget, budgets, (size_t)windows * 4, hipMemcpyHostToDevice, ctx->stream));
+    return WM_OK;
+}
+
+int wm_model_beam_close(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
+    WmModel *m = ctx->model;
+    const wm_dims &D = m->dims;
+    WmBeamDev bm;
+    WM_TRY(wm_model_beam_dev(ctx, mode, &bm));
+    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
+    const WmStopDev sp = wm_model_stop_dev(m, mode);
+    const WmXDev xd = wm_model_x_dev(m, mode);
+    WM_REQUIRE(xd.par, WM_ERR_STATE, "beam close: the extended decode is off");
+    WM_TRY(wm_beam_topk(ctx, m->dlogits, m->vpad, D.n_vocab, m->dargmax, B, ts, xd, mode.mask ? m->dmask : nullptr, m->vpad / 32,
+                        n_prompt, m->dpos, bm));
+    WM_TRY(wm_beam_select_step(ctx, B, m->dseq, m->dpos, n_prompt, m->tok_emb, m->dec_pos, D.n_text_state, m->dx, m->dxb, m->dstats,
+                               m->dmean, ts, sp, xd, mode.off ? m->doff : nullptr, bm));
+    return wm_beam_reorder(ctx, m->skv, D.n_text_layer * 2, B, D.n_text_head, D.n_text_ctx, m->dpos, n_prompt, m->dseq,
+                           m->dx_logprob, bm);
+}
+
 void wm_model_drop_graphs(WmModel *m) {
     for (WmModel::GraphSet &g : m->graph_sets) g.destroy();
     m->graph_sets.clear();
@@ -323,7 +396,7 @@ void wm_model_destroy(wm_ctx *ctx) {
     wm_model_drop_graphs(m);
     if (m->h_nlive) (void)hipHostFree(m->h_nlive);
     for (void *p : m->allocs) (void)hipFree(p);
-    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws}) b->release();
+    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->beam_ws, &m->beam_trace}) b->release();
     delete m;
     ctx->model = nullptr;
 }

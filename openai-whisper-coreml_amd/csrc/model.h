@@ -121,6 +121,35 @@ struct WmStopDev {
     int eot, pad_tok;
 };
 
+// Beam search (wm_transcribe_mel_beam, beam.hip).  A beam group is a candidate group (rows = windows x N, row c * N + k is beam
+// k of window c) whose rows are re-parented after every generated token.  What changes from call to call lives in device
+// memory (WmBeamPar, the budgets), so the captured positions replay; N and n_prompt are part of the graph key.
+struct WmBeamPar {
+    int max_cand;   // finished hypotheses after which a window leaves the decode
+    int max_new;
+    int eot;        // < 0: nothing finishes
+    int pad;        // what a dead beam and a window that has left keep emitting: eot, or 0
+};
+constexpr int WM_BEAM_TRACE = 2 + 2 * (WM_MAX_BEAM + 1);   // debug trace words per (generated index, row): n, sum, tokens, log-probs
+struct WmBeamDev {
+    const WmBeamPar *par;
+    int N, n_ctx;
+    const int *budget;   // [windows] tokens a window may generate (<= max_new)
+    float *sum;          // [rows] running f32 sum of the beam (-inf: dead)
+    int *src;            // [rows] the beam (0 .. N - 1) of its window a row continued at the last close
+    int *list_n;         // [rows] entries of the row's list
+    int *list_tok;       // [rows][WM_MAX_BEAM + 1]
+    float *list_lp;      // [rows][WM_MAX_BEAM + 1]
+    int *wdone;          // [windows] 1: the window has left the decode
+    int *wsteps;         // [windows] tokens it has generated
+    int *fin_n;          // [windows] finished hypotheses
+    int *fin_len;        // [windows][WM_MAX_BEAM_HYPS] tokens incl. eot
+    float *fin_sum;      // [windows][WM_MAX_BEAM_HYPS]
+    int *fin_tok;        // [windows][WM_MAX_BEAM_HYPS][n_ctx]
+    float *fin_lp;       // [windows][WM_MAX_BEAM_HYPS][n_ctx]
+    float *trace;        // debug library only (else null): [max_new][rows][WM_BEAM_TRACE], the lists and sums BEFORE each step
+};
+
 // Word-level timestamps (wm_align, align.hip).  The alignment heads of one decoder layer: n heads (ascending) whose
 // captured queries go to slots slot0 .. slot0 + n - 1 of the capture buffer.
 struct WmAlignLayer {
@@ -170,8 +199,11 @@ struct WmDecodeMode {
     // candidate s of window c, the cross-attention K/V cache holds one entry per WINDOW and is read by
     // wm_dec_attention_cand, once for all live candidates of a window.
     int n_cand = 1;
+    // Beam width (wm_transcribe_mel_beam; 0: no beam search): the generating positions close with the beam kernels
+    // (wm_model_beam_close) instead of the arg-max; above 1 the rows are a candidate group (n_cand = beam).
+    int beam = 0;
     bool operator==(const WmDecodeMode &o) const {
-        return n_cand == o.n_cand && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -273,8 +305,11 @@ struct WmModel {
         // workgroups); chosen burst by burst from the number of decodes in flight on the device, captured on first use
         int burst[2] = {0, 0};
         WmGraph g1[2], gk[2];   // one position, burst[.] positions
+        // a beam group (mode.beam): the graphs above are its PROMPT positions, these its generating ones
+        int bburst[2] = {0, 0};
+        WmGraph b1[2], bk[2];
         void destroy() {
-            for (int i = 0; i < 2; ++i) { g1[i].destroy(); gk[i].destroy(); }
+            for (int i = 0; i < 2; ++i) { g1[i].destroy(); gk[i].destroy(); b1[i].destroy(); bk[i].destroy(); }
         }
         unsigned long stamp = 0;   // last use (LRU eviction)
     };
@@ -311,6 +346,13 @@ struct WmModel {
     std::vector<int32_t> align_l, align_h;
     WmDevBuf align_ws;
     float *align_dbg_matrix = nullptr;
+    // wm_transcribe_mel_beam: the group's beam state (WmBeamDev; allocated once at its largest size, so captured graphs keep
+    // their addresses) and the debug library's one-shot trace capture (host destination, null in the product) with its
+    // device buffer
+    WmDevBuf beam_ws;
+    float *beam_dbg_trace = nullptr;
+    WmDevBuf beam_trace;
+    bool beam_trace_on = false;   // the group decoding on this context right now writes its trace
     WmDevBuf pcm_stage;   // host-pointer staging of a decode group's PCM (wm_transcribe*, wm_align)
     WmDevBuf io_stage;    // staging for host-pointer model calls
 };
@@ -353,6 +395,13 @@ int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *r
                         const WmDecodeMode &mode = WmDecodeMode());
 // the device view of the early-stop state (done == null when mode.stop is false)
 WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode);
+// beam search: the device view of the group's beam state (allocating it on first use), its initial state for `rows` rows in
+// `windows` windows (par and budgets [windows] are host memory that outlives the upload), and the close of a generating
+// position: per-row lists, per-window selection + next embedding + position advance, re-parenting of the caches
+int wm_model_beam_dev(wm_ctx *ctx, const WmDecodeMode &mode, WmBeamDev *out);
+int wm_model_beam_begin(wm_ctx *ctx, const WmDecodeMode &mode, int rows, int windows, const WmBeamPar *par, const int32_t *budgets);
+int wm_model_beam_close(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode);
+size_t wm_model_beam_state_bytes(const WmModel *m);   // the part of beam_ws in front of fin_tok (what a drain copies whole)
 void wm_model_drop_graphs(WmModel *m);
 int wm_model_set_pos(wm_ctx *ctx, int pos);
 
@@ -497,6 +546,23 @@ int wm_stop_init(wm_ctx *ctx, const WmStopDev &stop, int B);
 int wm_ts_init(wm_ctx *ctx, const WmTsDev &ts, int B);
 int wm_range_softmax(wm_ctx *ctx, const float *logits, long ldo, int B, int first, int n, float *probs);
 int wm_fill_synthetic(wm_ctx *ctx, const WmTensor &t, uint32_t seed, int tensor_id, float gain);
+
+// beam.hip (beam search)
+// Per row (grid: rows) the <= N + 1 best admissible tokens of the f32 logits [rows][ldo] with their log-probs under the
+// filtered distribution, from the partials the DE_LOGITS_X launch of the same position left (tilemax, xd, ts); rows of
+// windows that have left and dead beams get an empty list.  Also no_speech_prob when the position is par->sot_pos.
+int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
+                 const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
+                 const WmBeamDev &bm);
+// Per window the selection (beam.h), finished records, the rows' new tokens / sums / sources / timestamp-rule state, the
+// early-stop flags and live list, the embedding of the next position and *pos_ptr += 1 (one workgroup).
+int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const bf16_t *emb, const float *pemb, int d,
+                        float *x, bf16_t *xb, float *stats_out, float *mean_buf, const WmTsDev &ts, const WmStopDev &stop,
+                        const WmXDev &xd, const int *off, const WmBeamDev &bm);
+// Re-parent what follows a beam, by bm.src within each window, in place: rows [0, *pos_ptr - 1] of every layer's and head's
+// self-attention K/V (skv [L2][rows][H][T][64]) and the rows' token / log-prob histories.  Call after wm_beam_select_step.
+int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, const int *pos_ptr, int n_prompt, int *seq,
+                    float *logprob, const WmBeamDev &bm);
 
 // align.hip (word-level timestamps)
 // the alignment heads' queries of decode position *pos_ptr: dq [B][d] -> cap[b][*pos_ptr][L.slot0 + k][64]

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <vector>
 
+#include "beam.h"
 #include "model.h"
 
 #define WM_MODEL(ctx)                                                               \
@@ -399,6 +400,12 @@ struct LaneJob {
     std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
     std::vector<unsigned> ids;     // its sample ids (wm_transcribe_mel)
     std::vector<int32_t> off;      // its row offsets (wm_transcribe_mel_ragged)
+    // a beam group (wm_transcribe_mel_beam): its parameters and window budgets (sources of async uploads) and what a drain
+    // fetches: the state in front of the finished records, the finished tokens / log-probs of its windows, the debug trace
+    WmBeamPar bpar = {};
+    std::vector<int32_t> bbud, bfin_tok;
+    std::vector<char> bstate;
+    std::vector<float> bfin_lp, btrace;
     float stage_sum[3] = {0.f, 0.f, 0.f};
     ~LaneJob() {
         if (c) (void)hipStreamSynchronize(c->stream);  // error paths: nothing may outlive pr / gen / bud
@@ -427,6 +434,12 @@ struct TxSrc : WmAudioSrc {
     int sot_tail = 0;                      // ... whose <|startoftranscript|> is entry prompt_len[b] - sot_tail
     const uint32_t *sample_ids = nullptr;
     int n_cand = 1;   // candidates per row (wm_transcribe_mel_best_of): every row decodes n_cand times over ONE encoder pass
+    // wm_transcribe_mel_beam: the n_cand rows of a window are its BEAMS (n_cand = beam width, 1 included)
+    bool beam = false;
+    int max_cand = 0;
+    int32_t *n_hyp = nullptr;   // [B]
+    float *sums = nullptr;      // [B][max(n_cand, max_cand)]
+    float *trace = nullptr;     // debug library: [B][max_new][n_cand][WM_BEAM_TRACE] (null in the product)
 };
 
 struct StopCfg {
@@ -520,6 +533,9 @@ int stage_mel(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const 
     return WM_OK;
 }
 
+// the tokens row `b` of the call may generate
+int stop_budget(const StopCfg &stop, int b, int max_new) { return stop.budgets && stop.budgets[b] < max_new ? stop.budgets[b] : max_new; }
+
 // front end -> encoder -> cross K/V -> prompt upload -> first embedding, all enqueued on the lane's stream
 int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const StopCfg &stop, const XCfg &xc) {
     wm_ctx *c = j.c;
@@ -530,6 +546,7 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
     j.mode.mask = m->mask_on; j.mode.ts = m->ts_on; j.mode.x = xc.on; j.mode.off = src.prompt_len != nullptr;
     j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
     j.mode.n_cand = N;
+    j.mode.beam = src.beam ? N : 0;
     const void *d_pcm;
     WM_TRY(stage_pcm(c, src, j.b0, Cg, mem, &d_pcm));
     // decode state first (prompt tokens [n_prompt][Bg], position 0): a pageable H2D copy may wait for the
@@ -586,6 +603,17 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
     }
     WM_TRY(wm_model_reserve(c, Cg));
     if (N > 1) WM_TRY(wm_model_reserve_rows(c, Bg));
+    if (src.beam) {   // beam state: nothing finished, every sum 0; a window's budget is its own max_new
+        j.bbud.resize(Cg);
+        for (int w = 0; w < Cg; ++w) j.bbud[w] = stop_budget(stop, j.b0 + w, j.bpar.max_new);
+        m->beam_trace_on = src.trace != nullptr;
+        if (src.trace) {
+            const size_t bytes = (size_t)j.bpar.max_new * Bg * WM_BEAM_TRACE * 4;
+            WM_TRY(m->beam_trace.reserve(c->stream, bytes));
+            WM_HIP(hipMemsetAsync(m->beam_trace.p, 0, bytes, c->stream));
+        }
+        WM_TRY(wm_model_beam_begin(c, j.mode, Bg, Cg, &j.bpar, j.bbud.data()));
+    }
     WM_HIP(hipEventRecord(j.ev[0], c->stream));
     // 1. log-mel front end, or the caller's mel windows
     const float *enc_mel;
@@ -605,16 +633,18 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
 // One decoder position = 8 launches per layer + logits + arg-max/embed (which writes the next token, embeds the
 // next position and advances *dpos).  Nothing in it depends on host state, so it is captured ONCE into a
 // hipGraph per lane and replayed for every position -- and `burst` consecutive positions are captured as one more graph.
-int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt) {
-    WM_TRY(wm_model_decode_step(j.c, j.Bg, false, 0, j.c->model->dims.n_vocab - 1, nullptr, mode, n_prompt));
+// gen (a beam group's generating positions): the step also stores the f32 logits and the beam kernels close it.
+int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) {
+    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen, 0, j.c->model->dims.n_vocab - 1, nullptr, mode, n_prompt));
+    if (gen) return wm_model_beam_close(j.c, j.Bg, n_prompt, mode);
     return wm_model_close_step(j.c, j.Bg, n_prompt, true, nullptr, 0, mode);
 }
 
-int capture_positions(LaneJob &j, const WmDecodeMode &mode, int n_prompt, int n_pos, WmGraph *out) {
+int capture_positions(LaneJob &j, const WmDecodeMode &mode, int n_prompt, int n_pos, bool gen, WmGraph *out) {
     char what[48];
     snprintf(what, sizeof(what), "the %d-position decode graph", n_pos);
     return capture_graph(j.c->stream, out, what, [&]() -> int {
-        for (int i = 0; i < n_pos; ++i) WM_TRY(lane_position(j, mode, n_prompt));
+        for (int i = 0; i < n_pos; ++i) WM_TRY(lane_position(j, mode, n_prompt, gen));
         return WM_OK;
     });
 }
@@ -646,30 +676,111 @@ int lane_graph(LaneJob &j, int n_prompt) {
     return WM_OK;
 }
 
+// a beam group has enqueued everything: fetch its beam state behind the token streams
+int beam_fetch(LaneJob &j, int max_new, bool trace) {
+    WmModel *m = j.c->model;
+    WmBeamDev bm;
+    WM_TRY(wm_model_beam_dev(j.c, j.mode, &bm));
+    j.lp.resize((size_t)max_new * j.Bg);   // the live beams' log-probs [gi][row], whether or not the caller wants them
+    WM_HIP(hipMemcpyAsync(j.lp.data(), m->dx_logprob, j.lp.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    j.bstate.resize(wm_model_beam_state_bytes(m));
+    WM_HIP(hipMemcpyAsync(j.bstate.data(), m->beam_ws.p, j.bstate.size(), hipMemcpyDeviceToHost, j.c->stream));
+    const size_t nf = (size_t)j.Cg * WM_MAX_BEAM_HYPS * bm.n_ctx;
+    j.bfin_tok.resize(nf);
+    j.bfin_lp.resize(nf);
+    WM_HIP(hipMemcpyAsync(j.bfin_tok.data(), bm.fin_tok, nf * 4, hipMemcpyDeviceToHost, j.c->stream));
+    WM_HIP(hipMemcpyAsync(j.bfin_lp.data(), bm.fin_lp, nf * 4, hipMemcpyDeviceToHost, j.c->stream));
+    if (trace) {
+        j.btrace.resize((size_t)max_new * j.Bg * WM_BEAM_TRACE);
+        WM_HIP(hipMemcpyAsync(j.btrace.data(), m->beam_trace.p, j.btrace.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    }
+    return WM_OK;
+}
+
+// ... and, once it has arrived, write the windows' hypotheses: the finished ones in the order they finished, then (fewer
+// than N finished) the live beams by descending sum until there are N.  Output stride S = max(N, max_cand) per window.
+void beam_drain(const LaneJob &j, const TxSrc &src, int max_new, int32_t eot, int32_t *tokens_out, int32_t *lens_out,
+                float *logprobs_out, float *no_speech_out) {
+    const int N = src.n_cand, S = std::max(N, src.max_cand), n_ctx = j.c->model->dims.n_text_ctx;
+    // the device pointers of the state, as offsets into the fetched copy
+    WmBeamDev bm;
+    (void)wm_model_beam_dev(j.c, j.mode, &bm);
+    const char *dev0 = (const char *)j.c->model->beam_ws.p;
+    auto host = [&](const void *dev) { return j.bstate.data() + ((const char *)dev - dev0); };
+    const float *sum = (const float *)host(bm.sum), *fin_sum = (const float *)host(bm.fin_sum);
+    const int *fin_n = (const int *)host(bm.fin_n), *fin_len = (const int *)host(bm.fin_len), *wsteps = (const int *)host(bm.wsteps);
+    for (int w = 0; w < j.Cg; ++w) {
+        const int W = j.b0 + w;   // window of the call
+        int n_hyp = 0;
+        auto put = [&](const int32_t *tok, size_t tok_stride, const float *lp, size_t lp_stride, int len, float s) {
+            const size_t o = (size_t)W * S + n_hyp++;
+            for (int i = 0; i < max_new; ++i) {
+                tokens_out[o * max_new + i] = i < len ? tok[(size_t)i * tok_stride] : eot;
+                if (logprobs_out) logprobs_out[o * max_new + i] = i < len ? lp[(size_t)i * lp_stride] : 0.f;
+            }
+            lens_out[o] = len;
+            src.sums[o] = s;
+        };
+        for (int f = 0; f < fin_n[w]; ++f) {
+            const size_t base = ((size_t)w * WM_MAX_BEAM_HYPS + f) * n_ctx;
+            put(j.bfin_tok.data() + base, 1, j.bfin_lp.data() + base, 1, fin_len[w * WM_MAX_BEAM_HYPS + f], fin_sum[w * WM_MAX_BEAM_HYPS + f]);
+        }
+        if (n_hyp < N) {
+            int order[WM_MAX_BEAM];
+            const int n_live = wm_beam_fill_order(N, sum + (size_t)w * N, order);
+            for (int k = 0; k < n_live && n_hyp < N; ++k) {
+                const int b = w * N + order[k];
+                put(j.gen.data() + b, j.Bg, j.lp.data() + b, j.Bg, wsteps[w], sum[b]);
+            }
+        }
+        src.n_hyp[W] = n_hyp;
+        for (int h = n_hyp; h < S; ++h) {   // unused slots
+            const size_t o = (size_t)W * S + h;
+            for (int i = 0; i < max_new; ++i) {
+                tokens_out[o * max_new + i] = eot;
+                if (logprobs_out) logprobs_out[o * max_new + i] = 0.f;
+            }
+            lens_out[o] = 0;
+            src.sums[o] = -INFINITY;
+        }
+        if (no_speech_out) no_speech_out[W] = j.ns[(size_t)w * N];   // beam 0's
+        if (src.trace)     // [gi][row of the group] -> [window of the call][gi][beam]
+            for (int gi = 0; gi < max_new; ++gi)
+                memcpy(src.trace + (((size_t)W * max_new + gi) * N) * WM_BEAM_TRACE,
+                       j.btrace.data() + ((size_t)gi * j.Bg + (size_t)w * N) * WM_BEAM_TRACE, (size_t)N * WM_BEAM_TRACE * 4);
+    }
+}
+
 // enqueue the next burst of positions of a lane (<= burst_len(), up to the end of the sequence).  `shared`: other decode
 // groups are in flight on the device right now -- this burst's cross-attention launches are the short-lived shape.
 int lane_burst(LaneJob &j, int n_prompt, int n_steps, bool use_graph, bool shared) {
     wm_ctx *c = j.c;
     WmModel *m = c->model;
     const int K = burst_len();
-    const int k = n_steps - j.t < K ? n_steps - j.t : K;
+    // a beam group: positions 0 .. n_prompt - 2 step through the prompt (the arg-max close), the others generate (the beam
+    // close); a burst stays on one side
+    const bool gen = j.mode.beam && j.t >= n_prompt - 1;
+    const int left = (j.mode.beam && !gen ? n_prompt - 1 : n_steps) - j.t;
+    const int k = left < K ? left : K;
     const int sh = shared ? 1 : 0;
     WmDecodeMode mode = j.mode;   // what every step of this burst, launched or captured, is handed
     mode.xattn_shared = shared;
     WmModel::GraphSet *g = use_graph ? &m->graph_sets[j.gset] : nullptr;
+    WmGraph *g1 = g ? (gen ? g->b1 : g->g1) : nullptr, *gk = g ? (gen ? g->bk : g->gk) : nullptr;
+    int *burst = g ? (gen ? g->bburst : g->burst) : nullptr;
     if (use_graph && k == K && K > 1) {
-        if (!g->gk[sh].e || g->burst[sh] != K) {
-            WM_TRY(capture_positions(j, mode, n_prompt, K, &g->gk[sh]));
-            g->burst[sh] = K;
+        if (!gk[sh].e || burst[sh] != K) {
+            WM_TRY(capture_positions(j, mode, n_prompt, K, gen, &gk[sh]));
+            burst[sh] = K;
         }
-        WM_HIP(hipGraphLaunch(g->gk[sh].e, c->stream));
+        WM_HIP(hipGraphLaunch(gk[sh].e, c->stream));
     } else {
-        if (use_graph && !g->g1[sh].e) WM_TRY(capture_positions(j, mode, n_prompt, 1, &g->g1[sh]));
+        if (use_graph && !g1[sh].e) WM_TRY(capture_positions(j, mode, n_prompt, 1, gen, &g1[sh]));
         for (int i = 0; i < k; ++i) {
             if (use_graph) {
-                WM_HIP(hipGraphLaunch(g->g1[sh].e, c->stream));
+                WM_HIP(hipGraphLaunch(g1[sh].e, c->stream));
             } else {
-                WM_TRY(lane_position(j, mode, n_prompt));
+                WM_TRY(lane_position(j, mode, n_prompt, gen));
             }
         }
     }
@@ -844,6 +955,60 @@ extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const in
     return WM_OK;
 } WM_API_CATCH
 
+// Beam search: the call of wm_transcribe_mel_best_of with the rows of a window as its BEAMS (TxSrc::beam) -- the same groups,
+// the same prompt phase, one cross-K/V read per window; the generating positions close with the beam kernels (beam.hip)
+extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                      const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                      int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size, int max_candidates,
+                                      float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                      int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
+                                      float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+    float *trace = nullptr;   // the debug library's capture is for this call only
+    if (ctx && ctx->model) {
+        trace = ctx->model->beam_dbg_trace;
+        ctx->model->beam_dbg_trace = nullptr;
+    }
+    const int rc = [&]() -> int {   // (a call that fails these consumes the token budgets set for it, like any other)
+        WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
+        WM_REQUIRE(n_hyp_out && sum_logprobs_out, WM_ERR_INVALID, "null n_hyp_out / sum_logprobs_out");
+        WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
+        WM_REQUIRE(beam_size >= 1 && beam_size <= WM_MAX_BEAM, WM_ERR_INVALID, "beam_size %d outside [1, %d]", beam_size, WM_MAX_BEAM);
+        WM_REQUIRE(max_candidates >= 1 && max_candidates <= WM_MAX_BEAM_HYPS, WM_ERR_INVALID, "max_candidates %d outside [1, %d]",
+                   max_candidates, WM_MAX_BEAM_HYPS);
+        WM_REQUIRE(std::isnan(length_penalty) || (length_penalty >= 0.f && length_penalty <= 1.f), WM_ERR_INVALID,
+                   "length_penalty must be NaN (none) or in [0, 1]");
+        WM_REQUIRE(B >= 1 && max_new >= 1, WM_ERR_INVALID, "B < 1 or max_new < 1");
+        return WM_OK;
+    }();
+    if (rc != WM_OK) {
+        if (ctx && ctx->model) ctx->model->budget_host.clear();
+        return rc;
+    }
+    TxSrc src;
+    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
+    src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
+    src.n_cand = beam_size; src.beam = true; src.max_cand = max_candidates;
+    src.n_hyp = n_hyp_out; src.sums = sum_logprobs_out; src.trace = trace;
+    WM_TRY(transcribe_impl(ctx, src, B, prompt_stride, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
+                           no_speech_prob_out, mem));
+    if (best_out) {   // the MaximumLikelihoodRanker over the search's own sums
+        const int S = std::max(beam_size, max_candidates);
+        for (int b = 0; b < B; ++b) {
+            int best = 0;
+            double best_score = -INFINITY;
+            for (int h = 0; h < n_hyp_out[b]; ++h) {
+                const size_t r = (size_t)b * S + h;
+                int n_text = 0;
+                while (n_text < lens_out[r] && tokens_out[r * max_new + n_text] != eot) ++n_text;
+                const double score = wm_rank_score((double)sum_logprobs_out[r], n_text, length_penalty);
+                if (score > best_score) { best_score = score; best = h; }   // the first maximal score; all -inf: hypothesis 0
+            }
+            best_out[b] = best;
+        }
+    }
+    return WM_OK;
+} WM_API_CATCH
+
 // wm_transcribe_greedy, wm_transcribe, wm_transcribe_mel and wm_transcribe_mel_ragged: opts == null with both extra outputs
 // null is the greedy decode exactly
 static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, int max_new, int32_t eot,
@@ -901,7 +1066,8 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                    sot_index, n_prompt);
         WM_REQUIRE(ns_tok >= -1 && ns_tok < D.n_vocab, WM_ERR_INVALID, "no_speech_token %d outside the vocabulary", ns_tok);
         WM_REQUIRE(!no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
-        xc.on = T > 0.f || logprobs_out || no_speech_out;
+        WM_REQUIRE(!src.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
+        xc.on = T > 0.f || logprobs_out || no_speech_out || src.beam;   // (the beam close reads the filtered partials)
         xc.logprobs = logprobs_out;
         xc.no_speech = no_speech_out;
         const uint64_t seed = opts ? opts->seed : 0;
@@ -913,7 +1079,7 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
         xc.par.ns_tok = ns_tok;
     }
     const bool no_stop = g_wm_tuning.no_early_stop != 0;   // probes only: decode every position, truncate on the host
-    const bool use_graph = !graphs_off() && !ctx->prof.on;
+    const bool use_graph = !graphs_off() && !ctx->prof.on && !src.trace;   // (a traced call bakes nothing into graphs)
     StopCfg stop;
     stop.on = !no_stop && (eot >= 0 || !budgets.empty());
     stop.eot = eot;
@@ -1004,6 +1170,7 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                 j.t = 0; j.bursts = 0; j.stopped = false;
                 j.P = n_prompt;
                 if (src.prompt_len) j.P = *std::max_element(src.prompt_len + j.b0, src.prompt_len + j.b0 + j.Cg);
+                j.bpar.max_cand = src.max_cand; j.bpar.max_new = max_new; j.bpar.eot = eot; j.bpar.pad = eot >= 0 ? eot : 0;
                 WM_TRY(lane_prefill(j, src, j.P, mem, stop, xc));
                 if (use_graph) WM_TRY(lane_graph(j, j.P));
                 j.state = LaneJob::DECODING;
@@ -1035,7 +1202,7 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                 j.gen.resize((size_t)max_new * j.Bg);  // dseq[P + i][b]
                 WM_HIP(hipMemcpyAsync(j.gen.data(), j.c->model->dseq + (size_t)j.P * j.Bg, j.gen.size() * 4,
                                       hipMemcpyDeviceToHost, j.c->stream));
-                if (xc.logprobs) {   // [gi][b], laid out like dseq
+                if (xc.logprobs && !src.beam) {   // [gi][b], laid out like dseq
                     j.lp.resize((size_t)max_new * j.Bg);
                     WM_HIP(hipMemcpyAsync(j.lp.data(), j.c->model->dx_logprob, j.lp.size() * 4, hipMemcpyDeviceToHost,
                                           j.c->stream));
@@ -1045,6 +1212,7 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                     WM_HIP(hipMemcpyAsync(j.ns.data(), j.c->model->dx_nospeech, j.ns.size() * 4, hipMemcpyDeviceToHost,
                                           j.c->stream));
                 }
+                if (src.beam) WM_TRY(beam_fetch(j, max_new, src.trace != nullptr));
                 j.state = LaneJob::DRAINING;
                 progress = true;
                 continue;
@@ -1055,7 +1223,11 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
             if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
             WM_HIP(q);
             WM_HIP(hipStreamSynchronize(j.c->stream));
-            for (int b = 0; b < j.Bg; ++b) {   // [gi][row] -> [row of the call][candidate][gi]
+            if (src.beam) {
+                j.c->model->beam_trace_on = false;
+                beam_drain(j, src, max_new, eot, tokens_out, lens_out, xc.logprobs, xc.no_speech);
+            }
+            for (int b = 0; b < (src.beam ? 0 : j.Bg); ++b) {   // [gi][row] -> [row of the call][candidate][gi]
                 const int w = j.b0 + b / N;            // row of the call
                 const size_t o = (size_t)j.b0 * N + b; // its candidate's output row
                 int len = max_new;

@@ -200,6 +200,7 @@ void wm_balanced_cut(int B, int G, std::vector<int> &b0, std::vector<int> &cg); 
 // the right-aligned prompt table [P][Bg] and the row offsets [Bg] of rows [b0, b0 + Bg) of a ragged call; returns P (model_api.cpp)
 int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, std::vector<int32_t> &table,
                    std::vector<int32_t> &off);
+double wm_rank_score(double sum, int n_text, float length_penalty);   // api.cpp: the MaximumLikelihoodRanker's score
 // CU-masked groups of a call (0: none -- unmasked lanes as wm_group_count says; 2 / 3: that many groups, one per part of the chip)
 int wm_lane_parts(int B, int L, bool explicit_lanes, int n_text_state, int n_text_layer);
 

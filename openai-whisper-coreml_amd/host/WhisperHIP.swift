@@ -299,6 +299,38 @@ struct Whisper {
         return (cands, best)
     }
 
+    /// openai-whisper's beam search on the same step (wm_transcribe_mel_beam): beamSize beams per window that share the
+    /// window's encoder pass and cross-attention cache; patience nil = 1.0 (maxCandidates = round(beamSize * patience)),
+    /// lengthPenalty nil = openai-whisper's None.  Uniform prompts of one length (sotTail nil) or ragged ones.  Returns, per
+    /// window, the tokens and the summed log-prob of every hypothesis and the index of the best one.  Not compiled in this
+    /// repository.
+    func transcribeMelBeam(mel: [Float], melBase: [Int64], melLen: [Int32], seek: [Int32], nFrames: [Int32], prompts: [[Int32]],
+                           sotTail: Int32?, beamSize: Int32, patience: Float?, lengthPenalty: Float?, maxNew: Int32,
+                           eot: Int32) throws -> (hypotheses: [[[Int32]]], sums: [[Float]], best: [Int32]) {
+        typealias BeamFn = @convention(c) (OpaquePointer, UnsafePointer<Float>, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                           UnsafePointer<Int32>, UnsafePointer<Int32>, Int32, UnsafePointer<Int32>, Int32,
+                                           UnsafePointer<Int32>?, Int32, Int32, Int32, Float, Int32, Int32, UnsafeRawPointer?,
+                                           UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Int32>,
+                                           UnsafeMutablePointer<Float>, UnsafeMutablePointer<Float>?, UnsafeMutablePointer<Float>?,
+                                           UnsafeMutablePointer<Int32>?, Int32) -> Int32
+        let maxCand = Int32((Float(beamSize) * (patience ?? 1.0)).rounded(.toNearestOrEven))   // Python's round
+        let rows = melBase.count, s = Int(max(beamSize, maxCand)), m = Int(maxNew)
+        let stride = prompts.map { $0.count }.max() ?? 0
+        let lens = prompts.map { Int32($0.count) }
+        let flat = prompts.flatMap { $0 + [Int32](repeating: 0, count: stride - $0.count) }
+        var tokens = [Int32](repeating: 0, count: rows * s * m)
+        var outLens = [Int32](repeating: 0, count: rows * s)
+        var nHyp = [Int32](repeating: 0, count: rows)
+        var sums = [Float](repeating: 0, count: rows * s)
+        var best = [Int32](repeating: 0, count: rows)
+        let f: BeamFn = try sym("wm_transcribe_mel_beam")
+        try check(f(ctx, mel, melBase, melLen, seek, nFrames, Int32(rows), flat, Int32(stride), sotTail == nil ? nil : lens,
+                    sotTail ?? 0, beamSize, maxCand, lengthPenalty ?? Float.nan, maxNew, eot, nil, &tokens, &outLens, &nHyp, &sums,
+                    nil, nil, &best, 0))
+        let hyps = (0..<rows).map { r in (0..<Int(nHyp[r])).map { h in Array(tokens[(r * s + h) * m..<(r * s + h) * m + Int(outLens[r * s + h])]) } }
+        return (hyps, (0..<rows).map { r in Array(sums[r * s..<r * s + Int(nHyp[r])]) }, best)
+    }
+
     /// Word-level timing inputs of the windows of a long-form round (wm_align_mel): the window description of
     /// transcribeMel, one start sequence per row ([sot, language, task] with the row's own language) and the text tokens the
     /// round decoded for each window (all < eot).  Same outputs as align.  The word rules (add_word_timestamps) and the
