@@ -5,170 +5,18 @@
 //                          embedding of the next position, the live list and the position advance;
 //   * beam_reorder_kernel: the self-attention K/V cache and the rows' histories gathered by source beam, in place.
 // A beam of width 1 must reproduce the greedy decode BIT FOR BIT (tokens, log-probs), so a row's close here is the
-// arithmetic of dec_kernels.hip's argmax_embed_body in its summation orders: the functions of the first block below restate
-// that kernel's inline code (16 fixed tile segments, one wave per row for the merges and the embedding).  They are restated,
-// not shared: moving any of them out of argmax_embed_body into a common function changed that kernel's machine code
-// (instruction counts of both instantiations), which this project pins; tests/test_beam_gpu.py holds the two to equal bits.
+// arithmetic of dec_kernels.hip's argmax_embed_body in its summation orders (16 fixed tile segments, one wave per row for
+// the merges and the embedding): both call the same functions of dec_close.h -- lse_row_segments, lse_row_total,
+// ts_row_merge, ts_advance, embed_row -- and tests/test_beam_gpu.py holds the two closes to equal bits.
 #include "beam.h"
 #include "dec_close.h"
 #include "model.h"
 
 namespace {
 
-// ------------------------------------------------------------------ a row's close, as argmax_embed_body computes it ----
-// One wave's share of a row's 16 FIXED tile segments of the WmXDev partials: segments pi, pi + P, ... of the row whose
-// partials start at tile index rb; seg[sg] = allowed text (m, s), unfiltered (m, s) -- the latter merged when `sot` only.
-// Each segment has one summation order whatever P is.
-__device__ __forceinline__ void lse_row_segments(const WmXDev &xd, long rb, int n_tiles, bool sot, int pi, int P, int lane,
-                                                 float (*seg)[4]) {
-    const int cs = (n_tiles + 15) / 16;
-    for (int sg = pi; sg < 16; sg += P) {
-        const int lo = sg * cs, hi = lo + cs < n_tiles ? lo + cs : n_tiles;
-        const Lse none{-1e30f, 0.f};
-        Lse a = none, c = none;
-        for (int t0 = lo + lane; t0 < hi; t0 += 64 * 4) {
-            Lse va0 = none, va1 = none, va2 = none, va3 = none, vc0 = none, vc1 = none, vc2 = none, vc3 = none;
-            if (t0 < hi) va0 = lse_load(xd.txt + (rb + t0) * 2);
-            if (t0 + 64 < hi) va1 = lse_load(xd.txt + (rb + t0 + 64) * 2);
-            if (t0 + 128 < hi) va2 = lse_load(xd.txt + (rb + t0 + 128) * 2);
-            if (t0 + 192 < hi) va3 = lse_load(xd.txt + (rb + t0 + 192) * 2);
-            if (sot) {   // wave-uniform
-                if (t0 < hi) vc0 = lse_load(xd.all + (rb + t0) * 2);
-                if (t0 + 64 < hi) vc1 = lse_load(xd.all + (rb + t0 + 64) * 2);
-                if (t0 + 128 < hi) vc2 = lse_load(xd.all + (rb + t0 + 128) * 2);
-                if (t0 + 192 < hi) vc3 = lse_load(xd.all + (rb + t0 + 192) * 2);
-            }
-            a = lse_merge(lse_merge(lse_merge(lse_merge(a, va0), va1), va2), va3);
-            c = lse_merge(lse_merge(lse_merge(lse_merge(c, vc0), vc1), vc2), vc3);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            a = lse_merge(a, lse_shfl_xor(a, o));
-            c = lse_merge(c, lse_shfl_xor(c, o));
-        }
-        if (lane == 0) {
-            seg[sg][0] = a.m; seg[sg][1] = a.s;
-            seg[sg][2] = c.m; seg[sg][3] = c.s;
-        }
-    }
-}
-
-// The row's 16 segments merged in a fixed order (one wave): lt = allowed text, la = unfiltered; every lane gets both.
-__device__ __forceinline__ void lse_row_total(const float (*seg)[4], int lane, Lse &lt, Lse &la) {
-    if (lane < 16) {
-        lt.m = seg[lane][0]; lt.s = seg[lane][1];
-        la.m = seg[lane][2]; la.s = seg[lane][3];
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        lt = lse_merge(lt, lse_shfl_xor(lt, o));
-        la = lse_merge(la, lse_shfl_xor(la, o));
-    }
-    lt = Lse{__shfl(lt.m, 0), __shfl(lt.s, 0)};
-    la = Lse{__shfl(la.m, 0), __shfl(la.s, 0)};
-}
-
-// Row b's timestamp tiles merged by one wave: the best allowed timestamp key and (M, S) = (max, sum exp(v - M)) over the
-// allowed timestamps; every lane gets all three.
-__device__ __forceinline__ void ts_row_merge(const WmTsDev &ts, int b, int n_tiles, int lane, unsigned long long &kts, float &M,
-                                             float &S) {
-    const int t_first = ts.ts_begin >> 4;
-    kts = 0ull;
-    M = -1e30f;
-    for (int t = t_first + lane; t < n_tiles; t += 64) {
-        const unsigned long long k2 = ts.key_ts[(long)b * n_tiles + t];
-        kts = k2 > kts ? k2 : kts;
-        M = fmaxf(M, ts.lse[((long)b * n_tiles + t) * 2]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long ok = __shfl_xor(kts, o);
-        kts = ok > kts ? ok : kts;
-        M = fmaxf(M, __shfl_xor(M, o));
-    }
-    S = 0.f;
-    for (int t = t_first + lane; t < n_tiles; t += 64) {
-        const float2 ms = *(const float2 *)(ts.lse + ((long)b * n_tiles + t) * 2);
-        S += ms.y * __expf(ms.x - M);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
-}
-
-// `tok` was sampled for a row whose timestamp-rule history is hs[4] (n_sampled, last_is_ts, prev_is_ts, last_ts): advance
-// the history in place and return the ranges (text_lo, text_hi, ts_lo, ts_hi) of the next position.
-__device__ __forceinline__ int4 ts_advance(const WmTsDev &ts, int *hs, int tok) {
-    const int n_s = hs[0] + 1;
-    const bool prev_ts = hs[0] < 1 || hs[1] != 0;  // penultimate_was_timestamp = len(seq) < 2 or seq[-2] >= begin
-    const bool last_ts = tok >= ts.ts_begin;
-    const int last_val = last_ts ? tok : hs[3];
-    hs[0] = n_s; hs[2] = hs[1]; hs[1] = last_ts ? 1 : 0; hs[3] = last_val;
-    int text_lo = 0, text_hi = ts.ts_begin, ts_lo = ts.ts_begin, ts_hi = ts.n_vocab;
-    if (last_ts) {
-        if (prev_ts) ts_hi = ts_lo;        // a pair was just closed: the next token is not a timestamp
-        else text_lo = ts.eot;             // an opening timestamp needs its partner (or <|endoftext|>)
-    }
-    if (last_val >= 0) {                   // timestamps never decrease (and advance unless closing a pair)
-        const int floor_ts = (last_ts && !prev_ts) ? last_val : last_val + 1;
-        ts_lo = floor_ts > ts_lo ? floor_ts : ts_lo;
-    }
-    return make_int4(text_lo, text_hi, ts_lo, ts_hi);
-}
-
-// One wave embeds token `tok` at positional row `prow` into row b of the residual stream: x (f32), its mean-centred bf16
-// copy xb (WL_TILED order), the row mean and the LayerNorm partial statistics the next layer-0 GEMV expects.
-__device__ __forceinline__ void embed_row(long tok, int prow, int b, int lane, const bf16_t *__restrict__ emb,
-                                          const float *__restrict__ pemb, int d, float *__restrict__ x, bf16_t *__restrict__ xb,
-                                          float *__restrict__ stats_out, float *__restrict__ mean_buf) {
-    float s1 = 0.f, s2 = 0.f;
-    // the row stays in registers between the sums and the mean-centred bf16 copy (the first 512 columns: 8 values per lane; the
-    // round-4 kernel re-read what it had just stored: a store -> load round trip through L2 on the step's tail)
-    constexpr int EV = 8;   // (d <= 512 entirely: tiny, base -- where a step is 35 launches and this trip is 0.5 % of it)
-    float ev[EV];
-#pragma unroll
-    for (int i = 0; i < EV; ++i) {
-        const int j = lane + 64 * i;
-        ev[i] = 0.f;
-        if (j < d) {
-            const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
-            x[(long)b * d + j] = v;
-            ev[i] = v;
-            s1 += v;
-            s2 += v * v;
-        }
-    }
-    for (int j = lane + 64 * EV; j < d; j += 64) {  // (wider models than any Whisper: the re-reading path)
-        const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
-        x[(long)b * d + j] = v;
-        s1 += v;
-        s2 += v * v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o);
-        s2 += __shfl_xor(s2, o);
-    }
-    {   // bf16 copy, mean-centred (see DecGemvDev::mean_in)
-        const float mean = s1 / (float)d;
-#pragma unroll
-        for (int i = 0; i < EV; ++i) {
-            const int j = lane + 64 * i;
-            if (j < d) xb[wm_tiled_offset((size_t)b, (size_t)j, (size_t)d)] = f2bf(ev[i] - mean);
-        }
-        for (int j = lane + 64 * EV; j < d; j += 64)
-            xb[wm_tiled_offset((size_t)b, (size_t)j, (size_t)d)] = f2bf(x[(long)b * d + j] - mean);
-        if (lane == 0 && mean_buf) mean_buf[b] = mean;
-    }
-    if (stats_out) {  // one part (index 0) carries the row; the other d/16 - 1 parts the consumers sum are zero
-        float *blk = stats_out + (long)(b >> 4) * (2 * d) + (b & 15) * 2;
-        for (int pt = 1 + lane; pt < d / 16; pt += 64) *(float2 *)(blk + pt * 32) = make_float2(0.f, 0.f);
-        if (lane == 0) *(float2 *)blk = make_float2(s1, s2);
-    }
-}
-
 // ------------------------------------------------------------------ per-row list ------------------------------------
 // One 16-wave workgroup per row.  The reductions are maxima (any order, same bits) except the log-sum-exp, which follows
-// the fixed orders above: a row's list does not depend on the group's shape.
+// the fixed orders of dec_close.h: a row's list does not depend on the group's shape.
 __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict__ logits, long ldo, int V, int n_tiles,
                                                          const unsigned long long *__restrict__ tilemax, WmTsDev ts, WmXDev xd,
                                                          const unsigned *__restrict__ mask, int mask_words, int n_prompt,
@@ -198,11 +46,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
             const unsigned long long k = tilemax[rb + t];
             key = k > key ? k : key;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long ok = __shfl_xor(key, o);
-            key = ok > key ? ok : key;
-        }
+        key = key_max_xor<64>(key);
         if (lane == 0) red_s[0][wave] = key;
     }
     __syncthreads();
@@ -210,12 +54,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
         Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f}, lts{-1e30f, 0.f};
         lse_row_total(seg_s, lane, lt, la);
         unsigned long long key = lane < 16 ? red_s[0][lane] : 0ull;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            const unsigned long long ok = __shfl_xor(key, o);
-            key = ok > key ? ok : key;
-        }
-        key = __shfl(key, 0);
+        key = __shfl(key_max_xor<16>(key), 0);
         bool forced = false;
         if (ts.rng) {   // "if sum of probability over timestamps is above any other token, sample timestamp", on raw logits
             unsigned long long kts;
@@ -256,21 +95,11 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
     unsigned long long mine = local_best(~0ull);
     int count = 0;
     for (int r = 0; r < K; ++r) {   // K rounds of a workgroup-wide maximum; the winner's thread retires it
-        unsigned long long key = mine;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long ok = __shfl_xor(key, o);
-            key = ok > key ? ok : key;
-        }
+        unsigned long long key = key_max_xor<64>(mine);
         if (lane == 0) red_s[(r + 1) & 1][wave] = key;
         __syncthreads();
         key = lane < 16 ? red_s[(r + 1) & 1][lane] : 0ull;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            const unsigned long long ok = __shfl_xor(key, o);
-            key = ok > key ? ok : key;
-        }
-        key = __shfl(key, 0);
+        key = __shfl(key_max_xor<16>(key), 0);
         if (key == 0ull) break;                       // nothing admissible is left (uniform)
         const float lp = argmax_key_value(key) - norm;
         if (!(lp > -INFINITY)) break;                 // -inf (and NaN) is never listed (uniform)

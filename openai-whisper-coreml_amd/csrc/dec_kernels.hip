@@ -661,6 +661,9 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const bf16_t *__restrict__
 
 // ------------------------------------------------------------------ token embedding ------
 // x[b] = token_embedding[seq[pos][b]] + positional_embedding[pos]  (+ LayerNorm partial statistics)
+// The embedding of a call's FIRST position, one 4-wave workgroup per row.  Every later position is embedded by the launch that
+// closes the one before it (embed_row of dec_close.h: ONE wave per row, 64-lane stride).  The two are not one function: the
+// four-wave sums here and the one-wave sums there differ in the last place, so merging them would change results.
 // off (nullable, [B]): a ragged decode group -- row b's prompt starts at position off[b] of the group, so its positional
 // row is pos - off[b] (0 while the row has not started)
 __global__ __launch_bounds__(256) void dec_embed_kernel(const int *__restrict__ seq, const int *__restrict__ pos_ptr,
@@ -1546,47 +1549,12 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
 #pragma unroll
             for (int u = 0; u < 8; ++u) key = k[u] > key ? k[u] : key;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long ok = __shfl_xor(key, o);
-            key = ok > key ? ok : key;
-        }
+        key = key_max_xor<64>(key);
         if (lane == 0) part_s[my_row][my_pi] = key;
     }
     __shared__ float seg_s[X ? 16 : 1][X ? 16 : 1][4];   // [row][segment]: allowed text (m, s), unfiltered (m, s)
     if (X && my_row >= 0) {  // wave-uniform
-        const long rb = (long)(bw + my_row) * n_tiles;
-        const bool sot = pos_raw == xd.par->sot_pos;
-        const int cs = (n_tiles + 15) / 16;
-        for (int sg = my_pi; sg < 16; sg += P) {
-            const int lo = sg * cs, hi = lo + cs < n_tiles ? lo + cs : n_tiles;
-            const Lse none{-1e30f, 0.f};
-            Lse a = none, c = none;
-            for (int t0 = lo + lane; t0 < hi; t0 += 64 * 4) {
-                Lse va0 = none, va1 = none, va2 = none, va3 = none, vc0 = none, vc1 = none, vc2 = none, vc3 = none;
-                if (t0 < hi) va0 = lse_load(xd.txt + (rb + t0) * 2);
-                if (t0 + 64 < hi) va1 = lse_load(xd.txt + (rb + t0 + 64) * 2);
-                if (t0 + 128 < hi) va2 = lse_load(xd.txt + (rb + t0 + 128) * 2);
-                if (t0 + 192 < hi) va3 = lse_load(xd.txt + (rb + t0 + 192) * 2);
-                if (sot) {   // wave-uniform
-                    if (t0 < hi) vc0 = lse_load(xd.all + (rb + t0) * 2);
-                    if (t0 + 64 < hi) vc1 = lse_load(xd.all + (rb + t0 + 64) * 2);
-                    if (t0 + 128 < hi) vc2 = lse_load(xd.all + (rb + t0 + 128) * 2);
-                    if (t0 + 192 < hi) vc3 = lse_load(xd.all + (rb + t0 + 192) * 2);
-                }
-                a = lse_merge(lse_merge(lse_merge(lse_merge(a, va0), va1), va2), va3);
-                c = lse_merge(lse_merge(lse_merge(lse_merge(c, vc0), vc1), vc2), vc3);
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                a = lse_merge(a, lse_shfl_xor(a, o));
-                c = lse_merge(c, lse_shfl_xor(c, o));
-            }
-            if (lane == 0) {
-                seg_s[my_row][sg][0] = a.m; seg_s[my_row][sg][1] = a.s;
-                seg_s[my_row][sg][2] = c.m; seg_s[my_row][sg][3] = c.s;
-            }
-        }
+        lse_row_segments(xd, (long)(bw + my_row) * n_tiles, n_tiles, pos_raw == xd.par->sot_pos, my_pi, P, lane, seg_s[my_row]);
     }
     __syncthreads();
     for (int b = bw + wave; b < B && b < bw + nrows; b += 16) {  // wave-uniform, at most one trip: the owners
@@ -1596,56 +1564,19 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
             asm volatile("" : "+s"(pv) : "v"((unsigned)key));
             pos = pos_ptr ? pv : 0;
         }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {   // P <= 16 partial maxima in lanes 0 .. 15
-            const unsigned long long ok = __shfl_xor(key, o);
-            key = ok > key ? ok : key;
-        }
-        key = __shfl(key, 0);               // (every lane of the owner carries the row's key, as before)
+        key = __shfl(key_max_xor<16>(key), 0);   // P <= 16 partial maxima in lanes 0 .. 15; every lane of the owner carries the row's key
         Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f}, lts{-1e30f, 0.f};
         bool forced = false;
-        if (X) {   // the row's 16 segments, in a fixed order
-            if (lane < 16) {
-                lt.m = seg_s[wave][lane][0]; lt.s = seg_s[wave][lane][1];
-                la.m = seg_s[wave][lane][2]; la.s = seg_s[wave][lane][3];
-            }
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) {
-                lt = lse_merge(lt, lse_shfl_xor(lt, o));
-                la = lse_merge(la, lse_shfl_xor(la, o));
-            }
-            lt = Lse{__shfl(lt.m, 0), __shfl(lt.s, 0)};
-            la = Lse{__shfl(la.m, 0), __shfl(la.s, 0)};
-        }
+        if (X) lse_row_total(seg_s[wave], lane, lt, la);   // the row's 16 segments, in a fixed order
         if (ts.rng) {
             // `key` is the best allowed TEXT token.  Merge the timestamp tiles: best allowed timestamp and
             // log-sum-exp of the allowed timestamps; a timestamp is forced when that exceeds the best text logit
             // (ApplyTimestampRules: "if sum of probability over timestamps is above any other token, sample timestamp").
-            const int t_first = ts.ts_begin >> 4;
-            unsigned long long kts = 0ull;
-            float M = -1e30f;
-            for (int t = t_first + lane; t < n_tiles; t += 64) {
-                const unsigned long long k2 = ts.key_ts[(long)b * n_tiles + t];
-                kts = k2 > kts ? k2 : kts;
-                M = fmaxf(M, ts.lse[((long)b * n_tiles + t) * 2]);
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const unsigned long long ok = __shfl_xor(kts, o);
-                kts = ok > kts ? ok : kts;
-                M = fmaxf(M, __shfl_xor(M, o));
-            }
-            float S = 0.f;
-            for (int t = t_first + lane; t < n_tiles; t += 64) {
-                const float2 ms = *(const float2 *)(ts.lse + ((long)b * n_tiles + t) * 2);
-                S += ms.y * __expf(ms.x - M);
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
-            unsigned u = (unsigned)(key >> 32);
-            u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;  // inverse of argmax_key's order-preserving map
+            unsigned long long kts;
+            float M, S;
+            ts_row_merge(ts, b, n_tiles, lane, kts, M, S);
             // (X: the key may be a perturbed score; the rule compares RAW logits, as openai-whisper does)
-            const float text_best = key ? (X ? lt.m : __uint_as_float(u)) : -1e30f;
+            const float text_best = key ? (X ? lt.m : argmax_key_value(key)) : -1e30f;
             const float lse = S > 0.f ? M + __logf(S) : -1e30f;
             lts = Lse{M, S};
             forced = kts != 0ull && (key == 0ull || lse > text_best);
@@ -1654,7 +1585,7 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
         }
         if (lane == 0) {
             // key == 0: nothing admissible (every allowed id suppressed, or NaN logits): never index with -1
-            int tok = key ? (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)) : fallback_tok;
+            int tok = key ? argmax_key_index(key) : fallback_tok;
             if (X && pos + 1 >= n_prompt) {
                 // log-prob of the chosen token under the filtered distribution (temperature 1): the allowed set is the
                 // admissible timestamps when the sum rule forced one, else text and timestamps; nothing admissible: -inf
@@ -1681,22 +1612,7 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
             }
             if (ts.rng && pos + 1 >= n_prompt) {
                 // the token at index pos + 1 was sampled: advance the history and derive the ranges of the next position
-                int *hs = ts.hist + b * 4;
-                const int n_s = hs[0] + 1;
-                const bool prev_ts = hs[0] < 1 || hs[1] != 0;  // penultimate_was_timestamp = len(seq) < 2 or seq[-2] >= begin
-                const bool last_ts = tok >= ts.ts_begin;
-                const int last_val = last_ts ? tok : hs[3];
-                hs[0] = n_s; hs[2] = hs[1]; hs[1] = last_ts ? 1 : 0; hs[3] = last_val;
-                int text_lo = 0, text_hi = ts.ts_begin, ts_lo = ts.ts_begin, ts_hi = ts.n_vocab;
-                if (last_ts) {
-                    if (prev_ts) ts_hi = ts_lo;        // a pair was just closed: the next token is not a timestamp
-                    else text_lo = ts.eot;             // an opening timestamp needs its partner (or <|endoftext|>)
-                }
-                if (last_val >= 0) {                   // timestamps never decrease (and advance unless closing a pair)
-                    const int floor_ts = (last_ts && !prev_ts) ? last_val : last_val + 1;
-                    ts_lo = floor_ts > ts_lo ? floor_ts : ts_lo;
-                }
-                *(int4 *)(ts.rng + b * 4) = make_int4(text_lo, text_hi, ts_lo, ts_hi);
+                *(int4 *)(ts.rng + b * 4) = ts_advance(ts, ts.hist + b * 4, tok);
             }
             int nxt = tok;
             if (seq) {
@@ -1718,50 +1634,7 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
             const long tok = tok_s[b - bw];
             // a ragged group (off != null): row b's prompt starts at position off[b], its positional row counts from there
             const int prow = off ? max(pos + 1 - off[b], 0) : pos + 1;
-            float s1 = 0.f, s2 = 0.f;
-            // the row stays in registers between the sums and the mean-centred bf16 copy (the first 512 columns: 8 values per lane; the
-            // round-4 kernel re-read what it had just stored: a store -> load round trip through L2 on the step's tail)
-            constexpr int EV = 8;   // (d <= 512 entirely: tiny, base -- where a step is 35 launches and this trip is 0.5 % of it)
-            float ev[EV];
-#pragma unroll
-            for (int i = 0; i < EV; ++i) {
-                const int j = lane + 64 * i;
-                ev[i] = 0.f;
-                if (j < d) {
-                    const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
-                    x[(long)b * d + j] = v;
-                    ev[i] = v;
-                    s1 += v;
-                    s2 += v * v;
-                }
-            }
-            for (int j = lane + 64 * EV; j < d; j += 64) {  // (wider models than any Whisper: the re-reading path)
-                const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
-                x[(long)b * d + j] = v;
-                s1 += v;
-                s2 += v * v;
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                s1 += __shfl_xor(s1, o);
-                s2 += __shfl_xor(s2, o);
-            }
-            {   // bf16 copy, mean-centred (see DecGemvDev::mean_in)
-                const float mean = s1 / (float)d;
-#pragma unroll
-                for (int i = 0; i < EV; ++i) {
-                    const int j = lane + 64 * i;
-                    if (j < d) xb[wm_tiled_offset((size_t)b, (size_t)j, (size_t)d)] = f2bf(ev[i] - mean);
-                }
-                for (int j = lane + 64 * EV; j < d; j += 64)
-                    xb[wm_tiled_offset((size_t)b, (size_t)j, (size_t)d)] = f2bf(x[(long)b * d + j] - mean);
-                if (lane == 0 && mean_buf) mean_buf[b] = mean;
-            }
-            if (stats_out) {  // one part (index 0) carries the row; the other d/16 - 1 parts the consumers sum are zero
-                float *blk = stats_out + (long)(b >> 4) * (2 * d) + (b & 15) * 2;
-                for (int pt = 1 + lane; pt < d / 16; pt += 64) *(float2 *)(blk + pt * 32) = make_float2(0.f, 0.f);
-                if (lane == 0) *(float2 *)blk = make_float2(s1, s2);
-            }
+            embed_row(tok, prow, b, lane, emb, pemb, d, x, xb, stats_out, mean_buf);
         }
     }
     // *pos_ptr has ONE writer: the last workgroup to arrive (every workgroup read the position before it arrived)

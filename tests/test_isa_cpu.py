@@ -6,7 +6,9 @@ loads) puts such a trip back without any test noticing: the results are identica
 launches of a decoder position is 0.3 us slower.  This test pins the property in the machine code: in every
 dec_gemv_kernel instantiation, the straight-line code that issues the first weight loads contains no
 scalar-memory WAIT (the leading arguments arrive preloaded in SGPRs; csrc/dec_kernels.hip "KERNEL ARGUMENTS").
-DESIGN.md section 4; no reference counterpart (the reference's decoder is a CoreML graph)."""
+DESIGN.md section 4; no reference counterpart (the reference's decoder is a CoreML graph).
+The same compile also keeps the compiler's resource remarks: the step-closing arg-max kernels, which share a row's close
+with the beam kernels (csrc/dec_close.h), are held to no scratch and 4 waves per SIMD."""
 import os
 import re
 import subprocess
@@ -20,7 +22,8 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 @pytest.fixture(scope="module")
-def gemv_kernels(tmp_path_factory):
+def dec_compile(tmp_path_factory):
+    """ONE device-only compile of dec_kernels.hip with the product's flags: (dec_gemv_kernel disassembly, resource remarks)."""
     if not (os.path.exists(HIPCC) and os.path.exists(os.path.join(LLVM, "llvm-objdump"))):
         pytest.skip("no ROCm toolchain")
     d = tmp_path_factory.mktemp("isa")
@@ -31,7 +34,8 @@ def gemv_kernels(tmp_path_factory):
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
     flags = [f for f in b.FLAGS if f != "-fPIC"] + b.FILE_FLAGS.get("dec_kernels.hip", [])
-    subprocess.run([HIPCC] + flags + ["--cuda-device-only", "-c", "-x", "hip", src, "-o", co], check=True, capture_output=True)
+    remarks = subprocess.run([HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", "-x", "hip", src,
+                              "-o", co], check=True, capture_output=True, text=True).stderr
     subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + co,
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + elf], check=True, capture_output=True)
     out = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", elf], check=True, capture_output=True,
@@ -49,7 +53,27 @@ def gemv_kernels(tmp_path_factory):
             if ins and not ins.startswith("s_nop"):
                 kernels[cur].append(ins)
     assert len(kernels) >= 20, "no dec_gemv_kernel instantiations found in the disassembly"
-    return kernels
+    return kernels, remarks
+
+
+@pytest.fixture(scope="module")
+def gemv_kernels(dec_compile):
+    return dec_compile[0]
+
+
+@pytest.fixture(scope="module")
+def kernel_resources(dec_compile):
+    """{mangled kernel name: {field: int}} from the compiler's kernel-resource-usage remarks."""
+    res, cur = {}, None
+    for ln in dec_compile[1].splitlines():
+        m = re.search(r"remark:\s+(Function Name|[A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\S+) \[-Rpass-analysis=kernel-resource-usage\]", ln)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            cur = res.setdefault(m.group(2), {})
+        elif cur is not None and re.fullmatch(r"-?\d+", m.group(2)):
+            cur[m.group(1)] = int(m.group(2))
+    return res
 
 
 KNOWN_COMPILER = "7.2."   # the HIP version whose prologue shape is pinned below (hipcc --version: "HIP version: 7.2.x")
@@ -91,3 +115,18 @@ def test_no_scalar_round_trip_in_front_of_the_first_weight_load(gemv_kernels):
         if offenders:
             bad.append((name, offenders[:3]))
     assert not bad, "a kernel-argument fetch sits in front of the first weight load again: %r" % bad[:3]
+
+
+def test_step_close_kernels_keep_their_resources(kernel_resources):
+    """The step-closing arg-max kernels share a row's close with the beam kernels (csrc/dec_close.h), so an edit there is
+    an edit to both.  What is pinned for them is not an instruction stream but what an edit must not cost: no scratch (a
+    spilled row of the embedding or of the (max, sum exp) partials would be a memory round trip on the tail of every decode
+    position) and an occupancy of at least 4 waves per SIMD, i.e. the 16 waves of the 1024-thread workgroup on one CU
+    (<= 128 VGPRs).  Read from the compiler's resource remarks.  Results and time are held by the GPU suite and the A/B
+    record of DESIGN.md section 10."""
+    for kernel in ("argmax_embed_kernel", "argmax_embed_x_kernel"):
+        found = [r for name, r in kernel_resources.items() if re.search(r"\d+%sE" % kernel, name)]
+        assert len(found) == 1, (kernel, sorted(kernel_resources)[:5])
+        r = found[0]
+        assert r["ScratchSize"] == 0, (kernel, r)
+        assert r["Occupancy"] >= 4, (kernel, r)
