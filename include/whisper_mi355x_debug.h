@@ -34,7 +34,8 @@ WM_API int wmdbg_layernorm(wm_ctx *ctx, const float *x, const float *g, const fl
 /* Non-causal MHA, head_dim 64: q,k,v,out f32 [B][S][H*64]. */
 WM_API int wmdbg_enc_attention(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int S,
                         float *out);
-/* Decode-step skinny GEMM: out[B][N] = (ln_g ? LayerNorm(x) : x) . W[N][K]^T + bias; B <= 16. */
+/* Decode-step skinny GEMM (the DE_Q epilogue): out[B][N] = (ln_g ? LayerNorm(x) : x) . W[N][K]^T + bias; 1 <= B <= WM_DEC_MAXB
+ * (128). */
 WM_API int wmdbg_dec_gemv(wm_ctx *ctx, const float *x, const float *ln_g, const float *ln_b, const float *W,
                    const float *bias, float *out, int B, int N, int K);
 /* The decoder's residual product (out-projection / fc2): resid[B][N] += x[B][K] . W[N][K]^T + bias, any B <= 128.
@@ -42,6 +43,76 @@ WM_API int wmdbg_dec_gemv(wm_ctx *ctx, const float *x, const float *ln_g, const 
  * the per-tile LayerNorm partials the kernel leaves for the next folded GEMV: stats [B][2]. */
 WM_API int wmdbg_dec_gemv_resid(wm_ctx *ctx, const float *x, const float *W, const float *bias, float *resid, float *copy_bf16,
                          float *stats, int B, int N, int K);
+/* The LayerNorm-folded decode GEMV with any of its layer epilogues at any decode-group size, driven as the decoder drives it:
+ * wm_ln_fold on the bf16 weights, then wm_dec_gemv on bf16 activations in WL_TILED order with the producer's K/16 partial
+ * statistics of the f32 rows.  epi: 0 = DE_QKV (N = 3 d, d = n_head * 64: q third -> out_f32 [B][d], k / v thirds -> row pos
+ * of the caches), 1 = DE_Q (out_f32 [B][N]), 3 = DE_GELU (out_bf16 [B][N], un-tiled and widened; N % 32 == 0).  1 <= B <=
+ * WM_DEC_MAXB, K % 64 == 0, K <= 1280; bias nullable.  centre != 0: the activations are bf16(x - mean_b) with mean_in = the
+ * rows' f32 means, the statistics still those of the raw x (how the decoder holds its residual stream).  DE_QKV: kcache /
+ * vcache f32 [B][n_head][T][64] = the bf16 caches widened, pre-filled with the bf16 bit pattern WMDBG_SENTINEL_BF16 (a NaN);
+ * pos in [0, T) is read by the kernel from device memory.  Pointers of outputs an epilogue does not have may be NULL.  Always:
+ * mean_out f32 [B] (pre-filled with the NaN bits WMDBG_SENTINEL_F32), and the fold on its own: Wf f32 [pad16(N)][K] (the folded
+ * bf16 weights, un-tiled and widened), c1 / c2 f32 [pad16(N)]. */
+#define WMDBG_SENTINEL_BF16 0x7fc5u
+#define WMDBG_SENTINEL_F32 0x7fc0deadu
+WM_API int wmdbg_dec_gemv_ln(wm_ctx *ctx, int epi, const float *x, const float *ln_g, const float *ln_b, const float *W,
+                             const float *bias, int B, int N, int K, int centre, int n_head, int T, int pos, float *out_f32,
+                             float *out_bf16, float *kcache, float *vcache, float *mean_out, float *Wf, float *c1, float *c2);
+
+/* One decode position's logits launch and its close, as wm_model_decode_step / wm_model_close_step make them: wm_ln_fold of
+ * the token embedding, wm_dec_gemv with DE_LOGITS (x_on == 0) or DE_LOGITS_X, then wm_argmax_embed with the arrival counter,
+ * on one stream with the position in device memory.  All pointers are host memory; "in/out" fields are read and overwritten.
+ * The activations are staged mean-centred (see wmdbg_dec_gemv_ln).  Every per-tile partial buffer (tile maxima, timestamp
+ * keys and partials, the X-mode partials) is pre-filled with 0xff bytes, so a partial the close reads must have been written
+ * by this position's logits launch. */
+typedef struct wmdbg_step {
+    /* geometry: B rows (1 .. WM_DEC_MAXB), vocabulary V (>= 16), width K (K % 64 == 0, <= 1280), context n_ctx, decode position
+     * pos in [0, n_ctx), n_prompt >= 1 (positions pos + 1 >= n_prompt are generated) */
+    int32_t B, V, K, n_ctx, pos, n_prompt;
+    const float *x;        /* [B][K] the residual stream in front of the final LayerNorm */
+    const float *ln_g, *ln_b;   /* [K] */
+    const float *emb;      /* [V][K] token embedding (rounded to bf16): folded copy for the product, plain copy for the embedding */
+    const float *bias;     /* [V] or NULL: added to the logits (the model has none; places maxima) */
+    const float *pemb;     /* [n_ctx][K] positional embedding */
+    int32_t *seq;          /* in/out [n_ctx][B] token history, position-major (a token generated for position n_ctx is not returned here) */
+    /* filters: ids suppressed at every position; ids suppressed when mask_first != 0 (this position is the first generated one) */
+    const int32_t *suppress, *suppress_first;
+    int32_t n_suppress, n_suppress_first, mask_first;
+    int32_t arg_first, arg_last;   /* the arg-max range with the timestamp rules off */
+    int32_t fallback_tok;          /* the token when nothing is admissible */
+    /* timestamp rules: ts_mode 0 = off, 1 = the state wm_ts_init leaves, 2 = rng / hist as given */
+    int32_t ts_mode, ts_begin, eot, max_initial;
+    int32_t *rng, *hist;   /* [B][4] in (ts_mode 2) / out (ts_mode != 0) */
+    /* X mode (log-probs, no-speech, sampling at temperature > 0) */
+    int32_t x_on, chunk0, sot_pos, ns_tok;
+    float temperature;
+    uint64_t seed;
+    /* early stop: done in/out [B]; budget [B] or NULL */
+    int32_t stop_on, stop_eot, pad_tok;
+    int32_t *done;
+    const int32_t *budget;
+    const int32_t *off;    /* [B] ragged row offsets or NULL */
+    /* outputs */
+    float *logits;         /* [B][V] the launch's f32 logits */
+    int32_t *tok;          /* [B] result + arg_first: the token the close chose */
+    int32_t *result;       /* [B] */
+    float *logprob;        /* [B] the slot of generated index pos + 1 - n_prompt (X mode; else and for prompt positions the NaN bits WMDBG_SENTINEL_F32) */
+    int32_t logprob_written;   /* entries of the whole [n_ctx][B] log-prob buffer that no longer hold the sentinel */
+    float *nospeech;       /* [B], pre-filled with WMDBG_SENTINEL_F32 */
+    int32_t *live_rows;    /* [B] (stop_on): the list the close rebuilt, -1 where it wrote nothing (entries n_live .. B - 1) */
+    int32_t n_live;
+    int32_t pos_out;       /* *pos_ptr after the close */
+    int32_t arrive_out;    /* the arrival counter after the close (0 between launches) */
+    float *x_next;         /* [B][K] the embedded next row, pre-filled with WMDBG_SENTINEL_F32 */
+    float *xb_next;        /* [B][K] its bf16 copy, un-tiled and widened (pre-filled with WMDBG_SENTINEL_BF16) */
+    float *stats_next;     /* [B][2] (sum, sum of squares) rebuilt from the K/16 statistics parts (buffer pre-filled with WMDBG_SENTINEL_F32) */
+    int32_t stats_tail_nonzero;   /* words of parts 1 .. K/16 - 1 of the B rows that are not +0.0 */
+} wmdbg_step;
+WM_API int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io);
+/* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_step) and the offsets of seed, logits and
+ * stats_tail_nonzero (host only). */
+WM_API int wmdbg_step_layout(int32_t *out4);
+
 /* Single-query attention over a cache: q [B][H*64], k/v [B][H][T][64], keys 0..n_keys-1;
  * out = the bf16 head outputs widened to f32.  nsplit in 1..8. */
 WM_API int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int T,

@@ -2,6 +2,7 @@
 // NOT linked into libwhisper_mi355x.so: build.py links this translation unit, together with the product's objects, into
 // libwhisper_mi355x_dbg.so, which only tests/ and tools/ load (kernel-level parity tests against the oracle, probes).
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -967,4 +968,339 @@ extern "C" int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows
     }
     for (void *p : {dc, dsrc, dwd, dseq, dlp, dpos}) (void)hipFree(p);
     return rc;
+}
+
+// ------------------------------------------------------------------ the decode step's LN-folded GEMV and its close ----
+namespace {
+// device allocations of one hook call, freed when it returns (on an error path too)
+struct DevPool {
+    std::vector<void *> v;
+    ~DevPool() {
+        for (void *p : v) (void)hipFree(p);
+    }
+    // bytes of `fill` (a byte value), then the host data when given.  The 512 bytes of slack are the habit of up() above (a
+    // guard band behind host-staged buffers); nothing here relies on them: every kernel read of these buffers is clamped to
+    // the group's rows and the matrix's tiles (gemv_unit_load), and each buffer is sized for what its kernel may write.
+    int get(void **d, const void *h, size_t bytes, hipStream_t s, int fill = 0) {
+        WM_HIP(hipMalloc(d, bytes + 512));
+        v.push_back(*d);
+        WM_HIP(hipMemsetAsync(*d, fill, bytes + 512, s));
+        if (h) WM_HIP(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, s));
+        return WM_OK;
+    }
+};
+
+// [rows][K] f32 -> bf16 in WL_TILED order, rows padded to 16 with zeros
+void tile_bf16(const float *m, size_t rows, size_t K, std::vector<bf16_t> &out) {
+    const size_t rpad = (rows + 15) / 16 * 16;
+    std::vector<float> t(rpad * K, 0.f);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t k = 0; k < K; ++k) t[wm_tiled_offset(r, k, K)] = m[r * K + k];
+    to_bf16(t.data(), out, t.size());
+}
+// WL_TILED bf16 [rows][K] -> row-major f32
+void untile_bf16(const std::vector<bf16_t> &t, size_t rows, size_t K, float *out) {
+    std::vector<bf16_t> lin(rows * K);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t k = 0; k < K; ++k) lin[r * K + k] = t[wm_tiled_offset(r, k, K)];
+    from_bf16(lin, out);
+}
+
+// The A operand of a LayerNorm-folded GEMV as the decoder holds it: the producer's K/16 partial statistics of the raw f32
+// rows (as wmdbg_dec_gemv stages them), the rows' f32 means, and the bf16 activations in WL_TILED order -- of x - mean
+// when `centre`, else of x (the means are then not handed to the kernel).
+void stage_ln_rows(const float *x, int B, int K, bool centre, std::vector<bf16_t> &x16, std::vector<float> &st, std::vector<float> &mean) {
+    const int nblk = (B + 15) / 16;
+    st.assign((size_t)nblk * 2 * K, 0.f);   // block stride = 2 K floats, as in the decoder
+    mean.assign((size_t)B, 0.f);
+    std::vector<float> xc((size_t)B * K);
+    for (int b = 0; b < B; ++b) {
+        float s1 = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const float v = x[(size_t)b * K + k];
+            float *blk = st.data() + (size_t)(b >> 4) * 2 * K;
+            blk[((k >> 4) * 16 + (b & 15)) * 2] += v;
+            blk[((k >> 4) * 16 + (b & 15)) * 2 + 1] += v * v;
+            s1 += v;
+        }
+        mean[b] = s1 / (float)K;
+        for (int k = 0; k < K; ++k) xc[(size_t)b * K + k] = centre ? x[(size_t)b * K + k] - mean[b] : x[(size_t)b * K + k];
+    }
+    tile_bf16(xc.data(), (size_t)B, (size_t)K, x16);
+}
+}  // namespace
+
+extern "C" int wmdbg_dec_gemv_ln(wm_ctx *ctx, int epi, const float *x, const float *ln_g, const float *ln_b, const float *W,
+                                 const float *bias, int B, int N, int K, int centre, int n_head, int T, int pos, float *out_f32,
+                                 float *out_bf16, float *kcache, float *vcache, float *mean_out, float *Wf, float *c1, float *c2) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(epi == DE_QKV || epi == DE_Q || epi == DE_GELU, WM_ERR_INVALID, "wmdbg_dec_gemv_ln: epilogue %d not exposed", epi);
+    WM_REQUIRE(x && ln_g && ln_b && W && mean_out && Wf && c1 && c2, WM_ERR_INVALID, "wmdbg_dec_gemv_ln: null pointer");
+    WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && N >= 1 && K >= 64 && K % 64 == 0 && K <= 1280, WM_ERR_INVALID,
+               "wmdbg_dec_gemv_ln: B 1 .. %d, N >= 1, K a multiple of 64 up to 1280", WM_DEC_MAXB);
+    const int d = N / 3;
+    if (epi == DE_QKV)
+        WM_REQUIRE(N % 3 == 0 && n_head >= 1 && d == n_head * 64 && T >= 1 && pos >= 0 && pos < T && out_f32 && kcache && vcache,
+                   WM_ERR_INVALID, "wmdbg_dec_gemv_ln: DE_QKV needs N = 3 * n_head * 64, pos in [0, T) and its three outputs");
+    if (epi == DE_Q) WM_REQUIRE(out_f32, WM_ERR_INVALID, "wmdbg_dec_gemv_ln: DE_Q needs out_f32");
+    if (epi == DE_GELU) WM_REQUIRE(N % 32 == 0 && out_bf16, WM_ERR_INVALID, "wmdbg_dec_gemv_ln: DE_GELU needs N %% 32 == 0 and out_bf16");
+    const size_t Npad = ((size_t)N + 15) / 16 * 16, Bpad = ((size_t)B + 15) / 16 * 16;
+    std::vector<bf16_t> w16, x16;
+    std::vector<float> st, mean;
+    tile_bf16(W, (size_t)N, (size_t)K, w16);
+    stage_ln_rows(x, B, K, centre != 0, x16, st, mean);
+    const size_t n_f32 = epi == DE_QKV ? (size_t)B * d : epi == DE_Q ? (size_t)B * N : 0;
+    const size_t n_b16 = epi == DE_GELU ? Bpad * N : 0, n_cache = epi == DE_QKV ? (size_t)B * n_head * T * 64 : 0;
+    const std::vector<bf16_t> fill16(std::max(n_b16, n_cache), (bf16_t)WMDBG_SENTINEL_BF16);
+    const std::vector<uint32_t> fill32((size_t)B, WMDBG_SENTINEL_F32);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dx16, *dW, *dWf, *dc1, *dc2, *dg, *db, *dbias = nullptr, *dst, *dmin, *dmout, *dof = nullptr, *dob = nullptr, *dk = nullptr,
+                                                 *dv = nullptr, *dpos;
+    WM_TRY(pool.get(&dx16, x16.data(), x16.size() * 2, s));
+    WM_TRY(pool.get(&dW, w16.data(), w16.size() * 2, s));
+    WM_TRY(pool.get(&dWf, nullptr, w16.size() * 2, s));
+    WM_TRY(pool.get(&dc1, nullptr, Npad * 4, s));
+    WM_TRY(pool.get(&dc2, nullptr, Npad * 4, s));
+    WM_TRY(pool.get(&dg, ln_g, (size_t)K * 4, s));
+    WM_TRY(pool.get(&db, ln_b, (size_t)K * 4, s));
+    if (bias) WM_TRY(pool.get(&dbias, bias, (size_t)N * 4, s));
+    WM_TRY(pool.get(&dst, st.data(), st.size() * 4, s));
+    WM_TRY(pool.get(&dmin, mean.data(), (size_t)B * 4, s));
+    WM_TRY(pool.get(&dmout, fill32.data(), (size_t)B * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    if (n_f32) WM_TRY(pool.get(&dof, nullptr, n_f32 * 4, s));
+    if (n_b16) WM_TRY(pool.get(&dob, fill16.data(), n_b16 * 2, s));
+    if (n_cache) {
+        WM_TRY(pool.get(&dk, fill16.data(), n_cache * 2, s));
+        WM_TRY(pool.get(&dv, fill16.data(), n_cache * 2, s));
+    }
+    WM_TRY(wm_ln_fold(ctx, (const bf16_t *)dW, (const float *)dg, (const float *)db, (const float *)dbias, N, K, (bf16_t *)dWf,
+                      (float *)dc1, (float *)dc2));
+    DecGemvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.epi = epi; a.B = B; a.N = N; a.K = K; a.W = (const bf16_t *)dWf; a.c1 = (const float *)dc1; a.c2 = (const float *)dc2;
+    a.a = (const bf16_t *)dx16; a.stats_in = (const float *)dst; a.stats_parts = K / 16;
+    a.mean_in = centre ? (const float *)dmin : nullptr; a.mean_out = (float *)dmout;
+    a.out_f32 = (float *)dof; a.out_bf16 = (bf16_t *)dob; a.ldo = N;
+    if (epi == DE_QKV) { a.kcache = (bf16_t *)dk; a.vcache = (bf16_t *)dv; a.pos_ptr = (const int *)dpos; a.n_ctx = T; a.n_head = n_head; }
+    WM_TRY(wm_dec_gemv(ctx, a));
+    std::vector<bf16_t> wf16(w16.size()), ob16(n_b16), k16(n_cache), v16(n_cache);
+    WM_HIP(hipMemcpyAsync(wf16.data(), dWf, wf16.size() * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(c1, dc1, Npad * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(c2, dc2, Npad * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(mean_out, dmout, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    if (n_f32) WM_HIP(hipMemcpyAsync(out_f32, dof, n_f32 * 4, hipMemcpyDeviceToHost, s));
+    if (n_b16) WM_HIP(hipMemcpyAsync(ob16.data(), dob, n_b16 * 2, hipMemcpyDeviceToHost, s));
+    if (n_cache) {
+        WM_HIP(hipMemcpyAsync(k16.data(), dk, n_cache * 2, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(v16.data(), dv, n_cache * 2, hipMemcpyDeviceToHost, s));
+    }
+    WM_HIP(hipStreamSynchronize(s));
+    untile_bf16(wf16, Npad, (size_t)K, Wf);
+    if (n_b16) untile_bf16(ob16, (size_t)B, (size_t)N, out_bf16);
+    if (n_cache) { from_bf16(k16, kcache); from_bf16(v16, vcache); }
+    return WM_OK;
+}
+
+extern "C" int wmdbg_step_layout(int32_t *out4) {
+    if (!out4) return WM_ERR_INVALID;
+    out4[0] = (int32_t)sizeof(wmdbg_step); out4[1] = (int32_t)offsetof(wmdbg_step, seed);
+    out4[2] = (int32_t)offsetof(wmdbg_step, logits); out4[3] = (int32_t)offsetof(wmdbg_step, stats_tail_nonzero);
+    return WM_OK;
+}
+
+extern "C" int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
+    const int B = io->B, V = io->V, K = io->K, n_ctx = io->n_ctx, pos = io->pos, n_prompt = io->n_prompt;
+    WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && V >= 16 && K >= 64 && K % 64 == 0 && K <= 1280 && n_ctx >= 1 && pos >= 0 && pos < n_ctx &&
+                   n_prompt >= 1,
+               WM_ERR_INVALID, "wmdbg_decode_close: bad geometry");
+    WM_REQUIRE(io->x && io->ln_g && io->ln_b && io->emb && io->pemb && io->seq && io->logits && io->tok && io->result && io->logprob &&
+                   io->nospeech && io->x_next && io->xb_next && io->stats_next,
+               WM_ERR_INVALID, "wmdbg_decode_close: null pointer");
+    WM_REQUIRE(io->n_suppress >= 0 && io->n_suppress_first >= 0 && (io->n_suppress == 0 || io->suppress) &&
+                   (io->n_suppress_first == 0 || io->suppress_first),
+               WM_ERR_INVALID, "wmdbg_decode_close: bad suppress lists");
+    WM_REQUIRE(io->arg_first >= 0 && io->arg_first <= io->arg_last && io->arg_last < V && io->fallback_tok >= 0 && io->fallback_tok < V,
+               WM_ERR_INVALID, "wmdbg_decode_close: bad arg-max range / fallback token");
+    WM_REQUIRE(io->ts_mode >= 0 && io->ts_mode <= 2, WM_ERR_INVALID, "wmdbg_decode_close: ts_mode 0 .. 2");
+    if (io->ts_mode)
+        WM_REQUIRE(io->rng && io->hist && io->ts_begin > 0 && io->ts_begin < V && io->eot >= 0 && io->eot < io->ts_begin, WM_ERR_INVALID,
+                   "wmdbg_decode_close: timestamp rules need rng, hist and 0 <= eot < ts_begin < V");
+    if (io->x_on)
+        WM_REQUIRE(io->temperature >= 0.f && io->chunk0 >= 0 && (io->sot_pos < 0 || (io->ns_tok >= 0 && io->ns_tok < V)), WM_ERR_INVALID,
+                   "wmdbg_decode_close: bad X-mode parameters");
+    if (io->stop_on) WM_REQUIRE(io->done && io->live_rows && io->pad_tok >= 0 && io->pad_tok < V, WM_ERR_INVALID, "wmdbg_decode_close: early stop needs done, live_rows and a pad token");
+    const int vpad = (V + 15) / 16 * 16, n_tiles = vpad / 16, mw = (vpad + 31) / 32, Bpad = (B + 15) / 16 * 16;
+    for (int i = 0; i < n_ctx * B; ++i) WM_REQUIRE(io->seq[i] >= 0 && io->seq[i] < V, WM_ERR_INVALID, "wmdbg_decode_close: seq[%d] outside the vocabulary", i);
+    if (io->ts_mode == 2)
+        for (int i = 0; i < 4 * B; ++i) WM_REQUIRE(io->rng[i] >= 0 && io->rng[i] <= V, WM_ERR_INVALID, "wmdbg_decode_close: rng[%d] outside [0, V]", i);
+    std::vector<unsigned> mask((size_t)2 * mw, 0u);   // [0] every position, [1] = [0] | the first-position list (wm_set_suppress)
+    for (int i = 0; i < io->n_suppress; ++i) {
+        WM_REQUIRE(io->suppress[i] >= 0 && io->suppress[i] < V, WM_ERR_INVALID, "wmdbg_decode_close: suppressed id %d", io->suppress[i]);
+        mask[io->suppress[i] >> 5] |= 1u << (io->suppress[i] & 31);
+    }
+    for (int i = 0; i < mw; ++i) mask[mw + i] = mask[i];
+    for (int i = 0; i < io->n_suppress_first; ++i) {
+        WM_REQUIRE(io->suppress_first[i] >= 0 && io->suppress_first[i] < V, WM_ERR_INVALID, "wmdbg_decode_close: suppressed id %d", io->suppress_first[i]);
+        mask[mw + (io->suppress_first[i] >> 5)] |= 1u << (io->suppress_first[i] & 31);
+    }
+    const bool mask_on = io->n_suppress + io->n_suppress_first > 0;
+    std::vector<bf16_t> e16, x16;
+    std::vector<float> st, mean;
+    tile_bf16(io->emb, (size_t)V, (size_t)K, e16);
+    stage_ln_rows(io->x, B, K, true, x16, st, mean);
+    const size_t nt = (size_t)B * n_tiles, st_words = (size_t)(Bpad / 16) * 2 * K;
+    const std::vector<uint32_t> nan32(std::max({(size_t)n_ctx * B, (size_t)B * K, st_words}), WMDBG_SENTINEL_F32);
+    const std::vector<bf16_t> nan16((size_t)Bpad * K, (bf16_t)WMDBG_SENTINEL_BF16);
+    WmXPar xp;
+    memset(&xp, 0, sizeof(xp));
+    xp.key0 = (unsigned)io->seed; xp.key1 = (unsigned)(io->seed >> 32);
+    xp.sample = io->temperature > 0.f ? 1 : 0;
+    xp.inv_T = io->temperature > 0.f ? (float)(1.0 / (double)io->temperature) : 0.f;   // as wm_transcribe fills it
+    xp.sot_pos = io->sot_pos; xp.ns_tok = io->ns_tok; xp.chunk0 = io->chunk0; xp.n_prompt = n_prompt; xp.n_cand = 1;
+    const int zero = 0;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dx16, *dE, *dEf, *dc1, *dc2, *dg, *db, *dbias = nullptr, *dst, *dmin, *dmout, *dpemb, *dseq, *dpos, *darr, *dlog, *dtm, *dres, *dmask,
+        *drng = nullptr, *dhist = nullptr, *dkts = nullptr, *dlse = nullptr, *dxp = nullptr, *dtxt = nullptr, *dwin = nullptr, *dall = nullptr,
+        *dnsv = nullptr, *dlp = nullptr, *dns, *ddone = nullptr, *dbud = nullptr, *dlive = nullptr, *dnl = nullptr, *doff = nullptr, *dxn, *dxbn,
+        *dstn, *dmn;
+    WM_TRY(pool.get(&dx16, x16.data(), x16.size() * 2, s));
+    WM_TRY(pool.get(&dE, e16.data(), e16.size() * 2, s));
+    WM_TRY(pool.get(&dEf, nullptr, e16.size() * 2, s));
+    WM_TRY(pool.get(&dc1, nullptr, (size_t)vpad * 4, s));
+    WM_TRY(pool.get(&dc2, nullptr, (size_t)vpad * 4, s));
+    WM_TRY(pool.get(&dg, io->ln_g, (size_t)K * 4, s));
+    WM_TRY(pool.get(&db, io->ln_b, (size_t)K * 4, s));
+    if (io->bias) WM_TRY(pool.get(&dbias, io->bias, (size_t)V * 4, s));
+    WM_TRY(pool.get(&dst, st.data(), st.size() * 4, s));
+    WM_TRY(pool.get(&dmin, mean.data(), (size_t)B * 4, s));
+    WM_TRY(pool.get(&dmout, nullptr, (size_t)B * 4, s));
+    WM_TRY(pool.get(&dpemb, io->pemb, (size_t)n_ctx * K * 4, s));
+    {   // n_ctx + 1 rows, as the model's buffer: the close of the last position writes its token to row n_ctx
+        std::vector<int32_t> seq0((size_t)(n_ctx + 1) * B, 0);
+        std::copy(io->seq, io->seq + (size_t)n_ctx * B, seq0.begin());
+        WM_TRY(pool.get(&dseq, seq0.data(), seq0.size() * 4, s));
+        WM_HIP(hipStreamSynchronize(s));   // seq0 leaves scope
+    }
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&darr, &zero, 4, s));
+    WM_TRY(pool.get(&dlog, nullptr, (size_t)B * vpad * 4, s));
+    WM_TRY(pool.get(&dtm, nullptr, nt * 8, s, 0xff));
+    WM_TRY(pool.get(&dres, nullptr, (size_t)B * 4, s, 0xff));
+    WM_TRY(pool.get(&dmask, mask.data(), mask.size() * 4, s));
+    WmTsDev ts;
+    memset(&ts, 0, sizeof(ts));
+    if (io->ts_mode) {
+        WM_TRY(pool.get(&drng, io->ts_mode == 2 ? io->rng : nullptr, (size_t)B * 16, s));
+        WM_TRY(pool.get(&dhist, io->ts_mode == 2 ? io->hist : nullptr, (size_t)B * 16, s));
+        WM_TRY(pool.get(&dkts, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&dlse, nullptr, nt * 8, s, 0xff));
+        ts.rng = (int *)drng; ts.hist = (int *)dhist; ts.key_ts = (unsigned long long *)dkts; ts.lse = (float *)dlse;
+        ts.ts_begin = io->ts_begin; ts.eot = io->eot; ts.n_vocab = V; ts.max_initial = io->max_initial;
+        if (io->ts_mode == 1) WM_TRY(wm_ts_init(ctx, ts, B));
+    }
+    WmXDev xd;
+    memset(&xd, 0, sizeof(xd));
+    WM_TRY(pool.get(&dns, nan32.data(), (size_t)B * 4, s));
+    WM_TRY(pool.get(&dlp, nan32.data(), (size_t)n_ctx * B * 4, s));
+    if (io->x_on) {
+        WM_TRY(pool.get(&dxp, &xp, sizeof(xp), s));
+        WM_TRY(pool.get(&dtxt, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&dwin, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&dall, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&dnsv, nullptr, (size_t)B * 4, s, 0xff));
+        xd.par = (const WmXPar *)dxp; xd.txt = (float *)dtxt; xd.win = (float *)dwin; xd.all = (float *)dall; xd.ns_v = (float *)dnsv;
+        xd.logprob = (float *)dlp; xd.nospeech = (float *)dns;
+    }
+    WmStopDev sp;
+    memset(&sp, 0, sizeof(sp));
+    if (io->stop_on) {
+        WM_TRY(pool.get(&ddone, nullptr, (size_t)B * 4, s));
+        WM_TRY(pool.get(&dlive, nullptr, (size_t)B * 4, s));
+        WM_TRY(pool.get(&dnl, nullptr, 4, s));
+        if (io->budget) WM_TRY(pool.get(&dbud, io->budget, (size_t)B * 4, s));
+        sp.done = (int *)ddone; sp.budget = (const int *)dbud; sp.live_rows = (int *)dlive; sp.n_live = (int *)dnl;
+        sp.eot = io->stop_eot; sp.pad_tok = io->pad_tok;
+        WM_TRY(wm_stop_init(ctx, sp, B));
+        WM_HIP(hipMemcpyAsync(ddone, io->done, (size_t)B * 4, hipMemcpyHostToDevice, s));   // the flags of the positions before this one
+        WM_HIP(hipMemsetAsync(dlive, 0xff, (size_t)B * 4, s));   // -1: the close rebuilds the list, what it leaves alone shows
+    }
+    if (io->off) WM_TRY(pool.get(&doff, io->off, (size_t)B * 4, s));
+    WM_TRY(pool.get(&dxn, nan32.data(), (size_t)B * K * 4, s));
+    WM_TRY(pool.get(&dxbn, nan16.data(), nan16.size() * 2, s));
+    WM_TRY(pool.get(&dstn, nan32.data(), st_words * 4, s));
+    WM_TRY(pool.get(&dmn, nullptr, (size_t)B * 4, s));
+    WM_TRY(wm_ln_fold(ctx, (const bf16_t *)dE, (const float *)dg, (const float *)db, (const float *)dbias, V, K, (bf16_t *)dEf,
+                      (float *)dc1, (float *)dc2));
+    DecGemvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.epi = io->x_on ? DE_LOGITS_X : DE_LOGITS; a.B = B; a.N = V; a.K = K; a.W = (const bf16_t *)dEf; a.c1 = (const float *)dc1;
+    a.c2 = (const float *)dc2; a.a = (const bf16_t *)dx16; a.stats_in = (const float *)dst; a.stats_parts = K / 16;
+    a.mean_in = (const float *)dmin; a.mean_out = (float *)dmout;
+    a.out_f32 = (float *)dlog; a.ldo = vpad; a.argmax = (unsigned long long *)dtm; a.arg_first = io->arg_first; a.arg_last = io->arg_last;
+    a.pos_ptr = (const int *)dpos;
+    if (mask_on) { a.mask = (const unsigned *)dmask; a.mask_words = mw; a.mask_first_pos = io->mask_first ? pos : -1; }
+    a.ts = ts;
+    a.x = xd;
+    WM_TRY(wm_dec_gemv(ctx, a));
+    WM_TRY(wm_argmax_embed(ctx, (const unsigned long long *)dtm, n_tiles, B, (int *)dseq, (int *)dpos, n_prompt, (int *)dres, io->arg_first,
+                           (const bf16_t *)dE, (const float *)dpemb, K, n_ctx, (float *)dxn, (bf16_t *)dxbn, (float *)dstn,
+                           io->ts_mode ? &ts : nullptr, (int *)darr, io->fallback_tok, (float *)dmn, io->stop_on ? &sp : nullptr,
+                           io->x_on ? &xd : nullptr, (const int *)doff));
+    std::vector<float> lg((size_t)B * vpad), lp((size_t)n_ctx * B), stn(st_words);
+    std::vector<bf16_t> xbn(nan16.size());
+    WM_HIP(hipMemcpyAsync(lg.data(), dlog, lg.size() * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->result, dres, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->seq, dseq, (size_t)n_ctx * B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(lp.data(), dlp, lp.size() * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->nospeech, dns, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(&io->pos_out, dpos, 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(&io->arrive_out, darr, 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->x_next, dxn, (size_t)B * K * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(xbn.data(), dxbn, xbn.size() * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(stn.data(), dstn, stn.size() * 4, hipMemcpyDeviceToHost, s));
+    if (io->ts_mode) {
+        WM_HIP(hipMemcpyAsync(io->rng, drng, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->hist, dhist, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+    }
+    io->n_live = -1;
+    if (io->stop_on) {
+        WM_HIP(hipMemcpyAsync(io->done, ddone, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->live_rows, dlive, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(&io->n_live, dnl, 4, hipMemcpyDeviceToHost, s));
+    }
+    WM_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+        memcpy(io->logits + (size_t)b * V, lg.data() + (size_t)b * vpad, (size_t)V * 4);
+        io->tok[b] = io->result[b] + io->arg_first;
+    }
+    const int gi = pos + 1 - n_prompt;
+    io->logprob_written = 0;
+    for (size_t i = 0; i < lp.size(); ++i) {
+        uint32_t u;
+        memcpy(&u, &lp[i], 4);
+        io->logprob_written += u != WMDBG_SENTINEL_F32;
+    }
+    memcpy(io->logprob, gi >= 0 ? (const void *)(lp.data() + (size_t)gi * B) : (const void *)nan32.data(), (size_t)B * 4);
+    untile_bf16(xbn, (size_t)B, (size_t)K, io->xb_next);
+    io->stats_tail_nonzero = 0;
+    for (int b = 0; b < B; ++b) {   // block (b / 16): [K/16 parts][16][2], summed as wmdbg_dec_gemv_resid sums them
+        const float *blk = stn.data() + (size_t)(b >> 4) * 2 * K;
+        float s1 = 0.f, s2 = 0.f;
+        for (int part = 0; part < K / 16; ++part)
+            for (int c = 0; c < 2; ++c) {
+                const float v = blk[(part * 16 + (b & 15)) * 2 + c];
+                (c ? s2 : s1) += v;
+                uint32_t u;
+                memcpy(&u, &v, 4);
+                if (part > 0 && u != 0u) ++io->stats_tail_nonzero;
+            }
+        io->stats_next[b * 2] = s1;
+        io->stats_next[b * 2 + 1] = s2;
+    }
+    return WM_OK;
 }
