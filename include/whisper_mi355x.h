@@ -382,6 +382,64 @@ WM_API int wm_align_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_base, 
                         int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
                         int medfilt_width, float qk_scale, int32_t *start_frame_out, float *token_prob_out, wm_mem mem);
 
+/* ------------------------------------------------------------- window sets --- */
+/* Every call above that takes mel windows runs the encoder and the cross-attention K/V projection of its rows.  A caller that
+ * decodes the same window more than once -- openai-whisper's temperature fallback (up to six decodes of a hard window), the
+ * word-timestamp pass behind it, language identification on the first 30 s -- encodes it ONCE into a window set and reads the
+ * set from then on: everything downstream of the encoder reads a window's cross-attention K/V only. */
+typedef struct wm_windows wm_windows;
+
+/* Encode W mel windows ONCE and keep their cross-attention K/V (bf16) on the device.  Window description and `mem` exactly as
+ * wm_transcribe_mel (gather fused into the encoder's first step; WM_MEM_HOST copies only the windows).  Runs in decode groups
+ * of at most 128 rows on the context's stream; returns when the set is complete.  W >= 1.
+ * The set is immutable.  It remembers each window's n_frames, and the weights, dims and device it was made for: the context
+ * that made it and every wm_clone of that context or of its parent may read it (the lanes inside a call are such clones), any
+ * other context gets WM_ERR_INVALID.  Its store is an allocation of its own -- no call made between the encode and a read
+ * disturbs it -- of W * n_text_layer * 2 * 1500 * n_text_state * 2 bytes: 246 MB PER WINDOW at large-v2 (11 MB at tiny), so
+ * size sets by the memory you can spare.  A failed allocation is WM_ERR_NOMEM and leaks nothing.  Free the set before the
+ * context.  Not supported by the debug library's all-f32 precision path (WM_ERR_STATE).
+ * wm_last_stage_ms afterwards: [0] the window copies (WM_MEM_HOST), [1] encoder + cross-K/V projection + the copy into the
+ * store, [2] 0. */
+WM_API int  wm_windows_encode(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                              const int32_t *seek, const int32_t *n_frames, int W, wm_mem mem, wm_windows **out);
+WM_API void wm_windows_free(wm_windows *w);            /* NULL: no-op; may synchronise the device */
+WM_API int  wm_windows_count(const wm_windows *w);     /* W; a null set: -1 */
+WM_API size_t wm_windows_bytes(const wm_windows *w);   /* device bytes held: W * n_text_layer * 2 * 1500 * n_text_state * 2 */
+
+/* The mel calls over the windows of a set: (w, rows, B) in place of the five mel arguments and `mem`.
+ *   rows : i32 [B] (host) indices into the set, any order, repeats allowed; NULL: 0 .. B - 1, and B must be the set's W;
+ *   every output is host memory.
+ * At the prefill of each decode group the rows' K/V is copied from the set into the lane (one launch) where the mel call
+ * runs the encoder.  BIT FOR BIT the result of the corresponding mel call on the same windows, with every other promise of
+ * that call: a row depends only on itself, not on the grouping or the lanes; token budgets, suppress lists, timestamp rules,
+ * early stop as before.
+ *   wm_transcribe_windows      = wm_transcribe_mel_best_of (so best_of = 1 is wm_transcribe_mel_ragged with prompt_len, and
+ *                                wm_transcribe_mel with prompt_len NULL);
+ *   wm_transcribe_windows_beam = wm_transcribe_mel_beam;
+ *   wm_align_windows           = wm_align_mel, find_alignment's num_frames being the set's n_frames of the row (>= 2);
+ *   wm_windows_detect_language = wm_encode of the window zero-padded to 3000 frames followed by wm_detect_language_probs
+ *                                (probs nullable: wm_detect_language), B <= 128.
+ * wm_last_stage_ms after wm_transcribe_windows(_beam) and wm_windows_detect_language: [0] the copy from the set, [1] 0,
+ * [2] the decode loop / the decoder step; after wm_align_windows: [0] the copy, [1] and [2] as wm_align.
+ * Invalid: a null set, a row outside [0, W), rows NULL with B != W, a set of another model, device or dims,
+ * wm_align_windows on a window of fewer than 2 frames, and everything the mel counterpart rejects. */
+WM_API int wm_transcribe_windows(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                 int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                 int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                 int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                 int32_t *best_out);
+WM_API int wm_transcribe_windows_beam(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                      int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size,
+                                      int max_candidates, float length_penalty, int max_new, int32_t eot,
+                                      const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out,
+                                      float *sum_logprobs_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                      int32_t *best_out);
+WM_API int wm_align_windows(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *sot_seqs, int n_sot,
+                            int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text, int max_text,
+                            int medfilt_width, float qk_scale, int32_t *start_frame_out, float *token_prob_out);
+WM_API int wm_windows_detect_language(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, int32_t sot,
+                                      int32_t lang_first, int32_t lang_last, int32_t *lang_idx, float *probs /* nullable */);
+
 /* The alignment heads wm_align and wm_align_mel read: n (layer, head) pairs, any order (used ascending).  n = 0 restores the default, every
  * head of the decoder layers n_text_layer / 2 .. n_text_layer - 1 (openai-whisper's default when a checkpoint has no list);
  * a checkpoint's own list (openai-whisper _ALIGNMENT_HEADS, Hugging Face generation_config.alignment_heads) comes from the

@@ -244,6 +244,12 @@ WM_API int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V, in
  * [rows / N]: 1 = the window has just left the decode (its histories move, its cache does not). */
 WM_API int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows, int H, int T, int N, int pos, int n_prompt,
                               const int32_t *src, const int32_t *wdone, int32_t *seq, float *logprob);
+/* The window-set copy kernel alone (xkv_rows.hip), on DEVICE buffers of the caller (16-byte aligned, bf16 bits): group u16
+ * [2 * L][group_rows][H][1500][64], a decode group's cross-K/V cache, and store u16 [store_rows][2 * L][H][1500][64], a set's
+ * window-major store.  Group row b <-> store row rows[b] (i32 [n_rows], host; every entry in [0, store_rows)), b < n_rows <=
+ * group_rows <= 128.  to_store != 0: group -> store (the rows must differ), else store -> group.  Synchronous. */
+WM_API int wmdbg_xkv_rows(wm_ctx *ctx, uint16_t *group, int group_rows, uint16_t *store, int64_t store_rows, const int32_t *rows,
+                          int n_rows, int L, int H, int to_store);
 
 #ifdef __cplusplus
 }

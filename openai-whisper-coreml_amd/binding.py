@@ -125,6 +125,14 @@ def load_library(path=None):
         "wm_align": [vp, vp, ip, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, vp, ip, ctypes.c_float, vp, vp, ip],
         "wm_align_mel": [vp, vp, vp, vp, vp, vp, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, ip, ctypes.c_float, vp, vp,
                          ip],
+        "wm_windows_encode": [vp, vp, vp, vp, vp, vp, ip, ip, pp],
+        "wm_windows_count": [vp],
+        "wm_transcribe_windows": [vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_float, ip, ctypes.c_int32, vp, vp, vp, vp, vp,
+                                  vp],
+        "wm_transcribe_windows_beam": [vp, vp, vp, ip, vp, ip, vp, ip, ip, ip, ctypes.c_float, ip, ctypes.c_int32, vp, vp, vp, vp,
+                                       vp, vp, vp, vp],
+        "wm_align_windows": [vp, vp, vp, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, ip, ctypes.c_float, vp, vp],
+        "wm_windows_detect_language": [vp, vp, vp, ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp],
         "wm_set_lanes": [vp, ip],
         "wm_dev_malloc": [vp, sz, pp],
         "wm_dev_free": [vp, vp],
@@ -156,6 +164,10 @@ def load_library(path=None):
         fn.restype = ctypes.c_int
     lib.wm_destroy.argtypes = [vp]
     lib.wm_destroy.restype = None
+    lib.wm_windows_free.argtypes = [vp]
+    lib.wm_windows_free.restype = None
+    lib.wm_windows_bytes.argtypes = [vp]
+    lib.wm_windows_bytes.restype = sz
     lib.wm_multi_destroy.argtypes = [vp]
     lib.wm_multi_destroy.restype = None
     lib.wm_vocab_free.argtypes = [vp]
@@ -542,7 +554,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None, condition_on_previous_text=False,
                     prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
                     prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
-                    patience=None):
+                    patience=None, reuse_encoder=False):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings; hallucination_silence_threshold
     and clip_timestamps are not implemented.  condition_on_previous_text defaults to False here (openai-whisper: True);
     see 5.  word_timestamps: see 6.
@@ -584,6 +596,13 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        temperature 0 are unchanged (openai-whisper uses beam_size at temperature 0 and best_of above it).  Every window
        record then has `hypothesis`, the index that was kept (0 when a later step replaced the beam result).  patience
        without beam_size is a ValueError; with beam_size None the calls made are exactly those without the argument.
+    9. reuse_encoder=True: every window is encoded ONCE.  A round makes one wm_windows_encode of its live windows; every
+       fallback step decodes the rows it still has to do from that set (wm_transcribe_windows / _beam), the word step aligns
+       its kept rows from it (wm_align_windows), and the set is freed before the next round begins, also on an exception.
+       Language identification becomes one wm_windows_encode of every recording's frames [0, 3000) plus
+       wm_windows_detect_language, without host round trips.  The result equals the reuse_encoder=False run in every field;
+       what it costs is the sets' device memory (Windows.nbytes: 246 MB per live recording at large-v2).  The default,
+       False, makes exactly the calls this function made before the argument existed.
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
     no prompt).  Without conditioning a recording's list heads every one of its windows; with it, it seeds the history.
     Sets the context's timestamp rules (wm_set_timestamp_rules: timestamp_begin, eot, max initial timestamp 1.0 s);
@@ -622,12 +641,19 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     if R == 0:
         return out
     d_mel, mel_offs, T = ctx.logmel_long(recordings, n_mels=n_mels, device=True)
+    wset = None   # reuse_encoder: the Windows of the round in progress
     try:
         content = [int(t) - N_FRAMES for t in T]
         # 2. language
         if language is None:
             if lang_first is None or lang_last is None:
                 raise ValueError("language detection needs lang_first / lang_last")
+        if language is None and reuse_encoder:
+            with ctx.encode_windows(d_mel, mel_offs[:R], T, 0, N_FRAMES, mem=WM_MEM_DEVICE) as lid_set:
+                idx = np.concatenate([ctx.windows_detect_language(lid_set, np.arange(a, min(a + 128, R)), sot, lang_first,
+                                                                  lang_last)[0] for a in range(0, R, 128)])
+            langs = [int(lang_first + i) for i in idx]
+        elif language is None:
             win = np.empty((R, n_mels, N_FRAMES), dtype=np.float32)
             for r in range(R):
                 for c in range(n_mels):
@@ -662,6 +688,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             out[r]["language"] = langs[r]
         # 3. rounds in lockstep
         while True:
+            if wset is not None:   # the previous round's set
+                wset.close()
+                wset = None
             live = [r for r in range(R) if seek[r] < content[r]]
             if not live:
                 break
@@ -674,6 +703,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 plist = [head + [int(sot), langs[r], int(task)] for r in live]
                 prompts = np.array(plist, dtype=np.int32)
 
+            if reuse_encoder:   # 9. the round's windows, encoded once for every fallback step and the word step
+                wset = ctx.encode_windows(d_mel, mel_offs[live], T[live], [seek[r] for r in live], size, mem=WM_MEM_DEVICE)
+
             cand = {}   # best_of: row of the round -> candidate kept by its last step
             hyp = {}    # beam_size: row of the round -> hypothesis kept by its last step
 
@@ -684,7 +716,12 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 beam = beam_size is not None and t == 0
                 if beam:
                     extra = dict(beam_size=beam_size, patience=patience, length_penalty=length_penalty)
-                if ragged:
+                if wset is not None:   # rows of the round's set: the same call without the encoder pass
+                    r_ = ctx.transcribe_windows(wset, [int(i) for i in todo], [plist[i] for i in todo] if ragged else prompts[todo],
+                                                max_new, eot=eot, temperature=t, seed=sd, no_speech_token=no_speech_token,
+                                                sample_ids=[ids[i] for i in todo],
+                                                **(dict(sot_tail=3) if ragged else dict(sot_index=sot_index)), **extra)
+                elif ragged:
                     r_ = ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
                                             [size[i] for i in todo], [plist[i] for i in todo], max_new, eot=eot,
                                             temperature=t, seed=sd, no_speech_token=no_speech_token, sot_tail=3,
@@ -743,10 +780,15 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             go = [n for n, k in enumerate(kept) if texts[n] and size[k[0]] >= 2]
             if go:
                 rows = [live[kept[n][0]] for n in go]
-                sf, pr = ctx.align_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
-                                       [size[kept[n][0]] for n in go], [texts[n] for n in go],
-                                       [[int(sot), langs[r], int(task)] for r in rows], no_timestamps, eot,
-                                       medfilt_width=7, qk_scale=1.0, mem=WM_MEM_DEVICE)
+                if wset is not None:
+                    sf, pr = ctx.align_windows(wset, [kept[n][0] for n in go], [texts[n] for n in go],
+                                               [[int(sot), langs[r], int(task)] for r in rows], no_timestamps, eot,
+                                               medfilt_width=7, qk_scale=1.0)
+                else:
+                    sf, pr = ctx.align_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
+                                           [size[kept[n][0]] for n in go], [texts[n] for n in go],
+                                           [[int(sot), langs[r], int(task)] for r in rows], no_timestamps, eot,
+                                           medfilt_width=7, qk_scale=1.0, mem=WM_MEM_DEVICE)
             for n, (i, segs, next_seek, single_ending) in enumerate(kept):
                 r = live[i]
                 if n in go:
@@ -773,11 +815,47 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     sg["id"] = len(out[r]["segments"])
                     out[r]["segments"].append(sg)
     finally:
+        if wset is not None:
+            wset.close()
         ctx.dev_free(d_mel)
     if vocab is not None:
         for o in out:
             o["text"] = vocab.decode([t for sg in o["segments"] for t in sg["tokens"] if t < eot])
     return out
+
+
+class Windows:
+    """RAII wrapper over wm_windows (Context.encode_windows): the encoded state -- cross-attention K/V -- of W mel windows,
+    read by Context.transcribe_windows*, align_windows and windows_detect_language of the context that made it and of its
+    clones.  n_frames i32 [W]: the windows' mel frames.  Close it (or leave its `with` block) before the context."""
+
+    def __init__(self, ctx, handle, n_frames):
+        self.ctx, self.lib, self.handle, self.n_frames = ctx, ctx.lib, handle, n_frames
+
+    def __len__(self):
+        return int(self.lib.wm_windows_count(self.handle))
+
+    @property
+    def nbytes(self):
+        """device bytes the set holds"""
+        return int(self.lib.wm_windows_bytes(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle:
+            self.lib.wm_windows_free(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class Context:
@@ -1080,6 +1158,18 @@ class Context:
         mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (B,)))
         sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (B,)))
         nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
+        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
+        if mem == WM_MEM_HOST:
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            mp = _ptr(mel)
+        else:
+            mp = mel
+        return mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids
+
+    @staticmethod
+    def _prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail):
+        """The prompt arrays of a B-row wm_transcribe_mel* / wm_transcribe_windows* call: (prompts [B][stride], prompt_len or
+        None, opts, sample_ids or None)."""
         plen = None
         if prompt_len is not None:
             plen = np.ascontiguousarray(prompt_len, dtype=np.int32)
@@ -1096,14 +1186,9 @@ class Context:
         if plen is None and sot_tail is not None and opts is not None:
             opts = wm_decode_opts(opts.temperature, opts.seed, opts.no_speech_token, pr.shape[1] - int(sot_tail))
         ids = None if sample_ids is None else np.ascontiguousarray(sample_ids, dtype=np.uint32)
-        if mem == WM_MEM_HOST:
-            mel = np.ascontiguousarray(mel, dtype=np.float32)
-            mp = _ptr(mel)
-        else:
-            mp = mel
         if plen is not None and plen.shape != (B,):
             raise ValueError("prompt_len: one length per row")
-        return mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids
+        return pr, plen, opts, ids
 
     def transcribe_mel_raw(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, opts=None,
                            sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
@@ -1223,6 +1308,145 @@ class Context:
                                                      sample_ids, logprobs=True, no_speech=no_speech_token >= 0, mem=mem,
                                                      budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail)
         return TranscribeResult(toks, lens, lp, ns, eot)
+
+    # ---- window sets ----------------------------------------------------------------
+    def encode_windows(self, mel, mel_base, mel_len, seek, n_frames, mem=WM_MEM_HOST):
+        """wm_windows_encode: run the encoder and the cross-K/V projection of the windows ONCE (the window description of
+        transcribe_mel_raw) and keep the result on the device.  Returns a Windows; close it before this context."""
+        base = np.ascontiguousarray(mel_base, dtype=np.int64)
+        W = base.size
+        mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (W,)))
+        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (W,)))
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (W,)))
+        if mem == WM_MEM_HOST:
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            mp = _ptr(mel)
+        else:
+            mp = mel
+        h = ctypes.c_void_p()
+        _check(self.lib, self.lib.wm_windows_encode(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), W, mem,
+                                                    ctypes.byref(h)))
+        return Windows(self, h, nf.copy())
+
+    @staticmethod
+    def _window_rows(windows, rows):
+        """(rows i32 array or None, B) of a call that reads a set"""
+        if rows is None:
+            return None, len(windows)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        return r, int(r.size)
+
+    def transcribe_windows_best_of(self, windows, rows, prompts, max_new, best_of=1, eot=-1, temperature=0.0, seed=0,
+                                   no_speech_token=-1, sot_index=0, sample_ids=None, budgets=None, prompt_len=None,
+                                   sot_tail=None, length_penalty=None):
+        """wm_transcribe_windows: transcribe_mel_best_of with rows of a Windows set (rows None: all of them, in order) in
+        place of the mel windows.  Same bits.  Returns a BestOfResult."""
+        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        r, B = self._window_rows(windows, rows)
+        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
+        N = int(best_of)
+        shape = (B, max(N, 1), max_new)
+        toks = np.empty(shape, dtype=np.int32)
+        lens = np.empty(shape[:2], dtype=np.int32)
+        lp = np.empty(shape, dtype=np.float32)
+        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
+        best = np.empty(B, dtype=np.int32)
+        _check(self.lib, self.lib.wm_transcribe_windows(
+            self.handle, windows.handle, _ptr(r) if r is not None else None, B, _ptr(pr), pr.shape[1],
+            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail),
+            _ptr(ids) if ids is not None else None, N, float("nan") if length_penalty is None else float(length_penalty),
+            max_new, eot, ctypes.byref(opts), _ptr(toks), _ptr(lens), _ptr(lp), _ptr(ns) if ns is not None else None,
+            _ptr(best)))
+        return BestOfResult(toks, lens, lp, ns, best, eot)
+
+    def transcribe_windows_beam(self, windows, rows, prompts, max_new, beam_size, eot=-1, patience=None, no_speech_token=-1,
+                                sot_index=0, budgets=None, prompt_len=None, sot_tail=None, length_penalty=None,
+                                max_candidates=None):
+        """wm_transcribe_windows_beam: transcribe_mel_beam with rows of a Windows set.  Same bits.  Returns a BeamResult."""
+        if max_candidates is None:
+            max_candidates = beam_max_candidates(beam_size, patience)
+        elif patience is not None:
+            raise ValueError("give patience or max_candidates, not both")
+        opts = wm_decode_opts(0.0, 0, int(no_speech_token), int(sot_index))
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        r, B = self._window_rows(windows, rows)
+        pr, plen, opts, _ = self._prompt_call_args(B, prompts, opts, None, prompt_len, sot_tail)
+        N, C = int(beam_size), int(max_candidates)
+        shape = (B, max(N, C, 1), max_new)
+        toks = np.empty(shape, dtype=np.int32)
+        lens = np.empty(shape[:2], dtype=np.int32)
+        n_hyp = np.empty(B, dtype=np.int32)
+        sums = np.empty(shape[:2], dtype=np.float32)
+        lp = np.empty(shape, dtype=np.float32)
+        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
+        best = np.empty(B, dtype=np.int32)
+        _check(self.lib, self.lib.wm_transcribe_windows_beam(
+            self.handle, windows.handle, _ptr(r) if r is not None else None, B, _ptr(pr), pr.shape[1],
+            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail), N, C,
+            float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts), _ptr(toks),
+            _ptr(lens), _ptr(n_hyp), _ptr(sums), _ptr(lp), _ptr(ns) if ns is not None else None, _ptr(best)))
+        return BeamResult(toks, lens, n_hyp, sums, lp, ns, best, eot)
+
+    def transcribe_windows(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
+                           sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, best_of=None,
+                           length_penalty=None, beam_size=None, patience=None):
+        """transcribe_mel with rows of a Windows set in place of the mel windows: the same bits, no encoder pass.  Returns a
+        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel)."""
+        if beam_size is not None or patience is not None:
+            if best_of is not None:
+                raise ValueError("beam_size and best_of exclude each other (openai-whisper)")
+            if temperature != 0:
+                raise ValueError("beam search decodes at temperature 0")
+            beam_max_candidates(beam_size, patience)
+            return self.transcribe_windows_beam(windows, rows, prompts, max_new, beam_size, eot=eot, patience=patience,
+                                                no_speech_token=no_speech_token, sot_index=sot_index, budgets=budgets,
+                                                prompt_len=prompt_len, sot_tail=sot_tail, length_penalty=length_penalty).selected
+        r = self.transcribe_windows_best_of(windows, rows, prompts, max_new, 1 if best_of is None else best_of, eot=eot,
+                                            temperature=temperature, seed=seed, no_speech_token=no_speech_token,
+                                            sot_index=sot_index, sample_ids=sample_ids, budgets=budgets, prompt_len=prompt_len,
+                                            sot_tail=sot_tail, length_penalty=length_penalty)
+        if best_of is not None:
+            return r.selected
+        return TranscribeResult(np.ascontiguousarray(r.tokens[:, 0]), np.ascontiguousarray(r.lens[:, 0]),
+                                np.ascontiguousarray(r.logprobs[:, 0]), r.no_speech_prob, eot)
+
+    def align_windows(self, windows, rows, text_tokens, sot_seqs, no_timestamps, eot, medfilt_width=7, qk_scale=1.0):
+        """wm_align_windows: align_mel with rows of a Windows set (each of at least 2 frames); the alignment covers the set's
+        own n_frames of a row.  Returns (start_frames, token_probs) as align."""
+        r, B = self._window_rows(windows, rows)
+        toks = [list(np.asarray(t).reshape(-1)) for t in text_tokens]
+        if len(toks) != B:
+            raise ValueError("text_tokens: %d lists for %d windows" % (len(toks), B))
+        max_text = max([len(t) for t in toks] + [0])
+        tt = np.zeros((B, max(max_text, 1)), dtype=np.int32)
+        for b, t in enumerate(toks):
+            tt[b, :len(t)] = t
+        nt = np.ascontiguousarray([len(t) for t in toks], dtype=np.int32)
+        sot = np.asarray(sot_seqs, dtype=np.int32)
+        if sot.ndim == 1:
+            sot = np.broadcast_to(sot, (B, sot.size))
+        if sot.ndim != 2 or sot.shape[0] != B:
+            raise ValueError("sot_seqs: one start sequence, or one per window")
+        sot = np.ascontiguousarray(sot)
+        start = np.empty((B, max_text + 1), dtype=np.int32)
+        probs = np.empty((B, max_text), dtype=np.float32)
+        _check(self.lib, self.lib.wm_align_windows(self.handle, windows.handle, _ptr(r) if r is not None else None, B, _ptr(sot),
+                                                   sot.shape[1], int(no_timestamps), int(eot), _ptr(tt), _ptr(nt), max_text,
+                                                   int(medfilt_width), float(qk_scale), _ptr(start), _ptr(probs)))
+        return start, probs
+
+    def windows_detect_language(self, windows, rows=None, sot=50258, lang_first=50259, lang_last=50357):
+        """wm_windows_detect_language: detect_language_probs of encode_mel of the rows' zero-padded windows, from the set.
+        Returns (lang_idx [B], probs [B][n_lang])."""
+        r, B = self._window_rows(windows, rows)
+        idx = np.empty(B, dtype=np.int32)
+        probs = np.empty((B, lang_last - lang_first + 1), dtype=np.float32)
+        _check(self.lib, self.lib.wm_windows_detect_language(self.handle, windows.handle, _ptr(r) if r is not None else None, B,
+                                                             sot, lang_first, lang_last, _ptr(idx), _ptr(probs)))
+        return idx, probs
 
     def transcribe_long(self, recordings, **kw):
         """openai-whisper's long-form transcribe() (module function transcribe_long) on this context."""

@@ -970,6 +970,30 @@ extern "C" int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows
     return rc;
 }
 
+// ------------------------------------------------------------------ window sets: the copy kernel ----
+extern "C" int wmdbg_xkv_rows(wm_ctx *ctx, uint16_t *group, int group_rows, uint16_t *store, int64_t store_rows, const int32_t *rows,
+                              int n_rows, int L, int H, int to_store) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(group && store && rows && L >= 1 && H >= 1 && n_rows >= 1 && n_rows <= group_rows && group_rows <= WM_DEC_MAXB &&
+                   store_rows >= 1, WM_ERR_INVALID, "xkv_rows: bad args");
+    for (int b = 0; b < n_rows; ++b) {
+        WM_REQUIRE(rows[b] >= 0 && rows[b] < store_rows, WM_ERR_INVALID, "xkv_rows: rows[%d] = %d outside [0, %lld)", b, rows[b],
+                   (long long)store_rows);
+        for (int o = 0; to_store && o < b; ++o)
+            WM_REQUIRE(rows[o] != rows[b], WM_ERR_INVALID, "xkv_rows: store row %d named twice", rows[b]);
+    }
+    hipStream_t s = ctx->stream;
+    void *drows;
+    WM_TRY(up(&drows, rows, (size_t)n_rows * 4, s));
+    int rc = wm_xkv_rows(ctx, group, group_rows, store, (const int *)drows, 0, n_rows, 2 * L, (long)H * 1500 * 64, to_store != 0);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == WM_OK) {
+        wm_set_error("xkv_rows: %s", hipGetErrorString(hipGetLastError()));
+        rc = WM_ERR_HIP;
+    }
+    (void)hipFree(drows);
+    return rc;
+}
+
 // ------------------------------------------------------------------ the decode step's LN-folded GEMV and its close ----
 namespace {
 // device allocations of one hook call, freed when it returns (on an error path too)

@@ -80,6 +80,7 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     // (+16: the epilogue's padded 16-row blocks; second half: the rows' candidate words, WM_XIDS_CAND)
     WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)2 * WM_XIDS_CAND, s));
     WM_TRY(dalloc_t(m, &m->dmel_win, (size_t)WM_DEC_MAXB, s));
+    WM_TRY(dalloc_t(m, &m->dxkv_rows, (size_t)WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dmask, (size_t)2 * (m->vpad / 32), s));
     WM_HIP(hipMemsetAsync(m->dmask, 0, (size_t)2 * (m->vpad / 32) * 4, s));
     return WM_OK;

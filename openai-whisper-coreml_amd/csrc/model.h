@@ -341,6 +341,7 @@ struct WmModel {
     WmXPar *dx_par = nullptr;
     unsigned *dx_ids = nullptr;    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
+    int *dxkv_rows = nullptr;      // [WM_DEC_MAXB] the group's rows of a window set (wm_transcribe_windows): the gather's row map
     // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..), the
     // workspace of a call (grown on demand) and the debug library's one-shot cost-matrix capture (host, null in the product)
     std::vector<int32_t> align_l, align_h;
@@ -355,6 +356,20 @@ struct WmModel {
     bool beam_trace_on = false;   // the group decoding on this context right now writes its trace
     WmDevBuf pcm_stage;   // host-pointer staging of a decode group's PCM (wm_transcribe*, wm_align)
     WmDevBuf io_stage;    // staging for host-pointer model calls
+};
+
+// An immutable set of encoded windows (wm_windows_encode): the cross-attention K/V of W windows, window-major
+// [W][L][2][H][1500][64] bf16 -- one window's 2L slabs are contiguous --, in a device allocation of its own: no lane's
+// WmModel::xkv, so nothing a context runs between the encode and a read disturbs it.  A call that reads the set copies the
+// rows of each decode group into the lane's xkv (wm_xkv_rows) where the encoder + wm_model_cross_kv would have left them.
+struct wm_windows {
+    int device = 0;
+    wm_dims dims = {};
+    const void *weights = nullptr;   // WmModel::tok_emb of the context that made it: every wm_clone of that context aliases it
+    int W = 0;
+    std::vector<int32_t> n_frames;   // [W] mel frames of each window (find_alignment's num_frames)
+    bf16_t *store = nullptr;
+    size_t bytes = 0;
 };
 
 // model.cpp
@@ -563,6 +578,13 @@ int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_pro
 // self-attention K/V (skv [L2][rows][H][T][64]) and the rows' token / log-prob histories.  Call after wm_beam_select_step.
 int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, const int *pos_ptr, int n_prompt, int *seq,
                     float *logprob, const WmBeamDev &bm);
+
+// xkv_rows.hip (window sets)
+// Copy whole windows between a decode group's cross-attention K/V cache, group [L2][group_rows][slab] (slab = H * 1500 * 64
+// elements, L2 = 2 * n_text_layer), and a window-major store [.][L2][slab]: group row b <-> store row d_rows[b] (device,
+// nullable: row0 + b), b < n_rows <= group_rows.  to_store: group -> store (the rows of d_rows must differ), else store -> group.
+int wm_xkv_rows(wm_ctx *ctx, bf16_t *group, long group_rows, bf16_t *store, const int *d_rows, int row0, int n_rows, int L2,
+                long slab, bool to_store);
 
 // align.hip (word-level timestamps)
 // the alignment heads' queries of decode position *pos_ptr: dq [B][d] -> cap[b][*pos_ptr][L.slot0 + k][64]

@@ -291,7 +291,8 @@ extern "C" int wm_decode_logits(wm_ctx *ctx, const int32_t *tokens, int B, int T
 } WM_API_CATCH
 
 static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot, int32_t lang_first, int32_t lang_last,
-                                int32_t *lang_idx, float *probs, wm_mem mem);
+                                int32_t *lang_idx, float *probs, wm_mem mem, const wm_windows *set = nullptr,
+                                const int32_t *rows = nullptr);
 
 extern "C" int wm_detect_language(wm_ctx *ctx, const float *xa, int B, int32_t sot, int32_t lang_first,
                                   int32_t lang_last, int32_t *lang_idx, wm_mem mem) try {
@@ -304,10 +305,13 @@ extern "C" int wm_detect_language_probs(wm_ctx *ctx, const float *xa, int B, int
     return detect_language_impl(ctx, xa, B, sot, lang_first, lang_last, lang_idx, probs, mem);
 } WM_API_CATCH
 
+// (set: the features are rows of a window set -- wm_windows_detect_language, below the audio-source helpers -- and xa is null)
+static int windows_cross_kv(wm_ctx *ctx, const wm_windows *set, const int32_t *rows, int B, std::vector<int32_t> &map);
+
 static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot, int32_t lang_first, int32_t lang_last,
-                                int32_t *lang_idx, float *probs, wm_mem mem) {
+                                int32_t *lang_idx, float *probs, wm_mem mem, const wm_windows *set, const int32_t *rows) {
     WM_MODEL(ctx);
-    WM_REQUIRE(xa && lang_idx, WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE((xa || set) && lang_idx, WM_ERR_INVALID, "null pointer");
     WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB, WM_ERR_INVALID, "B must be 1..%d", WM_DEC_MAXB);
     const int V = m->dims.n_vocab;
     WM_REQUIRE(sot >= 0 && sot < V && lang_first >= 0 && lang_first <= lang_last && lang_last < V, WM_ERR_INVALID,
@@ -317,7 +321,25 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
     // a buffer that outlives the call, uploaded FIRST, and the features' K/V GEMMs + the decoder step are enqueued behind it)
     m->lid_host.assign(B, sot);  // Whisper.swift:34-35
     WM_HIP(hipMemcpyAsync(m->dseq, m->lid_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_TRY(load_xa(ctx, xa, B, mem));
+    std::vector<int32_t> map;   // a set's row map, the source of an asynchronous upload: error paths must not outlive it
+    struct MapFence {
+        hipStream_t s;
+        bool on;
+        ~MapFence() { if (on) (void)hipStreamSynchronize(s); }
+    } fence{ctx->stream, set != nullptr};
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() { for (int i = 0; i < 3; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
+    } ev_guard{ev};
+    if (set) {
+        for (auto &e : ev) WM_HIP(hipEventCreate(&e));
+        WM_HIP(hipEventRecord(ev[0], ctx->stream));
+        WM_TRY(windows_cross_kv(ctx, set, rows, B, map));
+        WM_HIP(hipEventRecord(ev[1], ctx->stream));
+    } else {
+        WM_TRY(load_xa(ctx, xa, B, mem));
+    }
     WM_TRY(wm_model_set_pos(ctx, 0));
     WM_TRY(wm_model_embed_first(ctx, B));
     auto step = [&]() -> int {
@@ -350,9 +372,16 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
             WM_HIP(hipMemcpyAsync(probs, d_probs, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     // (the caller's buffer in device memory: one device-to-device copy behind the step)
+    if (set) WM_HIP(hipEventRecord(ev[2], ctx->stream));
     WM_HIP(hipMemcpyAsync(lang_idx, m->dresult, (size_t)B * 4, mem == WM_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                           ctx->stream));
     WM_HIP(hipStreamSynchronize(ctx->stream));
+    if (set) {   // wm_last_stage_ms of a call that read a set: the gather, no encoder stage, the decoder step
+        float ms;
+        ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ctx->stage_ms[0] = ms;
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) ctx->stage_ms[2] = ms;
+    }
     return WM_OK;
 }
 
@@ -400,6 +429,7 @@ struct LaneJob {
     std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
     std::vector<unsigned> ids;     // its sample ids (wm_transcribe_mel)
     std::vector<int32_t> off;      // its row offsets (wm_transcribe_mel_ragged)
+    std::vector<int32_t> xrows;    // its rows of the window set (wm_transcribe_windows)
     // a beam group (wm_transcribe_mel_beam): its parameters and window budgets (sources of async uploads) and what a drain
     // fetches: the state in front of the finished records, the finished tokens / log-probs of its windows, the debug trace
     WmBeamPar bpar = {};
@@ -417,13 +447,17 @@ struct LaneJob {
 };
 
 // where a call's encoder input comes from: PCM chunks [.][480000], or (mel non-null) mel windows -- row b is frames
-// seek[b] .. seek[b] + n_frames[b] - 1 of the [n_mels][mel_len[b]] block at mel + mel_base[b]
+// seek[b] .. seek[b] + n_frames[b] - 1 of the [n_mels][mel_len[b]] block at mel + mel_base[b] --, or (windows) nothing
+// to encode at all: row b is window rows[b] (rows null: b) of an encoded set, whose cross-attention K/V is copied
 struct WmAudioSrc {
     const void *pcm = nullptr;
     wm_dtype pcm_dtype = WM_F32;
     const float *mel = nullptr;
     const int64_t *mel_base = nullptr;
     const int32_t *mel_len = nullptr, *seek = nullptr, *n_frames = nullptr;
+    bool windows = false;   // the wm_*_windows calls: `set` is the source (null: an invalid call)
+    const wm_windows *set = nullptr;
+    const int32_t *rows = nullptr;
 };
 
 // a transcribe call's rows (wm_transcribe: PCM, wm_transcribe_mel: windows) and their prompts
@@ -488,12 +522,42 @@ int check_window(const WmAudioSrc &a, int b, const char *who) {
     return WM_OK;
 }
 
+// the pointers of a window source: the five of a mel call, or the set
+int check_src_pointers(const WmAudioSrc &a) {
+    if (a.windows) {
+        WM_REQUIRE(a.set != nullptr, WM_ERR_INVALID, "null window set");
+        return WM_OK;
+    }
+    WM_REQUIRE(a.mel && a.mel_base && a.mel_len && a.seek && a.n_frames, WM_ERR_INVALID, "null mel / window pointer");
+    return WM_OK;
+}
+
+// a set may be read by the context that made it and by every context that shares that one's weights
+int check_set_owner(const wm_ctx *ctx, const wm_windows *w) {
+    const WmModel *m = ctx->model;
+    WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "window sets are not supported by the all-f32 precision path");
+    WM_REQUIRE(w->device == ctx->device && w->weights == (const void *)m->tok_emb && memcmp(&w->dims, &m->dims, sizeof(wm_dims)) == 0,
+               WM_ERR_INVALID, "the window set was made for another model, device or dims");
+    return WM_OK;
+}
+
+// the B rows of a call that reads a set: every one a window of the set, made for this context's weights
+int check_set_rows(const wm_ctx *ctx, const WmAudioSrc &a, int B, const char *who) {
+    WM_REQUIRE(a.set != nullptr, WM_ERR_INVALID, "%snull window set", who);
+    WM_TRY(check_set_owner(ctx, a.set));
+    const int W = a.set->W;
+    WM_REQUIRE(a.rows || B == W, WM_ERR_INVALID, "%srows is NULL: B (%d) must be the set's %d windows", who, B, W);
+    for (int b = 0; a.rows && b < B; ++b)
+        WM_REQUIRE(a.rows[b] >= 0 && a.rows[b] < W, WM_ERR_INVALID, "%srow %d: window %d outside the set's [0, %d)", who, b, a.rows[b], W);
+    return WM_OK;
+}
+
 // *d_pcm = the PCM of rows [b0, b0 + Bg) in device memory: the caller's, or (host memory) uploaded into m->pcm_stage.
-// Null for a mel source.
+// Null for a mel source and for a window set.
 int stage_pcm(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const void **d_pcm) {
     WmModel *m = c->model;
     *d_pcm = nullptr;
-    if (a.mel) return WM_OK;
+    if (a.mel || a.windows) return WM_OK;
     const size_t row = WM_N_SAMPLES * pcm_elem(a.pcm_dtype);
     *d_pcm = (const char *)a.pcm + (size_t)b0 * row;
     if (mem != WM_MEM_HOST) return WM_OK;
@@ -531,6 +595,31 @@ int stage_mel(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const 
     if (mem != WM_MEM_HOST) *enc_mel = a.mel;
     *enc_win = m->dmel_win;
     return WM_OK;
+}
+
+// The cross-attention K/V of rows [b0, b0 + Bg) of a call in m->xkv ([L][2][Bg][H][1500][64]), to be called after
+// wm_model_reserve.  PCM / mel windows: stage_mel, `staged` recorded, the encoder, wm_model_cross_kv.  A window set: the
+// rows' slabs copied from the set's store in one launch -- `map` is the CALLER's, the source of the asynchronous upload of
+// the row map --, then `staged`: there is no encoder stage.
+int stage_cross_kv(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const void *d_pcm, std::vector<WmMelWin> &win,
+                   std::vector<int32_t> &map, hipEvent_t staged) {
+    WmModel *m = c->model;
+    if (a.windows) {
+        const wm_dims &D = m->dims;
+        map.resize(Bg);
+        for (int b = 0; b < Bg; ++b) map[b] = a.rows ? a.rows[b0 + b] : b0 + b;
+        WM_HIP(hipMemcpyAsync(m->dxkv_rows, map.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
+        WM_TRY(wm_xkv_rows(c, m->xkv, Bg, a.set->store, m->dxkv_rows, 0, Bg, 2 * D.n_text_layer, (long)D.n_text_head * 1500 * 64,
+                           false));
+        if (staged) WM_HIP(hipEventRecord(staged, c->stream));
+        return WM_OK;
+    }
+    const float *enc_mel;
+    const WmMelWin *enc_win;
+    WM_TRY(stage_mel(c, a, b0, Bg, mem, d_pcm, win, &enc_mel, &enc_win));
+    if (staged) WM_HIP(hipEventRecord(staged, c->stream));
+    WM_TRY(wm_model_encode_win(c, enc_mel, enc_win, Bg, nullptr));
+    return wm_model_cross_kv(c, Bg);
 }
 
 // the tokens row `b` of the call may generate
@@ -615,14 +704,8 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
         WM_TRY(wm_model_beam_begin(c, j.mode, Bg, Cg, &j.bpar, j.bbud.data()));
     }
     WM_HIP(hipEventRecord(j.ev[0], c->stream));
-    // 1. log-mel front end, or the caller's mel windows
-    const float *enc_mel;
-    const WmMelWin *enc_win;
-    WM_TRY(stage_mel(c, src, j.b0, Cg, mem, d_pcm, j.win, &enc_mel, &enc_win));
-    WM_HIP(hipEventRecord(j.ev[1], c->stream));
-    // 2. encoder + cross-attention K/V
-    WM_TRY(wm_model_encode_win(c, enc_mel, enc_win, Cg, nullptr));
-    WM_TRY(wm_model_cross_kv(c, Cg));
+    // 1. log-mel front end, or the caller's mel windows;  2. encoder + cross-attention K/V  (a window set: 1. the gather)
+    WM_TRY(stage_cross_kv(c, src, j.b0, Cg, mem, d_pcm, j.win, j.xrows, j.ev[1]));
     WM_HIP(hipEventRecord(j.ev[2], c->stream));
     // 3. embedding of the first prompt token (+ the initial timestamp-rule state)
     WM_TRY(wm_model_embed_first(c, Bg, j.mode));
@@ -918,16 +1001,15 @@ extern "C" int wm_transcribe_mel_ragged(wm_ctx *ctx, const float *mel, const int
 
 // wm_transcribe_mel_ragged / wm_transcribe_mel with best_of candidates per row (TxSrc::n_cand): one encoder pass, one
 // cross-K/V cache and one read of it per window, best_of decoder rows (lane_prefill, wm_dec_attention_cand)
-extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
-                                         const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
-                                         int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
-                                         int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
-                                         int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
-                                         float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+// (src: the windows -- mel or a set -- and nothing else; wm_transcribe_mel_best_of and wm_transcribe_windows)
+static int best_of_impl(wm_ctx *ctx, TxSrc &src, int B, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len,
+                        int sot_tail, const uint32_t *sample_ids, int best_of, float length_penalty, int max_new, int32_t eot,
+                        const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                        float *no_speech_prob_out, int32_t *best_out, wm_mem mem) {
     // the checks of this entry point's own arguments; a call that fails them consumes the token budgets set for it, as a
     // call that fails transcribe_impl's checks does
     const int rc = [&]() -> int {
-        WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
+        WM_TRY(check_src_pointers(src));
         WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
         WM_REQUIRE(best_of >= 1 && best_of <= WM_MAX_BEST_OF, WM_ERR_INVALID, "best_of %d outside [1, %d]", best_of, WM_MAX_BEST_OF);
         WM_REQUIRE(std::isnan(length_penalty) || (length_penalty >= 0.f && length_penalty <= 1.f), WM_ERR_INVALID,
@@ -939,8 +1021,6 @@ extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const in
         if (ctx && ctx->model) ctx->model->budget_host.clear();
         return rc;
     }
-    TxSrc src;
-    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
     src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
     src.sample_ids = sample_ids; src.n_cand = best_of;
     std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
@@ -953,23 +1033,45 @@ extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const in
     if (best_out)
         WM_TRY(wm_rank_candidates(tokens_out, lens_out, lp, B, best_of, max_new, eot, length_penalty, best_out, nullptr));
     return WM_OK;
+}
+
+extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                         const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                         int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                         int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                         int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                         float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+    TxSrc src;
+    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
+    return best_of_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of, length_penalty, max_new,
+                        eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out, best_out, mem);
+} WM_API_CATCH
+
+// wm_transcribe_mel_best_of over the windows of an encoded set: the same call, its cross-K/V copied instead of computed
+extern "C" int wm_transcribe_windows(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                     int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                     int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                     int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                     float *no_speech_prob_out, int32_t *best_out) try {
+    TxSrc src;
+    src.windows = true; src.set = w; src.rows = rows;
+    return best_of_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of, length_penalty, max_new,
+                        eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out, best_out, WM_MEM_HOST);
 } WM_API_CATCH
 
 // Beam search: the call of wm_transcribe_mel_best_of with the rows of a window as its BEAMS (TxSrc::beam) -- the same groups,
 // the same prompt phase, one cross-K/V read per window; the generating positions close with the beam kernels (beam.hip)
-extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
-                                      const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
-                                      int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size, int max_candidates,
-                                      float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
-                                      int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
-                                      float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+static int beam_impl(wm_ctx *ctx, TxSrc &src, int B, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len,
+                     int sot_tail, int beam_size, int max_candidates, float length_penalty, int max_new, int32_t eot,
+                     const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out,
+                     float *sum_logprobs_out, float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) {
     float *trace = nullptr;   // the debug library's capture is for this call only
     if (ctx && ctx->model) {
         trace = ctx->model->beam_dbg_trace;
         ctx->model->beam_dbg_trace = nullptr;
     }
     const int rc = [&]() -> int {   // (a call that fails these consumes the token budgets set for it, like any other)
-        WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
+        WM_TRY(check_src_pointers(src));
         WM_REQUIRE(n_hyp_out && sum_logprobs_out, WM_ERR_INVALID, "null n_hyp_out / sum_logprobs_out");
         WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
         WM_REQUIRE(beam_size >= 1 && beam_size <= WM_MAX_BEAM, WM_ERR_INVALID, "beam_size %d outside [1, %d]", beam_size, WM_MAX_BEAM);
@@ -984,8 +1086,6 @@ extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64
         if (ctx && ctx->model) ctx->model->budget_host.clear();
         return rc;
     }
-    TxSrc src;
-    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
     src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
     src.n_cand = beam_size; src.beam = true; src.max_cand = max_candidates;
     src.n_hyp = n_hyp_out; src.sums = sum_logprobs_out; src.trace = trace;
@@ -1007,6 +1107,32 @@ extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64
         }
     }
     return WM_OK;
+}
+
+extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                      const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                      int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size, int max_candidates,
+                                      float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                      int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
+                                      float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+    TxSrc src;
+    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
+    return beam_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, max_new,
+                     eot, opts, tokens_out, lens_out, n_hyp_out, sum_logprobs_out, token_logprobs_out, no_speech_prob_out, best_out,
+                     mem);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_windows_beam(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                          int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size,
+                                          int max_candidates, float length_penalty, int max_new, int32_t eot,
+                                          const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out,
+                                          float *sum_logprobs_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                          int32_t *best_out) try {
+    TxSrc src;
+    src.windows = true; src.set = w; src.rows = rows;
+    return beam_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, max_new,
+                     eot, opts, tokens_out, lens_out, n_hyp_out, sum_logprobs_out, token_logprobs_out, no_speech_prob_out, best_out,
+                     WM_MEM_HOST);
 } WM_API_CATCH
 
 // wm_transcribe_greedy, wm_transcribe, wm_transcribe_mel and wm_transcribe_mel_ragged: opts == null with both extra outputs
@@ -1020,12 +1146,13 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
     std::vector<int32_t> budgets;
     budgets.swap(m->budget_host);
     WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
-    WM_REQUIRE((src.pcm || src.mel) && src.prompt && tokens_out && lens_out, WM_ERR_INVALID, "null pointer");
-    WM_REQUIRE(src.mel || src.pcm_dtype == WM_I16 || src.pcm_dtype == WM_F32 || src.pcm_dtype == WM_F64, WM_ERR_INVALID,
-               "bad pcm dtype");
+    WM_REQUIRE((src.pcm || src.mel || src.windows) && src.prompt && tokens_out && lens_out, WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE(src.mel || src.windows || src.pcm_dtype == WM_I16 || src.pcm_dtype == WM_F32 || src.pcm_dtype == WM_F64,
+               WM_ERR_INVALID, "bad pcm dtype");
     WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
     if (src.mel)
         for (int b = 0; b < B; ++b) WM_TRY(check_window(src, b, ""));
+    if (src.windows) WM_TRY(check_set_rows(ctx, src, B, ""));
     const wm_dims &D = m->dims;
     if (src.prompt_len) {   // ragged: n_prompt arrives as the row stride and becomes the call's longest prompt
         int longest = 0;
@@ -1243,8 +1370,8 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
                 if (xc.no_speech && b % N == 0) xc.no_speech[w] = j.ns[b];   // (candidates: candidate 0's)
             }
             float ms;
-            for (int i = 0; i < 3; ++i)
-                if (hipEventElapsedTime(&ms, j.ev[i], j.ev[i + 1]) == hipSuccess) j.stage_sum[i] += ms;
+            for (int i = 0; i < 3; ++i)   // (a window set: [0] the gather, no encoder stage)
+                if (!(src.windows && i == 1) && hipEventElapsedTime(&ms, j.ev[i], j.ev[i + 1]) == hipSuccess) j.stage_sum[i] += ms;
             j.state = LaneJob::IDLE;
             ++groups_done;
             progress = true;
@@ -1324,6 +1451,7 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     // host staging (fenced by the synchronisation at the end of the group): n_text, n_frames, DTW rows, DTW frames, heads
     std::vector<int32_t> hint(n_int), seq((size_t)T * Bg);
     std::vector<WmMelWin> win;
+    std::vector<int32_t> xrows;
     for (int b = 0; b < Bg; ++b) {
         const int n = c.n_text[b0 + b], nf = c.n_frames ? c.n_frames[b0 + b] : WM_N_FRAMES;
         hint[b] = n;
@@ -1353,11 +1481,7 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     const void *d_pcm;
     WM_TRY(stage_pcm(ctx, c, b0, Bg, c.mem, &d_pcm));
     WM_HIP(hipEventRecord(ev[0], ctx->stream));
-    const float *enc_mel;
-    const WmMelWin *enc_win;
-    WM_TRY(stage_mel(ctx, c, b0, Bg, c.mem, d_pcm, win, &enc_mel, &enc_win));
-    WM_TRY(wm_model_encode_win(ctx, enc_mel, enc_win, Bg, nullptr));
-    WM_TRY(wm_model_cross_kv(ctx, Bg));
+    WM_TRY(stage_cross_kv(ctx, c, b0, Bg, c.mem, d_pcm, win, xrows, nullptr));
     WM_HIP(hipEventRecord(ev[1], ctx->stream));
     // teacher-forced pass: every position is prompt, the alignment layers leave their queries in the capture buffer
     std::vector<WmAlignLayer> layers(D.n_text_layer);
@@ -1499,4 +1623,120 @@ extern "C" int wm_align_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_ba
     c.sot_seq = sot_seqs; c.sot_stride = n_sot; c.text_tokens = text_tokens; c.n_text = n_text; c.n_frames = n_frames;
     c.n_sot = n_sot; c.max_text = max_text;
     return align_impl(ctx, c, B, no_timestamps, eot, medfilt_width, qk_scale, start_frame_out, token_prob_out);
+} WM_API_CATCH
+
+// ---------------------------------------------------------------- window sets
+// wm_windows_encode runs the encoder and the cross-K/V projection of W windows once and keeps the result; the
+// wm_*_windows calls are the mel calls with that result copied into the lane (stage_cross_kv) instead of computed.
+static int windows_cross_kv(wm_ctx *ctx, const wm_windows *set, const int32_t *rows, int B, std::vector<int32_t> &map) {
+    WmAudioSrc a;
+    a.windows = true; a.set = set; a.rows = rows;
+    WM_TRY(check_set_rows(ctx, a, B, "detect_language: "));
+    WM_TRY(wm_model_reserve(ctx, B));
+    std::vector<WmMelWin> win;
+    return stage_cross_kv(ctx, a, 0, B, WM_MEM_HOST, nullptr, win, map, nullptr);
+}
+
+extern "C" int wm_windows_encode(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                 const int32_t *seek, const int32_t *n_frames, int W, wm_mem mem, wm_windows **out) try {
+    WM_REQUIRE(out != nullptr, WM_ERR_INVALID, "null out pointer");
+    *out = nullptr;
+    WM_MODEL(ctx);
+    WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "window sets are not supported by the all-f32 precision path");
+    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
+    WmAudioSrc a;
+    a.mel = mel; a.mel_base = mel_base; a.mel_len = mel_len; a.seek = seek; a.n_frames = n_frames;
+    WM_TRY(check_src_pointers(a));
+    WM_REQUIRE(W >= 1, WM_ERR_INVALID, "W < 1");
+    for (int b = 0; b < W; ++b) WM_TRY(check_window(a, b, "windows_encode: "));
+    const wm_dims &D = m->dims;
+    const long slab = (long)D.n_text_head * 1500 * 64;
+    const int L2 = 2 * D.n_text_layer;
+    struct Owner {   // nothing leaks on any way out
+        wm_windows *w = nullptr;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        ~Owner() {
+            for (auto &e : ev)
+                if (e) (void)hipEventDestroy(e);
+            if (w) wm_windows_free(w);
+        }
+    } own;
+    own.w = new wm_windows();
+    wm_windows *w = own.w;
+    w->device = ctx->device; w->dims = D; w->weights = m->tok_emb; w->W = W;
+    w->n_frames.assign(n_frames, n_frames + W);
+    w->bytes = (size_t)W * L2 * slab * sizeof(bf16_t);
+    const hipError_t me = hipMalloc((void **)&w->store, w->bytes);
+    if (me != hipSuccess) {
+        (void)hipGetLastError();
+        w->store = nullptr;
+        wm_set_error("windows_encode: no device memory for %d windows (%zu bytes): %s", W, w->bytes, hipGetErrorString(me));
+        return me == hipErrorOutOfMemory ? WM_ERR_NOMEM : WM_ERR_HIP;
+    }
+    for (auto &e : own.ev) WM_HIP(hipEventCreate(&e));
+    ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
+    std::vector<WmMelWin> win;
+    std::vector<int32_t> map;
+    struct StreamFence {   // error paths: no copy from win may outlive it
+        hipStream_t s;
+        ~StreamFence() { (void)hipStreamSynchronize(s); }
+    } fence{ctx->stream};
+    for (int b0 = 0; b0 < W; b0 += WM_DEC_MAXB) {
+        const int Bg = std::min(WM_DEC_MAXB, W - b0);
+        WM_TRY(wm_model_reserve(ctx, Bg));
+        WM_HIP(hipEventRecord(own.ev[0], ctx->stream));
+        WM_TRY(stage_cross_kv(ctx, a, b0, Bg, mem, nullptr, win, map, own.ev[1]));
+        WM_TRY(wm_xkv_rows(ctx, m->xkv, Bg, w->store, nullptr, b0, Bg, L2, slab, true));
+        WM_HIP(hipEventRecord(own.ev[2], ctx->stream));
+        WM_HIP(hipStreamSynchronize(ctx->stream));   // fences win; the next group overwrites m->xkv
+        float ms;
+        for (int i = 0; i < 2; ++i)
+            if (hipEventElapsedTime(&ms, own.ev[i], own.ev[i + 1]) == hipSuccess) ctx->stage_ms[i] += ms;
+    }
+    *out = w;
+    own.w = nullptr;
+    return WM_OK;
+} WM_API_CATCH
+
+extern "C" void wm_windows_free(wm_windows *w) {
+    if (!w) return;
+    if (w->store) {   // a reader may still be in flight on some lane's stream
+        (void)hipSetDevice(w->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(w->store);
+    }
+    delete w;
+}
+
+extern "C" int wm_windows_count(const wm_windows *w) { return w ? w->W : -1; }
+
+extern "C" size_t wm_windows_bytes(const wm_windows *w) { return w ? w->bytes : 0; }
+
+// wm_align_mel over the windows of an encoded set: find_alignment's num_frames is the set's n_frames of the row
+extern "C" int wm_align_windows(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *sot_seqs, int n_sot,
+                                int32_t no_timestamps, int32_t eot, const int32_t *text_tokens, const int32_t *n_text,
+                                int max_text, int medfilt_width, float qk_scale, int32_t *start_frame_out,
+                                float *token_prob_out) try {
+    WM_MODEL(ctx);
+    AlignCall c;
+    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
+    m->align_dbg_matrix = nullptr;
+    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
+    WM_REQUIRE(sot_seqs && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
+    c.windows = true; c.set = w; c.rows = rows; c.mem = WM_MEM_HOST;
+    WM_TRY(check_set_rows(ctx, c, B, "align: "));
+    std::vector<int32_t> nf(B);
+    for (int b = 0; b < B; ++b) nf[b] = w->n_frames[rows ? rows[b] : b];
+    c.sot_seq = sot_seqs; c.sot_stride = n_sot; c.text_tokens = text_tokens; c.n_text = n_text; c.n_frames = nf.data();
+    c.n_sot = n_sot; c.max_text = max_text;
+    return align_impl(ctx, c, B, no_timestamps, eot, medfilt_width, qk_scale, start_frame_out, token_prob_out);
+} WM_API_CATCH
+
+// Language identification from the windows of a set: wm_detect_language_probs with the features' cross-K/V copied from the
+// set -- the same captured step, the same bits as wm_encode of the zero-padded window followed by that call
+extern "C" int wm_windows_detect_language(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, int32_t sot,
+                                          int32_t lang_first, int32_t lang_last, int32_t *lang_idx, float *probs) try {
+    WM_REQUIRE(w != nullptr, WM_ERR_INVALID, "null window set");
+    return detect_language_impl(ctx, nullptr, B, sot, lang_first, lang_last, lang_idx, probs, WM_MEM_HOST, w, rows);
 } WM_API_CATCH

@@ -5,7 +5,7 @@ given as argv[1] (default base), every matrix scaled by weights.lively_gain so t
 length (argv[2], default 8: 10 .. 150 s), the production vocabulary's token ids, text context n_text_ctx.  Prints one JSON
 line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form.
 
-    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words]
+    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words | --reuse]
 
 --condition: the cost of condition_on_previous_text instead.  One more JSON line: wall seconds of the long form with
 conditioning off and on (the same recordings, after a warm-up of each; with the default fallback thresholds and with the
@@ -19,7 +19,15 @@ number of prompt positions (what the row-offset load in the self-attention launc
 through the alignment; a synthetic vocabulary (one piece per text token) is written to a temporary file.  One more JSON
 line: wall seconds of the long form with word_timestamps off and on, interleaved, three runs each after a warm-up of
 each, the windows and words of a run, and over the wm_align_mel calls of one run their number, rows, wall time and the
-wm_last_stage_ms split (window gather + encoder + cross K/V, teacher-forced pass, alignment kernels + DTW)."""
+wm_last_stage_ms split (window gather + encoder + cross K/V, teacher-forced pass, alignment kernels + DTW).
+
+--reuse: the cost and the gain of reuse_encoder (window sets) instead.  Two configurations -- (a) the default fallback, where
+the synthetic model takes all six temperatures, (b) fallback off with word_timestamps -- each with reuse_encoder off / on
+interleaved, three runs each after a warm-up of each; the two runs' results are asserted equal.  One JSON line per
+configuration: wall seconds, the wm_last_stage_ms splits summed over the calls of one run (off: staging, encoder + cross
+K/V, decode of every wm_transcribe_mel call and the encoder part of every wm_align_mel call; on: the wm_windows_encode
+calls and, per reading call, the copy from the set), the copy in GB/s (bytes read + bytes written) and per window next to
+the encoder + cross-K/V cost per window of the off run."""
 import json
 import os
 import sys
@@ -34,7 +42,8 @@ from openai_whisper_coreml_amd import weights as W  # noqa: E402
 b = pkg.binding
 CONDITION = "--condition" in sys.argv
 WORDS = "--words" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words")]
+REUSE = "--reuse" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words", "--reuse")]
 name = argv[0] if len(argv) > 0 else "base"
 N = int(argv[1]) if len(argv) > 1 else 8
 dims = dict(b.MODEL_DIMS[name])
@@ -127,7 +136,7 @@ def condition_probe():
                           ragged_over_uniform=per_pos["ragged"] / per_pos["uniform"])))
 
 
-def words_probe():
+def probe_vocab():
     import tempfile
     # GPT-2's byte alphabet: printable bytes stand for themselves, the others for U+0100 ...
     bs = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
@@ -137,7 +146,11 @@ def words_probe():
         path = os.path.join(tmp, "vocab.json")
         with open(path, "w") as f:
             json.dump({"".join(b2u[c] for c in ((" w%d" % i) if i % 3 else ("x%d" % i)).encode()): i for i in range(EOT)}, f)
-        vocab = b.Vocab(path)
+        return b.Vocab(path)
+
+
+def words_probe():
+    vocab = probe_vocab()
     calls = []
     inner = ctx.align_mel
 
@@ -174,8 +187,78 @@ def words_probe():
                           align_stage_ms=dict(encoder_cross_kv=stage[0], teacher_forced=stage[1], alignment_dtw=stage[2]))))
 
 
+def reuse_probe():
+    vocab = probe_vocab()
+    log = []   # (call, rows, wm_last_stage_ms) of every model call of the run in progress
+
+    def counted(fn_name, rows_of):
+        inner = getattr(ctx, fn_name)
+
+        def f(*a, **k):
+            r = inner(*a, **k)
+            log.append((fn_name, rows_of(a), [float(v) for v in ctx.last_stage_ms()]))
+            return r
+        setattr(ctx, fn_name, f)
+    counted("transcribe_mel", lambda a: len(a[1]))
+    counted("align_mel", lambda a: len(a[1]))
+    counted("encode_windows", lambda a: len(a[1]))
+    counted("transcribe_windows", lambda a: len(a[1]))
+    counted("align_windows", lambda a: len(a[1]))
+    window_bytes = dims["n_text_layer"] * 2 * 1500 * dims["n_text_state"] * 2
+    keep = dict(logprob_threshold=None, compression_ratio_threshold=None, no_speech_threshold=None)
+    configs = (("fallback", dict(vocab=vocab)),
+               ("words_no_fallback", dict(keep, vocab=vocab, word_timestamps=True, no_timestamps=50363)))
+    for label, extra in configs:
+        outs = {}
+        for reuse in (False, True):
+            outs[reuse] = ctx.transcribe_long(recs, **kw, **extra, reuse_encoder=reuse)     # warm-up of each
+        assert outs[True] == outs[False], "reuse_encoder changed the result"
+        walls, logs = {False: [], True: []}, {}
+        for _ in range(3):
+            for reuse in (False, True):
+                del log[:]
+                t0 = time.perf_counter()
+                ctx.transcribe_long(recs, **kw, **extra, reuse_encoder=reuse)
+                walls[reuse].append(time.perf_counter() - t0)
+                logs[reuse] = list(log)
+
+        def total(reuse, call, i):
+            return sum(c[2][i] for c in logs[reuse] if c[0] == call)
+
+        def rows(reuse, call):
+            return sum(c[1] for c in logs[reuse] if c[0] == call)
+        off_rows = rows(False, "transcribe_mel") + rows(False, "align_mel")
+        off_enc_ms = total(False, "transcribe_mel", 1) + total(False, "align_mel", 0)   # (align: [0] = staging + encoder + K/V)
+        on_rows = rows(True, "transcribe_windows") + rows(True, "align_windows")
+        gather_ms = total(True, "transcribe_windows", 0) + total(True, "align_windows", 0)
+        enc_rows = rows(True, "encode_windows")
+        res = dict(config=label, model=name, recordings=N, audio_s=audio_s,
+                   wall_s=dict(off=walls[False], on=walls[True]),
+                   median_wall_s=dict(off=float(np.median(walls[False])), on=float(np.median(walls[True]))),
+                   on_over_off=float(np.median(walls[True]) / np.median(walls[False])),
+                   windows=sum(len(o["windows"]) for o in outs[False]),
+                   off=dict(decode_calls=sum(c[0] == "transcribe_mel" for c in logs[False]), decode_rows=rows(False, "transcribe_mel"),
+                            align_calls=sum(c[0] == "align_mel" for c in logs[False]), align_rows=rows(False, "align_mel"),
+                            decode_stage_ms=[total(False, "transcribe_mel", i) for i in range(3)],
+                            align_stage_ms=[total(False, "align_mel", i) for i in range(3)],
+                            encoder_cross_kv_ms_per_window=off_enc_ms / max(off_rows, 1)),
+                   on=dict(encode_calls=sum(c[0] == "encode_windows" for c in logs[True]), encode_rows=enc_rows,
+                           encode_stage_ms=[total(True, "encode_windows", i) for i in range(3)],
+                           encode_ms_per_window=total(True, "encode_windows", 1) / max(enc_rows, 1),
+                           decode_rows=rows(True, "transcribe_windows"), align_rows=rows(True, "align_windows"),
+                           decode_stage_ms=[total(True, "transcribe_windows", i) for i in range(3)],
+                           align_stage_ms=[total(True, "align_windows", i) for i in range(3)],
+                           gather_ms=gather_ms, gather_rows=on_rows, gather_ms_per_window=gather_ms / max(on_rows, 1),
+                           gather_gb_per_s=2 * window_bytes * on_rows / max(gather_ms, 1e-9) / 1e6,
+                           set_bytes_per_window=window_bytes))
+        print(json.dumps(res), flush=True)
+
+
 if CONDITION:
     condition_probe()
+    sys.exit(0)
+if REUSE:
+    reuse_probe()
     sys.exit(0)
 if WORDS:
     words_probe()
