@@ -541,6 +541,69 @@ WM_API int wm_wav_num_chunks(const wm_wav *w);   /* ceil(samples / 480000), at l
 /* windows [first_chunk, first_chunk + n_chunks) -> out int16 [n_chunks][480000], the last window zero-padded */
 WM_API int wm_wav_read_chunks(const wm_wav *w, int first_chunk, int n_chunks, int16_t *out);
 
+/* ------------------------------------------------ audio at any sample rate -> 16 kHz mono --- */
+/* Everything above takes 16 kHz mono samples.  wm_resample_16k makes them, on the device, from recordings at their own
+ * rate and channel count: a polyphase Kaiser-windowed-sinc resampler, defined ONCE, on the host, in
+ * f64.  For input rate sr: g = gcd(sr, 16000), L = 16000 / g, M = sr / g, mx = max(L, M), K = WM_RESAMPLE_ZEROS * mx, and
+ * for j = -K .. K
+ *     c = WM_RESAMPLE_ROLLOFF / (2 mx)
+ *     h[j] = L * 2c * sinc(2c j) * I0(WM_RESAMPLE_BETA * sqrt(1 - (j / K)^2)) / I0(WM_RESAMPLE_BETA),  sinc(x) = sin(pi x) / (pi x)
+ * rounded once to f32.  Output n of a recording of N frames, n < N_out = ceil(N L / M):
+ *     y[n] = sum_k m[k] h[n M - k L],   m = the mono downmix, zero outside [0, N)
+ * -- scipy.signal.resample_poly(m, L, M, window=h / L).  Downmix of C channels, per frame: the f32 sum in channel order
+ * times (float)(1.0 / C); C == 1: the sample itself.  WM_I16 samples are s / 32768, WM_F32 samples are used as they are.
+ * Supported rates: 4000 <= sr <= 192000 with L <= 640 (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200,
+ * 96000, 176400, 192000, ...); sr == 16000 is a bypass (downmix only, no filter). */
+#define WM_RESAMPLE_ZEROS 32        /* zero-crossing spans of the sinc on each side */
+#define WM_RESAMPLE_ROLLOFF 0.9     /* cutoff as a fraction of the lower Nyquist frequency */
+#define WM_RESAMPLE_BETA 9.62       /* Kaiser window beta */
+
+/* ceil(n_frames L / M): the 16 kHz samples wm_resample_16k makes of n_frames frames at sample_rate.  Host only.
+ * -1: unsupported rate, negative length (or one above 2^40). */
+WM_API int64_t wm_resample_out_len(int64_t n_frames, int sample_rate);
+/* The f32 filter the kernel uses, h[i] = h[j = i - K], i = 0 .. 2K; *L, *M, *K (each nullable) as above.  Host only, no
+ * context.  cap: floats h can hold; cap = 0 only sizes (h is not read).  Invalid: an unsupported rate, 0 < cap < 2K + 1. */
+WM_API int wm_resample_filter(int sample_rate, float *h, size_t cap, int *L, int *M, int *K);
+/* R recordings, each at its own rate and channel count, to 16 kHz mono f32 in ONE launch.
+ *   pcm          : interleaved samples of all recordings back to back, WM_I16 or WM_F32, mem-space selectable (with
+ *                  WM_MEM_HOST only pcm[elem_offsets[0] .. elem_offsets[R]) is copied);
+ *   elem_offsets : i64 [R + 1] (host), non-decreasing: recording r = pcm[elem_offsets[r] .. elem_offsets[r + 1]), a
+ *                  multiple of n_channels[r] elements;  R : 0 .. 65535; empty recordings are legal;
+ *   n_channels   : i32 [R] (host), 1 .. 8;  sample_rates : i32 [R] (host);
+ *   out          : f32, recording r's wm_resample_out_len(frames_r, sample_rates[r]) samples (at most 2^30) after those of
+ *                  recordings 0 .. r - 1 -- the pcm / sample_offsets layout of wm_logmel_long(..., WM_F32, ...); same `mem`.
+ * A front-end-only context is enough.  The context builds and uploads a rate's filter on first use and keeps it.
+ * A recording's output depends on its own samples, rate and channel count only: bit-identical alone, among other
+ * recordings and at any offset (every output is one f32 fma chain over its taps in ascending input order).
+ * The call returns when the launch has finished, with WM_MEM_DEVICE too: the per-call tables are pageable host memory, so the
+ * stream is synchronised before they go out of scope (as wm_logmel_long does).  At most 2^24 - 1 tiles of 1024 outputs per call
+ * (298 hours of output); more is WM_ERR_INVALID.
+ * Profile family: "resample".  Invalid: a dtype other than WM_I16 / WM_F32, a length that is no multiple of the channel
+ * count, channels outside 1 .. 8, an unsupported rate, decreasing or negative offsets, null pointers with R > 0. */
+WM_API int wm_resample_16k(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *elem_offsets,
+                           const int32_t *n_channels, const int32_t *sample_rates, int R, float *out, wm_mem mem);
+
+/* ------------------------------------------------ general RIFF/WAVE reader (host only) --- */
+/* Beside wm_wav_* (which keeps its strict 16 kHz mono 16-bit rule): any rate, 1 .. 8 channels; integer PCM (format 1) at
+ * 8 bits (unsigned, (s - 128) / 128), 16 (s / 2^15), 24 (s / 2^23) and 32 (s / 2^31, computed in double, rounded once);
+ * IEEE float (format 3) at 32 and 64 bits (rounded to f32); WAVE_FORMAT_EXTENSIBLE with those sub-formats.  The hardening
+ * of wm_wav_open: a truncated or streamed data chunk gives the whole frames that are there, odd chunks are padded, files
+ * above 4 GiB and every malformed or inconsistent header (block_align != channels * bits / 8, ...) are WM_ERR_IO. */
+typedef struct wm_audio wm_audio;
+WM_API int wm_audio_open(const char *path, wm_audio **out);
+WM_API void wm_audio_close(wm_audio *w);
+WM_API int wm_audio_sample_rate(const wm_audio *w);      /* Hz; a null handle: 0 */
+WM_API int wm_audio_channels(const wm_audio *w);         /* 1 .. 8; a null handle: 0 */
+WM_API int64_t wm_audio_num_frames(const wm_audio *w);   /* frames (one sample of every channel); a null handle: 0 */
+WM_API int wm_audio_bits(const wm_audio *w);             /* bits per sample: 8 / 16 / 24 / 32 / 64; a null handle: 0 */
+WM_API int wm_audio_is_float(const wm_audio *w);         /* 1: IEEE float samples, 0: integer PCM */
+/* frames [first_frame, first_frame + n_frames) -> out f32 [n_frames][channels] (interleaved).  Invalid: a range outside
+ * the recording. */
+WM_API int wm_audio_read(const wm_audio *w, int64_t first_frame, int64_t n_frames, float *out);
+/* The same frames of a 16-bit integer file as raw int16 (for wm_resample_16k(..., WM_I16, ...): 2 bytes per sample across
+ * PCIe).  Invalid: any other format. */
+WM_API int wm_audio_read_i16(const wm_audio *w, int64_t first_frame, int64_t n_frames, int16_t *out);
+
 /* ------------------------------------------------------------ device memory helpers --- */
 /* For callers that keep inputs resident in HBM (bench.py; a Swift host would use them to
  * avoid the 5.7 MB/chunk PCIe round trip of the reference ABI). */

@@ -150,6 +150,15 @@ def load_library(path=None):
         "wm_wav_open": [ctypes.c_char_p, pp],
         "wm_wav_num_chunks": [vp],
         "wm_wav_read_chunks": [vp, ip, ip, vp],
+        "wm_resample_filter": [ip, vp, sz, vp, vp, vp],
+        "wm_resample_16k": [vp, vp, ip, vp, vp, vp, ip, vp, ip],
+        "wm_audio_open": [ctypes.c_char_p, pp],
+        "wm_audio_sample_rate": [vp],
+        "wm_audio_channels": [vp],
+        "wm_audio_bits": [vp],
+        "wm_audio_is_float": [vp],
+        "wm_audio_read": [vp, ctypes.c_int64, ctypes.c_int64, vp],
+        "wm_audio_read_i16": [vp, ctypes.c_int64, ctypes.c_int64, vp],
         "wm_multi_create": [ctypes.POINTER(wm_dims), vp, ip, pp],
         "wm_multi_size": [vp],
         "wm_multi_device_ctx": [vp, ip, pp],
@@ -176,6 +185,12 @@ def load_library(path=None):
     lib.wm_wav_close.restype = None
     lib.wm_wav_num_samples.argtypes = [vp]
     lib.wm_wav_num_samples.restype = ctypes.c_long
+    lib.wm_audio_close.argtypes = [vp]
+    lib.wm_audio_close.restype = None
+    lib.wm_audio_num_frames.argtypes = [vp]
+    lib.wm_audio_num_frames.restype = ctypes.c_int64
+    lib.wm_resample_out_len.argtypes = [ctypes.c_int64, ip]
+    lib.wm_resample_out_len.restype = ctypes.c_int64
     if path is None:
         _lib = lib
     return lib
@@ -443,6 +458,47 @@ def _pack_recordings(recordings):
     return pcm, offs
 
 
+def resample_out_len(n_frames, sample_rate):
+    """wm_resample_out_len: the 16 kHz samples of n_frames frames at sample_rate, ceil(n L / M); ValueError for an
+    unsupported rate."""
+    n = int(load_library().wm_resample_out_len(int(n_frames), int(sample_rate)))
+    if n < 0:
+        raise ValueError("unsupported sample rate %r (or a negative length)" % (sample_rate,))
+    return n
+
+
+def resample_filter(sample_rate):
+    """wm_resample_filter: (h f32 [2K + 1], L, M, K), the filter wm_resample_16k uses for this input rate."""
+    lib = load_library()
+    L, M, K = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _check(lib, lib.wm_resample_filter(int(sample_rate), None, 0, ctypes.byref(L), ctypes.byref(M), ctypes.byref(K)))
+    h = np.empty(2 * K.value + 1, dtype=np.float32)
+    _check(lib, lib.wm_resample_filter(int(sample_rate), _ptr(h), h.size, None, None, None))
+    return h, L.value, M.value, K.value
+
+
+def _pack_interleaved(recordings, sample_rates):
+    """Recordings ([n] or [n][C] int16 / float32 arrays, C-contiguous frames) back to back in one interleaved array, plus
+    element offsets i64 [R + 1], channel counts and rates i32 [R].  All int16: int16; otherwise int16 recordings become
+    float32 s / 32768 (exact: what the kernel computes)."""
+    recs = [np.asarray(r) for r in recordings]
+    if len(sample_rates) != len(recs):
+        raise ValueError("sample_rates: one per recording")
+    for r in recs:
+        if r.dtype not in (np.dtype(np.int16), np.dtype(np.float32)) or r.ndim not in (1, 2):
+            raise ValueError("a recording must be an int16 / float32 array [n] or [n][C], got %s %r" % (r.dtype, r.shape))
+    ch = np.array([r.shape[1] if r.ndim == 2 else 1 for r in recs], dtype=np.int32)
+    if recs and all(r.dtype == np.int16 for r in recs):
+        dt = np.dtype(np.int16)
+    else:
+        dt = np.dtype(np.float32)
+        recs = [(r.astype(np.float32) / np.float32(32768.0)) if r.dtype == np.int16 else r for r in recs]
+    offs = np.zeros(len(recs) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum([r.size for r in recs])
+    pcm = np.ascontiguousarray(np.concatenate([r.reshape(-1) for r in recs]) if recs else np.zeros(0, dt), dtype=dt)
+    return pcm, offs, ch, np.array([int(x) for x in sample_rates], dtype=np.int32)
+
+
 # ---- long-form transcription: openai-whisper transcribe()'s seek loop ---------------------------------------------------
 HOP_SECONDS = 160 / 16000     # one mel frame
 INPUT_STRIDE = 2              # mel frames per encoder output frame (N_FRAMES // n_audio_ctx)
@@ -554,12 +610,17 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None, condition_on_previous_text=False,
                     prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
                     prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
-                    patience=None, reuse_encoder=False):
+                    patience=None, reuse_encoder=False, sample_rates=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings; hallucination_silence_threshold
     and clip_timestamps are not implemented.  condition_on_previous_text defaults to False here (openai-whisper: True);
     see 5.  word_timestamps: see 6.
 
     1. One wm_logmel_long call for all recordings, kept on the device; content_frames = T_r - 3000.
+       sample_rates (one rate per recording; recordings [n] or [n][C] int16 / float32 at those rates): ONE wm_resample_16k
+       call first makes the 16 kHz mono samples on the device (Context.resample_16k) and the log-mel reads that buffer
+       where it lies (Context.logmel_long_device) -- no host round trip.  Everything behind the log-mel is as without the
+       argument, and equals transcribe_long on the samples downloaded from resample_16k.  None (the default): the
+       recordings are 16 kHz mono and the function makes exactly the calls it made before the argument existed.
     2. language None: per recording, openai-whisper's detect_language on mel[:, :3000] (wm_encode + the language-token
        softmax, ids lang_first .. lang_last); otherwise a token id for all recordings or a list of one per recording.
     3. Rounds: every unfinished recording decodes its window mel[:, seek : seek + segment_size], segment_size =
@@ -640,7 +701,16 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     out = [dict(language=None, segments=[], seeks=[], windows=[]) for _ in range(R)]
     if R == 0:
         return out
-    d_mel, mel_offs, T = ctx.logmel_long(recordings, n_mels=n_mels, device=True)
+    if sample_rates is None:
+        d_mel, mel_offs, T = ctx.logmel_long(recordings, n_mels=n_mels, device=True)
+    else:
+        if len(sample_rates) != R:
+            raise ValueError("sample_rates: one per recording")
+        d_pcm, pcm_offs = ctx.resample_16k(recordings, sample_rates, device=True)
+        try:
+            d_mel, mel_offs, T = ctx.logmel_long_device(d_pcm, np.float32, pcm_offs, n_mels=n_mels)
+        finally:
+            ctx.dev_free(d_pcm)
     wset = None   # reuse_encoder: the Windows of the round in progress
     try:
         content = [int(t) - N_FRAMES for t in T]
@@ -931,18 +1001,60 @@ class Context:
                                                      _ptr(out), WM_MEM_HOST))
             return [out[mel_offs[r]:mel_offs[r + 1]].reshape(n_mels, T[r]) for r in range(R)]
         d_pcm = self.to_device(pcm) if pcm.nbytes else None
+        try:
+            return self.logmel_long_device(d_pcm, pcm.dtype, offs, n_mels=n_mels)
+        finally:
+            if d_pcm is not None:
+                self.dev_free(d_pcm)
+
+    def logmel_long_device(self, d_pcm, dtype, sample_offsets, n_mels=80):
+        """wm_logmel_long on samples that are on the device already (e.g. resample_16k(..., device=True)'s): d_pcm of
+        `dtype` (int16 / float32 / float64), sample_offsets i64 [R + 1].  The caller keeps d_pcm.  Returns (pointer, element
+        offsets i64 [R + 1], T i32 [R]) -- free the pointer with dev_free."""
+        offs = np.ascontiguousarray(sample_offsets, dtype=np.int64)
+        R = len(offs) - 1
+        T = ((np.diff(offs) + N_SAMPLES) // 160).astype(np.int32)
+        mel_offs = np.concatenate([[0], np.cumsum(T.astype(np.int64) * n_mels)]).astype(np.int64)
         d_out = self.dev_malloc(max(int(mel_offs[-1]), 1) * 4)
         try:
-            _check(self.lib, self.lib.wm_logmel_long(self.handle, d_pcm, _DTYPES[pcm.dtype], _ptr(offs), R, n_mels, d_out,
+            _check(self.lib, self.lib.wm_logmel_long(self.handle, d_pcm, _DTYPES[np.dtype(dtype)], _ptr(offs), R, n_mels, d_out,
                                                      WM_MEM_DEVICE))
             self.sync()
         except Exception:
             self.dev_free(d_out)
             raise
+        return d_out, mel_offs, T
+
+    def resample_16k(self, recordings, sample_rates, device=False):
+        """wm_resample_16k: recordings ([n] or [n][C] int16 / float32 arrays) at sample_rates[r] Hz -> 16 kHz mono f32, one
+        launch for all of them.  Returns a list of f32 arrays [ceil(n_r L_r / M_r)]; device=True keeps the samples on the
+        device and returns (pointer, sample offsets i64 [R + 1]) -- what logmel_long_device reads; free the pointer with
+        dev_free."""
+        pcm, offs, ch, rates = _pack_interleaved(recordings, sample_rates)
+        R = len(ch)
+        frames = np.diff(offs) // np.maximum(ch, 1)
+        out_offs = np.zeros(R + 1, dtype=np.int64)
+        out_offs[1:] = np.cumsum([resample_out_len(int(n), int(sr)) for n, sr in zip(frames, rates)])
+        if not device:
+            out = np.empty(max(int(out_offs[-1]), 1), dtype=np.float32)
+            _check(self.lib, self.lib.wm_resample_16k(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], _ptr(offs), _ptr(ch), _ptr(rates),
+                                                      R, _ptr(out), WM_MEM_HOST))
+            return [out[out_offs[r]:out_offs[r + 1]] for r in range(R)]
+        d_pcm = self.to_device(pcm) if pcm.nbytes else None
+        d_out = None
+        try:
+            d_out = self.dev_malloc(max(int(out_offs[-1]), 1) * 4)
+            _check(self.lib, self.lib.wm_resample_16k(self.handle, d_pcm, _DTYPES[pcm.dtype], _ptr(offs), _ptr(ch), _ptr(rates), R,
+                                                      d_out, WM_MEM_DEVICE))
+            self.sync()
+        except Exception:
+            if d_out is not None:
+                self.dev_free(d_out)
+            raise
         finally:
             if d_pcm is not None:
                 self.dev_free(d_pcm)
-        return d_out, mel_offs, T
+        return d_out, out_offs
 
     # ---- device memory --------------------------------------------------------------
     def dev_malloc(self, nbytes):
@@ -1848,6 +1960,56 @@ class Wav:
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle:
             self.lib.wm_wav_close(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Audio:
+    """wm_audio: general RIFF/WAVE reader behind the C ABI (host only) -- any rate, 1 .. 8 channels, integer PCM 8 / 16 / 24 /
+    32 bits, IEEE float 32 / 64 bits, WAVE_FORMAT_EXTENSIBLE; what Context.resample_16k takes."""
+
+    def __init__(self, path):
+        self.lib = load_library()
+        self.handle = ctypes.c_void_p()
+        _check(self.lib, self.lib.wm_audio_open(str(path).encode(), ctypes.byref(self.handle)))
+
+    @property
+    def sample_rate(self):
+        return int(self.lib.wm_audio_sample_rate(self.handle))
+
+    @property
+    def channels(self):
+        return int(self.lib.wm_audio_channels(self.handle))
+
+    @property
+    def num_frames(self):
+        return int(self.lib.wm_audio_num_frames(self.handle))
+
+    @property
+    def bits(self):
+        return int(self.lib.wm_audio_bits(self.handle))
+
+    @property
+    def is_float(self):
+        return bool(self.lib.wm_audio_is_float(self.handle))
+
+    def read(self, first=0, n=None, raw_int16=False):
+        """Frames [first, first + n) as f32 [n][channels]; raw_int16=True (16-bit integer files only): the int16 samples."""
+        n = self.num_frames - first if n is None else n
+        rows = min(max(int(n), 0), self.num_frames)   # (a range outside the recording is the library's to refuse)
+        out = np.empty((rows, self.channels), dtype=np.int16 if raw_int16 else np.float32)
+        fn = self.lib.wm_audio_read_i16 if raw_int16 else self.lib.wm_audio_read
+        _check(self.lib, fn(self.handle, int(first), int(n), _ptr(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle:
+            self.lib.wm_audio_close(self.handle)
             self.handle = ctypes.c_void_p()
 
     def __del__(self):

@@ -191,6 +191,7 @@ extern "C" void wm_destroy(wm_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     wm_model_destroy(ctx);
     wm_frontend_destroy(&ctx->fe);
+    wm_resample_destroy(&ctx->rs);
     ctx->prof.reset();
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -414,6 +415,46 @@ extern "C" int wm_logmel_long(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, 
         WM_HIP(hipMemcpyAsync(d_in, (const char *)pcm + (size_t)sample_offsets[0] * dtype_size(pcm_dtype), in_b,
                               hipMemcpyHostToDevice, ctx->stream));
     WM_TRY(wm_frontend_run_long(&ctx->fe, &ctx->prof, ctx->stream, d_in, pcm_dtype, offs.data(), R, n_mels, (float *)d_out));
+    WM_HIP(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    return WM_OK;
+} WM_API_CATCH
+
+// Recordings at any rate / channel count -> 16 kHz mono f32 (resample.hip), in wm_logmel_long's input layout
+extern "C" int wm_resample_16k(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *elem_offsets,
+                               const int32_t *n_channels, const int32_t *sample_rates, int R, float *out, wm_mem mem) try {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(R >= 0 && R <= 65535, WM_ERR_INVALID, "resample: R must be 0 .. 65535, got %d", R);
+    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32, WM_ERR_INVALID, "resample: pcm dtype must be WM_I16 / WM_F32");
+    if (R == 0) return WM_OK;
+    WM_REQUIRE(elem_offsets && n_channels && sample_rates, WM_ERR_INVALID, "resample: null elem_offsets / n_channels / sample_rates");
+    int64_t n_out = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t len = elem_offsets[r + 1] - elem_offsets[r];
+        WM_REQUIRE(elem_offsets[r] >= 0 && len >= 0, WM_ERR_INVALID, "resample: elem_offsets must be >= 0 and non-decreasing (recording %d)", r);
+        WM_REQUIRE(n_channels[r] >= 1 && n_channels[r] <= WM_RS_MAX_CHANNELS, WM_ERR_INVALID,
+                   "resample: recording %d: %d channels (1 .. %d)", r, n_channels[r], WM_RS_MAX_CHANNELS);
+        WM_REQUIRE(len % n_channels[r] == 0, WM_ERR_INVALID, "resample: recording %d: %lld samples are no multiple of its %d channels",
+                   r, (long long)len, n_channels[r]);
+        const int64_t n = wm_resample_out_len(len / n_channels[r], sample_rates[r]);
+        WM_REQUIRE(n >= 0, WM_ERR_INVALID, "resample: recording %d: unsupported sample rate %d", r, sample_rates[r]);
+        n_out += n;
+    }
+    if (n_out == 0) return WM_OK;
+    WM_REQUIRE(pcm && out, WM_ERR_INVALID, "resample: null pcm / out");
+    if (mem == WM_MEM_DEVICE)
+        return wm_resample_run(&ctx->rs, &ctx->prof, ctx->stream, pcm, pcm_dtype, elem_offsets, n_channels, sample_rates, R, out);
+    // host memory: only the samples the recordings span cross PCIe (offsets rebased to the first one)
+    std::vector<int64_t> offs(elem_offsets, elem_offsets + R + 1);
+    for (auto &o : offs) o -= elem_offsets[0];
+    const size_t in_b = (size_t)offs[R] * dtype_size(pcm_dtype);
+    const size_t out_b = (size_t)n_out * sizeof(float);
+    const size_t in_al = (in_b + 255) & ~(size_t)255;
+    WM_TRY(ensure_scratch(ctx, in_al + out_b));
+    char *d_in = (char *)ctx->fe.scratch, *d_out = d_in + in_al;
+    WM_HIP(hipMemcpyAsync(d_in, (const char *)pcm + (size_t)elem_offsets[0] * dtype_size(pcm_dtype), in_b, hipMemcpyHostToDevice,
+                          ctx->stream));
+    WM_TRY(wm_resample_run(&ctx->rs, &ctx->prof, ctx->stream, d_in, pcm_dtype, offs.data(), n_channels, sample_rates, R, (float *)d_out));
     WM_HIP(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
     WM_HIP(hipStreamSynchronize(ctx->stream));
     return WM_OK;

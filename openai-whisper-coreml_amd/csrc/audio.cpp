@@ -101,3 +101,144 @@ extern "C" int wm_wav_read_chunks(const wm_wav *w, int first_chunk, int n_chunks
     }
     return WM_OK;
 } WM_API_CATCH
+
+// ---------------------------------------------------------------- general reader (wm_audio_*) ----------
+// Any rate, 1 .. 8 channels, integer PCM 8 / 16 / 24 / 32 bits, IEEE float 32 / 64 bits, plain or WAVE_FORMAT_EXTENSIBLE:
+// what wm_resample_16k takes.  The same parse and the same hardening as wm_wav_open; samples are decoded on read.
+struct wm_audio {
+    std::vector<unsigned char> raw;  // the file image
+    size_t data_off = 0;
+    uint64_t n_frames = 0;
+    unsigned rate = 0, channels = 0, bits = 0;
+    bool is_float = false;
+};
+
+namespace {
+constexpr unsigned kMaxAudioChannels = 8;
+
+int read_file(const char *path, std::vector<unsigned char> &buf) {
+    FILE *f = fopen(path, "rb");
+    WM_REQUIRE(f, WM_ERR_IO, "cannot open '%s'", path);
+    unsigned char tmp[1 << 16];
+    size_t n;
+    while ((n = fread(tmp, 1, sizeof(tmp), f)) > 0) {
+        if (buf.size() + n > kMaxWavBytes) { fclose(f); wm_set_error("'%s': larger than 4 GiB", path); return WM_ERR_IO; }
+        buf.insert(buf.end(), tmp, tmp + n);
+    }
+    fclose(f);
+    return WM_OK;
+}
+
+// one sample at p -> f32
+inline float audio_sample(const unsigned char *p, unsigned bits, bool is_float) {
+    if (is_float) {
+        if (bits == 32) { uint32_t u = rd32(p); float v; memcpy(&v, &u, 4); return v; }
+        uint64_t u = (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32);
+        double d; memcpy(&d, &u, 8);
+        if (d != d) return __builtin_nanf("");                                // (a cast of a NaN or an out-of-range double is
+        if (d > 3.4028234663852886e38) return __builtin_inff();              //  undefined behaviour in C++: saturate)
+        if (d < -3.4028234663852886e38) return -__builtin_inff();
+        return (float)d;
+    }
+    switch (bits) {
+        case 8: return (float)((int)p[0] - 128) * (1.0f / 128.0f);
+        case 16: return (float)(int16_t)rd16(p) * (1.0f / 32768.0f);
+        case 24: {
+            int32_t v = (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16));
+            if (v & 0x800000) v -= 0x1000000;
+            return (float)v * (1.0f / 8388608.0f);   // |v| < 2^24: exact
+        }
+        default: return (float)((double)(int32_t)rd32(p) / 2147483648.0);   // 32: in double, rounded once
+    }
+}
+}  // namespace
+
+extern "C" int wm_audio_open(const char *path, wm_audio **out) try {
+    WM_REQUIRE(path && out, WM_ERR_INVALID, "audio_open: null pointer");
+    *out = nullptr;
+    std::vector<unsigned char> buf;
+    WM_TRY(read_file(path, buf));
+    WM_REQUIRE(buf.size() >= 12 && memcmp(buf.data(), "RIFF", 4) == 0 && memcmp(buf.data() + 8, "WAVE", 4) == 0, WM_ERR_IO,
+               "'%s' is not a RIFF/WAVE file", path);
+    bool have_fmt = false, is_float = false;
+    unsigned ch = 0, rate = 0, bits = 0;
+    size_t pos = 12, data_off = 0, data_len = 0;
+    while (pos + 8 <= buf.size()) {
+        const unsigned char *h = buf.data() + pos;
+        size_t len = rd32(h + 4);
+        const size_t body = pos + 8;
+        if (memcmp(h, "fmt ", 4) == 0) {
+            WM_REQUIRE(len >= 16 && body + 16 <= buf.size(), WM_ERR_IO, "'%s': truncated fmt chunk", path);
+            const unsigned char *p = buf.data() + body;
+            unsigned fmt = rd16(p);
+            const unsigned align = rd16(p + 12);
+            ch = rd16(p + 2), rate = rd32(p + 4), bits = rd16(p + 14);
+            if (fmt == 0xFFFE) {   // WAVE_FORMAT_EXTENSIBLE: the sub-format's first two bytes are the format tag
+                WM_REQUIRE(len >= 26 && body + 26 <= buf.size(), WM_ERR_IO, "'%s': truncated extensible fmt chunk", path);
+                fmt = rd16(p + 24);
+            }
+            WM_REQUIRE(fmt == 1 || fmt == 3, WM_ERR_IO, "'%s': format %u is neither integer PCM (1) nor IEEE float (3)", path, fmt);
+            is_float = fmt == 3;
+            WM_REQUIRE(ch >= 1 && ch <= kMaxAudioChannels, WM_ERR_IO, "'%s': %u channels (1 .. %u)", path, ch, kMaxAudioChannels);
+            WM_REQUIRE(rate >= 1 && rate <= 0x7FFFFFFFu, WM_ERR_IO, "'%s': sample rate %u", path, rate);
+            WM_REQUIRE(is_float ? (bits == 32 || bits == 64) : (bits == 8 || bits == 16 || bits == 24 || bits == 32), WM_ERR_IO,
+                       "'%s': %u-bit %s samples are not supported", path, bits, is_float ? "float" : "integer");
+            WM_REQUIRE(align == ch * (bits / 8), WM_ERR_IO, "'%s': block align %u, but %u channels of %u bits", path, align, ch, bits);
+            have_fmt = true;
+        } else if (memcmp(h, "data", 4) == 0) {
+            if (len == 0xFFFFFFFFu || len > buf.size() - body) len = buf.size() - body;  // streamed / truncated: what is there
+            data_off = body;
+            data_len = len;
+            break;
+        }
+        if (len > buf.size() - body) break;   // a chunk that runs past the file: nothing behind it
+        pos = body + len + (len & 1);         // chunks are word-aligned
+    }
+    WM_REQUIRE(have_fmt, WM_ERR_IO, "'%s': no fmt chunk before the data", path);
+    WM_REQUIRE(data_off != 0, WM_ERR_IO, "'%s': no data chunk", path);
+    wm_audio *w = new wm_audio();
+    w->raw.swap(buf);
+    w->data_off = data_off;
+    w->n_frames = data_len / ((size_t)ch * (bits / 8));   // whole frames only; <= 2^32, so frames * channels cannot overflow
+    w->rate = rate;
+    w->channels = ch;
+    w->bits = bits;
+    w->is_float = is_float;
+    *out = w;
+    return WM_OK;
+} WM_API_CATCH
+
+extern "C" void wm_audio_close(wm_audio *w) { delete w; }
+extern "C" int wm_audio_sample_rate(const wm_audio *w) { return w ? (int)w->rate : 0; }
+extern "C" int wm_audio_channels(const wm_audio *w) { return w ? (int)w->channels : 0; }
+extern "C" int64_t wm_audio_num_frames(const wm_audio *w) { return w ? (int64_t)w->n_frames : 0; }
+extern "C" int wm_audio_bits(const wm_audio *w) { return w ? (int)w->bits : 0; }
+extern "C" int wm_audio_is_float(const wm_audio *w) { return w && w->is_float ? 1 : 0; }
+
+namespace {
+int audio_range(const wm_audio *w, int64_t first, int64_t n, const void *out, const char *what) {
+    WM_REQUIRE(w && first >= 0 && n >= 0 && (uint64_t)first <= w->n_frames && (uint64_t)n <= w->n_frames - (uint64_t)first,
+               WM_ERR_INVALID, "%s: frames [%lld, %lld + %lld) outside the recording's %lld", what, (long long)first,
+               (long long)first, (long long)n, w ? (long long)w->n_frames : 0LL);
+    WM_REQUIRE(out || n == 0, WM_ERR_INVALID, "%s: null output", what);
+    return WM_OK;
+}
+}  // namespace
+
+extern "C" int wm_audio_read(const wm_audio *w, int64_t first_frame, int64_t n_frames, float *out) try {
+    WM_TRY(audio_range(w, first_frame, n_frames, out, "audio_read"));
+    const size_t bytes = w->bits / 8, n = (size_t)n_frames * w->channels;
+    const unsigned char *src = w->raw.data() + w->data_off + (size_t)first_frame * w->channels * bytes;
+    for (size_t i = 0; i < n; ++i) out[i] = audio_sample(src + i * bytes, w->bits, w->is_float);
+    return WM_OK;
+} WM_API_CATCH
+
+extern "C" int wm_audio_read_i16(const wm_audio *w, int64_t first_frame, int64_t n_frames, int16_t *out) try {
+    WM_TRY(audio_range(w, first_frame, n_frames, out, "audio_read_i16"));
+    WM_REQUIRE(!w->is_float && w->bits == 16, WM_ERR_INVALID, "audio_read_i16: the file holds %u-bit %s samples", w->bits,
+               w->is_float ? "float" : "integer");
+    const size_t n = (size_t)n_frames * w->channels;
+    const unsigned char *src = w->raw.data() + w->data_off + (size_t)first_frame * w->channels * 2;
+    for (size_t i = 0; i < n; ++i) out[i] = (int16_t)rd16(src + 2 * i);
+    return WM_OK;
+} WM_API_CATCH

@@ -145,6 +145,28 @@ inline int64_t wm_long_frames(int64_t len) { return (len + WM_N_SAMPLES) / WM_HO
 void wm_mel_filterbank(int n_mels, std::vector<float> &out /* [n_mels][201] */);
 const float *wm_mel80_table();
 
+// ---------------------------------------------------------------- resampler (resample.hip) ----------
+constexpr int WM_RS_TARGET_RATE = 16000;
+constexpr int WM_RS_MIN_RATE = 4000, WM_RS_MAX_RATE = 192000;
+constexpr int WM_RS_MAX_L = 640;        // 16000 / gcd(rate, 16000): 11025 Hz and its multiples are the largest
+constexpr int WM_RS_MAX_CHANNELS = 8;
+struct WmRsFilter {
+    int L = 0, M = 0, K = 0, T4 = 0;    // T4: taps per output, rounded up to a multiple of 4
+    float *d_tab = nullptr;             // phase table [L][T4] on the device
+};
+struct WmResampler {
+    std::map<int, WmRsFilter> filt;     // by input rate, built and uploaded on first use
+    void *tab = nullptr;                // recording and workgroup tables of a call
+    size_t tab_bytes = 0;
+};
+bool wm_resample_params(long long sample_rate, int *L, int *M, int *K);   // false: unsupported rate
+void wm_resample_prototype(int L, int M, int K, std::vector<float> &h);   // h[0 .. 2K], f64 rounded once to f32
+void wm_resample_destroy(WmResampler *rs);
+// Device-pointer core of wm_resample_16k: recording r = d_pcm[offs[r] .. offs[r + 1]) (interleaved, n_channels[r] channels,
+// sample_rates[r] Hz) -> d_out, its ceil(n L / M) samples after those of the recordings before it.  One launch.
+int wm_resample_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
+                    const int64_t *offs, const int32_t *n_channels, const int32_t *sample_rates, int R, float *d_out);
+
 // ---------------------------------------------------------------- context ------------
 struct WmModel;  // model.h
 struct wm_ctx;
@@ -162,6 +184,7 @@ struct wm_ctx {
     hipStream_t stream = nullptr;
     WmProfiler prof;
     WmFrontend fe;
+    WmResampler rs;
     WmModel *model = nullptr;
     float stage_ms[3] = {0, 0, 0};
     std::vector<wm_ctx *> lanes;  // weight-sharing clones owned by this context (wm_transcribe_greedy)

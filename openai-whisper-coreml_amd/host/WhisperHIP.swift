@@ -223,6 +223,61 @@ struct Whisper {
         return result
     }
 
+    /// Recordings at their own sample rate and channel count -> 16 kHz mono f32 (wm_resample_16k: one launch, the polyphase
+    /// Kaiser-sinc resampler of DESIGN.md section 12), host memory.  recordings[r] holds interleaved frames of channels[r]
+    /// channels at sampleRates[r] Hz; the result feeds logMelLong as it is.
+    /// Not compiled in this repository (see the top of the file).
+    func resample16k(recordings: [[Float]], channels: [Int32], sampleRates: [Int32]) throws -> [[Float]] {
+        typealias ResampleFn = @convention(c) (OpaquePointer, UnsafeRawPointer?, Int32, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                               UnsafePointer<Int32>, Int32, UnsafeMutablePointer<Float>, Int32) -> Int32
+        typealias OutLenFn = @convention(c) (Int64, Int32) -> Int64
+        let outLen: OutLenFn = try sym("wm_resample_out_len")
+        var offsets: [Int64] = [0]
+        for r in recordings { offsets.append(offsets.last! + Int64(r.count)) }
+        let lens = try recordings.indices.map { r -> Int in
+            let n = outLen(Int64(recordings[r].count) / Int64(max(channels[r], 1)), sampleRates[r])
+            if n < 0 { throw WhisperError(description: "unsupported sample rate \(sampleRates[r])") }
+            return Int(n)
+        }
+        let pcm = recordings.flatMap { $0 }
+        var out = [Float](repeating: 0, count: max(1, lens.reduce(0, +)))
+        let f: ResampleFn = try sym("wm_resample_16k")
+        try pcm.withUnsafeBytes { p in
+            try check(f(ctx, p.baseAddress, 1 /* WM_F32 */, offsets, channels, sampleRates, Int32(recordings.count), &out, 0))
+        }
+        var result: [[Float]] = []
+        var at = 0
+        for n in lens {
+            result.append(Array(out[at..<at + n]))
+            at += n
+        }
+        return result
+    }
+
+    /// A RIFF/WAVE file of any rate, 1 ... 8 channels, integer PCM 8 / 16 / 24 / 32 bits or IEEE float 32 / 64 bits
+    /// (wm_audio_*: the general reader beside wm_wav_*): interleaved f32 frames, the rate and the channel count --
+    /// the arguments of resample16k.  Not compiled in this repository (see the top of the file).
+    func readAudio(path: String) throws -> (samples: [Float], sampleRate: Int32, channels: Int32) {
+        typealias AudioOpenFn = @convention(c) (UnsafePointer<CChar>, UnsafeMutablePointer<OpaquePointer?>) -> Int32
+        typealias AudioIntFn = @convention(c) (OpaquePointer?) -> Int32
+        typealias AudioFramesFn = @convention(c) (OpaquePointer?) -> Int64
+        typealias AudioReadFn = @convention(c) (OpaquePointer?, Int64, Int64, UnsafeMutablePointer<Float>) -> Int32
+        typealias AudioCloseFn = @convention(c) (OpaquePointer?) -> Void
+        let open: AudioOpenFn = try sym("wm_audio_open")
+        let rate: AudioIntFn = try sym("wm_audio_sample_rate")
+        let chans: AudioIntFn = try sym("wm_audio_channels")
+        let frames: AudioFramesFn = try sym("wm_audio_num_frames")
+        let read: AudioReadFn = try sym("wm_audio_read")
+        let close: AudioCloseFn = try sym("wm_audio_close")
+        var audio: OpaquePointer?
+        try check(open(path, &audio))
+        defer { close(audio) }
+        let n = frames(audio), c = chans(audio)
+        var out = [Float](repeating: 0, count: max(1, Int(n) * Int(c)))
+        try check(read(audio, 0, n, &out))
+        return (Array(out[0..<Int(n) * Int(c)]), rate(audio), c)
+    }
+
     /// One decode step of the long-form loop (wm_transcribe_mel): row b decodes mel[:, seek[b] ..< seek[b] + nFrames[b]] of
     /// the recording block at element melBase[b] (melLen[b] frames) with its own prompt; temperature 0, host memory.
     /// Returns each row's generated tokens.  Not compiled in this repository (see the top of the file).
