@@ -604,16 +604,143 @@ def conditioned_history(all_tokens, prompt_reset_since, segments, temperature, s
     return grown, prompt_reset_since
 
 
+def carried_prompt(initial_prompt, all_tokens, prompt_reset_since, sot_sequence, sot_prev, n_text_ctx):
+    """The prompt of a window under condition_on_previous_text with carry_initial_prompt, for a recording with a non-empty
+    initial prompt `ip` (all_tokens starts with it): [sot_prev] + ip + the last cap - len(ip) tokens of
+    all_tokens[max(len(ip), prompt_reset_since):] + sot_sequence, cap = n_text_ctx // 2 - 1.  This project's rule for
+    len(ip) >= cap, where openai-whisper's slice takes a non-positive count: ip[-cap:] and no history."""
+    ip = [int(t) for t in initial_prompt]
+    cap = n_text_ctx // 2 - 1
+    if len(ip) >= cap:
+        text = ip[-cap:]
+    else:
+        text = ip + [int(t) for t in all_tokens[max(len(ip), prompt_reset_since):]][-(cap - len(ip)):]
+    return [int(sot_prev)] + text + [int(t) for t in sot_sequence]
+
+
+def clip_times(clip_timestamps, R):
+    """transcribe_long's clip_timestamps as one list of seconds per recording: None, a string of comma-separated seconds
+    ("" = none), a flat list or one number (for every recording) or a list of R lists / strings.  Times must be finite,
+    >= 0 and non-decreasing (ValueError)."""
+    def one(x):
+        if isinstance(x, str):
+            x = [float(s) for s in x.split(",")] if x.strip() else []
+        elif np.isscalar(x):
+            x = [x]
+        t = [float(v) for v in x]
+        if any(not math.isfinite(v) or v < 0 for v in t) or any(b < a for a, b in zip(t, t[1:])):
+            raise ValueError("clip_timestamps: finite seconds >= 0 in non-decreasing order")
+        return t
+    if clip_timestamps is None:
+        return [[] for _ in range(R)]
+    if (not np.isscalar(clip_timestamps) and len(clip_timestamps) > 0
+            and all(isinstance(x, (list, tuple, np.ndarray, str)) for x in clip_timestamps)):
+        if len(clip_timestamps) != R:
+            raise ValueError("clip_timestamps: one list per recording")
+        return [one(x) for x in clip_timestamps]
+    t = one(clip_timestamps)
+    return [list(t) for _ in range(R)]
+
+
+def seek_clips(times, content):
+    """The clips of one recording of `content` frames from clip_times' seconds, as openai-whisper transcribe() pairs them:
+    seek points round(t * 100), `content` appended to an odd count, no time = the one clip [0, content).  This project's
+    rules on top: a clip is cut to [0, content) and one that is empty after the cut is dropped.  Returns
+    [(first frame, end frame, index of the pair)]."""
+    p = [int(round(t * 100)) for t in times]
+    if not p:
+        p = [0]
+    if len(p) % 2:
+        p.append(content)
+    clips = []
+    for k in range(0, len(p), 2):
+        a, b = min(p[k], content), min(p[k + 1], content)
+        if a < b:
+            clips.append((a, b, k // 2))
+    return clips
+
+
+HALLUCINATION_PUNCTUATION = "\"'“¿([{-\"'.。,，!！?？:：”)]}、"   # PREPEND_PUNCTUATIONS + APPEND_PUNCTUATIONS
+
+
+def word_anomaly_score(word):
+    """openai-whisper transcribe()'s word_anomaly_score: 1 for a probability below 0.15, 15 per second short of 0.133 s, and
+    the seconds beyond 2 s."""
+    d = word["end"] - word["start"]
+    score = 0.0
+    if word["probability"] < 0.15:
+        score += 1.0
+    if d < 0.133:
+        score += (0.133 - d) * 15
+    if d > 2.0:
+        score += d - 2.0
+    return score
+
+
+def is_segment_anomaly(segment):
+    """openai-whisper transcribe()'s is_segment_anomaly: over the first 8 words that are no substring of
+    HALLUCINATION_PUNCTUATION, a score sum of 3 or more, or of the word count less 0.01 or more; False for no segment and
+    for one without words."""
+    if segment is None or not segment["words"]:
+        return False
+    words = [w for w in segment["words"] if w["word"] not in HALLUCINATION_PUNCTUATION][:8]
+    score = sum(word_anomaly_score(w) for w in words)
+    return score >= 3 or score + 0.01 >= len(words)
+
+
+def hallucination_silence_skip(segments, seek, segment_size, content, threshold, single_timestamp_ending,
+                               last_speech_timestamp, next_seek):
+    """openai-whisper transcribe()'s hallucination_silence_threshold rules for ONE window, after the word step and before
+    the clearing of empty segments.  segments: the window's, with `words`; last_speech_timestamp: the recording's BEFORE
+    this window; next_seek: what the window's timestamps gave (window_segments).  Returns (next seek, segments kept, tag):
+      the last word's end e behind the window's start, no single timestamp ending: seek to e when more than `threshold`
+        of the 30 s window lies behind it, else past the window's frames;
+      "leading": the first segment with words is anomalous and starts more than `threshold` into the window -- the seek
+        moves by that gap and NO segment is kept;
+      "surrounded": an anomalous segment with silence (or the window's edge, or an anomalous neighbour) on both sides --
+        the seek goes to its start (at least 1 s on, or to `content` when less than `threshold` of the recording is left
+        behind it) and it and the later segments are dropped;
+      None otherwise."""
+    t0 = seek * HOP_SECONDS
+    wend = (seek + N_FRAMES) * HOP_SECONDS
+    with_words = [sg for sg in segments if sg["words"]]
+    if not single_timestamp_ending and with_words and with_words[-1]["words"][-1]["end"] > t0:
+        e = with_words[-1]["words"][-1]["end"]
+        next_seek = int(round(e * 100)) if wend - e > threshold else seek + segment_size
+    if with_words and is_segment_anomaly(with_words[0]):
+        gap = with_words[0]["start"] - t0
+        if gap > threshold:
+            return seek + int(round(gap * 100)), [], "leading"
+    hal_last = last_speech_timestamp
+    for si, g in enumerate(segments):
+        if not g["words"]:
+            continue
+        if is_segment_anomaly(g):
+            nxt = next((sg for sg in segments[si + 1:] if sg["words"]), None)
+            next_start = nxt["words"][0]["start"] if nxt is not None else t0 + segment_size * HOP_SECONDS
+            before = g["start"] - hal_last > threshold or g["start"] < threshold or g["start"] - t0 < 2.0
+            after = next_start - g["end"] > threshold or is_segment_anomaly(nxt) or wend - g["end"] < 2.0
+            if before and after:
+                next_seek = int(round(max(t0 + 1, g["start"]) * 100))
+                if content * HOP_SECONDS - g["end"] < threshold:
+                    next_seek = content
+                return next_seek, segments[:si], "surrounded"
+        hal_last = g["end"]
+    return next_seek, segments, None
+
+
 def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_speech_token, lang_first=None,
                     lang_last=None, language=None, sot_prev=None, initial_prompt_tokens=None, recording_ids=None,
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
                     no_speech_threshold=0.6, vocab=None, seed=0, vocab_size=None, condition_on_previous_text=False,
                     prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
                     prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
-                    patience=None, reuse_encoder=False, sample_rates=None):
-    """openai-whisper transcribe() for recordings of any length, batched across the recordings; hallucination_silence_threshold
-    and clip_timestamps are not implemented.  condition_on_previous_text defaults to False here (openai-whisper: True);
-    see 5.  word_timestamps: see 6.
+                    patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
+                    hallucination_silence_threshold=None, carry_initial_prompt=False):
+    """openai-whisper transcribe() for recordings of any length, batched across the recordings.
+    condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
+    clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
+    makes exactly the calls it made before they existed.
 
     1. One wm_logmel_long call for all recordings, kept on the device; content_frames = T_r - 3000.
        sample_rates (one rate per recording; recordings [n] or [n][C] int16 / float32 at those rates): ONE wm_resample_16k
@@ -664,6 +791,27 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        wm_windows_detect_language, without host round trips.  The result equals the reuse_encoder=False run in every field;
        what it costs is the sets' device memory (Windows.nbytes: 246 MB per live recording at large-v2).  The default,
        False, makes exactly the calls this function made before the argument existed.
+    10. clip_timestamps (None; a string of comma-separated seconds, "" = none; a flat list of seconds for every recording;
+       or a list of R such lists / strings): only these spans of a recording are decoded.  clip_times / seek_clips: seek
+       points round(t * 100), the recording's end closes an odd count, no time = the whole recording.  This project's
+       rules: times are finite, >= 0 and non-decreasing (ValueError, before any library call), a clip is cut to [0,
+       content_frames), a clip that is empty after the cut is dropped, and a recording left without a clip decodes no
+       window (segments, seeks, windows [], its language as usual).  Per recording a clip cursor: before a round, a seek
+       at or past the clip's end moves to the next clip's start (backwards too: a window's timestamps may point far
+       past a short clip), the recording is finished when the clips run out, and the window is segment_size = min(3000,
+       content_frames - seek, clip_end - seek) frames -- for the decode, the word step and every seek rule.  Language
+       identification still reads frames [0, 3000).  Every window record gains `clip`, the index of its (start, end)
+       pair in the times as given (dropped clips keep their number).
+    11. hallucination_silence_threshold (seconds, finite and >= 0; needs word_timestamps; else ValueError): per kept
+       window, after window_word_timestamps and before the clearing of empty segments, hallucination_silence_skip decides
+       the next seek and which segments stay; a "leading" window keeps no segment and changes neither the history nor the
+       last speech timestamp, which otherwise follows the segments that remain.  The window record gets `hallucination`
+       ("leading" / "surrounded") when a rule fired, and `dropped_segments` with "surrounded".
+    12. carry_initial_prompt=True: with condition_on_previous_text and a non-empty initial prompt, every window's prompt is
+       carried_prompt() -- the initial prompt stays in front of the history's tail.  This project's rule: an initial
+       prompt of n_text_ctx // 2 - 1 tokens or more leaves no room for history, and its last n_text_ctx // 2 - 1 tokens
+       are the text.  Without conditioning or without an initial prompt nothing changes.
+    A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
     no prompt).  Without conditioning a recording's list heads every one of its windows; with it, it seeds the history.
     Sets the context's timestamp rules (wm_set_timestamp_rules: timestamp_begin, eot, max initial timestamp 1.0 s);
@@ -693,6 +841,15 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     words_on = bool(word_timestamps)
     if words_on and (vocab is None or no_timestamps is None):
         raise ValueError("word_timestamps needs vocab and no_timestamps")
+    clips_on = clip_timestamps is not None
+    times = clip_times(clip_timestamps, R)
+    thr = hallucination_silence_threshold
+    if thr is not None:
+        thr = float(thr)
+        if not math.isfinite(thr) or thr < 0:
+            raise ValueError("hallucination_silence_threshold: finite seconds >= 0")
+        if not words_on:
+            raise ValueError("hallucination_silence_threshold needs word_timestamps")
     if prepend_punctuations is None:
         prepend_punctuations = PREPEND_PUNCTUATIONS
     if append_punctuations is None:
@@ -752,7 +909,11 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         all_tokens = [list(x) for x in seeds]
         reset_since = [0] * R
         ragged = cond or per_rec   # rows may differ in prompt length: wm_transcribe_mel_ragged, <|startoftranscript|> third from the end
-        seek = [0] * R
+        carry = [bool(carry_initial_prompt) and cond and len(seeds[r]) > 0 for r in range(R)]
+        clips = [seek_clips(times[r], content[r]) for r in range(R)]
+        cur = [0] * R          # clip cursor
+        seek = [c[0][0] if c else 0 for c in clips]
+        before = [None] * R    # (clip cursor, seek) of the recording's previous window
         last_speech = [0.0] * R
         for r in range(R):
             out[r]["language"] = langs[r]
@@ -761,13 +922,26 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             if wset is not None:   # the previous round's set
                 wset.close()
                 wset = None
-            live = [r for r in range(R) if seek[r] < content[r]]
+            for r in range(R):
+                while cur[r] < len(clips[r]) and seek[r] >= clips[r][cur[r]][1]:
+                    cur[r] += 1
+                    if cur[r] < len(clips[r]):
+                        seek[r] = clips[r][cur[r]][0]
+                if cur[r] < len(clips[r]):
+                    seek[r] = max(seek[r], clips[r][cur[r]][0])
+            live = [r for r in range(R) if cur[r] < len(clips[r])]
             if not live:
                 break
-            size = [min(N_FRAMES, content[r] - seek[r]) for r in live]
+            for r in live:
+                if before[r] is not None and before[r][0] == cur[r] and seek[r] <= before[r][1]:
+                    raise AssertionError("transcribe_long: recording %d stays at seek %d" % (r, seek[r]))
+                before[r] = (cur[r], seek[r])
+            size = [min(N_FRAMES, content[r] - seek[r], clips[r][cur[r]][1] - seek[r]) for r in live]
             ids = [((len(out[r]["windows"]) & 0xFFFF) << 16) | rec_ids[r] for r in live]
             if ragged:
-                plist = [conditioned_prompt(all_tokens[r], reset_since[r] if cond else 0, [int(sot), langs[r], int(task)],
+                plist = [carried_prompt(seeds[r], all_tokens[r], reset_since[r], [int(sot), langs[r], int(task)], sot_prev,
+                                        n_ctx) if carry[r] else
+                         conditioned_prompt(all_tokens[r], reset_since[r] if cond else 0, [int(sot), langs[r], int(task)],
                                             sot_prev, n_ctx) for r in live]
             else:
                 plist = [head + [int(sot), langs[r], int(task)] for r in live]
@@ -823,6 +997,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 out[r]["windows"].append(dict(seek=seek[r], segment_size=size[i], temperatures=temps, skipped=skip,
                                               tokens=[int(t) for t in res["tokens"][i, :n_text]],
                                               prompt_len=len(plist[i]), prompt=[int(t) for t in plist[i]]))
+                if clips_on:
+                    out[r]["windows"][-1]["clip"] = clips[r][cur[r]][2]
                 if best_of is not None:
                     out[r]["windows"][-1]["candidate"] = cand[i]
                 if beam_size is not None:
@@ -865,16 +1041,29 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     g = go.index(n)
                     code = langs[r] - int(sot) - 1
                     code = Whisper.LANGUAGES[code] if 0 <= code < len(Whisper.LANGUAGES) else None
-                    last_speech[r] = window_word_timestamps(vocab, segs, sf[g], pr[g], seek[r], eot, last_speech[r], code,
-                                                            prepend_punctuations, append_punctuations)
-                    ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
-                    if ends:
-                        if not single_ending and ends[-1] > seek[r] * HOP_SECONDS:
-                            next_seek = int(round(ends[-1] * 100))
-                        last_speech[r] = ends[-1]
+                    window_word_timestamps(vocab, segs, sf[g], pr[g], seek[r], eot, last_speech[r], code,
+                                           prepend_punctuations, append_punctuations)
                 else:
                     for sg in segs:
                         sg["words"] = []
+                if thr is None:
+                    ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
+                    if ends and not single_ending and ends[-1] > seek[r] * HOP_SECONDS:
+                        next_seek = int(round(ends[-1] * 100))
+                else:   # 11. (last_speech[r] is still the recording's value before this window)
+                    n_segs = len(segs)
+                    next_seek, segs, tag = hallucination_silence_skip(segs, seek[r], size[i], content[r], thr, single_ending,
+                                                                      last_speech[r], next_seek)
+                    if tag is not None:   # (the recording's one window of this round is its last record)
+                        out[r]["windows"][-1]["hallucination"] = tag
+                    if tag == "surrounded":
+                        out[r]["windows"][-1]["dropped_segments"] = n_segs - len(segs)
+                    if tag == "leading":
+                        seek[r] = next_seek
+                        continue
+                ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
+                if ends:
+                    last_speech[r] = ends[-1]
                 clear_empty_segments(segs, eot, vocab, words=True)
                 seek[r] = next_seek
                 if cond:
