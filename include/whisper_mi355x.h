@@ -604,6 +604,59 @@ WM_API int wm_audio_read(const wm_audio *w, int64_t first_frame, int64_t n_frame
  * PCIe).  Invalid: any other format. */
 WM_API int wm_audio_read_i16(const wm_audio *w, int64_t first_frame, int64_t n_frames, int16_t *out);
 
+/* ------------------------------------------------ speech-activity detection on the whole-recording log-mel --- */
+/* Cutting a long recording at its silences into clips that decode together (binding.transcribe_long(vad=..., parallel_clips=...),
+ * DESIGN.md section 13).  wm_vad_energy makes a per-frame energy track on the device from wm_logmel_long's output, where it
+ * already lies; wm_vad_segments turns a track into speech spans on the host.  Per recording r and frame t < n_frames[r],
+ * with v = the log-mel value ((max(log10 mel, gmax_r - 8) + 4) / 4) and the band rows m in [band_lo, band_hi):
+ *     vmax = max_m v[m][t]
+ *     s    = sum_m exp2f((v[m][t] - vmax) * (4 log2 10))                      f32, m ascending
+ *     e[t] = 4 vmax + log10f(s)                                               log10 of the band's mel power, + 4
+ *     y[t] = (sum_{u = max(0, t - h)}^{min(n - 1, t + h)} e[u]) * (1.0f / count),   h = smooth / 2;  f32, u ascending
+ * smooth is odd, 1 .. 31; smooth = 1 gives y = e.
+ *   mel        : wm_logmel_long's output, mem-space selectable (with WM_MEM_HOST only each recording's band rows are copied);
+ *   mel_base   : i64 [R] (host): element of recording r's [n_mels][mel_len[r]] block;  mel_len : i32 [R] (host), >= 1;
+ *   n_frames   : i32 [R] (host), 0 .. mel_len[r]: the frames to do -- pass the content frames T_r - 3000, so that the 30 s
+ *                of padding never count; 0 writes nothing;  R : 0 .. 65535;
+ *   raw_out    : f32, nullable: e;  energy_out : f32: y.  Both packed -- recording r's n_frames[r] values after those of
+ *                recordings 0 .. r - 1 -- and in the same `mem` as mel.
+ * A front-end-only context is enough.  One launch, one workgroup per (recording, tile of 224 frames); the summation orders are
+ * fixed, so a recording's output is bit-identical alone, among other recordings and at any mel_base.  Non-finite mel values
+ * propagate.  Returns when the launch has finished (per-call tables, as wm_resample_16k).  At most 2^24 - 1 tiles per call.
+ * Profile family: "vad".  Invalid: n_mels not 80 / 128, a band outside 0 <= lo < hi <= n_mels, an even or out-of-range smooth,
+ * n_frames outside [0, mel_len], mel_len < 1, mel_base < 0, null pointers with R > 0. */
+WM_API int wm_vad_energy(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len, const int32_t *n_frames,
+                         int R, int n_mels, int band_lo, int band_hi, int smooth, float *raw_out, float *energy_out, wm_mem mem);
+/* The segment rule's parameters.  Defaults (wm_vad_default_params): 0.10, 0.95, 0.6, 0.5, 0.35, 25, 50, 40 -- with smooth 5
+ * on the caller's side.  THESE DEFAULTS ARE NOT VALIDATED ON REAL SPEECH: the machines this project is built on hold none;
+ * they are set on synthetic bursts over noise (tests/test_vad_cpu.py).  Any other detector's spans can be passed to
+ * binding.transcribe_long as clip_timestamps instead. */
+typedef struct wm_vad_params {
+    float q_floor, q_peak;      /* quantiles of the track that stand for the noise floor and the speech level */
+    float min_range;            /* peak - floor below this: no contrast, the whole recording is one segment */
+    float on_frac, off_frac;    /* thresholds: floor + frac * (peak - floor); speech begins at >= on, ends below off */
+    int32_t min_speech;         /* frames: a shorter span is dropped */
+    int32_t min_silence;        /* frames below off that end a span */
+    int32_t speech_pad;         /* frames added to every span over both sides: speech_pad / 2 in front, speech_pad / 2 behind */
+} wm_vad_params;
+WM_API void wm_vad_default_params(wm_vad_params *p);   /* a null p: no-op */
+/* Speech spans [start, end) in frames of a track y f32 [n] (wm_vad_energy's energy_out of one recording).  Host only, no
+ * context.  All arithmetic in double on the f32 inputs.  s = y sorted; floor = s[(size_t)(q_floor (n - 1))], peak likewise.
+ * peak - floor < min_range: the one segment [0, n) (never drop audio when there is no contrast; thresholds NaN).  Otherwise
+ * thr_on = floor + on_frac (peak - floor), thr_off likewise, and the scan of Silero VAD's get_speech_timestamps on y: a span
+ * opens at the first y >= thr_on; y < thr_off marks a pending end, which any y >= thr_on cancels; the span closes at the
+ * pending end once min_silence frames lie behind it and is kept when at least min_speech long; a span open at the end is
+ * kept when n - start >= min_speech.  Every span is padded by speech_pad frames over both sides (speech_pad / 2 each, integer
+ * division), cut to [0, n), and merged into its
+ * predecessor when it begins at or before the predecessor's end.
+ *   segments   : i32 [cap][2], nullable with cap = 0;  *n_segments : the count NEEDED (at most cap pairs are written; cap = 0
+ *                sizes the buffer);  n = 0: no segment;  stats : f32 [4], nullable: floor, peak, thr_on, thr_off.
+ * Invalid: a NaN in y, quantiles outside 0 <= q_floor < q_peak <= 1, fractions outside 0 <= off_frac <= on_frac <= 1 or
+ * on_frac = 0, a negative or non-finite min_range, min_silence < 1, a negative min_speech or speech_pad, n above 2^31 - 1,
+ * null pointers. */
+WM_API int wm_vad_segments(const float *y, int64_t n, const wm_vad_params *p, int32_t *segments, int cap, int *n_segments,
+                           float stats[4]);
+
 /* ------------------------------------------------------------ device memory helpers --- */
 /* For callers that keep inputs resident in HBM (bench.py; a Swift host would use them to
  * avoid the 5.7 MB/chunk PCIe round trip of the reference ABI). */

@@ -152,6 +152,8 @@ def load_library(path=None):
         "wm_wav_read_chunks": [vp, ip, ip, vp],
         "wm_resample_filter": [ip, vp, sz, vp, vp, vp],
         "wm_resample_16k": [vp, vp, ip, vp, vp, vp, ip, vp, ip],
+        "wm_vad_energy": [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip],
+        "wm_vad_segments": [vp, ctypes.c_int64, vp, vp, ip, vp, vp],
         "wm_audio_open": [ctypes.c_char_p, pp],
         "wm_audio_sample_rate": [vp],
         "wm_audio_channels": [vp],
@@ -191,6 +193,8 @@ def load_library(path=None):
     lib.wm_audio_num_frames.restype = ctypes.c_int64
     lib.wm_resample_out_len.argtypes = [ctypes.c_int64, ip]
     lib.wm_resample_out_len.restype = ctypes.c_int64
+    lib.wm_vad_default_params.argtypes = [vp]
+    lib.wm_vad_default_params.restype = None
     if path is None:
         _lib = lib
     return lib
@@ -660,6 +664,74 @@ def seek_clips(times, content):
     return clips
 
 
+class wm_vad_params(ctypes.Structure):
+    _fields_ = [("q_floor", ctypes.c_float), ("q_peak", ctypes.c_float), ("min_range", ctypes.c_float),
+                ("on_frac", ctypes.c_float), ("off_frac", ctypes.c_float), ("min_speech", ctypes.c_int32),
+                ("min_silence", ctypes.c_int32), ("speech_pad", ctypes.c_int32)]
+
+
+VAD_SMOOTH = 5             # frames of the moving average transcribe_long(vad=True) asks wm_vad_energy for
+PARALLEL_CLIPS_TRUE = 56   # parallel_clips=True: the decode-group size of the bench headline
+
+
+def vad_default_params():
+    """wm_vad_default_params as a dict.  Not validated on real speech (include/whisper_mi355x.h)."""
+    p = wm_vad_params()
+    load_library().wm_vad_default_params(ctypes.byref(p))
+    return {k: getattr(p, k) for k, _ in wm_vad_params._fields_}
+
+
+def vad_segments(y, params=None, stats=False):
+    """wm_vad_segments: the speech spans [(start, end)] in frames of one recording's energy track y (f32 [n],
+    Context.vad_energy).  params: None (the defaults) or a dict of overrides of wm_vad_params' fields.  stats=True:
+    (spans, (floor, peak, thr_on, thr_off))."""
+    lib = load_library()
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    p = wm_vad_params()
+    lib.wm_vad_default_params(ctypes.byref(p))
+    for k, v in (params or {}).items():
+        if k not in dict(wm_vad_params._fields_):
+            raise ValueError("vad params: no field %r" % (k,))
+        setattr(p, k, v)
+    n = ctypes.c_int(0)
+    st = np.empty(4, dtype=np.float32)
+    _check(lib, lib.wm_vad_segments(_ptr(y), y.size, ctypes.byref(p), None, 0, ctypes.byref(n), None))
+    seg = np.empty((max(n.value, 1), 2), dtype=np.int32)
+    _check(lib, lib.wm_vad_segments(_ptr(y), y.size, ctypes.byref(p), _ptr(seg), n.value, ctypes.byref(n), _ptr(st)))
+    spans = [(int(a), int(b)) for a, b in seg[:n.value]]
+    return (spans, tuple(float(v) for v in st)) if stats else spans
+
+
+def _slaney_mel_to_hz(m):
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, math.log(6.4) / 27.0
+    return min_log_hz * math.exp(logstep * (m - min_log_mel)) if m >= min_log_mel else f_sp * m
+
+
+def vad_band(n_mels, f_lo=100.0, f_hi=4000.0):
+    """(band_lo, band_hi): the mel bins whose centre frequency -- Slaney scale, 0 .. 8000 Hz, the filterbank of the front
+    end -- lies in [f_lo, f_hi].  ValueError when there is none."""
+    top = 15.0 + math.log(8000.0 / 1000.0) / (math.log(6.4) / 27.0)   # 8000 Hz in mels
+    centres = [_slaney_mel_to_hz(top * (m + 1) / (n_mels + 1)) for m in range(n_mels)]
+    inside = [m for m, f in enumerate(centres) if f_lo <= f <= f_hi]
+    if not inside:
+        raise ValueError("vad_band: no mel bin between %g and %g Hz" % (f_lo, f_hi))
+    return inside[0], inside[-1] + 1
+
+
+def vad_clips(segments, max_frames=N_FRAMES):
+    """Speech spans -> the clips transcribe_long decodes, greedy in time: a clip grows over the next span, the silence
+    between included, while span end - clip start <= max_frames.  A single span longer than max_frames stays one clip
+    (the seek loop walks it).  Returns [(start, end)]."""
+    clips = []
+    for a, b in segments:
+        if clips and b - clips[-1][0] <= max_frames:
+            clips[-1][1] = int(b)
+        else:
+            clips.append([int(a), int(b)])
+    return [(a, b) for a, b in clips]
+
+
 HALLUCINATION_PUNCTUATION = "\"'“¿([{-\"'.。,，!！?？:：”)]}、"   # PREPEND_PUNCTUATIONS + APPEND_PUNCTUATIONS
 
 
@@ -736,7 +808,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
                     prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
-                    hallucination_silence_threshold=None, carry_initial_prompt=False):
+                    hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -811,6 +883,24 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        carried_prompt() -- the initial prompt stays in front of the history's tail.  This project's rule: an initial
        prompt of n_text_ctx // 2 - 1 tokens or more leaves no room for history, and its last n_text_ctx // 2 - 1 tokens
        are the text.  Without conditioning or without an initial prompt nothing changes.
+    13. vad (None; True; or a dict of overrides: band (lo, hi), smooth, params -- wm_vad_params' fields --, max_frames):
+       after the log-mel ONE wm_vad_energy call covers all recordings (n_frames = content_frames, band vad_band(n_mels),
+       smooth 5), the tracks are downloaded, and per recording vad_segments and vad_clips make its clip list directly in
+       frames, (start, end, index) as seek_clips returns it; everything behind is 10.  A recording without contrast is one
+       clip (wm_vad_segments' flat rule), one without a span decodes no window.  vad with clip_timestamps is a ValueError.
+       The recording's result gains vad_segments and vad_clips.  The defaults are not validated on real speech; any other
+       detector's spans can be passed as clip_timestamps instead.
+    14. parallel_clips (None; N >= 1; True = 56): the clips of a recording advance in the same round.  Every clip (of 10
+       or 13; without either, the recording's one clip) is a LANE with its own seek, "before" record and last speech
+       timestamp (which starts at the clip's start time); a round holds one window of each of the first N unfinished lanes
+       in (recording, clip) order, and a lane is finished when its seek reaches its clip's end.  The lanes are an index map
+       onto the recordings' mel, language, prompt and id.  Row sample id = (((clip << 4) | min(window index within the
+       clip, 15)) & 0xFFFF) << 16 | recording id: a lane's noise is its own, so a lane of a parallel run equals the same
+       clip run alone (its number kept).  At temperatures=(0.0,) the result equals the sequential clip run.  Per recording
+       the segments and windows come in (clip, decode order), ids renumbered; every window record carries `clip` and
+       `round`.  ValueError with condition_on_previous_text (history is serial) and with
+       hallucination_silence_threshold.  reuse_encoder encodes the round's lanes as one set: N bounds its memory.
+    With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
     no prompt).  Without conditioning a recording's list heads every one of its windows; with it, it seeds the history.
@@ -843,6 +933,21 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         raise ValueError("word_timestamps needs vocab and no_timestamps")
     clips_on = clip_timestamps is not None
     times = clip_times(clip_timestamps, R)
+    vad_on = vad is not None and vad is not False
+    if vad_on and clips_on:
+        raise ValueError("vad makes the clips: it cannot be combined with clip_timestamps")
+    vad_kw = dict(vad) if isinstance(vad, dict) else {}
+    if vad_on and set(vad_kw) - {"band", "smooth", "params", "max_frames"}:
+        raise ValueError("vad: the overrides are band, smooth, params and max_frames")
+    par = parallel_clips is not None
+    if par:
+        par_n = PARALLEL_CLIPS_TRUE if parallel_clips is True else int(parallel_clips)
+        if parallel_clips is False or par_n < 1:
+            raise ValueError("parallel_clips: None, True or a lane count >= 1")
+        if cond:
+            raise ValueError("parallel_clips cannot be combined with condition_on_previous_text: the history is serial")
+        if hallucination_silence_threshold is not None:
+            raise ValueError("parallel_clips cannot be combined with hallucination_silence_threshold")
     thr = hallucination_silence_threshold
     if thr is not None:
         thr = float(thr)
@@ -911,12 +1016,36 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         ragged = cond or per_rec   # rows may differ in prompt length: wm_transcribe_mel_ragged, <|startoftranscript|> third from the end
         carry = [bool(carry_initial_prompt) and cond and len(seeds[r]) > 0 for r in range(R)]
         clips = [seek_clips(times[r], content[r]) for r in range(R)]
-        cur = [0] * R          # clip cursor
-        seek = [c[0][0] if c else 0 for c in clips]
-        before = [None] * R    # (clip cursor, seek) of the recording's previous window
-        last_speech = [0.0] * R
+        if vad_on:   # 13. the clips from the audio
+            ys = ctx.vad_energy(d_mel, mel_offs[:R], T, content, vad_kw.get("band") or vad_band(n_mels),
+                                vad_kw.get("smooth", VAD_SMOOTH), device=True)
+            for r in range(R):
+                out[r]["vad_segments"] = vad_segments(ys[r], vad_kw.get("params"))
+                out[r]["vad_clips"] = vad_clips(out[r]["vad_segments"], vad_kw.get("max_frames", N_FRAMES))
+                clips[r] = [(a, b, k) for k, (a, b) in enumerate(out[r]["vad_clips"])]
         for r in range(R):
             out[r]["language"] = langs[r]
+        # The loop below runs over UNITS.  Without parallel_clips a unit is a recording (rec is the identity, uout is out);
+        # with it (14.) a unit is a lane: one clip of recording rec[u], with its own state and its own result lists.
+        if par:
+            rec = [r for r in range(R) for _ in clips[r]]
+            clips = [[c] for cl in clips for c in cl]
+            uout = [dict(segments=[], seeks=[], windows=[]) for _ in rec]
+            last_speech = [c[0][0] * HOP_SECONDS for c in clips]
+        else:
+            rec = list(range(R))
+            uout = out
+            last_speech = [0.0] * R
+        R = len(rec)   # (from here on R counts the units)
+        if par:
+            mel_offs, T = mel_offs[rec], T[rec]
+        content, langs, seeds, carry, all_tokens, rec_ids = ([x[r] for r in rec] for x in
+                                                            (content, langs, seeds, carry, all_tokens, rec_ids))
+        reset_since = [0] * R
+        cur = [0] * R          # clip cursor
+        seek = [c[0][0] if c else 0 for c in clips]
+        before = [None] * R    # (clip cursor, seek) of the unit's previous window
+        n_round = -1
         # 3. rounds in lockstep
         while True:
             if wset is not None:   # the previous round's set
@@ -930,14 +1059,20 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 if cur[r] < len(clips[r]):
                     seek[r] = max(seek[r], clips[r][cur[r]][0])
             live = [r for r in range(R) if cur[r] < len(clips[r])]
+            if par:
+                live = live[:par_n]
             if not live:
                 break
+            n_round += 1
             for r in live:
                 if before[r] is not None and before[r][0] == cur[r] and seek[r] <= before[r][1]:
                     raise AssertionError("transcribe_long: recording %d stays at seek %d" % (r, seek[r]))
                 before[r] = (cur[r], seek[r])
             size = [min(N_FRAMES, content[r] - seek[r], clips[r][cur[r]][1] - seek[r]) for r in live]
-            ids = [((len(out[r]["windows"]) & 0xFFFF) << 16) | rec_ids[r] for r in live]
+            if par:   # (clip, window within the clip): a lane's noise is its own
+                ids = [((((clips[r][0][2] << 4) | min(len(uout[r]["windows"]), 15)) & 0xFFFF) << 16) | rec_ids[r] for r in live]
+            else:
+                ids = [((len(uout[r]["windows"]) & 0xFFFF) << 16) | rec_ids[r] for r in live]
             if ragged:
                 plist = [carried_prompt(seeds[r], all_tokens[r], reset_since[r], [int(sot), langs[r], int(task)], sot_prev,
                                         n_ctx) if carry[r] else
@@ -993,16 +1128,18 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                               no_speech_prob=float(res["no_speech_prob"][i]))
                 skip = should_skip_window(result["no_speech_prob"], result["avg_logprob"], no_speech_threshold,
                                           logprob_threshold)
-                out[r]["seeks"].append(seek[r])
-                out[r]["windows"].append(dict(seek=seek[r], segment_size=size[i], temperatures=temps, skipped=skip,
+                uout[r]["seeks"].append(seek[r])
+                uout[r]["windows"].append(dict(seek=seek[r], segment_size=size[i], temperatures=temps, skipped=skip,
                                               tokens=[int(t) for t in res["tokens"][i, :n_text]],
                                               prompt_len=len(plist[i]), prompt=[int(t) for t in plist[i]]))
-                if clips_on:
-                    out[r]["windows"][-1]["clip"] = clips[r][cur[r]][2]
+                if clips_on or vad_on or par:
+                    uout[r]["windows"][-1]["clip"] = clips[r][cur[r]][2]
+                if par:
+                    uout[r]["windows"][-1]["round"] = n_round
                 if best_of is not None:
-                    out[r]["windows"][-1]["candidate"] = cand[i]
+                    uout[r]["windows"][-1]["candidate"] = cand[i]
                 if beam_size is not None:
-                    out[r]["windows"][-1]["hypothesis"] = hyp[i]
+                    uout[r]["windows"][-1]["hypothesis"] = hyp[i]
                 if skip:
                     seek[r] += size[i]
                     continue
@@ -1017,8 +1154,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                                                         result["temperature"], False,
                                                                         prompt_reset_on_temperature)
                 for sg in segs:
-                    sg["id"] = len(out[r]["segments"])
-                    out[r]["segments"].append(sg)
+                    sg["id"] = len(uout[r]["segments"])
+                    uout[r]["segments"].append(sg)
             if not kept:
                 continue
             # 6. the word step of the round: one alignment call, then per recording the word rules and the word-driven seek
@@ -1055,9 +1192,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     next_seek, segs, tag = hallucination_silence_skip(segs, seek[r], size[i], content[r], thr, single_ending,
                                                                       last_speech[r], next_seek)
                     if tag is not None:   # (the recording's one window of this round is its last record)
-                        out[r]["windows"][-1]["hallucination"] = tag
+                        uout[r]["windows"][-1]["hallucination"] = tag
                     if tag == "surrounded":
-                        out[r]["windows"][-1]["dropped_segments"] = n_segs - len(segs)
+                        uout[r]["windows"][-1]["dropped_segments"] = n_segs - len(segs)
                     if tag == "leading":
                         seek[r] = next_seek
                         continue
@@ -1071,8 +1208,15 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                                                         float(res["temperature"][i]), False,
                                                                         prompt_reset_on_temperature)
                 for sg in segs:
+                    sg["id"] = len(uout[r]["segments"])
+                    uout[r]["segments"].append(sg)
+        if par:   # per recording: its lanes in clip order, each in decode order, ids renumbered
+            for u, r in enumerate(rec):
+                for sg in uout[u]["segments"]:
                     sg["id"] = len(out[r]["segments"])
                     out[r]["segments"].append(sg)
+                out[r]["seeks"] += uout[u]["seeks"]
+                out[r]["windows"] += uout[u]["windows"]
     finally:
         if wset is not None:
             wset.close()
@@ -1244,6 +1388,42 @@ class Context:
             if d_pcm is not None:
                 self.dev_free(d_pcm)
         return d_out, out_offs
+
+    def vad_energy(self, mel, mel_offs, T, n_frames, band, smooth=VAD_SMOOTH, device=False, raw=False, n_mels=None):
+        """wm_vad_energy: the smoothed band energy of R recordings' log-mels in one launch.  mel: logmel_long's output --
+        a flat f32 array, or with device=True the device pointer; mel_offs i64 [R] and T i32 [R] as logmel_long(...,
+        device=True) returns them; n_frames: the frames to do per recording (the content frames T - 3000); band = (lo,
+        hi).  Returns a list of f32 [n_frames[r]] on the host (device=True: computed where the mel lies, then
+        downloaded); raw=True: (the unsmoothed tracks, the smoothed ones)."""
+        base = np.ascontiguousarray(mel_offs, dtype=np.int64)
+        R = len(base)
+        T = np.ascontiguousarray(T, dtype=np.int32)
+        n = np.ascontiguousarray(n_frames, dtype=np.int32)
+        if len(T) != R or len(n) != R:
+            raise ValueError("vad_energy: mel_offs, T and n_frames have one entry per recording")
+        offs = np.concatenate([[0], np.cumsum(np.maximum(n, 0).astype(np.int64))])
+        total = max(int(offs[-1]), 1)
+        lo, hi = int(band[0]), int(band[1])
+        if n_mels is None:   # (a front-end-only context has no dims)
+            n_mels = int(self.dims["n_mels"]) if self.dims else 80
+        if not device:
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            y = np.empty(total, dtype=np.float32)
+            e = np.empty(total, dtype=np.float32) if raw else None
+            _check(self.lib, self.lib.wm_vad_energy(self.handle, _ptr(mel), _ptr(base), _ptr(T), _ptr(n), R, n_mels, lo, hi,
+                                                    int(smooth), _ptr(e) if raw else None, _ptr(y), WM_MEM_HOST))
+        else:
+            d_y = self.dev_malloc(total * 4 * (2 if raw else 1))
+            try:
+                d_e = ctypes.c_void_p(d_y.value + total * 4) if raw else None
+                _check(self.lib, self.lib.wm_vad_energy(self.handle, mel, _ptr(base), _ptr(T), _ptr(n), R, n_mels, lo, hi,
+                                                        int(smooth), d_e, d_y, WM_MEM_DEVICE))
+                both = self.download(d_y, (2 if raw else 1, total), np.float32)
+            finally:
+                self.dev_free(d_y)
+            y, e = both[0], (both[1] if raw else None)
+        ys = [y[offs[r]:offs[r + 1]] for r in range(R)]
+        return ([e[offs[r]:offs[r + 1]] for r in range(R)], ys) if raw else ys
 
     # ---- device memory --------------------------------------------------------------
     def dev_malloc(self, nbytes):

@@ -192,6 +192,7 @@ extern "C" void wm_destroy(wm_ctx *ctx) {
     wm_model_destroy(ctx);
     wm_frontend_destroy(&ctx->fe);
     wm_resample_destroy(&ctx->rs);
+    wm_vad_destroy(&ctx->vad);
     ctx->prof.reset();
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -456,6 +457,50 @@ extern "C" int wm_resample_16k(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype,
                           ctx->stream));
     WM_TRY(wm_resample_run(&ctx->rs, &ctx->prof, ctx->stream, d_in, pcm_dtype, offs.data(), n_channels, sample_rates, R, (float *)d_out));
     WM_HIP(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    return WM_OK;
+} WM_API_CATCH
+
+// Speech-activity energy of wm_logmel_long's output (vad.hip): per frame, log10 of the band's mel power, smoothed
+extern "C" int wm_vad_energy(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len, const int32_t *n_frames,
+                             int R, int n_mels, int band_lo, int band_hi, int smooth, float *raw_out, float *energy_out,
+                             wm_mem mem) try {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(R >= 0 && R <= 65535, WM_ERR_INVALID, "vad: R must be 0 .. 65535, got %d", R);
+    WM_REQUIRE(n_mels == 80 || n_mels == 128, WM_ERR_INVALID, "vad: n_mels must be 80 or 128, got %d", n_mels);
+    WM_REQUIRE(band_lo >= 0 && band_lo < band_hi && band_hi <= n_mels, WM_ERR_INVALID, "vad: band [%d, %d) outside 0 <= lo < hi <= %d",
+               band_lo, band_hi, n_mels);
+    WM_REQUIRE(smooth >= 1 && smooth <= WM_VAD_MAX_SMOOTH && (smooth & 1), WM_ERR_INVALID, "vad: smooth must be odd, 1 .. %d, got %d",
+               WM_VAD_MAX_SMOOTH, smooth);
+    if (R == 0) return WM_OK;
+    WM_REQUIRE(mel && mel_base && mel_len && n_frames && energy_out, WM_ERR_INVALID, "vad: null pointer");
+    const int n_band = band_hi - band_lo;
+    std::vector<int64_t> row0(R);
+    int64_t n_out = 0, n_in = 0;
+    for (int r = 0; r < R; ++r) {
+        WM_REQUIRE(mel_base[r] >= 0 && mel_len[r] >= 1, WM_ERR_INVALID, "vad: recording %d: mel_base %lld, mel_len %d", r,
+                   (long long)mel_base[r], mel_len[r]);
+        WM_REQUIRE(n_frames[r] >= 0 && n_frames[r] <= mel_len[r], WM_ERR_INVALID, "vad: recording %d: n_frames %d outside [0, %d]", r,
+                   n_frames[r], mel_len[r]);
+        row0[r] = mem == WM_MEM_DEVICE ? mel_base[r] + (int64_t)band_lo * mel_len[r] : n_in;
+        n_out += n_frames[r];
+        n_in += (int64_t)n_band * mel_len[r];
+    }
+    if (mem == WM_MEM_DEVICE)
+        return wm_vad_run(&ctx->vad, &ctx->prof, ctx->stream, mel, row0.data(), mel_len, n_frames, R, n_band, smooth, raw_out, energy_out);
+    if (n_out == 0) return WM_OK;
+    // host memory: only each recording's band rows cross PCIe, packed one recording after the other
+    const size_t in_b = (size_t)n_in * sizeof(float), out_b = (size_t)n_out * sizeof(float);
+    const size_t in_al = (in_b + 255) & ~(size_t)255, out_al = (out_b + 255) & ~(size_t)255;
+    WM_TRY(ensure_scratch(ctx, in_al + 2 * out_al));
+    char *d_in = (char *)ctx->fe.scratch, *d_y = d_in + in_al, *d_raw = d_y + out_al;
+    for (int r = 0; r < R; ++r)
+        WM_HIP(hipMemcpyAsync(d_in + (size_t)row0[r] * sizeof(float), mel + mel_base[r] + (int64_t)band_lo * mel_len[r],
+                              (size_t)n_band * mel_len[r] * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    WM_TRY(wm_vad_run(&ctx->vad, &ctx->prof, ctx->stream, (const float *)d_in, row0.data(), mel_len, n_frames, R, n_band, smooth,
+                      raw_out ? (float *)d_raw : nullptr, (float *)d_y));
+    WM_HIP(hipMemcpyAsync(energy_out, d_y, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (raw_out) WM_HIP(hipMemcpyAsync(raw_out, d_raw, out_b, hipMemcpyDeviceToHost, ctx->stream));
     WM_HIP(hipStreamSynchronize(ctx->stream));
     return WM_OK;
 } WM_API_CATCH

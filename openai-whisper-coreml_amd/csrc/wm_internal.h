@@ -167,6 +167,19 @@ void wm_resample_destroy(WmResampler *rs);
 int wm_resample_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
                     const int64_t *offs, const int32_t *n_channels, const int32_t *sample_rates, int R, float *d_out);
 
+// ---------------------------------------------------------------- speech-activity energy (vad.hip) ----------
+constexpr int WM_VAD_MAX_SMOOTH = 31;
+struct WmVad {
+    void *tab = nullptr;                // recording and workgroup tables of a call
+    size_t tab_bytes = 0;
+};
+void wm_vad_destroy(WmVad *vad);
+// Device-pointer core of wm_vad_energy: recording r's band is the n_band rows of stride[r] frames from element row0[r] of
+// d_mel (row0, stride, n_frames: host) -> d_raw (nullable) and d_energy, n_frames[r] values after those of the recordings
+// before it.  One launch.
+int wm_vad_run(WmVad *vad, WmProfiler *prof, hipStream_t stream, const float *d_mel, const int64_t *row0, const int32_t *stride,
+               const int32_t *n_frames, int R, int n_band, int smooth, float *d_raw, float *d_energy);
+
 // ---------------------------------------------------------------- context ------------
 struct WmModel;  // model.h
 struct wm_ctx;
@@ -185,6 +198,7 @@ struct wm_ctx {
     WmProfiler prof;
     WmFrontend fe;
     WmResampler rs;
+    WmVad vad;
     WmModel *model = nullptr;
     float stage_ms[3] = {0, 0, 0};
     std::vector<wm_ctx *> lanes;  // weight-sharing clones owned by this context (wm_transcribe_greedy)

@@ -254,6 +254,60 @@ struct Whisper {
         return result
     }
 
+    /// wm_vad_params (include/whisper_mi355x.h), field for field; `VadParams.defaults()` is wm_vad_default_params.  The
+    /// defaults are not validated on real speech.
+    struct VadParams {
+        var qFloor: Float = 0, qPeak: Float = 0, minRange: Float = 0, onFrac: Float = 0, offFrac: Float = 0
+        var minSpeech: Int32 = 0, minSilence: Int32 = 0, speechPad: Int32 = 0
+    }
+
+    /// wm_vad_default_params.  Not compiled in this repository (see the top of the file).
+    func vadDefaultParams() throws -> VadParams {
+        typealias DefaultsFn = @convention(c) (UnsafeMutableRawPointer?) -> Void
+        let f: DefaultsFn = try sym("wm_vad_default_params")
+        var p = VadParams()
+        withUnsafeMutableBytes(of: &p) { f($0.baseAddress) }
+        return p
+    }
+
+    /// Smoothed band energy per frame of logMelLong's output (wm_vad_energy: one launch for all recordings), host memory.
+    /// mel: the recordings' [nMels][frames[r]] blocks back to back; nFrames[r]: the frames to do (the content frames,
+    /// frames[r] - 3000); band: the mel rows [lo, hi); smooth: odd, 1 ... 31.  Returns one track per recording.
+    /// Not compiled in this repository (see the top of the file).
+    func vadEnergy(mel: [Float], frames: [Int32], nFrames: [Int32], nMels: Int32, bandLo: Int32, bandHi: Int32,
+                   smooth: Int32 = 5) throws -> [[Float]] {
+        typealias VadFn = @convention(c) (OpaquePointer, UnsafePointer<Float>, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                          UnsafePointer<Int32>, Int32, Int32, Int32, Int32, Int32, UnsafeMutablePointer<Float>?,
+                                          UnsafeMutablePointer<Float>, Int32) -> Int32
+        var base: [Int64] = []
+        var at: Int64 = 0
+        for t in frames { base.append(at); at += Int64(t) * Int64(nMels) }
+        var out = [Float](repeating: 0, count: max(1, nFrames.reduce(0) { $0 + Int($1) }))
+        let f: VadFn = try sym("wm_vad_energy")
+        try check(f(ctx, mel, base, frames, nFrames, Int32(frames.count), nMels, bandLo, bandHi, smooth, nil, &out, 0))
+        var result: [[Float]] = []
+        var o = 0
+        for n in nFrames {
+            result.append(Array(out[o..<o + Int(n)]))
+            o += Int(n)
+        }
+        return result
+    }
+
+    /// Speech spans [start, end) in frames of one recording's energy track (wm_vad_segments: host only): a sizing call,
+    /// then the call that fills.  Not compiled in this repository (see the top of the file).
+    func vadSegments(track: [Float], params: VadParams) throws -> [(start: Int32, end: Int32)] {
+        typealias SegFn = @convention(c) (UnsafePointer<Float>?, Int64, UnsafeRawPointer?, UnsafeMutablePointer<Int32>?, Int32,
+                                          UnsafeMutablePointer<Int32>, UnsafeMutablePointer<Float>?) -> Int32
+        let f: SegFn = try sym("wm_vad_segments")
+        var p = params
+        var n: Int32 = 0
+        try withUnsafeBytes(of: &p) { try check(f(track, Int64(track.count), $0.baseAddress, nil, 0, &n, nil)) }
+        var pairs = [Int32](repeating: 0, count: max(2, 2 * Int(n)))
+        try withUnsafeBytes(of: &p) { try check(f(track, Int64(track.count), $0.baseAddress, &pairs, n, &n, nil)) }
+        return (0..<Int(n)).map { (pairs[2 * $0], pairs[2 * $0 + 1]) }
+    }
+
     /// A RIFF/WAVE file of any rate, 1 ... 8 channels, integer PCM 8 / 16 / 24 / 32 bits or IEEE float 32 / 64 bits
     /// (wm_audio_*: the general reader beside wm_wav_*): interleaved f32 frames, the rate and the channel count --
     /// the arguments of resample16k.  Not compiled in this repository (see the top of the file).
