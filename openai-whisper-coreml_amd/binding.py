@@ -16,6 +16,7 @@ CPU fallback: if the library is missing, or no gfx950 device is usable, calls ra
 import ctypes
 import math
 import os
+import types
 import zlib
 
 import numpy as np
@@ -209,6 +210,10 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _ptr_or_null(a):
+    return None if a is None else _ptr(a)
+
+
 def generateSpectrogram(audio):
     """stft.swift:8-19.  audio: 480000 doubles -> 240000 doubles ([80][3000] row-major).
 
@@ -345,6 +350,16 @@ def fallback_seed(seed, k):
     return (int(seed) + int(k)) & 0xFFFFFFFFFFFFFFFF
 
 
+def fallback_step_extra(t, best_of=None, length_penalty=None, beam_size=None, patience=None):
+    """The keywords the fallback step at temperature t adds to Context.transcribe_mel / transcribe_windows: openai-whisper
+    uses beam_size at temperature 0 and best_of above it; {}: the plain call."""
+    if beam_size is not None and t == 0:
+        return dict(beam_size=beam_size, patience=patience, length_penalty=length_penalty)
+    if best_of is not None and t > 0:
+        return dict(best_of=best_of, length_penalty=length_penalty)
+    return {}
+
+
 def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                              compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
                              vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None, best_of=None,
@@ -374,12 +389,8 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     beam_max_candidates(beam_size, patience)
 
     def decode(todo, t, sd):
-        extra = None
-        if beam_size is not None and t == 0:
-            extra = dict(beam_size=beam_size, patience=patience, length_penalty=length_penalty)
-        elif best_of is not None and t > 0:
-            extra = dict(best_of=best_of, length_penalty=length_penalty)
-        if extra is not None:
+        extra = fallback_step_extra(t, best_of, length_penalty, beam_size, patience)
+        if extra:
             n_mels = int(ctx.dims["n_mels"])
             mel = ctx.logmel(pcm[todo], n_mels=n_mels)
             return ctx.transcribe_mel(mel, np.arange(len(todo), dtype=np.int64) * (n_mels * N_FRAMES), N_FRAMES, 0, N_FRAMES,
@@ -801,6 +812,306 @@ def hallucination_silence_skip(segments, seek, segment_size, content, threshold,
     return next_seek, segments, None
 
 
+# ---- the parts of transcribe_long: options, units, the rows of a round, and the language / clip / word steps ---------------
+class _LongOptions(types.SimpleNamespace):
+    """transcribe_long's arguments under their names, plus what its checks derive from them.  The checks raise in the order
+    they always had: early() before any library call and prompt_head() behind the language step; between them the log-mel
+    and the language step check their own arguments (sample_rates; language, lang_first, lang_last)."""
+
+    def early(self, R):
+        beam_max_candidates(self.beam_size, self.patience)
+        self.rec_ids = list(range(R)) if self.recording_ids is None else [int(i) for i in self.recording_ids]
+        if len(self.rec_ids) != R or any(i < 0 or i >= 65536 for i in self.rec_ids):
+            raise ValueError("recording_ids: one per recording, each 0 .. 65535")
+        self.n_ctx = int(self.ctx.dims["n_text_ctx"])
+        self.n_mels = int(self.ctx.dims["n_mels"])
+        self.max_new = self.n_ctx // 2
+        self.cond = bool(self.condition_on_previous_text)
+        if self.cond:
+            if self.sot_prev is None:
+                raise ValueError("condition_on_previous_text needs sot_prev")
+            self.max_new = min(self.n_ctx // 2, self.n_ctx - (self.n_ctx // 2 + 3))
+        ip = self.initial_prompt_tokens
+        self.per_rec = ip is not None and len(ip) > 0 and all(isinstance(x, (list, tuple, np.ndarray)) for x in ip)
+        if self.per_rec and len(ip) != R:
+            raise ValueError("initial_prompt_tokens: one list per recording")
+        if self.vocab_size is None:
+            self.vocab_size = int(self.ctx.dims["n_vocab"])
+        self.words_on = bool(self.word_timestamps)
+        if self.words_on and (self.vocab is None or self.no_timestamps is None):
+            raise ValueError("word_timestamps needs vocab and no_timestamps")
+        self.clips_on = self.clip_timestamps is not None
+        self.times = clip_times(self.clip_timestamps, R)
+        self.vad_on = self.vad is not None and self.vad is not False
+        if self.vad_on and self.clips_on:
+            raise ValueError("vad makes the clips: it cannot be combined with clip_timestamps")
+        self.vad_kw = dict(self.vad) if isinstance(self.vad, dict) else {}
+        if self.vad_on and set(self.vad_kw) - {"band", "smooth", "params", "max_frames"}:
+            raise ValueError("vad: the overrides are band, smooth, params and max_frames")
+        self.par = self.parallel_clips is not None
+        self.par_n = None   # lanes per round (None: every live unit)
+        if self.par:
+            self.par_n = PARALLEL_CLIPS_TRUE if self.parallel_clips is True else int(self.parallel_clips)
+            if self.parallel_clips is False or self.par_n < 1:
+                raise ValueError("parallel_clips: None, True or a lane count >= 1")
+            if self.cond:
+                raise ValueError("parallel_clips cannot be combined with condition_on_previous_text: the history is serial")
+            if self.hallucination_silence_threshold is not None:
+                raise ValueError("parallel_clips cannot be combined with hallucination_silence_threshold")
+        self.thr = self.hallucination_silence_threshold
+        if self.thr is not None:
+            self.thr = float(self.thr)
+            if not math.isfinite(self.thr) or self.thr < 0:
+                raise ValueError("hallucination_silence_threshold: finite seconds >= 0")
+            if not self.words_on:
+                raise ValueError("hallucination_silence_threshold needs word_timestamps")
+        if self.prepend_punctuations is None:
+            self.prepend_punctuations = PREPEND_PUNCTUATIONS
+        if self.append_punctuations is None:
+            self.append_punctuations = APPEND_PUNCTUATIONS
+
+    def prompt_head(self):
+        """How the rows carry their prompts: head, the tokens in front of [sot, language, task] in a table of one length, or
+        ragged -- lists whose lengths may differ --, and sot_kw, which tells a decode call where <|startoftranscript|> is."""
+        self.head = []
+        if self.initial_prompt_tokens is not None:
+            if self.sot_prev is None:
+                raise ValueError("initial_prompt_tokens need sot_prev")
+            if not self.per_rec:
+                self.head = [int(self.sot_prev)] + [int(t) for t in self.initial_prompt_tokens][-(self.n_ctx // 2 - 1):]
+        self.ragged = self.cond or self.per_rec
+        self.sot_kw = dict(sot_tail=3) if self.ragged else dict(sot_index=len(self.head))
+
+
+class _Unit:
+    """What transcribe_long's rounds advance: a recording with its clip list or, with parallel_clips (lane=True), ONE of its
+    clips.  rec .. seed_tokens (the initial prompt) are the recording's; the history (all_tokens, reset_since), the clip
+    cursor, the seek, `before` -- (cursor, seek) of the previous window --, last_speech and the result lists its own."""
+    __slots__ = ("index", "rec", "rec_id", "mel_off", "T", "content", "lang", "seed_tokens", "carry", "all_tokens",
+                 "reset_since", "clips", "cur", "seek", "before", "last_speech", "lane", "segments", "seeks", "windows")
+
+    def __init__(self, index, rec, rec_id, mel_off, T, lang, seed_tokens, carry, clips, lane):
+        self.index, self.rec, self.rec_id, self.mel_off, self.T, self.lang = index, rec, rec_id, mel_off, T, lang
+        self.content = int(T) - N_FRAMES
+        self.seed_tokens, self.carry, self.clips, self.lane = seed_tokens, carry, clips, lane
+        self.all_tokens, self.reset_since = list(seed_tokens), 0
+        self.cur, self.seek, self.before = 0, clips[0][0] if clips else 0, None
+        self.last_speech = clips[0][0] * HOP_SECONDS if lane else 0.0
+        self.segments, self.seeks, self.windows = [], [], []
+
+    def advance(self):
+        """the clip cursor before a round: a seek at or past its clip's end moves to the next clip's start; False: none left"""
+        while self.cur < len(self.clips) and self.seek >= self.clips[self.cur][1]:
+            self.cur += 1
+            if self.cur < len(self.clips):
+                self.seek = self.clips[self.cur][0]
+        if self.cur == len(self.clips):
+            return False
+        self.seek = max(self.seek, self.clips[self.cur][0])
+        return True
+
+    def open_window(self):
+        """the frames of the window at the seek, which has grown since the unit's previous window within this clip"""
+        if self.before is not None and self.before[0] == self.cur and self.seek <= self.before[1]:
+            raise AssertionError("transcribe_long: recording %d stays at seek %d" % (self.index, self.seek))
+        self.before = (self.cur, self.seek)
+        return min(N_FRAMES, self.content - self.seek, self.clips[self.cur][1] - self.seek)
+
+    def sample_id(self):
+        """(window ordinal << 16) | recording id; a lane counts (clip, window within the clip): its noise is its own"""
+        n = len(self.windows)
+        if self.lane:
+            n = (self.clips[0][2] << 4) | min(n, 15)
+        return ((n & 0xFFFF) << 16) | self.rec_id
+
+    def prompt(self, o):
+        seq = [int(o.sot), self.lang, int(o.task)]
+        if not o.ragged:
+            return o.head + seq
+        if self.carry:
+            return carried_prompt(self.seed_tokens, self.all_tokens, self.reset_since, seq, o.sot_prev, o.n_ctx)
+        return conditioned_prompt(self.all_tokens, self.reset_since if o.cond else 0, seq, o.sot_prev, o.n_ctx)
+
+    def record_window(self, o, size, prompt, temperatures, skipped, tokens, n_round, kept_by):
+        self.seeks.append(self.seek)
+        w = dict(seek=self.seek, segment_size=size, temperatures=temperatures, skipped=skipped,
+                 tokens=[int(t) for t in tokens], prompt_len=len(prompt), prompt=[int(t) for t in prompt])
+        if o.clips_on or o.vad_on or o.par:
+            w["clip"] = self.clips[self.cur][2]
+        if o.par:
+            w["round"] = n_round
+        w.update(kept_by)
+        self.windows.append(w)
+
+    def commit(self, o, segments, next_seek, temperature):
+        """a kept window: the seek, the history of a conditioned run, and the segments"""
+        self.seek = next_seek
+        if o.cond:
+            self.all_tokens, self.reset_since = conditioned_history(self.all_tokens, self.reset_since, segments, temperature,
+                                                                    False, o.prompt_reset_on_temperature)
+        self.segments += segments
+
+    def deliver(self, out):
+        """the unit's lists behind those its recording has already (lanes arrive in clip order); the segments get their ids"""
+        for sg in self.segments:
+            sg["id"] = len(out["segments"])
+            out["segments"].append(sg)
+        out["seeks"] += self.seeks
+        out["windows"] += self.windows
+
+
+class _RoundRows:
+    """The rows of a round: row i is window [seek, seek + sizes[i]) of units[i], read from the recordings' log-mel on the
+    device or, with reuse_encoder, from the Windows set those windows are encoded into ONCE here (close() frees it).
+    decode is fallback_decode's `decode` with the step rule of fallback_step_extra; kept_by[row]: `candidate` (with best_of)
+    and `hypothesis` (with beam_size), the index the row's last step kept -- 0 after a step of the other kind."""
+
+    def __init__(self, o, d_mel, units, sizes, prompts, sample_ids):
+        self.o, self.d_mel, self.units, self.sizes, self.ids = o, d_mel, units, sizes, sample_ids
+        self.prompts = prompts if o.ragged else np.array(prompts, dtype=np.int32)
+        self.kept_by = [{} for _ in units]
+        self.set = o.ctx.encode_windows(*self._mel_windows(range(len(units))), mem=WM_MEM_DEVICE) if o.reuse_encoder else None
+
+    def _mel_windows(self, rows):
+        """(a unit's seek is still the window's while the round's calls run)"""
+        us = [self.units[i] for i in rows]
+        return (self.d_mel, np.array([u.mel_off for u in us]), np.array([u.T for u in us]), [u.seek for u in us],
+                [self.sizes[i] for i in rows])
+
+    def decode(self, todo, t, sd):
+        o = self.o
+        extra = fallback_step_extra(t, o.best_of, o.length_penalty, o.beam_size, o.patience)
+        prompts = [self.prompts[i] for i in todo] if o.ragged else self.prompts[todo]
+        kw = dict(eot=o.eot, temperature=t, seed=sd, no_speech_token=o.no_speech_token, sample_ids=[self.ids[i] for i in todo],
+                  **o.sot_kw, **extra)
+        if self.set is not None:   # the same call without the encoder pass
+            r = o.ctx.transcribe_windows(self.set, [int(i) for i in todo], prompts, o.max_new, **kw)
+        else:
+            r = o.ctx.transcribe_mel(*self._mel_windows(todo), prompts, o.max_new, mem=WM_MEM_DEVICE, **kw)
+        for k, i in enumerate(todo):
+            if o.best_of is not None:
+                self.kept_by[i]["candidate"] = int(r.candidate[k]) if "best_of" in extra else 0
+            if o.beam_size is not None:
+                self.kept_by[i]["hypothesis"] = int(r.hypothesis[k]) if "beam_size" in extra else 0
+        return r
+
+    def align(self, rows, texts, sot_seqs):
+        o = self.o
+        if self.set is not None:
+            return o.ctx.align_windows(self.set, rows, texts, sot_seqs, o.no_timestamps, o.eot, medfilt_width=7, qk_scale=1.0)
+        return o.ctx.align_mel(*self._mel_windows(rows), texts, sot_seqs, o.no_timestamps, o.eot, medfilt_width=7, qk_scale=1.0,
+                               mem=WM_MEM_DEVICE)
+
+    def close(self):
+        if self.set is not None:
+            self.set.close()
+
+
+def _long_mel(o, R):
+    """1. the log-mel of all recordings on the device: (pointer, element offsets, T)"""
+    ctx = o.ctx
+    if o.sample_rates is None:
+        return ctx.logmel_long(o.recordings, n_mels=o.n_mels, device=True)
+    if len(o.sample_rates) != R:
+        raise ValueError("sample_rates: one per recording")
+    d_pcm, pcm_offs = ctx.resample_16k(o.recordings, o.sample_rates, device=True)
+    try:
+        return ctx.logmel_long_device(d_pcm, np.float32, pcm_offs, n_mels=o.n_mels)
+    finally:
+        ctx.dev_free(d_pcm)
+
+
+def _long_languages(o, d_mel, mel_offs, T):
+    """2. one language token per recording: as given, or detected on frames [0, 3000) of every recording"""
+    ctx, R = o.ctx, len(T)
+    if o.language is not None:
+        langs = [int(o.language)] * R if np.ndim(o.language) == 0 else [int(x) for x in o.language]
+        if len(langs) != R:
+            raise ValueError("language: one token id per recording")
+        return langs
+    if o.lang_first is None or o.lang_last is None:
+        raise ValueError("language detection needs lang_first / lang_last")
+    if o.reuse_encoder:
+        with ctx.encode_windows(d_mel, mel_offs[:R], T, 0, N_FRAMES, mem=WM_MEM_DEVICE) as lid_set:
+            idx = np.concatenate([ctx.windows_detect_language(lid_set, np.arange(a, min(a + 128, R)), o.sot, o.lang_first,
+                                                              o.lang_last)[0] for a in range(0, R, 128)])
+    else:
+        win = np.empty((R, o.n_mels, N_FRAMES), dtype=np.float32)
+        for r in range(R):
+            for c in range(o.n_mels):
+                src = ctypes.c_void_p(d_mel.value + 4 * (int(mel_offs[r]) + c * int(T[r])))
+                win[r, c] = ctx.download(src, N_FRAMES, np.float32)
+        idx, _ = ctx.detect_language_probs(ctx.encode_mel(win), o.sot, o.lang_first, o.lang_last)
+    return [int(o.lang_first + i) for i in idx]
+
+
+def _long_units(o, out, langs, d_mel, mel_offs, T):
+    """One unit per recording holding its clips [(first frame, end frame, number)] -- of clip_timestamps (10.) or, with vad,
+    from the audio (13.) -- or, with parallel_clips (14.), one unit per clip, in (recording, clip) order."""
+    R, ip = len(T), o.initial_prompt_tokens
+    content = [int(t) - N_FRAMES for t in T]
+    clips = [seek_clips(o.times[r], content[r]) for r in range(R)]
+    if o.vad_on:
+        kw = o.vad_kw
+        ys = o.ctx.vad_energy(d_mel, mel_offs[:R], T, content, kw.get("band") or vad_band(o.n_mels),
+                              kw.get("smooth", VAD_SMOOTH), device=True)
+        for r in range(R):
+            out[r]["vad_segments"] = vad_segments(ys[r], kw.get("params"))
+            out[r]["vad_clips"] = vad_clips(out[r]["vad_segments"], kw.get("max_frames", N_FRAMES))
+            clips[r] = [(a, b, k) for k, (a, b) in enumerate(out[r]["vad_clips"])]
+    units = []
+    for r, cl in enumerate(clips):
+        out[r]["language"] = langs[r]
+        seed = [int(t) for t in (ip[r] if o.per_rec else ip if ip is not None else [])]
+        carry = bool(o.carry_initial_prompt) and o.cond and len(seed) > 0
+        for own in ([[c] for c in cl] if o.par else [cl]):
+            units.append(_Unit(len(units), r, o.rec_ids[r], mel_offs[r], T[r], langs[r], seed, carry, own, o.par))
+    return units
+
+
+def _long_word_step(o, source, live, sizes, kept, res):
+    """6. the word step of a round: ONE alignment call over the kept windows that have a text token and at least 2 frames,
+    then per window the word rules, the word-driven seek (or 11.), the clearing of empty segments and the commit.
+    kept: (row of the round, segments, next seek, single_timestamp_ending) of every kept window."""
+    eot = o.eot
+    texts = [[t for sg in k[1] for t in sg["tokens"] if t < eot] for k in kept]
+    go = [n for n, k in enumerate(kept) if texts[n] and sizes[k[0]] >= 2]
+    if go:
+        rows = [kept[n][0] for n in go]
+        sf, pr = source.align(rows, [texts[n] for n in go], [[int(o.sot), live[i].lang, int(o.task)] for i in rows])
+    for n, (i, segs, next_seek, single_ending) in enumerate(kept):
+        u = live[i]
+        if n in go:
+            g = go.index(n)
+            code = u.lang - int(o.sot) - 1
+            code = Whisper.LANGUAGES[code] if 0 <= code < len(Whisper.LANGUAGES) else None
+            window_word_timestamps(o.vocab, segs, sf[g], pr[g], u.seek, eot, u.last_speech, code, o.prepend_punctuations,
+                                   o.append_punctuations)
+        else:
+            for sg in segs:
+                sg["words"] = []
+        if o.thr is None:
+            ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
+            if ends and not single_ending and ends[-1] > u.seek * HOP_SECONDS:
+                next_seek = int(round(ends[-1] * 100))
+        else:   # 11. (u.last_speech is still the value before this window; the window is the unit's last record)
+            n_segs = len(segs)
+            next_seek, segs, tag = hallucination_silence_skip(segs, u.seek, sizes[i], u.content, o.thr, single_ending,
+                                                              u.last_speech, next_seek)
+            if tag is not None:
+                u.windows[-1]["hallucination"] = tag
+            if tag == "surrounded":
+                u.windows[-1]["dropped_segments"] = n_segs - len(segs)
+            if tag == "leading":
+                u.seek = next_seek
+                continue
+        ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
+        if ends:
+            u.last_speech = ends[-1]
+        clear_empty_segments(segs, eot, o.vocab, words=True)
+        u.commit(o, segs, next_seek, float(res["temperature"][i]))
+
+
 def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_speech_token, lang_first=None,
                     lang_last=None, language=None, sot_prev=None, initial_prompt_tokens=None, recording_ids=None,
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
@@ -909,321 +1220,63 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     segments (openai-whisper's keys id seek start end tokens temperature avg_logprob compression_ratio no_speech_prob, plus
     text with a Vocab and words [{word, start, end, probability}] with word_timestamps), text (with a Vocab), seeks (the first frame of every decoded window) and windows (per window:
     seek, segment_size, the fallback steps' temperatures, skipped, prompt_len, prompt)."""
+    o = _LongOptions(**locals())
     R = len(recordings)
-    beam_max_candidates(beam_size, patience)
-    rec_ids = list(range(R)) if recording_ids is None else [int(i) for i in recording_ids]
-    if len(rec_ids) != R or any(i < 0 or i >= 65536 for i in rec_ids):
-        raise ValueError("recording_ids: one per recording, each 0 .. 65535")
-    n_ctx = int(ctx.dims["n_text_ctx"])
-    n_mels = int(ctx.dims["n_mels"])
-    max_new = n_ctx // 2
-    cond = bool(condition_on_previous_text)
-    if cond:
-        if sot_prev is None:
-            raise ValueError("condition_on_previous_text needs sot_prev")
-        max_new = min(n_ctx // 2, n_ctx - (n_ctx // 2 + 3))
-    per_rec = (initial_prompt_tokens is not None and len(initial_prompt_tokens) > 0
-               and all(isinstance(x, (list, tuple, np.ndarray)) for x in initial_prompt_tokens))
-    if per_rec and len(initial_prompt_tokens) != R:
-        raise ValueError("initial_prompt_tokens: one list per recording")
-    if vocab_size is None:
-        vocab_size = int(ctx.dims["n_vocab"])
-    words_on = bool(word_timestamps)
-    if words_on and (vocab is None or no_timestamps is None):
-        raise ValueError("word_timestamps needs vocab and no_timestamps")
-    clips_on = clip_timestamps is not None
-    times = clip_times(clip_timestamps, R)
-    vad_on = vad is not None and vad is not False
-    if vad_on and clips_on:
-        raise ValueError("vad makes the clips: it cannot be combined with clip_timestamps")
-    vad_kw = dict(vad) if isinstance(vad, dict) else {}
-    if vad_on and set(vad_kw) - {"band", "smooth", "params", "max_frames"}:
-        raise ValueError("vad: the overrides are band, smooth, params and max_frames")
-    par = parallel_clips is not None
-    if par:
-        par_n = PARALLEL_CLIPS_TRUE if parallel_clips is True else int(parallel_clips)
-        if parallel_clips is False or par_n < 1:
-            raise ValueError("parallel_clips: None, True or a lane count >= 1")
-        if cond:
-            raise ValueError("parallel_clips cannot be combined with condition_on_previous_text: the history is serial")
-        if hallucination_silence_threshold is not None:
-            raise ValueError("parallel_clips cannot be combined with hallucination_silence_threshold")
-    thr = hallucination_silence_threshold
-    if thr is not None:
-        thr = float(thr)
-        if not math.isfinite(thr) or thr < 0:
-            raise ValueError("hallucination_silence_threshold: finite seconds >= 0")
-        if not words_on:
-            raise ValueError("hallucination_silence_threshold needs word_timestamps")
-    if prepend_punctuations is None:
-        prepend_punctuations = PREPEND_PUNCTUATIONS
-    if append_punctuations is None:
-        append_punctuations = APPEND_PUNCTUATIONS
+    o.early(R)
     ctx.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
     out = [dict(language=None, segments=[], seeks=[], windows=[]) for _ in range(R)]
     if R == 0:
         return out
-    if sample_rates is None:
-        d_mel, mel_offs, T = ctx.logmel_long(recordings, n_mels=n_mels, device=True)
-    else:
-        if len(sample_rates) != R:
-            raise ValueError("sample_rates: one per recording")
-        d_pcm, pcm_offs = ctx.resample_16k(recordings, sample_rates, device=True)
-        try:
-            d_mel, mel_offs, T = ctx.logmel_long_device(d_pcm, np.float32, pcm_offs, n_mels=n_mels)
-        finally:
-            ctx.dev_free(d_pcm)
-    wset = None   # reuse_encoder: the Windows of the round in progress
+    d_mel, mel_offs, T = _long_mel(o, R)
+    source = None   # the rows of the round in progress
     try:
-        content = [int(t) - N_FRAMES for t in T]
-        # 2. language
-        if language is None:
-            if lang_first is None or lang_last is None:
-                raise ValueError("language detection needs lang_first / lang_last")
-        if language is None and reuse_encoder:
-            with ctx.encode_windows(d_mel, mel_offs[:R], T, 0, N_FRAMES, mem=WM_MEM_DEVICE) as lid_set:
-                idx = np.concatenate([ctx.windows_detect_language(lid_set, np.arange(a, min(a + 128, R)), sot, lang_first,
-                                                                  lang_last)[0] for a in range(0, R, 128)])
-            langs = [int(lang_first + i) for i in idx]
-        elif language is None:
-            win = np.empty((R, n_mels, N_FRAMES), dtype=np.float32)
-            for r in range(R):
-                for c in range(n_mels):
-                    src = ctypes.c_void_p(d_mel.value + 4 * (int(mel_offs[r]) + c * int(T[r])))
-                    _check(ctx.lib, ctx.lib.wm_dev_download(ctx.handle, _ptr(win[r, c]), src, 4 * N_FRAMES))
-            idx, _ = ctx.detect_language_probs(ctx.encode_mel(win), sot, lang_first, lang_last)
-            langs = [int(lang_first + i) for i in idx]
-        elif np.ndim(language) == 0:
-            langs = [int(language)] * R
-        else:
-            langs = [int(x) for x in language]
-            if len(langs) != R:
-                raise ValueError("language: one token id per recording")
-        head = []
-        if initial_prompt_tokens is not None:
-            if sot_prev is None:
-                raise ValueError("initial_prompt_tokens need sot_prev")
-            if not per_rec:
-                head = [int(sot_prev)] + [int(t) for t in initial_prompt_tokens][-(n_ctx // 2 - 1):]
-        sot_index = len(head)
-        # per recording: the history of a conditioned run, or the fixed prompt tokens of its windows
-        if per_rec:
-            seeds = [[int(t) for t in x] for x in initial_prompt_tokens]
-        else:
-            seeds = [[int(t) for t in (initial_prompt_tokens if initial_prompt_tokens is not None else [])] for _ in range(R)]
-        all_tokens = [list(x) for x in seeds]
-        reset_since = [0] * R
-        ragged = cond or per_rec   # rows may differ in prompt length: wm_transcribe_mel_ragged, <|startoftranscript|> third from the end
-        carry = [bool(carry_initial_prompt) and cond and len(seeds[r]) > 0 for r in range(R)]
-        clips = [seek_clips(times[r], content[r]) for r in range(R)]
-        if vad_on:   # 13. the clips from the audio
-            ys = ctx.vad_energy(d_mel, mel_offs[:R], T, content, vad_kw.get("band") or vad_band(n_mels),
-                                vad_kw.get("smooth", VAD_SMOOTH), device=True)
-            for r in range(R):
-                out[r]["vad_segments"] = vad_segments(ys[r], vad_kw.get("params"))
-                out[r]["vad_clips"] = vad_clips(out[r]["vad_segments"], vad_kw.get("max_frames", N_FRAMES))
-                clips[r] = [(a, b, k) for k, (a, b) in enumerate(out[r]["vad_clips"])]
-        for r in range(R):
-            out[r]["language"] = langs[r]
-        # The loop below runs over UNITS.  Without parallel_clips a unit is a recording (rec is the identity, uout is out);
-        # with it (14.) a unit is a lane: one clip of recording rec[u], with its own state and its own result lists.
-        if par:
-            rec = [r for r in range(R) for _ in clips[r]]
-            clips = [[c] for cl in clips for c in cl]
-            uout = [dict(segments=[], seeks=[], windows=[]) for _ in rec]
-            last_speech = [c[0][0] * HOP_SECONDS for c in clips]
-        else:
-            rec = list(range(R))
-            uout = out
-            last_speech = [0.0] * R
-        R = len(rec)   # (from here on R counts the units)
-        if par:
-            mel_offs, T = mel_offs[rec], T[rec]
-        content, langs, seeds, carry, all_tokens, rec_ids = ([x[r] for r in rec] for x in
-                                                            (content, langs, seeds, carry, all_tokens, rec_ids))
-        reset_since = [0] * R
-        cur = [0] * R          # clip cursor
-        seek = [c[0][0] if c else 0 for c in clips]
-        before = [None] * R    # (clip cursor, seek) of the unit's previous window
+        langs = _long_languages(o, d_mel, mel_offs, T)
+        o.prompt_head()
+        units = _long_units(o, out, langs, d_mel, mel_offs, T)
         n_round = -1
         # 3. rounds in lockstep
         while True:
-            if wset is not None:   # the previous round's set
-                wset.close()
-                wset = None
-            for r in range(R):
-                while cur[r] < len(clips[r]) and seek[r] >= clips[r][cur[r]][1]:
-                    cur[r] += 1
-                    if cur[r] < len(clips[r]):
-                        seek[r] = clips[r][cur[r]][0]
-                if cur[r] < len(clips[r]):
-                    seek[r] = max(seek[r], clips[r][cur[r]][0])
-            live = [r for r in range(R) if cur[r] < len(clips[r])]
-            if par:
-                live = live[:par_n]
+            if source is not None:   # the previous round's (reuse_encoder: its set)
+                source.close()
+                source = None
+            live = [u for u in units if u.advance()][:o.par_n]
             if not live:
                 break
             n_round += 1
-            for r in live:
-                if before[r] is not None and before[r][0] == cur[r] and seek[r] <= before[r][1]:
-                    raise AssertionError("transcribe_long: recording %d stays at seek %d" % (r, seek[r]))
-                before[r] = (cur[r], seek[r])
-            size = [min(N_FRAMES, content[r] - seek[r], clips[r][cur[r]][1] - seek[r]) for r in live]
-            if par:   # (clip, window within the clip): a lane's noise is its own
-                ids = [((((clips[r][0][2] << 4) | min(len(uout[r]["windows"]), 15)) & 0xFFFF) << 16) | rec_ids[r] for r in live]
-            else:
-                ids = [((len(uout[r]["windows"]) & 0xFFFF) << 16) | rec_ids[r] for r in live]
-            if ragged:
-                plist = [carried_prompt(seeds[r], all_tokens[r], reset_since[r], [int(sot), langs[r], int(task)], sot_prev,
-                                        n_ctx) if carry[r] else
-                         conditioned_prompt(all_tokens[r], reset_since[r] if cond else 0, [int(sot), langs[r], int(task)],
-                                            sot_prev, n_ctx) for r in live]
-            else:
-                plist = [head + [int(sot), langs[r], int(task)] for r in live]
-                prompts = np.array(plist, dtype=np.int32)
-
-            if reuse_encoder:   # 9. the round's windows, encoded once for every fallback step and the word step
-                wset = ctx.encode_windows(d_mel, mel_offs[live], T[live], [seek[r] for r in live], size, mem=WM_MEM_DEVICE)
-
-            cand = {}   # best_of: row of the round -> candidate kept by its last step
-            hyp = {}    # beam_size: row of the round -> hypothesis kept by its last step
-
-            def decode(todo, t, sd):
-                rows = [live[i] for i in todo]
-                # (best_of None, or the temperature-0 step: exactly the call without candidates)
-                extra = dict(best_of=best_of, length_penalty=length_penalty) if best_of is not None and t > 0 else {}
-                beam = beam_size is not None and t == 0
-                if beam:
-                    extra = dict(beam_size=beam_size, patience=patience, length_penalty=length_penalty)
-                if wset is not None:   # rows of the round's set: the same call without the encoder pass
-                    r_ = ctx.transcribe_windows(wset, [int(i) for i in todo], [plist[i] for i in todo] if ragged else prompts[todo],
-                                                max_new, eot=eot, temperature=t, seed=sd, no_speech_token=no_speech_token,
-                                                sample_ids=[ids[i] for i in todo],
-                                                **(dict(sot_tail=3) if ragged else dict(sot_index=sot_index)), **extra)
-                elif ragged:
-                    r_ = ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
-                                            [size[i] for i in todo], [plist[i] for i in todo], max_new, eot=eot,
-                                            temperature=t, seed=sd, no_speech_token=no_speech_token, sot_tail=3,
-                                            sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE, **extra)
-                else:
-                    r_ = ctx.transcribe_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
-                                            [size[i] for i in todo], prompts[todo], max_new, eot=eot, temperature=t,
-                                            seed=sd, no_speech_token=no_speech_token, sot_index=sot_index,
-                                            sample_ids=[ids[i] for i in todo], mem=WM_MEM_DEVICE, **extra)
-                if best_of is not None:
-                    for k, i in enumerate(todo):
-                        cand[int(i)] = int(r_.candidate[k]) if extra and not beam else 0
-                if beam_size is not None:
-                    for k, i in enumerate(todo):
-                        hyp[int(i)] = int(r_.hypothesis[k]) if beam else 0
-                return r_
-            res = fallback_decode(decode, len(live), vocab_size, max_new, eot, temperatures, compression_ratio_threshold,
+            sizes = [u.open_window() for u in live]
+            prompts = [u.prompt(o) for u in live]
+            # (9. reuse_encoder: the round's windows are encoded once here, for every fallback step and the word step)
+            source = _RoundRows(o, d_mel, live, sizes, prompts, [u.sample_id() for u in live])
+            res = fallback_decode(source.decode, len(live), o.vocab_size, o.max_new, eot, temperatures, compression_ratio_threshold,
                                   logprob_threshold, no_speech_threshold, vocab, seed)
             kept = []   # word_timestamps: (row of the round, segments, next seek, single_timestamp_ending) of every kept window
-            for i, r in enumerate(live):
-                temps = [st[0] for st in res["steps"] if i in st[2]]
+            for i, u in enumerate(live):
                 n_text = n_text_tokens(res["tokens"][i, :res["lens"][i]], eot)
-                result = dict(temperature=float(res["temperature"][i]), avg_logprob=float(res["avg_logprob"][i]),
-                              compression_ratio=float(res["compression_ratio"][i]),
-                              no_speech_prob=float(res["no_speech_prob"][i]))
+                tokens = res["tokens"][i, :n_text]
+                result = {k: float(res[k][i]) for k in ("temperature", "avg_logprob", "compression_ratio", "no_speech_prob")}
                 skip = should_skip_window(result["no_speech_prob"], result["avg_logprob"], no_speech_threshold,
                                           logprob_threshold)
-                uout[r]["seeks"].append(seek[r])
-                uout[r]["windows"].append(dict(seek=seek[r], segment_size=size[i], temperatures=temps, skipped=skip,
-                                              tokens=[int(t) for t in res["tokens"][i, :n_text]],
-                                              prompt_len=len(plist[i]), prompt=[int(t) for t in plist[i]]))
-                if clips_on or vad_on or par:
-                    uout[r]["windows"][-1]["clip"] = clips[r][cur[r]][2]
-                if par:
-                    uout[r]["windows"][-1]["round"] = n_round
-                if best_of is not None:
-                    uout[r]["windows"][-1]["candidate"] = cand[i]
-                if beam_size is not None:
-                    uout[r]["windows"][-1]["hypothesis"] = hyp[i]
+                u.record_window(o, sizes[i], prompts[i], [st[0] for st in res["steps"] if i in st[2]], skip, tokens, n_round,
+                                source.kept_by[i])
                 if skip:
-                    seek[r] += size[i]
-                    continue
-                if words_on:
-                    kept.append((i,) + window_segments(res["tokens"][i, :n_text], seek[r], size[i], timestamp_begin, eot,
-                                                       result, vocab, cleanup=False))
-                    continue
-                segs, seek[r] = window_segments(res["tokens"][i, :n_text], seek[r], size[i], timestamp_begin, eot,
-                                                result, vocab)
-                if cond:
-                    all_tokens[r], reset_since[r] = conditioned_history(all_tokens[r], reset_since[r], segs,
-                                                                        result["temperature"], False,
-                                                                        prompt_reset_on_temperature)
-                for sg in segs:
-                    sg["id"] = len(uout[r]["segments"])
-                    uout[r]["segments"].append(sg)
-            if not kept:
-                continue
-            # 6. the word step of the round: one alignment call, then per recording the word rules and the word-driven seek
-            texts = [[t for sg in k[1] for t in sg["tokens"] if t < eot] for k in kept]
-            go = [n for n, k in enumerate(kept) if texts[n] and size[k[0]] >= 2]
-            if go:
-                rows = [live[kept[n][0]] for n in go]
-                if wset is not None:
-                    sf, pr = ctx.align_windows(wset, [kept[n][0] for n in go], [texts[n] for n in go],
-                                               [[int(sot), langs[r], int(task)] for r in rows], no_timestamps, eot,
-                                               medfilt_width=7, qk_scale=1.0)
+                    u.seek += sizes[i]
+                elif o.words_on:
+                    kept.append((i,) + window_segments(tokens, u.seek, sizes[i], timestamp_begin, eot, result, vocab,
+                                                       cleanup=False))
                 else:
-                    sf, pr = ctx.align_mel(d_mel, mel_offs[rows], T[rows], [seek[r] for r in rows],
-                                           [size[kept[n][0]] for n in go], [texts[n] for n in go],
-                                           [[int(sot), langs[r], int(task)] for r in rows], no_timestamps, eot,
-                                           medfilt_width=7, qk_scale=1.0, mem=WM_MEM_DEVICE)
-            for n, (i, segs, next_seek, single_ending) in enumerate(kept):
-                r = live[i]
-                if n in go:
-                    g = go.index(n)
-                    code = langs[r] - int(sot) - 1
-                    code = Whisper.LANGUAGES[code] if 0 <= code < len(Whisper.LANGUAGES) else None
-                    window_word_timestamps(vocab, segs, sf[g], pr[g], seek[r], eot, last_speech[r], code,
-                                           prepend_punctuations, append_punctuations)
-                else:
-                    for sg in segs:
-                        sg["words"] = []
-                if thr is None:
-                    ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
-                    if ends and not single_ending and ends[-1] > seek[r] * HOP_SECONDS:
-                        next_seek = int(round(ends[-1] * 100))
-                else:   # 11. (last_speech[r] is still the recording's value before this window)
-                    n_segs = len(segs)
-                    next_seek, segs, tag = hallucination_silence_skip(segs, seek[r], size[i], content[r], thr, single_ending,
-                                                                      last_speech[r], next_seek)
-                    if tag is not None:   # (the recording's one window of this round is its last record)
-                        uout[r]["windows"][-1]["hallucination"] = tag
-                    if tag == "surrounded":
-                        uout[r]["windows"][-1]["dropped_segments"] = n_segs - len(segs)
-                    if tag == "leading":
-                        seek[r] = next_seek
-                        continue
-                ends = [sg["words"][-1]["end"] for sg in segs if sg["words"]]
-                if ends:
-                    last_speech[r] = ends[-1]
-                clear_empty_segments(segs, eot, vocab, words=True)
-                seek[r] = next_seek
-                if cond:
-                    all_tokens[r], reset_since[r] = conditioned_history(all_tokens[r], reset_since[r], segs,
-                                                                        float(res["temperature"][i]), False,
-                                                                        prompt_reset_on_temperature)
-                for sg in segs:
-                    sg["id"] = len(uout[r]["segments"])
-                    uout[r]["segments"].append(sg)
-        if par:   # per recording: its lanes in clip order, each in decode order, ids renumbered
-            for u, r in enumerate(rec):
-                for sg in uout[u]["segments"]:
-                    sg["id"] = len(out[r]["segments"])
-                    out[r]["segments"].append(sg)
-                out[r]["seeks"] += uout[u]["seeks"]
-                out[r]["windows"] += uout[u]["windows"]
+                    u.commit(o, *window_segments(tokens, u.seek, sizes[i], timestamp_begin, eot, result, vocab),
+                             result["temperature"])
+            if kept:
+                _long_word_step(o, source, live, sizes, kept, res)
+        for u in units:
+            u.deliver(out[u.rec])
     finally:
-        if wset is not None:
-            wset.close()
+        if source is not None:
+            source.close()
         ctx.dev_free(d_mel)
     if vocab is not None:
-        for o in out:
-            o["text"] = vocab.decode([t for sg in o["segments"] for t in sg["tokens"] if t < eot])
+        for rec in out:
+            rec["text"] = vocab.decode([t for sg in rec["segments"] for t in sg["tokens"] if t < eot])
     return out
 
 
@@ -1631,21 +1684,22 @@ class Context:
                                         logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index,
                                         best_of=best_of, length_penalty=length_penalty, beam_size=beam_size, patience=patience)
 
-    def _mel_call_args(self, mel, mel_base, mel_len, seek, n_frames, prompts, opts, sample_ids, mem, prompt_len, sot_tail):
-        """The arrays of a wm_transcribe_mel* call (the conventions of transcribe_mel_raw): (mel kept alive, its pointer,
-        mel_base, mel_len, seek, n_frames, B, prompts [B][stride], prompt_len or None, opts, sample_ids or None)."""
+    def _mel_rows(self, mel, mel_base, mel_len, seek, n_frames, mem):
+        """(the arguments that name the B rows of a wm_*_mel* call, each keeping its array alive; B)"""
+        mel, mp, base, mlen, sk, nf, B = self._window_arrays(mel, mel_base, mel_len, seek, n_frames, mem)
+        return (mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf)), B
+
+    @staticmethod
+    def _window_arrays(mel, mel_base, mel_len, seek, n_frames, mem):
+        """The window description of transcribe_mel_raw as a call takes it: (mel kept alive, its pointer, mel_base i64 [B],
+        mel_len, seek, n_frames i32 broadcast to [B], B)."""
         base = np.ascontiguousarray(mel_base, dtype=np.int64)
         B = base.size
-        mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (B,)))
-        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (B,)))
-        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
-        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
+        mlen, sk, nf = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.int32), (B,)))
+                        for x in (mel_len, seek, n_frames))
         if mem == WM_MEM_HOST:
             mel = np.ascontiguousarray(mel, dtype=np.float32)
-            mp = _ptr(mel)
-        else:
-            mp = mel
-        return mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids
+        return mel, _ptr(mel) if mem == WM_MEM_HOST else mel, base, mlen, sk, nf, B
 
     @staticmethod
     def _prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail):
@@ -1683,24 +1737,19 @@ class Context:
         wm_transcribe_mel; there a sot_tail, when given, replaces opts.sot_index by n_prompt - sot_tail."""
         if budgets is not None:
             self.set_token_budgets(budgets)
-        mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids = self._mel_call_args(mel, mel_base, mel_len, seek, n_frames, prompts,
-                                                                                  opts, sample_ids, mem, prompt_len, sot_tail)
+        head, B = self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem)
+        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
         toks = np.empty((B, max_new), dtype=np.int32)
         lens = np.empty(B, dtype=np.int32)
         lp = np.empty((B, max_new), dtype=np.float32) if logprobs else None
         ns = np.empty(B, dtype=np.float32) if no_speech else None
+        rows = (self.handle, *head, B, _ptr(pr), pr.shape[1])
+        rest = (_ptr_or_null(ids), max_new, eot, ctypes.byref(opts) if opts is not None else None, _ptr(toks), _ptr(lens),
+                _ptr_or_null(lp), _ptr_or_null(ns), mem)
         if plen is not None:
-            _check(self.lib, self.lib.wm_transcribe_mel_ragged(
-                self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr), pr.shape[1], _ptr(plen),
-                1 if sot_tail is None else int(sot_tail), _ptr(ids) if ids is not None else None, max_new, eot,
-                ctypes.byref(opts) if opts is not None else None, _ptr(toks), _ptr(lens),
-                _ptr(lp) if lp is not None else None, _ptr(ns) if ns is not None else None, mem))
-            return toks, lens, lp, ns
-        _check(self.lib, self.lib.wm_transcribe_mel(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr),
-                                                    pr.shape[1], _ptr(ids) if ids is not None else None, max_new, eot,
-                                                    ctypes.byref(opts) if opts is not None else None, _ptr(toks),
-                                                    _ptr(lens), _ptr(lp) if lp is not None else None,
-                                                    _ptr(ns) if ns is not None else None, mem))
+            _check(self.lib, self.lib.wm_transcribe_mel_ragged(*rows, _ptr(plen), 1 if sot_tail is None else int(sot_tail), *rest))
+        else:
+            _check(self.lib, self.lib.wm_transcribe_mel(*rows, *rest))
         return toks, lens, lp, ns
 
     def transcribe_mel_best_of(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1, temperature=0.0,
@@ -1709,11 +1758,20 @@ class Context:
         """wm_transcribe_mel_best_of: transcribe_mel's arguments (uniform or ragged prompts as in transcribe_mel_raw) with
         best_of sampled candidates per row that share the row's encoder pass and cross-attention cache; length_penalty None
         is openai-whisper's None.  Returns a BestOfResult."""
+        return self._best_of_call(self.lib.wm_transcribe_mel_best_of,
+                                  lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new,
+                                  best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
+                                  sot_tail, length_penalty)
+
+    def _best_of_call(self, fn, rows, tail, prompts, max_new, best_of, eot, temperature, seed, no_speech_token, sot_index,
+                      sample_ids, budgets, prompt_len, sot_tail, length_penalty):
+        """wm_transcribe_mel_best_of / wm_transcribe_windows, which differ in the arguments that name the rows -- rows() gives
+        (them, B): _mel_rows, _window_rows -- and in the tail (mem)."""
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         if budgets is not None:
             self.set_token_budgets(budgets)
-        mel, mp, base, mlen, sk, nf, B, pr, plen, opts, ids = self._mel_call_args(mel, mel_base, mel_len, seek, n_frames, prompts,
-                                                                                  opts, sample_ids, mem, prompt_len, sot_tail)
+        head, B = rows()
+        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
         N = int(best_of)
         shape = (B, max(N, 1), max_new)
         toks = np.empty(shape, dtype=np.int32)
@@ -1721,12 +1779,10 @@ class Context:
         lp = np.empty(shape, dtype=np.float32)
         ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
         best = np.empty(B, dtype=np.int32)
-        _check(self.lib, self.lib.wm_transcribe_mel_best_of(
-            self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr), pr.shape[1],
-            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail),
-            _ptr(ids) if ids is not None else None, N, float("nan") if length_penalty is None else float(length_penalty),
-            max_new, eot, ctypes.byref(opts), _ptr(toks), _ptr(lens), _ptr(lp), _ptr(ns) if ns is not None else None,
-            _ptr(best), mem))
+        _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
+                            1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), N,
+                            float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts),
+                            _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(best), *tail))
         return BestOfResult(toks, lens, lp, ns, best, eot)
 
     def transcribe_mel_beam(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, beam_size, eot=-1, patience=None,
@@ -1736,6 +1792,13 @@ class Context:
         beam search with beam_size beams per row that share the row's encoder pass and cross-attention cache; max_candidates
         defaults to openai-whisper's round(beam_size * patience) (patience None = 1.0); length_penalty None is
         openai-whisper's None.  Returns a BeamResult."""
+        return self._beam_call(self.lib.wm_transcribe_mel_beam, lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem),
+                               (mem,), prompts, max_new, beam_size, eot, patience, no_speech_token, sot_index, budgets, prompt_len,
+                               sot_tail, length_penalty, max_candidates)
+
+    def _beam_call(self, fn, rows, tail, prompts, max_new, beam_size, eot, patience, no_speech_token, sot_index, budgets,
+                   prompt_len, sot_tail, length_penalty, max_candidates):
+        """wm_transcribe_mel_beam / wm_transcribe_windows_beam (rows, tail: as in _best_of_call)"""
         if max_candidates is None:
             max_candidates = beam_max_candidates(beam_size, patience)
         elif patience is not None:
@@ -1743,117 +1806,7 @@ class Context:
         opts = wm_decode_opts(0.0, 0, int(no_speech_token), int(sot_index))
         if budgets is not None:
             self.set_token_budgets(budgets)
-        mel, mp, base, mlen, sk, nf, B, pr, plen, opts, _ = self._mel_call_args(mel, mel_base, mel_len, seek, n_frames, prompts,
-                                                                                opts, None, mem, prompt_len, sot_tail)
-        N, C = int(beam_size), int(max_candidates)
-        shape = (B, max(N, C, 1), max_new)
-        toks = np.empty(shape, dtype=np.int32)
-        lens = np.empty(shape[:2], dtype=np.int32)
-        n_hyp = np.empty(B, dtype=np.int32)
-        sums = np.empty(shape[:2], dtype=np.float32)
-        lp = np.empty(shape, dtype=np.float32)
-        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
-        best = np.empty(B, dtype=np.int32)
-        _check(self.lib, self.lib.wm_transcribe_mel_beam(
-            self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(pr), pr.shape[1],
-            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail), N, C,
-            float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts), _ptr(toks),
-            _ptr(lens), _ptr(n_hyp), _ptr(sums), _ptr(lp), _ptr(ns) if ns is not None else None, _ptr(best), mem))
-        return BeamResult(toks, lens, n_hyp, sums, lp, ns, best, eot)
-
-    def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
-                       no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                       sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None):
-        """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
-        Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw.
-        best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`).
-        beam_size (None: no beam search; with patience): transcribe_mel_beam at temperature 0 -- sample_ids and the seed play
-        no part -- and the result is its `selected` (with `hypothesis`)."""
-        if beam_size is not None or patience is not None:
-            if best_of is not None:
-                raise ValueError("beam_size and best_of exclude each other (openai-whisper)")
-            if temperature != 0:
-                raise ValueError("beam search decodes at temperature 0")
-            beam_max_candidates(beam_size, patience)
-            return self.transcribe_mel_beam(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, beam_size, eot=eot,
-                                            patience=patience, no_speech_token=no_speech_token, sot_index=sot_index, mem=mem,
-                                            budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail,
-                                            length_penalty=length_penalty).selected
-        if best_of is not None:
-            return self.transcribe_mel_best_of(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=eot,
-                                               temperature=temperature, seed=seed, no_speech_token=no_speech_token,
-                                               sot_index=sot_index, sample_ids=sample_ids, mem=mem, budgets=budgets,
-                                               prompt_len=prompt_len, sot_tail=sot_tail, length_penalty=length_penalty).selected
-        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
-        toks, lens, lp, ns = self.transcribe_mel_raw(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot, opts,
-                                                     sample_ids, logprobs=True, no_speech=no_speech_token >= 0, mem=mem,
-                                                     budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail)
-        return TranscribeResult(toks, lens, lp, ns, eot)
-
-    # ---- window sets ----------------------------------------------------------------
-    def encode_windows(self, mel, mel_base, mel_len, seek, n_frames, mem=WM_MEM_HOST):
-        """wm_windows_encode: run the encoder and the cross-K/V projection of the windows ONCE (the window description of
-        transcribe_mel_raw) and keep the result on the device.  Returns a Windows; close it before this context."""
-        base = np.ascontiguousarray(mel_base, dtype=np.int64)
-        W = base.size
-        mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (W,)))
-        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (W,)))
-        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (W,)))
-        if mem == WM_MEM_HOST:
-            mel = np.ascontiguousarray(mel, dtype=np.float32)
-            mp = _ptr(mel)
-        else:
-            mp = mel
-        h = ctypes.c_void_p()
-        _check(self.lib, self.lib.wm_windows_encode(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), W, mem,
-                                                    ctypes.byref(h)))
-        return Windows(self, h, nf.copy())
-
-    @staticmethod
-    def _window_rows(windows, rows):
-        """(rows i32 array or None, B) of a call that reads a set"""
-        if rows is None:
-            return None, len(windows)
-        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
-        return r, int(r.size)
-
-    def transcribe_windows_best_of(self, windows, rows, prompts, max_new, best_of=1, eot=-1, temperature=0.0, seed=0,
-                                   no_speech_token=-1, sot_index=0, sample_ids=None, budgets=None, prompt_len=None,
-                                   sot_tail=None, length_penalty=None):
-        """wm_transcribe_windows: transcribe_mel_best_of with rows of a Windows set (rows None: all of them, in order) in
-        place of the mel windows.  Same bits.  Returns a BestOfResult."""
-        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
-        if budgets is not None:
-            self.set_token_budgets(budgets)
-        r, B = self._window_rows(windows, rows)
-        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
-        N = int(best_of)
-        shape = (B, max(N, 1), max_new)
-        toks = np.empty(shape, dtype=np.int32)
-        lens = np.empty(shape[:2], dtype=np.int32)
-        lp = np.empty(shape, dtype=np.float32)
-        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
-        best = np.empty(B, dtype=np.int32)
-        _check(self.lib, self.lib.wm_transcribe_windows(
-            self.handle, windows.handle, _ptr(r) if r is not None else None, B, _ptr(pr), pr.shape[1],
-            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail),
-            _ptr(ids) if ids is not None else None, N, float("nan") if length_penalty is None else float(length_penalty),
-            max_new, eot, ctypes.byref(opts), _ptr(toks), _ptr(lens), _ptr(lp), _ptr(ns) if ns is not None else None,
-            _ptr(best)))
-        return BestOfResult(toks, lens, lp, ns, best, eot)
-
-    def transcribe_windows_beam(self, windows, rows, prompts, max_new, beam_size, eot=-1, patience=None, no_speech_token=-1,
-                                sot_index=0, budgets=None, prompt_len=None, sot_tail=None, length_penalty=None,
-                                max_candidates=None):
-        """wm_transcribe_windows_beam: transcribe_mel_beam with rows of a Windows set.  Same bits.  Returns a BeamResult."""
-        if max_candidates is None:
-            max_candidates = beam_max_candidates(beam_size, patience)
-        elif patience is not None:
-            raise ValueError("give patience or max_candidates, not both")
-        opts = wm_decode_opts(0.0, 0, int(no_speech_token), int(sot_index))
-        if budgets is not None:
-            self.set_token_budgets(budgets)
-        r, B = self._window_rows(windows, rows)
+        head, B = rows()
         pr, plen, opts, _ = self._prompt_call_args(B, prompts, opts, None, prompt_len, sot_tail)
         N, C = int(beam_size), int(max_candidates)
         shape = (B, max(N, C, 1), max_new)
@@ -1864,69 +1817,119 @@ class Context:
         lp = np.empty(shape, dtype=np.float32)
         ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
         best = np.empty(B, dtype=np.int32)
-        _check(self.lib, self.lib.wm_transcribe_windows_beam(
-            self.handle, windows.handle, _ptr(r) if r is not None else None, B, _ptr(pr), pr.shape[1],
-            _ptr(plen) if plen is not None else None, 1 if sot_tail is None else int(sot_tail), N, C,
-            float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts), _ptr(toks),
-            _ptr(lens), _ptr(n_hyp), _ptr(sums), _ptr(lp), _ptr(ns) if ns is not None else None, _ptr(best)))
+        _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
+                            1 if sot_tail is None else int(sot_tail), N, C,
+                            float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts),
+                            _ptr(toks), _ptr(lens), _ptr(n_hyp), _ptr(sums), _ptr(lp), _ptr_or_null(ns), _ptr(best), *tail))
         return BeamResult(toks, lens, n_hyp, sums, lp, ns, best, eot)
 
-    def transcribe_windows(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
-                           sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, best_of=None,
-                           length_penalty=None, beam_size=None, patience=None):
-        """transcribe_mel with rows of a Windows set in place of the mel windows: the same bits, no encoder pass.  Returns a
-        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel)."""
+    def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
+                       no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
+                       sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None):
+        """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
+        Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw.
+        best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`).
+        beam_size (None: no beam search; with patience): transcribe_mel_beam at temperature 0 -- sample_ids and the seed play
+        no part -- and the result is its `selected` (with `hypothesis`)."""
+        win = (mel, mel_base, mel_len, seek, n_frames, prompts, max_new)
+        common = dict(mem=mem, budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail)
+        entry = dict(common, eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, length_penalty=length_penalty)
+        return self._decode_entry(
+            lambda: self.transcribe_mel_beam(*win, beam_size, patience=patience, **entry),
+            lambda: self.transcribe_mel_best_of(*win, best_of, temperature=temperature, seed=seed, sample_ids=sample_ids, **entry),
+            lambda: TranscribeResult(*self.transcribe_mel_raw(
+                *win, eot, wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index)),
+                sample_ids, logprobs=True, no_speech=no_speech_token >= 0, **common), eot),
+            temperature, best_of, beam_size, patience)
+
+    @staticmethod
+    def _decode_entry(beam, candidates, plain, temperature, best_of, beam_size, patience):
+        """transcribe_mel's / transcribe_windows' choice of entry, each a callable; beam search and best-of give `selected`"""
         if beam_size is not None or patience is not None:
             if best_of is not None:
                 raise ValueError("beam_size and best_of exclude each other (openai-whisper)")
             if temperature != 0:
                 raise ValueError("beam search decodes at temperature 0")
             beam_max_candidates(beam_size, patience)
-            return self.transcribe_windows_beam(windows, rows, prompts, max_new, beam_size, eot=eot, patience=patience,
-                                                no_speech_token=no_speech_token, sot_index=sot_index, budgets=budgets,
-                                                prompt_len=prompt_len, sot_tail=sot_tail, length_penalty=length_penalty).selected
-        r = self.transcribe_windows_best_of(windows, rows, prompts, max_new, 1 if best_of is None else best_of, eot=eot,
-                                            temperature=temperature, seed=seed, no_speech_token=no_speech_token,
-                                            sot_index=sot_index, sample_ids=sample_ids, budgets=budgets, prompt_len=prompt_len,
-                                            sot_tail=sot_tail, length_penalty=length_penalty)
+            return beam().selected
         if best_of is not None:
-            return r.selected
-        return TranscribeResult(np.ascontiguousarray(r.tokens[:, 0]), np.ascontiguousarray(r.lens[:, 0]),
-                                np.ascontiguousarray(r.logprobs[:, 0]), r.no_speech_prob, eot)
+            return candidates().selected
+        return plain()
+
+    # ---- window sets ----------------------------------------------------------------
+    def encode_windows(self, mel, mel_base, mel_len, seek, n_frames, mem=WM_MEM_HOST):
+        """wm_windows_encode: run the encoder and the cross-K/V projection of the windows ONCE (the window description of
+        transcribe_mel_raw) and keep the result on the device.  Returns a Windows; close it before this context."""
+        mel, mp, base, mlen, sk, nf, W = self._window_arrays(mel, mel_base, mel_len, seek, n_frames, mem)
+        h = ctypes.c_void_p()
+        _check(self.lib, self.lib.wm_windows_encode(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), W, mem,
+                                                    ctypes.byref(h)))
+        return Windows(self, h, nf.copy())
+
+    @staticmethod
+    def _window_rows(windows, rows):
+        """(the arguments that name the B rows of a call that reads a set -- the set, rows i32 [B] or NULL: all --, B)"""
+        if rows is None:
+            return (windows.handle, None), len(windows)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        return (windows.handle, _ptr(r)), int(r.size)
+
+    def transcribe_windows_best_of(self, windows, rows, prompts, max_new, best_of=1, eot=-1, temperature=0.0, seed=0,
+                                   no_speech_token=-1, sot_index=0, sample_ids=None, budgets=None, prompt_len=None,
+                                   sot_tail=None, length_penalty=None):
+        """wm_transcribe_windows: transcribe_mel_best_of with rows of a Windows set (rows None: all of them, in order) in
+        place of the mel windows.  Same bits.  Returns a BestOfResult."""
+        return self._best_of_call(self.lib.wm_transcribe_windows, lambda: self._window_rows(windows, rows), (), prompts, max_new,
+                                  best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
+                                  sot_tail, length_penalty)
+
+    def transcribe_windows_beam(self, windows, rows, prompts, max_new, beam_size, eot=-1, patience=None, no_speech_token=-1,
+                                sot_index=0, budgets=None, prompt_len=None, sot_tail=None, length_penalty=None,
+                                max_candidates=None):
+        """wm_transcribe_windows_beam: transcribe_mel_beam with rows of a Windows set.  Same bits.  Returns a BeamResult."""
+        return self._beam_call(self.lib.wm_transcribe_windows_beam, lambda: self._window_rows(windows, rows), (), prompts, max_new,
+                               beam_size, eot, patience, no_speech_token, sot_index, budgets, prompt_len, sot_tail, length_penalty,
+                               max_candidates)
+
+    def transcribe_windows(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
+                           sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, best_of=None,
+                           length_penalty=None, beam_size=None, patience=None):
+        """transcribe_mel with rows of a Windows set in place of the mel windows: the same bits, no encoder pass.  Returns a
+        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel)."""
+        common = dict(eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, budgets=budgets, prompt_len=prompt_len,
+                      sot_tail=sot_tail, length_penalty=length_penalty)
+
+        def candidates(n):
+            return self.transcribe_windows_best_of(windows, rows, prompts, max_new, n, temperature=temperature, seed=seed,
+                                                   sample_ids=sample_ids, **common)
+
+        def plain():   # (the set has no entry of its own for one sample: candidate 0 of N = 1)
+            r = candidates(1)
+            return TranscribeResult(np.ascontiguousarray(r.tokens[:, 0]), np.ascontiguousarray(r.lens[:, 0]),
+                                    np.ascontiguousarray(r.logprobs[:, 0]), r.no_speech_prob, eot)
+        return self._decode_entry(
+            lambda: self.transcribe_windows_beam(windows, rows, prompts, max_new, beam_size, patience=patience, **common),
+            lambda: candidates(best_of), plain, temperature, best_of, beam_size, patience)
 
     def align_windows(self, windows, rows, text_tokens, sot_seqs, no_timestamps, eot, medfilt_width=7, qk_scale=1.0):
         """wm_align_windows: align_mel with rows of a Windows set (each of at least 2 frames); the alignment covers the set's
         own n_frames of a row.  Returns (start_frames, token_probs) as align."""
-        r, B = self._window_rows(windows, rows)
-        toks = [list(np.asarray(t).reshape(-1)) for t in text_tokens]
-        if len(toks) != B:
-            raise ValueError("text_tokens: %d lists for %d windows" % (len(toks), B))
-        max_text = max([len(t) for t in toks] + [0])
-        tt = np.zeros((B, max(max_text, 1)), dtype=np.int32)
-        for b, t in enumerate(toks):
-            tt[b, :len(t)] = t
-        nt = np.ascontiguousarray([len(t) for t in toks], dtype=np.int32)
-        sot = np.asarray(sot_seqs, dtype=np.int32)
-        if sot.ndim == 1:
-            sot = np.broadcast_to(sot, (B, sot.size))
-        if sot.ndim != 2 or sot.shape[0] != B:
-            raise ValueError("sot_seqs: one start sequence, or one per window")
-        sot = np.ascontiguousarray(sot)
-        start = np.empty((B, max_text + 1), dtype=np.int32)
-        probs = np.empty((B, max_text), dtype=np.float32)
-        _check(self.lib, self.lib.wm_align_windows(self.handle, windows.handle, _ptr(r) if r is not None else None, B, _ptr(sot),
-                                                   sot.shape[1], int(no_timestamps), int(eot), _ptr(tt), _ptr(nt), max_text,
-                                                   int(medfilt_width), float(qk_scale), _ptr(start), _ptr(probs)))
+        head, B = self._window_rows(windows, rows)
+        tt, nt, max_text, start, probs = self._text_table(text_tokens, B, "windows")
+        sot = self._sot_table(sot_seqs, B)
+        _check(self.lib, self.lib.wm_align_windows(self.handle, *head, B, _ptr(sot), sot.shape[1], int(no_timestamps), int(eot),
+                                                   _ptr(tt), _ptr(nt), max_text, int(medfilt_width), float(qk_scale),
+                                                   _ptr(start), _ptr(probs)))
         return start, probs
 
     def windows_detect_language(self, windows, rows=None, sot=50258, lang_first=50259, lang_last=50357):
         """wm_windows_detect_language: detect_language_probs of encode_mel of the rows' zero-padded windows, from the set.
         Returns (lang_idx [B], probs [B][n_lang])."""
-        r, B = self._window_rows(windows, rows)
+        head, B = self._window_rows(windows, rows)
         idx = np.empty(B, dtype=np.int32)
         probs = np.empty((B, lang_last - lang_first + 1), dtype=np.float32)
-        _check(self.lib, self.lib.wm_windows_detect_language(self.handle, windows.handle, _ptr(r) if r is not None else None, B,
-                                                             sot, lang_first, lang_last, _ptr(idx), _ptr(probs)))
+        _check(self.lib, self.lib.wm_windows_detect_language(self.handle, *head, B, sot, lang_first, lang_last, _ptr(idx),
+                                                             _ptr(probs)))
         return idx, probs
 
     def transcribe_long(self, recordings, **kw):
@@ -1942,6 +1945,40 @@ class Context:
         _check(self.lib, self.lib.wm_set_alignment_heads(self.handle, _ptr(ls) if ls.size else None,
                                                          _ptr(hs) if hs.size else None, len(pairs)))
 
+    @staticmethod
+    def _text_table(text_tokens, B, rows_are):
+        """The text tokens of an alignment call over B rows and the outputs they size: (tt i32 [B][max(max_text, 1)] zero
+        padded, n_text i32 [B], max_text, start_frames i32 [B][max_text + 1], token_probs f32 [B][max_text])."""
+        rows = [list(np.asarray(t).reshape(-1)) for t in text_tokens]
+        if len(rows) != B:
+            raise ValueError("text_tokens: %d lists for %d %s" % (len(rows), B, rows_are))
+        max_text = max([len(r) for r in rows] + [0])
+        tt = np.zeros((B, max(max_text, 1)), dtype=np.int32)
+        for b, r in enumerate(rows):
+            tt[b, :len(r)] = r
+        nt = np.ascontiguousarray([len(r) for r in rows], dtype=np.int32)
+        return tt, nt, max_text, np.empty((B, max_text + 1), dtype=np.int32), np.empty((B, max_text), dtype=np.float32)
+
+    @staticmethod
+    def _sot_table(sot_seqs, B):
+        """one start sequence for every row, or B of one length: i32 [B][n]"""
+        sot = np.asarray(sot_seqs, dtype=np.int32)
+        if sot.ndim == 1:
+            sot = np.broadcast_to(sot, (B, sot.size))
+        if sot.ndim != 2 or sot.shape[0] != B:
+            raise ValueError("sot_seqs: one start sequence, or one per window")
+        return np.ascontiguousarray(sot)
+
+    def _capture_matrix(self, B, max_text):
+        """Debug library only: the buffer f32 [B][max_text + 1][1500] the NEXT alignment call writes its cost matrix to"""
+        if not hasattr(self.lib, "wmdbg_align_capture"):
+            raise WhisperError(-1, "capture_matrix needs the debug library: Context(dims, debug=True)")
+        matrix = np.empty((B, max_text + 1, 1500), dtype=np.float32)
+        self.lib.wmdbg_align_capture.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self.lib.wmdbg_align_capture.restype = ctypes.c_int
+        _check(self.lib, self.lib.wmdbg_align_capture(self.handle, _ptr(matrix)))
+        return matrix
+
     def align(self, pcm, text_tokens, sot_seq, no_timestamps, eot, n_frames=None, medfilt_width=7, qk_scale=1.0,
               capture_matrix=False):
         """wm_align: word-level timing inputs of every chunk.  pcm [B][480000]; text_tokens: a list of B token lists (or an
@@ -1949,29 +1986,13 @@ class Context:
         chunk's tokens; capture_matrix=True (debug library) also returns the cost matrix f32 [B][max_text + 1][1500]."""
         pcm = np.ascontiguousarray(pcm)
         B = pcm.shape[0]
-        rows = [list(np.asarray(t).reshape(-1)) for t in text_tokens]
-        if len(rows) != B:
-            raise ValueError("text_tokens: %d lists for %d chunks" % (len(rows), B))
-        max_text = max([len(r) for r in rows] + [0])
-        tt = np.zeros((B, max(max_text, 1)), dtype=np.int32)
-        for b, r in enumerate(rows):
-            tt[b, :len(r)] = r
-        nt = np.ascontiguousarray([len(r) for r in rows], dtype=np.int32)
+        tt, nt, max_text, start, probs = self._text_table(text_tokens, B, "chunks")
         sot = np.ascontiguousarray(sot_seq, dtype=np.int32)
         nf = None if n_frames is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
-        start = np.empty((B, max_text + 1), dtype=np.int32)
-        probs = np.empty((B, max_text), dtype=np.float32)
-        matrix = None
-        if capture_matrix:
-            if not hasattr(self.lib, "wmdbg_align_capture"):
-                raise WhisperError(-1, "capture_matrix needs the debug library: Context(dims, debug=True)")
-            matrix = np.empty((B, max_text + 1, 1500), dtype=np.float32)
-            self.lib.wmdbg_align_capture.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-            self.lib.wmdbg_align_capture.restype = ctypes.c_int
-            _check(self.lib, self.lib.wmdbg_align_capture(self.handle, _ptr(matrix)))
+        matrix = self._capture_matrix(B, max_text) if capture_matrix else None
         _check(self.lib, self.lib.wm_align(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], B, _ptr(sot), len(sot),
                                            int(no_timestamps), int(eot), _ptr(tt), _ptr(nt), max_text,
-                                           _ptr(nf) if nf is not None else None, int(medfilt_width), float(qk_scale),
+                                           _ptr_or_null(nf), int(medfilt_width), float(qk_scale),
                                            _ptr(start), _ptr(probs), WM_MEM_HOST))
         return (start, probs, matrix) if capture_matrix else (start, probs)
 
@@ -1980,40 +2001,10 @@ class Context:
         """wm_align_mel: Context.align on mel windows.  mel, mel_base, mel_len, seek, n_frames, mem: the window description
         of transcribe_mel_raw (n_frames 2 .. 3000: also the audio frames the alignment covers); sot_seqs: one start
         sequence for every row, or B of one length (one per row).  Returns what align returns."""
-        base = np.ascontiguousarray(mel_base, dtype=np.int64)
-        B = base.size
-        mlen = np.ascontiguousarray(np.broadcast_to(np.asarray(mel_len, dtype=np.int32), (B,)))
-        sk = np.ascontiguousarray(np.broadcast_to(np.asarray(seek, dtype=np.int32), (B,)))
-        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
-        rows = [list(np.asarray(t).reshape(-1)) for t in text_tokens]
-        if len(rows) != B:
-            raise ValueError("text_tokens: %d lists for %d windows" % (len(rows), B))
-        max_text = max([len(r) for r in rows] + [0])
-        tt = np.zeros((B, max(max_text, 1)), dtype=np.int32)
-        for b, r in enumerate(rows):
-            tt[b, :len(r)] = r
-        nt = np.ascontiguousarray([len(r) for r in rows], dtype=np.int32)
-        sot = np.asarray(sot_seqs, dtype=np.int32)
-        if sot.ndim == 1:
-            sot = np.broadcast_to(sot, (B, sot.size))
-        if sot.ndim != 2 or sot.shape[0] != B:
-            raise ValueError("sot_seqs: one start sequence, or one per window")
-        sot = np.ascontiguousarray(sot)
-        if mem == WM_MEM_HOST:
-            mel = np.ascontiguousarray(mel, dtype=np.float32)
-            mp = _ptr(mel)
-        else:
-            mp = mel
-        start = np.empty((B, max_text + 1), dtype=np.int32)
-        probs = np.empty((B, max_text), dtype=np.float32)
-        matrix = None
-        if capture_matrix:
-            if not hasattr(self.lib, "wmdbg_align_capture"):
-                raise WhisperError(-1, "capture_matrix needs the debug library: Context(dims, debug=True)")
-            matrix = np.empty((B, max_text + 1, 1500), dtype=np.float32)
-            self.lib.wmdbg_align_capture.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-            self.lib.wmdbg_align_capture.restype = ctypes.c_int
-            _check(self.lib, self.lib.wmdbg_align_capture(self.handle, _ptr(matrix)))
+        mel, mp, base, mlen, sk, nf, B = self._window_arrays(mel, mel_base, mel_len, seek, n_frames, mem)
+        tt, nt, max_text, start, probs = self._text_table(text_tokens, B, "windows")
+        sot = self._sot_table(sot_seqs, B)
+        matrix = self._capture_matrix(B, max_text) if capture_matrix else None
         _check(self.lib, self.lib.wm_align_mel(self.handle, mp, _ptr(base), _ptr(mlen), _ptr(sk), _ptr(nf), B, _ptr(sot),
                                                sot.shape[1], int(no_timestamps), int(eot), _ptr(tt), _ptr(nt), max_text,
                                                int(medfilt_width), float(qk_scale), _ptr(start), _ptr(probs), mem))
