@@ -482,6 +482,30 @@ WM_API int wm_set_suppress(wm_ctx *ctx, const int32_t *suppress, int n, const in
 WM_API int wm_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t timestamp_begin, int32_t eot,
                            int32_t max_initial_timestamp_index);
 
+/* The repetition rules: repetition_penalty and no_repeat_ngram_size of faster-whisper / CTranslate2 and Hugging Face generate,
+ * the remedy for Whisper's repetition loop that needs no second decode.  Both are logit processors over a row's own
+ * GENERATED history g[0 .. k) -- the tokens the row has generated in this call, prompt excluded (Hugging Face counts the
+ * prompt; here a previous-text prompt would otherwise penalise exactly the words most likely to continue; in a ragged call
+ * every row's history starts after its own prompt just the same).  Only ids < eot are ever penalised or banned: timestamps,
+ * <|endoftext|> and the specials are left to the timestamp rules and the suppress lists, but ids >= eot still stand in the
+ * history and take part in n-gram matching as themselves.
+ *   repetition_penalty p (finite, > 0; 1.0 = off): every eligible id t that occurs in g -- once, however often it occurs --
+ *     has its logit replaced by v > 0 ? v * inv_p : v * p with inv_p = (float)(1.0 / (double)p): one f32 multiply either way.
+ *     (HF / CT2 divide a positive logit by p: the results differ by at most one ulp.)
+ *   no_repeat_ngram_size n (0 = off, else 1 .. 32): eligible id t is banned at this position iff there is an i in [0, k - n]
+ *     with g[i .. i + n - 1) == g[k - n + 1 .. k) and g[i + n - 1] == t.  Nothing is banned while k < n - 1; n = 1 bans every
+ *     eligible id that was already generated.
+ * The penalised value replaces the logit before everything the decode does with it (arg-max, the sampling score
+ * v / T + Gumbel noise, the log-prob normalisers, the timestamp sum rule, beam lists); a banned id is treated exactly like a
+ * suppressed one.  no_speech_prob is read at <|startoftranscript|>, where the history is empty: untouched.  If the bans leave
+ * no admissible text token the existing paths apply (a forced timestamp, the fallback token, log-prob -inf).
+ * Applies to every transcribe entry (wm_transcribe_greedy, wm_transcribe, _mel, _ragged, _best_of, _beam, wm_transcribe_windows*);
+ * wm_decode_logits, wm_detect_language* and wm_align* are teacher-forced and stay raw.  With the rules set a call runs the
+ * extended decode (the one behind log-probs and sampling), which at temperature 0 produces wm_transcribe_greedy's tokens bit
+ * for bit.  (1.0, 0, any valid eot) switches the rules off.  WM_ERR_INVALID: p not finite or <= 0, n outside [0, 32], eot
+ * outside [0, n_vocab].  Same inheritance as wm_set_suppress. */
+WM_API int wm_set_repetition_rules(wm_ctx *ctx, float repetition_penalty, int no_repeat_ngram_size, int32_t eot);
+
 /* Per-chunk token budgets for the NEXT wm_transcribe_greedy call on this context (consumed by it; n must equal that
  * call's B): chunk i generates at most budgets[i] tokens (clamped to max_new), lens_out[i] <=
  * budgets[i].  A chunk that has reached its budget -- like one that has emitted `eot` -- LEAVES the decode: its caches are

@@ -109,6 +109,15 @@ typedef struct wmdbg_step {
     int32_t stats_tail_nonzero;   /* words of parts 1 .. K/16 - 1 of the B rows that are not +0.0 */
 } wmdbg_step;
 WM_API int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io);
+/* wmdbg_decode_close with the repetition rules on (wm_set_repetition_rules: penalty, ngram, and io->eot as the rules' eot, in
+ * [0, V] whatever ts_mode is): wm_repeat_state on the token history in front of a DE_LOGITS_XR launch.  Needs x_on and
+ * n_prompt <= n_ctx.  The bitmaps are pre-filled with 0xff bytes.  (1.0, 0) runs the same kernels with empty rules. */
+WM_API int wmdbg_decode_close_rep(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram);
+/* The state kernel of the repetition rules alone (repeat.hip): seq i32 [n_ctx][B] (host, position-major; any values), the
+ * history of row b = seq[n_prompt .. pos][b].  Out: seen / ban u32 [B][words], words = (pad16(V) + 31) / 32, bit (t & 31) of
+ * word t >> 5; both pre-filled with 0xff bytes on the device, so a word the kernel does not write shows. */
+WM_API int wmdbg_repeat_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V, int ngram,
+                              int32_t eot, uint32_t *seen_out, uint32_t *ban_out);
 /* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_step) and the offsets of seed, logits and
  * stats_tail_nonzero (host only). */
 WM_API int wmdbg_step_layout(int32_t *out4);

@@ -1119,7 +1119,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     prompt_reset_on_temperature=0.5, word_timestamps=False, no_timestamps=None,
                     prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
-                    hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None):
+                    hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
+                    repetition_penalty=None, no_repeat_ngram_size=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1211,6 +1212,11 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        the segments and windows come in (clip, decode order), ids renumbered; every window record carries `clip` and
        `round`.  ValueError with condition_on_previous_text (history is serial) and with
        hallucination_silence_threshold.  reuse_encoder encodes the round's lanes as one set: N bounds its memory.
+    15. repetition_penalty / no_repeat_ngram_size (None, None: off): the repetition rules of Context.set_repetition_rules
+       (wm_set_repetition_rules; a None of the two is 1.0 / 0, eot is this call's eot) are set on the context behind the
+       log-mel, hold for every decode call of the run -- greedy, sampled, best-of, beam, from windows --, and are cleared
+       again when the function leaves, also on an exception.  They act on a row's generated tokens only, so the prompts of
+       5 and 12 are never penalised.  With both None the function makes exactly the calls it made before they existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1229,7 +1235,11 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         return out
     d_mel, mel_offs, T = _long_mel(o, R)
     source = None   # the rows of the round in progress
+    rules = repetition_penalty is not None or no_repeat_ngram_size is not None
     try:
+        if rules:   # 15.
+            ctx.set_repetition_rules(1.0 if repetition_penalty is None else repetition_penalty,
+                                     0 if no_repeat_ngram_size is None else no_repeat_ngram_size, eot)
         langs = _long_languages(o, d_mel, mel_offs, T)
         o.prompt_head()
         units = _long_units(o, out, langs, d_mel, mel_offs, T)
@@ -1271,9 +1281,13 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         for u in units:
             u.deliver(out[u.rec])
     finally:
-        if source is not None:
-            source.close()
-        ctx.dev_free(d_mel)
+        try:
+            if source is not None:
+                source.close()
+            ctx.dev_free(d_mel)
+        finally:
+            if rules:
+                ctx.set_repetition_rules(1.0, 0, eot)
     if vocab is not None:
         for rec in out:
             rec["text"] = vocab.decode([t for sg in rec["segments"] for t in sg["tokens"] if t < eot])
@@ -1617,6 +1631,15 @@ class Context:
         self.lib.wm_set_timestamp_rules.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
                                                     ctypes.c_int32]
         _check(self.lib, self.lib.wm_set_timestamp_rules(self.handle, 1 if enable else 0, timestamp_begin, eot, max_initial))
+
+    def set_repetition_rules(self, penalty=1.0, no_repeat_ngram_size=0, eot=0):
+        """The repetition rules of every transcribe call on this context (wm_set_repetition_rules): `penalty` (> 0, 1.0 = off)
+        scales the logit of every id < eot the row has generated in the call (v > 0 ? v * (1 / penalty) : v * penalty, once
+        per id); `no_repeat_ngram_size` n (0 = off, 1 .. 32) bans the ids < eot that would repeat an n-gram of the row's
+        generated tokens.  The prompt never counts.  The defaults switch the rules off."""
+        self.lib.wm_set_repetition_rules.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_int32]
+        self.lib.wm_set_repetition_rules.restype = ctypes.c_int
+        _check(self.lib, self.lib.wm_set_repetition_rules(self.handle, float(penalty), int(no_repeat_ngram_size), int(eot)))
 
     def set_lanes(self, n):
         """Decode groups one transcribe_greedy call keeps in flight (0: default = $WM_LANES or 3; 1: one group per call)."""

@@ -20,7 +20,8 @@ namespace {
 __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict__ logits, long ldo, int V, int n_tiles,
                                                          const unsigned long long *__restrict__ tilemax, WmTsDev ts, WmXDev xd,
                                                          const unsigned *__restrict__ mask, int mask_words, int n_prompt,
-                                                         const int *__restrict__ pos_ptr, WmBeamDev bm) {
+                                                         const int *__restrict__ pos_ptr, WmBeamDev bm,
+                                                         const unsigned *__restrict__ ban, int ban_words) {
     __shared__ float seg_s[16][4];
     __shared__ unsigned long long red_s[2][16];
     __shared__ float norm_s;
@@ -82,11 +83,14 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
     int4 rng = make_int4(0, V, 0, 0);
     if (ts.rng) rng = *(const int4 *)(ts.rng + b * 4);
     const unsigned *mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
+    // repetition rules: the row's no-repeat bitmap (the penalty is already in the stored logits)
+    const unsigned *brow = ban ? ban + (long)b * ban_words : nullptr;
     auto local_best = [&](unsigned long long bound) {
         unsigned long long best = 0ull;
         for (int n = threadIdx.x; n < V; n += 1024) {
             const bool in_text = !forced && n >= rng.x && n < rng.y, in_ts = n >= rng.z && n < rng.w;
             if (!(in_text || in_ts) || (mrow && ((mrow[n >> 5] >> (n & 31)) & 1u))) continue;
+            if (brow && ((brow[n >> 5] >> (n & 31)) & 1u)) continue;
             const unsigned long long k = argmax_key(logits[(long)b * ldo + n], n);
             if (k < bound && k > best) best = k;
         }
@@ -292,12 +296,13 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(bf16_t *__restrict__ 
 
 int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
                  const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                 const WmBeamDev &bm) {
+                 const WmBeamDev &bm, const unsigned *ban, int ban_words) {
     WmProfScope ps(&ctx->prof, "beam_topk", ctx->stream);
+    WM_REQUIRE(!ban || (long)ban_words * 32 >= n_vocab, WM_ERR_INVALID, "beam_topk: %d ban words do not cover %d ids", ban_words, n_vocab);
     WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && bm.N >= 1 && bm.N <= WM_MAX_BEAM && rows % bm.N == 0 && xd.par, WM_ERR_INVALID,
                "beam_topk: bad group");
     beam_topk_kernel<<<rows, 1024, 0, ctx->stream>>>(logits, ldo, n_vocab, (n_vocab + 15) / 16, tilemax, ts, xd, mask, mask_words,
-                                                     n_prompt, pos_ptr, bm);
+                                                     n_prompt, pos_ptr, bm, ban, ban_words);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

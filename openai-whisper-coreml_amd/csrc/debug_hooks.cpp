@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/whisper_mi355x_debug.h"
@@ -1134,9 +1135,14 @@ extern "C" int wmdbg_step_layout(int32_t *out4) {
     return WM_OK;
 }
 
-extern "C" int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io) {
+// rep: the repetition rules (penalty, ngram, io->eot) are on -- wm_repeat_state in front of a DE_LOGITS_XR launch
+static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
+    if (rep)
+        WM_REQUIRE(io->x_on && std::isfinite(penalty) && penalty > 0.f && ngram >= 0 && ngram <= WM_MAX_NGRAM && io->eot >= 0 &&
+                       io->eot <= io->V && io->n_prompt <= io->n_ctx,
+                   WM_ERR_INVALID, "wmdbg_decode_close_rep: needs x_on, a finite penalty > 0, ngram 0 .. 32 and eot in [0, V]");
     const int B = io->B, V = io->V, K = io->K, n_ctx = io->n_ctx, pos = io->pos, n_prompt = io->n_prompt;
     WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && V >= 16 && K >= 64 && K % 64 == 0 && K <= 1280 && n_ctx >= 1 && pos >= 0 && pos < n_ctx &&
                    n_prompt >= 1,
@@ -1270,6 +1276,17 @@ extern "C" int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io) {
     if (mask_on) { a.mask = (const unsigned *)dmask; a.mask_words = mw; a.mask_first_pos = io->mask_first ? pos : -1; }
     a.ts = ts;
     a.x = xd;
+    WmRepPar rpar;
+    if (rep) {   // bitmaps pre-filled with 0xff: every word the epilogue reads must have been rebuilt by this position's launch
+        void *dseen, *dban, *drp;
+        rpar.p = penalty; rpar.inv_p = (float)(1.0 / (double)penalty); rpar.n = ngram; rpar.eot = io->eot;
+        WM_TRY(pool.get(&dseen, nullptr, (size_t)B * mw * 4, s, 0xff));
+        WM_TRY(pool.get(&dban, nullptr, (size_t)B * mw * 4, s, 0xff));
+        WM_TRY(pool.get(&drp, &rpar, sizeof(rpar), s));
+        a.epi = DE_LOGITS_XR;
+        a.rep.par = (const WmRepPar *)drp; a.rep.seen = (unsigned *)dseen; a.rep.ban = (unsigned *)dban; a.rep.words = mw;
+        WM_TRY(wm_repeat_state(ctx, (const int *)dseq, (const int *)dpos, B, n_prompt, n_ctx, V, a.rep));
+    }
     WM_TRY(wm_dec_gemv(ctx, a));
     WM_TRY(wm_argmax_embed(ctx, (const unsigned long long *)dtm, n_tiles, B, (int *)dseq, (int *)dpos, n_prompt, (int *)dres, io->arg_first,
                            (const bf16_t *)dE, (const float *)dpemb, K, n_ctx, (float *)dxn, (bf16_t *)dxbn, (float *)dstn,
@@ -1326,5 +1343,37 @@ extern "C" int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io) {
         io->stats_next[b * 2] = s1;
         io->stats_next[b * 2 + 1] = s2;
     }
+    return WM_OK;
+}
+
+extern "C" int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io) { return decode_close_run(ctx, io, false, 1.f, 0); }
+extern "C" int wmdbg_decode_close_rep(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram) {
+    return decode_close_run(ctx, io, true, penalty, ngram);
+}
+
+extern "C" int wmdbg_repeat_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V, int ngram,
+                                  int32_t eot, uint32_t *seen_out, uint32_t *ban_out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(seq && seen_out && ban_out, WM_ERR_INVALID, "wmdbg_repeat_state: null pointer");
+    WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && V >= 16 && n_ctx >= 1 && n_ctx <= 448 && pos >= 0 && pos < n_ctx && n_prompt >= 0 &&
+                   n_prompt <= n_ctx && ngram >= 0 && ngram <= WM_MAX_NGRAM && eot >= 0 && eot <= V,
+               WM_ERR_INVALID, "wmdbg_repeat_state: bad geometry");
+    const int words = ((V + 15) / 16 * 16 + 31) / 32;
+    WmRepPar rpar;
+    rpar.p = 1.f; rpar.inv_p = 1.f; rpar.n = ngram; rpar.eot = eot;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dseq, *dpos, *drp, *dseen, *dban;
+    WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * B * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&drp, &rpar, sizeof(rpar), s));
+    WM_TRY(pool.get(&dseen, nullptr, (size_t)B * words * 4, s, 0xff));   // 0xff: a word the kernel leaves alone shows
+    WM_TRY(pool.get(&dban, nullptr, (size_t)B * words * 4, s, 0xff));
+    WmRepDev rd;
+    rd.par = (const WmRepPar *)drp; rd.seen = (unsigned *)dseen; rd.ban = (unsigned *)dban; rd.words = words;
+    WM_TRY(wm_repeat_state(ctx, (const int *)dseq, (const int *)dpos, B, n_prompt, n_ctx, V, rd));
+    WM_HIP(hipMemcpyAsync(seen_out, dseen, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(ban_out, dban, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
     return WM_OK;
 }

@@ -85,7 +85,11 @@ struct DecGemvDev {
     int pf_tiles;
     int pf_head_major;     // warm-up placement for a consumer that runs head h on XCD h % 8 (dec_xattn_fq_kernel)
     int bgroups;           // workgroups per tile group along the batch: group g takes batch rows [g, g + 1) * NBLK * 16
+    WmRepDev rep;          // DE_LOGITS_XR: repetition rules (LAST: the fields above keep their kernel-argument offsets)
 };
+// the extended-decode epilogues (DE_LOGITS_XR = DE_LOGITS_X + the repetition rules), and every logits epilogue
+constexpr bool de_is_x(int epi) { return epi == DE_LOGITS_X || epi == DE_LOGITS_XR; }
+constexpr bool de_is_logits(int epi) { return epi == DE_LOGITS || de_is_x(epi); }
 
 // L2 warm-up workgroup: blockIdx >= n_tiles of the compute grid.  Workgroup n_tiles + t reads tile t of
 // the NEXT launch's weight matrix.  Dispatch places block b on XCD b % 8 (observed, not guaranteed --
@@ -141,8 +145,15 @@ __device__ __forceinline__ float attn_merge_core(const float (&m)[NS], const flo
 //     over the waves for the fused epilogue: bias / GELU / residual (+ bf16 copy + partial statistics) / KV append /
 //     arg-max (+ suppress bitmaps, timestamp rules).
 // LDS carve (dynamic): red [NW][TN*NBLK][64][4] f32 | st [NW][16][2] f32
+// repetition rules (DE_LOGITS_XR only: an empty base everywhere else): the bitmap words of the lane's four rows for this tile
+template <int EPI>
+struct GemvRepWords {};
+template <>
+struct GemvRepWords<DE_LOGITS_XR> {
+    unsigned rseen[4], rban[4];
+};
 template <int EPI, bool LN>
-struct GemvUnitOps {
+struct GemvUnitOps : GemvRepWords<EPI> {
     float c1v, c2v;
     float xold[4];
     float off4[4];   // DE_RESID: mean-centring offsets of the lane's four rows
@@ -181,12 +192,23 @@ __device__ __forceinline__ void gemv_unit_load(const DecGemvDev &p, GemvUnitOps<
         }
     }
     if (LN && p.mean_in && want_stats) o.offrow = p.mean_in[b0 + (nrow < nb ? nrow : nb - 1)];
-    if ((EPI == DE_LOGITS || EPI == DE_LOGITS_X) && p.ts.rng) {
+    if (de_is_logits(EPI) && p.ts.rng) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (r < r0 || r >= r1) continue;
             const int bl = kq * 4 + r;
             o.trng[r] = *(const int4 *)(p.ts.rng + (long)(b0 + (bl < nb ? bl : nb - 1)) * 4);
+        }
+    }
+    if constexpr (EPI == DE_LOGITS_XR) {
+        // the 16 ids of a tile share ONE bitmap word per row; rows past the group's are clamped like the ranges above
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (r < r0 || r >= r1) continue;
+            const int bl = kq * 4 + r;
+            const long wi = (long)(b0 + (bl < nb ? bl : nb - 1)) * p.rep.words + (nc >> 5);
+            o.rseen[r] = p.rep.seen[wi];
+            o.rban[r] = p.rep.ban[wi];
         }
     }
     if (LN) {
@@ -249,7 +271,7 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
     const bool nvalid = n < p.N;
     const int nb = p.B - b0 < 16 ? p.B - b0 : 16;
     unsigned draw[4] = {0u, 0u, 0u, 0u};   // DE_LOGITS_X under sampling: the 32-bit draw of (row kq * 4 + r, id n)
-    if (EPI == DE_LOGITS_X) {
+    if (de_is_x(EPI)) {
         const WmXPar xp = *p.x.par;
         const int gi = pos + 1 - xp.n_prompt;
         if (xp.sample && gi >= 0) {   // wave-uniform (every lane active)
@@ -280,14 +302,24 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
         } else {
             v = acc[r] + o.c2v;
         }
-        if (EPI == DE_LOGITS_X) {
+        bool rbanned = false;
+        if constexpr (EPI == DE_LOGITS_XR) {
+            // repetition rules first: the penalised value REPLACES the logit for everything below (keys, scores, partials,
+            // the winners' raw logits, the stored row); a banned id is treated like a suppressed one.  The bitmaps hold ids
+            // < eot only (wm_repeat_state) and are empty at a prompt position.
+            const WmRepPar rp = *p.rep.par;
+            const unsigned bit = 1u << (n & 31);
+            if (o.rseen[r] & bit) v = v > 0.f ? __fmul_rn(v, rp.inv_p) : __fmul_rn(v, rp.p);
+            rbanned = (o.rban[r] & bit) != 0u;
+        }
+        if (de_is_x(EPI)) {
             // extended decode: the DE_LOGITS keys (timestamp rules or the plain [arg_first, arg_last] range), over
             // Gumbel-perturbed scores when sampling, with the winners' RAW logits beside them (their log-probs; score - g
             // would lose bits), plus the (max, sum exp) partial of the allowed text ids and, at the <|startoftranscript|>
             // position only, the unfiltered one over the whole vocabulary (no_speech_prob).  Wave-uniform branches.
             const WmXPar xp = *p.x.par;
             const unsigned mw = (pos == p.mask_first_pos) ? mword1 : mword0;
-            const bool ok = bvalid && nvalid && !((mw >> (n & 31)) & 1u);
+            const bool ok = bvalid && nvalid && !((mw >> (n & 31)) & 1u) && !(EPI == DE_LOGITS_XR && rbanned);
             const bool ts_on = p.ts.rng != nullptr;
             const bool in_text = ts_on ? (ok && n >= o.trng[r].x && n < o.trng[r].y) : (ok && n >= p.arg_first && n <= p.arg_last);
             const bool in_ts = ts_on && ok && n >= o.trng[r].z && n < o.trng[r].w;
@@ -520,7 +552,8 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
     if (EPI == DE_RESID) { GEMV_PIN(p.out_bf16); GEMV_PIN(p.stats_out); GEMV_PIN(p.stats_stride); GEMV_PIN(p.mean_in); }
     if (EPI == DE_QKV) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); }
     if (EPI == DE_GELU) GEMV_PIN(p.out_bf16);
-    if (EPI == DE_LOGITS || EPI == DE_LOGITS_X) {
+    if (EPI == DE_LOGITS_XR) { GEMV_PIN(p.rep.par); GEMV_PIN(p.rep.seen); GEMV_PIN(p.rep.ban); GEMV_PIN(p.rep.words); }
+    if (de_is_logits(EPI)) {
         GEMV_PIN(p.tilemax); GEMV_PIN(p.arg_first); GEMV_PIN(p.arg_last); GEMV_PIN(p.mask); GEMV_PIN(p.mask_words);
         GEMV_PIN(p.mask_first_pos); GEMV_PIN(p.ts.rng); GEMV_PIN(p.ts.key_ts); GEMV_PIN(p.ts.lse); GEMV_PIN(p.ts.ts_begin);
     }
@@ -553,7 +586,7 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
         gemv_unit_load<EPI, LN>(p, ops, utile, ub0, lane, my_r0, my_r1, my_stats);
     }
     if (p.pos_ptr) pos = *p.pos_ptr;
-    if ((EPI == DE_LOGITS || EPI == DE_LOGITS_X) && p.mask && has_unit) {
+    if (de_is_logits(EPI) && p.mask && has_unit) {
         const int n = utile * 16 + nrow;
         const int nc = n < p.N ? n : p.N - 1;
         mword0 = p.mask[nc >> 5];
@@ -603,7 +636,7 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
         if (tk != wave) {  // more units than waves (small models; RS == 1): operands fetched late
             gemv_unit_load<EPI, LN>(p, ops, tile, b0, lane);
             gemv_unit_stats<EPI, LN>(p, ops, st, lane, tile, b0);
-            if ((EPI == DE_LOGITS || EPI == DE_LOGITS_X) && p.mask) {
+            if (de_is_logits(EPI) && p.mask) {
                 const int n = tile * 16 + nrow;
                 const int nc = n < p.N ? n : p.N - 1;
                 mword0 = p.mask[nc >> 5];
@@ -1803,7 +1836,7 @@ int launch_gemv_shape(wm_ctx *ctx, const DecGemvDev &p, int tn, int nblk, int nw
     }
     const size_t lds = (size_t)nw * tn * nblk * 1024 + (size_t)nw * 32 * 4;
     const int th = nw * 64;
-    constexpr bool LOGITS = EPI == DE_LOGITS || EPI == DE_LOGITS_X;
+    constexpr bool LOGITS = de_is_logits(EPI);
     constexpr bool WIDE = LN && (EPI == DE_QKV || EPI == DE_GELU || LOGITS) && SPW <= 6;
     if (tn == 1 && nblk == 1) dec_gemv_kernel<SPW, 1, 1, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 1 && nblk == 2 && SPW <= 8) dec_gemv_kernel<SPW <= 8 ? SPW : 2, 1, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
@@ -1868,7 +1901,7 @@ static void pick_shape(int epi, bool ln, int spw, int nw, int B, int n_tiles, in
     // 512, register budget) or more than 8 k-steps per wave (K = 4d at d = 576 / 640: spw 12 / 10 on <= 8 waves -- the
     // two-block kernel holds 2 x SPW activation fragments and exists for SPW <= 8 only): one unit per workgroup, more
     // workgroups along the batch
-    if (blocks < 2 && (epi == DE_LOGITS || epi == DE_LOGITS_X) && ln && spw <= 6) {
+    if (blocks < 2 && de_is_logits(epi) && ln && spw <= 6) {
         // the vocabulary product of a one-block group: 4 tiles per workgroup (810 workgroups instead of 3 242 two-wave
         // ones; -1.4 % per position at tiny.en / base / small, neutral at large-v2: profiles/r04_latency_probe.txt)
         *tn = (g_wm_tuning.logits_tn == 1 || g_wm_tuning.logits_tn == 2) ? g_wm_tuning.logits_tn : 4;
@@ -1876,7 +1909,7 @@ static void pick_shape(int epi, bool ln, int spw, int nw, int B, int n_tiles, in
     }
     if (blocks < 2 || nw > 8 || spw > 8) return;
     *nblk = env_nb == 1 ? 1 : 2;
-    const bool wide = ln && (epi == DE_QKV || epi == DE_GELU || epi == DE_LOGITS || epi == DE_LOGITS_X) && *nblk == 2 && spw <= 6;
+    const bool wide = ln && (epi == DE_QKV || epi == DE_GELU || de_is_logits(epi)) && *nblk == 2 && spw <= 6;
     if (!wide) return;
     // Tile-group width by RESIDENCY ROUNDS: an 8-wave workgroup of the (1, 2) shape needs <= 128 VGPRs and sits two per
     // CU, the wide shapes (136-190 VGPRs) one per CU; a grid that needs a second round of the chip costs a whole kernel
@@ -1921,7 +1954,10 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
     p.mask = a.mask; p.mask_words = a.mask_words; p.mask_first_pos = a.mask_first_pos;
     p.ts = a.ts;
     p.x = a.x;
-    WM_REQUIRE(a.epi != DE_LOGITS_X || (a.x.par && a.pos_ptr), WM_ERR_INVALID, "dec_gemv: DE_LOGITS_X needs its state and the device position");
+    p.rep = a.rep;
+    WM_REQUIRE(!de_is_x(a.epi) || (a.x.par && a.pos_ptr), WM_ERR_INVALID, "dec_gemv: DE_LOGITS_X needs its state and the device position");
+    WM_REQUIRE(a.epi != DE_LOGITS_XR || (a.rep.par && a.rep.seen && a.rep.ban && (long)a.rep.words * 32 >= a.N), WM_ERR_INVALID,
+               "dec_gemv: DE_LOGITS_XR needs the repetition-rule state");
     p.n_tiles = (a.N + 15) / 16;
     int tn = 1, nblk = 1;
     pick_shape(a.epi, ln, spw, nw, a.B, p.n_tiles, ctx->n_cus, &tn, &nblk);
@@ -1977,6 +2013,10 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
         case DE_LOGITS_X * 2 + 1: {
             WmProfScope ps(&ctx->prof, "dec_gemv_ln_logits_x", ctx->stream);
             return launch_gemv<DE_LOGITS_X, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
+        }
+        case DE_LOGITS_XR * 2 + 1: {
+            WmProfScope ps(&ctx->prof, "dec_gemv_ln_logits_xr", ctx->stream);
+            return launch_gemv<DE_LOGITS_XR, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
         }
         case DE_RESID * 2: {
             WmProfScope ps(&ctx->prof, a.K > a.N ? "dec_gemv_fc2" : "dec_gemv_attn_out", ctx->stream);

@@ -5,6 +5,7 @@
 #include "model.h"
 
 #include <math.h>
+#include <cmath>
 #include <string.h>
 
 static inline bf16_t host_f2bf(float f) {
@@ -83,6 +84,14 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc_t(m, &m->dxkv_rows, (size_t)WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dmask, (size_t)2 * (m->vpad / 32), s));
     WM_HIP(hipMemsetAsync(m->dmask, 0, (size_t)2 * (m->vpad / 32) * 4, s));
+    return WM_OK;
+}
+
+static int alloc_repetition_state(WmModel *m, hipStream_t s) {
+    const size_t words = (size_t)WM_DEC_MAXB * ((m->vpad + 31) / 32);
+    WM_TRY(dalloc_t(m, &m->drep_seen, words, s));
+    WM_TRY(dalloc_t(m, &m->drep_ban, words, s));
+    WM_TRY(dalloc(m, (void **)&m->drep_par, sizeof(WmRepPar), s));
     return WM_OK;
 }
 
@@ -170,8 +179,9 @@ int wm_model_beam_close(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mo
     const WmStopDev sp = wm_model_stop_dev(m, mode);
     const WmXDev xd = wm_model_x_dev(m, mode);
     WM_REQUIRE(xd.par, WM_ERR_STATE, "beam close: the extended decode is off");
+    const WmRepDev rp = wm_model_rep_dev(m, mode);
     WM_TRY(wm_beam_topk(ctx, m->dlogits, m->vpad, D.n_vocab, m->dargmax, B, ts, xd, mode.mask ? m->dmask : nullptr, m->vpad / 32,
-                        n_prompt, m->dpos, bm));
+                        n_prompt, m->dpos, bm, rp.par ? rp.ban : nullptr, rp.words));
     WM_TRY(wm_beam_select_step(ctx, B, m->dseq, m->dpos, n_prompt, m->tok_emb, m->dec_pos, D.n_text_state, m->dx, m->dxb, m->dstats,
                                m->dmean, ts, sp, xd, mode.off ? m->doff : nullptr, bm));
     return wm_beam_reorder(ctx, m->skv, D.n_text_layer * 2, B, D.n_text_head, D.n_text_ctx, m->dpos, n_prompt, m->dseq,
@@ -182,6 +192,38 @@ void wm_model_drop_graphs(WmModel *m) {
     for (WmModel::GraphSet &g : m->graph_sets) g.destroy();
     m->graph_sets.clear();
     m->lid_graph.destroy();
+}
+
+WmRepDev wm_model_rep_dev(const WmModel *m, const WmDecodeMode &mode) {
+    WmRepDev t;
+    memset(&t, 0, sizeof(t));
+    if (!mode.rep) return t;
+    t.par = m->drep_par; t.seen = m->drep_seen; t.ban = m->drep_ban; t.words = (m->vpad + 31) / 32;
+    return t;
+}
+
+// the bitmaps and the parameter block, once (captured graphs hold these addresses)
+static int alloc_repetition_state(WmModel *m, hipStream_t s);
+
+int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t eot) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m, WM_ERR_STATE, "context has no model");
+    WM_REQUIRE(std::isfinite(penalty) && penalty > 0.f, WM_ERR_INVALID, "repetition rules: the penalty must be finite and > 0 (1.0: off)");
+    // (1 / p is the multiplier of a positive logit: it must be a finite f32 as well)
+    WM_REQUIRE(std::isfinite((float)(1.0 / (double)penalty)), WM_ERR_INVALID, "repetition rules: penalty %g is too small: 1 / p overflows",
+               (double)penalty);
+    WM_REQUIRE(ngram >= 0 && ngram <= WM_MAX_NGRAM, WM_ERR_INVALID, "repetition rules: no_repeat_ngram_size %d outside [0, %d]", ngram,
+               WM_MAX_NGRAM);
+    WM_REQUIRE(eot >= 0 && eot <= m->dims.n_vocab, WM_ERR_INVALID, "repetition rules: eot %d outside [0, %d]", eot, m->dims.n_vocab);
+    const bool on = penalty != 1.f || ngram != 0;
+    if (on) {
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
+        WM_REQUIRE(((size_t)2 * ((m->vpad + 31) / 32) + m->dims.n_text_ctx) * 4 <= 64 * 1024, WM_ERR_INVALID,
+                   "repetition rules: a vocabulary of %d ids does not fit the state kernel's LDS", m->dims.n_vocab);
+        if (!m->drep_par) WM_TRY(alloc_repetition_state(m, ctx->stream));
+    }
+    m->rep_on = on; m->rep_p = penalty; m->rep_n = ngram; m->rep_eot = eot;
+    return WM_OK;
 }
 
 WmTsDev wm_model_ts_dev(const WmModel *m) {
@@ -387,6 +429,8 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->mask_on = pm->mask_on; m->mask_host = pm->mask_host;
     m->ts_on = pm->ts_on; m->ts_begin = pm->ts_begin; m->ts_eot = pm->ts_eot; m->ts_max_initial = pm->ts_max_initial;
     m->align_l = pm->align_l; m->align_h = pm->align_h;
+    m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
+    if (m->rep_on) WM_TRY(alloc_repetition_state(m, child->stream));
     WM_HIP(hipStreamSynchronize(child->stream));
     return WM_OK;
 }
@@ -797,6 +841,11 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         if (mode.ts) a.ts = wm_model_ts_dev(m);
         if (mode.x) {   // extended decode: its own epilogue instantiation, the position always from the device
             a.epi = DE_LOGITS_X; a.x = wm_model_x_dev(m, mode); a.pos_ptr = m->dpos;
+        }
+        if (mode.rep) {   // repetition rules: the rows' bitmaps rebuilt from their histories, in line in front of the product
+            WM_REQUIRE(mode.x, WM_ERR_STATE, "decode step: the repetition rules need the extended decode");
+            a.epi = DE_LOGITS_XR; a.rep = wm_model_rep_dev(m, mode);
+            WM_TRY(wm_repeat_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, a.rep));
         }
         WM_TRY(wm_dec_gemv(ctx, a));
     }

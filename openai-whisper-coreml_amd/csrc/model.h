@@ -110,6 +110,24 @@ struct WmXDev {
     float *nospeech;      // [B]
 };
 
+// The repetition rules (wm_set_repetition_rules; repeat.hip): two logit processors over a row's own
+// GENERATED history g[0 .. k) = positions n_prompt .. pos of the token buffer (the prompt is excluded).  Only ids < eot are
+// ever penalised or banned.  Penalty p: every id that occurs in g, once, v = v > 0 ? v * inv_p : v * p.  No-repeat n-gram n:
+// id t is banned iff some i in [0, k - n] has g[i .. i + n - 1) == g[k - n + 1 .. k) and g[i + n - 1] == t.  wm_repeat_state
+// REBUILDS both bitmaps from the history in front of every logits launch; the DE_LOGITS_XR epilogue applies them before
+// anything else looks at the logit.  What changes from call to call lives in device memory (WmRepPar, written at prefill).
+struct WmRepPar {
+    float p, inv_p;   // inv_p = (float)(1.0 / (double)p), computed on the host: the penalty is ONE f32 multiply either way
+    int n, eot;
+};
+struct WmRepDev {
+    const WmRepPar *par;   // null: the rules are off
+    unsigned *seen;        // [rows][words] ids < eot that occur in the row's history
+    unsigned *ban;         // [rows][words] ids < eot that would complete a repeated n-gram
+    int words;             // (vpad + 31) / 32
+};
+constexpr int WM_MAX_NGRAM = 32;
+
 // Early-stop state of a decode group (device view; done == null: off).  A row is DONE once it has emitted `eot`
 // (eot >= 0) or produced budget[b] tokens (budget != null); from then on its tokens are `pad_tok`, it is dropped from
 // the compact live list the attention kernels walk, and when the list is empty the host stops launching positions.
@@ -202,8 +220,9 @@ struct WmDecodeMode {
     // Beam width (wm_transcribe_mel_beam; 0: no beam search): the generating positions close with the beam kernels
     // (wm_model_beam_close) instead of the arg-max; above 1 the rows are a candidate group (n_cand = beam).
     int beam = 0;
+    bool rep = false;       // the repetition rules apply (wm_set_repetition_rules, WmRepDev): wm_repeat_state + DE_LOGITS_XR; needs x
     bool operator==(const WmDecodeMode &o) const {
-        return n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return rep == o.rep && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -339,6 +358,12 @@ struct WmModel {
     float *dx_logprob = nullptr;   // [n_text_ctx][WM_DEC_MAXB]
     float *dx_nospeech = nullptr;  // [WM_DEC_MAXB]
     WmXPar *dx_par = nullptr;
+    // repetition rules (wm_set_repetition_rules): the context's setting, and the device state allocated when first set
+    bool rep_on = false;
+    float rep_p = 1.f;
+    int rep_n = 0, rep_eot = 0;
+    unsigned *drep_seen = nullptr, *drep_ban = nullptr;   // [WM_DEC_MAXB][(vpad + 31) / 32]
+    WmRepPar *drep_par = nullptr;
     unsigned *dx_ids = nullptr;    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     int *dxkv_rows = nullptr;      // [WM_DEC_MAXB] the group's rows of a window set (wm_transcribe_windows): the gather's row map
@@ -402,6 +427,10 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
 WmXDev wm_model_x_dev(const WmModel *m, const WmDecodeMode &mode);
 // the device view of the context's timestamp-rule state (rng == null when the rules are off)
 WmTsDev wm_model_ts_dev(const WmModel *m);
+// the device view of the repetition-rule state (par == null when mode.rep is false)
+WmRepDev wm_model_rep_dev(const WmModel *m, const WmDecodeMode &mode);
+// (1.0, 0, any eot) switches the rules off; the first enabling call allocates the bitmaps
+int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t eot);
 int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int32_t eot, int32_t max_initial);
 int wm_model_set_suppress(wm_ctx *ctx, const int32_t *ids, int n, const int32_t *first_ids, int n_first);
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode = WmDecodeMode());
@@ -471,7 +500,9 @@ constexpr int WM_MAXSPLIT = 8;  // stream partials of a (sequence, head) pair of
 // DE_LOGITS_X: DE_LOGITS plus the WmXDev partials (text (max, sum exp), winners' raw logits, the unfiltered partial at
 // the <|startoftranscript|> position) and Gumbel-perturbed keys when sampling -- its own instantiations, so the plain
 // greedy logits kernel does none of it
-enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5 };
+// DE_LOGITS_XR: DE_LOGITS_X with the repetition rules (WmRepDev): the same body, the row's penalty and ban words applied to
+// the logit first -- again its own instantiations, so DE_LOGITS_X stays instruction for instruction what it was
+enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5, DE_LOGITS_XR = 6 };
 struct DecGemvArgs {
     int epi;
     int B, N, K;
@@ -506,6 +537,7 @@ struct DecGemvArgs {
     const bf16_t *pf_ptr;
     int pf_rows, pf_k;
     int pf_head_major;     // the next launch is wm_dec_xattn_fq: (pairs per XCD) place every head's tiles on the XCD(s) that run it
+    WmRepDev rep;          // DE_LOGITS_XR: repetition rules (rep.par non-null)
 };
 int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a);
 // cross_attn_ln + query projection fused INTO the cross-attention launch (96 .. 256 pairs, alone on the device): qa = the
@@ -566,9 +598,10 @@ int wm_fill_synthetic(wm_ctx *ctx, const WmTensor &t, uint32_t seed, int tensor_
 // Per row (grid: rows) the <= N + 1 best admissible tokens of the f32 logits [rows][ldo] with their log-probs under the
 // filtered distribution, from the partials the DE_LOGITS_X launch of the same position left (tilemax, xd, ts); rows of
 // windows that have left and dead beams get an empty list.  Also no_speech_prob when the position is par->sot_pos.
+// ban (nullable): the rows' no-repeat bitmaps [rows][ban_words] (WmRepDev::ban) -- a banned id is never listed.
 int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
                  const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                 const WmBeamDev &bm);
+                 const WmBeamDev &bm, const unsigned *ban = nullptr, int ban_words = 0);
 // Per window the selection (beam.h), finished records, the rows' new tokens / sums / sources / timestamp-rule state, the
 // early-stop flags and live list, the embedding of the next position and *pos_ptr += 1 (one workgroup).
 int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const bf16_t *emb, const float *pemb, int d,
@@ -578,6 +611,11 @@ int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_pro
 // self-attention K/V (skv [L2][rows][H][T][64]) and the rows' token / log-prob histories.  Call after wm_beam_select_step.
 int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, const int *pos_ptr, int n_prompt, int *seq,
                     float *logprob, const WmBeamDev &bm);
+
+// repeat.hip (repetition rules)
+// Rebuild rows 0 .. B - 1 of rep.seen / rep.ban from the generated history of position *pos_ptr: tokens seq[(n_prompt + i) * B + b],
+// i < min(*pos_ptr + 1 - n_prompt, n_ctx - n_prompt) (none at a prompt position).  V: ids at or above it set no bit.
+int wm_repeat_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int n_prompt, int n_ctx, int V, const WmRepDev &rep);
 
 // xkv_rows.hip (window sets)
 // Copy whole windows between a decode group's cross-attention K/V cache, group [L2][group_rows][slab] (slab = H * 1500 * 64

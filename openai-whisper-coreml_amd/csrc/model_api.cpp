@@ -113,6 +113,13 @@ extern "C" int wm_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t timestamp
         return wm_model_set_timestamp_rules(c, enable, timestamp_begin, eot, max_initial_timestamp_index);
     });
 } WM_API_CATCH
+extern "C" int wm_set_repetition_rules(wm_ctx *ctx, float repetition_penalty, int no_repeat_ngram_size, int32_t eot) try {
+    WM_MODEL(ctx);
+    (void)m;
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) {
+        return wm_model_set_repetition_rules(c, repetition_penalty, no_repeat_ngram_size, eot);
+    });
+} WM_API_CATCH
 extern "C" int wm_set_lanes(wm_ctx *ctx, int n_lanes) try {
     WM_REQUIRE(ctx, WM_ERR_INVALID, "null context");
     WM_REQUIRE(n_lanes >= 0 && n_lanes <= 8, WM_ERR_INVALID, "set_lanes: 0 (default) .. 8");
@@ -425,6 +432,7 @@ struct LaneJob {
     hipEvent_t burst_ev[WM_NLIVE_RING] = {};
     std::vector<int32_t> pr, gen, bud;
     WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
+    WmRepPar rpar = {};            // its repetition rules (likewise)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
     std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
     std::vector<unsigned> ids;     // its sample ids (wm_transcribe_mel)
@@ -636,6 +644,7 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
     j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
     j.mode.n_cand = N;
     j.mode.beam = src.beam ? N : 0;
+    j.mode.rep = m->rep_on;   // (transcribe_impl turns the extended decode on with them)
     const void *d_pcm;
     WM_TRY(stage_pcm(c, src, j.b0, Cg, mem, &d_pcm));
     // decode state first (prompt tokens [n_prompt][Bg], position 0): a pageable H2D copy may wait for the
@@ -689,6 +698,12 @@ int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const S
             WM_HIP(hipMemcpyAsync(m->dx_ids, j.ids.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
         }
         WM_HIP(hipMemcpyAsync(m->dx_par, &j.xpar, sizeof(WmXPar), hipMemcpyHostToDevice, c->stream));
+    }
+    // repetition rules: penalty, its reciprocal, n and eot live in device memory too (the graph key holds `rep` alone)
+    if (j.mode.rep) {
+        WM_REQUIRE(xc.on, WM_ERR_STATE, "the repetition rules need the extended decode");
+        j.rpar.p = m->rep_p; j.rpar.inv_p = (float)(1.0 / (double)m->rep_p); j.rpar.n = m->rep_n; j.rpar.eot = m->rep_eot;
+        WM_HIP(hipMemcpyAsync(m->drep_par, &j.rpar, sizeof(WmRepPar), hipMemcpyHostToDevice, c->stream));
     }
     WM_TRY(wm_model_reserve(c, Cg));
     if (N > 1) WM_TRY(wm_model_reserve_rows(c, Bg));
@@ -1194,7 +1209,9 @@ static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, i
         WM_REQUIRE(ns_tok >= -1 && ns_tok < D.n_vocab, WM_ERR_INVALID, "no_speech_token %d outside the vocabulary", ns_tok);
         WM_REQUIRE(!no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
         WM_REQUIRE(!src.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
-        xc.on = T > 0.f || logprobs_out || no_speech_out || src.beam;   // (the beam close reads the filtered partials)
+        // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
+        xc.on = T > 0.f || logprobs_out || no_speech_out || src.beam || m->rep_on;
+        WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
         xc.logprobs = logprobs_out;
         xc.no_speech = no_speech_out;
         const uint64_t seed = opts ? opts->seed : 0;

@@ -199,6 +199,16 @@ struct Whisper {
                 (0..<chunks).map { c in Array(probs[c * maxText..<c * maxText + text[c].count]) })
     }
 
+    /// The repetition rules of every later transcribe call on this context (wm_set_repetition_rules): `penalty` (> 0; 1 = off)
+    /// scales the logit of every id < eot a window has generated in the call, `noRepeatNgramSize` (0 = off, 1 ... 32) bans the
+    /// ids < eot that would repeat an n-gram of its generated tokens; the prompt never counts.  The defaults switch them off.
+    /// Not compiled in this repository (see the top of the file).
+    func setRepetitionRules(penalty: Float = 1.0, noRepeatNgramSize: Int32 = 0, eot: Int32 = 50257) throws {
+        typealias RulesFn = @convention(c) (OpaquePointer, Float, Int32, Int32) -> Int32
+        let f: RulesFn = try sym("wm_set_repetition_rules")
+        try check(f(ctx, penalty, noRepeatNgramSize, eot))
+    }
+
     /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
     /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
     /// Not compiled in this repository (see the top of the file).
