@@ -28,6 +28,55 @@ WM_API int wmdbg_mel80(float *out);
  * 2 = C += (f32 residual).  K % 64 == 0.  C is f32 on the host in every case. */
 WM_API int wmdbg_gemm(wm_ctx *ctx, const float *A, const float *W, const float *bias, float *C, int M, int N,
                int K, int epi);
+/* The same kernels with ANY of the seven epilogues and ANY row map, at small shapes: what wm_model_encode_win and
+ * wm_model_cross_kv ask of them (both Conv1d layers as implicit GEMMs, the V^T transpose, the cross-K/V scatter).
+ *   A row m = the K elements at a_off + (m / a_rpb) * a_bstride + (m % a_rpb) * a_rstride of A f32 [a_elems] (rounded to bf16,
+ *     uploaded with zeroed slack behind it); W f32 [N][K]; bias f32 [N] or NULL.
+ *   C row m starts at c_off + (m / c_rpb) * c_bstride + (m % c_rpb) * c_rstride of C f32 [c_elems]: the device buffer (bf16 for
+ *     epi 0, 1, 4, 5; f32 for 2, 3, 6) widened.  epi 5 (EPI_XKV) ignores the C map: C = [2][batch][n_head][seq][64].
+ *   epi 3 (EPI_CONV2_F32): pos f32 [c_rpb][N].  epi 4 (EPI_QKV_ENC): C rows hold the 2 * d_model query | key columns, vt f32
+ *     [vt_elems] = the bf16 V^T buffer [batch][n_head][64][seq_pad] widened.
+ * Before the launch every bf16 output element holds WMDBG_SENTINEL_BF16 and every f32 one WMDBG_SENTINEL_F32 (NaN bit
+ * patterns), except for epi 2 (EPI_RESID_F32), whose C is in / out: what the kernel did not write, or wrote where it should
+ * not, shows.  NOTHING is launched unless every address is inside its buffer -- WM_ERR_INVALID otherwise, with the reason in
+ * wm_last_error(): every A row inside a_elems + 128 elements (the 256 bytes of slack the product's allocations carry, which
+ * conv1 at n_mels = 80 over-reads by 16 elements), the A map a multiple of 8 elements, every C row inside c_elems, C rows
+ * disjoint (c_rstride >= N -- 2 * d_model for epi 4 -- and c_bstride >= c_rpb * c_rstride once M > c_rpb), the C map 16-byte
+ * aligned when N % 64 == 0 (the staged epilogues), K % 64 == 0; epi 5: M == batch * seq, N == 2 * d_model, d_model == 64 *
+ * n_head, c_elems == 2 * batch * n_head * seq * 64; epi 4: M == batch * seq, N == 3 * d_model, d_model == 64 * n_head,
+ * seq_pad % 16 == 0, seq_pad >= seq, vt_elems == batch * n_head * 64 * seq_pad. */
+typedef struct wmdbg_gemm_map {
+    int32_t M, N, K, epi;
+    int64_t a_off, a_rpb, a_bstride, a_rstride, a_elems;
+    int64_t c_off, c_rpb, c_bstride, c_rstride, c_elems;
+    int32_t d_model, n_head, seq, seq_pad, batch, reserved;
+    int64_t vt_elems;
+} wmdbg_gemm_map;
+WM_API int wmdbg_gemm_mapped(wm_ctx *ctx, const wmdbg_gemm_map *map, const float *A, const float *W, const float *bias,
+                             const float *pos, float *C, float *vt);
+/* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_gemm_map) and the offsets of a_off, d_model and vt_elems
+ * (host only). */
+WM_API int wmdbg_gemm_map_layout(int32_t *out4);
+
+/* ---- the product's own encoder-side launches, on a context with finalised weights (so the conv packing of wm_set_tensor is
+ * part of what runs).  1 <= B <= 16; C = n_mels, d = n_audio_state, H = n_audio_head. ------------------------------------------ */
+/* The stem of wm_model_encode_win (mel re-layout, conv1, conv2) by the function the encoder calls.  mel f32 [B][C][3000], or
+ * with wins i64 [B][4] = (base, T, seek, n) per row: row b = frames seek .. seek + n - 1 (n <= 3000, seek + n <= T, zeros
+ * after) of the [C][T] block at mel + base; mel then holds max(base + C * T) elements.  Out (bf16 widened / f32): mel_t
+ * [B][3002][C], h1p [B][3001][d], x [B][1500][d].  Before the launches the interiors hold the sentinels (mel_t rows 1 .. 3000,
+ * h1p rows 1 .. 3000, x); the guard rows -- mel_t rows 0 and 3001, h1p row 0 -- are left as the allocation zeroed them. */
+WM_API int wmdbg_encode_stem(wm_ctx *ctx, const float *mel, const int64_t *wins, int B, float *mel_t_out, float *h1p_out,
+                             float *x_out);
+/* Encoder layer `layer`'s LayerNorm + QKV launch on x f32 [B * 1500][d] uploaded into the model's residual buffer.  Out (bf16
+ * widened): xn [B * 1500][d], qk [B * 1500][2 d] (pre-scaled queries | keys), vt [B][H][64][1536].  xn, qk and vt hold
+ * WMDBG_SENTINEL_BF16 before the launches; afterwards vt is zeroed, so that its pad columns 1500 .. 1535 are zero again as a
+ * later encode expects. */
+WM_API int wmdbg_encode_layer_qkv(wm_ctx *ctx, int layer, const float *x, int B, float *xn_out, float *qk_out, float *vt_out);
+/* wm_model_set_xa + wm_model_cross_kv on xa f32 [B][1500][d]: xkv f32 [L][2][B][H][1500][64] (L = n_text_layer; bf16 widened).
+ * The model's whole cross-K/V allocation holds WMDBG_SENTINEL_BF16 before the launches; an element behind the B chunks' cache
+ * that no longer does is WM_ERR_STATE. */
+WM_API int wmdbg_cross_kv(wm_ctx *ctx, const float *xa, int B, float *xkv_out);
+
 /* LayerNorm over the last axis (eps 1e-5): f32 result and the bf16 result widened to f32. */
 WM_API int wmdbg_layernorm(wm_ctx *ctx, const float *x, const float *g, const float *b, int rows, int d,
                     float *out_f32, float *out_bf16_as_f32);

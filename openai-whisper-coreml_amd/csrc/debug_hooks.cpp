@@ -1377,3 +1377,256 @@ extern "C" int wmdbg_repeat_state(wm_ctx *ctx, const int32_t *seq, int B, int n_
     WM_HIP(hipStreamSynchronize(s));
     return WM_OK;
 }
+
+// ------------------------------------------------------------------ encoder GEMM: any epilogue, any row map -----------------
+extern "C" int wmdbg_gemm_map_layout(int32_t *out4) {
+    if (!out4) return WM_ERR_INVALID;
+    out4[0] = (int32_t)sizeof(wmdbg_gemm_map); out4[1] = (int32_t)offsetof(wmdbg_gemm_map, a_off);
+    out4[2] = (int32_t)offsetof(wmdbg_gemm_map, d_model); out4[3] = (int32_t)offsetof(wmdbg_gemm_map, vt_elems);
+    return WM_OK;
+}
+
+namespace {
+constexpr int64_t GEMM_MAP_MAX_ELEMS = (int64_t)1 << 28;   // per buffer: a test hook, not a product path
+constexpr int64_t GEMM_MAP_A_SLACK = 128;                  // elements: the 256 bytes of slack behind every dalloc of model.cpp
+
+// Every address the launch may touch, from the arguments alone.  Nothing is launched unless this returns WM_OK.
+int gemm_map_check(const wmdbg_gemm_map &g, const float *A, const float *W, const float *pos, const float *C, const float *vt) {
+    WM_REQUIRE(A && W && C, WM_ERR_INVALID, "wmdbg_gemm_mapped: null pointer");
+    WM_REQUIRE(g.epi >= EPI_BIAS_BF16 && g.epi <= EPI_F32, WM_ERR_INVALID, "wmdbg_gemm_mapped: bad epilogue %d", g.epi);
+    WM_REQUIRE(g.M >= 1 && g.M < (1 << 24) && g.N >= 1 && g.N < (1 << 20) && g.K >= 64 && g.K % 64 == 0 && g.K <= (1 << 16),
+               WM_ERR_INVALID, "wmdbg_gemm_mapped: bad problem size M=%d N=%d K=%d", g.M, g.N, g.K);
+    // ---- A: row m reads [off, off + K) (16-byte DMA pieces: every part of the address is a multiple of 8 elements)
+    WM_REQUIRE(g.a_rpb >= 1 && g.a_rpb <= 0x7fffffffLL && g.a_off >= 0 && g.a_bstride >= 0 && g.a_rstride >= 0 && g.a_elems >= 1 &&
+                   g.a_elems <= GEMM_MAP_MAX_ELEMS,
+               WM_ERR_INVALID, "wmdbg_gemm_mapped: bad A map");
+    WM_REQUIRE(g.a_off % 8 == 0 && g.a_bstride % 8 == 0 && g.a_rstride % 8 == 0, WM_ERR_INVALID,
+               "wmdbg_gemm_mapped: A map not 16-byte aligned");
+    WM_REQUIRE(g.a_bstride <= GEMM_MAP_MAX_ELEMS && g.a_rstride <= GEMM_MAP_MAX_ELEMS, WM_ERR_INVALID, "wmdbg_gemm_mapped: bad A map");
+    for (int64_t m = 0; m < g.M; ++m) {
+        const int64_t off = g.a_off + (m / g.a_rpb) * g.a_bstride + (m % g.a_rpb) * g.a_rstride;
+        WM_REQUIRE(off + g.K <= g.a_elems + GEMM_MAP_A_SLACK, WM_ERR_INVALID,
+                   "wmdbg_gemm_mapped: A row %lld reads [%lld, %lld) past a_elems %lld + slack", (long long)m, (long long)off,
+                   (long long)(off + g.K), (long long)g.a_elems);
+    }
+    // ---- the epilogue's own geometry
+    if (g.epi == EPI_XKV || g.epi == EPI_QKV_ENC) {
+        WM_REQUIRE(g.batch >= 1 && g.seq >= 1 && g.n_head >= 1 && g.d_model == 64 * g.n_head && (int64_t)g.batch * g.seq == g.M,
+                   WM_ERR_INVALID, "wmdbg_gemm_mapped: need M == batch * seq and d_model == 64 * n_head");
+    }
+    if (g.epi == EPI_XKV) {
+        WM_REQUIRE(g.N == 2 * g.d_model, WM_ERR_INVALID, "wmdbg_gemm_mapped: EPI_XKV needs N == 2 * d_model");
+        WM_REQUIRE(g.c_elems == (int64_t)2 * g.batch * g.n_head * g.seq * 64, WM_ERR_INVALID,
+                   "wmdbg_gemm_mapped: EPI_XKV needs c_elems == 2 * batch * n_head * seq * 64");
+        WM_REQUIRE(g.c_elems <= GEMM_MAP_MAX_ELEMS, WM_ERR_INVALID, "wmdbg_gemm_mapped: C too large");
+        return WM_OK;   // (the scatter does not use the C row map)
+    }
+    int64_t width = g.N;   // columns of a C row that the epilogue writes
+    if (g.epi == EPI_QKV_ENC) {
+        WM_REQUIRE(vt, WM_ERR_INVALID, "wmdbg_gemm_mapped: EPI_QKV_ENC needs vt");
+        WM_REQUIRE(g.N == 3 * g.d_model, WM_ERR_INVALID, "wmdbg_gemm_mapped: EPI_QKV_ENC needs N == 3 * d_model");
+        WM_REQUIRE(g.seq_pad % 16 == 0 && g.seq_pad >= g.seq, WM_ERR_INVALID,
+                   "wmdbg_gemm_mapped: EPI_QKV_ENC needs seq_pad %% 16 == 0 and seq_pad >= seq");
+        WM_REQUIRE(g.vt_elems == (int64_t)g.batch * g.n_head * 64 * g.seq_pad && g.vt_elems <= GEMM_MAP_MAX_ELEMS, WM_ERR_INVALID,
+                   "wmdbg_gemm_mapped: EPI_QKV_ENC needs vt_elems == batch * n_head * 64 * seq_pad");
+        width = 2 * g.d_model;
+    }
+    WM_REQUIRE(g.c_rpb >= 1 && g.c_rpb <= 0x7fffffffLL && g.c_off >= 0 && g.c_bstride >= 0 && g.c_elems >= 1 &&
+                   g.c_elems <= GEMM_MAP_MAX_ELEMS && g.c_rstride <= GEMM_MAP_MAX_ELEMS && g.c_bstride <= GEMM_MAP_MAX_ELEMS,
+               WM_ERR_INVALID, "wmdbg_gemm_mapped: bad C map");
+    WM_REQUIRE(g.c_rstride >= width && (g.M <= g.c_rpb || g.c_bstride >= g.c_rpb * g.c_rstride), WM_ERR_INVALID,
+               "wmdbg_gemm_mapped: C rows overlap (c_rstride >= N, c_bstride >= c_rpb * c_rstride)");
+    if (g.N % 64 == 0) {   // the staged epilogues store 16 bytes per lane
+        const int al = (g.epi == EPI_RESID_F32 || g.epi == EPI_CONV2_F32 || g.epi == EPI_F32) ? 4 : 8;
+        WM_REQUIRE(g.c_off % al == 0 && g.c_bstride % al == 0 && g.c_rstride % al == 0, WM_ERR_INVALID,
+                   "wmdbg_gemm_mapped: C map not 16-byte aligned");
+    }
+    for (int64_t m = 0; m < g.M; ++m) {
+        const int64_t off = g.c_off + (m / g.c_rpb) * g.c_bstride + (m % g.c_rpb) * g.c_rstride;
+        WM_REQUIRE(off + width <= g.c_elems, WM_ERR_INVALID, "wmdbg_gemm_mapped: C row %lld writes [%lld, %lld) past c_elems %lld",
+                   (long long)m, (long long)off, (long long)(off + width), (long long)g.c_elems);
+    }
+    if (g.epi == EPI_CONV2_F32) {
+        WM_REQUIRE(pos, WM_ERR_INVALID, "wmdbg_gemm_mapped: EPI_CONV2_F32 needs pos [c_rpb][N]");
+        WM_REQUIRE(g.c_rpb * g.N <= GEMM_MAP_MAX_ELEMS, WM_ERR_INVALID, "wmdbg_gemm_mapped: pos too large");
+    }
+    return WM_OK;
+}
+
+void fill_bf16(std::vector<bf16_t> &v, size_t n) { v.assign(n, (bf16_t)WMDBG_SENTINEL_BF16); }
+void fill_f32(std::vector<float> &v, size_t n) {
+    const uint32_t u = WMDBG_SENTINEL_F32;
+    float f;
+    memcpy(&f, &u, 4);
+    v.assign(n, f);
+}
+// device bf16 -> host f32 (widened), synchronous
+int down_bf16(const void *d, size_t n, float *out, hipStream_t s) {
+    std::vector<bf16_t> t(n);
+    WM_HIP(hipMemcpyAsync(t.data(), d, n * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    from_bf16(t, out);
+    return WM_OK;
+}
+}  // namespace
+
+extern "C" int wmdbg_gemm_mapped(wm_ctx *ctx, const wmdbg_gemm_map *map, const float *A, const float *W, const float *bias,
+                                 const float *pos, float *C, float *vt) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(map, WM_ERR_INVALID, "wmdbg_gemm_mapped: null map");
+    const wmdbg_gemm_map g = *map;
+    WM_TRY(gemm_map_check(g, A, W, pos, C, vt));
+    const bool f32out = g.epi == EPI_F32 || g.epi == EPI_RESID_F32 || g.epi == EPI_CONV2_F32;
+    std::vector<bf16_t> a16, w16, c16, vt16;
+    std::vector<float> c32;
+    to_bf16(A, a16, (size_t)g.a_elems);
+    to_bf16(W, w16, (size_t)g.N * g.K);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dA, *dW, *dB = nullptr, *dP = nullptr, *dC, *dVt = nullptr;
+    WM_TRY(pool.get(&dA, a16.data(), a16.size() * 2, s));
+    WM_TRY(pool.get(&dW, w16.data(), w16.size() * 2, s));
+    if (bias) WM_TRY(pool.get(&dB, bias, (size_t)g.N * 4, s));
+    if (g.epi == EPI_CONV2_F32) WM_TRY(pool.get(&dP, pos, (size_t)g.c_rpb * g.N * 4, s));
+    if (g.epi == EPI_RESID_F32) {
+        WM_TRY(pool.get(&dC, C, (size_t)g.c_elems * 4, s));   // in / out
+    } else if (f32out) {
+        fill_f32(c32, (size_t)g.c_elems);
+        WM_TRY(pool.get(&dC, c32.data(), c32.size() * 4, s));
+    } else {
+        fill_bf16(c16, (size_t)g.c_elems);
+        WM_TRY(pool.get(&dC, c16.data(), c16.size() * 2, s));
+    }
+    if (g.epi == EPI_QKV_ENC) {
+        fill_bf16(vt16, (size_t)g.vt_elems);
+        WM_TRY(pool.get(&dVt, vt16.data(), vt16.size() * 2, s));
+    }
+    GemmArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.A = (const bf16_t *)dA + g.a_off; ga.a_rpb = (long)g.a_rpb; ga.a_bstride = (long)g.a_bstride; ga.a_rstride = (long)g.a_rstride;
+    ga.W = (const bf16_t *)dW; ga.bias = (const float *)dB;
+    ga.C = f32out ? (void *)((float *)dC + g.c_off) : (void *)((bf16_t *)dC + g.c_off);
+    ga.c_rpb = (long)g.c_rpb; ga.c_bstride = (long)g.c_bstride; ga.c_rstride = (long)g.c_rstride;
+    ga.M = g.M; ga.N = g.N; ga.K = g.K; ga.epi = g.epi;
+    ga.pos = (const float *)dP; ga.vt = (bf16_t *)dVt;
+    ga.d_model = g.d_model; ga.n_head = g.n_head; ga.seq = g.seq; ga.seq_pad = g.seq_pad; ga.batch = g.batch;
+    if (g.epi == EPI_XKV) { ga.C = dC; ga.c_rpb = (long)g.M + 1; }   // (the scatter ignores the C map; wm_gemm wants c_rpb > 0)
+    WM_TRY(wm_gemm(ctx, ga));
+    if (f32out) {
+        WM_HIP(hipMemcpyAsync(C, dC, (size_t)g.c_elems * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    } else {
+        WM_TRY(down_bf16(dC, (size_t)g.c_elems, C, s));
+    }
+    if (g.epi == EPI_QKV_ENC) WM_TRY(down_bf16(dVt, (size_t)g.vt_elems, vt, s));
+    return WM_OK;
+}
+
+// ------------------------------------------------------------------ the product's own encoder-side launches on a loaded model
+namespace {
+int model_ready(wm_ctx *ctx, int B, const char *who) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(ctx->model && ctx->model->finalized, WM_ERR_STATE, "%s: model weights not finalised (wm_finalize)", who);
+    WM_REQUIRE(B >= 1 && B <= 16, WM_ERR_INVALID, "%s: B must be 1..16", who);
+    return wm_model_reserve(ctx, B);
+}
+}  // namespace
+
+extern "C" int wmdbg_encode_stem(wm_ctx *ctx, const float *mel, const int64_t *wins, int B, float *mel_t_out, float *h1p_out,
+                                 float *x_out) {
+    WM_REQUIRE(mel && mel_t_out && h1p_out && x_out, WM_ERR_INVALID, "wmdbg_encode_stem: null pointer");
+    WM_TRY(model_ready(ctx, B, "wmdbg_encode_stem"));
+    WmModel *m = ctx->model;
+    const int C = m->dims.n_mels, d = m->dims.n_audio_state;
+    size_t mel_elems = (size_t)B * C * WM_N_FRAMES;
+    std::vector<WmMelWin> win;
+    if (wins) {   // every read of the window kernel: mel[base + c * T + seek + t], c < C, t < n
+        mel_elems = 0;
+        win.resize(B);
+        for (int b = 0; b < B; ++b) {
+            const int64_t base = wins[b * 4], T = wins[b * 4 + 1], seek = wins[b * 4 + 2], n = wins[b * 4 + 3];
+            WM_REQUIRE(base >= 0 && base <= ((int64_t)1 << 28) && T >= 1 && T <= (1 << 22) && seek >= 0 && n >= 0 && n <= WM_N_FRAMES &&
+                           seek + n <= T,
+                       WM_ERR_INVALID, "wmdbg_encode_stem: window %d (base %lld, T %lld, seek %lld, n %lld) leaves its block", b,
+                       (long long)base, (long long)T, (long long)seek, (long long)n);
+            win[b].base = base; win[b].T = (int)T; win[b].seek = (int)seek; win[b].n = (int)n; win[b].pad = 0;
+            mel_elems = std::max(mel_elems, (size_t)(base + (int64_t)C * T));
+        }
+    }
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dmel, *dwin = nullptr;
+    WM_TRY(pool.get(&dmel, mel, mel_elems * 4, s));
+    if (wins) WM_TRY(pool.get(&dwin, win.data(), win.size() * sizeof(WmMelWin), s));
+    // sentinels in everything the three launches must write; the guard rows (mel_t rows 0 and 3001, h1p row 0) stay as the
+    // allocation left them
+    std::vector<bf16_t> s16;
+    std::vector<float> s32;
+    fill_bf16(s16, (size_t)3000 * std::max(C, d));
+    fill_f32(s32, (size_t)B * 1500 * d);
+    for (int b = 0; b < B; ++b) {
+        WM_HIP(hipMemcpyAsync(m->mel_t + ((size_t)b * 3002 + 1) * C, s16.data(), (size_t)3000 * C * 2, hipMemcpyHostToDevice, s));
+        WM_HIP(hipMemcpyAsync(m->h1p + ((size_t)b * 3001 + 1) * d, s16.data(), (size_t)3000 * d * 2, hipMemcpyHostToDevice, s));
+    }
+    WM_HIP(hipMemcpyAsync(m->x, s32.data(), s32.size() * 4, hipMemcpyHostToDevice, s));
+    WM_TRY(wm_model_encode_stem(ctx, (const float *)dmel, (const WmMelWin *)dwin, B));
+    WM_TRY(down_bf16(m->mel_t, (size_t)B * 3002 * C, mel_t_out, s));
+    WM_TRY(down_bf16(m->h1p, (size_t)B * 3001 * d, h1p_out, s));
+    WM_HIP(hipMemcpyAsync(x_out, m->x, (size_t)B * 1500 * d * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
+extern "C" int wmdbg_encode_layer_qkv(wm_ctx *ctx, int layer, const float *x, int B, float *xn_out, float *qk_out, float *vt_out) {
+    WM_REQUIRE(x && xn_out && qk_out && vt_out, WM_ERR_INVALID, "wmdbg_encode_layer_qkv: null pointer");
+    WM_TRY(model_ready(ctx, B, "wmdbg_encode_layer_qkv"));
+    WmModel *m = ctx->model;
+    WM_REQUIRE(layer >= 0 && layer < m->dims.n_audio_layer, WM_ERR_INVALID, "wmdbg_encode_layer_qkv: layer %d out of range", layer);
+    const int d = m->dims.n_audio_state, H = m->dims.n_audio_head;
+    const size_t M = (size_t)B * 1500, vt_n = (size_t)B * H * 64 * 1536;
+    hipStream_t s = ctx->stream;
+    std::vector<bf16_t> s16;
+    fill_bf16(s16, std::max(vt_n, M * 2 * d));
+    WM_HIP(hipMemcpyAsync(m->x, x, M * d * 4, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->xn, s16.data(), M * d * 2, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->qk, s16.data(), M * 2 * d * 2, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->vt, s16.data(), vt_n * 2, hipMemcpyHostToDevice, s));
+    int rc = wm_model_encode_layer_qkv(ctx, layer, B);
+    if (rc == WM_OK) rc = down_bf16(m->xn, M * d, xn_out, s);
+    if (rc == WM_OK) rc = down_bf16(m->qk, M * 2 * d, qk_out, s);
+    if (rc == WM_OK) rc = down_bf16(m->vt, vt_n, vt_out, s);
+    // the pad columns 1500 .. 1535 of vt are zero in the product (zeroed at allocation, never written): as a later encode expects
+    WM_HIP(hipMemsetAsync(m->vt, 0, vt_n * 2, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return rc;
+}
+
+extern "C" int wmdbg_cross_kv(wm_ctx *ctx, const float *xa, int B, float *xkv_out) {
+    WM_REQUIRE(xa && xkv_out, WM_ERR_INVALID, "wmdbg_cross_kv: null pointer");
+    WM_TRY(model_ready(ctx, B, "wmdbg_cross_kv"));
+    WmModel *m = ctx->model;
+    const wm_dims &D = m->dims;
+    WM_REQUIRE(D.n_text_state == D.n_audio_state, WM_ERR_INVALID, "wmdbg_cross_kv: encoder and decoder widths differ");
+    const int d = D.n_text_state, H = D.n_text_head;
+    const size_t M = (size_t)B * 1500, used = (size_t)D.n_text_layer * 2 * B * H * 1500 * 64,
+                 cap = (size_t)D.n_text_layer * 2 * m->cap_b * H * 1500 * 64;   // the whole allocation (wm_model_reserve)
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dxa;
+    WM_TRY(pool.get(&dxa, xa, M * d * 4, s));
+    std::vector<bf16_t> s16, got(cap);
+    fill_bf16(s16, cap);
+    WM_HIP(hipMemcpyAsync(m->xkv, s16.data(), cap * 2, hipMemcpyHostToDevice, s));
+    int rc = wm_model_set_xa(ctx, (const float *)dxa, B);
+    if (rc == WM_OK) rc = wm_model_cross_kv(ctx, B);
+    WM_HIP(hipMemcpyAsync(got.data(), m->xkv, cap * 2, hipMemcpyDeviceToHost, s));
+    if (cap > used) WM_HIP(hipMemsetAsync(m->xkv + used, 0, (cap - used) * 2, s));
+    WM_HIP(hipStreamSynchronize(s));
+    WM_TRY(rc);
+    size_t disturbed = 0;
+    for (size_t i = used; i < cap; ++i) disturbed += got[i] != (bf16_t)WMDBG_SENTINEL_BF16;
+    WM_REQUIRE(disturbed == 0, WM_ERR_STATE, "wmdbg_cross_kv: %zu elements behind the %d chunks' cache were written", disturbed, B);
+    got.resize(used);
+    from_bf16(got, xkv_out);
+    return WM_OK;
+}

@@ -651,13 +651,15 @@ int wm_model_encode_dev(wm_ctx *ctx, const float *d_mel, int B, float *d_xa_out)
     return wm_model_encode_win(ctx, d_mel, nullptr, B, d_xa_out);
 }
 
-int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out) {
+// The stem: mel re-layout, conv1, conv2 (+ positional embedding) -> m->x.  Its own function so that the debug library can run
+// exactly these three launches on a loaded model (wmdbg_encode_stem).
+int wm_model_encode_stem(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B) {
     WmModel *m = ctx->model;
     WM_REQUIRE(m && m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
     WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B must be >= 1");
     WM_TRY(wm_model_reserve(ctx, B));
     const wm_dims &D = m->dims;
-    const int d = D.n_audio_state, H = D.n_audio_head, S = 1500, C = D.n_mels;
+    const int d = D.n_audio_state, S = 1500, C = D.n_mels;
     const int M = B * S;
     // mel [B][C][3000] f32 (or the windows d_win) -> time-major bf16 with zero edge rows (conv padding = 1)
     WM_TRY(wm_mel_to_time_major(ctx, d_mel, B, C, m->mel_t, d_win));
@@ -679,12 +681,31 @@ int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, 
         g.M = M; g.N = d; g.K = 3 * d; g.epi = EPI_CONV2_F32; g.pos = m->enc_pos;
         WM_TRY(wm_gemm(ctx, g));
     }
+    return WM_OK;
+}
+
+// One encoder layer's first two launches: LayerNorm of the residual stream m->x into m->xn, then the QKV product (queries
+// pre-scaled and keys into m->qk, values transposed into m->vt).  (Also run on its own by wmdbg_encode_layer_qkv.)
+int wm_model_encode_layer_qkv(wm_ctx *ctx, int layer, int B) {
+    WmModel *m = ctx->model;
+    const wm_dims &D = m->dims;
+    const int d = D.n_audio_state, H = D.n_audio_head, S = 1500, M = B * S;
+    const EncLayerW &L = m->enc[layer];
+    WM_TRY(wm_layernorm(ctx, m->x, L.ln1_g, L.ln1_b, M, d, m->xn, nullptr));
+    GemmArgs g = plain_gemm(m->xn, d, L.wqkv, L.bqkv, m->qk, 2 * d, M, 3 * d, d, EPI_QKV_ENC);
+    g.vt = m->vt; g.d_model = d; g.n_head = H; g.seq = S; g.seq_pad = 1536; g.batch = B;
+    return wm_gemm(ctx, g);
+}
+
+int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out) {
+    WM_TRY(wm_model_encode_stem(ctx, d_mel, d_win, B));
+    WmModel *m = ctx->model;
+    const wm_dims &D = m->dims;
+    const int d = D.n_audio_state, H = D.n_audio_head, S = 1500;
+    const int M = B * S;
     for (int i = 0; i < D.n_audio_layer; ++i) {
         const EncLayerW &L = m->enc[i];
-        WM_TRY(wm_layernorm(ctx, m->x, L.ln1_g, L.ln1_b, M, d, m->xn, nullptr));
-        GemmArgs g = plain_gemm(m->xn, d, L.wqkv, L.bqkv, m->qk, 2 * d, M, 3 * d, d, EPI_QKV_ENC);
-        g.vt = m->vt; g.d_model = d; g.n_head = H; g.seq = S; g.seq_pad = 1536; g.batch = B;
-        WM_TRY(wm_gemm(ctx, g));
+        WM_TRY(wm_model_encode_layer_qkv(ctx, i, B));
         WM_TRY(wm_enc_attention(ctx, m->qk, m->vt, m->att, B, H, S, 1536, d));
         WM_TRY(wm_gemm(ctx, plain_gemm(m->att, d, L.wo, L.bo, m->x, d, M, d, d, EPI_RESID_F32)));
         WM_TRY(wm_layernorm(ctx, m->x, L.ln2_g, L.ln2_b, M, d, m->xn, nullptr));

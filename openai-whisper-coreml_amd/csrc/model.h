@@ -411,6 +411,10 @@ int wm_model_finalize(wm_ctx *ctx);
 int wm_model_encode_dev(wm_ctx *ctx, const float *d_mel, int B, float *d_xa_out /*nullable*/);
 // the same with row b's input the mel window d_win[b] (device, nullable: wm_model_encode_dev)
 int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out /*nullable*/);
+// the two parts of wm_model_encode_win that the debug library also runs on their own: the stem (mel re-layout, conv1, conv2 ->
+// m->x) and one layer's LayerNorm + QKV launch (m->x -> m->xn, m->qk, m->vt)
+int wm_model_encode_stem(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B);
+int wm_model_encode_layer_qkv(wm_ctx *ctx, int layer, int B);
 int wm_model_cross_kv(wm_ctx *ctx, int B);                 // from m->xn (bf16 encoder output)
 int wm_model_set_xa(wm_ctx *ctx, const float *d_xa, int B);  // f32 xa -> m->xn (bf16)
 int wm_model_decode_begin(wm_ctx *ctx, int B);
