@@ -446,6 +446,18 @@ WM_API int wm_windows_detect_language(wm_ctx *ctx, const wm_windows *w, const in
  * host.  Out-of-range pairs and duplicates are invalid.  Same inheritance as wm_set_suppress. */
 WM_API int wm_set_alignment_heads(wm_ctx *ctx, const int32_t *layers, const int32_t *heads, int n);
 
+/* Positions per decoder step of the TEACHER-FORCED passes: wm_align, wm_align_mel, wm_align_windows and wm_decode_logits
+ * (every token of such a pass is known up front).  With width w a step carries w consecutive positions of every window: the
+ * pass runs ceil(T / w) steps of up to WM_DEC_MAXB = 128 rows instead of T steps of B rows, streams the decoder weights once
+ * per w positions and reads a window's cross-attention K/V once per step for all w of them.
+ *   width : 1 .. WM_MAX_TEACHER_PANEL; 1 (the default) enqueues exactly the launches the pass always enqueued.
+ * A LAUNCH POLICY, NOT A NUMERICS SWITCH: every output of these calls (start frames, token probabilities, logits) is
+ * bit-identical for every width -- a row's arithmetic is the one-position step's, only the rows that share a launch change.
+ * The transcribe entries and wm_detect_language* are not affected.  WM_ERR_INVALID: width outside the range.  Same
+ * inheritance as wm_set_suppress (later wm_clone's and the lanes of a call take the setting over). */
+#define WM_MAX_TEACHER_PANEL 8   /* = WM_MAX_BEST_OF: the widths the shared cross-attention read is built for */
+WM_API int wm_set_teacher_panel(wm_ctx *ctx, int width);
+
 /* Decode groups a wm_transcribe_greedy call on this context keeps in flight.
  *   0 (default): the library's own measured policy -- one group below 32 chunks, two groups (two weight-sharing lanes)
  *                up to 143, three from 144 chunks, never more than $WM_LANES (default 3) at once; for the NARROW models

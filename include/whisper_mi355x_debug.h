@@ -181,6 +181,39 @@ WM_API int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, cons
 WM_API int wmdbg_dec_self_attention_off(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int T,
                                         int pos, const int32_t *off, float *out);
 
+/* ---- teacher-forced panels (wm_set_teacher_panel): the panel launches of a step alone, on host data.  A panel is C windows x
+ * w consecutive positions pos .. pos + w - 1, row r = c * w + s; 1 <= w <= WM_MAX_TEACHER_PANEL, C * w <= WM_DEC_MAXB. ---- */
+/* The self-attention launch of a panel step: q f32 [C * w][H * 64], k / v f32 [C][H][T][64] (rounded to bf16; window c's entry
+ * already holds positions 0 .. pos + w - 1), row (c, s) attends to rows [0, pos + s] of entry c.  out f32 [out_rows][H * 64],
+ * out_rows a multiple of 16 and >= C * w: the bf16 head outputs widened; the device buffer is pre-filled with the bf16 bit
+ * pattern WMDBG_SENTINEL_BF16, which rows >= C * w must still hold. */
+WM_API int wmdbg_dec_self_attention_panel(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int w, int H,
+                                          int T, int pos, int out_rows, float *out);
+/* wmdbg_dec_gemv_ln's DE_QKV launch (centre = 1) with the panel epilogue: x f32 [C * w][K]; q_out f32 [C * w][N / 3];
+ * kcache / vcache f32 [C][n_head][T][64], pre-filled with WMDBG_SENTINEL_BF16: row (c, s) appends at position pos + s of entry c. */
+WM_API int wmdbg_dec_qkv_panel(wm_ctx *ctx, const float *x, const float *ln_g, const float *ln_b, const float *W,
+                               const float *bias, int C, int w, int N, int K, int n_head, int T, int pos, float *q_out,
+                               float *kcache, float *vcache);
+/* The panel embedding: emb f32 [V][d] (rounded to bf16), pemb f32 [n_ctx][d], seq i32 [n_ctx][stride] (position-major), the
+ * panel's windows are columns c0 .. c0 + C - 1.  Out, per row r: x f32 [C * w][d], xb f32 [C * w][d] (the mean-centred bf16
+ * copy widened), stats f32 [C * w][d / 16][2] (the row's LayerNorm partials), mean f32 [C * w].  by_steps != 0: the same rows
+ * from the STEP path's launches, position by position over the C windows (wm_dec_embed at position 0, the teacher-forced
+ * close wm_argmax_embed afterwards). */
+WM_API int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
+                                 int stride, int c0, int C, int w, int pos, int by_steps, float *x, float *xb, float *stats,
+                                 float *mean);
+/* The query capture of an alignment layer in a panel step: dq f32 [C * w][d], the layer's n_heads heads into slots slot0 .. of
+ * cap f32 [C][Tq][J][64], pre-filled with the NaN bits WMDBG_SENTINEL_F32 (rows at positions >= Tq are not captured).
+ * by_steps != 0: w step launches over the C windows instead. */
+WM_API int wmdbg_align_capture_panel(wm_ctx *ctx, const float *dq, int d, int C, int w, int pos, const int32_t *heads,
+                                     int n_heads, int slot0, int Tq, int J, int by_steps, float *cap);
+/* The token-probability launch of a panel step: logits f32 [C * w][ldo], seq i32 [n_ctx][C] (ids < eot), chunk c has n_text[c]
+ * text tokens at positions S .. S + n_text[c] - 1; prob f32 [C][max_text], pre-filled with WMDBG_SENTINEL_F32 -- a row writes
+ * only when its own position is one of its chunk's text positions.  by_steps != 0: w step launches instead. */
+WM_API int wmdbg_align_token_prob_panel(wm_ctx *ctx, const float *logits, int C, int w, int V, int ldo, const int32_t *seq,
+                                        int n_ctx, int pos, int S, int eot, const int32_t *n_text, int max_text, int by_steps,
+                                        float *prob);
+
 /* ---- micro-benchmarks: average microseconds per launch over `iters` back-to-back launches
  * that cycle over n_mats weight matrices / n_slices cache slices (defeats L2 / MALL reuse). */
 WM_API int wmdbg_bench_dec_gemv(wm_ctx *ctx, int B, int N, int K, int ln, int resid, int n_mats, int iters,

@@ -682,6 +682,7 @@ class wm_vad_params(ctypes.Structure):
 
 
 VAD_SMOOTH = 5             # frames of the moving average transcribe_long(vad=True) asks wm_vad_energy for
+MAX_TEACHER_PANEL = 8      # WM_MAX_TEACHER_PANEL: positions per decoder step of a teacher-forced pass (Context.set_teacher_panel)
 PARALLEL_CLIPS_TRUE = 56   # parallel_clips=True: the decode-group size of the bench headline
 
 
@@ -865,6 +866,10 @@ class _LongOptions(types.SimpleNamespace):
                 raise ValueError("hallucination_silence_threshold: finite seconds >= 0")
             if not self.words_on:
                 raise ValueError("hallucination_silence_threshold needs word_timestamps")
+        if self.teacher_panel is not None:
+            if isinstance(self.teacher_panel, bool) or int(self.teacher_panel) != self.teacher_panel or not 1 <= self.teacher_panel <= MAX_TEACHER_PANEL:
+                raise ValueError("teacher_panel: None or a width 1 .. %d" % MAX_TEACHER_PANEL)
+        self.panel_pending = self.teacher_panel is not None   # set on the context in front of the first alignment call
         if self.prepend_punctuations is None:
             self.prepend_punctuations = PREPEND_PUNCTUATIONS
         if self.append_punctuations is None:
@@ -1120,7 +1125,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
-                    repetition_penalty=None, no_repeat_ngram_size=None):
+                    repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1217,6 +1222,10 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        log-mel, hold for every decode call of the run -- greedy, sampled, best-of, beam, from windows --, and are cleared
        again when the function leaves, also on an exception.  They act on a row's generated tokens only, so the prompts of
        5 and 12 are never penalised.  With both None the function makes exactly the calls it made before they existed.
+    16. teacher_panel (None; 1 .. 8): with word_timestamps, Context.set_teacher_panel(teacher_panel) is called ONCE, in front of
+       the run's first alignment call, and stays set on the context: the teacher-forced pass of every alignment then carries
+       that many positions per decoder step (wm_set_teacher_panel: a launch policy, the words are the same bit for bit).  A
+       value outside 1 .. 8 is a ValueError before any library call.  None makes no call.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1277,6 +1286,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     u.commit(o, *window_segments(tokens, u.seek, sizes[i], timestamp_begin, eot, result, vocab),
                              result["temperature"])
             if kept:
+                if o.panel_pending:   # 16.
+                    ctx.set_teacher_panel(int(teacher_panel))
+                    o.panel_pending = False
                 _long_word_step(o, source, live, sizes, kept, res)
         for u in units:
             u.deliver(out[u.rec])
@@ -1631,6 +1643,14 @@ class Context:
         self.lib.wm_set_timestamp_rules.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
                                                     ctypes.c_int32]
         _check(self.lib, self.lib.wm_set_timestamp_rules(self.handle, 1 if enable else 0, timestamp_begin, eot, max_initial))
+
+    def set_teacher_panel(self, n):
+        """wm_set_teacher_panel: positions per decoder step (1 .. MAX_TEACHER_PANEL; 1 = the default) of the teacher-forced passes
+        of align / align_mel / align_windows / decode_logits on this context, later clones and the lanes of a call.  A launch
+        policy: the results are bit-identical for every width."""
+        self.lib.wm_set_teacher_panel.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.lib.wm_set_teacher_panel.restype = ctypes.c_int
+        _check(self.lib, self.lib.wm_set_teacher_panel(self.handle, int(n)))
 
     def set_repetition_rules(self, penalty=1.0, no_repeat_ngram_size=0, eot=0):
         """The repetition rules of every transcribe call on this context (wm_set_repetition_rules): `penalty` (> 0, 1.0 = off)

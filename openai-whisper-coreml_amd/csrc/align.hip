@@ -69,21 +69,38 @@ __device__ __forceinline__ void lse_merge(float &m, float &s, float m2, float s2
     m = mm;
 }
 
+// PANEL (a teacher-forced panel step, wm_set_teacher_panel): dq row r is position *pos_ptr + r % w of chunk r / w; the capture
+// layout is unchanged.  Instantiations of their own, here and in the token-probability kernel: the step kernels stay as they were.
+template <bool PANEL>
 __global__ __launch_bounds__(64) void align_capture_kernel(const float *__restrict__ dq, int d, const int *__restrict__ pos_ptr,
-                                                           WmAlignLayer L, float *__restrict__ cap, int Tq, int J) {
-    const int b = blockIdx.x, k = blockIdx.y, pos = *pos_ptr;
+                                                           WmAlignLayer L, float *__restrict__ cap, int Tq, int J, int w) {
+    const int r = blockIdx.x, k = blockIdx.y;
+    int b = r, pos = *pos_ptr;
+    if constexpr (PANEL) {
+        b = r / w;
+        pos += r - b * w;
+    }
     if (pos >= Tq) return;
-    cap[(((size_t)b * Tq + pos) * J + L.slot0 + k) * 64 + threadIdx.x] = dq[(size_t)b * d + L.head[k] * 64 + threadIdx.x];
+    cap[(((size_t)b * Tq + pos) * J + L.slot0 + k) * 64 + threadIdx.x] = dq[(size_t)r * d + L.head[k] * 64 + threadIdx.x];
 }
 
+// B: chunks per position of seq.  PANEL: logits row r is position *pos_ptr + r % w of chunk r / w, and the row takes a
+// probability only when ITS position is one of the chunk's text positions.
+template <bool PANEL>
 __global__ __launch_bounds__(256) void align_token_prob_kernel(const float *__restrict__ logits, long ldo,
                                                                const int *__restrict__ seq, const int *__restrict__ pos_ptr,
                                                                int B, int S, int eot, const int *__restrict__ n_text,
-                                                               float *__restrict__ prob, int max_text) {
+                                                               float *__restrict__ prob, int max_text, int w) {
     __shared__ float red[4];
-    const int b = blockIdx.x, pos = *pos_ptr, i = pos - S, tid = threadIdx.x;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    int b = r, pos = *pos_ptr;
+    if constexpr (PANEL) {
+        b = r / w;
+        pos += r - b * w;
+    }
+    const int i = pos - S;
     if (i < 0 || i >= n_text[b]) return;
-    const float *row = logits + (long)b * ldo;
+    const float *row = logits + (long)r * ldo;
     float m = -INFINITY;
     for (int v = tid; v < eot; v += 256) m = fmaxf(m, row[v]);
 #pragma unroll
@@ -375,18 +392,23 @@ __global__ __launch_bounds__(64) void dtw_kernel(const float *__restrict__ x, lo
 }  // namespace
 
 int wm_align_capture_q(wm_ctx *ctx, const float *dq, int d, int B, const WmAlignLayer &L, float *cap, int Tq, int J,
-                       const int *pos_ptr) {
+                       const int *pos_ptr, int panel) {
     if (L.n <= 0) return WM_OK;
+    WM_REQUIRE(panel >= 1 && panel <= WM_MAX_TEACHER_PANEL && B % panel == 0, WM_ERR_INVALID, "align_capture: %d rows in panels of %d", B, panel);
     WmProfScope ps(&ctx->prof, "align_capture", ctx->stream);
-    align_capture_kernel<<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J);
+    if (panel > 1) align_capture_kernel<true><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, panel);
+    else align_capture_kernel<false><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, 1);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
 
 int wm_align_token_prob(wm_ctx *ctx, const float *logits, long ldo, const int *seq, const int *pos_ptr, int B, int S, int eot,
-                        const int *n_text, float *prob, int max_text) {
+                        const int *n_text, float *prob, int max_text, int panel, int seq_stride) {
+    WM_REQUIRE(panel >= 1 && panel <= WM_MAX_TEACHER_PANEL && B % panel == 0, WM_ERR_INVALID, "align_token_prob: %d rows in panels of %d", B, panel);
     WmProfScope ps(&ctx->prof, "align_token_prob", ctx->stream);
-    align_token_prob_kernel<<<B, 256, 0, ctx->stream>>>(logits, ldo, seq, pos_ptr, B, S, eot, n_text, prob, max_text);
+    const int stride = seq_stride > 0 ? seq_stride : B / panel;
+    if (panel > 1) align_token_prob_kernel<true><<<B, 256, 0, ctx->stream>>>(logits, ldo, seq, pos_ptr, stride, S, eot, n_text, prob, max_text, panel);
+    else align_token_prob_kernel<false><<<B, 256, 0, ctx->stream>>>(logits, ldo, seq, pos_ptr, stride, S, eot, n_text, prob, max_text, 1);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

@@ -30,7 +30,7 @@ extern "C" int wmdbg_set_tuning(const char *key, int value) {
         {"gemm_tile", &g_wm_tuning.gemm_tile}, {"gemm128_pipe", &g_wm_tuning.gemm128_pipe}, {"gemm_gm", &g_wm_tuning.gemm_gm}, {"no_early_stop", &g_wm_tuning.no_early_stop},
         {"xattn_no_deep", &g_wm_tuning.xattn_no_deep}, {"xattn_never_short", &g_wm_tuning.xattn_never_short},         {"logits_tn", &g_wm_tuning.logits_tn}, {"enc_attn_mfma_sum", &g_wm_tuning.enc_attn_mfma_sum},
         {"group_chunks", &g_wm_tuning.group_chunks}, {"argmax_rows_per_wg", &g_wm_tuning.argmax_rows_per_wg}, {"xattn_fuse_q", &g_wm_tuning.xattn_fuse_q},
-        {"lane_parts", &g_wm_tuning.lane_parts}, {"lane_solo_cus", &g_wm_tuning.lane_solo_cus}, {"frontend_per_wave_twiddles", &g_wm_tuning.frontend_per_wave_twiddles},
+        {"teacher_panel_cut", &g_wm_tuning.teacher_panel_cut}, {"lane_parts", &g_wm_tuning.lane_parts}, {"lane_solo_cus", &g_wm_tuning.lane_solo_cus}, {"frontend_per_wave_twiddles", &g_wm_tuning.frontend_per_wave_twiddles},
     };
     if (strcmp(key, "reset") == 0) { g_wm_tuning = WmTuning(); return WM_OK; }
     for (auto &e : table)
@@ -1055,10 +1055,13 @@ void stage_ln_rows(const float *x, int B, int K, bool centre, std::vector<bf16_t
 }
 }  // namespace
 
-extern "C" int wmdbg_dec_gemv_ln(wm_ctx *ctx, int epi, const float *x, const float *ln_g, const float *ln_b, const float *W,
-                                 const float *bias, int B, int N, int K, int centre, int n_head, int T, int pos, float *out_f32,
-                                 float *out_bf16, float *kcache, float *vcache, float *mean_out, float *Wf, float *c1, float *c2) {
+// panel: 0 = the step epilogues; w >= 1 (DE_QKV only) = the panel epilogue DE_QKV_P, caches [ceil(B / w)][n_head][T][64]
+static int dec_gemv_ln_run(wm_ctx *ctx, int epi, const float *x, const float *ln_g, const float *ln_b, const float *W,
+                           const float *bias, int B, int N, int K, int centre, int n_head, int T, int pos, int panel, float *out_f32,
+                           float *out_bf16, float *kcache, float *vcache, float *mean_out, float *Wf, float *c1, float *c2) {
     WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(panel == 0 || (epi == DE_QKV && panel >= 1 && panel <= WM_MAX_TEACHER_PANEL && pos + panel <= T), WM_ERR_INVALID,
+               "wmdbg_dec_qkv_panel: width 1 .. %d, pos + width <= T", WM_MAX_TEACHER_PANEL);
     WM_REQUIRE(epi == DE_QKV || epi == DE_Q || epi == DE_GELU, WM_ERR_INVALID, "wmdbg_dec_gemv_ln: epilogue %d not exposed", epi);
     WM_REQUIRE(x && ln_g && ln_b && W && mean_out && Wf && c1 && c2, WM_ERR_INVALID, "wmdbg_dec_gemv_ln: null pointer");
     WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && N >= 1 && K >= 64 && K % 64 == 0 && K <= 1280, WM_ERR_INVALID,
@@ -1075,7 +1078,7 @@ extern "C" int wmdbg_dec_gemv_ln(wm_ctx *ctx, int epi, const float *x, const flo
     tile_bf16(W, (size_t)N, (size_t)K, w16);
     stage_ln_rows(x, B, K, centre != 0, x16, st, mean);
     const size_t n_f32 = epi == DE_QKV ? (size_t)B * d : epi == DE_Q ? (size_t)B * N : 0;
-    const size_t n_b16 = epi == DE_GELU ? Bpad * N : 0, n_cache = epi == DE_QKV ? (size_t)B * n_head * T * 64 : 0;
+    const size_t n_b16 = epi == DE_GELU ? Bpad * N : 0, n_cache = epi == DE_QKV ? (size_t)(panel ? (B + panel - 1) / panel : B) * n_head * T * 64 : 0;
     const std::vector<bf16_t> fill16(std::max(n_b16, n_cache), (bf16_t)WMDBG_SENTINEL_BF16);
     const std::vector<uint32_t> fill32((size_t)B, WMDBG_SENTINEL_F32);
     DevPool pool;
@@ -1109,6 +1112,7 @@ extern "C" int wmdbg_dec_gemv_ln(wm_ctx *ctx, int epi, const float *x, const flo
     a.mean_in = centre ? (const float *)dmin : nullptr; a.mean_out = (float *)dmout;
     a.out_f32 = (float *)dof; a.out_bf16 = (bf16_t *)dob; a.ldo = N;
     if (epi == DE_QKV) { a.kcache = (bf16_t *)dk; a.vcache = (bf16_t *)dv; a.pos_ptr = (const int *)dpos; a.n_ctx = T; a.n_head = n_head; }
+    if (panel) { a.epi = DE_QKV_P; a.panel = panel; }
     WM_TRY(wm_dec_gemv(ctx, a));
     std::vector<bf16_t> wf16(w16.size()), ob16(n_b16), k16(n_cache), v16(n_cache);
     WM_HIP(hipMemcpyAsync(wf16.data(), dWf, wf16.size() * 2, hipMemcpyDeviceToHost, s));
@@ -1125,6 +1129,228 @@ extern "C" int wmdbg_dec_gemv_ln(wm_ctx *ctx, int epi, const float *x, const flo
     untile_bf16(wf16, Npad, (size_t)K, Wf);
     if (n_b16) untile_bf16(ob16, (size_t)B, (size_t)N, out_bf16);
     if (n_cache) { from_bf16(k16, kcache); from_bf16(v16, vcache); }
+    return WM_OK;
+}
+
+extern "C" int wmdbg_dec_gemv_ln(wm_ctx *ctx, int epi, const float *x, const float *ln_g, const float *ln_b, const float *W,
+                                 const float *bias, int B, int N, int K, int centre, int n_head, int T, int pos, float *out_f32,
+                                 float *out_bf16, float *kcache, float *vcache, float *mean_out, float *Wf, float *c1, float *c2) {
+    return dec_gemv_ln_run(ctx, epi, x, ln_g, ln_b, W, bias, B, N, K, centre, n_head, T, pos, 0, out_f32, out_bf16, kcache, vcache,
+                           mean_out, Wf, c1, c2);
+}
+
+// ------------------------------------------------------------------ teacher-forced panels (wm_set_teacher_panel) ----
+extern "C" int wmdbg_dec_qkv_panel(wm_ctx *ctx, const float *x, const float *ln_g, const float *ln_b, const float *W,
+                                   const float *bias, int C, int w, int N, int K, int n_head, int T, int pos, float *q_out,
+                                   float *kcache, float *vcache) {
+    WM_REQUIRE(C >= 1 && w >= 1 && C * w <= WM_DEC_MAXB, WM_ERR_INVALID, "wmdbg_dec_qkv_panel: C x w rows outside 1 .. %d", WM_DEC_MAXB);
+    const size_t Npad = ((size_t)(N > 0 ? N : 0) + 15) / 16 * 16;
+    std::vector<float> mean((size_t)C * w), Wf(Npad * (size_t)(K > 0 ? K : 0)), c1(Npad), c2(Npad);
+    return dec_gemv_ln_run(ctx, DE_QKV, x, ln_g, ln_b, W, bias, C * w, N, K, 1, n_head, T, pos, w, q_out, nullptr, kcache, vcache,
+                           mean.data(), Wf.data(), c1.data(), c2.data());
+}
+
+extern "C" int wmdbg_dec_self_attention_panel(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int w, int H,
+                                              int T, int pos, int out_rows, float *out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(q && k && v && out, WM_ERR_INVALID, "dec_self_attention_panel: null pointer");
+    WM_REQUIRE(C >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C * w <= WM_DEC_MAXB && H >= 1 && T >= 1 && pos >= 0 && pos + w <= T &&
+                   out_rows >= C * w && out_rows % 16 == 0,
+               WM_ERR_INVALID, "dec_self_attention_panel: bad geometry");
+    const int B = C * w;
+    std::vector<bf16_t> k16, v16;
+    to_bf16(k, k16, (size_t)C * H * T * 64);
+    to_bf16(v, v16, (size_t)C * H * T * 64);
+    const size_t dd = (size_t)H * 64;
+    const std::vector<bf16_t> fill((size_t)out_rows * dd, (bf16_t)WMDBG_SENTINEL_BF16);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dq, *dk, *dv, *dpos, *datt;
+    WM_TRY(pool.get(&dq, q, (size_t)B * dd * 4, s));
+    WM_TRY(pool.get(&dk, k16.data(), k16.size() * 2, s));
+    WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&datt, fill.data(), fill.size() * 2, s));
+    WM_TRY(wm_dec_self_attention_panel(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, C, w, H, T, (const int *)dpos,
+                                       (bf16_t *)datt));
+    std::vector<bf16_t> o16(fill.size()), lin(fill.size());
+    WM_HIP(hipMemcpyAsync(o16.data(), datt, o16.size() * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    for (size_t b = 0; b < (size_t)out_rows; ++b)
+        for (size_t j = 0; j < dd; ++j) lin[b * dd + j] = o16[wm_tiled_offset(b, j, dd)];
+    from_bf16(lin, out);
+    return WM_OK;
+}
+
+extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
+                                     int stride, int c0, int C, int w, int pos, int by_steps, float *x, float *xb, float *stats,
+                                     float *mean) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(emb && pemb && seq && x && xb && stats && mean, WM_ERR_INVALID, "dec_embed_panel: null pointer");
+    WM_REQUIRE(V >= 1 && d >= 64 && d % 64 == 0 && C >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C * w <= WM_DEC_MAXB && c0 >= 0 &&
+                   c0 + C <= stride && pos >= 0 && pos + w <= n_ctx,
+               WM_ERR_INVALID, "dec_embed_panel: bad geometry");
+    for (size_t i = 0; i < (size_t)n_ctx * stride; ++i) WM_REQUIRE(seq[i] >= 0 && seq[i] < V, WM_ERR_INVALID, "dec_embed_panel: token outside the vocabulary");
+    const int B = C * w, Bpad = (B + 15) / 16 * 16, n_tiles = (V + 15) / 16;
+    std::vector<bf16_t> e16;
+    tile_bf16(emb, (size_t)V, (size_t)d, e16);
+    const size_t n_st = (size_t)(Bpad / 16) * (d / 16) * 32;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *de, *dp, *dseq, *dpos, *dx, *dxb, *dst, *dmean, *dtile, *darr, *dx1, *dxb1, *dst1, *dmean1, *dseq1;
+    WM_TRY(pool.get(&de, e16.data(), e16.size() * 2, s));
+    WM_TRY(pool.get(&dp, pemb, (size_t)n_ctx * d * 4, s));
+    WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * stride * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&dx, nullptr, (size_t)B * d * 4, s, 0xff));
+    WM_TRY(pool.get(&dxb, nullptr, (size_t)Bpad * d * 2, s, 0xff));
+    WM_TRY(pool.get(&dst, nullptr, n_st * 4, s, 0xff));
+    WM_TRY(pool.get(&dmean, nullptr, (size_t)B * 4, s, 0xff));
+    std::vector<float> hx((size_t)B * d), hst(n_st), hmean(B);
+    std::vector<bf16_t> hxb((size_t)Bpad * d, (bf16_t)0xffffu);
+    if (!by_steps) {
+        WM_TRY(wm_dec_embed_panel(ctx, (const int *)dseq + c0, stride, (const int *)dpos, 0, C, w, (const bf16_t *)de, (const float *)dp, d,
+                                  n_ctx, (float *)dx, (bf16_t *)dxb, (float *)dst, (float *)dmean));
+        WM_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(hxb.data(), dxb, hxb.size() * 2, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(hst.data(), dst, hst.size() * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(hmean.data(), dmean, hmean.size() * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipStreamSynchronize(s));
+    } else {
+        // the step path, position by position over the C windows alone: wm_dec_embed for position 0, the teacher-forced close
+        // (wm_argmax_embed with every position a prompt position) for the others; row c of step s is row c * w + s of the panel
+        const int Cpad = (C + 15) / 16 * 16;
+        const size_t n_st1 = (size_t)(Cpad / 16) * (d / 16) * 32;
+        std::vector<int32_t> seq1((size_t)n_ctx * C);
+        for (int t = 0; t < n_ctx; ++t)
+            for (int c = 0; c < C; ++c) seq1[(size_t)t * C + c] = seq[(size_t)t * stride + c0 + c];
+        WM_TRY(pool.get(&dseq1, seq1.data(), seq1.size() * 4, s));
+        WM_TRY(pool.get(&dtile, nullptr, (size_t)C * n_tiles * 8, s));
+        WM_TRY(pool.get(&darr, nullptr, 4, s));
+        WM_TRY(pool.get(&dx1, nullptr, (size_t)C * d * 4, s));
+        WM_TRY(pool.get(&dxb1, nullptr, (size_t)Cpad * d * 2, s));
+        WM_TRY(pool.get(&dst1, nullptr, n_st1 * 4, s));
+        WM_TRY(pool.get(&dmean1, nullptr, (size_t)C * 4, s));
+        std::vector<float> x1((size_t)C * d), st1(n_st1), mean1(C);
+        std::vector<bf16_t> xb1((size_t)Cpad * d);
+        for (int sp = 0; sp < w; ++sp) {
+            const int p = pos + sp;
+            if (p == 0) {
+                WM_HIP(hipMemsetAsync(dpos, 0, 4, s));
+                WM_TRY(wm_dec_embed(ctx, (const int *)dseq1, (const int *)dpos, C, (const bf16_t *)de, (const float *)dp, d, (float *)dx1,
+                                    (bf16_t *)dxb1, (float *)dst1, (float *)dmean1));
+            } else {
+                const int pm = p - 1;
+                WM_HIP(hipMemcpyAsync(dpos, &pm, 4, hipMemcpyHostToDevice, s));
+                WM_HIP(hipStreamSynchronize(s));
+                WM_TRY(wm_argmax_embed(ctx, (const unsigned long long *)dtile, n_tiles, C, (int *)dseq1, (int *)dpos, n_ctx, nullptr, 0,
+                                       (const bf16_t *)de, (const float *)dp, d, n_ctx, (float *)dx1, (bf16_t *)dxb1, (float *)dst1, nullptr,
+                                       (int *)darr, 0, (float *)dmean1));
+            }
+            WM_HIP(hipMemcpyAsync(x1.data(), dx1, x1.size() * 4, hipMemcpyDeviceToHost, s));
+            WM_HIP(hipMemcpyAsync(xb1.data(), dxb1, xb1.size() * 2, hipMemcpyDeviceToHost, s));
+            WM_HIP(hipMemcpyAsync(st1.data(), dst1, st1.size() * 4, hipMemcpyDeviceToHost, s));
+            WM_HIP(hipMemcpyAsync(mean1.data(), dmean1, mean1.size() * 4, hipMemcpyDeviceToHost, s));
+            WM_HIP(hipStreamSynchronize(s));
+            for (int c = 0; c < C; ++c) {
+                const size_t r = (size_t)c * w + sp;
+                memcpy(&hx[r * d], &x1[(size_t)c * d], (size_t)d * 4);
+                for (int j = 0; j < d; ++j) hxb[wm_tiled_offset(r, (size_t)j, (size_t)d)] = xb1[wm_tiled_offset((size_t)c, (size_t)j, (size_t)d)];
+                for (int pt = 0; pt < d / 16; ++pt)
+                    for (int i = 0; i < 2; ++i)
+                        hst[(r >> 4) * (size_t)(2 * d) + (size_t)pt * 32 + (r & 15) * 2 + i] =
+                            st1[((size_t)c >> 4) * (size_t)(2 * d) + (size_t)pt * 32 + (c & 15) * 2 + i];
+                hmean[r] = mean1[c];
+            }
+        }
+    }
+    memcpy(x, hx.data(), hx.size() * 4);
+    memcpy(mean, hmean.data(), hmean.size() * 4);
+    untile_bf16(hxb, (size_t)B, (size_t)d, xb);
+    // statistics [B][d / 16][2]: the parts of row r
+    for (size_t r = 0; r < (size_t)B; ++r)
+        for (int pt = 0; pt < d / 16; ++pt)
+            for (int i = 0; i < 2; ++i) stats[(r * (d / 16) + pt) * 2 + i] = hst[(r >> 4) * (size_t)(2 * d) + (size_t)pt * 32 + (r & 15) * 2 + i];
+    return WM_OK;
+}
+
+extern "C" int wmdbg_align_capture_panel(wm_ctx *ctx, const float *dq, int d, int C, int w, int pos, const int32_t *heads, int n_heads,
+                                         int slot0, int Tq, int J, int by_steps, float *cap) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(dq && heads && cap && d >= 64 && d % 64 == 0 && C >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C * w <= WM_DEC_MAXB &&
+                   pos >= 0 && n_heads >= 1 && n_heads <= 32 && slot0 >= 0 && slot0 + n_heads <= J && Tq >= 1,
+               WM_ERR_INVALID, "align_capture_panel: bad geometry");
+    WmAlignLayer L;
+    L.n = n_heads; L.slot0 = slot0;
+    for (int i = 0; i < n_heads; ++i) {
+        WM_REQUIRE(heads[i] >= 0 && heads[i] < d / 64, WM_ERR_INVALID, "align_capture_panel: head %d outside the row", heads[i]);
+        L.head[i] = heads[i];
+    }
+    const int B = C * w;
+    const size_t n_cap = (size_t)C * Tq * J * 64;
+    const std::vector<uint32_t> fill(n_cap, WMDBG_SENTINEL_F32);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dd, *dpos, *dcap, *d1;
+    WM_TRY(pool.get(&dd, dq, (size_t)B * d * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&dcap, fill.data(), n_cap * 4, s));
+    if (!by_steps) {
+        WM_TRY(wm_align_capture_q(ctx, (const float *)dd, d, B, L, (float *)dcap, Tq, J, (const int *)dpos, w));
+    } else {
+        std::vector<float> q1((size_t)C * d);
+        WM_TRY(pool.get(&d1, nullptr, q1.size() * 4, s));
+        for (int sp = 0; sp < w; ++sp) {
+            for (int c = 0; c < C; ++c) memcpy(&q1[(size_t)c * d], dq + ((size_t)c * w + sp) * d, (size_t)d * 4);
+            const int p = pos + sp;
+            WM_HIP(hipMemcpyAsync(d1, q1.data(), q1.size() * 4, hipMemcpyHostToDevice, s));
+            WM_HIP(hipMemcpyAsync(dpos, &p, 4, hipMemcpyHostToDevice, s));
+            WM_HIP(hipStreamSynchronize(s));
+            WM_TRY(wm_align_capture_q(ctx, (const float *)d1, d, C, L, (float *)dcap, Tq, J, (const int *)dpos));
+        }
+    }
+    WM_HIP(hipMemcpyAsync(cap, dcap, n_cap * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
+extern "C" int wmdbg_align_token_prob_panel(wm_ctx *ctx, const float *logits, int C, int w, int V, int ldo, const int32_t *seq,
+                                            int n_ctx, int pos, int S, int eot, const int32_t *n_text, int max_text, int by_steps,
+                                            float *prob) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(logits && seq && n_text && prob && C >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C * w <= WM_DEC_MAXB && V >= 1 &&
+                   ldo >= V && eot >= 1 && eot <= V && pos >= 0 && pos + w < n_ctx && S >= 0 && max_text >= 1,
+               WM_ERR_INVALID, "align_token_prob_panel: bad geometry");
+    for (int c = 0; c < C; ++c) WM_REQUIRE(n_text[c] >= 0 && n_text[c] <= max_text, WM_ERR_INVALID, "align_token_prob_panel: n_text[%d]", c);
+    for (size_t i = 0; i < (size_t)n_ctx * C; ++i) WM_REQUIRE(seq[i] >= 0 && seq[i] < eot, WM_ERR_INVALID, "align_token_prob_panel: token not below eot");
+    const int B = C * w;
+    const std::vector<uint32_t> fill((size_t)C * max_text, WMDBG_SENTINEL_F32);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    void *dl, *dseq, *dn, *dpos, *dp, *d1;
+    WM_TRY(pool.get(&dl, logits, (size_t)B * ldo * 4, s));
+    WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * C * 4, s));
+    WM_TRY(pool.get(&dn, n_text, (size_t)C * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&dp, fill.data(), fill.size() * 4, s));
+    if (!by_steps) {
+        WM_TRY(wm_align_token_prob(ctx, (const float *)dl, ldo, (const int *)dseq, (const int *)dpos, B, S, eot, (const int *)dn, (float *)dp,
+                                   max_text, w, C));
+    } else {
+        std::vector<float> l1((size_t)C * ldo);
+        WM_TRY(pool.get(&d1, nullptr, l1.size() * 4, s));
+        for (int sp = 0; sp < w; ++sp) {
+            for (int c = 0; c < C; ++c) memcpy(&l1[(size_t)c * ldo], logits + ((size_t)c * w + sp) * ldo, (size_t)ldo * 4);
+            const int p = pos + sp;
+            WM_HIP(hipMemcpyAsync(d1, l1.data(), l1.size() * 4, hipMemcpyHostToDevice, s));
+            WM_HIP(hipMemcpyAsync(dpos, &p, 4, hipMemcpyHostToDevice, s));
+            WM_HIP(hipStreamSynchronize(s));
+            WM_TRY(wm_align_token_prob(ctx, (const float *)d1, ldo, (const int *)dseq, (const int *)dpos, C, S, eot, (const int *)dn,
+                                       (float *)dp, max_text));
+        }
+    }
+    WM_HIP(hipMemcpyAsync(prob, dp, fill.size() * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
     return WM_OK;
 }
 

@@ -85,11 +85,13 @@ struct DecGemvDev {
     int pf_tiles;
     int pf_head_major;     // warm-up placement for a consumer that runs head h on XCD h % 8 (dec_xattn_fq_kernel)
     int bgroups;           // workgroups per tile group along the batch: group g takes batch rows [g, g + 1) * NBLK * 16
-    WmRepDev rep;          // DE_LOGITS_XR: repetition rules (LAST: the fields above keep their kernel-argument offsets)
+    WmRepDev rep;          // DE_LOGITS_XR: repetition rules (behind the older fields: they keep their kernel-argument offsets)
+    int panel;             // DE_QKV_P: panel width (cold, like rep: read in the epilogue only)
 };
 // the extended-decode epilogues (DE_LOGITS_XR = DE_LOGITS_X + the repetition rules), and every logits epilogue
 constexpr bool de_is_x(int epi) { return epi == DE_LOGITS_X || epi == DE_LOGITS_XR; }
 constexpr bool de_is_logits(int epi) { return epi == DE_LOGITS || de_is_x(epi); }
+constexpr bool de_is_qkv(int epi) { return epi == DE_QKV || epi == DE_QKV_P; }
 
 // L2 warm-up workgroup: blockIdx >= n_tiles of the compute grid.  Workgroup n_tiles + t reads tile t of
 // the NEXT launch's weight matrix.  Dispatch places block b on XCD b % 8 (observed, not guaranteed --
@@ -450,6 +452,18 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             p.out_f32[(long)b * p.ldo + n] = v;
         } else if (EPI == DE_GELU) {
             p.out_bf16[wm_tiled_offset((size_t)b, (size_t)n, (size_t)p.ldo)] = f2bf(gelu_erf(v));
+        } else if (EPI == DE_QKV_P) {
+            // a panel step: row b = (window b / w, position pos + b % w) -- the query stays row b's, k / v are appended to the
+            // WINDOW's cache entry at the row's own position (< n_ctx by the host's cut of the pass; checked all the same)
+            const int d = p.N / 3;
+            if (n < d) {
+                p.out_f32[(long)b * d + n] = v;
+            } else {
+                const int hn = (n < 2 * d) ? n - d : n - 2 * d;
+                bf16_t *c = (n < 2 * d) ? p.kcache : p.vcache;
+                const int cw = b / p.panel, ps = pos + (b - cw * p.panel);
+                if (ps < p.n_ctx) c[((long)(cw * p.n_head + (hn >> 6)) * p.n_ctx + ps) * 64 + (hn & 63)] = f2bf(v);
+            }
         }
     }
 }
@@ -551,6 +565,7 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
     if (LN) { GEMV_PIN(p.c1); GEMV_PIN(p.stats_in); GEMV_PIN(p.stats_stride); GEMV_PIN(p.mean_in); GEMV_PIN(p.mean_out); }
     if (EPI == DE_RESID) { GEMV_PIN(p.out_bf16); GEMV_PIN(p.stats_out); GEMV_PIN(p.stats_stride); GEMV_PIN(p.mean_in); }
     if (EPI == DE_QKV) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); }
+    if (EPI == DE_QKV_P) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); GEMV_PIN(p.panel); }
     if (EPI == DE_GELU) GEMV_PIN(p.out_bf16);
     if (EPI == DE_LOGITS_XR) { GEMV_PIN(p.rep.par); GEMV_PIN(p.rep.seen); GEMV_PIN(p.rep.ban); GEMV_PIN(p.rep.words); }
     if (de_is_logits(EPI)) {
@@ -699,17 +714,12 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const bf16_t *__restrict__
 // four-wave sums here and the one-wave sums there differ in the last place, so merging them would change results.
 // off (nullable, [B]): a ragged decode group -- row b's prompt starts at position off[b] of the group, so its positional
 // row is pos - off[b] (0 while the row has not started)
-__global__ __launch_bounds__(256) void dec_embed_kernel(const int *__restrict__ seq, const int *__restrict__ pos_ptr,
-                                                        int B, const bf16_t *__restrict__ emb,
-                                                        const float *__restrict__ pemb, int d,
-                                                        float *__restrict__ x, bf16_t *__restrict__ xb,
-                                                        float *__restrict__ stats_out, float *__restrict__ mean_buf,
-                                                        const int *__restrict__ off) {
+// (the four-wave arithmetic as a device function: dec_embed_kernel and the panel embedding's position 0 call it)
+__device__ __forceinline__ void embed_first_row(long tok, int prow, int b, const bf16_t *__restrict__ emb,
+                                                const float *__restrict__ pemb, int d, float *__restrict__ x,
+                                                bf16_t *__restrict__ xb, float *__restrict__ stats_out,
+                                                float *__restrict__ mean_buf) {
     __shared__ float r1[4], r2[4];
-    const int b = blockIdx.x;
-    const int pos = *pos_ptr;
-    const long tok = seq[pos * B + b];
-    const int prow = off ? max(pos - off[b], 0) : pos;
     float s1 = 0.f, s2 = 0.f;
     for (int j = threadIdx.x; j < d; j += 256) {
         const float v = bf2f(emb[wm_tiled_offset((size_t)tok, (size_t)j, (size_t)d)]) + pemb[(long)prow * d + j];
@@ -741,6 +751,38 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const int *__restrict__ 
             *(float2 *)blk = make_float2((r1[0] + r1[1]) + (r1[2] + r1[3]), (r2[0] + r2[1]) + (r2[2] + r2[3]));
     }
 }
+__global__ __launch_bounds__(256) void dec_embed_kernel(const int *__restrict__ seq, const int *__restrict__ pos_ptr,
+                                                        int B, const bf16_t *__restrict__ emb,
+                                                        const float *__restrict__ pemb, int d,
+                                                        float *__restrict__ x, bf16_t *__restrict__ xb,
+                                                        float *__restrict__ stats_out, float *__restrict__ mean_buf,
+                                                        const int *__restrict__ off) {
+    const int b = blockIdx.x;
+    const int pos = *pos_ptr;
+    const long tok = seq[pos * B + b];
+    const int prow = off ? max(pos - off[b], 0) : pos;
+    embed_first_row(tok, prow, b, emb, pemb, d, x, xb, stats_out, mean_buf);
+}
+
+// The embedding of a teacher-forced PANEL (wm_set_teacher_panel): one workgroup per row r = c * w + s = (window c, position
+// *pos_ptr + pos_add + s).  A row at position 0 is the call's first embedding (the four-wave sums above), every later position
+// the embedding a closing launch would have written (embed_row of dec_close.h, ONE wave): per row the bits of the step path.
+__global__ __launch_bounds__(256) void dec_embed_panel_kernel(const int *__restrict__ seq, int seq_stride,
+                                                              const int *__restrict__ pos_ptr, int pos_add, int w,
+                                                              const bf16_t *__restrict__ emb, const float *__restrict__ pemb,
+                                                              int d, int n_ctx, float *__restrict__ x, bf16_t *__restrict__ xb,
+                                                              float *__restrict__ stats_out, float *__restrict__ mean_buf) {
+    const int r = blockIdx.x, c = r / w;
+    const int pos = *pos_ptr + pos_add + (r - c * w);
+    if (pos >= n_ctx) return;   // (workgroup-uniform; never taken in a pass cut by the host)
+    const long tok = seq[(long)pos * seq_stride + c];
+    if (pos == 0) {             // workgroup-uniform
+        embed_first_row(tok, 0, r, emb, pemb, d, x, xb, stats_out, mean_buf);
+    } else if (threadIdx.x < 64) {
+        embed_row(tok, pos, r, (int)threadIdx.x, emb, pemb, d, x, xb, stats_out, mean_buf);
+    }
+}
+__global__ void dec_pos_add_kernel(int *pos_ptr, int add) { *pos_ptr += add; }
 
 // ------------------------------------------------------------------ single-query attention
 // One kernel serves the decoder's two attentions.  The rows of a (sequence, head) pair are dealt to NS canonical
@@ -905,15 +947,30 @@ struct AttnColdOff {
     const char *pf_ptr;
     long pf_tile_bytes;
 };
-template <bool OFF> struct AttnColdSel { typedef AttnCold type; };
-template <> struct AttnColdSel<true> { typedef AttnColdOff type; };
-template <int NS, int U, bool NT, bool DEEP = false, bool OFF = false>
+// TEACHER-FORCED PANELS (PANEL, the self-attention only).  The rows of a panel step are C windows x w consecutive positions
+// of the SAME sequences: row r = c * w + s is position pos + s of window c.  Its pair reads the cache entry of WINDOW c (the
+// step's QKV epilogue has just appended all w positions there) with pos + s + 1 keys; query and output are row r's.  Stream and
+// block assignment, masks and merge order are functions of the key count only, so a row's bits are those of the uniform kernel
+// at that position.  The speculative first block is clamped to the cache entry's last row as before (pos + s < T_stride).
+// The width takes the place of `att` in the last preloaded dwords; uniform groups run the kernel they always ran.
+struct AttnColdPanel {
+    int w;
+    bf16_t *att;
+    float *part;
+    const char *pf_ptr;
+    long pf_tile_bytes;
+};
+template <bool OFF, bool PANEL> struct AttnColdSel { typedef AttnCold type; };
+template <> struct AttnColdSel<true, false> { typedef AttnColdOff type; };
+template <> struct AttnColdSel<false, true> { typedef AttnColdPanel type; };
+template <int NS, int U, bool NT, bool DEEP = false, bool OFF = false, bool PANEL = false>
 __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
     const int *__restrict__ pos_ptr, const int *__restrict__ live_rows /* [WM_DEC_MAXB] rows | [1] count, or null */,
     unsigned packA /* H | nsplit << 8 | flat_wpw << 16 */, unsigned packB /* T_stride | n_keys_const << 16 */,
-    unsigned packC /* n_bh | n_wg << 16 */, typename AttnColdSel<OFF>::type cold) {
+    unsigned packC /* n_bh | n_wg << 16 */, typename AttnColdSel<OFF, PANEL>::type cold) {
     static_assert(!OFF || (NS == 4 && !DEEP), "row offsets: the causal self-attention only");
+    static_assert(!PANEL || (NS == 4 && !DEEP && !OFF), "panels: the causal self-attention of a uniform group only");
     const int H = (int)(packA & 0xffu), nsplit = (int)((packA >> 8) & 0xffu), flat_wpw = (int)(packA >> 16);
     const int T_stride = (int)(packB & 0xffffu), n_keys_const = (int)(packB >> 16);
     const int n_bh_full = (int)(packC & 0xffffu), n_wg = (int)(packC >> 16);
@@ -964,12 +1021,19 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         int b = pi / H;
         if (live_rows) b = live_rows[pi / H];  // first pair: pi < n_bh_full, a (possibly stale) valid row id
         const int bh = b * H + h;
-        const bf16_t *kb = kc + (long)bh * T_stride * 64 + e8 * 8;
-        const bf16_t *vb = vc + (long)bh * T_stride * 64 + e8 * 8;
+        int bkv = bh;     // the pair's cache entry
+        int ps = 0;       // PANEL: the row's position within the panel
+        if constexpr (PANEL) {
+            const int cw = b / cold.w;
+            ps = b - cw * cold.w;
+            bkv = cw * H + h;
+        }
+        const bf16_t *kb = kc + (long)bkv * T_stride * 64 + e8 * 8;
+        const bf16_t *vb = vc + (long)bkv * T_stride * 64 + e8 * 8;
         const f32x4 *qp = (const f32x4 *)(q + (long)b * d + h * 64 + e8 * 8);
         const f32x4 q0 = qp[0], q1 = qp[1];
         int ob = 0;       // OFF: first cache row of this pair; row indices from here on are relative to it
-        int clamp0 = first ? n_clamp : n_keys - 1;
+        int clamp0 = first ? n_clamp : n_keys - 1 + ps;
         if constexpr (OFF) {
             if (first) {
                 ob = b == bh0 / H ? off_raw : cold.off[b];   // (the position is not known yet: see below)
@@ -1014,6 +1078,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         }
         int nk = n_keys;  // keys of this pair
         if constexpr (OFF) nk = pos_k + 1 - ob;
+        if constexpr (PANEL) nk = n_keys + ps;
         float qe[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1837,7 +1902,7 @@ int launch_gemv_shape(wm_ctx *ctx, const DecGemvDev &p, int tn, int nblk, int nw
     const size_t lds = (size_t)nw * tn * nblk * 1024 + (size_t)nw * 32 * 4;
     const int th = nw * 64;
     constexpr bool LOGITS = de_is_logits(EPI);
-    constexpr bool WIDE = LN && (EPI == DE_QKV || EPI == DE_GELU || LOGITS) && SPW <= 6;
+    constexpr bool WIDE = LN && (de_is_qkv(EPI) || EPI == DE_GELU || LOGITS) && SPW <= 6;
     if (tn == 1 && nblk == 1) dec_gemv_kernel<SPW, 1, 1, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 1 && nblk == 2 && SPW <= 8) dec_gemv_kernel<SPW <= 8 ? SPW : 2, 1, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 2 && nblk == 1 && WIDE && LOGITS) dec_gemv_kernel<WIDE ? SPW : 2, 2, 1, WIDE ? EPI : DE_LOGITS, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
@@ -1909,7 +1974,7 @@ static void pick_shape(int epi, bool ln, int spw, int nw, int B, int n_tiles, in
     }
     if (blocks < 2 || nw > 8 || spw > 8) return;
     *nblk = env_nb == 1 ? 1 : 2;
-    const bool wide = ln && (epi == DE_QKV || epi == DE_GELU || de_is_logits(epi)) && *nblk == 2 && spw <= 6;
+    const bool wide = ln && (de_is_qkv(epi) || epi == DE_GELU || de_is_logits(epi)) && *nblk == 2 && spw <= 6;
     if (!wide) return;
     // Tile-group width by RESIDENCY ROUNDS: an 8-wave workgroup of the (1, 2) shape needs <= 128 VGPRs and sits two per
     // CU, the wide shapes (136-190 VGPRs) one per CU; a grid that needs a second round of the chip costs a whole kernel
@@ -1955,6 +2020,9 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
     p.ts = a.ts;
     p.x = a.x;
     p.rep = a.rep;
+    p.panel = a.panel;
+    WM_REQUIRE(a.epi != DE_QKV_P || (a.panel >= 1 && a.panel <= WM_MAX_TEACHER_PANEL && a.pos_ptr), WM_ERR_INVALID,
+               "dec_gemv: DE_QKV_P needs a panel width of 1 .. %d and the device position", WM_MAX_TEACHER_PANEL);
     WM_REQUIRE(!de_is_x(a.epi) || (a.x.par && a.pos_ptr), WM_ERR_INVALID, "dec_gemv: DE_LOGITS_X needs its state and the device position");
     WM_REQUIRE(a.epi != DE_LOGITS_XR || (a.rep.par && a.rep.seen && a.rep.ban && (long)a.rep.words * 32 >= a.N), WM_ERR_INVALID,
                "dec_gemv: DE_LOGITS_XR needs the repetition-rule state");
@@ -1997,6 +2065,10 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
         case DE_QKV * 2 + 1: {
             WmProfScope ps(&ctx->prof, "dec_gemv_ln_qkv", ctx->stream);
             return launch_gemv<DE_QKV, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
+        }
+        case DE_QKV_P * 2 + 1: {
+            WmProfScope ps(&ctx->prof, "dec_gemv_ln_qkv", ctx->stream);
+            return launch_gemv<DE_QKV_P, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
         }
         case DE_Q * 2 + 1: {
             WmProfScope ps(&ctx->prof, "dec_gemv_ln_q", ctx->stream);
@@ -2050,6 +2122,23 @@ int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const b
 
 // Workgroups per (sequence, head) pair of the cross-attention: 1 when the pairs alone fill the chip, else the stream
 // set of a pair is dealt to 2, 4 or 8 workgroups.  A launch-shape choice: the arithmetic does not depend on it.
+int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, const bf16_t *emb,
+                       const float *pemb, int d, int n_ctx, float *x, bf16_t *xb, float *stats_out, float *mean_buf) {
+    WM_REQUIRE(w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && C * w <= WM_DEC_MAXB && seq_stride >= C, WM_ERR_INVALID,
+               "dec_embed_panel: %d windows x %d positions (stride %d)", C, w, seq_stride);
+    WmProfScope ps(&ctx->prof, "dec_embed_panel", ctx->stream);
+    dec_embed_panel_kernel<<<C * w, 256, 0, ctx->stream>>>(seq, seq_stride, pos_ptr, pos_add, w, emb, pemb, d, n_ctx, x, xb, stats_out,
+                                                          mean_buf);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+int wm_dec_pos_add(wm_ctx *ctx, int *pos_ptr, int add) {
+    dec_pos_add_kernel<<<1, 1, 0, ctx->stream>>>(pos_ptr, add);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
 int wm_dec_attn_splits(int B, int H) {
     const int bh = B * H;
     // few pairs: the (pair, stream) units are dealt flat over the chip and merged by a combine launch.  (Measured at
@@ -2303,6 +2392,29 @@ int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const b
     } else {
         dec_rows_attn_kernel<4, 4, false><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
     }
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+int wm_dec_self_attention_panel(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int w, int H, int T_stride,
+                                const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k) {
+    WM_REQUIRE(w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && C * w <= WM_DEC_MAXB, WM_ERR_INVALID,
+               "dec_self_attention_panel: %d windows x %d positions outside 1 .. %d rows of 1 .. %d positions", C, w, WM_DEC_MAXB,
+               WM_MAX_TEACHER_PANEL);
+    WM_REQUIRE(T_stride >= w && T_stride <= ATT_MAXK && pos_ptr, WM_ERR_INVALID, "dec_self_attention_panel: %d .. %d cache rows", w, ATT_MAXK);
+    WM_REQUIRE(H >= 1 && H <= 255, WM_ERR_INVALID, "dec_self_attention_panel: %d heads do not fit the packed arguments", H);
+    WmProfScope ps(&ctx->prof, "dec_attn_self", ctx->stream);
+    const int B = C * w;
+    int gx = B * H;
+    long tile_bytes = 0;
+    if (pf_enabled(B) && pf_ptr && gx % 8 == 0 && pf_rows >= 16) {
+        tile_bytes = 16L * pf_k * 2;
+        gx += pf_rows / 16;
+    }
+    const AttnColdPanel cold = {w, att, nullptr, (const char *)pf_ptr, tile_bytes};
+    const unsigned pA = (unsigned)H | (1u << 8), pB = (unsigned)T_stride;
+    const unsigned pC = (unsigned)(B * H) | ((unsigned)(B * H) << 16);
+    dec_rows_attn_kernel<4, 4, false, false, false, true><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, nullptr, pA, pB, pC, cold);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

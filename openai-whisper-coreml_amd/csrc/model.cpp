@@ -429,6 +429,7 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->mask_on = pm->mask_on; m->mask_host = pm->mask_host;
     m->ts_on = pm->ts_on; m->ts_begin = pm->ts_begin; m->ts_eot = pm->ts_eot; m->ts_max_initial = pm->ts_max_initial;
     m->align_l = pm->align_l; m->align_h = pm->align_h;
+    m->teacher_panel = pm->teacher_panel;
     m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
     if (m->rep_on) WM_TRY(alloc_repetition_state(m, child->stream));
     WM_HIP(hipStreamSynchronize(child->stream));
@@ -761,13 +762,20 @@ int wm_model_set_pos(wm_ctx *ctx, int pos) {
     return WM_OK;
 }
 
-int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, const WmAlignCap *cap,
-                         const WmDecodeMode &mode, int n_prompt) {
+// grp / c0 (a panel step only, else 0): the step's windows are rows c0 .. of a group of grp windows whose caches are laid out
+// [L][2][grp][H][.][64] -- the per-layer pointers advance by whole windows (wm_model_panel_step)
+static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, const WmAlignCap *cap,
+                            const WmDecodeMode &mode, int n_prompt, int grp, int c0) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head, T = D.n_text_ctx, S = 1500;
+    const int PW = mode.panel > 1 ? mode.panel : 1;     // panel step: B = Bx windows x PW positions, one self AND one cross cache entry per window
     const int NC = mode.n_cand > 1 ? mode.n_cand : 1;   // candidate group: B = Bx windows x NC rows, one cross cache per window
-    const int Bx = B / NC;
+    WM_REQUIRE(PW == 1 || (NC == 1 && !mode.stop && !mode.off && !mode.x && B % PW == 0), WM_ERR_STATE,
+               "decode step: a panel is a plain teacher-forced step of windows x width rows");
+    const int Bx = B / (NC * PW);
+    const int Gx = grp > 0 ? grp : Bx;                  // windows per layer of the cross cache
+    const int Gs = grp > 0 ? grp : (PW > 1 ? Bx : B);   // rows per layer of the self cache
     const int ns = wm_dec_attn_splits(B, H);
     const int xns = g_wm_tuning.xattn_splits > 0 ? g_wm_tuning.xattn_splits : ns;   // 0 in the product
     const int *live = mode.stop ? m->dlive : nullptr, *nlive = mode.stop ? m->dnlive : nullptr;
@@ -778,10 +786,10 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
     auto mean_buf = [&](int i) { return m->dmean + (size_t)i * WM_DEC_MAXB; };
     for (int l = 0; l < D.n_text_layer; ++l) {
         const DecLayerW &L = m->dec[l];
-        bf16_t *kc = m->skv + (size_t)(l * 2 + 0) * B * H * T * 64;
-        bf16_t *vc = m->skv + (size_t)(l * 2 + 1) * B * H * T * 64;
-        const bf16_t *xk = m->xkv + (size_t)(l * 2 + 0) * Bx * H * S * 64;
-        const bf16_t *xv = m->xkv + (size_t)(l * 2 + 1) * Bx * H * S * 64;
+        bf16_t *kc = m->skv + ((size_t)(l * 2 + 0) * Gs + c0) * H * T * 64;
+        bf16_t *vc = m->skv + ((size_t)(l * 2 + 1) * Gs + c0) * H * T * 64;
+        const bf16_t *xk = m->xkv + ((size_t)(l * 2 + 0) * Gx + c0) * H * S * 64;
+        const bf16_t *xv = m->xkv + ((size_t)(l * 2 + 1) * Gx + c0) * H * S * 64;
         DecGemvArgs a;
         // 1. attn_ln (folded) + fused q|k|v projection; k, v appended to the self-attention cache
         memset(&a, 0, sizeof(a));
@@ -790,9 +798,14 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         a.stats_in = m->dstats;
         a.mean_in = mean_buf(cur); a.mean_out = mean_buf(cur ^ 1); cur ^= 1;
         a.pos_ptr = m->dpos; a.n_ctx = T; a.n_head = H;
+        if (PW > 1) { a.epi = DE_QKV_P; a.panel = PW; }   // row (c, s) appends at position pos + s of window c
         WM_TRY(wm_dec_gemv(ctx, a));
-        // 2. causal self-attention over positions 0..pos
-        WM_TRY(wm_dec_self_attention(ctx, m->dq, kc, vc, B, H, T, 0, m->dpos, m->datt, L.wo, d, d, live, nlive, off));
+        // 2. causal self-attention over positions 0..pos (a panel row: 0 .. pos + s of its window)
+        if (PW > 1) {
+            WM_TRY(wm_dec_self_attention_panel(ctx, m->dq, kc, vc, Bx, PW, H, T, m->dpos, m->datt, L.wo, d, d));
+        } else {
+            WM_TRY(wm_dec_self_attention(ctx, m->dq, kc, vc, B, H, T, 0, m->dpos, m->datt, L.wo, d, d, live, nlive, off));
+        }
         // 3. out-projection + residual (f32 stream, its bf16 copy, partial statistics)
         memset(&a, 0, sizeof(a));
         a.epi = DE_RESID; a.B = B; a.N = d; a.K = d; a.W = L.wo; a.c2 = L.bo;
@@ -802,7 +815,7 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         const bool xshort = mode.xattn_shared && !g_wm_tuning.xattn_never_short;
         // wm_align: a layer with alignment heads leaves its f32 query in m->dq (the two launches: same bits as the fused one)
         const bool cap_l = cap && cap->layer[l].n > 0;
-        const bool fuse_q = NC == 1 && !cap_l && xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
+        const bool fuse_q = NC == 1 && PW == 1 && !cap_l && xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
         a.pf_head_major = fuse_q ? (H * B + 7) / 8 : 0;   // pairs per XCD of the fused consumer
         WM_TRY(wm_dec_gemv(ctx, a));
         // 4. cross_attn_ln (folded) + query projection
@@ -817,10 +830,10 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
             WM_TRY(wm_dec_xattn_fq(ctx, a, xk, xv, B, H, S, S, m->datt, live, nlive, L.wxo, d, d));
         } else {
             WM_TRY(wm_dec_gemv(ctx, a));
-            if (cap_l) WM_TRY(wm_align_capture_q(ctx, m->dq, d, B, cap->layer[l], cap->q, cap->Tq, cap->J, m->dpos));
-            // 5. cross-attention over the 1500 cached encoder frames (a candidate group: one K/V read per window)
-            if (NC > 1) {
-                WM_TRY(wm_dec_attention_cand(ctx, m->dq, xk, xv, Bx, NC, H, S, S, m->dpart, m->datt, L.wxo, d, d, live, nlive, xshort));
+            if (cap_l) WM_TRY(wm_align_capture_q(ctx, m->dq, d, B, cap->layer[l], cap->q, cap->Tq, cap->J, m->dpos, PW));
+            // 5. cross-attention over the 1500 cached encoder frames (a candidate group, a panel: one K/V read per window)
+            if (NC > 1 || PW > 1) {
+                WM_TRY(wm_dec_attention_cand(ctx, m->dq, xk, xv, Bx, NC * PW, H, S, S, m->dpart, m->datt, L.wxo, d, d, live, nlive, xshort));
             } else {
                 WM_TRY(wm_dec_attention(ctx, m->dq, xk, xv, B, H, S, S, nullptr, xns, m->dpart, m->datt, true, L.wxo, d, d, live, nlive, xshort));
             }
@@ -871,6 +884,73 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
         WM_TRY(wm_dec_gemv(ctx, a));
     }
     return WM_OK;
+}
+
+int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, const WmAlignCap *cap,
+                         const WmDecodeMode &mode, int n_prompt) {
+    WM_REQUIRE(mode.panel <= 1, WM_ERR_STATE, "decode step: panels run through wm_model_panel_step");
+    return decode_step_impl(ctx, B, want_logits, arg_first, arg_last, cap, mode, n_prompt, 0, 0);
+}
+
+// ------------------------------------------------------------------ teacher-forced panels
+// How a group of G windows is cut for a pass of T positions at the context's width: slices of C windows x panels of w positions,
+// C * w <= 128 rows.  A pass costs (steps) x (a + b * rows) with a -- the weight stream and the launch chain of a step -- the
+// larger part (large-v2: 3.3 ms at 64 rows, 4.4 at 120, 5.5 at 128), and steps x rows is the same G x T for every cut: the cut
+// with the FEWEST STEPS wins.  So: among the widths w' <= width, slices of floor(128 / w') windows, take the one with the fewest
+// slices x ceil(T / w') steps (ties: the wider); its slices are balanced.  Up to 128 / width windows that is the whole group at
+// the full width.  Measured, both candidate rules of a larger group (profiles/r18_teacher_panel.txt): 24 windows -- one panel
+// narrowed to 5 positions (46 steps) beats slices of 16 at width 8 (58 steps) by 21 - 26 %; 48 windows -- three slices at width 8
+// (87 steps) beat one panel narrowed to 2 (115 steps) by 14 %.  Results cannot depend on the cut.
+void wm_model_panel_slices(int G, int width, int T, int *C, int *w) {
+    const int wd = width < 1 ? 1 : (width > WM_MAX_TEACHER_PANEL ? WM_MAX_TEACHER_PANEL : width);
+    int best_w = wd, best_steps = 1 << 30;
+    for (int wc = wd; wc >= 1; --wc) {
+        const int cap = WM_DEC_MAXB / wc, steps = ((G + cap - 1) / cap) * ((T + wc - 1) / wc);
+        if (steps < best_steps) { best_steps = steps; best_w = wc; }
+    }
+    const int knob = g_wm_tuning.teacher_panel_cut;   // (probes: 1 = one narrowed panel, 2 = slices at the full width; 0: the rule)
+    if (knob == 1 && G > WM_DEC_MAXB / wd) best_w = WM_DEC_MAXB / G;
+    if (knob == 2) best_w = wd;
+    const int cap = WM_DEC_MAXB / best_w, n_slices = (G + cap - 1) / cap;
+    *w = best_w;
+    *C = (G + n_slices - 1) / n_slices;
+}
+
+static int panel_check(wm_ctx *ctx, int G, int c0, int C, int w) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && c0 >= 0 && c0 + C <= G && C * w <= WM_DEC_MAXB &&
+                   G <= m->cap_b && G <= m->cap_rows,
+               WM_ERR_INVALID, "panel: windows [%d, %d) of %d at width %d", c0, c0 + C, G, w);
+    return WM_OK;
+}
+
+int wm_model_panel_embed(wm_ctx *ctx, int G, int c0, int C, int w) {
+    WM_TRY(panel_check(ctx, G, c0, C, w));
+    WmModel *m = ctx->model;
+    return wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, 0, C, w, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dims.n_text_ctx,
+                              m->dx, m->dxb, m->dstats, m->dmean);
+}
+
+int wm_model_panel_step(wm_ctx *ctx, int G, int c0, int C, int w, bool want_logits, const WmAlignCap *cap) {
+    WM_TRY(panel_check(ctx, G, c0, C, w));
+    WmDecodeMode mode;
+    mode.panel = w;
+    WmAlignCap cs;
+    if (cap) {   // the slice's chunks start at c0 of the capture buffer [G][Tq][J][64]
+        cs = *cap;
+        cs.q = cap->q + (size_t)c0 * cap->Tq * cap->J * 64;
+    }
+    // (w == 1, the last panel of a pass with T mod width == 1: the plain step launches over the slice's windows)
+    return decode_step_impl(ctx, C * w, want_logits, 0, ctx->model->dims.n_vocab - 1, cap ? &cs : nullptr, mode, 0, G, c0);
+}
+
+int wm_model_panel_advance(wm_ctx *ctx, int G, int c0, int C, int w, int w_next) {
+    WM_TRY(panel_check(ctx, G, c0, C, w));
+    WmModel *m = ctx->model;
+    if (w_next > 0)   // the next panel's embedding reads the position BEFORE it advances (stream order)
+        WM_TRY(wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, w, C, w_next, m->tok_emb, m->dec_pos, m->dims.n_text_state,
+                                  m->dims.n_text_ctx, m->dx, m->dxb, m->dstats, m->dmean));
+    return wm_dec_pos_add(ctx, m->dpos, w);
 }
 
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode) {

@@ -221,8 +221,13 @@ struct WmDecodeMode {
     // (wm_model_beam_close) instead of the arg-max; above 1 the rows are a candidate group (n_cand = beam).
     int beam = 0;
     bool rep = false;       // the repetition rules apply (wm_set_repetition_rules, WmRepDev): wm_repeat_state + DE_LOGITS_XR; needs x
+    // Panel width of a teacher-forced pass (wm_set_teacher_panel; 1: none): the step's rows are windows x panel, row c * panel + s
+    // is position *dpos + s of window c -- the self-attention cache holds one entry per WINDOW, row (c, s) appends at and reads up
+    // to its own position, the cross-attention is the candidate-group launch (wm_model_panel_step).  The teacher-forced entries
+    // run eagerly, but a mode is a graph key member by member, so it is compared like the others.
+    int panel = 1;
     bool operator==(const WmDecodeMode &o) const {
-        return rep == o.rep && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return panel == o.panel && rep == o.rep && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -372,6 +377,7 @@ struct WmModel {
     std::vector<int32_t> align_l, align_h;
     WmDevBuf align_ws;
     float *align_dbg_matrix = nullptr;
+    int teacher_panel = 1;   // wm_set_teacher_panel: positions per step of the teacher-forced passes (a launch policy: same bits)
     // wm_transcribe_mel_beam: the group's beam state (WmBeamDev; allocated once at its largest size, so captured graphs keep
     // their addresses) and the debug library's one-shot trace capture (host destination, null in the product) with its
     // device buffer
@@ -452,6 +458,19 @@ int wm_model_beam_close(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mo
 size_t wm_model_beam_state_bytes(const WmModel *m);   // the part of beam_ws in front of fin_tok (what a drain copies whole)
 void wm_model_drop_graphs(WmModel *m);
 int wm_model_set_pos(wm_ctx *ctx, int pos);
+// Teacher-forced PANEL pass (wm_set_teacher_panel).  A panel step is wm_model_decode_step's layer body over C windows x w
+// consecutive positions (mode.panel = w, rows c * w + s <-> (window c0 + c, position *dpos + s)): the windows are rows
+// c0 .. c0 + C - 1 of a group of G whose token buffer m->dseq is [n_text_ctx][G] and whose caches are [L][2][G][H][.][64].
+// Row arithmetic is the step path's, so every output bit is the step path's.
+// wm_model_panel_slices: how a group of G windows is cut for a pass of T positions at the context's width -- *C windows per
+// slice, *w <= width positions per panel (C * w <= WM_DEC_MAXB; the measured rule: the fewest steps).
+void wm_model_panel_slices(int G, int width, int T, int *C, int *w);
+// embed positions *dpos .. *dpos + w - 1 of the slice's windows into rows c * w + s of m->dx / dxb / dstats / dmean
+int wm_model_panel_embed(wm_ctx *ctx, int G, int c0, int C, int w);
+int wm_model_panel_step(wm_ctx *ctx, int G, int c0, int C, int w, bool want_logits, const WmAlignCap *cap);
+// *dpos += w and the embedding of the next panel (w_next positions; 0: none) -- what wm_model_close_step does for a step,
+// without the arg-max nobody reads in teacher forcing
+int wm_model_panel_advance(wm_ctx *ctx, int G, int c0, int C, int w, int w_next);
 
 // ---------------------------------------------------------------- kernel launchers ----
 // gemm.hip
@@ -497,6 +516,7 @@ int wm_enc_attention(wm_ctx *ctx, const bf16_t *qk, const bf16_t *vt, bf16_t *at
                      int S, int S_pad, int d);
 
 // dec_kernels.hip
+static_assert(WM_MAX_TEACHER_PANEL == WM_MAX_BEST_OF, "a panel's cross-attention is dec_xcand_attn_kernel: its instantiated widths");
 constexpr int WM_DEC_MAXB = 128;  // decode group: up to eight batch blocks of 16 rows (the MFMA M dimension)
 static_assert(WM_XIDS_CAND == WM_DEC_MAXB + 16, "WmXDev::ids: the candidate words follow the padded sample ids");
 constexpr int WM_NLIVE_RING = 16;  // pinned host slots for the per-burst live-row counts (early stop)
@@ -506,7 +526,9 @@ constexpr int WM_MAXSPLIT = 8;  // stream partials of a (sequence, head) pair of
 // greedy logits kernel does none of it
 // DE_LOGITS_XR: DE_LOGITS_X with the repetition rules (WmRepDev): the same body, the row's penalty and ban words applied to
 // the logit first -- again its own instantiations, so DE_LOGITS_X stays instruction for instruction what it was
-enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5, DE_LOGITS_XR = 6 };
+// DE_QKV_P: DE_QKV of a panel step (DecGemvArgs::panel = w): k / v of row r go to cache entry r / w at position *pos_ptr + r % w --
+// its own instantiations, so DE_QKV stays instruction for instruction what it was
+enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5, DE_LOGITS_XR = 6, DE_QKV_P = 7 };
 struct DecGemvArgs {
     int epi;
     int B, N, K;
@@ -542,6 +564,7 @@ struct DecGemvArgs {
     int pf_rows, pf_k;
     int pf_head_major;     // the next launch is wm_dec_xattn_fq: (pairs per XCD) place every head's tiles on the XCD(s) that run it
     WmRepDev rep;          // DE_LOGITS_XR: repetition rules (rep.par non-null)
+    int panel;             // DE_QKV_P: panel width w (1 .. WM_MAX_TEACHER_PANEL); kcache / vcache are [ceil(B / w)][H][T][64]
 };
 int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a);
 // cross_attn_ln + query projection fused INTO the cross-attention launch (96 .. 256 pairs, alone on the device): qa = the
@@ -560,6 +583,13 @@ int wm_ln_fold(wm_ctx *ctx, const bf16_t *W, const float *g, const float *beta, 
 // max(*pos_ptr - off[b], 0); the same argument of wm_argmax_embed, and of wm_dec_self_attention (keys [min(off[b], pos), pos])
 int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const bf16_t *emb, const float *pemb,
                  int d, float *x, bf16_t *xb, float *stats_out, float *mean_buf /*nullable*/, const int *off = nullptr);
+// Panel embedding: row c * w + s (c < C, s < w) = token seq[(*pos_ptr + s) * seq_stride + c] at positional row *pos_ptr + s.
+// Position 0 is embedded with wm_dec_embed's four-wave sums, every later one with the closing kernels' embed_row: the bits of
+// the step path's first embedding and of its closes.  pos_add: added to *pos_ptr (the embedding of the NEXT panel).
+int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, const bf16_t *emb,
+                       const float *pemb, int d, int n_ctx, float *x, bf16_t *xb, float *stats_out, float *mean_buf);
+// *pos_ptr += add (one thread)
+int wm_dec_pos_add(wm_ctx *ctx, int *pos_ptr, int add);
 // Single-query attention over a K/V cache [B][H][T_stride][64] -> bf16 head outputs att[B][H*64] in WL_TILED order.
 // Keys 0 .. n-1 with n = *pos_ptr + 1 when pos_ptr != null, else n_keys.
 int wm_dec_attn_splits(int B, int H);
@@ -578,6 +608,10 @@ int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const b
                           int n_keys, const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0,
                           int pf_k = 0, const int *live_rows = nullptr, const int *n_live = nullptr,
                           const int *off = nullptr);
+// The self-attention of a panel step: B = C * w rows, the pair (r, h) reads cache entry (r / w, h) of kc / vc [C][H][T_stride][64]
+// with *pos_ptr + r % w + 1 keys; query and output are row r.  Row bits = wm_dec_self_attention's at that position.
+int wm_dec_self_attention_panel(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int w, int H, int T_stride,
+                                const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0, int pf_k = 0);
 // Close a decode step (one workgroup): reduce the per-tile packed maxima of a DE_LOGITS launch;
 // chosen token of row b -> seq[(*pos_ptr + 1) * B + b] when that position is >= n_prompt;
 // (token - arg_first) -> result[b]; embed the tokens of position *pos_ptr + 1 into x (+ LayerNorm
@@ -630,11 +664,14 @@ int wm_xkv_rows(wm_ctx *ctx, bf16_t *group, long group_rows, bf16_t *store, cons
 
 // align.hip (word-level timestamps)
 // the alignment heads' queries of decode position *pos_ptr: dq [B][d] -> cap[b][*pos_ptr][L.slot0 + k][64]
+// panel > 1: dq holds B = windows x panel rows, row r is position *pos_ptr + r % panel of chunk r / panel
 int wm_align_capture_q(wm_ctx *ctx, const float *dq, int d, int B, const WmAlignLayer &L, float *cap, int Tq, int J,
-                       const int *pos_ptr);
+                       const int *pos_ptr, int panel = 1);
 // position pos = *pos_ptr, i = pos - S in [0, n_text[b]): prob[b][i] = softmax(logits[b][0 : eot])[seq[pos + 1][b]]
+// panel > 1: logits holds B = windows x panel rows (row r: position *pos_ptr + r % panel of chunk r / panel; n_text and prob
+// per chunk); seq_stride: chunks per position of seq (0: B)
 int wm_align_token_prob(wm_ctx *ctx, const float *logits, long ldo, const int *seq, const int *pos_ptr, int B, int S, int eot,
-                        const int *n_text, float *prob, int max_text);
+                        const int *n_text, float *prob, int max_text, int panel = 1, int seq_stride = 0);
 // scores -> softmax -> z-score -> median filter -> head mean -> a.x (max_n: largest n_text, max_m: largest n_frames / 2)
 int wm_align_matrix(wm_ctx *ctx, const WmAlignDev &a, int max_n, int max_m);
 // trace words a chunk of max_rows rows needs in HBM (when its trace does not fit the DTW kernel's LDS)

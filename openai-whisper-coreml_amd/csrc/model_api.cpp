@@ -120,6 +120,13 @@ extern "C" int wm_set_repetition_rules(wm_ctx *ctx, float repetition_penalty, in
         return wm_model_set_repetition_rules(c, repetition_penalty, no_repeat_ngram_size, eot);
     });
 } WM_API_CATCH
+extern "C" int wm_set_teacher_panel(wm_ctx *ctx, int width) try {
+    WM_MODEL(ctx);
+    (void)m;
+    WM_REQUIRE(width >= 1 && width <= WM_MAX_TEACHER_PANEL, WM_ERR_INVALID, "set_teacher_panel: width %d outside [1, %d]", width,
+               WM_MAX_TEACHER_PANEL);
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { c->model->teacher_panel = width; return (int)WM_OK; });
+} WM_API_CATCH
 extern "C" int wm_set_lanes(wm_ctx *ctx, int n_lanes) try {
     WM_REQUIRE(ctx, WM_ERR_INVALID, "null context");
     WM_REQUIRE(n_lanes >= 0 && n_lanes <= 8, WM_ERR_INVALID, "set_lanes: 0 (default) .. 8");
@@ -216,6 +223,29 @@ static int load_xa(wm_ctx *ctx, const float *xa, int B, wm_mem mem) {
     return wm_model_cross_kv(ctx, B);
 }
 
+// wm_decode_logits at a panel width > 1 (wm_set_teacher_panel): slices of windows, each walking its panels from position 0;
+// the logits of row (c, s) of a panel at position t go to out [B][T][V] at [c0 + c][t + s] (strided copies)
+static int logits_in_panels(wm_ctx *ctx, int B, int T, int width, float *d_out) {
+    WmModel *m = ctx->model;
+    const int V = m->dims.n_vocab;
+    int Cs = 0, w = 0;
+    wm_model_panel_slices(B, width, T, &Cs, &w);
+    for (int c0 = 0; c0 < B; c0 += Cs) {
+        const int C = std::min(Cs, B - c0);
+        if (c0 > 0) WM_TRY(wm_model_set_pos(ctx, 0));
+        WM_TRY(wm_model_panel_embed(ctx, B, c0, C, std::min(w, T)));
+        for (int t = 0; t < T; t += w) {
+            const int wp = std::min(w, T - t);
+            WM_TRY(wm_model_panel_step(ctx, B, c0, C, wp, true, nullptr));
+            for (int s = 0; s < wp; ++s)
+                WM_HIP(hipMemcpy2DAsync(d_out + ((size_t)c0 * T + t + s) * V, (size_t)T * V * 4, m->dlogits + (size_t)s * m->vpad,
+                                        (size_t)wp * m->vpad * 4, (size_t)V * 4, C, hipMemcpyDeviceToDevice, ctx->stream));
+            if (t + wp < T) WM_TRY(wm_model_panel_advance(ctx, B, c0, C, wp, std::min(w, T - t - wp)));
+        }
+    }
+    return WM_OK;
+}
+
 extern "C" int wm_decode_logits(wm_ctx *ctx, const int32_t *tokens, int B, int T, const float *xa,
                                 float *logits, wm_mem mem) try {
     WM_MODEL(ctx);
@@ -260,7 +290,8 @@ extern "C" int wm_decode_logits(wm_ctx *ctx, const int32_t *tokens, int B, int T
     WM_HIP(hipMemcpyAsync(m->dseq, tb.data(), tb.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     WM_HIP(hipStreamSynchronize(ctx->stream));  // fences `tb`
     WM_TRY(wm_model_set_pos(ctx, 0));
-    WM_TRY(wm_model_embed_first(ctx, B));
+    const int width = m->teacher_panel;   // wm_set_teacher_panel: > 1 = the pass in panels (same bits, fewer launches)
+    if (width == 1) WM_TRY(wm_model_embed_first(ctx, B));
     float *d_out = logits;
     char *st = nullptr;
     if (mem == WM_MEM_HOST) {
@@ -269,7 +300,8 @@ extern "C" int wm_decode_logits(wm_ctx *ctx, const int32_t *tokens, int B, int T
         d_out = (float *)st;
     }
     int rc = WM_OK;
-    for (int t = 0; t < T && rc == WM_OK; ++t) {
+    if (width > 1) rc = logits_in_panels(ctx, B, T, width, d_out);
+    else for (int t = 0; t < T && rc == WM_OK; ++t) {
         rc = wm_model_decode_step(ctx, B, true, 0, V - 1);
         if (rc != WM_OK) break;
         // dlogits [B][vpad] -> out [B][T][V], row t
@@ -1508,12 +1540,32 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
         Ly.head[Ly.n++] = c.hh[j];
     }
     const WmAlignCap cap = {layers.data(), q, T, J};
-    WM_TRY(wm_model_embed_first(ctx, Bg));
-    for (int p = 0; p < T; ++p) {
-        const bool want = p >= S && p < S + nmax;   // rows whose logits give a token probability
-        WM_TRY(wm_model_decode_step(ctx, Bg, want, 0, V - 1, &cap));
-        if (want) WM_TRY(wm_align_token_prob(ctx, m->dlogits, m->vpad, m->dseq, m->dpos, Bg, S, c.eot, ints, prob, std::max(c.max_text, 1)));
-        if (p + 1 < T) WM_TRY(wm_model_close_step(ctx, Bg, T, true, nullptr, 0));
+    const int width = m->teacher_panel;   // wm_set_teacher_panel: > 1 = the pass in panels (same bits, ceil(T / w) steps)
+    if (width > 1) {
+        int Cs = 0, w = 0;
+        wm_model_panel_slices(Bg, width, T, &Cs, &w);
+        for (int c0 = 0; c0 < Bg; c0 += Cs) {   // a slice walks all its panels, then the next slice starts at position 0
+            const int C = std::min(Cs, Bg - c0);
+            if (c0 > 0) WM_TRY(wm_model_set_pos(ctx, 0));
+            WM_TRY(wm_model_panel_embed(ctx, Bg, c0, C, std::min(w, T)));
+            for (int p = 0; p < T; p += w) {
+                const int wp = std::min(w, T - p);   // the last panel is narrower: no row ever has a position >= T
+                const bool want = p + wp > S && p < S + nmax;   // some row's logits give a token probability
+                WM_TRY(wm_model_panel_step(ctx, Bg, c0, C, wp, want, &cap));
+                if (want)
+                    WM_TRY(wm_align_token_prob(ctx, m->dlogits, m->vpad, m->dseq + c0, m->dpos, C * wp, S, c.eot, ints + c0,
+                                               prob + (size_t)c0 * std::max(c.max_text, 1), std::max(c.max_text, 1), wp, Bg));
+                if (p + wp < T) WM_TRY(wm_model_panel_advance(ctx, Bg, c0, C, wp, std::min(w, T - p - wp)));
+            }
+        }
+    } else {
+        WM_TRY(wm_model_embed_first(ctx, Bg));
+        for (int p = 0; p < T; ++p) {
+            const bool want = p >= S && p < S + nmax;   // rows whose logits give a token probability
+            WM_TRY(wm_model_decode_step(ctx, Bg, want, 0, V - 1, &cap));
+            if (want) WM_TRY(wm_align_token_prob(ctx, m->dlogits, m->vpad, m->dseq, m->dpos, Bg, S, c.eot, ints, prob, std::max(c.max_text, 1)));
+            if (p + 1 < T) WM_TRY(wm_model_close_step(ctx, Bg, T, true, nullptr, 0));
+        }
     }
     WM_HIP(hipEventRecord(ev[2], ctx->stream));
     // alignment kernels and DTW

@@ -209,6 +209,15 @@ struct Whisper {
         try check(f(ctx, penalty, noRepeatNgramSize, eot))
     }
 
+    /// Positions per decoder step (1 ... 8; 1 = the default) of the teacher-forced passes behind align / alignMel / alignWindows /
+    /// decodeLogits on this context (wm_set_teacher_panel).  A launch policy: the results are bit-identical for every width.
+    /// Not compiled in this repository (see the top of the file).
+    func setTeacherPanel(_ width: Int32) throws {
+        typealias PanelFn = @convention(c) (OpaquePointer, Int32) -> Int32
+        let f: PanelFn = try sym("wm_set_teacher_panel")
+        try check(f(ctx, width))
+    }
+
     /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
     /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
     /// Not compiled in this repository (see the top of the file).

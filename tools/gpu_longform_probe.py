@@ -5,7 +5,7 @@ given as argv[1] (default base), every matrix scaled by weights.lively_gain so t
 length (argv[2], default 8: 10 .. 150 s), the production vocabulary's token ids, text context n_text_ctx.  Prints one JSON
 line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form.
 
-    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words | --reuse]
+    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words [--teacher-panel W] | --reuse]
 
 --condition: the cost of condition_on_previous_text instead.  One more JSON line: wall seconds of the long form with
 conditioning off and on (the same recordings, after a warm-up of each; with the default fallback thresholds and with the
@@ -20,6 +20,8 @@ through the alignment; a synthetic vocabulary (one piece per text token) is writ
 line: wall seconds of the long form with word_timestamps off and on, interleaved, three runs each after a warm-up of
 each, the windows and words of a run, and over the wm_align_mel calls of one run their number, rows, wall time and the
 wm_last_stage_ms split (window gather + encoder + cross K/V, teacher-forced pass, alignment kernels + DTW).
+--teacher-panel W (with --words): a third interleaved run, word_timestamps on with wm_set_teacher_panel(W) (label on_panel; the
+plain `on` run is width 1); its result is asserted equal to the width-1 run's, and the line gains the panel run's stage split.
 
 --reuse: the cost and the gain of reuse_encoder (window sets) instead.  Two configurations -- (a) the default fallback, where
 the synthetic model takes all six temperatures, (b) fallback off with word_timestamps -- each with reuse_encoder off / on
@@ -43,6 +45,11 @@ b = pkg.binding
 CONDITION = "--condition" in sys.argv
 WORDS = "--words" in sys.argv
 REUSE = "--reuse" in sys.argv
+PANEL = None
+if "--teacher-panel" in sys.argv:
+    i = sys.argv.index("--teacher-panel")
+    PANEL = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words", "--reuse")]
 name = argv[0] if len(argv) > 0 else "base"
 N = int(argv[1]) if len(argv) > 1 else 8
@@ -165,17 +172,35 @@ def words_probe():
     on = dict(keep, word_timestamps=True, no_timestamps=50363)
     ctx.transcribe_long(recs, **kw, **keep)
     ctx.transcribe_long(recs, **kw, **on)
-    walls = dict(off=[], on=[])
+    runs = [("off", keep, None), ("on", on, 1 if PANEL else None)] + ([("on_panel", on, PANEL)] if PANEL else [])
+    if PANEL:
+        ctx.set_teacher_panel(PANEL)
+        ctx.transcribe_long(recs, **kw, **on)
+    walls = {label: [] for label, _, _ in runs}
+    outs, stages = {}, {}
     for _ in range(3):
-        for label, extra in (("off", keep), ("on", on)):
+        for label, extra, width in runs:
+            if width is not None:
+                ctx.set_teacher_panel(width)
             del calls[:]
             t0 = time.perf_counter()
             out = ctx.transcribe_long(recs, **kw, **extra)
             walls[label].append(time.perf_counter() - t0)
+            outs[label] = out
+            stages[label] = [sum(c["stage_ms"][i] for c in calls) for i in range(3)]
             if label == "off":
                 windows_off = sum(len(o["windows"]) for o in out)
     ctx.align_mel = inner
-    stage = [sum(c["stage_ms"][i] for c in calls) for i in range(3)]
+    extra_out = {}
+    if PANEL:
+        ctx.set_teacher_panel(1)
+        assert outs["on_panel"] == outs["on"], "the panel width changed the result"
+        sp = stages["on_panel"]
+        extra_out = dict(teacher_panel=PANEL, on_panel_over_off=float(np.median(walls["on_panel"]) / np.median(walls["off"])),
+                         on_panel_over_on=float(np.median(walls["on_panel"]) / np.median(walls["on"])),
+                         align_stage_ms_panel=dict(encoder_cross_kv=sp[0], teacher_forced=sp[1], alignment_dtw=sp[2]))
+    out = outs["on"]
+    stage = stages["on"]
     print(json.dumps(dict(model=name, recordings=N, audio_s=audio_s, wall_s=walls,
                           median_wall_s={k: float(np.median(v)) for k, v in walls.items()},
                           on_over_off=float(np.median(walls["on"]) / np.median(walls["off"])),
@@ -184,7 +209,8 @@ def words_probe():
                           align_calls=len(calls), align_rows=sum(c["rows"] for c in calls),
                           align_text_tokens=sum(c["text_tokens"] for c in calls),
                           align_wall_s=sum(c["wall"] for c in calls),
-                          align_stage_ms=dict(encoder_cross_kv=stage[0], teacher_forced=stage[1], alignment_dtw=stage[2]))))
+                          align_stage_ms=dict(encoder_cross_kv=stage[0], teacher_forced=stage[1], alignment_dtw=stage[2]),
+                          **extra_out)))
 
 
 def reuse_probe():
