@@ -15,6 +15,232 @@
 #include "beam.h"
 #include "model.h"
 
+// ---------------------------------------------------------------- staging, timing and capture: what every hook below goes through
+// The only place in this file that allocates or frees device memory, creates or destroys events, streams and graphs, or begins
+// and ends a stream capture.  A hook that fails half-way hands back everything it took and leaves the context's stream usable.
+namespace {
+// Device allocations of one hook call, freed when the hook returns (on an error path too).  Lifetime rule: the pool is
+// declared AFTER every host buffer it uploads from or downloads into, so that its hipFree (which waits for the device) runs
+// before those buffers die.
+struct DevPool {
+    std::vector<void *> v;
+    DevPool() = default;
+    DevPool(const DevPool &) = delete;
+    DevPool &operator=(const DevPool &) = delete;
+    ~DevPool() {
+        for (void *p : v) (void)hipFree(p);
+    }
+    // bytes of `fill` (a byte value), then the host data when given.  The 512 bytes of slack are a guard band behind
+    // host-staged buffers; nothing relies on them: every kernel read of these buffers is clamped to the group's rows and the
+    // matrix's tiles (gemv_unit_load), and each buffer is sized for what its kernel may write.
+    template <class T>
+    int get(T **d, const void *h, size_t bytes, hipStream_t s, int fill = 0) {
+        void *p = nullptr;
+        WM_HIP(hipMalloc(&p, bytes + 512));
+        v.push_back(p);
+        *d = static_cast<T *>(p);
+        WM_HIP(hipMemsetAsync(p, fill, bytes + 512, s));
+        if (h) WM_HIP(hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, s));
+        return WM_OK;
+    }
+};
+
+// ---- bf16 (round to nearest even) and the WL_TILED order
+bf16_t f2bf(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (bf16_t)(u >> 16);
+}
+void to_bf16(const float *in, std::vector<bf16_t> &out, size_t n) {
+    out.resize(n);
+    for (size_t i = 0; i < n; ++i) out[i] = f2bf(in[i]);
+}
+void from_bf16(const std::vector<bf16_t> &in, float *out) {
+    for (size_t i = 0; i < in.size(); ++i) {
+        uint32_t u = (uint32_t)in[i] << 16;
+        memcpy(&out[i], &u, 4);
+    }
+}
+// [rows][K] f32 -> bf16 in WL_TILED order, rows padded to 16 with zeros
+void tile_bf16(const float *m, size_t rows, size_t K, std::vector<bf16_t> &out) {
+    const size_t rpad = (rows + 15) / 16 * 16;
+    std::vector<float> t(rpad * K, 0.f);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t k = 0; k < K; ++k) t[wm_tiled_offset(r, k, K)] = m[r * K + k];
+    to_bf16(t.data(), out, t.size());
+}
+// WL_TILED bf16 [rows][K] -> row-major f32
+void untile_bf16(const std::vector<bf16_t> &t, size_t rows, size_t K, float *out) {
+    std::vector<bf16_t> lin(rows * K);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t k = 0; k < K; ++k) lin[r * K + k] = t[wm_tiled_offset(r, k, K)];
+    from_bf16(lin, out);
+}
+void fill_bf16(std::vector<bf16_t> &v, size_t n) { v.assign(n, (bf16_t)WMDBG_SENTINEL_BF16); }
+void fill_f32(std::vector<float> &v, size_t n) {
+    const uint32_t u = WMDBG_SENTINEL_F32;
+    float f;
+    memcpy(&f, &u, 4);
+    v.assign(n, f);
+}
+// device bf16 -> host f32 (widened); synchronous: the stream has drained when it returns
+int down_bf16(const void *d, size_t n, float *out, hipStream_t s) {
+    std::vector<bf16_t> t(n);
+    WM_HIP(hipMemcpyAsync(t.data(), d, n * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    from_bf16(t, out);
+    return WM_OK;
+}
+// device WL_TILED bf16 [rows padded to 16][K] -> host row-major f32 [rows][K]; synchronous.  The attention kernels store their
+// head outputs [B][H * 64] this way: the out-projection's tiled A-operand order.
+int down_tiled_bf16(const bf16_t *d, size_t rows, size_t K, float *out, hipStream_t s) {
+    std::vector<bf16_t> t((rows + 15) / 16 * 16 * K);
+    WM_HIP(hipMemcpyAsync(t.data(), d, t.size() * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    untile_bf16(t, rows, K, out);
+    return WM_OK;
+}
+
+// ---- The decoder's partial row statistics of a [B][K] f32 matrix: per 16-row block (stride 2 K floats) K / 16 parts (part p =
+// columns 16 p .. 16 p + 15) of [16 rows][2] = (sum, sum of squares).  The tests compare these on bits: per row, k ascends
+// into its part's slot, and the parts ascend when they are summed.
+size_t stat_at(int K, size_t b, int part, int c) { return (b >> 4) * (size_t)(2 * K) + ((size_t)part * 16 + (b & 15)) * 2 + c; }
+void stats_pack(const float *x, int B, int K, std::vector<float> &st) {
+    st.assign((size_t)((B + 15) / 16) * 2 * K, 0.f);
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < K; ++k) {
+            const float v = x[(size_t)b * K + k];
+            st[stat_at(K, b, k >> 4, 0)] += v;
+            st[stat_at(K, b, k >> 4, 1)] += v * v;
+        }
+}
+// (sum, sum of squares) of row b to out2
+void stats_sum(const float *st, int K, int b, float *out2) {
+    float s1 = 0.f, s2 = 0.f;
+    for (int part = 0; part < K / 16; ++part) {
+        s1 += st[stat_at(K, b, part, 0)];
+        s2 += st[stat_at(K, b, part, 1)];
+    }
+    out2[0] = s1;
+    out2[1] = s2;
+}
+
+// The A operand of a LayerNorm-folded GEMV as the decoder holds it: the producer's partial statistics of the raw f32 rows,
+// the rows' f32 means, and the bf16 activations in WL_TILED order -- of x - mean when `centre`, else of x (the means are then
+// not handed to the kernel).
+void stage_ln_rows(const float *x, int B, int K, bool centre, std::vector<bf16_t> &x16, std::vector<float> &st, std::vector<float> &mean) {
+    stats_pack(x, B, K, st);
+    mean.assign((size_t)B, 0.f);
+    std::vector<float> xc((size_t)B * K);
+    for (int b = 0; b < B; ++b) {
+        float s1 = 0.f;
+        for (int k = 0; k < K; ++k) s1 += x[(size_t)b * K + k];
+        mean[b] = s1 / (float)K;
+        for (int k = 0; k < K; ++k) xc[(size_t)b * K + k] = centre ? x[(size_t)b * K + k] - mean[b] : x[(size_t)b * K + k];
+    }
+    tile_bf16(xc.data(), (size_t)B, (size_t)K, x16);
+}
+
+// ---- timing and capture
+// The two events of a timed region, destroyed with the object.
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    int init() {
+        WM_HIP(hipEventCreate(&e0));
+        WM_HIP(hipEventCreate(&e1));
+        return WM_OK;
+    }
+    int start(hipStream_t s) {
+        WM_HIP(hipEventRecord(e0, s));
+        return WM_OK;
+    }
+    // microseconds since start(), once the stream has drained
+    int stop_us(hipStream_t s, float *us) {
+        WM_HIP(hipEventRecord(e1, s));
+        WM_HIP(hipStreamSynchronize(s));
+        float ms = 0.f;
+        WM_HIP(hipEventElapsedTime(&ms, e0, e1));
+        *us = ms * 1e3f;
+        return WM_OK;
+    }
+};
+
+// One captured launch chain of a stream.  A capture it began is always ended -- on an error path too, where the graph is
+// discarded -- so the stream stays usable; the graph and its exec are destroyed with the object.
+struct GraphRun {
+    hipStream_t s;
+    bool capturing = false;
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ge = nullptr;
+    explicit GraphRun(hipStream_t s_) : s(s_) {}
+    GraphRun(const GraphRun &) = delete;
+    GraphRun &operator=(const GraphRun &) = delete;
+    ~GraphRun() {
+        if (capturing) (void)hipStreamEndCapture(s, &g);
+        if (ge) (void)hipGraphExecDestroy(ge);
+        if (g) (void)hipGraphDestroy(g);
+    }
+    int begin() {
+        WM_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        capturing = true;
+        return WM_OK;
+    }
+    int end() {
+        capturing = false;   // a failed end has ended the capture too
+        WM_HIP(hipStreamEndCapture(s, &g));
+        WM_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+        return WM_OK;
+    }
+    // one warm replay, then the timed one: microseconds of a whole replay
+    int replay_us(EventPair &ev, float *us) {
+        WM_HIP(hipGraphLaunch(ge, s));
+        WM_HIP(hipStreamSynchronize(s));
+        WM_TRY(ev.start(s));
+        WM_HIP(hipGraphLaunch(ge, s));
+        return ev.stop_us(s, us);
+    }
+};
+
+// A second stream that a capturing stream forks to and joins from: a parallel branch of the captured graph.  Declared before
+// the GraphRun whose capture it joins, so that the capture has ended when the stream is destroyed.
+struct SideBranch {
+    hipStream_t s2 = nullptr;
+    hipEvent_t ef = nullptr, ej = nullptr;
+    SideBranch() = default;
+    SideBranch(const SideBranch &) = delete;
+    SideBranch &operator=(const SideBranch &) = delete;
+    ~SideBranch() {
+        if (ef) (void)hipEventDestroy(ef);
+        if (ej) (void)hipEventDestroy(ej);
+        if (s2) (void)hipStreamDestroy(s2);
+    }
+    int init() {
+        WM_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+        WM_HIP(hipEventCreateWithFlags(&ef, hipEventDisableTiming));
+        WM_HIP(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
+        return WM_OK;
+    }
+    int fork(hipStream_t s) {
+        WM_HIP(hipEventRecord(ef, s));
+        WM_HIP(hipStreamWaitEvent(s2, ef, 0));
+        return WM_OK;
+    }
+    int join(hipStream_t s) {
+        WM_HIP(hipEventRecord(ej, s2));
+        WM_HIP(hipStreamWaitEvent(s, ej, 0));
+        return WM_OK;
+    }
+};
+}  // namespace
+
 // ---------------------------------------------------------------- host-only test hooks
 int wm_gemm_set_tile_override(int tile);
 extern "C" int wmdbg_set_gemm_tile(int tile) { return wm_gemm_set_tile_override(tile); }
@@ -74,28 +300,6 @@ extern "C" int wmdbg_mel80(float *out) {
 }
 
 // ------------------------------------------------------------------ per-kernel test hooks
-static int up(void **d, const void *h, size_t bytes, hipStream_t s) {
-    WM_HIP(hipMalloc(d, bytes + 512));
-    WM_HIP(hipMemsetAsync(*d, 0, bytes + 512, s));
-    if (h) WM_HIP(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, s));
-    return WM_OK;
-}
-static void to_bf16(const float *in, std::vector<bf16_t> &out, size_t n) {
-    out.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-        uint32_t u;
-        memcpy(&u, &in[i], 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        out[i] = (bf16_t)(u >> 16);
-    }
-}
-static void from_bf16(const std::vector<bf16_t> &in, float *out) {
-    for (size_t i = 0; i < in.size(); ++i) {
-        uint32_t u = (uint32_t)in[i] << 16;
-        memcpy(&out[i], &u, 4);
-    }
-}
-
 extern "C" int wmdbg_gemm(wm_ctx *ctx, const float *A, const float *W, const float *bias, float *C, int M, int N,
                           int K, int epi) {
     WM_TRY(wm_ctx_make_current(ctx));
@@ -104,55 +308,40 @@ extern "C" int wmdbg_gemm(wm_ctx *ctx, const float *A, const float *W, const flo
     std::vector<bf16_t> a16, w16;
     to_bf16(A, a16, (size_t)M * K);
     to_bf16(W, w16, (size_t)N * K);
-    void *dA, *dW, *dB = nullptr, *dC;
-    hipStream_t s = ctx->stream;
-    WM_TRY(up(&dA, a16.data(), a16.size() * 2, s));
-    WM_TRY(up(&dW, w16.data(), w16.size() * 2, s));
-    if (bias) WM_TRY(up(&dB, bias, (size_t)N * 4, s));
     const bool f32out = (epi == EPI_F32 || epi == EPI_RESID_F32);
-    WM_TRY(up(&dC, epi == EPI_RESID_F32 ? C : nullptr, (size_t)M * N * (f32out ? 4 : 2), s));
+    DevPool pool;
+    hipStream_t s = ctx->stream;
     GemmArgs g;
     memset(&g, 0, sizeof(g));
-    g.A = (const bf16_t *)dA; g.a_rpb = (long)M + 1; g.a_rstride = K;
-    g.W = (const bf16_t *)dW; g.bias = (const float *)dB; g.C = dC;
+    WM_TRY(pool.get(&g.A, a16.data(), a16.size() * 2, s));
+    WM_TRY(pool.get(&g.W, w16.data(), w16.size() * 2, s));
+    if (bias) WM_TRY(pool.get(&g.bias, bias, (size_t)N * 4, s));
+    WM_TRY(pool.get(&g.C, epi == EPI_RESID_F32 ? C : nullptr, (size_t)M * N * (f32out ? 4 : 2), s));
+    g.a_rpb = (long)M + 1; g.a_rstride = K;
     g.c_rpb = (long)M + 1; g.c_rstride = N; g.M = M; g.N = N; g.K = K; g.epi = epi;
-    int rc = wm_gemm(ctx, g);
-    if (rc == WM_OK) {
-        if (f32out) {
-            WM_HIP(hipMemcpyAsync(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost, s));
-            WM_HIP(hipStreamSynchronize(s));
-        } else {
-            std::vector<bf16_t> c16((size_t)M * N);
-            WM_HIP(hipMemcpyAsync(c16.data(), dC, c16.size() * 2, hipMemcpyDeviceToHost, s));
-            WM_HIP(hipStreamSynchronize(s));
-            from_bf16(c16, C);
-        }
-    }
-    (void)hipFree(dA); (void)hipFree(dW); (void)hipFree(dC);
-    if (dB) (void)hipFree(dB);
-    return rc;
+    WM_TRY(wm_gemm(ctx, g));
+    if (!f32out) return down_bf16(g.C, (size_t)M * N, C, s);
+    WM_HIP(hipMemcpyAsync(C, g.C, (size_t)M * N * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 extern "C" int wmdbg_layernorm(wm_ctx *ctx, const float *x, const float *g, const float *b, int rows, int d,
                                float *out_f32, float *out_bf16_as_f32) {
     WM_TRY(wm_ctx_make_current(ctx));
-    void *dx, *dg, *db, *of, *ob;
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    WM_TRY(up(&dx, x, (size_t)rows * d * 4, s));
-    WM_TRY(up(&dg, g, (size_t)d * 4, s));
-    WM_TRY(up(&db, b, (size_t)d * 4, s));
-    WM_TRY(up(&of, nullptr, (size_t)rows * d * 4, s));
-    WM_TRY(up(&ob, nullptr, (size_t)rows * d * 2, s));
-    int rc = wm_layernorm(ctx, (const float *)dx, (const float *)dg, (const float *)db, rows, d, (bf16_t *)ob, (float *)of);
-    if (rc == WM_OK) {
-        std::vector<bf16_t> t((size_t)rows * d);
-        WM_HIP(hipMemcpyAsync(out_f32, of, (size_t)rows * d * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(t.data(), ob, t.size() * 2, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-        from_bf16(t, out_bf16_as_f32);
-    }
-    (void)hipFree(dx); (void)hipFree(dg); (void)hipFree(db); (void)hipFree(of); (void)hipFree(ob);
-    return rc;
+    const float *dx, *dg, *db;
+    float *of;
+    bf16_t *ob;
+    WM_TRY(pool.get(&dx, x, (size_t)rows * d * 4, s));
+    WM_TRY(pool.get(&dg, g, (size_t)d * 4, s));
+    WM_TRY(pool.get(&db, b, (size_t)d * 4, s));
+    WM_TRY(pool.get(&of, nullptr, (size_t)rows * d * 4, s));
+    WM_TRY(pool.get(&ob, nullptr, (size_t)rows * d * 2, s));
+    WM_TRY(wm_layernorm(ctx, dx, dg, db, rows, d, ob, of));
+    WM_HIP(hipMemcpyAsync(out_f32, of, (size_t)rows * d * 4, hipMemcpyDeviceToHost, s));
+    return down_bf16(ob, (size_t)rows * d, out_bf16_as_f32, s);
 }
 
 // The sampling noise of wm_transcribe as the device computes it (the DE_LOGITS_X epilogue's philox.h functions).
@@ -160,16 +349,14 @@ extern "C" int wmdbg_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi,
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(g && count >= 0, WM_ERR_INVALID, "bad args");
     if (count == 0) return WM_OK;
-    void *dg;
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    WM_TRY(up(&dg, nullptr, (size_t)count * 4, s));
-    int rc = wm_sample_noise(ctx, seed, chunk, gi, n0, count, (float *)dg);
-    if (rc == WM_OK) {
-        WM_HIP(hipMemcpyAsync(g, dg, (size_t)count * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-    }
-    (void)hipFree(dg);
-    return rc;
+    float *dg;
+    WM_TRY(pool.get(&dg, nullptr, (size_t)count * 4, s));
+    WM_TRY(wm_sample_noise(ctx, seed, chunk, gi, n0, count, dg));
+    WM_HIP(hipMemcpyAsync(g, dg, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 // Encoder attention on host q, k, v given as f32 [B][S][H*64] each (rounded to bf16 inside).
@@ -178,31 +365,25 @@ extern "C" int wmdbg_enc_attention(wm_ctx *ctx, const float *q, const float *k, 
     WM_TRY(wm_ctx_make_current(ctx));
     const int d = H * 64, S_pad = ((S + 63) / 64) * 64;
     const size_t M = (size_t)B * S;
-    std::vector<bf16_t> qk((M + 64) * 2 * d, 0), vt((size_t)B * H * 64 * S_pad, 0), tmp;
-    auto bf = [](float f) { uint32_t u; memcpy(&u, &f, 4); u += 0x7fffu + ((u >> 16) & 1u); return (bf16_t)(u >> 16); };
+    std::vector<bf16_t> qk((M + 64) * 2 * d, 0), vt((size_t)B * H * 64 * S_pad, 0);
     for (size_t mrow = 0; mrow < M; ++mrow)
         for (int j = 0; j < d; ++j) {
-            qk[mrow * 2 * d + j] = bf(q[mrow * d + j] * WM_ENC_QSCALE);   // the kernel's contract: pre-scaled queries
-            qk[mrow * 2 * d + d + j] = bf(k[mrow * d + j]);
+            qk[mrow * 2 * d + j] = f2bf(q[mrow * d + j] * WM_ENC_QSCALE);   // the kernel's contract: pre-scaled queries
+            qk[mrow * 2 * d + d + j] = f2bf(k[mrow * d + j]);
         }
     for (int b = 0; b < B; ++b)
         for (int s = 0; s < S; ++s)
             for (int j = 0; j < d; ++j)
-                vt[((size_t)(b * H + j / 64) * 64 + j % 64) * S_pad + wm_att_vt_pos((unsigned)s)] = bf(v[((size_t)b * S + s) * d + j]);
-    void *dqk, *dvt, *datt;
+                vt[((size_t)(b * H + j / 64) * 64 + j % 64) * S_pad + wm_att_vt_pos((unsigned)s)] = f2bf(v[((size_t)b * S + s) * d + j]);
+    DevPool pool;
     hipStream_t st = ctx->stream;
-    WM_TRY(up(&dqk, qk.data(), qk.size() * 2, st));
-    WM_TRY(up(&dvt, vt.data(), vt.size() * 2, st));
-    WM_TRY(up(&datt, nullptr, M * d * 2, st));
-    int rc = wm_enc_attention(ctx, (const bf16_t *)dqk, (const bf16_t *)dvt, (bf16_t *)datt, B, H, S, S_pad, d);
-    if (rc == WM_OK) {
-        tmp.resize(M * d);
-        WM_HIP(hipMemcpyAsync(tmp.data(), datt, tmp.size() * 2, hipMemcpyDeviceToHost, st));
-        WM_HIP(hipStreamSynchronize(st));
-        from_bf16(tmp, out);
-    }
-    (void)hipFree(dqk); (void)hipFree(dvt); (void)hipFree(datt);
-    return rc;
+    const bf16_t *dqk, *dvt;
+    bf16_t *datt;
+    WM_TRY(pool.get(&dqk, qk.data(), qk.size() * 2, st));
+    WM_TRY(pool.get(&dvt, vt.data(), vt.size() * 2, st));
+    WM_TRY(pool.get(&datt, nullptr, M * d * 2, st));
+    WM_TRY(wm_enc_attention(ctx, dqk, dvt, datt, B, H, S, S_pad, d));
+    return down_bf16(datt, M * d, out, st);
 }
 
 // Skinny decode GEMV: out[B][N] = LN?(x)[B][K] . W[N][K]^T + bias, driven the way the decoder drives it: bf16 activations,
@@ -214,61 +395,36 @@ extern "C" int wmdbg_dec_gemv(wm_ctx *ctx, const float *x, const float *ln_g, co
     WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB, WM_ERR_INVALID, "wmdbg_dec_gemv: B out of range");
     const int Npad = ((N + 15) / 16) * 16;
     std::vector<bf16_t> w16, x16;
-    std::vector<float> wp((size_t)Npad * K, 0.f);   // fragment-tiled order (WL_TILED)
-    for (size_t r = 0; r < (size_t)N; ++r)
-        for (size_t k = 0; k < (size_t)K; ++k) wp[wm_tiled_offset(r, k, (size_t)K)] = W[r * K + k];
-    to_bf16(wp.data(), w16, wp.size());
-    {   // activations in the fragment-tiled order the decoder keeps them in (rows padded to 16)
-        const int Bpad = ((B + 15) / 16) * 16;
-        std::vector<float> xp((size_t)Bpad * K, 0.f);
-        for (size_t b = 0; b < (size_t)B; ++b)
-            for (size_t k = 0; k < (size_t)K; ++k) xp[wm_tiled_offset(b, k, (size_t)K)] = x[b * K + k];
-        to_bf16(xp.data(), x16, xp.size());
-    }
-    void *dx16, *dg = nullptr, *db = nullptr, *dW, *dWf = nullptr, *dc1 = nullptr, *dc2 = nullptr, *dbias = nullptr, *dout;
+    std::vector<float> st, mean;   // (the means are not handed over: the activations are not centred)
+    tile_bf16(W, (size_t)N, (size_t)K, w16);
+    stage_ln_rows(x, B, K, false, x16, st, mean);
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    WM_TRY(up(&dx16, x16.data(), x16.size() * 2, s));
-    WM_TRY(up(&dW, w16.data(), w16.size() * 2, s));
-    WM_TRY(up(&dout, nullptr, (size_t)B * N * 4, s));
-    if (bias) WM_TRY(up(&dbias, bias, (size_t)N * 4, s));
     DecGemvArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = B; a.N = N; a.K = K; a.W = (const bf16_t *)dW; a.c2 = (const float *)dbias; a.a = (const bf16_t *)dx16;
-    a.out_f32 = (float *)dout; a.ldo = N; a.epi = DE_Q; a.pos_ptr = nullptr;
-    void *dst = nullptr;
-    int rc = WM_OK;
+    a.B = B; a.N = N; a.K = K; a.ldo = N; a.epi = DE_Q; a.pos_ptr = nullptr;
+    WM_TRY(pool.get(&a.a, x16.data(), x16.size() * 2, s));
+    WM_TRY(pool.get(&a.W, w16.data(), w16.size() * 2, s));
+    WM_TRY(pool.get(&a.out_f32, nullptr, (size_t)B * N * 4, s));
+    if (bias) WM_TRY(pool.get(&a.c2, bias, (size_t)N * 4, s));
     if (ln_g) {
-        WM_TRY(up(&dg, ln_g, (size_t)K * 4, s));
-        WM_TRY(up(&db, ln_b, (size_t)K * 4, s));
-        WM_TRY(up(&dWf, nullptr, w16.size() * 2, s));
-        WM_TRY(up(&dc1, nullptr, (size_t)Npad * 4, s));
-        WM_TRY(up(&dc2, nullptr, (size_t)Npad * 4, s));
-        rc = wm_ln_fold(ctx, (const bf16_t *)dW, (const float *)dg, (const float *)db, (const float *)dbias, N, K,
-                        (bf16_t *)dWf, (float *)dc1, (float *)dc2);
-        // the producer's partial statistics per 16-row block: K/16 parts (part p = columns 16p .. 16p+15), host-computed
-        const int nblk = (B + 15) / 16;
-        std::vector<float> st((size_t)nblk * 2 * K, 0.f);   // block stride = 2 K floats, as in the decoder
-        for (int b = 0; b < B; ++b)
-            for (int k = 0; k < K; ++k) {
-                const int part = k >> 4;
-                const float v = x[(size_t)b * K + k];
-                float *blk = st.data() + (size_t)(b >> 4) * 2 * K;
-                blk[(part * 16 + (b & 15)) * 2] += v;
-                blk[(part * 16 + (b & 15)) * 2 + 1] += v * v;
-            }
-        WM_TRY(up(&dst, st.data(), st.size() * 4, s));
-        a.stats_in = (const float *)dst; a.stats_parts = K / 16;
-        a.W = (const bf16_t *)dWf; a.c1 = (const float *)dc1; a.c2 = (const float *)dc2;
+        const float *dg, *db;
+        bf16_t *dWf;
+        float *dc1, *dc2;
+        WM_TRY(pool.get(&dg, ln_g, (size_t)K * 4, s));
+        WM_TRY(pool.get(&db, ln_b, (size_t)K * 4, s));
+        WM_TRY(pool.get(&dWf, nullptr, w16.size() * 2, s));
+        WM_TRY(pool.get(&dc1, nullptr, (size_t)Npad * 4, s));
+        WM_TRY(pool.get(&dc2, nullptr, (size_t)Npad * 4, s));
+        WM_TRY(wm_ln_fold(ctx, a.W, dg, db, a.c2, N, K, dWf, dc1, dc2));
+        WM_TRY(pool.get(&a.stats_in, st.data(), st.size() * 4, s));
+        a.stats_parts = K / 16;
+        a.W = dWf; a.c1 = dc1; a.c2 = dc2;
     }
-    if (rc == WM_OK) rc = wm_dec_gemv(ctx, a);
-    if (rc == WM_OK) {
-        WM_HIP(hipMemcpyAsync(out, dout, (size_t)B * N * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-    }
-    void *fr[] = {dx16, dg, db, dW, dWf, dc1, dc2, dbias, dout, dst};
-    for (void *p : fr)
-        if (p) (void)hipFree(p);
-    return rc;
+    WM_TRY(wm_dec_gemv(ctx, a));
+    WM_HIP(hipMemcpyAsync(out, a.out_f32, (size_t)B * N * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 // The residual product of a decoder layer (DE_RESID: attention out-projection K = d, fc2 K = 4d) at any decode-group size:
@@ -279,54 +435,26 @@ extern "C" int wmdbg_dec_gemv_resid(wm_ctx *ctx, const float *x, const float *W,
     WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && N % 16 == 0, WM_ERR_INVALID, "wmdbg_dec_gemv_resid: B out of range / N % 16");
     const int Bpad = ((B + 15) / 16) * 16;
     std::vector<bf16_t> w16, x16;
-    {
-        std::vector<float> wp((size_t)N * K, 0.f), xp((size_t)Bpad * K, 0.f);
-        for (size_t r = 0; r < (size_t)N; ++r)
-            for (size_t k = 0; k < (size_t)K; ++k) wp[wm_tiled_offset(r, k, (size_t)K)] = W[r * K + k];
-        for (size_t b = 0; b < (size_t)B; ++b)
-            for (size_t k = 0; k < (size_t)K; ++k) xp[wm_tiled_offset(b, k, (size_t)K)] = x[b * K + k];
-        to_bf16(wp.data(), w16, wp.size());
-        to_bf16(xp.data(), x16, xp.size());
-    }
-    void *dx16, *dW, *dbias = nullptr, *dres, *dcopy, *dst;
+    tile_bf16(W, (size_t)N, (size_t)K, w16);
+    tile_bf16(x, (size_t)B, (size_t)K, x16);
+    std::vector<float> st((size_t)(Bpad / 16) * 2 * N);
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    WM_TRY(up(&dx16, x16.data(), x16.size() * 2, s));
-    WM_TRY(up(&dW, w16.data(), w16.size() * 2, s));
-    WM_TRY(up(&dres, resid, (size_t)B * N * 4, s));
-    WM_TRY(up(&dcopy, nullptr, (size_t)Bpad * N * 2, s));
-    WM_TRY(up(&dst, nullptr, (size_t)(Bpad / 16) * 2 * N * 4, s));
-    if (bias) WM_TRY(up(&dbias, bias, (size_t)N * 4, s));
     DecGemvArgs a;
     memset(&a, 0, sizeof(a));
-    a.epi = DE_RESID; a.B = B; a.N = N; a.K = K; a.W = (const bf16_t *)dW; a.c2 = (const float *)dbias;
-    a.a = (const bf16_t *)dx16; a.out_f32 = (float *)dres; a.out_bf16 = (bf16_t *)dcopy; a.ldo = N;
-    a.stats_out = (float *)dst;
-    int rc = wm_dec_gemv(ctx, a);
-    if (rc == WM_OK) {
-        std::vector<bf16_t> c16((size_t)Bpad * N), lin((size_t)B * N);
-        std::vector<float> st((size_t)(Bpad / 16) * 2 * N);
-        WM_HIP(hipMemcpyAsync(resid, dres, (size_t)B * N * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(c16.data(), dcopy, c16.size() * 2, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(st.data(), dst, st.size() * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-        for (size_t b = 0; b < (size_t)B; ++b)
-            for (size_t n = 0; n < (size_t)N; ++n) lin[b * N + n] = c16[wm_tiled_offset(b, n, (size_t)N)];
-        from_bf16(lin, copy_bf16);
-        for (int b = 0; b < B; ++b) {   // block (b / 16): [N/16 parts][16][2]
-            const float *blk = st.data() + (size_t)(b >> 4) * 2 * N;
-            float s1 = 0.f, s2 = 0.f;
-            for (int part = 0; part < N / 16; ++part) {
-                s1 += blk[(part * 16 + (b & 15)) * 2];
-                s2 += blk[(part * 16 + (b & 15)) * 2 + 1];
-            }
-            stats[b * 2] = s1;
-            stats[b * 2 + 1] = s2;
-        }
-    }
-    void *fr[] = {dx16, dW, dbias, dres, dcopy, dst};
-    for (void *p : fr)
-        if (p) (void)hipFree(p);
-    return rc;
+    a.epi = DE_RESID; a.B = B; a.N = N; a.K = K; a.ldo = N;
+    WM_TRY(pool.get(&a.a, x16.data(), x16.size() * 2, s));
+    WM_TRY(pool.get(&a.W, w16.data(), w16.size() * 2, s));
+    WM_TRY(pool.get(&a.out_f32, resid, (size_t)B * N * 4, s));
+    WM_TRY(pool.get(&a.out_bf16, nullptr, (size_t)Bpad * N * 2, s));
+    WM_TRY(pool.get(&a.stats_out, nullptr, st.size() * 4, s));
+    if (bias) WM_TRY(pool.get(&a.c2, bias, (size_t)N * 4, s));
+    WM_TRY(wm_dec_gemv(ctx, a));
+    WM_HIP(hipMemcpyAsync(resid, a.out_f32, (size_t)B * N * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(st.data(), a.stats_out, st.size() * 4, hipMemcpyDeviceToHost, s));
+    WM_TRY(down_tiled_bf16(a.out_bf16, (size_t)B, (size_t)N, copy_bf16, s));
+    for (int b = 0; b < B; ++b) stats_sum(st.data(), N, b, stats + b * 2);   // the N / 16 parts of the updated residual
+    return WM_OK;
 }
 
 // Single-query attention: q f32 [B][H*64], k/v f32 [B][H][T][64] (rounded to bf16), first
@@ -337,32 +465,22 @@ extern "C" int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, 
     std::vector<bf16_t> k16, v16;
     to_bf16(k, k16, (size_t)B * H * T * 64);
     to_bf16(v, v16, (size_t)B * H * T * 64);
-    void *dq, *dk, *dv, *dp;
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    WM_TRY(up(&dq, q, (size_t)B * H * 64 * 4, s));
-    WM_TRY(up(&dk, k16.data(), k16.size() * 2, s));
-    WM_TRY(up(&dv, v16.data(), v16.size() * 2, s));
-    WM_TRY(up(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
-    void *datt;
-    WM_TRY(up(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
+    const float *dq;
+    const bf16_t *dk, *dv;
+    float *dp;
+    bf16_t *datt;
+    WM_TRY(pool.get(&dq, q, (size_t)B * H * 64 * 4, s));
+    WM_TRY(pool.get(&dk, k16.data(), k16.size() * 2, s));
+    WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
+    WM_TRY(pool.get(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
+    WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
     // nsplit == 0 selects the decoder's self-attention kernel (one 4-wave workgroup per pair), nsplit == -1 the
     // cross-attention launch path (8-wave block-streaming kernel, capped grid)
-    int rc = nsplit == 0 ? wm_dec_self_attention(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, B, H, T,
-                                                 n_keys, nullptr, (bf16_t *)datt)
-                         : wm_dec_attention(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, B, H, T, n_keys,
-                                            nullptr, nsplit < 0 ? 1 : nsplit, (float *)dp, (bf16_t *)datt, nsplit < 0);
-    if (rc == WM_OK) {
-        const size_t Bpad = ((size_t)B + 15) / 16 * 16, dd = (size_t)H * 64;
-        std::vector<bf16_t> o16(Bpad * dd), lin((size_t)B * dd);
-        WM_HIP(hipMemcpyAsync(o16.data(), datt, o16.size() * 2, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-        for (size_t b = 0; b < (size_t)B; ++b)   // head outputs are stored in the out-projection's tiled A-operand order
-            for (size_t k = 0; k < dd; ++k) lin[b * dd + k] = o16[wm_tiled_offset(b, k, dd)];
-        from_bf16(lin, out);
-    }
-    (void)hipFree(datt);
-    (void)hipFree(dq); (void)hipFree(dk); (void)hipFree(dv); (void)hipFree(dp);
-    return rc;
+    WM_TRY(nsplit == 0 ? wm_dec_self_attention(ctx, dq, dk, dv, B, H, T, n_keys, nullptr, datt)
+                       : wm_dec_attention(ctx, dq, dk, dv, B, H, T, n_keys, nullptr, nsplit < 0 ? 1 : nsplit, dp, datt, nsplit < 0));
+    return down_tiled_bf16(datt, (size_t)B, (size_t)H * 64, out, s);
 }
 
 // The cross-attention launch of a candidate group (wm_transcribe_mel_best_of), as wm_model_decode_step makes it; short_lived:
@@ -388,32 +506,23 @@ static int dec_attention_cand(wm_ctx *ctx, const float *q, const float *k, const
     std::vector<bf16_t> k16, v16;
     to_bf16(k, k16, (size_t)C * H * T * 64);
     to_bf16(v, v16, (size_t)C * H * T * 64);
-    void *dq, *dk, *dv, *dp, *dl, *datt;
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    const size_t att_b = ((size_t)B + 15) / 16 * 16 * H * 64 * 2;
-    WM_TRY(up(&dq, q, (size_t)B * H * 64 * 4, s));
-    WM_TRY(up(&dk, k16.data(), k16.size() * 2, s));
-    WM_TRY(up(&dv, v16.data(), v16.size() * 2, s));
-    WM_TRY(up(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
-    WM_TRY(up(&dl, live.data(), live.size() * 4, s));
-    WM_TRY(up(&datt, nullptr, att_b, s));
-    WM_HIP(hipMemsetAsync(dp, 0, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
-    WM_HIP(hipMemsetAsync(datt, 0, att_b, s));
-    const int *lr = live_rows ? (const int *)dl : nullptr;
-    int rc = wm_dec_attention_cand(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, C, N, H, T, n_keys, (float *)dp,
-                                   (bf16_t *)datt, nullptr, 0, 0, lr, lr ? lr + WM_DEC_MAXB : nullptr, short_lived);
-    if (rc == WM_OK) {
-        const size_t Bpad = ((size_t)B + 15) / 16 * 16, dd = (size_t)H * 64;
-        std::vector<bf16_t> o16(Bpad * dd), lin((size_t)B * dd);
-        WM_HIP(hipMemcpyAsync(o16.data(), datt, o16.size() * 2, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-        for (size_t b = 0; b < (size_t)B; ++b)   // head outputs are stored in the out-projection's tiled A-operand order
-            for (size_t kk = 0; kk < dd; ++kk) lin[b * dd + kk] = o16[wm_tiled_offset(b, kk, dd)];
-        from_bf16(lin, out);
-    }
-    void *fr[] = {dq, dk, dv, dp, dl, datt};
-    for (void *p : fr) (void)hipFree(p);
-    return rc;
+    const float *dq;
+    const bf16_t *dk, *dv;
+    float *dp;
+    const int *dl;
+    bf16_t *datt;
+    WM_TRY(pool.get(&dq, q, (size_t)B * H * 64 * 4, s));
+    WM_TRY(pool.get(&dk, k16.data(), k16.size() * 2, s));
+    WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
+    WM_TRY(pool.get(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
+    WM_TRY(pool.get(&dl, live.data(), live.size() * 4, s));
+    WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
+    const int *lr = live_rows ? dl : nullptr;
+    WM_TRY(wm_dec_attention_cand(ctx, dq, dk, dv, C, N, H, T, n_keys, dp, datt, nullptr, 0, 0, lr, lr ? lr + WM_DEC_MAXB : nullptr,
+                                 short_lived));
+    return down_tiled_bf16(datt, (size_t)B, (size_t)H * 64, out, s);
 }
 
 extern "C" int wmdbg_dec_attention_cand(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int N, int H, int T,
@@ -436,29 +545,20 @@ extern "C" int wmdbg_dec_self_attention_off(wm_ctx *ctx, const float *q, const f
     std::vector<bf16_t> k16, v16;
     to_bf16(k, k16, (size_t)B * H * T * 64);
     to_bf16(v, v16, (size_t)B * H * T * 64);
-    void *dq, *dk, *dv, *doff, *dpos, *datt;
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    WM_TRY(up(&dq, q, (size_t)B * H * 64 * 4, s));
-    WM_TRY(up(&dk, k16.data(), k16.size() * 2, s));
-    WM_TRY(up(&dv, v16.data(), v16.size() * 2, s));
-    WM_TRY(up(&doff, off, (size_t)B * 4, s));
-    WM_TRY(up(&dpos, &pos, 4, s));
-    WM_TRY(up(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
-    int rc = wm_dec_self_attention(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, B, H, T, 0, (const int *)dpos,
-                                   (bf16_t *)datt, nullptr, 0, 0, nullptr, nullptr, (const int *)doff);
-    if (rc == WM_OK) {
-        const size_t Bpad = ((size_t)B + 15) / 16 * 16, dd = (size_t)H * 64;
-        std::vector<bf16_t> o16(Bpad * dd), lin((size_t)B * dd);
-        WM_HIP(hipMemcpyAsync(o16.data(), datt, o16.size() * 2, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-        for (size_t b = 0; b < (size_t)B; ++b)
-            for (size_t j = 0; j < dd; ++j) lin[b * dd + j] = o16[wm_tiled_offset(b, j, dd)];
-        from_bf16(lin, out);
-    }
-    void *fr[] = {dq, dk, dv, doff, dpos, datt};
-    for (void *p : fr)
-        if (p) (void)hipFree(p);
-    return rc;
+    const float *dq;
+    const bf16_t *dk, *dv;
+    const int *doff, *dpos;
+    bf16_t *datt;
+    WM_TRY(pool.get(&dq, q, (size_t)B * H * 64 * 4, s));
+    WM_TRY(pool.get(&dk, k16.data(), k16.size() * 2, s));
+    WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
+    WM_TRY(pool.get(&doff, off, (size_t)B * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
+    WM_TRY(wm_dec_self_attention(ctx, dq, dk, dv, B, H, T, 0, dpos, datt, nullptr, 0, 0, nullptr, nullptr, doff));
+    return down_tiled_bf16(datt, (size_t)B, (size_t)H * 64, out, s);
 }
 
 // ------------------------------------------------------------------ micro-benchmarks ------
@@ -471,87 +571,68 @@ extern "C" int wmdbg_bench_dec_gemv(wm_ctx *ctx, int B, int N, int K, int ln, in
     (void)nw_override;  // the K split is a function of K alone (wm_dec_gemv_split)
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB, WM_ERR_INVALID, "wmdbg_bench_dec_gemv: B out of range");
+    DevPool pool;
     hipStream_t s = ctx->stream;
     const int Npad = ((N + 15) / 16) * 16;
-    void *dW, *dx16, *dc, *dout, *dout16;
-    WM_TRY(up(&dW, nullptr, (size_t)n_mats * Npad * K * 2, s));
-    WM_TRY(up(&dx16, nullptr, (size_t)WM_DEC_MAXB * K * 2, s));
-    WM_TRY(up(&dc, nullptr, (size_t)Npad * 4, s));
-    WM_TRY(up(&dout, nullptr, (size_t)WM_DEC_MAXB * Npad * 4, s));
-    WM_TRY(up(&dout16, nullptr, (size_t)WM_DEC_MAXB * Npad * 2, s));
-    WM_HIP(hipMemsetAsync(dW, 0x3c, (size_t)n_mats * Npad * K * 2, s));
+    const bf16_t *dW;
+    const float *dc;
+    bf16_t *dout16;
+    float *dstat;
     DecGemvArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = B; a.N = N; a.K = K; a.out_f32 = (float *)dout; a.ldo = Npad; a.epi = resid ? DE_RESID : DE_Q;
-    a.a = (const bf16_t *)dx16; a.c2 = (const float *)dc;
-    void *dstat;
-    WM_TRY(up(&dstat, nullptr, (size_t)(WM_DEC_MAXB / 16) * 2 * (K > N ? K : N) * 4 + 4096, s));
-    if (resid) { a.stats_out = (float *)dstat; a.out_bf16 = (bf16_t *)dout16; }
-    if (ln) { a.c1 = (const float *)dc; a.stats_in = (const float *)dstat; a.stats_parts = K / 16; }
-    hipEvent_t e0, e1;
-    WM_HIP(hipEventCreate(&e0));
-    WM_HIP(hipEventCreate(&e1));
-    int rc = WM_OK;
+    a.B = B; a.N = N; a.K = K; a.ldo = Npad; a.epi = resid ? DE_RESID : DE_Q;
+    WM_TRY(pool.get(&dW, nullptr, (size_t)n_mats * Npad * K * 2, s, 0x3c));
+    WM_TRY(pool.get(&a.a, nullptr, (size_t)WM_DEC_MAXB * K * 2, s));
+    WM_TRY(pool.get(&dc, nullptr, (size_t)Npad * 4, s));
+    WM_TRY(pool.get(&a.out_f32, nullptr, (size_t)WM_DEC_MAXB * Npad * 4, s));
+    WM_TRY(pool.get(&dout16, nullptr, (size_t)WM_DEC_MAXB * Npad * 2, s));
+    WM_TRY(pool.get(&dstat, nullptr, (size_t)(WM_DEC_MAXB / 16) * 2 * (K > N ? K : N) * 4 + 4096, s));
+    a.c2 = dc;
+    if (resid) { a.stats_out = dstat; a.out_bf16 = dout16; }
+    if (ln) { a.c1 = dc; a.stats_in = dstat; a.stats_parts = K / 16; }
+    EventPair ev;
+    WM_TRY(ev.init());
     // capture the launch chain once, replay it: per-kernel time = true serialized duration
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    WM_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < iters && rc == WM_OK; ++i) {
-        a.W = (const bf16_t *)dW + (size_t)(i % n_mats) * Npad * K;
-        rc = wm_dec_gemv(ctx, a);
+    GraphRun run(s);
+    WM_TRY(run.begin());
+    for (int i = 0; i < iters; ++i) {
+        a.W = dW + (size_t)(i % n_mats) * Npad * K;
+        WM_TRY(wm_dec_gemv(ctx, a));
     }
-    WM_HIP(hipStreamEndCapture(s, &g));
-    if (rc == WM_OK) {
-        WM_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        WM_HIP(hipGraphLaunch(ge, s));
-        WM_HIP(hipStreamSynchronize(s));
-        WM_HIP(hipEventRecord(e0, s));
-        WM_HIP(hipGraphLaunch(ge, s));
-    }
-    WM_HIP(hipEventRecord(e1, s));
-    WM_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    WM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1e3f / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (ge) (void)hipGraphExecDestroy(ge);
-    if (g) (void)hipGraphDestroy(g);
-    void *fr[] = {dW, dx16, dc, dout, dout16, dstat};
-    for (void *p : fr) (void)hipFree(p);
-    return rc;
+    WM_TRY(run.end());
+    float us = 0.f;
+    WM_TRY(run.replay_us(ev, &us));
+    *avg_us = us / iters;
+    return WM_OK;
 }
 
 extern "C" int wmdbg_bench_dec_attention(wm_ctx *ctx, int B, int H, int T, int n_keys, int nsplit, int n_slices,
                                          int iters, float *avg_us) {
     WM_TRY(wm_ctx_make_current(ctx));
+    DevPool pool;
     hipStream_t s = ctx->stream;
     const size_t slice = (size_t)B * H * T * 64;
-    void *dk, *dv, *dq, *dp, *datt;
-    WM_TRY(up(&dk, nullptr, slice * n_slices * 2, s));
-    WM_TRY(up(&dv, nullptr, slice * n_slices * 2, s));
-    WM_TRY(up(&dq, nullptr, (size_t)B * H * 64 * 4, s));
-    WM_TRY(up(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
-    WM_TRY(up(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
-    hipEvent_t e0, e1;
-    WM_HIP(hipEventCreate(&e0));
-    WM_HIP(hipEventCreate(&e1));
-    int rc = WM_OK;
-    for (int pass = 0; pass < 2 && rc == WM_OK; ++pass) {
-        if (pass == 1) WM_HIP(hipEventRecord(e0, s));
-        for (int i = 0; i < iters && rc == WM_OK; ++i)
-            rc = wm_dec_attention(ctx, (const float *)dq, (const bf16_t *)dk + (size_t)(i % n_slices) * slice,
-                                  (const bf16_t *)dv + (size_t)(i % n_slices) * slice, B, H, T, n_keys, nullptr, nsplit,
-                                  (float *)dp, (bf16_t *)datt, true);
+    const bf16_t *dk, *dv;
+    const float *dq;
+    float *dp;
+    bf16_t *datt;
+    WM_TRY(pool.get(&dk, nullptr, slice * n_slices * 2, s));
+    WM_TRY(pool.get(&dv, nullptr, slice * n_slices * 2, s));
+    WM_TRY(pool.get(&dq, nullptr, (size_t)B * H * 64 * 4, s));
+    WM_TRY(pool.get(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
+    WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
+    EventPair ev;
+    WM_TRY(ev.init());
+    for (int pass = 0; pass < 2; ++pass) {   // a warm pass, then the timed one
+        if (pass == 1) WM_TRY(ev.start(s));
+        for (int i = 0; i < iters; ++i)
+            WM_TRY(wm_dec_attention(ctx, dq, dk + (size_t)(i % n_slices) * slice, dv + (size_t)(i % n_slices) * slice, B, H, T, n_keys,
+                                    nullptr, nsplit, dp, datt, true));
     }
-    WM_HIP(hipEventRecord(e1, s));
-    WM_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    WM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1e3f / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    void *fr[] = {dk, dv, dq, dp, datt};
-    for (void *p : fr) (void)hipFree(p);
-    return rc;
+    float us = 0.f;
+    WM_TRY(ev.stop_us(s, &us));
+    *avg_us = us / iters;
+    return WM_OK;
 }
 
 int wm_launch_trivial(wm_ctx *ctx, int *p, int grid);
@@ -559,36 +640,24 @@ int wm_launch_trivial(wm_ctx *ctx, int *p, int grid);
 // so they are truly serialised), eager stream launches vs one captured hipGraph replayed.
 extern "C" int wmdbg_bench_launch_floor(wm_ctx *ctx, int iters, int grid, float *eager_us, float *graph_us) {
     WM_TRY(wm_ctx_make_current(ctx));
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    void *d;
-    WM_TRY(up(&d, nullptr, 64, s));
-    hipEvent_t e0, e1;
-    WM_HIP(hipEventCreate(&e0));
-    WM_HIP(hipEventCreate(&e1));
-    for (int i = 0; i < 20; ++i) WM_TRY(wm_launch_trivial(ctx, (int *)d, grid));
-    WM_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) WM_TRY(wm_launch_trivial(ctx, (int *)d, grid));
-    WM_HIP(hipEventRecord(e1, s));
-    WM_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    WM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *eager_us = ms * 1e3f / iters;
-    hipGraph_t g;
-    hipGraphExec_t ge;
-    WM_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < iters; ++i) (void)wm_launch_trivial(ctx, (int *)d, grid);
-    WM_HIP(hipStreamEndCapture(s, &g));
-    WM_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    WM_HIP(hipGraphLaunch(ge, s));
-    WM_HIP(hipStreamSynchronize(s));
-    WM_HIP(hipEventRecord(e0, s));
-    WM_HIP(hipGraphLaunch(ge, s));
-    WM_HIP(hipEventRecord(e1, s));
-    WM_HIP(hipStreamSynchronize(s));
-    WM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *graph_us = ms * 1e3f / iters;
-    (void)hipGraphExecDestroy(ge); (void)hipGraphDestroy(g);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d);
+    int *d;
+    WM_TRY(pool.get(&d, nullptr, 64, s));
+    EventPair ev;
+    WM_TRY(ev.init());
+    float us = 0.f;
+    for (int i = 0; i < 20; ++i) WM_TRY(wm_launch_trivial(ctx, d, grid));
+    WM_TRY(ev.start(s));
+    for (int i = 0; i < iters; ++i) WM_TRY(wm_launch_trivial(ctx, d, grid));
+    WM_TRY(ev.stop_us(s, &us));
+    *eager_us = us / iters;
+    GraphRun run(s);
+    WM_TRY(run.begin());
+    for (int i = 0; i < iters; ++i) WM_TRY(wm_launch_trivial(ctx, d, grid));
+    WM_TRY(run.end());
+    WM_TRY(run.replay_us(ev, &us));
+    *graph_us = us / iters;
     return WM_OK;
 }
 
@@ -600,7 +669,6 @@ extern "C" int wmdbg_bench_gemm(wm_ctx *ctx, int M, int N, int K, int epi, int i
     WM_REQUIRE(epi == EPI_F32 || epi == EPI_BIAS_BF16 || epi == EPI_GELU_BF16 || epi == EPI_RESID_F32, WM_ERR_INVALID,
                "wmdbg_bench_gemm: epilogue %d not exposed", epi);
     WM_REQUIRE(n_w >= 1 && n_w <= 64, WM_ERR_INVALID, "wmdbg_bench_gemm: n_w out of range");
-    hipStream_t s = ctx->stream;
     std::vector<bf16_t> a16((size_t)M * K), w16((size_t)N * K);
     uint32_t x = 12345u;
     auto gauss = [&]() {  // Irwin-Hall(4), unit variance
@@ -608,41 +676,29 @@ extern "C" int wmdbg_bench_gemm(wm_ctx *ctx, int M, int N, int K, int epi, int i
         for (int i = 0; i < 4; ++i) { x = x * 1664525u + 1013904223u; acc += (float)(x >> 8) * (1.0f / 16777216.0f); }
         return (acc - 2.0f) * 1.7320508f;
     };
-    auto f2bf = [](float f) {
-        uint32_t u;
-        memcpy(&u, &f, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (bf16_t)(u >> 16);
-    };
     for (auto &v : a16) v = f2bf(gauss());
     for (auto &v : w16) v = f2bf(0.02f * gauss());
     std::vector<float> bias(N);
     for (auto &v : bias) v = 0.01f * gauss();
-    void *dA, *dB, *dC;
-    std::vector<void *> dW(n_w, nullptr);
-    WM_TRY(up(&dA, a16.data(), a16.size() * 2, s));
-    for (int i = 0; i < n_w; ++i) WM_TRY(up(&dW[i], w16.data(), w16.size() * 2, s));
-    WM_TRY(up(&dB, bias.data(), (size_t)N * 4, s));
-    WM_TRY(up(&dC, nullptr, (size_t)M * N * 4, s));
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    std::vector<const bf16_t *> dW(n_w, nullptr);
     GemmArgs g;
     memset(&g, 0, sizeof(g));
-    g.A = (const bf16_t *)dA; g.a_rpb = (long)M + 1; g.a_rstride = K;
-    g.bias = (const float *)dB; g.C = dC;
+    WM_TRY(pool.get(&g.A, a16.data(), a16.size() * 2, s));
+    for (int i = 0; i < n_w; ++i) WM_TRY(pool.get(&dW[i], w16.data(), w16.size() * 2, s));
+    WM_TRY(pool.get(&g.bias, bias.data(), (size_t)N * 4, s));
+    WM_TRY(pool.get(&g.C, nullptr, (size_t)M * N * 4, s));
+    g.a_rpb = (long)M + 1; g.a_rstride = K;
     g.c_rpb = (long)M + 1; g.c_rstride = N; g.M = M; g.N = N; g.K = K; g.epi = epi;
-    hipEvent_t e0, e1;
-    WM_HIP(hipEventCreate(&e0));
-    WM_HIP(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) { g.W = (const bf16_t *)dW[i % n_w]; WM_TRY(wm_gemm(ctx, g)); }
-    WM_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) { g.W = (const bf16_t *)dW[i % n_w]; WM_TRY(wm_gemm(ctx, g)); }
-    WM_HIP(hipEventRecord(e1, s));
-    WM_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    WM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *us = ms * 1e3f / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
-    for (void *w : dW) (void)hipFree(w);
+    EventPair ev;
+    WM_TRY(ev.init());
+    for (int i = 0; i < 3; ++i) { g.W = dW[i % n_w]; WM_TRY(wm_gemm(ctx, g)); }
+    WM_TRY(ev.start(s));
+    for (int i = 0; i < iters; ++i) { g.W = dW[i % n_w]; WM_TRY(wm_gemm(ctx, g)); }
+    float total = 0.f;
+    WM_TRY(ev.stop_us(s, &total));
+    *us = total / iters;
     return WM_OK;
 }
 
@@ -652,38 +708,27 @@ int wm_launch_spin(hipStream_t s, int *p, int grid, int cycles);
 // replay with 1 branch and with 2 branches.
 extern "C" int wmdbg_bench_graph_branches(wm_ctx *ctx, int iters, int grid, int us_each, float *one_us, float *two_us) {
     WM_TRY(wm_ctx_make_current(ctx));
-    hipStream_t s = ctx->stream, s2;
-    WM_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-    void *d;
-    WM_TRY(up(&d, nullptr, 256, s));
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    SideBranch side;
+    WM_TRY(side.init());
+    int *d;
+    WM_TRY(pool.get(&d, nullptr, 256, s));
     const int cycles = us_each * 100;  // wall_clock64 ticks at 100 MHz
-    hipEvent_t e0, e1, ef, ej;
-    WM_HIP(hipEventCreate(&e0)); WM_HIP(hipEventCreate(&e1));
-    WM_HIP(hipEventCreateWithFlags(&ef, hipEventDisableTiming)); WM_HIP(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
+    EventPair ev;
+    WM_TRY(ev.init());
     for (int nb = 1; nb <= 2; ++nb) {
-        hipGraph_t g; hipGraphExec_t ge;
-        WM_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        if (nb == 2) { WM_HIP(hipEventRecord(ef, s)); WM_HIP(hipStreamWaitEvent(s2, ef, 0)); }
+        GraphRun run(s);
+        WM_TRY(run.begin());
+        if (nb == 2) WM_TRY(side.fork(s));
         for (int i = 0; i < iters; ++i) {
-            WM_TRY(wm_launch_spin(s, (int *)d, grid, cycles));
-            if (nb == 2) WM_TRY(wm_launch_spin(s2, (int *)d + 16, grid, cycles));
+            WM_TRY(wm_launch_spin(s, d, grid, cycles));
+            if (nb == 2) WM_TRY(wm_launch_spin(side.s2, d + 16, grid, cycles));
         }
-        if (nb == 2) { WM_HIP(hipEventRecord(ej, s2)); WM_HIP(hipStreamWaitEvent(s, ej, 0)); }
-        WM_HIP(hipStreamEndCapture(s, &g));
-        WM_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        WM_HIP(hipGraphLaunch(ge, s));
-        WM_HIP(hipStreamSynchronize(s));
-        WM_HIP(hipEventRecord(e0, s));
-        WM_HIP(hipGraphLaunch(ge, s));
-        WM_HIP(hipEventRecord(e1, s));
-        WM_HIP(hipStreamSynchronize(s));
-        float ms = 0.f;
-        WM_HIP(hipEventElapsedTime(&ms, e0, e1));
-        *(nb == 1 ? one_us : two_us) = ms * 1e3f;
-        (void)hipGraphExecDestroy(ge); (void)hipGraphDestroy(g);
+        if (nb == 2) WM_TRY(side.join(s));
+        WM_TRY(run.end());
+        WM_TRY(run.replay_us(ev, nb == 1 ? one_us : two_us));
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(ef); (void)hipEventDestroy(ej);
-    (void)hipStreamDestroy(s2); (void)hipFree(d);
     return WM_OK;
 }
 
@@ -697,21 +742,21 @@ extern "C" int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, c
         mmax = M[b] > mmax ? M[b] : mmax;
     }
     if (nmax == 0) return WM_OK;
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dx, *dn, *dm, *dt, *ds;
-    WM_TRY(up(&dx, x, (size_t)B * nmax * ld * 4, s));
-    WM_TRY(up(&dn, N, (size_t)B * 4, s));
-    WM_TRY(up(&dm, M, (size_t)B * 4, s));
-    WM_TRY(up(&dt, nullptr, (size_t)B * wm_dtw_trace_words(nmax) * 4, s));
-    WM_TRY(up(&ds, nullptr, (size_t)B * nmax * 4, s));
-    int rc = wm_dtw(ctx, (const float *)dx, (long)nmax * ld, ld, (const int *)dn, (const int *)dm, B, nmax, mmax,
-                    (unsigned *)dt, (int *)ds, nmax);
-    if (rc == WM_OK) {
-        WM_HIP(hipMemcpyAsync(start, ds, (size_t)B * nmax * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-    }
-    for (void *p : {dx, dn, dm, dt, ds}) (void)hipFree(p);
-    return rc;
+    const float *dx;
+    const int *dn, *dm;
+    unsigned *dt;
+    int *ds;
+    WM_TRY(pool.get(&dx, x, (size_t)B * nmax * ld * 4, s));
+    WM_TRY(pool.get(&dn, N, (size_t)B * 4, s));
+    WM_TRY(pool.get(&dm, M, (size_t)B * 4, s));
+    WM_TRY(pool.get(&dt, nullptr, (size_t)B * wm_dtw_trace_words(nmax) * 4, s));
+    WM_TRY(pool.get(&ds, nullptr, (size_t)B * nmax * 4, s));
+    WM_TRY(wm_dtw(ctx, dx, (long)nmax * ld, ld, dn, dm, B, nmax, mmax, dt, ds, nmax));
+    WM_HIP(hipMemcpyAsync(start, ds, (size_t)B * nmax * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 extern "C" int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out) {
@@ -753,41 +798,32 @@ extern "C" int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys
                 const float *src = keys + (((size_t)l * B + b) * H + h) * head;
                 bf16_t *dst = kv.data() + (((size_t)l * 2 * B + b) * H + h) * head;
                 const size_t live = (size_t)(n_frames[b] / 2) * 64;
-                for (size_t i = 0; i < head; ++i) {
-                    uint32_t u;
-                    memcpy(&u, &src[i], 4);
-                    u += 0x7fffu + ((u >> 16) & 1u);
-                    dst[i] = i < live ? (bf16_t)(u >> 16) : (bf16_t)0x4700;   // 32768
-                }
+                for (size_t i = 0; i < head; ++i) dst[i] = i < live ? f2bf(src[i]) : (bf16_t)0x4700;   // 32768
             }
     std::vector<int32_t> ints((size_t)2 * B + 2 * J);
     for (int b = 0; b < B; ++b) { ints[b] = n_text[b]; ints[B + b] = n_frames[b]; }
     for (int j = 0; j < J; ++j) { ints[2 * B + j] = hl[j]; ints[2 * B + J + j] = hh[j]; }
     const uint32_t sentinel = 0x7fc0deadu;
     std::vector<uint32_t> x0((size_t)B * n_ld * 1500, sentinel);
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dq, *dkv, *di, *drow, *dcol, *dx;
-    WM_TRY(up(&dq, q, (size_t)B * Tq * J * 64 * 4, s));
-    WM_TRY(up(&dkv, kv.data(), kv.size() * 2, s));
-    WM_TRY(up(&di, ints.data(), ints.size() * 4, s));
-    WM_TRY(up(&drow, nullptr, (size_t)B * J * Tq * 2 * 4, s));
-    WM_TRY(up(&dcol, nullptr, (size_t)B * J * 1500 * 2 * 4, s));
-    WM_TRY(up(&dx, x0.data(), x0.size() * 4, s));
     WmAlignDev a;
-    a.q = (const float *)dq; a.xkv = (const bf16_t *)dkv;
-    a.n_text = (const int *)di; a.n_frames = (const int *)di + B; a.hl = (const int *)di + 2 * B; a.hh = (const int *)di + 2 * B + J;
-    a.rowst = (float *)drow; a.colst = (float *)dcol; a.x = (float *)dx;
+    const int *di;
+    WM_TRY(pool.get(&a.q, q, (size_t)B * Tq * J * 64 * 4, s));
+    WM_TRY(pool.get(&a.xkv, kv.data(), kv.size() * 2, s));
+    WM_TRY(pool.get(&di, ints.data(), ints.size() * 4, s));
+    WM_TRY(pool.get(&a.rowst, nullptr, (size_t)B * J * Tq * 2 * 4, s));
+    WM_TRY(pool.get(&a.colst, nullptr, (size_t)B * J * 1500 * 2 * 4, s));
+    WM_TRY(pool.get(&a.x, x0.data(), x0.size() * 4, s));
+    a.n_text = di; a.n_frames = di + B; a.hl = di + 2 * B; a.hh = di + 2 * B + J;
     a.B = B; a.H = H; a.Tq = Tq; a.J = J; a.S = S; a.n_ld = n_ld;
     a.sc = 0.125f * qk_scale * 1.44269504088896340736f;   // as wm_align
     a.half = medfilt_width / 2;
-    int rc = wm_align_matrix(ctx, a, nmax, mmax);
-    if (rc == WM_OK) {
-        WM_HIP(hipMemcpyAsync(x, dx, x0.size() * 4, hipMemcpyDeviceToHost, s));
-        if (col_stats) WM_HIP(hipMemcpyAsync(col_stats, dcol, (size_t)B * J * 1500 * 2 * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-    }
-    for (void *p : {dq, dkv, di, drow, dcol, dx}) (void)hipFree(p);
-    return rc;
+    WM_TRY(wm_align_matrix(ctx, a, nmax, mmax));
+    WM_HIP(hipMemcpyAsync(x, a.x, x0.size() * 4, hipMemcpyDeviceToHost, s));
+    if (col_stats) WM_HIP(hipMemcpyAsync(col_stats, a.colst, (size_t)B * J * 1500 * 2 * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 extern "C" int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, int V, int ldo, const int32_t *tok, int eot,
@@ -799,19 +835,19 @@ extern "C" int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, i
     // one decode position (pos 0, S = 0) with one text token per row: the token is seq[pos + 1][b]
     std::vector<int32_t> ints((size_t)3 * B + 1, 0);
     for (int b = 0; b < B; ++b) { ints[B + b] = tok[b]; ints[2 * B + b] = 1; }
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dl, *di, *dp;
-    WM_TRY(up(&dl, logits, (size_t)B * ldo * 4, s));
-    WM_TRY(up(&di, ints.data(), ints.size() * 4, s));
-    WM_TRY(up(&dp, nullptr, (size_t)B * 4, s));
-    const int *seq = (const int *)di, *n_text = seq + 2 * B, *pos = seq + 3 * B;
-    int rc = wm_align_token_prob(ctx, (const float *)dl, ldo, seq, pos, B, 0, eot, n_text, (float *)dp, 1);
-    if (rc == WM_OK) {
-        WM_HIP(hipMemcpyAsync(prob, dp, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-    }
-    for (void *p : {dl, di, dp}) (void)hipFree(p);
-    return rc;
+    const float *dl;
+    const int *seq;
+    float *dp;
+    WM_TRY(pool.get(&dl, logits, (size_t)B * ldo * 4, s));
+    WM_TRY(pool.get(&seq, ints.data(), ints.size() * 4, s));
+    WM_TRY(pool.get(&dp, nullptr, (size_t)B * 4, s));
+    const int *n_text = seq + 2 * B, *pos = seq + 3 * B;
+    WM_TRY(wm_align_token_prob(ctx, dl, ldo, seq, pos, B, 0, eot, n_text, dp, 1));
+    WM_HIP(hipMemcpyAsync(prob, dp, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 // ------------------------------------------------------------------ beam search ----
@@ -895,49 +931,50 @@ extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V
             }
         }
     }
-    hipStream_t s = ctx->stream;
     const int L = WM_MAX_BEAM + 1;
-    std::vector<int32_t> ints(2);   // pos, then the beam parameters are not read by this kernel
-    ints[0] = 0; ints[1] = 0;
+    const int32_t ints[2] = {0, 0};   // pos, then the beam parameters are not read by this kernel
     WmXPar xp;
     memset(&xp, 0, sizeof(xp));
     xp.sot_pos = -1;
-    void *dlg, *dtxt, *dtsl, *dkt, *dks, *dmask, *drng = nullptr, *dpos, *dxp, *dsum, *dwd, *dln, *dlt, *dlp;
-    WM_TRY(up(&dlg, lg.data(), lg.size() * 4, s));
-    WM_TRY(up(&dtxt, txt.data(), txt.size() * 4, s));
-    WM_TRY(up(&dtsl, tsl.data(), tsl.size() * 4, s));
-    WM_TRY(up(&dkt, kt.data(), kt.size() * 8, s));
-    WM_TRY(up(&dks, ks.data(), ks.size() * 8, s));
-    WM_TRY(up(&dmask, mask.data(), mask.size() * 4, s));
-    if (rng) WM_TRY(up(&drng, rng, (size_t)rows * 16, s));
-    WM_TRY(up(&dpos, ints.data(), 8, s));
-    WM_TRY(up(&dxp, &xp, sizeof(xp), s));
-    WM_TRY(up(&dsum, nullptr, (size_t)rows * 4, s));
-    WM_TRY(up(&dwd, nullptr, (size_t)rows * 4, s));
-    WM_TRY(up(&dln, nullptr, (size_t)rows * 4, s));
-    WM_TRY(up(&dlt, nullptr, (size_t)rows * L * 4, s));
-    WM_TRY(up(&dlp, nullptr, (size_t)rows * L * 4, s));
+    DevPool pool;
+    hipStream_t s = ctx->stream;
     WmTsDev ts;
     memset(&ts, 0, sizeof(ts));
-    if (rng) { ts.rng = (int *)drng; ts.key_ts = (unsigned long long *)dks; ts.lse = (float *)dtsl; ts.ts_begin = ts_begin; ts.n_vocab = V; }
     WmXDev xd;
     memset(&xd, 0, sizeof(xd));
-    xd.par = (const WmXPar *)dxp; xd.txt = (float *)dtxt;
     WmBeamDev bm;
     memset(&bm, 0, sizeof(bm));
-    bm.N = N; bm.sum = (float *)dsum; bm.wdone = (int *)dwd; bm.list_n = (int *)dln; bm.list_tok = (int *)dlt; bm.list_lp = (float *)dlp;
-    // n_prompt 2 at position 0: not the first generated token, so the every-position bitmap applies
-    int rc = wm_beam_topk(ctx, (const float *)dlg, vpad, V, (const unsigned long long *)dkt, rows, ts, xd, (const unsigned *)dmask, mw, 2,
-                          (const int *)dpos, bm);
-    if (rc == WM_OK) {
-        WM_HIP(hipMemcpyAsync(list_n, dln, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(list_tok, dlt, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(list_lp, dlp, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
+    bm.N = N;
+    const float *dlg;
+    float *dtsl;
+    const unsigned long long *dkt;
+    unsigned long long *dks;
+    const unsigned *dmask;
+    const int *dpos;
+    WM_TRY(pool.get(&dlg, lg.data(), lg.size() * 4, s));
+    WM_TRY(pool.get(&xd.txt, txt.data(), txt.size() * 4, s));
+    WM_TRY(pool.get(&dtsl, tsl.data(), tsl.size() * 4, s));
+    WM_TRY(pool.get(&dkt, kt.data(), kt.size() * 8, s));
+    WM_TRY(pool.get(&dks, ks.data(), ks.size() * 8, s));
+    WM_TRY(pool.get(&dmask, mask.data(), mask.size() * 4, s));
+    if (rng) {
+        WM_TRY(pool.get(&ts.rng, rng, (size_t)rows * 16, s));
+        ts.key_ts = dks; ts.lse = dtsl; ts.ts_begin = ts_begin; ts.n_vocab = V;
     }
-    for (void *p : {dlg, dtxt, dtsl, dkt, dks, dmask, drng, dpos, dxp, dsum, dwd, dln, dlt, dlp})
-        if (p) (void)hipFree(p);
-    return rc;
+    WM_TRY(pool.get(&dpos, ints, 8, s));
+    WM_TRY(pool.get(&xd.par, &xp, sizeof(xp), s));
+    WM_TRY(pool.get(&bm.sum, nullptr, (size_t)rows * 4, s));
+    WM_TRY(pool.get(&bm.wdone, nullptr, (size_t)rows * 4, s));
+    WM_TRY(pool.get(&bm.list_n, nullptr, (size_t)rows * 4, s));
+    WM_TRY(pool.get(&bm.list_tok, nullptr, (size_t)rows * L * 4, s));
+    WM_TRY(pool.get(&bm.list_lp, nullptr, (size_t)rows * L * 4, s));
+    // n_prompt 2 at position 0: not the first generated token, so the every-position bitmap applies
+    WM_TRY(wm_beam_topk(ctx, dlg, vpad, V, dkt, rows, ts, xd, dmask, mw, 2, dpos, bm));
+    WM_HIP(hipMemcpyAsync(list_n, bm.list_n, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(list_tok, bm.list_tok, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(list_lp, bm.list_lp, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 extern "C" int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows, int H, int T, int N, int pos, int n_prompt,
@@ -947,28 +984,29 @@ extern "C" int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows
                    rows <= WM_DEC_MAXB && rows % N == 0 && pos >= 0 && pos < T && n_prompt >= 1 && n_prompt <= pos + 1,
                WM_ERR_INVALID, "beam_reorder: bad args");
     for (int b = 0; b < rows; ++b) WM_REQUIRE(src[b] >= 0 && src[b] < N, WM_ERR_INVALID, "beam_reorder: src[%d] = %d", b, src[b]);
-    hipStream_t s = ctx->stream;
     const size_t nc = (size_t)L2 * rows * H * T * 64;
     const int after = pos + 1;   // the kernel runs behind the position advance
-    void *dc, *dsrc, *dwd, *dseq, *dlp, *dpos;
-    WM_TRY(up(&dc, cache, nc * 2, s));
-    WM_TRY(up(&dsrc, src, (size_t)rows * 4, s));
-    WM_TRY(up(&dwd, wdone, (size_t)(rows / N) * 4, s));
-    WM_TRY(up(&dseq, seq, (size_t)T * rows * 4, s));
-    WM_TRY(up(&dlp, logprob, (size_t)T * rows * 4, s));
-    WM_TRY(up(&dpos, &after, 4, s));
+    DevPool pool;
+    hipStream_t s = ctx->stream;
     WmBeamDev bm;
     memset(&bm, 0, sizeof(bm));
-    bm.N = N; bm.src = (int *)dsrc; bm.wdone = (int *)dwd;
-    int rc = wm_beam_reorder(ctx, (bf16_t *)dc, L2, rows, H, T, (const int *)dpos, n_prompt, (int *)dseq, (float *)dlp, bm);
-    if (rc == WM_OK) {
-        WM_HIP(hipMemcpyAsync(cache, dc, nc * 2, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(seq, dseq, (size_t)T * rows * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(logprob, dlp, (size_t)T * rows * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipStreamSynchronize(s));
-    }
-    for (void *p : {dc, dsrc, dwd, dseq, dlp, dpos}) (void)hipFree(p);
-    return rc;
+    bm.N = N;
+    bf16_t *dc;
+    int *dseq;
+    float *dlp;
+    const int *dpos;
+    WM_TRY(pool.get(&dc, cache, nc * 2, s));
+    WM_TRY(pool.get(&bm.src, src, (size_t)rows * 4, s));
+    WM_TRY(pool.get(&bm.wdone, wdone, (size_t)(rows / N) * 4, s));
+    WM_TRY(pool.get(&dseq, seq, (size_t)T * rows * 4, s));
+    WM_TRY(pool.get(&dlp, logprob, (size_t)T * rows * 4, s));
+    WM_TRY(pool.get(&dpos, &after, 4, s));
+    WM_TRY(wm_beam_reorder(ctx, dc, L2, rows, H, T, dpos, n_prompt, dseq, dlp, bm));
+    WM_HIP(hipMemcpyAsync(cache, dc, nc * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(seq, dseq, (size_t)T * rows * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(logprob, dlp, (size_t)T * rows * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 // ------------------------------------------------------------------ window sets: the copy kernel ----
@@ -983,78 +1021,19 @@ extern "C" int wmdbg_xkv_rows(wm_ctx *ctx, uint16_t *group, int group_rows, uint
         for (int o = 0; to_store && o < b; ++o)
             WM_REQUIRE(rows[o] != rows[b], WM_ERR_INVALID, "xkv_rows: store row %d named twice", rows[b]);
     }
+    DevPool pool;
     hipStream_t s = ctx->stream;
-    void *drows;
-    WM_TRY(up(&drows, rows, (size_t)n_rows * 4, s));
-    int rc = wm_xkv_rows(ctx, group, group_rows, store, (const int *)drows, 0, n_rows, 2 * L, (long)H * 1500 * 64, to_store != 0);
+    const int *drows;
+    WM_TRY(pool.get(&drows, rows, (size_t)n_rows * 4, s));
+    int rc = wm_xkv_rows(ctx, group, group_rows, store, drows, 0, n_rows, 2 * L, (long)H * 1500 * 64, to_store != 0);
     if (hipStreamSynchronize(s) != hipSuccess && rc == WM_OK) {
         wm_set_error("xkv_rows: %s", hipGetErrorString(hipGetLastError()));
         rc = WM_ERR_HIP;
     }
-    (void)hipFree(drows);
     return rc;
 }
 
 // ------------------------------------------------------------------ the decode step's LN-folded GEMV and its close ----
-namespace {
-// device allocations of one hook call, freed when it returns (on an error path too)
-struct DevPool {
-    std::vector<void *> v;
-    ~DevPool() {
-        for (void *p : v) (void)hipFree(p);
-    }
-    // bytes of `fill` (a byte value), then the host data when given.  The 512 bytes of slack are the habit of up() above (a
-    // guard band behind host-staged buffers); nothing here relies on them: every kernel read of these buffers is clamped to
-    // the group's rows and the matrix's tiles (gemv_unit_load), and each buffer is sized for what its kernel may write.
-    int get(void **d, const void *h, size_t bytes, hipStream_t s, int fill = 0) {
-        WM_HIP(hipMalloc(d, bytes + 512));
-        v.push_back(*d);
-        WM_HIP(hipMemsetAsync(*d, fill, bytes + 512, s));
-        if (h) WM_HIP(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, s));
-        return WM_OK;
-    }
-};
-
-// [rows][K] f32 -> bf16 in WL_TILED order, rows padded to 16 with zeros
-void tile_bf16(const float *m, size_t rows, size_t K, std::vector<bf16_t> &out) {
-    const size_t rpad = (rows + 15) / 16 * 16;
-    std::vector<float> t(rpad * K, 0.f);
-    for (size_t r = 0; r < rows; ++r)
-        for (size_t k = 0; k < K; ++k) t[wm_tiled_offset(r, k, K)] = m[r * K + k];
-    to_bf16(t.data(), out, t.size());
-}
-// WL_TILED bf16 [rows][K] -> row-major f32
-void untile_bf16(const std::vector<bf16_t> &t, size_t rows, size_t K, float *out) {
-    std::vector<bf16_t> lin(rows * K);
-    for (size_t r = 0; r < rows; ++r)
-        for (size_t k = 0; k < K; ++k) lin[r * K + k] = t[wm_tiled_offset(r, k, K)];
-    from_bf16(lin, out);
-}
-
-// The A operand of a LayerNorm-folded GEMV as the decoder holds it: the producer's K/16 partial statistics of the raw f32
-// rows (as wmdbg_dec_gemv stages them), the rows' f32 means, and the bf16 activations in WL_TILED order -- of x - mean
-// when `centre`, else of x (the means are then not handed to the kernel).
-void stage_ln_rows(const float *x, int B, int K, bool centre, std::vector<bf16_t> &x16, std::vector<float> &st, std::vector<float> &mean) {
-    const int nblk = (B + 15) / 16;
-    st.assign((size_t)nblk * 2 * K, 0.f);   // block stride = 2 K floats, as in the decoder
-    mean.assign((size_t)B, 0.f);
-    std::vector<float> xc((size_t)B * K);
-    for (int b = 0; b < B; ++b) {
-        float s1 = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const float v = x[(size_t)b * K + k];
-            float *blk = st.data() + (size_t)(b >> 4) * 2 * K;
-            blk[((k >> 4) * 16 + (b & 15)) * 2] += v;
-            blk[((k >> 4) * 16 + (b & 15)) * 2 + 1] += v * v;
-            s1 += v;
-        }
-        mean[b] = s1 / (float)K;
-        for (int k = 0; k < K; ++k) xc[(size_t)b * K + k] = centre ? x[(size_t)b * K + k] - mean[b] : x[(size_t)b * K + k];
-    }
-    tile_bf16(xc.data(), (size_t)B, (size_t)K, x16);
-}
-}  // namespace
-
 // panel: 0 = the step epilogues; w >= 1 (DE_QKV only) = the panel epilogue DE_QKV_P, caches [ceil(B / w)][n_head][T][64]
 static int dec_gemv_ln_run(wm_ctx *ctx, int epi, const float *x, const float *ln_g, const float *ln_b, const float *W,
                            const float *bias, int B, int N, int K, int centre, int n_head, int T, int pos, int panel, float *out_f32,
@@ -1081,11 +1060,18 @@ static int dec_gemv_ln_run(wm_ctx *ctx, int epi, const float *x, const float *ln
     const size_t n_b16 = epi == DE_GELU ? Bpad * N : 0, n_cache = epi == DE_QKV ? (size_t)(panel ? (B + panel - 1) / panel : B) * n_head * T * 64 : 0;
     const std::vector<bf16_t> fill16(std::max(n_b16, n_cache), (bf16_t)WMDBG_SENTINEL_BF16);
     const std::vector<uint32_t> fill32((size_t)B, WMDBG_SENTINEL_F32);
+    std::vector<bf16_t> wf16(w16.size()), ob16(n_b16), k16(n_cache), v16(n_cache);
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dx16, *dW, *dWf, *dc1, *dc2, *dg, *db, *dbias = nullptr, *dst, *dmin, *dmout, *dof = nullptr, *dob = nullptr, *dk = nullptr,
-                                                 *dv = nullptr, *dpos;
-    WM_TRY(pool.get(&dx16, x16.data(), x16.size() * 2, s));
+    DecGemvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.epi = epi; a.B = B; a.N = N; a.K = K; a.stats_parts = K / 16; a.ldo = N;
+    const bf16_t *dW;
+    bf16_t *dWf;
+    float *dc1, *dc2;
+    const float *dg, *db, *dbias = nullptr, *dmin;
+    const int *dpos;
+    WM_TRY(pool.get(&a.a, x16.data(), x16.size() * 2, s));
     WM_TRY(pool.get(&dW, w16.data(), w16.size() * 2, s));
     WM_TRY(pool.get(&dWf, nullptr, w16.size() * 2, s));
     WM_TRY(pool.get(&dc1, nullptr, Npad * 4, s));
@@ -1093,37 +1079,31 @@ static int dec_gemv_ln_run(wm_ctx *ctx, int epi, const float *x, const float *ln
     WM_TRY(pool.get(&dg, ln_g, (size_t)K * 4, s));
     WM_TRY(pool.get(&db, ln_b, (size_t)K * 4, s));
     if (bias) WM_TRY(pool.get(&dbias, bias, (size_t)N * 4, s));
-    WM_TRY(pool.get(&dst, st.data(), st.size() * 4, s));
+    WM_TRY(pool.get(&a.stats_in, st.data(), st.size() * 4, s));
     WM_TRY(pool.get(&dmin, mean.data(), (size_t)B * 4, s));
-    WM_TRY(pool.get(&dmout, fill32.data(), (size_t)B * 4, s));
+    WM_TRY(pool.get(&a.mean_out, fill32.data(), (size_t)B * 4, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
-    if (n_f32) WM_TRY(pool.get(&dof, nullptr, n_f32 * 4, s));
-    if (n_b16) WM_TRY(pool.get(&dob, fill16.data(), n_b16 * 2, s));
+    if (n_f32) WM_TRY(pool.get(&a.out_f32, nullptr, n_f32 * 4, s));
+    if (n_b16) WM_TRY(pool.get(&a.out_bf16, fill16.data(), n_b16 * 2, s));
     if (n_cache) {
-        WM_TRY(pool.get(&dk, fill16.data(), n_cache * 2, s));
-        WM_TRY(pool.get(&dv, fill16.data(), n_cache * 2, s));
+        WM_TRY(pool.get(&a.kcache, fill16.data(), n_cache * 2, s));
+        WM_TRY(pool.get(&a.vcache, fill16.data(), n_cache * 2, s));
     }
-    WM_TRY(wm_ln_fold(ctx, (const bf16_t *)dW, (const float *)dg, (const float *)db, (const float *)dbias, N, K, (bf16_t *)dWf,
-                      (float *)dc1, (float *)dc2));
-    DecGemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.epi = epi; a.B = B; a.N = N; a.K = K; a.W = (const bf16_t *)dWf; a.c1 = (const float *)dc1; a.c2 = (const float *)dc2;
-    a.a = (const bf16_t *)dx16; a.stats_in = (const float *)dst; a.stats_parts = K / 16;
-    a.mean_in = centre ? (const float *)dmin : nullptr; a.mean_out = (float *)dmout;
-    a.out_f32 = (float *)dof; a.out_bf16 = (bf16_t *)dob; a.ldo = N;
-    if (epi == DE_QKV) { a.kcache = (bf16_t *)dk; a.vcache = (bf16_t *)dv; a.pos_ptr = (const int *)dpos; a.n_ctx = T; a.n_head = n_head; }
+    WM_TRY(wm_ln_fold(ctx, dW, dg, db, dbias, N, K, dWf, dc1, dc2));
+    a.W = dWf; a.c1 = dc1; a.c2 = dc2;
+    a.mean_in = centre ? dmin : nullptr;
+    if (epi == DE_QKV) { a.pos_ptr = dpos; a.n_ctx = T; a.n_head = n_head; }
     if (panel) { a.epi = DE_QKV_P; a.panel = panel; }
     WM_TRY(wm_dec_gemv(ctx, a));
-    std::vector<bf16_t> wf16(w16.size()), ob16(n_b16), k16(n_cache), v16(n_cache);
     WM_HIP(hipMemcpyAsync(wf16.data(), dWf, wf16.size() * 2, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(c1, dc1, Npad * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(c2, dc2, Npad * 4, hipMemcpyDeviceToHost, s));
-    WM_HIP(hipMemcpyAsync(mean_out, dmout, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    if (n_f32) WM_HIP(hipMemcpyAsync(out_f32, dof, n_f32 * 4, hipMemcpyDeviceToHost, s));
-    if (n_b16) WM_HIP(hipMemcpyAsync(ob16.data(), dob, n_b16 * 2, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(mean_out, a.mean_out, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    if (n_f32) WM_HIP(hipMemcpyAsync(out_f32, a.out_f32, n_f32 * 4, hipMemcpyDeviceToHost, s));
+    if (n_b16) WM_HIP(hipMemcpyAsync(ob16.data(), a.out_bf16, n_b16 * 2, hipMemcpyDeviceToHost, s));
     if (n_cache) {
-        WM_HIP(hipMemcpyAsync(k16.data(), dk, n_cache * 2, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(v16.data(), dv, n_cache * 2, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(k16.data(), a.kcache, n_cache * 2, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(v16.data(), a.vcache, n_cache * 2, hipMemcpyDeviceToHost, s));
     }
     WM_HIP(hipStreamSynchronize(s));
     untile_bf16(wf16, Npad, (size_t)K, Wf);
@@ -1165,21 +1145,17 @@ extern "C" int wmdbg_dec_self_attention_panel(wm_ctx *ctx, const float *q, const
     const std::vector<bf16_t> fill((size_t)out_rows * dd, (bf16_t)WMDBG_SENTINEL_BF16);
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dq, *dk, *dv, *dpos, *datt;
+    const float *dq;
+    const bf16_t *dk, *dv;
+    const int *dpos;
+    bf16_t *datt;
     WM_TRY(pool.get(&dq, q, (size_t)B * dd * 4, s));
     WM_TRY(pool.get(&dk, k16.data(), k16.size() * 2, s));
     WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
     WM_TRY(pool.get(&datt, fill.data(), fill.size() * 2, s));
-    WM_TRY(wm_dec_self_attention_panel(ctx, (const float *)dq, (const bf16_t *)dk, (const bf16_t *)dv, C, w, H, T, (const int *)dpos,
-                                       (bf16_t *)datt));
-    std::vector<bf16_t> o16(fill.size()), lin(fill.size());
-    WM_HIP(hipMemcpyAsync(o16.data(), datt, o16.size() * 2, hipMemcpyDeviceToHost, s));
-    WM_HIP(hipStreamSynchronize(s));
-    for (size_t b = 0; b < (size_t)out_rows; ++b)
-        for (size_t j = 0; j < dd; ++j) lin[b * dd + j] = o16[wm_tiled_offset(b, j, dd)];
-    from_bf16(lin, out);
-    return WM_OK;
+    WM_TRY(wm_dec_self_attention_panel(ctx, dq, dk, dv, C, w, H, T, dpos, datt));
+    return down_tiled_bf16(datt, (size_t)out_rows, dd, out, s);
 }
 
 extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
@@ -1195,9 +1171,22 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
     std::vector<bf16_t> e16;
     tile_bf16(emb, (size_t)V, (size_t)d, e16);
     const size_t n_st = (size_t)(Bpad / 16) * (d / 16) * 32;
+    std::vector<float> hx((size_t)B * d), hst(n_st), hmean(B);
+    std::vector<bf16_t> hxb((size_t)Bpad * d, (bf16_t)0xffffu);
+    // the step path's own buffers: the C windows alone
+    const int Cpad = (C + 15) / 16 * 16;
+    const size_t n_st1 = (size_t)(Cpad / 16) * (d / 16) * 32;
+    std::vector<int32_t> seq1;
+    std::vector<float> x1, st1, mean1;
+    std::vector<bf16_t> xb1;
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *de, *dp, *dseq, *dpos, *dx, *dxb, *dst, *dmean, *dtile, *darr, *dx1, *dxb1, *dst1, *dmean1, *dseq1;
+    const bf16_t *de;
+    const float *dp;
+    const int *dseq;
+    int *dpos;
+    float *dx, *dst, *dmean;
+    bf16_t *dxb;
     WM_TRY(pool.get(&de, e16.data(), e16.size() * 2, s));
     WM_TRY(pool.get(&dp, pemb, (size_t)n_ctx * d * 4, s));
     WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * stride * 4, s));
@@ -1206,11 +1195,8 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
     WM_TRY(pool.get(&dxb, nullptr, (size_t)Bpad * d * 2, s, 0xff));
     WM_TRY(pool.get(&dst, nullptr, n_st * 4, s, 0xff));
     WM_TRY(pool.get(&dmean, nullptr, (size_t)B * 4, s, 0xff));
-    std::vector<float> hx((size_t)B * d), hst(n_st), hmean(B);
-    std::vector<bf16_t> hxb((size_t)Bpad * d, (bf16_t)0xffffu);
     if (!by_steps) {
-        WM_TRY(wm_dec_embed_panel(ctx, (const int *)dseq + c0, stride, (const int *)dpos, 0, C, w, (const bf16_t *)de, (const float *)dp, d,
-                                  n_ctx, (float *)dx, (bf16_t *)dxb, (float *)dst, (float *)dmean));
+        WM_TRY(wm_dec_embed_panel(ctx, dseq + c0, stride, dpos, 0, C, w, de, dp, d, n_ctx, dx, dxb, dst, dmean));
         WM_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * 4, hipMemcpyDeviceToHost, s));
         WM_HIP(hipMemcpyAsync(hxb.data(), dxb, hxb.size() * 2, hipMemcpyDeviceToHost, s));
         WM_HIP(hipMemcpyAsync(hst.data(), dst, hst.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1219,11 +1205,14 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
     } else {
         // the step path, position by position over the C windows alone: wm_dec_embed for position 0, the teacher-forced close
         // (wm_argmax_embed with every position a prompt position) for the others; row c of step s is row c * w + s of the panel
-        const int Cpad = (C + 15) / 16 * 16;
-        const size_t n_st1 = (size_t)(Cpad / 16) * (d / 16) * 32;
-        std::vector<int32_t> seq1((size_t)n_ctx * C);
+        seq1.resize((size_t)n_ctx * C);
         for (int t = 0; t < n_ctx; ++t)
             for (int c = 0; c < C; ++c) seq1[(size_t)t * C + c] = seq[(size_t)t * stride + c0 + c];
+        x1.resize((size_t)C * d); st1.resize(n_st1); mean1.resize(C); xb1.resize((size_t)Cpad * d);
+        int *dseq1, *darr;
+        const unsigned long long *dtile;
+        float *dx1, *dst1, *dmean1;
+        bf16_t *dxb1;
         WM_TRY(pool.get(&dseq1, seq1.data(), seq1.size() * 4, s));
         WM_TRY(pool.get(&dtile, nullptr, (size_t)C * n_tiles * 8, s));
         WM_TRY(pool.get(&darr, nullptr, 4, s));
@@ -1231,21 +1220,17 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
         WM_TRY(pool.get(&dxb1, nullptr, (size_t)Cpad * d * 2, s));
         WM_TRY(pool.get(&dst1, nullptr, n_st1 * 4, s));
         WM_TRY(pool.get(&dmean1, nullptr, (size_t)C * 4, s));
-        std::vector<float> x1((size_t)C * d), st1(n_st1), mean1(C);
-        std::vector<bf16_t> xb1((size_t)Cpad * d);
         for (int sp = 0; sp < w; ++sp) {
             const int p = pos + sp;
             if (p == 0) {
                 WM_HIP(hipMemsetAsync(dpos, 0, 4, s));
-                WM_TRY(wm_dec_embed(ctx, (const int *)dseq1, (const int *)dpos, C, (const bf16_t *)de, (const float *)dp, d, (float *)dx1,
-                                    (bf16_t *)dxb1, (float *)dst1, (float *)dmean1));
+                WM_TRY(wm_dec_embed(ctx, dseq1, dpos, C, de, dp, d, dx1, dxb1, dst1, dmean1));
             } else {
                 const int pm = p - 1;
                 WM_HIP(hipMemcpyAsync(dpos, &pm, 4, hipMemcpyHostToDevice, s));
                 WM_HIP(hipStreamSynchronize(s));
-                WM_TRY(wm_argmax_embed(ctx, (const unsigned long long *)dtile, n_tiles, C, (int *)dseq1, (int *)dpos, n_ctx, nullptr, 0,
-                                       (const bf16_t *)de, (const float *)dp, d, n_ctx, (float *)dx1, (bf16_t *)dxb1, (float *)dst1, nullptr,
-                                       (int *)darr, 0, (float *)dmean1));
+                WM_TRY(wm_argmax_embed(ctx, dtile, n_tiles, C, dseq1, dpos, n_ctx, nullptr, 0, de, dp, d, n_ctx, dx1, dxb1, dst1, nullptr,
+                                       darr, 0, dmean1));
             }
             WM_HIP(hipMemcpyAsync(x1.data(), dx1, x1.size() * 4, hipMemcpyDeviceToHost, s));
             WM_HIP(hipMemcpyAsync(xb1.data(), dxb1, xb1.size() * 2, hipMemcpyDeviceToHost, s));
@@ -1257,9 +1242,7 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
                 memcpy(&hx[r * d], &x1[(size_t)c * d], (size_t)d * 4);
                 for (int j = 0; j < d; ++j) hxb[wm_tiled_offset(r, (size_t)j, (size_t)d)] = xb1[wm_tiled_offset((size_t)c, (size_t)j, (size_t)d)];
                 for (int pt = 0; pt < d / 16; ++pt)
-                    for (int i = 0; i < 2; ++i)
-                        hst[(r >> 4) * (size_t)(2 * d) + (size_t)pt * 32 + (r & 15) * 2 + i] =
-                            st1[((size_t)c >> 4) * (size_t)(2 * d) + (size_t)pt * 32 + (c & 15) * 2 + i];
+                    for (int i = 0; i < 2; ++i) hst[stat_at(d, r, pt, i)] = st1[stat_at(d, (size_t)c, pt, i)];
                 hmean[r] = mean1[c];
             }
         }
@@ -1270,7 +1253,7 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
     // statistics [B][d / 16][2]: the parts of row r
     for (size_t r = 0; r < (size_t)B; ++r)
         for (int pt = 0; pt < d / 16; ++pt)
-            for (int i = 0; i < 2; ++i) stats[(r * (d / 16) + pt) * 2 + i] = hst[(r >> 4) * (size_t)(2 * d) + (size_t)pt * 32 + (r & 15) * 2 + i];
+            for (int i = 0; i < 2; ++i) stats[(r * (d / 16) + pt) * 2 + i] = hst[stat_at(d, r, pt, i)];
     return WM_OK;
 }
 
@@ -1289,16 +1272,19 @@ extern "C" int wmdbg_align_capture_panel(wm_ctx *ctx, const float *dq, int d, in
     const int B = C * w;
     const size_t n_cap = (size_t)C * Tq * J * 64;
     const std::vector<uint32_t> fill(n_cap, WMDBG_SENTINEL_F32);
+    std::vector<float> q1(by_steps ? (size_t)C * d : 0);   // the step path: one position's rows
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dd, *dpos, *dcap, *d1;
+    const float *dd;
+    int *dpos;
+    float *dcap;
     WM_TRY(pool.get(&dd, dq, (size_t)B * d * 4, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
     WM_TRY(pool.get(&dcap, fill.data(), n_cap * 4, s));
     if (!by_steps) {
-        WM_TRY(wm_align_capture_q(ctx, (const float *)dd, d, B, L, (float *)dcap, Tq, J, (const int *)dpos, w));
+        WM_TRY(wm_align_capture_q(ctx, dd, d, B, L, dcap, Tq, J, dpos, w));
     } else {
-        std::vector<float> q1((size_t)C * d);
+        float *d1;
         WM_TRY(pool.get(&d1, nullptr, q1.size() * 4, s));
         for (int sp = 0; sp < w; ++sp) {
             for (int c = 0; c < C; ++c) memcpy(&q1[(size_t)c * d], dq + ((size_t)c * w + sp) * d, (size_t)d * 4);
@@ -1306,7 +1292,7 @@ extern "C" int wmdbg_align_capture_panel(wm_ctx *ctx, const float *dq, int d, in
             WM_HIP(hipMemcpyAsync(d1, q1.data(), q1.size() * 4, hipMemcpyHostToDevice, s));
             WM_HIP(hipMemcpyAsync(dpos, &p, 4, hipMemcpyHostToDevice, s));
             WM_HIP(hipStreamSynchronize(s));
-            WM_TRY(wm_align_capture_q(ctx, (const float *)d1, d, C, L, (float *)dcap, Tq, J, (const int *)dpos));
+            WM_TRY(wm_align_capture_q(ctx, d1, d, C, L, dcap, Tq, J, dpos));
         }
     }
     WM_HIP(hipMemcpyAsync(cap, dcap, n_cap * 4, hipMemcpyDeviceToHost, s));
@@ -1325,19 +1311,22 @@ extern "C" int wmdbg_align_token_prob_panel(wm_ctx *ctx, const float *logits, in
     for (size_t i = 0; i < (size_t)n_ctx * C; ++i) WM_REQUIRE(seq[i] >= 0 && seq[i] < eot, WM_ERR_INVALID, "align_token_prob_panel: token not below eot");
     const int B = C * w;
     const std::vector<uint32_t> fill((size_t)C * max_text, WMDBG_SENTINEL_F32);
+    std::vector<float> l1(by_steps ? (size_t)C * ldo : 0);   // the step path: one position's rows
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dl, *dseq, *dn, *dpos, *dp, *d1;
+    const float *dl;
+    const int *dseq, *dn;
+    int *dpos;
+    float *dp;
     WM_TRY(pool.get(&dl, logits, (size_t)B * ldo * 4, s));
     WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * C * 4, s));
     WM_TRY(pool.get(&dn, n_text, (size_t)C * 4, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
     WM_TRY(pool.get(&dp, fill.data(), fill.size() * 4, s));
     if (!by_steps) {
-        WM_TRY(wm_align_token_prob(ctx, (const float *)dl, ldo, (const int *)dseq, (const int *)dpos, B, S, eot, (const int *)dn, (float *)dp,
-                                   max_text, w, C));
+        WM_TRY(wm_align_token_prob(ctx, dl, ldo, dseq, dpos, B, S, eot, dn, dp, max_text, w, C));
     } else {
-        std::vector<float> l1((size_t)C * ldo);
+        float *d1;
         WM_TRY(pool.get(&d1, nullptr, l1.size() * 4, s));
         for (int sp = 0; sp < w; ++sp) {
             for (int c = 0; c < C; ++c) memcpy(&l1[(size_t)c * ldo], logits + ((size_t)c * w + sp) * ldo, (size_t)ldo * 4);
@@ -1345,8 +1334,7 @@ extern "C" int wmdbg_align_token_prob_panel(wm_ctx *ctx, const float *logits, in
             WM_HIP(hipMemcpyAsync(d1, l1.data(), l1.size() * 4, hipMemcpyHostToDevice, s));
             WM_HIP(hipMemcpyAsync(dpos, &p, 4, hipMemcpyHostToDevice, s));
             WM_HIP(hipStreamSynchronize(s));
-            WM_TRY(wm_align_token_prob(ctx, (const float *)d1, ldo, (const int *)dseq, (const int *)dpos, C, S, eot, (const int *)dn,
-                                       (float *)dp, max_text));
+            WM_TRY(wm_align_token_prob(ctx, d1, ldo, dseq, dpos, C, S, eot, dn, dp, max_text));
         }
     }
     WM_HIP(hipMemcpyAsync(prob, dp, fill.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1417,14 +1405,20 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     xp.sample = io->temperature > 0.f ? 1 : 0;
     xp.inv_T = io->temperature > 0.f ? (float)(1.0 / (double)io->temperature) : 0.f;   // as wm_transcribe fills it
     xp.sot_pos = io->sot_pos; xp.ns_tok = io->ns_tok; xp.chunk0 = io->chunk0; xp.n_prompt = n_prompt; xp.n_cand = 1;
+    WmRepPar rpar;
     const int zero = 0;
+    std::vector<float> lg((size_t)B * vpad), lp((size_t)n_ctx * B), stn(st_words);
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dx16, *dE, *dEf, *dc1, *dc2, *dg, *db, *dbias = nullptr, *dst, *dmin, *dmout, *dpemb, *dseq, *dpos, *darr, *dlog, *dtm, *dres, *dmask,
-        *drng = nullptr, *dhist = nullptr, *dkts = nullptr, *dlse = nullptr, *dxp = nullptr, *dtxt = nullptr, *dwin = nullptr, *dall = nullptr,
-        *dnsv = nullptr, *dlp = nullptr, *dns, *ddone = nullptr, *dbud = nullptr, *dlive = nullptr, *dnl = nullptr, *doff = nullptr, *dxn, *dxbn,
-        *dstn, *dmn;
-    WM_TRY(pool.get(&dx16, x16.data(), x16.size() * 2, s));
+    DecGemvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.epi = io->x_on ? DE_LOGITS_X : DE_LOGITS; a.B = B; a.N = V; a.K = K; a.stats_parts = K / 16; a.ldo = vpad;
+    a.arg_first = io->arg_first; a.arg_last = io->arg_last;
+    const bf16_t *dE;
+    bf16_t *dEf;
+    float *dc1, *dc2;
+    const float *dg, *db, *dbias = nullptr, *dpemb;
+    WM_TRY(pool.get(&a.a, x16.data(), x16.size() * 2, s));
     WM_TRY(pool.get(&dE, e16.data(), e16.size() * 2, s));
     WM_TRY(pool.get(&dEf, nullptr, e16.size() * 2, s));
     WM_TRY(pool.get(&dc1, nullptr, (size_t)vpad * 4, s));
@@ -1432,95 +1426,88 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     WM_TRY(pool.get(&dg, io->ln_g, (size_t)K * 4, s));
     WM_TRY(pool.get(&db, io->ln_b, (size_t)K * 4, s));
     if (io->bias) WM_TRY(pool.get(&dbias, io->bias, (size_t)V * 4, s));
-    WM_TRY(pool.get(&dst, st.data(), st.size() * 4, s));
-    WM_TRY(pool.get(&dmin, mean.data(), (size_t)B * 4, s));
-    WM_TRY(pool.get(&dmout, nullptr, (size_t)B * 4, s));
+    WM_TRY(pool.get(&a.stats_in, st.data(), st.size() * 4, s));
+    WM_TRY(pool.get(&a.mean_in, mean.data(), (size_t)B * 4, s));
+    WM_TRY(pool.get(&a.mean_out, nullptr, (size_t)B * 4, s));
     WM_TRY(pool.get(&dpemb, io->pemb, (size_t)n_ctx * K * 4, s));
+    int *dseq;
     {   // n_ctx + 1 rows, as the model's buffer: the close of the last position writes its token to row n_ctx
         std::vector<int32_t> seq0((size_t)(n_ctx + 1) * B, 0);
         std::copy(io->seq, io->seq + (size_t)n_ctx * B, seq0.begin());
         WM_TRY(pool.get(&dseq, seq0.data(), seq0.size() * 4, s));
         WM_HIP(hipStreamSynchronize(s));   // seq0 leaves scope
     }
+    int *dpos, *darr, *dres;
+    const unsigned *dmask;
     WM_TRY(pool.get(&dpos, &pos, 4, s));
     WM_TRY(pool.get(&darr, &zero, 4, s));
-    WM_TRY(pool.get(&dlog, nullptr, (size_t)B * vpad * 4, s));
-    WM_TRY(pool.get(&dtm, nullptr, nt * 8, s, 0xff));
+    WM_TRY(pool.get(&a.out_f32, nullptr, (size_t)B * vpad * 4, s));
+    WM_TRY(pool.get(&a.argmax, nullptr, nt * 8, s, 0xff));
     WM_TRY(pool.get(&dres, nullptr, (size_t)B * 4, s, 0xff));
     WM_TRY(pool.get(&dmask, mask.data(), mask.size() * 4, s));
+    a.pos_ptr = dpos;
+    if (mask_on) { a.mask = dmask; a.mask_words = mw; a.mask_first_pos = io->mask_first ? pos : -1; }
     WmTsDev ts;
     memset(&ts, 0, sizeof(ts));
     if (io->ts_mode) {
-        WM_TRY(pool.get(&drng, io->ts_mode == 2 ? io->rng : nullptr, (size_t)B * 16, s));
-        WM_TRY(pool.get(&dhist, io->ts_mode == 2 ? io->hist : nullptr, (size_t)B * 16, s));
-        WM_TRY(pool.get(&dkts, nullptr, nt * 8, s, 0xff));
-        WM_TRY(pool.get(&dlse, nullptr, nt * 8, s, 0xff));
-        ts.rng = (int *)drng; ts.hist = (int *)dhist; ts.key_ts = (unsigned long long *)dkts; ts.lse = (float *)dlse;
+        WM_TRY(pool.get(&ts.rng, io->ts_mode == 2 ? io->rng : nullptr, (size_t)B * 16, s));
+        WM_TRY(pool.get(&ts.hist, io->ts_mode == 2 ? io->hist : nullptr, (size_t)B * 16, s));
+        WM_TRY(pool.get(&ts.key_ts, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&ts.lse, nullptr, nt * 8, s, 0xff));
         ts.ts_begin = io->ts_begin; ts.eot = io->eot; ts.n_vocab = V; ts.max_initial = io->max_initial;
         if (io->ts_mode == 1) WM_TRY(wm_ts_init(ctx, ts, B));
     }
+    a.ts = ts;
     WmXDev xd;
     memset(&xd, 0, sizeof(xd));
+    float *dns, *dlp;
     WM_TRY(pool.get(&dns, nan32.data(), (size_t)B * 4, s));
     WM_TRY(pool.get(&dlp, nan32.data(), (size_t)n_ctx * B * 4, s));
     if (io->x_on) {
-        WM_TRY(pool.get(&dxp, &xp, sizeof(xp), s));
-        WM_TRY(pool.get(&dtxt, nullptr, nt * 8, s, 0xff));
-        WM_TRY(pool.get(&dwin, nullptr, nt * 8, s, 0xff));
-        WM_TRY(pool.get(&dall, nullptr, nt * 8, s, 0xff));
-        WM_TRY(pool.get(&dnsv, nullptr, (size_t)B * 4, s, 0xff));
-        xd.par = (const WmXPar *)dxp; xd.txt = (float *)dtxt; xd.win = (float *)dwin; xd.all = (float *)dall; xd.ns_v = (float *)dnsv;
-        xd.logprob = (float *)dlp; xd.nospeech = (float *)dns;
+        WM_TRY(pool.get(&xd.par, &xp, sizeof(xp), s));
+        WM_TRY(pool.get(&xd.txt, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&xd.win, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&xd.all, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&xd.ns_v, nullptr, (size_t)B * 4, s, 0xff));
+        xd.logprob = dlp; xd.nospeech = dns;
     }
+    a.x = xd;
     WmStopDev sp;
     memset(&sp, 0, sizeof(sp));
     if (io->stop_on) {
-        WM_TRY(pool.get(&ddone, nullptr, (size_t)B * 4, s));
-        WM_TRY(pool.get(&dlive, nullptr, (size_t)B * 4, s));
-        WM_TRY(pool.get(&dnl, nullptr, 4, s));
-        if (io->budget) WM_TRY(pool.get(&dbud, io->budget, (size_t)B * 4, s));
-        sp.done = (int *)ddone; sp.budget = (const int *)dbud; sp.live_rows = (int *)dlive; sp.n_live = (int *)dnl;
+        WM_TRY(pool.get(&sp.done, nullptr, (size_t)B * 4, s));
+        WM_TRY(pool.get(&sp.live_rows, nullptr, (size_t)B * 4, s));
+        WM_TRY(pool.get(&sp.n_live, nullptr, 4, s));
+        if (io->budget) WM_TRY(pool.get(&sp.budget, io->budget, (size_t)B * 4, s));
         sp.eot = io->stop_eot; sp.pad_tok = io->pad_tok;
         WM_TRY(wm_stop_init(ctx, sp, B));
-        WM_HIP(hipMemcpyAsync(ddone, io->done, (size_t)B * 4, hipMemcpyHostToDevice, s));   // the flags of the positions before this one
-        WM_HIP(hipMemsetAsync(dlive, 0xff, (size_t)B * 4, s));   // -1: the close rebuilds the list, what it leaves alone shows
+        WM_HIP(hipMemcpyAsync(sp.done, io->done, (size_t)B * 4, hipMemcpyHostToDevice, s));   // the flags of the positions before this one
+        WM_HIP(hipMemsetAsync(sp.live_rows, 0xff, (size_t)B * 4, s));   // -1: the close rebuilds the list, what it leaves alone shows
     }
+    const int *doff = nullptr;
+    float *dxn, *dstn, *dmn;
+    bf16_t *dxbn;
     if (io->off) WM_TRY(pool.get(&doff, io->off, (size_t)B * 4, s));
     WM_TRY(pool.get(&dxn, nan32.data(), (size_t)B * K * 4, s));
     WM_TRY(pool.get(&dxbn, nan16.data(), nan16.size() * 2, s));
     WM_TRY(pool.get(&dstn, nan32.data(), st_words * 4, s));
     WM_TRY(pool.get(&dmn, nullptr, (size_t)B * 4, s));
-    WM_TRY(wm_ln_fold(ctx, (const bf16_t *)dE, (const float *)dg, (const float *)db, (const float *)dbias, V, K, (bf16_t *)dEf,
-                      (float *)dc1, (float *)dc2));
-    DecGemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.epi = io->x_on ? DE_LOGITS_X : DE_LOGITS; a.B = B; a.N = V; a.K = K; a.W = (const bf16_t *)dEf; a.c1 = (const float *)dc1;
-    a.c2 = (const float *)dc2; a.a = (const bf16_t *)dx16; a.stats_in = (const float *)dst; a.stats_parts = K / 16;
-    a.mean_in = (const float *)dmin; a.mean_out = (float *)dmout;
-    a.out_f32 = (float *)dlog; a.ldo = vpad; a.argmax = (unsigned long long *)dtm; a.arg_first = io->arg_first; a.arg_last = io->arg_last;
-    a.pos_ptr = (const int *)dpos;
-    if (mask_on) { a.mask = (const unsigned *)dmask; a.mask_words = mw; a.mask_first_pos = io->mask_first ? pos : -1; }
-    a.ts = ts;
-    a.x = xd;
-    WmRepPar rpar;
+    WM_TRY(wm_ln_fold(ctx, dE, dg, db, dbias, V, K, dEf, dc1, dc2));
+    a.W = dEf; a.c1 = dc1; a.c2 = dc2;
     if (rep) {   // bitmaps pre-filled with 0xff: every word the epilogue reads must have been rebuilt by this position's launch
-        void *dseen, *dban, *drp;
         rpar.p = penalty; rpar.inv_p = (float)(1.0 / (double)penalty); rpar.n = ngram; rpar.eot = io->eot;
-        WM_TRY(pool.get(&dseen, nullptr, (size_t)B * mw * 4, s, 0xff));
-        WM_TRY(pool.get(&dban, nullptr, (size_t)B * mw * 4, s, 0xff));
-        WM_TRY(pool.get(&drp, &rpar, sizeof(rpar), s));
+        WM_TRY(pool.get(&a.rep.seen, nullptr, (size_t)B * mw * 4, s, 0xff));
+        WM_TRY(pool.get(&a.rep.ban, nullptr, (size_t)B * mw * 4, s, 0xff));
+        WM_TRY(pool.get(&a.rep.par, &rpar, sizeof(rpar), s));
         a.epi = DE_LOGITS_XR;
-        a.rep.par = (const WmRepPar *)drp; a.rep.seen = (unsigned *)dseen; a.rep.ban = (unsigned *)dban; a.rep.words = mw;
-        WM_TRY(wm_repeat_state(ctx, (const int *)dseq, (const int *)dpos, B, n_prompt, n_ctx, V, a.rep));
+        a.rep.words = mw;
+        WM_TRY(wm_repeat_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, a.rep));
     }
     WM_TRY(wm_dec_gemv(ctx, a));
-    WM_TRY(wm_argmax_embed(ctx, (const unsigned long long *)dtm, n_tiles, B, (int *)dseq, (int *)dpos, n_prompt, (int *)dres, io->arg_first,
-                           (const bf16_t *)dE, (const float *)dpemb, K, n_ctx, (float *)dxn, (bf16_t *)dxbn, (float *)dstn,
-                           io->ts_mode ? &ts : nullptr, (int *)darr, io->fallback_tok, (float *)dmn, io->stop_on ? &sp : nullptr,
-                           io->x_on ? &xd : nullptr, (const int *)doff));
-    std::vector<float> lg((size_t)B * vpad), lp((size_t)n_ctx * B), stn(st_words);
-    std::vector<bf16_t> xbn(nan16.size());
-    WM_HIP(hipMemcpyAsync(lg.data(), dlog, lg.size() * 4, hipMemcpyDeviceToHost, s));
+    WM_TRY(wm_argmax_embed(ctx, a.argmax, n_tiles, B, dseq, dpos, n_prompt, dres, io->arg_first, dE, dpemb, K, n_ctx, dxn, dxbn, dstn,
+                           io->ts_mode ? &ts : nullptr, darr, io->fallback_tok, dmn, io->stop_on ? &sp : nullptr,
+                           io->x_on ? &xd : nullptr, doff));
+    WM_HIP(hipMemcpyAsync(lg.data(), a.out_f32, lg.size() * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(io->result, dres, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(io->seq, dseq, (size_t)n_ctx * B * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(lp.data(), dlp, lp.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1528,19 +1515,18 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     WM_HIP(hipMemcpyAsync(&io->pos_out, dpos, 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(&io->arrive_out, darr, 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(io->x_next, dxn, (size_t)B * K * 4, hipMemcpyDeviceToHost, s));
-    WM_HIP(hipMemcpyAsync(xbn.data(), dxbn, xbn.size() * 2, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(stn.data(), dstn, stn.size() * 4, hipMemcpyDeviceToHost, s));
     if (io->ts_mode) {
-        WM_HIP(hipMemcpyAsync(io->rng, drng, (size_t)B * 16, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(io->hist, dhist, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->rng, ts.rng, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->hist, ts.hist, (size_t)B * 16, hipMemcpyDeviceToHost, s));
     }
     io->n_live = -1;
     if (io->stop_on) {
-        WM_HIP(hipMemcpyAsync(io->done, ddone, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(io->live_rows, dlive, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        WM_HIP(hipMemcpyAsync(&io->n_live, dnl, 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->done, sp.done, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->live_rows, sp.live_rows, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(&io->n_live, sp.n_live, 4, hipMemcpyDeviceToHost, s));
     }
-    WM_HIP(hipStreamSynchronize(s));
+    WM_TRY(down_tiled_bf16(dxbn, (size_t)B, (size_t)K, io->xb_next, s));
     for (int b = 0; b < B; ++b) {
         memcpy(io->logits + (size_t)b * V, lg.data() + (size_t)b * vpad, (size_t)V * 4);
         io->tok[b] = io->result[b] + io->arg_first;
@@ -1553,21 +1539,15 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
         io->logprob_written += u != WMDBG_SENTINEL_F32;
     }
     memcpy(io->logprob, gi >= 0 ? (const void *)(lp.data() + (size_t)gi * B) : (const void *)nan32.data(), (size_t)B * 4);
-    untile_bf16(xbn, (size_t)B, (size_t)K, io->xb_next);
     io->stats_tail_nonzero = 0;
-    for (int b = 0; b < B; ++b) {   // block (b / 16): [K/16 parts][16][2], summed as wmdbg_dec_gemv_resid sums them
-        const float *blk = stn.data() + (size_t)(b >> 4) * 2 * K;
-        float s1 = 0.f, s2 = 0.f;
-        for (int part = 0; part < K / 16; ++part)
+    for (int b = 0; b < B; ++b) {   // summed as wmdbg_dec_gemv_resid sums them; the tail: words behind part 0 that are not zero bits
+        stats_sum(stn.data(), K, b, io->stats_next + b * 2);
+        for (int part = 1; part < K / 16; ++part)
             for (int c = 0; c < 2; ++c) {
-                const float v = blk[(part * 16 + (b & 15)) * 2 + c];
-                (c ? s2 : s1) += v;
                 uint32_t u;
-                memcpy(&u, &v, 4);
-                if (part > 0 && u != 0u) ++io->stats_tail_nonzero;
+                memcpy(&u, &stn[stat_at(K, b, part, c)], 4);
+                if (u != 0u) ++io->stats_tail_nonzero;
             }
-        io->stats_next[b * 2] = s1;
-        io->stats_next[b * 2 + 1] = s2;
     }
     return WM_OK;
 }
@@ -1589,17 +1569,17 @@ extern "C" int wmdbg_repeat_state(wm_ctx *ctx, const int32_t *seq, int B, int n_
     rpar.p = 1.f; rpar.inv_p = 1.f; rpar.n = ngram; rpar.eot = eot;
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dseq, *dpos, *drp, *dseen, *dban;
+    const int *dseq, *dpos;
+    WmRepDev rd;
+    rd.words = words;
     WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * B * 4, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
-    WM_TRY(pool.get(&drp, &rpar, sizeof(rpar), s));
-    WM_TRY(pool.get(&dseen, nullptr, (size_t)B * words * 4, s, 0xff));   // 0xff: a word the kernel leaves alone shows
-    WM_TRY(pool.get(&dban, nullptr, (size_t)B * words * 4, s, 0xff));
-    WmRepDev rd;
-    rd.par = (const WmRepPar *)drp; rd.seen = (unsigned *)dseen; rd.ban = (unsigned *)dban; rd.words = words;
-    WM_TRY(wm_repeat_state(ctx, (const int *)dseq, (const int *)dpos, B, n_prompt, n_ctx, V, rd));
-    WM_HIP(hipMemcpyAsync(seen_out, dseen, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
-    WM_HIP(hipMemcpyAsync(ban_out, dban, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_TRY(pool.get(&rd.par, &rpar, sizeof(rpar), s));
+    WM_TRY(pool.get(&rd.seen, nullptr, (size_t)B * words * 4, s, 0xff));   // 0xff: a word the kernel leaves alone shows
+    WM_TRY(pool.get(&rd.ban, nullptr, (size_t)B * words * 4, s, 0xff));
+    WM_TRY(wm_repeat_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, rd));
+    WM_HIP(hipMemcpyAsync(seen_out, rd.seen, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(ban_out, rd.ban, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipStreamSynchronize(s));
     return WM_OK;
 }
@@ -1678,22 +1658,6 @@ int gemm_map_check(const wmdbg_gemm_map &g, const float *A, const float *W, cons
     }
     return WM_OK;
 }
-
-void fill_bf16(std::vector<bf16_t> &v, size_t n) { v.assign(n, (bf16_t)WMDBG_SENTINEL_BF16); }
-void fill_f32(std::vector<float> &v, size_t n) {
-    const uint32_t u = WMDBG_SENTINEL_F32;
-    float f;
-    memcpy(&f, &u, 4);
-    v.assign(n, f);
-}
-// device bf16 -> host f32 (widened), synchronous
-int down_bf16(const void *d, size_t n, float *out, hipStream_t s) {
-    std::vector<bf16_t> t(n);
-    WM_HIP(hipMemcpyAsync(t.data(), d, n * 2, hipMemcpyDeviceToHost, s));
-    WM_HIP(hipStreamSynchronize(s));
-    from_bf16(t, out);
-    return WM_OK;
-}
 }  // namespace
 
 extern "C" int wmdbg_gemm_mapped(wm_ctx *ctx, const wmdbg_gemm_map *map, const float *A, const float *W, const float *bias,
@@ -1709,11 +1673,13 @@ extern "C" int wmdbg_gemm_mapped(wm_ctx *ctx, const wmdbg_gemm_map *map, const f
     to_bf16(W, w16, (size_t)g.N * g.K);
     DevPool pool;
     hipStream_t s = ctx->stream;
-    void *dA, *dW, *dB = nullptr, *dP = nullptr, *dC, *dVt = nullptr;
-    WM_TRY(pool.get(&dA, a16.data(), a16.size() * 2, s));
-    WM_TRY(pool.get(&dW, w16.data(), w16.size() * 2, s));
-    if (bias) WM_TRY(pool.get(&dB, bias, (size_t)g.N * 4, s));
-    if (g.epi == EPI_CONV2_F32) WM_TRY(pool.get(&dP, pos, (size_t)g.c_rpb * g.N * 4, s));
+    GemmArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    void *dC;   // f32 or bf16 by the epilogue
+    WM_TRY(pool.get(&ga.A, a16.data(), a16.size() * 2, s));
+    WM_TRY(pool.get(&ga.W, w16.data(), w16.size() * 2, s));
+    if (bias) WM_TRY(pool.get(&ga.bias, bias, (size_t)g.N * 4, s));
+    if (g.epi == EPI_CONV2_F32) WM_TRY(pool.get(&ga.pos, pos, (size_t)g.c_rpb * g.N * 4, s));
     if (g.epi == EPI_RESID_F32) {
         WM_TRY(pool.get(&dC, C, (size_t)g.c_elems * 4, s));   // in / out
     } else if (f32out) {
@@ -1725,16 +1691,12 @@ extern "C" int wmdbg_gemm_mapped(wm_ctx *ctx, const wmdbg_gemm_map *map, const f
     }
     if (g.epi == EPI_QKV_ENC) {
         fill_bf16(vt16, (size_t)g.vt_elems);
-        WM_TRY(pool.get(&dVt, vt16.data(), vt16.size() * 2, s));
+        WM_TRY(pool.get(&ga.vt, vt16.data(), vt16.size() * 2, s));
     }
-    GemmArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.A = (const bf16_t *)dA + g.a_off; ga.a_rpb = (long)g.a_rpb; ga.a_bstride = (long)g.a_bstride; ga.a_rstride = (long)g.a_rstride;
-    ga.W = (const bf16_t *)dW; ga.bias = (const float *)dB;
+    ga.A += g.a_off; ga.a_rpb = (long)g.a_rpb; ga.a_bstride = (long)g.a_bstride; ga.a_rstride = (long)g.a_rstride;
     ga.C = f32out ? (void *)((float *)dC + g.c_off) : (void *)((bf16_t *)dC + g.c_off);
     ga.c_rpb = (long)g.c_rpb; ga.c_bstride = (long)g.c_bstride; ga.c_rstride = (long)g.c_rstride;
     ga.M = g.M; ga.N = g.N; ga.K = g.K; ga.epi = g.epi;
-    ga.pos = (const float *)dP; ga.vt = (bf16_t *)dVt;
     ga.d_model = g.d_model; ga.n_head = g.n_head; ga.seq = g.seq; ga.seq_pad = g.seq_pad; ga.batch = g.batch;
     if (g.epi == EPI_XKV) { ga.C = dC; ga.c_rpb = (long)g.M + 1; }   // (the scatter ignores the C map; wm_gemm wants c_rpb > 0)
     WM_TRY(wm_gemm(ctx, ga));
@@ -1744,7 +1706,7 @@ extern "C" int wmdbg_gemm_mapped(wm_ctx *ctx, const wmdbg_gemm_map *map, const f
     } else {
         WM_TRY(down_bf16(dC, (size_t)g.c_elems, C, s));
     }
-    if (g.epi == EPI_QKV_ENC) WM_TRY(down_bf16(dVt, (size_t)g.vt_elems, vt, s));
+    if (g.epi == EPI_QKV_ENC) WM_TRY(down_bf16(ga.vt, (size_t)g.vt_elems, vt, s));
     return WM_OK;
 }
 
@@ -1779,23 +1741,24 @@ extern "C" int wmdbg_encode_stem(wm_ctx *ctx, const float *mel, const int64_t *w
             mel_elems = std::max(mel_elems, (size_t)(base + (int64_t)C * T));
         }
     }
-    DevPool pool;
-    hipStream_t s = ctx->stream;
-    void *dmel, *dwin = nullptr;
-    WM_TRY(pool.get(&dmel, mel, mel_elems * 4, s));
-    if (wins) WM_TRY(pool.get(&dwin, win.data(), win.size() * sizeof(WmMelWin), s));
     // sentinels in everything the three launches must write; the guard rows (mel_t rows 0 and 3001, h1p row 0) stay as the
     // allocation left them
     std::vector<bf16_t> s16;
     std::vector<float> s32;
     fill_bf16(s16, (size_t)3000 * std::max(C, d));
     fill_f32(s32, (size_t)B * 1500 * d);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    const float *dmel;
+    const WmMelWin *dwin = nullptr;
+    WM_TRY(pool.get(&dmel, mel, mel_elems * 4, s));
+    if (wins) WM_TRY(pool.get(&dwin, win.data(), win.size() * sizeof(WmMelWin), s));
     for (int b = 0; b < B; ++b) {
         WM_HIP(hipMemcpyAsync(m->mel_t + ((size_t)b * 3002 + 1) * C, s16.data(), (size_t)3000 * C * 2, hipMemcpyHostToDevice, s));
         WM_HIP(hipMemcpyAsync(m->h1p + ((size_t)b * 3001 + 1) * d, s16.data(), (size_t)3000 * d * 2, hipMemcpyHostToDevice, s));
     }
     WM_HIP(hipMemcpyAsync(m->x, s32.data(), s32.size() * 4, hipMemcpyHostToDevice, s));
-    WM_TRY(wm_model_encode_stem(ctx, (const float *)dmel, (const WmMelWin *)dwin, B));
+    WM_TRY(wm_model_encode_stem(ctx, dmel, dwin, B));
     WM_TRY(down_bf16(m->mel_t, (size_t)B * 3002 * C, mel_t_out, s));
     WM_TRY(down_bf16(m->h1p, (size_t)B * 3001 * d, h1p_out, s));
     WM_HIP(hipMemcpyAsync(x_out, m->x, (size_t)B * 1500 * d * 4, hipMemcpyDeviceToHost, s));
@@ -1836,14 +1799,14 @@ extern "C" int wmdbg_cross_kv(wm_ctx *ctx, const float *xa, int B, float *xkv_ou
     const int d = D.n_text_state, H = D.n_text_head;
     const size_t M = (size_t)B * 1500, used = (size_t)D.n_text_layer * 2 * B * H * 1500 * 64,
                  cap = (size_t)D.n_text_layer * 2 * m->cap_b * H * 1500 * 64;   // the whole allocation (wm_model_reserve)
-    DevPool pool;
-    hipStream_t s = ctx->stream;
-    void *dxa;
-    WM_TRY(pool.get(&dxa, xa, M * d * 4, s));
     std::vector<bf16_t> s16, got(cap);
     fill_bf16(s16, cap);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    const float *dxa;
+    WM_TRY(pool.get(&dxa, xa, M * d * 4, s));
     WM_HIP(hipMemcpyAsync(m->xkv, s16.data(), cap * 2, hipMemcpyHostToDevice, s));
-    int rc = wm_model_set_xa(ctx, (const float *)dxa, B);
+    int rc = wm_model_set_xa(ctx, dxa, B);
     if (rc == WM_OK) rc = wm_model_cross_kv(ctx, B);
     WM_HIP(hipMemcpyAsync(got.data(), m->xkv, cap * 2, hipMemcpyDeviceToHost, s));
     if (cap > used) WM_HIP(hipMemsetAsync(m->xkv + used, 0, (cap - used) * 2, s));
