@@ -247,7 +247,7 @@ WM_API int wmdbg_cu_mask(int cu_lo, int cu_hi, uint32_t *mask8);
  * WM_BF16 restores the product kernels.  wm_detect_language / wm_transcribe_greedy are not affected. */
 WM_API int wmdbg_set_precision(wm_ctx *ctx, int precision);
 
-/* Launch-shape experiment knobs (csrc/wm_internal.h, struct WmTuning), by name: "gemv_tn", "gemv_nblk", "gemv_no_ppw2",
+/* Launch-shape experiment knobs (csrc/wm_tuning.h, struct WmTuning), by name: "gemv_tn", "gemv_nblk", "gemv_no_ppw2",
  * "prefetch_max_b", "xattn_split_below", "xattn_wgs", "xattn_no_flat", "xattn_lds_pad", "xattn_splits", "gemm_tile",
  * "gemm_gm", "no_early_stop", "xattn_no_deep", "xattn_never_short", "logits_tn", "enc_attn_mfma_sum"; key "reset" restores the product's rules.  Process-wide.  The PRODUCT library has no such
  * entry point and reads no environment variable for launch shapes (rounds 1-3 had WM_GEMV_*, WM_XATTN_*, WM_GEMM_*). */
@@ -265,6 +265,19 @@ WM_API int wmdbg_right_align(const int32_t *prompts, int stride, const int32_t *
  * holds windows [b0_out[g], b0_out[g] + cg_out[g]) = cg_out[g] * N decoder rows.  Returns the number of groups (room for B
  * entries in both arrays), or -1 on bad arguments. */
 WM_API int wmdbg_cand_groups(int B, int N, int lanes, int explicit_lanes, int32_t *b0_out, int32_t *cg_out);
+/* The decode step's launch plans as pure functions (host only, no context, no GPU; csrc/dec_launch.h), under the current
+ * wmdbg_set_tuning state, for n cases at once; return n, or -1 on bad arguments.
+ * wmdbg_dec_attn_plan: in i32 [n][16] = form (0 cross, 1 candidate group, 2 fused query, 3 self, 4 panel), B, C, N (panel: the
+ *   width), H, T_stride, n_keys, nsplit, K (fused query), flags (1 device position, 2 partials buffer, 4 row offsets, 8 warm-up
+ *   matrix, 16 short_lived, 32 live list -- which no plan reads), pf_rows, pf_k, CUs of the lane, 0, 0, 0;
+ *   out i32 [n][16] = status (WM_OK / WM_ERR_INVALID; the rest 0 when refused), variant (DecAttnVariant), spw, grid x, grid y,
+ *   block, dynamic LDS bytes, compute workgroups, warm-up tiles, bytes per tile, packA, packB, packC, combine grid (0: none),
+ *   [14] (also when refused; B <= 128 and H <= 255 only) = cross: wm_dec_attn_splits(B, H); fused query: wm_dec_xattn_fq_applies(B, H, K, short_lived), 0.
+ * wmdbg_dec_gemv_plan: in i32 [n][12] = epilogue (DecEpi), LayerNorm mode, B, N, K, warm-up matrix present, pf_rows, pf_k,
+ *   pf_head_major, CUs of the lane, 0, 0;  out i32 [n][20] = status, nw, spw, tn, nblk, ppw, row split, bgroups, n_tiles, n_tg,
+ *   n_tg_pad, grid, block, dynamic LDS bytes, warm-up tiles, bytes per tile, pf_head_major, 0, 0, 0. */
+WM_API int wmdbg_dec_attn_plan(const int32_t *in, int n, int32_t *out);
+WM_API int wmdbg_dec_gemv_plan(const int32_t *in, int n, int32_t *out);
 /* The cross-attention launch of a candidate group exactly as the decode step makes it (wm_dec_attention_cand): C windows x N
  * candidates, q f32 [C * N][H * 64] (row c * N + s = candidate s of window c), k / v f32 [C][H][T][64] (rounded to bf16), the
  * first n_keys positions; live_rows: the compact ascending list of the n_live live rows (NULL: every row is live);

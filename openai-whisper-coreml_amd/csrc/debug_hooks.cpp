@@ -245,7 +245,7 @@ struct SideBranch {
 int wm_gemm_set_tile_override(int tile);
 extern "C" int wmdbg_set_gemm_tile(int tile) { return wm_gemm_set_tile_override(tile); }
 
-// The launch-shape experiment knobs (wm_internal.h WmTuning): by name, so that tools/ scripts need no struct mirror.
+// The launch-shape experiment knobs (wm_tuning.h WmTuning): by name, so that tools/ scripts need no struct mirror.
 extern "C" int wmdbg_set_tuning(const char *key, int value) {
     WM_REQUIRE(key, WM_ERR_INVALID, "wmdbg_set_tuning: null key");
     struct { const char *name; int *field; } table[] = {
@@ -272,6 +272,16 @@ extern "C" int wmdbg_cand_groups(int B, int N, int lanes, int explicit_lanes, in
     const int G = wm_cand_groups(B, N, lanes, explicit_lanes != 0, b0, cg);
     for (int g = 0; g < G; ++g) { b0_out[g] = b0[g]; cg_out[g] = cg[g]; }
     return G;
+}
+extern "C" int wmdbg_dec_attn_plan(const int32_t *in, int n, int32_t *out) {
+    if (!in || !out || n < 0) return -1;
+    for (int i = 0; i < n; ++i) wm_attn_plan_flat(in + (size_t)i * WM_ATTN_PLAN_IN, g_wm_tuning, out + (size_t)i * WM_ATTN_PLAN_OUT);
+    return n;
+}
+extern "C" int wmdbg_dec_gemv_plan(const int32_t *in, int n, int32_t *out) {
+    if (!in || !out || n < 0) return -1;
+    for (int i = 0; i < n; ++i) wm_gemv_plan_flat(in + (size_t)i * WM_GEMV_PLAN_IN, g_wm_tuning, out + (size_t)i * WM_GEMV_PLAN_OUT);
+    return n;
 }
 extern "C" int wmdbg_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg,
                                  int32_t *table_out, int32_t *off_out) {
@@ -478,8 +488,10 @@ extern "C" int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, 
     WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
     // nsplit == 0 selects the decoder's self-attention kernel (one 4-wave workgroup per pair), nsplit == -1 the
     // cross-attention launch path (8-wave block-streaming kernel, capped grid)
-    WM_TRY(nsplit == 0 ? wm_dec_self_attention(ctx, dq, dk, dv, B, H, T, n_keys, nullptr, datt)
-                       : wm_dec_attention(ctx, dq, dk, dv, B, H, T, n_keys, nullptr, nsplit < 0 ? 1 : nsplit, dp, datt, nsplit < 0));
+    DecAttnArgs t = {};
+    t.q = dq; t.kc = dk; t.vc = dv; t.att = datt; t.part = dp; t.B = B; t.H = H; t.T_stride = T; t.n_keys = n_keys;
+    t.nsplit = nsplit < 0 ? 1 : nsplit;
+    WM_TRY(nsplit == 0 ? wm_dec_self_attention(ctx, t) : wm_dec_attention(ctx, t));
     return down_tiled_bf16(datt, (size_t)B, (size_t)H * 64, out, s);
 }
 
@@ -519,9 +531,10 @@ static int dec_attention_cand(wm_ctx *ctx, const float *q, const float *k, const
     WM_TRY(pool.get(&dp, nullptr, (size_t)B * H * WM_MAXSPLIT * 66 * 4, s));
     WM_TRY(pool.get(&dl, live.data(), live.size() * 4, s));
     WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
-    const int *lr = live_rows ? dl : nullptr;
-    WM_TRY(wm_dec_attention_cand(ctx, dq, dk, dv, C, N, H, T, n_keys, dp, datt, nullptr, 0, 0, lr, lr ? lr + WM_DEC_MAXB : nullptr,
-                                 short_lived));
+    DecAttnArgs t = {};
+    t.q = dq; t.kc = dk; t.vc = dv; t.att = datt; t.part = dp; t.C = C; t.N = N; t.H = H; t.T_stride = T; t.n_keys = n_keys;
+    t.live = live_rows ? dl : nullptr; t.short_lived = short_lived;
+    WM_TRY(wm_dec_attention_cand(ctx, t));
     return down_tiled_bf16(datt, (size_t)B, (size_t)H * 64, out, s);
 }
 
@@ -557,7 +570,9 @@ extern "C" int wmdbg_dec_self_attention_off(wm_ctx *ctx, const float *q, const f
     WM_TRY(pool.get(&doff, off, (size_t)B * 4, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
     WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
-    WM_TRY(wm_dec_self_attention(ctx, dq, dk, dv, B, H, T, 0, dpos, datt, nullptr, 0, 0, nullptr, nullptr, doff));
+    DecAttnArgs t = {};
+    t.q = dq; t.kc = dk; t.vc = dv; t.att = datt; t.B = B; t.H = H; t.T_stride = T; t.pos_ptr = dpos; t.off = doff;
+    WM_TRY(wm_dec_self_attention(ctx, t));
     return down_tiled_bf16(datt, (size_t)B, (size_t)H * 64, out, s);
 }
 
@@ -623,11 +638,15 @@ extern "C" int wmdbg_bench_dec_attention(wm_ctx *ctx, int B, int H, int T, int n
     WM_TRY(pool.get(&datt, nullptr, ((size_t)B + 15) / 16 * 16 * H * 64 * 2, s));
     EventPair ev;
     WM_TRY(ev.init());
+    DecAttnArgs t = {};
+    t.q = dq; t.att = datt; t.part = dp; t.B = B; t.H = H; t.T_stride = T; t.n_keys = n_keys; t.nsplit = nsplit;
     for (int pass = 0; pass < 2; ++pass) {   // a warm pass, then the timed one
         if (pass == 1) WM_TRY(ev.start(s));
-        for (int i = 0; i < iters; ++i)
-            WM_TRY(wm_dec_attention(ctx, dq, dk + (size_t)(i % n_slices) * slice, dv + (size_t)(i % n_slices) * slice, B, H, T, n_keys,
-                                    nullptr, nsplit, dp, datt, true));
+        for (int i = 0; i < iters; ++i) {
+            t.kc = dk + (size_t)(i % n_slices) * slice;
+            t.vc = dv + (size_t)(i % n_slices) * slice;
+            WM_TRY(wm_dec_attention(ctx, t));
+        }
     }
     float us = 0.f;
     WM_TRY(ev.stop_us(s, &us));
@@ -1154,7 +1173,9 @@ extern "C" int wmdbg_dec_self_attention_panel(wm_ctx *ctx, const float *q, const
     WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
     WM_TRY(pool.get(&datt, fill.data(), fill.size() * 2, s));
-    WM_TRY(wm_dec_self_attention_panel(ctx, dq, dk, dv, C, w, H, T, dpos, datt));
+    DecAttnArgs t = {};
+    t.q = dq; t.kc = dk; t.vc = dv; t.att = datt; t.C = C; t.N = w; t.H = H; t.T_stride = T; t.pos_ptr = dpos;
+    WM_TRY(wm_dec_self_attention_panel(ctx, t));
     return down_tiled_bf16(datt, (size_t)out_rows, dd, out, s);
 }
 

@@ -88,10 +88,6 @@ struct DecGemvDev {
     WmRepDev rep;          // DE_LOGITS_XR: repetition rules (behind the older fields: they keep their kernel-argument offsets)
     int panel;             // DE_QKV_P: panel width (cold, like rep: read in the epilogue only)
 };
-// the extended-decode epilogues (DE_LOGITS_XR = DE_LOGITS_X + the repetition rules), and every logits epilogue
-constexpr bool de_is_x(int epi) { return epi == DE_LOGITS_X || epi == DE_LOGITS_XR; }
-constexpr bool de_is_logits(int epi) { return epi == DE_LOGITS || de_is_x(epi); }
-constexpr bool de_is_qkv(int epi) { return epi == DE_QKV || epi == DE_QKV_P; }
 
 // L2 warm-up workgroup: blockIdx >= n_tiles of the compute grid.  Workgroup n_tiles + t reads tile t of
 // the NEXT launch's weight matrix.  Dispatch places block b on XCD b % 8 (observed, not guaranteed --
@@ -797,7 +793,7 @@ __global__ void dec_pos_add_kernel(int *pos_ptr, int add) { *pos_ptr += add; }
 // waves takes the whole pair otherwise and writes the head output itself.  Tokens therefore do not depend on the size
 // of the decode group (bit-level batch invariance; the round-1 kernels switched arithmetic with the batch).
 // NT: non-temporal loads (a cross-attention cache row is read once per step).
-constexpr int ATT_MAXK = 1536;
+constexpr int ATT_MAXK = WM_ATT_MAXK;   // dec_launch.h: the plans check it
 #ifndef WM_XATTN_NT
 #define WM_XATTN_NT true  // cross-attention K/V rows: non-temporal loads (A/B builds: -DWM_XATTN_NT=false)
 #endif
@@ -963,6 +959,7 @@ struct AttnColdPanel {
 template <bool OFF, bool PANEL> struct AttnColdSel { typedef AttnCold type; };
 template <> struct AttnColdSel<true, false> { typedef AttnColdOff type; };
 template <> struct AttnColdSel<false, true> { typedef AttnColdPanel type; };
+// (packA / packB / packC: packed by wm_pack_attn_rows / wm_pack_attn_keys, dec_launch.h)
 template <int NS, int U, bool NT, bool DEEP = false, bool OFF = false, bool PANEL = false>
 __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
@@ -1143,6 +1140,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
 // schedule of THIS loop (packed FMAs across row groups, 196 instructions per block) is the one measured, and the shared
 // block helpers above reproduce it instruction for instruction.  Only the argument list is the new one (hot scalars
 // first, packed, preloaded); the key count of a cross-attention is an argument, so nothing here waits for the position.
+// (packA / packB / packC: packed by wm_pack_attn_rows / wm_pack_attn_keys, dec_launch.h)
 template <int NS, int U, bool NT, bool DEEP = false>
 __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
@@ -1292,6 +1290,7 @@ __device__ __forceinline__ void cand_window(const CandLive &L, int wj, int lane,
     }
 }
 
+// (packA / packB / packC: packed by wm_pack_attn_cand / wm_pack_attn_keys, dec_launch.h)
 template <int N, bool NT>
 __global__ __launch_bounds__(512) void dec_xcand_attn_kernel(
     const float *__restrict__ q, const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
@@ -1446,6 +1445,7 @@ struct FqCold {
     long pf_tile_bytes;
     int n_wg;              // compute workgroups; ids beyond are warm-up workgroups
 };
+// (packA / packB: packed by wm_pack_attn_fq / wm_pack_attn_keys, dec_launch.h)
 template <int SPW, bool NT>
 __global__ __launch_bounds__(512) void dec_xattn_fq_kernel(const bf16_t *__restrict__ Wq, const bf16_t *__restrict__ xb,
                                                            const bf16_t *__restrict__ kc, const bf16_t *__restrict__ vc,
@@ -1867,145 +1867,93 @@ __global__ __launch_bounds__(256) void synth_fill_kernel(void *dst, int is_bf16,
 }
 
 #define GEMV_ARGS(p) (p).W, (p).a, (p).pos_ptr, (p).c2, (p).K, (p).n_tiles, (p).B, (p).bgroups, (p).n_tg, (p).n_tg_pad, (p).out_f32, (p)
+// The plan (wm_plan_gemv) has chosen and checked the shape; here it is mapped to the kernel instantiation.  The TWO / RESID /
+// WIDE guards keep the set of instantiations to the shapes a plan can ask for.
 template <int SPW, int EPI, bool LN>
-int launch_gemv_shape(wm_ctx *ctx, const DecGemvDev &p, int tn, int nblk, int nw, int grid, int ppw) {
+int launch_gemv_shape(wm_ctx *ctx, const DecGemvDev &p, const DecGemvPlan &pl) {
     hipStream_t s = ctx->stream;
-    if (ppw == 2) {  // 16 K parts on 8 waves (the K = 4d residual products at more than one batch block)
-        constexpr bool TWO = !LN && EPI == DE_RESID && SPW >= 6 && SPW <= 10;
-        if (!TWO || tn != 1 || nblk < 1 || nblk > 2 || nw % 2) { wm_set_error("dec_gemv: no two-part kernel for this shape"); return WM_ERR_INVALID; }
-        const int w2 = nw / 2;
-        const size_t lds2 = (size_t)nw * nblk * 1024 + (size_t)w2 * 32 * 4;
-        if (nblk == 2) {   // two batch blocks per workgroup: a weight fragment feeds two products (w2 == 8: four waves per unit)
-            if (w2 != 8) { wm_set_error("dec_gemv: the two-block two-part kernel needs 8 waves"); return WM_ERR_INVALID; }
-            dec_gemv_kernel<TWO ? SPW : 6, 1, 2, TWO ? EPI : DE_RESID, TWO ? LN : false, 2, 4><<<grid, w2 * 64, lds2, s>>>(GEMV_ARGS(p));
-            WM_HIP(hipGetLastError());
-            return WM_OK;
-        }
-        // (row split, see the kernel: four waves per unit finish the residual epilogue; w2 >= 4 and more than one sequence)
-        if (w2 >= 4 && p.B > 1)
-            dec_gemv_kernel<TWO ? SPW : 6, 1, 1, TWO ? EPI : DE_RESID, TWO ? LN : false, 2, 4><<<grid, w2 * 64, lds2, s>>>(GEMV_ARGS(p));
-        else
-            dec_gemv_kernel<TWO ? SPW : 6, 1, 1, TWO ? EPI : DE_RESID, TWO ? LN : false, 2><<<grid, w2 * 64, lds2, s>>>(GEMV_ARGS(p));
-        WM_HIP(hipGetLastError());
-        return WM_OK;
-    }
+    const int tn = pl.tn, nblk = pl.nblk, grid = pl.grid, th = pl.block;
+    const size_t lds = (size_t)pl.lds;
+    constexpr bool TWO = !LN && EPI == DE_RESID && SPW >= 6 && SPW <= 10;
     constexpr bool RESID = !LN && EPI == DE_RESID;
-    const bool split = RESID && p.B > 1 && tn == 1 && nblk * 4 <= nw;   // four waves per (tile, block) unit
-    if (split && RESID) {
-        const size_t ldsr = (size_t)nw * nblk * 1024 + (size_t)nw * 32 * 4;
-        if (nblk == 1) dec_gemv_kernel<SPW, 1, 1, RESID ? EPI : DE_RESID, RESID ? LN : false, 1, 4><<<grid, nw * 64, ldsr, s>>>(GEMV_ARGS(p));
-        else if (nblk == 2 && SPW <= 8) dec_gemv_kernel<SPW <= 8 ? SPW : 2, 1, 2, RESID ? EPI : DE_RESID, RESID ? LN : false, 1, 4><<<grid, nw * 64, ldsr, s>>>(GEMV_ARGS(p));
-        else { wm_set_error("dec_gemv: unsupported row-split shape (nblk %d, spw %d)", nblk, SPW); return WM_ERR_INVALID; }
-        WM_HIP(hipGetLastError());
-        return WM_OK;
-    }
-    const size_t lds = (size_t)nw * tn * nblk * 1024 + (size_t)nw * 32 * 4;
-    const int th = nw * 64;
     constexpr bool LOGITS = de_is_logits(EPI);
     constexpr bool WIDE = LN && (de_is_qkv(EPI) || EPI == DE_GELU || LOGITS) && SPW <= 6;
-    if (tn == 1 && nblk == 1) dec_gemv_kernel<SPW, 1, 1, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+    if (pl.ppw == 2 && TWO) {  // 16 K parts on 8 waves (the K = 4d residual products at more than one batch block)
+        if (nblk == 2) dec_gemv_kernel<TWO ? SPW : 6, 1, 2, TWO ? EPI : DE_RESID, TWO ? LN : false, 2, 4><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+        else if (pl.row_split) dec_gemv_kernel<TWO ? SPW : 6, 1, 1, TWO ? EPI : DE_RESID, TWO ? LN : false, 2, 4><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+        else dec_gemv_kernel<TWO ? SPW : 6, 1, 1, TWO ? EPI : DE_RESID, TWO ? LN : false, 2><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+    } else if (pl.ppw == 1 && pl.row_split && RESID && nblk == 1) {   // four waves per (tile, block) unit
+        dec_gemv_kernel<SPW, 1, 1, RESID ? EPI : DE_RESID, RESID ? LN : false, 1, 4><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+    } else if (pl.ppw == 1 && pl.row_split && RESID && nblk == 2 && SPW <= 8) {
+        dec_gemv_kernel<SPW <= 8 ? SPW : 2, 1, 2, RESID ? EPI : DE_RESID, RESID ? LN : false, 1, 4><<<grid, th, lds, s>>>(GEMV_ARGS(p));
+    } else if (pl.ppw != 1 || pl.row_split) {
+        wm_set_error("dec_gemv: no kernel for the planned shape (ppw %d, row split %d, nblk %d, spw %d)", pl.ppw, pl.row_split, nblk, SPW);
+        return WM_ERR_INVALID;
+    }
+    else if (tn == 1 && nblk == 1) dec_gemv_kernel<SPW, 1, 1, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 1 && nblk == 2 && SPW <= 8) dec_gemv_kernel<SPW <= 8 ? SPW : 2, 1, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 2 && nblk == 1 && WIDE && LOGITS) dec_gemv_kernel<WIDE ? SPW : 2, 2, 1, WIDE ? EPI : DE_LOGITS, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 4 && nblk == 1 && WIDE && LOGITS) dec_gemv_kernel<WIDE ? SPW : 2, 4, 1, WIDE ? EPI : DE_LOGITS, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 2 && nblk == 2 && WIDE) dec_gemv_kernel<WIDE ? SPW : 2, 2, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
     else if (tn == 4 && nblk == 2 && WIDE) dec_gemv_kernel<WIDE ? SPW : 2, 4, 2, EPI, LN><<<grid, th, lds, s>>>(GEMV_ARGS(p));
-    else { wm_set_error("dec_gemv: unsupported launch shape (tn %d, nblk %d, spw %d)", tn, nblk, SPW); return WM_ERR_INVALID; }
+    else { wm_set_error("dec_gemv: no kernel for the planned shape (tn %d, nblk %d, spw %d)", tn, nblk, SPW); return WM_ERR_INVALID; }
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
 
 template <int EPI, bool LN>
-int launch_gemv(wm_ctx *ctx, const DecGemvDev &p, int spw, int tn, int nblk, int nw, int grid, int ppw) {
-    switch (spw) {
-        case 2: return launch_gemv_shape<2, EPI, LN>(ctx, p, tn, nblk, nw, grid, ppw);
-        case 4: return launch_gemv_shape<4, EPI, LN>(ctx, p, tn, nblk, nw, grid, ppw);
-        case 5: return launch_gemv_shape<5, EPI, LN>(ctx, p, tn, nblk, nw, grid, ppw);
-        case 6: return launch_gemv_shape<6, EPI, LN>(ctx, p, tn, nblk, nw, grid, ppw);
-        case 8: return launch_gemv_shape<8, EPI, LN>(ctx, p, tn, nblk, nw, grid, ppw);
-        case 10: return launch_gemv_shape<10, EPI, LN>(ctx, p, tn, nblk, nw, grid, ppw);
-        case 12: return launch_gemv_shape<12, EPI, LN>(ctx, p, tn, nblk, nw, grid, ppw);
-        default: wm_set_error("dec_gemv: unsupported k-steps per wave %d", spw); return WM_ERR_INVALID;
+int launch_gemv(wm_ctx *ctx, const DecGemvDev &p, const DecGemvPlan &pl) {
+    switch (pl.spw) {
+        case 2: return launch_gemv_shape<2, EPI, LN>(ctx, p, pl);
+        case 4: return launch_gemv_shape<4, EPI, LN>(ctx, p, pl);
+        case 5: return launch_gemv_shape<5, EPI, LN>(ctx, p, pl);
+        case 6: return launch_gemv_shape<6, EPI, LN>(ctx, p, pl);
+        case 8: return launch_gemv_shape<8, EPI, LN>(ctx, p, pl);
+        case 10: return launch_gemv_shape<10, EPI, LN>(ctx, p, pl);
+        case 12: return launch_gemv_shape<12, EPI, LN>(ctx, p, pl);
+        default: wm_set_error("dec_gemv: unsupported k-steps per wave %d", pl.spw); return WM_ERR_INVALID;
     }
 }
+
+// every (epilogue, LayerNorm) pair the GEMV is instantiated for, with its profiler label (label_k: the label when K > N)
+const struct GemvEpi {
+    int epi;
+    bool ln;
+    const char *label, *label_k;
+    int (*launch)(wm_ctx *, const DecGemvDev &, const DecGemvPlan &);
+} kGemvEpi[] = {
+    {DE_QKV, true, "dec_gemv_ln_qkv", nullptr, launch_gemv<DE_QKV, true>},
+    {DE_QKV_P, true, "dec_gemv_ln_qkv", nullptr, launch_gemv<DE_QKV_P, true>},
+    {DE_Q, true, "dec_gemv_ln_q", nullptr, launch_gemv<DE_Q, true>},
+    {DE_GELU, true, "dec_gemv_ln_fc1", nullptr, launch_gemv<DE_GELU, true>},
+    {DE_LOGITS, true, "dec_gemv_ln_logits", nullptr, launch_gemv<DE_LOGITS, true>},
+    {DE_LOGITS_X, true, "dec_gemv_ln_logits_x", nullptr, launch_gemv<DE_LOGITS_X, true>},
+    {DE_LOGITS_XR, true, "dec_gemv_ln_logits_xr", nullptr, launch_gemv<DE_LOGITS_XR, true>},
+    {DE_RESID, false, "dec_gemv_attn_out", "dec_gemv_fc2", launch_gemv<DE_RESID, false>},
+    {DE_Q, false, "dec_gemv_plain", nullptr, launch_gemv<DE_Q, false>},
+};
 
 }  // namespace
 
-// Split of K over the waves of a workgroup: a function of K ONLY (never of the batch), so that the order in which a
-// row's sum is formed -- and therefore every logit bit -- does not depend on the decode group the row is in.
-// Returns the wave count; *spw = k-steps (of 32) per wave, one of {2, 4, 5, 6, 8, 10, 12}.
-int wm_dec_gemv_split(int K, int *spw) {
-    const int steps = K / 32;
-    for (int nw = steps >= 96 ? 16 : 8; nw >= 1; --nw) {
-        if (steps % nw) continue;
-        const int s = steps / nw;
-        if (s == 2 || s == 4 || s == 5 || s == 6 || s == 8 || s == 10 || s == 12) {
-            if (spw) *spw = s;
-            return nw;
-        }
-    }
-    return 0;
-}
-
-// Launch shape at batch B -- tiles per workgroup (TN), batch blocks per workgroup (NBLK) and workgroups per tile group
-// (bgroups).  A scheduling choice only: every output element is computed by the same instruction sequence for any shape.
-// Small batches (one block): one tile per workgroup, as many workgroups as tiles (latency).  Large batches: two blocks
-// per workgroup and, for the wide matrices, 2 or 4 tiles per workgroup so that the grid stays near one round of the chip
-// and an activation fragment is fetched once per TN products.
-// L2 warm-up of the NEXT launch's weight matrix by extra workgroups of the current one: a latency lever for a decode
-// group of one batch block (the next GEMV finds its weights in L2: ~1 us off a 4-5 us launch).  Larger groups are
-// throughput-bound and run beside other groups; there the extra workgroups only take slots and bandwidth (measured,
-// 3 groups of 56 chunks: 1978 -> 2007 audio-s/s without).  (g_wm_tuning: probes only, see wm_internal.h.)
-static bool pf_enabled(int B) { return B <= g_wm_tuning.prefetch_max_b; }
-
-static void pick_shape(int epi, bool ln, int spw, int nw, int B, int n_tiles, int n_cus, int *tn, int *nblk) {
-    const int env_tn = g_wm_tuning.gemv_tn, env_nb = g_wm_tuning.gemv_nblk;   // 0 in the product
-    const int blocks = (B + 15) / 16;
-    *tn = 1;
-    *nblk = 1;
-    // one block, a 16-wave K split (K = 4d at d >= 768: the multi-unit kernels are built for <= 8 waves -- launch bounds
-    // 512, register budget) or more than 8 k-steps per wave (K = 4d at d = 576 / 640: spw 12 / 10 on <= 8 waves -- the
-    // two-block kernel holds 2 x SPW activation fragments and exists for SPW <= 8 only): one unit per workgroup, more
-    // workgroups along the batch
-    if (blocks < 2 && de_is_logits(epi) && ln && spw <= 6) {
-        // the vocabulary product of a one-block group: 4 tiles per workgroup (810 workgroups instead of 3 242 two-wave
-        // ones; -1.4 % per position at tiny.en / base / small, neutral at large-v2: profiles/r04_latency_probe.txt)
-        *tn = (g_wm_tuning.logits_tn == 1 || g_wm_tuning.logits_tn == 2) ? g_wm_tuning.logits_tn : 4;
-        return;
-    }
-    if (blocks < 2 || nw > 8 || spw > 8) return;
-    *nblk = env_nb == 1 ? 1 : 2;
-    const bool wide = ln && (de_is_qkv(epi) || epi == DE_GELU || de_is_logits(epi)) && *nblk == 2 && spw <= 6;
-    if (!wide) return;
-    // Tile-group width by RESIDENCY ROUNDS: an 8-wave workgroup of the (1, 2) shape needs <= 128 VGPRs and sits two per
-    // CU, the wide shapes (136-190 VGPRs) one per CU; a grid that needs a second round of the chip costs a whole kernel
-    // time (measured: fc1 at 56 rows as 320 one-per-CU workgroups = two rounds), so: fewest rounds first, then the
-    // narrowest group that still leaves >= 192 workgroups, else the widest.  (Groups of THREE tiles -- fc1 of d = 1280 at
-    // 49 .. 64 rows as 214 workgroups of 162 VGPRs instead of 160 of 186 -- were built in round 5 and cost the three-lane
-    // run 2 %: 2078 vs 2114-2125 audio-s/s, NOTEBOOK round 5.)
-    const int g = (blocks + 1) / 2;
-    int best = 1, best_rounds = 1 << 30, best_wgs = 0;
-    for (int t = 1; t <= 4; t *= 2) {
-        const int wgs = ((n_tiles + t - 1) / t) * g;
-        const int cap = n_cus * (t == 1 ? 2 : 1);   // n_cus: 256, or the CUs of a sub-chip lane (wm_ctx::n_cus)
-        const int rounds = (wgs + cap - 1) / cap;
-        const int fill = n_cus * 3 / 4;              // "still fills the chip": 192 of 256
-        const bool better = rounds < best_rounds || (rounds == best_rounds && best_wgs >= fill && wgs >= fill);
-        if (better) { best = t; best_rounds = rounds; best_wgs = wgs; }
-    }
-    if (env_tn == 1 || env_tn == 2 || env_tn == 4) best = env_tn;
-    *tn = best;
-}
-
 int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
-    WM_REQUIRE(a.B >= 1 && a.B <= WM_DEC_MAXB, WM_ERR_INVALID, "dec_gemv: B=%d out of range", a.B);
-    WM_REQUIRE(a.K % 32 == 0, WM_ERR_INVALID, "dec_gemv: K=%d must be a multiple of 32", a.K);
-    int spw = 0;
-    const int nw = wm_dec_gemv_split(a.K, &spw);
-    WM_REQUIRE(nw >= 1, WM_ERR_INVALID, "dec_gemv: K=%d cannot be split over the waves of a workgroup", a.K);
     const bool ln = a.c1 != nullptr;
-    WM_REQUIRE(!ln || (a.stats_in && a.K % 64 == 0 && a.K / 16 <= 80), WM_ERR_INVALID,
+    WM_REQUIRE(!ln || a.stats_in, WM_ERR_INVALID,
                "dec_gemv: LayerNorm mode needs the producer's K/16 partial statistics (K a multiple of 64, <= 1280)");
     WM_REQUIRE(a.a != nullptr && a.W != nullptr, WM_ERR_INVALID, "dec_gemv: null operand");
+    WM_REQUIRE(a.epi != DE_QKV_P || (a.panel >= 1 && a.panel <= WM_MAX_TEACHER_PANEL && a.pos_ptr), WM_ERR_INVALID,
+               "dec_gemv: DE_QKV_P needs a panel width of 1 .. %d and the device position", WM_MAX_TEACHER_PANEL);
+    WM_REQUIRE(!de_is_x(a.epi) || (a.x.par && a.pos_ptr), WM_ERR_INVALID, "dec_gemv: DE_LOGITS_X needs its state and the device position");
+    WM_REQUIRE(a.epi != DE_LOGITS_XR || (a.rep.par && a.rep.seen && a.rep.ban && (long)a.rep.words * 32 >= a.N), WM_ERR_INVALID,
+               "dec_gemv: DE_LOGITS_XR needs the repetition-rule state");
+    const GemvEpi *e = nullptr;
+    for (const GemvEpi &c : kGemvEpi)
+        if (c.epi == a.epi && c.ln == ln) e = &c;
+    WM_REQUIRE(e, WM_ERR_INVALID, "dec_gemv: unsupported (epilogue %d, LayerNorm %d) pair", a.epi, (int)ln);
+    DecGemvShape sh;
+    sh.epi = a.epi; sh.ln = ln; sh.B = a.B; sh.N = a.N; sh.K = a.K;
+    sh.has_pf = a.pf_ptr != nullptr; sh.pf_rows = a.pf_rows; sh.pf_k = a.pf_k; sh.pf_head_major = a.pf_head_major;
+    DecGemvPlan pl;
+    WM_TRY(wm_plan_gemv(sh, ctx->n_cus, g_wm_tuning, &pl));
     DecGemvDev p;
     memset(&p, 0, sizeof(p));
     p.B = a.B; p.N = a.N; p.K = a.K;
@@ -2021,87 +1969,13 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
     p.x = a.x;
     p.rep = a.rep;
     p.panel = a.panel;
-    WM_REQUIRE(a.epi != DE_QKV_P || (a.panel >= 1 && a.panel <= WM_MAX_TEACHER_PANEL && a.pos_ptr), WM_ERR_INVALID,
-               "dec_gemv: DE_QKV_P needs a panel width of 1 .. %d and the device position", WM_MAX_TEACHER_PANEL);
-    WM_REQUIRE(!de_is_x(a.epi) || (a.x.par && a.pos_ptr), WM_ERR_INVALID, "dec_gemv: DE_LOGITS_X needs its state and the device position");
-    WM_REQUIRE(a.epi != DE_LOGITS_XR || (a.rep.par && a.rep.seen && a.rep.ban && (long)a.rep.words * 32 >= a.N), WM_ERR_INVALID,
-               "dec_gemv: DE_LOGITS_XR needs the repetition-rule state");
-    p.n_tiles = (a.N + 15) / 16;
-    int tn = 1, nblk = 1;
-    pick_shape(a.epi, ln, spw, nw, a.B, p.n_tiles, ctx->n_cus, &tn, &nblk);
-    p.bgroups = ((a.B + 15) / 16 + nblk - 1) / nblk;
-    // the 16-part K = 4d residual product at more than one batch block: two parts per wave, 8-wave workgroups (two per
-    // CU).  pick_shape keeps every 16-wave split at one (tile, block) unit per workgroup, which is what the two-part
-    // kernel is built for (d = 768 / 1024 / 1280: spw = 6 / 8 / 10).
-    const bool no_ppw = g_wm_tuning.gemv_no_ppw2 != 0;
-    const int ppw = (!no_ppw && !ln && a.epi == DE_RESID && nw == 16 && a.B > 16 && spw >= 6 && spw <= 10 && tn == 1 &&
-                     nblk == 1) ? 2 : 1;
-    if (ppw == 2) {
-        // ... and TWO batch blocks per workgroup (a weight fragment feeds two products; 144 VGPRs at spw 10: one workgroup per
-        // CU) when the one-block grid would not fit one workgroup per CU but the two-block grid does: 1.25 workgroups per CU
-        // run at the pace of the CUs that hold two.  Measured alone, d = 1280: 53 .. 96 rows 12.2 -> 9.9 us, 128 rows (640
-        // two-per-CU vs 320 one-per-CU workgroups) 15.5 vs 16.7: the rule; d = 768 / 1024 at 96 / 128 rows: 5.9 -> 5.8 / 8.7 -> 8.1
-        // (profiles/r05_fc2_two_blocks.txt).  Same parts, same order of the sums: same bits.
-        const int blocks = (a.B + 15) / 16;
-        const int knob = g_wm_tuning.gemv_ppw2_nblk;   // probes: 1 / 2 force the shape
-        const bool two = knob ? knob == 2 : (p.n_tiles * blocks > ctx->n_cus && p.n_tiles * ((blocks + 1) / 2) <= ctx->n_cus);
-        if (two) {
-            nblk = 2;
-            p.bgroups = (blocks + 1) / 2;
-        }
-    }
-    p.n_tg = (p.n_tiles + tn - 1) / tn;
-    p.n_tg_pad = p.bgroups > 1 ? (p.n_tg + 7) / 8 * 8 : p.n_tg;  // (tile group, batch group) decode needs rows of 8
-    int grid = p.n_tg_pad * p.bgroups;
-    if (pf_enabled(a.B) && a.pf_ptr && a.pf_rows >= 16 && grid % 8 == 0) {
+    p.n_tiles = pl.n_tiles; p.bgroups = pl.bgroups; p.n_tg = pl.n_tg; p.n_tg_pad = pl.n_tg_pad;
+    if (pl.pf_tiles) {   // (no warm-up: the pointer stays null)
         p.pf_ptr = (const char *)a.pf_ptr;
-        p.pf_tile_bytes = 16L * a.pf_k * 2;
-        p.pf_tiles = a.pf_rows / 16;
-        p.pf_head_major = a.pf_head_major;   // = pairs per XCD of the fused consumer (0: plain placement, tile t on XCD t % 8)
-        // head-major: 8 XCDs x 4 tiles x the heads an XCD can host (a range of `per` pairs touches <= per / B + 2 heads)
-        grid += a.pf_head_major ? 32 * (a.pf_head_major / a.B + 2) : p.pf_tiles;
+        p.pf_tile_bytes = pl.pf_tile_bytes; p.pf_tiles = pl.pf_tiles; p.pf_head_major = pl.pf_head_major;
     }
-    switch (a.epi * 2 + (ln ? 1 : 0)) {
-        case DE_QKV * 2 + 1: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_ln_qkv", ctx->stream);
-            return launch_gemv<DE_QKV, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_QKV_P * 2 + 1: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_ln_qkv", ctx->stream);
-            return launch_gemv<DE_QKV_P, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_Q * 2 + 1: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_ln_q", ctx->stream);
-            return launch_gemv<DE_Q, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_GELU * 2 + 1: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_ln_fc1", ctx->stream);
-            return launch_gemv<DE_GELU, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_LOGITS * 2 + 1: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_ln_logits", ctx->stream);
-            return launch_gemv<DE_LOGITS, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_LOGITS_X * 2 + 1: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_ln_logits_x", ctx->stream);
-            return launch_gemv<DE_LOGITS_X, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_LOGITS_XR * 2 + 1: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_ln_logits_xr", ctx->stream);
-            return launch_gemv<DE_LOGITS_XR, true>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_RESID * 2: {
-            WmProfScope ps(&ctx->prof, a.K > a.N ? "dec_gemv_fc2" : "dec_gemv_attn_out", ctx->stream);
-            return launch_gemv<DE_RESID, false>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        case DE_Q * 2: {
-            WmProfScope ps(&ctx->prof, "dec_gemv_plain", ctx->stream);
-            return launch_gemv<DE_Q, false>(ctx, p, spw, tn, nblk, nw, grid, ppw);
-        }
-        default:
-            wm_set_error("dec_gemv: unsupported (epilogue %d, LayerNorm %d) pair", a.epi, (int)ln);
-            return WM_ERR_INVALID;
-    }
+    WmProfScope ps(&ctx->prof, e->label_k && a.K > a.N ? e->label_k : e->label, ctx->stream);
+    return e->launch(ctx, p, pl);
 }
 
 int wm_ln_fold(wm_ctx *ctx, const bf16_t *W, const float *g, const float *beta, const float *bias, int N, int K,
@@ -2120,8 +1994,6 @@ int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const b
     return WM_OK;
 }
 
-// Workgroups per (sequence, head) pair of the cross-attention: 1 when the pairs alone fill the chip, else the stream
-// set of a pair is dealt to 2, 4 or 8 workgroups.  A launch-shape choice: the arithmetic does not depend on it.
 int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, const bf16_t *emb,
                        const float *pemb, int d, int n_ctx, float *x, bf16_t *xb, float *stats_out, float *mean_buf) {
     WM_REQUIRE(w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && C * w <= WM_DEC_MAXB && seq_stride >= C, WM_ERR_INVALID,
@@ -2139,282 +2011,143 @@ int wm_dec_pos_add(wm_ctx *ctx, int *pos_ptr, int add) {
     return WM_OK;
 }
 
-int wm_dec_attn_splits(int B, int H) {
-    const int bh = B * H;
-    // few pairs: the (pair, stream) units are dealt flat over the chip and merged by a combine launch.  (Measured at
-    // B = 8 x 20 heads = 160 pairs: flat 11.5 + combine 3.0 us vs 12.2 us for one 8-wave workgroup per pair -- the kernel
-    // is bound by bytes in flight per CU, not by idle CUs -- so the split starts below 96 pairs only.)
-    const int thr = g_wm_tuning.xattn_split_below;   // 96
-    if (bh >= thr) return 1;
-    int ns = 2;
-    while (ns < 8 && bh * ns < 192) ns *= 2;
-    return ns;
-}
+// The launch-shape rules are the pure functions of dec_launch.cpp; these two read the process's tuning state for them.
+int wm_dec_attn_splits(int B, int H) { return wm_dec_attn_splits(B, H, g_wm_tuning); }
+bool wm_dec_xattn_fq_applies(int B, int H, int K, bool short_lived) { return wm_dec_xattn_fq_applies(B, H, K, short_lived, g_wm_tuning); }
 
-int wm_dec_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int B, int H,
-                     int T_stride, int n_keys, const int *pos_ptr, int nsplit, float *part, bf16_t *att,
-                     bool cross, const bf16_t *pf_ptr, int pf_rows, int pf_k, const int *live_rows, const int *n_live,
-                     bool short_lived) {
-    WM_REQUIRE(nsplit == 1 || nsplit == 2 || nsplit == 4 || nsplit == 8, WM_ERR_INVALID,
-               "dec_attention: nsplit %d is not 1, 2, 4 or 8", nsplit);
-    WM_REQUIRE(T_stride <= ATT_MAXK && n_keys <= ATT_MAXK, WM_ERR_INVALID,
-               "dec_attention: more than %d keys", ATT_MAXK);
-    WM_REQUIRE(nsplit == 1 || part != nullptr, WM_ERR_INVALID, "dec_attention: split launch without a partials buffer");
-    WM_REQUIRE(H >= 1 && H <= 255 && B * H < 65536, WM_ERR_INVALID, "dec_attention: %d heads x %d rows do not fit the packed arguments", H, B);
-    WM_REQUIRE((!live_rows && !n_live) || n_live == live_rows + WM_DEC_MAXB, WM_ERR_INVALID, "dec_attention: the live count must follow the live rows");
+namespace {
+// the integers of the arguments, for the plan functions
+DecAttnShape attn_shape(const DecAttnArgs &t) {
+    DecAttnShape s;
+    memset(&s, 0, sizeof(s));
+    s.B = t.B; s.C = t.C; s.N = t.N; s.H = t.H; s.T_stride = t.T_stride; s.n_keys = t.n_keys; s.nsplit = t.nsplit;
+    s.has_pos = t.pos_ptr != nullptr; s.has_part = t.part != nullptr; s.has_off = t.off != nullptr; s.short_lived = t.short_lived;
+    s.has_pf = t.pf.ptr != nullptr; s.pf_rows = t.pf.rows; s.pf_k = t.pf.k;
+    return s;
+}
+int launch_combine(wm_ctx *ctx, const DecAttnArgs &t, const DecAttnPlan &pl);   // (defined behind its first caller: keeps the kernels' order in the code object)
+}  // namespace
+
+// The cross-attention.  (The debug hooks also run it over a self-shaped cache.)
+int wm_dec_attention(wm_ctx *ctx, const DecAttnArgs &t) {
+    DecAttnPlan pl;
+    WM_TRY(wm_plan_attention(attn_shape(t), ctx->n_cus, g_wm_tuning, &pl));
     {
-        WmProfScope ps(&ctx->prof, cross ? "dec_attn_cross" : "dec_attn_self", ctx->stream);
-        // 8 streams x 4 loads = 126 VGPRs: an 8-wave GEMV workgroup of another decode group fits beside one of these on a
-        // CU (a second cross-attention workgroup does not: LDS reservation below); at most 256 workgroups -- one per CU --
-        // walk the pairs, balanced (56 chunks x 20 heads = 224 workgroups x 5 pairs).  Measured alone at B = 8 / 56 / 128:
-        // 12.8 / 67 / 144 us (4.8 / 6.4 / 6.8 TB/s: ~6.4 is what HBM reads deliver).
-        // short_lived (the chip is shared with other decode groups): one workgroup per pair, see WmModel::xattn_shared
-        // (a sub-chip lane: one persistent workgroup per CU of ITS part of the chip)
-        const int cap_cus = g_wm_tuning.xattn_wgs > 0 && g_wm_tuning.xattn_wgs < ctx->n_cus ? g_wm_tuning.xattn_wgs : ctx->n_cus;
-        const int cap = short_lived ? (1 << 30) : cap_cus;
-        int n_wg = B * H;
-        if (n_wg > cap) {
-            const int rounds = (n_wg + cap - 1) / cap;
-            n_wg = (n_wg + rounds - 1) / rounds;  // balanced: every workgroup walks `rounds` (or rounds - 1) pairs
-        }
-        int gx = n_wg;
-        long tile_bytes = 0;
-        if (pf_enabled(B) && pf_ptr && nsplit == 1 && gx % 8 == 0 && pf_rows >= 16) {
-            tile_bytes = 16L * pf_k * 2;
-            gx += pf_rows / 16;
-        }
-        const bool no_flat = g_wm_tuning.xattn_no_flat != 0;
-        if (nsplit > 1 && !no_flat) {
-            // few pairs: deal the (pair, stream) units evenly over ~256 workgroups (see the kernel)
-            const int units = B * H * 8;
-            int wpw = (units + 255) / 256;
-            wpw = wpw < 1 ? 1 : (wpw > 4 ? 4 : wpw);   // < 96 pairs = < 768 units: <= 3 (the DEEP kernel is built for <= 4 waves)
-            const int g = (units + wpw - 1) / wpw;
-            // (DEEP: every block of a stream requested up front -- the flat deal is the latency regime by construction)
-            const AttnCold cold = {att, part, nullptr, 0};
-            const unsigned pA = (unsigned)H | (8u << 8) | ((unsigned)wpw << 16), pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
-            const unsigned pC = (unsigned)(B * H) | ((unsigned)g << 16);
-            WM_REQUIRE(g < 65536, WM_ERR_INVALID, "dec_attention: flat grid too large");
-            if (g_wm_tuning.xattn_no_deep)
-                dec_xrows_attn_kernel<8, 4, WM_XATTN_NT><<<g, wpw * 64, 0, ctx->stream>>>(
-                    q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
-            // a cache of <= 3.2 MB per layer (tiny.en / base, single chunk) stays in the L2s from one position to the next
-            // when it is read with cacheable loads: -1 .. -2 % per position there; +5 % at `small` (4.6 MB): the rule
-            else if ((size_t)B * H * T_stride * 64 * 2 * 2 <= (size_t)3200 * 1024)
-                dec_rows_attn_kernel<8, 4, false, true><<<g, wpw * 64, 0, ctx->stream>>>(
-                    q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
-            else
-                dec_rows_attn_kernel<8, 4, WM_XATTN_NT, true><<<g, wpw * 64, 0, ctx->stream>>>(
-                    q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
-        } else {
-            dim3 grid(gx, nsplit);
-            // ONE cross-attention workgroup per CU, chip-wide: a workgroup reserves more than half of the CU's 160 KB of
-            // LDS (it uses 2 KB), so the cross-attention launches of the decode groups in flight take the CUs one after
-            // the other instead of side by side.  A single launch already saturates the HBM (6.4 TB/s alone); a second
-            // one beside it adds no bandwidth but fills the SIMDs' wave slots / VGPRs for the whole launch (persistent
-            // workgroups), and the other groups' GEMVs -- which fit beside ONE such workgroup, LDS included (<= 66 KB) --
-            // wait.  Measured, 3 groups in flight: 1920 -> 1966 audio-s/s (20 steps), 2014 -> 2118 (72 steps, decode stage
-            // 0.74 -> 0.79 of the HBM peak).
-            const int lds_pad = g_wm_tuning.xattn_lds_pad;   // 84 KB
+        WmProfScope ps(&ctx->prof, "dec_attn_cross", ctx->stream);
+        const dim3 grid(pl.grid_x, pl.grid_y);
+        if (pl.variant == DAV_STREAM) {
+            // the LDS reservation that keeps the launch at ONE workgroup per CU (wm_plan_attention) must be allowed first
+            const int lds_pad = g_wm_tuning.xattn_lds_pad;
             static std::atomic<int> pad_set[64];  // per device (wm_multi: one process, every GPU of the node): the size allowed so far
             if (lds_pad > pad_set[ctx->device & 63].load(std::memory_order_acquire)) {
                 WM_HIP(hipFuncSetAttribute((const void *)dec_xrows_attn_kernel<8, 4, WM_XATTN_NT>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_pad));
                 pad_set[ctx->device & 63].store(lds_pad, std::memory_order_release);
             }
-            const AttnCold cold = {att, part, (const char *)pf_ptr, tile_bytes};
-            const unsigned pA = (unsigned)H | ((unsigned)nsplit << 8), pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
-            const unsigned pC = (unsigned)(B * H) | ((unsigned)n_wg << 16);
-            dec_xrows_attn_kernel<8, 4, WM_XATTN_NT><<<grid, (8 / nsplit) * 64, nsplit == 1 ? lds_pad : 0, ctx->stream>>>(
-                q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
+            const AttnCold cold = {t.att, t.part, (const char *)t.pf.ptr, pl.tile_bytes};
+            dec_xrows_attn_kernel<8, 4, WM_XATTN_NT><<<grid, pl.block, pl.lds, ctx->stream>>>(
+                t.q, t.kc, t.vc, t.pos_ptr, t.live, pl.w.a, pl.w.b, pl.w.c, cold);
+        } else {
+            const AttnCold cold = {t.att, t.part, nullptr, 0};
+            if (pl.variant == DAV_FLAT)
+                dec_xrows_attn_kernel<8, 4, WM_XATTN_NT><<<grid, pl.block, 0, ctx->stream>>>(
+                    t.q, t.kc, t.vc, t.pos_ptr, t.live, pl.w.a, pl.w.b, pl.w.c, cold);
+            else if (pl.variant == DAV_FLAT_DEEP_C)
+                dec_rows_attn_kernel<8, 4, false, true><<<grid, pl.block, 0, ctx->stream>>>(
+                    t.q, t.kc, t.vc, t.pos_ptr, t.live, pl.w.a, pl.w.b, pl.w.c, cold);
+            else
+                dec_rows_attn_kernel<8, 4, WM_XATTN_NT, true><<<grid, pl.block, 0, ctx->stream>>>(
+                    t.q, t.kc, t.vc, t.pos_ptr, t.live, pl.w.a, pl.w.b, pl.w.c, cold);
         }
         WM_HIP(hipGetLastError());
     }
-    if (nsplit > 1) {
-        WmProfScope ps(&ctx->prof, "dec_attn_combine", ctx->stream);
-        dec_attn_combine_kernel<8><<<B * H, 64, 0, ctx->stream>>>(part, H, H * 64, att);
-        WM_HIP(hipGetLastError());
-    }
-    return WM_OK;
+    return pl.combine_grid ? launch_combine(ctx, t, pl) : WM_OK;
 }
 
-// Cross-attention of a candidate group (dec_xcand_attn_kernel): C windows x N candidates, q / att rows c * N + s, K/V
-// [C][H][T_stride][64].  part: [C * N][H][8][66] floats, needed below 256 (window, head) pairs (the flat deal).
 namespace {
-template <int N>
-int launch_xcand(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int H, int T_stride, int n_keys,
-                 float *part, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k, const int *live_rows, bool short_lived,
-                 bool *flat) {
-    const int pairs = C * H;
-    *flat = pairs < 256 && !short_lived;
-    const unsigned pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
-    long tile_bytes = 0;
-    int warm = 0;
-    if (pf_enabled(C * N) && pf_ptr && pf_rows >= 16) {
-        tile_bytes = 16L * pf_k * 2;
-        warm = pf_rows / 16;
-    }
-    if (*flat) {
-        // few pairs (8 windows x 20 heads = 160): every CU streams an equal share of the (pair, stream) units
-        const int units = pairs * 8;
-        int wpw = (units + 255) / 256;
-        wpw = wpw < 1 ? 1 : (wpw > 8 ? 8 : wpw);
-        const int g = (units + wpw - 1) / wpw;
-        if (g % 8 != 0) warm = 0;   // (the warm-up tiles follow the compute workgroups: keep their XCD placement)
-        const unsigned pA = (unsigned)H | ((unsigned)wpw << 16), pC = (unsigned)C | ((unsigned)g << 16);
-        dec_xcand_attn_kernel<N, WM_XATTN_NT><<<g + warm, wpw * 64, 0, ctx->stream>>>(
-            q, kc, vc, live_rows, att, part, pA, pB, pC, warm ? (const char *)pf_ptr : nullptr, warm ? tile_bytes : 0);
-        WM_HIP(hipGetLastError());
-        return WM_OK;   // (the caller launches the combine)
-    }
-    // one 8-wave workgroup per pair, at most one per CU (persistent, balanced), or one per pair when the chip is shared
-    const int cap_cus = g_wm_tuning.xattn_wgs > 0 && g_wm_tuning.xattn_wgs < ctx->n_cus ? g_wm_tuning.xattn_wgs : ctx->n_cus;
-    const int cap = short_lived ? (1 << 30) : cap_cus;
-    int n_wg = pairs;
-    if (n_wg > cap) {
-        const int rounds = (n_wg + cap - 1) / cap;
-        n_wg = (n_wg + rounds - 1) / rounds;
-    }
-    if (n_wg % 8 != 0) warm = 0;
-    WM_REQUIRE(n_wg < 65536, WM_ERR_INVALID, "dec_attention_cand: grid too large");
-    const unsigned pA = (unsigned)H, pC = (unsigned)C | ((unsigned)n_wg << 16);
-    dec_xcand_attn_kernel<N, WM_XATTN_NT><<<n_wg + warm, 512, 0, ctx->stream>>>(
-        q, kc, vc, live_rows, att, part, pA, pB, pC, warm ? (const char *)pf_ptr : nullptr, warm ? tile_bytes : 0);
+int launch_combine(wm_ctx *ctx, const DecAttnArgs &t, const DecAttnPlan &pl) {
+    WmProfScope ps(&ctx->prof, "dec_attn_combine", ctx->stream);
+    dec_attn_combine_kernel<8><<<pl.combine_grid, 64, 0, ctx->stream>>>(t.part, t.H, t.H * 64, t.att);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
 }  // namespace
 
-int wm_dec_attention_cand(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int N, int H, int T_stride,
-                          int n_keys, float *part, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k,
-                          const int *live_rows, const int *n_live, bool short_lived) {
-    WM_REQUIRE(N >= 1 && N <= WM_MAX_BEST_OF && C >= 1 && C * N <= WM_DEC_MAXB, WM_ERR_INVALID,
-               "dec_attention_cand: %d windows x %d candidates outside 1 .. %d rows of 1 .. %d candidates", C, N, WM_DEC_MAXB,
-               WM_MAX_BEST_OF);
-    WM_REQUIRE(T_stride >= 1 && T_stride <= ATT_MAXK && n_keys >= 1 && n_keys <= T_stride, WM_ERR_INVALID,
-               "dec_attention_cand: 1 .. %d keys", ATT_MAXK);
-    WM_REQUIRE(H >= 1 && H <= 255, WM_ERR_INVALID, "dec_attention_cand: %d heads do not fit the packed arguments", H);
-    WM_REQUIRE((!live_rows && !n_live) || n_live == live_rows + WM_DEC_MAXB, WM_ERR_INVALID,
-               "dec_attention_cand: the live count must follow the live rows");
-    WM_REQUIRE(part || C * H >= 256 || short_lived, WM_ERR_INVALID, "dec_attention_cand: flat launch without a partials buffer");
-    bool flat = false;
+// Cross-attention of a candidate group (dec_xcand_attn_kernel): C windows x N candidates, q / att rows c * N + s, K/V
+// [C][H][T_stride][64].  part: [C * N][H][8][66] floats, needed below 256 (window, head) pairs (the flat deal).
+int wm_dec_attention_cand(wm_ctx *ctx, const DecAttnArgs &t) {
+    DecAttnPlan pl;
+    WM_TRY(wm_plan_attention_cand(attn_shape(t), ctx->n_cus, g_wm_tuning, &pl));
     {
         WmProfScope ps(&ctx->prof, "dec_attn_cross_cand", ctx->stream);
-        int rc = WM_ERR_INVALID;
-        switch (N) {
-#define WM_XCAND_CASE(n)                                                                                                   \
-    case n:                                                                                                                \
-        rc = launch_xcand<n>(ctx, q, kc, vc, C, H, T_stride, n_keys, part, att, pf_ptr, pf_rows, pf_k, live_rows, short_lived, \
-                             &flat);                                                                                       \
+        const char *pf = pl.warm_tiles ? (const char *)t.pf.ptr : nullptr;
+        switch (t.N) {
+#define WM_XCAND_CASE(n)                                                                                              \
+    case n:                                                                                                           \
+        dec_xcand_attn_kernel<n, WM_XATTN_NT><<<pl.grid_x, pl.block, 0, ctx->stream>>>(                               \
+            t.q, t.kc, t.vc, t.live, t.att, t.part, pl.w.a, pl.w.b, pl.w.c, pf, pl.warm_tiles ? pl.tile_bytes : 0);   \
         break
             WM_XCAND_CASE(1); WM_XCAND_CASE(2); WM_XCAND_CASE(3); WM_XCAND_CASE(4);
             WM_XCAND_CASE(5); WM_XCAND_CASE(6); WM_XCAND_CASE(7); WM_XCAND_CASE(8);
 #undef WM_XCAND_CASE
         }
-        WM_TRY(rc);
-    }
-    if (flat) {
-        WmProfScope ps(&ctx->prof, "dec_attn_combine", ctx->stream);
-        dec_attn_combine_kernel<8><<<C * N * H, 64, 0, ctx->stream>>>(part, H, H * 64, att);
         WM_HIP(hipGetLastError());
     }
-    return WM_OK;
+    return pl.combine_grid ? launch_combine(ctx, t, pl) : WM_OK;
 }
 
-// Fused cross_attn_ln + query projection + cross-attention (dec_xattn_fq_kernel): the latency shape of 96 .. 256 pairs.
-// Returns WM_OK and *used = true when the shape was launched; *used = false: not applicable, the caller runs the two
-// separate launches (same results either way).
-bool wm_dec_xattn_fq_applies(int B, int H, int K, bool short_lived) {
-    if (!g_wm_tuning.xattn_fuse_q || short_lived) return false;
-    const int pairs = B * H;
-    if (pairs < g_wm_tuning.xattn_split_below || pairs > 256 || K != H * 64) return false;
-    int spw = 0;
-    const int nw = wm_dec_gemv_split(K, &spw);
-    return nw >= 1 && nw <= 8 && (spw == 2 || spw == 4 || spw == 5 || spw == 6);
-}
-
-int wm_dec_xattn_fq(wm_ctx *ctx, const DecGemvArgs &qa, const bf16_t *kc, const bf16_t *vc, int B, int H, int T_stride,
-                    int n_keys, bf16_t *att, const int *live_rows, const int *n_live, const bf16_t *pf_ptr, int pf_rows, int pf_k) {
-    WM_REQUIRE(qa.c1 && qa.stats_in && qa.N == qa.K && qa.K == H * 64, WM_ERR_INVALID, "xattn_fq: not a LayerNorm-folded d x d query projection");
-    WM_REQUIRE(H >= 1 && H <= 255 && B >= 1 && B <= WM_DEC_MAXB && T_stride <= ATT_MAXK && n_keys >= 1 && n_keys <= ATT_MAXK,
-               WM_ERR_INVALID, "xattn_fq: bad geometry");
-    WM_REQUIRE((!live_rows && !n_live) || n_live == live_rows + WM_DEC_MAXB, WM_ERR_INVALID, "xattn_fq: the live count must follow the live rows");
-    int spw = 0;
-    const int nw = wm_dec_gemv_split(qa.K, &spw);
-    WM_REQUIRE(nw >= 1 && nw <= 8, WM_ERR_INVALID, "xattn_fq: K split over more than 8 waves");
+// Fused cross_attn_ln + query projection + cross-attention (dec_xattn_fq_kernel): the latency shape of 96 .. 256 pairs
+// (wm_dec_xattn_fq_applies; else the caller runs the two separate launches: same results either way).
+int wm_dec_xattn_fq(wm_ctx *ctx, const DecGemvArgs &qa, const DecAttnArgs &t) {
+    WM_REQUIRE(qa.c1 && qa.stats_in && qa.N == qa.K && qa.K == t.H * 64, WM_ERR_INVALID, "xattn_fq: not a LayerNorm-folded d x d query projection");
+    DecAttnShape sh = attn_shape(t);
+    sh.K = qa.K;
+    DecAttnPlan pl;
+    WM_TRY(wm_plan_xattn_fq(sh, ctx->n_cus, g_wm_tuning, &pl));
     WmProfScope ps(&ctx->prof, "dec_attn_cross_fq", ctx->stream);
     FqCold cold;
     cold.c1 = qa.c1; cold.c2 = qa.c2; cold.stats_in = qa.stats_in; cold.mean_in = qa.mean_in; cold.mean_out = qa.mean_out;
-    cold.att = att; cold.stats_stride = 2L * qa.K; cold.K = qa.K; cold.N = qa.N;
-    const unsigned pA = (unsigned)H | ((unsigned)B << 8), pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
-    int grid = 8 * ((H * B + 7) / 8);
-    cold.n_wg = grid; cold.pf_ptr = nullptr; cold.pf_tile_bytes = 0;
-    if (pf_enabled(B) && pf_ptr && pf_rows >= 16) {
-        cold.pf_ptr = (const char *)pf_ptr;
-        cold.pf_tile_bytes = 16L * pf_k * 2;
-        grid += pf_rows / 16;
-    }
-    const size_t lds = ((size_t)nw * 1024 + 128 + 64) * sizeof(float);
+    cold.att = t.att; cold.stats_stride = 2L * qa.K; cold.K = qa.K; cold.N = qa.N;
+    cold.n_wg = pl.n_wg;
+    cold.pf_ptr = pl.warm_tiles ? (const char *)t.pf.ptr : nullptr;
+    cold.pf_tile_bytes = pl.tile_bytes;
+    const int grid = pl.grid_x;
+    const size_t lds = (size_t)pl.lds;
     hipStream_t s = ctx->stream;
-    switch (spw) {
-        case 2: dec_xattn_fq_kernel<2, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, kc, vc, live_rows, pA, pB, qa.K, cold); break;
-        case 4: dec_xattn_fq_kernel<4, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, kc, vc, live_rows, pA, pB, qa.K, cold); break;
-        case 5: dec_xattn_fq_kernel<5, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, kc, vc, live_rows, pA, pB, qa.K, cold); break;
-        case 6: dec_xattn_fq_kernel<6, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, kc, vc, live_rows, pA, pB, qa.K, cold); break;
-        default: wm_set_error("xattn_fq: unsupported k-steps per wave %d", spw); return WM_ERR_INVALID;
+    switch (pl.spw) {
+        case 2: dec_xattn_fq_kernel<2, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, t.kc, t.vc, t.live, pl.w.a, pl.w.b, qa.K, cold); break;
+        case 4: dec_xattn_fq_kernel<4, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, t.kc, t.vc, t.live, pl.w.a, pl.w.b, qa.K, cold); break;
+        case 5: dec_xattn_fq_kernel<5, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, t.kc, t.vc, t.live, pl.w.a, pl.w.b, qa.K, cold); break;
+        case 6: dec_xattn_fq_kernel<6, WM_XATTN_NT><<<grid, 512, lds, s>>>(qa.W, qa.a, t.kc, t.vc, t.live, pl.w.a, pl.w.b, qa.K, cold); break;
+        default: wm_set_error("xattn_fq: unsupported k-steps per wave %d", pl.spw); return WM_ERR_INVALID;
     }
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
 
-int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int B, int H, int T_stride,
-                          int n_keys, const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k,
-                          const int *live_rows, const int *n_live, const int *off) {
-    WM_REQUIRE(T_stride <= ATT_MAXK && n_keys <= ATT_MAXK && (pos_ptr || n_keys >= 1), WM_ERR_INVALID,
-               "dec_self_attention: 1..%d keys", ATT_MAXK);
-    WM_REQUIRE(H >= 1 && H <= 255 && B * H < 65536, WM_ERR_INVALID, "dec_self_attention: %d heads x %d rows do not fit the packed arguments", H, B);
-    WM_REQUIRE((!live_rows && !n_live) || n_live == live_rows + WM_DEC_MAXB, WM_ERR_INVALID, "dec_self_attention: the live count must follow the live rows");
+int wm_dec_self_attention(wm_ctx *ctx, const DecAttnArgs &t) {
+    DecAttnPlan pl;
+    WM_TRY(wm_plan_self_attention(attn_shape(t), ctx->n_cus, g_wm_tuning, &pl));
     WmProfScope ps(&ctx->prof, "dec_attn_self", ctx->stream);
-    int gx = B * H;
-    long tile_bytes = 0;
-    if (pf_enabled(B) && pf_ptr && gx % 8 == 0 && pf_rows >= 16) {
-        tile_bytes = 16L * pf_k * 2;
-        gx += pf_rows / 16;
-    }
-    // a pair is 15-57 KB of cache (<= 448 rows, ~115 on average over a 224-token decode): ONE 4-wave workgroup
-    const AttnCold cold = {att, nullptr, (const char *)pf_ptr, tile_bytes};
-    const unsigned pA = (unsigned)H | (1u << 8), pB = (unsigned)T_stride | ((unsigned)n_keys << 16);
-    const unsigned pC = (unsigned)(B * H) | ((unsigned)(B * H) << 16);
-    if (off) {   // a ragged decode group: the instantiation that places every pair at its row offset
-        const AttnColdOff cold_off = {off, att, nullptr, (const char *)pf_ptr, tile_bytes};
-        dec_rows_attn_kernel<4, 4, false, false, true><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, live_rows, pA, pB, pC,
-                                                                                    cold_off);
+    if (pl.variant == DAV_SELF_OFF) {
+        const AttnColdOff cold_off = {t.off, t.att, nullptr, (const char *)t.pf.ptr, pl.tile_bytes};
+        dec_rows_attn_kernel<4, 4, false, false, true><<<pl.grid_x, 256, 0, ctx->stream>>>(t.q, t.kc, t.vc, t.pos_ptr, t.live, pl.w.a,
+                                                                                          pl.w.b, pl.w.c, cold_off);
     } else {
-        dec_rows_attn_kernel<4, 4, false><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, live_rows, pA, pB, pC, cold);
+        const AttnCold cold = {t.att, nullptr, (const char *)t.pf.ptr, pl.tile_bytes};
+        dec_rows_attn_kernel<4, 4, false><<<pl.grid_x, 256, 0, ctx->stream>>>(t.q, t.kc, t.vc, t.pos_ptr, t.live, pl.w.a, pl.w.b, pl.w.c, cold);
     }
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
 
-int wm_dec_self_attention_panel(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int w, int H, int T_stride,
-                                const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr, int pf_rows, int pf_k) {
-    WM_REQUIRE(w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && C * w <= WM_DEC_MAXB, WM_ERR_INVALID,
-               "dec_self_attention_panel: %d windows x %d positions outside 1 .. %d rows of 1 .. %d positions", C, w, WM_DEC_MAXB,
-               WM_MAX_TEACHER_PANEL);
-    WM_REQUIRE(T_stride >= w && T_stride <= ATT_MAXK && pos_ptr, WM_ERR_INVALID, "dec_self_attention_panel: %d .. %d cache rows", w, ATT_MAXK);
-    WM_REQUIRE(H >= 1 && H <= 255, WM_ERR_INVALID, "dec_self_attention_panel: %d heads do not fit the packed arguments", H);
+int wm_dec_self_attention_panel(wm_ctx *ctx, const DecAttnArgs &t) {
+    DecAttnPlan pl;
+    WM_TRY(wm_plan_self_attention_panel(attn_shape(t), ctx->n_cus, g_wm_tuning, &pl));
     WmProfScope ps(&ctx->prof, "dec_attn_self", ctx->stream);
-    const int B = C * w;
-    int gx = B * H;
-    long tile_bytes = 0;
-    if (pf_enabled(B) && pf_ptr && gx % 8 == 0 && pf_rows >= 16) {
-        tile_bytes = 16L * pf_k * 2;
-        gx += pf_rows / 16;
-    }
-    const AttnColdPanel cold = {w, att, nullptr, (const char *)pf_ptr, tile_bytes};
-    const unsigned pA = (unsigned)H | (1u << 8), pB = (unsigned)T_stride;
-    const unsigned pC = (unsigned)(B * H) | ((unsigned)(B * H) << 16);
-    dec_rows_attn_kernel<4, 4, false, false, false, true><<<gx, 256, 0, ctx->stream>>>(q, kc, vc, pos_ptr, nullptr, pA, pB, pC, cold);
+    const AttnColdPanel cold = {t.N, t.att, nullptr, (const char *)t.pf.ptr, pl.tile_bytes};
+    dec_rows_attn_kernel<4, 4, false, false, false, true><<<pl.grid_x, 256, 0, ctx->stream>>>(t.q, t.kc, t.vc, t.pos_ptr, nullptr, pl.w.a,
+                                                                                             pl.w.b, pl.w.c, cold);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

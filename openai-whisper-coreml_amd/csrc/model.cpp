@@ -778,8 +778,7 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
     const int Gs = grp > 0 ? grp : (PW > 1 ? Bx : B);   // rows per layer of the self cache
     const int ns = wm_dec_attn_splits(B, H);
     const int xns = g_wm_tuning.xattn_splits > 0 ? g_wm_tuning.xattn_splits : ns;   // 0 in the product
-    const int *live = mode.stop ? m->dlive : nullptr, *nlive = mode.stop ? m->dnlive : nullptr;
-    const int *off = mode.off ? m->doff : nullptr;
+    const bool xshort = mode.xattn_shared && !g_wm_tuning.xattn_never_short;
     // mean-centring offsets of the bf16 residual copy: the embedding wrote buffer 0; every LayerNorm-folded GEMV reads
     // the current buffer and leaves the new means in the other one
     int cur = 0;
@@ -790,6 +789,10 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
         bf16_t *vc = m->skv + ((size_t)(l * 2 + 1) * Gs + c0) * H * T * 64;
         const bf16_t *xk = m->xkv + ((size_t)(l * 2 + 0) * Gx + c0) * H * S * 64;
         const bf16_t *xv = m->xkv + ((size_t)(l * 2 + 1) * Gx + c0) * H * S * 64;
+        // the layer's attentions: what self and cross share here, the rest at their calls
+        DecAttnArgs t = {};
+        t.q = m->dq; t.att = m->datt; t.H = H; t.live = mode.stop ? m->dlive : nullptr;
+        t.B = B; t.C = Bx; t.N = NC * PW;       // a candidate group / a panel: Bx windows x NC * PW rows
         DecGemvArgs a;
         // 1. attn_ln (folded) + fused q|k|v projection; k, v appended to the self-attention cache
         memset(&a, 0, sizeof(a));
@@ -801,18 +804,15 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
         if (PW > 1) { a.epi = DE_QKV_P; a.panel = PW; }   // row (c, s) appends at position pos + s of window c
         WM_TRY(wm_dec_gemv(ctx, a));
         // 2. causal self-attention over positions 0..pos (a panel row: 0 .. pos + s of its window)
-        if (PW > 1) {
-            WM_TRY(wm_dec_self_attention_panel(ctx, m->dq, kc, vc, Bx, PW, H, T, m->dpos, m->datt, L.wo, d, d));
-        } else {
-            WM_TRY(wm_dec_self_attention(ctx, m->dq, kc, vc, B, H, T, 0, m->dpos, m->datt, L.wo, d, d, live, nlive, off));
-        }
+        t.kc = kc; t.vc = vc; t.T_stride = T; t.n_keys = 0; t.pos_ptr = m->dpos; t.off = mode.off ? m->doff : nullptr;
+        t.pf = {L.wo, d, d};
+        WM_TRY(PW > 1 ? wm_dec_self_attention_panel(ctx, t) : wm_dec_self_attention(ctx, t));
         // 3. out-projection + residual (f32 stream, its bf16 copy, partial statistics)
         memset(&a, 0, sizeof(a));
         a.epi = DE_RESID; a.B = B; a.N = d; a.K = d; a.W = L.wo; a.c2 = L.bo;
         a.a = m->datt; a.out_f32 = m->dx; a.out_bf16 = m->dxb; a.ldo = d; a.stats_out = m->dstats;
         a.mean_in = mean_buf(cur);
         a.pf_ptr = L.wxq_f; a.pf_rows = d; a.pf_k = d;
-        const bool xshort = mode.xattn_shared && !g_wm_tuning.xattn_never_short;
         // wm_align: a layer with alignment heads leaves its f32 query in m->dq (the two launches: same bits as the fused one)
         const bool cap_l = cap && cap->layer[l].n > 0;
         const bool fuse_q = NC == 1 && PW == 1 && !cap_l && xns == 1 && wm_dec_xattn_fq_applies(B, H, d, xshort);
@@ -824,19 +824,18 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
         a.a = m->dxb; a.out_f32 = m->dq; a.ldo = d;
         a.stats_in = m->dstats;
         a.mean_in = mean_buf(cur); a.mean_out = mean_buf(cur ^ 1); cur ^= 1;
+        // the cross-attention over the 1500 cached encoder frames
+        t.kc = xk; t.vc = xv; t.T_stride = S; t.n_keys = S; t.pos_ptr = nullptr; t.off = nullptr;
+        t.part = m->dpart; t.nsplit = xns; t.short_lived = xshort; t.pf = {L.wxo, d, d};
         if (fuse_q) {
             // 4 + 5 as ONE launch (the latency shape: every pair's workgroup forms its own query, dec_kernels.hip).  Differs from
             // the two launches for FINISHED rows only (early stop): their block's means stay stale, m->dq is not written
-            WM_TRY(wm_dec_xattn_fq(ctx, a, xk, xv, B, H, S, S, m->datt, live, nlive, L.wxo, d, d));
+            WM_TRY(wm_dec_xattn_fq(ctx, a, t));
         } else {
             WM_TRY(wm_dec_gemv(ctx, a));
             if (cap_l) WM_TRY(wm_align_capture_q(ctx, m->dq, d, B, cap->layer[l], cap->q, cap->Tq, cap->J, m->dpos, PW));
-            // 5. cross-attention over the 1500 cached encoder frames (a candidate group, a panel: one K/V read per window)
-            if (NC > 1 || PW > 1) {
-                WM_TRY(wm_dec_attention_cand(ctx, m->dq, xk, xv, Bx, NC * PW, H, S, S, m->dpart, m->datt, L.wxo, d, d, live, nlive, xshort));
-            } else {
-                WM_TRY(wm_dec_attention(ctx, m->dq, xk, xv, B, H, S, S, nullptr, xns, m->dpart, m->datt, true, L.wxo, d, d, live, nlive, xshort));
-            }
+            // 5. the cross-attention (a candidate group, a panel: one K/V read per window)
+            WM_TRY(NC > 1 || PW > 1 ? wm_dec_attention_cand(ctx, t) : wm_dec_attention(ctx, t));
         }
         // 6. out-projection + residual
         memset(&a, 0, sizeof(a));

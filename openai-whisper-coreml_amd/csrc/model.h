@@ -4,6 +4,7 @@
 // = openai-whisper AudioEncoder / TextDecoder).
 #pragma once
 #include "wm_internal.h"
+#include "dec_launch.h"   // DecEpi, WM_DEC_MAXB, the launch plans
 
 // ---------------------------------------------------------------- HBM layout ----------
 // All matrix weights are bf16 [N][K] row-major (PyTorch Linear layout: K contiguous), so
@@ -517,18 +518,10 @@ int wm_enc_attention(wm_ctx *ctx, const bf16_t *qk, const bf16_t *vt, bf16_t *at
 
 // dec_kernels.hip
 static_assert(WM_MAX_TEACHER_PANEL == WM_MAX_BEST_OF, "a panel's cross-attention is dec_xcand_attn_kernel: its instantiated widths");
-constexpr int WM_DEC_MAXB = 128;  // decode group: up to eight batch blocks of 16 rows (the MFMA M dimension)
 static_assert(WM_XIDS_CAND == WM_DEC_MAXB + 16, "WmXDev::ids: the candidate words follow the padded sample ids");
 constexpr int WM_NLIVE_RING = 16;  // pinned host slots for the per-burst live-row counts (early stop)
 constexpr int WM_MAXSPLIT = 8;  // stream partials of a (sequence, head) pair of the cross-attention (small batches)
-// DE_LOGITS_X: DE_LOGITS plus the WmXDev partials (text (max, sum exp), winners' raw logits, the unfiltered partial at
-// the <|startoftranscript|> position) and Gumbel-perturbed keys when sampling -- its own instantiations, so the plain
-// greedy logits kernel does none of it
-// DE_LOGITS_XR: DE_LOGITS_X with the repetition rules (WmRepDev): the same body, the row's penalty and ban words applied to
-// the logit first -- again its own instantiations, so DE_LOGITS_X stays instruction for instruction what it was
-// DE_QKV_P: DE_QKV of a panel step (DecGemvArgs::panel = w): k / v of row r go to cache entry r / w at position *pos_ptr + r % w --
-// its own instantiations, so DE_QKV stays instruction for instruction what it was
-enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5, DE_LOGITS_XR = 6, DE_QKV_P = 7 };
+// (enum DecEpi: dec_launch.h)
 struct DecGemvArgs {
     int epi;
     int B, N, K;
@@ -568,13 +561,11 @@ struct DecGemvArgs {
 };
 int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a);
 // cross_attn_ln + query projection fused INTO the cross-attention launch (96 .. 256 pairs, alone on the device): qa = the
-// DE_Q LayerNorm-mode arguments the separate GEMV would get (out_f32 unused).  Same bits as the two launches.
+// DE_Q LayerNorm-mode arguments the separate GEMV would get (out_f32 unused), t = the cross-attention's (kc, vc, att, B, H,
+// T_stride, n_keys, live, pf).  Same bits as the two launches.
 bool wm_dec_xattn_fq_applies(int B, int H, int K, bool short_lived);
-int wm_dec_xattn_fq(wm_ctx *ctx, const DecGemvArgs &qa, const bf16_t *kc, const bf16_t *vc, int B, int H, int T_stride,
-                    int n_keys, bf16_t *att, const int *live_rows, const int *n_live, const bf16_t *pf_ptr = nullptr,
-                    int pf_rows = 0, int pf_k = 0);
-// waves per workgroup and k-steps per wave the GEMV uses for a given K (a function of K only)
-int wm_dec_gemv_split(int K, int *spw);
+struct DecAttnArgs;
+int wm_dec_xattn_fq(wm_ctx *ctx, const DecGemvArgs &qa, const DecAttnArgs &t);
 // W' = bf16(W g) (WL_TILED in, WL_TILED out), c1 = row sums of W', c2 = bias + W beta; rows N .. pad16(N) give zeros
 int wm_ln_fold(wm_ctx *ctx, const bf16_t *W, const float *g, const float *beta, const float *bias /*nullable*/, int N,
                int K, bf16_t *Wf, float *c1, float *c2);
@@ -591,27 +582,43 @@ int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *p
 // *pos_ptr += add (one thread)
 int wm_dec_pos_add(wm_ctx *ctx, int *pos_ptr, int add);
 // Single-query attention over a K/V cache [B][H][T_stride][64] -> bf16 head outputs att[B][H*64] in WL_TILED order.
-// Keys 0 .. n-1 with n = *pos_ptr + 1 when pos_ptr != null, else n_keys.
+// Keys 0 .. n-1 with n = *pos_ptr + 1 when pos_ptr != null, else n_keys.  One argument struct for every form; a form reads
+// the fields its comment names and ignores the rest (zero them: DecAttnArgs t = {}).
+struct DecWarm {           // optional L2 warm-up of the NEXT skinny GEMV's weights by extra workgroups of this launch
+    const bf16_t *ptr;     // [rows][k] bf16, WL_TILED; null: none
+    int rows, k;
+};
+struct DecAttnArgs {
+    const float *q;        // [rows][H * 64] f32 queries
+    const bf16_t *kc, *vc; // K / V cache [B (or C)][H][T_stride][64]
+    bf16_t *att;           // [rows][H * 64] bf16 head outputs, WL_TILED
+    float *part;           // [rows][H][8][66] f32 stream partials: a split cross launch, a candidate group below 256 pairs
+    int B;                 // rows = sequences (cross, fused-query, self)
+    int C, N;              // candidate group / panel: C windows x N rows per window (candidates; panel positions w), rows c * N + s
+    int H;                 // heads
+    int T_stride;          // cache rows per (sequence, head) pair
+    int n_keys;            // keys when pos_ptr is null (the cross forms: always)
+    const int *pos_ptr;    // self forms: device decode position, keys 0 .. *pos_ptr (a panel row: .. *pos_ptr + s)
+    int nsplit;            // cross: workgroups per pair, 1 / 2 / 4 / 8 (wm_dec_attn_splits)
+    const int *live;       // early stop: device [WM_DEC_MAXB] compact live rows | [1] their count; null: every row is live
+    const int *off;        // self: device [B] row offsets of a ragged decode group (keys [min(off[b], pos), pos]); null: all 0
+    DecWarm pf;            // warm-up of the next GEMV's weights
+    bool short_lived;      // cross forms: the chip is shared with other decode groups (one short-lived workgroup per pair)
+};
 int wm_dec_attn_splits(int B, int H);
-int wm_dec_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int B, int H,
-                     int T_stride, int n_keys, const int *pos_ptr, int nsplit, float *part, bf16_t *att,
-                     bool cross, const bf16_t *pf_ptr = nullptr, int pf_rows = 0, int pf_k = 0,
-                     const int *live_rows = nullptr, const int *n_live = nullptr, bool short_lived = false);
+// The cross-attention (8 streams per pair): q, kc, vc, att, part, B, H, T_stride, n_keys, nsplit, live, pf, short_lived
+int wm_dec_attention(wm_ctx *ctx, const DecAttnArgs &t);
 // Cross-attention of a candidate group: C windows x N candidates (rows c * N + s of q / att), K/V [C][H][T_stride][64], every
 // block of a window's K/V requested once for all its live candidates.  Row bits = wm_dec_attention's over a copy of the cache.
-// part: [C * N][H][8][66] floats (the flat deal below 256 pairs).
-int wm_dec_attention_cand(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int N, int H, int T_stride,
-                          int n_keys, float *part, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0, int pf_k = 0,
-                          const int *live_rows = nullptr, const int *n_live = nullptr, bool short_lived = false);
+// q, kc, vc, att, part (the flat deal below 256 pairs), C, N, H, T_stride, n_keys, live, pf, short_lived
+int wm_dec_attention_cand(wm_ctx *ctx, const DecAttnArgs &t);
 // The decoder's causal self-attention (<= 448 cached rows per pair): one 4-wave workgroup per (sequence, head).
-int wm_dec_self_attention(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int B, int H, int T_stride,
-                          int n_keys, const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0,
-                          int pf_k = 0, const int *live_rows = nullptr, const int *n_live = nullptr,
-                          const int *off = nullptr);
-// The self-attention of a panel step: B = C * w rows, the pair (r, h) reads cache entry (r / w, h) of kc / vc [C][H][T_stride][64]
+// q, kc, vc, att, B, H, T_stride, n_keys, pos_ptr, live, off, pf
+int wm_dec_self_attention(wm_ctx *ctx, const DecAttnArgs &t);
+// The self-attention of a panel step: B = C * w rows (w = N), the pair (r, h) reads cache entry (r / w, h) of kc / vc [C][H][T_stride][64]
 // with *pos_ptr + r % w + 1 keys; query and output are row r.  Row bits = wm_dec_self_attention's at that position.
-int wm_dec_self_attention_panel(wm_ctx *ctx, const float *q, const bf16_t *kc, const bf16_t *vc, int C, int w, int H, int T_stride,
-                                const int *pos_ptr, bf16_t *att, const bf16_t *pf_ptr = nullptr, int pf_rows = 0, int pf_k = 0);
+// q, kc, vc, att, C, N, H, T_stride, pos_ptr, pf
+int wm_dec_self_attention_panel(wm_ctx *ctx, const DecAttnArgs &t);
 // Close a decode step (one workgroup): reduce the per-tile packed maxima of a DE_LOGITS launch;
 // chosen token of row b -> seq[(*pos_ptr + 1) * B + b] when that position is >= n_prompt;
 // (token - arg_first) -> result[b]; embed the tokens of position *pos_ptr + 1 into x (+ LayerNorm
