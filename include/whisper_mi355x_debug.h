@@ -278,6 +278,25 @@ WM_API int wmdbg_cand_groups(int B, int N, int lanes, int explicit_lanes, int32_
  *   n_tg_pad, grid, block, dynamic LDS bytes, warm-up tiles, bytes per tile, pf_head_major, 0, 0, 0. */
 WM_API int wmdbg_dec_attn_plan(const int32_t *in, int n, int32_t *out);
 WM_API int wmdbg_dec_gemv_plan(const int32_t *in, int n, int32_t *out);
+/* The host arithmetic of a transcribe call as pure functions (host only, no context, no GPU; csrc/tx_plan.h), for n cases at
+ * once; each returns n, or -1 on bad arguments or a case it refuses.  None reads the wmdbg_set_tuning state.
+ * wmdbg_tx_plan: the lane plan.  in i32 [n][12] = B (rows of the call; a candidate call: windows), N (candidates per row), the
+ *   lane limit, explicit_lanes, prof_on, no_cu_masks, n_text_state, then the knobs lane_parts, lane_solo_cus, group_chunks, 0, 0;
+ *   out i32 [n][8] = L, parts, G, n_lanes, kind (0 the caller's context and its clones, 1 part lanes, 2 the solo lane), the
+ *   case's first entry in cut, 0, 0;  cut i32 [cut_cap]: per case b0[0 .. G) then cg[0 .. G), the cases back to back.
+ * wmdbg_group_tables: what a decode group uploads.  in i32 [n][256] = B, b0, Cg, N, prompt stride (0: one prompt for all),
+ *   ragged, n_prompt (of a uniform call), budgets given, sample ids given, extended decode on, 0 ...; [16] prompt_len [B],
+ *   [32] budgets [B], [48] sample_ids [B], [64] prompts [B][stride] (B <= 16, Cg * N <= 16, stride and n_prompt <= 12);
+ *   out i32 [n][576] = P, entries of the prompt table, of the offsets, of the budgets, of the id words, 0 ...; [16] the table
+ *   [P][Cg * N], [208] offsets, [224] budgets, [240] id words: a candidate group's [2][144], else the rows' sample ids.
+ * wmdbg_group_rows_out: the output rows of a finished group.  in i32 [n][320] = B, b0 (first row of the call; a candidate
+ *   call: window), Bg (decoder rows), N, max_new (<= 8), eot, budgets given, log-probs wanted, no-speech wanted, 0 ...;
+ *   [16] gen [max_new][Bg], [144] log-probs (f32 bits) [max_new][Bg], [272] no-speech (f32 bits) [Bg], [288] budgets [B]
+ *   (B * N <= 16);  out i32 [n][288], the caller's fill staying wherever no row is written = [0] tokens [B * N][max_new],
+ *   [128] lens [B * N], [144] log-probs (f32 bits), [272] no-speech (f32 bits) [B]. */
+WM_API int wmdbg_tx_plan(const int32_t *in, int n, int32_t *out, int32_t *cut, int cut_cap);
+WM_API int wmdbg_group_tables(const int32_t *in, int n, int32_t *out);
+WM_API int wmdbg_group_rows_out(const int32_t *in, int n, int32_t *out);
 /* The cross-attention launch of a candidate group exactly as the decode step makes it (wm_dec_attention_cand): C windows x N
  * candidates, q f32 [C * N][H * 64] (row c * N + s = candidate s of window c), k / v f32 [C][H][T][64] (rounded to bf16), the
  * first n_keys positions; live_rows: the compact ascending list of the n_live live rows (NULL: every row is live);

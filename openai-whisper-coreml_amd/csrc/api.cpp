@@ -1,7 +1,7 @@
 // api.cpp -- the C ABI of libwhisper_mi355x.so (declared in include/whisper_mi355x.h):
 // context life cycle, error reporting, the front-end entry points (boundary #1), device
 // memory helpers and the HIP-event profiler.  The model entry points (boundary #2) are in
-// model_api.cpp.
+// model_api.cpp and transcribe.cpp.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>

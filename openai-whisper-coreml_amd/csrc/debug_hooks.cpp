@@ -14,6 +14,7 @@
 #include "../../include/whisper_mi355x_debug.h"
 #include "beam.h"
 #include "model.h"
+#include "tx_plan.h"
 
 // ---------------------------------------------------------------- staging, timing and capture: what every hook below goes through
 // The only place in this file that allocates or frees device memory, creates or destroys events, streams and graphs, or begins
@@ -283,6 +284,30 @@ extern "C" int wmdbg_dec_gemv_plan(const int32_t *in, int n, int32_t *out) {
     for (int i = 0; i < n; ++i) wm_gemv_plan_flat(in + (size_t)i * WM_GEMV_PLAN_IN, g_wm_tuning, out + (size_t)i * WM_GEMV_PLAN_OUT);
     return n;
 }
+extern "C" int wmdbg_tx_plan(const int32_t *in, int n, int32_t *out, int32_t *cut, int cut_cap) {
+    if (!in || !out || !cut || n < 0 || cut_cap < 0) return -1;
+    int used = 0;
+    for (int i = 0; i < n; ++i) {
+        int32_t *o = out + (size_t)i * WM_TX_PLAN_OUT;
+        const int k = wm_tx_plan_flat(in + (size_t)i * WM_TX_PLAN_IN, o, cut + used, cut_cap - used);
+        if (k < 0) return -1;
+        o[5] = used;
+        used += k;
+    }
+    return n;
+}
+extern "C" int wmdbg_group_tables(const int32_t *in, int n, int32_t *out) {
+    if (!in || !out || n < 0) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!wm_group_tables_flat(in + (size_t)i * WM_TX_TAB_IN, WM_XIDS_CAND, out + (size_t)i * WM_TX_TAB_OUT)) return -1;
+    return n;
+}
+extern "C" int wmdbg_group_rows_out(const int32_t *in, int n, int32_t *out) {
+    if (!in || !out || n < 0) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!wm_group_rows_out_flat(in + (size_t)i * WM_TX_ROWS_IN, out + (size_t)i * WM_TX_ROWS_OUT)) return -1;
+    return n;
+}
 extern "C" int wmdbg_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg,
                                  int32_t *table_out, int32_t *off_out) {
     std::vector<int32_t> table, off;
@@ -292,7 +317,7 @@ extern "C" int wmdbg_right_align(const int32_t *prompts, int stride, const int32
     return P;
 }
 extern "C" int wmdbg_lane_parts(int B, int lanes, int explicit_lanes, int n_text_state) {
-    return wm_lane_parts(B, lanes, explicit_lanes != 0, n_text_state, 0);
+    return wm_lane_parts(B, lanes, explicit_lanes != 0, n_text_state, 0, g_wm_tuning);
 }
 extern "C" int wmdbg_cu_mask(int cu_lo, int cu_hi, uint32_t *mask8) { return wm_cu_mask(cu_lo, cu_hi, mask8); }
 

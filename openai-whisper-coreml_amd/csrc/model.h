@@ -198,7 +198,7 @@ struct WmAlignDev {
 
 // The mode of ONE decode: everything a captured position bakes into its kernel arguments that the context's weights and
 // shapes do not fix.  A default-constructed value is the plain teacher-forced step (wm_decode_logits, language
-// identification, wm_align); a transcribe call fills its groups' mode once (model_api.cpp lane_prefill) and every step,
+// identification, wm_align); a transcribe call fills its groups' mode once (transcribe.cpp lane_prefill) and every step,
 // eager or captured, is handed that value -- it is also, member by member, the key of the captured graphs (GraphSet).
 struct WmDecodeMode {
     bool mask = false;      // the suppress bitmaps apply (wm_set_suppress), the first-token one at position n_prompt - 1

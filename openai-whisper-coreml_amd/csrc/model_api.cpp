@@ -1,78 +1,24 @@
 // model_api.cpp -- boundary #2 of the C ABI (include/whisper_mi355x.h): weight loading, the
 // encoder / decoder entry points that replace the CoreML `encoder` / `decoder` classes
-// (Whisper/Whisper/Whisper.swift:17-40), the KV-cached greedy transcription asked for by
-// BASELINE.json.  (The per-kernel test hooks live in debug_hooks.cpp, which is NOT part of the product library.)
+// (Whisper/Whisper/Whisper.swift:17-40), language identification, word-level alignment and window sets.  The transcribe
+// calls live in transcribe.cpp.  (The per-kernel test hooks live in debug_hooks.cpp, which is NOT part of the product library.)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "beam.h"
+#include "call_src.h"
 #include "model.h"
-
-#define WM_MODEL(ctx)                                                               \
-    WM_TRY(wm_ctx_make_current(ctx));                                               \
-    WmModel *m = (ctx)->model;                                                      \
-    WM_REQUIRE(m != nullptr, WM_ERR_STATE, "context was created without a model (use wm_create)")
 
 static int io_stage(wm_ctx *ctx, size_t bytes, char **out) {
     WM_TRY(ctx->model->io_stage.reserve(ctx->stream, bytes));
     *out = (char *)ctx->model->io_stage.p;
     return WM_OK;
 }
-
-namespace {
-int lane_limit() {
-    static const int n = [] {
-        const char *e = getenv("WM_LANES");
-        const int v = e ? atoi(e) : 3;
-        return v < 1 ? 1 : (v > 8 ? 8 : v);
-    }();
-    return n;
-}
-
-int burst_len() {
-    static const int n = [] {
-        const char *e = getenv("WM_BURST");
-        const int v = e ? atoi(e) : 8;
-        return v < 1 ? 1 : (v > 32 ? 32 : v);
-    }();
-    return n;
-}
-
-bool graphs_off() {   // every decode step is launched eagerly
-    static const bool off = getenv("WM_NO_GRAPH") != nullptr;
-    return off;
-}
-
-// Capture what `enqueue` launches on the stream into *out (whatever it held is destroyed first) and instantiate it.  A
-// half-captured graph is of no use: on any failure *out is left empty; `what` names the graph in the error.
-template <typename F>
-int capture_graph(hipStream_t stream, WmGraph *out, const char *what, F &&enqueue) {
-    out->destroy();
-    WM_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    const int crc = enqueue();
-    const hipError_t ce = hipStreamEndCapture(stream, &out->g);
-    if (crc != WM_OK || ce != hipSuccess) {
-        if (ce != hipSuccess) out->g = nullptr;
-        out->destroy();
-        if (crc != WM_OK) return crc;
-        WM_HIP(ce);
-    }
-    if (hipGraphInstantiate(&out->e, out->g, nullptr, nullptr, 0) != hipSuccess) {
-        out->e = nullptr;
-        out->destroy();
-        wm_set_error("hipGraphInstantiate failed for %s", what);
-        return WM_ERR_HIP;
-    }
-    return WM_OK;
-}
-}  // namespace
 
 extern "C" int wm_set_tensor(wm_ctx *ctx, const char *name, const float *data, size_t n) try {
     WM_MODEL(ctx);
@@ -361,18 +307,10 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
     m->lid_host.assign(B, sot);  // Whisper.swift:34-35
     WM_HIP(hipMemcpyAsync(m->dseq, m->lid_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
     std::vector<int32_t> map;   // a set's row map, the source of an asynchronous upload: error paths must not outlive it
-    struct MapFence {
-        hipStream_t s;
-        bool on;
-        ~MapFence() { if (on) (void)hipStreamSynchronize(s); }
-    } fence{ctx->stream, set != nullptr};
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() { for (int i = 0; i < 3; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } ev_guard{ev};
+    WmStreamFence fence{ctx->stream, set != nullptr};
+    WmEvents<3> ev;
     if (set) {
-        for (auto &e : ev) WM_HIP(hipEventCreate(&e));
+        WM_TRY(ev.create());
         WM_HIP(hipEventRecord(ev[0], ctx->stream));
         WM_TRY(windows_cross_kv(ctx, set, rows, B, map));
         WM_HIP(hipEventRecord(ev[1], ctx->stream));
@@ -386,14 +324,14 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
         return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, nullptr, nullptr, 0, m->dresult, lang_first, nullptr,
                                nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, m->darrive, lang_first);  // :38
     };
-    if (graphs_off() || ctx->prof.on) {
+    if (wm_graphs_off() || ctx->prof.on) {
         WM_TRY(step());
     } else {
         WmModel::LidGraph &lg = m->lid_graph;
         const int want = probs != nullptr ? 1 : 0;
         if (!lg.graph.e || lg.B != B || lg.cap_b != m->cap_b || lg.first != lang_first || lg.last != lang_last || lg.logits != want) {
             lg.destroy();
-            WM_TRY(capture_graph(ctx->stream, &lg.graph, "the language-identification step", step));
+            WM_TRY(wm_capture_graph(ctx->stream, &lg.graph, "the language-identification step", step));
             lg.B = B; lg.cap_b = m->cap_b; lg.first = lang_first; lg.last = lang_last; lg.logits = want;
         }
         WM_HIP(hipGraphLaunch(lg.graph.e, ctx->stream));
@@ -424,9 +362,6 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
     return WM_OK;
 }
 
-// ------------------------------------------------------------------ greedy transcription
-static size_t pcm_elem(wm_dtype t) { return t == WM_I16 ? 2 : t == WM_F32 ? 4 : 8; }
-
 extern "C" int wm_set_token_budgets(wm_ctx *ctx, const int32_t *budgets, int n) try {
     WM_MODEL(ctx);
     WM_REQUIRE(n >= 0 && (n == 0 || budgets), WM_ERR_INVALID, "set_token_budgets: bad list");
@@ -435,1003 +370,6 @@ extern "C" int wm_set_token_budgets(wm_ctx *ctx, const int32_t *budgets, int n) 
     m->budget_host.assign(budgets, budgets + n);
     return WM_OK;
 } WM_API_CATCH
-
-// ---------------------------------------------------------------- greedy transcription
-// One batch's decode is a chain of ~260 dependent launches per position and is bound by launch latency, not by
-// HBM (NOTEBOOK.md section 4), so a call with more chunks than one decode group is spread over LANES: weight-sharing
-// clones of the context (wm_clone), each with its own stream, activations, KV caches and decode graphs.  The
-// single host thread drives the lanes as a small non-blocking scheduler: a lane takes the next decode group as soon as
-// it has finished its previous one, positions are enqueued in BURSTS (one hipGraph of WM_BURST consecutive positions --
-// the arg-max kernel advances the device-side position, so consecutive positions do not depend on the host), and with
-// early stop on (eot >= 0 or per-chunk token budgets) a lane stays at most two bursts ahead of the GPU and stops
-// enqueuing once the device reports that no sequence of its group is live any more.
-namespace {
-constexpr int kGroupChunks = 8;   // smallest decode group worth a lane (BASELINE.json configs[3]); up to WM_DEC_MAXB
-
-struct LaneJob {
-    enum State { IDLE, DECODING, DRAINING };
-    wm_ctx *c = nullptr;
-    int b0 = 0, Bg = 0;   // first row of the call (a candidate call: first WINDOW) and decoder rows of the group
-    int Cg = 0;           // its encoder rows: Bg, or (candidates) Bg / n_cand windows -- row c * n_cand + s is candidate s of window c
-    int P = 0;          // prompt positions of the group (a ragged call: the longest prompt among ITS rows)
-    WmDecodeMode mode;  // of the group's decode (xattn_shared: decided burst by burst), filled by lane_prefill
-    int gset = -1;      // its graph set in the lane's WmModel::graph_sets (lane_graph)
-    State state = IDLE;
-    int t = 0;          // decoder positions enqueued so far
-    int bursts = 0;     // bursts enqueued so far
-    bool stopped = false;   // the device reported zero live rows
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t burst_ev[WM_NLIVE_RING] = {};
-    std::vector<int32_t> pr, gen, bud;
-    WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
-    WmRepPar rpar = {};            // its repetition rules (likewise)
-    std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
-    std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
-    std::vector<unsigned> ids;     // its sample ids (wm_transcribe_mel)
-    std::vector<int32_t> off;      // its row offsets (wm_transcribe_mel_ragged)
-    std::vector<int32_t> xrows;    // its rows of the window set (wm_transcribe_windows)
-    // a beam group (wm_transcribe_mel_beam): its parameters and window budgets (sources of async uploads) and what a drain
-    // fetches: the state in front of the finished records, the finished tokens / log-probs of its windows, the debug trace
-    WmBeamPar bpar = {};
-    std::vector<int32_t> bbud, bfin_tok;
-    std::vector<char> bstate;
-    std::vector<float> bfin_lp, btrace;
-    float stage_sum[3] = {0.f, 0.f, 0.f};
-    ~LaneJob() {
-        if (c) (void)hipStreamSynchronize(c->stream);  // error paths: nothing may outlive pr / gen / bud
-        for (auto &e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto &e : burst_ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-// where a call's encoder input comes from: PCM chunks [.][480000], or (mel non-null) mel windows -- row b is frames
-// seek[b] .. seek[b] + n_frames[b] - 1 of the [n_mels][mel_len[b]] block at mel + mel_base[b] --, or (windows) nothing
-// to encode at all: row b is window rows[b] (rows null: b) of an encoded set, whose cross-attention K/V is copied
-struct WmAudioSrc {
-    const void *pcm = nullptr;
-    wm_dtype pcm_dtype = WM_F32;
-    const float *mel = nullptr;
-    const int64_t *mel_base = nullptr;
-    const int32_t *mel_len = nullptr, *seek = nullptr, *n_frames = nullptr;
-    bool windows = false;   // the wm_*_windows calls: `set` is the source (null: an invalid call)
-    const wm_windows *set = nullptr;
-    const int32_t *rows = nullptr;
-};
-
-// a transcribe call's rows (wm_transcribe: PCM, wm_transcribe_mel: windows) and their prompts
-struct TxSrc : WmAudioSrc {
-    const int32_t *prompt = nullptr;   // row b's prompt: prompt + b * prompt_stride (0: one prompt for all)
-    int prompt_stride = 0;
-    const int32_t *prompt_len = nullptr;   // non-null: a ragged call, row b's prompt is its first prompt_len[b] entries
-    int sot_tail = 0;                      // ... whose <|startoftranscript|> is entry prompt_len[b] - sot_tail
-    const uint32_t *sample_ids = nullptr;
-    int n_cand = 1;   // candidates per row (wm_transcribe_mel_best_of): every row decodes n_cand times over ONE encoder pass
-    // wm_transcribe_mel_beam: the n_cand rows of a window are its BEAMS (n_cand = beam width, 1 included)
-    bool beam = false;
-    int max_cand = 0;
-    int32_t *n_hyp = nullptr;   // [B]
-    float *sums = nullptr;      // [B][max(n_cand, max_cand)]
-    float *trace = nullptr;     // debug library: [B][max_new][n_cand][WM_BEAM_TRACE] (null in the product)
-};
-
-struct StopCfg {
-    bool on = false;
-    int32_t eot = -1;
-    const int32_t *budgets = nullptr;  // [B] of the call, already clamped to max_new (null: none)
-};
-
-// wm_transcribe's extended decode: off for wm_transcribe_greedy and for a wm_transcribe call that wants neither outputs nor
-// sampling (then it IS the greedy decode: same graphs, same kernels)
-struct XCfg {
-    bool on = false;
-    WmXPar par = {};               // chunk0 / n_prompt filled per group
-    float *logprobs = nullptr;     // [B][max_new] host, nullable
-    float *no_speech = nullptr;    // [B] host, nullable
-};
-
-}  // namespace
-
-// The prompt table of ONE decode group of a ragged call (pure: tests pin it through the debug library): rows
-// [b0, b0 + Bg) of prompts [.][stride], right-aligned to the group's own longest prompt P.  table [P][Bg] position-major
-// like dseq, off [Bg] = P - len.  The positions in front of a row's prompt repeat its first token: any valid id would
-// do, nothing decoded there is kept.
-int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, std::vector<int32_t> &table,
-                   std::vector<int32_t> &off) {
-    int P = 0;
-    for (int b = 0; b < Bg; ++b) P = std::max(P, (int)prompt_len[b0 + b]);
-    table.resize((size_t)P * Bg);
-    off.resize(Bg);
-    for (int b = 0; b < Bg; ++b) {
-        const int32_t *row = prompts + (size_t)(b0 + b) * stride;
-        const int o = P - prompt_len[b0 + b];
-        off[b] = o;
-        for (int t = 0; t < P; ++t) table[(size_t)t * Bg + b] = row[t < o ? 0 : t - o];
-    }
-    return P;
-}
-
-namespace {
-// row b of a mel source: its window lies inside its block (`who` prefixes the message; align bounds n_frames tighter itself)
-int check_window(const WmAudioSrc &a, int b, const char *who) {
-    WM_REQUIRE(a.mel_base[b] >= 0 && a.mel_len[b] >= 1 && a.seek[b] >= 0 && a.n_frames[b] >= 1 &&
-                   a.n_frames[b] <= WM_N_FRAMES && (int64_t)a.seek[b] + a.n_frames[b] <= a.mel_len[b],
-               WM_ERR_INVALID, "%srow %d: window (base %lld, T %d, seek %d, n_frames %d) invalid", who, b,
-               (long long)a.mel_base[b], a.mel_len[b], a.seek[b], a.n_frames[b]);
-    return WM_OK;
-}
-
-// the pointers of a window source: the five of a mel call, or the set
-int check_src_pointers(const WmAudioSrc &a) {
-    if (a.windows) {
-        WM_REQUIRE(a.set != nullptr, WM_ERR_INVALID, "null window set");
-        return WM_OK;
-    }
-    WM_REQUIRE(a.mel && a.mel_base && a.mel_len && a.seek && a.n_frames, WM_ERR_INVALID, "null mel / window pointer");
-    return WM_OK;
-}
-
-// a set may be read by the context that made it and by every context that shares that one's weights
-int check_set_owner(const wm_ctx *ctx, const wm_windows *w) {
-    const WmModel *m = ctx->model;
-    WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "window sets are not supported by the all-f32 precision path");
-    WM_REQUIRE(w->device == ctx->device && w->weights == (const void *)m->tok_emb && memcmp(&w->dims, &m->dims, sizeof(wm_dims)) == 0,
-               WM_ERR_INVALID, "the window set was made for another model, device or dims");
-    return WM_OK;
-}
-
-// the B rows of a call that reads a set: every one a window of the set, made for this context's weights
-int check_set_rows(const wm_ctx *ctx, const WmAudioSrc &a, int B, const char *who) {
-    WM_REQUIRE(a.set != nullptr, WM_ERR_INVALID, "%snull window set", who);
-    WM_TRY(check_set_owner(ctx, a.set));
-    const int W = a.set->W;
-    WM_REQUIRE(a.rows || B == W, WM_ERR_INVALID, "%srows is NULL: B (%d) must be the set's %d windows", who, B, W);
-    for (int b = 0; a.rows && b < B; ++b)
-        WM_REQUIRE(a.rows[b] >= 0 && a.rows[b] < W, WM_ERR_INVALID, "%srow %d: window %d outside the set's [0, %d)", who, b, a.rows[b], W);
-    return WM_OK;
-}
-
-// *d_pcm = the PCM of rows [b0, b0 + Bg) in device memory: the caller's, or (host memory) uploaded into m->pcm_stage.
-// Null for a mel source and for a window set.
-int stage_pcm(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const void **d_pcm) {
-    WmModel *m = c->model;
-    *d_pcm = nullptr;
-    if (a.mel || a.windows) return WM_OK;
-    const size_t row = WM_N_SAMPLES * pcm_elem(a.pcm_dtype);
-    *d_pcm = (const char *)a.pcm + (size_t)b0 * row;
-    if (mem != WM_MEM_HOST) return WM_OK;
-    WM_TRY(m->pcm_stage.reserve(c->stream, (size_t)Bg * row));
-    WM_HIP(hipMemcpyAsync(m->pcm_stage.p, *d_pcm, (size_t)Bg * row, hipMemcpyHostToDevice, c->stream));
-    *d_pcm = m->pcm_stage.p;
-    return WM_OK;
-}
-
-// The encoder input (enc_mel, enc_win) of rows [b0, b0 + Bg), to be called after wm_model_reserve.  PCM: the log-mel front
-// end (f32 fast path) of d_pcm into m->mel_f32, output stays in HBM, no windows.  Mel windows: the table `win` -- the
-// CALLER's, it is the source of an asynchronous upload -- in m->dmel_win, gathered by the encoder's first step from the
-// caller's device memory; with host memory only the windows are copied, into the front end's buffer.
-int stage_mel(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const void *d_pcm, std::vector<WmMelWin> &win,
-              const float **enc_mel, const WmMelWin **enc_win) {
-    WmModel *m = c->model;
-    const int C = m->dims.n_mels;
-    *enc_mel = m->mel_f32;
-    *enc_win = nullptr;
-    if (!a.mel) return wm_frontend_run(&c->fe, &c->prof, c->stream, d_pcm, a.pcm_dtype, Bg, C, m->mel_f32, WM_F32);
-    win.resize(Bg);
-    for (int b = 0; b < Bg; ++b) {
-        const int r = b0 + b;
-        WmMelWin &w = win[b];
-        w.T = a.mel_len[r]; w.seek = a.seek[r]; w.n = a.n_frames[r]; w.pad = 0;
-        w.base = a.mel_base[r];
-        if (mem == WM_MEM_HOST) {
-            WM_HIP(hipMemcpy2DAsync(m->mel_f32 + (size_t)b * C * WM_N_FRAMES, WM_N_FRAMES * sizeof(float),
-                                    a.mel + w.base + w.seek, (size_t)w.T * sizeof(float), (size_t)w.n * sizeof(float),
-                                    C, hipMemcpyHostToDevice, c->stream));
-            w.base = (long long)b * C * WM_N_FRAMES; w.T = WM_N_FRAMES; w.seek = 0;
-        }
-    }
-    WM_HIP(hipMemcpyAsync(m->dmel_win, win.data(), (size_t)Bg * sizeof(WmMelWin), hipMemcpyHostToDevice, c->stream));
-    if (mem != WM_MEM_HOST) *enc_mel = a.mel;
-    *enc_win = m->dmel_win;
-    return WM_OK;
-}
-
-// The cross-attention K/V of rows [b0, b0 + Bg) of a call in m->xkv ([L][2][Bg][H][1500][64]), to be called after
-// wm_model_reserve.  PCM / mel windows: stage_mel, `staged` recorded, the encoder, wm_model_cross_kv.  A window set: the
-// rows' slabs copied from the set's store in one launch -- `map` is the CALLER's, the source of the asynchronous upload of
-// the row map --, then `staged`: there is no encoder stage.
-int stage_cross_kv(wm_ctx *c, const WmAudioSrc &a, int b0, int Bg, wm_mem mem, const void *d_pcm, std::vector<WmMelWin> &win,
-                   std::vector<int32_t> &map, hipEvent_t staged) {
-    WmModel *m = c->model;
-    if (a.windows) {
-        const wm_dims &D = m->dims;
-        map.resize(Bg);
-        for (int b = 0; b < Bg; ++b) map[b] = a.rows ? a.rows[b0 + b] : b0 + b;
-        WM_HIP(hipMemcpyAsync(m->dxkv_rows, map.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
-        WM_TRY(wm_xkv_rows(c, m->xkv, Bg, a.set->store, m->dxkv_rows, 0, Bg, 2 * D.n_text_layer, (long)D.n_text_head * 1500 * 64,
-                           false));
-        if (staged) WM_HIP(hipEventRecord(staged, c->stream));
-        return WM_OK;
-    }
-    const float *enc_mel;
-    const WmMelWin *enc_win;
-    WM_TRY(stage_mel(c, a, b0, Bg, mem, d_pcm, win, &enc_mel, &enc_win));
-    if (staged) WM_HIP(hipEventRecord(staged, c->stream));
-    WM_TRY(wm_model_encode_win(c, enc_mel, enc_win, Bg, nullptr));
-    return wm_model_cross_kv(c, Bg);
-}
-
-// the tokens row `b` of the call may generate
-int stop_budget(const StopCfg &stop, int b, int max_new) { return stop.budgets && stop.budgets[b] < max_new ? stop.budgets[b] : max_new; }
-
-// front end -> encoder -> cross K/V -> prompt upload -> first embedding, all enqueued on the lane's stream
-int lane_prefill(LaneJob &j, const TxSrc &src, int n_prompt, wm_mem mem, const StopCfg &stop, const XCfg &xc) {
-    wm_ctx *c = j.c;
-    WmModel *m = c->model;
-    const int Bg = j.Bg, Cg = j.Cg, N = src.n_cand;   // decoder rows, encoder rows (windows), candidates per window
-    // the mode of this group's decode: the lane's own context settings and the call's options, in this one place
-    j.mode = WmDecodeMode();
-    j.mode.mask = m->mask_on; j.mode.ts = m->ts_on; j.mode.x = xc.on; j.mode.off = src.prompt_len != nullptr;
-    j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
-    j.mode.n_cand = N;
-    j.mode.beam = src.beam ? N : 0;
-    j.mode.rep = m->rep_on;   // (transcribe_impl turns the extended decode on with them)
-    const void *d_pcm;
-    WM_TRY(stage_pcm(c, src, j.b0, Cg, mem, &d_pcm));
-    // decode state first (prompt tokens [n_prompt][Bg], position 0): a pageable H2D copy may wait for the
-    // stream to drain, so it is issued while the lane is still idle
-    WM_TRY(wm_model_decode_begin(c, Bg));
-    if (src.prompt_len) {   // ragged: right-aligned to the group's longest prompt (n_prompt = j.P), offsets next to it
-        wm_right_align(src.prompt, src.prompt_stride, src.prompt_len, j.b0, Cg, j.pr, j.off);
-        if (N > 1) {   // every candidate of a window steps through the window's prompt
-            std::vector<int32_t> pr((size_t)n_prompt * Bg), off(Bg);
-            for (int b = 0; b < Bg; ++b) off[b] = j.off[b / N];
-            for (int t = 0; t < n_prompt; ++t)
-                for (int b = 0; b < Bg; ++b) pr[(size_t)t * Bg + b] = j.pr[(size_t)t * Cg + b / N];
-            j.pr.swap(pr);
-            j.off.swap(off);
-        }
-        WM_HIP(hipMemcpyAsync(m->doff, j.off.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
-    } else {
-        j.pr.resize((size_t)n_prompt * Bg);
-        for (int t = 0; t < n_prompt; ++t)
-            for (int b = 0; b < Bg; ++b) j.pr[(size_t)t * Bg + b] = src.prompt[(size_t)(j.b0 + b / N) * src.prompt_stride + t];
-    }
-    WM_HIP(hipMemcpyAsync(m->dseq, j.pr.data(), j.pr.size() * 4, hipMemcpyHostToDevice, c->stream));
-    WM_TRY(wm_model_set_pos(c, 0));
-    // early-stop state of this group: done flags, live list, per-row budgets (kernel arguments of the decode graphs)
-    if (stop.on) {
-        if (j.mode.budget) {
-            j.bud.resize(Bg);
-            for (int b = 0; b < Bg; ++b) j.bud[b] = stop.budgets[j.b0 + b / N];
-            WM_HIP(hipMemcpyAsync(m->dbudget, j.bud.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
-        }
-        WM_TRY(wm_stop_init(c, wm_model_stop_dev(m, j.mode), Bg));
-    }
-    // extended decode: seed, 1/T, the sot position and the group's first call index live in device memory, so the
-    // captured graphs replay for any of them
-    if (xc.on) {
-        j.xpar = xc.par;
-        j.xpar.chunk0 = j.b0;
-        j.xpar.n_prompt = n_prompt;
-        if (src.prompt_len && xc.no_speech) j.xpar.sot_pos = n_prompt - src.sot_tail;   // the same distance from every row's end
-        j.xpar.ids_on = (src.sample_ids || N > 1) ? 1 : 0;
-        j.xpar.n_cand = N;
-        if (N > 1) {   // a candidate group: per row the window's id (given, or its index in the call) and the candidate word
-            j.ids.assign((size_t)2 * WM_XIDS_CAND, 0u);
-            for (int b = 0; b < Bg; ++b) {
-                j.ids[b] = src.sample_ids ? src.sample_ids[j.b0 + b / N] : (unsigned)(j.b0 + b / N);
-                j.ids[WM_XIDS_CAND + b] = (unsigned)(b % N);
-            }
-            WM_HIP(hipMemcpyAsync(m->dx_ids, j.ids.data(), j.ids.size() * 4, hipMemcpyHostToDevice, c->stream));
-        } else if (src.sample_ids) {   // caller-given Philox counter words (wm_transcribe_mel): a row's noise follows its id
-            j.ids.assign(src.sample_ids + j.b0, src.sample_ids + j.b0 + Bg);
-            WM_HIP(hipMemcpyAsync(m->dx_ids, j.ids.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
-        }
-        WM_HIP(hipMemcpyAsync(m->dx_par, &j.xpar, sizeof(WmXPar), hipMemcpyHostToDevice, c->stream));
-    }
-    // repetition rules: penalty, its reciprocal, n and eot live in device memory too (the graph key holds `rep` alone)
-    if (j.mode.rep) {
-        WM_REQUIRE(xc.on, WM_ERR_STATE, "the repetition rules need the extended decode");
-        j.rpar.p = m->rep_p; j.rpar.inv_p = (float)(1.0 / (double)m->rep_p); j.rpar.n = m->rep_n; j.rpar.eot = m->rep_eot;
-        WM_HIP(hipMemcpyAsync(m->drep_par, &j.rpar, sizeof(WmRepPar), hipMemcpyHostToDevice, c->stream));
-    }
-    WM_TRY(wm_model_reserve(c, Cg));
-    if (N > 1) WM_TRY(wm_model_reserve_rows(c, Bg));
-    if (src.beam) {   // beam state: nothing finished, every sum 0; a window's budget is its own max_new
-        j.bbud.resize(Cg);
-        for (int w = 0; w < Cg; ++w) j.bbud[w] = stop_budget(stop, j.b0 + w, j.bpar.max_new);
-        m->beam_trace_on = src.trace != nullptr;
-        if (src.trace) {
-            const size_t bytes = (size_t)j.bpar.max_new * Bg * WM_BEAM_TRACE * 4;
-            WM_TRY(m->beam_trace.reserve(c->stream, bytes));
-            WM_HIP(hipMemsetAsync(m->beam_trace.p, 0, bytes, c->stream));
-        }
-        WM_TRY(wm_model_beam_begin(c, j.mode, Bg, Cg, &j.bpar, j.bbud.data()));
-    }
-    WM_HIP(hipEventRecord(j.ev[0], c->stream));
-    // 1. log-mel front end, or the caller's mel windows;  2. encoder + cross-attention K/V  (a window set: 1. the gather)
-    WM_TRY(stage_cross_kv(c, src, j.b0, Cg, mem, d_pcm, j.win, j.xrows, j.ev[1]));
-    WM_HIP(hipEventRecord(j.ev[2], c->stream));
-    // 3. embedding of the first prompt token (+ the initial timestamp-rule state)
-    WM_TRY(wm_model_embed_first(c, Bg, j.mode));
-    if (j.mode.ts) WM_TRY(wm_ts_init(c, wm_model_ts_dev(m), Bg));
-    return WM_OK;
-}
-
-// One decoder position = 8 launches per layer + logits + arg-max/embed (which writes the next token, embeds the
-// next position and advances *dpos).  Nothing in it depends on host state, so it is captured ONCE into a
-// hipGraph per lane and replayed for every position -- and `burst` consecutive positions are captured as one more graph.
-// gen (a beam group's generating positions): the step also stores the f32 logits and the beam kernels close it.
-int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) {
-    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen, 0, j.c->model->dims.n_vocab - 1, nullptr, mode, n_prompt));
-    if (gen) return wm_model_beam_close(j.c, j.Bg, n_prompt, mode);
-    return wm_model_close_step(j.c, j.Bg, n_prompt, true, nullptr, 0, mode);
-}
-
-int capture_positions(LaneJob &j, const WmDecodeMode &mode, int n_prompt, int n_pos, bool gen, WmGraph *out) {
-    char what[48];
-    snprintf(what, sizeof(what), "the %d-position decode graph", n_pos);
-    return capture_graph(j.c->stream, out, what, [&]() -> int {
-        for (int i = 0; i < n_pos; ++i) WM_TRY(lane_position(j, mode, n_prompt, gen));
-        return WM_OK;
-    });
-}
-
-// Select (creating it if needed) the graph set of the group's decode shape and mode.  The graphs themselves are captured
-// on first use, per sharing mode, by lane_burst.
-int lane_graph(LaneJob &j, int n_prompt) {
-    WmModel *m = j.c->model;
-    int cur = -1;
-    for (size_t i = 0; i < m->graph_sets.size(); ++i) {
-        const WmModel::GraphSet &g = m->graph_sets[i];
-        if (g.B == j.Bg && g.n_prompt == n_prompt && g.cap_b == m->cap_b && g.mode == j.mode) cur = (int)i;
-    }
-    if (cur < 0) {
-        if ((int)m->graph_sets.size() >= WmModel::kMaxGraphSets) {   // evict the least recently used shape
-            size_t old = 0;
-            for (size_t i = 1; i < m->graph_sets.size(); ++i)
-                if (m->graph_sets[i].stamp < m->graph_sets[old].stamp) old = i;
-            m->graph_sets[old].destroy();
-            m->graph_sets.erase(m->graph_sets.begin() + (long)old);
-        }
-        WmModel::GraphSet g;
-        g.B = j.Bg; g.n_prompt = n_prompt; g.cap_b = m->cap_b; g.mode = j.mode;
-        m->graph_sets.push_back(g);
-        cur = (int)m->graph_sets.size() - 1;
-    }
-    j.gset = cur;
-    m->graph_sets[cur].stamp = ++m->graph_clock;
-    return WM_OK;
-}
-
-// a beam group has enqueued everything: fetch its beam state behind the token streams
-int beam_fetch(LaneJob &j, int max_new, bool trace) {
-    WmModel *m = j.c->model;
-    WmBeamDev bm;
-    WM_TRY(wm_model_beam_dev(j.c, j.mode, &bm));
-    j.lp.resize((size_t)max_new * j.Bg);   // the live beams' log-probs [gi][row], whether or not the caller wants them
-    WM_HIP(hipMemcpyAsync(j.lp.data(), m->dx_logprob, j.lp.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
-    j.bstate.resize(wm_model_beam_state_bytes(m));
-    WM_HIP(hipMemcpyAsync(j.bstate.data(), m->beam_ws.p, j.bstate.size(), hipMemcpyDeviceToHost, j.c->stream));
-    const size_t nf = (size_t)j.Cg * WM_MAX_BEAM_HYPS * bm.n_ctx;
-    j.bfin_tok.resize(nf);
-    j.bfin_lp.resize(nf);
-    WM_HIP(hipMemcpyAsync(j.bfin_tok.data(), bm.fin_tok, nf * 4, hipMemcpyDeviceToHost, j.c->stream));
-    WM_HIP(hipMemcpyAsync(j.bfin_lp.data(), bm.fin_lp, nf * 4, hipMemcpyDeviceToHost, j.c->stream));
-    if (trace) {
-        j.btrace.resize((size_t)max_new * j.Bg * WM_BEAM_TRACE);
-        WM_HIP(hipMemcpyAsync(j.btrace.data(), m->beam_trace.p, j.btrace.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
-    }
-    return WM_OK;
-}
-
-// ... and, once it has arrived, write the windows' hypotheses: the finished ones in the order they finished, then (fewer
-// than N finished) the live beams by descending sum until there are N.  Output stride S = max(N, max_cand) per window.
-void beam_drain(const LaneJob &j, const TxSrc &src, int max_new, int32_t eot, int32_t *tokens_out, int32_t *lens_out,
-                float *logprobs_out, float *no_speech_out) {
-    const int N = src.n_cand, S = std::max(N, src.max_cand), n_ctx = j.c->model->dims.n_text_ctx;
-    // the device pointers of the state, as offsets into the fetched copy
-    WmBeamDev bm;
-    (void)wm_model_beam_dev(j.c, j.mode, &bm);
-    const char *dev0 = (const char *)j.c->model->beam_ws.p;
-    auto host = [&](const void *dev) { return j.bstate.data() + ((const char *)dev - dev0); };
-    const float *sum = (const float *)host(bm.sum), *fin_sum = (const float *)host(bm.fin_sum);
-    const int *fin_n = (const int *)host(bm.fin_n), *fin_len = (const int *)host(bm.fin_len), *wsteps = (const int *)host(bm.wsteps);
-    for (int w = 0; w < j.Cg; ++w) {
-        const int W = j.b0 + w;   // window of the call
-        int n_hyp = 0;
-        auto put = [&](const int32_t *tok, size_t tok_stride, const float *lp, size_t lp_stride, int len, float s) {
-            const size_t o = (size_t)W * S + n_hyp++;
-            for (int i = 0; i < max_new; ++i) {
-                tokens_out[o * max_new + i] = i < len ? tok[(size_t)i * tok_stride] : eot;
-                if (logprobs_out) logprobs_out[o * max_new + i] = i < len ? lp[(size_t)i * lp_stride] : 0.f;
-            }
-            lens_out[o] = len;
-            src.sums[o] = s;
-        };
-        for (int f = 0; f < fin_n[w]; ++f) {
-            const size_t base = ((size_t)w * WM_MAX_BEAM_HYPS + f) * n_ctx;
-            put(j.bfin_tok.data() + base, 1, j.bfin_lp.data() + base, 1, fin_len[w * WM_MAX_BEAM_HYPS + f], fin_sum[w * WM_MAX_BEAM_HYPS + f]);
-        }
-        if (n_hyp < N) {
-            int order[WM_MAX_BEAM];
-            const int n_live = wm_beam_fill_order(N, sum + (size_t)w * N, order);
-            for (int k = 0; k < n_live && n_hyp < N; ++k) {
-                const int b = w * N + order[k];
-                put(j.gen.data() + b, j.Bg, j.lp.data() + b, j.Bg, wsteps[w], sum[b]);
-            }
-        }
-        src.n_hyp[W] = n_hyp;
-        for (int h = n_hyp; h < S; ++h) {   // unused slots
-            const size_t o = (size_t)W * S + h;
-            for (int i = 0; i < max_new; ++i) {
-                tokens_out[o * max_new + i] = eot;
-                if (logprobs_out) logprobs_out[o * max_new + i] = 0.f;
-            }
-            lens_out[o] = 0;
-            src.sums[o] = -INFINITY;
-        }
-        if (no_speech_out) no_speech_out[W] = j.ns[(size_t)w * N];   // beam 0's
-        if (src.trace)     // [gi][row of the group] -> [window of the call][gi][beam]
-            for (int gi = 0; gi < max_new; ++gi)
-                memcpy(src.trace + (((size_t)W * max_new + gi) * N) * WM_BEAM_TRACE,
-                       j.btrace.data() + ((size_t)gi * j.Bg + (size_t)w * N) * WM_BEAM_TRACE, (size_t)N * WM_BEAM_TRACE * 4);
-    }
-}
-
-// enqueue the next burst of positions of a lane (<= burst_len(), up to the end of the sequence).  `shared`: other decode
-// groups are in flight on the device right now -- this burst's cross-attention launches are the short-lived shape.
-int lane_burst(LaneJob &j, int n_prompt, int n_steps, bool use_graph, bool shared) {
-    wm_ctx *c = j.c;
-    WmModel *m = c->model;
-    const int K = burst_len();
-    // a beam group: positions 0 .. n_prompt - 2 step through the prompt (the arg-max close), the others generate (the beam
-    // close); a burst stays on one side
-    const bool gen = j.mode.beam && j.t >= n_prompt - 1;
-    const int left = (j.mode.beam && !gen ? n_prompt - 1 : n_steps) - j.t;
-    const int k = left < K ? left : K;
-    const int sh = shared ? 1 : 0;
-    WmDecodeMode mode = j.mode;   // what every step of this burst, launched or captured, is handed
-    mode.xattn_shared = shared;
-    WmModel::GraphSet *g = use_graph ? &m->graph_sets[j.gset] : nullptr;
-    WmGraph *g1 = g ? (gen ? g->b1 : g->g1) : nullptr, *gk = g ? (gen ? g->bk : g->gk) : nullptr;
-    int *burst = g ? (gen ? g->bburst : g->burst) : nullptr;
-    if (use_graph && k == K && K > 1) {
-        if (!gk[sh].e || burst[sh] != K) {
-            WM_TRY(capture_positions(j, mode, n_prompt, K, gen, &gk[sh]));
-            burst[sh] = K;
-        }
-        WM_HIP(hipGraphLaunch(gk[sh].e, c->stream));
-    } else {
-        if (use_graph && !g1[sh].e) WM_TRY(capture_positions(j, mode, n_prompt, 1, gen, &g1[sh]));
-        for (int i = 0; i < k; ++i) {
-            if (use_graph) {
-                WM_HIP(hipGraphLaunch(g1[sh].e, c->stream));
-            } else {
-                WM_TRY(lane_position(j, mode, n_prompt, gen));
-            }
-        }
-    }
-    j.t += k;
-    if (j.mode.stop) {  // the live-row count after this burst, where the host can read it without touching the stream
-        const int slot = j.bursts % WM_NLIVE_RING;
-        WM_HIP(hipMemcpyAsync(m->h_nlive + slot, m->dnlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        WM_HIP(hipEventRecord(j.burst_ev[slot], c->stream));
-    }
-    ++j.bursts;
-    return WM_OK;
-}
-}  // namespace
-
-// Decode groups of a call of B chunks on at most L lanes (pure: tests/test_abi.py pins the table through the debug library).
-// explicit_lanes: the host set a lane count (wm_set_lanes n > 0); gc_probe: the debug knob group_chunks (0 in the product).
-// More groups than lanes run in rounds of the lanes; a group never exceeds WM_DEC_MAXB rows.
-int wm_group_count(int B, int L, bool explicit_lanes, int gc_probe) {
-    if (L < 1) L = 1;
-    int G;
-    const int gc = gc_probe > 0 ? gc_probe : kGroupChunks;
-    if (!explicit_lanes && gc_probe == 0 && B < 144) {
-        G = B < 32 ? 1 : 2;       // the measured policy (comment in wm_transcribe_greedy)
-        if (G > L) G = L;
-    } else if (B <= gc * L) {
-        G = (B + gc - 1) / gc;    // the rounds-1-4 rule: groups of ~gc while there is a lane for each
-    } else {
-        G = (B + WM_DEC_MAXB - 1) / WM_DEC_MAXB;
-        if (G < L) G = L;
-        G = (G + L - 1) / L * L;
-    }
-    const int g_min = (B + WM_DEC_MAXB - 1) / WM_DEC_MAXB;   // (one lane, 129 .. 143 chunks: still two groups)
-    return G < g_min ? g_min : (G < 1 ? 1 : G);
-}
-
-// B rows in G balanced runs (sizes differ by at most one, the larger ones first): run g is rows [b0[g], b0[g] + cg[g]).  The cut
-// of every transcribe call, with or without candidates.
-void wm_balanced_cut(int B, int G, std::vector<int> &b0, std::vector<int> &cg) {
-    b0.resize(G);
-    cg.resize(G);
-    const int base = B / G, rem = B % G;
-    for (int g = 0; g < G; ++g) {
-        cg[g] = base + (g < rem ? 1 : 0);
-        b0[g] = g * base + (g < rem ? g : rem);
-    }
-}
-
-// Decode groups of a CANDIDATE call (wm_transcribe_mel_best_of) of B windows x N candidates: a group holds whole windows,
-// cg[g] of them from window b0[g], cg[g] * N <= WM_DEC_MAXB rows.  The number of groups is wm_group_count's for the B * N
-// decoder rows (what the GEMVs and the self-attention see), at least what the row cap asks for and at most one per window;
-// the windows are dealt in balanced runs.  Pure: tests pin it through the debug library.  Returns the number of groups.
-int wm_cand_groups(int B, int N, int L, bool explicit_lanes, std::vector<int> &b0, std::vector<int> &cg) {
-    const int c_max = WM_DEC_MAXB / N;
-    int G = wm_group_count(B * N, L, explicit_lanes, 0);
-    G = std::max(G, (B + c_max - 1) / c_max);
-    G = std::min(G, B);
-    wm_balanced_cut(B, G, b0, cg);
-    return G;
-}
-
-// SUB-CHIP LANES (round 6): P = 2 (or 3) decode groups of a call, each on its OWN part of the chip -- weight-sharing clones
-// whose streams carry complementary CU masks (wm_clone_cus: a slice of the CUs of every XCD) -- instead of one
-// latency-bound chain, or unmasked chains whose every launch floods all 256 CUs.  Returns 0 when the call is served better
-// by the unmasked lanes of wm_group_count.  Launch shapes only: same kernels, same bits (tests).
-// MEASURED (profiles/r06_group_policy.txt, r06_solo_lane_latency.txt): whether it pays is decided by how much ONE chain
-// needs the CUs.  A NARROW model's chain does not (base, 16 rows: 0.2375 ms per position on 256 CUs, 0.2452 on 128 --
-// launch latency, the matrices are 0.5-2 MB), so two half-chip chains run truly side by side: base x 32 +7 % over the best
-// unmasked split (14 350 vs 13 400 audio-s/s), x 64 +9 %, tiny.en x 32 +6 %.  A WIDE model's chain does: large-v2, 8 rows,
-// 1.55 ms per position on 256 CUs, 2.21 on 128 -- the streaming phases of its big launches are bound by bytes in flight PER
-// CU (cross-attention 61 MB: 16.4 -> 27.1 us, fc1 13 MB: 6.4 -> 10.7 us on half the CUs), so two half-chip chains lose to
-// one group at every size (15 chunks: 765 vs 937; 24: 1098 vs 1170; 48: 1522 vs 1582) and three thirds lose more.
-int wm_lane_parts(int B, int L, bool explicit_lanes, int n_text_state, int n_text_layer) {
-    (void)n_text_layer;
-    const int knob = g_wm_tuning.lane_parts;     // 0 in the product
-    if (knob == 1) return 0;
-    if (knob == 2 || knob == 3) return (B >= 2 * knob && B <= knob * WM_DEC_MAXB) ? knob : 0;
-    if (explicit_lanes || L < 2) return 0;       // a host that sets a lane count gets the lanes it asked for
-    if (n_text_state <= 384) return (B >= 32 && B < 48) ? 2 : 0;      // tiny: 32 .. 47 chunks (+6 %; -2 % from 48)
-    if (n_text_state <= 512) return (B >= 24 && B <= 128) ? 2 : 0;    // base: 24 .. 128 chunks (+2 .. +9 %; 40 - 48: -1 %)
-    return 0;                                    // d >= 768: the chain needs the whole chip
-}
-
-static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, int max_new, int32_t eot,
-                           const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, float *logprobs_out,
-                           float *no_speech_out, wm_mem mem);
-
-extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
-                                    const int32_t *prompt, int n_prompt, int max_new, int32_t eot,
-                                    int32_t *tokens_out, int32_t *lens_out, wm_mem mem) try {
-    TxSrc src;
-    src.pcm = pcm; src.pcm_dtype = pcm_dtype; src.prompt = prompt;
-    return transcribe_impl(ctx, src, B, n_prompt, max_new, eot, nullptr, tokens_out, lens_out, nullptr, nullptr, mem);
-} WM_API_CATCH
-
-extern "C" int wm_transcribe(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
-                             int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
-                             float *token_logprobs_out, float *no_speech_prob_out, wm_mem mem) try {
-    TxSrc src;
-    src.pcm = pcm; src.pcm_dtype = pcm_dtype; src.prompt = prompt;
-    return transcribe_impl(ctx, src, B, n_prompt, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
-                           no_speech_prob_out, mem);
-} WM_API_CATCH
-
-extern "C" int wm_transcribe_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
-                                 const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts, int n_prompt,
-                                 const uint32_t *sample_ids, int max_new, int32_t eot, const wm_decode_opts *opts,
-                                 int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
-                                 wm_mem mem) try {
-    WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
-    TxSrc src;
-    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
-    src.prompt = prompts; src.prompt_stride = n_prompt; src.sample_ids = sample_ids;
-    return transcribe_impl(ctx, src, B, n_prompt, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
-                           no_speech_prob_out, mem);
-} WM_API_CATCH
-
-// wm_transcribe_mel with prompts of different lengths: every decode group right-aligns its rows to its own longest prompt
-// (wm_right_align, WmModel::doff); a row's results are those of wm_transcribe_mel on that row alone with its own prompt
-extern "C" int wm_transcribe_mel_ragged(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
-                                        const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
-                                        int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
-                                        int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out,
-                                        int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
-                                        wm_mem mem) try {
-    WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
-    WM_REQUIRE(prompt_len, WM_ERR_INVALID, "null prompt_len");
-    WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
-    TxSrc src;
-    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
-    src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
-    src.sample_ids = sample_ids;
-    return transcribe_impl(ctx, src, B, prompt_stride, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
-                           no_speech_prob_out, mem);
-} WM_API_CATCH
-
-// wm_transcribe_mel_ragged / wm_transcribe_mel with best_of candidates per row (TxSrc::n_cand): one encoder pass, one
-// cross-K/V cache and one read of it per window, best_of decoder rows (lane_prefill, wm_dec_attention_cand)
-// (src: the windows -- mel or a set -- and nothing else; wm_transcribe_mel_best_of and wm_transcribe_windows)
-static int best_of_impl(wm_ctx *ctx, TxSrc &src, int B, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len,
-                        int sot_tail, const uint32_t *sample_ids, int best_of, float length_penalty, int max_new, int32_t eot,
-                        const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
-                        float *no_speech_prob_out, int32_t *best_out, wm_mem mem) {
-    // the checks of this entry point's own arguments; a call that fails them consumes the token budgets set for it, as a
-    // call that fails transcribe_impl's checks does
-    const int rc = [&]() -> int {
-        WM_TRY(check_src_pointers(src));
-        WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
-        WM_REQUIRE(best_of >= 1 && best_of <= WM_MAX_BEST_OF, WM_ERR_INVALID, "best_of %d outside [1, %d]", best_of, WM_MAX_BEST_OF);
-        WM_REQUIRE(std::isnan(length_penalty) || (length_penalty >= 0.f && length_penalty <= 1.f), WM_ERR_INVALID,
-                   "length_penalty must be NaN (none) or in [0, 1]");
-        WM_REQUIRE(B >= 1 && max_new >= 1, WM_ERR_INVALID, "B < 1 or max_new < 1");
-        return WM_OK;
-    }();
-    if (rc != WM_OK) {
-        if (ctx && ctx->model) ctx->model->budget_host.clear();
-        return rc;
-    }
-    src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
-    src.sample_ids = sample_ids; src.n_cand = best_of;
-    std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
-    float *lp = token_logprobs_out;
-    if (best_out && !lp) {
-        lp_own.resize((size_t)B * best_of * max_new);
-        lp = lp_own.data();
-    }
-    WM_TRY(transcribe_impl(ctx, src, B, prompt_stride, max_new, eot, opts, tokens_out, lens_out, lp, no_speech_prob_out, mem));
-    if (best_out)
-        WM_TRY(wm_rank_candidates(tokens_out, lens_out, lp, B, best_of, max_new, eot, length_penalty, best_out, nullptr));
-    return WM_OK;
-}
-
-extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
-                                         const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
-                                         int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
-                                         int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
-                                         int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
-                                         float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
-    TxSrc src;
-    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
-    return best_of_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of, length_penalty, max_new,
-                        eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out, best_out, mem);
-} WM_API_CATCH
-
-// wm_transcribe_mel_best_of over the windows of an encoded set: the same call, its cross-K/V copied instead of computed
-extern "C" int wm_transcribe_windows(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
-                                     int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
-                                     int best_of, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
-                                     int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
-                                     float *no_speech_prob_out, int32_t *best_out) try {
-    TxSrc src;
-    src.windows = true; src.set = w; src.rows = rows;
-    return best_of_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of, length_penalty, max_new,
-                        eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out, best_out, WM_MEM_HOST);
-} WM_API_CATCH
-
-// Beam search: the call of wm_transcribe_mel_best_of with the rows of a window as its BEAMS (TxSrc::beam) -- the same groups,
-// the same prompt phase, one cross-K/V read per window; the generating positions close with the beam kernels (beam.hip)
-static int beam_impl(wm_ctx *ctx, TxSrc &src, int B, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len,
-                     int sot_tail, int beam_size, int max_candidates, float length_penalty, int max_new, int32_t eot,
-                     const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out,
-                     float *sum_logprobs_out, float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) {
-    float *trace = nullptr;   // the debug library's capture is for this call only
-    if (ctx && ctx->model) {
-        trace = ctx->model->beam_dbg_trace;
-        ctx->model->beam_dbg_trace = nullptr;
-    }
-    const int rc = [&]() -> int {   // (a call that fails these consumes the token budgets set for it, like any other)
-        WM_TRY(check_src_pointers(src));
-        WM_REQUIRE(n_hyp_out && sum_logprobs_out, WM_ERR_INVALID, "null n_hyp_out / sum_logprobs_out");
-        WM_REQUIRE(prompt_stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", prompt_stride);
-        WM_REQUIRE(beam_size >= 1 && beam_size <= WM_MAX_BEAM, WM_ERR_INVALID, "beam_size %d outside [1, %d]", beam_size, WM_MAX_BEAM);
-        WM_REQUIRE(max_candidates >= 1 && max_candidates <= WM_MAX_BEAM_HYPS, WM_ERR_INVALID, "max_candidates %d outside [1, %d]",
-                   max_candidates, WM_MAX_BEAM_HYPS);
-        WM_REQUIRE(std::isnan(length_penalty) || (length_penalty >= 0.f && length_penalty <= 1.f), WM_ERR_INVALID,
-                   "length_penalty must be NaN (none) or in [0, 1]");
-        WM_REQUIRE(B >= 1 && max_new >= 1, WM_ERR_INVALID, "B < 1 or max_new < 1");
-        return WM_OK;
-    }();
-    if (rc != WM_OK) {
-        if (ctx && ctx->model) ctx->model->budget_host.clear();
-        return rc;
-    }
-    src.prompt = prompts; src.prompt_stride = prompt_stride; src.prompt_len = prompt_len; src.sot_tail = sot_tail;
-    src.n_cand = beam_size; src.beam = true; src.max_cand = max_candidates;
-    src.n_hyp = n_hyp_out; src.sums = sum_logprobs_out; src.trace = trace;
-    WM_TRY(transcribe_impl(ctx, src, B, prompt_stride, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out,
-                           no_speech_prob_out, mem));
-    if (best_out) {   // the MaximumLikelihoodRanker over the search's own sums
-        const int S = std::max(beam_size, max_candidates);
-        for (int b = 0; b < B; ++b) {
-            int best = 0;
-            double best_score = -INFINITY;
-            for (int h = 0; h < n_hyp_out[b]; ++h) {
-                const size_t r = (size_t)b * S + h;
-                int n_text = 0;
-                while (n_text < lens_out[r] && tokens_out[r * max_new + n_text] != eot) ++n_text;
-                const double score = wm_rank_score((double)sum_logprobs_out[r], n_text, length_penalty);
-                if (score > best_score) { best_score = score; best = h; }   // the first maximal score; all -inf: hypothesis 0
-            }
-            best_out[b] = best;
-        }
-    }
-    return WM_OK;
-}
-
-extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
-                                      const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
-                                      int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size, int max_candidates,
-                                      float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
-                                      int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
-                                      float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
-    TxSrc src;
-    src.mel = mel; src.mel_base = mel_base; src.mel_len = mel_len; src.seek = seek; src.n_frames = n_frames;
-    return beam_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, max_new,
-                     eot, opts, tokens_out, lens_out, n_hyp_out, sum_logprobs_out, token_logprobs_out, no_speech_prob_out, best_out,
-                     mem);
-} WM_API_CATCH
-
-extern "C" int wm_transcribe_windows_beam(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
-                                          int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size,
-                                          int max_candidates, float length_penalty, int max_new, int32_t eot,
-                                          const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out,
-                                          float *sum_logprobs_out, float *token_logprobs_out, float *no_speech_prob_out,
-                                          int32_t *best_out) try {
-    TxSrc src;
-    src.windows = true; src.set = w; src.rows = rows;
-    return beam_impl(ctx, src, B, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, max_new,
-                     eot, opts, tokens_out, lens_out, n_hyp_out, sum_logprobs_out, token_logprobs_out, no_speech_prob_out, best_out,
-                     WM_MEM_HOST);
-} WM_API_CATCH
-
-// wm_transcribe_greedy, wm_transcribe, wm_transcribe_mel and wm_transcribe_mel_ragged: opts == null with both extra outputs
-// null is the greedy decode exactly
-static int transcribe_impl(wm_ctx *ctx, const TxSrc &src, int B, int n_prompt, int max_new, int32_t eot,
-                           const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, float *logprobs_out,
-                           float *no_speech_out, wm_mem mem) {
-    WM_MODEL(ctx);
-    // per-chunk token budgets set for THIS call (wm_set_token_budgets) are consumed by it whatever happens next: a call
-    // that fails validation must not leave them armed for a later, unrelated call with the same B
-    std::vector<int32_t> budgets;
-    budgets.swap(m->budget_host);
-    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
-    WM_REQUIRE((src.pcm || src.mel || src.windows) && src.prompt && tokens_out && lens_out, WM_ERR_INVALID, "null pointer");
-    WM_REQUIRE(src.mel || src.windows || src.pcm_dtype == WM_I16 || src.pcm_dtype == WM_F32 || src.pcm_dtype == WM_F64,
-               WM_ERR_INVALID, "bad pcm dtype");
-    WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
-    if (src.mel)
-        for (int b = 0; b < B; ++b) WM_TRY(check_window(src, b, ""));
-    if (src.windows) WM_TRY(check_set_rows(ctx, src, B, ""));
-    const wm_dims &D = m->dims;
-    if (src.prompt_len) {   // ragged: n_prompt arrives as the row stride and becomes the call's longest prompt
-        int longest = 0;
-        for (int b = 0; b < B; ++b) {
-            WM_REQUIRE(src.prompt_len[b] >= 1 && src.prompt_len[b] <= src.prompt_stride, WM_ERR_INVALID,
-                       "row %d: prompt_len %d outside [1, %d]", b, src.prompt_len[b], src.prompt_stride);
-            longest = std::max(longest, (int)src.prompt_len[b]);
-        }
-        n_prompt = longest;
-    }
-    WM_REQUIRE(n_prompt >= 1 && max_new >= 1 && n_prompt + max_new <= D.n_text_ctx, WM_ERR_INVALID,
-               "prompt (%d) + new tokens (%d) must fit the %d-token context", n_prompt, max_new, D.n_text_ctx);
-    for (int b = 0; b < (src.prompt_stride ? B : 1); ++b)
-        for (int i = 0; i < (src.prompt_len ? src.prompt_len[b] : n_prompt); ++i) {
-            const int32_t t = src.prompt[(size_t)b * src.prompt_stride + i];
-            WM_REQUIRE(t >= 0 && t < D.n_vocab, WM_ERR_INVALID, "prompt token %d out of range", t);
-        }
-    WM_REQUIRE(eot < D.n_vocab, WM_ERR_INVALID, "eot %d outside the vocabulary", eot);
-    WM_REQUIRE(budgets.empty() || (int)budgets.size() == B, WM_ERR_INVALID,
-               "token budgets were set for %d chunks, the call has %d", (int)budgets.size(), B);
-    for (auto &b : budgets) b = b > max_new ? max_new : b;
-    XCfg xc;
-    {
-        const float T = opts ? opts->temperature : 0.f;
-        const int32_t ns_tok = opts ? opts->no_speech_token : -1;
-        // (a ragged call places <|startoftranscript|> by sot_tail; opts->sot_index is not read)
-        const int32_t sot_index = (opts && !src.prompt_len) ? opts->sot_index : 0;
-        if (src.prompt_len && no_speech_out) {
-            const int shortest = *std::min_element(src.prompt_len, src.prompt_len + B);
-            WM_REQUIRE(src.sot_tail >= 1 && src.sot_tail <= shortest, WM_ERR_INVALID,
-                       "sot_tail %d outside [1, %d] (the shortest prompt)", src.sot_tail, shortest);
-        }
-        WM_REQUIRE(std::isfinite(T) && T >= 0.f, WM_ERR_INVALID, "temperature must be finite and >= 0");
-        // (1 / T must be a finite f32 too: an infinite scale turns a zero logit's score into NaN)
-        WM_REQUIRE(T == 0.f || std::isfinite((float)(1.0 / (double)T)), WM_ERR_INVALID,
-                   "temperature %g is too small: 1 / T overflows", (double)T);
-        WM_REQUIRE(sot_index >= 0 && sot_index < n_prompt, WM_ERR_INVALID, "sot_index %d outside the prompt [0, %d)",
-                   sot_index, n_prompt);
-        WM_REQUIRE(ns_tok >= -1 && ns_tok < D.n_vocab, WM_ERR_INVALID, "no_speech_token %d outside the vocabulary", ns_tok);
-        WM_REQUIRE(!no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
-        WM_REQUIRE(!src.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
-        // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
-        xc.on = T > 0.f || logprobs_out || no_speech_out || src.beam || m->rep_on;
-        WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
-        xc.logprobs = logprobs_out;
-        xc.no_speech = no_speech_out;
-        const uint64_t seed = opts ? opts->seed : 0;
-        xc.par.key0 = (unsigned)seed;
-        xc.par.key1 = (unsigned)(seed >> 32);
-        xc.par.sample = T > 0.f ? 1 : 0;
-        xc.par.inv_T = T > 0.f ? (float)(1.0 / (double)T) : 0.f;
-        xc.par.sot_pos = no_speech_out ? sot_index : -1;
-        xc.par.ns_tok = ns_tok;
-    }
-    const bool no_stop = g_wm_tuning.no_early_stop != 0;   // probes only: decode every position, truncate on the host
-    const bool use_graph = !graphs_off() && !ctx->prof.on && !src.trace;   // (a traced call bakes nothing into graphs)
-    StopCfg stop;
-    stop.on = !no_stop && (eot >= 0 || !budgets.empty());
-    stop.eot = eot;
-    stop.budgets = budgets.empty() ? nullptr : budgets.data();
-    // Split the B chunks into G balanced decode groups (<= WM_DEC_MAXB each, kGroupChunks preferred) and run
-    // them on L lanes.  Per-kernel profiling keeps everything on the caller's context (one lane).
-    // GROUP POLICY (round 5, measured: profiles/r05_group_policy.txt).  Rounds 1-4 cut every call into groups of ~8 chunks
-    // on up to three lanes.  At large-v2 that is the WORST choice below ~50 chunks (15 chunks: 8 + 7 on two lanes 826
-    // audio-s/s, one group of 15 860; 48 chunks: 3 x 16 1449, one group 1538): a group's weight stream is shared by all its
-    // rows, and two latency-bound chains on two hardware queues do not overlap for free.  Two groups start to pay once each
-    // is big enough to be bandwidth-bound (64: 2 x 32 1697 vs 1661; 96: 2 x 48 1946 vs 1860; 128: 2 x 64 2019 vs 1896), three
-    // from ~150 (160: 3 x 53 = 2 x 80).  A small model wants the second group earlier (base, 32 chunks: 2 x 16 +10 %), hence
-    // the threshold of 32.  A host that SETS a lane count (wm_set_lanes n > 1) asks for n groups in flight whenever there are
-    // 8 chunks for each -- the rounds-1-4 rule, and what keeps the lanes under test at small sizes.
-    const bool explicit_lanes = ctx->max_lanes > 0;
-    const int L = ctx->prof.on ? 1 : (explicit_lanes ? ctx->max_lanes : lane_limit());
-    const int solo = g_wm_tuning.lane_solo_cus;   // probes only (0 in the product)
-    const int N = src.n_cand;   // candidates per row: tokens_out [B][N][max_new], a decode group holds whole rows
-    int parts = (ctx->prof.on || solo || ctx->no_cu_masks || N > 1) ? 0 : wm_lane_parts(B, L, explicit_lanes, D.n_text_state, D.n_text_layer);
-    if (parts) {
-        // the sub-chip lanes of this partition, created on first use.  A device / driver that refuses CU-masked streams (a
-        // partitioned GPU, an older KFD) is not an error: the call falls back to the unmasked policy, once and for all
-        std::vector<wm_ctx *> &pl = ctx->part_lanes[parts - 2];
-        while ((int)pl.size() < parts) {
-            wm_ctx *c = nullptr;
-            const int k = (int)pl.size();
-            if (wm_clone_cus(ctx, k * 32 / parts, (k + 1) * 32 / parts, &c) != WM_OK) {   // 16 + 16, or 10 + 11 + 11 CUs of every XCD
-                ctx->no_cu_masks = true;
-                parts = 0;
-                break;
-            }
-            pl.push_back(c);
-        }
-        WM_TRY(wm_ctx_make_current(ctx));
-    }
-    // group g: rows (a candidate call: windows) [grp_b0[g], grp_b0[g] + grp_cg[g]) of the call.  (Sub-chip parts stay off for
-    // candidate calls: not measured.)
-    std::vector<int> grp_b0, grp_cg;
-    int G;
-    if (N > 1) {
-        G = wm_cand_groups(B, N, L, explicit_lanes, grp_b0, grp_cg);
-    } else {
-        G = parts ? parts : wm_group_count(B, L, explicit_lanes, g_wm_tuning.group_chunks);
-        wm_balanced_cut(B, G, grp_b0, grp_cg);
-    }
-    const int n_lanes = solo ? 1 : (parts ? parts : (G < L ? G : L));
-    wm_ctx *solo_ctx = nullptr;
-    if (solo) {
-        WM_REQUIRE(solo >= 1 && solo <= 31, WM_ERR_INVALID, "lane_solo_cus: 1 .. 31 CUs per XCD");
-        wm_ctx *&c = ctx->solo_lanes[solo];
-        if (!c) WM_TRY(wm_clone_cus(ctx, 0, solo, &c));
-        solo_ctx = c;
-    } else if (!parts) {
-        while ((int)ctx->lanes.size() < n_lanes - 1) {
-            wm_ctx *c = nullptr;
-            WM_TRY(wm_clone(ctx, &c));
-            ctx->lanes.push_back(c);
-        }
-    }
-    std::vector<LaneJob> jobs(n_lanes);
-    for (int l = 0; l < n_lanes; ++l) {
-        jobs[l].c = solo_ctx ? solo_ctx : parts ? ctx->part_lanes[parts - 2][l] : (l == 0 ? ctx : ctx->lanes[l - 1]);
-        for (auto &e : jobs[l].ev) WM_HIP(hipEventCreate(&e));
-        if (stop.on)
-            for (auto &e : jobs[l].burst_ev) WM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
-    // (a ragged call: a group's prompt positions are its own longest prompt, LaneJob::P; n_prompt is the call's longest)
-    auto n_steps = [&](const LaneJob &j) { return j.P + max_new - 1; };
-    // decodes in flight on this device (this call included): other lanes of this call, other contexts' calls
-    struct ActiveGuard {
-        std::atomic<int> &n;
-        explicit ActiveGuard(std::atomic<int> &a) : n(a) { n.fetch_add(1, std::memory_order_relaxed); }
-        ~ActiveGuard() { n.fetch_sub(1, std::memory_order_relaxed); }
-    } active_guard(g_wm_active_decodes[ctx->device & 63]);
-    int next_group = 0, groups_done = 0;
-    while (groups_done < G) {
-        bool progress = false;
-        for (int l = 0; l < n_lanes; ++l) {
-            LaneJob &j = jobs[l];
-            WM_TRY(wm_ctx_make_current(j.c));
-            if (j.state == LaneJob::IDLE) {
-                if (next_group >= G) continue;
-                const int g = next_group++;
-                j.Cg = grp_cg[g];
-                j.b0 = grp_b0[g];
-                j.Bg = j.Cg * N;
-                j.t = 0; j.bursts = 0; j.stopped = false;
-                j.P = n_prompt;
-                if (src.prompt_len) j.P = *std::max_element(src.prompt_len + j.b0, src.prompt_len + j.b0 + j.Cg);
-                j.bpar.max_cand = src.max_cand; j.bpar.max_new = max_new; j.bpar.eot = eot; j.bpar.pad = eot >= 0 ? eot : 0;
-                WM_TRY(lane_prefill(j, src, j.P, mem, stop, xc));
-                if (use_graph) WM_TRY(lane_graph(j, j.P));
-                j.state = LaneJob::DECODING;
-                progress = true;
-                continue;   // the other lanes get their prefill before anyone's first burst
-            }
-            if (j.state == LaneJob::DECODING) {
-                if (stop.on && j.bursts >= 2 && !j.stopped) {
-                    // stay at most two bursts ahead of the GPU: burst (bursts - 2) must have finished, and its live count
-                    // says whether there is anything left to decode
-                    const int slot = (j.bursts - 2) % WM_NLIVE_RING;
-                    const hipError_t q = hipEventQuery(j.burst_ev[slot]);
-                    if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }   // "not ready" is not an error to keep
-                    WM_HIP(q);
-                    if (j.c->model->h_nlive[slot] == 0) j.stopped = true;
-                }
-                if (j.t < n_steps(j) && !j.stopped) {
-                    // does this burst share the chip?  other lanes of this call still decoding, or other calls in flight
-                    int busy = 0;
-                    for (int o = 0; o < n_lanes; ++o) busy += jobs[o].state == LaneJob::DECODING && jobs[o].t < n_steps(jobs[o]) && !jobs[o].stopped;
-                    // (sub-chip lanes own their CUs: the other lanes of THIS call do not make the chip "shared")
-                    const bool shared = (busy > 1 && !parts) || g_wm_active_decodes[ctx->device & 63].load(std::memory_order_relaxed) > 1;
-                    WM_TRY(lane_burst(j, j.P, n_steps(j), use_graph, shared));
-                    progress = true;
-                    continue;
-                }
-                // everything enqueued (or nothing left to decode): fetch the token streams
-                WM_HIP(hipEventRecord(j.ev[3], j.c->stream));
-                j.gen.resize((size_t)max_new * j.Bg);  // dseq[P + i][b]
-                WM_HIP(hipMemcpyAsync(j.gen.data(), j.c->model->dseq + (size_t)j.P * j.Bg, j.gen.size() * 4,
-                                      hipMemcpyDeviceToHost, j.c->stream));
-                if (xc.logprobs && !src.beam) {   // [gi][b], laid out like dseq
-                    j.lp.resize((size_t)max_new * j.Bg);
-                    WM_HIP(hipMemcpyAsync(j.lp.data(), j.c->model->dx_logprob, j.lp.size() * 4, hipMemcpyDeviceToHost,
-                                          j.c->stream));
-                }
-                if (xc.no_speech) {
-                    j.ns.resize(j.Bg);
-                    WM_HIP(hipMemcpyAsync(j.ns.data(), j.c->model->dx_nospeech, j.ns.size() * 4, hipMemcpyDeviceToHost,
-                                          j.c->stream));
-                }
-                if (src.beam) WM_TRY(beam_fetch(j, max_new, src.trace != nullptr));
-                j.state = LaneJob::DRAINING;
-                progress = true;
-                continue;
-            }
-            // DRAINING: a decode group runs for seconds -- poll instead of spinning in hipStreamSynchronize, so that the
-            // host threads of the other lanes / ranks (one process per GPU, several contexts each) keep their cores
-            const hipError_t q = hipStreamQuery(j.c->stream);
-            if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
-            WM_HIP(q);
-            WM_HIP(hipStreamSynchronize(j.c->stream));
-            if (src.beam) {
-                j.c->model->beam_trace_on = false;
-                beam_drain(j, src, max_new, eot, tokens_out, lens_out, xc.logprobs, xc.no_speech);
-            }
-            for (int b = 0; b < (src.beam ? 0 : j.Bg); ++b) {   // [gi][row] -> [row of the call][candidate][gi]
-                const int w = j.b0 + b / N;            // row of the call
-                const size_t o = (size_t)j.b0 * N + b; // its candidate's output row
-                int len = max_new;
-                if (stop.budgets && stop.budgets[w] < len) len = stop.budgets[w];
-                for (int i = 0; i < len; ++i)
-                    if (eot >= 0 && j.gen[(size_t)i * j.Bg + b] == eot) { len = i + 1; break; }
-                for (int i = 0; i < max_new; ++i)
-                    tokens_out[o * max_new + i] = i < len ? j.gen[(size_t)i * j.Bg + b] : eot;
-                lens_out[o] = len;
-                if (xc.logprobs)   // the token that stops a chunk has its log-prob; nothing after it
-                    for (int i = 0; i < max_new; ++i)
-                        xc.logprobs[o * max_new + i] = i < len ? j.lp[(size_t)i * j.Bg + b] : 0.f;
-                if (xc.no_speech && b % N == 0) xc.no_speech[w] = j.ns[b];   // (candidates: candidate 0's)
-            }
-            float ms;
-            for (int i = 0; i < 3; ++i)   // (a window set: [0] the gather, no encoder stage)
-                if (!(src.windows && i == 1) && hipEventElapsedTime(&ms, j.ev[i], j.ev[i + 1]) == hipSuccess) j.stage_sum[i] += ms;
-            j.state = LaneJob::IDLE;
-            ++groups_done;
-            progress = true;
-        }
-        if (!progress) usleep(100);
-    }
-    for (int l = 0; l < n_lanes; ++l)   // lanes overlap: the busiest lane per stage
-        for (int i = 0; i < 3; ++i)
-            if (jobs[l].stage_sum[i] > ctx->stage_ms[i]) ctx->stage_ms[i] = jobs[l].stage_sum[i];
-    return WM_OK;
-}
 
 // ---------------------------------------------------------------- word-level timestamps
 // openai-whisper's find_alignment (whisper/timing.py): a teacher-forced decoder pass that captures the alignment heads'
@@ -1475,7 +413,7 @@ struct AlignCall : WmAudioSrc {
 };
 
 // one decode group: chunks [b0, b0 + Bg) of the call
-int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4]) {
+int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, const WmEvents<4> &ev) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     const int S = c.n_sot, J = (int)c.hl.size(), n_ld = c.max_text + 1, V = D.n_vocab;
@@ -1515,10 +453,7 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
         }
     }
     for (int j = 0; j < J; ++j) { hint[4 * Bg + j] = c.hl[j]; hint[4 * Bg + J + j] = c.hh[j]; }
-    struct StreamFence {   // error paths: no copy from seq / hint may outlive them
-        hipStream_t s;
-        ~StreamFence() { (void)hipStreamSynchronize(s); }
-    } fence{ctx->stream};
+    WmStreamFence fence{ctx->stream};   // error paths: no copy from seq / hint may outlive them
     // decode state, then the front end -> encoder -> cross K/V of the group
     WM_TRY(wm_model_decode_begin(ctx, Bg));
     WM_HIP(hipMemcpyAsync(m->dseq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1528,9 +463,9 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
     WM_TRY(wm_model_set_pos(ctx, 0));
     WM_TRY(wm_model_reserve(ctx, Bg));
     const void *d_pcm;
-    WM_TRY(stage_pcm(ctx, c, b0, Bg, c.mem, &d_pcm));
+    WM_TRY(wm_stage_pcm(ctx, c, b0, Bg, c.mem, &d_pcm));
     WM_HIP(hipEventRecord(ev[0], ctx->stream));
-    WM_TRY(stage_cross_kv(ctx, c, b0, Bg, c.mem, d_pcm, win, xrows, nullptr));
+    WM_TRY(wm_stage_cross_kv(ctx, c, b0, Bg, c.mem, d_pcm, win, xrows, nullptr));
     WM_HIP(hipEventRecord(ev[1], ctx->stream));
     // teacher-forced pass: every position is prompt, the alignment layers leave their queries in the capture buffer
     std::vector<WmAlignLayer> layers(D.n_text_layer);
@@ -1587,9 +522,7 @@ int align_group(wm_ctx *ctx, const AlignCall &c, int b0, int Bg, hipEvent_t ev[4
         WM_HIP(hipMemcpyAsync(c.dbg_matrix + (size_t)b0 * n_ld * 1500, x, (size_t)Bg * n_ld * 1500 * 4, hipMemcpyDeviceToHost,
                               ctx->stream));
     WM_HIP(hipStreamSynchronize(ctx->stream));
-    float ms;
-    for (int i = 0; i < 3; ++i)
-        if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) ctx->stage_ms[i] += ms;
+    wm_add_stage_ms(ev.e, 3, false, ctx->stage_ms);
     return WM_OK;
 }
 }  // namespace
@@ -1623,7 +556,7 @@ static int align_impl(wm_ctx *ctx, AlignCall &c, int B, int32_t no_timestamps, i
         if (n_frames)
             WM_REQUIRE(n_frames[b] >= 2 && n_frames[b] <= WM_N_FRAMES, WM_ERR_INVALID, "align: n_frames[%d] = %d outside [2, %d]",
                        b, n_frames[b], WM_N_FRAMES);
-        if (c.mel) WM_TRY(check_window(c, b, "align: "));
+        if (c.mel) WM_TRY(wm_check_window(c, b, "align: "));
     }
     if (m->align_l.empty()) {   // openai-whisper's default: every head of the last half of the decoder layers
         for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)
@@ -1645,14 +578,10 @@ static int align_impl(wm_ctx *ctx, AlignCall &c, int B, int32_t no_timestamps, i
     const size_t per_chunk = T * J * (64 * 4 + 8) + J * 1500 * 8 + (size_t)n_ld * 1500 * 4;
     const int G = (int)std::max<size_t>(1, std::min<size_t>(WM_DEC_MAXB, kAlignCaptureBudget / per_chunk));
     ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int rc = WM_OK;
-    for (auto &e : ev)
-        if (rc == WM_OK && hipEventCreate(&e) != hipSuccess) { wm_set_error("hipEventCreate failed"); rc = WM_ERR_HIP; }
+    WmEvents<4> ev;
+    WmStreamFence fence{ctx->stream};   // drained before the events go, whatever a group returned
+    int rc = ev.create();
     for (int b0 = 0; b0 < B && rc == WM_OK; b0 += G) rc = align_group(ctx, c, b0, std::min(G, B - b0), ev);
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto &e : ev)
-        if (e) (void)hipEventDestroy(e);
     return rc;
 }
 
@@ -1696,14 +625,14 @@ extern "C" int wm_align_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_ba
 
 // ---------------------------------------------------------------- window sets
 // wm_windows_encode runs the encoder and the cross-K/V projection of W windows once and keeps the result; the
-// wm_*_windows calls are the mel calls with that result copied into the lane (stage_cross_kv) instead of computed.
+// wm_*_windows calls are the mel calls with that result copied into the lane (wm_stage_cross_kv) instead of computed.
 static int windows_cross_kv(wm_ctx *ctx, const wm_windows *set, const int32_t *rows, int B, std::vector<int32_t> &map) {
     WmAudioSrc a;
     a.windows = true; a.set = set; a.rows = rows;
-    WM_TRY(check_set_rows(ctx, a, B, "detect_language: "));
+    WM_TRY(wm_check_set_rows(ctx, a, B, "detect_language: "));
     WM_TRY(wm_model_reserve(ctx, B));
     std::vector<WmMelWin> win;
-    return stage_cross_kv(ctx, a, 0, B, WM_MEM_HOST, nullptr, win, map, nullptr);
+    return wm_stage_cross_kv(ctx, a, 0, B, WM_MEM_HOST, nullptr, win, map, nullptr);
 }
 
 extern "C" int wm_windows_encode(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
@@ -1715,21 +644,17 @@ extern "C" int wm_windows_encode(wm_ctx *ctx, const float *mel, const int64_t *m
     WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
     WmAudioSrc a;
     a.mel = mel; a.mel_base = mel_base; a.mel_len = mel_len; a.seek = seek; a.n_frames = n_frames;
-    WM_TRY(check_src_pointers(a));
+    WM_TRY(wm_check_src_pointers(a));
     WM_REQUIRE(W >= 1, WM_ERR_INVALID, "W < 1");
-    for (int b = 0; b < W; ++b) WM_TRY(check_window(a, b, "windows_encode: "));
+    for (int b = 0; b < W; ++b) WM_TRY(wm_check_window(a, b, "windows_encode: "));
     const wm_dims &D = m->dims;
     const long slab = (long)D.n_text_head * 1500 * 64;
     const int L2 = 2 * D.n_text_layer;
     struct Owner {   // nothing leaks on any way out
         wm_windows *w = nullptr;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        ~Owner() {
-            for (auto &e : ev)
-                if (e) (void)hipEventDestroy(e);
-            if (w) wm_windows_free(w);
-        }
+        ~Owner() { if (w) wm_windows_free(w); }
     } own;
+    WmEvents<3> ev;
     own.w = new wm_windows();
     wm_windows *w = own.w;
     w->device = ctx->device; w->dims = D; w->weights = m->tok_emb; w->W = W;
@@ -1742,25 +667,20 @@ extern "C" int wm_windows_encode(wm_ctx *ctx, const float *mel, const int64_t *m
         wm_set_error("windows_encode: no device memory for %d windows (%zu bytes): %s", W, w->bytes, hipGetErrorString(me));
         return me == hipErrorOutOfMemory ? WM_ERR_NOMEM : WM_ERR_HIP;
     }
-    for (auto &e : own.ev) WM_HIP(hipEventCreate(&e));
+    WM_TRY(ev.create());
     ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
     std::vector<WmMelWin> win;
     std::vector<int32_t> map;
-    struct StreamFence {   // error paths: no copy from win may outlive it
-        hipStream_t s;
-        ~StreamFence() { (void)hipStreamSynchronize(s); }
-    } fence{ctx->stream};
+    WmStreamFence fence{ctx->stream};   // error paths: no copy from win may outlive it
     for (int b0 = 0; b0 < W; b0 += WM_DEC_MAXB) {
         const int Bg = std::min(WM_DEC_MAXB, W - b0);
         WM_TRY(wm_model_reserve(ctx, Bg));
-        WM_HIP(hipEventRecord(own.ev[0], ctx->stream));
-        WM_TRY(stage_cross_kv(ctx, a, b0, Bg, mem, nullptr, win, map, own.ev[1]));
+        WM_HIP(hipEventRecord(ev[0], ctx->stream));
+        WM_TRY(wm_stage_cross_kv(ctx, a, b0, Bg, mem, nullptr, win, map, ev[1]));
         WM_TRY(wm_xkv_rows(ctx, m->xkv, Bg, w->store, nullptr, b0, Bg, L2, slab, true));
-        WM_HIP(hipEventRecord(own.ev[2], ctx->stream));
+        WM_HIP(hipEventRecord(ev[2], ctx->stream));
         WM_HIP(hipStreamSynchronize(ctx->stream));   // fences win; the next group overwrites m->xkv
-        float ms;
-        for (int i = 0; i < 2; ++i)
-            if (hipEventElapsedTime(&ms, own.ev[i], own.ev[i + 1]) == hipSuccess) ctx->stage_ms[i] += ms;
+        wm_add_stage_ms(ev.e, 2, false, ctx->stage_ms);
     }
     *out = w;
     own.w = nullptr;
@@ -1794,7 +714,7 @@ extern "C" int wm_align_windows(wm_ctx *ctx, const wm_windows *w, const int32_t 
     WM_REQUIRE(sot_seqs && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
     WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
     c.windows = true; c.set = w; c.rows = rows; c.mem = WM_MEM_HOST;
-    WM_TRY(check_set_rows(ctx, c, B, "align: "));
+    WM_TRY(wm_check_set_rows(ctx, c, B, "align: "));
     std::vector<int32_t> nf(B);
     for (int b = 0; b < B; ++b) nf[b] = w->n_frames[rows ? rows[b] : b];
     c.sot_seq = sot_seqs; c.sot_stride = n_sot; c.text_tokens = text_tokens; c.n_text = n_text; c.n_frames = nf.data();

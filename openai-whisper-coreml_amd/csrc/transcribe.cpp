@@ -1,0 +1,879 @@
+// transcribe.cpp -- the transcribe calls of the C ABI (include/whisper_mi355x.h): wm_transcribe_greedy, wm_transcribe,
+// wm_transcribe_mel, wm_transcribe_mel_ragged, wm_transcribe_mel_best_of, wm_transcribe_windows, wm_transcribe_mel_beam and
+// wm_transcribe_windows_beam.  Each entry point fills one request value (TxCall) and hands it to tx_transcribe: budgets, the
+// entry's own checks, validation (tx_validate), the lane plan (tx_plan.h), the lanes (tx_lanes), the scheduler (tx_run: lane_start /
+// lane_advance / lane_fetch / lane_finish), the ranking step of a best-of or beam call.  DESIGN.md section 4d.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "beam.h"
+#include "call_src.h"
+#include "model.h"
+#include "tx_plan.h"
+
+
+// One batch's decode is a chain of ~260 dependent launches per position and is bound by launch latency, not by
+// HBM (NOTEBOOK.md section 4), so a call with more chunks than one decode group is spread over LANES: weight-sharing
+// clones of the context (wm_clone), each with its own stream, activations, KV caches and decode graphs.  The
+// single host thread drives the lanes as a small non-blocking scheduler: a lane takes the next decode group as soon as
+// it has finished its previous one, positions are enqueued in BURSTS (one hipGraph of WM_BURST consecutive positions --
+// the arg-max kernel advances the device-side position, so consecutive positions do not depend on the host), and with
+// early stop on (eot >= 0 or per-chunk token budgets) a lane stays at most two bursts ahead of the GPU and stops
+// enqueuing once the device reports that no sequence of its group is live any more.
+namespace {
+int lane_limit() {
+    static const int n = [] {
+        const char *e = getenv("WM_LANES");
+        const int v = e ? atoi(e) : 3;
+        return v < 1 ? 1 : (v > 8 ? 8 : v);
+    }();
+    return n;
+}
+
+int burst_len() {
+    static const int n = [] {
+        const char *e = getenv("WM_BURST");
+        const int v = e ? atoi(e) : 8;
+        return v < 1 ? 1 : (v > 32 ? 32 : v);
+    }();
+    return n;
+}
+
+struct LaneJob {
+    enum State { IDLE, DECODING, DRAINING };
+    wm_ctx *c = nullptr;
+    int b0 = 0, Bg = 0;   // first row of the call (a candidate call: first WINDOW) and decoder rows of the group
+    int Cg = 0;           // its encoder rows: Bg, or (candidates) Bg / n_cand windows -- row c * n_cand + s is candidate s of window c
+    int P = 0;          // prompt positions of the group (a ragged call: the longest prompt among ITS rows)
+    WmDecodeMode mode;  // of the group's decode (xattn_shared: decided burst by burst), filled by lane_prefill
+    int gset = -1;      // its graph set in the lane's WmModel::graph_sets (lane_graph)
+    State state = IDLE;
+    int t = 0;          // decoder positions enqueued so far
+    int bursts = 0;     // bursts enqueued so far
+    bool stopped = false;   // the device reported zero live rows
+    WmEvents<4> ev;                      // prefill begun, input staged, cross-K/V ready, everything enqueued
+    WmEvents<WM_NLIVE_RING> burst_ev;    // (early stop) burst i has finished: its live count can be read
+    TxGroupTables tab;             // its prompt table, offsets, budgets and sample ids (tx_plan.h)
+    std::vector<int32_t> gen;      // its fetched token stream [max_new][Bg]
+    WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
+    WmRepPar rpar = {};            // its repetition rules (likewise)
+    std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
+    std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
+    std::vector<int32_t> xrows;    // its rows of the window set (wm_transcribe_windows)
+    // a beam group (wm_transcribe_mel_beam): its parameters and window budgets (sources of async uploads) and what a drain
+    // fetches: the state in front of the finished records, the finished tokens / log-probs of its windows, the debug trace
+    WmBeamPar bpar = {};
+    std::vector<int32_t> bbud, bfin_tok;
+    std::vector<char> bstate;
+    std::vector<float> bfin_lp, btrace;
+    float stage_sum[3] = {0.f, 0.f, 0.f};
+    WmStreamFence fence;   // last member, first to go: nothing in flight outlives the tables, the events or the fetched streams
+};
+
+// A transcribe call: its rows (PCM chunks, mel windows or the rows of a window set), their prompts, what decodes them
+// (arg-max / sampling, best_of candidates, beams) and where the results go.
+struct TxCall {
+    enum Entry { PLAIN, MEL, RAGGED, BEST_OF, BEAM } entry = PLAIN;   // whose own checks run first
+    WmAudioSrc src;
+    TxPrompts prompts;
+    int n_prompt = 0;   // the prompt length of a uniform call (a ragged call: TxCfg::n_prompt, found by validation)
+    int n_cand = 1;     // candidates per row (wm_transcribe_mel_best_of): every row decodes n_cand times over ONE encoder pass
+    // wm_transcribe_mel_beam: the n_cand rows of a window are its BEAMS (n_cand = beam width, 1 included)
+    bool beam = false;
+    int max_cand = 0;
+    float length_penalty = NAN;   // of the ranking step
+    int B = 0, max_new = 0;
+    int32_t eot = -1;
+    const wm_decode_opts *opts = nullptr;
+    int32_t *tokens_out = nullptr, *lens_out = nullptr;   // [B][S][max_new], [B][S]; S = n_cand, a beam call: max(n_cand, max_cand)
+    float *logprobs_out = nullptr;    // like tokens_out, nullable
+    float *no_speech_out = nullptr;   // [B], nullable
+    int32_t *best_out = nullptr;      // [B], nullable: the ranking step's choice
+    int32_t *n_hyp = nullptr;   // beam: [B]
+    float *sums = nullptr;      // beam: [B][S]
+    float *trace = nullptr;     // beam, debug library: [B][max_new][n_cand][WM_BEAM_TRACE] (null in the product)
+    wm_mem mem = WM_MEM_HOST;
+};
+
+struct StopCfg {
+    bool on = false;
+    int32_t eot = -1;
+    const int32_t *budgets = nullptr;  // [B] of the call, already clamped to max_new (null: none)
+};
+
+// wm_transcribe's extended decode: off for wm_transcribe_greedy and for a wm_transcribe call that wants neither outputs nor
+// sampling (then it IS the greedy decode: same graphs, same kernels)
+struct XCfg {
+    bool on = false;
+    WmXPar par = {};               // chunk0 / n_prompt filled per group
+    float *logprobs = nullptr;     // [B][max_new] host, nullable
+    float *no_speech = nullptr;    // [B] host, nullable
+};
+
+// what validation makes of a call
+struct TxCfg {
+    int n_prompt = 0;   // the call's longest prompt
+    StopCfg stop;
+    XCfg xc;
+    bool use_graph = false;
+};
+
+// the tokens row `b` of the call may generate
+int stop_budget(const StopCfg &stop, int b, int max_new) { return stop.budgets && stop.budgets[b] < max_new ? stop.budgets[b] : max_new; }
+
+// front end -> encoder -> cross K/V -> prompt upload -> first embedding, all enqueued on the lane's stream
+int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
+    wm_ctx *c = j.c;
+    WmModel *m = c->model;
+    const StopCfg &stop = cfg.stop;
+    const XCfg &xc = cfg.xc;
+    const int Bg = j.Bg, Cg = j.Cg, N = call.n_cand;   // decoder rows, encoder rows (windows), candidates per window
+    // the mode of this group's decode: the lane's own context settings and the call's options, in this one place
+    j.mode = WmDecodeMode();
+    j.mode.mask = m->mask_on; j.mode.ts = m->ts_on; j.mode.x = xc.on; j.mode.off = call.prompts.len != nullptr;
+    j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
+    j.mode.n_cand = N;
+    j.mode.beam = call.beam ? N : 0;
+    j.mode.rep = m->rep_on;   // (tx_validate turns the extended decode on with them)
+    // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
+    j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
+    const void *d_pcm;
+    WM_TRY(wm_stage_pcm(c, call.src, j.b0, Cg, call.mem, &d_pcm));
+    // decode state first (prompt tokens, position 0): a pageable H2D copy may wait for the stream to drain, so it is issued
+    // while the lane is still idle
+    WM_TRY(wm_model_decode_begin(c, Bg));
+    if (call.prompts.len) WM_HIP(hipMemcpyAsync(m->doff, j.tab.off.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
+    WM_HIP(hipMemcpyAsync(m->dseq, j.tab.pr.data(), j.tab.pr.size() * 4, hipMemcpyHostToDevice, c->stream));
+    WM_TRY(wm_model_set_pos(c, 0));
+    // early-stop state of this group: done flags, live list, per-row budgets (kernel arguments of the decode graphs)
+    if (stop.on) {
+        if (j.mode.budget) WM_HIP(hipMemcpyAsync(m->dbudget, j.tab.bud.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
+        WM_TRY(wm_stop_init(c, wm_model_stop_dev(m, j.mode), Bg));
+    }
+    // extended decode: seed, 1/T, the sot position and the group's first call index live in device memory, so the
+    // captured graphs replay for any of them
+    if (xc.on) {
+        j.xpar = xc.par;
+        j.xpar.chunk0 = j.b0;
+        j.xpar.n_prompt = j.P;
+        if (call.prompts.len && xc.no_speech) j.xpar.sot_pos = j.P - call.prompts.sot_tail;   // the same distance from every row's end
+        j.xpar.ids_on = (call.prompts.sample_ids || N > 1) ? 1 : 0;
+        j.xpar.n_cand = N;
+        if (!j.tab.ids.empty()) WM_HIP(hipMemcpyAsync(m->dx_ids, j.tab.ids.data(), j.tab.ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+        WM_HIP(hipMemcpyAsync(m->dx_par, &j.xpar, sizeof(WmXPar), hipMemcpyHostToDevice, c->stream));
+    }
+
+    // repetition rules: penalty, its reciprocal, n and eot live in device memory too (the graph key holds `rep` alone)
+    if (j.mode.rep) {
+        WM_REQUIRE(xc.on, WM_ERR_STATE, "the repetition rules need the extended decode");
+        j.rpar.p = m->rep_p; j.rpar.inv_p = (float)(1.0 / (double)m->rep_p); j.rpar.n = m->rep_n; j.rpar.eot = m->rep_eot;
+        WM_HIP(hipMemcpyAsync(m->drep_par, &j.rpar, sizeof(WmRepPar), hipMemcpyHostToDevice, c->stream));
+    }
+    WM_TRY(wm_model_reserve(c, Cg));
+    if (N > 1) WM_TRY(wm_model_reserve_rows(c, Bg));
+    if (call.beam) {   // beam state: nothing finished, every sum 0; a window's budget is its own max_new
+        j.bbud.resize(Cg);
+        for (int w = 0; w < Cg; ++w) j.bbud[w] = stop_budget(stop, j.b0 + w, j.bpar.max_new);
+        m->beam_trace_on = call.trace != nullptr;
+        if (call.trace) {
+            const size_t bytes = (size_t)j.bpar.max_new * Bg * WM_BEAM_TRACE * 4;
+            WM_TRY(m->beam_trace.reserve(c->stream, bytes));
+            WM_HIP(hipMemsetAsync(m->beam_trace.p, 0, bytes, c->stream));
+        }
+        WM_TRY(wm_model_beam_begin(c, j.mode, Bg, Cg, &j.bpar, j.bbud.data()));
+    }
+    WM_HIP(hipEventRecord(j.ev[0], c->stream));
+    // 1. log-mel front end, or the caller's mel windows;  2. encoder + cross-attention K/V  (a window set: 1. the gather)
+    WM_TRY(wm_stage_cross_kv(c, call.src, j.b0, Cg, call.mem, d_pcm, j.win, j.xrows, j.ev[1]));
+
+    WM_HIP(hipEventRecord(j.ev[2], c->stream));
+    // 3. embedding of the first prompt token (+ the initial timestamp-rule state)
+    WM_TRY(wm_model_embed_first(c, Bg, j.mode));
+    if (j.mode.ts) WM_TRY(wm_ts_init(c, wm_model_ts_dev(m), Bg));
+    return WM_OK;
+}
+
+// One decoder position = 8 launches per layer + logits + arg-max/embed (which writes the next token, embeds the
+// next position and advances *dpos).  Nothing in it depends on host state, so it is captured ONCE into a
+// hipGraph per lane and replayed for every position -- and `burst` consecutive positions are captured as one more graph.
+// gen (a beam group's generating positions): the step also stores the f32 logits and the beam kernels close it.
+int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) {
+    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen, 0, j.c->model->dims.n_vocab - 1, nullptr, mode, n_prompt));
+    if (gen) return wm_model_beam_close(j.c, j.Bg, n_prompt, mode);
+    return wm_model_close_step(j.c, j.Bg, n_prompt, true, nullptr, 0, mode);
+}
+
+int capture_positions(LaneJob &j, const WmDecodeMode &mode, int n_prompt, int n_pos, bool gen, WmGraph *out) {
+    char what[48];
+    snprintf(what, sizeof(what), "the %d-position decode graph", n_pos);
+    return wm_capture_graph(j.c->stream, out, what, [&]() -> int {
+        for (int i = 0; i < n_pos; ++i) WM_TRY(lane_position(j, mode, n_prompt, gen));
+        return WM_OK;
+    });
+}
+
+// Select (creating it if needed) the graph set of the group's decode shape and mode.  The graphs themselves are captured
+// on first use, per sharing mode, by lane_burst.
+int lane_graph(LaneJob &j, int n_prompt) {
+    WmModel *m = j.c->model;
+    int cur = -1;
+    for (size_t i = 0; i < m->graph_sets.size(); ++i) {
+        const WmModel::GraphSet &g = m->graph_sets[i];
+        if (g.B == j.Bg && g.n_prompt == n_prompt && g.cap_b == m->cap_b && g.mode == j.mode) cur = (int)i;
+    }
+    if (cur < 0) {
+        if ((int)m->graph_sets.size() >= WmModel::kMaxGraphSets) {   // evict the least recently used shape
+            size_t old = 0;
+            for (size_t i = 1; i < m->graph_sets.size(); ++i)
+                if (m->graph_sets[i].stamp < m->graph_sets[old].stamp) old = i;
+            m->graph_sets[old].destroy();
+            m->graph_sets.erase(m->graph_sets.begin() + (long)old);
+        }
+        WmModel::GraphSet g;
+        g.B = j.Bg; g.n_prompt = n_prompt; g.cap_b = m->cap_b; g.mode = j.mode;
+        m->graph_sets.push_back(g);
+        cur = (int)m->graph_sets.size() - 1;
+    }
+    j.gset = cur;
+    m->graph_sets[cur].stamp = ++m->graph_clock;
+    return WM_OK;
+}
+
+// a beam group has enqueued everything: fetch its beam state behind the token streams
+int beam_fetch(LaneJob &j, int max_new, bool trace) {
+    WmModel *m = j.c->model;
+    WmBeamDev bm;
+    WM_TRY(wm_model_beam_dev(j.c, j.mode, &bm));
+    j.lp.resize((size_t)max_new * j.Bg);   // the live beams' log-probs [gi][row], whether or not the caller wants them
+    WM_HIP(hipMemcpyAsync(j.lp.data(), m->dx_logprob, j.lp.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    j.bstate.resize(wm_model_beam_state_bytes(m));
+    WM_HIP(hipMemcpyAsync(j.bstate.data(), m->beam_ws.p, j.bstate.size(), hipMemcpyDeviceToHost, j.c->stream));
+    const size_t nf = (size_t)j.Cg * WM_MAX_BEAM_HYPS * bm.n_ctx;
+    j.bfin_tok.resize(nf);
+    j.bfin_lp.resize(nf);
+    WM_HIP(hipMemcpyAsync(j.bfin_tok.data(), bm.fin_tok, nf * 4, hipMemcpyDeviceToHost, j.c->stream));
+    WM_HIP(hipMemcpyAsync(j.bfin_lp.data(), bm.fin_lp, nf * 4, hipMemcpyDeviceToHost, j.c->stream));
+    if (trace) {
+        j.btrace.resize((size_t)max_new * j.Bg * WM_BEAM_TRACE);
+        WM_HIP(hipMemcpyAsync(j.btrace.data(), m->beam_trace.p, j.btrace.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    }
+    return WM_OK;
+}
+
+// ... and, once it has arrived, write the windows' hypotheses: the finished ones in the order they finished, then (fewer
+// than N finished) the live beams by descending sum until there are N.  Output stride S = max(N, max_cand) per window.
+void beam_drain(const LaneJob &j, const TxCall &call) {
+    const int N = call.n_cand, S = std::max(N, call.max_cand), n_ctx = j.c->model->dims.n_text_ctx, max_new = call.max_new;
+    const int32_t eot = call.eot;
+    int32_t *tokens_out = call.tokens_out, *lens_out = call.lens_out;
+    float *logprobs_out = call.logprobs_out, *no_speech_out = call.no_speech_out;
+    // the device pointers of the state, as offsets into the fetched copy
+    WmBeamDev bm;
+    (void)wm_model_beam_dev(j.c, j.mode, &bm);
+    const char *dev0 = (const char *)j.c->model->beam_ws.p;
+    auto host = [&](const void *dev) { return j.bstate.data() + ((const char *)dev - dev0); };
+    const float *sum = (const float *)host(bm.sum), *fin_sum = (const float *)host(bm.fin_sum);
+    const int *fin_n = (const int *)host(bm.fin_n), *fin_len = (const int *)host(bm.fin_len), *wsteps = (const int *)host(bm.wsteps);
+    for (int w = 0; w < j.Cg; ++w) {
+        const int W = j.b0 + w;   // window of the call
+        int n_hyp = 0;
+        auto put = [&](const int32_t *tok, size_t tok_stride, const float *lp, size_t lp_stride, int len, float s) {
+            const size_t o = (size_t)W * S + n_hyp++;
+            for (int i = 0; i < max_new; ++i) {
+                tokens_out[o * max_new + i] = i < len ? tok[(size_t)i * tok_stride] : eot;
+                if (logprobs_out) logprobs_out[o * max_new + i] = i < len ? lp[(size_t)i * lp_stride] : 0.f;
+            }
+            lens_out[o] = len;
+            call.sums[o] = s;
+        };
+        for (int f = 0; f < fin_n[w]; ++f) {
+            const size_t base = ((size_t)w * WM_MAX_BEAM_HYPS + f) * n_ctx;
+            put(j.bfin_tok.data() + base, 1, j.bfin_lp.data() + base, 1, fin_len[w * WM_MAX_BEAM_HYPS + f], fin_sum[w * WM_MAX_BEAM_HYPS + f]);
+        }
+        if (n_hyp < N) {
+            int order[WM_MAX_BEAM];
+            const int n_live = wm_beam_fill_order(N, sum + (size_t)w * N, order);
+            for (int k = 0; k < n_live && n_hyp < N; ++k) {
+                const int b = w * N + order[k];
+                put(j.gen.data() + b, j.Bg, j.lp.data() + b, j.Bg, wsteps[w], sum[b]);
+            }
+        }
+        call.n_hyp[W] = n_hyp;
+        for (int h = n_hyp; h < S; ++h) {   // unused slots
+            const size_t o = (size_t)W * S + h;
+            for (int i = 0; i < max_new; ++i) {
+                tokens_out[o * max_new + i] = eot;
+                if (logprobs_out) logprobs_out[o * max_new + i] = 0.f;
+            }
+            lens_out[o] = 0;
+            call.sums[o] = -INFINITY;
+        }
+        if (no_speech_out) no_speech_out[W] = j.ns[(size_t)w * N];   // beam 0's
+        if (call.trace)     // [gi][row of the group] -> [window of the call][gi][beam]
+            for (int gi = 0; gi < max_new; ++gi)
+                memcpy(call.trace + (((size_t)W * max_new + gi) * N) * WM_BEAM_TRACE,
+                       j.btrace.data() + ((size_t)gi * j.Bg + (size_t)w * N) * WM_BEAM_TRACE, (size_t)N * WM_BEAM_TRACE * 4);
+    }
+}
+
+// enqueue the next burst of positions of a lane (<= burst_len(), up to the end of the sequence).  `shared`: other decode
+// groups are in flight on the device right now -- this burst's cross-attention launches are the short-lived shape.
+int lane_burst(LaneJob &j, int n_prompt, int n_steps, bool use_graph, bool shared) {
+    wm_ctx *c = j.c;
+    WmModel *m = c->model;
+    const int K = burst_len();
+    // a beam group: positions 0 .. n_prompt - 2 step through the prompt (the arg-max close), the others generate (the beam
+    // close); a burst stays on one side
+    const bool gen = j.mode.beam && j.t >= n_prompt - 1;
+    const int left = (j.mode.beam && !gen ? n_prompt - 1 : n_steps) - j.t;
+    const int k = left < K ? left : K;
+    const int sh = shared ? 1 : 0;
+    WmDecodeMode mode = j.mode;   // what every step of this burst, launched or captured, is handed
+    mode.xattn_shared = shared;
+    WmModel::GraphSet *g = use_graph ? &m->graph_sets[j.gset] : nullptr;
+    WmGraph *g1 = g ? (gen ? g->b1 : g->g1) : nullptr, *gk = g ? (gen ? g->bk : g->gk) : nullptr;
+    int *burst = g ? (gen ? g->bburst : g->burst) : nullptr;
+    if (use_graph && k == K && K > 1) {
+        if (!gk[sh].e || burst[sh] != K) {
+            WM_TRY(capture_positions(j, mode, n_prompt, K, gen, &gk[sh]));
+            burst[sh] = K;
+        }
+        WM_HIP(hipGraphLaunch(gk[sh].e, c->stream));
+    } else {
+        if (use_graph && !g1[sh].e) WM_TRY(capture_positions(j, mode, n_prompt, 1, gen, &g1[sh]));
+        for (int i = 0; i < k; ++i) {
+            if (use_graph) {
+                WM_HIP(hipGraphLaunch(g1[sh].e, c->stream));
+            } else {
+                WM_TRY(lane_position(j, mode, n_prompt, gen));
+            }
+        }
+    }
+    j.t += k;
+    if (j.mode.stop) {  // the live-row count after this burst, where the host can read it without touching the stream
+        const int slot = j.bursts % WM_NLIVE_RING;
+        WM_HIP(hipMemcpyAsync(m->h_nlive + slot, m->dnlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        WM_HIP(hipEventRecord(j.burst_ev[slot], c->stream));
+    }
+    ++j.bursts;
+    return WM_OK;
+}
+// ---------------------------------------------------------------- the entries' own checks, validation ----
+// The checks of an entry point's own arguments.  They run before the context is looked at: which error wins when several
+// apply is part of the ABI (tests/test_transcribe_errors_gpu.py).
+int entry_checks(const TxCall &call) {
+    const TxPrompts &p = call.prompts;
+    switch (call.entry) {
+    case TxCall::PLAIN:
+        break;
+    case TxCall::MEL:
+    case TxCall::RAGGED:
+        WM_REQUIRE(call.src.mel && call.src.mel_base && call.src.mel_len && call.src.seek && call.src.n_frames, WM_ERR_INVALID,
+                   "null mel / window pointer");
+        if (call.entry == TxCall::MEL) break;
+        WM_REQUIRE(p.len, WM_ERR_INVALID, "null prompt_len");
+        WM_REQUIRE(p.stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", p.stride);
+        break;
+    case TxCall::BEST_OF:
+    case TxCall::BEAM:
+        WM_TRY(wm_check_src_pointers(call.src));
+        if (call.beam) WM_REQUIRE(call.n_hyp && call.sums, WM_ERR_INVALID, "null n_hyp_out / sum_logprobs_out");
+        WM_REQUIRE(p.stride >= 1, WM_ERR_INVALID, "prompt_stride %d < 1", p.stride);
+        if (call.beam) {
+            WM_REQUIRE(call.n_cand >= 1 && call.n_cand <= WM_MAX_BEAM, WM_ERR_INVALID, "beam_size %d outside [1, %d]", call.n_cand,
+                       WM_MAX_BEAM);
+            WM_REQUIRE(call.max_cand >= 1 && call.max_cand <= WM_MAX_BEAM_HYPS, WM_ERR_INVALID, "max_candidates %d outside [1, %d]",
+                       call.max_cand, WM_MAX_BEAM_HYPS);
+        } else {
+            WM_REQUIRE(call.n_cand >= 1 && call.n_cand <= WM_MAX_BEST_OF, WM_ERR_INVALID, "best_of %d outside [1, %d]", call.n_cand,
+                       WM_MAX_BEST_OF);
+        }
+        WM_REQUIRE(std::isnan(call.length_penalty) || (call.length_penalty >= 0.f && call.length_penalty <= 1.f), WM_ERR_INVALID,
+                   "length_penalty must be NaN (none) or in [0, 1]");
+        WM_REQUIRE(call.B >= 1 && call.max_new >= 1, WM_ERR_INVALID, "B < 1 or max_new < 1");
+        break;
+    }
+    return WM_OK;
+}
+
+// The checks every transcribe call goes through, and what they make of it: the call's longest prompt, the early stop, the
+// extended decode.  budgets: the call's (wm_set_token_budgets), clamped to max_new here.  opts == null with both extra
+// outputs null is the greedy decode exactly.
+int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg) {
+    WmModel *m = ctx->model;
+    const WmAudioSrc &src = call.src;
+    const TxPrompts &p = call.prompts;
+    const int B = call.B, max_new = call.max_new;
+    WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
+    WM_REQUIRE((src.pcm || src.mel || src.windows) && p.prompt && call.tokens_out && call.lens_out, WM_ERR_INVALID, "null pointer");
+    WM_REQUIRE(src.mel || src.windows || src.pcm_dtype == WM_I16 || src.pcm_dtype == WM_F32 || src.pcm_dtype == WM_F64,
+               WM_ERR_INVALID, "bad pcm dtype");
+    WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");
+    if (src.mel)
+        for (int b = 0; b < B; ++b) WM_TRY(wm_check_window(src, b, ""));
+    if (src.windows) WM_TRY(wm_check_set_rows(ctx, src, B, ""));
+    const wm_dims &D = m->dims;
+    int n_prompt = call.n_prompt;
+    if (p.len) {   // ragged: the call's longest prompt
+        n_prompt = 0;
+        for (int b = 0; b < B; ++b) {
+            WM_REQUIRE(p.len[b] >= 1 && p.len[b] <= p.stride, WM_ERR_INVALID, "row %d: prompt_len %d outside [1, %d]", b, p.len[b],
+                       p.stride);
+            n_prompt = std::max(n_prompt, (int)p.len[b]);
+        }
+    }
+    cfg->n_prompt = n_prompt;
+    WM_REQUIRE(n_prompt >= 1 && max_new >= 1 && n_prompt + max_new <= D.n_text_ctx, WM_ERR_INVALID,
+               "prompt (%d) + new tokens (%d) must fit the %d-token context", n_prompt, max_new, D.n_text_ctx);
+    for (int b = 0; b < (p.stride ? B : 1); ++b)
+        for (int i = 0; i < (p.len ? p.len[b] : n_prompt); ++i) {
+            const int32_t t = p.prompt[(size_t)b * p.stride + i];
+            WM_REQUIRE(t >= 0 && t < D.n_vocab, WM_ERR_INVALID, "prompt token %d out of range", t);
+        }
+    WM_REQUIRE(call.eot < D.n_vocab, WM_ERR_INVALID, "eot %d outside the vocabulary", call.eot);
+    WM_REQUIRE(budgets.empty() || (int)budgets.size() == B, WM_ERR_INVALID,
+               "token budgets were set for %d chunks, the call has %d", (int)budgets.size(), B);
+    for (auto &b : budgets) b = b > max_new ? max_new : b;
+    XCfg &xc = cfg->xc;
+    const wm_decode_opts *opts = call.opts;
+    const float T = opts ? opts->temperature : 0.f;
+    const int32_t ns_tok = opts ? opts->no_speech_token : -1;
+    // (a ragged call places <|startoftranscript|> by sot_tail; opts->sot_index is not read)
+    const int32_t sot_index = (opts && !p.len) ? opts->sot_index : 0;
+    if (p.len && call.no_speech_out) {
+        const int shortest = *std::min_element(p.len, p.len + B);
+        WM_REQUIRE(p.sot_tail >= 1 && p.sot_tail <= shortest, WM_ERR_INVALID, "sot_tail %d outside [1, %d] (the shortest prompt)",
+                   p.sot_tail, shortest);
+    }
+    WM_REQUIRE(std::isfinite(T) && T >= 0.f, WM_ERR_INVALID, "temperature must be finite and >= 0");
+    // (1 / T must be a finite f32 too: an infinite scale turns a zero logit's score into NaN)
+    WM_REQUIRE(T == 0.f || std::isfinite((float)(1.0 / (double)T)), WM_ERR_INVALID,
+               "temperature %g is too small: 1 / T overflows", (double)T);
+    WM_REQUIRE(sot_index >= 0 && sot_index < n_prompt, WM_ERR_INVALID, "sot_index %d outside the prompt [0, %d)",
+               sot_index, n_prompt);
+    WM_REQUIRE(ns_tok >= -1 && ns_tok < D.n_vocab, WM_ERR_INVALID, "no_speech_token %d outside the vocabulary", ns_tok);
+    WM_REQUIRE(!call.no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
+    WM_REQUIRE(!call.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
+    // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
+    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on;
+    WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
+    xc.logprobs = call.logprobs_out;
+    xc.no_speech = call.no_speech_out;
+    const uint64_t seed = opts ? opts->seed : 0;
+    xc.par.key0 = (unsigned)seed;
+    xc.par.key1 = (unsigned)(seed >> 32);
+    xc.par.sample = T > 0.f ? 1 : 0;
+    xc.par.inv_T = T > 0.f ? (float)(1.0 / (double)T) : 0.f;
+    xc.par.sot_pos = call.no_speech_out ? sot_index : -1;
+    xc.par.ns_tok = ns_tok;
+    const bool no_stop = g_wm_tuning.no_early_stop != 0;   // probes only: decode every position, truncate on the host
+    cfg->use_graph = !wm_graphs_off() && !ctx->prof.on && !call.trace;   // (a traced call bakes nothing into graphs)
+    cfg->stop.on = !no_stop && (call.eot >= 0 || !budgets.empty());
+    cfg->stop.eot = call.eot;
+    cfg->stop.budgets = budgets.empty() ? nullptr : budgets.data();
+    return WM_OK;
+}
+
+// ---------------------------------------------------------------- lanes ----
+// The contexts the plan's lanes run on, created on first use: the caller's context and its clones (wm_clone), the CU-masked
+// clones of a partition (wm_clone_cus: a slice of the CUs of every XCD), or the solo lane.  *masks_refused: a device / driver
+// that refuses CU-masked streams (a partitioned GPU, an older KFD) is not an error -- the caller falls back to the unmasked
+// policy, once and for all.
+int tx_lanes(wm_ctx *ctx, const WmTxPlan &plan, std::vector<wm_ctx *> *lanes, bool *masks_refused) {
+    *masks_refused = false;
+    lanes->clear();
+    if (plan.kind == WM_LANES_PARTS) {
+        const int parts = plan.parts;
+        std::vector<wm_ctx *> &pl = ctx->part_lanes[parts - 2];
+        while ((int)pl.size() < parts && !*masks_refused) {
+            wm_ctx *c = nullptr;
+            const int k = (int)pl.size();
+            if (wm_clone_cus(ctx, k * 32 / parts, (k + 1) * 32 / parts, &c) != WM_OK) *masks_refused = true;   // 16 + 16, or 10 + 11 + 11 CUs of every XCD
+            else pl.push_back(c);
+        }
+        WM_TRY(wm_ctx_make_current(ctx));
+        if (!*masks_refused) lanes->assign(pl.begin(), pl.begin() + parts);
+        return WM_OK;
+    }
+    if (plan.kind == WM_LANES_SOLO) {
+        const int solo = g_wm_tuning.lane_solo_cus;   // probes only (0 in the product)
+        WM_REQUIRE(solo >= 1 && solo <= 31, WM_ERR_INVALID, "lane_solo_cus: 1 .. 31 CUs per XCD");
+        wm_ctx *&c = ctx->solo_lanes[solo];
+        if (!c) WM_TRY(wm_clone_cus(ctx, 0, solo, &c));
+        lanes->assign(plan.n_lanes, c);
+        return WM_OK;
+    }
+    while ((int)ctx->lanes.size() < plan.n_lanes - 1) {
+        wm_ctx *c = nullptr;
+        WM_TRY(wm_clone(ctx, &c));
+        ctx->lanes.push_back(c);
+    }
+    lanes->push_back(ctx);
+    lanes->insert(lanes->end(), ctx->lanes.begin(), ctx->lanes.begin() + (plan.n_lanes - 1));
+    return WM_OK;
+}
+
+// ---------------------------------------------------------------- the scheduler ----
+// decodes in flight on this device (this call included): other lanes of this call, other contexts' calls
+struct ActiveGuard {
+    std::atomic<int> &n;
+    explicit ActiveGuard(std::atomic<int> &a) : n(a) { n.fetch_add(1, std::memory_order_relaxed); }
+    ~ActiveGuard() { n.fetch_sub(1, std::memory_order_relaxed); }
+};
+
+struct TxRun {
+    wm_ctx *ctx;
+    const TxCall &call;
+    const TxCfg &cfg;
+    const WmTxPlan &plan;
+    std::vector<LaneJob> jobs;
+    int next_group = 0, groups_done = 0;
+    // (a ragged call: a group's prompt positions are its own longest prompt, LaneJob::P)
+    int n_steps(const LaneJob &j) const { return j.P + call.max_new - 1; }
+    bool decoding(const LaneJob &j) const { return j.state == LaneJob::DECODING && j.t < n_steps(j) && !j.stopped; }
+};
+
+// an idle lane takes the next group: prefill, its graph set
+int lane_start(TxRun &r, LaneJob &j) {
+    const TxCall &call = r.call;
+    const int g = r.next_group++;
+    j.Cg = r.plan.cg[g];
+    j.b0 = r.plan.b0[g];
+    j.Bg = j.Cg * call.n_cand;
+    j.t = 0; j.bursts = 0; j.stopped = false;
+    j.bpar.max_cand = call.max_cand; j.bpar.max_new = call.max_new; j.bpar.eot = call.eot; j.bpar.pad = call.eot >= 0 ? call.eot : 0;
+    WM_TRY(lane_prefill(j, call, r.cfg));
+    if (r.cfg.use_graph) WM_TRY(lane_graph(j, j.P));
+    j.state = LaneJob::DECODING;
+    return WM_OK;
+}
+
+enum LaneStep { LANE_WAITS, LANE_MOVED, LANE_ENQUEUED_ALL };
+
+// a decoding lane enqueues its next burst, unless it has to wait for the device or has nothing left to enqueue
+int lane_advance(TxRun &r, LaneJob &j, LaneStep *step) {
+    *step = LANE_WAITS;
+    if (r.cfg.stop.on && j.bursts >= 2 && !j.stopped) {
+        // stay at most two bursts ahead of the GPU: burst (bursts - 2) must have finished, and its live count
+        // says whether there is anything left to decode
+        const int slot = (j.bursts - 2) % WM_NLIVE_RING;
+        const hipError_t q = hipEventQuery(j.burst_ev[slot]);
+        if (q == hipErrorNotReady) { (void)hipGetLastError(); return WM_OK; }   // "not ready" is not an error to keep
+        WM_HIP(q);
+        if (j.c->model->h_nlive[slot] == 0) j.stopped = true;
+    }
+    if (!r.decoding(j)) {   // everything enqueued, or nothing left to decode
+        *step = LANE_ENQUEUED_ALL;
+        return WM_OK;
+    }
+    // does this burst share the chip?  other lanes of this call still decoding, or other calls in flight
+    int busy = 0;
+    for (const LaneJob &o : r.jobs) busy += r.decoding(o);
+    // (sub-chip lanes own their CUs: the other lanes of THIS call do not make the chip "shared")
+    const bool shared = (busy > 1 && r.plan.kind != WM_LANES_PARTS) ||
+                        g_wm_active_decodes[r.ctx->device & 63].load(std::memory_order_relaxed) > 1;
+    WM_TRY(lane_burst(j, j.P, r.n_steps(j), r.cfg.use_graph, shared));
+    *step = LANE_MOVED;
+    return WM_OK;
+}
+
+// everything is enqueued: fetch the token streams, the log-probs, the no-speech probabilities, a beam group's state
+int lane_fetch(TxRun &r, LaneJob &j) {
+    const TxCall &call = r.call;
+    const XCfg &xc = r.cfg.xc;
+    WmModel *m = j.c->model;
+    WM_HIP(hipEventRecord(j.ev[3], j.c->stream));
+    j.gen.resize((size_t)call.max_new * j.Bg);  // dseq[P + i][b]
+    WM_HIP(hipMemcpyAsync(j.gen.data(), m->dseq + (size_t)j.P * j.Bg, j.gen.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    if (xc.logprobs && !call.beam) {   // [gi][b], laid out like dseq
+        j.lp.resize((size_t)call.max_new * j.Bg);
+        WM_HIP(hipMemcpyAsync(j.lp.data(), m->dx_logprob, j.lp.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    }
+    if (xc.no_speech) {
+        j.ns.resize(j.Bg);
+        WM_HIP(hipMemcpyAsync(j.ns.data(), m->dx_nospeech, j.ns.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    }
+    if (call.beam) WM_TRY(beam_fetch(j, call.max_new, call.trace != nullptr));
+    j.state = LaneJob::DRAINING;
+    return WM_OK;
+}
+
+// A draining lane whose stream has drained writes its rows of the call's outputs and adds its stage times.  A decode group
+// runs for seconds -- poll instead of spinning in hipStreamSynchronize, so that the host threads of the other lanes / ranks
+// (one process per GPU, several contexts each) keep their cores.
+int lane_finish(TxRun &r, LaneJob &j, bool *done) {
+    const TxCall &call = r.call;
+    *done = false;
+    const hipError_t q = hipStreamQuery(j.c->stream);
+    if (q == hipErrorNotReady) { (void)hipGetLastError(); return WM_OK; }
+    WM_HIP(q);
+    WM_HIP(hipStreamSynchronize(j.c->stream));
+    if (call.beam) {
+        j.c->model->beam_trace_on = false;
+        beam_drain(j, call);
+    } else {
+        wm_group_rows_out(j.gen.data(), j.lp.data(), j.ns.data(), r.cfg.stop.budgets, call.eot, call.n_cand, j.b0, j.Bg, call.max_new,
+                          call.tokens_out, call.lens_out, r.cfg.xc.logprobs, r.cfg.xc.no_speech);
+    }
+    wm_add_stage_ms(j.ev.e, 3, call.src.windows, j.stage_sum);
+    j.state = LaneJob::IDLE;
+    ++r.groups_done;
+    *done = true;
+    return WM_OK;
+}
+
+// The single host thread drives the lanes round-robin, one step per lane and turn, and sleeps 100 us when nobody moved.  A
+// prefill ends the lane's turn, so every lane has its prefill before anyone's first burst.
+int tx_run(wm_ctx *ctx, const TxCall &call, const TxCfg &cfg, const WmTxPlan &plan, const std::vector<wm_ctx *> &lanes) {
+    TxRun r{ctx, call, cfg, plan, std::vector<LaneJob>(lanes.size())};
+    for (size_t l = 0; l < lanes.size(); ++l) {
+        LaneJob &j = r.jobs[l];
+        j.c = lanes[l];
+        j.fence.s = j.c->stream;
+        WM_TRY(j.ev.create());
+        if (cfg.stop.on) WM_TRY(j.burst_ev.create_untimed());
+    }
+    ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
+    ActiveGuard active_guard(g_wm_active_decodes[ctx->device & 63]);
+    while (r.groups_done < plan.G) {
+        bool progress = false;
+        for (LaneJob &j : r.jobs) {
+            WM_TRY(wm_ctx_make_current(j.c));
+            if (j.state == LaneJob::IDLE) {
+                if (r.next_group >= plan.G) continue;
+                WM_TRY(lane_start(r, j));
+                progress = true;
+            } else if (j.state == LaneJob::DECODING) {
+                LaneStep step;
+                WM_TRY(lane_advance(r, j, &step));
+                if (step == LANE_ENQUEUED_ALL) WM_TRY(lane_fetch(r, j));
+                progress |= step != LANE_WAITS;
+            } else {
+                bool done;
+                WM_TRY(lane_finish(r, j, &done));
+                progress |= done;
+            }
+        }
+        if (!progress) usleep(100);
+    }
+    for (const LaneJob &j : r.jobs)   // lanes overlap: the busiest lane per stage
+        for (int i = 0; i < 3; ++i)
+            if (j.stage_sum[i] > ctx->stage_ms[i]) ctx->stage_ms[i] = j.stage_sum[i];
+    return WM_OK;
+}
+
+// ---------------------------------------------------------------- the ranking step ----
+// a best-of call: wm_rank_candidates over the candidates' log-probs; a beam call: the MaximumLikelihoodRanker over the
+// search's own sums
+int tx_rank(const TxCall &call) {
+    if (!call.best_out) return WM_OK;
+    const int B = call.B, max_new = call.max_new;
+    if (!call.beam)
+        return wm_rank_candidates(call.tokens_out, call.lens_out, call.logprobs_out, B, call.n_cand, max_new, call.eot,
+                                  call.length_penalty, call.best_out, nullptr);
+    const int S = std::max(call.n_cand, call.max_cand);
+    for (int b = 0; b < B; ++b) {
+        int best = 0;
+        double best_score = -INFINITY;
+        for (int h = 0; h < call.n_hyp[b]; ++h) {
+            const size_t r = (size_t)b * S + h;
+            int n_text = 0;
+            while (n_text < call.lens_out[r] && call.tokens_out[r * max_new + n_text] != call.eot) ++n_text;
+            const double score = wm_rank_score((double)call.sums[r], n_text, call.length_penalty);
+            if (score > best_score) { best_score = score; best = h; }   // the first maximal score; all -inf: hypothesis 0
+        }
+        call.best_out[b] = best;
+    }
+    return WM_OK;
+}
+
+// ---------------------------------------------------------------- the call ----
+int tx_transcribe(wm_ctx *ctx, TxCall &call) {
+    // per-chunk token budgets set for THIS call (wm_set_token_budgets) are consumed by it whatever happens next: a call
+    // that fails any check must not leave them armed for a later, unrelated call with the same B
+    std::vector<int32_t> budgets;
+    if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
+    WM_TRY(entry_checks(call));
+    WM_MODEL(ctx);
+    std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
+    if (call.entry == TxCall::BEST_OF && call.best_out && !call.logprobs_out) {
+        lp_own.resize((size_t)call.B * call.n_cand * call.max_new);
+        call.logprobs_out = lp_own.data();
+    }
+    TxCfg cfg;
+    WM_TRY(tx_validate(ctx, call, budgets, &cfg));
+    // the plan: decode groups and lanes.  A masked clone that cannot be made switches the masks off and asks again.
+    WmTxPlanIn pin;
+    pin.B = call.B; pin.N = call.n_cand;
+    pin.explicit_lanes = ctx->max_lanes > 0;
+    pin.lanes = pin.explicit_lanes ? ctx->max_lanes : lane_limit();
+    pin.prof_on = ctx->prof.on; pin.no_cu_masks = ctx->no_cu_masks; pin.n_text_state = m->dims.n_text_state;
+    WmTxPlan plan;
+    std::vector<wm_ctx *> lanes;
+    bool masks_refused = false;
+    wm_tx_plan(pin, g_wm_tuning, &plan);
+    WM_TRY(tx_lanes(ctx, plan, &lanes, &masks_refused));
+    if (masks_refused) {
+        ctx->no_cu_masks = pin.no_cu_masks = true;
+        wm_tx_plan(pin, g_wm_tuning, &plan);
+        WM_TRY(tx_lanes(ctx, plan, &lanes, &masks_refused));
+    }
+    WM_TRY(tx_run(ctx, call, cfg, plan, lanes));
+    return tx_rank(call);
+}
+
+// ---------------------------------------------------------------- filling a call ----
+void mel_src(TxCall &call, const float *mel, const int64_t *mel_base, const int32_t *mel_len, const int32_t *seek,
+             const int32_t *n_frames, wm_mem mem) {
+    call.src.mel = mel; call.src.mel_base = mel_base; call.src.mel_len = mel_len; call.src.seek = seek; call.src.n_frames = n_frames;
+    call.mem = mem;
+}
+
+void set_src(TxCall &call, const wm_windows *w, const int32_t *rows) {
+    call.src.windows = true; call.src.set = w; call.src.rows = rows;
+    call.mem = WM_MEM_HOST;
+}
+
+void outputs(TxCall &call, int B, int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
+             float *logprobs_out, float *no_speech_out) {
+    call.B = B; call.max_new = max_new; call.eot = eot; call.opts = opts;
+    call.tokens_out = tokens_out; call.lens_out = lens_out; call.logprobs_out = logprobs_out; call.no_speech_out = no_speech_out;
+}
+
+// wm_transcribe_mel_ragged / wm_transcribe_mel with best_of candidates per row (TxCall::n_cand): one encoder pass, one
+// cross-K/V cache and one read of it per window, best_of decoder rows (lane_prefill, wm_dec_attention_cand)
+void best_of(TxCall &call, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len, int sot_tail,
+             const uint32_t *sample_ids, int n, float length_penalty, int32_t *best_out) {
+    call.entry = TxCall::BEST_OF;
+    call.prompts = {prompts, prompt_stride, prompt_len, sot_tail, sample_ids};
+    call.n_prompt = prompt_stride;
+    call.n_cand = n; call.length_penalty = length_penalty; call.best_out = best_out;
+}
+
+// Beam search: the call of wm_transcribe_mel_best_of with the rows of a window as its BEAMS (TxCall::beam) -- the same groups,
+// the same prompt phase, one cross-K/V read per window; the generating positions close with the beam kernels (beam.hip)
+void beam(wm_ctx *ctx, TxCall &call, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len, int sot_tail,
+          int beam_size, int max_candidates, float length_penalty, int32_t *n_hyp_out, float *sum_logprobs_out, int32_t *best_out) {
+    call.entry = TxCall::BEAM;
+    call.prompts = {prompts, prompt_stride, prompt_len, sot_tail, nullptr};
+    call.n_prompt = prompt_stride;
+    call.n_cand = beam_size; call.beam = true; call.max_cand = max_candidates; call.length_penalty = length_penalty;
+    call.n_hyp = n_hyp_out; call.sums = sum_logprobs_out; call.best_out = best_out;
+    if (ctx && ctx->model) {   // the debug library's capture is for this call only
+        call.trace = ctx->model->beam_dbg_trace;
+        ctx->model->beam_dbg_trace = nullptr;
+    }
+}
+}  // namespace
+
+extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
+                                    const int32_t *prompt, int n_prompt, int max_new, int32_t eot,
+                                    int32_t *tokens_out, int32_t *lens_out, wm_mem mem) try {
+    TxCall call;
+    call.src.pcm = pcm; call.src.pcm_dtype = pcm_dtype; call.mem = mem;
+    call.prompts.prompt = prompt; call.n_prompt = n_prompt;
+    outputs(call, B, max_new, eot, nullptr, tokens_out, lens_out, nullptr, nullptr);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B, const int32_t *prompt, int n_prompt,
+                             int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
+                             float *token_logprobs_out, float *no_speech_prob_out, wm_mem mem) try {
+    TxCall call;
+    call.src.pcm = pcm; call.src.pcm_dtype = pcm_dtype; call.mem = mem;
+    call.prompts.prompt = prompt; call.n_prompt = n_prompt;
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                 const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts, int n_prompt,
+                                 const uint32_t *sample_ids, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                 int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                 wm_mem mem) try {
+    TxCall call;
+    call.entry = TxCall::MEL;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    call.prompts = {prompts, n_prompt, nullptr, 0, sample_ids};
+    call.n_prompt = n_prompt;
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+// wm_transcribe_mel with prompts of different lengths: every decode group right-aligns its rows to its own longest prompt
+// (wm_right_align, WmModel::doff); a row's results are those of wm_transcribe_mel on that row alone with its own prompt
+extern "C" int wm_transcribe_mel_ragged(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                        const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                        int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                        int max_new, int32_t eot, const wm_decode_opts *opts, int32_t *tokens_out,
+                                        int32_t *lens_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                        wm_mem mem) try {
+    TxCall call;
+    call.entry = TxCall::RAGGED;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    call.prompts = {prompts, prompt_stride, prompt_len, sot_tail, sample_ids};
+    call.n_prompt = prompt_stride;
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_mel_best_of(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                         const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                         int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                         int best_of_n, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                         int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                         float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+    TxCall call;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of_n, length_penalty, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+// wm_transcribe_mel_best_of over the windows of an encoded set: the same call, its cross-K/V copied instead of computed
+extern "C" int wm_transcribe_windows(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                     int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                     int best_of_n, float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                     int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                     float *no_speech_prob_out, int32_t *best_out) try {
+    TxCall call;
+    set_src(call, w, rows);
+    best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of_n, length_penalty, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                      const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                      int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size, int max_candidates,
+                                      float length_penalty, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                      int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
+                                      float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
+    TxCall call;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+         sum_logprobs_out, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_windows_beam(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                          int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size,
+                                          int max_candidates, float length_penalty, int max_new, int32_t eot,
+                                          const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out, int32_t *n_hyp_out,
+                                          float *sum_logprobs_out, float *token_logprobs_out, float *no_speech_prob_out,
+                                          int32_t *best_out) try {
+    TxCall call;
+    set_src(call, w, rows);
+    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+         sum_logprobs_out, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH

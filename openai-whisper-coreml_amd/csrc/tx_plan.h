@@ -1,0 +1,95 @@
+// tx_plan.h -- the host arithmetic of a transcribe call as pure functions (tx_plan.cpp).
+//
+// What transcribe.cpp decides before it touches the device, and what it computes from a group's fetched streams after: how a
+// call of B rows is cut into decode groups and which lanes run them (wm_tx_plan and its four ingredients), the tables a group
+// uploads (wm_group_tables) and the rows of the call's outputs a finished group fills (wm_group_rows_out).  Plain C++, no HIP
+// headers, no context, no global state -- the tuning knobs are passed in -- so tests/test_tx_plan_cpu.py pins every rule on the
+// CPU (wmdbg_tx_plan / wmdbg_group_tables / wmdbg_group_rows_out) against the restatement in tests/tx_plan_ref.py.
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+#include "dec_launch.h"   // WM_DEC_MAXB
+#include "wm_tuning.h"
+
+// ---------------------------------------------------------------- decode groups and lanes ----
+// Decode groups of a call of B chunks on at most L lanes.  explicit_lanes: the host set a lane count (wm_set_lanes n > 0);
+// gc_probe: the debug knob group_chunks (0 in the product).
+int wm_group_count(int B, int L, bool explicit_lanes, int gc_probe);
+// B rows in G balanced runs: run g is rows [b0[g], b0[g] + cg[g])
+void wm_balanced_cut(int B, int G, std::vector<int> &b0, std::vector<int> &cg);
+// ... of a candidate call (wm_transcribe_mel_best_of) of B windows x N candidates: groups of whole windows; returns their number
+int wm_cand_groups(int B, int N, int L, bool explicit_lanes, std::vector<int> &b0, std::vector<int> &cg);
+// CU-masked groups of a call (0: none -- unmasked lanes as wm_group_count says; 2 / 3: that many groups, one per part of the chip)
+int wm_lane_parts(int B, int L, bool explicit_lanes, int n_text_state, int n_text_layer, const WmTuning &t);
+
+// the contexts a call's lanes run on: the caller's context and its clones, the CU-masked clones of a partition of the chip,
+// or (probes) one clone confined to a few CUs
+enum WmLaneKind { WM_LANES_CLONES = 0, WM_LANES_PARTS = 1, WM_LANES_SOLO = 2 };
+
+struct WmTxPlanIn {
+    int B = 1;                    // rows of the call (a candidate call: windows)
+    int N = 1;                    // candidates (beams) per row
+    int lanes = 1;                // the lane limit: wm_set_lanes' count when the host set one, else the default
+    bool explicit_lanes = false;  // the host set it
+    bool prof_on = false;         // per-kernel profiling: everything on the caller's context
+    bool no_cu_masks = false;     // this device refused a CU-masked stream before
+    int n_text_state = 0;
+};
+
+struct WmTxPlan {
+    int L = 1;              // lanes the call may use
+    int parts = 0;          // 2 / 3: sub-chip lanes
+    int G = 1;              // decode groups: group g is rows (windows) [b0[g], b0[g] + cg[g])
+    std::vector<int> b0, cg;
+    int n_lanes = 1;        // lanes that run: more groups than lanes go in rounds
+    WmLaneKind kind = WM_LANES_CLONES;
+};
+
+// The composite decision, once.  Reads lane_parts, lane_solo_cus and group_chunks of the tuning.
+void wm_tx_plan(const WmTxPlanIn &in, const WmTuning &t, WmTxPlan *out);
+
+// ---------------------------------------------------------------- a group's tables ----
+// the prompts of a call: row b's is prompt + b * stride (stride 0: one prompt for all)
+struct TxPrompts {
+    const int32_t *prompt = nullptr;
+    int stride = 0;
+    const int32_t *len = nullptr;   // non-null: a ragged call, row b's prompt is its first len[b] entries
+    int sot_tail = 0;               // ... whose <|startoftranscript|> is entry len[b] - sot_tail
+    const uint32_t *sample_ids = nullptr;
+};
+
+// what a group uploads before its first position (sources of asynchronous copies: they live in the lane's job)
+struct TxGroupTables {
+    std::vector<int32_t> pr;     // prompt tokens [P][Bg], position-major like dseq
+    std::vector<int32_t> off;    // a ragged call: row offsets [Bg] = P - len
+    std::vector<int32_t> bud;    // token budgets [Bg] (a call with budgets)
+    std::vector<unsigned> ids;   // a candidate group: [2][ids_stride] window ids | candidate words; else the rows' sample ids [Bg]
+};
+
+// the right-aligned prompt table [P][Bg] and the row offsets [Bg] of rows [b0, b0 + Bg) of a ragged call; returns P
+int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, std::vector<int32_t> &table,
+                   std::vector<int32_t> &off);
+// The tables of the group of rows (windows) [b0, b0 + Cg) x N candidates: decoder row b belongs to window b / N and is its
+// candidate b % N.  n_prompt: the prompt length of a uniform call; budgets: [B] of the call (null: none); want_ids: the
+// extended decode is on.  Returns P, the group's prompt positions (a ragged call: the longest prompt among ITS rows).
+int wm_group_tables(const TxPrompts &p, int n_prompt, const int32_t *budgets, int b0, int Cg, int N, int ids_stride, bool want_ids,
+                    TxGroupTables *out);
+
+// ---------------------------------------------------------------- a group's outputs ----
+// The output rows of a finished plain (not beam) group from its fetched streams gen [max_new][Bg], lp [max_new][Bg] (read
+// when logprobs is given) and ns [Bg] (when no_speech is): decoder row b is output row b0 * N + b.  A row ends at its budget
+// or with its first eot; tokens past the end read eot, log-probs 0 -- the stopping token has its log-prob, nothing after it.
+void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, const int32_t *budgets, int32_t eot, int N, int b0,
+                       int Bg, int max_new, int32_t *tokens, int32_t *lens, float *logprobs, float *no_speech);
+
+// ---------------------------------------------------------------- the hooks' flat forms ----
+// documented at wmdbg_tx_plan / wmdbg_group_tables / wmdbg_group_rows_out (include/whisper_mi355x_debug.h)
+constexpr int WM_TX_PLAN_IN = 12, WM_TX_PLAN_OUT = 8;
+constexpr int WM_TX_TAB_IN = 256, WM_TX_TAB_OUT = 576, WM_TX_TAB_ROWS = 16, WM_TX_TAB_POS = 12;
+constexpr int WM_TX_ROWS_IN = 320, WM_TX_ROWS_OUT = 288, WM_TX_ROWS_NEW = 8;
+// returns the entries written to cut (b0[0 .. G), cg[0 .. G)), or -1 when they do not fit cut_cap
+int wm_tx_plan_flat(const int32_t *in, int32_t *out, int32_t *cut, int cut_cap);
+bool wm_group_tables_flat(const int32_t *in, int ids_stride, int32_t *out);
+bool wm_group_rows_out_flat(const int32_t *in, int32_t *out);

@@ -207,7 +207,7 @@ struct wm_ctx {
     // SUB-CHIP LANES (round 6).  A context whose stream was created with a CU mask (hipExtStreamCreateWithCUMask) runs
     // everything it launches on `n_cus` of the 256 CUs: the CUs [cu_lo, cu_hi) of every XCD.  Two or
     // three SMALL decode groups (latency-bound launch chains) then run side by side on disjoint CUs instead of flooding
-    // all 256 CUs with every launch and serialising at the CU level (model_api.cpp, the group policy).
+    // all 256 CUs with every launch and serialising at the CU level (tx_plan.cpp, the group policy).
     int n_cus = 256, cu_lo = 0, cu_hi = 32;   // the CUs [cu_lo, cu_hi) of every XCD
     std::vector<wm_ctx *> part_lanes[2];   // [0]: the two clones of the 2-way partition, [1]: the three of the 3-way one (created on first use)
     bool no_cu_masks = false;              // a CU-masked stream could not be created on this device: the policy stays unmasked
@@ -230,16 +230,8 @@ int wm_clone_cus(wm_ctx *parent, int cu_lo, int cu_hi, wm_ctx **out);
 int wm_cu_mask(int cu_lo, int cu_hi, uint32_t mask[8]);
 
 int wm_ctx_make_current(const wm_ctx *ctx);
-int wm_group_count(int B, int L, bool explicit_lanes, int gc_probe);   // model_api.cpp: decode groups of a wm_transcribe_greedy call
-// ... and of a wm_transcribe_mel_best_of call of B windows x N candidates: groups of whole windows (first window, windows)
-int wm_cand_groups(int B, int N, int L, bool explicit_lanes, std::vector<int> &b0, std::vector<int> &cg);
-void wm_balanced_cut(int B, int G, std::vector<int> &b0, std::vector<int> &cg);   // B rows in G balanced runs
-// the right-aligned prompt table [P][Bg] and the row offsets [Bg] of rows [b0, b0 + Bg) of a ragged call; returns P (model_api.cpp)
-int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len, int b0, int Bg, std::vector<int32_t> &table,
-                   std::vector<int32_t> &off);
 double wm_rank_score(double sum, int n_text, float length_penalty);   // api.cpp: the MaximumLikelihoodRanker's score
-// CU-masked groups of a call (0: none -- unmasked lanes as wm_group_count says; 2 / 3: that many groups, one per part of the chip)
-int wm_lane_parts(int B, int L, bool explicit_lanes, int n_text_state, int n_text_layer);
+// (decode groups, lanes and a group's tables of a transcribe call: tx_plan.h)
 
 // ---------------------------------------------------------------- launch-shape experiment knobs
 // Launch shapes are chosen by fixed rules (dec_launch.cpp: the decode plans; gemm.hip wm_gemm): the

@@ -136,7 +136,7 @@ def test_multi_host_helpers_reject_bad_sizes(pkg):
 
 
 def test_group_policy_of_a_call(pkg):
-    """wm_transcribe_greedy's decode groups (model_api.cpp wm_group_count, measured in round 5: profiles/r05_group_policy.txt):
+    """wm_transcribe_greedy's decode groups (tx_plan.cpp wm_group_count, measured in round 5: profiles/r05_group_policy.txt):
     the library's own policy -- one group below 32 chunks, two up to 143, three from 144, never a group above 128 rows, never
     more groups in flight than lanes -- and the rounds-1-4 rule when the host sets a lane count."""
     lib = pkg.binding.load_debug_library()
@@ -157,7 +157,7 @@ def test_group_policy_of_a_call(pkg):
 
 
 def test_sub_chip_lane_policy_and_cu_masks(pkg):
-    """Round 6 (model_api.cpp wm_lane_parts, measured: profiles/r06_group_policy.txt): two CU-masked half-chip decode groups
+    """Round 6 (tx_plan.cpp wm_lane_parts, measured: profiles/r06_group_policy.txt): two CU-masked half-chip decode groups
     for the NARROW models only (their chains do not need the CUs) -- tiny (d 384) at 32 .. 47 chunks, base (d 512) at
     24 .. 128 -- never for d >= 768 (large-v2 on half the CUs: 1.55 -> 2.21 ms per position), never when the host set a
     lane count or has one lane.  The masks: a slice of the CUs of EVERY XCD (bit i = CU i / 8 of XCD i % 8), complementary."""

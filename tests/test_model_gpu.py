@@ -988,7 +988,7 @@ def test_large_v3_full_depth_one_chunk(pkg):
 def test_large_v3_fifteen_chunk_shard_on_the_products_own_lanes(pkg):
     """BASELINE.json configs[4] at its PER-GPU size: 1 h of audio = 120 chunks over 8 GPUs = 15 chunks per rank, large-v3 at
     FULL depth (128 mel bins, 51 866 tokens), through wm_transcribe_greedy with the product's DEFAULT group / lane policy
-    (model_api.cpp, measured in round 5: below 32 chunks ONE decode group -- 8 + 7 on two lanes was 4 % slower) and with an
+    (tx_plan.cpp, measured in round 5: below 32 chunks ONE decode group -- 8 + 7 on two lanes was 4 % slower) and with an
     explicit lane count (wm_set_lanes 3: groups of 8 + 7 on two weight-sharing lanes).  15 distinct recordings, `lively`
     weights with perturbed LayerNorms; every row must equal the row of the same chunk decoded ALONE (one chunk per call:
     a one-row group, other launch shapes, no lanes), the rows must be pairwise distinct, and three of them are
@@ -1875,6 +1875,31 @@ def test_sub_chip_lanes_carry_the_decode_policy_state(pkg):
     assert l3.min() < NEW and len({r.tobytes() for r in t2}) >= 30
     for i in range(40):
         assert np.array_equal(t3[i, :l3[i]], t2[i, :l3[i]])          # early stop == decode everything and truncate
+    ctx.close()
+
+
+def test_solo_lane_takes_the_groups_in_turn(pkg):
+    """The probes' solo lane (debug knob lane_solo_cus): ONE clone confined to 8 CUs of every XCD runs the call's decode groups
+    one after the other -- with group_chunks = 2, five chunks are three groups, so the lane takes a second and a third group.
+    tiny.en geometry, 8 tokens: tokens and lengths == the same rows decoded in one group on the context's own stream."""
+    import ctypes
+    dims = dict(pkg.binding.MODEL_DIMS["tiny.en"])
+    ctx = pkg.binding.Context(dims, debug=True)
+    ctx.init_synthetic(23, matrix_gain=4.0)
+    ctx.finalize()
+    ctx.lib.wmdbg_set_tuning.argtypes = [ctypes.c_char_p, ctypes.c_int]
+    pcm, prompt = tones(5), [50257, 50362]
+    try:
+        ctx.set_lanes(1)
+        want = ctx.transcribe_greedy(pcm, prompt, 8, eot=50256, budgets=[8, 3, 8, 5, 8])
+        ctx.set_lanes(0)
+        assert ctx.lib.wmdbg_set_tuning(b"lane_solo_cus", 8) == 0 and ctx.lib.wmdbg_set_tuning(b"group_chunks", 2) == 0
+        got = ctx.transcribe_greedy(pcm, prompt, 8, eot=50256, budgets=[8, 3, 8, 5, 8])
+    finally:
+        ctx.lib.wmdbg_set_tuning(b"reset", 0)
+        ctx.set_lanes(0)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    assert want[1].tolist()[1] == 3 and want[1].tolist()[3] == 5
     ctx.close()
 
 
