@@ -518,6 +518,46 @@ WM_API int wm_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t timestamp_beg
  * outside [0, n_vocab].  Same inheritance as wm_set_suppress. */
 WM_API int wm_set_repetition_rules(wm_ctx *ctx, float repetition_penalty, int no_repeat_ngram_size, int32_t eot);
 
+/* The sequence bias: Hugging Face generate's sequence_bias, and with it bad_words_ids (CTranslate2's suppress_sequences) and
+ * phrase boosting (contextual biasing: product names, people, jargon).  A token sequence carries a bias, and the bias is added
+ * to the logit of its LAST token whenever the row's history ends in its other tokens.
+ *   History: g[0 .. k), the row's GENERATED tokens of this call, exactly as for wm_set_repetition_rules (prompt excluded, a
+ *     ragged row counts from its own prompt's end, a beam row has the history of the hypothesis it continues).
+ *   Entries: n_seq sequences, sequence i = tokens[seq_offsets[i] .. seq_offsets[i + 1]) with 1 <= length <= WM_MAX_BIAS_SEQ_LEN
+ *     and bias[i].  Every token in [0, n_vocab); the LAST token < eot (only text ids are ever biased or banned); ids >= eot may
+ *     stand inside a sequence and match as themselves.  bias[i] is finite or -INFINITY.  Two sequences with identical tokens
+ *     are invalid.
+ *   Match: at a position, entry s[0 .. n) matches a row iff n == 1, or k >= n - 1 and g[k - n + 1 .. k) == s[0 .. n - 1).
+ *   Effect: total(t) is an f32 sum that starts at +0.0f and adds the bias of every matching entry whose last token is t, in the
+ *     order the entries were given (an implicit entry, below, follows the entry that produced it).  The logit becomes
+ *     v[t] + total(t): one f32 add.  A total of -INFINITY is a BAN: the id is treated exactly like a suppressed one.  Fed the
+ *     same order this is, bit for bit, Hugging Face's SequenceBiasLogitsProcessor over the generated tokens, and with -INFINITY
+ *     its NoBadWordsLogitsProcessor.
+ *   Boosted prefixes: boost_prefixes[i] != 0 (the array may be NULL: none) needs a finite bias and adds, for every proper
+ *     prefix s[0 .. j), 1 <= j < n, an IMPLICIT entry with the same bias, so that a multi-token phrase is helped from its first
+ *     token on.  Implicit entries with identical tokens merge into one that carries the MAXIMUM bias (two phrases that share a
+ *     first word boost it once, as a trie would) and stands where the first of them stood; an implicit entry identical to a
+ *     given sequence is dropped, and so is a prefix that ends in an id >= eot.  At most WM_MAX_BIAS_ENTRIES entries after the
+ *     expansion.
+ *   Order: the repetition penalty multiplies first, then the bias is added; the bans of both rules are OR-ed.  The biased value
+ *     replaces the logit before everything the decode does with it (arg-max, sampling score, log-prob normalisers, the timestamp
+ *     sum rule, the stored f32 row, beam lists).  no_speech_prob is read from the raw logits: single-token entries do not touch
+ *     it.
+ * Ids are the caller's tokenizer's: Whisper's " word" and "word" are different ids, and both variants are the caller's to list.
+ * Scope and inheritance as wm_set_repetition_rules: every transcribe entry, the teacher-forced calls stay raw, the call runs the
+ * extended decode, the all-f32 debug path answers WM_ERR_STATE; applied to every lane, copied by later wm_clone's.  n_seq = 0
+ * switches it off (the other pointers may then be NULL).  WM_ERR_INVALID -- and the table in force stays -- for a token outside
+ * the vocabulary, a last token >= eot, a length of 0 or above 32, offsets that do not start at 0 or decrease, a NaN or +INFINITY
+ * bias, a duplicate sequence, -INFINITY with boost_prefixes, more than WM_MAX_BIAS_ENTRIES entries, eot outside [0, n_vocab].
+ * Cost, measured: + 6 .. 15 us per decode position with 8 entries (base x 32 rows, large-v2 x 56) -- two
+ * state launches and the wider epilogue --, + 12 us / + 27 us with WM_MAX_BIAS_ENTRIES entries that ALL match every row: below
+ * the logits launch itself (35 / 82 us), 3.8 % / 0.6 % of a position. */
+#define WM_MAX_BIAS_SEQ_LEN 32      /* tokens per sequence (as no_repeat_ngram_size)              */
+#define WM_MAX_BIAS_ENTRIES 4096    /* entries after prefix expansion (a full table costs less than the logits launch) */
+WM_API int wm_set_sequence_bias(wm_ctx *ctx, const int32_t *tokens, const int32_t *seq_offsets /* [n_seq + 1] */,
+                                const float *bias /* [n_seq] */, const uint8_t *boost_prefixes /* [n_seq], nullable */,
+                                int n_seq, int32_t eot);
+
 /* Per-chunk token budgets for the NEXT wm_transcribe_greedy call on this context (consumed by it; n must equal that
  * call's B): chunk i generates at most budgets[i] tokens (clamped to max_new), lens_out[i] <=
  * budgets[i].  A chunk that has reached its budget -- like one that has emitted `eot` -- LEAVES the decode: its caches are

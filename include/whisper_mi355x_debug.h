@@ -167,6 +167,19 @@ WM_API int wmdbg_decode_close_rep(wm_ctx *ctx, wmdbg_step *io, float penalty, in
  * word t >> 5; both pre-filled with 0xff bytes on the device, so a word the kernel does not write shows. */
 WM_API int wmdbg_repeat_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V, int ngram,
                               int32_t eot, uint32_t *seen_out, uint32_t *ban_out);
+/* wmdbg_decode_close_rep with the sequence bias on as well (wm_set_sequence_bias: the table arguments are that call's, io->eot its
+ * eot): wm_repeat_state, wm_seqbias_state behind it, then a DE_LOGITS_XB launch -- for n_seq = 0 too (an empty table).  The
+ * per-row state is pre-filled with 0xff bytes.  WM_ERR_INVALID for a table wm_set_sequence_bias would refuse. */
+WM_API int wmdbg_decode_close_sb(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram, const int32_t *tokens,
+                                 const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq);
+/* The state kernel of the sequence bias alone (seqbias.hip) behind wm_repeat_state with empty rules: seq as for
+ * wmdbg_repeat_state, the table as for wm_set_sequence_bias with V as the vocabulary.  Out: hit / ban u32 [B][words],
+ * words = (pad16(V) + 31) / 32; cnt i32 [B]; id i32 / total f32 [B][WM_MAX_BIAS_ENTRIES], the first cnt[b] of row b written; woff
+ * i32 [B][words], the hit bits in the words below each word (the list index of its first hit id) -- everything pre-filled with 0xff bytes on the device, so a word or element the kernels do not write shows. */
+WM_API int wmdbg_seqbias_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V, const int32_t *tokens,
+                               const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq, int32_t eot,
+                               uint32_t *hit_out, uint32_t *ban_out, int32_t *cnt_out, int32_t *id_out, float *total_out,
+                               int32_t *woff_out);
 /* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_step) and the offsets of seed, logits and
  * stats_tail_nonzero (host only). */
 WM_API int wmdbg_step_layout(int32_t *out4);

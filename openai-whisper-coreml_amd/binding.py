@@ -1117,6 +1117,32 @@ def _long_word_step(o, source, live, sizes, kept, res):
         u.commit(o, segs, next_seek, float(res["temperature"][i]))
 
 
+def long_bias_table(sequence_bias, bad_words, boost_phrases, phrase_boost):
+    """transcribe_long's sequence_bias / bad_words / boost_phrases as ONE table for Context.set_sequence_bias: ({token tuple:
+    bias} in the order sequence_bias, bad_words, boost_phrases; the tuples whose prefixes are boosted), or None when all three
+    are None.  ValueError for a sequence named twice and for boost_phrases without a finite phrase_boost."""
+    if sequence_bias is None and bad_words is None and boost_phrases is None:
+        return None
+    table, boost = {}, []
+
+    def add(seq, bias):
+        key = tuple(int(t) for t in seq)
+        if key in table:
+            raise ValueError("sequence bias: %r is named twice" % (key,))
+        table[key] = float(bias)
+        return key
+    for seq, bias in (sequence_bias or {}).items():
+        add(seq, bias)
+    for seq in bad_words or ():
+        add(seq, -math.inf)
+    if boost_phrases:
+        if phrase_boost is None or not math.isfinite(float(phrase_boost)):
+            raise ValueError("boost_phrases needs a finite phrase_boost")
+        for seq in boost_phrases:
+            boost.append(add(seq, phrase_boost))
+    return table, boost
+
+
 def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_speech_token, lang_first=None,
                     lang_last=None, language=None, sot_prev=None, initial_prompt_tokens=None, recording_ids=None,
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
@@ -1125,7 +1151,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     prepend_punctuations=None, append_punctuations=None, best_of=None, length_penalty=None, beam_size=None,
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
-                    repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None):
+                    repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
+                    boost_phrases=None, phrase_boost=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1226,6 +1253,15 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        the run's first alignment call, and stays set on the context: the teacher-forced pass of every alignment then carries
        that many positions per decoder step (wm_set_teacher_panel: a launch policy, the words are the same bit for bit).  A
        value outside 1 .. 8 is a ValueError before any library call.  None makes no call.
+    17. sequence_bias / bad_words / boost_phrases (all None: off): ONE table for Context.set_sequence_bias
+       (wm_set_sequence_bias, eot is this call's eot) -- sequence_bias {token tuple: bias} as Hugging Face's sequence_bias,
+       bad_words [token sequence, ...] with bias -inf (bad_words_ids; CTranslate2's suppress_sequences), boost_phrases [token
+       sequence, ...] with bias phrase_boost (a finite float, required with them) and boosted prefixes, so that a phrase is
+       helped from its first token on.  A sequence named twice is a ValueError before any library call.  The table is set
+       behind the log-mel (behind the repetition rules of 15), holds for every decode call of the run and is cleared again
+       when the function leaves, also on an exception.  It acts on a row's generated tokens only.  The ids are the caller's
+       tokenizer's: Whisper's " word" and "word" are different ids, and both variants are the caller's to list.  With all
+       three None the function makes exactly the calls it made before they existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1238,6 +1274,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     o = _LongOptions(**locals())
     R = len(recordings)
     o.early(R)
+    bias_table = long_bias_table(sequence_bias, bad_words, boost_phrases, phrase_boost)   # 17. (None: off)
     ctx.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
     out = [dict(language=None, segments=[], seeks=[], windows=[]) for _ in range(R)]
     if R == 0:
@@ -1249,6 +1286,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
         if rules:   # 15.
             ctx.set_repetition_rules(1.0 if repetition_penalty is None else repetition_penalty,
                                      0 if no_repeat_ngram_size is None else no_repeat_ngram_size, eot)
+        if bias_table is not None:   # 17.
+            ctx.set_sequence_bias(bias_table[0], bias_table[1], eot=eot)
         langs = _long_languages(o, d_mel, mel_offs, T)
         o.prompt_head()
         units = _long_units(o, out, langs, d_mel, mel_offs, T)
@@ -1298,8 +1337,12 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 source.close()
             ctx.dev_free(d_mel)
         finally:
-            if rules:
-                ctx.set_repetition_rules(1.0, 0, eot)
+            try:
+                if bias_table is not None:
+                    ctx.set_sequence_bias(None)
+            finally:
+                if rules:
+                    ctx.set_repetition_rules(1.0, 0, eot)
     if vocab is not None:
         for rec in out:
             rec["text"] = vocab.decode([t for sg in rec["segments"] for t in sg["tokens"] if t < eot])
@@ -1660,6 +1703,33 @@ class Context:
         self.lib.wm_set_repetition_rules.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_int32]
         self.lib.wm_set_repetition_rules.restype = ctypes.c_int
         _check(self.lib, self.lib.wm_set_repetition_rules(self.handle, float(penalty), int(no_repeat_ngram_size), int(eot)))
+
+    def set_sequence_bias(self, sequences=None, boost=(), eot=None):
+        """The sequence bias of every transcribe call on this context (wm_set_sequence_bias; Hugging Face's sequence_bias,
+        with -inf its bad_words_ids): `sequences` {tuple of token ids: bias}, in the dict's order -- the bias (finite or -inf)
+        is added to the logit of a sequence's LAST token whenever the row's generated tokens end in its other tokens; the
+        prompt never counts.  `boost`: the keys whose proper prefixes are biased too (finite bias), so that a phrase is
+        helped from its first token on; prefixes shared by several phrases take the largest bias once.  Only ids < eot
+        (default: the vocabulary size) may end a sequence.  The ids are the caller's tokenizer's: Whisper's " word" and
+        "word" are different ids, both variants are the caller's to list.  None or {} switches the bias off."""
+        fn = self.lib.wm_set_sequence_bias
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int32]
+        fn.restype = ctypes.c_int
+        eot = int(self.dims["n_vocab"]) if eot is None else int(eot)
+        if not sequences:
+            _check(self.lib, fn(self.handle, None, None, None, None, 0, eot))
+            return
+        keys = [tuple(int(t) for t in k) for k in sequences]
+        marked = {tuple(int(t) for t in k) for k in boost}
+        if not marked <= set(keys):
+            raise ValueError("set_sequence_bias: boost names a sequence that is not in the table")
+        toks = np.array([t for k in keys for t in k], dtype=np.int32)
+        offs = np.zeros(len(keys) + 1, dtype=np.int32)
+        offs[1:] = np.cumsum([len(k) for k in keys])
+        bias = np.array([float(v) for v in sequences.values()], dtype=np.float32)
+        flags = np.array([1 if k in marked else 0 for k in keys], dtype=np.uint8)
+        _check(self.lib, fn(self.handle, _ptr(toks) if toks.size else None, _ptr(offs), _ptr(bias), _ptr(flags) if marked else None,
+                            len(keys), eot))
 
     def set_lanes(self, n):
         """Decode groups one transcribe_greedy call keeps in flight (0: default = $WM_LANES or 3; 1: one group per call)."""

@@ -1395,8 +1395,36 @@ extern "C" int wmdbg_step_layout(int32_t *out4) {
     return WM_OK;
 }
 
+// A sequence-bias table (wm_sb_expand) in device memory as the product lays it out, the per-row state pre-filled with 0xff
+// bytes: a word or list element the state kernel leaves alone shows.
+static int stage_seqbias(DevPool &pool, hipStream_t s, const WmSbTable &t, int B, int words, WmSbPar *par_host, WmSbDev *out) {
+    const size_t cap = WM_MAX_BIAS_ENTRIES;
+    const int ng = t.n_groups(), ne = t.n_entries();
+    WmSbDev d;
+    memset(&d, 0, sizeof(d));
+    par_host->n_groups = ng; par_host->n_entries = ne;
+    std::vector<int32_t> beg(t.grp_beg);
+    if (beg.empty()) beg.push_back(0);
+    WM_TRY(pool.get(&d.par, par_host, sizeof(WmSbPar), s));
+    WM_TRY(pool.get(&d.grp_id, ng ? t.grp_id.data() : nullptr, std::max<size_t>(ng, 1) * 4, s));
+    WM_TRY(pool.get(&d.grp_beg, beg.data(), beg.size() * 4, s));
+    WM_TRY(pool.get(&d.ent_len, ne ? t.ent_len.data() : nullptr, std::max<size_t>(ne, 1) * 4, s));
+    WM_TRY(pool.get(&d.ent_bias, ne ? t.ent_bias.data() : nullptr, std::max<size_t>(ne, 1) * 4, s));
+    WM_TRY(pool.get(&d.ent_ctx, ne ? t.ent_ctx.data() : nullptr, std::max<size_t>(ne, 1) * WM_SB_CTX * 4, s));
+    WM_HIP(hipStreamSynchronize(s));   // `beg` leaves scope
+    WM_TRY(pool.get(&d.e.hit, nullptr, (size_t)B * words * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.cnt, nullptr, (size_t)B * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.lid, nullptr, (size_t)B * cap * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.ltot, nullptr, (size_t)B * cap * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.woff, nullptr, (size_t)B * words * 4, s, 0xff));
+    d.e.words = words;
+    *out = d;
+    return WM_OK;
+}
+
 // rep: the repetition rules (penalty, ngram, io->eot) are on -- wm_repeat_state in front of a DE_LOGITS_XR launch
-static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram) {
+// sbt (with rep): the sequence bias as well -- wm_seqbias_state behind it and a DE_LOGITS_XB launch, also for an empty table
+static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram, const WmSbTable *sbt = nullptr) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
     if (rep)
@@ -1452,6 +1480,7 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     xp.inv_T = io->temperature > 0.f ? (float)(1.0 / (double)io->temperature) : 0.f;   // as wm_transcribe fills it
     xp.sot_pos = io->sot_pos; xp.ns_tok = io->ns_tok; xp.chunk0 = io->chunk0; xp.n_prompt = n_prompt; xp.n_cand = 1;
     WmRepPar rpar;
+    WmSbPar sbpar;
     const int zero = 0;
     std::vector<float> lg((size_t)B * vpad), lp((size_t)n_ctx * B), stn(st_words);
     DevPool pool;
@@ -1548,6 +1577,13 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
         a.epi = DE_LOGITS_XR;
         a.rep.words = mw;
         WM_TRY(wm_repeat_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, a.rep));
+        if (sbt) {
+            WmSbDev sd;
+            WM_TRY(stage_seqbias(pool, s, *sbt, B, mw, &sbpar, &sd));
+            a.epi = DE_LOGITS_XB;
+            a.sb = sd.e;
+            WM_TRY(wm_seqbias_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, sd, a.rep.ban, mw));
+        }
     }
     WM_TRY(wm_dec_gemv(ctx, a));
     WM_TRY(wm_argmax_embed(ctx, a.argmax, n_tiles, B, dseq, dpos, n_prompt, dres, io->arg_first, dE, dpemb, K, n_ctx, dxn, dxbn, dstn,
@@ -1601,6 +1637,54 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
 extern "C" int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io) { return decode_close_run(ctx, io, false, 1.f, 0); }
 extern "C" int wmdbg_decode_close_rep(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram) {
     return decode_close_run(ctx, io, true, penalty, ngram);
+}
+
+extern "C" int wmdbg_decode_close_sb(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram, const int32_t *tokens,
+                                     const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq) {
+    WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close_sb: null");
+    WmSbTable t;
+    WM_TRY(wm_sb_expand(tokens, seq_offsets, bias, boost_prefixes, n_seq, io->eot, io->V, &t));
+    return decode_close_run(ctx, io, true, penalty, ngram, &t);
+}
+
+extern "C" int wmdbg_seqbias_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V, const int32_t *tokens,
+                                   const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq, int32_t eot,
+                                   uint32_t *hit_out, uint32_t *ban_out, int32_t *cnt_out, int32_t *id_out, float *total_out,
+                                   int32_t *woff_out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(seq && hit_out && ban_out && cnt_out && id_out && total_out && woff_out, WM_ERR_INVALID, "wmdbg_seqbias_state: null pointer");
+    WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && V >= 16 && n_ctx >= 1 && n_ctx <= 448 && pos >= 0 && pos < n_ctx && n_prompt >= 0 &&
+                   n_prompt <= n_ctx,
+               WM_ERR_INVALID, "wmdbg_seqbias_state: bad geometry");
+    WmSbTable t;
+    WM_TRY(wm_sb_expand(tokens, seq_offsets, bias, boost_prefixes, n_seq, eot, V, &t));
+    const int words = ((V + 15) / 16 * 16 + 31) / 32;
+    const size_t cap = WM_MAX_BIAS_ENTRIES;
+    WmRepPar rpar;
+    rpar.p = 1.f; rpar.inv_p = 1.f; rpar.n = 0; rpar.eot = 0;   // the bitmaps' owner with empty rules, as the product runs it
+    WmSbPar sbpar;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    const int *dseq, *dpos;
+    WmRepDev rd;
+    rd.words = words;
+    WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * B * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&rd.par, &rpar, sizeof(rpar), s));
+    WM_TRY(pool.get(&rd.seen, nullptr, (size_t)B * words * 4, s, 0xff));
+    WM_TRY(pool.get(&rd.ban, nullptr, (size_t)B * words * 4, s, 0xff));
+    WmSbDev sd;
+    WM_TRY(stage_seqbias(pool, s, t, B, words, &sbpar, &sd));
+    WM_TRY(wm_repeat_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, rd));
+    WM_TRY(wm_seqbias_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, sd, rd.ban, words));
+    WM_HIP(hipMemcpyAsync(hit_out, sd.e.hit, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(ban_out, rd.ban, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(cnt_out, sd.e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(id_out, sd.e.lid, (size_t)B * cap * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(total_out, sd.e.ltot, (size_t)B * cap * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(woff_out, sd.e.woff, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 extern "C" int wmdbg_repeat_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V, int ngram,

@@ -87,6 +87,7 @@ struct DecGemvDev {
     int bgroups;           // workgroups per tile group along the batch: group g takes batch rows [g, g + 1) * NBLK * 16
     WmRepDev rep;          // DE_LOGITS_XR: repetition rules (behind the older fields: they keep their kernel-argument offsets)
     int panel;             // DE_QKV_P: panel width (cold, like rep: read in the epilogue only)
+    WmSbEpi sb;            // DE_LOGITS_XB: sequence bias (LAST: every older field keeps its kernel-argument offset)
 };
 
 // L2 warm-up workgroup: blockIdx >= n_tiles of the compute grid.  Workgroup n_tiles + t reads tile t of
@@ -150,8 +151,18 @@ template <>
 struct GemvRepWords<DE_LOGITS_XR> {
     unsigned rseen[4], rban[4];
 };
+template <>
+struct GemvRepWords<DE_LOGITS_XB> : GemvRepWords<DE_LOGITS_XR> {};
+// sequence bias (DE_LOGITS_XB only, an empty base everywhere else, for the reason DESIGN.md section 14 gives): the hit words
+template <int EPI>
+struct GemvSbWords {};
+template <>
+struct GemvSbWords<DE_LOGITS_XB> {
+    unsigned rhit[4];
+    int roff[4];   // list index of the word's first hit id (WmSbEpi::woff)
+};
 template <int EPI, bool LN>
-struct GemvUnitOps : GemvRepWords<EPI> {
+struct GemvUnitOps : GemvRepWords<EPI>, GemvSbWords<EPI> {
     float c1v, c2v;
     float xold[4];
     float off4[4];   // DE_RESID: mean-centring offsets of the lane's four rows
@@ -198,7 +209,7 @@ __device__ __forceinline__ void gemv_unit_load(const DecGemvDev &p, GemvUnitOps<
             o.trng[r] = *(const int4 *)(p.ts.rng + (long)(b0 + (bl < nb ? bl : nb - 1)) * 4);
         }
     }
-    if constexpr (EPI == DE_LOGITS_XR) {
+    if constexpr (de_has_rep(EPI)) {
         // the 16 ids of a tile share ONE bitmap word per row; rows past the group's are clamped like the ranges above
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -207,6 +218,11 @@ __device__ __forceinline__ void gemv_unit_load(const DecGemvDev &p, GemvUnitOps<
             const long wi = (long)(b0 + (bl < nb ? bl : nb - 1)) * p.rep.words + (nc >> 5);
             o.rseen[r] = p.rep.seen[wi];
             o.rban[r] = p.rep.ban[wi];
+            if constexpr (EPI == DE_LOGITS_XB) {
+                const long si = (long)(b0 + (bl < nb ? bl : nb - 1)) * p.sb.words + (nc >> 5);
+                o.rhit[r] = p.sb.hit[si];
+                o.roff[r] = p.sb.woff[si];
+            }
         }
     }
     if (LN) {
@@ -301,7 +317,8 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             v = acc[r] + o.c2v;
         }
         bool rbanned = false;
-        if constexpr (EPI == DE_LOGITS_XR) {
+        const float vraw = v;   // DE_LOGITS_XB: no_speech_prob is read from the raw logits
+        if constexpr (de_has_rep(EPI)) {
             // repetition rules first: the penalised value REPLACES the logit for everything below (keys, scores, partials,
             // the winners' raw logits, the stored row); a banned id is treated like a suppressed one.  The bitmaps hold ids
             // < eot only (wm_repeat_state) and are empty at a prompt position.
@@ -309,6 +326,18 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             const unsigned bit = 1u << (n & 31);
             if (o.rseen[r] & bit) v = v > 0.f ? __fmul_rn(v, rp.inv_p) : __fmul_rn(v, rp.p);
             rbanned = (o.rban[r] & bit) != 0u;
+            if constexpr (EPI == DE_LOGITS_XB) {
+                // sequence bias behind the penalty: v + total(n), ONE f32 add for every id (total = +0.0f without a matching
+                // entry); only a set hit bit pays for the lookup, ONE load: the list is sorted by id, so the id's place in it is
+                // the word's offset + the hit bits below the id.  A banned id has total -inf and its ban bit set.
+                float tot = 0.f;
+                if (o.rhit[r] & bit) {
+                    int at = o.roff[r] + __popc(o.rhit[r] & (bit - 1u));
+                    at = at < 0 ? 0 : (at < WM_MAX_BIAS_ENTRIES ? at : WM_MAX_BIAS_ENTRIES - 1);
+                    tot = p.sb.ltot[(long)(b0 + (bl < nb ? bl : nb - 1)) * WM_MAX_BIAS_ENTRIES + at];
+                }
+                v = __fadd_rn(v, tot);
+            }
         }
         if (de_is_x(EPI)) {
             // extended decode: the DE_LOGITS keys (timestamp rules or the plain [arg_first, arg_last] range), over
@@ -317,7 +346,7 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             // position only, the unfiltered one over the whole vocabulary (no_speech_prob).  Wave-uniform branches.
             const WmXPar xp = *p.x.par;
             const unsigned mw = (pos == p.mask_first_pos) ? mword1 : mword0;
-            const bool ok = bvalid && nvalid && !((mw >> (n & 31)) & 1u) && !(EPI == DE_LOGITS_XR && rbanned);
+            const bool ok = bvalid && nvalid && !((mw >> (n & 31)) & 1u) && !(de_has_rep(EPI) && rbanned);
             const bool ts_on = p.ts.rng != nullptr;
             const bool in_text = ts_on ? (ok && n >= o.trng[r].x && n < o.trng[r].y) : (ok && n >= p.arg_first && n <= p.arg_last);
             const bool in_ts = ts_on && ok && n >= o.trng[r].z && n < o.trng[r].w;
@@ -359,14 +388,15 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             }
             if (pos == xp.sot_pos) {  // wave-uniform: openai-whisper reads no_speech_prob before any filter
                 const bool any = bvalid && nvalid;
-                float ma = any ? v : -1e30f;
+                const float vn = EPI == DE_LOGITS_XB ? vraw : v;   // (the history is empty here: the penalty has not touched it)
+                float ma = any ? vn : -1e30f;
 #pragma unroll
                 for (int q = 1; q < 16; q <<= 1) ma = fmaxf(ma, __shfl_xor(ma, q));
-                float sa = any ? __expf(v - ma) : 0.f;
+                float sa = any ? __expf(vn - ma) : 0.f;
 #pragma unroll
                 for (int q = 1; q < 16; q <<= 1) sa += __shfl_xor(sa, q);
                 if (bvalid && nrow == 0) *(float2 *)(p.x.all + ti * 2) = make_float2(ma, sa);
-                if (bvalid && n == xp.ns_tok) p.x.ns_v[b] = v;
+                if (bvalid && n == xp.ns_tok) p.x.ns_v[b] = vn;
             }
             if (bvalid && nvalid && p.out_f32) p.out_f32[(long)b * p.ldo + n] = v;
             continue;
@@ -563,7 +593,8 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
     if (EPI == DE_QKV) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); }
     if (EPI == DE_QKV_P) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); GEMV_PIN(p.panel); }
     if (EPI == DE_GELU) GEMV_PIN(p.out_bf16);
-    if (EPI == DE_LOGITS_XR) { GEMV_PIN(p.rep.par); GEMV_PIN(p.rep.seen); GEMV_PIN(p.rep.ban); GEMV_PIN(p.rep.words); }
+    if (de_has_rep(EPI)) { GEMV_PIN(p.rep.par); GEMV_PIN(p.rep.seen); GEMV_PIN(p.rep.ban); GEMV_PIN(p.rep.words); }
+    if (EPI == DE_LOGITS_XB) { GEMV_PIN(p.sb.hit); GEMV_PIN(p.sb.woff); GEMV_PIN(p.sb.ltot); GEMV_PIN(p.sb.words); }
     if (de_is_logits(EPI)) {
         GEMV_PIN(p.tilemax); GEMV_PIN(p.arg_first); GEMV_PIN(p.arg_last); GEMV_PIN(p.mask); GEMV_PIN(p.mask_words);
         GEMV_PIN(p.mask_first_pos); GEMV_PIN(p.ts.rng); GEMV_PIN(p.ts.key_ts); GEMV_PIN(p.ts.lse); GEMV_PIN(p.ts.ts_begin);
@@ -1929,6 +1960,7 @@ const struct GemvEpi {
     {DE_LOGITS, true, "dec_gemv_ln_logits", nullptr, launch_gemv<DE_LOGITS, true>},
     {DE_LOGITS_X, true, "dec_gemv_ln_logits_x", nullptr, launch_gemv<DE_LOGITS_X, true>},
     {DE_LOGITS_XR, true, "dec_gemv_ln_logits_xr", nullptr, launch_gemv<DE_LOGITS_XR, true>},
+    {DE_LOGITS_XB, true, "dec_gemv_ln_logits_xb", nullptr, launch_gemv<DE_LOGITS_XB, true>},
     {DE_RESID, false, "dec_gemv_attn_out", "dec_gemv_fc2", launch_gemv<DE_RESID, false>},
     {DE_Q, false, "dec_gemv_plain", nullptr, launch_gemv<DE_Q, false>},
 };
@@ -1943,8 +1975,10 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
     WM_REQUIRE(a.epi != DE_QKV_P || (a.panel >= 1 && a.panel <= WM_MAX_TEACHER_PANEL && a.pos_ptr), WM_ERR_INVALID,
                "dec_gemv: DE_QKV_P needs a panel width of 1 .. %d and the device position", WM_MAX_TEACHER_PANEL);
     WM_REQUIRE(!de_is_x(a.epi) || (a.x.par && a.pos_ptr), WM_ERR_INVALID, "dec_gemv: DE_LOGITS_X needs its state and the device position");
-    WM_REQUIRE(a.epi != DE_LOGITS_XR || (a.rep.par && a.rep.seen && a.rep.ban && (long)a.rep.words * 32 >= a.N), WM_ERR_INVALID,
+    WM_REQUIRE(!de_has_rep(a.epi) || (a.rep.par && a.rep.seen && a.rep.ban && (long)a.rep.words * 32 >= a.N), WM_ERR_INVALID,
                "dec_gemv: DE_LOGITS_XR needs the repetition-rule state");
+    WM_REQUIRE(a.epi != DE_LOGITS_XB || (a.sb.hit && a.sb.woff && a.sb.ltot && (long)a.sb.words * 32 >= a.N), WM_ERR_INVALID,
+               "dec_gemv: DE_LOGITS_XB needs the sequence-bias state");
     const GemvEpi *e = nullptr;
     for (const GemvEpi &c : kGemvEpi)
         if (c.epi == a.epi && c.ln == ln) e = &c;
@@ -1969,6 +2003,7 @@ int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a) {
     p.x = a.x;
     p.rep = a.rep;
     p.panel = a.panel;
+    p.sb = a.sb;
     p.n_tiles = pl.n_tiles; p.bgroups = pl.bgroups; p.n_tg = pl.n_tg; p.n_tg_pad = pl.n_tg_pad;
     if (pl.pf_tiles) {   // (no warm-up: the pointer stays null)
         p.pf_ptr = (const char *)a.pf_ptr;

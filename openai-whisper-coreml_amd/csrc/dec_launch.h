@@ -20,9 +20,13 @@ constexpr int WM_ATT_MAXK = 1536;  // keys per (sequence, head) pair the attenti
 // the logit first -- again its own instantiations, so DE_LOGITS_X stays instruction for instruction what it was
 // DE_QKV_P: DE_QKV of a panel step (DecGemvArgs::panel = w): k / v of row r go to cache entry r / w at position *pos_ptr + r % w --
 // its own instantiations, so DE_QKV stays instruction for instruction what it was
-enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5, DE_LOGITS_XR = 6, DE_QKV_P = 7 };
-// the extended-decode epilogues (DE_LOGITS_XR = DE_LOGITS_X + the repetition rules), and every logits epilogue
-constexpr bool de_is_x(int epi) { return epi == DE_LOGITS_X || epi == DE_LOGITS_XR; }
+// DE_LOGITS_XB: DE_LOGITS_XR with the sequence bias (WmSbDev): the same body, the row's bias total added
+// to the logit behind the penalty -- its own instantiations once more, so DE_LOGITS_X and DE_LOGITS_XR stay what they were
+enum DecEpi { DE_QKV = 0, DE_Q = 1, DE_RESID = 2, DE_GELU = 3, DE_LOGITS = 4, DE_LOGITS_X = 5, DE_LOGITS_XR = 6, DE_QKV_P = 7, DE_LOGITS_XB = 8 };
+// the extended-decode epilogues (DE_LOGITS_XR = DE_LOGITS_X + the repetition rules, DE_LOGITS_XB = DE_LOGITS_XR + the sequence
+// bias), the ones that read the repetition bitmaps, and every logits epilogue
+constexpr bool de_is_x(int epi) { return epi == DE_LOGITS_X || epi == DE_LOGITS_XR || epi == DE_LOGITS_XB; }
+constexpr bool de_has_rep(int epi) { return epi == DE_LOGITS_XR || epi == DE_LOGITS_XB; }
 constexpr bool de_is_logits(int epi) { return epi == DE_LOGITS || de_is_x(epi); }
 constexpr bool de_is_qkv(int epi) { return epi == DE_QKV || epi == DE_QKV_P; }
 

@@ -95,6 +95,29 @@ static int alloc_repetition_state(WmModel *m, hipStream_t s) {
     return WM_OK;
 }
 
+// the sequence-bias state at FULL capacity (WM_MAX_BIAS_ENTRIES entries, WM_DEC_MAXB rows), once
+static int alloc_seqbias_state(WmModel *m, hipStream_t s) {
+    const size_t cap = WM_MAX_BIAS_ENTRIES, words = (size_t)(m->vpad + 31) / 32;
+    int *grp_id, *grp_beg, *ent_len, *ent_ctx;
+    float *ent_bias;
+    WM_TRY(dalloc_t(m, &grp_id, cap, s));
+    WM_TRY(dalloc_t(m, &grp_beg, cap + 1, s));
+    WM_TRY(dalloc_t(m, &ent_len, cap, s));
+    WM_TRY(dalloc_t(m, &ent_bias, cap, s));
+    WM_TRY(dalloc_t(m, &ent_ctx, cap * WM_SB_CTX, s));
+    WM_TRY(dalloc_t(m, &m->dsb.e.hit, (size_t)WM_DEC_MAXB * words, s));
+    WM_TRY(dalloc_t(m, &m->dsb.e.cnt, (size_t)WM_DEC_MAXB, s));
+    WM_TRY(dalloc_t(m, &m->dsb.e.lid, (size_t)WM_DEC_MAXB * cap, s));
+    WM_TRY(dalloc_t(m, &m->dsb.e.ltot, (size_t)WM_DEC_MAXB * cap, s));
+    WM_TRY(dalloc_t(m, &m->dsb.e.woff, (size_t)WM_DEC_MAXB * words, s));
+    WmSbPar *par;
+    WM_TRY(dalloc(m, (void **)&par, sizeof(WmSbPar), s));
+    m->dsb.grp_id = grp_id; m->dsb.grp_beg = grp_beg; m->dsb.ent_len = ent_len; m->dsb.ent_bias = ent_bias; m->dsb.ent_ctx = ent_ctx;
+    m->dsb.e.words = (int)words;
+    m->dsb.par = par;   // last: non-null = allocated
+    return WM_OK;
+}
+
 WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode) {
     WmStopDev t;
     memset(&t, 0, sizeof(t));
@@ -202,8 +225,41 @@ WmRepDev wm_model_rep_dev(const WmModel *m, const WmDecodeMode &mode) {
     return t;
 }
 
+WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode) {
+    WmSbDev t;
+    memset(&t, 0, sizeof(t));
+    if (!mode.sb) return t;
+    return m->dsb;
+}
+
 // the bitmaps and the parameter block, once (captured graphs hold these addresses)
 static int alloc_repetition_state(WmModel *m, hipStream_t s);
+
+int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m, WM_ERR_STATE, "context has no model");
+    const int ng = t.n_groups(), ne = t.n_entries();
+    WM_REQUIRE(ne <= WM_MAX_BIAS_ENTRIES && ng <= ne && (int)t.grp_beg.size() == (ne ? ng + 1 : 0) && (int)t.ent_bias.size() == ne &&
+                   t.ent_ctx.size() == (size_t)ne * WM_SB_CTX,
+               WM_ERR_INVALID, "sequence bias: malformed table");
+    if (ne) {
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
+        WM_REQUIRE(((size_t)3 * ((m->vpad + 31) / 32) + WM_MAX_BIAS_ENTRIES + 512) * 4 <= 64 * 1024 && (m->vpad + 31) / 32 <= 2048, WM_ERR_INVALID,
+                   "sequence bias: a vocabulary of %d ids does not fit the state kernel's LDS", m->dims.n_vocab);
+        // the bitmaps are wm_repeat_state's: a group with the bias on runs it too (with (1.0, 0) when the repetition rules are off)
+        if (!m->drep_par) WM_TRY(alloc_repetition_state(m, ctx->stream));
+        if (!m->dsb.par) WM_TRY(alloc_seqbias_state(m, ctx->stream));
+        hipStream_t s = ctx->stream;
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.grp_id, t.grp_id.data(), (size_t)ng * 4, hipMemcpyHostToDevice, s));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.grp_beg, t.grp_beg.data(), (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, s));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_len, t.ent_len.data(), (size_t)ne * 4, hipMemcpyHostToDevice, s));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_bias, t.ent_bias.data(), (size_t)ne * 4, hipMemcpyHostToDevice, s));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_ctx, t.ent_ctx.data(), (size_t)ne * WM_SB_CTX * 4, hipMemcpyHostToDevice, s));
+        WM_HIP(hipStreamSynchronize(s));   // (the table's vectors are the caller's)
+    }
+    m->sb_on = ne > 0; m->sb_groups = ng; m->sb_entries = ne;
+    return WM_OK;
+}
 
 int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t eot) {
     WmModel *m = ctx->model;
@@ -431,7 +487,17 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->align_l = pm->align_l; m->align_h = pm->align_h;
     m->teacher_panel = pm->teacher_panel;
     m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
-    if (m->rep_on) WM_TRY(alloc_repetition_state(m, child->stream));
+    if (m->rep_on || pm->sb_on) WM_TRY(alloc_repetition_state(m, child->stream));
+    if (pm->sb_on) {   // the parent's device table, as the suppress bitmaps above
+        WM_TRY(alloc_seqbias_state(m, child->stream));
+        const size_t ng = (size_t)pm->sb_groups, ne = (size_t)pm->sb_entries;
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.grp_id, pm->dsb.grp_id, ng * 4, hipMemcpyDeviceToDevice, child->stream));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.grp_beg, pm->dsb.grp_beg, (ng + 1) * 4, hipMemcpyDeviceToDevice, child->stream));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_len, pm->dsb.ent_len, ne * 4, hipMemcpyDeviceToDevice, child->stream));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_bias, pm->dsb.ent_bias, ne * 4, hipMemcpyDeviceToDevice, child->stream));
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_ctx, pm->dsb.ent_ctx, ne * WM_SB_CTX * 4, hipMemcpyDeviceToDevice, child->stream));
+        m->sb_on = true; m->sb_groups = pm->sb_groups; m->sb_entries = pm->sb_entries;
+    }
     WM_HIP(hipStreamSynchronize(child->stream));
     return WM_OK;
 }
@@ -879,6 +945,12 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
             WM_REQUIRE(mode.x, WM_ERR_STATE, "decode step: the repetition rules need the extended decode");
             a.epi = DE_LOGITS_XR; a.rep = wm_model_rep_dev(m, mode);
             WM_TRY(wm_repeat_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, a.rep));
+        }
+        if (mode.sb) {   // sequence bias: the rows' hit words and totals, behind the bitmaps it ORs its bans into
+            WM_REQUIRE(mode.rep, WM_ERR_STATE, "decode step: the sequence bias needs the repetition-rule state");
+            const WmSbDev sb = wm_model_sb_dev(m, mode);
+            a.epi = DE_LOGITS_XB; a.sb = sb.e;
+            WM_TRY(wm_seqbias_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, sb, a.rep.ban, a.rep.words));
         }
         WM_TRY(wm_dec_gemv(ctx, a));
     }

@@ -129,6 +129,46 @@ struct WmRepDev {
 };
 constexpr int WM_MAX_NGRAM = 32;
 
+// The sequence bias (wm_set_sequence_bias; seqbias.hip): a table of token sequences with a bias each.
+// Entry s[0 .. n) matches a row iff n == 1 or the row's generated history g[0 .. k) ends in s[0 .. n - 1); total(t) is the f32
+// sum, from +0.0f in table order, of the biases of the matching entries whose last token is t, and the logit becomes
+// v[t] + total(t) behind the repetition penalty.  A total of -inf is a ban (OR-ed into WmRepDev::ban).  The table is expanded
+// (boosted prefixes), sorted stably by last token and uploaded at set time: entries with the same last token form a GROUP,
+// groups ascend by id.  wm_seqbias_state REBUILDS the per-row state from the history in front of every logits launch, behind
+// wm_repeat_state; the DE_LOGITS_XB epilogue adds the totals.  What changes from call to call lives in device memory.
+struct WmSbPar {
+    int n_groups, n_entries;
+};
+// what the epilogue reads (the LAST member of the GEMV's kernel-argument struct)
+struct WmSbEpi {
+    unsigned *hit;   // [rows][words] ids with a matching entry at this position (bans included: their total is -inf)
+    int *cnt;        // [rows] list length
+    int *lid;        // [rows][WM_MAX_BIAS_ENTRIES] the ids of the hit bits, ascending
+    float *ltot;     // [rows][WM_MAX_BIAS_ENTRIES] their totals
+    int *woff;       // [rows][words] hit bits in the words below: total(t) = ltot[woff[t >> 5] + popcount(hit bits of the word below t)]
+    int words;       // (vpad + 31) / 32
+};
+struct WmSbDev {
+    const WmSbPar *par;      // null: the bias is off
+    const int *grp_id;       // [WM_MAX_BIAS_ENTRIES] last token of group g, ascending
+    const int *grp_beg;      // [WM_MAX_BIAS_ENTRIES + 1] group g = entries [grp_beg[g], grp_beg[g + 1])
+    const int *ent_len;      // [WM_MAX_BIAS_ENTRIES] context length n - 1 of entry e (0 .. 31)
+    const float *ent_bias;   // [WM_MAX_BIAS_ENTRIES]
+    const int *ent_ctx;      // [WM_MAX_BIAS_ENTRIES][WM_SB_CTX] context of entry e, NEWEST token first: s[n - 2], s[n - 3], ...
+    WmSbEpi e;
+};
+constexpr int WM_SB_CTX = WM_MAX_BIAS_SEQ_LEN - 1;
+// The expanded table on the host (wm_sb_expand: validation, prefix expansion, merge, stable sort by last token).
+struct WmSbTable {
+    std::vector<int32_t> grp_id, grp_beg, ent_len, ent_ctx;   // ent_ctx: [n_entries][WM_SB_CTX], newest first, padded with 0
+    std::vector<float> ent_bias;
+    int n_groups() const { return (int)grp_id.size(); }
+    int n_entries() const { return (int)ent_len.size(); }
+};
+// WM_OK, or WM_ERR_INVALID with the message set; n_seq = 0 gives the empty table.  Pure host code (model_api.cpp).
+int wm_sb_expand(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq,
+                 int32_t eot, int n_vocab, WmSbTable *out);
+
 // Early-stop state of a decode group (device view; done == null: off).  A row is DONE once it has emitted `eot`
 // (eot >= 0) or produced budget[b] tokens (budget != null); from then on its tokens are `pad_tok`, it is dropped from
 // the compact live list the attention kernels walk, and when the list is empty the host stops launching positions.
@@ -222,13 +262,16 @@ struct WmDecodeMode {
     // (wm_model_beam_close) instead of the arg-max; above 1 the rows are a candidate group (n_cand = beam).
     int beam = 0;
     bool rep = false;       // the repetition rules apply (wm_set_repetition_rules, WmRepDev): wm_repeat_state + DE_LOGITS_XR; needs x
+    // The sequence bias applies (wm_set_sequence_bias, WmSbDev): wm_seqbias_state behind wm_repeat_state + DE_LOGITS_XB.  A group
+    // with sb has rep too -- the bitmaps are wm_repeat_state's, rebuilt with the rules (1.0, 0) when the repetition rules are off.
+    bool sb = false;
     // Panel width of a teacher-forced pass (wm_set_teacher_panel; 1: none): the step's rows are windows x panel, row c * panel + s
     // is position *dpos + s of window c -- the self-attention cache holds one entry per WINDOW, row (c, s) appends at and reads up
     // to its own position, the cross-attention is the candidate-group launch (wm_model_panel_step).  The teacher-forced entries
     // run eagerly, but a mode is a graph key member by member, so it is compared like the others.
     int panel = 1;
     bool operator==(const WmDecodeMode &o) const {
-        return panel == o.panel && rep == o.rep && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return panel == o.panel && rep == o.rep && sb == o.sb && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -370,6 +413,11 @@ struct WmModel {
     int rep_n = 0, rep_eot = 0;
     unsigned *drep_seen = nullptr, *drep_ban = nullptr;   // [WM_DEC_MAXB][(vpad + 31) / 32]
     WmRepPar *drep_par = nullptr;
+    // sequence bias (wm_set_sequence_bias): the context's expanded table, and the device state allocated at full capacity when
+    // first switched on (dsb.par == null before that) -- never moved: the captured graphs hold the addresses
+    bool sb_on = false;
+    int sb_groups = 0, sb_entries = 0;
+    WmSbDev dsb = {};
     unsigned *dx_ids = nullptr;    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     int *dxkv_rows = nullptr;      // [WM_DEC_MAXB] the group's rows of a window set (wm_transcribe_windows): the gather's row map
@@ -442,6 +490,10 @@ WmTsDev wm_model_ts_dev(const WmModel *m);
 WmRepDev wm_model_rep_dev(const WmModel *m, const WmDecodeMode &mode);
 // (1.0, 0, any eot) switches the rules off; the first enabling call allocates the bitmaps
 int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t eot);
+// the device view of the sequence-bias state (par == null when mode.sb is false)
+WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode);
+// an expanded table (empty: off) -> this context's device table; the first non-empty one allocates the state
+int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t);
 int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int32_t eot, int32_t max_initial);
 int wm_model_set_suppress(wm_ctx *ctx, const int32_t *ids, int n, const int32_t *first_ids, int n_first);
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode = WmDecodeMode());
@@ -556,7 +608,8 @@ struct DecGemvArgs {
     const bf16_t *pf_ptr;
     int pf_rows, pf_k;
     int pf_head_major;     // the next launch is wm_dec_xattn_fq: (pairs per XCD) place every head's tiles on the XCD(s) that run it
-    WmRepDev rep;          // DE_LOGITS_XR: repetition rules (rep.par non-null)
+    WmRepDev rep;          // DE_LOGITS_XR / _XB: repetition rules (rep.par non-null)
+    WmSbEpi sb;            // DE_LOGITS_XB: sequence bias (sb.hit non-null)
     int panel;             // DE_QKV_P: panel width w (1 .. WM_MAX_TEACHER_PANEL); kcache / vcache are [ceil(B / w)][H][T][64]
 };
 int wm_dec_gemv(wm_ctx *ctx, const DecGemvArgs &a);
@@ -661,6 +714,13 @@ int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, co
 // Rebuild rows 0 .. B - 1 of rep.seen / rep.ban from the generated history of position *pos_ptr: tokens seq[(n_prompt + i) * B + b],
 // i < min(*pos_ptr + 1 - n_prompt, n_ctx - n_prompt) (none at a prompt position).  V: ids at or above it set no bit.
 int wm_repeat_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int n_prompt, int n_ctx, int V, const WmRepDev &rep);
+
+// seqbias.hip (sequence bias)
+// Rebuild rows 0 .. B - 1 of sb.e (hit bitmap, sorted (id, total) list, count) from the generated history of position *pos_ptr, as
+// wm_repeat_state reads it, and OR the banned ids (total -inf) into ban [B][ban_words] -- which a wm_repeat_state launch in front
+// of this one has rebuilt.  V: ids at or above it set no bit.
+int wm_seqbias_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int n_prompt, int n_ctx, int V, const WmSbDev &sb,
+                     unsigned *ban, int ban_words);
 
 // xkv_rows.hip (window sets)
 // Copy whole windows between a decode group's cross-attention K/V cache, group [L2][group_rows][slab] (slab = H * 1500 * 64

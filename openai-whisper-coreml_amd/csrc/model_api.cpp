@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <map>
 #include <vector>
 
 #include "call_src.h"
@@ -65,6 +66,85 @@ extern "C" int wm_set_repetition_rules(wm_ctx *ctx, float repetition_penalty, in
     return wm_for_each_lane(ctx, true, [&](wm_ctx *c) {
         return wm_model_set_repetition_rules(c, repetition_penalty, no_repeat_ngram_size, eot);
     });
+} WM_API_CATCH
+// The table of wm_set_sequence_bias, checked and expanded: given sequences in order, each followed by its implicit prefix
+// entries (shortest first); implicit entries with identical tokens merged into the first of them with the maximum bias, an
+// implicit entry identical to a given sequence dropped; then a STABLE sort by last token, so that the entries of one id are a
+// contiguous group in table order -- the order of the f32 sum.  Contexts are stored newest token first.
+int wm_sb_expand(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq,
+                 int32_t eot, int n_vocab, WmSbTable *out) {
+    *out = WmSbTable();
+    WM_REQUIRE(n_seq >= 0, WM_ERR_INVALID, "sequence bias: n_seq %d", n_seq);
+    WM_REQUIRE(eot >= 0 && eot <= n_vocab, WM_ERR_INVALID, "sequence bias: eot %d outside [0, %d]", eot, n_vocab);
+    if (n_seq == 0) return WM_OK;
+    WM_REQUIRE(tokens && seq_offsets && bias, WM_ERR_INVALID, "sequence bias: null pointer");
+    WM_REQUIRE(n_seq <= WM_MAX_BIAS_ENTRIES, WM_ERR_INVALID, "sequence bias: %d sequences, at most %d entries", n_seq, WM_MAX_BIAS_ENTRIES);
+    WM_REQUIRE(seq_offsets[0] == 0, WM_ERR_INVALID, "sequence bias: seq_offsets[0] must be 0");
+    struct Ent { std::vector<int32_t> tok; float bias; bool given; };
+    std::vector<Ent> ents;
+    std::map<std::vector<int32_t>, int> given, implicit;   // tokens -> index in ents
+    for (int i = 0; i < n_seq; ++i) {
+        const long n = (long)seq_offsets[i + 1] - seq_offsets[i];
+        WM_REQUIRE(n >= 1 && n <= WM_MAX_BIAS_SEQ_LEN, WM_ERR_INVALID, "sequence bias: sequence %d has %ld tokens (1 .. %d)", i, n,
+                   WM_MAX_BIAS_SEQ_LEN);
+        const int32_t *t = tokens + seq_offsets[i];
+        for (long j = 0; j < n; ++j)
+            WM_REQUIRE(t[j] >= 0 && t[j] < n_vocab, WM_ERR_INVALID, "sequence bias: token %d of sequence %d outside [0, %d)", t[j], i, n_vocab);
+        WM_REQUIRE(t[n - 1] < eot, WM_ERR_INVALID, "sequence bias: sequence %d ends in %d, not a text id (< %d)", i, t[n - 1], eot);
+        WM_REQUIRE(!std::isnan(bias[i]) && bias[i] != INFINITY, WM_ERR_INVALID, "sequence bias: the bias of sequence %d must be finite or -inf", i);
+        WM_REQUIRE(!(boost_prefixes && boost_prefixes[i]) || std::isfinite(bias[i]), WM_ERR_INVALID,
+                   "sequence bias: sequence %d boosts its prefixes, which needs a finite bias", i);
+        std::vector<int32_t> key(t, t + n);
+        WM_REQUIRE(given.emplace(key, i).second, WM_ERR_INVALID, "sequence bias: sequence %d repeats an earlier one", i);
+    }
+    for (int i = 0; i < n_seq; ++i) {
+        const int32_t *t = tokens + seq_offsets[i];
+        const int n = seq_offsets[i + 1] - seq_offsets[i];
+        ents.push_back(Ent{std::vector<int32_t>(t, t + n), bias[i], true});
+        if (!(boost_prefixes && boost_prefixes[i])) continue;
+        for (int j = 1; j < n; ++j) {
+            if (t[j - 1] >= eot) continue;   // (a prefix that ends in a special: only text ids are ever biased)
+            std::vector<int32_t> key(t, t + j);
+            if (given.count(key)) continue;   // the caller has said what that sequence is worth
+            auto it = implicit.find(key);
+            if (it != implicit.end()) {
+                Ent &e = ents[it->second];
+                e.bias = bias[i] > e.bias ? bias[i] : e.bias;
+                continue;
+            }
+            implicit.emplace(key, (int)ents.size());
+            ents.push_back(Ent{key, bias[i], false});
+        }
+    }
+    WM_REQUIRE((int)ents.size() <= WM_MAX_BIAS_ENTRIES, WM_ERR_INVALID, "sequence bias: %d entries after the prefix expansion, at most %d",
+               (int)ents.size(), WM_MAX_BIAS_ENTRIES);
+    std::vector<int> order(ents.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ents[a].tok.back() < ents[b].tok.back(); });
+    out->ent_ctx.assign(ents.size() * WM_SB_CTX, 0);
+    for (size_t k = 0; k < order.size(); ++k) {
+        const Ent &e = ents[order[k]];
+        const int n = (int)e.tok.size();
+        if (out->grp_id.empty() || out->grp_id.back() != e.tok[n - 1]) {
+            out->grp_id.push_back(e.tok[n - 1]);
+            out->grp_beg.push_back((int32_t)k);
+        }
+        out->ent_len.push_back(n - 1);
+        out->ent_bias.push_back(e.bias);
+        for (int j = 0; j < n - 1; ++j) out->ent_ctx[k * WM_SB_CTX + j] = e.tok[n - 2 - j];
+    }
+    out->grp_beg.push_back((int32_t)ents.size());
+    return WM_OK;
+}
+
+extern "C" int wm_set_sequence_bias(wm_ctx *ctx, const int32_t *tokens, const int32_t *seq_offsets, const float *bias,
+                                    const uint8_t *boost_prefixes, int n_seq, int32_t eot) try {
+    WM_MODEL(ctx);
+    // checked and expanded ONCE, before any lane is touched: a refused call leaves the table in force where it was
+    WmSbTable t;
+    WM_TRY(wm_sb_expand(tokens, seq_offsets, bias, boost_prefixes, n_seq, eot, m->dims.n_vocab, &t));
+    WM_REQUIRE(t.n_entries() == 0 || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { return wm_model_set_sequence_bias(c, t); });
 } WM_API_CATCH
 extern "C" int wm_set_teacher_panel(wm_ctx *ctx, int width) try {
     WM_MODEL(ctx);

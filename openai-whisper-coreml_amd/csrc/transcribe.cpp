@@ -64,6 +64,7 @@ struct LaneJob {
     std::vector<int32_t> gen;      // its fetched token stream [max_new][Bg]
     WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
     WmRepPar rpar = {};            // its repetition rules (likewise)
+    WmSbPar sbpar = {};            // its sequence-bias table's counts (likewise)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
     std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
     std::vector<int32_t> xrows;    // its rows of the window set (wm_transcribe_windows)
@@ -141,7 +142,8 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
     j.mode.n_cand = N;
     j.mode.beam = call.beam ? N : 0;
-    j.mode.rep = m->rep_on;   // (tx_validate turns the extended decode on with them)
+    j.mode.sb = m->sb_on;
+    j.mode.rep = m->rep_on || m->sb_on;   // (tx_validate turns the extended decode on with them; the bias reads the rules' bitmaps)
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
     const void *d_pcm;
@@ -174,7 +176,13 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     if (j.mode.rep) {
         WM_REQUIRE(xc.on, WM_ERR_STATE, "the repetition rules need the extended decode");
         j.rpar.p = m->rep_p; j.rpar.inv_p = (float)(1.0 / (double)m->rep_p); j.rpar.n = m->rep_n; j.rpar.eot = m->rep_eot;
+        if (!m->rep_on) { j.rpar.p = 1.f; j.rpar.inv_p = 1.f; j.rpar.n = 0; j.rpar.eot = 0; }   // the sequence bias alone: empty rules
         WM_HIP(hipMemcpyAsync(m->drep_par, &j.rpar, sizeof(WmRepPar), hipMemcpyHostToDevice, c->stream));
+    }
+    // sequence bias: the table was uploaded when it was set; its counts go with the group, so a captured graph replays for any table
+    if (j.mode.sb) {
+        j.sbpar.n_groups = m->sb_groups; j.sbpar.n_entries = m->sb_entries;
+        WM_HIP(hipMemcpyAsync((void *)m->dsb.par, &j.sbpar, sizeof(WmSbPar), hipMemcpyHostToDevice, c->stream));
     }
     WM_TRY(wm_model_reserve(c, Cg));
     if (N > 1) WM_TRY(wm_model_reserve_rows(c, Bg));
@@ -462,8 +470,9 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     WM_REQUIRE(!call.no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
     WM_REQUIRE(!call.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
     // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
-    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on;
+    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on;
     WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
+    WM_REQUIRE(!m->sb_on || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
     xc.logprobs = call.logprobs_out;
     xc.no_speech = call.no_speech_out;
     const uint64_t seed = opts ? opts->seed : 0;

@@ -218,6 +218,28 @@ struct Whisper {
         try check(f(ctx, width))
     }
 
+    /// The sequence bias of every later transcribe call on this context (wm_set_sequence_bias): `sequences[i]` carries `bias[i]`
+    /// (finite, or -.infinity = a banned sequence), added to the logit of its last token whenever a window's generated tokens end
+    /// in its other tokens; `boostPrefixes[i]` biases every proper prefix too, so a phrase is helped from its first token on.
+    /// Only ids < eot may end a sequence.  The ids are the caller's tokenizer's: " word" and "word" are different ids, both
+    /// variants are the caller's to list.  An empty list switches the bias off.
+    /// Not compiled in this repository (see the top of the file).
+    func setSequenceBias(sequences: [[Int32]] = [], bias: [Float] = [], boostPrefixes: [Bool] = [], eot: Int32 = 50257) throws {
+        typealias BiasFn = @convention(c) (OpaquePointer, UnsafePointer<Int32>?, UnsafePointer<Int32>?, UnsafePointer<Float>?,
+                                           UnsafePointer<UInt8>?, Int32, Int32) -> Int32
+        let f: BiasFn = try sym("wm_set_sequence_bias")
+        precondition(bias.count == sequences.count && (boostPrefixes.isEmpty || boostPrefixes.count == sequences.count))
+        if sequences.isEmpty {
+            try check(f(ctx, nil, nil, nil, nil, 0, eot))
+            return
+        }
+        var offsets: [Int32] = [0]
+        for s in sequences { offsets.append(offsets.last! + Int32(s.count)) }
+        let tokens = sequences.flatMap { $0 }
+        let flags: [UInt8] = boostPrefixes.map { $0 ? 1 : 0 }
+        try check(f(ctx, tokens, offsets, bias, flags.isEmpty ? nil : flags, Int32(sequences.count), eot))
+    }
+
     /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
     /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
     /// Not compiled in this repository (see the top of the file).
