@@ -440,7 +440,62 @@ WM_API int wm_align_windows(wm_ctx *ctx, const wm_windows *w, const int32_t *row
 WM_API int wm_windows_detect_language(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, int32_t sot,
                                       int32_t lang_first, int32_t lang_last, int32_t *lang_idx, float *probs /* nullable */);
 
-/* The alignment heads wm_align and wm_align_mel read: n (layer, head) pairs, any order (used ascending).  n = 0 restores the default, every
+/* ------------------------------------------------------------- word timestamps from the decode's own pass --- */
+/* wm_transcribe_mel_ragged (prompt_len NULL: wm_transcribe_mel) that ALSO aligns what it generates, from the cross-attention
+ * queries the decode itself formed: no second, teacher-forced pass (wm_align_mel re-runs the decoder over the kept text, which
+ * is 93 % of its cost).  This is how Hugging Face's return_token_timestamps works.  Every argument but medfilt_width, qk_scale
+ * and start_frame_out is that call's, and tokens_out, lens_out, token_logprobs_out and no_speech_prob_out are BIT FOR BIT
+ * that call's for the same arguments -- at any temperature, with suppress lists, timestamp rules, repetition rules, sequence
+ * bias, token budgets, early stop and any lane count: the decoder layers with alignment heads form their query in a launch of
+ * its own instead of inside the cross-attention launch (the same bits), and nothing else changes.
+ * Row b, with a_b the prompt index of <|startoftranscript|> (prompt_len[b] - sot_tail; a uniform call: opts->sot_index, 0
+ * without opts), P_b its prompt length, g[0 .. len_b) its generated tokens (a stopping eot included), M_b = n_frames[b] / 2:
+ *   1. decoder rows: the inputs u = prompt[a_b .. P_b) ++ g[0 .. len_b - 1), R_b = (P_b - a_b) + len_b - 1 of them -- the last
+ *      generated token is never fed; prompt positions in front of <|startoftranscript|> (previous text) are no rows;
+ *   2. - 4. of wm_align over these R_b rows and the frames [0, M_b): softmax of q.k / 8 * qk_scale per alignment head
+ *      (wm_set_alignment_heads, the same default), z-score per head and frame over the R_b rows (std with 1 / R_b), median
+ *      filter of medfilt_width with reflect padding;
+ *   5. -mean over the heads of the LAST len_b rows: matrix row k is the decoder position whose OUTPUT was g[k] -- wm_align's
+ *      row meaning (the row in front of text token i belongs to token i), except that no row follows the final token
+ *      (wm_align teacher-forces eot as an input, a decode never does);
+ *   6. wm_align's DTW on [len_b][M_b];
+ *   7. start_frame_out[b][k], k < len_b: the first frame of row k on the path; start_frame_out[b][len_b] = M_b; -1 behind.
+ *   Degenerate rows: all -1 when len_b == 0 or n_frames[b] < 2 (the row decodes normally); R_b < 2 (one row: the standard
+ *   deviation over the rows is zero) gives start_frame_out[b] = 0, M_b, -1 ...
+ *   medfilt_width : odd, 1 .. 31;  qk_scale finite;  start_frame_out i32 [B][max_new + 1] (host).
+ * The rows are the DECODE's: its prompt, with timestamp tokens interleaved when the timestamp rules are on -- not
+ * openai-whisper's clean [sot, lang, task, <|notimestamps|>, text] pass; generated tokens >= eot (timestamps, the stopping
+ * eot) have a row and a start frame like any other, and the host drops them (binding.py decode_alignment_text).
+ * Token probabilities are NOT a new output: a word's probability on this path is exp(token_logprobs_out) -- the log-prob of
+ * the FILTERED distribution the decode sampled from (suppress lists, timestamp rules, repetition rules and bias applied, at
+ * temperature 1) -- which differs from wm_align's token_prob_out = softmax(raw logits[0 : eot]).
+ * A decode group's capture buffer (R rows x alignment heads x 64 f32 per row of the call) and alignment workspace live in the
+ * lane and grow on demand; a group holds as many rows as fit 2 GiB of them (wm_align's rule: large-v2's default 320 heads at
+ * max_new 224 behind a 3-token start sequence -> 88 rows), so a call may run in more groups than its plain counterpart --
+ * same bits.  A failed allocation is WM_ERR_NOMEM and leaks nothing.  wm_last_stage_ms[2] includes the alignment kernels
+ * and the DTW.
+ * A row's results depend on the row alone (as wm_transcribe_mel_ragged); scope and inheritance of every setting as there.
+ * No aligned counterpart exists for best_of > 1 or beam search.
+ * Invalid: medfilt_width even or outside 1 .. 31, a qk_scale that is not finite, a null start_frame_out, in a ragged call a
+ * sot_tail outside [1, the shortest prompt_len] (always read here), and everything the underlying call rejects.  The debug
+ * library's all-f32 precision path answers WM_ERR_STATE. */
+WM_API int wm_transcribe_mel_aligned(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                     const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                     int prompt_stride, const int32_t *prompt_len /* nullable */, int sot_tail,
+                                     const uint32_t *sample_ids, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                     int medfilt_width, float qk_scale, int32_t *tokens_out, int32_t *lens_out,
+                                     float *token_logprobs_out, float *no_speech_prob_out,
+                                     int32_t *start_frame_out /* [B][max_new + 1] */, wm_mem mem);
+/* ... over the windows of a set (wm_transcribe_windows with best_of 1): (w, rows, B) in place of the five mel arguments and
+ * `mem`, M_b from the set's n_frames of the row.  Bit for bit wm_transcribe_mel_aligned on the same windows. */
+WM_API int wm_transcribe_windows_aligned(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                         int prompt_stride, const int32_t *prompt_len /* nullable */, int sot_tail,
+                                         const uint32_t *sample_ids, int max_new, int32_t eot, const wm_decode_opts *opts,
+                                         int medfilt_width, float qk_scale, int32_t *tokens_out, int32_t *lens_out,
+                                         float *token_logprobs_out, float *no_speech_prob_out,
+                                         int32_t *start_frame_out /* [B][max_new + 1] */);
+
+/* The alignment heads wm_align, wm_align_mel and the aligned transcribe calls read: n (layer, head) pairs, any order (used ascending).  n = 0 restores the default, every
  * head of the decoder layers n_text_layer / 2 .. n_text_layer - 1 (openai-whisper's default when a checkpoint has no list);
  * a checkpoint's own list (openai-whisper _ALIGNMENT_HEADS, Hugging Face generation_config.alignment_heads) comes from the
  * host.  Out-of-range pairs and duplicates are invalid.  Same inheritance as wm_set_suppress. */

@@ -308,6 +308,9 @@ WM_API int wmdbg_dec_gemv_plan(const int32_t *in, int n, int32_t *out);
  *   (B * N <= 16);  out i32 [n][288], the caller's fill staying wherever no row is written = [0] tokens [B * N][max_new],
  *   [128] lens [B * N], [144] log-probs (f32 bits), [272] no-speech (f32 bits) [B]. */
 WM_API int wmdbg_tx_plan(const int32_t *in, int n, int32_t *out, int32_t *cut, int cut_cap);
+/* wmdbg_tx_plan with the plan's optional upper bound on the rows of one group beside each case (max_group_rows i32 [n]; 0:
+ * none, and then the case's plan is wmdbg_tx_plan's): an aligned transcribe call's capture budget. */
+WM_API int wmdbg_tx_plan_bounded(const int32_t *in, const int32_t *max_group_rows, int n, int32_t *out, int32_t *cut, int cut_cap);
 WM_API int wmdbg_group_tables(const int32_t *in, int n, int32_t *out);
 WM_API int wmdbg_group_rows_out(const int32_t *in, int n, int32_t *out);
 /* The cross-attention launch of a candidate group exactly as the decode step makes it (wm_dec_attention_cand): C windows x N
@@ -329,7 +332,9 @@ WM_API int wmdbg_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int
  * (<= 1500, <= ld), row stride ld.  start_frame_out i32 [B][max(N)]: the first frame of every row on the path, -1 past N[b]. */
 WM_API int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, const int32_t *M, int ld, int32_t *start_frame_out);
 /* Makes the NEXT wm_align or wm_align_mel call on ctx also return its cost matrix -- AFTER negation, i.e. x = -mean over heads, the matrix
- * the DTW runs on -- into matrix_out f32 [B][max_text + 1][1500] (0 outside each chunk's n + 1 rows x n_frames / 2 frames). */
+ * the DTW runs on -- into matrix_out f32 [B][max_text + 1][1500] (0 outside each chunk's n + 1 rows x n_frames / 2 frames).
+ * The next aligned transcribe call (wm_transcribe_mel_aligned, wm_transcribe_windows_aligned) is served the same way:
+ * matrix_out f32 [B][max_new + 1][1500], 0 outside each row's len_b x M_b block. */
 WM_API int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out);
 /* The alignment kernels of wm_align alone (column statistics, then the cost matrix) on host data.  q f32 [B][Tq][J][64] (the
  * capture buffer: chunk b's decoder rows 0 .. S + n_text[b] + 1), keys f32 [L][B][H][1500][64] (the cross-attention keys of
@@ -342,6 +347,13 @@ WM_API int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out);
 WM_API int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
                               const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
                               int medfilt_width, float qk_scale, float *x, float *col_stats);
+/* wmdbg_align_matrix with the row rule of an aligned transcribe group (wm_transcribe_mel_aligned): tail_rows = decoder rows
+ * behind the last cost-matrix row.  1: wmdbg_align_matrix exactly.  0: chunk b has S + n_text[b] + 1 decoder rows, its matrix
+ * is the last n_text[b] + 1 of them, n_text[b] in [-1, Tq - S - 1] with -1 the untouched chunk and 0 a one-row matrix, S >= 0
+ * (a chunk of ONE decoder row is invalid: no spread over the rows); x f32 [B][Tq - S][1500]. */
+WM_API int wmdbg_align_matrix_rows(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
+                                   const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
+                                   int medfilt_width, float qk_scale, float *x, float *col_stats, int tail_rows);
 /* The token-probability kernel of wm_align alone: prob[b] = softmax(logits[b][0 : eot])[tok[b]] for B host rows of row stride
  * ldo >= V (entries eot .. ldo - 1 are never read), 1 <= eot <= V, 0 <= tok[b] < eot. */
 WM_API int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, int V, int ldo, const int32_t *tok, int eot,

@@ -134,6 +134,10 @@ def load_library(path=None):
                                        vp, vp, vp, vp],
         "wm_align_windows": [vp, vp, vp, ip, vp, ip, ctypes.c_int32, ctypes.c_int32, vp, vp, ip, ip, ctypes.c_float, vp, vp],
         "wm_windows_detect_language": [vp, vp, vp, ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp],
+        "wm_transcribe_mel_aligned": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, ip, ctypes.c_float,
+                                      vp, vp, vp, vp, vp, ip],
+        "wm_transcribe_windows_aligned": [vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, ip, ctypes.c_float, vp, vp,
+                                          vp, vp, vp],
         "wm_set_lanes": [vp, ip],
         "wm_dev_malloc": [vp, sz, pp],
         "wm_dev_free": [vp, vp],
@@ -249,6 +253,39 @@ class TranscribeResult:
         self.sum_logprob = np.array([float(np.sum(logprobs[b, :lens[b]], dtype=np.float64)) for b in range(B)])
         self.n_text = np.array([n_text_tokens(tokens[b, :lens[b]], eot) for b in range(B)], dtype=np.int64)
         self.avg_logprob = self.sum_logprob / (self.n_text + 1)
+
+
+class AlignedResult(TranscribeResult):
+    """What Context.transcribe_mel_aligned / transcribe_windows_aligned return: a TranscribeResult plus start_frames i32
+    [B][max_new + 1] -- entry k < lens[b] is the first audio frame (20 ms) of generated token k, entry lens[b] is the
+    window's n_frames // 2, -1 behind (wm_transcribe_mel_aligned) --, and with capture_matrix=True `matrix`, the cost
+    matrices f32 [B][max_new + 1][1500]."""
+
+    def __init__(self, tokens, lens, logprobs, no_speech_prob, eot, start_frames, matrix=None):
+        TranscribeResult.__init__(self, tokens, lens, logprobs, no_speech_prob, eot)
+        self.start_frames, self.matrix = start_frames, matrix
+
+
+def decode_alignment_text(tokens, length, start_frames, logprobs, eot, n_text=None):
+    """One row of an AlignedResult as the arrays window_word_timestamps / word_timestamps take: (text_tokens [n],
+    text_start_frames i32 [n + 1], token_probs f64 [n]).  The text tokens are the generated tokens tokens[:length] with id
+    < eot (timestamp tokens and the stopping eot have rows of the alignment but are no text), the first n_text of them when
+    n_text is given (a long-form window keeps the tokens of its segments only).  Boundary i < n is the start frame of text
+    token i, the final boundary the start frame of the row BEHIND the last text token -- the next generated token's, or
+    start_frames[length], the window's end.  token_probs = exp(logprob): the probability under the filtered distribution the
+    decode chose from, not wm_align's softmax over the raw text logits.  Without a text token: ([], [start_frames[0]], [])."""
+    toks = np.asarray(tokens).reshape(-1)
+    sf = np.asarray(start_frames).reshape(-1)
+    lp = np.asarray(logprobs, dtype=np.float64).reshape(-1)
+    idx = [k for k in range(int(length)) if toks[k] < eot]
+    if n_text is not None:
+        if n_text > len(idx):
+            raise ValueError("decode_alignment_text: the row has %d text tokens, not %d" % (len(idx), n_text))
+        idx = idx[:int(n_text)]
+    if not idx:
+        return [], np.array([int(sf[0])], dtype=np.int32), np.zeros(0, dtype=np.float64)
+    bounds = [int(sf[k]) for k in idx] + [int(sf[idx[-1] + 1])]
+    return [int(toks[k]) for k in idx], np.array(bounds, dtype=np.int32), np.exp(lp[idx])
 
 
 class BestOfResult:
@@ -838,8 +875,13 @@ class _LongOptions(types.SimpleNamespace):
             raise ValueError("initial_prompt_tokens: one list per recording")
         if self.vocab_size is None:
             self.vocab_size = int(self.ctx.dims["n_vocab"])
+        if isinstance(self.word_timestamps, str) and self.word_timestamps != "decode":
+            raise ValueError("word_timestamps: False, True or 'decode'")
         self.words_on = bool(self.word_timestamps)
-        if self.words_on and (self.vocab is None or self.no_timestamps is None):
+        self.words_decode = isinstance(self.word_timestamps, str)   # 18.: the alignment comes with the decode
+        if self.words_decode and (self.best_of is not None or self.beam_size is not None):
+            raise ValueError("word_timestamps='decode' cannot be combined with best_of or beam_size: they have no aligned call")
+        if self.words_on and (self.vocab is None or (self.no_timestamps is None and not self.words_decode)):
             raise ValueError("word_timestamps needs vocab and no_timestamps")
         self.clips_on = self.clip_timestamps is not None
         self.times = clip_times(self.clip_timestamps, R)
@@ -975,6 +1017,7 @@ class _RoundRows:
         self.o, self.d_mel, self.units, self.sizes, self.ids = o, d_mel, units, sizes, sample_ids
         self.prompts = prompts if o.ragged else np.array(prompts, dtype=np.int32)
         self.kept_by = [{} for _ in units]
+        self.aligned = [None] * len(units)   # word_timestamps="decode": (start_frames, logprobs, lens) of the row's last step
         self.set = o.ctx.encode_windows(*self._mel_windows(range(len(units))), mem=WM_MEM_DEVICE) if o.reuse_encoder else None
 
     def _mel_windows(self, rows):
@@ -989,7 +1032,14 @@ class _RoundRows:
         prompts = [self.prompts[i] for i in todo] if o.ragged else self.prompts[todo]
         kw = dict(eot=o.eot, temperature=t, seed=sd, no_speech_token=o.no_speech_token, sample_ids=[self.ids[i] for i in todo],
                   **o.sot_kw, **extra)
-        if self.set is not None:   # the same call without the encoder pass
+        if o.words_decode:   # 18.: every attempt through the aligned entry; the kept one's start frames feed the word step
+            if self.set is not None:
+                r = o.ctx.transcribe_windows_aligned(self.set, [int(i) for i in todo], prompts, o.max_new, **kw)
+            else:
+                r = o.ctx.transcribe_mel_aligned(*self._mel_windows(todo), prompts, o.max_new, mem=WM_MEM_DEVICE, **kw)
+            for k, i in enumerate(todo):
+                self.aligned[i] = (r.start_frames[k], r.logprobs[k], int(r.lens[k]), r.tokens[k])
+        elif self.set is not None:   # the same call without the encoder pass
             r = o.ctx.transcribe_windows(self.set, [int(i) for i in todo], prompts, o.max_new, **kw)
         else:
             r = o.ctx.transcribe_mel(*self._mel_windows(todo), prompts, o.max_new, mem=WM_MEM_DEVICE, **kw)
@@ -1002,6 +1052,13 @@ class _RoundRows:
 
     def align(self, rows, texts, sot_seqs):
         o = self.o
+        if o.words_decode:   # no call: the kept attempts' own start frames, cut to the text the segments kept
+            out = [decode_alignment_text(self.aligned[i][3], self.aligned[i][2], self.aligned[i][0], self.aligned[i][1], o.eot,
+                                         n_text=len(t)) for i, t in zip(rows, texts)]
+            for (toks, _, _), t in zip(out, texts):
+                if toks != [int(x) for x in t]:
+                    raise AssertionError("transcribe_long: a window's segments do not hold a prefix of its text tokens")
+            return [sf for _, sf, _ in out], [pr for _, _, pr in out]
         if self.set is not None:
             return o.ctx.align_windows(self.set, rows, texts, sot_seqs, o.no_timestamps, o.eot, medfilt_width=7, qk_scale=1.0)
         return o.ctx.align_mel(*self._mel_windows(rows), texts, sot_seqs, o.no_timestamps, o.eot, medfilt_width=7, qk_scale=1.0,
@@ -1262,6 +1319,18 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        when the function leaves, also on an exception.  It acts on a row's generated tokens only.  The ids are the caller's
        tokenizer's: Whisper's " word" and "word" are different ids, and both variants are the caller's to list.  With all
        three None the function makes exactly the calls it made before they existed.
+    18. word_timestamps="decode": the words of 6. WITHOUT the alignment call.  Every fallback attempt of a round goes through
+       the aligned entry (Context.transcribe_mel_aligned; with reuse_encoder transcribe_windows_aligned: the same tokens bit
+       for bit, plus the start frame of every generated token from the decode's own cross-attention queries), and the kept
+       attempt's start frames feed window_word_timestamps through decode_alignment_text, cut to the text tokens the window's
+       segments kept.  No align_* call is made; the seek to the last word's end, the hallucination rules of 11 and the
+       clearing of empty segments run unchanged on the new word times.  The semantic difference from openai-whisper (and
+       from word_timestamps=True): the aligned queries are the DECODE's -- its prompt (previous text is no row, but
+       [sot, language, task] are), timestamp tokens interleaved with the text -- not those of a clean [sot, language, task,
+       <|notimestamps|>, text] pass, and a word's probability is exp(log-prob) under the filtered distribution the decode
+       chose from.  The word times therefore differ slightly from 6.'s; the tokens do not.  no_timestamps is not needed;
+       teacher_panel has nothing to act on.  Together with best_of or beam_size it is a ValueError before any library call.
+       word_timestamps True / False make exactly the calls they made before the mode existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1325,7 +1394,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     u.commit(o, *window_segments(tokens, u.seek, sizes[i], timestamp_begin, eot, result, vocab),
                              result["temperature"])
             if kept:
-                if o.panel_pending:   # 16.
+                if o.panel_pending and not o.words_decode:   # 16.
                     ctx.set_teacher_panel(int(teacher_panel))
                     o.panel_pending = False
                 _long_word_step(o, source, live, sizes, kept, res)
@@ -2024,6 +2093,46 @@ class Context:
             lambda: self.transcribe_windows_beam(windows, rows, prompts, max_new, beam_size, patience=patience, **common),
             lambda: candidates(best_of), plain, temperature, best_of, beam_size, patience)
 
+    def _aligned_call(self, fn, rows, tail, prompts, max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids,
+                      budgets, prompt_len, sot_tail, medfilt_width, qk_scale, capture_matrix):
+        """wm_transcribe_mel_aligned / wm_transcribe_windows_aligned (rows, tail: as in _best_of_call)"""
+        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        head, B = rows()
+        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
+        toks = np.empty((B, max_new), dtype=np.int32)
+        lens = np.empty(B, dtype=np.int32)
+        lp = np.empty((B, max_new), dtype=np.float32)
+        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
+        start = np.empty((B, max_new + 1), dtype=np.int32)
+        matrix = self._capture_matrix(B, max_new) if capture_matrix else None
+        _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
+                            1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), max_new, eot, ctypes.byref(opts),
+                            int(medfilt_width), float(qk_scale), _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(start),
+                            *tail))
+        return AlignedResult(toks, lens, lp, ns, eot, start, matrix)
+
+    def transcribe_mel_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
+                               no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
+                               sot_tail=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False):
+        """wm_transcribe_mel_aligned: transcribe_mel (one sample per row; uniform or ragged prompts as in transcribe_mel_raw)
+        whose decode also aligns what it generates, from its own cross-attention queries.  Tokens, lens, log-probs and
+        no_speech_prob are transcribe_mel's bit for bit.  Returns an AlignedResult (start_frames; decode_alignment_text turns
+        a row into word_timestamps' arrays); capture_matrix=True (debug library) also keeps the cost matrices."""
+        return self._aligned_call(self.lib.wm_transcribe_mel_aligned,
+                                  lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new, eot,
+                                  temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len, sot_tail,
+                                  medfilt_width, qk_scale, capture_matrix)
+
+    def transcribe_windows_aligned(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
+                                   sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, medfilt_width=7,
+                                   qk_scale=1.0, capture_matrix=False):
+        """wm_transcribe_windows_aligned: transcribe_mel_aligned with rows of a Windows set.  Same bits."""
+        return self._aligned_call(self.lib.wm_transcribe_windows_aligned, lambda: self._window_rows(windows, rows), (), prompts,
+                                  max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
+                                  sot_tail, medfilt_width, qk_scale, capture_matrix)
+
     def align_windows(self, windows, rows, text_tokens, sot_seqs, no_timestamps, eot, medfilt_width=7, qk_scale=1.0):
         """wm_align_windows: align_mel with rows of a Windows set (each of at least 2 frames); the alignment covers the set's
         own n_frames of a row.  Returns (start_frames, token_probs) as align."""
@@ -2169,6 +2278,31 @@ class Context:
         _check(self.lib, fn(self.handle, _ptr(q), _ptr(keys), L, H, B, Tq, J, _ptr(hl), _ptr(hh), int(S), _ptr(nt), _ptr(nf),
                             int(medfilt_width), float(qk_scale), _ptr(x), _ptr(cs) if col_stats else None))
         return (x, cs) if col_stats else x
+
+    def align_matrix_rows(self, q, keys, heads, S, n_text, n_frames, medfilt_width=7, qk_scale=1.0, tail_rows=0):
+        """Debug library only: align_matrix with the row rule of an aligned transcribe group (wmdbg_align_matrix_rows):
+        tail_rows decoder rows behind the last matrix row.  0: chunk b has S + n_text[b] + 1 decoder rows and n_text[b] + 1
+        matrix rows (-1: none), x f32 [B][Tq - S][1500]; 1: align_matrix."""
+        if not hasattr(self.lib, "wmdbg_align_matrix_rows"):
+            raise WhisperError(-1, "align_matrix_rows needs the debug library: Context(dims, debug=True)")
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        keys = np.ascontiguousarray(keys, dtype=np.float32)
+        B, Tq, J = q.shape[:3]
+        L, H = keys.shape[0], keys.shape[2]
+        if q.shape[3] != 64 or keys.shape[1:] != (B, H, 1500, 64) or len(heads) != J:
+            raise ValueError("align_matrix_rows: q %s, keys %s, %d heads" % (q.shape, keys.shape, len(heads)))
+        hl = np.ascontiguousarray([p[0] for p in heads], dtype=np.int32)
+        hh = np.ascontiguousarray([p[1] for p in heads], dtype=np.int32)
+        nt = np.ascontiguousarray(np.broadcast_to(np.asarray(n_text, dtype=np.int32), (B,)))
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, dtype=np.int32), (B,)))
+        x = np.empty((B, max(Tq - S - int(tail_rows), 1), 1500), dtype=np.float32)
+        fn = self.lib.wmdbg_align_matrix_rows
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        fn.argtypes = [vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, ctypes.c_float, vp, vp, ip]
+        fn.restype = ctypes.c_int
+        _check(self.lib, fn(self.handle, _ptr(q), _ptr(keys), L, H, B, Tq, J, _ptr(hl), _ptr(hh), int(S), _ptr(nt), _ptr(nf),
+                            int(medfilt_width), float(qk_scale), _ptr(x), None, int(tail_rows)))
+        return x
 
     def align_token_prob(self, logits, tok, eot, V=None):
         """Debug library only: the token-probability kernel of wm_align alone (wmdbg_align_token_prob) on logits rows f32

@@ -3,6 +3,9 @@
 //
 //   * align_capture_kernel: inside the teacher-forced pass, the alignment heads' 64-wide cross-attention queries of the
 //     current decode position (read from HBM: the device-side position) -> the capture buffer q [B][T][J][64] f32.
+//     An aligned transcribe group (wm_transcribe_mel_aligned) captures inside its OWN decode steps, eager or replayed from the
+//     position graphs: the <false, true> instantiation writes capture row position - base, base = the group's
+//     <|startoftranscript|> position, and nothing in front of it.
 //   * align_token_prob_kernel: softmax(logits[S + i][0 : eot])[t[i]] per chunk, from the logits row of the position.
 //   * align_stats_kernel (pass 1, one workgroup per (chunk, head)): the scores q.k / 8 * qk_scale over frames [0, M) are
 //     recomputed from the bf16 cross-K cache with the exact-f32 MFMA (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain),
@@ -11,6 +14,10 @@
 //     passes: the one-pass E[p^2] - mean^2 cancels to nothing in f32 once std / mean falls to ~1e-3).  Each wave owns its LDS
 //     column partials, summed in wave order: no float atomics.
 //     Out: row statistics [B][J][T][2] and column (mean, std) [B][J][1500][2] -- never the [J][T][1500] probabilities.
+//     The row rule (WmAlignDev::tail, n_min): a chunk has T = S + n + 1 + tail decoder rows, of which rows S .. S + n are the cost
+//     matrix.  wm_align: tail 1 (the teacher-forced eot's row), a chunk needs n >= 1.  An aligned transcribe group: tail 0 (a
+//     decode never feeds its last token), n = len - 1 >= 0, absent rows -1.  Rows at or past T of the capture buffer -- where a
+//     stopped row of a decode group keeps writing -- are never read: every row index is clamped to T - 1.
 //   * align_matrix_kernel (pass 2, one workgroup per (chunk, 16 text rows, 64 frames)): for every head in ascending
 //     (layer, head) order it recomputes the scores of its rows over its frames plus the filter's halo, normalises them
 //     (softmax, z-score), applies the median filter (reflect padding) and adds the result to a register accumulator; the
@@ -71,7 +78,10 @@ __device__ __forceinline__ void lse_merge(float &m, float &s, float m2, float s2
 
 // PANEL (a teacher-forced panel step, wm_set_teacher_panel): dq row r is position *pos_ptr + r % w of chunk r / w; the capture
 // layout is unchanged.  Instantiations of their own, here and in the token-probability kernel: the step kernels stay as they were.
-template <bool PANEL>
+// BASED (an aligned transcribe group, its own instantiation too): w is the absolute position of capture row 0 -- the group's
+// <|startoftranscript|> position --, the positions in front of it are not captured.  A row that has stopped keeps writing its
+// (stale) query at the group's position: rows past a chunk's own T, which the alignment kernels clamp away.
+template <bool PANEL, bool BASED = false>
 __global__ __launch_bounds__(64) void align_capture_kernel(const float *__restrict__ dq, int d, const int *__restrict__ pos_ptr,
                                                            WmAlignLayer L, float *__restrict__ cap, int Tq, int J, int w) {
     const int r = blockIdx.x, k = blockIdx.y;
@@ -79,6 +89,10 @@ __global__ __launch_bounds__(64) void align_capture_kernel(const float *__restri
     if constexpr (PANEL) {
         b = r / w;
         pos += r - b * w;
+    }
+    if constexpr (BASED) {
+        pos -= w;
+        if (pos < 0) return;
     }
     if (pos >= Tq) return;
     cap[(((size_t)b * Tq + pos) * J + L.slot0 + k) * 64 + threadIdx.x] = dq[(size_t)r * d + L.head[k] * 64 + threadIdx.x];
@@ -126,8 +140,8 @@ __global__ __launch_bounds__(256) void align_stats_kernel(WmAlignDev a) {
     __shared__ float mean[1500];
     __shared__ float rowl[AL_MAXT][2];   // the rows' (max, 1 / sum) for sweep 3
     const int j = blockIdx.x, b = blockIdx.y, n = a.n_text[b];
-    if (n <= 0) return;
-    const int T = a.S + n + 2, M = a.n_frames[b] / 2;
+    if (n < a.n_min) return;
+    const int T = a.S + n + 1 + a.tail, M = a.n_frames[b] / 2;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
     for (int i = threadIdx.x; i < 4 * 1500; i += 256) (&part[0][0])[i] = 0.f;
     __syncthreads();
@@ -270,8 +284,8 @@ __global__ __launch_bounds__(256) void align_matrix_kernel(WmAlignDev a) {
     __shared__ float zl[16][AL_ZW];
     const int b = blockIdx.z, n = a.n_text[b];
     const int N = n + 1, i0 = blockIdx.y * 16, f0 = blockIdx.x * AL_OUT, M = a.n_frames[b] / 2;
-    if (n <= 0 || i0 >= N || f0 >= M) return;
-    const int T = a.S + n + 2, h = a.half;
+    if (n < a.n_min || i0 >= N || f0 >= M) return;
+    const int T = a.S + n + 1 + a.tail, h = a.half;
     const bool filt = h > 0 && M > h;   // openai-whisper: no filtering when the window's padding would not fit
     const int lo = filt ? max(0, f0 - h) : f0, hi = filt ? min(M, f0 + AL_OUT + h) : min(M, f0 + AL_OUT);
     const int ntile = (hi - lo + 15) / 16;
@@ -392,11 +406,13 @@ __global__ __launch_bounds__(64) void dtw_kernel(const float *__restrict__ x, lo
 }  // namespace
 
 int wm_align_capture_q(wm_ctx *ctx, const float *dq, int d, int B, const WmAlignLayer &L, float *cap, int Tq, int J,
-                       const int *pos_ptr, int panel) {
+                       const int *pos_ptr, int panel, int base) {
     if (L.n <= 0) return WM_OK;
     WM_REQUIRE(panel >= 1 && panel <= WM_MAX_TEACHER_PANEL && B % panel == 0, WM_ERR_INVALID, "align_capture: %d rows in panels of %d", B, panel);
+    WM_REQUIRE(base < 0 || panel == 1, WM_ERR_INVALID, "align_capture: a capture base goes with single steps");
     WmProfScope ps(&ctx->prof, "align_capture", ctx->stream);
-    if (panel > 1) align_capture_kernel<true><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, panel);
+    if (base >= 0) align_capture_kernel<false, true><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, base);
+    else if (panel > 1) align_capture_kernel<true><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, panel);
     else align_capture_kernel<false><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, 1);
     WM_HIP(hipGetLastError());
     return WM_OK;
@@ -417,7 +433,8 @@ int wm_align_matrix(wm_ctx *ctx, const WmAlignDev &a, int max_n, int max_m) {
     WM_REQUIRE(a.half >= 0 && a.half <= AL_MAXHALF, WM_ERR_INVALID, "align: median filter half-width %d > %d", a.half,
                AL_MAXHALF);
     WM_REQUIRE(a.Tq <= AL_MAXT, WM_ERR_INVALID, "align: %d decoder rows > %d", a.Tq, AL_MAXT);
-    if (max_n <= 0 || max_m <= 0) return WM_OK;
+    WM_REQUIRE((a.tail == 0 || a.tail == 1) && (a.n_min == 0 || a.n_min == 1), WM_ERR_INVALID, "align: row rule (%d, %d)", a.tail, a.n_min);
+    if (max_n < a.n_min || max_m <= 0) return WM_OK;
     {
         WmProfScope ps(&ctx->prof, "align_stats", ctx->stream);
         align_stats_kernel<<<dim3(a.J, a.B), 256, 0, ctx->stream>>>(a);

@@ -296,6 +296,18 @@ extern "C" int wmdbg_tx_plan(const int32_t *in, int n, int32_t *out, int32_t *cu
     }
     return n;
 }
+extern "C" int wmdbg_tx_plan_bounded(const int32_t *in, const int32_t *max_group_rows, int n, int32_t *out, int32_t *cut, int cut_cap) {
+    if (!in || !max_group_rows || !out || !cut || n < 0 || cut_cap < 0) return -1;
+    int used = 0;
+    for (int i = 0; i < n; ++i) {
+        int32_t *o = out + (size_t)i * WM_TX_PLAN_OUT;
+        const int k = wm_tx_plan_flat(in + (size_t)i * WM_TX_PLAN_IN, o, cut + used, cut_cap - used, max_group_rows[i]);
+        if (k < 0) return -1;
+        o[5] = used;
+        used += k;
+    }
+    return n;
+}
 extern "C" int wmdbg_group_tables(const int32_t *in, int n, int32_t *out) {
     if (!in || !out || n < 0) return -1;
     for (int i = 0; i < n; ++i)
@@ -810,14 +822,17 @@ extern "C" int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out) {
     return WM_OK;
 }
 
-extern "C" int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
-                                  const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
-                                  int medfilt_width, float qk_scale, float *x, float *col_stats) {
+// tail: decoder rows behind the last cost-matrix row (WmAlignDev::tail, and n_min with it).  1: wm_align's row rule -- chunk b
+// has S + n_text[b] + 2 decoder rows, n_text 0 is an untouched chunk; 0: an aligned transcribe group's -- S + n_text[b] + 1
+// decoder rows, n_text -1 is the untouched chunk and 0 a one-row matrix.  Either way the matrix has n_text[b] + 1 rows.
+static int align_matrix_hook(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
+                             const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
+                             int medfilt_width, float qk_scale, float *x, float *col_stats, int tail) {
     WM_TRY(wm_ctx_make_current(ctx));
-    WM_REQUIRE(q && keys && hl && hh && n_text && n_frames && x && L >= 1 && H >= 1 && B >= 1 && J >= 1 && S >= 1,
+    WM_REQUIRE(q && keys && hl && hh && n_text && n_frames && x && L >= 1 && H >= 1 && B >= 1 && J >= 1 && S >= (tail ? 1 : 0),
                WM_ERR_INVALID, "bad args");
     const int n_ctx = ctx->model ? ctx->model->dims.n_text_ctx : 448;
-    WM_REQUIRE(Tq >= S + 2 && Tq <= n_ctx, WM_ERR_INVALID, "align: Tq = %d outside [S + 2, %d]", Tq, n_ctx);
+    WM_REQUIRE(Tq >= S + 1 + tail && Tq <= n_ctx, WM_ERR_INVALID, "align: Tq = %d outside [S + %d, %d]", Tq, 1 + tail, n_ctx);
     WM_REQUIRE(medfilt_width >= 1 && medfilt_width <= 31 && medfilt_width % 2 == 1, WM_ERR_INVALID,
                "align: medfilt_width %d must be odd, 1 .. 31", medfilt_width);
     WM_REQUIRE(isfinite(qk_scale), WM_ERR_INVALID, "align: qk_scale must be finite");
@@ -825,14 +840,15 @@ extern "C" int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys
         WM_REQUIRE(hl[j] >= 0 && hl[j] < L && hh[j] >= 0 && hh[j] < H, WM_ERR_INVALID, "align: head %d outside the model", j);
     int nmax = 0, mmax = 0;
     for (int b = 0; b < B; ++b) {
-        WM_REQUIRE(n_text[b] >= 0 && n_text[b] <= Tq - S - 2, WM_ERR_INVALID, "align: n_text[%d] = %d outside [0, %d]", b,
-                   n_text[b], Tq - S - 2);
+        WM_REQUIRE(n_text[b] >= tail - 1 && n_text[b] <= Tq - S - 1 - tail, WM_ERR_INVALID, "align: n_text[%d] = %d outside [%d, %d]", b,
+                   n_text[b], tail - 1, Tq - S - 1 - tail);
+        WM_REQUIRE(tail || n_text[b] < 0 || S + n_text[b] + 1 >= 2, WM_ERR_INVALID, "align: chunk %d has one decoder row (no spread over rows)", b);
         WM_REQUIRE(n_frames[b] >= 2 && n_frames[b] <= WM_N_FRAMES, WM_ERR_INVALID, "align: n_frames[%d] = %d outside [2, %d]",
                    b, n_frames[b], WM_N_FRAMES);
         nmax = n_text[b] > nmax ? n_text[b] : nmax;
         mmax = n_frames[b] / 2 > mmax ? n_frames[b] / 2 : mmax;
     }
-    const int n_ld = Tq - S - 1;
+    const int n_ld = Tq - S - tail;
     const size_t head = (size_t)1500 * 64;
     // the cross-K/V cache [L][2][B][H][1500][64]: keys rounded as to_bf16 rounds, V halves NaN, frames >= M a large key
     std::vector<bf16_t> kv((size_t)L * 2 * B * H * head, (bf16_t)0x7fc0);
@@ -863,11 +879,25 @@ extern "C" int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys
     a.B = B; a.H = H; a.Tq = Tq; a.J = J; a.S = S; a.n_ld = n_ld;
     a.sc = 0.125f * qk_scale * 1.44269504088896340736f;   // as wm_align
     a.half = medfilt_width / 2;
+    if (!tail) { a.tail = 0; a.n_min = 0; }
     WM_TRY(wm_align_matrix(ctx, a, nmax, mmax));
     WM_HIP(hipMemcpyAsync(x, a.x, x0.size() * 4, hipMemcpyDeviceToHost, s));
     if (col_stats) WM_HIP(hipMemcpyAsync(col_stats, a.colst, (size_t)B * J * 1500 * 2 * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipStreamSynchronize(s));
     return WM_OK;
+}
+
+extern "C" int wmdbg_align_matrix(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
+                                  const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
+                                  int medfilt_width, float qk_scale, float *x, float *col_stats) {
+    return align_matrix_hook(ctx, q, keys, L, H, B, Tq, J, hl, hh, S, n_text, n_frames, medfilt_width, qk_scale, x, col_stats, 1);
+}
+
+extern "C" int wmdbg_align_matrix_rows(wm_ctx *ctx, const float *q, const float *keys, int L, int H, int B, int Tq, int J,
+                                       const int32_t *hl, const int32_t *hh, int S, const int32_t *n_text, const int32_t *n_frames,
+                                       int medfilt_width, float qk_scale, float *x, float *col_stats, int tail_rows) {
+    WM_REQUIRE(tail_rows == 0 || tail_rows == 1, WM_ERR_INVALID, "align: tail_rows %d is neither 0 nor 1", tail_rows);
+    return align_matrix_hook(ctx, q, keys, L, H, B, Tq, J, hl, hh, S, n_text, n_frames, medfilt_width, qk_scale, x, col_stats, tail_rows);
 }
 
 extern "C" int wmdbg_align_token_prob(wm_ctx *ctx, const float *logits, int B, int V, int ldo, const int32_t *tok, int eot,

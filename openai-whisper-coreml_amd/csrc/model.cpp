@@ -508,7 +508,7 @@ void wm_model_destroy(wm_ctx *ctx) {
     wm_model_drop_graphs(m);
     if (m->h_nlive) (void)hipHostFree(m->h_nlive);
     for (void *p : m->allocs) (void)hipFree(p);
-    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->beam_ws, &m->beam_trace}) b->release();
+    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->acap_ws, &m->beam_ws, &m->beam_trace}) b->release();
     delete m;
     ctx->model = nullptr;
 }
@@ -899,7 +899,7 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
             WM_TRY(wm_dec_xattn_fq(ctx, a, t));
         } else {
             WM_TRY(wm_dec_gemv(ctx, a));
-            if (cap_l) WM_TRY(wm_align_capture_q(ctx, m->dq, d, B, cap->layer[l], cap->q, cap->Tq, cap->J, m->dpos, PW));
+            if (cap_l) WM_TRY(wm_align_capture_q(ctx, m->dq, d, B, cap->layer[l], cap->q, cap->Tq, cap->J, m->dpos, PW, cap->base));
             // 5. the cross-attention (a candidate group, a panel: one K/V read per window)
             WM_TRY(NC > 1 || PW > 1 ? wm_dec_attention_cand(ctx, t) : wm_dec_attention(ctx, t));
         }

@@ -220,13 +220,16 @@ struct WmAlignCap {
     const WmAlignLayer *layer;  // [n_text_layer] (host)
     float *q;
     int Tq, J;
+    // >= 0 (an aligned transcribe group): the query of absolute position pos goes to capture row pos - base, positions in front
+    // of base and rows at or past Tq are not captured; -1: capture row = position (the teacher-forced passes)
+    int base = -1;
 };
 // the alignment kernels' view of one decode group (device pointers)
 struct WmAlignDev {
     const float *q;          // [B][Tq][J][64] captured cross-attention queries (f32)
     const bf16_t *xkv;       // the group's cross-attention K/V cache [L][2][B][H][1500][64]
     const int *hl, *hh;      // [J] alignment heads (layer, head), ascending
-    const int *n_text;       // [B] text tokens n of each chunk: decoder rows S + n + 2, cost-matrix rows n + 1; 0 = none
+    const int *n_text;       // [B] text tokens n of each chunk: decoder rows S + n + 1 + tail, cost-matrix rows n + 1; below n_min = none
     const int *n_frames;     // [B] mel frames; the alignment uses audio frames [0, n_frames / 2)
     float *rowst;            // [B][J][Tq][2] per decoder row: softmax max and 1 / sum (scores in log2 units)
     float *colst;            // [B][J][1500][2] per frame: mean and std of the probabilities over the chunk's rows
@@ -234,6 +237,11 @@ struct WmAlignDev {
     int B, H, Tq, J, S, n_ld;
     float sc;                // 0.125 * qk_scale * log2(e)
     int half;                // medfilt_width / 2
+    // The row rule.  tail: decoder rows behind the last cost-matrix row -- 1 for wm_align (the row of the teacher-forced eot),
+    // 0 for an aligned transcribe group (a decode never feeds its last token).  n_min: the smallest n_text that is a chunk at
+    // all -- 1 for wm_align (n = 0: no text), 0 for an aligned group (n = len - 1: a one-token row is a one-row matrix; absent
+    // rows carry -1).
+    int tail = 1, n_min = 1;
 };
 
 // The mode of ONE decode: everything a captured position bakes into its kernel arguments that the context's weights and
@@ -270,8 +278,15 @@ struct WmDecodeMode {
     // to its own position, the cross-attention is the candidate-group launch (wm_model_panel_step).  The teacher-forced entries
     // run eagerly, but a mode is a graph key member by member, so it is compared like the others.
     int panel = 1;
+    // An aligned transcribe group (wm_transcribe_mel_aligned): every step captures the alignment heads' queries, so the layers
+    // with alignment heads take the unfused cross_attn_ln + query launches (same bits).  What the capture launch bakes in --
+    // the buffer, its row count, the head count, the position of capture row 0 -- is part of the key; the head list itself is
+    // not: wm_set_alignment_heads drops the captured graphs.
+    bool acap = false;
+    int acap_base = 0, acap_Tq = 0, acap_J = 0;
+    float *acap_q = nullptr;
     bool operator==(const WmDecodeMode &o) const {
-        return panel == o.panel && rep == o.rep && sb == o.sb && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && rep == o.rep && sb == o.sb && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -425,6 +440,7 @@ struct WmModel {
     // workspace of a call (grown on demand) and the debug library's one-shot cost-matrix capture (host, null in the product)
     std::vector<int32_t> align_l, align_h;
     WmDevBuf align_ws;
+    WmDevBuf acap_ws;   // an aligned transcribe group's capture buffer and alignment workspace (reserved at prefill, grow-only)
     float *align_dbg_matrix = nullptr;
     int teacher_panel = 1;   // wm_set_teacher_panel: positions per step of the teacher-forced passes (a launch policy: same bits)
     // wm_transcribe_mel_beam: the group's beam state (WmBeamDev; allocated once at its largest size, so captured graphs keep
@@ -732,14 +748,26 @@ int wm_xkv_rows(wm_ctx *ctx, bf16_t *group, long group_rows, bf16_t *store, cons
 // align.hip (word-level timestamps)
 // the alignment heads' queries of decode position *pos_ptr: dq [B][d] -> cap[b][*pos_ptr][L.slot0 + k][64]
 // panel > 1: dq holds B = windows x panel rows, row r is position *pos_ptr + r % panel of chunk r / panel
+// base >= 0 (panel 1 only): capture row *pos_ptr - base, nothing in front of base (WmAlignCap::base)
 int wm_align_capture_q(wm_ctx *ctx, const float *dq, int d, int B, const WmAlignLayer &L, float *cap, int Tq, int J,
-                       const int *pos_ptr, int panel = 1);
+                       const int *pos_ptr, int panel = 1, int base = -1);
 // position pos = *pos_ptr, i = pos - S in [0, n_text[b]): prob[b][i] = softmax(logits[b][0 : eot])[seq[pos + 1][b]]
 // panel > 1: logits holds B = windows x panel rows (row r: position *pos_ptr + r % panel of chunk r / panel; n_text and prob
 // per chunk); seq_stride: chunks per position of seq (0: B)
 int wm_align_token_prob(wm_ctx *ctx, const float *logits, long ldo, const int *seq, const int *pos_ptr, int B, int S, int eot,
                         const int *n_text, float *prob, int max_text, int panel = 1, int seq_stride = 0);
 // scores -> softmax -> z-score -> median filter -> head mean -> a.x (max_n: largest n_text, max_m: largest n_frames / 2)
+// Captured queries + statistics + cost matrix of ONE chunk of an alignment group (T decoder rows, J heads, n_ld matrix rows), and
+// the chunks a group may hold under the 2 GiB budget of wm_align and of an aligned transcribe call alike
+constexpr size_t WM_ALIGN_CAPTURE_BUDGET = (size_t)2 << 30;
+inline size_t wm_align_chunk_bytes(size_t T, size_t J, size_t n_ld) { return T * J * (64 * 4 + 8) + J * 1500 * 8 + n_ld * 1500 * 4; }
+inline int wm_align_group_rows(size_t T, size_t J, size_t n_ld) {
+    const size_t g = WM_ALIGN_CAPTURE_BUDGET / wm_align_chunk_bytes(T, J, n_ld);
+    return (int)(g < 1 ? 1 : (g > (size_t)WM_DEC_MAXB ? (size_t)WM_DEC_MAXB : g));
+}
+// the alignment heads of a context: wm_set_alignment_heads' list, or openai-whisper's default (every head of the last half of
+// the decoder layers), ascending by (layer, head)
+void wm_align_heads(const WmModel *m, std::vector<int32_t> *hl, std::vector<int32_t> *hh);
 int wm_align_matrix(wm_ctx *ctx, const WmAlignDev &a, int max_n, int max_m);
 // trace words a chunk of max_rows rows needs in HBM (when its trace does not fit the DTW kernel's LDS)
 size_t wm_dtw_trace_words(int max_rows);

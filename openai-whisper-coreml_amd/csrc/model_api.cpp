@@ -469,12 +469,30 @@ extern "C" int wm_set_alignment_heads(wm_ctx *ctx, const int32_t *layers, const 
         WM_REQUIRE(v[i] != v[i - 1], WM_ERR_INVALID, "set_alignment_heads: (%d, %d) listed twice", v[i].first, v[i].second);
     std::vector<int32_t> hl, hh;
     for (auto &p : v) { hl.push_back(p.first); hh.push_back(p.second); }
-    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { c->model->align_l = hl; c->model->align_h = hh; return (int)WM_OK; });
+    // (an aligned transcribe group's captured positions hold the head list in their launches: they are captured afresh)
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) {
+        c->model->align_l = hl; c->model->align_h = hh;
+        std::vector<WmModel::GraphSet> &gs = c->model->graph_sets;
+        for (size_t i = gs.size(); i-- > 0;)
+            if (gs[i].mode.acap) { gs[i].destroy(); gs.erase(gs.begin() + (long)i); }
+        return (int)WM_OK;
+    });
 } WM_API_CATCH
 
-namespace {
-constexpr size_t kAlignCaptureBudget = (size_t)2 << 30;   // bytes of captured queries + statistics per decode group
+void wm_align_heads(const WmModel *m, std::vector<int32_t> *hl, std::vector<int32_t> *hh) {
+    if (!m->align_l.empty()) {
+        *hl = m->align_l;
+        *hh = m->align_h;
+        return;
+    }
+    hl->clear();
+    hh->clear();
+    const wm_dims &D = m->dims;   // openai-whisper's default: every head of the last half of the decoder layers
+    for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)
+        for (int h = 0; h < D.n_text_head; ++h) { hl->push_back(l); hh->push_back(h); }
+}
 
+namespace {
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // an align call's encoder input -- PCM chunks (wm_align; n_frames nullable: whole chunks) or mel windows (wm_align_mel) --
@@ -638,13 +656,7 @@ static int align_impl(wm_ctx *ctx, AlignCall &c, int B, int32_t no_timestamps, i
                        b, n_frames[b], WM_N_FRAMES);
         if (c.mel) WM_TRY(wm_check_window(c, b, "align: "));
     }
-    if (m->align_l.empty()) {   // openai-whisper's default: every head of the last half of the decoder layers
-        for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)
-            for (int h = 0; h < D.n_text_head; ++h) { c.hl.push_back(l); c.hh.push_back(h); }
-    } else {
-        c.hl = m->align_l;
-        c.hh = m->align_h;
-    }
+    wm_align_heads(m, &c.hl, &c.hh);
     c.no_timestamps = no_timestamps; c.eot = eot;
     c.half = medfilt_width / 2; c.qk_scale = qk_scale;
     c.start_out = start_frame_out; c.prob_out = token_prob_out;
@@ -654,9 +666,7 @@ static int align_impl(wm_ctx *ctx, AlignCall &c, int B, int32_t no_timestamps, i
         for (size_t i = 0; i < (size_t)B * max_text; ++i) token_prob_out[i] = 0.f;
     if (c.dbg_matrix) memset(c.dbg_matrix, 0, (size_t)B * n_ld * 1500 * 4);
     // decode groups of at most WM_DEC_MAXB chunks, fewer when the captured queries would outgrow the budget
-    const size_t J = c.hl.size(), T = (size_t)n_sot + max_text + 2;
-    const size_t per_chunk = T * J * (64 * 4 + 8) + J * 1500 * 8 + (size_t)n_ld * 1500 * 4;
-    const int G = (int)std::max<size_t>(1, std::min<size_t>(WM_DEC_MAXB, kAlignCaptureBudget / per_chunk));
+    const int G = wm_align_group_rows((size_t)n_sot + max_text + 2, c.hl.size(), (size_t)n_ld);
     ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
     WmEvents<4> ev;
     WmStreamFence fence{ctx->stream};   // drained before the events go, whatever a group returned

@@ -1,8 +1,10 @@
 // transcribe.cpp -- the transcribe calls of the C ABI (include/whisper_mi355x.h): wm_transcribe_greedy, wm_transcribe,
-// wm_transcribe_mel, wm_transcribe_mel_ragged, wm_transcribe_mel_best_of, wm_transcribe_windows, wm_transcribe_mel_beam and
-// wm_transcribe_windows_beam.  Each entry point fills one request value (TxCall) and hands it to tx_transcribe: budgets, the
-// entry's own checks, validation (tx_validate), the lane plan (tx_plan.h), the lanes (tx_lanes), the scheduler (tx_run: lane_start /
-// lane_advance / lane_fetch / lane_finish), the ranking step of a best-of or beam call.  DESIGN.md section 4d.
+// wm_transcribe_mel, wm_transcribe_mel_ragged, wm_transcribe_mel_best_of, wm_transcribe_windows, wm_transcribe_mel_beam,
+// wm_transcribe_windows_beam, and the aligned pair wm_transcribe_mel_aligned / wm_transcribe_windows_aligned (the decode also
+// captures the alignment heads' queries, a group ends with the alignment kernels and the DTW: lane_align).  Each entry point
+// fills one request value (TxCall) and hands it to tx_transcribe: budgets, the entry's own checks, validation (tx_validate),
+// the lane plan (tx_plan.h), the lanes (tx_lanes), the scheduler (tx_run: lane_start / lane_advance / lane_fetch /
+// lane_finish), the ranking step of a best-of or beam call.  DESIGN.md section 4d.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -46,8 +48,29 @@ int burst_len() {
     return n;
 }
 
+// an aligned group's slice of WmModel::acap_ws: the capture buffer q [Bg][Tq][J][64], the row and column statistics, the cost
+// matrix x [Bg][n_ld][1500], the DTW trace and start frames, and the ints n_text | n_frames | DTW rows | DTW frames [Bg] each,
+// then the heads' layers | heads [J] each
+struct AcapWs {
+    size_t q = 0, row = 0, col = 0, x = 0, tr = 0, start = 0, ints = 0, bytes = 0;
+    int Tq = 0, J = 0, n_ld = 0;
+};
+AcapWs acap_layout(int Bg, int Tq, int J, int n_ld) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    AcapWs w;
+    w.Tq = Tq; w.J = J; w.n_ld = n_ld;
+    w.row = w.q + up((size_t)Bg * Tq * J * 64 * 4);
+    w.col = w.row + up((size_t)Bg * J * Tq * 8);
+    w.x = w.col + up((size_t)Bg * J * 1500 * 8);
+    w.tr = w.x + up((size_t)Bg * n_ld * 1500 * 4);
+    w.start = w.tr + up((size_t)Bg * wm_dtw_trace_words(n_ld) * 4);
+    w.ints = w.start + up((size_t)Bg * n_ld * 4);
+    w.bytes = w.ints + up(((size_t)4 * Bg + 2 * J) * 4);
+    return w;
+}
+
 struct LaneJob {
-    enum State { IDLE, DECODING, DRAINING };
+    enum State { IDLE, DECODING, DRAINING, ALIGNING };
     wm_ctx *c = nullptr;
     int b0 = 0, Bg = 0;   // first row of the call (a candidate call: first WINDOW) and decoder rows of the group
     int Cg = 0;           // its encoder rows: Bg, or (candidates) Bg / n_cand windows -- row c * n_cand + s is candidate s of window c
@@ -74,6 +97,13 @@ struct LaneJob {
     std::vector<int32_t> bbud, bfin_tok;
     std::vector<char> bstate;
     std::vector<float> bfin_lp, btrace;
+    // an aligned group: its workspace, the layers' alignment heads (kernel arguments of its steps), the host side of the ints
+    // (source of async uploads), the rows that have a matrix, the fetched start frames [Bg][n_ld], the tail's two events
+    AcapWs aw;
+    std::vector<WmAlignLayer> alayers;
+    std::vector<int32_t> aints, astart;
+    std::vector<char> aok;
+    WmEvents<2> tail_ev;
     float stage_sum[3] = {0.f, 0.f, 0.f};
     WmStreamFence fence;   // last member, first to go: nothing in flight outlives the tables, the events or the fetched streams
 };
@@ -100,6 +130,12 @@ struct TxCall {
     int32_t *n_hyp = nullptr;   // beam: [B]
     float *sums = nullptr;      // beam: [B][S]
     float *trace = nullptr;     // beam, debug library: [B][max_new][n_cand][WM_BEAM_TRACE] (null in the product)
+    // wm_transcribe_mel_aligned / wm_transcribe_windows_aligned: word-timestamp alignment from the decode's own queries
+    bool aligned = false;
+    int medfilt = 0;
+    float qk_scale = 1.f;
+    int32_t *start_out = nullptr;   // [B][max_new + 1]
+    float *dbg_matrix = nullptr;    // debug library: [B][max_new + 1][1500] (null in the product)
     wm_mem mem = WM_MEM_HOST;
 };
 
@@ -124,6 +160,11 @@ struct TxCfg {
     StopCfg stop;
     XCfg xc;
     bool use_graph = false;
+    // an aligned call: prompt positions from <|startoftranscript|> to the prompt's end (the same for every row), the
+    // alignment heads (ascending), the capture budget's bound on a group's rows (0: none)
+    int sot_tail = 0;
+    std::vector<int32_t> hl, hh;
+    int max_group_rows = 0;
 };
 
 // the tokens row `b` of the call may generate
@@ -146,6 +187,23 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     j.mode.rep = m->rep_on || m->sb_on;   // (tx_validate turns the extended decode on with them; the bias reads the rules' bitmaps)
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
+    if (call.aligned) {   // the capture buffer and the alignment workspace, reserved before anything is enqueued
+        const int J = (int)cfg.hl.size();
+        j.aw = acap_layout(Bg, cfg.sot_tail + call.max_new - 1, J, call.max_new + 1);
+        WM_TRY(m->acap_ws.reserve(c->stream, j.aw.bytes));
+        j.alayers.assign(m->dims.n_text_layer, WmAlignLayer());
+        j.aints.assign((size_t)4 * Bg + 2 * J, 0);
+        for (int k = 0; k < J; ++k) {
+            WmAlignLayer &Ly = j.alayers[cfg.hl[k]];
+            if (Ly.n == 0) Ly.slot0 = k;
+            Ly.head[Ly.n++] = cfg.hh[k];
+            j.aints[4 * Bg + k] = cfg.hl[k];
+            j.aints[4 * Bg + J + k] = cfg.hh[k];
+        }
+        j.mode.acap = true; j.mode.acap_base = j.P - cfg.sot_tail; j.mode.acap_Tq = j.aw.Tq; j.mode.acap_J = J;
+        j.mode.acap_q = (float *)((char *)m->acap_ws.p + j.aw.q);
+        if (call.dbg_matrix) WM_HIP(hipMemsetAsync((char *)m->acap_ws.p + j.aw.x, 0, (size_t)Bg * j.aw.n_ld * 1500 * 4, c->stream));
+    }
     const void *d_pcm;
     WM_TRY(wm_stage_pcm(c, call.src, j.b0, Cg, call.mem, &d_pcm));
     // decode state first (prompt tokens, position 0): a pageable H2D copy may wait for the stream to drain, so it is issued
@@ -213,7 +271,8 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
 // hipGraph per lane and replayed for every position -- and `burst` consecutive positions are captured as one more graph.
 // gen (a beam group's generating positions): the step also stores the f32 logits and the beam kernels close it.
 int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) {
-    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen, 0, j.c->model->dims.n_vocab - 1, nullptr, mode, n_prompt));
+    WmAlignCap cap = {j.alayers.data(), mode.acap_q, mode.acap_Tq, mode.acap_J, mode.acap_base};   // an aligned group: every step captures
+    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen, 0, j.c->model->dims.n_vocab - 1, mode.acap ? &cap : nullptr, mode, n_prompt));
     if (gen) return wm_model_beam_close(j.c, j.Bg, n_prompt, mode);
     return wm_model_close_step(j.c, j.Bg, n_prompt, true, nullptr, 0, mode);
 }
@@ -455,7 +514,7 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     const int32_t ns_tok = opts ? opts->no_speech_token : -1;
     // (a ragged call places <|startoftranscript|> by sot_tail; opts->sot_index is not read)
     const int32_t sot_index = (opts && !p.len) ? opts->sot_index : 0;
-    if (p.len && call.no_speech_out) {
+    if (p.len && (call.no_speech_out || call.aligned)) {   // (an aligned call always reads sot_tail: its capture starts there)
         const int shortest = *std::min_element(p.len, p.len + B);
         WM_REQUIRE(p.sot_tail >= 1 && p.sot_tail <= shortest, WM_ERR_INVALID, "sot_tail %d outside [1, %d] (the shortest prompt)",
                    p.sot_tail, shortest);
@@ -487,6 +546,18 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     cfg->stop.on = !no_stop && (call.eot >= 0 || !budgets.empty());
     cfg->stop.eot = call.eot;
     cfg->stop.budgets = budgets.empty() ? nullptr : budgets.data();
+    if (call.aligned) {
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "aligned transcribe calls are not supported by the all-f32 precision path");
+        WM_REQUIRE(call.start_out, WM_ERR_INVALID, "null start_frame_out");
+        WM_REQUIRE(call.medfilt >= 1 && call.medfilt <= 31 && call.medfilt % 2 == 1, WM_ERR_INVALID,
+                   "medfilt_width %d must be odd, 1 .. 31", call.medfilt);
+        WM_REQUIRE(std::isfinite(call.qk_scale), WM_ERR_INVALID, "qk_scale must be finite");
+        WM_REQUIRE(call.n_cand == 1 && !call.beam, WM_ERR_INVALID, "an aligned call decodes one sample per row");
+        cfg->sot_tail = p.len ? p.sot_tail : n_prompt - sot_index;
+        wm_align_heads(m, &cfg->hl, &cfg->hh);
+        const int rows = wm_align_group_rows((size_t)cfg->sot_tail + max_new - 1, cfg->hl.size(), (size_t)max_new + 1);
+        cfg->max_group_rows = rows < WM_DEC_MAXB ? rows : 0;
+    }
     return WM_OK;
 }
 
@@ -614,6 +685,54 @@ int lane_fetch(TxRun &r, LaneJob &j) {
     return WM_OK;
 }
 
+// The tail of an aligned group, enqueued once its rows' lengths are known: matrix row k of row b is the decoder position whose
+// output was generated token k, i.e. capture row S + k with S = sot_tail - 1 rows in front (the prompt from
+// <|startoftranscript|> on, less the one whose output is token 0); a row's decoder rows are S + len, none behind the last matrix
+// row (WmAlignDev::tail 0).  Against the lane's own cross-K/V, on the lane's stream.
+int lane_align(TxRun &r, LaneJob &j) {
+    const TxCall &call = r.call;
+    wm_ctx *c = j.c;
+    WmModel *m = c->model;
+    const int Bg = j.Bg, S = r.cfg.sot_tail - 1, n_ld = j.aw.n_ld, J = j.aw.J;
+    char *ws = (char *)m->acap_ws.p;
+    int nmax = -1, mmax = 0, rows_max = 0;
+    j.aok.assign(Bg, 0);
+    for (int b = 0; b < Bg; ++b) {
+        const int row = j.b0 + b, len = call.lens_out[row];
+        const int nf = call.src.windows ? call.src.set->n_frames[call.src.rows ? call.src.rows[row] : row] : call.src.n_frames[row];
+        const bool ok = len >= 1 && nf >= 2 && S + len >= 2;
+        j.aok[b] = ok;
+        j.aints[b] = ok ? len - 1 : -1;
+        j.aints[Bg + b] = nf;
+        j.aints[2 * Bg + b] = ok ? len : 0;
+        j.aints[3 * Bg + b] = nf / 2;
+        if (ok) { nmax = std::max(nmax, len - 1); mmax = std::max(mmax, nf / 2); rows_max = std::max(rows_max, len); }
+    }
+    WM_HIP(hipEventRecord(j.tail_ev[0], c->stream));
+    if (nmax >= 0) {
+        int *ints = (int *)(ws + j.aw.ints);
+        float *x = (float *)(ws + j.aw.x);
+        WM_HIP(hipMemcpyAsync(ints, j.aints.data(), j.aints.size() * 4, hipMemcpyHostToDevice, c->stream));
+        WmAlignDev a;
+        a.q = j.mode.acap_q; a.xkv = m->xkv; a.hl = ints + 4 * Bg; a.hh = ints + 4 * Bg + J; a.n_text = ints; a.n_frames = ints + Bg;
+        a.rowst = (float *)(ws + j.aw.row); a.colst = (float *)(ws + j.aw.col); a.x = x;
+        a.B = Bg; a.H = m->dims.n_text_head; a.Tq = j.aw.Tq; a.J = J; a.S = S; a.n_ld = n_ld;
+        a.sc = 0.125f * call.qk_scale * 1.44269504088896340736f;
+        a.half = call.medfilt / 2;
+        a.tail = 0; a.n_min = 0;
+        WM_TRY(wm_align_matrix(c, a, nmax, mmax));
+        int *start = (int *)(ws + j.aw.start);
+        WM_TRY(wm_dtw(c, x, (long)n_ld * 1500, 1500, ints + 2 * Bg, ints + 3 * Bg, Bg, rows_max, mmax, (unsigned *)(ws + j.aw.tr), start, n_ld));
+        j.astart.resize((size_t)Bg * n_ld);
+        WM_HIP(hipMemcpyAsync(j.astart.data(), start, j.astart.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        if (call.dbg_matrix)
+            WM_HIP(hipMemcpyAsync(call.dbg_matrix + (size_t)j.b0 * n_ld * 1500, x, (size_t)Bg * n_ld * 1500 * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    WM_HIP(hipEventRecord(j.tail_ev[1], c->stream));
+    j.state = LaneJob::ALIGNING;
+    return WM_OK;
+}
+
 // A draining lane whose stream has drained writes its rows of the call's outputs and adds its stage times.  A decode group
 // runs for seconds -- poll instead of spinning in hipStreamSynchronize, so that the host threads of the other lanes / ranks
 // (one process per GPU, several contexts each) keep their cores.
@@ -632,6 +751,38 @@ int lane_finish(TxRun &r, LaneJob &j, bool *done) {
                           call.tokens_out, call.lens_out, r.cfg.xc.logprobs, r.cfg.xc.no_speech);
     }
     wm_add_stage_ms(j.ev.e, 3, call.src.windows, j.stage_sum);
+    if (call.aligned) return lane_align(r, j);   // the rows' lengths are known now: the alignment tail, then ALIGNING
+    j.state = LaneJob::IDLE;
+    ++r.groups_done;
+    *done = true;
+    return WM_OK;
+}
+
+// An aligned group whose tail has drained writes its rows of start_frame_out: row k < len starts at the first frame of matrix
+// row k on the DTW path, entry len is M, -1 behind; a row without a matrix is all -1, or (0, M) when its one decoder row
+// has nothing to be z-scored against.
+int lane_align_finish(TxRun &r, LaneJob &j, bool *done) {
+    const TxCall &call = r.call;
+    *done = false;
+    const hipError_t q = hipStreamQuery(j.c->stream);
+    if (q == hipErrorNotReady) { (void)hipGetLastError(); return WM_OK; }
+    WM_HIP(q);
+    WM_HIP(hipStreamSynchronize(j.c->stream));
+    const int n_ld = j.aw.n_ld, Bg = j.Bg;
+    for (int b = 0; b < Bg; ++b) {
+        int32_t *out = call.start_out + (size_t)(j.b0 + b) * n_ld;
+        const int len = call.lens_out[j.b0 + b], nf = j.aints[Bg + b], M = nf / 2;
+        for (int k = 0; k < n_ld; ++k) out[k] = -1;
+        if (j.aok[b]) {
+            for (int k = 0; k < len; ++k) out[k] = j.astart[(size_t)b * n_ld + k];
+            out[len] = M;
+        } else if (len == 1 && nf >= 2) {   // R = 1: the standard deviation over one row is zero
+            out[0] = 0;
+            out[1] = M;
+        }
+    }
+    float ms;
+    if (hipEventElapsedTime(&ms, j.tail_ev[0], j.tail_ev[1]) == hipSuccess) j.stage_sum[2] += ms;
     j.state = LaneJob::IDLE;
     ++r.groups_done;
     *done = true;
@@ -648,6 +799,7 @@ int tx_run(wm_ctx *ctx, const TxCall &call, const TxCfg &cfg, const WmTxPlan &pl
         j.fence.s = j.c->stream;
         WM_TRY(j.ev.create());
         if (cfg.stop.on) WM_TRY(j.burst_ev.create_untimed());
+        if (call.aligned) WM_TRY(j.tail_ev.create());
     }
     ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
     ActiveGuard active_guard(g_wm_active_decodes[ctx->device & 63]);
@@ -664,9 +816,13 @@ int tx_run(wm_ctx *ctx, const TxCall &call, const TxCfg &cfg, const WmTxPlan &pl
                 WM_TRY(lane_advance(r, j, &step));
                 if (step == LANE_ENQUEUED_ALL) WM_TRY(lane_fetch(r, j));
                 progress |= step != LANE_WAITS;
-            } else {
+            } else if (j.state == LaneJob::DRAINING) {
                 bool done;
                 WM_TRY(lane_finish(r, j, &done));
+                progress |= done || j.state == LaneJob::ALIGNING;
+            } else {
+                bool done;
+                WM_TRY(lane_align_finish(r, j, &done));
                 progress |= done;
             }
         }
@@ -724,6 +880,7 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
     pin.explicit_lanes = ctx->max_lanes > 0;
     pin.lanes = pin.explicit_lanes ? ctx->max_lanes : lane_limit();
     pin.prof_on = ctx->prof.on; pin.no_cu_masks = ctx->no_cu_masks; pin.n_text_state = m->dims.n_text_state;
+    pin.max_group_rows = cfg.max_group_rows;   // (an aligned call under its capture budget; else 0: none)
     WmTxPlan plan;
     std::vector<wm_ctx *> lanes;
     bool masks_refused = false;
@@ -733,6 +890,10 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
         ctx->no_cu_masks = pin.no_cu_masks = true;
         wm_tx_plan(pin, g_wm_tuning, &plan);
         WM_TRY(tx_lanes(ctx, plan, &lanes, &masks_refused));
+    }
+    if (call.aligned) {   // rows of a group that never ran (an error below) read "no alignment"
+        std::fill(call.start_out, call.start_out + (size_t)call.B * (call.max_new + 1), -1);
+        if (call.dbg_matrix) memset(call.dbg_matrix, 0, (size_t)call.B * (call.max_new + 1) * 1500 * 4);
     }
     WM_TRY(tx_run(ctx, call, cfg, plan, lanes));
     return tx_rank(call);
@@ -778,6 +939,15 @@ void beam(wm_ctx *ctx, TxCall &call, const int32_t *prompts, int prompt_stride, 
     if (ctx && ctx->model) {   // the debug library's capture is for this call only
         call.trace = ctx->model->beam_dbg_trace;
         ctx->model->beam_dbg_trace = nullptr;
+    }
+}
+
+// the aligned calls: the three new arguments, and the debug library's one-shot cost-matrix capture (for this call only)
+void aligned(wm_ctx *ctx, TxCall &call, int medfilt_width, float qk_scale, int32_t *start_frame_out) {
+    call.aligned = true; call.medfilt = medfilt_width; call.qk_scale = qk_scale; call.start_out = start_frame_out;
+    if (ctx && ctx->model) {
+        call.dbg_matrix = ctx->model->align_dbg_matrix;
+        ctx->model->align_dbg_matrix = nullptr;
     }
 }
 }  // namespace
@@ -884,5 +1054,37 @@ extern "C" int wm_transcribe_windows_beam(wm_ctx *ctx, const wm_windows *w, cons
     beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
          sum_logprobs_out, best_out);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+// wm_transcribe_mel_ragged (prompt_len null: wm_transcribe_mel) whose decode keeps the alignment heads' cross-attention queries:
+// the same tokens, plus the start frame of every generated token (lane_align)
+extern "C" int wm_transcribe_mel_aligned(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                         const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                         int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                         int max_new, int32_t eot, const wm_decode_opts *opts, int medfilt_width, float qk_scale,
+                                         int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                         float *no_speech_prob_out, int32_t *start_frame_out, wm_mem mem) try {
+    TxCall call;
+    call.entry = prompt_len ? TxCall::RAGGED : TxCall::MEL;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    call.prompts = {prompts, prompt_stride, prompt_len, prompt_len ? sot_tail : 0, sample_ids};
+    call.n_prompt = prompt_stride;
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+// ... over the windows of an encoded set (wm_transcribe_windows with one sample per row)
+extern "C" int wm_transcribe_windows_aligned(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                             int prompt_stride, const int32_t *prompt_len, int sot_tail, const uint32_t *sample_ids,
+                                             int max_new, int32_t eot, const wm_decode_opts *opts, int medfilt_width,
+                                             float qk_scale, int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                             float *no_speech_prob_out, int32_t *start_frame_out) try {
+    TxCall call;
+    set_src(call, w, rows);
+    best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, 1, NAN, nullptr);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH

@@ -93,10 +93,18 @@ void wm_tx_plan(const WmTxPlanIn &in, const WmTuning &t, WmTxPlan *out) {
     const int L = in.prof_on ? 1 : in.lanes;
     out->L = L;
     out->parts = (in.prof_on || solo || in.no_cu_masks || N > 1) ? 0 : wm_lane_parts(B, L, in.explicit_lanes, in.n_text_state, 0, t);
+    // the row bound of a group (0: none) as a least number of groups: whole windows, at least one per group
+    const int w_max = in.max_group_rows > 0 ? std::max(1, in.max_group_rows / N) : 0;
+    const int g_min = w_max > 0 ? (B + w_max - 1) / w_max : 1;
+    if (out->parts && g_min > out->parts) out->parts = 0;   // the parts are one group each
     if (N > 1) {   // a decode group holds whole rows: tokens_out [B][N][max_new]
         out->G = wm_cand_groups(B, N, L, in.explicit_lanes, out->b0, out->cg);
     } else {
         out->G = out->parts ? out->parts : wm_group_count(B, L, in.explicit_lanes, t.group_chunks);
+        wm_balanced_cut(B, out->G, out->b0, out->cg);
+    }
+    if (out->G < g_min) {
+        out->G = g_min;
         wm_balanced_cut(B, out->G, out->b0, out->cg);
     }
     out->n_lanes = solo ? 1 : (out->parts ? out->parts : (out->G < L ? out->G : L));
@@ -178,14 +186,15 @@ void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, con
 }
 
 // ---------------------------------------------------------------- the hooks' flat forms ----
-int wm_tx_plan_flat(const int32_t *in, int32_t *out, int32_t *cut, int cut_cap) {
+int wm_tx_plan_flat(const int32_t *in, int32_t *out, int32_t *cut, int cut_cap, int max_group_rows) {
     WmTxPlanIn pin;
+    pin.max_group_rows = max_group_rows;
     pin.B = in[0]; pin.N = in[1]; pin.lanes = in[2]; pin.explicit_lanes = in[3] != 0; pin.prof_on = in[4] != 0;
     pin.no_cu_masks = in[5] != 0; pin.n_text_state = in[6];
     WmTuning t;
     t.lane_parts = in[7]; t.lane_solo_cus = in[8]; t.group_chunks = in[9];
     for (int i = 0; i < WM_TX_PLAN_OUT; ++i) out[i] = 0;
-    if (pin.B < 1 || pin.N < 1 || pin.N > WM_DEC_MAXB || pin.lanes < 1 || t.group_chunks < 0) return -1;
+    if (pin.B < 1 || pin.N < 1 || pin.N > WM_DEC_MAXB || pin.lanes < 1 || t.group_chunks < 0 || max_group_rows < 0) return -1;
     WmTxPlan plan;
     wm_tx_plan(pin, t, &plan);
     if (2 * plan.G > cut_cap) return -1;

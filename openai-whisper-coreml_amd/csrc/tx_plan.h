@@ -36,6 +36,10 @@ struct WmTxPlanIn {
     bool prof_on = false;         // per-kernel profiling: everything on the caller's context
     bool no_cu_masks = false;     // this device refused a CU-masked stream before
     int n_text_state = 0;
+    // Upper bound on the rows (candidate call: windows x N decoder rows) of ONE group; 0: none.  An aligned call's capture
+    // budget (wm_transcribe_mel_aligned): at least ceil(B / bound) balanced groups, and no sub-chip parts when they would be
+    // too few.  With 0 the plan is what it was before the bound existed.
+    int max_group_rows = 0;
 };
 
 struct WmTxPlan {
@@ -90,6 +94,7 @@ constexpr int WM_TX_PLAN_IN = 12, WM_TX_PLAN_OUT = 8;
 constexpr int WM_TX_TAB_IN = 256, WM_TX_TAB_OUT = 576, WM_TX_TAB_ROWS = 16, WM_TX_TAB_POS = 12;
 constexpr int WM_TX_ROWS_IN = 320, WM_TX_ROWS_OUT = 288, WM_TX_ROWS_NEW = 8;
 // returns the entries written to cut (b0[0 .. G), cg[0 .. G)), or -1 when they do not fit cut_cap
-int wm_tx_plan_flat(const int32_t *in, int32_t *out, int32_t *cut, int cut_cap);
+// (max_group_rows: WmTxPlanIn's, not part of the flat input -- wmdbg_tx_plan_bounded passes it beside)
+int wm_tx_plan_flat(const int32_t *in, int32_t *out, int32_t *cut, int cut_cap, int max_group_rows = 0);
 bool wm_group_tables_flat(const int32_t *in, int ids_stride, int32_t *out);
 bool wm_group_rows_out_flat(const int32_t *in, int32_t *out);

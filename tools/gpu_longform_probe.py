@@ -5,7 +5,7 @@ given as argv[1] (default base), every matrix scaled by weights.lively_gain so t
 length (argv[2], default 8: 10 .. 150 s), the production vocabulary's token ids, text context n_text_ctx.  Prints one JSON
 line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form.
 
-    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words [--teacher-panel W] | --reuse]
+    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words [--teacher-panel W] [--decode] | --reuse]
 
 --condition: the cost of condition_on_previous_text instead.  One more JSON line: wall seconds of the long form with
 conditioning off and on (the same recordings, after a warm-up of each; with the default fallback thresholds and with the
@@ -22,6 +22,10 @@ each, the windows and words of a run, and over the wm_align_mel calls of one run
 wm_last_stage_ms split (window gather + encoder + cross K/V, teacher-forced pass, alignment kernels + DTW).
 --teacher-panel W (with --words): a third interleaved run, word_timestamps on with wm_set_teacher_panel(W) (label on_panel; the
 plain `on` run is width 1); its result is asserted equal to the width-1 run's, and the line gains the panel run's stage split.
+--decode (with --words): one more interleaved run, word_timestamps="decode" (label decode: the alignment from the decode's own
+pass, no wm_align_mel call); the line gains its wall time over `off` and over the teacher-forced runs, whether its windows'
+tokens are the `off` run's (the word-driven seek may cut other windows), and the decode-loop time (wm_last_stage_ms[2], the
+alignment tail included) of its calls.
 
 --reuse: the cost and the gain of reuse_encoder (window sets) instead.  Two configurations -- (a) the default fallback, where
 the synthetic model takes all six temperatures, (b) fallback off with word_timestamps -- each with reuse_encoder off / on
@@ -45,12 +49,13 @@ b = pkg.binding
 CONDITION = "--condition" in sys.argv
 WORDS = "--words" in sys.argv
 REUSE = "--reuse" in sys.argv
+DECODE = "--decode" in sys.argv
 PANEL = None
 if "--teacher-panel" in sys.argv:
     i = sys.argv.index("--teacher-panel")
     PANEL = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
-argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words", "--reuse")]
+argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words", "--reuse", "--decode")]
 name = argv[0] if len(argv) > 0 else "base"
 N = int(argv[1]) if len(argv) > 1 else 8
 dims = dict(b.MODEL_DIMS[name])
@@ -176,6 +181,18 @@ def words_probe():
     if PANEL:
         ctx.set_teacher_panel(PANEL)
         ctx.transcribe_long(recs, **kw, **on)
+    dec_ms = []   # wm_last_stage_ms[2] of the aligned decode calls of the run in progress
+    if DECODE:
+        dec = dict(keep, word_timestamps="decode")
+        inner_dec = ctx.transcribe_mel_aligned
+
+        def counted_dec(*a, **k):
+            r = inner_dec(*a, **k)
+            dec_ms.append(float(ctx.last_stage_ms()[2]))
+            return r
+        ctx.transcribe_mel_aligned = counted_dec
+        ctx.transcribe_long(recs, **kw, **dec)
+        runs.append(("decode", dec, None))
     walls = {label: [] for label, _, _ in runs}
     outs, stages = {}, {}
     for _ in range(3):
@@ -183,6 +200,7 @@ def words_probe():
             if width is not None:
                 ctx.set_teacher_panel(width)
             del calls[:]
+            del dec_ms[:]
             t0 = time.perf_counter()
             out = ctx.transcribe_long(recs, **kw, **extra)
             walls[label].append(time.perf_counter() - t0)
@@ -199,6 +217,17 @@ def words_probe():
         extra_out = dict(teacher_panel=PANEL, on_panel_over_off=float(np.median(walls["on_panel"]) / np.median(walls["off"])),
                          on_panel_over_on=float(np.median(walls["on_panel"]) / np.median(walls["on"])),
                          align_stage_ms_panel=dict(encoder_cross_kv=sp[0], teacher_forced=sp[1], alignment_dtw=sp[2]))
+    if DECODE:
+        ctx.transcribe_mel_aligned = inner_dec
+        tok = lambda o: [[w["tokens"] for w in r["windows"]] for r in o]   # noqa: E731
+        same_windows = tok(outs["decode"]) == tok(outs["off"])   # (the word-driven seek may cut other windows than `off`)
+        med = {k: float(np.median(v)) for k, v in walls.items()}
+        extra_out.update(decode_over_off=med["decode"] / med["off"], decode_over_on=med["decode"] / med["on"],
+                         decode_windows=sum(len(o["windows"]) for o in outs["decode"]),
+                         decode_words=sum(len(s["words"]) for o in outs["decode"] for s in o["segments"]),
+                         decode_same_windows_as_off=same_windows, decode_loop_ms=sum(dec_ms), decode_calls=len(dec_ms))
+        if PANEL:
+            extra_out["decode_over_on_panel"] = med["decode"] / med["on_panel"]
     out = outs["on"]
     stage = stages["on"]
     print(json.dumps(dict(model=name, recordings=N, audio_s=audio_s, wall_s=walls,
