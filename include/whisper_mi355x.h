@@ -475,7 +475,7 @@ WM_API int wm_windows_detect_language(wm_ctx *ctx, const wm_windows *w, const in
  * same bits.  A failed allocation is WM_ERR_NOMEM and leaks nothing.  wm_last_stage_ms[2] includes the alignment kernels
  * and the DTW.
  * A row's results depend on the row alone (as wm_transcribe_mel_ragged); scope and inheritance of every setting as there.
- * No aligned counterpart exists for best_of > 1 or beam search.
+ * best_of > 1 and beam search: the four entries below.
  * Invalid: medfilt_width even or outside 1 .. 31, a qk_scale that is not finite, a null start_frame_out, in a ragged call a
  * sot_tail outside [1, the shortest prompt_len] (always read here), and everything the underlying call rejects.  The debug
  * library's all-f32 precision path answers WM_ERR_STATE. */
@@ -494,6 +494,61 @@ WM_API int wm_transcribe_windows_aligned(wm_ctx *ctx, const wm_windows *w, const
                                          int medfilt_width, float qk_scale, int32_t *tokens_out, int32_t *lens_out,
                                          float *token_logprobs_out, float *no_speech_prob_out,
                                          int32_t *start_frame_out /* [B][max_new + 1] */);
+
+/* The aligned counterparts of the best-of and beam calls:
+ *   wm_transcribe_mel_best_of_aligned     = wm_transcribe_mel_best_of
+ *   wm_transcribe_windows_best_of_aligned = wm_transcribe_windows
+ *   wm_transcribe_mel_beam_aligned        = wm_transcribe_mel_beam
+ *   wm_transcribe_windows_beam_aligned    = wm_transcribe_windows_beam
+ * each with the arguments of its plain counterpart plus medfilt_width, qk_scale and start_frame_out i32 [B][max_new + 1] (as in
+ * wm_transcribe_mel_aligned).
+ * Decode outputs: every output of the plain counterpart -- tokens, lengths, log-probs, sums, n_hyp, no_speech_prob, best_out --
+ * is BIT FOR BIT that call's for the same arguments: at any temperature (best-of), with suppress lists, timestamp rules,
+ * repetition rules, sequence bias, token budgets, early stop and any lane count.
+ * Alignment output: best_out must not be null (WM_ERR_INVALID).  start_frame_out[b] belongs to the ONE hypothesis h =
+ * best_out[b] of window b and follows wm_transcribe_mel_aligned's row rule applied to that hypothesis' own tokens g_h[0 ..
+ * len_h): decoder rows prompt[a_b .. P_b) ++ g_h[0 .. len_h - 1), the cost matrix their last len_h rows, the DTW on [len_h][M_b],
+ * start_frame_out[b][len_h] = M_b and -1 behind.  Degenerate cases as there: len_h == 0 or n_frames[b] < 2 gives all -1, fewer
+ * than 2 decoder rows give 0, M_b.  The other hypotheses of a window get NO alignment: a host that ranks the hypotheses by a rule
+ * of its own aligns its choice with wm_align_mel.
+ * best_of 1 is wm_transcribe_mel_aligned bit for bit, start frames included, and so is beam_size 1 with max_candidates 1; at
+ * temperature 0 a best-of call aligns candidate 0.
+ * Every candidate / beam of a window keeps its queries while the decode runs (a beam search re-parents its beams after every
+ * token: the rows stay where they were captured and the search records which beam each row continued), so a window counts
+ * best_of / beam_size rows, the chosen hypothesis' gathered queries and the window's own statistics and cost matrix towards the
+ * 2 GiB a group may hold; groups are made of whole windows.  A window's results depend on the window alone.
+ * Invalid: a null best_out, and everything the plain counterpart and wm_transcribe_mel_aligned reject.  The debug library's
+ * all-f32 precision path answers WM_ERR_STATE. */
+WM_API int wm_transcribe_mel_best_of_aligned(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                             const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                             int prompt_stride, const int32_t *prompt_len /* nullable */, int sot_tail,
+                                             const uint32_t *sample_ids, int best_of, float length_penalty, int max_new,
+                                             int32_t eot, const wm_decode_opts *opts, int medfilt_width, float qk_scale,
+                                             int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                             float *no_speech_prob_out, int32_t *best_out,
+                                             int32_t *start_frame_out /* [B][max_new + 1] */, wm_mem mem);
+WM_API int wm_transcribe_windows_best_of_aligned(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B,
+                                                 const int32_t *prompts, int prompt_stride, const int32_t *prompt_len /* nullable */,
+                                                 int sot_tail, const uint32_t *sample_ids, int best_of, float length_penalty,
+                                                 int max_new, int32_t eot, const wm_decode_opts *opts, int medfilt_width,
+                                                 float qk_scale, int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                                 float *no_speech_prob_out, int32_t *best_out,
+                                                 int32_t *start_frame_out /* [B][max_new + 1] */);
+WM_API int wm_transcribe_mel_beam_aligned(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                          const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                          int prompt_stride, const int32_t *prompt_len /* nullable */, int sot_tail, int beam_size,
+                                          int max_candidates, float length_penalty, int max_new, int32_t eot,
+                                          const wm_decode_opts *opts, int medfilt_width, float qk_scale, int32_t *tokens_out,
+                                          int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out, float *token_logprobs_out,
+                                          float *no_speech_prob_out, int32_t *best_out,
+                                          int32_t *start_frame_out /* [B][max_new + 1] */, wm_mem mem);
+WM_API int wm_transcribe_windows_beam_aligned(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B, const int32_t *prompts,
+                                              int prompt_stride, const int32_t *prompt_len /* nullable */, int sot_tail,
+                                              int beam_size, int max_candidates, float length_penalty, int max_new, int32_t eot,
+                                              const wm_decode_opts *opts, int medfilt_width, float qk_scale, int32_t *tokens_out,
+                                              int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
+                                              float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out,
+                                              int32_t *start_frame_out /* [B][max_new + 1] */);
 
 /* The alignment heads wm_align, wm_align_mel and the aligned transcribe calls read: n (layer, head) pairs, any order (used ascending).  n = 0 restores the default, every
  * head of the decoder layers n_text_layer / 2 .. n_text_layer - 1 (openai-whisper's default when a checkpoint has no list);

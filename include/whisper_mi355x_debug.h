@@ -336,6 +336,27 @@ WM_API int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, const
  * The next aligned transcribe call (wm_transcribe_mel_aligned, wm_transcribe_windows_aligned) is served the same way:
  * matrix_out f32 [B][max_new + 1][1500], 0 outside each row's len_b x M_b block. */
 WM_API int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out);
+/* The aligned best-of / beam calls (wm_transcribe_mel_best_of_aligned, wm_transcribe_mel_beam_aligned and the window-set
+ * pair), each for the NEXT aligned transcribe call on ctx only.  wmdbg_align_capture and wmdbg_beam_trace serve them too.
+ * wmdbg_align_hyp: the call aligns hypothesis min(h, n_hyp - 1) of every window instead of best_out[b] (best-of: n_hyp =
+ * best_of); best_out itself is the ranking's, as always.  For tests only.
+ * wmdbg_hyp_slots: the call leaves the slot tables it aligned from in slots_out i32 [B][Tq], Tq = sot_tail + max_new - 1: entry t
+ * is the candidate / beam (0 .. N - 1) whose capture slot held capture row t of the aligned hypothesis (zeros with one row per
+ * window; entries at or past the hypothesis' own S + len rows are not read by the alignment). */
+WM_API int wmdbg_align_hyp(wm_ctx *ctx, int h);
+WM_API int wmdbg_hyp_slots(wm_ctx *ctx, int32_t *slots_out);
+/* wm_beam_ancestry (csrc/beam.h), the host function an aligned beam group finds a hypothesis' capture slots with, for ONE window:
+ * anc i32 [max_new][N] (the source beam of every slot at every close), fin_n finished hypotheses with fin_src / fin_len [fin_n],
+ * wsteps closes, the live beams' sums f32 [N] (-inf: dead); h in the window's output order (finished first, then the live beams by
+ * descending sum until there are N); S = sot_tail - 1.  Fills slot i32 [Tq] and returns the hypothesis' length, -1 when the window
+ * has no hypothesis h, -2 on bad arguments.  Host only. */
+WM_API int wmdbg_beam_ancestry(int N, int max_new, const int32_t *anc, int fin_n, const int32_t *fin_src, const int32_t *fin_len,
+                               int wsteps, const float *sum, int h, int S, int Tq, int32_t *slot);
+/* The gather kernel of an aligned best-of / beam group alone (align.hip), on host data: cap f32 [C * N][Tq][J][64], slot i32
+ * [C][Tq] (each in [0, N)), n_rows i32 [C] (each in [0, Tq]); q_sel f32 [C][Tq][J][64] goes to the device as the caller filled
+ * it and comes back with q_sel[c][t] = cap[c * N + slot[c][t]][t] for t < n_rows[c], everything else untouched. */
+WM_API int wmdbg_align_gather(wm_ctx *ctx, const float *cap, int C, int N, int Tq, int J, const int32_t *slot,
+                              const int32_t *n_rows, float *q_sel);
 /* The alignment kernels of wm_align alone (column statistics, then the cost matrix) on host data.  q f32 [B][Tq][J][64] (the
  * capture buffer: chunk b's decoder rows 0 .. S + n_text[b] + 1), keys f32 [L][B][H][1500][64] (the cross-attention keys of
  * every decoder layer, chunk and head), alignment heads (hl[j], hh[j]), j < J, in the order the mean adds them.  Row counts as

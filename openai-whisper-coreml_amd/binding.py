@@ -138,6 +138,14 @@ def load_library(path=None):
                                       vp, vp, vp, vp, vp, ip],
         "wm_transcribe_windows_aligned": [vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_int32, vp, ip, ctypes.c_float, vp, vp,
                                           vp, vp, vp],
+        "wm_transcribe_mel_best_of_aligned": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_float, ip, ctypes.c_int32,
+                                              vp, ip, ctypes.c_float, vp, vp, vp, vp, vp, vp, ip],
+        "wm_transcribe_windows_best_of_aligned": [vp, vp, vp, ip, vp, ip, vp, ip, vp, ip, ctypes.c_float, ip, ctypes.c_int32, vp, ip,
+                                                  ctypes.c_float, vp, vp, vp, vp, vp, vp],
+        "wm_transcribe_mel_beam_aligned": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, ip, ip, ctypes.c_float, ip, ctypes.c_int32, vp,
+                                           ip, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, vp, ip],
+        "wm_transcribe_windows_beam_aligned": [vp, vp, vp, ip, vp, ip, vp, ip, ip, ip, ctypes.c_float, ip, ctypes.c_int32, vp, ip,
+                                               ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, vp],
         "wm_set_lanes": [vp, ip],
         "wm_dev_malloc": [vp, sz, pp],
         "wm_dev_free": [vp, vp],
@@ -875,12 +883,13 @@ class _LongOptions(types.SimpleNamespace):
             raise ValueError("initial_prompt_tokens: one list per recording")
         if self.vocab_size is None:
             self.vocab_size = int(self.ctx.dims["n_vocab"])
-        if isinstance(self.word_timestamps, str) and self.word_timestamps != "decode":
-            raise ValueError("word_timestamps: False, True or 'decode'")
+        if isinstance(self.word_timestamps, str) and self.word_timestamps not in ("decode", "decode_best"):
+            raise ValueError("word_timestamps: False, True, 'decode' or 'decode_best'")
         self.words_on = bool(self.word_timestamps)
         self.words_decode = isinstance(self.word_timestamps, str)   # 18.: the alignment comes with the decode
-        if self.words_decode and (self.best_of is not None or self.beam_size is not None):
-            raise ValueError("word_timestamps='decode' cannot be combined with best_of or beam_size: they have no aligned call")
+        self.words_best = self.word_timestamps == "decode_best"     # 19.: ... of best_of candidates and beams too
+        if self.words_decode and not self.words_best and (self.best_of is not None or self.beam_size is not None):
+            raise ValueError("word_timestamps='decode' cannot be combined with best_of or beam_size: that is 'decode_best'")
         if self.words_on and (self.vocab is None or (self.no_timestamps is None and not self.words_decode)):
             raise ValueError("word_timestamps needs vocab and no_timestamps")
         self.clips_on = self.clip_timestamps is not None
@@ -1033,10 +1042,7 @@ class _RoundRows:
         kw = dict(eot=o.eot, temperature=t, seed=sd, no_speech_token=o.no_speech_token, sample_ids=[self.ids[i] for i in todo],
                   **o.sot_kw, **extra)
         if o.words_decode:   # 18.: every attempt through the aligned entry; the kept one's start frames feed the word step
-            if self.set is not None:
-                r = o.ctx.transcribe_windows_aligned(self.set, [int(i) for i in todo], prompts, o.max_new, **kw)
-            else:
-                r = o.ctx.transcribe_mel_aligned(*self._mel_windows(todo), prompts, o.max_new, mem=WM_MEM_DEVICE, **kw)
+            r = self._decode_aligned(todo, prompts, kw, extra)
             for k, i in enumerate(todo):
                 self.aligned[i] = (r.start_frames[k], r.logprobs[k], int(r.lens[k]), r.tokens[k])
         elif self.set is not None:   # the same call without the encoder pass
@@ -1048,6 +1054,28 @@ class _RoundRows:
                 self.kept_by[i]["candidate"] = int(r.candidate[k]) if "best_of" in extra else 0
             if o.beam_size is not None:
                 self.kept_by[i]["hypothesis"] = int(r.hypothesis[k]) if "beam_size" in extra else 0
+        return r
+
+    def _decode_aligned(self, todo, prompts, kw, extra):
+        """The aligned entry of a fallback step: the plain one or, 19., the beam / best-of one the step's `extra` asks for
+        (fallback_step_extra) -- then the TranscribeResult of the hypotheses it chose, with their start_frames."""
+        o = self.o
+        if self.set is not None:
+            rows, tail, kind = (self.set, [int(i) for i in todo], prompts, o.max_new), {}, "windows"
+        else:
+            rows, tail, kind = (*self._mel_windows(todo), prompts, o.max_new), dict(mem=WM_MEM_DEVICE), "mel"
+        if not extra:
+            return getattr(o.ctx, "transcribe_%s_aligned" % kind)(*rows, **tail, **kw)
+        if "beam_size" in extra:   # beam search decodes at temperature 0: no seed, no sample ids
+            kw = {k: v for k, v in kw.items() if k not in ("temperature", "seed", "sample_ids", "beam_size")}
+            res = getattr(o.ctx, "transcribe_%s_beam_aligned" % kind)(*rows, extra["beam_size"], **tail, **kw)
+            res.selected.hypothesis = res.best
+        else:
+            kw = {k: v for k, v in kw.items() if k != "best_of"}
+            res = getattr(o.ctx, "transcribe_%s_best_of_aligned" % kind)(*rows, extra["best_of"], **tail, **kw)
+            res.selected.candidate = res.best
+        r = res.selected
+        r.start_frames = res.start_frames
         return r
 
     def align(self, rows, texts, sot_seqs):
@@ -1331,6 +1359,11 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        chose from.  The word times therefore differ slightly from 6.'s; the tokens do not.  no_timestamps is not needed;
        teacher_panel has nothing to act on.  Together with best_of or beam_size it is a ValueError before any library call.
        word_timestamps True / False make exactly the calls they made before the mode existed.
+    19. word_timestamps="decode_best": 18. for a run with best_of and / or beam_size ("decode" exactly when neither is set).  A
+       fallback step that decodes by beam search goes through Context.transcribe_mel_beam_aligned, one that samples best_of
+       candidates through transcribe_mel_best_of_aligned (with reuse_encoder the transcribe_windows_* pair), any other through
+       18.'s entry; the tokens are those of the plain entries bit for bit, and the start frames are those of the hypothesis
+       the step's ranking chose -- the one the window keeps.  For every other value of word_timestamps the calls are unchanged.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1946,9 +1979,10 @@ class Context:
                                   sot_tail, length_penalty)
 
     def _best_of_call(self, fn, rows, tail, prompts, max_new, best_of, eot, temperature, seed, no_speech_token, sot_index,
-                      sample_ids, budgets, prompt_len, sot_tail, length_penalty):
+                      sample_ids, budgets, prompt_len, sot_tail, length_penalty, aligned=None):
         """wm_transcribe_mel_best_of / wm_transcribe_windows, which differ in the arguments that name the rows -- rows() gives
-        (them, B): _mel_rows, _window_rows -- and in the tail (mem)."""
+        (them, B): _mel_rows, _window_rows -- and in the tail (mem).  aligned = (medfilt_width, qk_scale, capture_matrix): fn is
+        the aligned counterpart, and the result carries start_frames (and matrix)."""
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         if budgets is not None:
             self.set_token_budgets(budgets)
@@ -1961,11 +1995,26 @@ class Context:
         lp = np.empty(shape, dtype=np.float32)
         ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
         best = np.empty(B, dtype=np.int32)
+        align_in, align_out, start, matrix = self._hyp_aligned_args(aligned, B, max_new)
         _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
                             1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), N,
                             float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts),
-                            _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(best), *tail))
-        return BestOfResult(toks, lens, lp, ns, best, eot)
+                            *align_in, _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(best), *align_out, *tail))
+        r = BestOfResult(toks, lens, lp, ns, best, eot)
+        if aligned is not None:
+            r.start_frames, r.matrix = start, matrix
+        return r
+
+    def _hyp_aligned_args(self, aligned, B, max_new):
+        """What an aligned best-of / beam entry takes beyond its plain counterpart: ((medfilt_width, qk_scale) behind opts,
+        (start_frame_out,) behind best_out, start_frames i32 [B][max_new + 1], the captured matrix or None); all empty / None for
+        the plain entry."""
+        if aligned is None:
+            return (), (), None, None
+        medfilt_width, qk_scale, capture_matrix = aligned
+        start = np.empty((B, max_new + 1), dtype=np.int32)
+        matrix = self._capture_matrix(B, max_new) if capture_matrix else None
+        return (int(medfilt_width), float(qk_scale)), (_ptr(start),), start, matrix
 
     def transcribe_mel_beam(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, beam_size, eot=-1, patience=None,
                             no_speech_token=-1, sot_index=0, mem=WM_MEM_HOST, budgets=None, prompt_len=None, sot_tail=None,
@@ -1979,8 +2028,8 @@ class Context:
                                sot_tail, length_penalty, max_candidates)
 
     def _beam_call(self, fn, rows, tail, prompts, max_new, beam_size, eot, patience, no_speech_token, sot_index, budgets,
-                   prompt_len, sot_tail, length_penalty, max_candidates):
-        """wm_transcribe_mel_beam / wm_transcribe_windows_beam (rows, tail: as in _best_of_call)"""
+                   prompt_len, sot_tail, length_penalty, max_candidates, aligned=None):
+        """wm_transcribe_mel_beam / wm_transcribe_windows_beam (rows, tail, aligned: as in _best_of_call)"""
         if max_candidates is None:
             max_candidates = beam_max_candidates(beam_size, patience)
         elif patience is not None:
@@ -1999,11 +2048,16 @@ class Context:
         lp = np.empty(shape, dtype=np.float32)
         ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
         best = np.empty(B, dtype=np.int32)
+        align_in, align_out, start, matrix = self._hyp_aligned_args(aligned, B, max_new)
         _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
                             1 if sot_tail is None else int(sot_tail), N, C,
                             float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts),
-                            _ptr(toks), _ptr(lens), _ptr(n_hyp), _ptr(sums), _ptr(lp), _ptr_or_null(ns), _ptr(best), *tail))
-        return BeamResult(toks, lens, n_hyp, sums, lp, ns, best, eot)
+                            *align_in, _ptr(toks), _ptr(lens), _ptr(n_hyp), _ptr(sums), _ptr(lp), _ptr_or_null(ns), _ptr(best),
+                            *align_out, *tail))
+        r = BeamResult(toks, lens, n_hyp, sums, lp, ns, best, eot)
+        if aligned is not None:
+            r.start_frames, r.matrix = start, matrix
+        return r
 
     def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                        no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
@@ -2132,6 +2186,48 @@ class Context:
         return self._aligned_call(self.lib.wm_transcribe_windows_aligned, lambda: self._window_rows(windows, rows), (), prompts,
                                   max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
                                   sot_tail, medfilt_width, qk_scale, capture_matrix)
+
+    def transcribe_mel_best_of_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1,
+                                       temperature=0.0, seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST,
+                                       budgets=None, prompt_len=None, sot_tail=None, length_penalty=None, medfilt_width=7,
+                                       qk_scale=1.0, capture_matrix=False):
+        """wm_transcribe_mel_best_of_aligned: transcribe_mel_best_of whose decode also aligns, per row, the candidate best[b]
+        from its own cross-attention queries.  Every field of the BestOfResult is transcribe_mel_best_of's bit for bit; it also
+        carries start_frames i32 [B][max_new + 1] of candidate best[b] (as AlignedResult's; decode_alignment_text takes
+        selected.tokens[b], selected.lens[b], start_frames[b], selected.logprobs[b]) and matrix (capture_matrix=True, debug
+        library; else None)."""
+        return self._best_of_call(self.lib.wm_transcribe_mel_best_of_aligned,
+                                  lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new,
+                                  best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
+                                  sot_tail, length_penalty, aligned=(medfilt_width, qk_scale, capture_matrix))
+
+    def transcribe_windows_best_of_aligned(self, windows, rows, prompts, max_new, best_of=1, eot=-1, temperature=0.0, seed=0,
+                                           no_speech_token=-1, sot_index=0, sample_ids=None, budgets=None, prompt_len=None,
+                                           sot_tail=None, length_penalty=None, medfilt_width=7, qk_scale=1.0,
+                                           capture_matrix=False):
+        """wm_transcribe_windows_best_of_aligned: transcribe_mel_best_of_aligned with rows of a Windows set.  Same bits."""
+        return self._best_of_call(self.lib.wm_transcribe_windows_best_of_aligned, lambda: self._window_rows(windows, rows), (),
+                                  prompts, max_new, best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets,
+                                  prompt_len, sot_tail, length_penalty, aligned=(medfilt_width, qk_scale, capture_matrix))
+
+    def transcribe_mel_beam_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, beam_size, eot=-1, patience=None,
+                                    no_speech_token=-1, sot_index=0, mem=WM_MEM_HOST, budgets=None, prompt_len=None, sot_tail=None,
+                                    length_penalty=None, max_candidates=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False):
+        """wm_transcribe_mel_beam_aligned: transcribe_mel_beam whose decode also aligns, per row, the hypothesis best[b] from the
+        search's own cross-attention queries.  Every field of the BeamResult is transcribe_mel_beam's bit for bit; it also
+        carries start_frames i32 [B][max_new + 1] of hypothesis best[b] and matrix (as transcribe_mel_best_of_aligned)."""
+        return self._beam_call(self.lib.wm_transcribe_mel_beam_aligned,
+                               lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new,
+                               beam_size, eot, patience, no_speech_token, sot_index, budgets, prompt_len, sot_tail, length_penalty,
+                               max_candidates, aligned=(medfilt_width, qk_scale, capture_matrix))
+
+    def transcribe_windows_beam_aligned(self, windows, rows, prompts, max_new, beam_size, eot=-1, patience=None, no_speech_token=-1,
+                                        sot_index=0, budgets=None, prompt_len=None, sot_tail=None, length_penalty=None,
+                                        max_candidates=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False):
+        """wm_transcribe_windows_beam_aligned: transcribe_mel_beam_aligned with rows of a Windows set.  Same bits."""
+        return self._beam_call(self.lib.wm_transcribe_windows_beam_aligned, lambda: self._window_rows(windows, rows), (), prompts,
+                               max_new, beam_size, eot, patience, no_speech_token, sot_index, budgets, prompt_len, sot_tail,
+                               length_penalty, max_candidates, aligned=(medfilt_width, qk_scale, capture_matrix))
 
     def align_windows(self, windows, rows, text_tokens, sot_seqs, no_timestamps, eot, medfilt_width=7, qk_scale=1.0):
         """wm_align_windows: align_mel with rows of a Windows set (each of at least 2 frames); the alignment covers the set's

@@ -6,6 +6,9 @@
 //     An aligned transcribe group (wm_transcribe_mel_aligned) captures inside its OWN decode steps, eager or replayed from the
 //     position graphs: the <false, true> instantiation writes capture row position - base, base = the group's
 //     <|startoftranscript|> position, and nothing in front of it.
+//   * align_gather_kernel: an aligned best-of / beam group (wm_transcribe_mel_beam_aligned) captures every row of a window; the
+//     rows of the ONE hypothesis that is aligned are copied, capture row by capture row from the slot that held them
+//     (wm_beam_ancestry), into a buffer laid out as a plain aligned group's -- 16-byte vector copies, no LDS.
 //   * align_token_prob_kernel: softmax(logits[S + i][0 : eot])[t[i]] per chunk, from the logits row of the position.
 //   * align_stats_kernel (pass 1, one workgroup per (chunk, head)): the scores q.k / 8 * qk_scale over frames [0, M) are
 //     recomputed from the bf16 cross-K cache with the exact-f32 MFMA (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain),
@@ -96,6 +99,24 @@ __global__ __launch_bounds__(64) void align_capture_kernel(const float *__restri
     }
     if (pos >= Tq) return;
     cap[(((size_t)b * Tq + pos) * J + L.slot0 + k) * 64 + threadIdx.x] = dq[(size_t)r * d + L.head[k] * 64 + threadIdx.x];
+}
+
+// The chosen hypothesis' queries of an aligned best-of / beam group (wm_align_gather): grid (tile of AL_GATHER_ROWS capture rows,
+// window).  Capture row t of window c is J * 256 contiguous bytes in row c * N + slot[c][t] of the capture buffer and goes to
+// row c of q_sel: consecutive lanes move consecutive 16-byte units, a wave 1 KiB per instruction.  Rows at or past n_rows[c]
+// are not touched.
+constexpr int AL_GATHER_ROWS = 4;
+__global__ __launch_bounds__(256) void align_gather_kernel(const uint4 *__restrict__ cap, uint4 *__restrict__ q_sel,
+                                                           const int *__restrict__ slot, const int *__restrict__ n_rows, int N, int Tq,
+                                                           int J) {
+    const int c = blockIdx.y, R = min(n_rows[c], Tq);
+    const size_t row_u = (size_t)J * 16;   // 16-byte units of one capture row
+    for (int t = blockIdx.x * AL_GATHER_ROWS; t < (blockIdx.x + 1) * AL_GATHER_ROWS && t < R; ++t) {
+        const int s = min(max(slot[(size_t)c * Tq + t], 0), N - 1);
+        const uint4 *src = cap + (((size_t)c * N + s) * Tq + t) * row_u;
+        uint4 *dst = q_sel + ((size_t)c * Tq + t) * row_u;
+        for (size_t u = threadIdx.x; u < row_u; u += 256) dst[u] = src[u];
+    }
 }
 
 // B: chunks per position of seq.  PANEL: logits row r is position *pos_ptr + r % w of chunk r / w, and the row takes a
@@ -414,6 +435,17 @@ int wm_align_capture_q(wm_ctx *ctx, const float *dq, int d, int B, const WmAlign
     if (base >= 0) align_capture_kernel<false, true><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, base);
     else if (panel > 1) align_capture_kernel<true><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, panel);
     else align_capture_kernel<false><<<dim3(B, L.n), 64, 0, ctx->stream>>>(dq, d, pos_ptr, L, cap, Tq, J, 1);
+    WM_HIP(hipGetLastError());
+    return WM_OK;
+}
+
+int wm_align_gather(wm_ctx *ctx, const float *cap, float *q_sel, const int *slot, const int *n_rows, int C, int N, int Tq, int J) {
+    WM_REQUIRE(cap && q_sel && slot && n_rows && C >= 1 && N >= 1 && C * N <= WM_DEC_MAXB && Tq >= 1 && Tq <= AL_MAXT && J >= 1,
+               WM_ERR_INVALID, "align_gather: bad geometry");
+    WM_REQUIRE(((uintptr_t)cap | (uintptr_t)q_sel) % 16 == 0, WM_ERR_INVALID, "align_gather: buffers not 16-byte aligned");
+    WmProfScope ps(&ctx->prof, "align_gather", ctx->stream);
+    align_gather_kernel<<<dim3((Tq + AL_GATHER_ROWS - 1) / AL_GATHER_ROWS, C), 256, 0, ctx->stream>>>(
+        (const uint4 *)cap, (uint4 *)q_sel, slot, n_rows, N, Tq, J);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

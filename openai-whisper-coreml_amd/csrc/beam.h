@@ -79,3 +79,36 @@ WM_BEAM_FN int wm_beam_fill_order(int N, const float *sum, int *order_out) {
     }
     return n;
 }
+
+// Where the capture rows of ONE hypothesis of a window lie (an aligned beam group, wm_transcribe_mel_beam_aligned).  The rows
+// of the group keep their capture slots while the search re-parents its beams, and records its ancestry: anc[gi * anc_stride
+// + k] is the beam that slot k continued at close gi (WmBeamStep::src; `anc` points at the window's beam 0), fin_src[f] the
+// beam finished hypothesis f continued.  h indexes the window's hypotheses in their output order: the fin_n finished ones as
+// they finished, then the live beams by descending sum until there are N.  S = sot_tail - 1 capture rows lie in front of the
+// one whose output is generated token 0.  With slot_after[gi] the beam that holds the hypothesis after close gi, capture row
+// S + 1 + gi (the step that is fed token gi) lies in slot_after[gi], and slot_after[gi - 1] = anc[gi][slot_after[gi]]; a
+// live beam k of wsteps tokens starts the walk at slot_after[wsteps - 1] = k, a finished hypothesis of len tokens (its eot
+// counted) at slot_after[len - 2] = fin_src; rows 0 .. S -- the prompt, where all beams are equal -- take the slot the walk
+// ends in.  Rows behind the hypothesis' own take the slot the walk starts in (no alignment reads them).  Fills slot [Tq] and
+// returns the hypothesis' length, or -1 when the window has no hypothesis h.  Pure.
+WM_BEAM_FN int wm_beam_ancestry(int N, const int *anc, int anc_stride, int fin_n, const int *fin_src, const int *fin_len, int wsteps,
+                                const float *sum, int h, int S, int Tq, int *slot) {
+    int k, gi, len;
+    if (h < 0) return -1;
+    if (h < fin_n) {
+        k = fin_src[h]; len = fin_len[h]; gi = len - 2;
+    } else {
+        int order[WM_MAX_BEAM];
+        const int n_live = wm_beam_fill_order(N, sum, order);
+        if (h >= N || h - fin_n >= n_live) return -1;
+        k = order[h - fin_n]; len = wsteps; gi = len - 1;
+    }
+    for (int t = S + 1 + gi; t < Tq; ++t)
+        if (t >= 0) slot[t] = k;
+    for (; gi >= 0; --gi) {
+        if (S + 1 + gi < Tq) slot[S + 1 + gi] = k;
+        k = anc[gi * anc_stride + k];
+    }
+    for (int t = 0; t <= S && t < Tq; ++t) slot[t] = k;
+    return len;
+}

@@ -2,7 +2,8 @@
 // launches behind the decode step's DE_LOGITS_X product (which leaves the f32 logits and the filtered per-tile partials):
 //   * beam_topk_kernel   : per row, the log-sum-exp of the admissible ids and its N + 1 best tokens;
 //   * beam_select_kernel : per window, the selection rule of beam.h, the finished records, the rows' new state, the
-//                          embedding of the next position, the live list and the position advance;
+//                          embedding of the next position, the live list and the position advance; in an aligned group
+//                          (WmBeamDev::anc) also the ancestry record wm_beam_ancestry walks;
 //   * beam_reorder_kernel: the self-attention K/V cache and the rows' histories gathered by source beam, in place.
 // A beam of width 1 must reproduce the greedy decode BIT FOR BIT (tokens, log-probs), so a row's close here is the
 // arithmetic of dec_kernels.hip's argmax_embed_body in its summation orders (16 fixed tile segments, one wave per row for
@@ -145,6 +146,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(int B, int *__restric
                 seq[(pos + 1) * B + row0 + lane] = par.pad;
                 xd.logprob[(long)gi * B + row0 + lane] = 0.f;
                 bm.src[row0 + lane] = lane;
+                if (bm.anc) bm.anc[gi * B + row0 + lane] = lane;
                 done_s[row0 + lane] = 1;
                 st.tok[lane] = par.pad;
             }
@@ -181,6 +183,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(int B, int *__restric
                     bm.fin_lp[base + gi] = st.fin_lp[f];
                     bm.fin_len[w * WM_MAX_BEAM_HYPS + slot] = gi + 1;
                     bm.fin_sum[w * WM_MAX_BEAM_HYPS + slot] = st.fin_sum[f];
+                    if (bm.fin_src) bm.fin_src[w * WM_MAX_BEAM_HYPS + slot] = st.fin_src[f];
                 }
             }
             const int nfin = nfin0 + st.n_fin;
@@ -191,6 +194,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(int B, int *__restric
                 xd.logprob[(long)gi * B + row] = st.lp[lane];
                 bm.sum[row] = st.sum[lane];
                 bm.src[row] = st.src[lane];
+                if (bm.anc) bm.anc[gi * B + row] = st.src[lane];
                 if (ts.rng) {   // the timestamp-rule state follows the source beam
                     __align__(16) int hs[4];
                     *(int4 *)hs = *(const int4 *)hist_s[wave][st.src[lane]];

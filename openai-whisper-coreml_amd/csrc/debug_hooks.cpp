@@ -822,6 +822,59 @@ extern "C" int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out) {
     return WM_OK;
 }
 
+// ---- the aligned best-of / beam calls (wm_transcribe_mel_beam_aligned) ----
+extern "C" int wmdbg_align_hyp(wm_ctx *ctx, int h) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(ctx->model && h >= 0, WM_ERR_INVALID, "bad args");
+    ctx->model->align_dbg_hyp = h;
+    return WM_OK;
+}
+
+extern "C" int wmdbg_hyp_slots(wm_ctx *ctx, int32_t *slots_out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(ctx->model && slots_out, WM_ERR_INVALID, "bad args");
+    ctx->model->align_dbg_slots = slots_out;
+    return WM_OK;
+}
+
+extern "C" int wmdbg_beam_ancestry(int N, int max_new, const int32_t *anc, int fin_n, const int32_t *fin_src, const int32_t *fin_len,
+                                   int wsteps, const float *sum, int h, int S, int Tq, int32_t *slot) {
+    if (N < 1 || N > WM_MAX_BEAM || max_new < 1 || !anc || !fin_src || !fin_len || !sum || !slot || fin_n < 0 ||
+        fin_n > WM_MAX_BEAM_HYPS || wsteps < 0 || wsteps > max_new || S < 0 || Tq < 1)
+        return -2;
+    for (int i = 0; i < max_new * N; ++i)
+        if (anc[i] < 0 || anc[i] >= N) return -2;
+    for (int f = 0; f < fin_n; ++f)
+        if (fin_src[f] < 0 || fin_src[f] >= N || fin_len[f] < 1 || fin_len[f] > max_new) return -2;
+    return wm_beam_ancestry(N, anc, N, fin_n, fin_src, fin_len, wsteps, sum, h, S, Tq, slot);
+}
+
+extern "C" int wmdbg_align_gather(wm_ctx *ctx, const float *cap, int C, int N, int Tq, int J, const int32_t *slot,
+                                  const int32_t *n_rows, float *q_sel) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(cap && slot && n_rows && q_sel && C >= 1 && N >= 1 && N <= WM_MAX_BEAM && C * N <= WM_DEC_MAXB && Tq >= 1 && Tq <= 448 &&
+                   J >= 1, WM_ERR_INVALID, "align_gather: bad args");
+    for (int c = 0; c < C; ++c) {
+        WM_REQUIRE(n_rows[c] >= 0 && n_rows[c] <= Tq, WM_ERR_INVALID, "align_gather: n_rows[%d] = %d outside [0, %d]", c, n_rows[c], Tq);
+        for (int t = 0; t < Tq; ++t)
+            WM_REQUIRE(slot[c * Tq + t] >= 0 && slot[c * Tq + t] < N, WM_ERR_INVALID, "align_gather: slot[%d][%d] = %d", c, t, slot[c * Tq + t]);
+    }
+    const size_t sel_bytes = (size_t)C * Tq * J * 64 * 4;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    const float *dcap;
+    const int *dslot, *drows;
+    float *dsel;
+    WM_TRY(pool.get(&dcap, cap, sel_bytes * N, s));
+    WM_TRY(pool.get(&dslot, slot, (size_t)C * Tq * 4, s));
+    WM_TRY(pool.get(&drows, n_rows, (size_t)C * 4, s));
+    WM_TRY(pool.get(&dsel, q_sel, sel_bytes, s));   // the caller's fill stays where nothing is written
+    WM_TRY(wm_align_gather(ctx, dcap, dsel, dslot, drows, C, N, Tq, J));
+    WM_HIP(hipMemcpyAsync(q_sel, dsel, sel_bytes, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
 // tail: decoder rows behind the last cost-matrix row (WmAlignDev::tail, and n_min with it).  1: wm_align's row rule -- chunk b
 // has S + n_text[b] + 2 decoder rows, n_text 0 is an untouched chunk; 0: an aligned transcribe group's -- S + n_text[b] + 1
 // decoder rows, n_text -1 is the untouched chunk and 0 a one-row matrix.  Either way the matrix has n_text[b] + 1 rows.

@@ -139,9 +139,10 @@ WmXDev wm_model_x_dev(const WmModel *m, const WmDecodeMode &mode) {
 
 // ------------------------------------------------------------------ beam search state ----
 namespace {
-// beam_ws: [WmBeamPar | per-row and per-window state | fin_tok | fin_lp], sized for WM_DEC_MAXB rows and as many windows
+// beam_ws: [WmBeamPar | per-row and per-window state | fin_tok | fin_lp | fin_src | anc], sized for WM_DEC_MAXB rows and as many
+// windows (the ancestry record behind everything a plain beam group touches or fetches)
 struct BeamLayout {
-    size_t par, budget, sum, src, list_n, list_tok, list_lp, wdone, wsteps, fin_n, fin_len, fin_sum, fin_tok, fin_lp, end;
+    size_t par, budget, sum, src, list_n, list_tok, list_lp, wdone, wsteps, fin_n, fin_len, fin_sum, fin_tok, fin_lp, fin_src, anc, end;
     explicit BeamLayout(int n_ctx) {
         size_t o = 0;
         auto take = [&](size_t words) { const size_t at = o; o += (words * 4 + 255) & ~(size_t)255; return at; };
@@ -150,6 +151,7 @@ struct BeamLayout {
         list_tok = take(R * (WM_MAX_BEAM + 1)); list_lp = take(R * (WM_MAX_BEAM + 1));
         wdone = take(R); wsteps = take(R); fin_n = take(R); fin_len = take(R * WM_MAX_BEAM_HYPS); fin_sum = take(R * WM_MAX_BEAM_HYPS);
         fin_tok = take(R * WM_MAX_BEAM_HYPS * n_ctx); fin_lp = take(R * WM_MAX_BEAM_HYPS * n_ctx);
+        fin_src = take(R * WM_MAX_BEAM_HYPS); anc = take(R * n_ctx);
         end = o;
     }
 };
@@ -174,6 +176,7 @@ int wm_model_beam_dev(wm_ctx *ctx, const WmDecodeMode &mode, WmBeamDev *out) {
     d.fin_len = (int *)(p + L.fin_len); d.fin_sum = (float *)(p + L.fin_sum);
     d.fin_tok = (int *)(p + L.fin_tok); d.fin_lp = (float *)(p + L.fin_lp);
     d.trace = m->beam_trace_on ? (float *)m->beam_trace.p : nullptr;   // (the debug library asked for this call's trace)
+    if (mode.acap) { d.fin_src = (int *)(p + L.fin_src); d.anc = (int *)(p + L.anc); }   // an aligned group records its ancestry
     *out = d;
     return WM_OK;
 }

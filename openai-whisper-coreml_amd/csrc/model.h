@@ -207,6 +207,9 @@ struct WmBeamDev {
     int *fin_tok;        // [windows][WM_MAX_BEAM_HYPS][n_ctx]
     float *fin_lp;       // [windows][WM_MAX_BEAM_HYPS][n_ctx]
     float *trace;        // debug library only (else null): [max_new][rows][WM_BEAM_TRACE], the lists and sums BEFORE each step
+    // an aligned beam group only (else null): the search's ancestry, which wm_beam_ancestry walks (beam.h)
+    int *anc;            // [max_new][rows] the source beam of every row at every close
+    int *fin_src;        // [windows][WM_MAX_BEAM_HYPS] the source beam of each finished hypothesis
 };
 
 // Word-level timestamps (wm_align, align.hip).  The alignment heads of one decoder layer: n heads (ascending) whose
@@ -442,6 +445,10 @@ struct WmModel {
     WmDevBuf align_ws;
     WmDevBuf acap_ws;   // an aligned transcribe group's capture buffer and alignment workspace (reserved at prefill, grow-only)
     float *align_dbg_matrix = nullptr;
+    // debug library, one-shot each: the hypothesis the next aligned best-of / beam call aligns instead of best_out (-1: none),
+    // and where that call leaves its slot tables [B][Tq]
+    int align_dbg_hyp = -1;
+    int32_t *align_dbg_slots = nullptr;
     int teacher_panel = 1;   // wm_set_teacher_panel: positions per step of the teacher-forced passes (a launch policy: same bits)
     // wm_transcribe_mel_beam: the group's beam state (WmBeamDev; allocated once at its largest size, so captured graphs keep
     // their addresses) and the debug library's one-shot trace capture (host destination, null in the product) with its
@@ -765,6 +772,20 @@ inline int wm_align_group_rows(size_t T, size_t J, size_t n_ld) {
     const size_t g = WM_ALIGN_CAPTURE_BUDGET / wm_align_chunk_bytes(T, J, n_ld);
     return (int)(g < 1 ? 1 : (g > (size_t)WM_DEC_MAXB ? (size_t)WM_DEC_MAXB : g));
 }
+// ... of an aligned call with N rows per window (wm_transcribe_mel_best_of_aligned, wm_transcribe_mel_beam_aligned), in WINDOWS:
+// a window captures N rows, and above 1 keeps the chosen hypothesis' gathered queries and its slot table beside them; the
+// statistics, the cost matrix and the DTW are the window's.  N = 1: wm_align_group_rows.
+inline size_t wm_align_window_bytes(size_t T, size_t J, size_t n_ld, size_t N) {
+    return wm_align_chunk_bytes(T, J, n_ld) + (N > 1 ? (N * T * J * 64 + T) * 4 : 0);
+}
+inline int wm_align_group_windows(size_t T, size_t J, size_t n_ld, size_t N) {
+    const size_t g = WM_ALIGN_CAPTURE_BUDGET / wm_align_window_bytes(T, J, n_ld, N), c_max = (size_t)WM_DEC_MAXB / N;
+    return (int)(g < 1 ? 1 : (g > c_max ? c_max : g));
+}
+// q_sel[c][t][j][0 .. 64) = cap[c * N + slot[c * Tq + t]][t][j][.] for t < n_rows[c] (cap [C * N][Tq][J][64], q_sel [C][Tq][J][64],
+// slot and n_rows on the device; a slot outside [0, N) is clamped): the chosen hypothesis' queries in the layout of a plain
+// aligned group of C rows
+int wm_align_gather(wm_ctx *ctx, const float *cap, float *q_sel, const int *slot, const int *n_rows, int C, int N, int Tq, int J);
 // the alignment heads of a context: wm_set_alignment_heads' list, or openai-whisper's default (every head of the last half of
 // the decoder layers), ascending by (layer, head)
 void wm_align_heads(const WmModel *m, std::vector<int32_t> *hl, std::vector<int32_t> *hh);

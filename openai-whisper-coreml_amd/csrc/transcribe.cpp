@@ -1,7 +1,9 @@
 // transcribe.cpp -- the transcribe calls of the C ABI (include/whisper_mi355x.h): wm_transcribe_greedy, wm_transcribe,
 // wm_transcribe_mel, wm_transcribe_mel_ragged, wm_transcribe_mel_best_of, wm_transcribe_windows, wm_transcribe_mel_beam,
-// wm_transcribe_windows_beam, and the aligned pair wm_transcribe_mel_aligned / wm_transcribe_windows_aligned (the decode also
-// captures the alignment heads' queries, a group ends with the alignment kernels and the DTW: lane_align).  Each entry point
+// wm_transcribe_windows_beam, and the aligned entries wm_transcribe_mel_aligned / wm_transcribe_windows_aligned and their
+// best-of and beam counterparts wm_transcribe_{mel,windows}_{best_of,beam}_aligned (the decode also captures the alignment
+// heads' queries, a group ends with the alignment kernels and the DTW: lane_align; a group of candidates or beams aligns the
+// ONE hypothesis of each window that its ranking chose).  Each entry point
 // fills one request value (TxCall) and hands it to tx_transcribe: budgets, the entry's own checks, validation (tx_validate),
 // the lane plan (tx_plan.h), the lanes (tx_lanes), the scheduler (tx_run: lane_start / lane_advance / lane_fetch /
 // lane_finish), the ranking step of a best-of or beam call.  DESIGN.md section 4d.
@@ -48,24 +50,27 @@ int burst_len() {
     return n;
 }
 
-// an aligned group's slice of WmModel::acap_ws: the capture buffer q [Bg][Tq][J][64], the row and column statistics, the cost
-// matrix x [Bg][n_ld][1500], the DTW trace and start frames, and the ints n_text | n_frames | DTW rows | DTW frames [Bg] each,
-// then the heads' layers | heads [J] each
+// an aligned group's slice of WmModel::acap_ws, Cg windows of N rows: the capture buffer q [Cg * N][Tq][J][64]; per WINDOW the
+// row and column statistics, the cost matrix x [Cg][n_ld][1500], the DTW trace and start frames; the ints n_text | n_frames |
+// DTW rows | DTW frames [Cg] each, then the heads' layers | heads [J] each.  N > 1 (candidates, beams) adds the aligned
+// hypotheses' gathered queries sel [Cg][Tq][J][64] and, behind the other ints, the gather's rows [Cg] | slot tables [Cg][Tq].
 struct AcapWs {
-    size_t q = 0, row = 0, col = 0, x = 0, tr = 0, start = 0, ints = 0, bytes = 0;
-    int Tq = 0, J = 0, n_ld = 0;
+    size_t q = 0, sel = 0, row = 0, col = 0, x = 0, tr = 0, start = 0, ints = 0, bytes = 0;
+    int Tq = 0, J = 0, n_ld = 0, n_ints = 0;
 };
-AcapWs acap_layout(int Bg, int Tq, int J, int n_ld) {
+AcapWs acap_layout(int Cg, int N, int Tq, int J, int n_ld) {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     AcapWs w;
     w.Tq = Tq; w.J = J; w.n_ld = n_ld;
-    w.row = w.q + up((size_t)Bg * Tq * J * 64 * 4);
-    w.col = w.row + up((size_t)Bg * J * Tq * 8);
-    w.x = w.col + up((size_t)Bg * J * 1500 * 8);
-    w.tr = w.x + up((size_t)Bg * n_ld * 1500 * 4);
-    w.start = w.tr + up((size_t)Bg * wm_dtw_trace_words(n_ld) * 4);
-    w.ints = w.start + up((size_t)Bg * n_ld * 4);
-    w.bytes = w.ints + up(((size_t)4 * Bg + 2 * J) * 4);
+    w.sel = w.q + up((size_t)Cg * N * Tq * J * 64 * 4);
+    w.row = w.sel + (N > 1 ? up((size_t)Cg * Tq * J * 64 * 4) : 0);
+    w.col = w.row + up((size_t)Cg * J * Tq * 8);
+    w.x = w.col + up((size_t)Cg * J * 1500 * 8);
+    w.tr = w.x + up((size_t)Cg * n_ld * 1500 * 4);
+    w.start = w.tr + up((size_t)Cg * wm_dtw_trace_words(n_ld) * 4);
+    w.ints = w.start + up((size_t)Cg * n_ld * 4);
+    w.n_ints = 4 * Cg + 2 * J + (N > 1 ? Cg + Cg * Tq : 0);
+    w.bytes = w.ints + up((size_t)w.n_ints * 4);
     return w;
 }
 
@@ -97,11 +102,13 @@ struct LaneJob {
     std::vector<int32_t> bbud, bfin_tok;
     std::vector<char> bstate;
     std::vector<float> bfin_lp, btrace;
+    std::vector<int32_t> banc, bfin_src;   // an aligned beam group: the ancestry record [max_new][Bg], [Cg][WM_MAX_BEAM_HYPS]
     // an aligned group: its workspace, the layers' alignment heads (kernel arguments of its steps), the host side of the ints
-    // (source of async uploads), the rows that have a matrix, the fetched start frames [Bg][n_ld], the tail's two events
+    // (source of async uploads), the windows that have a matrix, the aligned rows' lengths, the fetched start frames [Cg][n_ld],
+    // the tail's two events
     AcapWs aw;
     std::vector<WmAlignLayer> alayers;
-    std::vector<int32_t> aints, astart;
+    std::vector<int32_t> aints, astart, alen;
     std::vector<char> aok;
     WmEvents<2> tail_ev;
     float stage_sum[3] = {0.f, 0.f, 0.f};
@@ -131,11 +138,16 @@ struct TxCall {
     float *sums = nullptr;      // beam: [B][S]
     float *trace = nullptr;     // beam, debug library: [B][max_new][n_cand][WM_BEAM_TRACE] (null in the product)
     // wm_transcribe_mel_aligned / wm_transcribe_windows_aligned: word-timestamp alignment from the decode's own queries
-    bool aligned = false;
+    // hyp (the best-of and beam counterparts): a window decodes n_cand rows and aligns hypothesis best_out[b] alone
+    bool aligned = false, hyp = false;
     int medfilt = 0;
     float qk_scale = 1.f;
     int32_t *start_out = nullptr;   // [B][max_new + 1]
     float *dbg_matrix = nullptr;    // debug library: [B][max_new + 1][1500] (null in the product)
+    int dbg_hyp = -1;               // debug library: align hypothesis min(dbg_hyp, n_hyp - 1) instead (-1 in the product)
+    int32_t *dbg_slots = nullptr;   // debug library: the slot tables [B][Tq] (null in the product)
+    // hypotheses per window of the outputs: tokens_out [B][S][max_new]
+    int out_stride() const { return beam ? std::max(n_cand, max_cand) : n_cand; }
     wm_mem mem = WM_MEM_HOST;
 };
 
@@ -189,20 +201,20 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
     if (call.aligned) {   // the capture buffer and the alignment workspace, reserved before anything is enqueued
         const int J = (int)cfg.hl.size();
-        j.aw = acap_layout(Bg, cfg.sot_tail + call.max_new - 1, J, call.max_new + 1);
+        j.aw = acap_layout(Cg, N, cfg.sot_tail + call.max_new - 1, J, call.max_new + 1);
         WM_TRY(m->acap_ws.reserve(c->stream, j.aw.bytes));
         j.alayers.assign(m->dims.n_text_layer, WmAlignLayer());
-        j.aints.assign((size_t)4 * Bg + 2 * J, 0);
+        j.aints.assign((size_t)j.aw.n_ints, 0);
         for (int k = 0; k < J; ++k) {
             WmAlignLayer &Ly = j.alayers[cfg.hl[k]];
             if (Ly.n == 0) Ly.slot0 = k;
             Ly.head[Ly.n++] = cfg.hh[k];
-            j.aints[4 * Bg + k] = cfg.hl[k];
-            j.aints[4 * Bg + J + k] = cfg.hh[k];
+            j.aints[4 * Cg + k] = cfg.hl[k];
+            j.aints[4 * Cg + J + k] = cfg.hh[k];
         }
         j.mode.acap = true; j.mode.acap_base = j.P - cfg.sot_tail; j.mode.acap_Tq = j.aw.Tq; j.mode.acap_J = J;
         j.mode.acap_q = (float *)((char *)m->acap_ws.p + j.aw.q);
-        if (call.dbg_matrix) WM_HIP(hipMemsetAsync((char *)m->acap_ws.p + j.aw.x, 0, (size_t)Bg * j.aw.n_ld * 1500 * 4, c->stream));
+        if (call.dbg_matrix) WM_HIP(hipMemsetAsync((char *)m->acap_ws.p + j.aw.x, 0, (size_t)Cg * j.aw.n_ld * 1500 * 4, c->stream));
     }
     const void *d_pcm;
     WM_TRY(wm_stage_pcm(c, call.src, j.b0, Cg, call.mem, &d_pcm));
@@ -330,6 +342,12 @@ int beam_fetch(LaneJob &j, int max_new, bool trace) {
     if (trace) {
         j.btrace.resize((size_t)max_new * j.Bg * WM_BEAM_TRACE);
         WM_HIP(hipMemcpyAsync(j.btrace.data(), m->beam_trace.p, j.btrace.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+    }
+    if (bm.anc) {   // an aligned group: the ancestry record lane_align walks
+        j.banc.resize((size_t)max_new * j.Bg);
+        j.bfin_src.resize((size_t)j.Cg * WM_MAX_BEAM_HYPS);
+        WM_HIP(hipMemcpyAsync(j.banc.data(), bm.anc, j.banc.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+        WM_HIP(hipMemcpyAsync(j.bfin_src.data(), bm.fin_src, j.bfin_src.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
     }
     return WM_OK;
 }
@@ -552,11 +570,14 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
         WM_REQUIRE(call.medfilt >= 1 && call.medfilt <= 31 && call.medfilt % 2 == 1, WM_ERR_INVALID,
                    "medfilt_width %d must be odd, 1 .. 31", call.medfilt);
         WM_REQUIRE(std::isfinite(call.qk_scale), WM_ERR_INVALID, "qk_scale must be finite");
-        WM_REQUIRE(call.n_cand == 1 && !call.beam, WM_ERR_INVALID, "an aligned call decodes one sample per row");
+        WM_REQUIRE(call.hyp || (call.n_cand == 1 && !call.beam), WM_ERR_INVALID, "an aligned call decodes one sample per row");
+        WM_REQUIRE(!call.hyp || call.best_out, WM_ERR_INVALID, "null best_out: an aligned best-of / beam call aligns the hypothesis it names");
         cfg->sot_tail = p.len ? p.sot_tail : n_prompt - sot_index;
         wm_align_heads(m, &cfg->hl, &cfg->hh);
-        const int rows = wm_align_group_rows((size_t)cfg->sot_tail + max_new - 1, cfg->hl.size(), (size_t)max_new + 1);
-        cfg->max_group_rows = rows < WM_DEC_MAXB ? rows : 0;
+        // the capture budget's bound, in rows (the plan divides by the rows of a window); none when a full group fits
+        const int N = call.n_cand;
+        const int windows = wm_align_group_windows((size_t)cfg->sot_tail + max_new - 1, cfg->hl.size(), (size_t)max_new + 1, (size_t)N);
+        cfg->max_group_rows = windows < WM_DEC_MAXB / N ? windows * N : 0;
     }
     return WM_OK;
 }
@@ -685,28 +706,83 @@ int lane_fetch(TxRun &r, LaneJob &j) {
     return WM_OK;
 }
 
-// The tail of an aligned group, enqueued once its rows' lengths are known: matrix row k of row b is the decoder position whose
+// ---------------------------------------------------------------- the ranking step ----
+// The hypothesis of window b a best-of or beam call names in best_out: a best-of call's is wm_rank_candidates' over the
+// candidates' log-probs, a beam call's the MaximumLikelihoodRanker's over the search's own sums.  Per window, so that an aligned
+// group ranks its windows as soon as their outputs are written (lane_finish) and every other call at its end (tx_rank).
+int tx_rank_window(const TxCall &call, int b) {
+    const int max_new = call.max_new, S = call.out_stride();
+    const size_t r0 = (size_t)b * S;
+    if (!call.beam)
+        return wm_rank_candidates(call.tokens_out + r0 * max_new, call.lens_out + r0, call.logprobs_out + r0 * max_new, 1, S, max_new,
+                                  call.eot, call.length_penalty, call.best_out + b, nullptr);
+    int best = 0;
+    double best_score = -INFINITY;
+    for (int h = 0; h < call.n_hyp[b]; ++h) {
+        const size_t r = r0 + h;
+        int n_text = 0;
+        while (n_text < call.lens_out[r] && call.tokens_out[r * max_new + n_text] != call.eot) ++n_text;
+        const double score = wm_rank_score((double)call.sums[r], n_text, call.length_penalty);
+        if (score > best_score) { best_score = score; best = h; }   // the first maximal score; all -inf: hypothesis 0
+    }
+    call.best_out[b] = best;
+    return WM_OK;
+}
+
+// The tail of an aligned group, enqueued once its rows' lengths are known: matrix row k of a window is the decoder position whose
 // output was generated token k, i.e. capture row S + k with S = sot_tail - 1 rows in front (the prompt from
-// <|startoftranscript|> on, less the one whose output is token 0); a row's decoder rows are S + len, none behind the last matrix
-// row (WmAlignDev::tail 0).  Against the lane's own cross-K/V, on the lane's stream.
+// <|startoftranscript|> on, less the one whose output is token 0); a window's decoder rows are S + len, none behind the last
+// matrix row (WmAlignDev::tail 0).  Against the lane's own cross-K/V, on the lane's stream.
+// A group of candidates or beams (N rows per window) aligns hypothesis best_out of each window: its capture rows are gathered
+// from the slots that held them -- a candidate's own slot; a beam hypothesis' by wm_beam_ancestry over the fetched search
+// state -- into the layout of a plain group of Cg rows, which the same two launches then read.
 int lane_align(TxRun &r, LaneJob &j) {
     const TxCall &call = r.call;
     wm_ctx *c = j.c;
     WmModel *m = c->model;
-    const int Bg = j.Bg, S = r.cfg.sot_tail - 1, n_ld = j.aw.n_ld, J = j.aw.J;
+    const int Cg = j.Cg, N = call.n_cand, S = r.cfg.sot_tail - 1, n_ld = j.aw.n_ld, J = j.aw.J, Tq = j.aw.Tq;
     char *ws = (char *)m->acap_ws.p;
     int nmax = -1, mmax = 0, rows_max = 0;
-    j.aok.assign(Bg, 0);
-    for (int b = 0; b < Bg; ++b) {
-        const int row = j.b0 + b, len = call.lens_out[row];
-        const int nf = call.src.windows ? call.src.set->n_frames[call.src.rows ? call.src.rows[row] : row] : call.src.n_frames[row];
+    j.aok.assign(Cg, 0);
+    j.alen.assign(Cg, 0);
+    int32_t *grows = N > 1 ? j.aints.data() + 4 * Cg + 2 * J : nullptr, *slots = N > 1 ? grows + Cg : nullptr;
+    // a beam group's fetched state (beam_drain)
+    WmBeamDev bm;
+    memset(&bm, 0, sizeof(bm));
+    if (call.beam && N > 1) WM_TRY(wm_model_beam_dev(c, j.mode, &bm));
+    const char *dev0 = (const char *)m->beam_ws.p;
+    auto host = [&](const void *dev) { return j.bstate.data() + ((const char *)dev - dev0); };
+    for (int w = 0; w < Cg; ++w) {
+        const int W = j.b0 + w;   // window of the call
+        int h = 0;
+        if (call.hyp) {
+            h = call.best_out[W];
+            if (call.dbg_hyp >= 0) h = std::min(call.dbg_hyp, (call.beam ? call.n_hyp[W] : N) - 1);
+        }
+        const int len = call.lens_out[(size_t)W * call.out_stride() + h];
+        const int nf = call.src.windows ? call.src.set->n_frames[call.src.rows ? call.src.rows[W] : W] : call.src.n_frames[W];
         const bool ok = len >= 1 && nf >= 2 && S + len >= 2;
-        j.aok[b] = ok;
-        j.aints[b] = ok ? len - 1 : -1;
-        j.aints[Bg + b] = nf;
-        j.aints[2 * Bg + b] = ok ? len : 0;
-        j.aints[3 * Bg + b] = nf / 2;
+        j.aok[w] = ok;
+        j.alen[w] = len;
+        j.aints[w] = ok ? len - 1 : -1;
+        j.aints[Cg + w] = nf;
+        j.aints[2 * Cg + w] = ok ? len : 0;
+        j.aints[3 * Cg + w] = nf / 2;
         if (ok) { nmax = std::max(nmax, len - 1); mmax = std::max(mmax, nf / 2); rows_max = std::max(rows_max, len); }
+        if (N > 1) {
+            grows[w] = ok ? S + len : 0;
+            int32_t *sl = slots + (size_t)w * Tq;
+            std::fill(sl, sl + Tq, call.beam ? 0 : h);   // a candidate keeps its slot
+            if (call.beam && h >= 0) {
+                const int got = wm_beam_ancestry(N, j.banc.data() + (size_t)w * N, j.Bg, ((const int *)host(bm.fin_n))[w],
+                                                 j.bfin_src.data() + (size_t)w * WM_MAX_BEAM_HYPS,
+                                                 (const int *)host(bm.fin_len) + (size_t)w * WM_MAX_BEAM_HYPS,
+                                                 ((const int *)host(bm.wsteps))[w], (const float *)host(bm.sum) + (size_t)w * N, h, S, Tq, sl);
+                WM_REQUIRE(got == len || (got < 0 && len == 0), WM_ERR_STATE, "aligned beam group: window %d, hypothesis %d has %d tokens, its ancestry %d", W, h, len, got);
+            }
+        }
+        if (call.dbg_slots)
+            for (int t = 0; t < Tq; ++t) call.dbg_slots[(size_t)W * Tq + t] = N > 1 ? slots[(size_t)w * Tq + t] : 0;
     }
     WM_HIP(hipEventRecord(j.tail_ev[0], c->stream));
     if (nmax >= 0) {
@@ -714,19 +790,25 @@ int lane_align(TxRun &r, LaneJob &j) {
         float *x = (float *)(ws + j.aw.x);
         WM_HIP(hipMemcpyAsync(ints, j.aints.data(), j.aints.size() * 4, hipMemcpyHostToDevice, c->stream));
         WmAlignDev a;
-        a.q = j.mode.acap_q; a.xkv = m->xkv; a.hl = ints + 4 * Bg; a.hh = ints + 4 * Bg + J; a.n_text = ints; a.n_frames = ints + Bg;
+        a.q = j.mode.acap_q;
+        if (N > 1) {
+            float *sel = (float *)(ws + j.aw.sel);
+            WM_TRY(wm_align_gather(c, j.mode.acap_q, sel, ints + 5 * Cg + 2 * J, ints + 4 * Cg + 2 * J, Cg, N, Tq, J));
+            a.q = sel;
+        }
+        a.xkv = m->xkv; a.hl = ints + 4 * Cg; a.hh = ints + 4 * Cg + J; a.n_text = ints; a.n_frames = ints + Cg;
         a.rowst = (float *)(ws + j.aw.row); a.colst = (float *)(ws + j.aw.col); a.x = x;
-        a.B = Bg; a.H = m->dims.n_text_head; a.Tq = j.aw.Tq; a.J = J; a.S = S; a.n_ld = n_ld;
+        a.B = Cg; a.H = m->dims.n_text_head; a.Tq = Tq; a.J = J; a.S = S; a.n_ld = n_ld;
         a.sc = 0.125f * call.qk_scale * 1.44269504088896340736f;
         a.half = call.medfilt / 2;
         a.tail = 0; a.n_min = 0;
         WM_TRY(wm_align_matrix(c, a, nmax, mmax));
         int *start = (int *)(ws + j.aw.start);
-        WM_TRY(wm_dtw(c, x, (long)n_ld * 1500, 1500, ints + 2 * Bg, ints + 3 * Bg, Bg, rows_max, mmax, (unsigned *)(ws + j.aw.tr), start, n_ld));
-        j.astart.resize((size_t)Bg * n_ld);
+        WM_TRY(wm_dtw(c, x, (long)n_ld * 1500, 1500, ints + 2 * Cg, ints + 3 * Cg, Cg, rows_max, mmax, (unsigned *)(ws + j.aw.tr), start, n_ld));
+        j.astart.resize((size_t)Cg * n_ld);
         WM_HIP(hipMemcpyAsync(j.astart.data(), start, j.astart.size() * 4, hipMemcpyDeviceToHost, c->stream));
         if (call.dbg_matrix)
-            WM_HIP(hipMemcpyAsync(call.dbg_matrix + (size_t)j.b0 * n_ld * 1500, x, (size_t)Bg * n_ld * 1500 * 4, hipMemcpyDeviceToHost, c->stream));
+            WM_HIP(hipMemcpyAsync(call.dbg_matrix + (size_t)j.b0 * n_ld * 1500, x, (size_t)Cg * n_ld * 1500 * 4, hipMemcpyDeviceToHost, c->stream));
     }
     WM_HIP(hipEventRecord(j.tail_ev[1], c->stream));
     j.state = LaneJob::ALIGNING;
@@ -751,16 +833,20 @@ int lane_finish(TxRun &r, LaneJob &j, bool *done) {
                           call.tokens_out, call.lens_out, r.cfg.xc.logprobs, r.cfg.xc.no_speech);
     }
     wm_add_stage_ms(j.ev.e, 3, call.src.windows, j.stage_sum);
-    if (call.aligned) return lane_align(r, j);   // the rows' lengths are known now: the alignment tail, then ALIGNING
+    if (call.aligned) {   // the rows' lengths are known now: (candidates, beams) the windows' ranking, the alignment tail, then ALIGNING
+        if (call.hyp)
+            for (int w = 0; w < j.Cg; ++w) WM_TRY(tx_rank_window(call, j.b0 + w));
+        return lane_align(r, j);
+    }
     j.state = LaneJob::IDLE;
     ++r.groups_done;
     *done = true;
     return WM_OK;
 }
 
-// An aligned group whose tail has drained writes its rows of start_frame_out: row k < len starts at the first frame of matrix
-// row k on the DTW path, entry len is M, -1 behind; a row without a matrix is all -1, or (0, M) when its one decoder row
-// has nothing to be z-scored against.
+// An aligned group whose tail has drained writes its windows' rows of start_frame_out (of the hypothesis lane_align chose): row
+// k < len starts at the first frame of matrix row k on the DTW path, entry len is M, -1 behind; a row without a matrix is all
+// -1, or (0, M) when its one decoder row has nothing to be z-scored against.
 int lane_align_finish(TxRun &r, LaneJob &j, bool *done) {
     const TxCall &call = r.call;
     *done = false;
@@ -768,10 +854,10 @@ int lane_align_finish(TxRun &r, LaneJob &j, bool *done) {
     if (q == hipErrorNotReady) { (void)hipGetLastError(); return WM_OK; }
     WM_HIP(q);
     WM_HIP(hipStreamSynchronize(j.c->stream));
-    const int n_ld = j.aw.n_ld, Bg = j.Bg;
-    for (int b = 0; b < Bg; ++b) {
+    const int n_ld = j.aw.n_ld, Cg = j.Cg;
+    for (int b = 0; b < Cg; ++b) {
         int32_t *out = call.start_out + (size_t)(j.b0 + b) * n_ld;
-        const int len = call.lens_out[j.b0 + b], nf = j.aints[Bg + b], M = nf / 2;
+        const int len = j.alen[b], nf = j.aints[Cg + b], M = nf / 2;
         for (int k = 0; k < n_ld; ++k) out[k] = -1;
         if (j.aok[b]) {
             for (int k = 0; k < len; ++k) out[k] = j.astart[(size_t)b * n_ld + k];
@@ -834,28 +920,10 @@ int tx_run(wm_ctx *ctx, const TxCall &call, const TxCfg &cfg, const WmTxPlan &pl
     return WM_OK;
 }
 
-// ---------------------------------------------------------------- the ranking step ----
-// a best-of call: wm_rank_candidates over the candidates' log-probs; a beam call: the MaximumLikelihoodRanker over the
-// search's own sums
+// the ranking step of a best-of or beam call (an aligned one has ranked its windows group by group: lane_finish)
 int tx_rank(const TxCall &call) {
-    if (!call.best_out) return WM_OK;
-    const int B = call.B, max_new = call.max_new;
-    if (!call.beam)
-        return wm_rank_candidates(call.tokens_out, call.lens_out, call.logprobs_out, B, call.n_cand, max_new, call.eot,
-                                  call.length_penalty, call.best_out, nullptr);
-    const int S = std::max(call.n_cand, call.max_cand);
-    for (int b = 0; b < B; ++b) {
-        int best = 0;
-        double best_score = -INFINITY;
-        for (int h = 0; h < call.n_hyp[b]; ++h) {
-            const size_t r = (size_t)b * S + h;
-            int n_text = 0;
-            while (n_text < call.lens_out[r] && call.tokens_out[r * max_new + n_text] != call.eot) ++n_text;
-            const double score = wm_rank_score((double)call.sums[r], n_text, call.length_penalty);
-            if (score > best_score) { best_score = score; best = h; }   // the first maximal score; all -inf: hypothesis 0
-        }
-        call.best_out[b] = best;
-    }
+    if (!call.best_out || (call.aligned && call.hyp)) return WM_OK;
+    for (int b = 0; b < call.B; ++b) WM_TRY(tx_rank_window(call, b));
     return WM_OK;
 }
 
@@ -942,12 +1010,15 @@ void beam(wm_ctx *ctx, TxCall &call, const int32_t *prompts, int prompt_stride, 
     }
 }
 
-// the aligned calls: the three new arguments, and the debug library's one-shot cost-matrix capture (for this call only)
-void aligned(wm_ctx *ctx, TxCall &call, int medfilt_width, float qk_scale, int32_t *start_frame_out) {
+// the aligned calls: their three arguments, and the debug library's one-shot cost-matrix capture (for this call only)
+// hyp: a best-of / beam counterpart, which aligns the hypothesis best_out names
+void aligned(wm_ctx *ctx, TxCall &call, int medfilt_width, float qk_scale, int32_t *start_frame_out, bool hyp = false) {
     call.aligned = true; call.medfilt = medfilt_width; call.qk_scale = qk_scale; call.start_out = start_frame_out;
+    call.hyp = hyp;
     if (ctx && ctx->model) {
-        call.dbg_matrix = ctx->model->align_dbg_matrix;
-        ctx->model->align_dbg_matrix = nullptr;
+        WmModel *m = ctx->model;
+        call.dbg_matrix = m->align_dbg_matrix; call.dbg_hyp = m->align_dbg_hyp; call.dbg_slots = m->align_dbg_slots;
+        m->align_dbg_matrix = nullptr; m->align_dbg_hyp = -1; m->align_dbg_slots = nullptr;
     }
 }
 }  // namespace
@@ -1086,5 +1157,71 @@ extern "C" int wm_transcribe_windows_aligned(wm_ctx *ctx, const wm_windows *w, c
     best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, 1, NAN, nullptr);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
     aligned(ctx, call, medfilt_width, qk_scale, start_frame_out);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+// The best-of and beam calls whose decode keeps the alignment heads' queries of every candidate / beam: the same outputs, plus
+// the start frames of the ONE hypothesis best_out names (lane_align)
+extern "C" int wm_transcribe_mel_best_of_aligned(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                                 const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                                 int prompt_stride, const int32_t *prompt_len, int sot_tail,
+                                                 const uint32_t *sample_ids, int best_of_n, float length_penalty, int max_new,
+                                                 int32_t eot, const wm_decode_opts *opts, int medfilt_width, float qk_scale,
+                                                 int32_t *tokens_out, int32_t *lens_out, float *token_logprobs_out,
+                                                 float *no_speech_prob_out, int32_t *best_out, int32_t *start_frame_out,
+                                                 wm_mem mem) try {
+    TxCall call;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of_n, length_penalty, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_windows_best_of_aligned(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B,
+                                                     const int32_t *prompts, int prompt_stride, const int32_t *prompt_len,
+                                                     int sot_tail, const uint32_t *sample_ids, int best_of_n, float length_penalty,
+                                                     int max_new, int32_t eot, const wm_decode_opts *opts, int medfilt_width,
+                                                     float qk_scale, int32_t *tokens_out, int32_t *lens_out,
+                                                     float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out,
+                                                     int32_t *start_frame_out) try {
+    TxCall call;
+    set_src(call, w, rows);
+    best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of_n, length_penalty, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_mel_beam_aligned(wm_ctx *ctx, const float *mel, const int64_t *mel_base, const int32_t *mel_len,
+                                              const int32_t *seek, const int32_t *n_frames, int B, const int32_t *prompts,
+                                              int prompt_stride, const int32_t *prompt_len, int sot_tail, int beam_size,
+                                              int max_candidates, float length_penalty, int max_new, int32_t eot,
+                                              const wm_decode_opts *opts, int medfilt_width, float qk_scale, int32_t *tokens_out,
+                                              int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
+                                              float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out,
+                                              int32_t *start_frame_out, wm_mem mem) try {
+    TxCall call;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+         sum_logprobs_out, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
+    return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+extern "C" int wm_transcribe_windows_beam_aligned(wm_ctx *ctx, const wm_windows *w, const int32_t *rows, int B,
+                                                  const int32_t *prompts, int prompt_stride, const int32_t *prompt_len, int sot_tail,
+                                                  int beam_size, int max_candidates, float length_penalty, int max_new, int32_t eot,
+                                                  const wm_decode_opts *opts, int medfilt_width, float qk_scale, int32_t *tokens_out,
+                                                  int32_t *lens_out, int32_t *n_hyp_out, float *sum_logprobs_out,
+                                                  float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out,
+                                                  int32_t *start_frame_out) try {
+    TxCall call;
+    set_src(call, w, rows);
+    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+         sum_logprobs_out, best_out);
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
