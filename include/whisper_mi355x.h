@@ -568,6 +568,42 @@ WM_API int wm_set_alignment_heads(wm_ctx *ctx, const int32_t *layers, const int3
 #define WM_MAX_TEACHER_PANEL 8   /* = WM_MAX_BEST_OF: the widths the shared cross-attention read is built for */
 WM_API int wm_set_teacher_panel(wm_ctx *ctx, int width);
 
+/* SPECULATIVE DECODING: wm_transcribe_mel on `ctx` (the target) whose tokens a small DRAFT model proposes.  Per round the draft
+ * proposes up to draft_len tokens with plain greedy steps, the target checks all of them in ONE panel step (up to draft_len + 1
+ * consecutive positions of every window: the weights streamed once, a window's cross-attention K/V read once) and keeps the
+ * longest prefix it would have produced itself, plus its own next token.
+ * THE CONTRACT: tokens_out, lens_out, token_logprobs_out and no_speech_prob_out are bit for bit those of wm_transcribe_mel on
+ * `ctx` with the same arguments -- for every draft, every draft_len and every grouping, with wm_set_suppress lists (the
+ * first-token list included), wm_set_timestamp_rules, wm_set_token_budgets, early stop on eot and eot < 0.  A panel row has
+ * the one-position step's bits; the draft decides how many rounds a call takes, never what it returns.
+ *   draft     : a finalised model context on the same device, with its own weights (a wm_clone of ctx, or a second context with
+ *               the same weights, is legal and has every proposal accepted).  Its n_mels, n_vocab, n_text_ctx and n_audio_ctx
+ *               must equal the target's.  It runs its own encoder over the same windows.  Its OWN suppress lists and timestamp
+ *               rules shape what it proposes -- they affect acceptance, never the result: set them as on the target.  Nothing
+ *               else may use the draft context during the call.
+ *   draft_len : 1 .. WM_MAX_DRAFT_LEN proposals per round.
+ *   stats_out : nullable, [B]: what the draft was worth, per window (wm_spec_stats).
+ * The windows of a call are decoded in groups of windows that advance in LOCKSTEP: a round advances a group by the smallest
+ * number of tokens any of its live windows could keep, so a group's acceptance is that of its worst window, round by round.
+ * The groups run one after the other on ctx's stream; wm_set_lanes is not consulted.
+ * NOT OFFERED (each rejected with its own message): a non-zero temperature (WM_ERR_INVALID); repetition rules or a sequence
+ * bias set on ctx (WM_ERR_STATE); the all-f32 debug path (WM_ERR_STATE).  There are no ragged-prompt, best-of, beam-search,
+ * aligned or window-set forms of this call.  Every other argument and error: wm_transcribe_mel (sample ids play no part at
+ * temperature 0). */
+#define WM_MAX_DRAFT_LEN 7          /* draft_len + 1 <= WM_MAX_TEACHER_PANEL */
+typedef struct wm_spec_stats {
+    int32_t rounds;                 /* verify steps the window took part in while live */
+    int32_t proposed;               /* draft tokens verified for it */
+    int32_t accepted;               /* of those, equal to the target's own choice (the leading run) */
+    int32_t kept;                   /* of those, kept after the group's lockstep cut */
+} wm_spec_stats;
+WM_API int wm_transcribe_mel_speculative(wm_ctx *ctx, wm_ctx *draft, const float *mel, const int64_t *mel_base,
+                                         const int32_t *mel_len, const int32_t *seek, const int32_t *n_frames, int B,
+                                         const int32_t *prompts, int n_prompt, int draft_len, int max_new, int32_t eot,
+                                         const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
+                                         float *token_logprobs_out /* nullable */, float *no_speech_prob_out /* nullable */,
+                                         wm_spec_stats *stats_out /* nullable */, wm_mem mem);
+
 /* Decode groups a wm_transcribe_greedy call on this context keeps in flight.
  *   0 (default): the library's own measured policy -- one group below 32 chunks, two groups (two weight-sharing lanes)
  *                up to 143, three from 144 chunks, never more than $WM_LANES (default 3) at once; for the NARROW models

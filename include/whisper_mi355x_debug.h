@@ -313,6 +313,37 @@ WM_API int wmdbg_tx_plan(const int32_t *in, int n, int32_t *out, int32_t *cut, i
 WM_API int wmdbg_tx_plan_bounded(const int32_t *in, const int32_t *max_group_rows, int n, int32_t *out, int32_t *cut, int cut_cap);
 WM_API int wmdbg_group_tables(const int32_t *in, int n, int32_t *out);
 WM_API int wmdbg_group_rows_out(const int32_t *in, int n, int32_t *out);
+/* Speculative decoding (wm_transcribe_mel_speculative): the pure host rules of tx_plan.cpp, restated in tests/spec_ref.py.
+ * wmdbg_spec_groups: the decode groups of B windows at draft length k and preferred group size spec_group (0: the default) into
+ *   b0_out / cg_out [<= B]; returns their number (-1: bad arguments).
+ * wmdbg_spec_width: the width of the next verify step from the draft length, an upper bound on the device position and the
+ *   last position a row may have (0: none).
+ * wmdbg_spec_round: one round of G windows whose verify step had w rows each -- accepted / live / eot_at (index of the first
+ *   end-of-text among a window's own tokens, -1: none) / left (tokens its budget still allows) i32 [G] -> returns n, the
+ *   positions the group advances; live_out i32 [G]; inc_out i32 [G][4] = increments of (rounds, proposed, accepted, kept). */
+WM_API int wmdbg_spec_groups(int B, int k, int spec_group, int32_t *b0_out, int32_t *cg_out);
+WM_API int wmdbg_spec_width(int k, int bound, int last);
+WM_API int wmdbg_spec_round(int G, int w, const int32_t *accepted, const int32_t *live, const int32_t *eot_at, const int32_t *left,
+                            int32_t *live_out, int32_t *inc_out);
+/* wmdbg_spec_round over n cases of one shape: in i32 [n][4][G] = accepted | live | eot_at | left, out i32 [n][1 + 5 G] = n |
+ * live_out [G] | inc [G][4]; returns n (-1: bad arguments). */
+WM_API int wmdbg_spec_round_batch(int n, int G, int w, const int32_t *in, int32_t *out);
+/* Scoped to the NEXT wm_transcribe_mel_speculative call on ctx, which clears it whatever its outcome: the proposal for generated
+ * index i of row b of that call is tokens[b * max_new + i] (B and max_new must be the call's; ids inside the vocabulary).  The
+ * draft model still runs; only what the target is asked to verify changes, so tests and timings fix the acceptance pattern
+ * exactly.  tokens is host memory that lives until that call returns; NULL clears the hook. */
+WM_API int wmdbg_spec_script(wm_ctx *ctx, const int32_t *tokens, int B, int max_new);
+/* The accept and commit launches of one speculative round alone, timestamp rules off: G windows x w rows at position pos (rows
+ * at positions pos .. pos + w - 1 <= n_prompt + max_new - 2).  tilemax u64 [G * w][n_tiles] packed (value, ~index) text keys, txt /
+ * win f32 [G * w][n_tiles][2] the extended decode's partials -- (max, sum exp) of the tile's allowed ids, raw logit of its winner
+ * -- as a verify step's logits launch leaves them; seq i32 [n_ctx][G] (in: the last token at pos, the proposals behind it; out:
+ * the kept tokens), done i32 [G] (in / out), budget i32 [G] or NULL.  Out: logprob f32 [max_new][G] (zero where nothing was
+ * written), stats i32 [G][4], round i32 [2] = (live windows, position), acc i32 [G], the draft's token buffer i32 [n_ctx][G]
+ * (zero but for the token it continues from), pos_out i32 [2] = the target's and the draft's position. */
+WM_API int wmdbg_spec_accept(wm_ctx *ctx, int G, int w, int n_tiles, int pos, int n_prompt, int n_ctx, int max_new, int32_t eot,
+                             const int32_t *budget, const uint64_t *tilemax, const float *txt, const float *win, int32_t *seq,
+                             int32_t *done, float *logprob_out, int32_t *stats_out, int32_t *round_out, int32_t *acc_out,
+                             int32_t *draft_seq_out, int32_t *pos_out);
 /* The cross-attention launch of a candidate group exactly as the decode step makes it (wm_dec_attention_cand): C windows x N
  * candidates, q f32 [C * N][H * 64] (row c * N + s = candidate s of window c), k / v f32 [C][H][T][64] (rounded to bf16), the
  * first n_keys positions; live_rows: the compact ascending list of the n_live live rows (NULL: every row is live);

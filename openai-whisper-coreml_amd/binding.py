@@ -120,6 +120,7 @@ def load_library(path=None):
                                       vp, vp, vp, vp, vp, ip],
         "wm_transcribe_mel_beam": [vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, ip, ip, ctypes.c_float, ip, ctypes.c_int32, vp,
                                    vp, vp, vp, vp, vp, vp, vp, ip],
+        "wm_transcribe_mel_speculative": [vp, vp, vp, vp, vp, vp, vp, ip, vp, ip, ip, ip, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ip],
         "wm_rank_candidates": [vp, vp, vp, ip, ip, ip, ctypes.c_int32, ctypes.c_float, vp, vp],
         "wm_set_token_budgets": [vp, vp, ip],
         "wm_set_alignment_heads": [vp, vp, vp, ip],
@@ -261,6 +262,16 @@ class TranscribeResult:
         self.sum_logprob = np.array([float(np.sum(logprobs[b, :lens[b]], dtype=np.float64)) for b in range(B)])
         self.n_text = np.array([n_text_tokens(tokens[b, :lens[b]], eot) for b in range(B)], dtype=np.int64)
         self.avg_logprob = self.sum_logprob / (self.n_text + 1)
+
+
+class SpeculativeResult(TranscribeResult):
+    """What Context.transcribe_mel_speculative returns: the TranscribeResult of the plain call, bit for bit, plus `stats`, i32
+    [B][4] = (rounds, proposed, accepted, kept) per window (wm_spec_stats)."""
+
+    def __init__(self, tokens, lens, logprobs, no_speech_prob, eot, stats):
+        TranscribeResult.__init__(self, tokens, lens, logprobs, no_speech_prob, eot)
+        self.stats = stats
+        self.rounds, self.proposed, self.accepted, self.kept = (stats[:, i] for i in range(4))
 
 
 class AlignedResult(TranscribeResult):
@@ -727,6 +738,7 @@ class wm_vad_params(ctypes.Structure):
 
 
 VAD_SMOOTH = 5             # frames of the moving average transcribe_long(vad=True) asks wm_vad_energy for
+MAX_DRAFT_LEN = 7          # WM_MAX_DRAFT_LEN: proposals per round of a speculative call (Context.transcribe_mel_speculative)
 MAX_TEACHER_PANEL = 8      # WM_MAX_TEACHER_PANEL: positions per decoder step of a teacher-forced pass (Context.set_teacher_panel)
 PARALLEL_CLIPS_TRUE = 56   # parallel_clips=True: the decode-group size of the bench headline
 
@@ -920,6 +932,20 @@ class _LongOptions(types.SimpleNamespace):
         if self.teacher_panel is not None:
             if isinstance(self.teacher_panel, bool) or int(self.teacher_panel) != self.teacher_panel or not 1 <= self.teacher_panel <= MAX_TEACHER_PANEL:
                 raise ValueError("teacher_panel: None or a width 1 .. %d" % MAX_TEACHER_PANEL)
+        if self.draft is None:
+            if self.draft_len is not None:
+                raise ValueError("draft_len needs draft")
+        else:   # 20.
+            self.draft_len = 4 if self.draft_len is None else self.draft_len
+            if isinstance(self.draft_len, bool) or int(self.draft_len) != self.draft_len or not 1 <= self.draft_len <= MAX_DRAFT_LEN:
+                raise ValueError("draft_len: 1 .. %d" % MAX_DRAFT_LEN)
+            for on, what in ((self.cond, "condition_on_previous_text"), (self.best_of is not None, "best_of"),
+                             (self.beam_size is not None, "beam_size"), (self.words_decode, "word_timestamps='decode*'"),
+                             (bool(self.reuse_encoder), "reuse_encoder"),
+                             (self.repetition_penalty is not None or self.no_repeat_ngram_size is not None, "the repetition rules"),
+                             (bool(self.sequence_bias) or bool(self.bad_words) or bool(self.boost_phrases), "a sequence bias")):
+                if on:
+                    raise ValueError("draft (speculative decoding) cannot be combined with %s" % what)
         self.panel_pending = self.teacher_panel is not None   # set on the context in front of the first alignment call
         if self.prepend_punctuations is None:
             self.prepend_punctuations = PREPEND_PUNCTUATIONS
@@ -1045,6 +1071,9 @@ class _RoundRows:
             r = self._decode_aligned(todo, prompts, kw, extra)
             for k, i in enumerate(todo):
                 self.aligned[i] = (r.start_frames[k], r.logprobs[k], int(r.lens[k]), r.tokens[k])
+        elif o.draft is not None and t == 0 and not o.ragged:   # 20.: the same tokens, proposed by the draft
+            r = o.ctx.transcribe_mel_speculative(o.draft, *self._mel_windows(todo), prompts, o.max_new, o.draft_len, eot=o.eot,
+                                                 no_speech_token=o.no_speech_token, mem=WM_MEM_DEVICE, **o.sot_kw)
         elif self.set is not None:   # the same call without the encoder pass
             r = o.ctx.transcribe_windows(self.set, [int(i) for i in todo], prompts, o.max_new, **kw)
         else:
@@ -1237,7 +1266,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
-                    boost_phrases=None, phrase_boost=None):
+                    boost_phrases=None, phrase_boost=None, draft=None, draft_len=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1364,6 +1393,15 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        candidates through transcribe_mel_best_of_aligned (with reuse_encoder the transcribe_windows_* pair), any other through
        18.'s entry; the tokens are those of the plain entries bit for bit, and the start frames are those of the hypothesis
        the step's ranking chose -- the one the window keeps.  For every other value of word_timestamps the calls are unchanged.
+    20. draft (None; a Context with a small model of the same vocabulary on the same device) / draft_len (1 .. 7, default 4):
+       speculative decoding.  The temperature-0 step of every round whose rows have prompts of one length goes through
+       Context.transcribe_mel_speculative -- the draft proposes draft_len tokens at a time, panels of this context verify
+       them; the tokens, log-probs and no_speech_prob are those of the plain call bit for bit, so the run's result is the
+       same in every field --, every other step and a round of ragged prompts (per-recording initial prompts) through the
+       plain entries.  The timestamp rules this function sets on the context are set on the draft too; the suppress lists
+       of both are the caller's.  ValueError before any library call: with condition_on_previous_text=True, best_of,
+       beam_size, word_timestamps='decode*', reuse_encoder, repetition_penalty / no_repeat_ngram_size, a sequence bias, or
+       draft_len without draft.  With draft None the function makes exactly the calls it made before the argument existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1378,6 +1416,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     o.early(R)
     bias_table = long_bias_table(sequence_bias, bad_words, boost_phrases, phrase_boost)   # 17. (None: off)
     ctx.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
+    if draft is not None:   # 20.: the draft proposes under the same rules
+        draft.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
     out = [dict(language=None, segments=[], seeks=[], windows=[]) for _ in range(R)]
     if R == 0:
         return out
@@ -1732,6 +1772,21 @@ class Context:
         self.lib.wmdbg_set_precision.restype = ctypes.c_int
         _check(self.lib, self.lib.wmdbg_set_precision(self.handle, WM_F32 if f32 else WM_BF16))
 
+    def set_spec_script(self, tokens):
+        """Debug library only: the proposals of the NEXT transcribe_mel_speculative call on this context come from tokens i32
+        [B][max_new] (by generated index) instead of the draft (wmdbg_spec_script); None clears the hook."""
+        if not hasattr(self.lib, "wmdbg_spec_script"):
+            raise WhisperError(-1, "set_spec_script needs the debug library: Context(dims, debug=True)")
+        self.lib.wmdbg_spec_script.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        self.lib.wmdbg_spec_script.restype = ctypes.c_int
+        if tokens is None:
+            self._spec_script = None
+            _check(self.lib, self.lib.wmdbg_spec_script(self.handle, None, 0, 0))
+            return
+        self._spec_script = np.ascontiguousarray(tokens, dtype=np.int32)   # lives until the call
+        B, max_new = self._spec_script.shape
+        _check(self.lib, self.lib.wmdbg_spec_script(self.handle, _ptr(self._spec_script), B, max_new))
+
     def finalize(self):
         _check(self.lib, self.lib.wm_finalize(self.handle))
 
@@ -1966,6 +2021,29 @@ class Context:
         else:
             _check(self.lib, self.lib.wm_transcribe_mel(*rows, *rest))
         return toks, lens, lp, ns
+
+    def transcribe_mel_speculative(self, draft, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, draft_len, eot=-1,
+                                   temperature=0.0, no_speech_token=-1, sot_index=0, mem=WM_MEM_HOST, budgets=None):
+        """wm_transcribe_mel_speculative: transcribe_mel's uniform-prompt call at temperature 0 whose tokens the Context
+        `draft` (same device, same vocabulary; its own suppress lists and timestamp rules set as on this one) proposes
+        draft_len at a time and panels of this context verify.  The TranscribeResult is transcribe_mel's bit for bit; the
+        returned SpeculativeResult adds the per-window statistics."""
+        opts = wm_decode_opts(float(temperature), 0, int(no_speech_token), int(sot_index))
+        head, B = self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem)
+        pr, plen, opts, _ = self._prompt_call_args(B, prompts, opts, None, None, None)
+        if plen is not None:   # (before the budgets are set: a rejected call leaves none behind)
+            raise ValueError("speculative decoding takes prompts of one length")
+        if budgets is not None:
+            self.set_token_budgets(budgets)
+        toks = np.empty((B, max_new), dtype=np.int32)
+        lens = np.empty(B, dtype=np.int32)
+        lp = np.empty((B, max_new), dtype=np.float32)
+        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
+        stats = np.zeros((B, 4), dtype=np.int32)
+        _check(self.lib, self.lib.wm_transcribe_mel_speculative(
+            self.handle, draft.handle if draft is not None else None, *head, B, _ptr(pr), pr.shape[1], int(draft_len), max_new, eot,
+            ctypes.byref(opts), _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(stats), mem))
+        return SpeculativeResult(toks, lens, lp, ns, eot, stats)
 
     def transcribe_mel_best_of(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1, temperature=0.0,
                                seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None,

@@ -257,7 +257,7 @@ extern "C" int wmdbg_set_tuning(const char *key, int value) {
         {"gemm_tile", &g_wm_tuning.gemm_tile}, {"gemm128_pipe", &g_wm_tuning.gemm128_pipe}, {"gemm_gm", &g_wm_tuning.gemm_gm}, {"no_early_stop", &g_wm_tuning.no_early_stop},
         {"xattn_no_deep", &g_wm_tuning.xattn_no_deep}, {"xattn_never_short", &g_wm_tuning.xattn_never_short},         {"logits_tn", &g_wm_tuning.logits_tn}, {"enc_attn_mfma_sum", &g_wm_tuning.enc_attn_mfma_sum},
         {"group_chunks", &g_wm_tuning.group_chunks}, {"argmax_rows_per_wg", &g_wm_tuning.argmax_rows_per_wg}, {"xattn_fuse_q", &g_wm_tuning.xattn_fuse_q},
-        {"teacher_panel_cut", &g_wm_tuning.teacher_panel_cut}, {"lane_parts", &g_wm_tuning.lane_parts}, {"lane_solo_cus", &g_wm_tuning.lane_solo_cus}, {"frontend_per_wave_twiddles", &g_wm_tuning.frontend_per_wave_twiddles},
+        {"teacher_panel_cut", &g_wm_tuning.teacher_panel_cut}, {"lane_parts", &g_wm_tuning.lane_parts}, {"lane_solo_cus", &g_wm_tuning.lane_solo_cus}, {"spec_group", &g_wm_tuning.spec_group}, {"frontend_per_wave_twiddles", &g_wm_tuning.frontend_per_wave_twiddles},
     };
     if (strcmp(key, "reset") == 0) { g_wm_tuning = WmTuning(); return WM_OK; }
     for (auto &e : table)
@@ -313,6 +313,108 @@ extern "C" int wmdbg_group_tables(const int32_t *in, int n, int32_t *out) {
     for (int i = 0; i < n; ++i)
         if (!wm_group_tables_flat(in + (size_t)i * WM_TX_TAB_IN, WM_XIDS_CAND, out + (size_t)i * WM_TX_TAB_OUT)) return -1;
     return n;
+}
+// ---- speculative decoding (tx_plan.h): the group cut, the width rule and a round's arithmetic, case by case
+extern "C" int wmdbg_spec_groups(int B, int k, int spec_group, int32_t *b0_out, int32_t *cg_out) {
+    if (B < 1 || k < 1 || k > WM_MAX_DRAFT_LEN || !b0_out || !cg_out) return -1;
+    std::vector<int> b0, cg;
+    const int G = wm_spec_groups(B, k, spec_group, b0, cg);
+    for (int g = 0; g < G; ++g) { b0_out[g] = b0[g]; cg_out[g] = cg[g]; }
+    return G;
+}
+extern "C" int wmdbg_spec_width(int k, int bound, int last) { return wm_spec_width(k, bound, last); }
+extern "C" int wmdbg_spec_round(int G, int w, const int32_t *accepted, const int32_t *live, const int32_t *eot_at, const int32_t *left,
+                                int32_t *live_out, int32_t *inc_out) {
+    if (G < 1 || w < 1 || !accepted || !live || !eot_at || !left || !live_out || !inc_out) return -1;
+    return wm_spec_round(G, w, accepted, live, eot_at, left, live_out, inc_out);
+}
+// n cases of one shape at once: in i32 [n][4][G] = accepted | live | eot_at | left, out i32 [n][1 + 5 G] = n | live_out [G] | inc [G][4]
+extern "C" int wmdbg_spec_round_batch(int n, int G, int w, const int32_t *in, int32_t *out) {
+    if (n < 0 || G < 1 || w < 1 || !in || !out) return -1;
+    for (int i = 0; i < n; ++i) {
+        const int32_t *c = in + (size_t)i * 4 * G;
+        int32_t *o = out + (size_t)i * (1 + 5 * G);
+        o[0] = wm_spec_round(G, w, c, c + G, c + 2 * G, c + 3 * G, o + 1, o + 1 + G);
+    }
+    return n;
+}
+// Scoped to the NEXT wm_transcribe_mel_speculative call on ctx (which clears it, whatever its outcome): the proposal for
+// generated index i of row b of that call is tokens[b * max_new + i].  `tokens` is host memory that lives until the call returns.
+extern "C" int wmdbg_spec_script(wm_ctx *ctx, const int32_t *tokens, int B, int max_new) {
+    WM_REQUIRE(ctx && ctx->model, WM_ERR_STATE, "wmdbg_spec_script: context has no model");
+    WmModel *m = ctx->model;
+    m->spec_dbg_script = nullptr; m->spec_dbg_script_new = m->spec_dbg_script_rows = 0;
+    if (!tokens) return WM_OK;
+    WM_REQUIRE(B >= 1 && max_new >= 1, WM_ERR_INVALID, "wmdbg_spec_script: B < 1 or max_new < 1");
+    for (size_t i = 0; i < (size_t)B * max_new; ++i)
+        WM_REQUIRE(tokens[i] >= 0 && tokens[i] < m->dims.n_vocab, WM_ERR_INVALID, "wmdbg_spec_script: token %d outside the vocabulary", tokens[i]);
+    m->spec_dbg_script = tokens; m->spec_dbg_script_new = max_new; m->spec_dbg_script_rows = B;
+    return WM_OK;
+}
+// The accept + commit launches of a speculative round alone (spec.hip), timestamp rules off: a group of G windows x w rows at
+// position pos, staged from the per-tile partials a verify step's logits launch would have left.
+extern "C" int wmdbg_spec_accept(wm_ctx *ctx, int G, int w, int n_tiles, int pos, int n_prompt, int n_ctx, int max_new, int32_t eot,
+                                 const int32_t *budget, const uint64_t *tilemax, const float *txt, const float *win, int32_t *seq,
+                                 int32_t *done, float *logprob_out, int32_t *stats_out, int32_t *round_out, int32_t *acc_out,
+                                 int32_t *draft_seq_out, int32_t *pos_out) {
+    WM_REQUIRE(ctx && tilemax && txt && win && seq && done && logprob_out && stats_out && round_out && acc_out && draft_seq_out && pos_out,
+               WM_ERR_INVALID, "wmdbg_spec_accept: null pointer");
+    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB && n_tiles >= 1 && n_prompt >= 1 && max_new >= 1 &&
+                   pos >= n_prompt && pos + w < n_ctx && pos + w <= n_prompt + max_new - 1 && n_ctx <= 4096,
+               WM_ERR_INVALID, "wmdbg_spec_accept: bad geometry");
+    for (int i = 0; i < G * w; ++i)
+        for (int t = 0; t < n_tiles; ++t) {
+            const uint64_t k = tilemax[(size_t)i * n_tiles + t];
+            WM_REQUIRE(k == 0 || (int)((0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)) >> 4) < n_tiles, WM_ERR_INVALID,
+                       "wmdbg_spec_accept: a key names an id outside the tiles");
+        }
+    hipStream_t s = ctx->stream;
+    const size_t rows = (size_t)G * w, nt = rows * n_tiles, ns = (size_t)n_ctx * G;
+    std::vector<int32_t> zeros((size_t)WM_DEC_MAXB * 4, 0);
+    DevPool pool;
+    unsigned long long *d_tm;
+    float *d_txt, *d_win, *d_lp, *d_wlp;
+    int *d_seq, *d_dseq, *d_done, *d_bud = nullptr, *d_pos, *d_wtok, *d_acc, *d_stats, *d_round, *d_nlive;
+    WmXPar *d_par;
+    WM_TRY(pool.get(&d_tm, tilemax, nt * 8, s));
+    WM_TRY(pool.get(&d_txt, txt, nt * 8, s));
+    WM_TRY(pool.get(&d_win, win, nt * 8, s));
+    WM_TRY(pool.get(&d_lp, nullptr, (size_t)max_new * G * 4, s));
+    WM_TRY(pool.get(&d_wlp, nullptr, rows * 4, s));
+    WM_TRY(pool.get(&d_seq, seq, ns * 4, s));
+    WM_TRY(pool.get(&d_dseq, nullptr, ns * 4, s));
+    WM_TRY(pool.get(&d_done, done, (size_t)G * 4, s));
+    if (budget) WM_TRY(pool.get(&d_bud, budget, (size_t)G * 4, s));
+    const int pos2[2] = {pos, pos + w};   // (the draft has taken its w steps)
+    WM_TRY(pool.get(&d_pos, pos2, 8, s));
+    WM_TRY(pool.get(&d_wtok, nullptr, rows * 4, s));
+    WM_TRY(pool.get(&d_acc, nullptr, (size_t)G * 4, s));
+    WM_TRY(pool.get(&d_stats, zeros.data(), (size_t)G * 16, s));
+    WM_TRY(pool.get(&d_round, nullptr, 8, s));
+    WM_TRY(pool.get(&d_nlive, nullptr, 4, s));
+    WM_TRY(pool.get(&d_par, nullptr, sizeof(WmXPar), s));
+    WmSpecDev sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.tseq = d_seq; sp.dseq = d_dseq; sp.tpos = d_pos; sp.dpos = d_pos + 1;
+    sp.wtok = d_wtok; sp.wlp = d_wlp; sp.acc = d_acc; sp.stats = d_stats; sp.round = d_round;
+    sp.max_new = max_new; sp.n_vocab = n_tiles * 16;
+    WmXDev xd;
+    memset(&xd, 0, sizeof(xd));
+    xd.par = d_par; xd.txt = d_txt; xd.win = d_win; xd.logprob = d_lp;
+    WmStopDev st;
+    memset(&st, 0, sizeof(st));
+    st.done = d_done; st.budget = d_bud; st.n_live = d_nlive; st.eot = eot; st.pad_tok = eot >= 0 ? eot : 0;
+    WM_TRY(wm_spec_accept(ctx, d_tm, n_tiles, sp, xd, st, G, w, n_prompt, n_ctx, 0));
+    WM_HIP(hipMemcpyAsync(seq, d_seq, ns * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(draft_seq_out, d_dseq, ns * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(done, d_done, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(logprob_out, d_lp, (size_t)max_new * G * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(stats_out, d_stats, (size_t)G * 16, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(round_out, d_round, 8, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(acc_out, d_acc, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(pos_out, d_pos, 8, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 extern "C" int wmdbg_group_rows_out(const int32_t *in, int n, int32_t *out) {
     if (!in || !out || n < 0) return -1;

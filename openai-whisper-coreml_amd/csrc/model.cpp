@@ -510,6 +510,8 @@ void wm_model_destroy(wm_ctx *ctx) {
     if (!m) return;
     wm_model_drop_graphs(m);
     if (m->h_nlive) (void)hipHostFree(m->h_nlive);
+    if (m->h_spec) (void)hipHostFree(m->h_spec);
+    m->spec_ws.release();
     for (void *p : m->allocs) (void)hipFree(p);
     for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->acap_ws, &m->beam_ws, &m->beam_trace}) b->release();
     delete m;
@@ -840,7 +842,8 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
     const int d = D.n_text_state, H = D.n_text_head, T = D.n_text_ctx, S = 1500;
     const int PW = mode.panel > 1 ? mode.panel : 1;     // panel step: B = Bx windows x PW positions, one self AND one cross cache entry per window
     const int NC = mode.n_cand > 1 ? mode.n_cand : 1;   // candidate group: B = Bx windows x NC rows, one cross cache per window
-    WM_REQUIRE(PW == 1 || (NC == 1 && !mode.stop && !mode.off && !mode.x && B % PW == 0), WM_ERR_STATE,
+    // (mode.x without the repetition rules: the verify step of a speculative group, wm_model_spec_panel_step)
+    WM_REQUIRE(PW == 1 || (NC == 1 && !mode.stop && !mode.off && !(mode.x && mode.rep) && B % PW == 0), WM_ERR_STATE,
                "decode step: a panel is a plain teacher-forced step of windows x width rows");
     const int Bx = B / (NC * PW);
     const int Gx = grp > 0 ? grp : Bx;                  // windows per layer of the cross cache
@@ -1025,6 +1028,34 @@ int wm_model_panel_advance(wm_ctx *ctx, int G, int c0, int C, int w, int w_next)
         WM_TRY(wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, w, C, w_next, m->tok_emb, m->dec_pos, m->dims.n_text_state,
                                   m->dims.n_text_ctx, m->dx, m->dxb, m->dstats, m->dmean));
     return wm_dec_pos_add(ctx, m->dpos, w);
+}
+
+// ------------------------------------------------------------------ speculative decoding
+int wm_model_spec_panel_step(wm_ctx *ctx, int G, int w, const WmDecodeMode &mode, int n_prompt) {
+    WM_TRY(panel_check(ctx, G, 0, G, w));
+    WM_REQUIRE(mode.x && !mode.off && !mode.rep && mode.n_cand <= 1 && !mode.beam && !mode.acap, WM_ERR_STATE,
+               "speculative verify step: a plain extended-decode group");
+    WmDecodeMode pm = mode;   // the rows of frozen windows are computed and ignored: no live list
+    pm.panel = w; pm.stop = false; pm.budget = false; pm.stop_eot = -1;
+    return decode_step_impl(ctx, G * w, false, 0, ctx->model->dims.n_vocab - 1, nullptr, pm, n_prompt, G, 0);
+}
+
+int wm_model_spec_dev(wm_ctx *ctx, wm_ctx *draft, int max_new, WmSpecDev *out, int **script_area) {
+    WmModel *m = ctx->model, *dm = draft->model;
+    constexpr size_t R = WM_DEC_MAXB;
+    WM_TRY(m->spec_ws.reserve(ctx->stream, (R * 24 + R * (size_t)m->dims.n_text_ctx) * 4));
+    if (!m->h_spec) WM_HIP(hipHostMalloc((void **)&m->h_spec, WM_NLIVE_RING * 2 * sizeof(int), hipHostMallocDefault));
+    int *p = (int *)m->spec_ws.p;
+    WmSpecDev sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.tseq = m->dseq; sp.dseq = dm->dseq; sp.tpos = m->dpos; sp.dpos = dm->dpos;
+    sp.tts = wm_model_ts_dev(m); sp.dts = wm_model_ts_dev(dm);
+    sp.chist = p; sp.crng = p + R * 4; sp.dchist = p + R * 8; sp.dcrng = p + R * 12;
+    sp.wtok = p + R * 16; sp.wlp = (float *)(p + R * 17); sp.acc = p + R * 18; sp.stats = p + R * 19; sp.round = p + R * 23;
+    sp.max_new = max_new; sp.n_vocab = m->dims.n_vocab;
+    *script_area = p + R * 24;
+    *out = sp;
+    return WM_OK;
 }
 
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode) {

@@ -457,6 +457,12 @@ struct WmModel {
     float *beam_dbg_trace = nullptr;
     WmDevBuf beam_trace;
     bool beam_trace_on = false;   // the group decoding on this context right now writes its trace
+    // wm_transcribe_mel_speculative: the group's state (WmSpecDev), the pinned ring the host reads a round's (live windows,
+    // position) from, and the debug library's scoped proposal script (host, [B][max_new]; null in the product)
+    WmDevBuf spec_ws;
+    int *h_spec = nullptr;
+    const int32_t *spec_dbg_script = nullptr;
+    int spec_dbg_script_new = 0, spec_dbg_script_rows = 0;
     WmDevBuf pcm_stage;   // host-pointer staging of a decode group's PCM (wm_transcribe*, wm_align)
     WmDevBuf io_stage;    // staging for host-pointer model calls
 };
@@ -519,6 +525,33 @@ WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode);
 int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t);
 int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int32_t eot, int32_t max_initial);
 int wm_model_set_suppress(wm_ctx *ctx, const int32_t *ids, int n, const int32_t *first_ids, int n_first);
+// Speculative decoding (wm_transcribe_mel_speculative, spec.hip): the device view of one decode group of G
+// windows on the target context and its draft.  The target's WmTsDev rng slots are per ROW of the verify step (G x w); the
+// windows' committed timestamp-rule state lives here, beside the draft's.
+struct WmSpecDev {
+    int *tseq, *dseq;        // the two token buffers [n_text_ctx][G]
+    int *tpos, *dpos;        // the two device positions
+    WmTsDev tts, dts;        // the two models' timestamp rules (rng == null: off)
+    int *chist, *crng;       // [G][4] the target's committed history and ranges
+    int *dchist, *dcrng;     // [G][4] the draft's
+    int *wtok;               // [G x w] the rows' winners
+    float *wlp;              // [G x w] and their log-probs
+    int *acc;                // [G] leading rows whose winner equals the proposal
+    int *stats;              // [G][4] wm_spec_stats
+    int *round;              // [2] live windows, position after the round (what the host reads behind an event)
+    const int *script;       // debug library (wmdbg_spec_script; null in the product): [G][max_new] proposals by generated index
+    int max_new, n_vocab;
+};
+// the verify step: wm_model_decode_step's layer body over G windows x w consecutive positions with the group's own mode (the
+// masks, the extended-decode partials, the timestamp rules of the plain step), closed by wm_spec_accept instead of the arg-max
+int wm_model_spec_panel_step(wm_ctx *ctx, int G, int w, const WmDecodeMode &mode, int n_prompt);
+// the group's state on the target context (allocated on first use) for `draft`
+// *script_area: device room for a debug script of the group, [WM_DEC_MAXB][n_text_ctx] ints (WmSpecDev::script stays null)
+int wm_model_spec_dev(wm_ctx *ctx, wm_ctx *draft, int max_new, WmSpecDev *out, int **script_area);
+int wm_spec_adopt(wm_ctx *draft, const WmSpecDev &sp, int G, int n_prompt);
+int wm_spec_stage(wm_ctx *ctx, const WmSpecDev &sp, int G, int w, int n_prompt, int n_ctx);
+int wm_spec_accept(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, const WmSpecDev &sp, const WmXDev &xd,
+                   const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx, int fallback_tok);
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode = WmDecodeMode());
 // arg-max reduce + write next token (positions >= n_prompt) + embed next position + advance *dpos
 int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first,

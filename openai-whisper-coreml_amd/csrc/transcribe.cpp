@@ -1021,6 +1021,179 @@ void aligned(wm_ctx *ctx, TxCall &call, int medfilt_width, float qk_scale, int32
         m->align_dbg_matrix = nullptr; m->align_dbg_hyp = -1; m->align_dbg_slots = nullptr;
     }
 }
+
+// ---------------------------------------------------------------- speculative decoding ----
+// wm_transcribe_mel_speculative.  A decode group of G windows lives on TWO contexts: the target (the
+// caller's, whose plain call this one reproduces bit for bit) and the draft.  Both prefill and step through the prompt exactly
+// as a plain group does and take the first generated token with a plain step; then rounds of [draft: w plain steps | target:
+// proposals staged, ONE verify step of G x w rows, accept + commit] until the device reports no live window.  The two streams
+// are ordered by events; the host reads a round's (live windows, position) through pinned memory, at most two rounds behind.
+struct SpecCall {
+    wm_ctx *draft = nullptr;
+    int k = 0;                        // draft_len
+    wm_spec_stats *stats = nullptr;   // [B] of the call, nullable
+};
+
+int spec_checks(wm_ctx *ctx, const SpecCall &sc, const TxCall &call) {
+    WM_REQUIRE(sc.draft && sc.draft != ctx, WM_ERR_INVALID, "speculative decoding needs a draft context of its own (a wm_clone will do)");
+    WM_REQUIRE(sc.k >= 1 && sc.k <= WM_MAX_DRAFT_LEN, WM_ERR_INVALID, "draft_len %d outside [1, %d]", sc.k, WM_MAX_DRAFT_LEN);
+    const float T = call.opts ? call.opts->temperature : 0.f;
+    WM_REQUIRE(T == 0.f, WM_ERR_INVALID, "speculative decoding verifies the greedy choice: temperature must be 0 (got %g)", (double)T);
+    WmModel *m = ctx->model, *dm = sc.draft->model;
+    WM_REQUIRE(!m->rep_on, WM_ERR_STATE, "speculative decoding does not support the repetition rules set on this context");
+    WM_REQUIRE(!m->sb_on, WM_ERR_STATE, "speculative decoding does not support the sequence bias set on this context");
+    WM_REQUIRE(!ctx->dbg_hooks && !sc.draft->dbg_hooks, WM_ERR_STATE, "speculative decoding is not supported by the all-f32 precision path");
+    WM_REQUIRE(dm && dm->finalized, WM_ERR_STATE, "the draft's model weights are not finalised (wm_finalize)");
+    WM_REQUIRE(sc.draft->device == ctx->device, WM_ERR_INVALID, "the draft context lives on device %d, the target on %d",
+               sc.draft->device, ctx->device);
+    const wm_dims &a = m->dims, &b = dm->dims;
+    WM_REQUIRE(a.n_mels == b.n_mels && a.n_vocab == b.n_vocab && a.n_text_ctx == b.n_text_ctx && a.n_audio_ctx == b.n_audio_ctx,
+               WM_ERR_INVALID, "the draft's n_mels / n_vocab / n_text_ctx / n_audio_ctx (%d / %d / %d / %d) differ from the target's (%d / %d / %d / %d)",
+               b.n_mels, b.n_vocab, b.n_text_ctx, b.n_audio_ctx, a.n_mels, a.n_vocab, a.n_text_ctx, a.n_audio_ctx);
+    WM_REQUIRE(!dm->rep_on && !dm->sb_on, WM_ERR_STATE, "the draft context has repetition rules or a sequence bias set");
+    return WM_OK;
+}
+
+int spec_group(wm_ctx *ctx, const SpecCall &sc, const TxCall &call, const TxCfg &cfg, const TxCfg &dcfg, int b0, int G) {
+    wm_ctx *dc = sc.draft;
+    WmModel *m = ctx->model, *dm = dc->model;
+    const int k = sc.k, n_ctx = m->dims.n_text_ctx, max_new = call.max_new;
+    std::vector<int32_t> script, stats;   // (sources / destinations of asynchronous copies: declared before the jobs' fences)
+    WmEvents<WM_NLIVE_RING> round_ev;
+    WmEvents<2> x_ev;
+    LaneJob tj, dj;
+    tj.c = ctx; tj.fence.s = ctx->stream;
+    dj.c = dc; dj.fence.s = dc->stream;
+    WM_TRY(tj.ev.create());
+    WM_TRY(dj.ev.create());
+    WM_TRY(round_ev.create_untimed());
+    WM_TRY(x_ev.create_untimed());
+    tj.b0 = dj.b0 = b0; tj.Cg = dj.Cg = tj.Bg = dj.Bg = G;
+    WmSpecDev sp;
+    int *script_area = nullptr;
+    WM_TRY(wm_model_spec_dev(ctx, dc, max_new, &sp, &script_area));
+    WM_TRY(lane_prefill(tj, call, cfg));
+    WM_TRY(lane_prefill(dj, call, dcfg));
+    const int P = tj.P;
+    if (m->spec_dbg_script) {   // debug library: the proposals come from the script (the draft still runs)
+        script.assign(m->spec_dbg_script + (size_t)b0 * max_new, m->spec_dbg_script + (size_t)(b0 + G) * max_new);
+        WM_HIP(hipMemcpyAsync(script_area, script.data(), script.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        sp.script = script_area;
+    }
+    // the prompt and the first generated token: plain steps on both models
+    for (int i = 0; i < P; ++i) WM_TRY(lane_position(tj, tj.mode, P, false));
+    for (int i = 0; i < P; ++i) WM_TRY(lane_position(dj, dj.mode, P, false));
+    const WmXDev xd = wm_model_x_dev(m, tj.mode);
+    const WmStopDev stop = wm_model_stop_dev(m, tj.mode);
+    const int fallback = tj.mode.ts ? m->ts_eot : 0;
+    auto draft_embed = [&]() {   // the draft's next step starts from the token the commit left at its position
+        return wm_dec_embed_panel(dc, dm->dseq, G, dm->dpos, 0, G, 1, dm->tok_emb, dm->dec_pos, dm->dims.n_text_state, n_ctx, dm->dx,
+                                  dm->dxb, dm->dstats, dm->dmean);
+    };
+    const int last = P + max_new - 2;   // the last position a row may have: its output is generated token max_new - 1
+    int rounds = 0, seen = 0, bound = P;
+    bool stopped = false;
+    std::vector<int> widths;
+    if (max_new > 1) {
+        WM_HIP(hipEventRecord(x_ev[1], ctx->stream));
+        WM_HIP(hipStreamWaitEvent(dc->stream, x_ev[1], 0));
+        WM_TRY(wm_spec_adopt(dc, sp, G, P));
+        WM_TRY(draft_embed());
+    }
+    while (max_new > 1) {
+        int w = wm_spec_width(k, bound, last);
+        // at most two rounds ahead of the device -- and when the bound on the position leaves no room, what the device says
+        while (seen < rounds && (rounds - seen >= 2 || w == 0)) {
+            const int slot = seen % WM_NLIVE_RING;
+            WM_HIP(hipEventSynchronize(round_ev[slot]));
+            if (m->h_spec[slot * 2] == 0) stopped = true;
+            bound = m->h_spec[slot * 2 + 1];
+            ++seen;
+            for (int r = seen; r < rounds; ++r) bound += widths[r];
+            w = wm_spec_width(k, bound, last);
+        }
+        if (stopped || w == 0) break;
+        // DRAFT: w plain greedy steps from the target's last token (the last one for its cache alone)
+        for (int s = 0; s < w; ++s) WM_TRY(lane_position(dj, dj.mode, P, false));
+        WM_HIP(hipEventRecord(x_ev[0], dc->stream));
+        WM_HIP(hipStreamWaitEvent(ctx->stream, x_ev[0], 0));
+        // VERIFY: the proposals behind the last token, one panel step of G x w rows, then accept + commit
+        WM_TRY(wm_spec_stage(ctx, sp, G, w, P, n_ctx));
+        WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, w, m->tok_emb, m->dec_pos, m->dims.n_text_state, n_ctx, m->dx, m->dxb,
+                                  m->dstats, m->dmean));
+        WM_TRY(wm_model_spec_panel_step(ctx, G, w, tj.mode, P));
+        WM_TRY(wm_spec_accept(ctx, m->dargmax, m->vpad / 16, sp, xd, stop, G, w, P, n_ctx, fallback));
+        const int slot = rounds % WM_NLIVE_RING;
+        WM_HIP(hipMemcpyAsync(m->h_spec + slot * 2, sp.round, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        WM_HIP(hipEventRecord(round_ev[slot], ctx->stream));
+        WM_HIP(hipStreamWaitEvent(dc->stream, round_ev[slot], 0));
+        WM_TRY(draft_embed());
+        widths.push_back(w);
+        bound += w;
+        ++rounds;
+    }
+    // the group's streams, as a plain group fetches them
+    WM_HIP(hipEventRecord(tj.ev[3], ctx->stream));
+    tj.gen.resize((size_t)max_new * G);
+    WM_HIP(hipMemcpyAsync(tj.gen.data(), m->dseq + (size_t)P * G, tj.gen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (cfg.xc.logprobs) {
+        tj.lp.resize((size_t)max_new * G);
+        WM_HIP(hipMemcpyAsync(tj.lp.data(), m->dx_logprob, tj.lp.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (cfg.xc.no_speech) {
+        tj.ns.resize(G);
+        WM_HIP(hipMemcpyAsync(tj.ns.data(), m->dx_nospeech, tj.ns.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (sc.stats && max_new > 1) {
+        stats.resize((size_t)G * 4);
+        WM_HIP(hipMemcpyAsync(stats.data(), sp.stats, stats.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    WM_HIP(hipStreamSynchronize(dc->stream));
+    wm_group_rows_out(tj.gen.data(), tj.lp.data(), tj.ns.data(), cfg.stop.budgets, call.eot, 1, b0, G, max_new, call.tokens_out,
+                      call.lens_out, cfg.xc.logprobs, cfg.xc.no_speech);
+    if (sc.stats)
+        for (int c = 0; c < G; ++c) {
+            wm_spec_stats &o = sc.stats[b0 + c];
+            o.rounds = o.proposed = o.accepted = o.kept = 0;
+            if (!stats.empty()) { o.rounds = stats[c * 4]; o.proposed = stats[c * 4 + 1]; o.accepted = stats[c * 4 + 2]; o.kept = stats[c * 4 + 3]; }
+        }
+    wm_add_stage_ms(tj.ev.e, 3, false, tj.stage_sum);
+    for (int i = 0; i < 3; ++i) ctx->stage_ms[i] += tj.stage_sum[i];
+    return WM_OK;
+}
+
+int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
+    std::vector<int32_t> budgets;   // consumed by this call whatever happens next (tx_transcribe)
+    if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
+    const int32_t *dbg_script = nullptr;   // the debug library's script is for this call only
+    if (ctx && ctx->model) dbg_script = ctx->model->spec_dbg_script;
+    struct ScriptScope {
+        WmModel *m;
+        ~ScriptScope() { if (m) { m->spec_dbg_script = nullptr; m->spec_dbg_script_new = m->spec_dbg_script_rows = 0; } }
+    } script_scope{ctx && ctx->model ? ctx->model : nullptr};
+    WM_TRY(entry_checks(call));
+    WM_MODEL(ctx);
+    WM_TRY(spec_checks(ctx, sc, call));
+    TxCfg cfg;
+    WM_TRY(tx_validate(ctx, call, budgets, &cfg));
+    WM_REQUIRE(!dbg_script || (m->spec_dbg_script_new == call.max_new && m->spec_dbg_script_rows == call.B), WM_ERR_INVALID,
+               "the proposal script was set for %d rows x %d tokens, the call has %d x %d", m->spec_dbg_script_rows,
+               m->spec_dbg_script_new, call.B, call.max_new);
+    // the accept kernel closes a row from the extended decode's partials and keeps the windows' stop state itself: both on
+    // for every speculative call (a plain call without them gives the same tokens: DESIGN.md sections 4, 7)
+    cfg.xc.on = true;
+    cfg.stop.on = true;
+    TxCfg dcfg = cfg;   // the draft: a greedy decode with its own masks and rules, nothing else
+    dcfg.xc = XCfg();
+    dcfg.stop = StopCfg();
+    std::vector<int> b0, cg;
+    const int n_groups = wm_spec_groups(call.B, sc.k, g_wm_tuning.spec_group, b0, cg);
+    ctx->stage_ms[0] = ctx->stage_ms[1] = ctx->stage_ms[2] = 0.f;
+    ActiveGuard active_guard(g_wm_active_decodes[ctx->device & 63]);
+    for (int g = 0; g < n_groups; ++g) WM_TRY(spec_group(ctx, sc, call, cfg, dcfg, b0[g], cg[g]));
+    return WM_OK;
+}
 }  // namespace
 
 extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
@@ -1224,4 +1397,22 @@ extern "C" int wm_transcribe_windows_beam_aligned(wm_ctx *ctx, const wm_windows 
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
     aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
     return tx_transcribe(ctx, call);
+} WM_API_CATCH
+
+// wm_transcribe_mel whose tokens a draft model proposes and panels of the target verify: the same outputs, bit for bit
+extern "C" int wm_transcribe_mel_speculative(wm_ctx *ctx, wm_ctx *draft, const float *mel, const int64_t *mel_base,
+                                             const int32_t *mel_len, const int32_t *seek, const int32_t *n_frames, int B,
+                                             const int32_t *prompts, int n_prompt, int draft_len, int max_new, int32_t eot,
+                                             const wm_decode_opts *opts, int32_t *tokens_out, int32_t *lens_out,
+                                             float *token_logprobs_out, float *no_speech_prob_out, wm_spec_stats *stats_out,
+                                             wm_mem mem) try {
+    TxCall call;
+    call.entry = TxCall::MEL;
+    mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
+    call.prompts = {prompts, n_prompt, nullptr, 0, nullptr};
+    call.n_prompt = n_prompt;
+    outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
+    SpecCall sc;
+    sc.draft = draft; sc.k = draft_len; sc.stats = stats_out;
+    return tx_speculative(ctx, sc, call);
 } WM_API_CATCH

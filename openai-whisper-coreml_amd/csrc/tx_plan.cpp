@@ -4,6 +4,8 @@
 
 #include <algorithm>
 
+#include "spec_round.h"
+
 namespace {
 constexpr int kGroupChunks = 8;   // smallest decode group worth a lane (BASELINE.json configs[3]); up to WM_DEC_MAXB
 }  // namespace
@@ -242,4 +244,53 @@ bool wm_group_rows_out_flat(const int32_t *in, int32_t *out) {
     wm_group_rows_out(in + 16, (const float *)(in + 144), (const float *)(in + 272), in[6] ? in + 288 : nullptr, in[5], N, b0, Bg,
                       max_new, out, out + 128, in[7] ? (float *)(out + 144) : nullptr, in[8] ? (float *)(out + 272) : nullptr);
     return true;
+}
+
+// ---------------------------------------------------------------- speculative decoding ----
+namespace {
+// The preferred group size of a speculative call: the whole call, up to the row bound 128 / (k + 1), in balanced groups (24
+// windows at k = 5: the bound is 21, so two groups of 12).  The groups of a call run one after the other and a round costs
+// about the same for 1 window as for 12 (the weight stream and the launch chain), so fewer, larger groups won at every
+// acceptance pattern measured -- also with independent windows, where the lockstep cut advances a group by its WORST window:
+// large-v2 + tiny draft, k = 5, 75 % per proposal independently per row, 8 windows in groups of 1 / 2 / 4 / 8: 2106 / 1516 / 1245 /
+// 919 ms; 24 windows in groups of 1 / 2 / 4 / 8 / 12: 6220 / 4619 / 3802 / 2697 / 2096 ms (profiles/r22_speculative.txt).
+constexpr int kSpecGroup = WM_DEC_MAXB;
+}  // namespace
+
+int wm_spec_groups(int B, int k, int spec_group, std::vector<int> &b0, std::vector<int> &cg) {
+    if (B < 1) B = 1;
+    if (k < 1) k = 1;
+    const int cap = std::max(1, WM_DEC_MAXB / (k + 1));
+    const int size = std::min(cap, spec_group > 0 ? spec_group : kSpecGroup);
+    const int G = (B + size - 1) / size;
+    wm_balanced_cut(B, G, b0, cg);
+    return G;
+}
+
+int wm_spec_width(int k, int bound, int last) {
+    const int room = last - bound + 1;
+    return room < 1 ? 0 : std::min(k + 1, room);
+}
+
+int wm_spec_round(int G, int w, const int32_t *accepted, const int32_t *live, const int32_t *eot_at, const int32_t *left,
+                  int32_t *live_out, int32_t *inc) {
+    int n = WM_SPEC_NO_CUT;
+    bool any = false;
+    for (int c = 0; c < G; ++c) {
+        if (!live[c]) continue;
+        n = std::min(n, wm_spec_window_ask(accepted[c], eot_at[c], left[c]));
+        any = true;
+    }
+    n = any ? std::min(n, w) : 0;   // (every live window finishes: the whole width)
+    for (int c = 0; c < G; ++c) {
+        int32_t *o = inc + (size_t)c * 4;
+        o[0] = o[1] = o[2] = o[3] = 0;
+        live_out[c] = 0;
+        if (!live[c]) continue;
+        int m, stop, acc, kept;
+        wm_spec_window_cut(n, accepted[c], eot_at[c], left[c], &m, &stop, &acc, &kept);
+        live_out[c] = stop ? 0 : 1;
+        o[0] = 1; o[1] = w - 1; o[2] = acc; o[3] = kept;
+    }
+    return n;
 }

@@ -88,6 +88,20 @@ int wm_group_tables(const TxPrompts &p, int n_prompt, const int32_t *budgets, in
 void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, const int32_t *budgets, int32_t eot, int N, int b0,
                        int Bg, int max_new, int32_t *tokens, int32_t *lens, float *logprobs, float *no_speech);
 
+// ---------------------------------------------------------------- speculative decoding ----
+// wm_transcribe_mel_speculative.  The decode groups of a call of B windows at draft length k: a verify
+// step holds G x (k + 1) <= WM_DEC_MAXB rows, and below that bound the lockstep cut trades group size against acceptance --
+// spec_group (WmTuning; 0: the measured default) is the preferred group size.  Balanced runs; returns their number.
+int wm_spec_groups(int B, int k, int spec_group, std::vector<int> &b0, std::vector<int> &cg);
+// The width of the next verify step: draft length k, `bound` = an upper bound on the group's device position, `last` = the last
+// position a row may have (n_prompt + max_new - 2).  0: no row is left, or the bound is too loose to tell -- ask the device.
+int wm_spec_width(int k, int bound, int last);
+// One round of a group of G windows whose verify step had w rows per window: accepted[c] leading rows matched, live[c] != 0 =
+// the window was live, eot_at[c] / left[c]: spec_round.h.  Returns n, the positions the group advances (0: nobody is live);
+// live_out[c], and inc [G][4] = the increments of wm_spec_stats (rounds, proposed, accepted, kept; zero for a frozen window).
+int wm_spec_round(int G, int w, const int32_t *accepted, const int32_t *live, const int32_t *eot_at, const int32_t *left,
+                  int32_t *live_out, int32_t *inc);
+
 // ---------------------------------------------------------------- the hooks' flat forms ----
 // documented at wmdbg_tx_plan / wmdbg_group_tables / wmdbg_group_rows_out (include/whisper_mi355x_debug.h)
 constexpr int WM_TX_PLAN_IN = 12, WM_TX_PLAN_OUT = 8;

@@ -26,5 +26,6 @@ struct WmTuning {
     int frontend_per_wave_twiddles = 0;   // 1: the f32 front end's round-1-5 stage-1 kernel (every wave fetches its own twiddles from L2)
     int lane_parts = 0;           // sub-chip lanes: 0 = the product's rule, 1 = never, 2 / 3 = that many CU-masked groups whenever the call has >= 2 chunks per part
     int teacher_panel_cut = 0;    // PROBE: how a teacher-forced group of more windows than fit a full-width panel is cut: 1 = ONE panel narrowed to floor(128 / windows) positions, 2 = slices at the full width (0 = the rule, the fewest steps: model.cpp wm_model_panel_slices)
+    int spec_group = 0;           // windows per decode group of a speculative call (0 = the measured default, the whole call: tx_plan.cpp wm_spec_groups); always <= 128 / (draft_len + 1)
     int lane_solo_cus = 0;        // PROBE: n in 1 .. 31 = run the call's decode groups one after the other on ONE lane confined to the first n CUs of every XCD
 };
