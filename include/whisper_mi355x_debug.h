@@ -158,6 +158,15 @@ typedef struct wmdbg_step {
     int32_t stats_tail_nonzero;   /* words of parts 1 .. K/16 - 1 of the B rows that are not +0.0 */
 } wmdbg_step;
 WM_API int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io);
+/* The THREE closes on one step's partials.  wmdbg_decode_close's launches with x_on, temperature 0, ts_mode 0 or 2 and a
+ * generated position; between the DE_LOGITS_X launch and the arg-max close -- before that close moves the rule state and the
+ * position -- the beam close's list kernel (wm_beam_topk: B windows of N = 1) and the speculative round's accept + commit
+ * (wm_spec_accept: B / w windows of w rows, w dividing B, the rows' ranges the step's rng; token buffer, positions, stop state
+ * and statistics are scratch copies) run on the same partials.  Out, per row: the beam list's length, first token and first
+ * log-prob (WM_MAX_BEAM + 1 slots per row are not returned: slot 0 only), the beam close's no_speech_prob (pre-filled with
+ * WMDBG_SENTINEL_F32; written when sot_pos == pos), the accept kernel's winner and log-prob; the arg-max close's are io's. */
+WM_API int wmdbg_decode_close_shared(wm_ctx *ctx, wmdbg_step *io, int w, int32_t *beam_n, int32_t *beam_tok, float *beam_lp,
+                                     float *beam_nospeech, int32_t *acc_tok, float *acc_lp);
 /* wmdbg_decode_close with the repetition rules on (wm_set_repetition_rules: penalty, ngram, and io->eot as the rules' eot, in
  * [0, V] whatever ts_mode is): wm_repeat_state on the token history in front of a DE_LOGITS_XR launch.  Needs x_on and
  * n_prompt <= n_ctx.  The bitmaps are pre-filled with 0xff bytes.  (1.0, 0) runs the same kernels with empty rules. */

@@ -8,7 +8,8 @@
 // A beam of width 1 must reproduce the greedy decode BIT FOR BIT (tokens, log-probs), so a row's close here is the
 // arithmetic of dec_kernels.hip's argmax_embed_body in its summation orders (16 fixed tile segments, one wave per row for
 // the merges and the embedding): both call the same functions of dec_close.h -- lse_row_segments, lse_row_total,
-// ts_row_merge, ts_advance, embed_row -- and tests/test_beam_gpu.py holds the two closes to equal bits.
+// row_choose (with ts_row_merge inside), row_log_norm, row_no_speech, ts_advance, embed_row, live_list_rebuild -- and
+// tests/test_beam_gpu.py (end to end) and tests/test_close_shared_gpu.py (on one step's partials) hold the closes to equal bits.
 #include "beam.h"
 #include "dec_close.h"
 #include "model.h"
@@ -53,27 +54,16 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
     }
     __syncthreads();
     if (wave == 0) {
-        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f}, lts{-1e30f, 0.f};
+        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f};
         lse_row_total(seg_s, lane, lt, la);
         unsigned long long key = lane < 16 ? red_s[0][lane] : 0ull;
         key = __shfl(key_max_xor<16>(key), 0);
-        bool forced = false;
-        if (ts.rng) {   // "if sum of probability over timestamps is above any other token, sample timestamp", on raw logits
-            unsigned long long kts;
-            float M, S;
-            ts_row_merge(ts, b, n_tiles, lane, kts, M, S);
-            const float text_best = key ? lt.m : -1e30f;
-            const float lse = S > 0.f ? M + __logf(S) : -1e30f;
-            lts = Lse{M, S};
-            forced = kts != 0ull && (key == 0ull || lse > text_best);
-        }
-        Lse al = lt;
-        if (forced) al = lts;
-        else if (ts.rng) al = lse_merge(lt, lts);
+        const RowChoice ch = row_choose(ts, b, n_tiles, lane, key, lt.m);   // (for `forced` and the normaliser: the list scan below picks)
+        const float norm = row_log_norm(ts, ch, lt);
         if (lane == 0) {
-            norm_s = al.m + __logf(al.s);
-            forced_s = forced ? 1 : 0;
-            if (sot) xd.nospeech[b] = __expf(xd.ns_v[b] - la.m) / la.s;
+            norm_s = norm;
+            forced_s = ch.forced ? 1 : 0;
+            if (sot) xd.nospeech[b] = row_no_speech(xd, b, la);
         }
     }
     __syncthreads();
@@ -225,16 +215,11 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(int B, int *__restric
     __syncthreads();
     if (wave == 0) {
         if (stop.done) {   // early stop: the flags and the compact list of live rows the attention kernels walk
-            int n = 0;
-            for (int b0 = 0; b0 < B; b0 += 64) {
-                const int b = b0 + lane;
-                const bool live = b < B && done_s[b < B ? b : 0] == 0;
-                if (b < B) stop.done[b] = live ? 0 : 1;
-                const unsigned long long m = __ballot(live);
-                if (live) stop.live_rows[n + __popcll(m & ((1ull << lane) - 1ull))] = b;
-                n += __popcll(m);
-            }
-            if (lane == 0) *stop.n_live = n;
+            live_list_rebuild(stop, B, lane, [&](int b) {
+                const bool live = done_s[b] == 0;
+                stop.done[b] = live ? 0 : 1;
+                return live;
+            });
         }
         if (lane == 0) *pos_ptr = pos + 1;
     }
@@ -311,14 +296,13 @@ int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const 
     return WM_OK;
 }
 
-int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const bf16_t *emb, const float *pemb, int d,
-                        float *x, bf16_t *xb, float *stats_out, float *mean_buf, const WmTsDev &ts, const WmStopDev &stop,
-                        const WmXDev &xd, const int *off, const WmBeamDev &bm) {
+int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const WmEmbedDev &e, const WmTsDev &ts,
+                        const WmStopDev &stop, const WmXDev &xd, const int *off, const WmBeamDev &bm) {
     WmProfScope ps(&ctx->prof, "beam_select", ctx->stream);
     WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && bm.N >= 1 && bm.N <= WM_MAX_BEAM && rows % bm.N == 0 && xd.par, WM_ERR_INVALID,
                "beam_select: bad group");
-    beam_select_kernel<<<1, 1024, 0, ctx->stream>>>(rows, seq, pos_ptr, n_prompt, emb, pemb, d, x, xb, stats_out, mean_buf, ts, stop,
-                                                    xd, off, bm);
+    beam_select_kernel<<<1, 1024, 0, ctx->stream>>>(rows, seq, pos_ptr, n_prompt, e.emb, e.pemb, e.d, e.x, e.xb, e.stats_out, e.mean_buf,
+                                                    ts, stop, xd, off, bm);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

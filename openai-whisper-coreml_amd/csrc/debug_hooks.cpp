@@ -1427,7 +1427,7 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
     WM_TRY(pool.get(&dst, nullptr, n_st * 4, s, 0xff));
     WM_TRY(pool.get(&dmean, nullptr, (size_t)B * 4, s, 0xff));
     if (!by_steps) {
-        WM_TRY(wm_dec_embed_panel(ctx, dseq + c0, stride, dpos, 0, C, w, de, dp, d, n_ctx, dx, dxb, dst, dmean));
+        WM_TRY(wm_dec_embed_panel(ctx, dseq + c0, stride, dpos, 0, C, w, n_ctx, WmEmbedDev{de, dp, d, dx, dxb, dst, dmean}));
         WM_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * 4, hipMemcpyDeviceToHost, s));
         WM_HIP(hipMemcpyAsync(hxb.data(), dxb, hxb.size() * 2, hipMemcpyDeviceToHost, s));
         WM_HIP(hipMemcpyAsync(hst.data(), dst, hst.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1451,17 +1451,18 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
         WM_TRY(pool.get(&dxb1, nullptr, (size_t)Cpad * d * 2, s));
         WM_TRY(pool.get(&dst1, nullptr, n_st1 * 4, s));
         WM_TRY(pool.get(&dmean1, nullptr, (size_t)C * 4, s));
+        const WmEmbedDev e1 = {de, dp, d, dx1, dxb1, dst1, dmean1};
         for (int sp = 0; sp < w; ++sp) {
             const int p = pos + sp;
             if (p == 0) {
                 WM_HIP(hipMemsetAsync(dpos, 0, 4, s));
-                WM_TRY(wm_dec_embed(ctx, dseq1, dpos, C, de, dp, d, dx1, dxb1, dst1, dmean1));
+                WM_TRY(wm_dec_embed(ctx, dseq1, dpos, C, e1, nullptr));
             } else {
                 const int pm = p - 1;
                 WM_HIP(hipMemcpyAsync(dpos, &pm, 4, hipMemcpyHostToDevice, s));
                 WM_HIP(hipStreamSynchronize(s));
-                WM_TRY(wm_argmax_embed(ctx, dtile, n_tiles, C, dseq1, dpos, n_ctx, nullptr, 0, de, dp, d, n_ctx, dx1, dxb1, dst1, nullptr,
-                                       darr, 0, dmean1));
+                WM_TRY(wm_argmax_embed(ctx, dtile, n_tiles, C, dseq1, dpos, n_ctx, nullptr, 0, n_ctx, e1, WmTsDev{}, darr, 0, WmStopDev{},
+                                       WmXDev{}, nullptr));
             }
             WM_HIP(hipMemcpyAsync(x1.data(), dx1, x1.size() * 4, hipMemcpyDeviceToHost, s));
             WM_HIP(hipMemcpyAsync(xb1.data(), dxb1, xb1.size() * 2, hipMemcpyDeviceToHost, s));
@@ -1607,9 +1608,71 @@ static int stage_seqbias(DevPool &pool, hipStream_t s, const WmSbTable &t, int B
     return WM_OK;
 }
 
+// wmdbg_decode_close_shared: where the beam and accept closes of the step's partials go (host, [B] each)
+struct CloseShared {
+    int w;
+    int32_t *beam_n, *beam_tok, *acc_tok;
+    float *beam_lp, *beam_nospeech, *acc_lp;
+};
+// The beam list kernel (B windows, N = 1) and the accept + commit of B / w windows x w rows on the partials the logits launch
+// `a` left, enqueued in front of the arg-max close.  Everything either one writes is scratch of `pool`: the arg-max close behind
+// them reads the step's own state.  The copies to the host are synchronised by the caller.
+static int shared_closes_run(wm_ctx *ctx, DevPool &pool, const wmdbg_step *io, const CloseShared &sh, const DecGemvArgs &a,
+                             const unsigned *dmask, int mw) {
+    const int B = io->B, w = sh.w, G = B / w, n_ctx = io->n_ctx, L = WM_MAX_BEAM + 1;
+    hipStream_t s = ctx->stream;
+    const std::vector<uint32_t> nan32(B, WMDBG_SENTINEL_F32);
+    // beam: live beams with sum 0 in windows that have not left; no_speech_prob into a buffer of its own
+    WmBeamDev bm;
+    memset(&bm, 0, sizeof(bm));
+    bm.N = 1; bm.n_ctx = n_ctx;
+    WmXDev bx = a.x;
+    WM_TRY(pool.get(&bx.nospeech, nan32.data(), (size_t)B * 4, s));
+    WM_HIP(hipStreamSynchronize(s));   // nan32 leaves scope with this function
+    WM_TRY(pool.get(&bm.sum, nullptr, (size_t)B * 4, s));
+    WM_TRY(pool.get(&bm.wdone, nullptr, (size_t)B * 4, s));
+    WM_TRY(pool.get(&bm.list_n, nullptr, (size_t)B * 4, s, 0xff));
+    WM_TRY(pool.get(&bm.list_tok, nullptr, (size_t)B * L * 4, s, 0xff));
+    WM_TRY(pool.get(&bm.list_lp, nullptr, (size_t)B * L * 4, s, 0xff));
+    WM_TRY(wm_beam_topk(ctx, a.out_f32, a.ldo, io->V, a.argmax, B, a.ts, bx, a.mask ? dmask : nullptr, mw, io->n_prompt, a.pos_ptr, bm));
+    // accept: the rows' ranges are the step's; the commit launch behind it advances scratch copies only
+    WmSpecDev sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.tts = a.ts; sp.max_new = n_ctx; sp.n_vocab = io->V;
+    int *dpos2, *dstate;
+    WM_TRY(pool.get(&sp.tseq, nullptr, (size_t)(n_ctx + w + 1) * G * 4, s));
+    WM_TRY(pool.get(&sp.dseq, nullptr, (size_t)(n_ctx + w + 1) * G * 4, s));
+    const int pos2[2] = {io->pos, io->pos};
+    WM_TRY(pool.get(&dpos2, pos2, 8, s));
+    WM_HIP(hipStreamSynchronize(s));   // pos2 too
+    sp.tpos = dpos2; sp.dpos = dpos2 + 1;
+    WM_TRY(pool.get(&dstate, nullptr, ((size_t)G * 21 + 2) * 4, s));   // chist | crng | dchist | dcrng | stats | acc | round
+    sp.chist = dstate; sp.crng = dstate + G * 4; sp.dchist = dstate + G * 8; sp.dcrng = dstate + G * 12;
+    sp.stats = dstate + G * 16; sp.acc = dstate + G * 20; sp.round = dstate + G * 21;
+    WM_TRY(pool.get(&sp.wtok, nullptr, (size_t)B * 4, s, 0xff));
+    WM_TRY(pool.get(&sp.wlp, nullptr, (size_t)B * 4, s, 0xff));
+    WmXDev ax = a.x;
+    WM_TRY(pool.get(&ax.logprob, nullptr, (size_t)n_ctx * G * 4, s));
+    WmStopDev st;
+    memset(&st, 0, sizeof(st));
+    WM_TRY(pool.get(&st.done, nullptr, (size_t)G * 4, s));
+    WM_TRY(pool.get(&st.n_live, nullptr, 4, s));
+    st.eot = -1;
+    WM_TRY(wm_spec_accept(ctx, a.argmax, (io->V + 15) / 16, sp, ax, st, G, w, io->n_prompt, n_ctx, io->fallback_tok));
+    WM_HIP(hipMemcpyAsync(sh.beam_n, bm.list_n, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpy2DAsync(sh.beam_tok, 4, bm.list_tok, (size_t)L * 4, 4, B, hipMemcpyDeviceToHost, s));   // slot 0 of every row
+    WM_HIP(hipMemcpy2DAsync(sh.beam_lp, 4, bm.list_lp, (size_t)L * 4, 4, B, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(sh.beam_nospeech, bx.nospeech, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(sh.acc_tok, sp.wtok, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(sh.acc_lp, sp.wlp, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    return WM_OK;
+}
+
 // rep: the repetition rules (penalty, ngram, io->eot) are on -- wm_repeat_state in front of a DE_LOGITS_XR launch
 // sbt (with rep): the sequence bias as well -- wm_seqbias_state behind it and a DE_LOGITS_XB launch, also for an empty table
-static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram, const WmSbTable *sbt = nullptr) {
+// sh: the beam and accept closes on the same partials, in front of the arg-max close (wmdbg_decode_close_shared)
+static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram, const WmSbTable *sbt = nullptr,
+                            const CloseShared *sh = nullptr) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
     if (rep)
@@ -1771,9 +1834,10 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
         }
     }
     WM_TRY(wm_dec_gemv(ctx, a));
-    WM_TRY(wm_argmax_embed(ctx, a.argmax, n_tiles, B, dseq, dpos, n_prompt, dres, io->arg_first, dE, dpemb, K, n_ctx, dxn, dxbn, dstn,
-                           io->ts_mode ? &ts : nullptr, darr, io->fallback_tok, dmn, io->stop_on ? &sp : nullptr,
-                           io->x_on ? &xd : nullptr, doff));
+    if (sh) WM_TRY(shared_closes_run(ctx, pool, io, *sh, a, dmask, mw));
+    // (ts, sp and xd are empty structs unless ts_mode, stop_on and x_on filled them)
+    WM_TRY(wm_argmax_embed(ctx, a.argmax, n_tiles, B, dseq, dpos, n_prompt, dres, io->arg_first, n_ctx,
+                           WmEmbedDev{dE, dpemb, K, dxn, dxbn, dstn, dmn}, ts, darr, io->fallback_tok, sp, xd, doff));
     WM_HIP(hipMemcpyAsync(lg.data(), a.out_f32, lg.size() * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(io->result, dres, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(io->seq, dseq, (size_t)n_ctx * B * 4, hipMemcpyDeviceToHost, s));
@@ -1820,6 +1884,19 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
 }
 
 extern "C" int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io) { return decode_close_run(ctx, io, false, 1.f, 0); }
+extern "C" int wmdbg_decode_close_shared(wm_ctx *ctx, wmdbg_step *io, int w, int32_t *beam_n, int32_t *beam_tok, float *beam_lp,
+                                         float *beam_nospeech, int32_t *acc_tok, float *acc_lp) {
+    WM_REQUIRE(io && beam_n && beam_tok && beam_lp && beam_nospeech && acc_tok && acc_lp, WM_ERR_INVALID, "wmdbg_decode_close_shared: null");
+    WM_REQUIRE(io->x_on && io->temperature == 0.f && (io->ts_mode == 0 || io->ts_mode == 2) && !io->stop_on && io->pos + 1 >= io->n_prompt,
+               WM_ERR_INVALID, "wmdbg_decode_close_shared: needs x_on, temperature 0, ts_mode 0 or 2, no early stop and a generated position");
+    WM_REQUIRE(w >= 1 && w <= WM_MAX_TEACHER_PANEL && io->B >= 1 && io->B % w == 0, WM_ERR_INVALID,
+               "wmdbg_decode_close_shared: the panel width %d does not divide %d rows", w, io->B);
+    // (the list kernel takes the first-position bitmap at position n_prompt - 1, the logits launch where mask_first says)
+    WM_REQUIRE(io->n_suppress_first == 0 || (io->mask_first != 0) == (io->pos == io->n_prompt - 1), WM_ERR_INVALID,
+               "wmdbg_decode_close_shared: mask_first must say whether this is position n_prompt - 1");
+    const CloseShared sh = {w, beam_n, beam_tok, acc_tok, beam_lp, beam_nospeech, acc_lp};
+    return decode_close_run(ctx, io, false, 1.f, 0, nullptr, &sh);
+}
 extern "C" int wmdbg_decode_close_rep(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram) {
     return decode_close_run(ctx, io, true, penalty, ngram);
 }

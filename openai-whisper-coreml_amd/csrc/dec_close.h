@@ -1,8 +1,9 @@
 // dec_close.h -- device code shared by the kernels that CLOSE a decode position: the step-closing arg-max of the greedy /
-// sampling decode (dec_kernels.hip argmax_embed_body) and the beam-search close (beam.hip).  First the small helpers (bf16
-// conversion, the packed (value, ~index) arg-max key and its butterfly maximum, the (max, sum exp) merge), then a row's close
-// itself: the five order-sensitive pieces whose bits make a beam of width 1 the greedy decode, each stated here and nowhere
-// else.  An edit to one of them is an edit to both closes (what holds them -- results, resources, time).
+// sampling decode (dec_kernels.hip argmax_embed_body), the beam-search close (beam.hip) and the accept of a speculative
+// round (spec.hip).  First the small helpers (bf16 conversion, the packed (value, ~index) arg-max key and its butterfly
+// maximum, the (max, sum exp) merge), then a row's close itself: the order-sensitive pieces whose bits make a beam of width 1
+// the greedy decode and a speculative decode the plain one, each stated here and nowhere else.  An edit to one of them is an
+// edit to all three closes (what holds them -- results, resources, time).
 #pragma once
 #include "model.h"
 
@@ -56,9 +57,10 @@ __device__ __forceinline__ Lse lse_load(const float *p) {
 }
 
 // ------------------------------------------------------------------ a row's close -------------------------------------
-// The order-sensitive pieces of a row's close, stated ONCE: argmax_embed_body and the beam kernels call these, which is
-// what makes a beam of width 1 the greedy decode bit for bit (16 fixed tile segments, one wave per row for the merges and
-// the embedding).  The callers keep their own guards (X, ts.rng, generated position, context end).
+// The order-sensitive pieces of a row's close, stated ONCE: argmax_embed_body, the beam kernels and spec_accept_kernel call
+// these, which is what makes a beam of width 1 the greedy decode and a verified round the plain steps bit for bit (16 fixed
+// tile segments, one wave per row for the merges, the decision and the embedding).  The callers keep their own guards (X,
+// generated position, finished row, <|startoftranscript|> position, context end).
 
 // One wave's share of a row's 16 FIXED tile segments of the WmXDev partials: segments pi, pi + P, ... of the row whose
 // partials start at tile index rb; seg[sg] = allowed text (m, s), unfiltered (m, s) -- the latter merged when `sot` only.
@@ -137,6 +139,66 @@ __device__ __forceinline__ void ts_row_merge(const WmTsDev &ts, int b, int n_til
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) S += __shfl_xor(S, o);
+}
+
+// The row's decision between its text and its timestamps, by one wave, every lane holding it.  key = the best allowed text
+// key (0: none), text_max = the RAW maximum of the allowed text: the key's own value, or lt.m where the key may carry a
+// perturbed score (the rule compares raw logits, as openai-whisper does).  ApplyTimestampRules: "if sum of probability over
+// timestamps is above any other token, sample timestamp".
+struct RowChoice {
+    unsigned long long key;   // the winner; 0: nothing admissible (every allowed id suppressed, or NaN logits)
+    bool forced;              // the sum rule forced a timestamp: the allowed set is the admissible timestamps alone
+    Lse lts;                  // (max, sum exp) over the allowed timestamps
+};
+__device__ __forceinline__ RowChoice row_choose(const WmTsDev &ts, int b, int n_tiles, int lane, unsigned long long key, float text_max) {
+    RowChoice c{key, false, Lse{-1e30f, 0.f}};
+    if (ts.rng) {
+        unsigned long long kts;
+        float M, S;
+        ts_row_merge(ts, b, n_tiles, lane, kts, M, S);
+        const float text_best = key ? text_max : -1e30f;
+        const float lse = S > 0.f ? M + __logf(S) : -1e30f;
+        c.lts = Lse{M, S};
+        c.forced = kts != 0ull && (key == 0ull || lse > text_best);
+        if (c.forced) c.key = kts;                  // timestamps only
+        else c.key = kts > key ? kts : key;         // arg-max over everything allowed
+    }
+    return c;
+}
+// log of the filtered distribution's normaliser (temperature 1): over the timestamps when one was forced, else over the
+// allowed text and, under the rules, the timestamps
+__device__ __forceinline__ float row_log_norm(const WmTsDev &ts, const RowChoice &c, Lse lt) {
+    Lse al = lt;
+    if (c.forced) al = c.lts;
+    else if (ts.rng) al = lse_merge(lt, c.lts);
+    return al.m + __logf(al.s);
+}
+// log-prob of row b's winner under the filtered distribution; nothing admissible: -inf
+__device__ __forceinline__ float row_logprob(const WmTsDev &ts, const WmXDev &xd, int b, int n_tiles, const RowChoice &c, Lse lt) {
+    const float norm = row_log_norm(ts, c, lt);
+    float lp = -INFINITY;
+    if (c.key) {
+        const int tok = argmax_key_index(c.key), side = (ts.rng && tok >= ts.ts_begin) ? 1 : 0;
+        lp = xd.win[((long)b * n_tiles + (tok >> 4)) * 2 + side] - norm;
+    }
+    return lp;
+}
+// no_speech_prob of row b from the unfiltered (max, sum exp)
+__device__ __forceinline__ float row_no_speech(const WmXDev &xd, int b, Lse la) { return __expf(xd.ns_v[b] - la.m) / la.s; }
+
+// The compact list of live rows the attention kernels walk, rebuilt by ONE wave from a per-row predicate (B <= WM_DEC_MAXB:
+// two ballots): stop.live_rows and *stop.n_live.  is_live(b) is called exactly once per row b < B, by the row's lane.
+template <class IsLive>
+__device__ __forceinline__ void live_list_rebuild(const WmStopDev &stop, int B, int lane, IsLive is_live) {
+    int n = 0;
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int b = b0 + lane;
+        const bool live = b < B && is_live(b < B ? b : 0);   // (the clamp: a load the compiler may issue ahead of the test)
+        const unsigned long long m = __ballot(live);
+        if (live) stop.live_rows[n + __popcll(m & ((1ull << lane) - 1ull))] = b;
+        n += __popcll(m);
+    }
+    if (lane == 0) *stop.n_live = n;
 }
 
 // `tok` was sampled for a row whose timestamp-rule history is hs[4] (n_sampled, last_is_ts, prev_is_ts, last_ts): advance

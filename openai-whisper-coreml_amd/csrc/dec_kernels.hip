@@ -1694,42 +1694,19 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
             pos = pos_ptr ? pv : 0;
         }
         key = __shfl(key_max_xor<16>(key), 0);   // P <= 16 partial maxima in lanes 0 .. 15; every lane of the owner carries the row's key
-        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f}, lts{-1e30f, 0.f};
-        bool forced = false;
+        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f};
         if (X) lse_row_total(seg_s[wave], lane, lt, la);   // the row's 16 segments, in a fixed order
-        if (ts.rng) {
-            // `key` is the best allowed TEXT token.  Merge the timestamp tiles: best allowed timestamp and
-            // log-sum-exp of the allowed timestamps; a timestamp is forced when that exceeds the best text logit
-            // (ApplyTimestampRules: "if sum of probability over timestamps is above any other token, sample timestamp").
-            unsigned long long kts;
-            float M, S;
-            ts_row_merge(ts, b, n_tiles, lane, kts, M, S);
-            // (X: the key may be a perturbed score; the rule compares RAW logits, as openai-whisper does)
-            const float text_best = key ? (X ? lt.m : argmax_key_value(key)) : -1e30f;
-            const float lse = S > 0.f ? M + __logf(S) : -1e30f;
-            lts = Lse{M, S};
-            forced = kts != 0ull && (key == 0ull || lse > text_best);
-            if (forced) key = kts;                    // timestamps only
-            else key = kts > key ? kts : key;         // arg-max over everything allowed
-        }
+        // `key` is the best allowed TEXT token; the decision against the timestamps (X: the key may be a perturbed score)
+        const RowChoice ch = row_choose(ts, b, n_tiles, lane, key, X ? lt.m : argmax_key_value(key));
         if (lane == 0) {
-            // key == 0: nothing admissible (every allowed id suppressed, or NaN logits): never index with -1
-            int tok = key ? argmax_key_index(key) : fallback_tok;
+            // ch.key == 0: nothing admissible: never index with -1
+            int tok = ch.key ? argmax_key_index(ch.key) : fallback_tok;
             if (X && pos + 1 >= n_prompt) {
-                // log-prob of the chosen token under the filtered distribution (temperature 1): the allowed set is the
-                // admissible timestamps when the sum rule forced one, else text and timestamps; nothing admissible: -inf
-                Lse al = lt;
-                if (forced) al = lts;
-                else if (ts.rng) al = lse_merge(lt, lts);
-                float lp = -INFINITY;
-                if (key) {
-                    const int side = (ts.rng && tok >= ts.ts_begin) ? 1 : 0;
-                    lp = xd.win[((long)b * n_tiles + (tok >> 4)) * 2 + side] - (al.m + __logf(al.s));
-                }
+                float lp = row_logprob(ts, xd, b, n_tiles, ch, lt);
                 if (stop.done && stop.done[b]) lp = 0.f;   // finished earlier: nothing is generated here
                 xd.logprob[(long)(pos + 1 - n_prompt) * B + b] = lp;
             }
-            if (X && pos == xd.par->sot_pos) xd.nospeech[b] = __expf(xd.ns_v[b] - la.m) / la.s;
+            if (X && pos == xd.par->sot_pos) xd.nospeech[b] = row_no_speech(xd, b, la);
             if (stop.done && pos + 1 >= n_prompt) {
                 // the token at index pos + 1 is generated token number gi (0-based)
                 const int gi = pos + 1 - n_prompt;
@@ -1795,18 +1772,9 @@ __device__ __forceinline__ void argmax_embed_body(const unsigned long long *__re
     }
     __syncthreads();
     if (is_last_s && wave == 0) {
-        int n = 0;
-        for (int b0 = 0; b0 < B; b0 += 64) {  // B <= 128: two ballots
-            const int b = b0 + lane;
-            const bool live = b < B && __hip_atomic_load(stop.done + (b < B ? b : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
-            const unsigned long long m = __ballot(live);
-            if (live) stop.live_rows[n + __popcll(m & ((1ull << lane) - 1ull))] = b;
-            n += __popcll(m);
-        }
-        if (lane == 0) {
-            *stop.n_live = n;
-            if (pos_ptr) *pos_ptr = pos + 1;
-        }
+        live_list_rebuild(stop, B, lane,
+                          [&](int b) { return __hip_atomic_load(stop.done + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0; });
+        if (lane == 0 && pos_ptr) *pos_ptr = pos + 1;
     }
 }
 
@@ -2021,21 +1989,20 @@ int wm_ln_fold(wm_ctx *ctx, const bf16_t *W, const float *g, const float *beta, 
     return WM_OK;
 }
 
-int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const bf16_t *emb, const float *pemb,
-                 int d, float *x, bf16_t *xb, float *stats_out, float *mean_buf, const int *off) {
+int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const WmEmbedDev &e, const int *off) {
     WmProfScope ps(&ctx->prof, "dec_embed", ctx->stream);
-    dec_embed_kernel<<<B, 256, 0, ctx->stream>>>(seq, pos_ptr, B, emb, pemb, d, x, xb, stats_out, mean_buf, off);
+    dec_embed_kernel<<<B, 256, 0, ctx->stream>>>(seq, pos_ptr, B, e.emb, e.pemb, e.d, e.x, e.xb, e.stats_out, e.mean_buf, off);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
 
-int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, const bf16_t *emb,
-                       const float *pemb, int d, int n_ctx, float *x, bf16_t *xb, float *stats_out, float *mean_buf) {
+int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, int n_ctx,
+                       const WmEmbedDev &e) {
     WM_REQUIRE(w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && C * w <= WM_DEC_MAXB && seq_stride >= C, WM_ERR_INVALID,
                "dec_embed_panel: %d windows x %d positions (stride %d)", C, w, seq_stride);
     WmProfScope ps(&ctx->prof, "dec_embed_panel", ctx->stream);
-    dec_embed_panel_kernel<<<C * w, 256, 0, ctx->stream>>>(seq, seq_stride, pos_ptr, pos_add, w, emb, pemb, d, n_ctx, x, xb, stats_out,
-                                                          mean_buf);
+    dec_embed_panel_kernel<<<C * w, 256, 0, ctx->stream>>>(seq, seq_stride, pos_ptr, pos_add, w, e.emb, e.pemb, e.d, n_ctx, e.x, e.xb,
+                                                          e.stats_out, e.mean_buf);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
@@ -2188,34 +2155,27 @@ int wm_dec_self_attention_panel(wm_ctx *ctx, const DecAttnArgs &t) {
 }
 
 int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, int B, int *seq, int *pos_ptr,
-                    int n_prompt, int *result, int arg_first, const bf16_t *emb, const float *pemb, int d, int n_ctx,
-                    float *x, bf16_t *xb, float *stats_out, const WmTsDev *ts, int *arrive, int fallback_tok,
-                    float *mean_buf, const WmStopDev *stop, const WmXDev *xd, const int *off) {
+                    int n_prompt, int *result, int arg_first, int n_ctx, const WmEmbedDev &e, const WmTsDev &ts, int *arrive,
+                    int fallback_tok, const WmStopDev &stop, const WmXDev &xd, const int *off) {
     WmProfScope ps(&ctx->prof, "argmax_embed", ctx->stream);
-    WmTsDev t;
-    memset(&t, 0, sizeof(t));
-    if (ts) t = *ts;
-    WmStopDev sp;
-    memset(&sp, 0, sizeof(sp));
-    if (stop) sp = *stop;
     // Rows per workgroup.  A row's 3 242 keys (26 KB) are what the kernel pulls, and ONE CU pulls ~25 GB/s: a workgroup per
     // row (all 16 waves on its keys, one trip) instead of a workgroup per 16 rows -- in situ at 56 rows 37.5 -> 23.2 us,
     // driver command +0.7 %, tiny.en x 8 -1.6 % per position (profiles/r05_latency_probe.txt, run Q).  With early stop on,
     // several workgroups cost two agent-scope fences for the live list, so a group of <= 16 rows stays on one workgroup there.
-    int rpw = (arrive && (B > 16 || !sp.done)) ? 1 : 16;
+    int rpw = (arrive && (B > 16 || !stop.done)) ? 1 : 16;
     if (arrive && g_wm_tuning.argmax_rows_per_wg >= 1 && g_wm_tuning.argmax_rows_per_wg <= 16) rpw = g_wm_tuning.argmax_rows_per_wg;   // (probes)
     const int grid = arrive ? (B + rpw - 1) / rpw : 1;
     WM_REQUIRE(grid == 1 || B <= rpw * grid, WM_ERR_INVALID, "argmax_embed: bad grid");
     WM_REQUIRE(arrive || B <= 16, WM_ERR_INVALID, "argmax_embed: more than 16 rows need the arrival counter");
-    if (xd && xd->par) {
+    if (xd.par) {
         WM_REQUIRE(pos_ptr != nullptr, WM_ERR_INVALID, "argmax_embed: the extended decode needs the device position");
         argmax_embed_x_kernel<<<grid, 1024, 0, ctx->stream>>>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first,
-                                                              emb, pemb, d, n_ctx, x, xb, stats_out, t, arrive, fallback_tok,
-                                                              mean_buf, sp, rpw, *xd, off);
+                                                              e.emb, e.pemb, e.d, n_ctx, e.x, e.xb, e.stats_out, ts, arrive,
+                                                              fallback_tok, e.mean_buf, stop, rpw, xd, off);
     } else {
         argmax_embed_kernel<<<grid, 1024, 0, ctx->stream>>>(tilemax, n_tiles, B, seq, pos_ptr, n_prompt, result, arg_first,
-                                                            emb, pemb, d, n_ctx, x, xb, stats_out, t, arrive, fallback_tok,
-                                                            mean_buf, sp, rpw, off);
+                                                            e.emb, e.pemb, e.d, n_ctx, e.x, e.xb, e.stats_out, ts, arrive,
+                                                            fallback_tok, e.mean_buf, stop, rpw, off);
     }
     WM_HIP(hipGetLastError());
     return WM_OK;

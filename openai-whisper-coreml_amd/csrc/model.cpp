@@ -128,6 +128,10 @@ WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode) {
     return t;
 }
 
+WmEmbedDev wm_model_embed_dev(const WmModel *m) {
+    return WmEmbedDev{m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dx, m->dxb, m->dstats, m->dmean};
+}
+
 WmXDev wm_model_x_dev(const WmModel *m, const WmDecodeMode &mode) {
     WmXDev t;
     memset(&t, 0, sizeof(t));
@@ -208,8 +212,7 @@ int wm_model_beam_close(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mo
     const WmRepDev rp = wm_model_rep_dev(m, mode);
     WM_TRY(wm_beam_topk(ctx, m->dlogits, m->vpad, D.n_vocab, m->dargmax, B, ts, xd, mode.mask ? m->dmask : nullptr, m->vpad / 32,
                         n_prompt, m->dpos, bm, rp.par ? rp.ban : nullptr, rp.words));
-    WM_TRY(wm_beam_select_step(ctx, B, m->dseq, m->dpos, n_prompt, m->tok_emb, m->dec_pos, D.n_text_state, m->dx, m->dxb, m->dstats,
-                               m->dmean, ts, sp, xd, mode.off ? m->doff : nullptr, bm));
+    WM_TRY(wm_beam_select_step(ctx, B, m->dseq, m->dpos, n_prompt, wm_model_embed_dev(m), ts, sp, xd, mode.off ? m->doff : nullptr, bm));
     return wm_beam_reorder(ctx, m->skv, D.n_text_layer * 2, B, D.n_text_head, D.n_text_ctx, m->dpos, n_prompt, m->dseq,
                            m->dx_logprob, bm);
 }
@@ -1004,8 +1007,7 @@ static int panel_check(wm_ctx *ctx, int G, int c0, int C, int w) {
 int wm_model_panel_embed(wm_ctx *ctx, int G, int c0, int C, int w) {
     WM_TRY(panel_check(ctx, G, c0, C, w));
     WmModel *m = ctx->model;
-    return wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, 0, C, w, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dims.n_text_ctx,
-                              m->dx, m->dxb, m->dstats, m->dmean);
+    return wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, 0, C, w, m->dims.n_text_ctx, wm_model_embed_dev(m));
 }
 
 int wm_model_panel_step(wm_ctx *ctx, int G, int c0, int C, int w, bool want_logits, const WmAlignCap *cap) {
@@ -1025,8 +1027,7 @@ int wm_model_panel_advance(wm_ctx *ctx, int G, int c0, int C, int w, int w_next)
     WM_TRY(panel_check(ctx, G, c0, C, w));
     WmModel *m = ctx->model;
     if (w_next > 0)   // the next panel's embedding reads the position BEFORE it advances (stream order)
-        WM_TRY(wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, w, C, w_next, m->tok_emb, m->dec_pos, m->dims.n_text_state,
-                                  m->dims.n_text_ctx, m->dx, m->dxb, m->dstats, m->dmean));
+        WM_TRY(wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, w, C, w_next, m->dims.n_text_ctx, wm_model_embed_dev(m)));
     return wm_dec_pos_add(ctx, m->dpos, w);
 }
 
@@ -1060,17 +1061,14 @@ int wm_model_spec_dev(wm_ctx *ctx, wm_ctx *draft, int max_new, WmSpecDev *out, i
 
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
-    return wm_dec_embed(ctx, m->dseq, m->dpos, B, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dx, m->dxb, m->dstats, m->dmean,
-                        mode.off ? m->doff : nullptr);
+    return wm_dec_embed(ctx, m->dseq, m->dpos, B, wm_model_embed_dev(m), mode.off ? m->doff : nullptr);
 }
 
 int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
-    const WmTsDev t = wm_model_ts_dev(m);
-    const WmStopDev sp = wm_model_stop_dev(m, mode);
-    const WmXDev xd = wm_model_x_dev(m, mode);
-    return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, write_seq ? m->dseq : nullptr, m->dpos, n_prompt, result,
-                           arg_first, m->tok_emb, m->dec_pos, m->dims.n_text_state, m->dims.n_text_ctx, m->dx, m->dxb,
-                           m->dstats, mode.ts ? &t : nullptr, m->darrive, mode.ts ? m->ts_eot : arg_first, m->dmean,
-                           mode.stop ? &sp : nullptr, mode.x ? &xd : nullptr, mode.off ? m->doff : nullptr);
+    // (the device views of a mode that is off are empty: wm_model_stop_dev, wm_model_x_dev)
+    return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, write_seq ? m->dseq : nullptr, m->dpos, n_prompt, result, arg_first,
+                           m->dims.n_text_ctx, wm_model_embed_dev(m), mode.ts ? wm_model_ts_dev(m) : WmTsDev{}, m->darrive,
+                           mode.ts ? m->ts_eot : arg_first, wm_model_stop_dev(m, mode), wm_model_x_dev(m, mode),
+                           mode.off ? m->doff : nullptr);
 }

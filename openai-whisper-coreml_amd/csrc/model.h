@@ -180,6 +180,18 @@ struct WmStopDev {
     int eot, pad_tok;
 };
 
+// Where an embedding goes: the tables and the residual-stream target of the launches that embed a position (wm_dec_embed,
+// wm_dec_embed_panel, and the closes wm_argmax_embed and wm_beam_select_step).  x == null (WmEmbedDev{}): a close embeds nothing.
+struct WmEmbedDev {
+    const bf16_t *emb;   // token embedding [n_vocab][d] bf16, WL_TILED
+    const float *pemb;   // positional embedding [n_ctx][d]
+    int d;
+    float *x;            // [rows][d] f32 residual stream
+    bf16_t *xb;          // its mean-centred bf16 copy, WL_TILED
+    float *stats_out;    // LayerNorm partial statistics the next layer-0 GEMV expects (nullable)
+    float *mean_buf;     // [rows] row means (nullable)
+};
+
 // Beam search (wm_transcribe_mel_beam, beam.hip).  A beam group is a candidate group (rows = windows x N, row c * N + k is beam
 // k of window c) whose rows are re-parented after every generated token.  What changes from call to call lives in device
 // memory (WmBeamPar, the budgets), so the captured positions replay; N and n_prompt are part of the graph key.
@@ -558,6 +570,8 @@ int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *r
                         const WmDecodeMode &mode = WmDecodeMode());
 // the device view of the early-stop state (done == null when mode.stop is false)
 WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode);
+// the embedding tables and the residual-stream target of the context's decoder
+WmEmbedDev wm_model_embed_dev(const WmModel *m);
 // beam search: the device view of the group's beam state (allocating it on first use), its initial state for `rows` rows in
 // `windows` windows (par and budgets [windows] are host memory that outlives the upload), and the close of a generating
 // position: per-row lists, per-window selection + next embedding + position advance, re-parenting of the caches
@@ -681,13 +695,12 @@ int wm_ln_fold(wm_ctx *ctx, const bf16_t *W, const float *g, const float *beta, 
 // x[b] = token_embedding[seq[*pos_ptr][b]] + positional_embedding[*pos_ptr]
 // off (device [B], nullable: all 0): the row offsets of a ragged decode group -- row b's positional row is
 // max(*pos_ptr - off[b], 0); the same argument of wm_argmax_embed, and of wm_dec_self_attention (keys [min(off[b], pos), pos])
-int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const bf16_t *emb, const float *pemb,
-                 int d, float *x, bf16_t *xb, float *stats_out, float *mean_buf /*nullable*/, const int *off = nullptr);
+int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const WmEmbedDev &e, const int *off);
 // Panel embedding: row c * w + s (c < C, s < w) = token seq[(*pos_ptr + s) * seq_stride + c] at positional row *pos_ptr + s.
 // Position 0 is embedded with wm_dec_embed's four-wave sums, every later one with the closing kernels' embed_row: the bits of
 // the step path's first embedding and of its closes.  pos_add: added to *pos_ptr (the embedding of the NEXT panel).
-int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, const bf16_t *emb,
-                       const float *pemb, int d, int n_ctx, float *x, bf16_t *xb, float *stats_out, float *mean_buf);
+int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, int n_ctx,
+                       const WmEmbedDev &e);
 // *pos_ptr += add (one thread)
 int wm_dec_pos_add(wm_ctx *ctx, int *pos_ptr, int add);
 // Single-query attention over a K/V cache [B][H][T_stride][64] -> bf16 head outputs att[B][H*64] in WL_TILED order.
@@ -731,14 +744,13 @@ int wm_dec_self_attention_panel(wm_ctx *ctx, const DecAttnArgs &t);
 // Close a decode step (one workgroup): reduce the per-tile packed maxima of a DE_LOGITS launch;
 // chosen token of row b -> seq[(*pos_ptr + 1) * B + b] when that position is >= n_prompt;
 // (token - arg_first) -> result[b]; embed the tokens of position *pos_ptr + 1 into x (+ LayerNorm
-// partial statistics) when x != null; then *pos_ptr += 1.  seq / pos_ptr / result / x may be null.
+// partial statistics) when e.x != null; then *pos_ptr += 1.  seq / pos_ptr / result / e.x may be null.
 // arrive: zero-initialised device counter, required above 16 rows (one workgroup per 16 rows; the last one to arrive
-// advances the position).  fallback_tok: the token taken when nothing is admissible (all suppressed / NaN logits).
+// advances the position; null: one workgroup).  fallback_tok: the token taken when nothing is admissible (all suppressed /
+// NaN logits).  ts / stop / xd: an empty struct (WmTsDev{} ...) is "off"; off: see wm_dec_embed.
 int wm_argmax_embed(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, int B, int *seq, int *pos_ptr,
-                    int n_prompt, int *result, int arg_first, const bf16_t *emb, const float *pemb, int d, int n_ctx,
-                    float *x, bf16_t *xb, float *stats_out, const WmTsDev *ts = nullptr, int *arrive = nullptr,
-                    int fallback_tok = 0, float *mean_buf = nullptr, const WmStopDev *stop = nullptr,
-                    const WmXDev *xd = nullptr, const int *off = nullptr);
+                    int n_prompt, int *result, int arg_first, int n_ctx, const WmEmbedDev &e, const WmTsDev &ts, int *arrive,
+                    int fallback_tok, const WmStopDev &stop, const WmXDev &xd, const int *off);
 // Gumbel noise g(n) of ids n0 .. n0 + count - 1 as the DE_LOGITS_X epilogue computes it (philox.h), into device memory
 int wm_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi, int n0, int count, float *out);
 // start of a decode with early stop: no row done, every row live
@@ -758,9 +770,8 @@ int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const 
                  const WmBeamDev &bm, const unsigned *ban = nullptr, int ban_words = 0);
 // Per window the selection (beam.h), finished records, the rows' new tokens / sums / sources / timestamp-rule state, the
 // early-stop flags and live list, the embedding of the next position and *pos_ptr += 1 (one workgroup).
-int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const bf16_t *emb, const float *pemb, int d,
-                        float *x, bf16_t *xb, float *stats_out, float *mean_buf, const WmTsDev &ts, const WmStopDev &stop,
-                        const WmXDev &xd, const int *off, const WmBeamDev &bm);
+int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const WmEmbedDev &e, const WmTsDev &ts,
+                        const WmStopDev &stop, const WmXDev &xd, const int *off, const WmBeamDev &bm);
 // Re-parent what follows a beam, by bm.src within each window, in place: rows [0, *pos_ptr - 1] of every layer's and head's
 // self-attention K/V (skv [L2][rows][H][T][64]) and the rows' token / log-prob histories.  Call after wm_beam_select_step.
 int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, const int *pos_ptr, int n_prompt, int *seq,

@@ -401,8 +401,9 @@ static int detect_language_impl(wm_ctx *ctx, const float *xa, int B, int32_t sot
     WM_TRY(wm_model_embed_first(ctx, B));
     auto step = [&]() -> int {
         WM_TRY(wm_model_decode_step(ctx, B, probs != nullptr, lang_first, lang_last));     // :36-37
-        return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, nullptr, nullptr, 0, m->dresult, lang_first, nullptr,
-                               nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, m->darrive, lang_first);  // :38
+        // the arg-max alone: no token buffer, no position, nothing embedded, every rule off
+        return wm_argmax_embed(ctx, m->dargmax, m->vpad / 16, B, nullptr, nullptr, 0, m->dresult, lang_first, 0, WmEmbedDev{},
+                               WmTsDev{}, m->darrive, lang_first, WmStopDev{}, WmXDev{}, nullptr);  // :38
     };
     if (wm_graphs_off() || ctx->prof.on) {
         WM_TRY(step());

@@ -1,8 +1,9 @@
 // spec.hip -- the kernels of a speculative decode round (wm_transcribe_mel_speculative) around the
 // target's verify step: the draft's adoption of the first token, the staging of a round's proposals (with the replay of the
 // timestamp rules along them), the close of the verify step's rows (accept) and the group's lockstep cut (commit).
-// A row's close is the arg-max close of dec_kernels.hip argmax_embed_body<true>, from the same pieces of dec_close.h in the same
-// order, by ONE wave per row: winner, tie order, forced timestamps and log-prob are the plain step's.
+// A row's close is the arg-max close of dec_kernels.hip argmax_embed_body<true>: the same calls into dec_close.h (segments,
+// totals, row_choose, row_logprob), by ONE wave per row, so winner, tie order, forced timestamps and log-prob are the plain
+// step's; the kernel itself holds only its tile-key maximum and the window's acceptance count.
 #include "dec_close.h"
 #include "spec_round.h"
 
@@ -77,32 +78,12 @@ __global__ __launch_bounds__(512) void spec_accept_kernel(const unsigned long lo
     __syncthreads();   // lane 0 wrote the row's 16 segments, lanes 0 .. 15 read them: the barrier argmax_embed_body has here
     if (s < w) {   // wave-uniform
         const int b = c * w + s;
-        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f}, lts{-1e30f, 0.f};
-        bool forced = false;
+        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f};
         lse_row_total(seg_s[s], lane, lt, la);
-        if (ts.rng) {
-            unsigned long long kts;
-            float M, S;
-            ts_row_merge(ts, b, n_tiles, lane, kts, M, S);
-            const float text_best = key ? lt.m : -1e30f;
-            const float lse = S > 0.f ? M + __logf(S) : -1e30f;
-            lts = Lse{M, S};
-            forced = kts != 0ull && (key == 0ull || lse > text_best);
-            if (forced) key = kts;
-            else key = kts > key ? kts : key;
-        }
+        const RowChoice ch = row_choose(ts, b, n_tiles, lane, key, lt.m);
         if (lane == 0) {
-            const int tok = key ? argmax_key_index(key) : fallback_tok;
-            Lse al = lt;
-            if (forced) al = lts;
-            else if (ts.rng) al = lse_merge(lt, lts);
-            float lp = -INFINITY;
-            if (key) {
-                const int side = (ts.rng && tok >= ts.ts_begin) ? 1 : 0;
-                lp = xd.win[((long)b * n_tiles + (tok >> 4)) * 2 + side] - (al.m + __logf(al.s));
-            }
-            tok_s[s] = tok;
-            lp_s[s] = lp;
+            tok_s[s] = ch.key ? argmax_key_index(ch.key) : fallback_tok;
+            lp_s[s] = row_logprob(ts, xd, b, n_tiles, ch, lt);
         }
     }
     __syncthreads();

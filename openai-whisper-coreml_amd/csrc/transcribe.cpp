@@ -1087,8 +1087,7 @@ int spec_group(wm_ctx *ctx, const SpecCall &sc, const TxCall &call, const TxCfg 
     const WmStopDev stop = wm_model_stop_dev(m, tj.mode);
     const int fallback = tj.mode.ts ? m->ts_eot : 0;
     auto draft_embed = [&]() {   // the draft's next step starts from the token the commit left at its position
-        return wm_dec_embed_panel(dc, dm->dseq, G, dm->dpos, 0, G, 1, dm->tok_emb, dm->dec_pos, dm->dims.n_text_state, n_ctx, dm->dx,
-                                  dm->dxb, dm->dstats, dm->dmean);
+        return wm_dec_embed_panel(dc, dm->dseq, G, dm->dpos, 0, G, 1, n_ctx, wm_model_embed_dev(dm));
     };
     const int last = P + max_new - 2;   // the last position a row may have: its output is generated token max_new - 1
     int rounds = 0, seen = 0, bound = P;
@@ -1119,8 +1118,7 @@ int spec_group(wm_ctx *ctx, const SpecCall &sc, const TxCall &call, const TxCfg 
         WM_HIP(hipStreamWaitEvent(ctx->stream, x_ev[0], 0));
         // VERIFY: the proposals behind the last token, one panel step of G x w rows, then accept + commit
         WM_TRY(wm_spec_stage(ctx, sp, G, w, P, n_ctx));
-        WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, w, m->tok_emb, m->dec_pos, m->dims.n_text_state, n_ctx, m->dx, m->dxb,
-                                  m->dstats, m->dmean));
+        WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, w, n_ctx, wm_model_embed_dev(m)));
         WM_TRY(wm_model_spec_panel_step(ctx, G, w, tj.mode, P));
         WM_TRY(wm_spec_accept(ctx, m->dargmax, m->vpad / 16, sp, xd, stop, G, w, P, n_ctx, fallback));
         const int slot = rounds % WM_NLIVE_RING;
