@@ -275,6 +275,49 @@ __device__ __forceinline__ void quad_words(const wm_philox4 &w, int k, unsigned 
     out = (k & 2) ? hi : lo;
 }
 
+// ---- the pieces of the logits epilogues (DE_LOGITS*), each stated ONCE.  The 16 lanes that share kq hold the 16 ids of the
+// tile for one batch row; their butterflies walk q = 1, 2, 4, 8.  (Which arm calls which, and why not all: DESIGN.md section 4.)
+// index of (row b, tile) in the per-tile arrays: tilemax, ts.key_ts, ts.lse, x.txt / x.win / x.all
+__device__ __forceinline__ long tile_index(const DecGemvDev &p, int b, int tile) { return (long)b * p.n_tiles + tile; }
+// id n is not suppressed: bit n of the row's bitmap word -- the second bitmap at mask_first_pos; zero when no filter is set
+__device__ __forceinline__ bool id_allowed(const DecGemvDev &p, int pos, unsigned mword0, unsigned mword1, int n) {
+    const unsigned mw = (pos == p.mask_first_pos) ? mword1 : mword0;
+    return !((mw >> (n & 31)) & 1u);
+}
+// id n against a row's timestamp rules (WmTsDev::rng): allowed text [x, y), allowed timestamps [z, w)
+__device__ __forceinline__ bool in_text_range(const int4 &rng, int n) { return n >= rng.x && n < rng.y; }
+__device__ __forceinline__ bool in_ts_range(const int4 &rng, int n) { return n >= rng.z && n < rng.w; }
+// the tile's (max, sum exp) partial of v over the lanes with `in` set (none: (-1e30, 0))
+__device__ __forceinline__ float2 tile_lse(bool in, float v) {
+    float mx = in ? v : -1e30f;
+#pragma unroll
+    for (int q = 1; q < 16; q <<= 1) mx = fmaxf(mx, __shfl_xor(mx, q));
+    float se = in ? __expf(v - mx) : 0.f;
+#pragma unroll
+    for (int q = 1; q < 16; q <<= 1) se += __shfl_xor(se, q);
+    return make_float2(mx, se);
+}
+// the 16-lane maximum of two keys, each with a value carried beside it (the extended decode: the winners' RAW logits)
+__device__ __forceinline__ void tile_key_max_carry(unsigned long long &kt, float &vt, unsigned long long &ks, float &vs) {
+#pragma unroll
+    for (int q = 1; q < 16; q <<= 1) {
+        const unsigned long long a = __shfl_xor(kt, q), c = __shfl_xor(ks, q);
+        const float av = __shfl_xor(vt, q), cv = __shfl_xor(vs, q);
+        if (a > kt) { kt = a; vt = av; }
+        if (c > ks) { ks = c; vs = cv; }
+    }
+}
+// the tile's timestamp partial: best allowed timestamp and the (max, sum exp) of the allowed timestamps' raw logits (only
+// tiles that reach into the timestamp range carry it)
+__device__ __forceinline__ void store_ts_partial(const DecGemvDev &p, long ti, unsigned long long ks, float2 lse) {
+    p.ts.key_ts[ti] = ks;
+    *(float2 *)(p.ts.lse + ti * 2) = lse;
+}
+// the logits row, when the caller asked for it
+__device__ __forceinline__ void store_logit(const DecGemvDev &p, int b, int n, float v) {
+    if (p.out_f32) p.out_f32[(long)b * p.ldo + n] = v;
+}
+
 // epilogue of one (tile, block) unit by one wave: D col n = lane & 15, rows b = b0 + kq*4 + r
 template <int EPI, bool LN>
 __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const GemvUnitOps<EPI, LN> &o, const f32x4 acc,
@@ -345,67 +388,40 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             // would lose bits), plus the (max, sum exp) partial of the allowed text ids and, at the <|startoftranscript|>
             // position only, the unfiltered one over the whole vocabulary (no_speech_prob).  Wave-uniform branches.
             const WmXPar xp = *p.x.par;
-            const unsigned mw = (pos == p.mask_first_pos) ? mword1 : mword0;
-            const bool ok = bvalid && nvalid && !((mw >> (n & 31)) & 1u) && !(de_has_rep(EPI) && rbanned);
+            const bool ok = bvalid && nvalid && id_allowed(p, pos, mword0, mword1, n) && !(de_has_rep(EPI) && rbanned);
             const bool ts_on = p.ts.rng != nullptr;
-            const bool in_text = ts_on ? (ok && n >= o.trng[r].x && n < o.trng[r].y) : (ok && n >= p.arg_first && n <= p.arg_last);
-            const bool in_ts = ts_on && ok && n >= o.trng[r].z && n < o.trng[r].w;
+            const bool in_text = ts_on ? (ok && in_text_range(o.trng[r], n)) : (ok && n >= p.arg_first && n <= p.arg_last);
+            const bool in_ts = ts_on && ok && in_ts_range(o.trng[r], n);
             const int gi = pos + 1 - xp.n_prompt;
             float sc = v;
             if (xp.sample && gi >= 0) sc = __fmaf_rn(v, xp.inv_T, wm_gumbel_from_bits(draw[r]));
             unsigned long long kt = in_text ? argmax_key(sc, n) : 0ull, ks = in_ts ? argmax_key(sc, n) : 0ull;
             float vt = v, vs = v;
-#pragma unroll
-            for (int q = 1; q < 16; q <<= 1) {
-                const unsigned long long a = __shfl_xor(kt, q), c = __shfl_xor(ks, q);
-                const float av = __shfl_xor(vt, q), cv = __shfl_xor(vs, q);
-                if (a > kt) { kt = a; vt = av; }
-                if (c > ks) { ks = c; vs = cv; }
-            }
-            float mx = in_text ? v : -1e30f;
-#pragma unroll
-            for (int q = 1; q < 16; q <<= 1) mx = fmaxf(mx, __shfl_xor(mx, q));
-            float se = in_text ? __expf(v - mx) : 0.f;
-#pragma unroll
-            for (int q = 1; q < 16; q <<= 1) se += __shfl_xor(se, q);
-            const long ti = (long)b * p.n_tiles + tile;
+            tile_key_max_carry(kt, vt, ks, vs);
+            const float2 lt = tile_lse(in_text, v);
+            const long ti = tile_index(p, b, tile);
             if (bvalid && nrow == 0) {
                 p.tilemax[ti] = kt;
-                *(float2 *)(p.x.txt + ti * 2) = make_float2(mx, se);
+                *(float2 *)(p.x.txt + ti * 2) = lt;
                 *(float2 *)(p.x.win + ti * 2) = make_float2(vt, vs);
             }
             if (ts_on && n0 + 16 > p.ts.ts_begin) {  // wave-uniform: the DE_LOGITS timestamp partial (raw logits)
-                float mt = in_ts ? v : -1e30f;
-#pragma unroll
-                for (int q = 1; q < 16; q <<= 1) mt = fmaxf(mt, __shfl_xor(mt, q));
-                float st2 = in_ts ? __expf(v - mt) : 0.f;
-#pragma unroll
-                for (int q = 1; q < 16; q <<= 1) st2 += __shfl_xor(st2, q);
-                if (bvalid && nrow == 0) {
-                    p.ts.key_ts[ti] = ks;
-                    *(float2 *)(p.ts.lse + ti * 2) = make_float2(mt, st2);
-                }
+                const float2 ls = tile_lse(in_ts, v);
+                if (bvalid && nrow == 0) store_ts_partial(p, ti, ks, ls);
             }
             if (pos == xp.sot_pos) {  // wave-uniform: openai-whisper reads no_speech_prob before any filter
-                const bool any = bvalid && nvalid;
                 const float vn = EPI == DE_LOGITS_XB ? vraw : v;   // (the history is empty here: the penalty has not touched it)
-                float ma = any ? vn : -1e30f;
-#pragma unroll
-                for (int q = 1; q < 16; q <<= 1) ma = fmaxf(ma, __shfl_xor(ma, q));
-                float sa = any ? __expf(vn - ma) : 0.f;
-#pragma unroll
-                for (int q = 1; q < 16; q <<= 1) sa += __shfl_xor(sa, q);
-                if (bvalid && nrow == 0) *(float2 *)(p.x.all + ti * 2) = make_float2(ma, sa);
+                const float2 la = tile_lse(bvalid && nvalid, vn);
+                if (bvalid && nrow == 0) *(float2 *)(p.x.all + ti * 2) = la;
                 if (bvalid && n == xp.ns_tok) p.x.ns_v[b] = vn;
             }
-            if (bvalid && nvalid && p.out_f32) p.out_f32[(long)b * p.ldo + n] = v;
+            if (bvalid && nvalid) store_logit(p, b, n, v);
             continue;
         }
         if (EPI == DE_LOGITS && p.ts.rng) {
             // timestamp rules: best allowed text token, best allowed timestamp, and the (max, sum exp) partial of the
             // allowed timestamps of this tile (only tiles that reach into the timestamp range carry the last two)
-            const unsigned mw = (pos == p.mask_first_pos) ? mword1 : mword0;
-            const bool ok = bvalid && nvalid && !((mw >> (n & 31)) & 1u);
+            const bool ok = bvalid && nvalid && id_allowed(p, pos, mword0, mword1, n);
             const bool in_text = ok && n >= o.trng[r].x && n < o.trng[r].y;
             const bool in_ts = ok && n >= o.trng[r].z && n < o.trng[r].w;
             unsigned long long kt = in_text ? argmax_key(v, n) : 0ull, ks = in_ts ? argmax_key(v, n) : 0ull;
@@ -415,34 +431,28 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
                 kt = a > kt ? a : kt;
                 ks = c > ks ? c : ks;
             }
-            if (bvalid && nrow == 0) p.tilemax[(long)b * p.n_tiles + tile] = kt;
+            if (bvalid && nrow == 0) p.tilemax[tile_index(p, b, tile)] = kt;
             if (n0 + 16 > p.ts.ts_begin) {  // wave-uniform
-                float mx = in_ts ? v : -1e30f;
-#pragma unroll
-                for (int q = 1; q < 16; q <<= 1) mx = fmaxf(mx, __shfl_xor(mx, q));
-                float se = in_ts ? __expf(v - mx) : 0.f;
-#pragma unroll
-                for (int q = 1; q < 16; q <<= 1) se += __shfl_xor(se, q);
+                const float2 ls = tile_lse(in_ts, v);
                 if (bvalid && nrow == 0) {
                     p.ts.key_ts[(long)b * p.n_tiles + tile] = ks;
-                    *(float2 *)(p.ts.lse + ((long)b * p.n_tiles + tile) * 2) = make_float2(mx, se);
+                    *(float2 *)(p.ts.lse + ((long)b * p.n_tiles + tile) * 2) = ls;
                 }
             }
-            if (bvalid && nvalid && p.out_f32) p.out_f32[(long)b * p.ldo + n] = v;
+            if (bvalid && nvalid) store_logit(p, b, n, v);
             continue;
         }
         if (EPI == DE_LOGITS) {
             // arg-max over [arg_first, arg_last], first maximal index wins (Whisper.swift:38)
             unsigned long long key = 0ull;
-            const unsigned mw = (pos == p.mask_first_pos) ? mword1 : mword0;  // zero when no filter is set
-            if (bvalid && nvalid && n >= p.arg_first && n <= p.arg_last && !((mw >> (n & 31)) & 1u)) key = argmax_key(v, n);
+            if (bvalid && nvalid && n >= p.arg_first && n <= p.arg_last && id_allowed(p, pos, mword0, mword1, n)) key = argmax_key(v, n);
 #pragma unroll
             for (int q = 1; q < 16; q <<= 1) {
                 const unsigned long long ok = __shfl_xor(key, q);
                 key = ok > key ? ok : key;
             }
-            if (bvalid && nrow == 0) p.tilemax[(long)b * p.n_tiles + tile] = key;
-            if (bvalid && nvalid && p.out_f32) p.out_f32[(long)b * p.ldo + n] = v;
+            if (bvalid && nrow == 0) p.tilemax[tile_index(p, b, tile)] = key;
+            if (bvalid && nvalid) store_logit(p, b, n, v);
             continue;
         }
         if (EPI == DE_RESID) {
@@ -590,8 +600,8 @@ __global__ __launch_bounds__((LN || SPW == 12 || TN * NBLK > 1 || PPW > 1) ? 512
     GEMV_PIN(p.N); GEMV_PIN(p.ldo);
     if (LN) { GEMV_PIN(p.c1); GEMV_PIN(p.stats_in); GEMV_PIN(p.stats_stride); GEMV_PIN(p.mean_in); GEMV_PIN(p.mean_out); }
     if (EPI == DE_RESID) { GEMV_PIN(p.out_bf16); GEMV_PIN(p.stats_out); GEMV_PIN(p.stats_stride); GEMV_PIN(p.mean_in); }
-    if (EPI == DE_QKV) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); }
-    if (EPI == DE_QKV_P) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); GEMV_PIN(p.panel); }
+    if (EPI == DE_QKV || EPI == DE_QKV_P) { GEMV_PIN(p.kcache); GEMV_PIN(p.vcache); GEMV_PIN(p.n_ctx); GEMV_PIN(p.n_head); }
+    if (EPI == DE_QKV_P) GEMV_PIN(p.panel);
     if (EPI == DE_GELU) GEMV_PIN(p.out_bf16);
     if (de_has_rep(EPI)) { GEMV_PIN(p.rep.par); GEMV_PIN(p.rep.seen); GEMV_PIN(p.rep.ban); GEMV_PIN(p.rep.words); }
     if (EPI == DE_LOGITS_XB) { GEMV_PIN(p.sb.hit); GEMV_PIN(p.sb.woff); GEMV_PIN(p.sb.ltot); GEMV_PIN(p.sb.words); }
@@ -942,6 +952,43 @@ __device__ __forceinline__ void attn_stream_reduce(float &l_run, float (&oa)[8])
     l_run += __shfl_xor(l_run, 32);
 }
 
+// ---- the ends of a stream, each stated once (which of the four attention kernels call which: DESIGN.md section 4)
+// the eight query columns of a lane, scaled: hd^-0.5 (== hd^-0.25 on q and on k)
+__device__ __forceinline__ void attn_scale_query(const float *qv, float (&qe)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qe[i] = qv[i] * 0.125f;
+}
+// a reduced stream's partial (m, l, o[64]) to the 66 floats at `po` (HBM: dec_attn_combine_kernel merges them); row group 0
+// holds it, lane e8 its columns e8 * 8 .. + 7
+__device__ __forceinline__ void attn_store_partial(float *po, int rg, int e8, float m_run, float l_run, const float (&oa)[8]) {
+    if (rg == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) po[2 + e8 * 8 + i] = oa[i];
+        if (e8 == 0) {
+            po[0] = m_run;
+            po[1] = l_run;
+        }
+    }
+}
+// the same partial staged as stream w of the in-workgroup merge: wm[w], wl[w], wo[w][64]
+__device__ __forceinline__ void attn_stage_partial(float *wm, float *wl, float *wo, int w, int rg, int e8, float m_run,
+                                                   float l_run, const float (&oa)[8]) {
+    if (rg == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wo[w * 64 + e8 * 8 + i] = oa[i];
+        if (e8 == 0) {
+            wm[w] = m_run;
+            wl[w] = l_run;
+        }
+    }
+}
+// a workgroup behind the n_wg compute workgroups warms the L2 for the next GEMV's weights (l2_warm_tile); true: this was one
+__device__ __forceinline__ bool attn_warm_up(int n_wg, const char *pf_ptr, long pf_tile_bytes, int nthreads) {
+    if ((int)blockIdx.x < n_wg) return false;
+    l2_warm_tile(pf_ptr, pf_tile_bytes, (int)blockIdx.x - n_wg, nthreads);
+    return true;
+}
+
 // KERNEL ARGUMENTS / FIRST LOADS (round 5).  The round-4 kernel reached its first K/V load after six to seven DEPENDENT
 // memory round trips (three lazy kernarg bursts, *n_live_ptr, *pos_ptr, live_rows[..], the query), each a cache miss on
 // a fresh dispatch: 5.0 us for the ~1 MB self-attention of a batch of 8.  Now (a) the first 15 dwords of the argument
@@ -1005,10 +1052,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     const int d = H * 64;
     const int *n_live_ptr = live_rows ? live_rows + WM_DEC_MAXB : nullptr;
     constexpr bool SELF = NS == 4;  // the causal self-attention: the key count is the device-side position
-    if ((int)blockIdx.x >= n_wg) {  // L2 warm-up workgroup for the next GEMV's weights
-        l2_warm_tile(cold.pf_ptr, cold.pf_tile_bytes, (int)blockIdx.x - n_wg, blockDim.x);
-        return;
-    }
+    if (attn_warm_up(n_wg, cold.pf_ptr, cold.pf_tile_bytes, blockDim.x)) return;
     __shared__ float wm_[NS], wl_[NS];
     __shared__ float wo_[NS][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1139,25 +1183,10 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         }
         attn_stream_reduce(l_run, oa);
         if (nsplit > 1) {  // workgroup-uniform: the stream partials go to HBM, dec_attn_combine_kernel merges them
-            if (rg == 0) {
-                float *po = cold.part + ((long)bh * NS + stream) * 66;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) po[2 + e8 * 8 + i] = oa[i];
-                if (e8 == 0) {
-                    po[0] = m_run;
-                    po[1] = l_run;
-                }
-            }
+            attn_store_partial(cold.part + ((long)bh * NS + stream) * 66, rg, e8, m_run, l_run, oa);
             continue;
         }
-        if (rg == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) wo_[wave][e8 * 8 + i] = oa[i];
-            if (e8 == 0) {
-                wm_[wave] = m_run;
-                wl_[wave] = l_run;
-            }
-        }
+        attn_stage_partial(wm_, wl_, &wo_[0][0], wave, rg, e8, m_run, l_run, oa);
         __syncthreads();
         if (tid < 64)  // head outputs feed the out-projection GEMV: stored in its fragment-tiled A-operand order
             cold.att[wm_tiled_offset((size_t)b, (size_t)(h * 64 + tid), (size_t)d)] = f2bf(attn_merge<NS>(wm_, wl_, &wo_[0][0], 64, tid));
@@ -1171,6 +1200,8 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
 // schedule of THIS loop (packed FMAs across row groups, 196 instructions per block) is the one measured, and the shared
 // block helpers above reproduce it instruction for instruction.  Only the argument list is the new one (hot scalars
 // first, packed, preloaded); the key count of a cross-attention is an argument, so nothing here waits for the position.
+// Of the stream-end helpers above it calls attn_scale_query alone: its warm-up return and its two partial stores stay spelled
+// out because attn_warm_up, attn_store_partial and attn_stage_partial each change this kernel's instructions.
 // (packA / packB / packC: packed by wm_pack_attn_rows / wm_pack_attn_keys, dec_launch.h)
 template <int NS, int U, bool NT, bool DEEP = false>
 __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
@@ -1224,11 +1255,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_xrows_attn_kernel(
         const bf16_t *kb = kc + (long)bh * T_stride * 64 + e8 * 8;
         const bf16_t *vb = vc + (long)bh * T_stride * 64 + e8 * 8;
         float qe[8];
-        {
-            const float *qp = q + (long)b * d + h * 64 + e8 * 8;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) qe[i] = qp[i] * 0.125f;  // hd^-0.5 (== hd^-0.25 on q and on k)
-        }
+        attn_scale_query(q + (long)b * d + h * 64 + e8 * 8, qe);
         float m_run = -1e30f, l_run = 0.f;
         float oa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         auto load_block = [&](int r0, u32x4 (&kv)[U], u32x4 (&vv)[U]) {
@@ -1339,10 +1366,7 @@ __global__ __launch_bounds__(512) void dec_xcand_attn_kernel(
     const int T_stride = (int)(packB & 0xffffu), n_keys = (int)(packB >> 16);
     const int C = (int)(packC & 0xffffu), n_wg = (int)(packC >> 16);
     const int d = H * 64;
-    if ((int)blockIdx.x >= n_wg) {  // L2 warm-up workgroup for the next GEMV's weights
-        l2_warm_tile(pf_ptr, pf_tile_bytes, (int)blockIdx.x - n_wg, blockDim.x);
-        return;
-    }
+    if (attn_warm_up(n_wg, pf_ptr, pf_tile_bytes, blockDim.x)) return;
     __shared__ float wm_[N][NS], wl_[N][NS];
     __shared__ float wo_[N][NS][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1400,11 +1424,7 @@ __global__ __launch_bounds__(512) void dec_xcand_attn_kernel(
                     qe[s][i] = 0.f;
                     oa[s][i] = 0.f;
                 }
-                if ((pm >> s) & 1u) {
-                    const float *qp = q + (long)(c * N + s0 + s) * d + h * 64 + e8 * 8;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) qe[s][i] = qp[i] * 0.125f;  // hd^-0.5 (== hd^-0.25 on q and on k)
-                }
+                if ((pm >> s) & 1u) attn_scale_query(q + (long)(c * N + s0 + s) * d + h * 64 + e8 * 8, qe[s]);
             }
             for (int r0 = 0; r0 < n_keys; r0 += NS * 8 * U) {  // workgroup-uniform trip count
                 u32x4 kv[U], vv[U];
@@ -1418,22 +1438,10 @@ __global__ __launch_bounds__(512) void dec_xcand_attn_kernel(
                 if (!((pm >> s) & 1u)) continue;   // wave-uniform
                 attn_stream_reduce(l_run[s], oa[s]);
                 if (rg != 0) continue;
-                if (flat_wpw > 0) {  // the stream partials go to HBM, dec_attn_combine_kernel merges them
-                    float *po = part + ((long)((c * N + s0 + s) * H + h) * NS + stream) * 66;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) po[2 + e8 * 8 + i] = oa[s][i];
-                    if (e8 == 0) {
-                        po[0] = m_run[s];
-                        po[1] = l_run[s];
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) wo_[s0 + s][wave][e8 * 8 + i] = oa[s][i];
-                    if (e8 == 0) {
-                        wm_[s0 + s][wave] = m_run[s];
-                        wl_[s0 + s][wave] = l_run[s];
-                    }
-                }
+                if (flat_wpw > 0)  // the stream partials go to HBM, dec_attn_combine_kernel merges them
+                    attn_store_partial(part + ((long)((c * N + s0 + s) * H + h) * NS + stream) * 66, rg, e8, m_run[s], l_run[s], oa[s]);
+                else
+                    attn_stage_partial(wm_[s0 + s], wl_[s0 + s], &wo_[s0 + s][0][0], wave, rg, e8, m_run[s], l_run[s], oa[s]);
             }
         }
         if (flat_wpw > 0) continue;
@@ -1489,10 +1497,7 @@ __global__ __launch_bounds__(512) void dec_xattn_fq_kernel(const bf16_t *__restr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rg = lane >> 3, e8 = lane & 7;
     // workgroup -> (head, sequence): residue r = id % 8 is the XCD; the heads r, r + 8, r + 16 live there
-    if ((int)blockIdx.x >= cold.n_wg) {  // L2 warm-up workgroup for the next GEMV's weights
-        l2_warm_tile(cold.pf_ptr, cold.pf_tile_bytes, (int)blockIdx.x - cold.n_wg, 512);
-        return;
-    }
+    if (attn_warm_up(cold.n_wg, cold.pf_ptr, cold.pf_tile_bytes, 512)) return;
     // workgroup -> pair: the head-major pair list (h, b) is cut into 8 equal ranges, one per XCD (id % 8, observed
     // placement): every XCD streams the same number of caches and hosts 2 - 4 heads' weight slices
     const int per = (H * B + 7) >> 3;
@@ -1566,8 +1571,7 @@ __global__ __launch_bounds__(512) void dec_xattn_fq_kernel(const bf16_t *__restr
     }
     __syncthreads();
     float qe[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qe[i] = q_lds[e8 * 8 + i] * 0.125f;  // hd^-0.5 (== hd^-0.25 on q and on k)
+    attn_scale_query(q_lds + e8 * 8, qe);
     // ---- the stream, block by block: the shared block arithmetic (attn_block)
     float m_run = -1e30f, l_run = 0.f;
     float oa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1584,14 +1588,7 @@ __global__ __launch_bounds__(512) void dec_xattn_fq_kernel(const bf16_t *__restr
     attn_stream_reduce(l_run, oa);
     float *wm_ = red, *wl_ = red + NS, *wo_ = red + 2 * NS;  // (the split-K partials are dead: both barriers passed)
     __syncthreads();
-    if (rg == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wo_[wave * 64 + e8 * 8 + i] = oa[i];
-        if (e8 == 0) {
-            wm_[wave] = m_run;
-            wl_[wave] = l_run;
-        }
-    }
+    attn_stage_partial(wm_, wl_, wo_, wave, rg, e8, m_run, l_run, oa);
     __syncthreads();
     if (tid < 64)
         cold.att[wm_tiled_offset((size_t)b, (size_t)(h * 64 + tid), (size_t)(H * 64))] = f2bf(attn_merge<NS>(wm_, wl_, wo_, 64, tid));
