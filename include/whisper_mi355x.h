@@ -568,6 +568,26 @@ WM_API int wm_set_alignment_heads(wm_ctx *ctx, const int32_t *layers, const int3
 #define WM_MAX_TEACHER_PANEL 8   /* = WM_MAX_BEST_OF: the widths the shared cross-attention read is built for */
 WM_API int wm_set_teacher_panel(wm_ctx *ctx, int width);
 
+/* PROMPT PANELS: positions per decoder step over the PROMPT of a transcribe call (the previous text of a conditioned long-form
+ * run above all).  A decode group steps through its prompt one position per step, each with the full logits product, although
+ * only the last positions' logits are read.  With width w > 1 the positions [0, P0) in front of the first one the call reads
+ * run as teacher-forced panel steps instead -- w consecutive positions of every row per step, the decoder weights streamed
+ * once and a window's cross-attention K/V read once per step, NO logits product and no close -- and the group's ordinary steps
+ * begin at P0:
+ *   P0 = the <|startoftranscript|> position (opts->sot_index; a ragged call: prompt_len - sot_tail of the group's longest
+ *        prompt) when the call computes no_speech_prob, else the prompt's last position P - 1; an aligned call caps it at its
+ *        first captured position (<|startoftranscript|>).  A ragged group's rows are right-aligned as always; P is its longest.
+ *   width : 1 .. WM_MAX_TEACHER_PANEL; 1 (the default) enqueues exactly the launches a call always enqueued, and so does any
+ *           width for a group with P0 < 2.  Groups of more rows than 128 / w are cut like the teacher-forced passes.
+ * A LAUNCH POLICY, NOT A NUMERICS SWITCH: tokens, lengths, token log-probs, no_speech_prob and start frames are bit-identical
+ * for every width.  TAKING PART: the plain groups of wm_transcribe_greedy, wm_transcribe, wm_transcribe_mel,
+ * wm_transcribe_mel_ragged, wm_transcribe_windows, wm_transcribe_mel_aligned and wm_transcribe_windows_aligned, under explicit
+ * lanes and sub-chip parts too.  IGNORING THE WIDTH (they step through their prompts as always, and do not reject the
+ * setting): the best-of and beam-search entries, both models of wm_transcribe_mel_speculative, the all-f32 debug path.  The
+ * panel steps run eagerly, not from captured graphs; no graph is dropped by this call.  WM_ERR_INVALID: width outside the
+ * range.  Same inheritance as wm_set_suppress. */
+WM_API int wm_set_prompt_panel(wm_ctx *ctx, int width);
+
 /* SPECULATIVE DECODING: wm_transcribe_mel on `ctx` (the target) whose tokens a small DRAFT model proposes.  Per round the draft
  * proposes up to draft_len tokens with plain greedy steps, the target checks all of them in ONE panel step (up to draft_len + 1
  * consecutive positions of every window: the weights streamed once, a window's cross-attention K/V read once) and keeps the

@@ -224,6 +224,29 @@ WM_API int wmdbg_dec_qkv_panel(wm_ctx *ctx, const float *x, const float *ln_g, c
 WM_API int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
                                  int stride, int c0, int C, int w, int pos, int by_steps, float *x, float *xb, float *stats,
                                  float *mean);
+/* ---- prompt panels (wm_set_prompt_panel): the panel launches of a RAGGED group, and the plan ---- */
+/* wmdbg_dec_self_attention_panel with the windows' offsets off i32 [C], each in [0, T): row (c, s) is group position
+ * p = pos + s of window c and attends to the rows [min(off[c], p), p] of entry c -- the bits of wmdbg_dec_self_attention_off at
+ * position p.  A row with p < off[c] has not started: its output is finite, nothing more.  Cache rows outside a row's range may
+ * hold anything, NaN included. */
+WM_API int wmdbg_dec_self_attention_panel_off(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int w, int H,
+                                              int T, int pos, const int32_t *off, int out_rows, float *out);
+/* wmdbg_dec_embed_panel with the offsets off i32 [C] of the panel's windows, each in [0, n_ctx): the positional row of row
+ * (c, s) is max(pos + s - off[c], 0).  by_steps != 0: the step path's launches with the same offsets. */
+WM_API int wmdbg_dec_embed_panel_off(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
+                                     int stride, int c0, int C, int w, int pos, const int32_t *off, int by_steps, float *x, float *xb,
+                                     float *stats, float *mean);
+/* The prompt-panel plan of a plain decode group (host only, tx_plan.cpp wm_prompt_panel_plan): G rows (1 .. 128), the width
+ * (1 .. 8), P prompt positions (a ragged group: its longest prompt), sot_pos = the <|startoftranscript|> position when
+ * no_speech_prob is computed (else -1), acap_base = an aligned group's first captured position (else -1); both < P.
+ * out i32 [5] = P0 (the group's first ordinary step), C (windows per slice), w' (positions per panel), slices, panel steps per
+ * slice.  No prefill (width 1, or P0 < 2): C = w' = slices = steps = 0.  _batch: n cases, in i32 [n][5] in the argument order,
+ * out i32 [n][5]. */
+WM_API int wmdbg_prompt_panel_plan(int G, int width, int P, int sot_pos, int acap_base, int32_t *out);
+WM_API int wmdbg_prompt_panel_plan_batch(int n, const int32_t *in, int32_t *out);
+/* What the context's last decode-group prefill enqueued as prompt panels: out i32 [3] = P0, slices, panel steps (all slices).
+ * All 0 when that group ran none (width 1, P0 < 2, a candidate / beam / speculative group). */
+WM_API int wmdbg_last_prompt_prefill(wm_ctx *ctx, int32_t *out);
 /* The query capture of an alignment layer in a panel step: dq f32 [C * w][d], the layer's n_heads heads into slots slot0 .. of
  * cap f32 [C][Tq][J][64], pre-filled with the NaN bits WMDBG_SENTINEL_F32 (rows at positions >= Tq are not captured).
  * by_steps != 0: w step launches over the C windows instead. */

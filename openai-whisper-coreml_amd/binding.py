@@ -932,6 +932,10 @@ class _LongOptions(types.SimpleNamespace):
         if self.teacher_panel is not None:
             if isinstance(self.teacher_panel, bool) or int(self.teacher_panel) != self.teacher_panel or not 1 <= self.teacher_panel <= MAX_TEACHER_PANEL:
                 raise ValueError("teacher_panel: None or a width 1 .. %d" % MAX_TEACHER_PANEL)
+        if self.prompt_panel is not None:   # 21.
+            if isinstance(self.prompt_panel, bool) or not isinstance(self.prompt_panel, (int, np.integer)) or not 1 <= self.prompt_panel <= MAX_TEACHER_PANEL:
+                raise ValueError("prompt_panel: None or a width 1 .. %d" % MAX_TEACHER_PANEL)
+        self.prompt_panel_pending = self.prompt_panel is not None   # set on the context in front of the first decode call
         if self.draft is None:
             if self.draft_len is not None:
                 raise ValueError("draft_len needs draft")
@@ -1266,7 +1270,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
-                    boost_phrases=None, phrase_boost=None, draft=None, draft_len=None):
+                    boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1402,6 +1406,13 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        of both are the caller's.  ValueError before any library call: with condition_on_previous_text=True, best_of,
        beam_size, word_timestamps='decode*', reuse_encoder, repetition_penalty / no_repeat_ngram_size, a sequence bias, or
        draft_len without draft.  With draft None the function makes exactly the calls it made before the argument existed.
+    21. prompt_panel (None; 1 .. 8): Context.set_prompt_panel(prompt_panel) is called ONCE, in front of the first decode call:
+       from then on a decode group steps through the prompt positions whose logits nobody reads that many at a time, without
+       the logits product (wm_set_prompt_panel: a launch policy -- every segment is the same bit for bit).  What it is for is
+       condition_on_previous_text, whose prompts carry up to n_text_ctx / 2 - 1 tokens of previous text.  The width is not
+       restored afterwards.  Best-of, beam-search and speculative steps ignore it.  ValueError before any library call for
+       anything but None or an integer 1 .. 8.  With None the function makes exactly the calls it made before the argument
+       existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1447,6 +1458,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             prompts = [u.prompt(o) for u in live]
             # (9. reuse_encoder: the round's windows are encoded once here, for every fallback step and the word step)
             source = _RoundRows(o, d_mel, live, sizes, prompts, [u.sample_id() for u in live])
+            if o.prompt_panel_pending:   # 21.
+                ctx.set_prompt_panel(int(prompt_panel))
+                o.prompt_panel_pending = False
             res = fallback_decode(source.decode, len(live), o.vocab_size, o.max_new, eot, temperatures, compression_ratio_threshold,
                                   logprob_threshold, no_speech_threshold, vocab, seed)
             kept = []   # word_timestamps: (row of the round, segments, next seek, single_timestamp_ending) of every kept window
@@ -1843,6 +1857,16 @@ class Context:
         self.lib.wm_set_timestamp_rules.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
                                                     ctypes.c_int32]
         _check(self.lib, self.lib.wm_set_timestamp_rules(self.handle, 1 if enable else 0, timestamp_begin, eot, max_initial))
+
+    def set_prompt_panel(self, n):
+        """wm_set_prompt_panel: positions per decoder step (1 .. MAX_TEACHER_PANEL; 1 = the default) over the prompt positions of
+        a transcribe call whose logits nobody reads -- cache-only panel steps, no logits product.  A launch policy: every
+        output of every entry is bit-identical for every width.  The plain groups of transcribe_greedy / transcribe /
+        transcribe_mel (ragged prompts included) / transcribe_windows and their aligned forms take part; best-of, beam-search
+        and speculative calls ignore it.  Inherited by later clones and by the lanes of a call."""
+        self.lib.wm_set_prompt_panel.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.lib.wm_set_prompt_panel.restype = ctypes.c_int
+        _check(self.lib, self.lib.wm_set_prompt_panel(self.handle, int(n)))
 
     def set_teacher_panel(self, n):
         """wm_set_teacher_panel: positions per decoder step (1 .. MAX_TEACHER_PANEL; 1 = the default) of the teacher-forced passes

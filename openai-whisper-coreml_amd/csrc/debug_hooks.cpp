@@ -1359,13 +1359,16 @@ extern "C" int wmdbg_dec_qkv_panel(wm_ctx *ctx, const float *x, const float *ln_
                            mean.data(), Wf.data(), c1.data(), c2.data());
 }
 
-extern "C" int wmdbg_dec_self_attention_panel(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int w, int H,
-                                              int T, int pos, int out_rows, float *out) {
+// (off: null = the uniform panel launch; else the windows' offsets [C] of a ragged group's prompt panel)
+static int dec_self_attention_panel(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int w, int H, int T, int pos,
+                                    const int32_t *off, int out_rows, float *out) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(q && k && v && out, WM_ERR_INVALID, "dec_self_attention_panel: null pointer");
     WM_REQUIRE(C >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C * w <= WM_DEC_MAXB && H >= 1 && T >= 1 && pos >= 0 && pos + w <= T &&
                    out_rows >= C * w && out_rows % 16 == 0,
                WM_ERR_INVALID, "dec_self_attention_panel: bad geometry");
+    for (int c = 0; off && c < C; ++c)
+        WM_REQUIRE(off[c] >= 0 && off[c] < T, WM_ERR_INVALID, "dec_self_attention_panel: off[%d] = %d outside [0, %d)", c, off[c], T);
     const int B = C * w;
     std::vector<bf16_t> k16, v16;
     to_bf16(k, k16, (size_t)C * H * T * 64);
@@ -1383,15 +1386,27 @@ extern "C" int wmdbg_dec_self_attention_panel(wm_ctx *ctx, const float *q, const
     WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
     WM_TRY(pool.get(&dpos, &pos, 4, s));
     WM_TRY(pool.get(&datt, fill.data(), fill.size() * 2, s));
+    const int *doff = nullptr;
+    if (off) WM_TRY(pool.get(&doff, off, (size_t)C * 4, s));
     DecAttnArgs t = {};
-    t.q = dq; t.kc = dk; t.vc = dv; t.att = datt; t.C = C; t.N = w; t.H = H; t.T_stride = T; t.pos_ptr = dpos;
+    t.q = dq; t.kc = dk; t.vc = dv; t.att = datt; t.C = C; t.N = w; t.H = H; t.T_stride = T; t.pos_ptr = dpos; t.off = doff;
     WM_TRY(wm_dec_self_attention_panel(ctx, t));
     return down_tiled_bf16(datt, (size_t)out_rows, dd, out, s);
 }
+extern "C" int wmdbg_dec_self_attention_panel(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int w, int H,
+                                              int T, int pos, int out_rows, float *out) {
+    return dec_self_attention_panel(ctx, q, k, v, C, w, H, T, pos, nullptr, out_rows, out);
+}
+extern "C" int wmdbg_dec_self_attention_panel_off(wm_ctx *ctx, const float *q, const float *k, const float *v, int C, int w, int H,
+                                                  int T, int pos, const int32_t *off, int out_rows, float *out) {
+    WM_REQUIRE(off, WM_ERR_INVALID, "dec_self_attention_panel_off: null offsets");
+    return dec_self_attention_panel(ctx, q, k, v, C, w, H, T, pos, off, out_rows, out);
+}
 
-extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
-                                     int stride, int c0, int C, int w, int pos, int by_steps, float *x, float *xb, float *stats,
-                                     float *mean) {
+// (off: null = the uniform panel; else the offsets [C] of the panel's windows in a ragged group)
+static int dec_embed_panel(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq, int stride,
+                           int c0, int C, int w, int pos, const int32_t *off, int by_steps, float *x, float *xb, float *stats,
+                           float *mean) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(emb && pemb && seq && x && xb && stats && mean, WM_ERR_INVALID, "dec_embed_panel: null pointer");
     WM_REQUIRE(V >= 1 && d >= 64 && d % 64 == 0 && C >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C * w <= WM_DEC_MAXB && c0 >= 0 &&
@@ -1426,8 +1441,13 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
     WM_TRY(pool.get(&dxb, nullptr, (size_t)Bpad * d * 2, s, 0xff));
     WM_TRY(pool.get(&dst, nullptr, n_st * 4, s, 0xff));
     WM_TRY(pool.get(&dmean, nullptr, (size_t)B * 4, s, 0xff));
+    const int *doff = nullptr;
+    if (off) {
+        for (int c = 0; c < C; ++c) WM_REQUIRE(off[c] >= 0 && off[c] < n_ctx, WM_ERR_INVALID, "dec_embed_panel: off[%d] = %d outside [0, %d)", c, off[c], n_ctx);
+        WM_TRY(pool.get(&doff, off, (size_t)C * 4, s));
+    }
     if (!by_steps) {
-        WM_TRY(wm_dec_embed_panel(ctx, dseq + c0, stride, dpos, 0, C, w, n_ctx, WmEmbedDev{de, dp, d, dx, dxb, dst, dmean}));
+        WM_TRY(wm_dec_embed_panel(ctx, dseq + c0, stride, dpos, 0, C, w, n_ctx, WmEmbedDev{de, dp, d, dx, dxb, dst, dmean}, doff));
         WM_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * 4, hipMemcpyDeviceToHost, s));
         WM_HIP(hipMemcpyAsync(hxb.data(), dxb, hxb.size() * 2, hipMemcpyDeviceToHost, s));
         WM_HIP(hipMemcpyAsync(hst.data(), dst, hst.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1456,13 +1476,13 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
             const int p = pos + sp;
             if (p == 0) {
                 WM_HIP(hipMemsetAsync(dpos, 0, 4, s));
-                WM_TRY(wm_dec_embed(ctx, dseq1, dpos, C, e1, nullptr));
+                WM_TRY(wm_dec_embed(ctx, dseq1, dpos, C, e1, doff));
             } else {
                 const int pm = p - 1;
                 WM_HIP(hipMemcpyAsync(dpos, &pm, 4, hipMemcpyHostToDevice, s));
                 WM_HIP(hipStreamSynchronize(s));
                 WM_TRY(wm_argmax_embed(ctx, dtile, n_tiles, C, dseq1, dpos, n_ctx, nullptr, 0, n_ctx, e1, WmTsDev{}, darr, 0, WmStopDev{},
-                                       WmXDev{}, nullptr));
+                                       WmXDev{}, doff));
             }
             WM_HIP(hipMemcpyAsync(x1.data(), dx1, x1.size() * 4, hipMemcpyDeviceToHost, s));
             WM_HIP(hipMemcpyAsync(xb1.data(), dxb1, xb1.size() * 2, hipMemcpyDeviceToHost, s));
@@ -1486,6 +1506,40 @@ extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float 
     for (size_t r = 0; r < (size_t)B; ++r)
         for (int pt = 0; pt < d / 16; ++pt)
             for (int i = 0; i < 2; ++i) stats[(r * (d / 16) + pt) * 2 + i] = hst[stat_at(d, r, pt, i)];
+    return WM_OK;
+}
+extern "C" int wmdbg_dec_embed_panel(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
+                                     int stride, int c0, int C, int w, int pos, int by_steps, float *x, float *xb, float *stats,
+                                     float *mean) {
+    return dec_embed_panel(ctx, emb, pemb, V, d, n_ctx, seq, stride, c0, C, w, pos, nullptr, by_steps, x, xb, stats, mean);
+}
+extern "C" int wmdbg_dec_embed_panel_off(wm_ctx *ctx, const float *emb, const float *pemb, int V, int d, int n_ctx, const int32_t *seq,
+                                         int stride, int c0, int C, int w, int pos, const int32_t *off, int by_steps, float *x,
+                                         float *xb, float *stats, float *mean) {
+    WM_REQUIRE(off, WM_ERR_INVALID, "dec_embed_panel_off: null offsets");
+    return dec_embed_panel(ctx, emb, pemb, V, d, n_ctx, seq, stride, c0, C, w, pos, off, by_steps, x, xb, stats, mean);
+}
+
+// ------------------------------------------------------------------ prompt panels (wm_set_prompt_panel) ----
+extern "C" int wmdbg_prompt_panel_plan(int G, int width, int P, int sot_pos, int acap_base, int32_t *out) {
+    WM_REQUIRE(out && G >= 1 && G <= WM_DEC_MAXB && width >= 1 && width <= WM_MAX_TEACHER_PANEL && P >= 1 && sot_pos >= -1 && sot_pos < P &&
+                   acap_base >= -1 && acap_base < P,
+               WM_ERR_INVALID, "wmdbg_prompt_panel_plan: bad arguments");
+    WmPromptPanelPlan pl;
+    wm_prompt_panel_plan(G, width, P, sot_pos, acap_base, 0, &pl);
+    out[0] = pl.P0; out[1] = pl.C; out[2] = pl.w; out[3] = pl.slices; out[4] = pl.steps;
+    return WM_OK;
+}
+extern "C" int wmdbg_prompt_panel_plan_batch(int n, const int32_t *in, int32_t *out) {
+    WM_REQUIRE(n >= 0 && (n == 0 || (in && out)), WM_ERR_INVALID, "wmdbg_prompt_panel_plan_batch: bad arguments");
+    for (int i = 0; i < n; ++i)
+        WM_TRY(wmdbg_prompt_panel_plan(in[5 * (size_t)i], in[5 * (size_t)i + 1], in[5 * (size_t)i + 2], in[5 * (size_t)i + 3], in[5 * (size_t)i + 4],
+                                       out + 5 * (size_t)i));
+    return WM_OK;
+}
+extern "C" int wmdbg_last_prompt_prefill(wm_ctx *ctx, int32_t *out) {
+    WM_REQUIRE(ctx && ctx->model && out, WM_ERR_INVALID, "wmdbg_last_prompt_prefill: null pointer");
+    for (int i = 0; i < 3; ++i) out[i] = ctx->model->last_prefill[i];
     return WM_OK;
 }
 

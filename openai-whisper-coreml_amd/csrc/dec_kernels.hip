@@ -819,6 +819,25 @@ __global__ __launch_bounds__(256) void dec_embed_panel_kernel(const int *__restr
         embed_row(tok, pos, r, (int)threadIdx.x, emb, pemb, d, x, xb, stats_out, mean_buf);
     }
 }
+// ... of a RAGGED group (wm_set_prompt_panel): window c's prompt starts at group position off[c], so the row's positional row
+// is max(pos - off[c], 0) -- what dec_embed_kernel writes at group position 0 and the closing launch at every later one.
+__global__ __launch_bounds__(256) void dec_embed_panel_off_kernel(const int *__restrict__ seq, int seq_stride,
+                                                                  const int *__restrict__ pos_ptr, int pos_add, int w,
+                                                                  const bf16_t *__restrict__ emb, const float *__restrict__ pemb,
+                                                                  int d, int n_ctx, float *__restrict__ x, bf16_t *__restrict__ xb,
+                                                                  float *__restrict__ stats_out, float *__restrict__ mean_buf,
+                                                                  const int *__restrict__ off) {
+    const int r = blockIdx.x, c = r / w;
+    const int pos = *pos_ptr + pos_add + (r - c * w);
+    if (pos >= n_ctx) return;   // (workgroup-uniform; never taken in a pass cut by the host)
+    const long tok = seq[(long)pos * seq_stride + c];
+    const int prow = max(pos - off[c], 0);
+    if (pos == 0) {             // workgroup-uniform
+        embed_first_row(tok, prow, r, emb, pemb, d, x, xb, stats_out, mean_buf);
+    } else if (threadIdx.x < 64) {
+        embed_row(tok, prow, r, (int)threadIdx.x, emb, pemb, d, x, xb, stats_out, mean_buf);
+    }
+}
 __global__ void dec_pos_add_kernel(int *pos_ptr, int add) { *pos_ptr += add; }
 
 // ------------------------------------------------------------------ single-query attention
@@ -1034,9 +1053,23 @@ struct AttnColdPanel {
     const char *pf_ptr;
     long pf_tile_bytes;
 };
+// PROMPT PANELS (OFF and PANEL, wm_set_prompt_panel): a panel step over the prompt of a RAGGED group.  Row r = c * w + s is group
+// position p = pos + s of window c: its cache entry is window c's, its keys are the cache rows [min(off[c], p), p] -- the base
+// pointers advance by that offset and every row index is relative to it, so the row's bits are those of the OFF kernel at
+// position p.  A row that has not started (p < off[c]) attends to its one current row, as there.  The speculative first block
+// is clamped to the cache entry's last row (off[c] < T_stride, pos + s < T_stride).  An instantiation of its own.
+struct AttnColdOffPanel {
+    const int *off;   // [>= windows of the step]
+    int w;
+    bf16_t *att;
+    float *part;
+    const char *pf_ptr;
+    long pf_tile_bytes;
+};
 template <bool OFF, bool PANEL> struct AttnColdSel { typedef AttnCold type; };
 template <> struct AttnColdSel<true, false> { typedef AttnColdOff type; };
 template <> struct AttnColdSel<false, true> { typedef AttnColdPanel type; };
+template <> struct AttnColdSel<true, true> { typedef AttnColdOffPanel type; };
 // (packA / packB / packC: packed by wm_pack_attn_rows / wm_pack_attn_keys, dec_launch.h)
 template <int NS, int U, bool NT, bool DEEP = false, bool OFF = false, bool PANEL = false>
 __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
@@ -1045,7 +1078,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     unsigned packA /* H | nsplit << 8 | flat_wpw << 16 */, unsigned packB /* T_stride | n_keys_const << 16 */,
     unsigned packC /* n_bh | n_wg << 16 */, typename AttnColdSel<OFF, PANEL>::type cold) {
     static_assert(!OFF || (NS == 4 && !DEEP), "row offsets: the causal self-attention only");
-    static_assert(!PANEL || (NS == 4 && !DEEP && !OFF), "panels: the causal self-attention of a uniform group only");
+    static_assert(!PANEL || (NS == 4 && !DEEP), "panels: the causal self-attention only");
     const int H = (int)(packA & 0xffu), nsplit = (int)((packA >> 8) & 0xffu), flat_wpw = (int)(packA >> 16);
     const int T_stride = (int)(packB & 0xffffu), n_keys_const = (int)(packB >> 16);
     const int n_bh_full = (int)(packC & 0xffffu), n_wg = (int)(packC >> 16);
@@ -1074,7 +1107,8 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
     const int pos_raw = *(pos_ptr ? pos_ptr : dummy);
     const int nl_raw = *(n_live_ptr ? n_live_ptr : dummy);
     int off_raw = 0;
-    if constexpr (OFF) off_raw = cold.off[bh0 / H];
+    if constexpr (OFF && !PANEL) off_raw = cold.off[bh0 / H];
+    if constexpr (OFF && PANEL) off_raw = cold.off[(bh0 / H) / cold.w];   // the first pair's WINDOW
     // Early stop: sequences that have emitted <|endoftext|> (or used up their token budget) leave the decode group.
     // The arg-max kernel keeps a COMPACT list of the live rows; the pairs walked here are (live row, head), dealt to the
     // workgroups exactly like the full set, so the cache of a finished sequence is never read again and the remaining
@@ -1106,7 +1140,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
         const f32x4 q0 = qp[0], q1 = qp[1];
         int ob = 0;       // OFF: first cache row of this pair; row indices from here on are relative to it
         int clamp0 = first ? n_clamp : n_keys - 1 + ps;
-        if constexpr (OFF) {
+        if constexpr (OFF && !PANEL) {
             if (first) {
                 ob = b == bh0 / H ? off_raw : cold.off[b];   // (the position is not known yet: see below)
                 clamp0 = n_clamp - ob;
@@ -1114,6 +1148,19 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
                 ob = cold.off[b];
                 ob = ob < pos_k ? ob : pos_k;
                 clamp0 = pos_k - ob;
+            }
+            kb += (long)ob * 64;
+            vb += (long)ob * 64;
+        }
+        if constexpr (OFF && PANEL) {   // the offset is the WINDOW's, the position the row's own: pos + ps
+            if (first) {
+                ob = b == bh0 / H ? off_raw : cold.off[b / cold.w];
+                clamp0 = n_clamp - ob;
+            } else {
+                const int pk = pos_k + ps;
+                ob = cold.off[b / cold.w];
+                ob = ob < pk ? ob : pk;
+                clamp0 = pk - ob;
             }
             kb += (long)ob * 64;
             vb += (long)ob * 64;
@@ -1138,7 +1185,7 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
             if (pos_ptr) n_keys = pos_v + 1;
             first = false;
             if (pi >= n_bh) break;  // (workgroup- / wave-uniform) the speculative pair is not live
-            if constexpr (OFF) {
+            if constexpr (OFF && !PANEL) {
                 pos_k = n_keys - 1;
                 if (pos_k < ob) {   // (workgroup-uniform) a sequence that has not started: its one key is the current row
                     kb -= (long)(ob - pos_k) * 64;
@@ -1147,10 +1194,21 @@ __global__ __launch_bounds__(DEEP ? 256 : NS * 64) void dec_rows_attn_kernel(
                     load_block(kb, vb, 0, 0, kall[0], vall[0]);
                 }
             }
+            if constexpr (OFF && PANEL) {
+                pos_k = n_keys - 1;   // (the panel's first position; this row's is pos_k + ps)
+                const int pk = pos_k + ps;
+                if (pk < ob) {   // (workgroup-uniform) a row that has not started: its one key is its own current row
+                    kb -= (long)(ob - pk) * 64;
+                    vb -= (long)(ob - pk) * 64;
+                    ob = pk;
+                    load_block(kb, vb, 0, 0, kall[0], vall[0]);
+                }
+            }
         }
         int nk = n_keys;  // keys of this pair
         if constexpr (OFF) nk = pos_k + 1 - ob;
         if constexpr (PANEL) nk = n_keys + ps;
+        if constexpr (OFF && PANEL) nk = pos_k + ps + 1 - ob;
         float qe[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1994,12 +2052,16 @@ int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const W
 }
 
 int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, int n_ctx,
-                       const WmEmbedDev &e) {
+                       const WmEmbedDev &e, const int *off) {
     WM_REQUIRE(w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && C * w <= WM_DEC_MAXB && seq_stride >= C, WM_ERR_INVALID,
                "dec_embed_panel: %d windows x %d positions (stride %d)", C, w, seq_stride);
     WmProfScope ps(&ctx->prof, "dec_embed_panel", ctx->stream);
-    dec_embed_panel_kernel<<<C * w, 256, 0, ctx->stream>>>(seq, seq_stride, pos_ptr, pos_add, w, e.emb, e.pemb, e.d, n_ctx, e.x, e.xb,
-                                                          e.stats_out, e.mean_buf);
+    if (off)   // a ragged group: the windows' offsets
+        dec_embed_panel_off_kernel<<<C * w, 256, 0, ctx->stream>>>(seq, seq_stride, pos_ptr, pos_add, w, e.emb, e.pemb, e.d, n_ctx, e.x,
+                                                                  e.xb, e.stats_out, e.mean_buf, off);
+    else
+        dec_embed_panel_kernel<<<C * w, 256, 0, ctx->stream>>>(seq, seq_stride, pos_ptr, pos_add, w, e.emb, e.pemb, e.d, n_ctx, e.x, e.xb,
+                                                              e.stats_out, e.mean_buf);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }
@@ -2144,9 +2206,15 @@ int wm_dec_self_attention_panel(wm_ctx *ctx, const DecAttnArgs &t) {
     DecAttnPlan pl;
     WM_TRY(wm_plan_self_attention_panel(attn_shape(t), ctx->n_cus, g_wm_tuning, &pl));
     WmProfScope ps(&ctx->prof, "dec_attn_self", ctx->stream);
-    const AttnColdPanel cold = {t.N, t.att, nullptr, (const char *)t.pf.ptr, pl.tile_bytes};
-    dec_rows_attn_kernel<4, 4, false, false, false, true><<<pl.grid_x, 256, 0, ctx->stream>>>(t.q, t.kc, t.vc, t.pos_ptr, nullptr, pl.w.a,
-                                                                                             pl.w.b, pl.w.c, cold);
+    if (pl.variant == DAV_SELF_OFF_PANEL) {   // a ragged group's prompt panel: t.off = the offsets of the step's C windows
+        const AttnColdOffPanel cold_off = {t.off, t.N, t.att, nullptr, (const char *)t.pf.ptr, pl.tile_bytes};
+        dec_rows_attn_kernel<4, 4, false, false, true, true><<<pl.grid_x, 256, 0, ctx->stream>>>(t.q, t.kc, t.vc, t.pos_ptr, nullptr, pl.w.a,
+                                                                                                pl.w.b, pl.w.c, cold_off);
+    } else {
+        const AttnColdPanel cold = {t.N, t.att, nullptr, (const char *)t.pf.ptr, pl.tile_bytes};
+        dec_rows_attn_kernel<4, 4, false, false, false, true><<<pl.grid_x, 256, 0, ctx->stream>>>(t.q, t.kc, t.vc, t.pos_ptr, nullptr, pl.w.a,
+                                                                                                 pl.w.b, pl.w.c, cold);
+    }
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

@@ -269,7 +269,7 @@ int wm_plan_self_attention_panel(const DecAttnShape &s, int n_cus, const WmTunin
     const int B = C * w;
     const bool ok = wm_pack_attn_rows(H, 1, 0, B * H, B * H, &p->w.a, &p->w.c) && wm_pack_attn_keys(s.T_stride, 0, &p->w.b);
     PLAN_REQUIRE(ok, "dec_self_attention_panel: a packed argument does not fit its bits");
-    p->variant = DAV_SELF_PANEL;
+    p->variant = s.has_off ? DAV_SELF_OFF_PANEL : DAV_SELF_PANEL;   // a ragged group's prompt panel: the same launch shape
     p->n_wg = B * H;
     p->warm_tiles = wm_dec_warm_tiles(B, s.has_pf, s.pf_rows, s.pf_k, p->n_wg, t, &p->tile_bytes);
     p->grid_x = p->n_wg + p->warm_tiles;

@@ -90,6 +90,7 @@ enum DecAttnVariant {
     DAV_CAND = 7,         // dec_xcand_attn_kernel<N, NT>, one 8-wave workgroup per pair, persistent
     DAV_CAND_FLAT = 8,    // dec_xcand_attn_kernel<N, NT>, the flat deal
     DAV_FQ = 9,           // dec_xattn_fq_kernel<spw, NT>
+    DAV_SELF_OFF_PANEL = 10,   // dec_rows_attn_kernel<4, 4, false, false, true, true>: a prompt panel of ragged rows
 };
 // the integers of a DecAttnArgs (model.h); which fields a form reads is said at its plan function
 struct DecAttnShape {
@@ -121,7 +122,7 @@ int wm_plan_attention_cand(const DecAttnShape &s, int n_cus, const WmTuning &t, 
 int wm_plan_xattn_fq(const DecAttnShape &s, int n_cus, const WmTuning &t, DecAttnPlan *p);
 // self (wm_dec_self_attention): B, H, T_stride, n_keys, has_pos, has_off, warm-up
 int wm_plan_self_attention(const DecAttnShape &s, int n_cus, const WmTuning &t, DecAttnPlan *p);
-// panel (wm_dec_self_attention_panel): C, N (= the width w), H, T_stride, has_pos, warm-up
+// panel (wm_dec_self_attention_panel): C, N (= the width w), H, T_stride, has_pos, has_off (the windows' offsets), warm-up
 int wm_plan_self_attention_panel(const DecAttnShape &s, int n_cus, const WmTuning &t, DecAttnPlan *p);
 
 // ---------------------------------------------------------------- GEMV plan ----

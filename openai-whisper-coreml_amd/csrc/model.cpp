@@ -3,6 +3,7 @@
 // cross-attention K/V projection, and one KV-cached decoder position
 // (TextDecoder.forward, traced at whisper_to_cml.py:25-43).
 #include "model.h"
+#include "tx_plan.h"   // wm_panel_slices, wm_prompt_panel_plan
 
 #include <math.h>
 #include <cmath>
@@ -492,6 +493,7 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->ts_on = pm->ts_on; m->ts_begin = pm->ts_begin; m->ts_eot = pm->ts_eot; m->ts_max_initial = pm->ts_max_initial;
     m->align_l = pm->align_l; m->align_h = pm->align_h;
     m->teacher_panel = pm->teacher_panel;
+    m->prompt_panel = pm->prompt_panel;
     m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
     if (m->rep_on || pm->sb_on) WM_TRY(alloc_repetition_state(m, child->stream));
     if (pm->sb_on) {   // the parent's device table, as the suppress bitmaps above
@@ -838,15 +840,17 @@ int wm_model_set_pos(wm_ctx *ctx, int pos) {
 
 // grp / c0 (a panel step only, else 0): the step's windows are rows c0 .. of a group of grp windows whose caches are laid out
 // [L][2][grp][H][.][64] -- the per-layer pointers advance by whole windows (wm_model_panel_step)
+// cache_only (a prompt-prefill step, wm_model_prompt_prefill): the layers alone -- no logits product; the one panel step that
+// admits the row offsets of a ragged group (the offsets of the step's windows: m->doff + c0)
 static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first, int arg_last, const WmAlignCap *cap,
-                            const WmDecodeMode &mode, int n_prompt, int grp, int c0) {
+                            const WmDecodeMode &mode, int n_prompt, int grp, int c0, bool cache_only = false) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head, T = D.n_text_ctx, S = 1500;
     const int PW = mode.panel > 1 ? mode.panel : 1;     // panel step: B = Bx windows x PW positions, one self AND one cross cache entry per window
     const int NC = mode.n_cand > 1 ? mode.n_cand : 1;   // candidate group: B = Bx windows x NC rows, one cross cache per window
     // (mode.x without the repetition rules: the verify step of a speculative group, wm_model_spec_panel_step)
-    WM_REQUIRE(PW == 1 || (NC == 1 && !mode.stop && !mode.off && !(mode.x && mode.rep) && B % PW == 0), WM_ERR_STATE,
+    WM_REQUIRE(PW == 1 || (NC == 1 && !mode.stop && (!mode.off || cache_only) && !(mode.x && mode.rep) && B % PW == 0), WM_ERR_STATE,
                "decode step: a panel is a plain teacher-forced step of windows x width rows");
     const int Bx = B / (NC * PW);
     const int Gx = grp > 0 ? grp : Bx;                  // windows per layer of the cross cache
@@ -879,7 +883,7 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
         if (PW > 1) { a.epi = DE_QKV_P; a.panel = PW; }   // row (c, s) appends at position pos + s of window c
         WM_TRY(wm_dec_gemv(ctx, a));
         // 2. causal self-attention over positions 0..pos (a panel row: 0 .. pos + s of its window)
-        t.kc = kc; t.vc = vc; t.T_stride = T; t.n_keys = 0; t.pos_ptr = m->dpos; t.off = mode.off ? m->doff : nullptr;
+        t.kc = kc; t.vc = vc; t.T_stride = T; t.n_keys = 0; t.pos_ptr = m->dpos; t.off = mode.off ? m->doff + c0 : nullptr;
         t.pf = {L.wo, d, d};
         WM_TRY(PW > 1 ? wm_dec_self_attention_panel(ctx, t) : wm_dec_self_attention(ctx, t));
         // 3. out-projection + residual (f32 stream, its bf16 copy, partial statistics)
@@ -935,6 +939,7 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
         if (l + 1 < D.n_text_layer) { a.pf_ptr = m->dec[l + 1].wqkv_f; a.pf_rows = 3 * d; a.pf_k = d; }
         WM_TRY(wm_dec_gemv(ctx, a));
     }
+    if (cache_only) return WM_OK;   // the positions' k / v are in the self-attention cache: nobody reads their logits
     {   // final LayerNorm (folded) + tied-embedding logits + fused per-tile arg-max
         DecGemvArgs a;
         memset(&a, 0, sizeof(a));
@@ -982,18 +987,8 @@ int wm_model_decode_step(wm_ctx *ctx, int B, bool want_logits, int arg_first, in
 // narrowed to 5 positions (46 steps) beats slices of 16 at width 8 (58 steps) by 21 - 26 %; 48 windows -- three slices at width 8
 // (87 steps) beat one panel narrowed to 2 (115 steps) by 14 %.  Results cannot depend on the cut.
 void wm_model_panel_slices(int G, int width, int T, int *C, int *w) {
-    const int wd = width < 1 ? 1 : (width > WM_MAX_TEACHER_PANEL ? WM_MAX_TEACHER_PANEL : width);
-    int best_w = wd, best_steps = 1 << 30;
-    for (int wc = wd; wc >= 1; --wc) {
-        const int cap = WM_DEC_MAXB / wc, steps = ((G + cap - 1) / cap) * ((T + wc - 1) / wc);
-        if (steps < best_steps) { best_steps = steps; best_w = wc; }
-    }
     const int knob = g_wm_tuning.teacher_panel_cut;   // (probes: 1 = one narrowed panel, 2 = slices at the full width; 0: the rule)
-    if (knob == 1 && G > WM_DEC_MAXB / wd) best_w = WM_DEC_MAXB / G;
-    if (knob == 2) best_w = wd;
-    const int cap = WM_DEC_MAXB / best_w, n_slices = (G + cap - 1) / cap;
-    *w = best_w;
-    *C = (G + n_slices - 1) / n_slices;
+    wm_panel_slices(G, width, T, knob, C, w);   // (stated in tx_plan.cpp: the prompt-panel plan cuts by the same rule)
 }
 
 static int panel_check(wm_ctx *ctx, int G, int c0, int C, int w) {
@@ -1056,6 +1051,47 @@ int wm_model_spec_dev(wm_ctx *ctx, wm_ctx *draft, int max_new, WmSpecDev *out, i
     sp.max_new = max_new; sp.n_vocab = m->dims.n_vocab;
     *script_area = p + R * 24;
     *out = sp;
+    return WM_OK;
+}
+
+// ------------------------------------------------------------------ prompt panels (wm_set_prompt_panel)
+// Positions [0, P0) of a plain decode group of G rows as panel steps that only fill the self-attention cache (tx_plan.h
+// wm_prompt_panel_plan): per slice of C windows -- position 0, the panels' embeddings, cache-only steps under a copy of the
+// group's mode without anything a close or a logits epilogue would read (the pattern of wm_model_spec_panel_step), the
+// position advanced by the panel's width.  Then the device position is P0 and the embedding of position P0 of all G rows is
+// written with embed_row's arithmetic into rows 0 .. G - 1 of dx / dxb / dstats / dmean[0]: what the close of step P0 - 1
+// leaves, so the group's ordinary steps and captured graphs continue from t = P0.  Expects the prompt table in m->dseq, the
+// offsets of a ragged group in m->doff and the cross-K/V of the G windows in m->xkv.
+int wm_model_prompt_prefill(wm_ctx *ctx, int G, int P0, const WmDecodeMode &mode) {
+    WmModel *m = ctx->model;
+    WmPromptPanelPlan pl;
+    wm_prompt_panel_plan(G, m->prompt_panel, P0 + 1, P0, -1, g_wm_tuning.teacher_panel_cut, &pl);
+    WM_REQUIRE(pl.w >= 1 && pl.P0 == P0 && P0 < m->dims.n_text_ctx, WM_ERR_STATE, "prompt prefill: nothing to run for %d rows up to position %d",
+               G, P0);
+    WM_REQUIRE(mode.n_cand <= 1 && !mode.beam, WM_ERR_STATE, "prompt prefill: a plain decode group");
+    WmDecodeMode pm = mode;
+    pm.stop = false; pm.budget = false; pm.stop_eot = -1; pm.acap = false; pm.acap_base = pm.acap_Tq = pm.acap_J = 0; pm.acap_q = nullptr;
+    pm.rep = false; pm.sb = false; pm.mask = false; pm.ts = false; pm.x = false;
+    const int *off0 = mode.off ? m->doff : nullptr;
+    const WmEmbedDev e = wm_model_embed_dev(m);
+    const int T = m->dims.n_text_ctx;
+    for (int c0 = 0; c0 < G; c0 += pl.C) {
+        const int C = std::min(pl.C, G - c0);
+        const int *off = off0 ? off0 + c0 : nullptr;
+        WM_TRY(panel_check(ctx, G, c0, C, pl.w));
+        WM_TRY(wm_model_set_pos(ctx, 0));
+        WM_TRY(wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, 0, C, std::min(pl.w, P0), T, e, off));
+        for (int t = 0; t < P0; t += pl.w) {
+            const int wp = std::min(pl.w, P0 - t), wn = std::min(pl.w, P0 - t - wp);
+            pm.panel = wp;
+            WM_TRY(decode_step_impl(ctx, C * wp, false, 0, m->dims.n_vocab - 1, nullptr, pm, 0, G, c0, true));
+            if (wn > 0) WM_TRY(wm_dec_embed_panel(ctx, m->dseq + c0, G, m->dpos, wp, C, wn, T, e, off));
+            WM_TRY(wm_dec_pos_add(ctx, m->dpos, wp));
+        }
+    }
+    // *dpos == P0: the group's rows at that position (one row per window: embed_row, P0 >= 2)
+    WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, 1, T, e, off0));
+    m->last_prefill[0] = P0; m->last_prefill[1] = pl.slices; m->last_prefill[2] = pl.slices * pl.steps;
     return WM_OK;
 }
 

@@ -462,6 +462,11 @@ struct WmModel {
     int align_dbg_hyp = -1;
     int32_t *align_dbg_slots = nullptr;
     int teacher_panel = 1;   // wm_set_teacher_panel: positions per step of the teacher-forced passes (a launch policy: same bits)
+    // wm_set_prompt_panel: positions per step of a transcribe group's prompt prefill (1: none -- every prompt position is an
+    // ordinary step; a launch policy: same bits), and what the context's last group prefill enqueued (P0, slices, panel steps;
+    // all 0: none ran -- wmdbg_last_prompt_prefill)
+    int prompt_panel = 1;
+    int last_prefill[3] = {0, 0, 0};
     // wm_transcribe_mel_beam: the group's beam state (WmBeamDev; allocated once at its largest size, so captured graphs keep
     // their addresses) and the debug library's one-shot trace capture (host destination, null in the product) with its
     // device buffer
@@ -564,6 +569,10 @@ int wm_spec_adopt(wm_ctx *draft, const WmSpecDev &sp, int G, int n_prompt);
 int wm_spec_stage(wm_ctx *ctx, const WmSpecDev &sp, int G, int w, int n_prompt, int n_ctx);
 int wm_spec_accept(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, const WmSpecDev &sp, const WmXDev &xd,
                    const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx, int fallback_tok);
+// Prompt panels (wm_set_prompt_panel, tx_plan.h wm_prompt_panel_plan): positions [0, P0) of a plain group of G rows as
+// cache-only panel steps at the context's width, then *dpos = P0 and rows 0 .. G - 1 of dx / dxb / dstats / dmean hold the
+// embedding of position P0 as the close of step P0 - 1 would have left it.  P0 >= 2 and a width > 1 (the plan says so).
+int wm_model_prompt_prefill(wm_ctx *ctx, int G, int P0, const WmDecodeMode &mode);
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode = WmDecodeMode());
 // arg-max reduce + write next token (positions >= n_prompt) + embed next position + advance *dpos
 int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first,
@@ -639,6 +648,7 @@ int wm_enc_attention(wm_ctx *ctx, const bf16_t *qk, const bf16_t *vt, bf16_t *at
                      int S, int S_pad, int d);
 
 // dec_kernels.hip
+static_assert(WM_MAX_TEACHER_PANEL == 8, "tx_plan.h WM_PANEL_MAX_WIDTH restates it");
 static_assert(WM_MAX_TEACHER_PANEL == WM_MAX_BEST_OF, "a panel's cross-attention is dec_xcand_attn_kernel: its instantiated widths");
 static_assert(WM_XIDS_CAND == WM_DEC_MAXB + 16, "WmXDev::ids: the candidate words follow the padded sample ids");
 constexpr int WM_NLIVE_RING = 16;  // pinned host slots for the per-burst live-row counts (early stop)
@@ -699,8 +709,9 @@ int wm_dec_embed(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, const W
 // Panel embedding: row c * w + s (c < C, s < w) = token seq[(*pos_ptr + s) * seq_stride + c] at positional row *pos_ptr + s.
 // Position 0 is embedded with wm_dec_embed's four-wave sums, every later one with the closing kernels' embed_row: the bits of
 // the step path's first embedding and of its closes.  pos_add: added to *pos_ptr (the embedding of the NEXT panel).
+// off (device [C], nullable): the windows' offsets in a ragged group -- the positional row is max(*pos_ptr + s - off[c], 0)
 int wm_dec_embed_panel(wm_ctx *ctx, const int *seq, int seq_stride, const int *pos_ptr, int pos_add, int C, int w, int n_ctx,
-                       const WmEmbedDev &e);
+                       const WmEmbedDev &e, const int *off = nullptr);
 // *pos_ptr += add (one thread)
 int wm_dec_pos_add(wm_ctx *ctx, int *pos_ptr, int add);
 // Single-query attention over a K/V cache [B][H][T_stride][64] -> bf16 head outputs att[B][H*64] in WL_TILED order.

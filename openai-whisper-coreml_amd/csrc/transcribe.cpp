@@ -189,6 +189,7 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     const StopCfg &stop = cfg.stop;
     const XCfg &xc = cfg.xc;
     const int Bg = j.Bg, Cg = j.Cg, N = call.n_cand;   // decoder rows, encoder rows (windows), candidates per window
+    m->last_prefill[0] = m->last_prefill[1] = m->last_prefill[2] = 0;   // (set again by this group's prompt panels, if it runs any)
     // the mode of this group's decode: the lane's own context settings and the call's options, in this one place
     j.mode = WmDecodeMode();
     j.mode.mask = m->mask_on; j.mode.ts = m->ts_on; j.mode.x = xc.on; j.mode.off = call.prompts.len != nullptr;
@@ -275,6 +276,23 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     // 3. embedding of the first prompt token (+ the initial timestamp-rule state)
     WM_TRY(wm_model_embed_first(c, Bg, j.mode));
     if (j.mode.ts) WM_TRY(wm_ts_init(c, wm_model_ts_dev(m), Bg));
+    return WM_OK;
+}
+
+// Prompt panels (wm_set_prompt_panel), enqueued behind the group's prefill and before anyone's first
+// burst: the prompt positions whose logits the call does not read -- everything in front of <|startoftranscript|> when
+// no_speech_prob is computed, in front of the prompt's last position otherwise, and never an aligned group's captured
+// positions -- run as cache-only panel steps, and the group's ordinary steps begin at that position.  Plain groups only: a
+// candidate or beam group, a speculative call and the all-f32 precision path step through their prompts as they always did.
+int lane_prompt_panels(LaneJob &j, const TxCall &call, const wm_ctx *caller) {
+    WmModel *m = j.c->model;
+    if (m->prompt_panel <= 1 || call.n_cand != 1 || call.beam || caller->dbg_hooks) return WM_OK;
+    WmPromptPanelPlan pl;
+    wm_prompt_panel_plan(j.Bg, m->prompt_panel, j.P, j.mode.x ? j.xpar.sot_pos : -1, j.mode.acap ? j.mode.acap_base : -1,
+                         g_wm_tuning.teacher_panel_cut, &pl);
+    if (pl.w < 1) return WM_OK;
+    WM_TRY(wm_model_prompt_prefill(j.c, j.Bg, pl.P0, j.mode));
+    j.t = pl.P0;
     return WM_OK;
 }
 
@@ -651,6 +669,7 @@ int lane_start(TxRun &r, LaneJob &j) {
     j.t = 0; j.bursts = 0; j.stopped = false;
     j.bpar.max_cand = call.max_cand; j.bpar.max_new = call.max_new; j.bpar.eot = call.eot; j.bpar.pad = call.eot >= 0 ? call.eot : 0;
     WM_TRY(lane_prefill(j, call, r.cfg));
+    WM_TRY(lane_prompt_panels(j, call, r.ctx));
     if (r.cfg.use_graph) WM_TRY(lane_graph(j, j.P));
     j.state = LaneJob::DECODING;
     return WM_OK;

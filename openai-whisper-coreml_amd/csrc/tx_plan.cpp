@@ -187,6 +187,34 @@ void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, con
     }
 }
 
+// ---------------------------------------------------------------- prompt panels ----
+void wm_panel_slices(int G, int width, int T, int knob, int *C, int *w) {
+    const int wd = width < 1 ? 1 : (width > WM_PANEL_MAX_WIDTH ? WM_PANEL_MAX_WIDTH : width);
+    int best_w = wd, best_steps = 1 << 30;
+    for (int wc = wd; wc >= 1; --wc) {
+        const int cap = WM_DEC_MAXB / wc, steps = ((G + cap - 1) / cap) * ((T + wc - 1) / wc);
+        if (steps < best_steps) { best_steps = steps; best_w = wc; }
+    }
+    if (knob == 1 && G > WM_DEC_MAXB / wd) best_w = WM_DEC_MAXB / G;
+    if (knob == 2) best_w = wd;
+    const int cap = WM_DEC_MAXB / best_w, n_slices = (G + cap - 1) / cap;
+    *w = best_w;
+    *C = (G + n_slices - 1) / n_slices;
+}
+
+void wm_prompt_panel_plan(int G, int width, int P, int sot_pos, int acap_base, int knob, WmPromptPanelPlan *out) {
+    *out = WmPromptPanelPlan();
+    int P0 = sot_pos >= 0 ? sot_pos : P - 1;
+    if (acap_base >= 0 && acap_base < P0) P0 = acap_base;
+    if (P0 > P - 1) P0 = P - 1;   // (a position of the prompt: the last one's logits are always read)
+    if (P0 < 0) P0 = 0;
+    out->P0 = P0;
+    if (width <= 1 || P0 < 2 || G < 1 || G > WM_DEC_MAXB) return;
+    wm_panel_slices(G, width, P0, knob, &out->C, &out->w);
+    out->slices = (G + out->C - 1) / out->C;
+    out->steps = (P0 + out->w - 1) / out->w;
+}
+
 // ---------------------------------------------------------------- the hooks' flat forms ----
 int wm_tx_plan_flat(const int32_t *in, int32_t *out, int32_t *cut, int cut_cap, int max_group_rows) {
     WmTxPlanIn pin;

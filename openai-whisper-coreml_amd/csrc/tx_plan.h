@@ -102,6 +102,26 @@ int wm_spec_width(int k, int bound, int last);
 int wm_spec_round(int G, int w, const int32_t *accepted, const int32_t *live, const int32_t *eot_at, const int32_t *left,
                   int32_t *live_out, int32_t *inc);
 
+// ---------------------------------------------------------------- prompt panels ----
+// wm_set_prompt_panel: the prompt positions of a plain decode group whose logits nobody reads run as
+// teacher-forced panel steps -- `width` positions of the same sequences per decoder step, no logits product, no close.
+constexpr int WM_PANEL_MAX_WIDTH = 8;   // = WM_MAX_TEACHER_PANEL (model.h asserts it)
+// How a group of G windows is cut for a panel pass of T positions at `width`: *C windows per slice, *w <= width positions per
+// panel, C * w <= WM_DEC_MAXB -- the cut with the fewest steps (the rule and its measurements: model.cpp
+// wm_model_panel_slices, which passes the probe knob teacher_panel_cut; 0 = the rule).
+void wm_panel_slices(int G, int width, int T, int knob, int *C, int *w);
+struct WmPromptPanelPlan {
+    int P0 = 0;       // the first position whose logits the call reads: the group's first ordinary step
+    int C = 0, w = 0; // windows per slice, positions per panel (0: no prefill -- every position is an ordinary step)
+    int slices = 0;   // slices of the group
+    int steps = 0;    // panel steps per slice: ceil(P0 / w), the last one narrower when w does not divide P0
+};
+// The rule.  P: the group's prompt positions (a ragged group: its longest prompt); sot_pos: the <|startoftranscript|> position
+// when the call computes no_speech_prob, else -1; acap_base: an aligned group's first captured position, else -1.
+// P0 = sot_pos when given, else P - 1; an aligned group caps it at acap_base.  Positions [0, P0) only fill the self-attention
+// cache.  width <= 1 or P0 < 2: no prefill (C = w = slices = steps = 0) -- the lane enqueues exactly what it always did.
+void wm_prompt_panel_plan(int G, int width, int P, int sot_pos, int acap_base, int knob, WmPromptPanelPlan *out);
+
 // ---------------------------------------------------------------- the hooks' flat forms ----
 // documented at wmdbg_tx_plan / wmdbg_group_tables / wmdbg_group_rows_out (include/whisper_mi355x_debug.h)
 constexpr int WM_TX_PLAN_IN = 12, WM_TX_PLAN_OUT = 8;

@@ -5,7 +5,7 @@ given as argv[1] (default base), every matrix scaled by weights.lively_gain so t
 length (argv[2], default 8: 10 .. 150 s), the production vocabulary's token ids, text context n_text_ctx.  Prints one JSON
 line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form.
 
-    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --words [--teacher-panel W] [--decode] | --reuse]
+    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --prompt-panel W | --words [--teacher-panel W] [--decode] | --reuse]
 
 --condition: the cost of condition_on_previous_text instead.  One more JSON line: wall seconds of the long form with
 conditioning off and on (the same recordings, after a warm-up of each; with the default fallback thresholds and with the
@@ -14,6 +14,14 @@ run decoded (per wm_transcribe_mel[_ragged] call: rows x the longest prompt of t
 length), the position graphs captured (distinct (rows, prompt positions) pairs among the calls, against the 4 graph sets a
 lane keeps), and the per-position time of ONE ragged decode group against a uniform group of the same size and the same
 number of prompt positions (what the row-offset load in the self-attention launch costs).
+
+--prompt-panel W: what wm_set_prompt_panel(W) is worth on --condition's conditioned run without fallback (the run whose prompts
+accumulate).  ONE width per process, so that widths are compared in interleaved processes: after a warm-up, the wall seconds
+of the run at that width (W = 1: the setter is not called at all, so the same line can be taken with another build's library,
+WM_LIB_PATH), its calls, prompt steps and prompt positions, and from the plan (wmdbg_prompt_panel_plan, host only) the panel
+steps that replaced them and the ordinary prompt steps left; then ONE uniform group of `recordings` rows with n_text_ctx / 2 + 3
+prompt positions and a single new token, best of 4: the decode stage at width 1 and at W, and from the two the time per
+ordinary prompt step and per panel step.  One JSON line.
 
 --words: the cost of word_timestamps instead.  Fallback and the silence skip are off, so every window is kept and goes
 through the alignment; a synthetic vocabulary (one piece per text token) is written to a temporary file.  One more JSON
@@ -50,6 +58,11 @@ CONDITION = "--condition" in sys.argv
 WORDS = "--words" in sys.argv
 REUSE = "--reuse" in sys.argv
 DECODE = "--decode" in sys.argv
+PPANEL = None
+if "--prompt-panel" in sys.argv:
+    i = sys.argv.index("--prompt-panel")
+    PPANEL = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 PANEL = None
 if "--teacher-panel" in sys.argv:
     i = sys.argv.index("--teacher-panel")
@@ -146,6 +159,78 @@ def condition_probe():
     print(json.dumps(dict(model=name, recordings=N, audio_s=audio_s, conditioning=res, group_rows=N, group_P=P,
                           ragged_prompt_lengths=[len(p) for p in ragged], decode_ms_per_position=per_pos,
                           ragged_over_uniform=per_pos["ragged"] / per_pos["uniform"])))
+
+
+def prompt_panel_probe():
+    import ctypes
+    SOT_PREV = 50361
+    dbg = b.load_debug_library()
+    ip = ctypes.POINTER(ctypes.c_int32)
+    dbg.wmdbg_prompt_panel_plan.argtypes = [ctypes.c_int] * 5 + [ip]
+
+    def plan(rows, P, sot):
+        out = np.zeros(5, dtype=np.int32)
+        assert dbg.wmdbg_prompt_panel_plan(rows, PPANEL, P, sot, -1, out.ctypes.data_as(ip)) == 0
+        return [int(v) for v in out]   # P0, C, w', slices, panel steps per slice
+    calls = []
+    inner = ctx.transcribe_mel
+
+    def counted(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, **k):
+        t0 = time.perf_counter()
+        r = inner(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, **k)
+        calls.append(dict(rows=len(prompts), P=max(len(p) for p in prompts), wall=time.perf_counter() - t0,
+                          decode_ms=float(ctx.last_stage_ms()[2]), gen=int(r.lens.max())))
+        return r
+    ctx.transcribe_mel = counted
+    run = dict(condition_on_previous_text=True, sot_prev=SOT_PREV, logprob_threshold=None, compression_ratio_threshold=None,
+               prompt_panel=PPANEL if PPANEL > 1 else None)
+    ctx.transcribe_long(recs, **kw, **run)     # warm-up
+    walls = []
+    for _ in range(2):
+        del calls[:]
+        t0 = time.perf_counter()
+        out = ctx.transcribe_long(recs, **kw, **run)
+        walls.append(time.perf_counter() - t0)
+    ctx.transcribe_mel = inner
+    plans = [plan(c["rows"], c["P"], c["P"] - 3) for c in calls]   # (no_speech_prob is computed: P0 = <|startoftranscript|>)
+    res = dict(model=name, recordings=N, audio_s=audio_s, prompt_panel=PPANEL, wall_s=walls, calls=len(calls),
+               windows=sum(len(o["windows"]) for o in out), prompt_steps=sum(c["P"] for c in calls),
+               generated_steps=sum(c["gen"] for c in calls), prompt_positions=sum(c["rows"] * c["P"] for c in calls),
+               prefilled_positions=sum(c["rows"] * pl[0] for c, pl in zip(calls, plans) if pl[2]),
+               panel_steps=sum(pl[3] * pl[4] for pl in plans),
+               ordinary_prompt_steps=sum(c["P"] - (pl[0] if pl[2] else 0) for c, pl in zip(calls, plans)),
+               decode_ms=sum(c["decode_ms"] for c in calls),
+               tokens_digest=int(sum(int(t) * (i + 1) for o in out for s_ in o["segments"] for i, t in enumerate(s_["tokens"])) % 1000000007))
+    # one uniform group: n_ctx / 2 + 3 prompt positions, one new token -- the decode stage is the prompt phase alone
+    n_ctx = dims["n_text_ctx"]
+    P = n_ctx // 2 + 3
+    d_mel, offs, T = ctx.logmel_long(recs, n_mels=dims["n_mels"], device=True)
+    rows = list(range(N))
+    prng = np.random.default_rng(5)
+    uniform = [[int(t) for t in prng.integers(0, 50000, size=P - 3)] + [SOT, 50259, TASK] for _ in rows]
+    group = {}
+    try:
+        for width in sorted({1, PPANEL}):
+            if PPANEL > 1:
+                ctx.set_prompt_panel(width)
+            best = None
+            for _ in range(4):
+                ctx.transcribe_mel(d_mel, offs[rows], T[rows], 0, [min(3000, int(t) - 3000) for t in T[rows]], uniform, 1,
+                                   eot=-1, no_speech_token=NS, sot_tail=3, mem=b.WM_MEM_DEVICE)
+                ms = float(ctx.last_stage_ms()[2])
+                best = ms if best is None else min(best, ms)
+            group[width] = best
+    finally:
+        ctx.dev_free(d_mel)
+    pl = plan(N, P, P - 3)
+    step_ms = group[1] / P
+    res["group"] = dict(rows=N, P=P, decode_ms=group, ms_per_prompt_step=step_ms)
+    if PPANEL > 1 and pl[2]:
+        n_panel = pl[3] * pl[4]
+        res["group"].update(P0=pl[0], slice_windows=pl[1], panel_width=pl[2], panel_steps=n_panel,
+                            ms_per_panel_step=(group[PPANEL] - (P - pl[0]) * step_ms) / n_panel,
+                            prompt_phase_speedup=group[1] / group[PPANEL])
+    print(json.dumps(res))
 
 
 def probe_vocab():
@@ -311,6 +396,9 @@ def reuse_probe():
 
 if CONDITION:
     condition_probe()
+    sys.exit(0)
+if PPANEL is not None:
+    prompt_panel_probe()
     sys.exit(0)
 if REUSE:
     reuse_probe()
