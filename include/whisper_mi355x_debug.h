@@ -203,6 +203,47 @@ WM_API int wmdbg_dec_attention(wm_ctx *ctx, const float *q, const float *k, cons
 WM_API int wmdbg_dec_self_attention_off(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int T,
                                         int pos, const int32_t *off, float *out);
 
+/* Every decode-attention launch form alone, driven as the decode step drives it: one call of wm_dec_attention (form 0),
+ * wm_dec_attention_cand (1), wm_dec_xattn_fq (2) or wm_dec_self_attention (3) on host data.  All pointers are host memory.
+ * rows = B (forms 0, 2, 3) or C * N (form 1: row c * N + s = candidate s of window c); cache entries = B, or C for form 1.
+ * Nothing is launched for a geometry the launcher's plan refuses, or when an address would leave a buffer (T outside
+ * 1 .. WM_ATT_MAXK, no key or more than T, an offset outside [0, T), a live list that is not ascending rows of the group, a
+ * packed field that does not fit): WM_ERR_INVALID with the reason in wm_last_error(), `out` (and mean_out) left at the
+ * sentinels, plan[0] = the plan's status. */
+typedef struct wmdbg_attn {
+    int32_t form;
+    int32_t B, C, N, H;        /* B rows, or C windows x N candidates; H heads of 64 */
+    int32_t T;                 /* cache rows per (entry, head) pair */
+    int32_t n_keys;            /* the constant key count (pos < 0) */
+    int32_t nsplit;            /* form 0: workgroups per pair, 1 / 2 / 4 / 8 */
+    int32_t pos;               /* >= 0 (forms 0 and 3): uploaded and passed as pos_ptr, keys 0 .. pos (form 0: n_keys = pos + 1 as
+                                  well, the cross kernels' row clamp); -1: n_keys keys */
+    int32_t n_live;            /* entries of live_rows */
+    int32_t short_lived;       /* forms 0 and 1: the shape of a burst that shares the chip */
+    int32_t warm_rows, warm_k; /* both non-zero: a [warm_rows][warm_k] bf16 matrix is allocated and passed as the warm-up matrix
+                                  (warm_rows % 16 == 0, warm_k % 32 == 0) */
+    int32_t K;                 /* form 2: the width of the query projection (= H * 64, <= 1280) */
+    const int32_t *off;        /* form 3, with pos >= 0: [B] row offsets, each in [0, T): row b's keys are [min(off[b], pos), pos]; NULL: none.
+                                  A row with pos < off[b] has not started: its output is finite, nothing more */
+    const int32_t *live_rows;  /* the compact ascending list of the n_live live rows; NULL: every row is live */
+    const float *q;            /* forms 0, 1, 3: [rows][H * 64] */
+    const float *k, *v;        /* [entries][H][T][64], rounded to bf16; rows outside a pair's key range may hold anything, NaN included */
+    /* form 2, the query side as wmdbg_dec_gemv_ln takes it (DE_Q, centre = 1; wm_ln_fold runs first): */
+    const float *x;            /* [B][K] */
+    const float *ln_g, *ln_b;  /* [K] */
+    const float *Wq;           /* [K][K] */
+    const float *bias;         /* [K] or NULL */
+    /* outputs */
+    float *out;                /* [ceil16(rows)][H * 64]: the bf16 head outputs widened; the device buffer is pre-filled with
+                                  WMDBG_SENTINEL_BF16, which rows that are not live and the pad rows must still hold */
+    float *mean_out;           /* form 2: [B], pre-filled with WMDBG_SENTINEL_F32 */
+    int32_t plan[16];          /* the wmdbg_dec_attn_plan output record of the plan the launcher used (same plan function, the
+                                  context's CUs, the current wmdbg_set_tuning state) */
+} wmdbg_attn;
+WM_API int wmdbg_dec_attention_form(wm_ctx *ctx, wmdbg_attn *io);
+/* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_attn) and the offsets of off, out and plan (host only). */
+WM_API int wmdbg_attn_layout(int32_t *out4);
+
 /* ---- teacher-forced panels (wm_set_teacher_panel): the panel launches of a step alone, on host data.  A panel is C windows x
  * w consecutive positions pos .. pos + w - 1, row r = c * w + s; 1 <= w <= WM_MAX_TEACHER_PANEL, C * w <= WM_DEC_MAXB. ---- */
 /* The self-attention launch of a panel step: q f32 [C * w][H * 64], k / v f32 [C][H][T][64] (rounded to bf16; window c's entry

@@ -715,6 +715,137 @@ extern "C" int wmdbg_dec_self_attention_off(wm_ctx *ctx, const float *q, const f
     return down_tiled_bf16(datt, (size_t)B, (size_t)H * 64, out, s);
 }
 
+// Every decode-attention form as the decode step drives it (struct wmdbg_attn): one launcher call on staged host data, the
+// plan the launcher used beside the outputs.  Nothing is launched for a geometry the plan refuses or for an address that would
+// leave a buffer; the caller's output buffers then hold the sentinels.
+extern "C" int wmdbg_attn_layout(int32_t *out4) {
+    if (!out4) return WM_ERR_INVALID;
+    out4[0] = (int32_t)sizeof(wmdbg_attn); out4[1] = (int32_t)offsetof(wmdbg_attn, off);
+    out4[2] = (int32_t)offsetof(wmdbg_attn, out); out4[3] = (int32_t)offsetof(wmdbg_attn, plan);
+    return WM_OK;
+}
+
+extern "C" int wmdbg_dec_attention_form(wm_ctx *ctx, wmdbg_attn *io) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(io && io->out && io->k && io->v, WM_ERR_INVALID, "dec_attention_form: null pointer");
+    memset(io->plan, 0, sizeof(io->plan));
+    const int form = io->form, H = io->H, T = io->T;
+    WM_REQUIRE(form >= 0 && form <= 3, WM_ERR_INVALID, "dec_attention_form: form %d is not 0 .. 3", form);
+    const bool cand = form == 1, fq = form == 2, self = form == 3;
+    WM_REQUIRE(!cand || (io->C >= 1 && io->N >= 1 && io->N <= WM_MAX_BEST_OF && io->C <= WM_DEC_MAXB), WM_ERR_INVALID,
+               "dec_attention_form: %d windows x %d candidates", io->C, io->N);
+    const int rows = cand ? io->C * io->N : io->B, entries = cand ? io->C : io->B;
+    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && H >= 1 && H <= 1024, WM_ERR_INVALID, "dec_attention_form: %d rows x %d heads", rows, H);
+    const size_t dd = (size_t)H * 64, rpad = ((size_t)rows + 15) / 16 * 16;
+    {   // what a refused call leaves behind: the sentinels
+        std::vector<bf16_t> s16;
+        fill_bf16(s16, rpad * dd);
+        from_bf16(s16, io->out);
+        const uint32_t u = WMDBG_SENTINEL_F32;
+        for (int b = 0; fq && io->mean_out && b < rows; ++b) memcpy(io->mean_out + b, &u, 4);
+    }
+    // ---- the plan, from the function the launcher asks (and with the context's CUs)
+    const bool has_pos = io->pos >= 0, has_pf = io->warm_rows > 0 && io->warm_k > 0;
+    int32_t pin[WM_ATTN_PLAN_IN] = {0};
+    pin[0] = form; pin[1] = cand ? 0 : io->B; pin[2] = cand ? io->C : 0; pin[3] = cand ? io->N : 0; pin[4] = H; pin[5] = T;
+    pin[6] = io->n_keys; pin[7] = io->nsplit; pin[8] = fq ? io->K : 0;
+    pin[9] = (has_pos ? 1 : 0) | (fq || self ? 0 : 2) | (io->off ? 4 : 0) | (has_pf ? 8 : 0) | (io->short_lived ? 16 : 0) | (io->live_rows ? 32 : 0);
+    pin[10] = has_pf ? io->warm_rows : 0; pin[11] = has_pf ? io->warm_k : 0; pin[12] = ctx->n_cus;
+    wm_attn_plan_flat(pin, g_wm_tuning, io->plan);
+    if (io->plan[0] != WM_OK) return WM_ERR_INVALID;   // (the plan function has set the message)
+    // ---- every address inside its buffer
+    WM_REQUIRE(H <= 255 && T >= 1 && T <= WM_ATT_MAXK, WM_ERR_INVALID, "dec_attention_form: H 1 .. 255, T 1 .. %d", WM_ATT_MAXK);
+    WM_REQUIRE(!has_pos || form == 0 || self, WM_ERR_INVALID, "dec_attention_form: form %d takes no device position", form);
+    const int nk = has_pos ? io->pos + 1 : io->n_keys;
+    WM_REQUIRE(nk >= 1 && nk <= T && io->n_keys >= 0 && io->n_keys <= T, WM_ERR_INVALID, "dec_attention_form: %d keys outside 1 .. T = %d", nk, T);
+    // (the cross kernels clamp their loads to row n_keys - 1 whether or not the position comes from device memory)
+    WM_REQUIRE(self || (io->n_keys >= 1 && (!has_pos || io->n_keys == nk)), WM_ERR_INVALID,
+               "dec_attention_form: a cross form needs n_keys >= 1 keys, and n_keys = pos + 1 with a device position");
+    WM_REQUIRE(!io->off || self, WM_ERR_INVALID, "dec_attention_form: row offsets belong to the self-attention");
+    WM_REQUIRE(!io->off || has_pos, WM_ERR_INVALID, "dec_attention_form: row offsets need the device position");
+    for (int b = 0; io->off && b < rows; ++b)
+        WM_REQUIRE(io->off[b] >= 0 && io->off[b] < T, WM_ERR_INVALID, "dec_attention_form: off[%d] = %d outside [0, %d)", b, io->off[b], T);
+    WM_REQUIRE(!io->short_lived || form <= 1, WM_ERR_INVALID, "dec_attention_form: short_lived is a cross-attention shape");
+    WM_REQUIRE(io->warm_rows >= 0 && io->warm_rows <= 8192 && io->warm_k >= 0 && io->warm_k <= 8192 && io->warm_k % 32 == 0 && io->warm_rows % 16 == 0,
+               WM_ERR_INVALID, "dec_attention_form: warm-up matrix of %d x %d", io->warm_rows, io->warm_k);
+    std::vector<int32_t> live((size_t)WM_DEC_MAXB + 4, 0);
+    if (io->live_rows) {
+        WM_REQUIRE(io->n_live >= 0 && io->n_live <= rows, WM_ERR_INVALID, "dec_attention_form: n_live %d outside [0, %d]", io->n_live, rows);
+        for (int i = 0; i < io->n_live; ++i) {
+            WM_REQUIRE(io->live_rows[i] >= 0 && io->live_rows[i] < rows && (i == 0 || io->live_rows[i] > io->live_rows[i - 1]), WM_ERR_INVALID,
+                       "dec_attention_form: the live list must be ascending rows of the group");
+            live[i] = io->live_rows[i];
+        }
+        live[WM_DEC_MAXB] = io->n_live;
+    }
+    if (fq)
+        WM_REQUIRE(io->x && io->ln_g && io->ln_b && io->Wq && io->mean_out && io->K == H * 64 && io->K <= 1280, WM_ERR_INVALID,
+                   "dec_attention_form: the fused query needs x, ln_g, ln_b, Wq, mean_out and K = H * 64 <= 1280");
+    else
+        WM_REQUIRE(io->q, WM_ERR_INVALID, "dec_attention_form: null query");
+    // ---- staging
+    std::vector<bf16_t> k16, v16, w16, x16, fill;
+    std::vector<float> st, mean;
+    to_bf16(io->k, k16, (size_t)entries * dd * T);
+    to_bf16(io->v, v16, (size_t)entries * dd * T);
+    fill_bf16(fill, rpad * dd);
+    const std::vector<uint32_t> fill32((size_t)rows, WMDBG_SENTINEL_F32);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    const bf16_t *dk, *dv;
+    bf16_t *datt;
+    WM_TRY(pool.get(&dk, k16.data(), k16.size() * 2, s));
+    WM_TRY(pool.get(&dv, v16.data(), v16.size() * 2, s));
+    WM_TRY(pool.get(&datt, fill.data(), fill.size() * 2, s));
+    DecAttnArgs t = {};
+    t.kc = dk; t.vc = dv; t.att = datt; t.H = H; t.T_stride = T; t.n_keys = io->n_keys; t.short_lived = io->short_lived != 0;
+    if (cand) { t.C = io->C; t.N = io->N; } else t.B = io->B;
+    if (!fq) WM_TRY(pool.get(&t.q, io->q, (size_t)rows * dd * 4, s));
+    if (form <= 1) WM_TRY(pool.get(&t.part, nullptr, (size_t)rows * H * WM_MAXSPLIT * 66 * 4, s));
+    if (has_pos) WM_TRY(pool.get(&t.pos_ptr, &io->pos, 4, s));
+    if (io->off) WM_TRY(pool.get(&t.off, io->off, (size_t)rows * 4, s));
+    if (io->live_rows) WM_TRY(pool.get(&t.live, live.data(), live.size() * 4, s));
+    if (has_pf) {
+        WM_TRY(pool.get(&t.pf.ptr, nullptr, (size_t)io->warm_rows * io->warm_k * 2, s));
+        t.pf.rows = io->warm_rows; t.pf.k = io->warm_k;
+    }
+    float *dmean_out = nullptr;
+    switch (form) {
+        case 0: t.nsplit = io->nsplit; WM_TRY(wm_dec_attention(ctx, t)); break;
+        case 1: WM_TRY(wm_dec_attention_cand(ctx, t)); break;
+        case 3: WM_TRY(wm_dec_self_attention(ctx, t)); break;
+        default: {   // the query side as wmdbg_dec_gemv_ln stages it (DE_Q, centre = 1), wm_ln_fold first
+            const int K = io->K, B = io->B;
+            tile_bf16(io->Wq, (size_t)K, (size_t)K, w16);
+            stage_ln_rows(io->x, B, K, true, x16, st, mean);
+            DecGemvArgs a;
+            memset(&a, 0, sizeof(a));
+            a.epi = DE_Q; a.B = B; a.N = K; a.K = K; a.stats_parts = K / 16; a.ldo = K;
+            const bf16_t *dW;
+            bf16_t *dWf;
+            float *dc1, *dc2;
+            const float *dg, *db, *dbias = nullptr;
+            WM_TRY(pool.get(&a.a, x16.data(), x16.size() * 2, s));
+            WM_TRY(pool.get(&dW, w16.data(), w16.size() * 2, s));
+            WM_TRY(pool.get(&dWf, nullptr, w16.size() * 2, s));
+            WM_TRY(pool.get(&dc1, nullptr, (size_t)K * 4, s));
+            WM_TRY(pool.get(&dc2, nullptr, (size_t)K * 4, s));
+            WM_TRY(pool.get(&dg, io->ln_g, (size_t)K * 4, s));
+            WM_TRY(pool.get(&db, io->ln_b, (size_t)K * 4, s));
+            if (io->bias) WM_TRY(pool.get(&dbias, io->bias, (size_t)K * 4, s));
+            WM_TRY(pool.get(&a.stats_in, st.data(), st.size() * 4, s));
+            WM_TRY(pool.get(&a.mean_in, mean.data(), (size_t)B * 4, s));
+            WM_TRY(pool.get(&a.mean_out, fill32.data(), (size_t)B * 4, s));
+            WM_TRY(wm_ln_fold(ctx, dW, dg, db, dbias, K, K, dWf, dc1, dc2));
+            a.W = dWf; a.c1 = dc1; a.c2 = dc2;
+            dmean_out = a.mean_out;
+            WM_TRY(wm_dec_xattn_fq(ctx, a, t));
+        }
+    }
+    if (dmean_out) WM_HIP(hipMemcpyAsync(io->mean_out, dmean_out, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+    return down_tiled_bf16(datt, rpad, dd, io->out, s);
+}
+
 // ------------------------------------------------------------------ micro-benchmarks ------
 // Time `iters` back-to-back launches of one decode kernel, cycling over `n_mats` distinct weight
 // matrices / cache slices so nothing is served from L2 or MALL.  Returns average microseconds
