@@ -417,6 +417,42 @@ WM_API int wmdbg_spec_accept(wm_ctx *ctx, int G, int w, int n_tiles, int pos, in
                              const int32_t *budget, const uint64_t *tilemax, const float *txt, const float *win, int32_t *seq,
                              int32_t *done, float *logprob_out, int32_t *stats_out, int32_t *round_out, int32_t *acc_out,
                              int32_t *draft_seq_out, int32_t *pos_out);
+/* The bookkeeping kernels of a speculative round alone (spec.hip), each on caller-given state: which = 0 wm_spec_adopt
+ * (spec_adopt_kernel), 1 wm_spec_stage (spec_stage_kernel), 2 wm_spec_commit (spec_commit_kernel WITHOUT the accept launch in
+ * front of it: wtok, wlp and acc are the caller's).  G windows x w rows, 1 <= G <= WM_DEC_MAXB, 1 <= w <= 8, G * w <=
+ * WM_DEC_MAXB, as the launchers take them; the rules of the target (tts) and of the draft (dts) are on or off independently.
+ * Every buffer is host memory that the hook uploads WHOLE before the launch and downloads WHOLE behind it, whichever kernel
+ * runs and whether the rules are on: the caller pre-fills what it does not give with a sentinel (the NaN bits
+ * WMDBG_SENTINEL_F32 for floats, a fixed negative int) and reads from the buffers what was written and that nothing else was.
+ * Per-window arrays have cap >= G rows, per-row arrays cap * w: rows behind the group's must come back untouched.  Nothing is
+ * launched when a kernel could leave a buffer (bad geometry, n_prompt >= n_ctx for the adoption, a position outside
+ * [n_prompt - 1, n_ctx) for the staging or with pos + w >= n_ctx for the commit, acc[c] outside [0, w)): WM_ERR_INVALID. */
+typedef struct wmdbg_spec {
+    int32_t which;
+    int32_t G, w, cap;
+    int32_t n_prompt, n_ctx, max_new, n_vocab;   /* WmSpecDev::max_new and n_vocab (the staging's clamp of proposal ids) */
+    int32_t tts_on, dts_on;
+    int32_t tts_par[4], dts_par[4];              /* ts_begin, eot, n_vocab, max_initial of WmTsDev */
+    int32_t eot, pad_tok;                        /* WmStopDev */
+    const int32_t *script;     /* [G][max_new] proposals by generated index, or NULL: the draft's own tokens */
+    const int32_t *budget;     /* [cap] or NULL */
+    int32_t *tseq, *dseq;      /* [n_ctx][G] the two token buffers */
+    int32_t *pos2;             /* [2] the target's and the draft's device position */
+    int32_t *tts_hist;         /* [cap][4] */
+    int32_t *tts_rng;          /* [cap * w][4]: per window for the adoption, the verify step's per-row slots for the staging */
+    int32_t *dts_hist, *dts_rng;                 /* [cap][4] */
+    int32_t *chist, *crng, *dchist, *dcrng;      /* [cap][4] the committed states */
+    int32_t *wtok;             /* [cap * w] */
+    float *wlp;                /* [cap * w] */
+    int32_t *acc, *done;       /* [cap] */
+    int32_t *stats;            /* [cap][4] */
+    int32_t *round;            /* [2] */
+    int32_t *n_live;           /* [1] */
+    float *logprob;            /* [max_new][G] */
+} wmdbg_spec;
+WM_API int wmdbg_spec_kernel(wm_ctx *ctx, wmdbg_spec *io);
+/* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_spec) and the offsets of tts_par, script and logprob (host only). */
+WM_API int wmdbg_spec_layout(int32_t *out4);
 /* The cross-attention launch of a candidate group exactly as the decode step makes it (wm_dec_attention_cand): C windows x N
  * candidates, q f32 [C * N][H * 64] (row c * N + s = candidate s of window c), k / v f32 [C][H][T][64] (rounded to bf16), the
  * first n_keys positions; live_rows: the compact ascending list of the n_live live rows (NULL: every row is live);

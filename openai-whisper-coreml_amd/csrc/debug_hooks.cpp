@@ -416,6 +416,82 @@ extern "C" int wmdbg_spec_accept(wm_ctx *ctx, int G, int w, int n_tiles, int pos
     WM_HIP(hipStreamSynchronize(s));
     return WM_OK;
 }
+extern "C" int wmdbg_spec_layout(int32_t *out4) {
+    if (!out4) return WM_ERR_INVALID;
+    out4[0] = (int32_t)sizeof(wmdbg_spec); out4[1] = (int32_t)offsetof(wmdbg_spec, tts_par);
+    out4[2] = (int32_t)offsetof(wmdbg_spec, script); out4[3] = (int32_t)offsetof(wmdbg_spec, logprob);
+    return WM_OK;
+}
+// The adoption, the staging or the commit of a speculative round alone (spec.hip) on the caller's state.  Every buffer goes to
+// the device whole and comes back whole, so the caller's sentinels show what the kernel left alone.
+extern "C" int wmdbg_spec_kernel(wm_ctx *ctx, wmdbg_spec *io) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(io && io->tseq && io->dseq && io->pos2 && io->tts_hist && io->tts_rng && io->dts_hist && io->dts_rng && io->chist &&
+                   io->crng && io->dchist && io->dcrng && io->wtok && io->wlp && io->acc && io->done && io->stats && io->round &&
+                   io->n_live && io->logprob,
+               WM_ERR_INVALID, "wmdbg_spec_kernel: null pointer");
+    const int G = io->G, w = io->w, cap = io->cap, n_ctx = io->n_ctx, n_prompt = io->n_prompt, max_new = io->max_new, pos = io->pos2[0];
+    WM_REQUIRE(io->which >= 0 && io->which <= 2, WM_ERR_INVALID, "wmdbg_spec_kernel: which %d is not 0 .. 2", io->which);
+    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB && cap >= G && cap <= 2 * WM_DEC_MAXB &&
+                   n_prompt >= 1 && n_prompt < n_ctx && n_ctx <= 4096 && max_new >= 1 && max_new <= 4096 && io->n_vocab >= 1,
+               WM_ERR_INVALID, "wmdbg_spec_kernel: bad geometry");
+    // the positions a kernel addresses the token buffers with: the staging stops at n_ctx by itself, the commit relies on its
+    // launcher (the host narrows the last rounds); its reads of wtok go up to row acc[c].  pos = n_prompt - 1: a round whose first
+    // token is generated index 0 (the product's first round stands one further: the first token is a plain step's)
+    if (io->which == 1) WM_REQUIRE(pos >= n_prompt - 1 && pos < n_ctx, WM_ERR_INVALID, "wmdbg_spec_kernel: position %d outside [n_prompt - 1, n_ctx)", pos);
+    if (io->which == 2) {
+        WM_REQUIRE(pos >= n_prompt - 1 && pos + w < n_ctx, WM_ERR_INVALID, "wmdbg_spec_kernel: position %d + %d rows leaves the context", pos, w);
+        for (int c = 0; c < G; ++c)
+            WM_REQUIRE(io->acc[c] >= 0 && io->acc[c] < w, WM_ERR_INVALID, "wmdbg_spec_kernel: acc[%d] = %d outside [0, w)", c, io->acc[c]);
+    }
+    hipStream_t s = ctx->stream;
+    const size_t ns = (size_t)n_ctx * G * 4, win4 = (size_t)cap * 16, rows = (size_t)cap * w;
+    DevPool pool;
+    // every buffer once: host pointer, bytes, device pointer
+    struct Buf { void *h; size_t bytes; void *d; };
+    Buf bufs[] = {{io->tseq, ns, nullptr},          {io->dseq, ns, nullptr},        {io->pos2, 8, nullptr},           {io->tts_hist, win4, nullptr},
+                  {io->tts_rng, rows * 16, nullptr}, {io->dts_hist, win4, nullptr},  {io->dts_rng, win4, nullptr},     {io->chist, win4, nullptr},
+                  {io->crng, win4, nullptr},        {io->dchist, win4, nullptr},    {io->dcrng, win4, nullptr},       {io->wtok, rows * 4, nullptr},
+                  {io->wlp, rows * 4, nullptr},     {io->acc, (size_t)cap * 4, nullptr}, {io->done, (size_t)cap * 4, nullptr}, {io->stats, win4, nullptr},
+                  {io->round, 8, nullptr},          {io->n_live, 4, nullptr},       {io->logprob, (size_t)max_new * G * 4, nullptr}};
+    for (Buf &b : bufs) WM_TRY(pool.get(&b.d, b.h, b.bytes, s));
+    int *d_script = nullptr, *d_bud = nullptr;
+    if (io->script) WM_TRY(pool.get(&d_script, io->script, (size_t)G * max_new * 4, s));
+    if (io->budget) WM_TRY(pool.get(&d_bud, io->budget, (size_t)cap * 4, s));
+    auto dev = [&](const void *h) {
+        for (const Buf &b : bufs)
+            if (b.h == h) return b.d;
+        return (void *)nullptr;
+    };
+    WmSpecDev sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.tseq = (int *)dev(io->tseq); sp.dseq = (int *)dev(io->dseq);
+    sp.tpos = (int *)dev(io->pos2); sp.dpos = sp.tpos + 1;
+    sp.tts.rng = io->tts_on ? (int *)dev(io->tts_rng) : nullptr; sp.tts.hist = (int *)dev(io->tts_hist);
+    sp.tts.ts_begin = io->tts_par[0]; sp.tts.eot = io->tts_par[1]; sp.tts.n_vocab = io->tts_par[2]; sp.tts.max_initial = io->tts_par[3];
+    sp.dts.rng = io->dts_on ? (int *)dev(io->dts_rng) : nullptr; sp.dts.hist = (int *)dev(io->dts_hist);
+    sp.dts.ts_begin = io->dts_par[0]; sp.dts.eot = io->dts_par[1]; sp.dts.n_vocab = io->dts_par[2]; sp.dts.max_initial = io->dts_par[3];
+    sp.chist = (int *)dev(io->chist); sp.crng = (int *)dev(io->crng); sp.dchist = (int *)dev(io->dchist); sp.dcrng = (int *)dev(io->dcrng);
+    sp.wtok = (int *)dev(io->wtok); sp.wlp = (float *)dev(io->wlp); sp.acc = (int *)dev(io->acc);
+    sp.stats = (int *)dev(io->stats); sp.round = (int *)dev(io->round);
+    sp.script = d_script; sp.max_new = max_new; sp.n_vocab = io->n_vocab;
+    if (io->which == 0) {
+        WM_TRY(wm_spec_adopt(ctx, sp, G, n_prompt));
+    } else if (io->which == 1) {
+        WM_TRY(wm_spec_stage(ctx, sp, G, w, n_prompt, n_ctx));
+    } else {
+        WmXDev xd;
+        memset(&xd, 0, sizeof(xd));
+        xd.logprob = (float *)dev(io->logprob);
+        WmStopDev st;
+        memset(&st, 0, sizeof(st));
+        st.done = (int *)dev(io->done); st.budget = d_bud; st.n_live = (int *)dev(io->n_live); st.eot = io->eot; st.pad_tok = io->pad_tok;
+        WM_TRY(wm_spec_commit(ctx, sp, xd, st, G, w, n_prompt, n_ctx));
+    }
+    for (const Buf &b : bufs) WM_HIP(hipMemcpyAsync(b.h, b.d, b.bytes, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
 extern "C" int wmdbg_group_rows_out(const int32_t *in, int n, int32_t *out) {
     if (!in || !out || n < 0) return -1;
     for (int i = 0; i < n; ++i)

@@ -569,6 +569,8 @@ int wm_spec_adopt(wm_ctx *draft, const WmSpecDev &sp, int G, int n_prompt);
 int wm_spec_stage(wm_ctx *ctx, const WmSpecDev &sp, int G, int w, int n_prompt, int n_ctx);
 int wm_spec_accept(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, const WmSpecDev &sp, const WmXDev &xd,
                    const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx, int fallback_tok);
+// wm_spec_accept = the accept launch, then this one on the same stream
+int wm_spec_commit(wm_ctx *ctx, const WmSpecDev &sp, const WmXDev &xd, const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx);
 // Prompt panels (wm_set_prompt_panel, tx_plan.h wm_prompt_panel_plan): positions [0, P0) of a plain group of G rows as
 // cache-only panel steps at the context's width, then *dpos = P0 and rows 0 .. G - 1 of dx / dxb / dstats / dmean hold the
 // embedding of position P0 as the close of step P0 - 1 would have left it.  P0 >= 2 and a width > 1 (the plan says so).

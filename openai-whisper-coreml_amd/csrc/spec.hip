@@ -223,6 +223,14 @@ int wm_spec_accept(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, 
     WmProfScope ps(&ctx->prof, "spec_accept", ctx->stream);
     spec_accept_kernel<<<G, 512, 0, ctx->stream>>>(tilemax, n_tiles, G, w, sp, xd, fallback_tok);
     WM_HIP(hipGetLastError());
+    return wm_spec_commit(ctx, sp, xd, stop, G, w, n_prompt, n_ctx);
+}
+
+// the second launch of wm_spec_accept (which the product always makes through it; alone: the debug library's kernel tests)
+int wm_spec_commit(wm_ctx *ctx, const WmSpecDev &sp, const WmXDev &xd, const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx) {
+    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB, WM_ERR_INVALID, "spec_commit: %d windows x %d rows",
+               G, w);
+    WM_REQUIRE(xd.logprob && stop.done, WM_ERR_STATE, "spec_commit: needs the extended decode and the stop state");
     spec_commit_kernel<<<1, WM_DEC_MAXB, 0, ctx->stream>>>(sp, xd, stop, G, w, n_prompt, n_ctx);
     WM_HIP(hipGetLastError());
     return WM_OK;

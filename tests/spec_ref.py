@@ -1,6 +1,7 @@
 """Speculative decoding (wm_transcribe_mel_speculative) restated in plain Python: the group cut, the
 width of a verify step, the arithmetic of one round (csrc/spec_round.h, tx_plan.cpp wm_spec_round) and -- from them -- the walk
-of a whole call over a script of proposals, which gives the statistics the library must report.  No numpy in the rules: the
+of a whole call over a script of proposals, which gives the statistics the library must report; the timestamp rules' state
+(dec_close.h ts_advance) and, over plain lists, the adopt, stage and commit kernels of spec.hip.  No numpy in the rules: the
 tests compare these against the library's pure functions (wmdbg_spec_*) and its kernels."""
 
 DEC_MAXB = 128          # WM_DEC_MAXB
@@ -59,6 +60,154 @@ def spec_round(w, accepted, live, eot_at, left):
         live_out[c] = 0 if window_stops(m, eot_at[c], left[c]) else 1
         inc[c] = (1, w - 1, min(accepted[c], own), min(accepted[c], m))
     return n, live_out, inc
+
+
+# ---------------------------------------------------------------- the timestamp rules' state (model.h WmTsDev, dec_close.h)
+def ts_start(ts_begin, n_vocab, max_initial):
+    """(hist, rng) before the first sampled token, as ts_init_kernel leaves them: no text token may open the transcript and
+    the first timestamp is at most max_initial (< 0: unlimited).  hist = (n_sampled, last_is_ts, prev_is_ts, last_ts)."""
+    hi = ts_begin + max_initial + 1 if 0 <= max_initial and ts_begin + max_initial + 1 < n_vocab else n_vocab
+    return (0, 0, 1, -1), (0, 0, ts_begin, hi)
+
+
+def ts_advance(hist, tok, ts_begin, eot, n_vocab):
+    """dec_close.h ts_advance: `tok` was sampled behind the history `hist`.  Returns (hist', (text_lo, text_hi, ts_lo, ts_hi)),
+    the ranges of allowed text and timestamp ids at the next position (ApplyTimestampRules without the sum rule).  An empty
+    timestamp range behind a closed pair is stated the way the device states it: ts_hi = ts_begin, ts_lo still the floor."""
+    n, last_is_ts, _, last_ts = hist
+    is_ts = tok >= ts_begin
+    penultimate_ts = n < 1 or last_is_ts != 0        # of the history WITH tok: len(seq) < 2 or seq[-2] >= ts_begin
+    newest = tok if is_ts else last_ts
+    text_lo, text_hi, ts_lo, ts_hi = 0, ts_begin, ts_begin, n_vocab
+    if is_ts and penultimate_ts:
+        ts_hi = ts_begin                             # a pair was closed: no timestamp next
+    elif is_ts:
+        text_lo = eot                                # an opening timestamp: its partner, or end-of-text
+    if newest >= 0:                                  # timestamps do not decrease, and advance unless they close a pair
+        ts_lo = max(ts_lo, newest if (is_ts and not penultimate_ts) else newest + 1)
+    return (n + 1, 1 if is_ts else 0, last_is_ts, newest), (text_lo, text_hi, ts_lo, ts_hi)
+
+
+def ts_replay(hist, rng, toks, ts):
+    """(hist, rng) advanced along toks with the rule parameters ts = (ts_begin, eot, n_vocab, max_initial)"""
+    for t in toks:
+        hist, rng = ts_advance(hist, t, ts[0], ts[1], ts[2])
+    return tuple(hist), tuple(rng)
+
+
+def rule_histories(alphabet, ts, max_len=5):
+    """Every token history of length 0 .. max_len over `alphabet` that the rules allow -- each token inside the ranges behind
+    the tokens in front of it --, shortest first, in the alphabet's order: a list of (tokens, hist, rng), and the number of
+    histories of those lengths that were left out."""
+    out, level = [], [((),) + ts_start(ts[0], ts[2], ts[3])]
+    for _ in range(max_len + 1):
+        out += level
+        level = [(toks + (t,),) + ts_advance(h, t, ts[0], ts[1], ts[2]) for toks, h, r in level for t in alphabet
+                 if r[0] <= t < r[1] or r[2] <= t < r[3]]
+    return out, sum(len(alphabet) ** n for n in range(max_len + 1)) - len(out)
+
+
+# ---------------------------------------------------------------- the bookkeeping kernels of a round (spec.hip), on plain lists
+# A state `st` is a dict of nested lists in the device's shapes: tseq / dseq [n_ctx][G], the [.][4] state arrays (tts_hist,
+# tts_rng, dts_hist, dts_rng, chist, crng, dchist, dcrng, stats), wtok / wlp [G * w], acc / done / budget [G], logprob
+# [max_new][G], script [G][max_new] or None, pos.  tts / dts: a model's rule parameters (ts_begin, eot, n_vocab, max_initial),
+# None = its rules are off.  Each function returns a dict of the arrays the kernel writes, whole and new; st is not modified.
+def _copy(a):
+    return [list(r) if isinstance(r, (list, tuple)) else r for r in a]
+
+
+def adopt_ref(st, G, n_prompt, tts, dts):
+    """The draft adopts the target's first generated token (position n_prompt): its token buffer takes it, the statistics
+    start at zero, the target's state after its first close becomes the committed one, and the draft's state -- running and
+    committed -- is the initial history advanced by that token with the draft's own parameters."""
+    out = {k: _copy(st[k]) for k in ("dseq", "stats")}
+    for c in range(G):
+        out["dseq"][n_prompt][c] = st["tseq"][n_prompt][c]
+        out["stats"][c] = [0, 0, 0, 0]
+    if tts is not None:
+        out["chist"], out["crng"] = _copy(st["chist"]), _copy(st["crng"])
+        for c in range(G):
+            out["chist"][c], out["crng"][c] = list(st["tts_hist"][c]), list(st["tts_rng"][c])
+    if dts is not None:
+        for k in ("dts_hist", "dts_rng", "dchist", "dcrng"):
+            out[k] = _copy(st[k])
+        for c in range(G):
+            h, r = ts_advance(ts_start(dts[0], dts[2], dts[3])[0], st["tseq"][n_prompt][c], dts[0], dts[1], dts[2])
+            out["dts_hist"][c], out["dchist"][c] = list(h), list(h)
+            out["dts_rng"][c], out["dcrng"][c] = list(r), list(r)
+    return out
+
+
+def stage_ref(st, G, w, n_prompt, n_ctx, max_new, n_vocab, tts):
+    """The proposals d[0 .. w - 1) of window c go to positions pos + 1 .. pos + w - 1 of the target's token buffer, as far as
+    the context reaches: the script's entry for that generated index where there is one, else the draft's token at that
+    position, clamped into the vocabulary.  Row (c, s) of the verify step gets the ranges behind d[0 .. s), replayed from the
+    window's committed state; row (c, 0) the committed ranges themselves."""
+    pos = st["pos"]
+    out = {"tseq": _copy(st["tseq"])}
+    if tts is not None:
+        out["tts_rng"] = _copy(st["tts_rng"])
+    for c in range(G):
+        d = []
+        for p in range(pos + 1, min(pos + w, n_ctx)):
+            gi = p - n_prompt
+            t = st["script"][c][gi] if st["script"] is not None and 0 <= gi < max_new else st["dseq"][p][c]
+            d.append(min(max(t, 0), n_vocab - 1))
+            out["tseq"][p][c] = d[-1]
+        if tts is not None:
+            out["tts_rng"][c * w] = list(st["crng"][c])
+            for s in range(1, len(d) + 1):
+                out["tts_rng"][c * w + s] = list(ts_replay(st["chist"][c], st["crng"][c], d[:s], tts)[1])
+    return out
+
+
+def commit_ref(st, G, w, n_prompt, n_ctx, max_new, eot, pad_tok, tts, dts):
+    """The lockstep cut (spec_round) and what follows from it.  A live window keeps m = min(n, its own tokens) winners and their
+    log-probs and pads up to n (token pad_tok, log-prob 0; log-probs only inside max_new); a frozen window pads all n.  The
+    target's committed state advances along the m kept tokens.  Both positions become pos + n, the draft's token buffer takes
+    the target's token there, and the draft's state, running and committed, is its committed one advanced along the n tokens
+    the group moved by, with the draft's parameters.  wlp values are copied as given (the tests pass bit patterns)."""
+    pos = st["pos"]
+    g0 = pos + 1 - n_prompt
+    acc = [st["acc"][c] for c in range(G)]
+    live = [1 if st["done"][c] == 0 else 0 for c in range(G)]
+    eot_at, left = [-1] * G, [0] * G
+    for c in range(G):
+        if not live[c]:
+            continue
+        own = st["wtok"][c * w:c * w + acc[c] + 1]
+        if eot >= 0 and eot in own:
+            eot_at[c] = own.index(eot)
+        left[c] = min(max_new, st["budget"][c] if st["budget"] is not None else max_new) - g0
+    n, live_out, inc = spec_round(w, acc, live, eot_at, left)
+    out = {k: _copy(st[k]) for k in ("tseq", "dseq", "logprob", "done", "stats")}
+    for k in ("chist", "crng") if tts is not None else ():
+        out[k] = _copy(st[k])
+    for k in ("dts_hist", "dts_rng", "dchist", "dcrng") if dts is not None else ():
+        out[k] = _copy(st[k])
+    for c in range(G):
+        m = min(n, window_own(acc[c], eot_at[c], left[c])) if live[c] else 0
+        toks = st["wtok"][c * w:c * w + m] + [pad_tok] * (n - m)
+        lps = st["wlp"][c * w:c * w + m] + [0] * (n - m)
+        for i in range(n):
+            out["tseq"][pos + 1 + i][c] = toks[i]
+            if 0 <= g0 + i < max_new:
+                out["logprob"][g0 + i][c] = lps[i]
+        if live[c]:
+            out["done"][c] = 0 if live_out[c] else 1
+            out["stats"][c] = [a + b for a, b in zip(st["stats"][c], inc[c])]
+        if tts is not None and m > 0:
+            h, r = ts_replay(st["chist"][c], st["crng"][c], toks[:m], tts)
+            out["chist"][c], out["crng"][c] = list(h), list(r)
+        if n > 0:
+            out["dseq"][pos + n][c] = toks[n - 1]
+        if dts is not None:
+            h, r = ts_replay(st["dchist"][c], st["dcrng"][c], toks, dts)
+            out["dts_hist"][c], out["dchist"][c] = list(h), list(h)
+            out["dts_rng"][c], out["dcrng"][c] = list(r), list(r)
+    n_live = sum(live_out)
+    out.update(n_live=n_live, round=[n_live, pos + n], tpos=pos + n, dpos=pos + n)
+    return out
 
 
 def walk_group(plain, lens, script, n_prompt, max_new, k, eot, budgets=None, trace=None):

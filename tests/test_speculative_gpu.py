@@ -268,6 +268,89 @@ def test_results_do_not_depend_on_the_group_cut(pkg, models, mel):
         _rules((tgt, other), False)
 
 
+# ---------------------------------------------------------------- 5b. groups as large as the product cuts them
+def _win_many(B):
+    """_win for any B: the seeks wrap inside the recordings (the same windows as _win up to B = 67)"""
+    b = np.arange(B)
+    return (b % 5).astype(np.int64) * 240000, 3000, ((37 * b + 11) % 2500).astype(np.int32), (200 + 60 * (b % 5)).astype(np.int32)
+
+
+def _plain_many(pkg, ctx, mel, B):
+    base, mlen, seek, nf = _win_many(B)
+    opts = pkg.binding.wm_decode_opts(0.0, 0, NS_TOK, 0)
+    return ctx.transcribe_mel_raw(mel, base, mlen, seek, nf, _prompts(B), NEW, EOT, opts, logprobs=True, no_speech=True)
+
+
+def _spec_many(ctx, draft, mel, B, k, script=None):
+    base, mlen, seek, nf = _win_many(B)
+    if script is not None:
+        ctx.set_spec_script(script)
+    return ctx.transcribe_mel_speculative(draft, mel, base, mlen, seek, nf, _prompts(B), NEW, k, eot=EOT, no_speech_token=NS_TOK)
+
+
+def _misses(trace, c, row, k):
+    """the rounds of full width in which window c, live, missed at proposal `row`"""
+    return sum(1 for w, live, acc, n in trace if w == k + 1 and live[c] and acc[c] == row)
+
+
+def _corrupt_rows(want, windows, k):
+    """the plain call's tokens with, in each window of `windows`, one wrong proposal that meets the verify step as proposal 0
+    and one as proposal k - 1, the last one a panel of k + 1 rows compares (found by walking the call: where an index lands
+    depends on every miss in front of it).  Returns the script and the (window, row) pairs that were placed."""
+    script, placed = np.array(want[0], dtype=np.int32), []
+    for c in windows:
+        for row in sorted({0, k - 1}):
+            trace = []
+            _walk(want, script, k, EOT, trace=trace)
+            before = _misses(trace, c, row, k)
+            for i in range(1, int(want[1][c])):
+                if script[c, i] != want[0][c, i]:
+                    continue
+                trial, trace = _corrupt(script, [(c, i)]), []
+                _walk(want, trial, k, EOT, trace=trace)
+                if _misses(trace, c, row, k) == before + 1:
+                    script = trial
+                    placed.append((c, row))
+                    break
+    return script, placed
+
+
+@pytest.mark.parametrize("B,k", [(64, 1), (42, 2)])
+def test_one_group_at_the_row_bound(pkg, models, mel, B, k):
+    """B (k + 1) = 128 / 126 rows: ONE decode group as wide as a verify step can be, windows 6 .. 63 of a group included"""
+    tgt, _, _, other = models
+    assert S.spec_groups(B, k)[1] == [B] and (B + 1) * (k + 1) > S.DEC_MAXB
+    _rules((tgt, other), True)
+    try:
+        want = _plain_many(pkg, tgt, mel, B)
+        windows = [0, 5, 6, 31, 41, B - 1]
+        script, placed = _corrupt_rows(want, windows, k)
+        # every listed window whose transcript is long enough has both misses (k = 1: they are one)
+        long_enough = [c for c in windows if want[1][c] >= 2 * (k + 1) + 2]
+        assert len(long_enough) >= 3, want[1][windows]
+        assert all((c, row) in placed for c in long_enough for row in {0, k - 1}), (placed, want[1][windows])
+        r = _spec_many(tgt, other, mel, B, k, script=script)
+        _same(r, want, ("row bound", B, k))
+        assert r.stats.tolist() == [list(s) for s in _walk(want, script, k, EOT)]
+        assert k == 1 or np.any(r.kept < r.accepted)      # (k = 1: the one token a cut leaves IS the accepted proposal)
+    finally:
+        _rules((tgt, other), False)
+
+
+def test_several_groups_of_an_unrelated_draft(pkg, models, mel):
+    tgt, _, _, other = models
+    B, k = 130, 3
+    assert S.spec_groups(B, k)[1] == [26] * 5
+    _rules((tgt, other), True)
+    try:
+        want = _plain_many(pkg, tgt, mel, B)
+        r = _spec_many(tgt, other, mel, B, k)
+        _same(r, want, ("several groups", B, k))
+        assert np.all(r.kept <= r.accepted) and np.all(r.accepted <= r.proposed) and np.all(r.rounds <= NEW - 1)
+    finally:
+        _rules((tgt, other), False)
+
+
 # ---------------------------------------------------------------- 6. the accept and commit kernels alone
 def _key(v, n):
     u = int(np.float32(v).view(np.uint32))
