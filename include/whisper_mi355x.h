@@ -724,6 +724,43 @@ WM_API int wm_set_sequence_bias(wm_ctx *ctx, const int32_t *tokens, const int32_
                                 const float *bias /* [n_seq] */, const uint8_t *boost_prefixes /* [n_seq], nullable */,
                                 int n_seq, int32_t eot);
 
+/* Row tables: a sequence-bias table PER ROW of a call, so that requests with different phrase lists (a call's agent roster, a
+ * meeting's attendees, a customer's catalogue) decode in ONE batched call instead of one context and one call per table.
+ *   Tables: wm_set_sequence_bias_tables gives the context n_tables tables; table t is sequences [table_offsets[t],
+ *     table_offsets[t + 1]) of the n_seq = table_offsets[n_tables] sequences, which are given exactly as for
+ *     wm_set_sequence_bias.  Every table is checked and expanded ON ITS OWN by that call's rules and limits (32 tokens,
+ *     WM_MAX_BIAS_ENTRIES entries after the expansion; duplicates are invalid within a table only); a table may be empty.  At most
+ *     WM_MAX_BIAS_TABLES tables and WM_MAX_BIAS_POOL entries after the expansion, all tables together.
+ *   Rows: wm_set_bias_rows names the table of every row of the NEXT transcribe call on the context, like wm_set_token_budgets: it
+ *     is consumed by that call whatever happens, and n must equal its B.  Row b (a chunk, a window) uses table table_of_row[b];
+ *     -1: no bias.  Every candidate of a best-of window and every beam of a beam window uses its window's table.  n = 0 drops a
+ *     pending map.  WM_ERR_STATE when the context has no tables; WM_ERR_INVALID for an index outside [-1, n_tables).
+ *   A row with table t gives, bit for bit, what the same call gives that row with t as the context's single table: history,
+ *     match, the f32 total in table order, bans, boosted prefixes and the order with the repetition rules are
+ *     wm_set_sequence_bias's over that table alone.  A row on -1 or on an empty table decodes as with the bias off (the call
+ *     still runs the extended decode).
+ *   Exclusive with the single table: a successful wm_set_sequence_bias_tables replaces it; wm_set_sequence_bias with n_seq > 0
+ *     replaces the tables, with n_seq = 0 it clears both.  n_tables = 0 clears the tables and a pending map (the other pointers
+ *     may then be NULL).  Either call drops a pending map.
+ *   Scope: every entry the single table serves.  With tables in force a transcribe call WITHOUT a pending map answers
+ *     WM_ERR_STATE; a map whose n differs from the call's B, or with an index outside [-1, n_tables), WM_ERR_INVALID.
+ *     wm_transcribe_mel_speculative and the all-f32 debug path answer WM_ERR_STATE, as for the single table, and so does
+ *     wm_multi_transcribe_greedy on a device context with tables (not built).  The teacher-forced calls stay raw.  Applied to
+ *     every lane, copied by later wm_clone's.
+ * WM_ERR_INVALID -- and whatever was in force stays -- for anything wm_set_sequence_bias refuses in any table, table_offsets that
+ * do not start at 0, decrease or (through seq_offsets) leave the sequences, more than WM_MAX_BIAS_TABLES tables, a pool above
+ * WM_MAX_BIAS_POOL entries.
+ * Cost, measured: the single table's per position plus 0 .. 2 us -- large-v2 x 56 rows + 13.5 us with
+ * 8 entries per row, + 30.8 us with full tables of 4096 entries that all match (single table, same build: + 13.4 / + 29.0); the
+ * state launch walks each row's own table instead of the one table, the logits launch and its epilogue are the same. */
+#define WM_MAX_BIAS_TABLES 1024     /* tables of one context                                  */
+#define WM_MAX_BIAS_POOL   65536    /* entries after prefix expansion, all tables together    */
+WM_API int wm_set_sequence_bias_tables(wm_ctx *ctx, const int32_t *tokens, const int32_t *seq_offsets /* [n_seq + 1] */,
+                                       const float *bias, const uint8_t *boost_prefixes /* nullable */,
+                                       const int32_t *table_offsets /* [n_tables + 1], into the sequences */,
+                                       int n_tables, int32_t eot);
+WM_API int wm_set_bias_rows(wm_ctx *ctx, const int32_t *table_of_row /* [n], -1 .. n_tables - 1 */, int n);
+
 /* Per-chunk token budgets for the NEXT wm_transcribe_greedy call on this context (consumed by it; n must equal that
  * call's B): chunk i generates at most budgets[i] tokens (clamped to max_new), lens_out[i] <=
  * budgets[i].  A chunk that has reached its budget -- like one that has emitted `eot` -- LEAVES the decode: its caches are

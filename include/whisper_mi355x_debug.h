@@ -189,6 +189,30 @@ WM_API int wmdbg_seqbias_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx
                                const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq, int32_t eot,
                                uint32_t *hit_out, uint32_t *ban_out, int32_t *cnt_out, int32_t *id_out, float *total_out,
                                int32_t *woff_out);
+/* Row tables (wm_set_sequence_bias_tables) on the host, no context and no device: the tables as that call takes them with V as the
+ * vocabulary, each checked and expanded on its own and concatenated into the pool.  counts_out i32 [3] = tables, groups, entries;
+ * the other outputs (each may be NULL: call once for the counts) = tab_grp i32 [tables + 1] (table t is groups [tab_grp[t],
+ * tab_grp[t + 1])), grp_id i32 [groups], grp_beg i32 [groups + 1] (absolute into the pool's entries; nothing written for 0
+ * tables), ent_len i32 / ent_bias f32 [entries], ent_ctx i32 [entries][31] newest token first.  WM_ERR_INVALID -- and nothing
+ * written -- where wm_set_sequence_bias_tables answers it. */
+WM_API int wmdbg_sb_expand_tables(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes,
+                                  const int32_t *table_offsets, int n_tables, int32_t eot, int V, int32_t *counts_out,
+                                  int32_t *tab_grp_out, int32_t *grp_id_out, int32_t *grp_beg_out, int32_t *ent_len_out,
+                                  float *ent_bias_out, int32_t *ent_ctx_out);
+/* The per-row group ranges a decode group uploads under row tables (tx_plan.cpp wm_group_bias_rows; the group-tables dump of
+ * wmdbg_group_tables is left as it is): table_of_row i32 [B] of the call (wm_set_bias_rows), the group of windows [b0, b0 + Cg) x N
+ * candidates, tab_grp [n_tables + 1] -> rng_out i32 [Cg * N][2] = (first group, end group) of each decoder row; (0, 0) for -1. */
+WM_API int wmdbg_group_bias_rows(const int32_t *table_of_row, int B, const int32_t *tab_grp, int n_tables, int b0, int Cg, int N,
+                                 int32_t *rng_out);
+/* The state kernel of the row tables alone (seqbias_rows.hip), as wmdbg_seqbias_state: the tables as for
+ * wm_set_sequence_bias_tables (n_tables >= 1), table_of_row i32 [B] in [-1, n_tables).  ban_in NULL: behind wm_repeat_state with
+ * empty rules, as the product runs it; else u32 [B][words] the ban words as given and NO wm_repeat_state launch -- what the kernel
+ * leaves alone shows.  Outputs as wmdbg_seqbias_state's, pre-filled with 0xff bytes. */
+WM_API int wmdbg_seqbias_rows_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V,
+                                    const int32_t *tokens, const int32_t *seq_offsets, const float *bias,
+                                    const uint8_t *boost_prefixes, const int32_t *table_offsets, int n_tables, int32_t eot,
+                                    const int32_t *table_of_row, const uint32_t *ban_in, uint32_t *hit_out, uint32_t *ban_out,
+                                    int32_t *cnt_out, int32_t *id_out, float *total_out, int32_t *woff_out);
 /* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_step) and the offsets of seed, logits and
  * stats_tail_nonzero (host only). */
 WM_API int wmdbg_step_layout(int32_t *out4);

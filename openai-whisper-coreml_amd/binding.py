@@ -1069,6 +1069,8 @@ class _RoundRows:
         o = self.o
         extra = fallback_step_extra(t, o.best_of, o.length_penalty, o.beam_size, o.patience)
         prompts = [self.prompts[i] for i in todo] if o.ragged else self.prompts[todo]
+        if o.rec_tables is not None:   # 22.: the tables of exactly this call's rows (a clip: its recording's)
+            o.ctx.set_bias_rows([o.rec_tables[self.units[i].rec] for i in todo])
         kw = dict(eot=o.eot, temperature=t, seed=sd, no_speech_token=o.no_speech_token, sample_ids=[self.ids[i] for i in todo],
                   **o.sot_kw, **extra)
         if o.words_decode:   # 18.: every attempt through the aligned entry; the kept one's start frames feed the word step
@@ -1261,6 +1263,34 @@ def long_bias_table(sequence_bias, bad_words, boost_phrases, phrase_boost):
     return table, boost
 
 
+def long_recording_tables(recording_bias, R):
+    """transcribe_long's recording_bias as the tables of Context.set_sequence_bias_tables: (tables [{token tuple: bias}], boosts
+    [[token tuple]], table_of_recording [R] with -1 for None).  An entry is None or a dict with any of sequence_bias, bad_words,
+    boost_phrases, phrase_boost, turned into a table by long_bias_table (an entry whose three lists are all None reads as None);
+    equal tables -- the same entries in the same order with the same boosted keys -- are stored once."""
+    entries = list(recording_bias)
+    if len(entries) != R:
+        raise ValueError("recording_bias: one entry per recording")
+    tables, boosts, of, seen = [], [], [], {}
+    for e in entries:
+        if e is None:
+            of.append(-1)
+            continue
+        if not isinstance(e, dict) or set(e) - {"sequence_bias", "bad_words", "boost_phrases", "phrase_boost"}:
+            raise ValueError("recording_bias: an entry is None or a dict of sequence_bias, bad_words, boost_phrases, phrase_boost")
+        t = long_bias_table(e.get("sequence_bias"), e.get("bad_words"), e.get("boost_phrases"), e.get("phrase_boost"))
+        if t is None:
+            of.append(-1)
+            continue
+        key = (tuple(t[0].items()), tuple(t[1]))
+        if key not in seen:
+            seen[key] = len(tables)
+            tables.append(t[0])
+            boosts.append(t[1])
+        of.append(seen[key])
+    return tables, boosts, of
+
+
 def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_speech_token, lang_first=None,
                     lang_last=None, language=None, sot_prev=None, initial_prompt_tokens=None, recording_ids=None,
                     temperatures=FALLBACK_TEMPERATURES, compression_ratio_threshold="auto", logprob_threshold=-1.0,
@@ -1270,7 +1300,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
-                    boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None):
+                    boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None, recording_bias=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1413,6 +1443,18 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        restored afterwards.  Best-of, beam-search and speculative steps ignore it.  ValueError before any library call for
        anything but None or an integer 1 .. 8.  With None the function makes exactly the calls it made before the argument
        existed.
+    22. recording_bias (None; a list of R entries): 17. PER RECORDING, in the same batched calls.  Entry r is None (no bias) or a
+       dict with any of sequence_bias / bad_words / boost_phrases / phrase_boost, which long_bias_table turns into recording
+       r's table exactly as 17. does for the run's one table (long_recording_tables; equal tables are stored once).  The tables
+       are set ONCE behind the log-mel (Context.set_sequence_bias_tables, eot is this call's eot; behind the repetition rules
+       of 15), and in front of EVERY decode call -- every fallback step's rows, from the mel or from a reuse_encoder set, best-of,
+       beam and aligned steps alike -- Context.set_bias_rows names the tables of exactly that call's rows; with parallel_clips a
+       clip takes its recording's table.  A row then decodes, bit for bit, as the run of its recording alone with its table as
+       17.'s.  The tables are cleared again when the function leaves, also on an exception.  Where NO entry has a table
+       (all None, or dicts whose three lists are None) the function makes the plain run's calls: nothing is set.
+       ValueError before any library call: together with sequence_bias, bad_words or boost_phrases, with draft, for anything
+       but one entry per recording, for an unknown key and for what long_bias_table refuses.  With None the function makes
+       exactly the calls it made before the argument existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1426,6 +1468,16 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     R = len(recordings)
     o.early(R)
     bias_table = long_bias_table(sequence_bias, bad_words, boost_phrases, phrase_boost)   # 17. (None: off)
+    o.rec_tables = None   # 22.: the table of every recording (None: off)
+    if recording_bias is not None:
+        if bias_table is not None:
+            raise ValueError("recording_bias cannot be combined with sequence_bias, bad_words or boost_phrases: a context has "
+                             "one table or a table per row")
+        if draft is not None:
+            raise ValueError("draft (speculative decoding) cannot be combined with a sequence bias")
+        rec_tables, rec_boosts, of_rec = long_recording_tables(recording_bias, R)
+        if rec_tables:   # no entry with a table: off (a map needs tables in force, and an all -1 map is the plain run)
+            o.rec_tables = of_rec
     ctx.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
     if draft is not None:   # 20.: the draft proposes under the same rules
         draft.set_timestamp_rules(True, timestamp_begin, eot, int(round(1.0 / TIME_PRECISION)))
@@ -1441,6 +1493,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                      0 if no_repeat_ngram_size is None else no_repeat_ngram_size, eot)
         if bias_table is not None:   # 17.
             ctx.set_sequence_bias(bias_table[0], bias_table[1], eot=eot)
+        if o.rec_tables is not None:   # 22.
+            ctx.set_sequence_bias_tables(rec_tables, rec_boosts, eot=eot)
         langs = _long_languages(o, d_mel, mel_offs, T)
         o.prompt_head()
         units = _long_units(o, out, langs, d_mel, mel_offs, T)
@@ -1496,6 +1550,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             try:
                 if bias_table is not None:
                     ctx.set_sequence_bias(None)
+                if o.rec_tables is not None:
+                    ctx.set_sequence_bias_tables(None)
             finally:
                 if rules:
                     ctx.set_repetition_rules(1.0, 0, eot)
@@ -1911,6 +1967,51 @@ class Context:
         flags = np.array([1 if k in marked else 0 for k in keys], dtype=np.uint8)
         _check(self.lib, fn(self.handle, _ptr(toks) if toks.size else None, _ptr(offs), _ptr(bias), _ptr(flags) if marked else None,
                             len(keys), eot))
+
+    def set_sequence_bias_tables(self, tables, boosts=None, eot=None):
+        """Row tables (wm_set_sequence_bias_tables): one sequence-bias table PER ROW of a call instead of one per context, so
+        that requests with different phrase lists decode in one batched call.  `tables`: a list of {tuple of token ids: bias},
+        each as set_sequence_bias takes it (an empty dict: a table without entries); `boosts`: per table the keys whose proper
+        prefixes are biased too (None: none).  Replaces the context's single table; set_sequence_bias replaces the tables.
+        Every transcribe call on the context then needs set_bias_rows in front of it.  None or [] clears the tables."""
+        fn = self.lib.wm_set_sequence_bias_tables
+        fn.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int32]
+        fn.restype = ctypes.c_int
+        eot = int(self.dims["n_vocab"]) if eot is None else int(eot)
+        if not tables:
+            _check(self.lib, fn(self.handle, None, None, None, None, None, 0, eot))
+            return
+        boosts = [()] * len(tables) if boosts is None else list(boosts)
+        if len(boosts) != len(tables):
+            raise ValueError("set_sequence_bias_tables: boosts has one entry per table")
+        keys, bias, flags, toffs = [], [], [], [0]
+        for table, boost in zip(tables, boosts):
+            own = [tuple(int(t) for t in k) for k in table]
+            marked = {tuple(int(t) for t in k) for k in boost or ()}
+            if not marked <= set(own):
+                raise ValueError("set_sequence_bias_tables: boosts names a sequence that is not in its table")
+            keys += own
+            bias += [float(v) for v in table.values()]
+            flags += [1 if k in marked else 0 for k in own]
+            toffs.append(len(keys))
+        toks = np.array([t for k in keys for t in k], dtype=np.int32)
+        offs = np.zeros(len(keys) + 1, dtype=np.int32)
+        offs[1:] = np.cumsum([len(k) for k in keys])
+        bias = np.array(bias, dtype=np.float32)
+        flags = np.array(flags, dtype=np.uint8)
+        toffs = np.array(toffs, dtype=np.int32)
+        _check(self.lib, fn(self.handle, _ptr(toks) if toks.size else None, _ptr(offs), _ptr(bias) if bias.size else None,
+                            _ptr(flags) if flags.any() else None, _ptr(toffs), len(tables), eot))
+
+    def set_bias_rows(self, rows):
+        """The table of every row of the NEXT transcribe call (wm_set_bias_rows; len == its B; consumed by it): an index into
+        the tables of set_sequence_bias_tables, or -1 (None reads as -1) for a row without a bias.  A best-of window's candidates
+        and a beam window's beams use their window's table.  [] drops a pending map."""
+        fn = self.lib.wm_set_bias_rows
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        fn.restype = ctypes.c_int
+        a = np.ascontiguousarray([-1 if r is None else int(r) for r in rows], dtype=np.int32)
+        _check(self.lib, fn(self.handle, _ptr(a) if a.size else None, int(a.size)))
 
     def set_lanes(self, n):
         """Decode groups one transcribe_greedy call keeps in flight (0: default = $WM_LANES or 3; 1: one group per call)."""

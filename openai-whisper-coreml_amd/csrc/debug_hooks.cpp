@@ -2210,6 +2210,99 @@ extern "C" int wmdbg_seqbias_state(wm_ctx *ctx, const int32_t *seq, int B, int n
     return WM_OK;
 }
 
+extern "C" int wmdbg_sb_expand_tables(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes,
+                                      const int32_t *table_offsets, int n_tables, int32_t eot, int V, int32_t *counts_out,
+                                      int32_t *tab_grp_out, int32_t *grp_id_out, int32_t *grp_beg_out, int32_t *ent_len_out,
+                                      float *ent_bias_out, int32_t *ent_ctx_out) {
+    WM_REQUIRE(counts_out && V >= 1, WM_ERR_INVALID, "wmdbg_sb_expand_tables: null counts / V < 1");
+    WM_REQUIRE(n_tables <= 0 || n_tables > WM_MAX_BIAS_TABLES || (table_offsets && table_offsets[n_tables] >= 0), WM_ERR_INVALID,
+               "wmdbg_sb_expand_tables: bad table_offsets");
+    WmSbPool p;
+    WM_TRY(wm_sb_expand_tables(tokens, seq_offsets, bias, boost_prefixes, table_offsets, n_tables,
+                               n_tables > 0 && n_tables <= WM_MAX_BIAS_TABLES ? table_offsets[n_tables] : 0, eot, V, &p));
+    counts_out[0] = p.n_tables(); counts_out[1] = p.t.n_groups(); counts_out[2] = p.t.n_entries();
+    if (tab_grp_out) std::copy(p.tab_grp.begin(), p.tab_grp.end(), tab_grp_out);
+    if (grp_id_out) std::copy(p.t.grp_id.begin(), p.t.grp_id.end(), grp_id_out);
+    if (grp_beg_out) std::copy(p.t.grp_beg.begin(), p.t.grp_beg.end(), grp_beg_out);
+    if (ent_len_out) std::copy(p.t.ent_len.begin(), p.t.ent_len.end(), ent_len_out);
+    if (ent_bias_out) std::copy(p.t.ent_bias.begin(), p.t.ent_bias.end(), ent_bias_out);
+    if (ent_ctx_out) std::copy(p.t.ent_ctx.begin(), p.t.ent_ctx.end(), ent_ctx_out);
+    return WM_OK;
+}
+
+extern "C" int wmdbg_group_bias_rows(const int32_t *table_of_row, int B, const int32_t *tab_grp, int n_tables, int b0, int Cg, int N,
+                                     int32_t *rng_out) {
+    WM_REQUIRE(table_of_row && tab_grp && rng_out && B >= 1 && n_tables >= 0 && b0 >= 0 && Cg >= 1 && b0 + Cg <= B && N >= 1 &&
+                   Cg * N <= WM_DEC_MAXB,
+               WM_ERR_INVALID, "wmdbg_group_bias_rows: bad geometry");
+    std::vector<int32_t> r;
+    wm_group_bias_rows(table_of_row, tab_grp, n_tables, b0, Cg, N, &r);
+    std::copy(r.begin(), r.end(), rng_out);
+    return WM_OK;
+}
+
+extern "C" int wmdbg_seqbias_rows_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V,
+                                        const int32_t *tokens, const int32_t *seq_offsets, const float *bias,
+                                        const uint8_t *boost_prefixes, const int32_t *table_offsets, int n_tables, int32_t eot,
+                                        const int32_t *table_of_row, const uint32_t *ban_in, uint32_t *hit_out, uint32_t *ban_out,
+                                        int32_t *cnt_out, int32_t *id_out, float *total_out, int32_t *woff_out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(seq && table_of_row && hit_out && ban_out && cnt_out && id_out && total_out && woff_out, WM_ERR_INVALID,
+               "wmdbg_seqbias_rows_state: null pointer");
+    WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && V >= 16 && n_ctx >= 1 && n_ctx <= 448 && pos >= 0 && pos < n_ctx && n_prompt >= 0 &&
+                   n_prompt <= n_ctx,
+               WM_ERR_INVALID, "wmdbg_seqbias_rows_state: bad geometry");
+    WM_REQUIRE(n_tables >= 1 && n_tables <= WM_MAX_BIAS_TABLES && table_offsets && table_offsets[n_tables] >= 0, WM_ERR_INVALID,
+               "wmdbg_seqbias_rows_state: bad tables");
+    WmSbPool p;
+    WM_TRY(wm_sb_expand_tables(tokens, seq_offsets, bias, boost_prefixes, table_offsets, n_tables, table_offsets[n_tables], eot, V, &p));
+    for (int b = 0; b < B; ++b)
+        WM_REQUIRE(table_of_row[b] >= -1 && table_of_row[b] < n_tables, WM_ERR_INVALID, "wmdbg_seqbias_rows_state: table of row %d", b);
+    std::vector<int32_t> rng;
+    wm_group_bias_rows(table_of_row, p.tab_grp.data(), n_tables, 0, B, 1, &rng);
+    const int words = ((V + 15) / 16 * 16 + 31) / 32;
+    const size_t cap = WM_MAX_BIAS_ENTRIES;
+    const int ng = p.t.n_groups(), ne = p.t.n_entries();
+    WmRepPar rpar;
+    rpar.p = 1.f; rpar.inv_p = 1.f; rpar.n = 0; rpar.eot = 0;   // the bitmaps' owner with empty rules, as the product runs it
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    const int *dseq, *dpos, *drng;
+    WmRepDev rd;
+    rd.words = words;
+    WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * B * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&drng, rng.data(), rng.size() * 4, s));
+    WM_TRY(pool.get(&rd.par, &rpar, sizeof(rpar), s));
+    WM_TRY(pool.get(&rd.seen, nullptr, (size_t)B * words * 4, s, 0xff));
+    if (ban_in) WM_TRY(pool.get(&rd.ban, ban_in, (size_t)B * words * 4, s));
+    else WM_TRY(pool.get(&rd.ban, nullptr, (size_t)B * words * 4, s, 0xff));
+    // the pool as the product lays it out (the kernel reads groups and entries the ranges name, nothing else)
+    WmSbDev d;
+    memset(&d, 0, sizeof(d));
+    WM_TRY(pool.get(&d.grp_id, ng ? p.t.grp_id.data() : nullptr, std::max<size_t>(ng, 1) * 4, s));
+    WM_TRY(pool.get(&d.grp_beg, p.t.grp_beg.data(), p.t.grp_beg.size() * 4, s));
+    WM_TRY(pool.get(&d.ent_len, ne ? p.t.ent_len.data() : nullptr, std::max<size_t>(ne, 1) * 4, s));
+    WM_TRY(pool.get(&d.ent_bias, ne ? p.t.ent_bias.data() : nullptr, std::max<size_t>(ne, 1) * 4, s));
+    WM_TRY(pool.get(&d.ent_ctx, ne ? p.t.ent_ctx.data() : nullptr, std::max<size_t>(ne, 1) * WM_SB_CTX * 4, s));
+    WM_TRY(pool.get(&d.e.hit, nullptr, (size_t)B * words * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.cnt, nullptr, (size_t)B * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.lid, nullptr, (size_t)B * cap * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.ltot, nullptr, (size_t)B * cap * 4, s, 0xff));
+    WM_TRY(pool.get(&d.e.woff, nullptr, (size_t)B * words * 4, s, 0xff));
+    d.e.words = words;
+    if (!ban_in) WM_TRY(wm_repeat_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, rd));
+    WM_TRY(wm_seqbias_rows_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, d, drng, rd.ban, words));
+    WM_HIP(hipMemcpyAsync(hit_out, d.e.hit, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(ban_out, rd.ban, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(cnt_out, d.e.cnt, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(id_out, d.e.lid, (size_t)B * cap * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(total_out, d.e.ltot, (size_t)B * cap * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(woff_out, d.e.woff, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
 extern "C" int wmdbg_repeat_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V, int ngram,
                                   int32_t eot, uint32_t *seen_out, uint32_t *ban_out) {
     WM_TRY(wm_ctx_make_current(ctx));

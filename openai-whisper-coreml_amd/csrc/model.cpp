@@ -119,6 +119,24 @@ static int alloc_seqbias_state(WmModel *m, hipStream_t s) {
     return WM_OK;
 }
 
+// the pool of the row tables at FULL capacity (WM_MAX_BIAS_POOL entries) and the per-row group ranges, once; the per-row state the
+// epilogue reads is the single table's (alloc_seqbias_state)
+static int alloc_seqbias_pool(WmModel *m, hipStream_t s) {
+    const size_t cap = WM_MAX_BIAS_POOL;
+    int *grp_id, *grp_beg, *ent_len, *ent_ctx;
+    float *ent_bias;
+    WM_TRY(dalloc_t(m, &grp_id, cap, s));
+    WM_TRY(dalloc_t(m, &grp_beg, cap + 1, s));
+    WM_TRY(dalloc_t(m, &ent_len, cap, s));
+    WM_TRY(dalloc_t(m, &ent_bias, cap, s));
+    WM_TRY(dalloc_t(m, &ent_ctx, cap * WM_SB_CTX, s));
+    WM_TRY(dalloc_t(m, &m->dsb_rng, (size_t)WM_DEC_MAXB * 2, s));
+    m->dsbt.ent_len = ent_len; m->dsbt.ent_bias = ent_bias; m->dsbt.ent_ctx = ent_ctx; m->dsbt.grp_beg = grp_beg;
+    m->dsbt.e = m->dsb.e;
+    m->dsbt.grp_id = grp_id;   // last: non-null = allocated
+    return WM_OK;
+}
+
 WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode) {
     WmStopDev t;
     memset(&t, 0, sizeof(t));
@@ -236,7 +254,7 @@ WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode) {
     WmSbDev t;
     memset(&t, 0, sizeof(t));
     if (!mode.sb) return t;
-    return m->dsb;
+    return mode.sbt ? m->dsbt : m->dsb;   // (row tables: the pool; par is null, the rows' ranges are m->dsb_rng)
 }
 
 // the bitmaps and the parameter block, once (captured graphs hold these addresses)
@@ -265,6 +283,52 @@ int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t) {
         WM_HIP(hipStreamSynchronize(s));   // (the table's vectors are the caller's)
     }
     m->sb_on = ne > 0; m->sb_groups = ng; m->sb_entries = ne;
+    // exclusive with the row tables: a table replaces them, the empty table clears both
+    m->sbt_on = false; m->sbt_groups = m->sbt_entries = 0; m->sbt_tab_grp.clear();
+    m->bias_rows_host.clear();
+    return WM_OK;
+}
+
+static int upload_seqbias_pool(WmModel *m, const WmSbDev &from, int ng, int ne, hipMemcpyKind kind, hipStream_t s) {
+    WM_HIP(hipMemcpyAsync((void *)m->dsbt.grp_beg, from.grp_beg, (size_t)(ng + 1) * 4, kind, s));
+    if (ng) WM_HIP(hipMemcpyAsync((void *)m->dsbt.grp_id, from.grp_id, (size_t)ng * 4, kind, s));
+    if (ne) {
+        WM_HIP(hipMemcpyAsync((void *)m->dsbt.ent_len, from.ent_len, (size_t)ne * 4, kind, s));
+        WM_HIP(hipMemcpyAsync((void *)m->dsbt.ent_bias, from.ent_bias, (size_t)ne * 4, kind, s));
+        WM_HIP(hipMemcpyAsync((void *)m->dsbt.ent_ctx, from.ent_ctx, (size_t)ne * WM_SB_CTX * 4, kind, s));
+    }
+    return WM_OK;
+}
+
+// One lane's tables.  "A refused call leaves whatever was in force" is about the ARGUMENTS: they are checked and expanded once
+// (wm_sb_expand_tables) before any lane is touched.  A device failure in here -- the pool's one allocation, a copy -- on lane k
+// leaves the lanes in front with the new pool and the others with the old state, as wm_model_set_sequence_bias does for its
+// table; the caller sets the tables again (or clears them) after such a WM_ERR_HIP / WM_ERR_NOMEM.
+int wm_model_set_sequence_bias_tables(wm_ctx *ctx, const WmSbPool &p) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m, WM_ERR_STATE, "context has no model");
+    const int nt = p.n_tables(), ng = p.t.n_groups(), ne = p.t.n_entries();
+    WM_REQUIRE(nt <= WM_MAX_BIAS_TABLES && ne <= WM_MAX_BIAS_POOL && ng <= ne && (nt == 0 || (int)p.t.grp_beg.size() == ng + 1) &&
+                   (int)p.t.ent_bias.size() == ne && p.t.ent_ctx.size() == (size_t)ne * WM_SB_CTX && (nt == 0 || p.tab_grp.back() == ng),
+               WM_ERR_INVALID, "sequence bias tables: malformed pool");
+    if (nt) {
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
+        WM_REQUIRE(((size_t)3 * ((m->vpad + 31) / 32) + WM_MAX_BIAS_ENTRIES + 512) * 4 <= 64 * 1024 && (m->vpad + 31) / 32 <= 2048, WM_ERR_INVALID,
+                   "sequence bias: a vocabulary of %d ids does not fit the state kernel's LDS", m->dims.n_vocab);
+        if (!m->drep_par) WM_TRY(alloc_repetition_state(m, ctx->stream));
+        if (!m->dsb.par) WM_TRY(alloc_seqbias_state(m, ctx->stream));
+        if (!m->dsbt.grp_id) WM_TRY(alloc_seqbias_pool(m, ctx->stream));
+        WmSbDev from;
+        memset(&from, 0, sizeof(from));
+        from.grp_id = p.t.grp_id.data(); from.grp_beg = p.t.grp_beg.data(); from.ent_len = p.t.ent_len.data();
+        from.ent_bias = p.t.ent_bias.data(); from.ent_ctx = p.t.ent_ctx.data();
+        WM_TRY(upload_seqbias_pool(m, from, ng, ne, hipMemcpyHostToDevice, ctx->stream));
+        WM_HIP(hipStreamSynchronize(ctx->stream));   // (the pool's vectors are the caller's)
+        m->sb_on = false; m->sb_groups = m->sb_entries = 0;   // replaces the single table
+    }
+    m->sbt_on = nt > 0; m->sbt_groups = ng; m->sbt_entries = ne;
+    m->sbt_tab_grp = p.tab_grp;
+    m->bias_rows_host.clear();
     return WM_OK;
 }
 
@@ -495,7 +559,7 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->teacher_panel = pm->teacher_panel;
     m->prompt_panel = pm->prompt_panel;
     m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
-    if (m->rep_on || pm->sb_on) WM_TRY(alloc_repetition_state(m, child->stream));
+    if (m->rep_on || pm->sb_on || pm->sbt_on) WM_TRY(alloc_repetition_state(m, child->stream));
     if (pm->sb_on) {   // the parent's device table, as the suppress bitmaps above
         WM_TRY(alloc_seqbias_state(m, child->stream));
         const size_t ng = (size_t)pm->sb_groups, ne = (size_t)pm->sb_entries;
@@ -505,6 +569,12 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
         WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_bias, pm->dsb.ent_bias, ne * 4, hipMemcpyDeviceToDevice, child->stream));
         WM_HIP(hipMemcpyAsync((void *)m->dsb.ent_ctx, pm->dsb.ent_ctx, ne * WM_SB_CTX * 4, hipMemcpyDeviceToDevice, child->stream));
         m->sb_on = true; m->sb_groups = pm->sb_groups; m->sb_entries = pm->sb_entries;
+    }
+    if (pm->sbt_on) {   // ... and the parent's pool of row tables
+        WM_TRY(alloc_seqbias_state(m, child->stream));
+        WM_TRY(alloc_seqbias_pool(m, child->stream));
+        WM_TRY(upload_seqbias_pool(m, pm->dsbt, pm->sbt_groups, pm->sbt_entries, hipMemcpyDeviceToDevice, child->stream));
+        m->sbt_on = true; m->sbt_groups = pm->sbt_groups; m->sbt_entries = pm->sbt_entries; m->sbt_tab_grp = pm->sbt_tab_grp;
     }
     WM_HIP(hipStreamSynchronize(child->stream));
     return WM_OK;
@@ -964,7 +1034,10 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
             WM_REQUIRE(mode.rep, WM_ERR_STATE, "decode step: the sequence bias needs the repetition-rule state");
             const WmSbDev sb = wm_model_sb_dev(m, mode);
             a.epi = DE_LOGITS_XB; a.sb = sb.e;
-            WM_TRY(wm_seqbias_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, sb, a.rep.ban, a.rep.words));
+            if (mode.sbt)   // row tables: each row walks its own table's groups of the pool
+                WM_TRY(wm_seqbias_rows_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, sb, m->dsb_rng, a.rep.ban, a.rep.words));
+            else
+                WM_TRY(wm_seqbias_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, sb, a.rep.ban, a.rep.words));
         }
         WM_TRY(wm_dec_gemv(ctx, a));
     }
@@ -1071,7 +1144,7 @@ int wm_model_prompt_prefill(wm_ctx *ctx, int G, int P0, const WmDecodeMode &mode
     WM_REQUIRE(mode.n_cand <= 1 && !mode.beam, WM_ERR_STATE, "prompt prefill: a plain decode group");
     WmDecodeMode pm = mode;
     pm.stop = false; pm.budget = false; pm.stop_eot = -1; pm.acap = false; pm.acap_base = pm.acap_Tq = pm.acap_J = 0; pm.acap_q = nullptr;
-    pm.rep = false; pm.sb = false; pm.mask = false; pm.ts = false; pm.x = false;
+    pm.rep = false; pm.sb = false; pm.sbt = false; pm.mask = false; pm.ts = false; pm.x = false;
     const int *off0 = mode.off ? m->doff : nullptr;
     const WmEmbedDev e = wm_model_embed_dev(m);
     const int T = m->dims.n_text_ctx;

@@ -168,6 +168,18 @@ struct WmSbTable {
 // WM_OK, or WM_ERR_INVALID with the message set; n_seq = 0 gives the empty table.  Pure host code (model_api.cpp).
 int wm_sb_expand(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes, int n_seq,
                  int32_t eot, int n_vocab, WmSbTable *out);
+// Row tables (wm_set_sequence_bias_tables): the expanded tables of a context CONCATENATED in the layout of WmSbDev -- the POOL.
+// grp_beg is absolute into the pool's entries (one array of n_groups + 1: a table's last boundary is the next one's first);
+// table t is groups [tab_grp[t], tab_grp[t + 1]), each table at most WM_MAX_BIAS_ENTRIES entries, the pool at most
+// WM_MAX_BIAS_POOL.  A row of a decode group walks its own table's group range (WmModel::dsb_rng, wm_seqbias_rows_state).
+struct WmSbPool {
+    WmSbTable t;                    // the pooled arrays (grp_beg: [n_groups + 1], {0} when the pool has no entry)
+    std::vector<int32_t> tab_grp;   // [n_tables + 1] (empty: no tables)
+    int n_tables() const { return tab_grp.empty() ? 0 : (int)tab_grp.size() - 1; }
+};
+// wm_sb_expand per table (sequences [table_offsets[t], table_offsets[t + 1])) and the concatenation.  Pure host code.
+int wm_sb_expand_tables(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes,
+                        const int32_t *table_offsets, int n_tables, int n_seq, int32_t eot, int n_vocab, WmSbPool *out);
 
 // Early-stop state of a decode group (device view; done == null: off).  A row is DONE once it has emitted `eot`
 // (eot >= 0) or produced budget[b] tokens (budget != null); from then on its tokens are `pad_tok`, it is dropped from
@@ -288,6 +300,9 @@ struct WmDecodeMode {
     // The sequence bias applies (wm_set_sequence_bias, WmSbDev): wm_seqbias_state behind wm_repeat_state + DE_LOGITS_XB.  A group
     // with sb has rep too -- the bitmaps are wm_repeat_state's, rebuilt with the rules (1.0, 0) when the repetition rules are off.
     bool sb = false;
+    // Row tables (wm_set_sequence_bias_tables): the state kernel is wm_seqbias_rows_state over the pool and the group's per-row
+    // group ranges instead of wm_seqbias_state over the one table.  Implies sb and rep; the epilogue is the same DE_LOGITS_XB.
+    bool sbt = false;
     // Panel width of a teacher-forced pass (wm_set_teacher_panel; 1: none): the step's rows are windows x panel, row c * panel + s
     // is position *dpos + s of window c -- the self-attention cache holds one entry per WINDOW, row (c, s) appends at and reads up
     // to its own position, the cross-attention is the candidate-group launch (wm_model_panel_step).  The teacher-forced entries
@@ -301,7 +316,7 @@ struct WmDecodeMode {
     int acap_base = 0, acap_Tq = 0, acap_J = 0;
     float *acap_q = nullptr;
     bool operator==(const WmDecodeMode &o) const {
-        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && rep == o.rep && sb == o.sb && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && rep == o.rep && sb == o.sb && sbt == o.sbt && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -448,6 +463,15 @@ struct WmModel {
     bool sb_on = false;
     int sb_groups = 0, sb_entries = 0;
     WmSbDev dsb = {};
+    // row tables (wm_set_sequence_bias_tables; exclusive with the single table): each table's group range on the host, the pool
+    // on the device at full capacity (WM_MAX_BIAS_POOL; dsbt.par stays null, dsbt.e is dsb.e) and the group's per-row
+    // (first group, end group) pairs, uploaded at prefill -- allocated once, never moved
+    bool sbt_on = false;
+    int sbt_groups = 0, sbt_entries = 0;
+    std::vector<int32_t> sbt_tab_grp;   // [n_tables + 1]
+    WmSbDev dsbt = {};
+    int *dsb_rng = nullptr;             // [WM_DEC_MAXB][2]
+    std::vector<int32_t> bias_rows_host;   // wm_set_bias_rows: the table of each row of the NEXT call (empty: none pending)
     unsigned *dx_ids = nullptr;    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     int *dxkv_rows = nullptr;      // [WM_DEC_MAXB] the group's rows of a window set (wm_transcribe_windows): the gather's row map
@@ -540,6 +564,9 @@ int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t
 WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode);
 // an expanded table (empty: off) -> this context's device table; the first non-empty one allocates the state
 int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t);
+// the pooled tables (no tables: off) -> this context's device pool; the first non-empty set allocates it.  Replaces the single
+// table, as wm_model_set_sequence_bias replaces the tables.
+int wm_model_set_sequence_bias_tables(wm_ctx *ctx, const WmSbPool &p);
 int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int32_t eot, int32_t max_initial);
 int wm_model_set_suppress(wm_ctx *ctx, const int32_t *ids, int n, const int32_t *first_ids, int n_first);
 // Speculative decoding (wm_transcribe_mel_speculative, spec.hip): the device view of one decode group of G
@@ -801,6 +828,12 @@ int wm_repeat_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int 
 // of this one has rebuilt.  V: ids at or above it set no bit.
 int wm_seqbias_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int n_prompt, int n_ctx, int V, const WmSbDev &sb,
                      unsigned *ban, int ban_words);
+// seqbias_rows.hip (row tables)
+// The same rebuild with a table per row: `pool` holds the concatenated tables (WmSbPool; pool.par is not read), row b walks groups
+// [rng[2 * b], rng[2 * b + 1]) of it -- at most WM_MAX_BIAS_ENTRIES groups; an empty range (no table, an empty table) gives an
+// all-zero hit row, cnt 0 and leaves the row's ban words alone.
+int wm_seqbias_rows_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int n_prompt, int n_ctx, int V, const WmSbDev &pool,
+                          const int *rng, unsigned *ban, int ban_words);
 
 // xkv_rows.hip (window sets)
 // Copy whole windows between a decode group's cross-attention K/V cache, group [L2][group_rows][slab] (slab = H * 1500 * 64

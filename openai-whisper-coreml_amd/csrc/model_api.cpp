@@ -146,6 +146,85 @@ extern "C" int wm_set_sequence_bias(wm_ctx *ctx, const int32_t *tokens, const in
     WM_REQUIRE(t.n_entries() == 0 || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
     return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { return wm_model_set_sequence_bias(c, t); });
 } WM_API_CATCH
+// The tables of wm_set_sequence_bias_tables: every table checked and expanded on its own (wm_sb_expand), then concatenated --
+// grp_beg shifted by the entries in front, so it is absolute into the pool and one array of n_groups + 1 serves all tables.
+int wm_sb_expand_tables(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes,
+                        const int32_t *table_offsets, int n_tables, int n_seq, int32_t eot, int n_vocab, WmSbPool *out) {
+    *out = WmSbPool();
+    WM_REQUIRE(n_tables >= 0 && n_tables <= WM_MAX_BIAS_TABLES, WM_ERR_INVALID, "sequence bias tables: %d tables (0 .. %d)", n_tables,
+               WM_MAX_BIAS_TABLES);
+    WM_REQUIRE(eot >= 0 && eot <= n_vocab, WM_ERR_INVALID, "sequence bias: eot %d outside [0, %d]", eot, n_vocab);
+    if (n_tables == 0) return WM_OK;
+    WM_REQUIRE(table_offsets, WM_ERR_INVALID, "sequence bias tables: null table_offsets");
+    WM_REQUIRE(table_offsets[0] == 0 && table_offsets[n_tables] == n_seq, WM_ERR_INVALID,
+               "sequence bias tables: table_offsets must run from 0 to the %d sequences", n_seq);
+    for (int t = 0; t < n_tables; ++t)
+        WM_REQUIRE(table_offsets[t + 1] >= table_offsets[t], WM_ERR_INVALID, "sequence bias tables: table_offsets decrease at table %d", t);
+    WM_REQUIRE(n_seq == 0 || (tokens && seq_offsets && bias), WM_ERR_INVALID, "sequence bias: null pointer");
+    WM_REQUIRE(n_seq == 0 || seq_offsets[0] == 0, WM_ERR_INVALID, "sequence bias: seq_offsets[0] must be 0");
+    WmSbPool p;
+    p.tab_grp.push_back(0);
+    p.t.grp_beg.push_back(0);
+    std::vector<int32_t> offs;
+    for (int t = 0; t < n_tables; ++t) {
+        const int s0 = table_offsets[t], n = table_offsets[t + 1] - s0;
+        WmSbTable one;
+        if (n > 0) {   // the table's own offsets from 0, as wm_set_sequence_bias takes them
+            WM_REQUIRE(n <= WM_MAX_BIAS_ENTRIES, WM_ERR_INVALID, "sequence bias: table %d has %d sequences, at most %d entries", t, n,
+                       WM_MAX_BIAS_ENTRIES);
+            offs.resize((size_t)n + 1);
+            for (int i = 0; i <= n; ++i) {
+                const long o = (long)seq_offsets[s0 + i] - seq_offsets[s0];
+                WM_REQUIRE(o >= 0 && o <= (long)WM_MAX_BIAS_ENTRIES * WM_MAX_BIAS_SEQ_LEN, WM_ERR_INVALID,
+                           "sequence bias: seq_offsets of table %d decrease or run away", t);
+                offs[i] = (int32_t)o;
+            }
+            WM_TRY(wm_sb_expand(tokens + seq_offsets[s0], offs.data(), bias + s0, boost_prefixes ? boost_prefixes + s0 : nullptr, n, eot,
+                                n_vocab, &one));
+        }
+        const int e0 = p.t.n_entries();
+        WM_REQUIRE(e0 + one.n_entries() <= WM_MAX_BIAS_POOL, WM_ERR_INVALID,
+                   "sequence bias tables: more than %d entries after the prefix expansion, all tables together", WM_MAX_BIAS_POOL);
+        p.t.grp_id.insert(p.t.grp_id.end(), one.grp_id.begin(), one.grp_id.end());
+        for (int g = 0; g < one.n_groups(); ++g) p.t.grp_beg.push_back(e0 + one.grp_beg[g + 1]);
+        p.t.ent_len.insert(p.t.ent_len.end(), one.ent_len.begin(), one.ent_len.end());
+        p.t.ent_bias.insert(p.t.ent_bias.end(), one.ent_bias.begin(), one.ent_bias.end());
+        p.t.ent_ctx.insert(p.t.ent_ctx.end(), one.ent_ctx.begin(), one.ent_ctx.end());
+        p.tab_grp.push_back(p.t.n_groups());
+    }
+    *out = std::move(p);
+    return WM_OK;
+}
+
+extern "C" int wm_set_sequence_bias_tables(wm_ctx *ctx, const int32_t *tokens, const int32_t *seq_offsets, const float *bias,
+                                           const uint8_t *boost_prefixes, const int32_t *table_offsets, int n_tables, int32_t eot) try {
+    WM_MODEL(ctx);
+    // checked and expanded ONCE, before any lane is touched: a refused call leaves whatever was in force
+    WM_REQUIRE(n_tables >= 0 && n_tables <= WM_MAX_BIAS_TABLES, WM_ERR_INVALID, "sequence bias tables: %d tables (0 .. %d)", n_tables,
+               WM_MAX_BIAS_TABLES);
+    WM_REQUIRE(n_tables == 0 || table_offsets, WM_ERR_INVALID, "sequence bias tables: null table_offsets");
+    WM_REQUIRE(n_tables == 0 || table_offsets[n_tables] >= 0, WM_ERR_INVALID, "sequence bias tables: table_offsets end below 0");
+    WmSbPool p;
+    WM_TRY(wm_sb_expand_tables(tokens, seq_offsets, bias, boost_prefixes, table_offsets, n_tables, n_tables ? table_offsets[n_tables] : 0,
+                               eot, m->dims.n_vocab, &p));
+    WM_REQUIRE(n_tables == 0 || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { return wm_model_set_sequence_bias_tables(c, p); });
+} WM_API_CATCH
+extern "C" int wm_set_bias_rows(wm_ctx *ctx, const int32_t *table_of_row, int n) try {
+    WM_MODEL(ctx);
+    WM_REQUIRE(n >= 0 && (n == 0 || table_of_row), WM_ERR_INVALID, "set_bias_rows: bad list");
+    if (n == 0) {
+        m->bias_rows_host.clear();
+        return WM_OK;
+    }
+    WM_REQUIRE(m->sbt_on, WM_ERR_STATE, "set_bias_rows: the context has no sequence-bias tables (wm_set_sequence_bias_tables)");
+    const int nt = (int)m->sbt_tab_grp.size() - 1;
+    for (int i = 0; i < n; ++i)
+        WM_REQUIRE(table_of_row[i] >= -1 && table_of_row[i] < nt, WM_ERR_INVALID, "set_bias_rows: table %d of row %d outside [-1, %d)",
+                   table_of_row[i], i, nt);
+    m->bias_rows_host.assign(table_of_row, table_of_row + n);
+    return WM_OK;
+} WM_API_CATCH
 extern "C" int wm_set_teacher_panel(wm_ctx *ctx, int width) try {
     WM_MODEL(ctx);
     (void)m;

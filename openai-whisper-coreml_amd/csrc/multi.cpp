@@ -210,6 +210,10 @@ extern "C" int wm_multi_transcribe_greedy(wm_multi *m, const void *pcm, wm_dtype
     WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID, "bad pcm dtype");
     const int R = (int)m->ctx.size();
     WM_REQUIRE(R >= 1 && m->ctx[0]->model, WM_ERR_STATE, "multi_transcribe_greedy: no model");
+    // (row tables need a row map per device's slice of the call: not built)
+    for (int r = 0; r < R; ++r)
+        WM_REQUIRE(!m->ctx[r]->model || !m->ctx[r]->model->sbt_on, WM_ERR_STATE,
+                   "multi_transcribe_greedy does not support sequence-bias tables (device context %d has them)", r);
     {   // every size that feeds an allocation below is checked against the model BEFORE any thread exists
         const wm_dims &D = m->ctx[0]->model->dims;
         WM_REQUIRE(n_prompt >= 1 && n_prompt + max_new <= D.n_text_ctx, WM_ERR_INVALID,

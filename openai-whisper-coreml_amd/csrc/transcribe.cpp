@@ -177,6 +177,7 @@ struct TxCfg {
     int sot_tail = 0;
     std::vector<int32_t> hl, hh;
     int max_group_rows = 0;
+    const int32_t *bias_rows = nullptr;   // row tables in force: the table of each row of the call [B] (wm_set_bias_rows), checked
 };
 
 // the tokens row `b` of the call may generate
@@ -196,8 +197,9 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     j.mode.stop = stop.on; j.mode.budget = stop.on && stop.budgets != nullptr; j.mode.stop_eot = stop.on ? stop.eot : -1;
     j.mode.n_cand = N;
     j.mode.beam = call.beam ? N : 0;
-    j.mode.sb = m->sb_on;
-    j.mode.rep = m->rep_on || m->sb_on;   // (tx_validate turns the extended decode on with them; the bias reads the rules' bitmaps)
+    j.mode.sbt = m->sbt_on;
+    j.mode.sb = m->sb_on || m->sbt_on;
+    j.mode.rep = m->rep_on || j.mode.sb;   // (tx_validate turns the extended decode on with them; the bias reads the rules' bitmaps)
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
     if (call.aligned) {   // the capture buffer and the alignment workspace, reserved before anything is enqueued
@@ -251,7 +253,11 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
         WM_HIP(hipMemcpyAsync(m->drep_par, &j.rpar, sizeof(WmRepPar), hipMemcpyHostToDevice, c->stream));
     }
     // sequence bias: the table was uploaded when it was set; its counts go with the group, so a captured graph replays for any table
-    if (j.mode.sb) {
+    if (j.mode.sbt) {   // row tables: the pool was uploaded when it was set; the rows' group ranges go with the group likewise
+        WM_REQUIRE(cfg.bias_rows, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
+        wm_group_bias_rows(cfg.bias_rows, m->sbt_tab_grp.data(), (int)m->sbt_tab_grp.size() - 1, j.b0, Cg, N, &j.tab.sbr);
+        WM_HIP(hipMemcpyAsync(m->dsb_rng, j.tab.sbr.data(), j.tab.sbr.size() * 4, hipMemcpyHostToDevice, c->stream));
+    } else if (j.mode.sb) {
         j.sbpar.n_groups = m->sb_groups; j.sbpar.n_entries = m->sb_entries;
         WM_HIP(hipMemcpyAsync((void *)m->dsb.par, &j.sbpar, sizeof(WmSbPar), hipMemcpyHostToDevice, c->stream));
     }
@@ -509,7 +515,7 @@ int entry_checks(const TxCall &call) {
 // The checks every transcribe call goes through, and what they make of it: the call's longest prompt, the early stop, the
 // extended decode.  budgets: the call's (wm_set_token_budgets), clamped to max_new here.  opts == null with both extra
 // outputs null is the greedy decode exactly.
-int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg) {
+int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg, const std::vector<int32_t> *bias_rows = nullptr) {
     WmModel *m = ctx->model;
     const WmAudioSrc &src = call.src;
     const TxPrompts &p = call.prompts;
@@ -565,9 +571,18 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     WM_REQUIRE(!call.no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
     WM_REQUIRE(!call.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
     // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
-    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on;
+    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on;
     WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
-    WM_REQUIRE(!m->sb_on || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
+    WM_REQUIRE(!(m->sb_on || m->sbt_on) || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
+    if (m->sbt_on) {   // row tables: the call's row map (wm_set_bias_rows), one entry per row of the call
+        WM_REQUIRE(bias_rows, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
+        WM_REQUIRE((int)bias_rows->size() == B, WM_ERR_INVALID, "the bias row map was set for %d rows, the call has %d", (int)bias_rows->size(), B);
+        const int nt = (int)m->sbt_tab_grp.size() - 1;
+        for (int b = 0; b < B; ++b)
+            WM_REQUIRE((*bias_rows)[b] >= -1 && (*bias_rows)[b] < nt, WM_ERR_INVALID, "bias row map: table %d of row %d outside [-1, %d)",
+                       (*bias_rows)[b], b, nt);
+        cfg->bias_rows = bias_rows->data();
+    }
     xc.logprobs = call.logprobs_out;
     xc.no_speech = call.no_speech_out;
     const uint64_t seed = opts ? opts->seed : 0;
@@ -952,6 +967,9 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
     // that fails any check must not leave them armed for a later, unrelated call with the same B
     std::vector<int32_t> budgets;
     if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
+    // ... and so is the row map of the sequence-bias tables (wm_set_bias_rows)
+    std::vector<int32_t> bias_rows;
+    if (ctx && ctx->model) bias_rows.swap(ctx->model->bias_rows_host);
     WM_TRY(entry_checks(call));
     WM_MODEL(ctx);
     std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
@@ -960,7 +978,7 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
         call.logprobs_out = lp_own.data();
     }
     TxCfg cfg;
-    WM_TRY(tx_validate(ctx, call, budgets, &cfg));
+    WM_TRY(tx_validate(ctx, call, budgets, &cfg, bias_rows.empty() ? nullptr : &bias_rows));
     // the plan: decode groups and lanes.  A masked clone that cannot be made switches the masks off and asks again.
     WmTxPlanIn pin;
     pin.B = call.B; pin.N = call.n_cand;
@@ -1060,7 +1078,7 @@ int spec_checks(wm_ctx *ctx, const SpecCall &sc, const TxCall &call) {
     WM_REQUIRE(T == 0.f, WM_ERR_INVALID, "speculative decoding verifies the greedy choice: temperature must be 0 (got %g)", (double)T);
     WmModel *m = ctx->model, *dm = sc.draft->model;
     WM_REQUIRE(!m->rep_on, WM_ERR_STATE, "speculative decoding does not support the repetition rules set on this context");
-    WM_REQUIRE(!m->sb_on, WM_ERR_STATE, "speculative decoding does not support the sequence bias set on this context");
+    WM_REQUIRE(!m->sb_on && !m->sbt_on, WM_ERR_STATE, "speculative decoding does not support the sequence bias set on this context");
     WM_REQUIRE(!ctx->dbg_hooks && !sc.draft->dbg_hooks, WM_ERR_STATE, "speculative decoding is not supported by the all-f32 precision path");
     WM_REQUIRE(dm && dm->finalized, WM_ERR_STATE, "the draft's model weights are not finalised (wm_finalize)");
     WM_REQUIRE(sc.draft->device == ctx->device, WM_ERR_INVALID, "the draft context lives on device %d, the target on %d",
@@ -1069,7 +1087,7 @@ int spec_checks(wm_ctx *ctx, const SpecCall &sc, const TxCall &call) {
     WM_REQUIRE(a.n_mels == b.n_mels && a.n_vocab == b.n_vocab && a.n_text_ctx == b.n_text_ctx && a.n_audio_ctx == b.n_audio_ctx,
                WM_ERR_INVALID, "the draft's n_mels / n_vocab / n_text_ctx / n_audio_ctx (%d / %d / %d / %d) differ from the target's (%d / %d / %d / %d)",
                b.n_mels, b.n_vocab, b.n_text_ctx, b.n_audio_ctx, a.n_mels, a.n_vocab, a.n_text_ctx, a.n_audio_ctx);
-    WM_REQUIRE(!dm->rep_on && !dm->sb_on, WM_ERR_STATE, "the draft context has repetition rules or a sequence bias set");
+    WM_REQUIRE(!dm->rep_on && !dm->sb_on && !dm->sbt_on, WM_ERR_STATE, "the draft context has repetition rules or a sequence bias set");
     return WM_OK;
 }
 
@@ -1183,6 +1201,7 @@ int spec_group(wm_ctx *ctx, const SpecCall &sc, const TxCall &call, const TxCfg 
 int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
     std::vector<int32_t> budgets;   // consumed by this call whatever happens next (tx_transcribe)
     if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
+    if (ctx && ctx->model) ctx->model->bias_rows_host.clear();   // a pending row map likewise
     const int32_t *dbg_script = nullptr;   // the debug library's script is for this call only
     if (ctx && ctx->model) dbg_script = ctx->model->spec_dbg_script;
     struct ScriptScope {

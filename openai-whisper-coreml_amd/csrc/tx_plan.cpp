@@ -154,6 +154,7 @@ int wm_group_tables(const TxPrompts &p, int n_prompt, const int32_t *budgets, in
     if (!p.len) out->off.clear();
     out->bud.clear();
     out->ids.clear();
+    out->sbr.clear();
     if (budgets) {
         out->bud.resize(Bg);
         for (int b = 0; b < Bg; ++b) out->bud[b] = budgets[b0 + b / N];
@@ -168,6 +169,18 @@ int wm_group_tables(const TxPrompts &p, int n_prompt, const int32_t *budgets, in
         out->ids.assign(p.sample_ids + b0, p.sample_ids + b0 + Bg);
     }
     return P;
+}
+
+void wm_group_bias_rows(const int32_t *table_of_row, const int32_t *tab_grp, int n_tables, int b0, int Cg, int N,
+                        std::vector<int32_t> *out) {
+    const int Bg = Cg * N;
+    out->assign((size_t)Bg * 2, 0);
+    for (int b = 0; b < Bg; ++b) {
+        const int t = table_of_row[b0 + b / N];
+        if (t < 0 || t >= n_tables) continue;
+        (*out)[2 * b] = tab_grp[t];
+        (*out)[2 * b + 1] = tab_grp[t + 1];
+    }
 }
 
 void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, const int32_t *budgets, int32_t eot, int N, int b0,

@@ -70,6 +70,7 @@ struct TxGroupTables {
     std::vector<int32_t> off;    // a ragged call: row offsets [Bg] = P - len
     std::vector<int32_t> bud;    // token budgets [Bg] (a call with budgets)
     std::vector<unsigned> ids;   // a candidate group: [2][ids_stride] window ids | candidate words; else the rows' sample ids [Bg]
+    std::vector<int32_t> sbr;    // row tables (wm_set_bias_rows): [Bg][2] (first group, end group) of each row's table in the pool
 };
 
 // the right-aligned prompt table [P][Bg] and the row offsets [Bg] of rows [b0, b0 + Bg) of a ragged call; returns P
@@ -80,6 +81,13 @@ int wm_right_align(const int32_t *prompts, int stride, const int32_t *prompt_len
 // extended decode is on.  Returns P, the group's prompt positions (a ragged call: the longest prompt among ITS rows).
 int wm_group_tables(const TxPrompts &p, int n_prompt, const int32_t *budgets, int b0, int Cg, int N, int ids_stride, bool want_ids,
                     TxGroupTables *out);
+
+// The per-row group ranges of the same group under row tables (wm_set_sequence_bias_tables): decoder row b takes the table of
+// window b0 + b / N of the call -- table_of_row [B] of the call, -1: none; tab_grp [n_tables + 1]: table t is groups
+// [tab_grp[t], tab_grp[t + 1]) of the pool.  out [Bg][2]; a row without a table gets (0, 0).  An index outside [-1, n_tables)
+// is the caller's to refuse; here it reads as none.
+void wm_group_bias_rows(const int32_t *table_of_row, const int32_t *tab_grp, int n_tables, int b0, int Cg, int N,
+                        std::vector<int32_t> *out);
 
 // ---------------------------------------------------------------- a group's outputs ----
 // The output rows of a finished plain (not beam) group from its fetched streams gen [max_new][Bg], lp [max_new][Bg] (read

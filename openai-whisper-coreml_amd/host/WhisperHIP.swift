@@ -240,6 +240,42 @@ struct Whisper {
         try check(f(ctx, tokens, offsets, bias, flags.isEmpty ? nil : flags, Int32(sequences.count), eot))
     }
 
+    /// A sequence-bias table PER ROW (wm_set_sequence_bias_tables): `tables[t]` is a list of (sequence, bias, boostPrefixes) as
+    /// setSequenceBias takes them, checked and expanded on its own; it replaces the context's single table.  Every later transcribe
+    /// call needs setBiasRows in front of it.  An empty list clears the tables.
+    /// Not compiled in this repository (see the top of the file).
+    func setSequenceBiasTables(_ tables: [[(sequence: [Int32], bias: Float, boostPrefixes: Bool)]], eot: Int32 = 50257) throws {
+        typealias TablesFn = @convention(c) (OpaquePointer, UnsafePointer<Int32>?, UnsafePointer<Int32>?, UnsafePointer<Float>?,
+                                             UnsafePointer<UInt8>?, UnsafePointer<Int32>?, Int32, Int32) -> Int32
+        let f: TablesFn = try sym("wm_set_sequence_bias_tables")
+        if tables.isEmpty {
+            try check(f(ctx, nil, nil, nil, nil, nil, 0, eot))
+            return
+        }
+        var tableOffsets: [Int32] = [0]
+        var offsets: [Int32] = [0]
+        var tokens: [Int32] = [], bias: [Float] = [], flags: [UInt8] = []
+        for t in tables {
+            for e in t {
+                tokens += e.sequence
+                offsets.append(offsets.last! + Int32(e.sequence.count))
+                bias.append(e.bias)
+                flags.append(e.boostPrefixes ? 1 : 0)
+            }
+            tableOffsets.append(Int32(bias.count))
+        }
+        try check(f(ctx, tokens, offsets, bias, flags, tableOffsets, Int32(tables.count), eot))
+    }
+
+    /// The table of every row of the NEXT transcribe call on this context (wm_set_bias_rows; one entry per row of that call,
+    /// consumed by it): an index into setSequenceBiasTables' tables, or -1 for a row without a bias.  [] drops a pending map.
+    /// Not compiled in this repository (see the top of the file).
+    func setBiasRows(_ tableOfRow: [Int32]) throws {
+        typealias RowsFn = @convention(c) (OpaquePointer, UnsafePointer<Int32>?, Int32) -> Int32
+        let f: RowsFn = try sym("wm_set_bias_rows")
+        try check(f(ctx, tableOfRow.isEmpty ? nil : tableOfRow, Int32(tableOfRow.count)))
+    }
+
     /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
     /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
     /// Not compiled in this repository (see the top of the file).
