@@ -684,6 +684,38 @@ WM_API int wm_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t timestamp_beg
  * outside [0, n_vocab].  Same inheritance as wm_set_suppress. */
 WM_API int wm_set_repetition_rules(wm_ctx *ctx, float repetition_penalty, int no_repeat_ngram_size, int32_t eot);
 
+/* The sampling rules: top_k, top_p and min_p of Hugging Face generate (CTranslate2 / faster-whisper: sampling_topk,
+ * sampling_topp) -- the distribution a sampling call draws from is truncated, on the device, before the draw.  The rules act
+ * at every generated position of a row whose call samples (opts->temperature > 0); a call at temperature 0 (wm_transcribe_greedy,
+ * beam search and speculative calls among them) ignores them completely and makes the launches it makes without them.
+ *   A, the admissible set: exactly the ids the call may draw today -- the suppress lists (the first-token list too), the timestamp
+ *     rules (when the sum rule forces a timestamp, A is the admissible timestamps alone), the no-repeat bans, the sequence-bias
+ *     bans.  v(n): the logit after the repetition penalty and the sequence bias.
+ *   Order: descending value, equal values lower id first.  An id whose value is -INFINITY is never kept.
+ *   Masses: m(n) = exp((v(n) - vmax) * inv_T) with inv_T = (float)(1 / T) as the call uses it and vmax the best value in A.
+ *   The kept set K is the shortest prefix of A in that order that satisfies every active rule, applied in Hugging Face's
+ *     sequence -- temperature, top_k, top_p over what top_k left, min_p -- and never holds fewer than one id:
+ *       top_k > 0  : at most top_k ids.  EXACTLY k: Hugging Face keeps every id tied with the k-th, this library the lowest ids
+ *                    among the ties.  top_k >= |A| keeps all.
+ *       top_p < 1  : with Z_k the mass of the top_k prefix, the shortest prefix whose mass is >= top_p * Z_k.
+ *       min_p > 0  : only ids with m(n) >= min_p (a threshold relative to the best id, so the renormalisations do not move it).
+ *   Draw: the token is the arg-max over K of fmaf(v(n), inv_T, g(n)) with the Gumbel noise g(n) of the same Philox counters as
+ *     without the rules (id quad, generated index, sample id or call index, candidate word): top_k >= |A| reproduces the
+ *     untruncated call bit for bit, top_k = 1 the temperature-0 call.
+ *   Unchanged: token_logprobs_out stays v[tok] - logsumexp(A) at temperature 1 -- the truncation is NOT part of the normaliser
+ *     (openai-whisper's thresholds and the rankers are calibrated on that; Hugging Face reports post-warper scores);
+ *     no_speech_prob; the sum rule compares unperturbed values; an empty A takes the existing path (forced timestamp, fallback
+ *     token, log-prob -inf).
+ *   Determinism: K and the token depend on the row's own values, ids and seed alone -- masses are summed as 64-bit fixed point
+ *     (rint(m * 2^40)), never as floats -- not on the group's shape, the lanes, the other rows or the run.
+ * Scope: wm_transcribe, _mel, _ragged, _best_of (every candidate of a row gets the same rules and its own noise), the
+ * wm_transcribe_windows* counterparts, the *_aligned entries, and wm_multi_* device contexts when set there.  Teacher-forced
+ * calls stay raw.  (0, 1.0f, 0.0f) switches the rules off and is the initial state.  WM_ERR_INVALID: top_k < 0, top_p outside
+ * (0, 1], min_p outside [0, 1), a NaN.  The all-f32 debug path answers WM_ERR_STATE.  Applied to every lane and copied by later
+ * wm_clone's, as wm_set_repetition_rules.  Cost: one launch per generated position and the stored f32 logits row (DESIGN.md
+ * section 20). */
+WM_API int wm_set_sampling_rules(wm_ctx *ctx, int top_k, float top_p, float min_p);
+
 /* The sequence bias: Hugging Face generate's sequence_bias, and with it bad_words_ids (CTranslate2's suppress_sequences) and
  * phrase boosting (contextual biasing: product names, people, jargon).  A token sequence carries a bias, and the bias is added
  * to the logit of its LAST token whenever the row's history ends in its other tokens.

@@ -167,6 +167,11 @@ WM_API int wmdbg_decode_close(wm_ctx *ctx, wmdbg_step *io);
  * WMDBG_SENTINEL_F32; written when sot_pos == pos), the accept kernel's winner and log-prob; the arg-max close's are io's. */
 WM_API int wmdbg_decode_close_shared(wm_ctx *ctx, wmdbg_step *io, int w, int32_t *beam_n, int32_t *beam_tok, float *beam_lp,
                                      float *beam_nospeech, int32_t *acc_tok, float *acc_lp);
+/* wmdbg_decode_close with the sampling rules on (wm_set_sampling_rules): the truncation launch between the logits launch and
+ * the close, for the whole step.  The rules act on a sampling X-mode step (x_on, temperature > 0); with (0, 1, 0), x_on 0 or
+ * temperature 0 the launches are wmdbg_decode_close's.  With first-position suppress ids, mask_first must say whether pos is
+ * n_prompt - 1. */
+WM_API int wmdbg_decode_close_trunc(wm_ctx *ctx, wmdbg_step *io, int top_k, float top_p, float min_p);
 /* wmdbg_decode_close with the repetition rules on (wm_set_repetition_rules: penalty, ngram, and io->eot as the rules' eot, in
  * [0, V] whatever ts_mode is): wm_repeat_state on the token history in front of a DE_LOGITS_XR launch.  Needs x_on and
  * n_prompt <= n_ctx.  The bitmaps are pre-filled with 0xff bytes.  (1.0, 0) runs the same kernels with empty rules. */
@@ -571,6 +576,13 @@ WM_API int wmdbg_beam_trace(wm_ctx *ctx, float *trace_out);
  * list_tok i32 / list_lp f32 [rows][WM_MAX_BEAM + 1]. */
 WM_API int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V, int N, const int32_t *suppress, int n_suppress,
                            const int32_t *rng, int32_t ts_begin, int32_t *list_n, int32_t *list_tok, float *list_lp);
+/* The truncation kernel of the sampling rules alone, on host-given logits rows [rows][V] at generated index gi: suppress /
+ * rng [rows][4] (nullable: no timestamp rules) / ts_begin as wmdbg_beam_topk, the per-tile partials restated on the host the
+ * same way.  temperature > 0, seed and sample_ids [rows] (the rows' Philox counter words) are the call's.  Out, [rows] each:
+ * kept_n = |K|, cut_tok = the last kept id, tok = the drawn id (0, -1, -1 where nothing can be kept). */
+WM_API int wmdbg_sample_truncate(wm_ctx *ctx, const float *logits, int rows, int V, const int32_t *suppress, int n_suppress,
+                                 const int32_t *rng, int32_t ts_begin, float temperature, uint64_t seed, const uint32_t *sample_ids,
+                                 int gi, int top_k, float top_p, float min_p, int32_t *kept_n, int32_t *cut_tok, int32_t *tok);
 /* The re-parenting kernel alone, in place on host data: cache u16 [L2][rows][H][T][64] (bf16 bits), seq i32 [T][rows] and
  * logprob f32 [T][rows] (position-major), for the close of position pos (rows 0 .. pos of the cache, generated indices
  * 0 .. pos - n_prompt of the histories); src i32 [rows]: the beam (0 .. N - 1) of its window each row continues; wdone i32

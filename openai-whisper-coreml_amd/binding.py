@@ -416,10 +416,28 @@ def fallback_step_extra(t, best_of=None, length_penalty=None, beam_size=None, pa
     return {}
 
 
+def sampling_rules_args(top_k=None, top_p=None, min_p=None):
+    """top_k / top_p / min_p of transcribe_with_fallback and transcribe_long as the arguments of Context.set_sampling_rules:
+    None when all three are None (the rules are not touched), else (top_k, top_p, min_p) with a None read as off (0, 1.0, 0.0).
+    ValueError -- before any library call -- for top_k < 0 or not an integer, top_p outside (0, 1], min_p outside [0, 1), a NaN."""
+    if top_k is None and top_p is None and min_p is None:
+        return None
+    k = 0 if top_k is None else top_k
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 0 or k > 2 ** 31 - 1:
+        raise ValueError("top_k: an integer >= 0 (0: off)")
+    p = 1.0 if top_p is None else float(top_p)
+    if not (0.0 < p <= 1.0):
+        raise ValueError("top_p: a number in (0, 1] (1: off)")
+    m = 0.0 if min_p is None else float(min_p)
+    if not (0.0 <= m < 1.0):
+        raise ValueError("min_p: a number in [0, 1) (0: off)")
+    return int(k), p, m
+
+
 def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                              compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
                              vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None, best_of=None,
-                             length_penalty=None, beam_size=None, patience=None):
+                             length_penalty=None, beam_size=None, patience=None, top_k=None, top_p=None, min_p=None):
     """openai-whisper's decode_with_fallback, per chunk, over ctx.transcribe.
 
     Temperature step k decodes, as ONE batched call, the chunks that still need fallback (step 0: all of them) at
@@ -435,6 +453,11 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     ids (the index within the call) -- and keeps each chunk's best one under length_penalty (rank_candidates).  The
     temperature-0 step is unchanged.
 
+    top_k / top_p / min_p (all None: the context's sampling rules are not touched): the sampling rules of
+    Context.set_sampling_rules are set on the context for the run -- a None of the three reads as off -- and cleared on leaving,
+    also on an exception.  They act on the steps above temperature 0 (best_of candidates included); the temperature-0 step
+    ignores them.  ValueError before any library call for a bad value (sampling_rules_args).
+
     beam_size (openai-whisper's beam_size, with patience; None: greedy): the temperature-0 step is ONE wm_transcribe_mel_beam
     call over the chunks' Context.logmel windows and keeps each chunk's best hypothesis under length_penalty; the steps
     above temperature 0 are unchanged.  patience without beam_size is a ValueError.
@@ -443,6 +466,7 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     compression_ratio, temperature, seed, needs_fallback) and `steps`: [(temperature, seed, chunk indices)] per call."""
     pcm = np.asarray(pcm)
     beam_max_candidates(beam_size, patience)
+    sampling = sampling_rules_args(top_k, top_p, min_p)
 
     def decode(todo, t, sd):
         extra = fallback_step_extra(t, best_of, length_penalty, beam_size, patience)
@@ -454,9 +478,15 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
                                       sot_index=sot_index, **extra)
         return ctx.transcribe(pcm[todo], prompt, max_new, eot=eot, temperature=t, seed=sd,
                               no_speech_token=no_speech_token, sot_index=sot_index)
-    return fallback_decode(decode, pcm.shape[0], int(ctx.dims["n_vocab"]) if vocab_size is None else vocab_size, max_new,
-                           eot, temperatures, compression_ratio_threshold, logprob_threshold, no_speech_threshold, vocab,
-                           seed)
+    if sampling is not None:
+        ctx.set_sampling_rules(*sampling)
+    try:
+        return fallback_decode(decode, pcm.shape[0], int(ctx.dims["n_vocab"]) if vocab_size is None else vocab_size, max_new,
+                               eot, temperatures, compression_ratio_threshold, logprob_threshold, no_speech_threshold, vocab,
+                               seed)
+    finally:
+        if sampling is not None:
+            ctx.set_sampling_rules()
 
 
 def fallback_decode(decode, B, vocab_size, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
@@ -1300,7 +1330,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     patience=None, reuse_encoder=False, sample_rates=None, clip_timestamps=None,
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
-                    boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None, recording_bias=None):
+                    boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None, recording_bias=None,
+                    top_k=None, top_p=None, min_p=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1455,6 +1486,12 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        ValueError before any library call: together with sequence_bias, bad_words or boost_phrases, with draft, for anything
        but one entry per recording, for an unknown key and for what long_bias_table refuses.  With None the function makes
        exactly the calls it made before the argument existed.
+    23. top_k / top_p / min_p (all None: off): the sampling rules of Context.set_sampling_rules (wm_set_sampling_rules; a None of
+       the three reads as off) are set on the context behind the sequence bias, held for the run and cleared on leaving it, also on
+       an exception.  They truncate the distribution of every fallback step above temperature 0 (best_of candidates included);
+       the temperature-0 step, beam search and a draft's speculative steps ignore them.  Hugging Face's long-form fallback samples
+       under its generation config's top_k = 50.  ValueError before any library call for a bad value (sampling_rules_args).  With
+       all three None the function makes exactly the calls it made before the arguments existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1467,6 +1504,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     o = _LongOptions(**locals())
     R = len(recordings)
     o.early(R)
+    sampling = sampling_rules_args(top_k, top_p, min_p)   # 23. (None: off)
     bias_table = long_bias_table(sequence_bias, bad_words, boost_phrases, phrase_boost)   # 17. (None: off)
     o.rec_tables = None   # 22.: the table of every recording (None: off)
     if recording_bias is not None:
@@ -1495,6 +1533,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             ctx.set_sequence_bias(bias_table[0], bias_table[1], eot=eot)
         if o.rec_tables is not None:   # 22.
             ctx.set_sequence_bias_tables(rec_tables, rec_boosts, eot=eot)
+        if sampling is not None:   # 23.
+            ctx.set_sampling_rules(*sampling)
         langs = _long_languages(o, d_mel, mel_offs, T)
         o.prompt_head()
         units = _long_units(o, out, langs, d_mel, mel_offs, T)
@@ -1548,13 +1588,17 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             ctx.dev_free(d_mel)
         finally:
             try:
-                if bias_table is not None:
-                    ctx.set_sequence_bias(None)
-                if o.rec_tables is not None:
-                    ctx.set_sequence_bias_tables(None)
+                if sampling is not None:
+                    ctx.set_sampling_rules()
             finally:
-                if rules:
-                    ctx.set_repetition_rules(1.0, 0, eot)
+                try:
+                    if bias_table is not None:
+                        ctx.set_sequence_bias(None)
+                    if o.rec_tables is not None:
+                        ctx.set_sequence_bias_tables(None)
+                finally:
+                    if rules:
+                        ctx.set_repetition_rules(1.0, 0, eot)
     if vocab is not None:
         for rec in out:
             rec["text"] = vocab.decode([t for sg in rec["segments"] for t in sg["tokens"] if t < eot])
@@ -1941,6 +1985,16 @@ class Context:
         self.lib.wm_set_repetition_rules.restype = ctypes.c_int
         _check(self.lib, self.lib.wm_set_repetition_rules(self.handle, float(penalty), int(no_repeat_ngram_size), int(eot)))
 
+    def set_sampling_rules(self, top_k=0, top_p=1.0, min_p=0.0):
+        """The sampling rules of every transcribe call on this context that samples (wm_set_sampling_rules; temperature > 0):
+        the distribution is truncated on the device before the draw -- `top_k` (0 = off) keeps exactly the k best admissible ids
+        (ties: the lowest ids), `top_p` (1.0 = off) the shortest prefix of them holding that share of their mass, `min_p` (0.0 =
+        off) the ids whose probability is at least min_p times the best one's.  Log-probs stay those of the untruncated filtered
+        distribution.  Calls at temperature 0 ignore the rules.  The defaults switch them off."""
+        self.lib.wm_set_sampling_rules.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float]
+        self.lib.wm_set_sampling_rules.restype = ctypes.c_int
+        _check(self.lib, self.lib.wm_set_sampling_rules(self.handle, int(top_k), float(top_p), float(min_p)))
+
     def set_sequence_bias(self, sequences=None, boost=(), eot=None):
         """The sequence bias of every transcribe call on this context (wm_set_sequence_bias; Hugging Face's sequence_bias,
         with -inf its bad_words_ids): `sequences` {tuple of token ids: bias}, in the dict's order -- the bias (finite or -inf)
@@ -2073,11 +2127,12 @@ class Context:
     def transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                                  compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
                                  vocab=None, seed=0, no_speech_token=-1, sot_index=0, best_of=None, length_penalty=None,
-                                 beam_size=None, patience=None):
+                                 beam_size=None, patience=None, top_k=None, top_p=None, min_p=None):
         """openai-whisper's temperature fallback (module function transcribe_with_fallback) on this context."""
         return transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures, compression_ratio_threshold,
                                         logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index,
-                                        best_of=best_of, length_penalty=length_penalty, beam_size=beam_size, patience=patience)
+                                        best_of=best_of, length_penalty=length_penalty, beam_size=beam_size, patience=patience,
+                                        top_k=top_k, top_p=top_p, min_p=min_p)
 
     def _mel_rows(self, mel, mel_base, mel_len, seek, n_frames, mem):
         """(the arguments that name the B rows of a wm_*_mel* call, each keeping its array alive; B)"""

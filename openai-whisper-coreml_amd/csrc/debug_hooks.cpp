@@ -1327,20 +1327,28 @@ static unsigned long long host_key(float v, int n) {
     return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
 }
 
-extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V, int N, const int32_t *suppress, int n_suppress,
-                               const int32_t *rng, int32_t ts_begin, int32_t *list_n, int32_t *list_tok, float *list_lp) {
-    WM_TRY(wm_ctx_make_current(ctx));
-    WM_REQUIRE(logits && list_n && list_tok && list_lp && rows >= 1 && rows <= WM_DEC_MAXB && V >= 16 && N >= 1 && N <= WM_MAX_BEAM &&
-                   rows % N == 0 && n_suppress >= 0 && (n_suppress == 0 || suppress) && (!rng || (ts_begin >= 0 && ts_begin <= V)),
-               WM_ERR_INVALID, "beam_topk: bad args");
+// (wmdbg_beam_topk and wmdbg_sample_truncate stage the same rows)
+struct HostPartials {
+    int vpad, nt, mw;
+    std::vector<unsigned> mask;                  // [2][mw]: the every-position bitmap, then room for the first-position one
+    std::vector<float> lg, txt, tsl;             // logits [rows][vpad]; text and timestamp (max, sum exp) [rows][nt][2]
+    std::vector<unsigned long long> kt, ks;      // best allowed text / timestamp key [rows][nt]
+};
+static int host_row_partials(const char *who, const float *logits, int rows, int V, const int32_t *suppress, int n_suppress,
+                             const int32_t *rng, HostPartials *out) {
+    HostPartials &h = *out;
     const int vpad = (V + 15) / 16 * 16, nt = vpad / 16, mw = (vpad + 31) / 32;
-    std::vector<unsigned> mask((size_t)2 * mw, 0u);
+    h.vpad = vpad; h.nt = nt; h.mw = mw;
+    std::vector<unsigned> &mask = h.mask;
+    mask.assign((size_t)2 * mw, 0u);
     for (int i = 0; i < n_suppress; ++i) {
-        WM_REQUIRE(suppress[i] >= 0 && suppress[i] < V, WM_ERR_INVALID, "beam_topk: suppressed id %d", suppress[i]);
+        WM_REQUIRE(suppress[i] >= 0 && suppress[i] < V, WM_ERR_INVALID, "%s: suppressed id %d", who, suppress[i]);
         mask[suppress[i] >> 5] |= 1u << (suppress[i] & 31);
     }
-    std::vector<float> lg((size_t)rows * vpad, 0.f), txt((size_t)rows * nt * 2), tsl((size_t)rows * nt * 2);
-    std::vector<unsigned long long> kt((size_t)rows * nt, 0ull), ks((size_t)rows * nt, 0ull);
+    std::vector<float> &lg = h.lg, &txt = h.txt, &tsl = h.tsl;
+    std::vector<unsigned long long> &kt = h.kt, &ks = h.ks;
+    lg.assign((size_t)rows * vpad, 0.f); txt.assign((size_t)rows * nt * 2, 0.f); tsl.assign((size_t)rows * nt * 2, 0.f);
+    kt.assign((size_t)rows * nt, 0ull); ks.assign((size_t)rows * nt, 0ull);
     for (int b = 0; b < rows; ++b) {
         memcpy(&lg[(size_t)b * vpad], logits + (size_t)b * V, (size_t)V * 4);
         const int32_t *r = rng ? rng + b * 4 : nullptr;
@@ -1367,6 +1375,21 @@ extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V
             }
         }
     }
+    return WM_OK;
+}
+
+extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V, int N, const int32_t *suppress, int n_suppress,
+                               const int32_t *rng, int32_t ts_begin, int32_t *list_n, int32_t *list_tok, float *list_lp) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(logits && list_n && list_tok && list_lp && rows >= 1 && rows <= WM_DEC_MAXB && V >= 16 && N >= 1 && N <= WM_MAX_BEAM &&
+                   rows % N == 0 && n_suppress >= 0 && (n_suppress == 0 || suppress) && (!rng || (ts_begin >= 0 && ts_begin <= V)),
+               WM_ERR_INVALID, "beam_topk: bad args");
+    HostPartials hp;
+    WM_TRY(host_row_partials("beam_topk", logits, rows, V, suppress, n_suppress, rng, &hp));
+    const int vpad = hp.vpad, mw = hp.mw;
+    const std::vector<unsigned> &mask = hp.mask;
+    const std::vector<float> &lg = hp.lg, &txt = hp.txt, &tsl = hp.tsl;
+    const std::vector<unsigned long long> &kt = hp.kt, &ks = hp.ks;
     const int L = WM_MAX_BEAM + 1;
     const int32_t ints[2] = {0, 0};   // pos, then the beam parameters are not read by this kernel
     WmXPar xp;
@@ -1410,6 +1433,64 @@ extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V
     WM_HIP(hipMemcpyAsync(list_tok, bm.list_tok, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(list_lp, bm.list_lp, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
+// The truncation kernel alone on host-given rows at generated index gi (n_prompt 2, position gi + 1): the partials restated on
+// the host as for wmdbg_beam_topk, the row's keys and winner values in scratch.
+extern "C" int wmdbg_sample_truncate(wm_ctx *ctx, const float *logits, int rows, int V, const int32_t *suppress, int n_suppress,
+                                     const int32_t *rng, int32_t ts_begin, float temperature, uint64_t seed, const uint32_t *sample_ids,
+                                     int gi, int top_k, float top_p, float min_p, int32_t *kept_n, int32_t *cut_tok, int32_t *tok) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(logits && sample_ids && kept_n && cut_tok && tok && rows >= 1 && rows <= WM_DEC_MAXB && V >= 16 && n_suppress >= 0 &&
+                   (n_suppress == 0 || suppress) && (!rng || (ts_begin >= 0 && ts_begin <= V)) && gi >= 0,
+               WM_ERR_INVALID, "sample_truncate: bad args");
+    WM_REQUIRE(std::isfinite(temperature) && temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p < 1.f,
+               WM_ERR_INVALID, "sample_truncate: temperature > 0, top_k >= 0, top_p in (0, 1], min_p in [0, 1)");
+    HostPartials hp;
+    WM_TRY(host_row_partials("sample_truncate", logits, rows, V, suppress, n_suppress, rng, &hp));
+    std::copy(hp.mask.begin(), hp.mask.begin() + hp.mw, hp.mask.begin() + hp.mw);   // (gi 0 reads the first-position bitmap)
+    const int32_t pos = gi + 1;
+    WmXPar xp;
+    memset(&xp, 0, sizeof(xp));
+    xp.key0 = (unsigned)seed; xp.key1 = (unsigned)(seed >> 32);
+    xp.sample = 1; xp.inv_T = (float)(1.0 / (double)temperature);
+    xp.sot_pos = -1; xp.n_prompt = 2; xp.ids_on = 1; xp.n_cand = 1;
+    const WmSampPar spar = {top_k, top_p, min_p};
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    WmTsDev ts;
+    memset(&ts, 0, sizeof(ts));
+    WmXDev xd;
+    memset(&xd, 0, sizeof(xd));
+    const size_t nt = (size_t)rows * hp.nt;
+    const float *dlg;
+    unsigned long long *dkt;
+    const unsigned *dmask;
+    const int *dpos;
+    const WmSampPar *dpar;
+    int *ddbg;
+    WM_TRY(pool.get(&dlg, hp.lg.data(), hp.lg.size() * 4, s));
+    WM_TRY(pool.get(&xd.txt, hp.txt.data(), hp.txt.size() * 4, s));
+    WM_TRY(pool.get(&xd.win, nullptr, nt * 8, s));
+    WM_TRY(pool.get(&xd.ids, sample_ids, (size_t)rows * 4, s));
+    WM_TRY(pool.get(&dkt, hp.kt.data(), hp.kt.size() * 8, s));
+    WM_TRY(pool.get(&dmask, hp.mask.data(), hp.mask.size() * 4, s));
+    if (rng) {
+        WM_TRY(pool.get(&ts.rng, rng, (size_t)rows * 16, s));
+        WM_TRY(pool.get(&ts.key_ts, hp.ks.data(), hp.ks.size() * 8, s));
+        WM_TRY(pool.get(&ts.lse, hp.tsl.data(), hp.tsl.size() * 4, s));
+        ts.ts_begin = ts_begin; ts.n_vocab = V;
+    }
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&xd.par, &xp, sizeof(xp), s));
+    WM_TRY(pool.get(&dpar, &spar, sizeof(spar), s));
+    WM_TRY(pool.get(&ddbg, nullptr, (size_t)rows * 12, s, 0xff));
+    WM_TRY(wm_sample_truncate(ctx, dlg, hp.vpad, V, dkt, rows, ts, xd, dmask, hp.mw, 2, dpos, WmStopDev{}, nullptr, 0, dpar, ddbg));
+    std::vector<int32_t> out((size_t)rows * 3);
+    WM_HIP(hipMemcpyAsync(out.data(), ddbg, out.size() * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < rows; ++b) { kept_n[b] = out[b * 3]; cut_tok[b] = out[b * 3 + 1]; tok[b] = out[b * 3 + 2]; }
     return WM_OK;
 }
 
@@ -1932,8 +2013,9 @@ static int shared_closes_run(wm_ctx *ctx, DevPool &pool, const wmdbg_step *io, c
 // rep: the repetition rules (penalty, ngram, io->eot) are on -- wm_repeat_state in front of a DE_LOGITS_XR launch
 // sbt (with rep): the sequence bias as well -- wm_seqbias_state behind it and a DE_LOGITS_XB launch, also for an empty table
 // sh: the beam and accept closes on the same partials, in front of the arg-max close (wmdbg_decode_close_shared)
+// trunc: the sampling rules are on -- wm_sample_truncate between the logits launch and the close (a sampling X-mode step)
 static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram, const WmSbTable *sbt = nullptr,
-                            const CloseShared *sh = nullptr) {
+                            const CloseShared *sh = nullptr, const WmSampPar *trunc = nullptr) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
     if (rep)
@@ -2096,6 +2178,12 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     }
     WM_TRY(wm_dec_gemv(ctx, a));
     if (sh) WM_TRY(shared_closes_run(ctx, pool, io, *sh, a, dmask, mw));
+    if (trunc) {
+        const WmSampPar *dtr;
+        WM_TRY(pool.get(&dtr, trunc, sizeof(*trunc), s));
+        WM_TRY(wm_sample_truncate(ctx, a.out_f32, a.ldo, V, a.argmax, B, ts, xd, a.mask ? dmask : nullptr, mw, n_prompt, dpos, sp,
+                                  rep ? a.rep.ban : nullptr, mw, dtr, nullptr));
+    }
     // (ts, sp and xd are empty structs unless ts_mode, stop_on and x_on filled them)
     WM_TRY(wm_argmax_embed(ctx, a.argmax, n_tiles, B, dseq, dpos, n_prompt, dres, io->arg_first, n_ctx,
                            WmEmbedDev{dE, dpemb, K, dxn, dxbn, dstn, dmn}, ts, darr, io->fallback_tok, sp, xd, doff));
@@ -2157,6 +2245,19 @@ extern "C" int wmdbg_decode_close_shared(wm_ctx *ctx, wmdbg_step *io, int w, int
                "wmdbg_decode_close_shared: mask_first must say whether this is position n_prompt - 1");
     const CloseShared sh = {w, beam_n, beam_tok, acc_tok, beam_lp, beam_nospeech, acc_lp};
     return decode_close_run(ctx, io, false, 1.f, 0, nullptr, &sh);
+}
+extern "C" int wmdbg_decode_close_trunc(wm_ctx *ctx, wmdbg_step *io, int top_k, float top_p, float min_p) {
+    WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close_trunc: null");
+    WM_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p < 1.f, WM_ERR_INVALID,
+               "wmdbg_decode_close_trunc: top_k >= 0, top_p in (0, 1], min_p in [0, 1)");
+    const WmSampPar sp = {top_k, top_p, min_p};
+    const bool on = top_k > 0 || top_p < 1.f || min_p > 0.f;
+    // as the product: the rules act on a sampling extended-decode step; everywhere else the launches are wmdbg_decode_close's
+    if (!on || !io->x_on || !(io->temperature > 0.f)) return decode_close_run(ctx, io, false, 1.f, 0);
+    // (the kernel takes the first-position bitmap at position n_prompt - 1, the logits launch where mask_first says)
+    WM_REQUIRE(io->n_suppress_first == 0 || (io->mask_first != 0) == (io->pos == io->n_prompt - 1), WM_ERR_INVALID,
+               "wmdbg_decode_close_trunc: mask_first must say whether this is position n_prompt - 1");
+    return decode_close_run(ctx, io, false, 1.f, 0, nullptr, nullptr, &sp);
 }
 extern "C" int wmdbg_decode_close_rep(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram) {
     return decode_close_run(ctx, io, true, penalty, ngram);

@@ -79,6 +79,7 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc_t(m, &m->dx_logprob, (size_t)D.n_text_ctx * WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dx_nospeech, WM_DEC_MAXB, s));
     WM_TRY(dalloc(m, (void **)&m->dx_par, sizeof(WmXPar), s));
+    WM_TRY(dalloc(m, (void **)&m->dsamp_par, sizeof(WmSampPar), s));
     // (+16: the epilogue's padded 16-row blocks; second half: the rows' candidate words, WM_XIDS_CAND)
     WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)2 * WM_XIDS_CAND, s));
     WM_TRY(dalloc_t(m, &m->dmel_win, (size_t)WM_DEC_MAXB, s));
@@ -353,6 +354,29 @@ int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t
     return WM_OK;
 }
 
+int wm_model_set_sampling_rules(wm_ctx *ctx, int top_k, float top_p, float min_p) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m, WM_ERR_STATE, "context has no model");
+    const bool on = top_k > 0 || top_p < 1.f || min_p > 0.f;
+    if (on) {
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "the sampling rules are not supported by the all-f32 precision path");
+        WM_REQUIRE(m->dims.n_vocab <= 64 * 2048, WM_ERR_INVALID, "sampling rules: a vocabulary of %d ids does not fit the truncation kernel",
+                   m->dims.n_vocab);
+    }
+    m->samp_k = top_k; m->samp_p = top_p; m->samp_minp = min_p;
+    return WM_OK;
+}
+
+int wm_model_sample_truncate(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(mode.trunc && mode.x && !mode.beam && mode.panel <= 1, WM_ERR_STATE, "sampling rules: a sampling extended-decode group");
+    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
+    const WmRepDev rp = wm_model_rep_dev(m, mode);
+    return wm_sample_truncate(ctx, m->dlogits, m->vpad, m->dims.n_vocab, m->dargmax, B, ts, wm_model_x_dev(m, mode),
+                              mode.mask ? m->dmask : nullptr, m->vpad / 32, n_prompt, m->dpos, wm_model_stop_dev(m, mode),
+                              rp.par ? rp.ban : nullptr, rp.words, m->dsamp_par, nullptr);
+}
+
 WmTsDev wm_model_ts_dev(const WmModel *m) {
     WmTsDev t;
     memset(&t, 0, sizeof(t));
@@ -559,6 +583,7 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->teacher_panel = pm->teacher_panel;
     m->prompt_panel = pm->prompt_panel;
     m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
+    m->samp_k = pm->samp_k; m->samp_p = pm->samp_p; m->samp_minp = pm->samp_minp;
     if (m->rep_on || pm->sb_on || pm->sbt_on) WM_TRY(alloc_repetition_state(m, child->stream));
     if (pm->sb_on) {   // the parent's device table, as the suppress bitmaps above
         WM_TRY(alloc_seqbias_state(m, child->stream));

@@ -129,6 +129,14 @@ struct WmRepDev {
 };
 constexpr int WM_MAX_NGRAM = 32;
 
+// The sampling rules (wm_set_sampling_rules; sample_trunc.hip): top-k, top-p and min-p truncation of a
+// sampling row's filtered distribution, applied by one launch between the logits product and the close.  What changes from call
+// to call lives in device memory (WmSampPar, written at prefill); (0, 1, 0) is off.
+struct WmSampPar {
+    int top_k;
+    float top_p, min_p;
+};
+
 // The sequence bias (wm_set_sequence_bias; seqbias.hip): a table of token sequences with a bias each.
 // Entry s[0 .. n) matches a row iff n == 1 or the row's generated history g[0 .. k) ends in s[0 .. n - 1); total(t) is the f32
 // sum, from +0.0f in table order, of the biases of the matching entries whose last token is t, and the logit becomes
@@ -303,6 +311,9 @@ struct WmDecodeMode {
     // Row tables (wm_set_sequence_bias_tables): the state kernel is wm_seqbias_rows_state over the pool and the group's per-row
     // group ranges instead of wm_seqbias_state over the one table.  Implies sb and rep; the epilogue is the same DE_LOGITS_XB.
     bool sbt = false;
+    // The sampling rules apply (wm_set_sampling_rules on a call with temperature > 0): the logits launch stores the f32 row and
+    // wm_sample_truncate runs between it and the close.  Needs x.
+    bool trunc = false;
     // Panel width of a teacher-forced pass (wm_set_teacher_panel; 1: none): the step's rows are windows x panel, row c * panel + s
     // is position *dpos + s of window c -- the self-attention cache holds one entry per WINDOW, row (c, s) appends at and reads up
     // to its own position, the cross-attention is the candidate-group launch (wm_model_panel_step).  The teacher-forced entries
@@ -316,7 +327,7 @@ struct WmDecodeMode {
     int acap_base = 0, acap_Tq = 0, acap_J = 0;
     float *acap_q = nullptr;
     bool operator==(const WmDecodeMode &o) const {
-        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && rep == o.rep && sb == o.sb && sbt == o.sbt && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && rep == o.rep && sb == o.sb && sbt == o.sbt && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -458,6 +469,11 @@ struct WmModel {
     int rep_n = 0, rep_eot = 0;
     unsigned *drep_seen = nullptr, *drep_ban = nullptr;   // [WM_DEC_MAXB][(vpad + 31) / 32]
     WmRepPar *drep_par = nullptr;
+    // sampling rules (wm_set_sampling_rules): the context's setting and the device block a group's prefill writes
+    int samp_k = 0;
+    float samp_p = 1.f, samp_minp = 0.f;
+    bool samp_on() const { return samp_k > 0 || samp_p < 1.f || samp_minp > 0.f; }
+    WmSampPar *dsamp_par = nullptr;
     // sequence bias (wm_set_sequence_bias): the context's expanded table, and the device state allocated at full capacity when
     // first switched on (dsb.par == null before that) -- never moved: the captured graphs hold the addresses
     bool sb_on = false;
@@ -560,6 +576,10 @@ WmTsDev wm_model_ts_dev(const WmModel *m);
 WmRepDev wm_model_rep_dev(const WmModel *m, const WmDecodeMode &mode);
 // (1.0, 0, any eot) switches the rules off; the first enabling call allocates the bitmaps
 int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t eot);
+// (0, 1, 0) switches the rules off; validation is the caller's (wm_set_sampling_rules)
+int wm_model_set_sampling_rules(wm_ctx *ctx, int top_k, float top_p, float min_p);
+// the truncation launch of a generating position of a group with mode.trunc, between wm_model_decode_step (want_logits) and the close
+int wm_model_sample_truncate(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode);
 // the device view of the sequence-bias state (par == null when mode.sb is false)
 WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode);
 // an expanded table (empty: off) -> this context's device table; the first non-empty one allocates the state
@@ -816,6 +836,16 @@ int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_pro
 // self-attention K/V (skv [L2][rows][H][T][64]) and the rows' token / log-prob histories.  Call after wm_beam_select_step.
 int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, const int *pos_ptr, int n_prompt, int *seq,
                     float *logprob, const WmBeamDev &bm);
+
+// sample_trunc.hip (sampling rules)
+// Per row (grid: rows) of a sampling group at a generated position: the kept set of *par over the admissible ids of the stored
+// f32 logits [rows][ldo] (beam_topk's admissibility: ranges, mask, ban; `forced` from the partials), the Gumbel-max draw over
+// it with the epilogue's Philox counters, and the row's per-tile keys (tilemax, ts.key_ts) and winner values (xd.win) rewritten
+// so that the close picks that id; the log-sum-exp partials are left alone.  Rows with stop.done set, prompt positions and
+// arg-max calls are skipped.  dbg (nullable, device): [rows][3] kept count, last kept id, drawn id.
+int wm_sample_truncate(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, unsigned long long *tilemax, int rows,
+                       const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
+                       const WmStopDev &stop, const unsigned *ban, int ban_words, const WmSampPar *par, int *dbg);
 
 // repeat.hip (repetition rules)
 // Rebuild rows 0 .. B - 1 of rep.seen / rep.ban from the generated history of position *pos_ptr: tokens seq[(n_prompt + i) * B + b],

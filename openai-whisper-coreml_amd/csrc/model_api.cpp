@@ -67,6 +67,14 @@ extern "C" int wm_set_repetition_rules(wm_ctx *ctx, float repetition_penalty, in
         return wm_model_set_repetition_rules(c, repetition_penalty, no_repeat_ngram_size, eot);
     });
 } WM_API_CATCH
+extern "C" int wm_set_sampling_rules(wm_ctx *ctx, int top_k, float top_p, float min_p) try {
+    WM_MODEL(ctx);
+    (void)m;
+    WM_REQUIRE(top_k >= 0, WM_ERR_INVALID, "sampling rules: top_k %d is negative (0: off)", top_k);
+    WM_REQUIRE(top_p > 0.f && top_p <= 1.f, WM_ERR_INVALID, "sampling rules: top_p must lie in (0, 1] (1: off)");   // (a NaN fails it)
+    WM_REQUIRE(min_p >= 0.f && min_p < 1.f, WM_ERR_INVALID, "sampling rules: min_p must lie in [0, 1) (0: off)");
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { return wm_model_set_sampling_rules(c, top_k, top_p, min_p); });
+} WM_API_CATCH
 // The table of wm_set_sequence_bias, checked and expanded: given sequences in order, each followed by its implicit prefix
 // entries (shortest first); implicit entries with identical tokens merged into the first of them with the maximum bias, an
 // implicit entry identical to a given sequence dropped; then a STABLE sort by last token, so that the entries of one id are a

@@ -92,6 +92,7 @@ struct LaneJob {
     std::vector<int32_t> gen;      // its fetched token stream [max_new][Bg]
     WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
     WmRepPar rpar = {};            // its repetition rules (likewise)
+    WmSampPar spar = {};           // its sampling rules (likewise)
     WmSbPar sbpar = {};            // its sequence-bias table's counts (likewise)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
     std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
@@ -200,6 +201,7 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     j.mode.sbt = m->sbt_on;
     j.mode.sb = m->sb_on || m->sbt_on;
     j.mode.rep = m->rep_on || j.mode.sb;   // (tx_validate turns the extended decode on with them; the bias reads the rules' bitmaps)
+    j.mode.trunc = m->samp_on() && xc.on && xc.par.sample != 0;   // temperature 0 ignores the sampling rules: today's launches
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
     if (call.aligned) {   // the capture buffer and the alignment workspace, reserved before anything is enqueued
@@ -251,6 +253,11 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
         j.rpar.p = m->rep_p; j.rpar.inv_p = (float)(1.0 / (double)m->rep_p); j.rpar.n = m->rep_n; j.rpar.eot = m->rep_eot;
         if (!m->rep_on) { j.rpar.p = 1.f; j.rpar.inv_p = 1.f; j.rpar.n = 0; j.rpar.eot = 0; }   // the sequence bias alone: empty rules
         WM_HIP(hipMemcpyAsync(m->drep_par, &j.rpar, sizeof(WmRepPar), hipMemcpyHostToDevice, c->stream));
+    }
+    // sampling rules: top_k, top_p and min_p live in device memory as well (the graph key holds `trunc` alone)
+    if (j.mode.trunc) {
+        j.spar.top_k = m->samp_k; j.spar.top_p = m->samp_p; j.spar.min_p = m->samp_minp;
+        WM_HIP(hipMemcpyAsync(m->dsamp_par, &j.spar, sizeof(WmSampPar), hipMemcpyHostToDevice, c->stream));
     }
     // sequence bias: the table was uploaded when it was set; its counts go with the group, so a captured graph replays for any table
     if (j.mode.sbt) {   // row tables: the pool was uploaded when it was set; the rows' group ranges go with the group likewise
@@ -308,8 +315,13 @@ int lane_prompt_panels(LaneJob &j, const TxCall &call, const wm_ctx *caller) {
 // gen (a beam group's generating positions): the step also stores the f32 logits and the beam kernels close it.
 int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) {
     WmAlignCap cap = {j.alayers.data(), mode.acap_q, mode.acap_Tq, mode.acap_J, mode.acap_base};   // an aligned group: every step captures
-    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen, 0, j.c->model->dims.n_vocab - 1, mode.acap ? &cap : nullptr, mode, n_prompt));
+    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen || mode.trunc, 0, j.c->model->dims.n_vocab - 1, mode.acap ? &cap : nullptr, mode, n_prompt));
     if (gen) return wm_model_beam_close(j.c, j.Bg, n_prompt, mode);
+    // sampling rules: the kept set and its draw, in line between the logits launch (which stored the f32 row) and the close.
+    // The graph of a position is one for prompt and generated positions alike (the position lives on the device), so at a
+    // prompt position of such a group the row store is wasted and the truncation workgroups return at once (gi < 0): one
+    // launch of the floor's cost per prompt position, paid so that no second graph shape exists.
+    if (mode.trunc) WM_TRY(wm_model_sample_truncate(j.c, j.Bg, n_prompt, mode));
     return wm_model_close_step(j.c, j.Bg, n_prompt, true, nullptr, 0, mode);
 }
 
@@ -574,6 +586,7 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on;
     WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
     WM_REQUIRE(!(m->sb_on || m->sbt_on) || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
+    WM_REQUIRE(!(m->samp_on() && T > 0.f) || !ctx->dbg_hooks, WM_ERR_STATE, "the sampling rules are not supported by the all-f32 precision path");
     if (m->sbt_on) {   // row tables: the call's row map (wm_set_bias_rows), one entry per row of the call
         WM_REQUIRE(bias_rows, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
         WM_REQUIRE((int)bias_rows->size() == B, WM_ERR_INVALID, "the bias row map was set for %d rows, the call has %d", (int)bias_rows->size(), B);

@@ -209,6 +209,17 @@ struct Whisper {
         try check(f(ctx, penalty, noRepeatNgramSize, eot))
     }
 
+    /// The sampling rules of every later transcribe call on this context that samples (wm_set_sampling_rules; temperature > 0):
+    /// `topK` (0 = off) keeps exactly the k best admissible ids, `topP` (1 = off) the shortest prefix of them that holds that share
+    /// of their mass, `minP` (0 = off) the ids at least minP times as probable as the best; log-probs stay those of the
+    /// untruncated filtered distribution, calls at temperature 0 ignore the rules.  The defaults switch them off.
+    /// Not compiled in this repository (see the top of the file).
+    func setSamplingRules(topK: Int32 = 0, topP: Float = 1.0, minP: Float = 0.0) throws {
+        typealias SamplingFn = @convention(c) (OpaquePointer, Int32, Float, Float) -> Int32
+        let f: SamplingFn = try sym("wm_set_sampling_rules")
+        try check(f(ctx, topK, topP, minP))
+    }
+
     /// Positions per decoder step (1 ... 8; 1 = the default) of the teacher-forced passes behind align / alignMel / alignWindows /
     /// decodeLogits on this context (wm_set_teacher_panel).  A launch policy: the results are bit-identical for every width.
     /// Not compiled in this repository (see the top of the file).
