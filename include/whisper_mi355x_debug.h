@@ -589,6 +589,57 @@ WM_API int wmdbg_sample_truncate(wm_ctx *ctx, const float *logits, int rows, int
  * [rows / N]: 1 = the window has just left the decode (its histories move, its cache does not). */
 WM_API int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows, int H, int T, int N, int pos, int n_prompt,
                               const int32_t *src, const int32_t *wdone, int32_t *seq, float *logprob);
+/* The select kernel alone (beam.hip beam_select_kernel): ONE wm_beam_select_step launch on caller-given state -- the lists are
+ * the caller's, no logits and no list kernel in front of it.  A group of C windows x N beams (rows = C * N <= WM_DEC_MAXB) at
+ * position pos, generated index gi = pos + 1 - n_prompt.  Every buffer is host memory that the hook uploads WHOLE before the
+ * launch and downloads WHOLE behind it, whether the rules, the early stop or the ancestry are on: the caller pre-fills what it
+ * does not give with a sentinel (the NaN bits WMDBG_SENTINEL_F32 for floats, a fixed negative int) and reads from the buffers
+ * what was written and that nothing else was.  Per-window arrays have cap >= C entries, per-row arrays cap * N: entries behind
+ * the group's must come back untouched.  The position-major arrays (seq, logprob, anc) and off have the group's row stride.
+ * The embedded next row comes back with the conventions of wmdbg_step: the device buffers are pre-filled with the sentinels by
+ * the hook, x_next / xb_next f32 [cap * N][d] (xb_next un-tiled and widened), stats_next [cap * N][2] summed from the d / 16
+ * parts, stats_tail_nonzero the words behind part 0 of the GROUP's rows that are not zero bits, mean_next [cap * N].
+ * Nothing is launched when the kernel could leave a buffer -- WM_ERR_INVALID with a message: C < 1, N outside 1 ..
+ * WM_MAX_BEAM, cap < C, rows > WM_DEC_MAXB; pos outside [n_prompt - 1, n_ctx); gi >= max_new; max_cand outside 1 ..
+ * WM_MAX_BEAM_HYPS; fin_n[w] outside 0 .. max_cand; a list_n outside 0 .. N + 1; a listed token, pad or eot outside the
+ * vocabulary; a negative off; d that the tiled layout does not take (a multiple of 64, 64 .. 1280). */
+typedef struct wmdbg_beam_io {
+    int32_t C, N, cap;
+    int32_t n_ctx, pos, n_prompt, d, n_vocab;
+    int32_t max_cand, max_new, eot, pad;   /* WmBeamPar */
+    int32_t ts_on;                         /* timestamp rules: 0 = the kernel gets no hist / rng */
+    int32_t ts_par[4];                     /* ts_begin, eot, n_vocab, max_initial of WmTsDev */
+    int32_t stop_on;                       /* early stop: 0 = the kernel gets no done / live_rows / n_live */
+    const int32_t *budget;     /* [cap] */
+    float *sum;                /* [cap * N] in / out */
+    int32_t *list_n;           /* [cap * N] */
+    int32_t *list_tok;         /* [cap * N][WM_MAX_BEAM + 1] */
+    float *list_lp;            /* [cap * N][WM_MAX_BEAM + 1] */
+    int32_t *src;              /* [cap * N] */
+    int32_t *wdone, *wsteps, *fin_n;       /* [cap] */
+    int32_t *fin_len;          /* [cap][WM_MAX_BEAM_HYPS] */
+    float *fin_sum;            /* [cap][WM_MAX_BEAM_HYPS] */
+    int32_t *fin_src;          /* [cap][WM_MAX_BEAM_HYPS]; handed to the kernel with anc only, as the product does */
+    int32_t *fin_tok;          /* [cap][WM_MAX_BEAM_HYPS][n_ctx] */
+    float *fin_lp;             /* [cap][WM_MAX_BEAM_HYPS][n_ctx] */
+    int32_t *anc;              /* [max_new][rows], or NULL: a group that is not aligned (no anc, no fin_src) */
+    int32_t *seq;              /* [n_ctx + 1][rows], as the model's buffer: the close of position n_ctx - 1 writes row n_ctx */
+    float *logprob;            /* [max_new][rows] */
+    int32_t *hist, *rng;       /* [cap * N][4] */
+    int32_t *done, *live_rows; /* [cap * N] */
+    int32_t *n_live;           /* [1] */
+    const int32_t *off;        /* [rows] or NULL: a ragged group's prompt starts */
+    const float *emb;          /* [n_vocab][d], rounded to bf16 and tiled by the hook */
+    const float *pemb;         /* [n_ctx][d] */
+    float *x_next, *xb_next;   /* [cap * N][d] */
+    float *stats_next;         /* [cap * N][2] */
+    float *mean_next;          /* [cap * N] */
+    int32_t stats_tail_nonzero;
+    int32_t pos_out;
+} wmdbg_beam_io;
+WM_API int wmdbg_beam_step(wm_ctx *ctx, wmdbg_beam_io *io);
+/* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_beam_io) and the offsets of ts_par, budget and x_next (host only). */
+WM_API int wmdbg_beam_step_layout(int32_t *out4);
 /* The window-set copy kernel alone (xkv_rows.hip), on DEVICE buffers of the caller (16-byte aligned, bf16 bits): group u16
  * [2 * L][group_rows][H][1500][64], a decode group's cross-K/V cache, and store u16 [store_rows][2 * L][H][1500][64], a set's
  * window-major store.  Group row b <-> store row rows[b] (i32 [n_rows], host; every entry in [0, store_rows)), b < n_rows <=

@@ -1526,6 +1526,139 @@ extern "C" int wmdbg_beam_reorder(wm_ctx *ctx, uint16_t *cache, int L2, int rows
     return WM_OK;
 }
 
+extern "C" int wmdbg_beam_step_layout(int32_t *out4) {
+    if (!out4) return WM_ERR_INVALID;
+    out4[0] = (int32_t)sizeof(wmdbg_beam_io); out4[1] = (int32_t)offsetof(wmdbg_beam_io, ts_par);
+    out4[2] = (int32_t)offsetof(wmdbg_beam_io, budget); out4[3] = (int32_t)offsetof(wmdbg_beam_io, x_next);
+    return WM_OK;
+}
+// The select kernel alone (beam.hip) on the caller's state.  Every buffer goes to the device whole and comes back whole, so the
+// caller's sentinels show what the kernel left alone; nothing is launched when the kernel could leave a buffer.
+extern "C" int wmdbg_beam_step(wm_ctx *ctx, wmdbg_beam_io *io) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(io && io->budget && io->sum && io->list_n && io->list_tok && io->list_lp && io->src && io->wdone && io->wsteps &&
+                   io->fin_n && io->fin_len && io->fin_sum && io->fin_src && io->fin_tok && io->fin_lp && io->seq && io->logprob &&
+                   io->hist && io->rng && io->done && io->live_rows && io->n_live && io->emb && io->pemb && io->x_next &&
+                   io->xb_next && io->stats_next && io->mean_next,
+               WM_ERR_INVALID, "wmdbg_beam_step: null pointer");
+    const int C = io->C, N = io->N, cap = io->cap, n_ctx = io->n_ctx, pos = io->pos, n_prompt = io->n_prompt, d = io->d, V = io->n_vocab;
+    WM_REQUIRE(C >= 1 && N >= 1 && N <= WM_MAX_BEAM && cap >= C && cap <= 2 * WM_DEC_MAXB, WM_ERR_INVALID,
+               "wmdbg_beam_step: bad group: C %d, N %d (1 .. %d), cap %d", C, N, WM_MAX_BEAM, cap);
+    WM_REQUIRE(C * N <= WM_DEC_MAXB, WM_ERR_INVALID, "wmdbg_beam_step: %d rows are more than %d", C * N, WM_DEC_MAXB);
+    WM_REQUIRE(n_prompt >= 1 && n_ctx >= 1 && n_ctx <= 4096 && V >= 1 && io->max_new >= 1 && io->max_new <= 4096, WM_ERR_INVALID,
+               "wmdbg_beam_step: bad geometry");
+    WM_REQUIRE(pos >= n_prompt - 1 && pos < n_ctx, WM_ERR_INVALID, "wmdbg_beam_step: position %d outside [n_prompt - 1, n_ctx)", pos);
+    const int gi = pos + 1 - n_prompt, rows = C * N;
+    WM_REQUIRE(gi < io->max_new, WM_ERR_INVALID, "wmdbg_beam_step: generated index %d is not below max_new %d", gi, io->max_new);
+    WM_REQUIRE(io->max_cand >= 1 && io->max_cand <= WM_MAX_BEAM_HYPS, WM_ERR_INVALID, "wmdbg_beam_step: max_cand %d outside 1 .. %d",
+               io->max_cand, WM_MAX_BEAM_HYPS);
+    WM_REQUIRE(d >= 64 && d % 64 == 0 && d <= 1280, WM_ERR_INVALID, "wmdbg_beam_step: d %d is not a multiple of 64 in 64 .. 1280", d);
+    WM_REQUIRE(io->pad >= 0 && io->pad < V && io->eot < V, WM_ERR_INVALID, "wmdbg_beam_step: pad %d or eot %d outside the vocabulary",
+               io->pad, io->eot);
+    for (int w = 0; w < C; ++w)
+        WM_REQUIRE(io->fin_n[w] >= 0 && io->fin_n[w] <= io->max_cand, WM_ERR_INVALID, "wmdbg_beam_step: fin_n[%d] = %d outside 0 .. max_cand",
+                   w, io->fin_n[w]);
+    for (int b = 0; b < rows; ++b) {
+        WM_REQUIRE(io->list_n[b] >= 0 && io->list_n[b] <= N + 1, WM_ERR_INVALID, "wmdbg_beam_step: list_n[%d] = %d outside 0 .. N + 1", b,
+                   io->list_n[b]);
+        for (int e = 0; e < io->list_n[b]; ++e) {
+            const int t = io->list_tok[b * WM_BEAM_LIST + e];
+            WM_REQUIRE(t >= 0 && t < V, WM_ERR_INVALID, "wmdbg_beam_step: list token %d of row %d outside the vocabulary", t, b);
+        }
+        if (io->off) WM_REQUIRE(io->off[b] >= 0, WM_ERR_INVALID, "wmdbg_beam_step: off[%d] = %d is negative", b, io->off[b]);
+    }
+    hipStream_t s = ctx->stream;
+    const size_t nr = (size_t)cap * N, nh = (size_t)cap * WM_MAX_BEAM_HYPS, rpad = (nr + 15) / 16 * 16, st_words = rpad / 16 * 2 * d;
+    std::vector<bf16_t> e16;
+    tile_bf16(io->emb, (size_t)V, (size_t)d, e16);
+    const std::vector<uint32_t> nan32(std::max(nr * d, st_words), WMDBG_SENTINEL_F32);
+    const std::vector<bf16_t> nan16(rpad * d, (bf16_t)WMDBG_SENTINEL_BF16);
+    std::vector<float> stn(st_words);
+    const WmBeamPar par{io->max_cand, io->max_new, io->eot, io->pad};
+    WmXPar xp;
+    memset(&xp, 0, sizeof(xp));
+    xp.sot_pos = -1; xp.n_prompt = n_prompt; xp.n_cand = N;
+    DevPool pool;
+    // every in / out buffer once: host pointer, bytes, device pointer
+    struct Buf { void *h; size_t bytes; void *d; };
+    Buf bufs[] = {{io->sum, nr * 4, nullptr},          {io->list_n, nr * 4, nullptr},       {io->list_tok, nr * WM_BEAM_LIST * 4, nullptr},
+                  {io->list_lp, nr * WM_BEAM_LIST * 4, nullptr}, {io->src, nr * 4, nullptr}, {io->wdone, (size_t)cap * 4, nullptr},
+                  {io->wsteps, (size_t)cap * 4, nullptr}, {io->fin_n, (size_t)cap * 4, nullptr}, {io->fin_len, nh * 4, nullptr},
+                  {io->fin_sum, nh * 4, nullptr},      {io->fin_src, nh * 4, nullptr},      {io->fin_tok, nh * n_ctx * 4, nullptr},
+                  {io->fin_lp, nh * n_ctx * 4, nullptr}, {io->seq, (size_t)(n_ctx + 1) * rows * 4, nullptr},
+                  {io->logprob, (size_t)io->max_new * rows * 4, nullptr}, {io->hist, nr * 16, nullptr}, {io->rng, nr * 16, nullptr},
+                  {io->done, nr * 4, nullptr},         {io->live_rows, nr * 4, nullptr},    {io->n_live, 4, nullptr},
+                  {io->anc, io->anc ? (size_t)io->max_new * rows * 4 : 0, nullptr}};
+    for (Buf &b : bufs)
+        if (b.h) WM_TRY(pool.get(&b.d, b.h, b.bytes, s));
+    auto dev = [&](const void *h) {
+        for (const Buf &b : bufs)
+            if (b.h == h) return b.d;
+        return (void *)nullptr;
+    };
+    const int *d_bud, *d_off = nullptr;
+    int *d_pos;
+    const bf16_t *d_emb;
+    const float *d_pemb;
+    float *d_x, *d_st, *d_mean;
+    bf16_t *d_xb;
+    WM_TRY(pool.get(&d_bud, io->budget, (size_t)cap * 4, s));
+    if (io->off) WM_TRY(pool.get(&d_off, io->off, (size_t)rows * 4, s));
+    WM_TRY(pool.get(&d_pos, &pos, 4, s));
+    WM_TRY(pool.get(&d_emb, e16.data(), e16.size() * 2, s));
+    WM_TRY(pool.get(&d_pemb, io->pemb, (size_t)n_ctx * d * 4, s));
+    WM_TRY(pool.get(&d_x, nan32.data(), nr * d * 4, s));
+    WM_TRY(pool.get(&d_xb, nan16.data(), nan16.size() * 2, s));
+    WM_TRY(pool.get(&d_st, nan32.data(), st_words * 4, s));
+    WM_TRY(pool.get(&d_mean, nan32.data(), nr * 4, s));
+    WmBeamDev bm;
+    memset(&bm, 0, sizeof(bm));
+    WM_TRY(pool.get(&bm.par, &par, sizeof(par), s));
+    bm.N = N; bm.n_ctx = n_ctx; bm.budget = d_bud;
+    bm.sum = (float *)dev(io->sum); bm.src = (int *)dev(io->src); bm.list_n = (int *)dev(io->list_n);
+    bm.list_tok = (int *)dev(io->list_tok); bm.list_lp = (float *)dev(io->list_lp);
+    bm.wdone = (int *)dev(io->wdone); bm.wsteps = (int *)dev(io->wsteps); bm.fin_n = (int *)dev(io->fin_n);
+    bm.fin_len = (int *)dev(io->fin_len); bm.fin_sum = (float *)dev(io->fin_sum);
+    bm.fin_tok = (int *)dev(io->fin_tok); bm.fin_lp = (float *)dev(io->fin_lp);
+    if (io->anc) { bm.anc = (int *)dev(io->anc); bm.fin_src = (int *)dev(io->fin_src); }   // an aligned group (wm_model_beam_dev)
+    WmTsDev ts;
+    memset(&ts, 0, sizeof(ts));
+    if (io->ts_on) {
+        ts.hist = (int *)dev(io->hist); ts.rng = (int *)dev(io->rng);
+        ts.ts_begin = io->ts_par[0]; ts.eot = io->ts_par[1]; ts.n_vocab = io->ts_par[2]; ts.max_initial = io->ts_par[3];
+    }
+    WmStopDev sp;
+    memset(&sp, 0, sizeof(sp));
+    if (io->stop_on) {
+        sp.done = (int *)dev(io->done); sp.live_rows = (int *)dev(io->live_rows); sp.n_live = (int *)dev(io->n_live);
+        sp.eot = io->eot; sp.pad_tok = io->pad;
+    }
+    WmXDev xd;
+    memset(&xd, 0, sizeof(xd));
+    WM_TRY(pool.get(&xd.par, &xp, sizeof(xp), s));
+    xd.logprob = (float *)dev(io->logprob);
+    WM_TRY(wm_beam_select_step(ctx, rows, (int *)dev(io->seq), d_pos, n_prompt, WmEmbedDev{d_emb, d_pemb, d, d_x, d_xb, d_st, d_mean}, ts, sp,
+                               xd, d_off, bm));
+    for (const Buf &b : bufs)
+        if (b.h) WM_HIP(hipMemcpyAsync(b.h, b.d, b.bytes, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(&io->pos_out, d_pos, 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->x_next, d_x, nr * d * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->mean_next, d_mean, nr * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(stn.data(), d_st, st_words * 4, hipMemcpyDeviceToHost, s));
+    WM_TRY(down_tiled_bf16(d_xb, nr, (size_t)d, io->xb_next, s));   // (synchronises the stream)
+    io->stats_tail_nonzero = 0;
+    for (size_t b = 0; b < nr; ++b) {   // summed as wmdbg_decode_close sums them; the tail: words behind part 0 that are not zero bits
+        stats_sum(stn.data(), d, (int)b, io->stats_next + b * 2);
+        for (int part = 1; part < d / 16 && b < (size_t)rows; ++part)
+            for (int c = 0; c < 2; ++c) {
+                uint32_t u;
+                memcpy(&u, &stn[stat_at(d, b, part, c)], 4);
+                if (u != 0u) ++io->stats_tail_nonzero;
+            }
+    }
+    return WM_OK;
+}
+
 // ------------------------------------------------------------------ window sets: the copy kernel ----
 extern "C" int wmdbg_xkv_rows(wm_ctx *ctx, uint16_t *group, int group_rows, uint16_t *store, int64_t store_rows, const int32_t *rows,
                               int n_rows, int L, int H, int to_store) {

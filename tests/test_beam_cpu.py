@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+from beam_step_ref import beam_select_np
 from conftest import ROOT
 from test_best_of_cpu import rank_np
 from test_ragged_prompts_cpu import EOT, FakeCtx, _fake_kw
@@ -28,30 +29,6 @@ NINF = f32(-np.inf)
 
 
 # ---------------------------------------------------------------- the numpy restatement
-def beam_select_np(N, n_from, eot, pad, room, sums, lists):
-    """lists[j] = [(token, lp)], best first.  Returns (n_next, src, tok, lp, new_sum, fins) with fins = [(src, lp, sum)]."""
-    cands = []
-    for j in range(n_from):
-        if sums[j] == NINF:
-            continue
-        for e, (t, lp) in enumerate(lists[j]):
-            cands.append((f32(f32(sums[j]) + f32(lp)), j, e, int(t), f32(lp)))
-    cands.sort(key=lambda c: -float(c[0]))          # Python's sort is stable: ties keep (beam, entry) order
-    src, tok, lps, new, fins = [], [], [], [], []
-    for score, j, _, t, lp in cands:
-        if len(src) == N:
-            break
-        if eot >= 0 and t == eot:
-            if len(fins) < room:
-                fins.append((j, lp, score))
-        else:
-            src.append(j); tok.append(t); lps.append(lp); new.append(score)
-    n_next = len(src)
-    for k in range(n_next, N):
-        src.append(k); tok.append(pad); lps.append(f32(0)); new.append(NINF)
-    return n_next, src, tok, lps, new, fins
-
-
 def fill_order_np(sums):
     live = [j for j in range(len(sums)) if sums[j] != NINF]
     return sorted(live, key=lambda j: -float(sums[j]))
@@ -288,7 +265,8 @@ def test_header_declares_and_both_libraries_export_the_call(pkg):
     for lib in (pkg.binding.load_library(), pkg.binding.load_debug_library()):
         assert hasattr(lib, "wm_transcribe_mel_beam")
     dbg = pkg.binding.load_debug_library()
-    for name in ("wmdbg_beam_select", "wmdbg_beam_fill_order", "wmdbg_beam_trace", "wmdbg_beam_topk", "wmdbg_beam_reorder"):
+    for name in ("wmdbg_beam_select", "wmdbg_beam_fill_order", "wmdbg_beam_trace", "wmdbg_beam_topk", "wmdbg_beam_reorder",
+                 "wmdbg_beam_step", "wmdbg_beam_step_layout"):
         assert hasattr(dbg, name), name
         assert not hasattr(pkg.binding.load_library(), name), name
 
