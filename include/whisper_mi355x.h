@@ -800,6 +800,46 @@ WM_API int wm_set_bias_rows(wm_ctx *ctx, const int32_t *table_of_row /* [n], -1 
  * (serving: per-request max_tokens; bench.py: a synthetic early-stop workload).  n = 0 clears. */
 WM_API int wm_set_token_budgets(wm_ctx *ctx, const int32_t *budgets, int n);
 
+/* Top-n alternatives and entropy per generated token (OpenAI's `logprobs`, Hugging Face generate's output_scores, CTranslate2's
+ * return_scores): what else the model considered at a position, and how peaked its distribution was.  A request applies to the
+ * NEXT transcribe call on the context and is consumed by it whatever happens, as wm_set_token_budgets; req == NULL drops a
+ * pending request.  The buffers are the caller's and must stay valid until that call returns.  With no request pending every call
+ * makes exactly the launches it makes without this entry.
+ * At generated index gi of hypothesis row r, gi < lens of that row:
+ *   A, the admissible set, and v(id): exactly those of wm_set_sampling_rules -- A is what is left after the suppress lists (the
+ *     first-token list too), the timestamp rules (when the sum rule forces a timestamp, A is the admissible timestamps alone),
+ *     the no-repeat bans and the sequence-bias bans; v is the stored logit after the repetition penalty and the sequence bias.
+ *     An id with v = -INFINITY is not in A.
+ *   Order: descending value, equal values lower id first.
+ *   tokens[r][gi][j], logprobs[r][gi][j]: the j-th id of A in that order, and v(id) - norm, with norm the normaliser of
+ *     token_logprobs_out: log sum over A of exp(v) at temperature 1, truncation (the sampling rules) not part of it -- at any call
+ *     temperature and under any sampling rules.  At temperature 0 entry 0 is the generated token, with token_logprobs_out's bits;
+ *     at temperature > 0 the drawn token, where it is listed, has token_logprobs_out's bits.
+ *   counts[r][gi]: min(n, |A|).  Entries past the count, and every position gi >= lens, are pads: id -1, log-prob 0, count 0,
+ *     entropy 0.  The position that stops a row (eot or budget) has its values.
+ *   entropy[r][gi]: -sum over A of p log p, p = exp(v - norm), in nats.  The f32 sum runs in a fixed order (each thread of the
+ *     row's workgroup adds its ids ascending, then one fixed tree), so a row's bits depend on the row alone -- not on the group's
+ *     shape, the lanes, the other rows or the run.  An empty A gives 0.
+ * Served: wm_transcribe_greedy (the request turns the extended decode on, as the repetition rules do), wm_transcribe, _mel,
+ * _mel_ragged, _mel_best_of (every candidate: rows = B * best_of in the call's hypothesis order [B][best_of]),
+ * wm_transcribe_windows, and the *_aligned counterparts of these.  Refused with WM_ERR_STATE, the request consumed:
+ * wm_transcribe_mel_beam*, wm_transcribe_windows_beam*, wm_transcribe_mel_speculative, wm_multi_transcribe_greedy (a request
+ * pending on a device context) and the all-f32 debug path.  WM_ERR_INVALID: n outside [1, WM_MAX_ALTERNATIVES], null tokens /
+ * logprobs, rows or max_new below 1 (answered here); rows / max_new that do not match the call (answered by the call, which
+ * still consumes the request).  Teacher-forced calls neither read nor consume a request.  Cost: one launch per position and
+ * the stored f32 logits row. */
+#define WM_MAX_ALTERNATIVES 16
+typedef struct wm_alternatives_out {
+    int32_t  n;          /* 1 .. WM_MAX_ALTERNATIVES entries per position                       */
+    int64_t  rows;       /* hypotheses of the call the buffers are sized for: B, or B * best_of */
+    int32_t  max_new;    /* must equal the call's                                               */
+    int32_t *tokens;     /* i32 [rows][max_new][n]  (host)                                      */
+    float   *logprobs;   /* f32 [rows][max_new][n]  (host)                                      */
+    int32_t *counts;     /* i32 [rows][max_new]     (host, nullable)                            */
+    float   *entropy;    /* f32 [rows][max_new]     (host, nullable)                            */
+} wm_alternatives_out;
+WM_API int wm_request_alternatives(wm_ctx *ctx, const wm_alternatives_out *req /* NULL: drop a pending request */);
+
 /* ------------------------------------------------- all GPUs of the node, one host process --- */
 /* the Swift host dlopens ONE library in ONE process; wm_multi drives n GPUs from it.  Weights are
  * replicated (one wm_ctx per device: fetch each with wm_multi_device_ctx and fill it with wm_load_weights /

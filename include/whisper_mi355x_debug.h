@@ -576,6 +576,14 @@ WM_API int wmdbg_beam_trace(wm_ctx *ctx, float *trace_out);
  * list_tok i32 / list_lp f32 [rows][WM_MAX_BEAM + 1]. */
 WM_API int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V, int N, const int32_t *suppress, int n_suppress,
                            const int32_t *rng, int32_t ts_begin, int32_t *list_n, int32_t *list_tok, float *list_lp);
+/* The alternatives kernel (wm_request_alternatives) alone, on host-given logits rows [rows][V] at generated index 0: suppress /
+ * rng [rows][4] (nullable: no timestamp rules) / ts_begin as wmdbg_beam_topk, the per-tile partials restated on the host by the
+ * same helper -- for n <= WM_MAX_BEAM + 1 the lists are wmdbg_beam_topk's of N = n - 1 bit for bit.  n in [1,
+ * WM_MAX_ALTERNATIVES].  In and out: tokens i32 / logprobs f32 [rows][n], counts i32 / entropy f32 [rows] (both nullable) --
+ * uploaded as given and downloaded whole, so a sentinel shows what the kernel wrote. */
+WM_API int wmdbg_alternatives(wm_ctx *ctx, const float *logits, int rows, int V, int n, const int32_t *suppress, int n_suppress,
+                              const int32_t *rng, int32_t ts_begin, int32_t *counts, int32_t *tokens, float *logprobs,
+                              float *entropy);
 /* The truncation kernel of the sampling rules alone, on host-given logits rows [rows][V] at generated index gi: suppress /
  * rng [rows][4] (nullable: no timestamp rules) / ts_begin as wmdbg_beam_topk, the per-tile partials restated on the host the
  * same way.  temperature > 0, seed and sample_ids [rows] (the rows' Philox counter words) are the call's.  Out, [rows] each:

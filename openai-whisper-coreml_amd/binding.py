@@ -250,11 +250,66 @@ class wm_decode_opts(ctypes.Structure):
                 ("sot_index", ctypes.c_int32)]
 
 
+MAX_ALTERNATIVES = 16   # WM_MAX_ALTERNATIVES
+
+
+class wm_alternatives_out(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int32), ("rows", ctypes.c_int64), ("max_new", ctypes.c_int32), ("tokens", ctypes.c_void_p),
+                ("logprobs", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("entropy", ctypes.c_void_p)]
+
+
+def alternatives_arg(alternatives, beam_size=None, draft=None):
+    """`alternatives=` of the transcribe wrappers as wm_request_alternatives' n: None (no request) or an integer in 1 ..
+    MAX_ALTERNATIVES.  ValueError -- before any library call -- for anything else, and together with beam search or a draft
+    model (a beam's alternatives need its ancestry; a speculative call verifies the greedy choice alone)."""
+    if alternatives is None:
+        return None
+    n = alternatives
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= n <= MAX_ALTERNATIVES:
+        raise ValueError("alternatives: an integer in 1 .. %d (None: no request)" % MAX_ALTERNATIVES)
+    if beam_size is not None:
+        raise ValueError("alternatives are not served by beam search (beam_size)")
+    if draft is not None:
+        raise ValueError("alternatives are not served by speculative decoding (draft)")
+    return int(n)
+
+
+class Alternatives:
+    """The arrays of one wm_request_alternatives request, filled by the transcribe call that consumes it: tokens i32 / logprobs
+    f32 [rows][max_new][n] (-1 / 0 past counts and past a row's length), counts i32 [rows][max_new], entropy f32
+    [rows][max_new] (None when not requested), in nats."""
+
+    def __init__(self, n, rows, max_new, entropy=True):
+        self.n, self.rows, self.max_new = int(n), int(rows), int(max_new)
+        self.tokens = np.full((self.rows, self.max_new, self.n), -1, dtype=np.int32)
+        self.logprobs = np.zeros((self.rows, self.max_new, self.n), dtype=np.float32)
+        self.counts = np.zeros((self.rows, self.max_new), dtype=np.int32)
+        self.entropy = np.zeros((self.rows, self.max_new), dtype=np.float32) if entropy else None
+
+    def attach(self, result, lead=None):
+        """The arrays as attributes alt_tokens / alt_logprobs / alt_counts / entropy of `result`, rows reshaped to `lead`"""
+        lead = (self.rows,) if lead is None else tuple(lead)
+        result.alt_tokens = self.tokens.reshape(lead + (self.max_new, self.n))
+        result.alt_logprobs = self.logprobs.reshape(lead + (self.max_new, self.n))
+        result.alt_counts = self.counts.reshape(lead + (self.max_new,))
+        result.entropy = None if self.entropy is None else self.entropy.reshape(lead + (self.max_new,))
+        return result
+
+
+def token_alternatives(alt_tokens, alt_logprobs, alt_counts):
+    """One row's alternatives [max_new][n] as a list per token of (id, logprob) pairs"""
+    return [[(int(alt_tokens[i, j]), float(alt_logprobs[i, j])) for j in range(int(alt_counts[i]))]
+            for i in range(alt_tokens.shape[0])]
+
+
 class TranscribeResult:
     """What Context.transcribe returns.  tokens i32 [B][max_new] (padded with eot), lens i32 [B], logprobs f32 [B][max_new]
     (0 past lens), sum_logprob / avg_logprob f64 [B], no_speech_prob f32 [B] (None without a no-speech token).
     sum_logprob adds the log-probs of all lens[b] tokens (the stopping eot included) and avg_logprob = sum / (n_text + 1),
-    n_text = tokens before eot -- openai-whisper's DecodingTask.run (its finalize pads with eot)."""
+    n_text = tokens before eot -- openai-whisper's DecodingTask.run (its finalize pads with eot).
+    With alternatives=n: alt_tokens i32 / alt_logprobs f32 [B][max_new][n], alt_counts i32 and entropy f32 [B][max_new]
+    (Alternatives); None when not requested."""
+    alt_tokens = alt_logprobs = alt_counts = entropy = None
 
     def __init__(self, tokens, lens, logprobs, no_speech_prob, eot):
         self.tokens, self.lens, self.logprobs, self.no_speech_prob = tokens, lens, logprobs, no_speech_prob
@@ -310,14 +365,23 @@ def decode_alignment_text(tokens, length, start_frames, logprobs, eot, n_text=No
 class BestOfResult:
     """What Context.transcribe_mel_best_of returns.  tokens i32 [B][N][max_new], lens i32 [B][N], logprobs f32 [B][N][max_new],
     no_speech_prob f32 [B] (candidate 0's; None without a no-speech token), best i32 [B] (wm_rank_candidates) and
-    selected: the TranscribeResult of candidate best[b] of every row, with the same indices as its attribute `candidate`."""
+    selected: the TranscribeResult of candidate best[b] of every row, with the same indices as its attribute `candidate`.
+    With alternatives=n: alt_tokens / alt_logprobs [B][N][max_new][n], alt_counts / entropy [B][N][max_new] of every candidate
+    (None when not requested), and `selected` carries the chosen candidate's."""
+    alt_tokens = alt_logprobs = alt_counts = entropy = None
 
-    def __init__(self, tokens, lens, logprobs, no_speech_prob, best, eot):
+    def __init__(self, tokens, lens, logprobs, no_speech_prob, best, eot, alternatives=None):
         self.tokens, self.lens, self.logprobs, self.no_speech_prob, self.best = tokens, lens, logprobs, no_speech_prob, best
         rows = np.arange(tokens.shape[0])
         self.selected = TranscribeResult(np.ascontiguousarray(tokens[rows, best]), np.ascontiguousarray(lens[rows, best]),
                                          np.ascontiguousarray(logprobs[rows, best]), no_speech_prob, eot)
         self.selected.candidate = best
+        if alternatives is not None:
+            alternatives.attach(self, tokens.shape[:2])
+            s = self.selected
+            s.alt_tokens, s.alt_logprobs = (np.ascontiguousarray(a[rows, best]) for a in (self.alt_tokens, self.alt_logprobs))
+            s.alt_counts = np.ascontiguousarray(self.alt_counts[rows, best])
+            s.entropy = None if self.entropy is None else np.ascontiguousarray(self.entropy[rows, best])
 
 
 MAX_BEAM, MAX_BEAM_HYPS = 8, 16   # WM_MAX_BEAM, WM_MAX_BEAM_HYPS
@@ -437,7 +501,8 @@ def sampling_rules_args(top_k=None, top_p=None, min_p=None):
 def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                              compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
                              vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None, best_of=None,
-                             length_penalty=None, beam_size=None, patience=None, top_k=None, top_p=None, min_p=None):
+                             length_penalty=None, beam_size=None, patience=None, top_k=None, top_p=None, min_p=None,
+                             alternatives=None):
     """openai-whisper's decode_with_fallback, per chunk, over ctx.transcribe.
 
     Temperature step k decodes, as ONE batched call, the chunks that still need fallback (step 0: all of them) at
@@ -462,11 +527,17 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     call over the chunks' Context.logmel windows and keeps each chunk's best hypothesis under length_penalty; the steps
     above temperature 0 are unchanged.  patience without beam_size is a ValueError.
 
+    alternatives (None; 1 .. MAX_ALTERNATIVES): Context.request_alternatives goes in front of every decode call of the loop,
+    and the result gains alt_tokens / alt_logprobs [B][max_new][n], alt_counts / entropy [B][max_new] of each chunk's kept
+    attempt.  ValueError before any library call for a value out of range or together with beam_size.
+
     Returns a dict of per-chunk arrays (tokens, lens, logprobs, sum_logprob, avg_logprob, no_speech_prob,
     compression_ratio, temperature, seed, needs_fallback) and `steps`: [(temperature, seed, chunk indices)] per call."""
     pcm = np.asarray(pcm)
     beam_max_candidates(beam_size, patience)
     sampling = sampling_rules_args(top_k, top_p, min_p)
+    alt_kw = {} if alternatives_arg(alternatives, beam_size if beam_size is not None else patience) is None \
+        else dict(alternatives=int(alternatives))
 
     def decode(todo, t, sd):
         extra = fallback_step_extra(t, best_of, length_penalty, beam_size, patience)
@@ -475,9 +546,9 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
             mel = ctx.logmel(pcm[todo], n_mels=n_mels)
             return ctx.transcribe_mel(mel, np.arange(len(todo), dtype=np.int64) * (n_mels * N_FRAMES), N_FRAMES, 0, N_FRAMES,
                                       prompt, max_new, eot=eot, temperature=t, seed=sd, no_speech_token=no_speech_token,
-                                      sot_index=sot_index, **extra)
+                                      sot_index=sot_index, **extra, **alt_kw)
         return ctx.transcribe(pcm[todo], prompt, max_new, eot=eot, temperature=t, seed=sd,
-                              no_speech_token=no_speech_token, sot_index=sot_index)
+                              no_speech_token=no_speech_token, sot_index=sot_index, **alt_kw)
     if sampling is not None:
         ctx.set_sampling_rules(*sampling)
     try:
@@ -536,6 +607,14 @@ def fallback_decode(decode, B, vocab_size, max_new, eot, temperatures=FALLBACK_T
             out["temperature"][b] = t
             out["seed"][b] = sd
             out["needs_fallback"][b] = nf
+        if getattr(r, "alt_tokens", None) is not None:   # alternatives were requested: the kept attempt's, like everything else
+            for key in ("alt_tokens", "alt_logprobs", "alt_counts", "entropy"):
+                a = getattr(r, key)
+                if a is None:
+                    continue
+                if key not in out:
+                    out[key] = np.full((B,) + a.shape[1:], -1 if key == "alt_tokens" else 0, dtype=a.dtype)
+                out[key][todo] = a
         todo = todo[need]
     out["steps"] = steps
     return out
@@ -616,7 +695,7 @@ def should_skip_window(no_speech_prob, avg_logprob, no_speech_threshold=0.6, log
     return bool(skip)
 
 
-def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vocab=None, cleanup=True):
+def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vocab=None, cleanup=True, alternatives=None):
     """openai-whisper transcribe()'s handling of one decoded window (word_timestamps=False): slicing at consecutive
     timestamps, single_timestamp_ending, the seek update and the clearing of instantaneous / text-less segments.
       tokens : the window's generated tokens without the final eot (openai-whisper DecodingResult.tokens);
@@ -624,15 +703,20 @@ def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vo
       result : dict with temperature, avg_logprob, compression_ratio, no_speech_prob (copied into every segment).
     Returns (segments, next_seek).  A segment is text-less when, with a Vocab, its decoded text is blank, and without one
     when it has no token below eot.  cleanup=False (the word-timestamp path, where openai-whisper clears AFTER the word
-    step: clear_empty_segments) leaves the segments as sliced and returns (segments, next_seek, single_timestamp_ending)."""
+    step: clear_empty_segments) leaves the segments as sliced and returns (segments, next_seek, single_timestamp_ending).
+    alternatives (None: none): (per token of `tokens` its list of (id, logprob), per token its entropy) -- every segment then
+    carries the values of its own tokens as token_alternatives and token_entropy."""
     tokens = [int(t) for t in tokens]
     time_offset = float(seek * HOP_SECONDS)
     segment_duration = segment_size * HOP_SECONDS
 
-    def new_segment(start, end, toks):
+    def new_segment(start, end, toks, first=0):
         seg = dict(seek=seek, start=start, end=end, tokens=list(toks), temperature=result["temperature"],
                    avg_logprob=result["avg_logprob"], compression_ratio=result["compression_ratio"],
                    no_speech_prob=result["no_speech_prob"])
+        if alternatives is not None:
+            seg["token_alternatives"] = list(alternatives[0][first:first + len(toks)])
+            seg["token_entropy"] = list(alternatives[1][first:first + len(toks)])
         if vocab is not None:
             seg["text"] = vocab.decode([t for t in toks if t < eot])
         return seg
@@ -649,7 +733,7 @@ def window_segments(tokens, seek, segment_size, timestamp_begin, eot, result, vo
         for cur in slices:
             sl = tokens[last_slice:cur]
             segments.append(new_segment(time_offset + (sl[0] - timestamp_begin) * TIME_PRECISION,
-                                        time_offset + (sl[-1] - timestamp_begin) * TIME_PRECISION, sl))
+                                        time_offset + (sl[-1] - timestamp_begin) * TIME_PRECISION, sl, last_slice))
             last_slice = cur
         if single_timestamp_ending:
             next_seek = seek + segment_size
@@ -675,6 +759,8 @@ def clear_empty_segments(segments, eot, vocab=None, words=False):
         blank = (seg["text"].strip() == "") if vocab is not None else not any(t < eot for t in seg["tokens"])
         if seg["start"] == seg["end"] or blank:
             seg["tokens"] = []
+            if "token_alternatives" in seg:
+                seg["token_alternatives"], seg["token_entropy"] = [], []
             if vocab is not None:
                 seg["text"] = ""
             if words:
@@ -908,6 +994,9 @@ class _LongOptions(types.SimpleNamespace):
 
     def early(self, R):
         beam_max_candidates(self.beam_size, self.patience)
+        self.alt_kw = {}   # 24.
+        if alternatives_arg(self.alternatives, self.beam_size if self.beam_size is not None else self.patience, self.draft) is not None:
+            self.alt_kw = dict(alternatives=int(self.alternatives))
         self.rec_ids = list(range(R)) if self.recording_ids is None else [int(i) for i in self.recording_ids]
         if len(self.rec_ids) != R or any(i < 0 or i >= 65536 for i in self.rec_ids):
             raise ValueError("recording_ids: one per recording, each 0 .. 65535")
@@ -1102,7 +1191,7 @@ class _RoundRows:
         if o.rec_tables is not None:   # 22.: the tables of exactly this call's rows (a clip: its recording's)
             o.ctx.set_bias_rows([o.rec_tables[self.units[i].rec] for i in todo])
         kw = dict(eot=o.eot, temperature=t, seed=sd, no_speech_token=o.no_speech_token, sample_ids=[self.ids[i] for i in todo],
-                  **o.sot_kw, **extra)
+                  **o.sot_kw, **extra, **o.alt_kw)
         if o.words_decode:   # 18.: every attempt through the aligned entry; the kept one's start frames feed the word step
             r = self._decode_aligned(todo, prompts, kw, extra)
             for k, i in enumerate(todo):
@@ -1139,7 +1228,7 @@ class _RoundRows:
             kw = {k: v for k, v in kw.items() if k != "best_of"}
             res = getattr(o.ctx, "transcribe_%s_best_of_aligned" % kind)(*rows, extra["best_of"], **tail, **kw)
             res.selected.candidate = res.best
-        r = res.selected
+        r = res.selected   # (with alternatives: the chosen candidate's)
         r.start_frames = res.start_frames
         return r
 
@@ -1331,7 +1420,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
                     boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None, recording_bias=None,
-                    top_k=None, top_p=None, min_p=None):
+                    top_k=None, top_p=None, min_p=None, alternatives=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1492,6 +1581,14 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        the temperature-0 step, beam search and a draft's speculative steps ignore them.  Hugging Face's long-form fallback samples
        under its generation config's top_k = 50.  ValueError before any library call for a bad value (sampling_rules_args).  With
        all three None the function makes exactly the calls it made before the arguments existed.
+    24. alternatives (None; 1 .. MAX_ALTERNATIVES): Context.request_alternatives (wm_request_alternatives) goes in front of EVERY
+       decode call of every round -- each fallback step's rows, from the mel or from a reuse_encoder set, best-of and aligned
+       steps alike --, and the kept attempt's values go into each segment: token_alternatives, per token of the segment's `tokens`
+       a list of (id, logprob) -- the n best admissible ids at that position with their log-probs under the filtered
+       distribution at temperature 1 --, and token_entropy, per token the entropy of that distribution in nats.  A segment
+       cleared as empty loses both with its tokens.  ValueError before any library call for a value out of range and together
+       with beam_size or draft (a beam's alternatives need its ancestry; a speculative step verifies the greedy choice alone).
+       With None the function makes exactly the calls it made before the argument existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1562,6 +1659,11 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                 n_text = n_text_tokens(res["tokens"][i, :res["lens"][i]], eot)
                 tokens = res["tokens"][i, :n_text]
                 result = {k: float(res[k][i]) for k in ("temperature", "avg_logprob", "compression_ratio", "no_speech_prob")}
+                alt_kw = {}   # 24.: the kept attempt's alternatives and entropy of the window's tokens
+                if "alt_tokens" in res:
+                    alt_kw = dict(alternatives=(token_alternatives(res["alt_tokens"][i, :n_text], res["alt_logprobs"][i, :n_text],
+                                                                   res["alt_counts"][i, :n_text]),
+                                                [float(h) for h in res["entropy"][i, :n_text]]))
                 skip = should_skip_window(result["no_speech_prob"], result["avg_logprob"], no_speech_threshold,
                                           logprob_threshold)
                 u.record_window(o, sizes[i], prompts[i], [st[0] for st in res["steps"] if i in st[2]], skip, tokens, n_round,
@@ -1570,9 +1672,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     u.seek += sizes[i]
                 elif o.words_on:
                     kept.append((i,) + window_segments(tokens, u.seek, sizes[i], timestamp_begin, eot, result, vocab,
-                                                       cleanup=False))
+                                                       cleanup=False, **alt_kw))
                 else:
-                    u.commit(o, *window_segments(tokens, u.seek, sizes[i], timestamp_begin, eot, result, vocab),
+                    u.commit(o, *window_segments(tokens, u.seek, sizes[i], timestamp_begin, eot, result, vocab, **alt_kw),
                              result["temperature"])
             if kept:
                 if o.panel_pending and not o.words_decode:   # 16.
@@ -2076,6 +2178,25 @@ class Context:
         a = np.ascontiguousarray(list(budgets), dtype=np.int32)
         _check(self.lib, self.lib.wm_set_token_budgets(self.handle, _ptr(a) if a.size else None, int(a.size)))
 
+    def request_alternatives(self, n, rows, max_new, entropy=True):
+        """Top-n alternatives and entropy per generated token of the NEXT transcribe call on this context
+        (wm_request_alternatives; consumed by it whatever happens): `rows` hypotheses (the call's B, or B * best_of) of max_new
+        tokens, n in 1 .. MAX_ALTERNATIVES.  Returns the Alternatives whose arrays that call fills; the context keeps them alive
+        until the next request.  n None drops a pending request."""
+        fn = self.lib.wm_request_alternatives
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        if n is None:
+            _check(self.lib, fn(self.handle, None))
+            self._alt_request = None
+            return None
+        a = Alternatives(n, rows, max_new, entropy)
+        req = wm_alternatives_out(a.n, a.rows, a.max_new, _ptr(a.tokens).value, _ptr(a.logprobs).value, _ptr(a.counts).value,
+                                  _ptr(a.entropy).value if a.entropy is not None else None)
+        self._alt_request = (a, req)
+        _check(self.lib, fn(self.handle, ctypes.byref(req)))
+        return a
+
     def transcribe_greedy(self, pcm, prompt, max_new, eot=-1, mem=WM_MEM_HOST, pcm_dtype=None, B=None, budgets=None):
         """pcm: host array [B][480000] (int16/float32/float64), or a device pointer
         (c_void_p) with pcm_dtype and B given when mem == WM_MEM_DEVICE.  budgets: per-chunk token budgets
@@ -2097,9 +2218,12 @@ class Context:
                                                        _ptr(lens), mem))
         return toks, lens
 
-    def transcribe_raw(self, pcm, prompt, max_new, eot=-1, opts=None, logprobs=True, no_speech=False, budgets=None):
+    def transcribe_raw(self, pcm, prompt, max_new, eot=-1, opts=None, logprobs=True, no_speech=False, budgets=None,
+                       alternatives=None):
         """wm_transcribe on host arrays: opts a wm_decode_opts or None (NULL); logprobs / no_speech request the two
-        optional outputs.  Returns (tokens, lens, logprobs or None, no_speech_prob or None)."""
+        optional outputs.  Returns (tokens, lens, logprobs or None, no_speech_prob or None) -- and, with alternatives=n, the
+        call's Alternatives as a fifth element."""
+        n_alt = alternatives_arg(alternatives)
         if budgets is not None:
             self.set_token_budgets(budgets)
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
@@ -2109,30 +2233,37 @@ class Context:
         lens = np.empty(B, dtype=np.int32)
         lp = np.empty((B, max_new), dtype=np.float32) if logprobs else None
         ns = np.empty(B, dtype=np.float32) if no_speech else None
+        alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None   # (last: nothing can fail between it and the call)
         _check(self.lib, self.lib.wm_transcribe(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], B, _ptr(prompt), len(prompt),
                                                 max_new, eot, ctypes.byref(opts) if opts is not None else None,
                                                 _ptr(toks), _ptr(lens), _ptr(lp) if lp is not None else None,
                                                 _ptr(ns) if ns is not None else None, WM_MEM_HOST))
-        return toks, lens, lp, ns
+        return (toks, lens, lp, ns) if alt is None else (toks, lens, lp, ns, alt)
 
     def transcribe(self, pcm, prompt, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1, sot_index=0,
-                   budgets=None):
+                   budgets=None, alternatives=None):
         """wm_transcribe: greedy (temperature 0) or sampled decode with per-token log-probs and, with no_speech_token >= 0,
-        openai-whisper's no_speech_prob.  Returns a TranscribeResult."""
+        openai-whisper's no_speech_prob.  alternatives=n: also the n best admissible tokens and the entropy of every generated
+        position (request_alternatives).  Returns a TranscribeResult."""
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
-        toks, lens, lp, ns = self.transcribe_raw(pcm, prompt, max_new, eot, opts, logprobs=True,
-                                                 no_speech=no_speech_token >= 0, budgets=budgets)
-        return TranscribeResult(toks, lens, lp, ns, eot)
+        toks, lens, lp, ns, *alt = self.transcribe_raw(pcm, prompt, max_new, eot, opts, logprobs=True,
+                                                       no_speech=no_speech_token >= 0, budgets=budgets, alternatives=alternatives)
+        return self._with_alternatives(TranscribeResult(toks, lens, lp, ns, eot), alt)
+
+    @staticmethod
+    def _with_alternatives(result, alt):
+        """`result` with the Alternatives of a raw call's optional fifth element (alt: [] or [Alternatives]) attached"""
+        return alt[0].attach(result) if alt else result
 
     def transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                                  compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
                                  vocab=None, seed=0, no_speech_token=-1, sot_index=0, best_of=None, length_penalty=None,
-                                 beam_size=None, patience=None, top_k=None, top_p=None, min_p=None):
+                                 beam_size=None, patience=None, top_k=None, top_p=None, min_p=None, alternatives=None):
         """openai-whisper's temperature fallback (module function transcribe_with_fallback) on this context."""
         return transcribe_with_fallback(self, pcm, prompt, max_new, eot, temperatures, compression_ratio_threshold,
                                         logprob_threshold, no_speech_threshold, vocab, seed, no_speech_token, sot_index,
                                         best_of=best_of, length_penalty=length_penalty, beam_size=beam_size, patience=patience,
-                                        top_k=top_k, top_p=top_p, min_p=min_p)
+                                        top_k=top_k, top_p=top_p, min_p=min_p, alternatives=alternatives)
 
     def _mel_rows(self, mel, mel_base, mel_len, seek, n_frames, mem):
         """(the arguments that name the B rows of a wm_*_mel* call, each keeping its array alive; B)"""
@@ -2177,14 +2308,16 @@ class Context:
 
     def transcribe_mel_raw(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, opts=None,
                            sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                           sot_tail=None):
+                           sot_tail=None, alternatives=None):
         """wm_transcribe_mel: mel is a host f32 array (mem WM_MEM_HOST) or a device pointer (WM_MEM_DEVICE); mel_base i64,
         mel_len / seek / n_frames i32 [B]; prompts [B][n_prompt]; sample_ids u32 [B] or None.  Returns (tokens, lens,
         logprobs or None, no_speech_prob or None).
         Prompts of different lengths -- a list of B lists, or prompts [B][stride] with prompt_len i32 [B] -- go to
         wm_transcribe_mel_ragged with sot_tail (<|startoftranscript|> is the sot_tail-th token from the end of every
         prompt; default 1, opts.sot_index is not read).  A list of lists of ONE length without prompt_len stays
-        wm_transcribe_mel; there a sot_tail, when given, replaces opts.sot_index by n_prompt - sot_tail."""
+        wm_transcribe_mel; there a sot_tail, when given, replaces opts.sot_index by n_prompt - sot_tail.
+        alternatives=n: the call's Alternatives as a fifth element (request_alternatives)."""
+        n_alt = alternatives_arg(alternatives)
         if budgets is not None:
             self.set_token_budgets(budgets)
         head, B = self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem)
@@ -2196,11 +2329,12 @@ class Context:
         rows = (self.handle, *head, B, _ptr(pr), pr.shape[1])
         rest = (_ptr_or_null(ids), max_new, eot, ctypes.byref(opts) if opts is not None else None, _ptr(toks), _ptr(lens),
                 _ptr_or_null(lp), _ptr_or_null(ns), mem)
+        alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None
         if plen is not None:
             _check(self.lib, self.lib.wm_transcribe_mel_ragged(*rows, _ptr(plen), 1 if sot_tail is None else int(sot_tail), *rest))
         else:
             _check(self.lib, self.lib.wm_transcribe_mel(*rows, *rest))
-        return toks, lens, lp, ns
+        return (toks, lens, lp, ns) if alt is None else (toks, lens, lp, ns, alt)
 
     def transcribe_mel_speculative(self, draft, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, draft_len, eot=-1,
                                    temperature=0.0, no_speech_token=-1, sot_index=0, mem=WM_MEM_HOST, budgets=None):
@@ -2227,20 +2361,21 @@ class Context:
 
     def transcribe_mel_best_of(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1, temperature=0.0,
                                seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None,
-                               prompt_len=None, sot_tail=None, length_penalty=None):
+                               prompt_len=None, sot_tail=None, length_penalty=None, alternatives=None):
         """wm_transcribe_mel_best_of: transcribe_mel's arguments (uniform or ragged prompts as in transcribe_mel_raw) with
         best_of sampled candidates per row that share the row's encoder pass and cross-attention cache; length_penalty None
-        is openai-whisper's None.  Returns a BestOfResult."""
+        is openai-whisper's None.  alternatives=n: every candidate's alternatives and entropy.  Returns a BestOfResult."""
         return self._best_of_call(self.lib.wm_transcribe_mel_best_of,
                                   lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new,
                                   best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
-                                  sot_tail, length_penalty)
+                                  sot_tail, length_penalty, alternatives=alternatives)
 
     def _best_of_call(self, fn, rows, tail, prompts, max_new, best_of, eot, temperature, seed, no_speech_token, sot_index,
-                      sample_ids, budgets, prompt_len, sot_tail, length_penalty, aligned=None):
+                      sample_ids, budgets, prompt_len, sot_tail, length_penalty, aligned=None, alternatives=None):
         """wm_transcribe_mel_best_of / wm_transcribe_windows, which differ in the arguments that name the rows -- rows() gives
         (them, B): _mel_rows, _window_rows -- and in the tail (mem).  aligned = (medfilt_width, qk_scale, capture_matrix): fn is
-        the aligned counterpart, and the result carries start_frames (and matrix)."""
+        the aligned counterpart, and the result carries start_frames (and matrix).  alternatives: None or n (every candidate's)."""
+        n_alt = alternatives_arg(alternatives)
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         if budgets is not None:
             self.set_token_budgets(budgets)
@@ -2254,11 +2389,12 @@ class Context:
         ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
         best = np.empty(B, dtype=np.int32)
         align_in, align_out, start, matrix = self._hyp_aligned_args(aligned, B, max_new)
+        alt = self.request_alternatives(n_alt, B * max(N, 1), max_new) if n_alt else None
         _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
                             1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), N,
                             float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts),
                             *align_in, _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(best), *align_out, *tail))
-        r = BestOfResult(toks, lens, lp, ns, best, eot)
+        r = BestOfResult(toks, lens, lp, ns, best, eot, alternatives=alt)
         if aligned is not None:
             r.start_frames, r.matrix = start, matrix
         return r
@@ -2319,22 +2455,28 @@ class Context:
 
     def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                        no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                       sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None):
+                       sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None, alternatives=None):
         """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
+        alternatives=n: also the n best admissible tokens and the entropy of every generated position (not with beam_size).
         Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw.
         best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`).
         beam_size (None: no beam search; with patience): transcribe_mel_beam at temperature 0 -- sample_ids and the seed play
         no part -- and the result is its `selected` (with `hypothesis`)."""
+        alternatives_arg(alternatives, beam_size if beam_size is not None else patience)
         win = (mel, mel_base, mel_len, seek, n_frames, prompts, max_new)
         common = dict(mem=mem, budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail)
         entry = dict(common, eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, length_penalty=length_penalty)
+
+        def plain():
+            toks, lens, lp, ns, *alt = self.transcribe_mel_raw(
+                *win, eot, wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index)),
+                sample_ids, logprobs=True, no_speech=no_speech_token >= 0, alternatives=alternatives, **common)
+            return self._with_alternatives(TranscribeResult(toks, lens, lp, ns, eot), alt)
         return self._decode_entry(
             lambda: self.transcribe_mel_beam(*win, beam_size, patience=patience, **entry),
-            lambda: self.transcribe_mel_best_of(*win, best_of, temperature=temperature, seed=seed, sample_ids=sample_ids, **entry),
-            lambda: TranscribeResult(*self.transcribe_mel_raw(
-                *win, eot, wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index)),
-                sample_ids, logprobs=True, no_speech=no_speech_token >= 0, **common), eot),
-            temperature, best_of, beam_size, patience)
+            lambda: self.transcribe_mel_best_of(*win, best_of, temperature=temperature, seed=seed, sample_ids=sample_ids,
+                                                alternatives=alternatives, **entry),
+            plain, temperature, best_of, beam_size, patience)
 
     @staticmethod
     def _decode_entry(beam, candidates, plain, temperature, best_of, beam_size, patience):
@@ -2370,12 +2512,12 @@ class Context:
 
     def transcribe_windows_best_of(self, windows, rows, prompts, max_new, best_of=1, eot=-1, temperature=0.0, seed=0,
                                    no_speech_token=-1, sot_index=0, sample_ids=None, budgets=None, prompt_len=None,
-                                   sot_tail=None, length_penalty=None):
+                                   sot_tail=None, length_penalty=None, alternatives=None):
         """wm_transcribe_windows: transcribe_mel_best_of with rows of a Windows set (rows None: all of them, in order) in
         place of the mel windows.  Same bits.  Returns a BestOfResult."""
         return self._best_of_call(self.lib.wm_transcribe_windows, lambda: self._window_rows(windows, rows), (), prompts, max_new,
                                   best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
-                                  sot_tail, length_penalty)
+                                  sot_tail, length_penalty, alternatives=alternatives)
 
     def transcribe_windows_beam(self, windows, rows, prompts, max_new, beam_size, eot=-1, patience=None, no_speech_token=-1,
                                 sot_index=0, budgets=None, prompt_len=None, sot_tail=None, length_penalty=None,
@@ -2387,27 +2529,34 @@ class Context:
 
     def transcribe_windows(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
                            sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, best_of=None,
-                           length_penalty=None, beam_size=None, patience=None):
+                           length_penalty=None, beam_size=None, patience=None, alternatives=None):
         """transcribe_mel with rows of a Windows set in place of the mel windows: the same bits, no encoder pass.  Returns a
-        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel)."""
+        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel; alternatives=n as there)."""
+        alternatives_arg(alternatives, beam_size if beam_size is not None else patience)
         common = dict(eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, budgets=budgets, prompt_len=prompt_len,
                       sot_tail=sot_tail, length_penalty=length_penalty)
 
         def candidates(n):
             return self.transcribe_windows_best_of(windows, rows, prompts, max_new, n, temperature=temperature, seed=seed,
-                                                   sample_ids=sample_ids, **common)
+                                                   sample_ids=sample_ids, alternatives=alternatives, **common)
 
         def plain():   # (the set has no entry of its own for one sample: candidate 0 of N = 1)
             r = candidates(1)
-            return TranscribeResult(np.ascontiguousarray(r.tokens[:, 0]), np.ascontiguousarray(r.lens[:, 0]),
-                                    np.ascontiguousarray(r.logprobs[:, 0]), r.no_speech_prob, eot)
+            t = TranscribeResult(np.ascontiguousarray(r.tokens[:, 0]), np.ascontiguousarray(r.lens[:, 0]),
+                                 np.ascontiguousarray(r.logprobs[:, 0]), r.no_speech_prob, eot)
+            if r.alt_tokens is not None:
+                t.alt_tokens, t.alt_logprobs, t.alt_counts = (np.ascontiguousarray(a[:, 0]) for a in
+                                                              (r.alt_tokens, r.alt_logprobs, r.alt_counts))
+                t.entropy = None if r.entropy is None else np.ascontiguousarray(r.entropy[:, 0])
+            return t
         return self._decode_entry(
             lambda: self.transcribe_windows_beam(windows, rows, prompts, max_new, beam_size, patience=patience, **common),
             lambda: candidates(best_of), plain, temperature, best_of, beam_size, patience)
 
     def _aligned_call(self, fn, rows, tail, prompts, max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids,
-                      budgets, prompt_len, sot_tail, medfilt_width, qk_scale, capture_matrix):
+                      budgets, prompt_len, sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=None):
         """wm_transcribe_mel_aligned / wm_transcribe_windows_aligned (rows, tail: as in _best_of_call)"""
+        n_alt = alternatives_arg(alternatives)
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         if budgets is not None:
             self.set_token_budgets(budgets)
@@ -2419,15 +2568,17 @@ class Context:
         ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
         start = np.empty((B, max_new + 1), dtype=np.int32)
         matrix = self._capture_matrix(B, max_new) if capture_matrix else None
+        alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None
         _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
                             1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), max_new, eot, ctypes.byref(opts),
                             int(medfilt_width), float(qk_scale), _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(start),
                             *tail))
-        return AlignedResult(toks, lens, lp, ns, eot, start, matrix)
+        r = AlignedResult(toks, lens, lp, ns, eot, start, matrix)
+        return r if alt is None else alt.attach(r)
 
     def transcribe_mel_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                                no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                               sot_tail=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False):
+                               sot_tail=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False, alternatives=None):
         """wm_transcribe_mel_aligned: transcribe_mel (one sample per row; uniform or ragged prompts as in transcribe_mel_raw)
         whose decode also aligns what it generates, from its own cross-attention queries.  Tokens, lens, log-probs and
         no_speech_prob are transcribe_mel's bit for bit.  Returns an AlignedResult (start_frames; decode_alignment_text turns
@@ -2435,20 +2586,20 @@ class Context:
         return self._aligned_call(self.lib.wm_transcribe_mel_aligned,
                                   lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new, eot,
                                   temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len, sot_tail,
-                                  medfilt_width, qk_scale, capture_matrix)
+                                  medfilt_width, qk_scale, capture_matrix, alternatives=alternatives)
 
     def transcribe_windows_aligned(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
                                    sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, medfilt_width=7,
-                                   qk_scale=1.0, capture_matrix=False):
+                                   qk_scale=1.0, capture_matrix=False, alternatives=None):
         """wm_transcribe_windows_aligned: transcribe_mel_aligned with rows of a Windows set.  Same bits."""
         return self._aligned_call(self.lib.wm_transcribe_windows_aligned, lambda: self._window_rows(windows, rows), (), prompts,
                                   max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
-                                  sot_tail, medfilt_width, qk_scale, capture_matrix)
+                                  sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=alternatives)
 
     def transcribe_mel_best_of_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1,
                                        temperature=0.0, seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST,
                                        budgets=None, prompt_len=None, sot_tail=None, length_penalty=None, medfilt_width=7,
-                                       qk_scale=1.0, capture_matrix=False):
+                                       qk_scale=1.0, capture_matrix=False, alternatives=None):
         """wm_transcribe_mel_best_of_aligned: transcribe_mel_best_of whose decode also aligns, per row, the candidate best[b]
         from its own cross-attention queries.  Every field of the BestOfResult is transcribe_mel_best_of's bit for bit; it also
         carries start_frames i32 [B][max_new + 1] of candidate best[b] (as AlignedResult's; decode_alignment_text takes
@@ -2457,16 +2608,17 @@ class Context:
         return self._best_of_call(self.lib.wm_transcribe_mel_best_of_aligned,
                                   lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new,
                                   best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
-                                  sot_tail, length_penalty, aligned=(medfilt_width, qk_scale, capture_matrix))
+                                  sot_tail, length_penalty, aligned=(medfilt_width, qk_scale, capture_matrix), alternatives=alternatives)
 
     def transcribe_windows_best_of_aligned(self, windows, rows, prompts, max_new, best_of=1, eot=-1, temperature=0.0, seed=0,
                                            no_speech_token=-1, sot_index=0, sample_ids=None, budgets=None, prompt_len=None,
                                            sot_tail=None, length_penalty=None, medfilt_width=7, qk_scale=1.0,
-                                           capture_matrix=False):
+                                           capture_matrix=False, alternatives=None):
         """wm_transcribe_windows_best_of_aligned: transcribe_mel_best_of_aligned with rows of a Windows set.  Same bits."""
         return self._best_of_call(self.lib.wm_transcribe_windows_best_of_aligned, lambda: self._window_rows(windows, rows), (),
                                   prompts, max_new, best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets,
-                                  prompt_len, sot_tail, length_penalty, aligned=(medfilt_width, qk_scale, capture_matrix))
+                                  prompt_len, sot_tail, length_penalty, aligned=(medfilt_width, qk_scale, capture_matrix),
+                                  alternatives=alternatives)
 
     def transcribe_mel_beam_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, beam_size, eot=-1, patience=None,
                                     no_speech_token=-1, sot_index=0, mem=WM_MEM_HOST, budgets=None, prompt_len=None, sot_tail=None,

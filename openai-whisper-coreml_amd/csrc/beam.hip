@@ -13,6 +13,7 @@
 #include "beam.h"
 #include "dec_close.h"
 #include "model.h"
+#include "row_list.h"
 
 namespace {
 
@@ -69,43 +70,21 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
     __syncthreads();
     const float norm = norm_s;
     const bool forced = forced_s != 0;
-    // a thread's ids are n = tid + 1024 i; its best admissible key below `bound` (the keys at and above the last listed one are
-    // taken: the list is built in descending key order).  Every thread scans once; afterwards only a round's winner rescans.
-    int4 rng = make_int4(0, V, 0, 0);
-    if (ts.rng) rng = *(const int4 *)(ts.rng + b * 4);
-    const unsigned *mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
+    // the row's N + 1 best admissible ids in descending key order: the list scan of row_list.h
+    RowAdmit adm;
+    adm.V = V;
+    adm.rng = make_int4(0, V, 0, 0);
+    if (ts.rng) adm.rng = *(const int4 *)(ts.rng + b * 4);
+    adm.forced = forced;
+    adm.mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
     // repetition rules: the row's no-repeat bitmap (the penalty is already in the stored logits)
-    const unsigned *brow = ban ? ban + (long)b * ban_words : nullptr;
-    auto local_best = [&](unsigned long long bound) {
-        unsigned long long best = 0ull;
-        for (int n = threadIdx.x; n < V; n += 1024) {
-            const bool in_text = !forced && n >= rng.x && n < rng.y, in_ts = n >= rng.z && n < rng.w;
-            if (!(in_text || in_ts) || (mrow && ((mrow[n >> 5] >> (n & 31)) & 1u))) continue;
-            if (brow && ((brow[n >> 5] >> (n & 31)) & 1u)) continue;
-            const unsigned long long k = argmax_key(logits[(long)b * ldo + n], n);
-            if (k < bound && k > best) best = k;
-        }
-        return best;
-    };
-    unsigned long long mine = local_best(~0ull);
-    int count = 0;
-    for (int r = 0; r < K; ++r) {   // K rounds of a workgroup-wide maximum; the winner's thread retires it
-        unsigned long long key = key_max_xor<64>(mine);
-        if (lane == 0) red_s[(r + 1) & 1][wave] = key;
-        __syncthreads();
-        key = lane < 16 ? red_s[(r + 1) & 1][lane] : 0ull;
-        key = __shfl(key_max_xor<16>(key), 0);
-        if (key == 0ull) break;                       // nothing admissible is left (uniform)
-        const float lp = argmax_key_value(key) - norm;
-        if (!(lp > -INFINITY)) break;                 // -inf (and NaN) is never listed (uniform)
-        if (threadIdx.x == 0) {
-            bm.list_tok[b * WM_BEAM_LIST + r] = argmax_key_index(key);
-            bm.list_lp[b * WM_BEAM_LIST + r] = lp;
-            if (tr) { tr[2 + r] = __int_as_float(argmax_key_index(key)); tr[2 + WM_BEAM_LIST + r] = lp; }
-        }
-        ++count;
-        if (mine == key) mine = local_best(key);
-    }
+    adm.brow = ban ? ban + (long)b * ban_words : nullptr;
+    const int count = row_list_scan(logits + (long)b * ldo, adm, K, norm, red_s, [](int, float) {},
+                                    [&](int r, unsigned long long key, float lp) {
+        bm.list_tok[b * WM_BEAM_LIST + r] = argmax_key_index(key);
+        bm.list_lp[b * WM_BEAM_LIST + r] = lp;
+        if (tr) { tr[2 + r] = __int_as_float(argmax_key_index(key)); tr[2 + WM_BEAM_LIST + r] = lp; }
+    });
     if (threadIdx.x == 0) {
         bm.list_n[b] = count;
         if (tr) { tr[0] = __int_as_float(count); tr[1] = my_sum; }

@@ -1436,6 +1436,63 @@ extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V
     return WM_OK;
 }
 
+// The alternatives kernel alone on host-given rows at generated index 0 (n_prompt 2, position 1): the partials restated on the
+// host as for wmdbg_beam_topk (host_row_partials), so the two kernels see the same normaliser.  The outputs are uploaded as the
+// caller filled them and downloaded whole: a sentinel shows what the kernel wrote.
+extern "C" int wmdbg_alternatives(wm_ctx *ctx, const float *logits, int rows, int V, int n, const int32_t *suppress, int n_suppress,
+                                  const int32_t *rng, int32_t ts_begin, int32_t *counts, int32_t *tokens, float *logprobs,
+                                  float *entropy) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(logits && tokens && logprobs && rows >= 1 && rows <= WM_DEC_MAXB && V >= 16 && n >= 1 && n <= WM_MAX_ALTERNATIVES &&
+                   n_suppress >= 0 && (n_suppress == 0 || suppress) && (!rng || (ts_begin >= 0 && ts_begin <= V)),
+               WM_ERR_INVALID, "alternatives: bad args");
+    HostPartials hp;
+    WM_TRY(host_row_partials("alternatives", logits, rows, V, suppress, n_suppress, rng, &hp));
+    std::copy(hp.mask.begin(), hp.mask.begin() + hp.mw, hp.mask.begin() + hp.mw);   // (gi 0 reads the first-position bitmap)
+    const int32_t pos = 1;
+    WmXPar xp;
+    memset(&xp, 0, sizeof(xp));
+    xp.sot_pos = -1; xp.n_prompt = 2;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    WmTsDev ts;
+    memset(&ts, 0, sizeof(ts));
+    WmXDev xd;
+    memset(&xd, 0, sizeof(xd));
+    WmAltPar ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.n = n; ap.max_new = 1;
+    const float *dlg;
+    const unsigned long long *dkt;
+    const unsigned *dmask;
+    const int *dpos;
+    const WmAltPar *dpar;
+    WM_TRY(pool.get(&dlg, hp.lg.data(), hp.lg.size() * 4, s));
+    WM_TRY(pool.get(&xd.txt, hp.txt.data(), hp.txt.size() * 4, s));
+    WM_TRY(pool.get(&dkt, hp.kt.data(), hp.kt.size() * 8, s));
+    WM_TRY(pool.get(&dmask, hp.mask.data(), hp.mask.size() * 4, s));
+    if (rng) {
+        WM_TRY(pool.get(&ts.rng, rng, (size_t)rows * 16, s));
+        WM_TRY(pool.get(&ts.key_ts, hp.ks.data(), hp.ks.size() * 8, s));
+        WM_TRY(pool.get(&ts.lse, hp.tsl.data(), hp.tsl.size() * 4, s));
+        ts.ts_begin = ts_begin; ts.n_vocab = V;
+    }
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&xd.par, &xp, sizeof(xp), s));
+    WM_TRY(pool.get(&ap.tok, tokens, (size_t)rows * n * 4, s));
+    WM_TRY(pool.get(&ap.lp, logprobs, (size_t)rows * n * 4, s));
+    if (counts) WM_TRY(pool.get(&ap.cnt, counts, (size_t)rows * 4, s));
+    if (entropy) WM_TRY(pool.get(&ap.ent, entropy, (size_t)rows * 4, s));
+    WM_TRY(pool.get(&dpar, &ap, sizeof(ap), s));
+    WM_TRY(wm_alternatives(ctx, dlg, hp.vpad, V, dkt, rows, ts, xd, dmask, hp.mw, 2, dpos, WmStopDev{}, nullptr, 0, dpar));
+    WM_HIP(hipMemcpyAsync(tokens, ap.tok, (size_t)rows * n * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(logprobs, ap.lp, (size_t)rows * n * 4, hipMemcpyDeviceToHost, s));
+    if (counts) WM_HIP(hipMemcpyAsync(counts, ap.cnt, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+    if (entropy) WM_HIP(hipMemcpyAsync(entropy, ap.ent, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
 // The truncation kernel alone on host-given rows at generated index gi (n_prompt 2, position gi + 1): the partials restated on
 // the host as for wmdbg_beam_topk, the row's keys and winner values in scratch.
 extern "C" int wmdbg_sample_truncate(wm_ctx *ctx, const float *logits, int rows, int V, const int32_t *suppress, int n_suppress,

@@ -80,6 +80,7 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc_t(m, &m->dx_nospeech, WM_DEC_MAXB, s));
     WM_TRY(dalloc(m, (void **)&m->dx_par, sizeof(WmXPar), s));
     WM_TRY(dalloc(m, (void **)&m->dsamp_par, sizeof(WmSampPar), s));
+    WM_TRY(dalloc(m, (void **)&m->dalt_par, sizeof(WmAltPar), s));
     // (+16: the epilogue's padded 16-row blocks; second half: the rows' candidate words, WM_XIDS_CAND)
     WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)2 * WM_XIDS_CAND, s));
     WM_TRY(dalloc_t(m, &m->dmel_win, (size_t)WM_DEC_MAXB, s));
@@ -377,6 +378,33 @@ int wm_model_sample_truncate(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMod
                               rp.par ? rp.ban : nullptr, rp.words, m->dsamp_par, nullptr);
 }
 
+int wm_model_alt_begin(wm_ctx *ctx, int rows, int max_new, int n, WmAltPar *host_par) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && max_new >= 1 && n >= 1 && n <= WM_MAX_ALTERNATIVES, WM_ERR_INVALID,
+               "alternatives: %d rows x %d positions x %d entries", rows, max_new, n);
+    const size_t pos = (size_t)max_new * rows, list = (pos * n * 4 + 255) & ~(size_t)255, one = (pos * 4 + 255) & ~(size_t)255;
+    WM_TRY(m->alt_ws.reserve(ctx->stream, 2 * list + 2 * one));
+    char *p = (char *)m->alt_ws.p;
+    host_par->n = n; host_par->max_new = max_new;
+    host_par->tok = (int *)p; host_par->lp = (float *)(p + list);
+    host_par->cnt = (int *)(p + 2 * list); host_par->ent = (float *)(p + 2 * list + one);
+    // the pads: id -1 (0xff bytes), log-prob 0, count 0, entropy 0 -- what a position no workgroup writes keeps
+    WM_HIP(hipMemsetAsync(p, 0xff, list, ctx->stream));
+    WM_HIP(hipMemsetAsync(p + list, 0, list + 2 * one, ctx->stream));
+    WM_HIP(hipMemcpyAsync(m->dalt_par, host_par, sizeof(WmAltPar), hipMemcpyHostToDevice, ctx->stream));
+    return WM_OK;
+}
+
+int wm_model_alternatives(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(mode.alt && mode.x && !mode.beam && mode.panel <= 1, WM_ERR_STATE, "alternatives: an extended-decode group without beams");
+    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
+    const WmRepDev rp = wm_model_rep_dev(m, mode);
+    return wm_alternatives(ctx, m->dlogits, m->vpad, m->dims.n_vocab, m->dargmax, B, ts, wm_model_x_dev(m, mode),
+                           mode.mask ? m->dmask : nullptr, m->vpad / 32, n_prompt, m->dpos, wm_model_stop_dev(m, mode),
+                           rp.par ? rp.ban : nullptr, rp.words, m->dalt_par);
+}
+
 WmTsDev wm_model_ts_dev(const WmModel *m) {
     WmTsDev t;
     memset(&t, 0, sizeof(t));
@@ -613,7 +641,7 @@ void wm_model_destroy(wm_ctx *ctx) {
     if (m->h_spec) (void)hipHostFree(m->h_spec);
     m->spec_ws.release();
     for (void *p : m->allocs) (void)hipFree(p);
-    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->acap_ws, &m->beam_ws, &m->beam_trace}) b->release();
+    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->acap_ws, &m->beam_ws, &m->beam_trace, &m->alt_ws}) b->release();
     delete m;
     ctx->model = nullptr;
 }

@@ -137,6 +137,17 @@ struct WmSampPar {
     float top_p, min_p;
 };
 
+// Top-n alternatives and entropy (wm_request_alternatives; alternatives.hip): one launch per position
+// between the logits product and the close lists a row's n best admissible ids with their log-probs and sums its entropy.  n
+// and the buffers live in device memory (WmAltPar, written at prefill), so a captured position replays for any request.
+struct WmAltPar {
+    int n, max_new;   // entries per position; positions the buffers hold
+    int *tok;         // [max_new][rows][n] ids, -1 past the count
+    float *lp;        // [max_new][rows][n] log-probs, 0 past the count
+    int *cnt;         // [max_new][rows]
+    float *ent;       // [max_new][rows]
+};
+
 // The sequence bias (wm_set_sequence_bias; seqbias.hip): a table of token sequences with a bias each.
 // Entry s[0 .. n) matches a row iff n == 1 or the row's generated history g[0 .. k) ends in s[0 .. n - 1); total(t) is the f32
 // sum, from +0.0f in table order, of the biases of the matching entries whose last token is t, and the logit becomes
@@ -314,6 +325,9 @@ struct WmDecodeMode {
     // The sampling rules apply (wm_set_sampling_rules on a call with temperature > 0): the logits launch stores the f32 row and
     // wm_sample_truncate runs between it and the close.  Needs x.
     bool trunc = false;
+    // A request for alternatives is served (wm_request_alternatives): the logits launch stores the f32 row and wm_alternatives
+    // runs between it and the close (in front of wm_sample_truncate).  Needs x.
+    bool alt = false;
     // Panel width of a teacher-forced pass (wm_set_teacher_panel; 1: none): the step's rows are windows x panel, row c * panel + s
     // is position *dpos + s of window c -- the self-attention cache holds one entry per WINDOW, row (c, s) appends at and reads up
     // to its own position, the cross-attention is the candidate-group launch (wm_model_panel_step).  The teacher-forced entries
@@ -327,7 +341,7 @@ struct WmDecodeMode {
     int acap_base = 0, acap_Tq = 0, acap_J = 0;
     float *acap_q = nullptr;
     bool operator==(const WmDecodeMode &o) const {
-        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && rep == o.rep && sb == o.sb && sbt == o.sbt && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && alt == o.alt && rep == o.rep && sb == o.sb && sbt == o.sbt && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -474,6 +488,12 @@ struct WmModel {
     float samp_p = 1.f, samp_minp = 0.f;
     bool samp_on() const { return samp_k > 0 || samp_p < 1.f || samp_minp > 0.f; }
     WmSampPar *dsamp_par = nullptr;
+    // alternatives (wm_request_alternatives): the request pending for the NEXT transcribe call, the device block a group's
+    // prefill writes and the group's output buffers [tok | lp | cnt | ent] (reserved and pad-filled at prefill, grow-only)
+    bool alt_pending = false;
+    wm_alternatives_out alt_req = {};
+    WmAltPar *dalt_par = nullptr;
+    WmDevBuf alt_ws;
     // sequence bias (wm_set_sequence_bias): the context's expanded table, and the device state allocated at full capacity when
     // first switched on (dsb.par == null before that) -- never moved: the captured graphs hold the addresses
     bool sb_on = false;
@@ -580,6 +600,11 @@ int wm_model_set_repetition_rules(wm_ctx *ctx, float penalty, int ngram, int32_t
 int wm_model_set_sampling_rules(wm_ctx *ctx, int top_k, float top_p, float min_p);
 // the truncation launch of a generating position of a group with mode.trunc, between wm_model_decode_step (want_logits) and the close
 int wm_model_sample_truncate(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode);
+// a group's prefill with mode.alt: reserves alt_ws for rows x max_new x n, pad-fills it and uploads *host_par (which must outlive
+// the stream's copy) with the buffers' addresses filled in
+int wm_model_alt_begin(wm_ctx *ctx, int rows, int max_new, int n, WmAltPar *host_par);
+// the alternatives launch of a position of a group with mode.alt, between wm_model_decode_step (want_logits) and the close
+int wm_model_alternatives(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode);
 // the device view of the sequence-bias state (par == null when mode.sb is false)
 WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode);
 // an expanded table (empty: off) -> this context's device table; the first non-empty one allocates the state
@@ -846,6 +871,15 @@ int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, co
 int wm_sample_truncate(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, unsigned long long *tilemax, int rows,
                        const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
                        const WmStopDev &stop, const unsigned *ban, int ban_words, const WmSampPar *par, int *dbg);
+
+// alternatives.hip (top-n alternatives and entropy)
+// Per row (grid: rows) at a generated position gi < par->max_new: the par->n best ids of the admissible set of the stored f32
+// logits [rows][ldo] in descending key order (beam_topk's admissibility and list scan: row_list.h; `forced` and the normaliser
+// from the partials) with log-probs value - norm, the count and the entropy, written at [gi][row] of par's buffers (cnt, ent
+// nullable).  Rows with stop.done set and prompt positions are skipped.  Reads the partials, writes par's buffers alone.
+int wm_alternatives(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
+                    const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
+                    const WmStopDev &stop, const unsigned *ban, int ban_words, const WmAltPar *par);
 
 // repeat.hip (repetition rules)
 // Rebuild rows 0 .. B - 1 of rep.seen / rep.ban from the generated history of position *pos_ptr: tokens seq[(n_prompt + i) * B + b],

@@ -546,6 +546,21 @@ extern "C" int wm_set_token_budgets(wm_ctx *ctx, const int32_t *budgets, int n) 
     return WM_OK;
 } WM_API_CATCH
 
+extern "C" int wm_request_alternatives(wm_ctx *ctx, const wm_alternatives_out *req) try {
+    WM_MODEL(ctx);
+    if (!req) {
+        m->alt_pending = false;
+        return WM_OK;
+    }
+    WM_REQUIRE(req->n >= 1 && req->n <= WM_MAX_ALTERNATIVES, WM_ERR_INVALID, "request_alternatives: n %d outside [1, %d]", req->n,
+               WM_MAX_ALTERNATIVES);
+    WM_REQUIRE(req->tokens && req->logprobs, WM_ERR_INVALID, "request_alternatives: null tokens / logprobs");
+    WM_REQUIRE(req->rows >= 1 && req->max_new >= 1, WM_ERR_INVALID, "request_alternatives: rows or max_new below 1");
+    m->alt_req = *req;
+    m->alt_pending = true;
+    return WM_OK;
+} WM_API_CATCH
+
 // ---------------------------------------------------------------- word-level timestamps
 // openai-whisper's find_alignment (whisper/timing.py): a teacher-forced decoder pass that captures the alignment heads'
 // cross-attention queries, then the alignment kernels and DTW of align.hip.

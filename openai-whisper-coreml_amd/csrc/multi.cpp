@@ -214,6 +214,12 @@ extern "C" int wm_multi_transcribe_greedy(wm_multi *m, const void *pcm, wm_dtype
     for (int r = 0; r < R; ++r)
         WM_REQUIRE(!m->ctx[r]->model || !m->ctx[r]->model->sbt_on, WM_ERR_STATE,
                    "multi_transcribe_greedy does not support sequence-bias tables (device context %d has them)", r);
+    {   // a request for alternatives pending on a device context is consumed and refused (its rows are the device's slice: not built)
+        bool alt = false;
+        for (int r = 0; r < R; ++r)
+            if (m->ctx[r]->model && m->ctx[r]->model->alt_pending) { alt = true; m->ctx[r]->model->alt_pending = false; }
+        WM_REQUIRE(!alt, WM_ERR_STATE, "multi_transcribe_greedy does not serve alternatives (wm_request_alternatives)");
+    }
     {   // every size that feeds an allocation below is checked against the model BEFORE any thread exists
         const wm_dims &D = m->ctx[0]->model->dims;
         WM_REQUIRE(n_prompt >= 1 && n_prompt + max_new <= D.n_text_ctx, WM_ERR_INVALID,

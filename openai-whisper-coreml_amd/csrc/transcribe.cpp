@@ -94,7 +94,10 @@ struct LaneJob {
     WmRepPar rpar = {};            // its repetition rules (likewise)
     WmSampPar spar = {};           // its sampling rules (likewise)
     WmSbPar sbpar = {};            // its sequence-bias table's counts (likewise)
+    WmAltPar apar = {};            // its alternatives request: n and the lane's buffers (likewise)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
+    std::vector<int32_t> atok, acnt;   // its fetched alternatives: ids [max_new][Bg][n], counts [max_new][Bg]
+    std::vector<float> alp, aent;      // ... log-probs [max_new][Bg][n], entropy [max_new][Bg]
     std::vector<WmMelWin> win;     // its mel windows (wm_transcribe_mel)
     std::vector<int32_t> xrows;    // its rows of the window set (wm_transcribe_windows)
     // a beam group (wm_transcribe_mel_beam): its parameters and window budgets (sources of async uploads) and what a drain
@@ -179,6 +182,7 @@ struct TxCfg {
     std::vector<int32_t> hl, hh;
     int max_group_rows = 0;
     const int32_t *bias_rows = nullptr;   // row tables in force: the table of each row of the call [B] (wm_set_bias_rows), checked
+    const wm_alternatives_out *alt = nullptr;   // the call's alternatives request (wm_request_alternatives), checked; null: none
 };
 
 // the tokens row `b` of the call may generate
@@ -202,6 +206,7 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     j.mode.sb = m->sb_on || m->sbt_on;
     j.mode.rep = m->rep_on || j.mode.sb;   // (tx_validate turns the extended decode on with them; the bias reads the rules' bitmaps)
     j.mode.trunc = m->samp_on() && xc.on && xc.par.sample != 0;   // temperature 0 ignores the sampling rules: today's launches
+    j.mode.alt = cfg.alt != nullptr;   // (tx_validate turned the extended decode on with it)
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
     if (call.aligned) {   // the capture buffer and the alignment workspace, reserved before anything is enqueued
@@ -259,6 +264,12 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
         j.spar.top_k = m->samp_k; j.spar.top_p = m->samp_p; j.spar.min_p = m->samp_minp;
         WM_HIP(hipMemcpyAsync(m->dsamp_par, &j.spar, sizeof(WmSampPar), hipMemcpyHostToDevice, c->stream));
     }
+    // alternatives: n and the lane's buffers live in device memory too (the graph key holds `alt` alone); the buffers are
+    // reserved for this group and pad-filled here, so positions no workgroup writes (finished rows) read as pads
+    if (j.mode.alt) {
+        WM_REQUIRE(xc.on, WM_ERR_STATE, "alternatives need the extended decode");
+        WM_TRY(wm_model_alt_begin(c, Bg, call.max_new, cfg.alt->n, &j.apar));
+    }
     // sequence bias: the table was uploaded when it was set; its counts go with the group, so a captured graph replays for any table
     if (j.mode.sbt) {   // row tables: the pool was uploaded when it was set; the rows' group ranges go with the group likewise
         WM_REQUIRE(cfg.bias_rows, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
@@ -315,8 +326,11 @@ int lane_prompt_panels(LaneJob &j, const TxCall &call, const wm_ctx *caller) {
 // gen (a beam group's generating positions): the step also stores the f32 logits and the beam kernels close it.
 int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) {
     WmAlignCap cap = {j.alayers.data(), mode.acap_q, mode.acap_Tq, mode.acap_J, mode.acap_base};   // an aligned group: every step captures
-    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen || mode.trunc, 0, j.c->model->dims.n_vocab - 1, mode.acap ? &cap : nullptr, mode, n_prompt));
+    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen || mode.trunc || mode.alt, 0, j.c->model->dims.n_vocab - 1, mode.acap ? &cap : nullptr, mode, n_prompt));
     if (gen) return wm_model_beam_close(j.c, j.Bg, n_prompt, mode);
+    // alternatives: the row's list and entropy from the stored row and the partials as the logits launch left them -- in front of
+    // the truncation, which rewrites the per-tile keys.  At a prompt position its workgroups return at once, as the truncation's.
+    if (mode.alt) WM_TRY(wm_model_alternatives(j.c, j.Bg, n_prompt, mode));
     // sampling rules: the kept set and its draw, in line between the logits launch (which stored the f32 row) and the close.
     // The graph of a position is one for prompt and generated positions alike (the position lives on the device), so at a
     // prompt position of such a group the row store is wasted and the truncation workgroups return at once (gi < 0): one
@@ -527,7 +541,8 @@ int entry_checks(const TxCall &call) {
 // The checks every transcribe call goes through, and what they make of it: the call's longest prompt, the early stop, the
 // extended decode.  budgets: the call's (wm_set_token_budgets), clamped to max_new here.  opts == null with both extra
 // outputs null is the greedy decode exactly.
-int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg, const std::vector<int32_t> *bias_rows = nullptr) {
+int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg, const std::vector<int32_t> *bias_rows = nullptr,
+                const wm_alternatives_out *alt = nullptr) {
     WmModel *m = ctx->model;
     const WmAudioSrc &src = call.src;
     const TxPrompts &p = call.prompts;
@@ -583,7 +598,15 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     WM_REQUIRE(!call.no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
     WM_REQUIRE(!call.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
     // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
-    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on;
+    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || alt;
+    if (alt) {   // the call's alternatives request (wm_request_alternatives checked n and the pointers)
+        WM_REQUIRE(!call.beam, WM_ERR_STATE, "alternatives are not served by beam-search calls");
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "alternatives are not supported by the all-f32 precision path");
+        WM_REQUIRE(alt->rows == (int64_t)B * call.n_cand && alt->max_new == max_new, WM_ERR_INVALID,
+                   "alternatives were requested for %lld rows x %d tokens, the call has %lld x %d", (long long)alt->rows, alt->max_new,
+                   (long long)B * call.n_cand, max_new);
+        cfg->alt = alt;
+    }
     WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
     WM_REQUIRE(!(m->sb_on || m->sbt_on) || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
     WM_REQUIRE(!(m->samp_on() && T > 0.f) || !ctx->dbg_hooks, WM_ERR_STATE, "the sampling rules are not supported by the all-f32 precision path");
@@ -748,6 +771,14 @@ int lane_fetch(TxRun &r, LaneJob &j) {
         j.ns.resize(j.Bg);
         WM_HIP(hipMemcpyAsync(j.ns.data(), m->dx_nospeech, j.ns.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
     }
+    if (j.mode.alt) {   // [gi][b][n] and [gi][b], as the kernel left them
+        const size_t np = (size_t)call.max_new * j.Bg;
+        j.atok.resize(np * j.apar.n); j.alp.resize(np * j.apar.n); j.acnt.resize(np); j.aent.resize(np);
+        WM_HIP(hipMemcpyAsync(j.atok.data(), j.apar.tok, j.atok.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+        WM_HIP(hipMemcpyAsync(j.alp.data(), j.apar.lp, j.alp.size() * 4, hipMemcpyDeviceToHost, j.c->stream));
+        WM_HIP(hipMemcpyAsync(j.acnt.data(), j.apar.cnt, np * 4, hipMemcpyDeviceToHost, j.c->stream));
+        WM_HIP(hipMemcpyAsync(j.aent.data(), j.apar.ent, np * 4, hipMemcpyDeviceToHost, j.c->stream));
+    }
     if (call.beam) WM_TRY(beam_fetch(j, call.max_new, call.trace != nullptr));
     j.state = LaneJob::DRAINING;
     return WM_OK;
@@ -878,6 +909,9 @@ int lane_finish(TxRun &r, LaneJob &j, bool *done) {
     } else {
         wm_group_rows_out(j.gen.data(), j.lp.data(), j.ns.data(), r.cfg.stop.budgets, call.eot, call.n_cand, j.b0, j.Bg, call.max_new,
                           call.tokens_out, call.lens_out, r.cfg.xc.logprobs, r.cfg.xc.no_speech);
+        if (const wm_alternatives_out *a = r.cfg.alt)   // by the row map and the lengths just written
+            wm_group_alt_out(j.atok.data(), j.alp.data(), j.acnt.data(), j.aent.data(), a->n, call.n_cand, j.b0, j.Bg, call.max_new,
+                             call.lens_out, a->tokens, a->logprobs, a->counts, a->entropy);
     }
     wm_add_stage_ms(j.ev.e, 3, call.src.windows, j.stage_sum);
     if (call.aligned) {   // the rows' lengths are known now: (candidates, beams) the windows' ranking, the alignment tail, then ALIGNING
@@ -983,6 +1017,10 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
     // ... and so is the row map of the sequence-bias tables (wm_set_bias_rows)
     std::vector<int32_t> bias_rows;
     if (ctx && ctx->model) bias_rows.swap(ctx->model->bias_rows_host);
+    // ... and the request for alternatives (wm_request_alternatives)
+    wm_alternatives_out alt_req = {};
+    bool alt_on = false;
+    if (ctx && ctx->model) { alt_on = ctx->model->alt_pending; alt_req = ctx->model->alt_req; ctx->model->alt_pending = false; }
     WM_TRY(entry_checks(call));
     WM_MODEL(ctx);
     std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
@@ -991,7 +1029,7 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
         call.logprobs_out = lp_own.data();
     }
     TxCfg cfg;
-    WM_TRY(tx_validate(ctx, call, budgets, &cfg, bias_rows.empty() ? nullptr : &bias_rows));
+    WM_TRY(tx_validate(ctx, call, budgets, &cfg, bias_rows.empty() ? nullptr : &bias_rows, alt_on ? &alt_req : nullptr));
     // the plan: decode groups and lanes.  A masked clone that cannot be made switches the masks off and asks again.
     WmTxPlanIn pin;
     pin.B = call.B; pin.N = call.n_cand;
@@ -1215,6 +1253,8 @@ int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
     std::vector<int32_t> budgets;   // consumed by this call whatever happens next (tx_transcribe)
     if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
     if (ctx && ctx->model) ctx->model->bias_rows_host.clear();   // a pending row map likewise
+    bool alt_on = false;   // ... and a request for alternatives, which this call refuses below
+    if (ctx && ctx->model) { alt_on = ctx->model->alt_pending; ctx->model->alt_pending = false; }
     const int32_t *dbg_script = nullptr;   // the debug library's script is for this call only
     if (ctx && ctx->model) dbg_script = ctx->model->spec_dbg_script;
     struct ScriptScope {
@@ -1224,6 +1264,7 @@ int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
     WM_TRY(entry_checks(call));
     WM_MODEL(ctx);
     WM_TRY(spec_checks(ctx, sc, call));
+    WM_REQUIRE(!alt_on, WM_ERR_STATE, "alternatives are not served by speculative decoding");
     TxCfg cfg;
     WM_TRY(tx_validate(ctx, call, budgets, &cfg));
     WM_REQUIRE(!dbg_script || (m->spec_dbg_script_new == call.max_new && m->spec_dbg_script_rows == call.B), WM_ERR_INVALID,

@@ -200,6 +200,23 @@ void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, con
     }
 }
 
+void wm_group_alt_out(const int32_t *tok, const float *lp, const int32_t *cnt, const float *ent, int n, int N, int b0, int Bg,
+                      int max_new, const int32_t *lens, int32_t *tokens, float *logprobs, int32_t *counts, float *entropy) {
+    for (int b = 0; b < Bg; ++b) {   // [gi][row][n] -> [row of the call][candidate][gi][n]
+        const size_t o = (size_t)b0 * N + b;
+        for (int i = 0; i < max_new; ++i) {
+            const bool live = i < lens[o];
+            const size_t src = (size_t)i * Bg + b, dst = o * max_new + i;
+            for (int k = 0; k < n; ++k) {
+                tokens[dst * n + k] = live ? tok[src * n + k] : -1;
+                logprobs[dst * n + k] = live ? lp[src * n + k] : 0.f;
+            }
+            if (counts) counts[dst] = live ? cnt[src] : 0;
+            if (entropy) entropy[dst] = live ? ent[src] : 0.f;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- prompt panels ----
 void wm_panel_slices(int G, int width, int T, int knob, int *C, int *w) {
     const int wd = width < 1 ? 1 : (width > WM_PANEL_MAX_WIDTH ? WM_PANEL_MAX_WIDTH : width);

@@ -95,6 +95,12 @@ void wm_group_bias_rows(const int32_t *table_of_row, const int32_t *tab_grp, int
 // or with its first eot; tokens past the end read eot, log-probs 0 -- the stopping token has its log-prob, nothing after it.
 void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, const int32_t *budgets, int32_t eot, int N, int b0,
                        int Bg, int max_new, int32_t *tokens, int32_t *lens, float *logprobs, float *no_speech);
+// The same rows' alternatives (wm_request_alternatives) from the fetched tok / lp [max_new][Bg][n] and cnt / ent [max_new][Bg],
+// by the same row map, into tokens / logprobs [rows][max_new][n] and counts / entropy [rows][max_new] (both nullable).  lens:
+// the call's, as wm_group_rows_out wrote them -- every position at or past a row's length is a pad (id -1, log-prob 0, count 0,
+// entropy 0), whatever the device left there.
+void wm_group_alt_out(const int32_t *tok, const float *lp, const int32_t *cnt, const float *ent, int n, int N, int b0, int Bg,
+                      int max_new, const int32_t *lens, int32_t *tokens, float *logprobs, int32_t *counts, float *entropy);
 
 // ---------------------------------------------------------------- speculative decoding ----
 // wm_transcribe_mel_speculative.  The decode groups of a call of B windows at draft length k: a verify
