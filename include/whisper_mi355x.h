@@ -793,6 +793,57 @@ WM_API int wm_set_sequence_bias_tables(wm_ctx *ctx, const int32_t *tokens, const
                                        int n_tables, int32_t eot);
 WM_API int wm_set_bias_rows(wm_ctx *ctx, const int32_t *table_of_row /* [n], -1 .. n_tables - 1 */, int n);
 
+/* Constrained decoding: an AUTOMATON over token ids says, position by position, which ids a row may generate -- "one of these
+ * phrases", "digits only", "`call ` followed by free text" (whisper.cpp's grammars, Hugging Face generate's
+ * prefix_allowed_tokens_fn).  A bias tilts the odds and a ban list cannot say "nothing else"; this is the hard rule.
+ *   Automaton: S states (1 <= S <= WM_MAX_CST_STATES) and E explicit edges (0 <= E <= WM_MAX_CST_EDGES) as flat arrays:
+ *     edge_beg[S + 1] (state s owns edges [edge_beg[s], edge_beg[s + 1]), E = edge_beg[S]), edge_tok[E] (strictly ascending
+ *     within a state), edge_next[E], def_next[S], accept[S] (u8), and eot.
+ *   Explicit edge (s, t) -> n: t is a text id in [0, eot).  n in [0, S): id t is allowed in state s and leads to n.  n = -1: t is
+ *     forbidden in s -- valid only where def_next[s] >= 0 ("anything but").
+ *   Default def_next[s]: -1, a text id without an explicit edge is forbidden in s; >= 0, every such id is allowed and leads
+ *     there (free-text stretches, wildcards).
+ *   Accepting: eot is allowed in state s iff accept[s] != 0.
+ *   Ids above eot (timestamps, the specials) are TRANSPARENT: the constraint never bans them and they do not move the state,
+ *     delta(s, t) = s; eot itself behaves the same way where it stands in the history as the padding of a finished row.  They stay
+ *     the business of the timestamp rules and the suppress lists, so `<|0.00|> turn left <|1.20|>` is the phrase `turn left`.
+ *   Dead state -1: reached by a text id the state forbids (possible only through an existing empty-set fallback path); it allows
+ *     eot alone and stays dead.
+ *   History: g[0 .. k), the tokens the row has generated in this call, exactly as for wm_set_repetition_rules -- the prompt is
+ *     excluded, a ragged row counts from the group's longest prompt, a beam row carries the history of the hypothesis it continues.
+ *   State of a row at a position: delta folded over g[0 .. k) from the row's start state -- a pure function of the history.
+ *   Effect: every id in [0, eot] the state does not allow is BANNED at that position, together with the no-repeat bans and the
+ *     sequence-bias bans, and a banned id is treated exactly like a suppressed one everywhere: the arg-max, the Gumbel draw, the
+ *     log-prob normaliser, the sum rule of the timestamp rules, the beam lists, the kept set of the sampling rules, the
+ *     alternatives.  The stored f32 logit is unchanged (as for a no-repeat ban), token_logprobs_out is the log-prob under the
+ *     CONSTRAINED distribution, no_speech_prob is untouched.  An empty admissible set takes the path it always took.  When
+ *     max_new or a token budget runs out before an accepting state, the output is a PREFIX of a member of the language.
+ *   wm_set_constraint(n_states = 0) switches the constraint off (the initial state; the pointers may be NULL).  Applied to every
+ *     lane and copied by later wm_clone's, as wm_set_repetition_rules.  It drops a pending row map.
+ *   Rows: wm_set_constraint_rows names the start state of every row of the NEXT transcribe call on the context, like
+ *     wm_set_bias_rows: consumed by that call whatever happens, n must equal its B, n = 0 drops a pending map.  Row b starts in
+ *     state start_of_row[b]; -1: the row is unconstrained and decodes as with the constraint off.  Every candidate of a best-of
+ *     window and every beam of a beam window takes its window's start.  With an automaton in force and no pending map every row
+ *     starts in state 0.  One automaton that holds disjoint sub-automata is therefore a grammar per request in one batched call.
+ *     WM_ERR_STATE when the context has no automaton; WM_ERR_INVALID for a start outside [-1, S).
+ *   Served: wm_transcribe_greedy (the constraint turns the extended decode on, as the repetition rules do), wm_transcribe, _mel,
+ *     _mel_ragged, _mel_best_of, _mel_beam, the wm_transcribe_windows* counterparts and the *_aligned entries.  Refused with
+ *     WM_ERR_STATE (not built): wm_transcribe_mel_speculative, wm_multi_transcribe_greedy on a device context that has an
+ *     automaton, the all-f32 debug path.  The teacher-forced calls stay raw.
+ * WM_ERR_INVALID -- and whatever was in force stays -- for: offsets that do not start at 0 or that decrease; edge tokens not
+ * strictly ascending within a state; an edge token >= eot; an edge_next or def_next outside [-1, S); an explicit -1 edge in a
+ * state whose default is -1; a STUCK state (no allowing edge, no default, not accepting); a count above its limit; eot outside
+ * [0, n_vocab).
+ * Token ids are the caller's tokenizer's: Whisper's " word" and "word" are different ids, both variants are the caller's to list.
+ * Cost: one launch per position that walks the row's history from its start state -- it grows with the
+ * history, one dependent lookup per generated text token. */
+#define WM_MAX_CST_STATES 4096      /* states of one automaton                                    */
+#define WM_MAX_CST_EDGES  65536     /* explicit edges, all states together                        */
+WM_API int wm_set_constraint(wm_ctx *ctx, const int32_t *edge_beg /* [n_states + 1] */, const int32_t *edge_tok /* [E] */,
+                             const int32_t *edge_next /* [E] */, const int32_t *def_next /* [n_states] */,
+                             const uint8_t *accept /* [n_states] */, int n_states, int32_t eot);
+WM_API int wm_set_constraint_rows(wm_ctx *ctx, const int32_t *start_of_row /* [n], -1 .. n_states - 1 */, int n);
+
 /* Per-chunk token budgets for the NEXT wm_transcribe_greedy call on this context (consumed by it; n must equal that
  * call's B): chunk i generates at most budgets[i] tokens (clamped to max_new), lens_out[i] <=
  * budgets[i].  A chunk that has reached its budget -- like one that has emitted `eot` -- LEAVES the decode: its caches are

@@ -218,6 +218,21 @@ WM_API int wmdbg_seqbias_rows_state(wm_ctx *ctx, const int32_t *seq, int B, int 
                                     const uint8_t *boost_prefixes, const int32_t *table_offsets, int n_tables, int32_t eot,
                                     const int32_t *table_of_row, const uint32_t *ban_in, uint32_t *hit_out, uint32_t *ban_out,
                                     int32_t *cnt_out, int32_t *id_out, float *total_out, int32_t *woff_out);
+/* The state kernel of the constraint alone (constraint.hip): seq as for wmdbg_repeat_state; the automaton as for
+ * wm_set_constraint with V as the vocabulary (WM_ERR_INVALID where that call answers it; n_states >= 1); starts i32 [B] in
+ * [-1, n_states); ban_in u32 [B][words], words = (pad16(V) + 31) / 32: the ban words as given -- NO wm_repeat_state launch, so what
+ * the kernel leaves alone shows.  Out: ban_out u32 [B][words]; state_out i32 [B] the state each row reached (-1: dead), pre-filled
+ * with 0xfe bytes (0xff bytes would read as the dead state), so a row the kernel does not write reads 0xfefefefe. */
+WM_API int wmdbg_constraint_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V,
+                                  const int32_t *edge_beg, const int32_t *edge_tok, const int32_t *edge_next, const int32_t *def_next,
+                                  const uint8_t *accept, int n_states, int32_t eot, const int32_t *starts, const uint32_t *ban_in,
+                                  uint32_t *ban_out, int32_t *state_out);
+/* wmdbg_decode_close_rep with empty rules (1.0, 0) and the constraint on (wm_set_constraint: the automaton arguments are that
+ * call's, eot its eot -- the rules' eot stays io->eot; starts i32 [B]): wm_repeat_state, wm_constraint_state behind it, then the
+ * DE_LOGITS_XR launch and the close.  WM_ERR_INVALID for an automaton wm_set_constraint would refuse. */
+WM_API int wmdbg_decode_close_cst(wm_ctx *ctx, wmdbg_step *io, const int32_t *edge_beg, const int32_t *edge_tok,
+                                  const int32_t *edge_next, const int32_t *def_next, const uint8_t *accept, int n_states, int32_t eot,
+                                  const int32_t *starts);
 /* For callers that restate the struct (ctypes): out4 = sizeof(wmdbg_step) and the offsets of seed, logits and
  * stats_tail_nonzero (host only). */
 WM_API int wmdbg_step_layout(int32_t *out4);

@@ -498,11 +498,128 @@ def sampling_rules_args(top_k=None, top_p=None, min_p=None):
     return int(k), p, m
 
 
+MAX_CST_STATES, MAX_CST_EDGES = 4096, 65536   # WM_MAX_CST_STATES, WM_MAX_CST_EDGES
+
+
+class Constraint:
+    """A token automaton for Context.set_constraint (wm_set_constraint), as that call's flat arrays: edge_beg i32 [S + 1],
+    edge_tok / edge_next i32 [E] (tokens strictly ascending within a state; next -1: forbidden), def_next i32 [S] (-1: a text id
+    without an explicit edge is forbidden), accept u8 [S] (eot is allowed).  Built by constraint_from_choices / constraint_join,
+    or from the arrays of any grammar compiler.  The library validates it; the ids are the caller's tokenizer's."""
+
+    def __init__(self, edge_beg, edge_tok, edge_next, def_next, accept):
+        self.edge_beg = np.ascontiguousarray(edge_beg, dtype=np.int32).reshape(-1)
+        self.edge_tok = np.ascontiguousarray(edge_tok, dtype=np.int32).reshape(-1)
+        self.edge_next = np.ascontiguousarray(edge_next, dtype=np.int32).reshape(-1)
+        self.def_next = np.ascontiguousarray(def_next, dtype=np.int32).reshape(-1)
+        self.accept = np.ascontiguousarray(accept, dtype=np.uint8).reshape(-1)
+        S = self.def_next.size
+        if S < 1 or self.edge_beg.size != S + 1 or self.accept.size != S or self.edge_tok.size != self.edge_next.size \
+                or int(self.edge_beg[-1]) != self.edge_tok.size:
+            raise ValueError("Constraint: edge_beg [S + 1], edge_tok / edge_next [edge_beg[S]], def_next / accept [S], S >= 1")
+
+    @property
+    def n_states(self):
+        return int(self.def_next.size)
+
+    @property
+    def n_edges(self):
+        return int(self.edge_tok.size)
+
+
+def constraint_from_choices(choices, repeat=False):
+    """The automaton of a list of token sequences (a trie from state 0): exactly those sequences are allowed, eot where one ends.
+    repeat=True: where a sequence ends the next token may also start another one (the ends lead back to the root's edges) --
+    digit strings, several commands in a row; the empty output is then allowed too.  A sequence that is a prefix of another is
+    fine.  ValueError for an empty list, an empty sequence, a negative id or a trie above MAX_CST_STATES / MAX_CST_EDGES."""
+    seqs = [tuple(int(t) for t in c) for c in choices]
+    if not seqs or any(len(q) == 0 or min(q) < 0 for q in seqs):
+        raise ValueError("constraint_from_choices: a non-empty list of non-empty sequences of ids >= 0")
+    kids, accept = [{}], [bool(repeat)]
+    for q in seqs:
+        s = 0
+        for i, t in enumerate(q):
+            if repeat and i == len(q) - 1:   # the end of a phrase IS the root: it accepts and continues with any first token
+                if kids[s].get(t, 0) != 0:
+                    raise ValueError("constraint_from_choices: with repeat, a sequence may not be a prefix of another")
+                kids[s][t] = 0
+                break
+            if kids[s].get(t) == 0 and repeat:
+                raise ValueError("constraint_from_choices: with repeat, a sequence may not be a prefix of another")
+            if t not in kids[s]:
+                kids[s][t] = len(kids)
+                kids.append({})
+                accept.append(False)
+            s = kids[s][t]
+        else:
+            accept[s] = True
+    # the leaves -- accepting, nothing behind them -- are ONE state: 4096 one-token phrases are two states, not 4097
+    keep, num, leaf = [], {}, None       # the states that stay, old index -> new index, the shared leaf's new index
+    for i, k in enumerate(kids):
+        if i > 0 and not k:
+            if leaf is None:
+                leaf = len(keep)
+                keep.append(i)
+            num[i] = leaf
+        else:
+            num[i] = len(keep)
+            keep.append(i)
+    if len(keep) > MAX_CST_STATES or sum(len(k) for k in kids) > MAX_CST_EDGES:
+        raise ValueError("constraint_from_choices: more than %d states or %d edges" % (MAX_CST_STATES, MAX_CST_EDGES))
+    beg, tok, nxt = [0], [], []
+    for i in keep:
+        for t in sorted(kids[i]):
+            tok.append(t)
+            nxt.append(num[kids[i][t]])
+        beg.append(len(tok))
+    return Constraint(beg, tok, nxt, [-1] * len(keep), [accept[i] for i in keep])
+
+
+def constraint_join(automata):
+    """Disjoint automata as ONE (states and edges concatenated, targets shifted) and the start state of each: a grammar per
+    request in one batched call -- Context.set_constraint(joined), then Context.set_constraint_rows([starts[i] ...]) per call.
+    -> (Constraint, starts)."""
+    automata = list(automata)
+    if not automata or not all(isinstance(a, Constraint) for a in automata):
+        raise ValueError("constraint_join: a non-empty list of Constraint")
+    beg, tok, nxt, dn, acc, starts = [np.zeros(1, np.int32)], [], [], [], [], []
+    s0 = e0 = 0
+    for a in automata:
+        starts.append(s0)
+        beg.append(a.edge_beg[1:] + e0)
+        tok.append(a.edge_tok)
+        nxt.append(np.where(a.edge_next >= 0, a.edge_next + s0, -1))
+        dn.append(np.where(a.def_next >= 0, a.def_next + s0, -1))
+        acc.append(a.accept)
+        s0 += a.n_states
+        e0 += a.n_edges
+    if s0 > MAX_CST_STATES or e0 > MAX_CST_EDGES:
+        raise ValueError("constraint_join: more than %d states or %d edges" % (MAX_CST_STATES, MAX_CST_EDGES))
+    return Constraint(np.concatenate(beg), np.concatenate(tok), np.concatenate(nxt), np.concatenate(dn), np.concatenate(acc)), starts
+
+
+def constraint_args(constraint, constraint_rows=None, rows=None):
+    """constraint / constraint_rows of transcribe_with_fallback and transcribe_long, checked before any library call: None or a
+    Constraint; the rows None or one start state in [-1, n_states) per row (`rows`, where known).  -> the rows as a list or None."""
+    if constraint is None:
+        if constraint_rows is not None:
+            raise ValueError("constraint_rows needs a constraint")
+        return None
+    if not isinstance(constraint, Constraint):
+        raise ValueError("constraint: a Constraint (constraint_from_choices, constraint_join) or None")
+    if constraint_rows is None:
+        return None
+    out = [-1 if r is None else int(r) for r in constraint_rows]
+    if (rows is not None and len(out) != rows) or any(r < -1 or r >= constraint.n_states for r in out):
+        raise ValueError("constraint_rows: one start state in [-1, n_states) per row")
+    return out
+
+
 def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                              compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6,
                              vocab=None, seed=0, no_speech_token=-1, sot_index=0, vocab_size=None, best_of=None,
                              length_penalty=None, beam_size=None, patience=None, top_k=None, top_p=None, min_p=None,
-                             alternatives=None):
+                             alternatives=None, constraint=None, constraint_rows=None):
     """openai-whisper's decode_with_fallback, per chunk, over ctx.transcribe.
 
     Temperature step k decodes, as ONE batched call, the chunks that still need fallback (step 0: all of them) at
@@ -531,16 +648,25 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     and the result gains alt_tokens / alt_logprobs [B][max_new][n], alt_counts / entropy [B][max_new] of each chunk's kept
     attempt.  ValueError before any library call for a value out of range or together with beam_size.
 
+    constraint (None: the context's constraint is not touched; a Constraint): set on the context for the run
+    (Context.set_constraint, eot is this call's eot) and cleared on leaving, also on an exception.  constraint_rows (None: every
+    chunk starts in state 0): the start state of every chunk, -1 for an unconstrained one; Context.set_constraint_rows goes in
+    front of every decode call of the loop with the starts of exactly that call's chunks.  ValueError before any library call
+    for a bad value (constraint_args).
+
     Returns a dict of per-chunk arrays (tokens, lens, logprobs, sum_logprob, avg_logprob, no_speech_prob,
     compression_ratio, temperature, seed, needs_fallback) and `steps`: [(temperature, seed, chunk indices)] per call."""
     pcm = np.asarray(pcm)
     beam_max_candidates(beam_size, patience)
     sampling = sampling_rules_args(top_k, top_p, min_p)
+    cst_rows = constraint_args(constraint, constraint_rows, pcm.shape[0])
     alt_kw = {} if alternatives_arg(alternatives, beam_size if beam_size is not None else patience) is None \
         else dict(alternatives=int(alternatives))
 
     def decode(todo, t, sd):
         extra = fallback_step_extra(t, best_of, length_penalty, beam_size, patience)
+        if cst_rows is not None:
+            ctx.set_constraint_rows([cst_rows[int(i)] for i in todo])
         if extra:
             n_mels = int(ctx.dims["n_mels"])
             mel = ctx.logmel(pcm[todo], n_mels=n_mels)
@@ -552,12 +678,18 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
     if sampling is not None:
         ctx.set_sampling_rules(*sampling)
     try:
+        if constraint is not None:
+            ctx.set_constraint(constraint, eot=eot)
         return fallback_decode(decode, pcm.shape[0], int(ctx.dims["n_vocab"]) if vocab_size is None else vocab_size, max_new,
                                eot, temperatures, compression_ratio_threshold, logprob_threshold, no_speech_threshold, vocab,
                                seed)
     finally:
-        if sampling is not None:
-            ctx.set_sampling_rules()
+        try:
+            if constraint is not None:
+                ctx.set_constraint(None)
+        finally:
+            if sampling is not None:
+                ctx.set_sampling_rules()
 
 
 def fallback_decode(decode, B, vocab_size, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
@@ -1420,7 +1552,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
                     boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None, recording_bias=None,
-                    top_k=None, top_p=None, min_p=None, alternatives=None):
+                    top_k=None, top_p=None, min_p=None, alternatives=None, constraint=None):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1589,6 +1721,13 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        cleared as empty loses both with its tokens.  ValueError before any library call for a value out of range and together
        with beam_size or draft (a beam's alternatives need its ancestry; a speculative step verifies the greedy choice alone).
        With None the function makes exactly the calls it made before the argument existed.
+    25. constraint (None: off; a Constraint of constraint_from_choices / constraint_join or of the caller's own arrays): the
+       automaton of Context.set_constraint (wm_set_constraint, eot is this call's eot) is set on the context behind the sampling
+       rules, held for the run and cleared on leaving it, also when a decode raises.  Every window of every recording starts in
+       state 0: the text ids of a window form a member of the language (or a prefix of one where the window's tokens run out),
+       the timestamps around and between them are the timestamp rules' business.  ValueError before any library call for
+       anything but a Constraint and together with draft.  With None the function makes exactly the calls it made before the
+       argument existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1602,6 +1741,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     R = len(recordings)
     o.early(R)
     sampling = sampling_rules_args(top_k, top_p, min_p)   # 23. (None: off)
+    constraint_args(constraint)   # 25. (None: off)
+    if constraint is not None and draft is not None:
+        raise ValueError("draft (speculative decoding) cannot be combined with a constraint")
     bias_table = long_bias_table(sequence_bias, bad_words, boost_phrases, phrase_boost)   # 17. (None: off)
     o.rec_tables = None   # 22.: the table of every recording (None: off)
     if recording_bias is not None:
@@ -1632,6 +1774,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             ctx.set_sequence_bias_tables(rec_tables, rec_boosts, eot=eot)
         if sampling is not None:   # 23.
             ctx.set_sampling_rules(*sampling)
+        if constraint is not None:   # 25.
+            ctx.set_constraint(constraint, eot=eot)
         langs = _long_languages(o, d_mel, mel_offs, T)
         o.prompt_head()
         units = _long_units(o, out, langs, d_mel, mel_offs, T)
@@ -1690,8 +1834,12 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             ctx.dev_free(d_mel)
         finally:
             try:
-                if sampling is not None:
-                    ctx.set_sampling_rules()
+                try:
+                    if constraint is not None:
+                        ctx.set_constraint(None)
+                finally:
+                    if sampling is not None:
+                        ctx.set_sampling_rules()
             finally:
                 try:
                     if bias_table is not None:
@@ -2167,6 +2315,35 @@ class Context:
         fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         fn.restype = ctypes.c_int
         a = np.ascontiguousarray([-1 if r is None else int(r) for r in rows], dtype=np.int32)
+        _check(self.lib, fn(self.handle, _ptr(a) if a.size else None, int(a.size)))
+
+    def set_constraint(self, automaton=None, eot=None):
+        """The constraint of every transcribe call on this context (wm_set_constraint): a Constraint -- a token automaton that
+        says which text ids (< eot) and whether eot a row may generate next, from the tokens it has generated in the call; ids
+        above eot (timestamps, specials) are never banned and do not move the state.  A banned id is treated like a suppressed
+        one everywhere; log-probs are those of the constrained distribution.  eot defaults to the vocabulary's last id.  Every
+        row starts in state 0 unless set_constraint_rows says otherwise.  None switches the constraint off."""
+        fn = self.lib.wm_set_constraint
+        fn.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int32]
+        fn.restype = ctypes.c_int
+        if automaton is None:
+            _check(self.lib, fn(self.handle, None, None, None, None, None, 0, 0))
+            return
+        if not isinstance(automaton, Constraint):
+            raise ValueError("set_constraint: a Constraint (constraint_from_choices, constraint_join) or None")
+        eot = int(self.dims["n_vocab"]) - 1 if eot is None else int(eot)
+        a = automaton
+        _check(self.lib, fn(self.handle, _ptr(a.edge_beg), _ptr(a.edge_tok) if a.n_edges else None,
+                            _ptr(a.edge_next) if a.n_edges else None, _ptr(a.def_next), _ptr(a.accept), a.n_states, eot))
+
+    def set_constraint_rows(self, starts):
+        """The start state of every row of the NEXT transcribe call (wm_set_constraint_rows; len == its B; consumed by it): a
+        state of the automaton of set_constraint, or -1 (None reads as -1) for an unconstrained row.  A best-of window's
+        candidates and a beam window's beams take their window's start.  [] drops a pending map."""
+        fn = self.lib.wm_set_constraint_rows
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        fn.restype = ctypes.c_int
+        a = np.ascontiguousarray([-1 if r is None else int(r) for r in starts], dtype=np.int32)
         _check(self.lib, fn(self.handle, _ptr(a) if a.size else None, int(a.size)))
 
     def set_lanes(self, n):

@@ -2140,6 +2140,24 @@ static int stage_seqbias(DevPool &pool, hipStream_t s, const WmSbTable &t, int B
     return WM_OK;
 }
 
+// A constraint automaton (wm_cst_build) in device memory as the product lays it out, with the rows' starts.
+static int stage_constraint(DevPool &pool, hipStream_t s, const WmCstTable &t, const int32_t *starts, int B, WmCstPar *par_host, WmCstDev *out) {
+    const int ns = t.n_states(), ne = t.n_edges();
+    WmCstDev d;
+    memset(&d, 0, sizeof(d));
+    par_host->n_states = ns; par_host->n_edges = ne; par_host->eot = t.eot;
+    WM_TRY(pool.get(&d.par, par_host, sizeof(WmCstPar), s));
+    WM_TRY(pool.get(&d.edge_beg, t.edge_beg.data(), (size_t)(ns + 1) * 4, s));
+    WM_TRY(pool.get(&d.edge_tok, ne ? t.edge_tok.data() : nullptr, std::max<size_t>(ne, 1) * 4, s));
+    WM_TRY(pool.get(&d.edge_next, ne ? t.edge_next.data() : nullptr, std::max<size_t>(ne, 1) * 4, s));
+    WM_TRY(pool.get(&d.def_next, t.def_next.data(), (size_t)ns * 4, s));
+    WM_TRY(pool.get(&d.accept, t.accept.data(), (size_t)ns * 4, s));
+    WM_TRY(pool.get(&d.hash, t.hash.data(), t.hash.size() * 4, s));
+    WM_TRY(pool.get(&d.start, starts, (size_t)B * 4, s));
+    *out = d;
+    return WM_OK;
+}
+
 // wmdbg_decode_close_shared: where the beam and accept closes of the step's partials go (host, [B] each)
 struct CloseShared {
     int w;
@@ -2204,8 +2222,10 @@ static int shared_closes_run(wm_ctx *ctx, DevPool &pool, const wmdbg_step *io, c
 // sbt (with rep): the sequence bias as well -- wm_seqbias_state behind it and a DE_LOGITS_XB launch, also for an empty table
 // sh: the beam and accept closes on the same partials, in front of the arg-max close (wmdbg_decode_close_shared)
 // trunc: the sampling rules are on -- wm_sample_truncate between the logits launch and the close (a sampling X-mode step)
+// cst (with rep): the constraint as well -- wm_constraint_state behind the other state launches, with the rows' starts
 static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram, const WmSbTable *sbt = nullptr,
-                            const CloseShared *sh = nullptr, const WmSampPar *trunc = nullptr) {
+                            const CloseShared *sh = nullptr, const WmSampPar *trunc = nullptr, const WmCstTable *cst = nullptr,
+                            const int32_t *cst_starts = nullptr) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
     if (rep)
@@ -2262,6 +2282,7 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     xp.sot_pos = io->sot_pos; xp.ns_tok = io->ns_tok; xp.chunk0 = io->chunk0; xp.n_prompt = n_prompt; xp.n_cand = 1;
     WmRepPar rpar;
     WmSbPar sbpar;
+    WmCstPar cpar;
     const int zero = 0;
     std::vector<float> lg((size_t)B * vpad), lp((size_t)n_ctx * B), stn(st_words);
     DevPool pool;
@@ -2364,6 +2385,11 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
             a.epi = DE_LOGITS_XB;
             a.sb = sd.e;
             WM_TRY(wm_seqbias_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, sd, a.rep.ban, mw));
+        }
+        if (cst) {
+            WmCstDev cd;
+            WM_TRY(stage_constraint(pool, s, *cst, cst_starts, B, &cpar, &cd));
+            WM_TRY(wm_constraint_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, cd, a.rep.ban, mw, nullptr));
         }
     }
     WM_TRY(wm_dec_gemv(ctx, a));
@@ -2497,6 +2523,50 @@ extern "C" int wmdbg_seqbias_state(wm_ctx *ctx, const int32_t *seq, int B, int n
     WM_HIP(hipMemcpyAsync(id_out, sd.e.lid, (size_t)B * cap * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(total_out, sd.e.ltot, (size_t)B * cap * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(woff_out, sd.e.woff, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
+}
+
+extern "C" int wmdbg_decode_close_cst(wm_ctx *ctx, wmdbg_step *io, const int32_t *edge_beg, const int32_t *edge_tok,
+                                      const int32_t *edge_next, const int32_t *def_next, const uint8_t *accept, int n_states, int32_t eot,
+                                      const int32_t *starts) {
+    WM_REQUIRE(io && starts && n_states >= 1, WM_ERR_INVALID, "wmdbg_decode_close_cst: null / no automaton");
+    WmCstTable t;
+    WM_TRY(wm_cst_build(edge_beg, edge_tok, edge_next, def_next, accept, n_states, eot, io->V, &t));
+    for (int b = 0; b < io->B && b < WM_DEC_MAXB; ++b)
+        WM_REQUIRE(starts[b] >= -1 && starts[b] < n_states, WM_ERR_INVALID, "wmdbg_decode_close_cst: start of row %d", b);
+    return decode_close_run(ctx, io, true, 1.f, 0, nullptr, nullptr, nullptr, &t, starts);
+}
+
+extern "C" int wmdbg_constraint_state(wm_ctx *ctx, const int32_t *seq, int B, int n_ctx, int pos, int n_prompt, int V,
+                                      const int32_t *edge_beg, const int32_t *edge_tok, const int32_t *edge_next, const int32_t *def_next,
+                                      const uint8_t *accept, int n_states, int32_t eot, const int32_t *starts, const uint32_t *ban_in,
+                                      uint32_t *ban_out, int32_t *state_out) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(seq && starts && ban_in && ban_out && state_out, WM_ERR_INVALID, "wmdbg_constraint_state: null pointer");
+    WM_REQUIRE(B >= 1 && B <= WM_DEC_MAXB && V >= 16 && n_ctx >= 1 && n_ctx <= 448 && pos >= 0 && pos < n_ctx && n_prompt >= 0 &&
+                   n_prompt <= n_ctx && n_states >= 1,
+               WM_ERR_INVALID, "wmdbg_constraint_state: bad geometry");
+    WmCstTable t;
+    WM_TRY(wm_cst_build(edge_beg, edge_tok, edge_next, def_next, accept, n_states, eot, V, &t));
+    for (int b = 0; b < B; ++b)
+        WM_REQUIRE(starts[b] >= -1 && starts[b] < n_states, WM_ERR_INVALID, "wmdbg_constraint_state: start of row %d", b);
+    const int words = ((V + 15) / 16 * 16 + 31) / 32;
+    WmCstPar cpar;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    const int *dseq, *dpos;
+    unsigned *dban;
+    int *dstate;
+    WM_TRY(pool.get(&dseq, seq, (size_t)n_ctx * B * 4, s));
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&dban, ban_in, (size_t)B * words * 4, s));
+    WM_TRY(pool.get(&dstate, nullptr, (size_t)B * 4, s, 0xfe));   // (0xff bytes would read -1, the dead state)
+    WmCstDev cd;
+    WM_TRY(stage_constraint(pool, s, t, starts, B, &cpar, &cd));
+    WM_TRY(wm_constraint_state(ctx, dseq, dpos, B, n_prompt, n_ctx, V, cd, dban, words, dstate));
+    WM_HIP(hipMemcpyAsync(ban_out, dban, (size_t)B * words * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(state_out, dstate, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipStreamSynchronize(s));
     return WM_OK;
 }

@@ -139,6 +139,37 @@ static int alloc_seqbias_pool(WmModel *m, hipStream_t s) {
     return WM_OK;
 }
 
+// the constraint's tables at FULL capacity (WM_MAX_CST_STATES states, WM_MAX_CST_EDGES edges, the hash) and the rows' starts, once
+static int alloc_constraint_state(WmModel *m, hipStream_t s) {
+    int *edge_beg, *edge_tok, *edge_next, *def_next, *accept, *hash, *start;
+    WM_TRY(dalloc_t(m, &edge_beg, (size_t)WM_MAX_CST_STATES + 1, s));
+    WM_TRY(dalloc_t(m, &edge_tok, (size_t)WM_MAX_CST_EDGES, s));
+    WM_TRY(dalloc_t(m, &edge_next, (size_t)WM_MAX_CST_EDGES, s));
+    WM_TRY(dalloc_t(m, &def_next, (size_t)WM_MAX_CST_STATES, s));
+    WM_TRY(dalloc_t(m, &accept, (size_t)WM_MAX_CST_STATES, s));
+    WM_TRY(dalloc_t(m, &hash, (size_t)2 * WM_CST_HASH_SLOTS, s));
+    WM_TRY(dalloc_t(m, &start, (size_t)WM_DEC_MAXB, s));
+    WmCstPar *par;
+    WM_TRY(dalloc(m, (void **)&par, sizeof(WmCstPar), s));
+    m->dcst.edge_beg = edge_beg; m->dcst.edge_tok = edge_tok; m->dcst.edge_next = edge_next; m->dcst.def_next = def_next;
+    m->dcst.accept = accept; m->dcst.hash = hash; m->dcst.start = start;
+    m->dcst.par = par;   // last: non-null = allocated
+    return WM_OK;
+}
+
+// an automaton's arrays (host or another context's device tables) -> this context's tables
+static int upload_constraint(WmModel *m, const WmCstDev &from, int ns, int ne, hipMemcpyKind kind, hipStream_t s) {
+    WM_HIP(hipMemcpyAsync((void *)m->dcst.edge_beg, from.edge_beg, (size_t)(ns + 1) * 4, kind, s));
+    if (ne) {
+        WM_HIP(hipMemcpyAsync((void *)m->dcst.edge_tok, from.edge_tok, (size_t)ne * 4, kind, s));
+        WM_HIP(hipMemcpyAsync((void *)m->dcst.edge_next, from.edge_next, (size_t)ne * 4, kind, s));
+    }
+    WM_HIP(hipMemcpyAsync((void *)m->dcst.def_next, from.def_next, (size_t)ns * 4, kind, s));
+    WM_HIP(hipMemcpyAsync((void *)m->dcst.accept, from.accept, (size_t)ns * 4, kind, s));
+    WM_HIP(hipMemcpyAsync((void *)m->dcst.hash, from.hash, (size_t)2 * WM_CST_HASH_SLOTS * 4, kind, s));
+    return WM_OK;
+}
+
 WmStopDev wm_model_stop_dev(const WmModel *m, const WmDecodeMode &mode) {
     WmStopDev t;
     memset(&t, 0, sizeof(t));
@@ -288,6 +319,33 @@ int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t) {
     // exclusive with the row tables: a table replaces them, the empty table clears both
     m->sbt_on = false; m->sbt_groups = m->sbt_entries = 0; m->sbt_tab_grp.clear();
     m->bias_rows_host.clear();
+    return WM_OK;
+}
+
+int wm_model_set_constraint(wm_ctx *ctx, const WmCstTable &t) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m, WM_ERR_STATE, "context has no model");
+    const int ns = t.n_states(), ne = t.n_edges();
+    WM_REQUIRE(ns <= WM_MAX_CST_STATES && ne <= WM_MAX_CST_EDGES && (int)t.edge_beg.size() == (ns ? ns + 1 : 0) && (int)t.edge_next.size() == ne &&
+                   (int)t.accept.size() == ns && t.hash.size() == (ns ? (size_t)2 * WM_CST_HASH_SLOTS : 0),
+               WM_ERR_INVALID, "constraint: malformed table");
+    if (ns) {
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "the constraint is not supported by the all-f32 precision path");
+        WM_REQUIRE(t.eot >= 0 && t.eot < m->dims.n_vocab, WM_ERR_INVALID, "constraint: eot %d outside [0, %d)", t.eot, m->dims.n_vocab);
+        WM_REQUIRE(((size_t)2 * ((m->vpad + 31) / 32) + m->dims.n_text_ctx + 1) * 4 <= 64 * 1024, WM_ERR_INVALID,
+                   "constraint: a vocabulary of %d ids does not fit the state kernels' LDS", m->dims.n_vocab);
+        // the ban words are wm_repeat_state's: a group with the constraint on runs it too (with (1.0, 0) when the repetition rules are off)
+        if (!m->drep_par) WM_TRY(alloc_repetition_state(m, ctx->stream));
+        if (!m->dcst.par) WM_TRY(alloc_constraint_state(m, ctx->stream));
+        WmCstDev from;
+        memset(&from, 0, sizeof(from));
+        from.edge_beg = t.edge_beg.data(); from.edge_tok = t.edge_tok.data(); from.edge_next = t.edge_next.data();
+        from.def_next = t.def_next.data(); from.accept = t.accept.data(); from.hash = t.hash.data();
+        WM_TRY(upload_constraint(m, from, ns, ne, hipMemcpyHostToDevice, ctx->stream));
+        WM_HIP(hipStreamSynchronize(ctx->stream));   // (the table's vectors are the caller's)
+    }
+    m->cst_on = ns > 0; m->cst_states = ns; m->cst_edges = ne; m->cst_eot = ns ? t.eot : 0;
+    m->cst_rows_host.clear();
     return WM_OK;
 }
 
@@ -612,7 +670,12 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->prompt_panel = pm->prompt_panel;
     m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
     m->samp_k = pm->samp_k; m->samp_p = pm->samp_p; m->samp_minp = pm->samp_minp;
-    if (m->rep_on || pm->sb_on || pm->sbt_on) WM_TRY(alloc_repetition_state(m, child->stream));
+    if (m->rep_on || pm->sb_on || pm->sbt_on || pm->cst_on) WM_TRY(alloc_repetition_state(m, child->stream));
+    if (pm->cst_on) {   // the parent's automaton
+        WM_TRY(alloc_constraint_state(m, child->stream));
+        WM_TRY(upload_constraint(m, pm->dcst, pm->cst_states, pm->cst_edges, hipMemcpyDeviceToDevice, child->stream));
+        m->cst_on = true; m->cst_states = pm->cst_states; m->cst_edges = pm->cst_edges; m->cst_eot = pm->cst_eot;
+    }
     if (pm->sb_on) {   // the parent's device table, as the suppress bitmaps above
         WM_TRY(alloc_seqbias_state(m, child->stream));
         const size_t ng = (size_t)pm->sb_groups, ne = (size_t)pm->sb_entries;
@@ -1092,6 +1155,10 @@ static int decode_step_impl(wm_ctx *ctx, int B, bool want_logits, int arg_first,
             else
                 WM_TRY(wm_seqbias_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, sb, a.rep.ban, a.rep.words));
         }
+        if (mode.cst) {   // constraint: the ids the rows' automaton states do not allow, OR-ed into the same ban words
+            WM_REQUIRE(mode.rep && m->dcst.par, WM_ERR_STATE, "decode step: the constraint needs the repetition-rule state and its tables");
+            WM_TRY(wm_constraint_state(ctx, m->dseq, m->dpos, B, n_prompt, D.n_text_ctx, D.n_vocab, m->dcst, a.rep.ban, a.rep.words, nullptr));
+        }
         WM_TRY(wm_dec_gemv(ctx, a));
     }
     return WM_OK;
@@ -1197,7 +1264,7 @@ int wm_model_prompt_prefill(wm_ctx *ctx, int G, int P0, const WmDecodeMode &mode
     WM_REQUIRE(mode.n_cand <= 1 && !mode.beam, WM_ERR_STATE, "prompt prefill: a plain decode group");
     WmDecodeMode pm = mode;
     pm.stop = false; pm.budget = false; pm.stop_eot = -1; pm.acap = false; pm.acap_base = pm.acap_Tq = pm.acap_J = 0; pm.acap_q = nullptr;
-    pm.rep = false; pm.sb = false; pm.sbt = false; pm.mask = false; pm.ts = false; pm.x = false;
+    pm.rep = false; pm.sb = false; pm.sbt = false; pm.cst = false; pm.mask = false; pm.ts = false; pm.x = false;
     const int *off0 = mode.off ? m->doff : nullptr;
     const WmEmbedDev e = wm_model_embed_dev(m);
     const int T = m->dims.n_text_ctx;

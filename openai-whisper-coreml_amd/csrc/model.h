@@ -200,6 +200,44 @@ struct WmSbPool {
 int wm_sb_expand_tables(const int32_t *tokens, const int32_t *seq_offsets, const float *bias, const uint8_t *boost_prefixes,
                         const int32_t *table_offsets, int n_tables, int n_seq, int32_t eot, int n_vocab, WmSbPool *out);
 
+// The constraint (wm_set_constraint; constraint.hip): an automaton over token ids that says which text ids
+// and whether `eot` a row may generate next.  State s allows text id t < eot iff an explicit edge (s, t) has a target >= 0, or no
+// explicit edge exists and def_next[s] >= 0; it allows eot iff accept[s].  Ids above eot are never banned and do not move the
+// state, nor does eot in the history (the padding of a finished row); a forbidden text id in the history leads to the dead state
+// -1, which allows eot alone.  wm_constraint_state REBUILDS a row's state from its generated history g[0 .. k) in front of every
+// logits launch, behind wm_repeat_state (and wm_seqbias_state), and ORs the ids of [0, eot] the state does not allow into the ban
+// words wm_repeat_state has just rebuilt: everything that tests a ban bit treats them as suppressed.  The walk looks an edge up
+// in an open-addressing hash of (state, token) built on the host: one 8-byte load per probe, the table at most half full.
+struct WmCstPar {
+    int n_states, n_edges, eot;
+};
+constexpr int WM_CST_TOK_BITS = 20;                          // key = state << 20 | token: eot <= 2^20, states <= 2^12
+constexpr int WM_CST_HASH_BITS = 17;                         // 2 * WM_MAX_CST_EDGES slots
+constexpr int WM_CST_HASH_SLOTS = 1 << WM_CST_HASH_BITS;
+static_assert(WM_CST_HASH_SLOTS >= 2 * WM_MAX_CST_EDGES && WM_MAX_CST_STATES <= (1 << (32 - WM_CST_TOK_BITS)), "constraint hash geometry");
+__host__ __device__ inline unsigned wm_cst_key(int state, int tok) { return (unsigned)state << WM_CST_TOK_BITS | (unsigned)tok; }
+__host__ __device__ inline unsigned wm_cst_slot(unsigned key) { return (key * 0x9E3779B1u) >> (32 - WM_CST_HASH_BITS); }
+struct WmCstDev {
+    const WmCstPar *par;    // null: the constraint is off
+    const int *edge_beg;    // [WM_MAX_CST_STATES + 1] state s = edges [edge_beg[s], edge_beg[s + 1])
+    const int *edge_tok;    // [WM_MAX_CST_EDGES] ascending within a state
+    const int *edge_next;   // [WM_MAX_CST_EDGES] target state, or -1: forbidden
+    const int *def_next;    // [WM_MAX_CST_STATES] target of a text id without an explicit edge, or -1
+    const int *accept;      // [WM_MAX_CST_STATES] 0 / 1
+    const int *hash;        // [WM_CST_HASH_SLOTS][2] (key, target); key -1: empty.  Linear probing from wm_cst_slot(key)
+    const int *start;       // [rows] start state of each row; -1: the row is unconstrained
+};
+// The checked automaton on the host with its hash (wm_cst_build: validation and packing).  n_states == 0: off.
+struct WmCstTable {
+    std::vector<int32_t> edge_beg, edge_tok, edge_next, def_next, accept, hash;
+    int32_t eot = 0;
+    int n_states() const { return (int)def_next.size(); }
+    int n_edges() const { return (int)edge_tok.size(); }
+};
+// WM_OK, or WM_ERR_INVALID with the message set; n_states = 0 gives the empty table.  Pure host code (constraint_table.cpp).
+int wm_cst_build(const int32_t *edge_beg, const int32_t *edge_tok, const int32_t *edge_next, const int32_t *def_next,
+                 const uint8_t *accept, int n_states, int32_t eot, int n_vocab, WmCstTable *out);
+
 // Early-stop state of a decode group (device view; done == null: off).  A row is DONE once it has emitted `eot`
 // (eot >= 0) or produced budget[b] tokens (budget != null); from then on its tokens are `pad_tok`, it is dropped from
 // the compact live list the attention kernels walk, and when the list is empty the host stops launching positions.
@@ -322,6 +360,10 @@ struct WmDecodeMode {
     // Row tables (wm_set_sequence_bias_tables): the state kernel is wm_seqbias_rows_state over the pool and the group's per-row
     // group ranges instead of wm_seqbias_state over the one table.  Implies sb and rep; the epilogue is the same DE_LOGITS_XB.
     bool sbt = false;
+    // The constraint applies (wm_set_constraint, WmCstDev): wm_constraint_state behind wm_repeat_state (and the sequence-bias
+    // launch) ORs the ids the rows' automaton states do not allow into the ban words.  Implies rep and x -- the bitmaps are
+    // wm_repeat_state's, rebuilt with the rules (1.0, 0) when the repetition rules are off; the epilogue is whatever rep / sb choose.
+    bool cst = false;
     // The sampling rules apply (wm_set_sampling_rules on a call with temperature > 0): the logits launch stores the f32 row and
     // wm_sample_truncate runs between it and the close.  Needs x.
     bool trunc = false;
@@ -341,7 +383,7 @@ struct WmDecodeMode {
     int acap_base = 0, acap_Tq = 0, acap_J = 0;
     float *acap_q = nullptr;
     bool operator==(const WmDecodeMode &o) const {
-        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && alt == o.alt && rep == o.rep && sb == o.sb && sbt == o.sbt && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && alt == o.alt && rep == o.rep && sb == o.sb && sbt == o.sbt && cst == o.cst && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -508,6 +550,12 @@ struct WmModel {
     WmSbDev dsbt = {};
     int *dsb_rng = nullptr;             // [WM_DEC_MAXB][2]
     std::vector<int32_t> bias_rows_host;   // wm_set_bias_rows: the table of each row of the NEXT call (empty: none pending)
+    // constraint (wm_set_constraint): the automaton's counts, and the device tables allocated at full capacity when first switched
+    // on (dcst.par == null before that) -- never moved: the captured graphs hold the addresses; dcst.start is the group's row starts
+    bool cst_on = false;
+    int cst_states = 0, cst_edges = 0, cst_eot = 0;
+    WmCstDev dcst = {};
+    std::vector<int32_t> cst_rows_host;    // wm_set_constraint_rows: the start state of each row of the NEXT call (empty: none pending)
     unsigned *dx_ids = nullptr;    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     int *dxkv_rows = nullptr;      // [WM_DEC_MAXB] the group's rows of a window set (wm_transcribe_windows): the gather's row map
@@ -612,6 +660,8 @@ int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t);
 // the pooled tables (no tables: off) -> this context's device pool; the first non-empty set allocates it.  Replaces the single
 // table, as wm_model_set_sequence_bias replaces the tables.
 int wm_model_set_sequence_bias_tables(wm_ctx *ctx, const WmSbPool &p);
+// a checked automaton (no states: off) -> this context's device tables; the first non-empty one allocates them
+int wm_model_set_constraint(wm_ctx *ctx, const WmCstTable &t);
 int wm_model_set_timestamp_rules(wm_ctx *ctx, int enable, int32_t ts_begin, int32_t eot, int32_t max_initial);
 int wm_model_set_suppress(wm_ctx *ctx, const int32_t *ids, int n, const int32_t *first_ids, int n_first);
 // Speculative decoding (wm_transcribe_mel_speculative, spec.hip): the device view of one decode group of G
@@ -892,6 +942,12 @@ int wm_repeat_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int 
 // of this one has rebuilt.  V: ids at or above it set no bit.
 int wm_seqbias_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int n_prompt, int n_ctx, int V, const WmSbDev &sb,
                      unsigned *ban, int ban_words);
+// constraint.hip (constraint)
+// The rows' ban words |= the ids of [0, eot] their automaton states do not allow; launched behind wm_repeat_state (and the
+// sequence-bias launch) on the same stream.  state_out (nullable, [B]): the state each row reached (-1: dead; a row that wrote
+// nothing keeps what it had).
+int wm_constraint_state(wm_ctx *ctx, const int *seq, const int *pos_ptr, int B, int n_prompt, int n_ctx, int V, const WmCstDev &cst,
+                        unsigned *ban, int ban_words, int *state_out);
 // seqbias_rows.hip (row tables)
 // The same rebuild with a table per row: `pool` holds the concatenated tables (WmSbPool; pool.par is not read), row b walks groups
 // [rng[2 * b], rng[2 * b + 1]) of it -- at most WM_MAX_BIAS_ENTRIES groups; an empty range (no table, an empty table) gives an

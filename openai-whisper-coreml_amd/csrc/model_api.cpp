@@ -233,6 +233,29 @@ extern "C" int wm_set_bias_rows(wm_ctx *ctx, const int32_t *table_of_row, int n)
     m->bias_rows_host.assign(table_of_row, table_of_row + n);
     return WM_OK;
 } WM_API_CATCH
+extern "C" int wm_set_constraint(wm_ctx *ctx, const int32_t *edge_beg, const int32_t *edge_tok, const int32_t *edge_next,
+                                 const int32_t *def_next, const uint8_t *accept, int n_states, int32_t eot) try {
+    WM_MODEL(ctx);
+    // checked and packed ONCE, before any lane is touched: a refused call leaves the automaton in force where it was
+    WmCstTable t;
+    WM_TRY(wm_cst_build(edge_beg, edge_tok, edge_next, def_next, accept, n_states, eot, m->dims.n_vocab, &t));
+    WM_REQUIRE(t.n_states() == 0 || !ctx->dbg_hooks, WM_ERR_STATE, "the constraint is not supported by the all-f32 precision path");
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { return wm_model_set_constraint(c, t); });
+} WM_API_CATCH
+extern "C" int wm_set_constraint_rows(wm_ctx *ctx, const int32_t *start_of_row, int n) try {
+    WM_MODEL(ctx);
+    WM_REQUIRE(n >= 0 && (n == 0 || start_of_row), WM_ERR_INVALID, "set_constraint_rows: bad list");
+    if (n == 0) {
+        m->cst_rows_host.clear();
+        return WM_OK;
+    }
+    WM_REQUIRE(m->cst_on, WM_ERR_STATE, "set_constraint_rows: the context has no automaton (wm_set_constraint)");
+    for (int i = 0; i < n; ++i)
+        WM_REQUIRE(start_of_row[i] >= -1 && start_of_row[i] < m->cst_states, WM_ERR_INVALID,
+                   "set_constraint_rows: start state %d of row %d outside [-1, %d)", start_of_row[i], i, m->cst_states);
+    m->cst_rows_host.assign(start_of_row, start_of_row + n);
+    return WM_OK;
+} WM_API_CATCH
 extern "C" int wm_set_teacher_panel(wm_ctx *ctx, int width) try {
     WM_MODEL(ctx);
     (void)m;

@@ -214,6 +214,10 @@ extern "C" int wm_multi_transcribe_greedy(wm_multi *m, const void *pcm, wm_dtype
     for (int r = 0; r < R; ++r)
         WM_REQUIRE(!m->ctx[r]->model || !m->ctx[r]->model->sbt_on, WM_ERR_STATE,
                    "multi_transcribe_greedy does not support sequence-bias tables (device context %d has them)", r);
+    // (a constraint's row starts would need a map per device's slice of the call: not built)
+    for (int r = 0; r < R; ++r)
+        WM_REQUIRE(!m->ctx[r]->model || !m->ctx[r]->model->cst_on, WM_ERR_STATE,
+                   "multi_transcribe_greedy does not support a constraint (device context %d has an automaton)", r);
     {   // a request for alternatives pending on a device context is consumed and refused (its rows are the device's slice: not built)
         bool alt = false;
         for (int r = 0; r < R; ++r)

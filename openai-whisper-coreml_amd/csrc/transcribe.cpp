@@ -95,6 +95,8 @@ struct LaneJob {
     WmSampPar spar = {};           // its sampling rules (likewise)
     WmSbPar sbpar = {};            // its sequence-bias table's counts (likewise)
     WmAltPar apar = {};            // its alternatives request: n and the lane's buffers (likewise)
+    WmCstPar cpar = {};            // its constraint automaton's counts (likewise)
+    std::vector<int32_t> cstart;   // ... and its rows' start states [Bg] (likewise)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
     std::vector<int32_t> atok, acnt;   // its fetched alternatives: ids [max_new][Bg][n], counts [max_new][Bg]
     std::vector<float> alp, aent;      // ... log-probs [max_new][Bg][n], entropy [max_new][Bg]
@@ -183,6 +185,8 @@ struct TxCfg {
     int max_group_rows = 0;
     const int32_t *bias_rows = nullptr;   // row tables in force: the table of each row of the call [B] (wm_set_bias_rows), checked
     const wm_alternatives_out *alt = nullptr;   // the call's alternatives request (wm_request_alternatives), checked; null: none
+    // a constraint in force: the start state of each row of the call [B] (wm_set_constraint_rows), checked; null: every row starts in 0
+    const int32_t *cst_rows = nullptr;
 };
 
 // the tokens row `b` of the call may generate
@@ -204,7 +208,9 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     j.mode.beam = call.beam ? N : 0;
     j.mode.sbt = m->sbt_on;
     j.mode.sb = m->sb_on || m->sbt_on;
-    j.mode.rep = m->rep_on || j.mode.sb;   // (tx_validate turns the extended decode on with them; the bias reads the rules' bitmaps)
+    j.mode.cst = m->cst_on;
+    // (tx_validate turns the extended decode on with them; the bias and the constraint use the rules' bitmaps)
+    j.mode.rep = m->rep_on || j.mode.sb || j.mode.cst;
     j.mode.trunc = m->samp_on() && xc.on && xc.par.sample != 0;   // temperature 0 ignores the sampling rules: today's launches
     j.mode.alt = cfg.alt != nullptr;   // (tx_validate turned the extended decode on with it)
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
@@ -256,7 +262,7 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     if (j.mode.rep) {
         WM_REQUIRE(xc.on, WM_ERR_STATE, "the repetition rules need the extended decode");
         j.rpar.p = m->rep_p; j.rpar.inv_p = (float)(1.0 / (double)m->rep_p); j.rpar.n = m->rep_n; j.rpar.eot = m->rep_eot;
-        if (!m->rep_on) { j.rpar.p = 1.f; j.rpar.inv_p = 1.f; j.rpar.n = 0; j.rpar.eot = 0; }   // the sequence bias alone: empty rules
+        if (!m->rep_on) { j.rpar.p = 1.f; j.rpar.inv_p = 1.f; j.rpar.n = 0; j.rpar.eot = 0; }   // the bias or the constraint alone: empty rules
         WM_HIP(hipMemcpyAsync(m->drep_par, &j.rpar, sizeof(WmRepPar), hipMemcpyHostToDevice, c->stream));
     }
     // sampling rules: top_k, top_p and min_p live in device memory as well (the graph key holds `trunc` alone)
@@ -278,6 +284,15 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     } else if (j.mode.sb) {
         j.sbpar.n_groups = m->sb_groups; j.sbpar.n_entries = m->sb_entries;
         WM_HIP(hipMemcpyAsync((void *)m->dsb.par, &j.sbpar, sizeof(WmSbPar), hipMemcpyHostToDevice, c->stream));
+    }
+    // constraint: the automaton was uploaded when it was set; its counts and the rows' start states go with the group, so a captured
+    // graph replays for any automaton.  Row c * N + s (a candidate, a beam) takes the start of its window.
+    if (j.mode.cst) {
+        j.cpar.n_states = m->cst_states; j.cpar.n_edges = m->cst_edges; j.cpar.eot = m->cst_eot;
+        j.cstart.resize(Bg);
+        for (int r = 0; r < Bg; ++r) j.cstart[r] = cfg.cst_rows ? cfg.cst_rows[j.b0 + r / N] : 0;
+        WM_HIP(hipMemcpyAsync((void *)m->dcst.par, &j.cpar, sizeof(WmCstPar), hipMemcpyHostToDevice, c->stream));
+        WM_HIP(hipMemcpyAsync((void *)m->dcst.start, j.cstart.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
     }
     WM_TRY(wm_model_reserve(c, Cg));
     if (N > 1) WM_TRY(wm_model_reserve_rows(c, Bg));
@@ -542,7 +557,7 @@ int entry_checks(const TxCall &call) {
 // extended decode.  budgets: the call's (wm_set_token_budgets), clamped to max_new here.  opts == null with both extra
 // outputs null is the greedy decode exactly.
 int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg, const std::vector<int32_t> *bias_rows = nullptr,
-                const wm_alternatives_out *alt = nullptr) {
+                const wm_alternatives_out *alt = nullptr, const std::vector<int32_t> *cst_rows = nullptr) {
     WmModel *m = ctx->model;
     const WmAudioSrc &src = call.src;
     const TxPrompts &p = call.prompts;
@@ -598,7 +613,7 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     WM_REQUIRE(!call.no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
     WM_REQUIRE(!call.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
     // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
-    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || alt;
+    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || m->cst_on || alt;
     if (alt) {   // the call's alternatives request (wm_request_alternatives checked n and the pointers)
         WM_REQUIRE(!call.beam, WM_ERR_STATE, "alternatives are not served by beam-search calls");
         WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "alternatives are not supported by the all-f32 precision path");
@@ -618,6 +633,14 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
             WM_REQUIRE((*bias_rows)[b] >= -1 && (*bias_rows)[b] < nt, WM_ERR_INVALID, "bias row map: table %d of row %d outside [-1, %d)",
                        (*bias_rows)[b], b, nt);
         cfg->bias_rows = bias_rows->data();
+    }
+    WM_REQUIRE(!m->cst_on || !ctx->dbg_hooks, WM_ERR_STATE, "the constraint is not supported by the all-f32 precision path");
+    if (m->cst_on && cst_rows) {   // the call's start states (wm_set_constraint_rows), one per row of the call; none: every row starts in 0
+        WM_REQUIRE((int)cst_rows->size() == B, WM_ERR_INVALID, "the constraint row map was set for %d rows, the call has %d", (int)cst_rows->size(), B);
+        for (int b = 0; b < B; ++b)
+            WM_REQUIRE((*cst_rows)[b] >= -1 && (*cst_rows)[b] < m->cst_states, WM_ERR_INVALID,
+                       "constraint row map: start state %d of row %d outside [-1, %d)", (*cst_rows)[b], b, m->cst_states);
+        cfg->cst_rows = cst_rows->data();
     }
     xc.logprobs = call.logprobs_out;
     xc.no_speech = call.no_speech_out;
@@ -1017,6 +1040,9 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
     // ... and so is the row map of the sequence-bias tables (wm_set_bias_rows)
     std::vector<int32_t> bias_rows;
     if (ctx && ctx->model) bias_rows.swap(ctx->model->bias_rows_host);
+    // ... and the start states of the constraint's rows (wm_set_constraint_rows)
+    std::vector<int32_t> cst_rows;
+    if (ctx && ctx->model) cst_rows.swap(ctx->model->cst_rows_host);
     // ... and the request for alternatives (wm_request_alternatives)
     wm_alternatives_out alt_req = {};
     bool alt_on = false;
@@ -1029,7 +1055,8 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
         call.logprobs_out = lp_own.data();
     }
     TxCfg cfg;
-    WM_TRY(tx_validate(ctx, call, budgets, &cfg, bias_rows.empty() ? nullptr : &bias_rows, alt_on ? &alt_req : nullptr));
+    WM_TRY(tx_validate(ctx, call, budgets, &cfg, bias_rows.empty() ? nullptr : &bias_rows, alt_on ? &alt_req : nullptr,
+                       cst_rows.empty() ? nullptr : &cst_rows));
     // the plan: decode groups and lanes.  A masked clone that cannot be made switches the masks off and asks again.
     WmTxPlanIn pin;
     pin.B = call.B; pin.N = call.n_cand;
@@ -1130,6 +1157,7 @@ int spec_checks(wm_ctx *ctx, const SpecCall &sc, const TxCall &call) {
     WmModel *m = ctx->model, *dm = sc.draft->model;
     WM_REQUIRE(!m->rep_on, WM_ERR_STATE, "speculative decoding does not support the repetition rules set on this context");
     WM_REQUIRE(!m->sb_on && !m->sbt_on, WM_ERR_STATE, "speculative decoding does not support the sequence bias set on this context");
+    WM_REQUIRE(!m->cst_on, WM_ERR_STATE, "speculative decoding does not support the constraint set on this context");
     WM_REQUIRE(!ctx->dbg_hooks && !sc.draft->dbg_hooks, WM_ERR_STATE, "speculative decoding is not supported by the all-f32 precision path");
     WM_REQUIRE(dm && dm->finalized, WM_ERR_STATE, "the draft's model weights are not finalised (wm_finalize)");
     WM_REQUIRE(sc.draft->device == ctx->device, WM_ERR_INVALID, "the draft context lives on device %d, the target on %d",
@@ -1138,7 +1166,8 @@ int spec_checks(wm_ctx *ctx, const SpecCall &sc, const TxCall &call) {
     WM_REQUIRE(a.n_mels == b.n_mels && a.n_vocab == b.n_vocab && a.n_text_ctx == b.n_text_ctx && a.n_audio_ctx == b.n_audio_ctx,
                WM_ERR_INVALID, "the draft's n_mels / n_vocab / n_text_ctx / n_audio_ctx (%d / %d / %d / %d) differ from the target's (%d / %d / %d / %d)",
                b.n_mels, b.n_vocab, b.n_text_ctx, b.n_audio_ctx, a.n_mels, a.n_vocab, a.n_text_ctx, a.n_audio_ctx);
-    WM_REQUIRE(!dm->rep_on && !dm->sb_on && !dm->sbt_on, WM_ERR_STATE, "the draft context has repetition rules or a sequence bias set");
+    WM_REQUIRE(!dm->rep_on && !dm->sb_on && !dm->sbt_on && !dm->cst_on, WM_ERR_STATE,
+               "the draft context has repetition rules, a sequence bias or a constraint set");
     return WM_OK;
 }
 
@@ -1253,6 +1282,7 @@ int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
     std::vector<int32_t> budgets;   // consumed by this call whatever happens next (tx_transcribe)
     if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
     if (ctx && ctx->model) ctx->model->bias_rows_host.clear();   // a pending row map likewise
+    if (ctx && ctx->model) ctx->model->cst_rows_host.clear();    // ... and the constraint's
     bool alt_on = false;   // ... and a request for alternatives, which this call refuses below
     if (ctx && ctx->model) { alt_on = ctx->model->alt_pending; ctx->model->alt_pending = false; }
     const int32_t *dbg_script = nullptr;   // the debug library's script is for this call only
