@@ -844,6 +844,28 @@ WM_API int wm_set_constraint(wm_ctx *ctx, const int32_t *edge_beg /* [n_states +
                              const uint8_t *accept /* [n_states] */, int n_states, int32_t eot);
 WM_API int wm_set_constraint_rows(wm_ctx *ctx, const int32_t *start_of_row /* [n], -1 .. n_states - 1 */, int n);
 
+/* Temperature and seed per ROW: wm_set_sampling_rows names the temperature and the seed of every row of the NEXT transcribe call
+ * on the context, like wm_set_bias_rows -- so requests with different temperatures batch into one call, and a long-form window
+ * that needs a temperature fallback rides the next round's call beside the other recordings' temperature-0 windows
+ * (DESIGN.md section 23).
+ *   Life: consumed by that call whatever happens; n must equal its B (WM_ERR_INVALID otherwise); n = 0 drops a pending map.  With
+ *     a pending map, opts->temperature and opts->seed of that call are validated as always and not read.  The map is per call:
+ *     it applies to the lanes of the call like the other row maps, and wm_clone has nothing to copy.
+ *   Row b under (temperature[b], seed[b]): its tokens, length, log-probs and no-speech probability -- and its alternatives,
+ *     entropy and the start frames of an aligned entry -- equal, bit for bit, what the same call gives that row when every row
+ *     runs at opts->temperature = temperature[b], opts->seed = seed[b].  The Philox counter words are unchanged: id quad,
+ *     generated index, sample id or call index, 0.  A row with temperature[b] == 0 is an arg-max row: the temperature-0 call's
+ *     bits, its seed is ignored.  The sampling rules (wm_set_sampling_rules) act on the rows whose temperature is > 0 and leave
+ *     the others alone.  Results do not depend on the other rows, the grouping or the lanes.
+ *   Checked here (on failure the pending map stays dropped): no null pointer when n > 0; every temperature finite and >= 0;
+ *     (float)(1.0 / (double)T) finite for every T > 0, the rule of opts->temperature.
+ *   Served: wm_transcribe, wm_transcribe_mel, _mel_ragged, wm_transcribe_windows, wm_transcribe_mel_aligned and
+ *     wm_transcribe_windows_aligned.  Refused with WM_ERR_STATE (not built; the map is consumed all the same):
+ *     wm_transcribe_greedy, the best-of entries, the beam entries and wm_transcribe_mel_speculative (the last two decode at
+ *     temperature 0 by definition), wm_multi_transcribe_greedy on a device context with a pending map, the all-f32 debug path.
+ * A call without a pending map makes exactly the launches it makes without this entry. */
+WM_API int wm_set_sampling_rows(wm_ctx *ctx, const float *temperature /* [n] */, const uint64_t *seed /* [n] */, int n);
+
 /* Per-chunk token budgets for the NEXT wm_transcribe_greedy call on this context (consumed by it; n must equal that
  * call's B): chunk i generates at most budgets[i] tokens (clamped to max_new), lens_out[i] <=
  * budgets[i].  A chunk that has reached its budget -- like one that has emitted `eot` -- LEAVES the decode: its caches are

@@ -172,6 +172,12 @@ WM_API int wmdbg_decode_close_shared(wm_ctx *ctx, wmdbg_step *io, int w, int32_t
  * temperature 0 the launches are wmdbg_decode_close's.  With first-position suppress ids, mask_first must say whether pos is
  * n_prompt - 1. */
 WM_API int wmdbg_decode_close_trunc(wm_ctx *ctx, wmdbg_step *io, int top_k, float top_p, float min_p);
+/* wmdbg_decode_close / wmdbg_decode_close_trunc with a temperature and a seed per row in force (wm_set_sampling_rows): one decode
+ * position -- the logits launch, the truncation launch when the rules are on ((0, 1, 0): no truncation launch) and some row
+ * samples, and the close -- with the rows' table handed to the X-mode kernels.  Needs x_on; io->temperature and io->seed are not
+ * read; row_T[b] == 0 is an arg-max row.  struct wmdbg_step is unchanged: the row arrays [io->B] are arguments. */
+WM_API int wmdbg_decode_close_rows(wm_ctx *ctx, wmdbg_step *io, const float *row_T, const uint64_t *row_seed, int top_k, float top_p,
+                                   float min_p);
 /* wmdbg_decode_close with the repetition rules on (wm_set_repetition_rules: penalty, ngram, and io->eot as the rules' eot, in
  * [0, V] whatever ts_mode is): wm_repeat_state on the token history in front of a DE_LOGITS_XR launch.  Needs x_on and
  * n_prompt <= n_ctx.  The bitmaps are pre-filled with 0xff bytes.  (1.0, 0) runs the same kernels with empty rules. */

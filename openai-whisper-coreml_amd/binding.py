@@ -13,6 +13,7 @@ same names, argument meaning and error behaviour:
 Everything goes through libwhisper_mi355x.so (include/whisper_mi355x.h).  There is no
 CPU fallback: if the library is missing, or no gfx950 device is usable, calls raise.
 """
+import contextlib
 import ctypes
 import math
 import os
@@ -692,6 +693,37 @@ def transcribe_with_fallback(ctx, pcm, prompt, max_new, eot, temperatures=FALLBA
                 ctx.set_sampling_rules()
 
 
+def needs_fallback(compression_ratio, avg_logprob, no_speech_prob, compression_ratio_threshold, logprob_threshold,
+                   no_speech_threshold):
+    """The decision rule of the temperature fallback (openai-whisper's decode_with_fallback), stated once for fallback_decode and
+    for transcribe_long's deferred rounds: an attempt fails when its compression ratio exceeds compression_ratio_threshold or its
+    avg_logprob is below logprob_threshold -- and does not when its no_speech_prob (None: not computed) exceeds
+    no_speech_threshold, checked last.  A threshold of None is not checked (compression_ratio_threshold: a number here, 'auto'
+    is fallback_decode's to resolve)."""
+    nf = False
+    if compression_ratio_threshold is not None and compression_ratio > compression_ratio_threshold:
+        nf = True
+    if logprob_threshold is not None and avg_logprob < logprob_threshold:
+        nf = True
+    if no_speech_threshold is not None and no_speech_prob is not None and no_speech_prob > no_speech_threshold:
+        nf = False
+    return nf
+
+
+def sampling_rows_args(row_temperatures, row_seeds, rows=None):
+    """row_temperatures / row_seeds of the transcribe wrappers, checked before any library call: both None (-> None) or one
+    value per row each (-> (f32 array, u64 array)); ValueError for one without the other or lengths that differ."""
+    if row_temperatures is None and row_seeds is None:
+        return None
+    if row_temperatures is None or row_seeds is None:
+        raise ValueError("row_temperatures and row_seeds: both or neither")
+    t = np.ascontiguousarray([float(x) for x in row_temperatures], dtype=np.float32)
+    sd = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in row_seeds], dtype=np.uint64)
+    if t.size != sd.size or (rows is not None and t.size != rows):
+        raise ValueError("row_temperatures and row_seeds: one value per row each")
+    return t, sd
+
+
 def fallback_decode(decode, B, vocab_size, max_new, eot, temperatures=FALLBACK_TEMPERATURES,
                     compression_ratio_threshold="auto", logprob_threshold=-1.0, no_speech_threshold=0.6, vocab=None,
                     seed=0):
@@ -719,14 +751,8 @@ def fallback_decode(decode, B, vocab_size, max_new, eot, temperatures=FALLBACK_T
             text_toks = r.tokens[i, :n_text]
             cr = (compression_ratio_text(vocab.decode(text_toks)) if vocab is not None
                   else compression_ratio_tokens(text_toks, vocab_size))
-            nf = False
-            if compression_ratio_threshold is not None and cr > compression_ratio_threshold:
-                nf = True
-            if logprob_threshold is not None and r.avg_logprob[i] < logprob_threshold:
-                nf = True
-            if (no_speech_threshold is not None and r.no_speech_prob is not None
-                    and r.no_speech_prob[i] > no_speech_threshold):
-                nf = False
+            nf = needs_fallback(cr, r.avg_logprob[i], None if r.no_speech_prob is None else r.no_speech_prob[i],
+                                compression_ratio_threshold, logprob_threshold, no_speech_threshold)
             need[i] = nf
             out["tokens"][b] = r.tokens[i]
             out["lens"][b] = r.lens[i]
@@ -1201,6 +1227,16 @@ class _LongOptions(types.SimpleNamespace):
                              (bool(self.sequence_bias) or bool(self.bad_words) or bool(self.boost_phrases), "a sequence bias")):
                 if on:
                     raise ValueError("draft (speculative decoding) cannot be combined with %s" % what)
+        if self.fallback not in ("lockstep", "deferred"):   # 26.
+            raise ValueError("fallback: 'lockstep' or 'deferred'")
+        self.deferred = self.fallback == "deferred"
+        if self.deferred:
+            for on, what in ((self.best_of is not None, "best_of"), (self.beam_size is not None or self.patience is not None, "beam_size"),
+                             (self.draft is not None, "draft"), (bool(self.reuse_encoder), "reuse_encoder")):
+                if on:
+                    raise ValueError("fallback='deferred' cannot be combined with %s" % what)
+            if len(self.temperatures) == 0:
+                raise ValueError("fallback='deferred' needs at least one temperature")
         self.panel_pending = self.teacher_panel is not None   # set on the context in front of the first alignment call
         if self.prepend_punctuations is None:
             self.prepend_punctuations = PREPEND_PUNCTUATIONS
@@ -1225,7 +1261,8 @@ class _Unit:
     clips.  rec .. seed_tokens (the initial prompt) are the recording's; the history (all_tokens, reset_since), the clip
     cursor, the seek, `before` -- (cursor, seek) of the previous window --, last_speech and the result lists its own."""
     __slots__ = ("index", "rec", "rec_id", "mel_off", "T", "content", "lang", "seed_tokens", "carry", "all_tokens",
-                 "reset_since", "clips", "cur", "seek", "before", "last_speech", "lane", "segments", "seeks", "windows")
+                 "reset_since", "clips", "cur", "seek", "before", "last_speech", "lane", "segments", "seeks", "windows",
+                 "attempt", "tried", "size")
 
     def __init__(self, index, rec, rec_id, mel_off, T, lang, seed_tokens, carry, clips, lane):
         self.index, self.rec, self.rec_id, self.mel_off, self.T, self.lang = index, rec, rec_id, mel_off, T, lang
@@ -1235,6 +1272,8 @@ class _Unit:
         self.cur, self.seek, self.before = 0, clips[0][0] if clips else 0, None
         self.last_speech = clips[0][0] * HOP_SECONDS if lane else 0.0
         self.segments, self.seeks, self.windows = [], [], []
+        # fallback="deferred": the open window's next attempt (0: no window is held open), the temperatures it has run, its frames
+        self.attempt, self.tried, self.size = 0, [], 0
 
     def advance(self):
         """the clip cursor before a round: a seek at or past its clip's end moves to the next clip's start; False: none left"""
@@ -1316,7 +1355,8 @@ class _RoundRows:
         return (self.d_mel, np.array([u.mel_off for u in us]), np.array([u.T for u in us]), [u.seek for u in us],
                 [self.sizes[i] for i in rows])
 
-    def decode(self, todo, t, sd):
+    def decode(self, todo, t, sd, rows=None):
+        """rows (fallback="deferred"): (temperatures, seeds) of the ROUND's rows -- the call carries its rows' own"""
         o = self.o
         extra = fallback_step_extra(t, o.best_of, o.length_penalty, o.beam_size, o.patience)
         prompts = [self.prompts[i] for i in todo] if o.ragged else self.prompts[todo]
@@ -1324,6 +1364,8 @@ class _RoundRows:
             o.ctx.set_bias_rows([o.rec_tables[self.units[i].rec] for i in todo])
         kw = dict(eot=o.eot, temperature=t, seed=sd, no_speech_token=o.no_speech_token, sample_ids=[self.ids[i] for i in todo],
                   **o.sot_kw, **extra, **o.alt_kw)
+        if rows is not None:   # 26.
+            kw.update(row_temperatures=[rows[0][i] for i in todo], row_seeds=[rows[1][i] for i in todo])
         if o.words_decode:   # 18.: every attempt through the aligned entry; the kept one's start frames feed the word step
             r = self._decode_aligned(todo, prompts, kw, extra)
             for k, i in enumerate(todo):
@@ -1552,7 +1594,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
                     boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None, recording_bias=None,
-                    top_k=None, top_p=None, min_p=None, alternatives=None, constraint=None):
+                    top_k=None, top_p=None, min_p=None, alternatives=None, constraint=None, fallback="lockstep"):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1728,6 +1770,17 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        the timestamps around and between them are the timestamp rules' business.  ValueError before any library call for
        anything but a Constraint and together with draft.  With None the function makes exactly the calls it made before the
        argument existed.
+    26. fallback ("lockstep", the default: the rounds of 3.; "deferred"): a window that needs a temperature fallback does not hold
+       its round open.  Every round makes ONE decode call whose rows carry their own temperature and seed
+       (Context.set_sampling_rows, wm_set_sampling_rows): a unit whose window's attempt k failed fallback_decode's rule
+       (needs_fallback) and has a temperature left keeps that window open, does not advance, and is a live unit of the next round
+       with attempt k + 1 -- the same window, prompt and sample id at temperatures[k + 1] and fallback_seed(seed, k + 1) -- beside
+       the other units' next windows at temperatures[0].  The window's record lists the temperatures it ran, its kept attempt is
+       the last one, and the word step runs over the windows a round kept.  Per recording, language, segments, seeks and the
+       window records except `round` equal the lockstep run's exactly: a row's bits depend on its own window, prompt, sample id,
+       temperature and seed, and the sample id does not depend on the round.  ValueError before any library call for any other
+       value and for "deferred" together with best_of, beam_size, draft or reuse_encoder.  With "lockstep" the function makes
+       exactly the calls it made before the argument existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1785,21 +1838,39 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
             if source is not None:   # the previous round's (reuse_encoder: its set)
                 source.close()
                 source = None
-            live = [u for u in units if u.advance()][:o.par_n]
+            live = [u for u in units if u.attempt or u.advance()][:o.par_n]   # (26.: a window held open is not advanced past)
             if not live:
                 break
             n_round += 1
-            sizes = [u.open_window() for u in live]
+            for u in live:
+                if not u.attempt:
+                    u.size = u.open_window()
+            sizes = [u.size for u in live]
             prompts = [u.prompt(o) for u in live]
             # (9. reuse_encoder: the round's windows are encoded once here, for every fallback step and the word step)
             source = _RoundRows(o, d_mel, live, sizes, prompts, [u.sample_id() for u in live])
             if o.prompt_panel_pending:   # 21.
                 ctx.set_prompt_panel(int(prompt_panel))
                 o.prompt_panel_pending = False
-            res = fallback_decode(source.decode, len(live), o.vocab_size, o.max_new, eot, temperatures, compression_ratio_threshold,
-                                  logprob_threshold, no_speech_threshold, vocab, seed)
+            if o.deferred:   # 26.: ONE call, every row at its own attempt's temperature and seed; the rule is fallback_decode's
+                ks = [u.attempt for u in live]
+                row_ts = ([float(temperatures[k]) for k in ks], [fallback_seed(seed, k) for k in ks])
+                res = fallback_decode(lambda todo, t, sd: source.decode(todo, t, sd, rows=row_ts), len(live), o.vocab_size, o.max_new,
+                                      eot, (0.0,), compression_ratio_threshold, logprob_threshold, no_speech_threshold, vocab, seed)
+                res["temperature"][:] = row_ts[0]
+                res["seed"][:] = row_ts[1]
+            else:
+                res = fallback_decode(source.decode, len(live), o.vocab_size, o.max_new, eot, temperatures, compression_ratio_threshold,
+                                      logprob_threshold, no_speech_threshold, vocab, seed)
             kept = []   # word_timestamps: (row of the round, segments, next seek, single_timestamp_ending) of every kept window
             for i, u in enumerate(live):
+                ran = [st[0] for st in res["steps"] if i in st[2]]
+                if o.deferred:
+                    u.tried.append(row_ts[0][i])
+                    if res["needs_fallback"][i] and u.attempt + 1 < len(temperatures):   # the window stays open: the next round
+                        u.attempt += 1
+                        continue
+                    ran, u.tried, u.attempt = u.tried, [], 0
                 n_text = n_text_tokens(res["tokens"][i, :res["lens"][i]], eot)
                 tokens = res["tokens"][i, :n_text]
                 result = {k: float(res[k][i]) for k in ("temperature", "avg_logprob", "compression_ratio", "no_speech_prob")}
@@ -1810,8 +1881,7 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                                                 [float(h) for h in res["entropy"][i, :n_text]]))
                 skip = should_skip_window(result["no_speech_prob"], result["avg_logprob"], no_speech_threshold,
                                           logprob_threshold)
-                u.record_window(o, sizes[i], prompts[i], [st[0] for st in res["steps"] if i in st[2]], skip, tokens, n_round,
-                                source.kept_by[i])
+                u.record_window(o, sizes[i], prompts[i], ran, skip, tokens, n_round, source.kept_by[i])
                 if skip:
                     u.seek += sizes[i]
                 elif o.words_on:
@@ -2346,6 +2416,20 @@ class Context:
         a = np.ascontiguousarray([-1 if r is None else int(r) for r in starts], dtype=np.int32)
         _check(self.lib, fn(self.handle, _ptr(a) if a.size else None, int(a.size)))
 
+    def set_sampling_rows(self, temperatures, seeds):
+        """Temperature and seed of every row of the NEXT transcribe call (wm_set_sampling_rows; len == its B; consumed by it):
+        that call's own temperature and seed are then not read, a row with temperature 0 is an arg-max row.  Served by
+        transcribe, transcribe_mel, transcribe_windows and the two aligned wrappers (row_temperatures= / row_seeds=); refused by
+        the greedy, best-of, beam-search and speculative entries.  [] and [] (or None and None) drop a pending map."""
+        self._put_sampling_rows(*(sampling_rows_args(temperatures, seeds) or sampling_rows_args([], [])))
+
+    def _put_sampling_rows(self, t, sd):
+        """wm_set_sampling_rows on checked arrays (sampling_rows_args)"""
+        fn = self.lib.wm_set_sampling_rows
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        fn.restype = ctypes.c_int
+        _check(self.lib, fn(self.handle, _ptr(t) if t.size else None, _ptr(sd) if sd.size else None, int(t.size)))
+
     def set_lanes(self, n):
         """Decode groups one transcribe_greedy call keeps in flight (0: default = $WM_LANES or 3; 1: one group per call)."""
         _check(self.lib, self.lib.wm_set_lanes(self.handle, int(n)))
@@ -2418,14 +2502,35 @@ class Context:
         return (toks, lens, lp, ns) if alt is None else (toks, lens, lp, ns, alt)
 
     def transcribe(self, pcm, prompt, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1, sot_index=0,
-                   budgets=None, alternatives=None):
+                   budgets=None, alternatives=None, row_temperatures=None, row_seeds=None):
         """wm_transcribe: greedy (temperature 0) or sampled decode with per-token log-probs and, with no_speech_token >= 0,
         openai-whisper's no_speech_prob.  alternatives=n: also the n best admissible tokens and the entropy of every generated
-        position (request_alternatives).  Returns a TranscribeResult."""
+        position (request_alternatives).  row_temperatures / row_seeds (both or neither): a temperature and a seed per row
+        (set_sampling_rows in front of the call; temperature and seed are then not read).  Returns a TranscribeResult."""
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
-        toks, lens, lp, ns, *alt = self.transcribe_raw(pcm, prompt, max_new, eot, opts, logprobs=True,
-                                                       no_speech=no_speech_token >= 0, budgets=budgets, alternatives=alternatives)
+        with self._rows_map(row_temperatures, row_seeds):
+            toks, lens, lp, ns, *alt = self.transcribe_raw(pcm, prompt, max_new, eot, opts, logprobs=True,
+                                                           no_speech=no_speech_token >= 0, budgets=budgets, alternatives=alternatives)
         return self._with_alternatives(TranscribeResult(toks, lens, lp, ns, eot), alt)
+
+    @contextlib.contextmanager
+    def _rows_map(self, row_temperatures, row_seeds):
+        """row_temperatures / row_seeds of a wrapper around its call: the map is set on entry (both None: no library call is
+        made at all), and whatever raises between there and the C call -- an argument check in Python -- drops it again, so
+        that it cannot stay pending for a later, unrelated call.  (A C call that fails has consumed it; dropping twice is harmless.)"""
+        rows = sampling_rows_args(row_temperatures, row_seeds)
+        if rows is None:
+            yield
+            return
+        self._put_sampling_rows(*rows)
+        try:
+            yield
+        except BaseException:
+            try:
+                self.set_sampling_rows([], [])
+            except WhisperError:
+                pass
+            raise
 
     @staticmethod
     def _with_alternatives(result, alt):
@@ -2632,8 +2737,11 @@ class Context:
 
     def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                        no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                       sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None, alternatives=None):
+                       sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None, alternatives=None,
+                       row_temperatures=None, row_seeds=None):
         """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
+        row_temperatures / row_seeds (both or neither; not with best_of or beam_size): a temperature and a seed per row
+        (set_sampling_rows in front of the call; temperature and seed are then not read).
         alternatives=n: also the n best admissible tokens and the entropy of every generated position (not with beam_size).
         Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw.
         best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`).
@@ -2644,16 +2752,26 @@ class Context:
         common = dict(mem=mem, budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail)
         entry = dict(common, eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, length_penalty=length_penalty)
 
+        self._rows_entry(row_temperatures, row_seeds, best_of, beam_size, patience)
+
         def plain():
-            toks, lens, lp, ns, *alt = self.transcribe_mel_raw(
-                *win, eot, wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index)),
-                sample_ids, logprobs=True, no_speech=no_speech_token >= 0, alternatives=alternatives, **common)
+            with self._rows_map(row_temperatures, row_seeds):
+                toks, lens, lp, ns, *alt = self.transcribe_mel_raw(
+                    *win, eot, wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index)),
+                    sample_ids, logprobs=True, no_speech=no_speech_token >= 0, alternatives=alternatives, **common)
             return self._with_alternatives(TranscribeResult(toks, lens, lp, ns, eot), alt)
         return self._decode_entry(
             lambda: self.transcribe_mel_beam(*win, beam_size, patience=patience, **entry),
             lambda: self.transcribe_mel_best_of(*win, best_of, temperature=temperature, seed=seed, sample_ids=sample_ids,
                                                 alternatives=alternatives, **entry),
             plain, temperature, best_of, beam_size, patience)
+
+    @staticmethod
+    def _rows_entry(row_temperatures, row_seeds, best_of, beam_size, patience):
+        """a row map goes with the plain entry alone (checked before any library call)"""
+        if sampling_rows_args(row_temperatures, row_seeds) is not None and (best_of is not None or beam_size is not None or
+                                                                            patience is not None):
+            raise ValueError("row_temperatures / row_seeds cannot be combined with best_of or beam_size")
 
     @staticmethod
     def _decode_entry(beam, candidates, plain, temperature, best_of, beam_size, patience):
@@ -2706,10 +2824,13 @@ class Context:
 
     def transcribe_windows(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
                            sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, best_of=None,
-                           length_penalty=None, beam_size=None, patience=None, alternatives=None):
+                           length_penalty=None, beam_size=None, patience=None, alternatives=None, row_temperatures=None,
+                           row_seeds=None):
         """transcribe_mel with rows of a Windows set in place of the mel windows: the same bits, no encoder pass.  Returns a
-        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel; alternatives=n as there)."""
+        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel; alternatives=n and row_temperatures /
+        row_seeds as there)."""
         alternatives_arg(alternatives, beam_size if beam_size is not None else patience)
+        self._rows_entry(row_temperatures, row_seeds, best_of, beam_size, patience)
         common = dict(eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, budgets=budgets, prompt_len=prompt_len,
                       sot_tail=sot_tail, length_penalty=length_penalty)
 
@@ -2718,7 +2839,8 @@ class Context:
                                                    sample_ids=sample_ids, alternatives=alternatives, **common)
 
         def plain():   # (the set has no entry of its own for one sample: candidate 0 of N = 1)
-            r = candidates(1)
+            with self._rows_map(row_temperatures, row_seeds):
+                r = candidates(1)
             t = TranscribeResult(np.ascontiguousarray(r.tokens[:, 0]), np.ascontiguousarray(r.lens[:, 0]),
                                  np.ascontiguousarray(r.logprobs[:, 0]), r.no_speech_prob, eot)
             if r.alt_tokens is not None:
@@ -2731,31 +2853,34 @@ class Context:
             lambda: candidates(best_of), plain, temperature, best_of, beam_size, patience)
 
     def _aligned_call(self, fn, rows, tail, prompts, max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids,
-                      budgets, prompt_len, sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=None):
+                      budgets, prompt_len, sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=None, row_temperatures=None,
+                      row_seeds=None):
         """wm_transcribe_mel_aligned / wm_transcribe_windows_aligned (rows, tail: as in _best_of_call)"""
         n_alt = alternatives_arg(alternatives)
-        opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
-        if budgets is not None:
-            self.set_token_budgets(budgets)
-        head, B = rows()
-        pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
-        toks = np.empty((B, max_new), dtype=np.int32)
-        lens = np.empty(B, dtype=np.int32)
-        lp = np.empty((B, max_new), dtype=np.float32)
-        ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
-        start = np.empty((B, max_new + 1), dtype=np.int32)
-        matrix = self._capture_matrix(B, max_new) if capture_matrix else None
-        alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None
-        _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
-                            1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), max_new, eot, ctypes.byref(opts),
-                            int(medfilt_width), float(qk_scale), _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(start),
-                            *tail))
+        with self._rows_map(row_temperatures, row_seeds):
+            opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
+            if budgets is not None:
+                self.set_token_budgets(budgets)
+            head, B = rows()
+            pr, plen, opts, ids = self._prompt_call_args(B, prompts, opts, sample_ids, prompt_len, sot_tail)
+            toks = np.empty((B, max_new), dtype=np.int32)
+            lens = np.empty(B, dtype=np.int32)
+            lp = np.empty((B, max_new), dtype=np.float32)
+            ns = np.empty(B, dtype=np.float32) if no_speech_token >= 0 else None
+            start = np.empty((B, max_new + 1), dtype=np.int32)
+            matrix = self._capture_matrix(B, max_new) if capture_matrix else None
+            alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None
+            _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
+                                1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), max_new, eot, ctypes.byref(opts),
+                                int(medfilt_width), float(qk_scale), _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(start),
+                                *tail))
         r = AlignedResult(toks, lens, lp, ns, eot, start, matrix)
         return r if alt is None else alt.attach(r)
 
     def transcribe_mel_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                                no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                               sot_tail=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False, alternatives=None):
+                               sot_tail=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False, alternatives=None,
+                               row_temperatures=None, row_seeds=None):
         """wm_transcribe_mel_aligned: transcribe_mel (one sample per row; uniform or ragged prompts as in transcribe_mel_raw)
         whose decode also aligns what it generates, from its own cross-attention queries.  Tokens, lens, log-probs and
         no_speech_prob are transcribe_mel's bit for bit.  Returns an AlignedResult (start_frames; decode_alignment_text turns
@@ -2763,15 +2888,17 @@ class Context:
         return self._aligned_call(self.lib.wm_transcribe_mel_aligned,
                                   lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new, eot,
                                   temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len, sot_tail,
-                                  medfilt_width, qk_scale, capture_matrix, alternatives=alternatives)
+                                  medfilt_width, qk_scale, capture_matrix, alternatives=alternatives,
+                                  row_temperatures=row_temperatures, row_seeds=row_seeds)
 
     def transcribe_windows_aligned(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
                                    sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, medfilt_width=7,
-                                   qk_scale=1.0, capture_matrix=False, alternatives=None):
+                                   qk_scale=1.0, capture_matrix=False, alternatives=None, row_temperatures=None, row_seeds=None):
         """wm_transcribe_windows_aligned: transcribe_mel_aligned with rows of a Windows set.  Same bits."""
         return self._aligned_call(self.lib.wm_transcribe_windows_aligned, lambda: self._window_rows(windows, rows), (), prompts,
                                   max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
-                                  sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=alternatives)
+                                  sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=alternatives,
+                                  row_temperatures=row_temperatures, row_seeds=row_seeds)
 
     def transcribe_mel_best_of_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1,
                                        temperature=0.0, seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST,

@@ -2223,9 +2223,11 @@ static int shared_closes_run(wm_ctx *ctx, DevPool &pool, const wmdbg_step *io, c
 // sh: the beam and accept closes on the same partials, in front of the arg-max close (wmdbg_decode_close_shared)
 // trunc: the sampling rules are on -- wm_sample_truncate between the logits launch and the close (a sampling X-mode step)
 // cst (with rep): the constraint as well -- wm_constraint_state behind the other state launches, with the rows' starts
+// row_T / row_seed: temperature and seed per row (wm_set_sampling_rows) -- io->temperature and io->seed are not read, the X-mode
+// kernels are handed the rows' table
 static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram, const WmSbTable *sbt = nullptr,
                             const CloseShared *sh = nullptr, const WmSampPar *trunc = nullptr, const WmCstTable *cst = nullptr,
-                            const int32_t *cst_starts = nullptr) {
+                            const int32_t *cst_starts = nullptr, const float *row_T = nullptr, const uint64_t *row_seed = nullptr) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
     if (rep)
@@ -2280,6 +2282,19 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     xp.sample = io->temperature > 0.f ? 1 : 0;
     xp.inv_T = io->temperature > 0.f ? (float)(1.0 / (double)io->temperature) : 0.f;   // as wm_transcribe fills it
     xp.sot_pos = io->sot_pos; xp.ns_tok = io->ns_tok; xp.chunk0 = io->chunk0; xp.n_prompt = n_prompt; xp.n_cand = 1;
+    std::vector<WmXRow> xrows;
+    if (row_T) {   // as lane_prefill fills it: behind the (unused) id words, padded with arg-max rows, the scalar fields unused
+        WM_REQUIRE(io->x_on && row_seed, WM_ERR_INVALID, "wmdbg_decode_close_rows: needs x_on and both row arrays");
+        xrows.assign((size_t)WM_XIDS_WORDS / 4, WmXRow{0.f, 0u, 0u, 0u});
+        WmXRow *tab = const_cast<WmXRow *>(wm_x_rows((const unsigned *)xrows.data()));
+        xp.key0 = xp.key1 = 0u; xp.inv_T = 0.f; xp.sample = 0; xp.rows_on = 1;
+        for (int b = 0; b < B; ++b) {
+            WM_REQUIRE(std::isfinite(row_T[b]) && row_T[b] >= 0.f, WM_ERR_INVALID, "wmdbg_decode_close_rows: temperature of row %d", b);
+            if (!(row_T[b] > 0.f)) continue;
+            tab[b] = WmXRow{(float)(1.0 / (double)row_T[b]), (unsigned)row_seed[b], (unsigned)(row_seed[b] >> 32), 0u};
+            xp.sample = 1;
+        }
+    }
     WmRepPar rpar;
     WmSbPar sbpar;
     WmCstPar cpar;
@@ -2347,6 +2362,7 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
         WM_TRY(pool.get(&xd.all, nullptr, nt * 8, s, 0xff));
         WM_TRY(pool.get(&xd.ns_v, nullptr, (size_t)B * 4, s, 0xff));
         xd.logprob = dlp; xd.nospeech = dns;
+        if (row_T) WM_TRY(pool.get(&xd.ids, (const unsigned *)xrows.data(), xrows.size() * sizeof(WmXRow), s));
     }
     a.x = xd;
     WmStopDev sp;
@@ -2474,6 +2490,22 @@ extern "C" int wmdbg_decode_close_trunc(wm_ctx *ctx, wmdbg_step *io, int top_k, 
     WM_REQUIRE(io->n_suppress_first == 0 || (io->mask_first != 0) == (io->pos == io->n_prompt - 1), WM_ERR_INVALID,
                "wmdbg_decode_close_trunc: mask_first must say whether this is position n_prompt - 1");
     return decode_close_run(ctx, io, false, 1.f, 0, nullptr, nullptr, &sp);
+}
+extern "C" int wmdbg_decode_close_rows(wm_ctx *ctx, wmdbg_step *io, const float *row_T, const uint64_t *row_seed, int top_k,
+                                        float top_p, float min_p) {
+    WM_REQUIRE(io && row_T && row_seed, WM_ERR_INVALID, "wmdbg_decode_close_rows: null");
+    WM_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p < 1.f, WM_ERR_INVALID,
+               "wmdbg_decode_close_rows: top_k >= 0, top_p in (0, 1], min_p in [0, 1)");
+    WM_REQUIRE(io->x_on && io->B >= 1 && io->B <= WM_DEC_MAXB, WM_ERR_INVALID, "wmdbg_decode_close_rows: needs x_on and 1 .. %d rows", WM_DEC_MAXB);
+    const WmSampPar sp = {top_k, top_p, min_p};
+    bool any = false;
+    for (int b = 0; b < io->B; ++b) any = any || row_T[b] > 0.f;
+    // as the product: the truncation launch is in the plan when the rules are on and some row samples
+    const bool on = (top_k > 0 || top_p < 1.f || min_p > 0.f) && any;
+    if (on)
+        WM_REQUIRE(io->n_suppress_first == 0 || (io->mask_first != 0) == (io->pos == io->n_prompt - 1), WM_ERR_INVALID,
+                   "wmdbg_decode_close_rows: mask_first must say whether this is position n_prompt - 1");
+    return decode_close_run(ctx, io, false, 1.f, 0, nullptr, nullptr, on ? &sp : nullptr, nullptr, nullptr, row_T, row_seed);
 }
 extern "C" int wmdbg_decode_close_rep(wm_ctx *ctx, wmdbg_step *io, float penalty, int ngram) {
     return decode_close_run(ctx, io, true, penalty, ngram);

@@ -275,6 +275,12 @@ __device__ __forceinline__ void quad_words(const wm_philox4 &w, int k, unsigned 
     out = (k & 2) ? hi : lo;
 }
 
+// the value quad lane R holds, for every lane of the quad
+template <int R>
+__device__ __forceinline__ float quad_bcast(float x) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), R * 0x55, 0xf, 0xf, false));
+}
+
 // ---- the pieces of the logits epilogues (DE_LOGITS*), each stated ONCE.  The 16 lanes that share kq hold the 16 ids of the
 // tile for one batch row; their butterflies walk q = 1, 2, 4, 8.  (Which arm calls which, and why not all: DESIGN.md section 4.)
 // index of (row b, tile) in the per-tile arrays: tilemax, ts.key_ts, ts.lse, x.txt / x.win / x.all
@@ -328,10 +334,11 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
     const bool nvalid = n < p.N;
     const int nb = p.B - b0 < 16 ? p.B - b0 : 16;
     unsigned draw[4] = {0u, 0u, 0u, 0u};   // DE_LOGITS_X under sampling: the 32-bit draw of (row kq * 4 + r, id n)
+    float inv_t[4] = {0.f, 0.f, 0.f, 0.f};   // ... and the row's 1 / T: the call's, or the row's own (WmXPar::rows_on; 0: an arg-max row)
     if (de_is_x(EPI)) {
         const WmXPar xp = *p.x.par;
         const int gi = pos + 1 - xp.n_prompt;
-        if (xp.sample && gi >= 0) {   // wave-uniform (every lane active)
+        if (xp.sample && gi >= 0) {   // wave-uniform (every lane active); with a row table: some row of the call samples
             // ONE Philox call serves the four ids of a quad (lanes 4q .. 4q + 3 = ids 4 (n >> 2) .. + 3) for one row: lane j
             // of the quad runs the call of row kq * 4 + j, and DPP broadcasts hand every lane its word (n & 3) of each row's call
             const int j = nrow & 3;
@@ -339,11 +346,22 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             const int row = b0 + kq * 4 + j;   // (rows past the group's: their draws are never used)
             c.v[0] = (unsigned)n >> 2; c.v[1] = (unsigned)gi; c.v[2] = xp.ids_on ? p.x.ids[row] : (unsigned)(xp.chunk0 + row);
             c.v[3] = xp.n_cand > 1 ? p.x.ids[WM_XIDS_CAND + row] : 0u;   // the candidate word (best-of-N; 0 in every other call)
-            const wm_philox4 w = wm_philox4x32_10(c, xp.key0, xp.key1);
+            unsigned k0 = xp.key0, k1 = xp.key1;
+            float it = xp.inv_T;
+            if (xp.rows_on) {   // wave-uniform: the call of row kq * 4 + j takes that row's key (the table is padded like ids)
+                const WmXRow rw = wm_x_rows(p.x.ids)[row];
+                k0 = rw.key0; k1 = rw.key1; it = rw.inv_T;
+            }
+            const wm_philox4 w = wm_philox4x32_10(c, k0, k1);
             quad_words<0>(w, j, draw[0]);
             quad_words<1>(w, j, draw[1]);
             quad_words<2>(w, j, draw[2]);
             quad_words<3>(w, j, draw[3]);
+            // lane j holds 1 / T of row kq * 4 + j: one more broadcast per row (without a table: four copies of the call's)
+            inv_t[0] = quad_bcast<0>(it);
+            inv_t[1] = quad_bcast<1>(it);
+            inv_t[2] = quad_bcast<2>(it);
+            inv_t[3] = quad_bcast<3>(it);
         }
     }
 #pragma unroll
@@ -394,7 +412,9 @@ __device__ __forceinline__ void gemv_unit_epilogue(const DecGemvDev &p, const Ge
             const bool in_ts = ts_on && ok && in_ts_range(o.trng[r], n);
             const int gi = pos + 1 - xp.n_prompt;
             float sc = v;
-            if (xp.sample && gi >= 0) sc = __fmaf_rn(v, xp.inv_T, wm_gumbel_from_bits(draw[r]));
+            // (a row of a table whose 1 / T is zero is an arg-max row: its score is the logit, bit for bit the temperature-0 call's)
+            if (xp.sample && gi >= 0 && !(xp.rows_on && __float_as_uint(inv_t[r]) == 0u))
+                sc = __fmaf_rn(v, inv_t[r], wm_gumbel_from_bits(draw[r]));
             unsigned long long kt = in_text ? argmax_key(sc, n) : 0ull, ks = in_ts ? argmax_key(sc, n) : 0ull;
             float vt = v, vs = v;
             tile_key_max_carry(kt, vt, ks, vs);

@@ -82,7 +82,7 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc(m, (void **)&m->dsamp_par, sizeof(WmSampPar), s));
     WM_TRY(dalloc(m, (void **)&m->dalt_par, sizeof(WmAltPar), s));
     // (+16: the epilogue's padded 16-row blocks; second half: the rows' candidate words, WM_XIDS_CAND)
-    WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)2 * WM_XIDS_CAND, s));
+    WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)WM_XIDS_WORDS, s));   // (third part: the sampling rows, WM_XIDS_ROWS)
     WM_TRY(dalloc_t(m, &m->dmel_win, (size_t)WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dxkv_rows, (size_t)WM_DEC_MAXB, s));
     WM_TRY(dalloc_t(m, &m->dmask, (size_t)2 * (m->vpad / 32), s));

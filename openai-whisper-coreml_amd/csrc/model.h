@@ -92,7 +92,21 @@ struct WmXPar {
     int n_prompt;         // generated index gi = pos + 1 - n_prompt
     int ids_on;           // 1: row b's counter word is WmXDev::ids[b] (caller-given sample ids), not chunk0 + b
     int n_cand;           // > 1: a candidate group -- row b's FOURTH counter word is WmXDev::ids[WM_XIDS_CAND + b] (else 0)
+    // 1: temperature and seed are per row (wm_set_sampling_rows): inv_T, key0 and key1 above are not read,
+    // row b's are wm_x_rows(WmXDev::ids)[b]; `sample` then says "some row of the call samples"
+    int rows_on;
 };
+// a row's own sampling parameters (WmXPar::rows_on): one 16-byte load.  inv_T == 0 (all bits): an arg-max row, its key is not read
+struct WmXRow {
+    float inv_T;          // (float)(1.0 / (double)T), computed on the host
+    unsigned key0, key1;  // the row's seed (Philox key: low, high word)
+    unsigned pad;
+};
+// ... which live BEHIND the two halves of WmXDev::ids, so that WmXDev -- a member of every decode GEMV's argument struct -- keeps its
+// size and the kernels that never read the table keep their text: [WM_XIDS_CAND] rows, padded like the ids
+constexpr int WM_XIDS_ROWS = 2 * (128 + 16);   // in words of WmXDev::ids (a multiple of 4: the rows are 16-byte aligned)
+constexpr int WM_XIDS_WORDS = WM_XIDS_ROWS + 4 * (128 + 16);   // the whole buffer
+__host__ __device__ inline const WmXRow *wm_x_rows(const unsigned *ids) { return (const WmXRow *)(ids + WM_XIDS_ROWS); }
 constexpr int WM_XIDS_CAND = 128 + 16;   // WmXDev::ids: [WM_DEC_MAXB + 16] sample ids | [WM_DEC_MAXB + 16] candidate words
 
 // wm_transcribe_mel: row b's encoder input = frames seek .. seek + n - 1 of the [n_mels][T] block at mel + base, zeros after
@@ -103,6 +117,7 @@ struct WmMelWin {
 struct WmXDev {
     const WmXPar *par;    // null: X mode off
     const unsigned *ids;  // [>= WM_DEC_MAXB] per-row Philox counter words, read when par->ids_on (wm_transcribe_mel sample_ids)
+                          // (with par->rows_on: WM_XIDS_WORDS words, the rows' WmXRow table at WM_XIDS_ROWS -- wm_x_rows)
     float *txt;           // [B][n_tiles][2] (max, sum exp) over the tile's allowed TEXT ids (raw logits)
     float *win;           // [B][n_tiles][2] raw logit of the tile's winner: text, timestamp
     float *all;           // [B][n_tiles][2] (max, sum exp) over every id -- at pos == sot_pos only
@@ -370,6 +385,10 @@ struct WmDecodeMode {
     // A request for alternatives is served (wm_request_alternatives): the logits launch stores the f32 row and wm_alternatives
     // runs between it and the close (in front of wm_sample_truncate).  Needs x.
     bool alt = false;
+    // Temperature and seed are per row (wm_set_sampling_rows): the X-mode kernels read the rows' table behind WmModel::dx_ids.
+    // Needs x.  The table's contents are uploaded at prefill; the key holds the flag, so a group with a table and one without
+    // never share a captured graph.
+    bool srows = false;
     // Panel width of a teacher-forced pass (wm_set_teacher_panel; 1: none): the step's rows are windows x panel, row c * panel + s
     // is position *dpos + s of window c -- the self-attention cache holds one entry per WINDOW, row (c, s) appends at and reads up
     // to its own position, the cross-attention is the candidate-group launch (wm_model_panel_step).  The teacher-forced entries
@@ -383,7 +402,7 @@ struct WmDecodeMode {
     int acap_base = 0, acap_Tq = 0, acap_J = 0;
     float *acap_q = nullptr;
     bool operator==(const WmDecodeMode &o) const {
-        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && alt == o.alt && rep == o.rep && sb == o.sb && sbt == o.sbt && cst == o.cst && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && alt == o.alt && srows == o.srows && rep == o.rep && sb == o.sb && sbt == o.sbt && cst == o.cst && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -556,7 +575,12 @@ struct WmModel {
     int cst_states = 0, cst_edges = 0, cst_eot = 0;
     WmCstDev dcst = {};
     std::vector<int32_t> cst_rows_host;    // wm_set_constraint_rows: the start state of each row of the NEXT call (empty: none pending)
-    unsigned *dx_ids = nullptr;    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words
+    // wm_set_sampling_rows: temperature and seed of each row of the NEXT call (empty: none pending; the two have one length)
+    std::vector<float> samp_rows_T;
+    std::vector<uint64_t> samp_rows_seed;
+    // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words, and behind the two, at WM_XIDS_ROWS,
+    // [WM_XIDS_CAND] WmXRow: the rows' (1 / T, seed) of wm_set_sampling_rows (wm_x_rows), uploaded at prefill like the ids
+    unsigned *dx_ids = nullptr;
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     int *dxkv_rows = nullptr;      // [WM_DEC_MAXB] the group's rows of a window set (wm_transcribe_windows): the gather's row map
     // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..), the
@@ -775,6 +799,8 @@ int wm_enc_attention(wm_ctx *ctx, const bf16_t *qk, const bf16_t *vt, bf16_t *at
 static_assert(WM_MAX_TEACHER_PANEL == 8, "tx_plan.h WM_PANEL_MAX_WIDTH restates it");
 static_assert(WM_MAX_TEACHER_PANEL == WM_MAX_BEST_OF, "a panel's cross-attention is dec_xcand_attn_kernel: its instantiated widths");
 static_assert(WM_XIDS_CAND == WM_DEC_MAXB + 16, "WmXDev::ids: the candidate words follow the padded sample ids");
+static_assert(WM_XIDS_ROWS == 2 * WM_XIDS_CAND && WM_XIDS_ROWS % 4 == 0 && WM_XIDS_WORDS == WM_XIDS_ROWS + 4 * WM_XIDS_CAND && sizeof(WmXRow) == 16,
+              "WmXDev::ids: the sampling rows follow the candidate words, 16-byte aligned");
 constexpr int WM_NLIVE_RING = 16;  // pinned host slots for the per-burst live-row counts (early stop)
 constexpr int WM_MAXSPLIT = 8;  // stream partials of a (sequence, head) pair of the cross-attention (small batches)
 // (enum DecEpi: dec_launch.h)

@@ -256,6 +256,22 @@ extern "C" int wm_set_constraint_rows(wm_ctx *ctx, const int32_t *start_of_row, 
     m->cst_rows_host.assign(start_of_row, start_of_row + n);
     return WM_OK;
 } WM_API_CATCH
+extern "C" int wm_set_sampling_rows(wm_ctx *ctx, const float *temperature, const uint64_t *seed, int n) try {
+    WM_MODEL(ctx);
+    m->samp_rows_T.clear();   // whatever happens below, the map that was pending is gone
+    m->samp_rows_seed.clear();
+    WM_REQUIRE(n >= 0 && (n == 0 || (temperature && seed)), WM_ERR_INVALID, "set_sampling_rows: bad list");
+    for (int i = 0; i < n; ++i) {
+        const float T = temperature[i];
+        WM_REQUIRE(std::isfinite(T) && T >= 0.f, WM_ERR_INVALID, "set_sampling_rows: temperature of row %d must be finite and >= 0", i);
+        // (1 / T must be a finite f32 too: an infinite scale turns a zero logit's score into NaN)
+        WM_REQUIRE(T == 0.f || std::isfinite((float)(1.0 / (double)T)), WM_ERR_INVALID,
+                   "set_sampling_rows: temperature %g of row %d is too small: 1 / T overflows", (double)T, i);
+    }
+    m->samp_rows_T.assign(temperature, temperature + n);
+    m->samp_rows_seed.assign(seed, seed + n);
+    return WM_OK;
+} WM_API_CATCH
 extern "C" int wm_set_teacher_panel(wm_ctx *ctx, int width) try {
     WM_MODEL(ctx);
     (void)m;

@@ -224,6 +224,15 @@ extern "C" int wm_multi_transcribe_greedy(wm_multi *m, const void *pcm, wm_dtype
             if (m->ctx[r]->model && m->ctx[r]->model->alt_pending) { alt = true; m->ctx[r]->model->alt_pending = false; }
         WM_REQUIRE(!alt, WM_ERR_STATE, "multi_transcribe_greedy does not serve alternatives (wm_request_alternatives)");
     }
+    {   // a sampling row map pending on a device context likewise (wm_set_sampling_rows)
+        bool rows = false;
+        for (int r = 0; r < R; ++r)
+            if (m->ctx[r]->model && !m->ctx[r]->model->samp_rows_T.empty()) {
+                rows = true;
+                m->ctx[r]->model->samp_rows_T.clear(); m->ctx[r]->model->samp_rows_seed.clear();
+            }
+        WM_REQUIRE(!rows, WM_ERR_STATE, "multi_transcribe_greedy takes no sampling row map (wm_set_sampling_rows)");
+    }
     {   // every size that feeds an allocation below is checked against the model BEFORE any thread exists
         const wm_dims &D = m->ctx[0]->model->dims;
         WM_REQUIRE(n_prompt >= 1 && n_prompt + max_new <= D.n_text_ctx, WM_ERR_INVALID,

@@ -234,6 +234,14 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
     if (dbg && threadIdx.x == 0) { dbg[b * 3] = 0; dbg[b * 3 + 1] = -1; dbg[b * 3 + 2] = -1; }
     // workgroup-uniform: a prompt position, an arg-max call, a row that is done (a window that has left: its rows are done)
     if (gi < 0 || !xp.sample || (done && done[b])) return;
+    // the row's own 1 / T and key under a row table (wm_set_sampling_rows); an arg-max row of it is left alone (uniform)
+    float inv_T = xp.inv_T;
+    unsigned key0 = xp.key0, key1 = xp.key1;
+    if (xp.rows_on) {
+        const WmXRow rw = wm_x_rows(xd.ids)[b];
+        inv_T = rw.inv_T; key0 = rw.key0; key1 = rw.key1;
+        if (__float_as_uint(inv_T) == 0u) return;
+    }
     const long rb = (long)b * n_tiles;
     // `forced` (the sum rule) and the best value of A, from the partials: beam_topk_kernel's steps
     lse_row_segments(xd, rb, n_tiles, false, wave, 16, lane, seg_s);
@@ -272,7 +280,7 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
     r.mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
     r.brow = ban ? ban + (long)b * ban_words : nullptr;
     r.vmax = vmax_s;
-    r.inv_T = xp.inv_T;
+    r.inv_T = inv_T;
     // the cut
     unsigned long long cut = 1ull;   // every key of A is at or above it
     const bool p_on = sp.top_p < 1.f;
@@ -332,10 +340,10 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
                 if (!have) {
                     wm_philox4 c;
                     c.v[0] = (unsigned)q; c.v[1] = (unsigned)gi; c.v[2] = cw2; c.v[3] = cw3;
-                    w = wm_philox4x32_10(c, xp.key0, xp.key1);
+                    w = wm_philox4x32_10(c, key0, key1);
                     have = true;
                 }
-                const float sc = __fmaf_rn(v, xp.inv_T, wm_gumbel_from_bits(wm_philox_word(w, (unsigned)j)));
+                const float sc = __fmaf_rn(v, inv_T, wm_gumbel_from_bits(wm_philox_word(w, (unsigned)j)));
                 const unsigned long long sk = argmax_key(sc, n);
                 if (sk > best) { best = sk; best_v = v; }
                 low = k < low ? k : low;

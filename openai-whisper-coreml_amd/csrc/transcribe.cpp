@@ -93,6 +93,7 @@ struct LaneJob {
     WmXPar xpar = {};              // the group's extended-decode parameters (source of an async upload: lives here)
     WmRepPar rpar = {};            // its repetition rules (likewise)
     WmSampPar spar = {};           // its sampling rules (likewise)
+    std::vector<WmXRow> samp;      // its rows' temperatures and seeds, padded (wm_set_sampling_rows; likewise)
     WmSbPar sbpar = {};            // its sequence-bias table's counts (likewise)
     WmAltPar apar = {};            // its alternatives request: n and the lane's buffers (likewise)
     WmCstPar cpar = {};            // its constraint automaton's counts (likewise)
@@ -125,6 +126,7 @@ struct LaneJob {
 // (arg-max / sampling, best_of candidates, beams) and where the results go.
 struct TxCall {
     enum Entry { PLAIN, MEL, RAGGED, BEST_OF, BEAM } entry = PLAIN;   // whose own checks run first
+    bool greedy_entry = false;   // wm_transcribe_greedy: no options, so no per-row ones either (wm_set_sampling_rows is refused)
     WmAudioSrc src;
     TxPrompts prompts;
     int n_prompt = 0;   // the prompt length of a uniform call (a ragged call: TxCfg::n_prompt, found by validation)
@@ -187,6 +189,10 @@ struct TxCfg {
     const wm_alternatives_out *alt = nullptr;   // the call's alternatives request (wm_request_alternatives), checked; null: none
     // a constraint in force: the start state of each row of the call [B] (wm_set_constraint_rows), checked; null: every row starts in 0
     const int32_t *cst_rows = nullptr;
+    // a sampling row map in force (wm_set_sampling_rows) with at least one sampling row: temperature and seed of each row of the
+    // call [B], checked; null: opts->temperature and opts->seed hold for every row
+    const float *samp_T = nullptr;
+    const uint64_t *samp_seed = nullptr;
 };
 
 // the tokens row `b` of the call may generate
@@ -212,6 +218,7 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     // (tx_validate turns the extended decode on with them; the bias and the constraint use the rules' bitmaps)
     j.mode.rep = m->rep_on || j.mode.sb || j.mode.cst;
     j.mode.trunc = m->samp_on() && xc.on && xc.par.sample != 0;   // temperature 0 ignores the sampling rules: today's launches
+    j.mode.srows = xc.on && cfg.samp_T != nullptr;   // (a row map: the launch is in the plan when any row of the CALL samples)
     j.mode.alt = cfg.alt != nullptr;   // (tx_validate turned the extended decode on with it)
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
@@ -255,6 +262,15 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
         j.xpar.ids_on = (call.prompts.sample_ids || N > 1) ? 1 : 0;
         j.xpar.n_cand = N;
         if (!j.tab.ids.empty()) WM_HIP(hipMemcpyAsync(m->dx_ids, j.tab.ids.data(), j.tab.ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+        if (j.mode.srows) {   // the rows' own 1 / T and keys, padded with arg-max rows like the ids (the epilogue's 16-row blocks)
+            j.samp.assign(WM_XIDS_CAND, WmXRow{0.f, 0u, 0u, 0u});
+            for (int r = 0; r < Bg; ++r) {
+                const float T = cfg.samp_T[j.b0 + r / N];
+                const uint64_t seed = cfg.samp_seed[j.b0 + r / N];
+                if (T > 0.f) j.samp[r] = WmXRow{(float)(1.0 / (double)T), (unsigned)seed, (unsigned)(seed >> 32), 0u};
+            }
+            WM_HIP(hipMemcpyAsync((void *)wm_x_rows(m->dx_ids), j.samp.data(), j.samp.size() * sizeof(WmXRow), hipMemcpyHostToDevice, c->stream));
+        }
         WM_HIP(hipMemcpyAsync(m->dx_par, &j.xpar, sizeof(WmXPar), hipMemcpyHostToDevice, c->stream));
     }
 
@@ -557,7 +573,8 @@ int entry_checks(const TxCall &call) {
 // extended decode.  budgets: the call's (wm_set_token_budgets), clamped to max_new here.  opts == null with both extra
 // outputs null is the greedy decode exactly.
 int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg, const std::vector<int32_t> *bias_rows = nullptr,
-                const wm_alternatives_out *alt = nullptr, const std::vector<int32_t> *cst_rows = nullptr) {
+                const wm_alternatives_out *alt = nullptr, const std::vector<int32_t> *cst_rows = nullptr,
+                const std::vector<float> *samp_T = nullptr, const std::vector<uint64_t> *samp_seed = nullptr) {
     WmModel *m = ctx->model;
     const WmAudioSrc &src = call.src;
     const TxPrompts &p = call.prompts;
@@ -612,8 +629,19 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     WM_REQUIRE(ns_tok >= -1 && ns_tok < D.n_vocab, WM_ERR_INVALID, "no_speech_token %d outside the vocabulary", ns_tok);
     WM_REQUIRE(!call.no_speech_out || ns_tok >= 0, WM_ERR_INVALID, "no_speech_prob_out needs opts->no_speech_token");
     WM_REQUIRE(!call.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
+    // the call's sampling row map (wm_set_sampling_rows checked the values): opts->temperature and opts->seed are validated above
+    // and not read below.  A map without a sampling row is the temperature-0 call.
+    const bool rows_map = samp_T != nullptr;
+    bool sampling = T > 0.f;
+    if (rows_map) {
+        WM_REQUIRE((int)samp_T->size() == B && samp_seed && samp_seed->size() == samp_T->size(), WM_ERR_INVALID,
+                   "the sampling row map was set for %d rows, the call has %d", (int)samp_T->size(), B);
+        sampling = false;
+        for (int b = 0; b < B; ++b) sampling = sampling || (*samp_T)[b] > 0.f;
+        if (sampling) { cfg->samp_T = samp_T->data(); cfg->samp_seed = samp_seed->data(); }
+    }
     // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
-    xc.on = T > 0.f || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || m->cst_on || alt;
+    xc.on = sampling || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || m->cst_on || alt;
     if (alt) {   // the call's alternatives request (wm_request_alternatives checked n and the pointers)
         WM_REQUIRE(!call.beam, WM_ERR_STATE, "alternatives are not served by beam-search calls");
         WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "alternatives are not supported by the all-f32 precision path");
@@ -624,7 +652,7 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     }
     WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
     WM_REQUIRE(!(m->sb_on || m->sbt_on) || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
-    WM_REQUIRE(!(m->samp_on() && T > 0.f) || !ctx->dbg_hooks, WM_ERR_STATE, "the sampling rules are not supported by the all-f32 precision path");
+    WM_REQUIRE(!(m->samp_on() && sampling) || !ctx->dbg_hooks, WM_ERR_STATE, "the sampling rules are not supported by the all-f32 precision path");
     if (m->sbt_on) {   // row tables: the call's row map (wm_set_bias_rows), one entry per row of the call
         WM_REQUIRE(bias_rows, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
         WM_REQUIRE((int)bias_rows->size() == B, WM_ERR_INVALID, "the bias row map was set for %d rows, the call has %d", (int)bias_rows->size(), B);
@@ -644,11 +672,12 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     }
     xc.logprobs = call.logprobs_out;
     xc.no_speech = call.no_speech_out;
-    const uint64_t seed = opts ? opts->seed : 0;
+    const uint64_t seed = (opts && !rows_map) ? opts->seed : 0;
     xc.par.key0 = (unsigned)seed;
     xc.par.key1 = (unsigned)(seed >> 32);
-    xc.par.sample = T > 0.f ? 1 : 0;
-    xc.par.inv_T = T > 0.f ? (float)(1.0 / (double)T) : 0.f;
+    xc.par.sample = sampling ? 1 : 0;
+    xc.par.inv_T = (T > 0.f && !rows_map) ? (float)(1.0 / (double)T) : 0.f;
+    xc.par.rows_on = cfg->samp_T ? 1 : 0;   // the rows' own 1 / T and keys: behind WmXDev::ids (lane_prefill)
     xc.par.sot_pos = call.no_speech_out ? sot_index : -1;
     xc.par.ns_tok = ns_tok;
     const bool no_stop = g_wm_tuning.no_early_stop != 0;   // probes only: decode every position, truncate on the host
@@ -1047,6 +1076,18 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
     wm_alternatives_out alt_req = {};
     bool alt_on = false;
     if (ctx && ctx->model) { alt_on = ctx->model->alt_pending; alt_req = ctx->model->alt_req; ctx->model->alt_pending = false; }
+    // ... and the temperature and seed of its rows (wm_set_sampling_rows)
+    std::vector<float> samp_T;
+    std::vector<uint64_t> samp_seed;
+    if (ctx && ctx->model) { samp_T.swap(ctx->model->samp_rows_T); samp_seed.swap(ctx->model->samp_rows_seed); }
+    if (!samp_T.empty()) {   // served by the plain, mel, ragged, window-set and aligned entries
+        WM_REQUIRE(!call.greedy_entry, WM_ERR_STATE, "wm_transcribe_greedy takes no sampling row map (wm_set_sampling_rows)");
+        // (wm_transcribe_windows is the best-of entry of a window set: one sample per row is the plain call)
+        const bool one_sample = call.entry == TxCall::BEST_OF && call.src.windows && call.n_cand == 1 && !call.hyp;
+        WM_REQUIRE((call.entry != TxCall::BEST_OF && call.entry != TxCall::BEAM) || one_sample, WM_ERR_STATE,
+                   "best-of and beam-search calls take no sampling row map (wm_set_sampling_rows)");
+        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "a sampling row map is not supported by the all-f32 precision path");
+    }
     WM_TRY(entry_checks(call));
     WM_MODEL(ctx);
     std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
@@ -1056,7 +1097,7 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
     }
     TxCfg cfg;
     WM_TRY(tx_validate(ctx, call, budgets, &cfg, bias_rows.empty() ? nullptr : &bias_rows, alt_on ? &alt_req : nullptr,
-                       cst_rows.empty() ? nullptr : &cst_rows));
+                       cst_rows.empty() ? nullptr : &cst_rows, samp_T.empty() ? nullptr : &samp_T, samp_T.empty() ? nullptr : &samp_seed));
     // the plan: decode groups and lanes.  A masked clone that cannot be made switches the masks off and asks again.
     WmTxPlanIn pin;
     pin.B = call.B; pin.N = call.n_cand;
@@ -1283,6 +1324,11 @@ int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
     if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
     if (ctx && ctx->model) ctx->model->bias_rows_host.clear();   // a pending row map likewise
     if (ctx && ctx->model) ctx->model->cst_rows_host.clear();    // ... and the constraint's
+    bool samp_rows = false;   // ... and a sampling row map, which this call refuses below (it verifies the greedy choice)
+    if (ctx && ctx->model) {
+        samp_rows = !ctx->model->samp_rows_T.empty();
+        ctx->model->samp_rows_T.clear(); ctx->model->samp_rows_seed.clear();
+    }
     bool alt_on = false;   // ... and a request for alternatives, which this call refuses below
     if (ctx && ctx->model) { alt_on = ctx->model->alt_pending; ctx->model->alt_pending = false; }
     const int32_t *dbg_script = nullptr;   // the debug library's script is for this call only
@@ -1295,6 +1341,7 @@ int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
     WM_MODEL(ctx);
     WM_TRY(spec_checks(ctx, sc, call));
     WM_REQUIRE(!alt_on, WM_ERR_STATE, "alternatives are not served by speculative decoding");
+    WM_REQUIRE(!samp_rows, WM_ERR_STATE, "speculative decoding takes no sampling row map (wm_set_sampling_rows)");
     TxCfg cfg;
     WM_TRY(tx_validate(ctx, call, budgets, &cfg));
     WM_REQUIRE(!dbg_script || (m->spec_dbg_script_new == call.max_new && m->spec_dbg_script_rows == call.B), WM_ERR_INVALID,
@@ -1323,6 +1370,7 @@ extern "C" int wm_transcribe_greedy(wm_ctx *ctx, const void *pcm, wm_dtype pcm_d
     call.src.pcm = pcm; call.src.pcm_dtype = pcm_dtype; call.mem = mem;
     call.prompts.prompt = prompt; call.n_prompt = n_prompt;
     outputs(call, B, max_new, eot, nullptr, tokens_out, lens_out, nullptr, nullptr);
+    call.greedy_entry = true;
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
 

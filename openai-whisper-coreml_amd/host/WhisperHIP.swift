@@ -287,6 +287,16 @@ struct Whisper {
         try check(f(ctx, tableOfRow.isEmpty ? nil : tableOfRow, Int32(tableOfRow.count)))
     }
 
+    /// Temperature and seed of every row of the NEXT transcribe call on this context (wm_set_sampling_rows; one entry per row of
+    /// that call, consumed by it): the call's own temperature and seed are then not read; temperature 0 is an arg-max row.
+    /// Empty arrays drop a pending map.  Not compiled in this repository (see the top of the file).
+    func setSamplingRows(temperatures: [Float], seeds: [UInt64]) throws {
+        typealias RowsFn = @convention(c) (OpaquePointer, UnsafePointer<Float>?, UnsafePointer<UInt64>?, Int32) -> Int32
+        precondition(temperatures.count == seeds.count)
+        let f: RowsFn = try sym("wm_set_sampling_rows")
+        try check(f(ctx, temperatures.isEmpty ? nil : temperatures, seeds.isEmpty ? nil : seeds, Int32(temperatures.count)))
+    }
+
     /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
     /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
     /// Not compiled in this repository (see the top of the file).

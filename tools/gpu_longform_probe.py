@@ -5,7 +5,8 @@ given as argv[1] (default base), every matrix scaled by weights.lively_gain so t
 length (argv[2], default 8: 10 .. 150 s), the production vocabulary's token ids, text context n_text_ctx.  Prints one JSON
 line: wall seconds and audio-s/s of both, windows decoded and fallback steps taken by the long form.
 
-    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --prompt-panel W | --words [--teacher-panel W] [--decode] | --reuse]
+    python tools/gpu_longform_probe.py [model] [recordings] [--condition | --prompt-panel W | --words [--teacher-panel W] [--decode] | --reuse
+                                                            | --fallback {lockstep,deferred} [--fallback-share S] | --rows-position]
 
 --condition: the cost of condition_on_previous_text instead.  One more JSON line: wall seconds of the long form with
 conditioning off and on (the same recordings, after a warm-up of each; with the default fallback thresholds and with the
@@ -41,7 +42,22 @@ interleaved, three runs each after a warm-up of each; the two runs' results are 
 configuration: wall seconds, the wm_last_stage_ms splits summed over the calls of one run (off: staging, encoder + cross
 K/V, decode of every wm_transcribe_mel call and the encoder part of every wm_align_mel call; on: the wm_windows_encode
 calls and, per reading call, the copy from the set), the copy in GB/s (bytes read + bytes written) and per window next to
-the encoder + cross-K/V cost per window of the off run."""
+the encoder + cross-K/V cost per window of the off run.
+
+--fallback {lockstep,deferred}: the temperature-fallback loop instead.  The synthetic model fails the
+log-prob test on EVERY window, so --fallback-share S (default 1.0: the default thresholds, every window runs all six
+temperatures) makes only a share fall back: a calibration run at temperature 0 without thresholds gives every window's
+avg_logprob, and logprob_threshold is their S-quantile (the compression-ratio test is off).  The share is a stand-in for a real
+checkpoint's, which nobody has measured here.  lockstep: three runs after a warm-up.  deferred: lockstep and deferred alternating,
+three runs each after a warm-up of each, their results asserted equal (round numbers aside).  One JSON line: per variant the
+wall seconds of every run, rounds (counted in the loop), decode calls, decode positions stepped (per call: its prompt positions + its longest generated
+row) and rows x positions, plus the windows and the share that fell back.
+
+--rows-position: the cost of one X-mode decode position with a sampling row map against without one (wm_set_sampling_rows), ONE
+uniform group of `recordings` rows, 64 new tokens, eot off, alternating, best of 4: a sampling call at temperature 0.8, the same
+call under a map of that pair for every row, under a map of mixed temperatures (0, 0.8, 0, 1.0 ...), and the three again with the
+sampling rules (50, 0.9, 0) on.  One JSON line: ms per position (wm_last_stage_ms[2] / positions), and from one profiled call per
+variant (eager launches, a HIP event pair round every launch) the mean us of the logits launch and of the truncation launch."""
 import json
 import os
 import sys
@@ -68,7 +84,20 @@ if "--teacher-panel" in sys.argv:
     i = sys.argv.index("--teacher-panel")
     PANEL = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
-argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words", "--reuse", "--decode")]
+FALLBACK = None
+if "--fallback" in sys.argv:
+    i = sys.argv.index("--fallback")
+    FALLBACK = sys.argv[i + 1]
+    if FALLBACK not in ("lockstep", "deferred"):
+        sys.exit("--fallback: lockstep or deferred")
+    del sys.argv[i:i + 2]
+SHARE = 1.0
+if "--fallback-share" in sys.argv:
+    i = sys.argv.index("--fallback-share")
+    SHARE = float(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+ROWS_POSITION = "--rows-position" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--condition", "--words", "--reuse", "--decode", "--rows-position")]
 name = argv[0] if len(argv) > 0 else "base"
 N = int(argv[1]) if len(argv) > 1 else 8
 dims = dict(b.MODEL_DIMS[name])
@@ -394,6 +423,103 @@ def reuse_probe():
         print(json.dumps(res), flush=True)
 
 
+def fallback_probe():
+    calls = []
+    inner = ctx.transcribe_mel
+
+    def counted(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, **k):
+        r = inner(mel, mel_base, mel_len, seek, n_frames, prompts, max_new, **k)
+        calls.append((len(prompts), max(len(p) for p in prompts) + int(r.lens.max())))
+        return r
+    ctx.transcribe_mel = counted
+    rounds = []
+    round_rows = b._RoundRows
+
+    class CountedRound(round_rows):   # one row source per round: the loop's own count, whatever parallel_clips bounds
+        def __init__(self, *a, **k):
+            rounds.append(1)
+            round_rows.__init__(self, *a, **k)
+    b._RoundRows = CountedRound
+    extra = {}
+    if SHARE < 1.0:   # a calibration run: the S-quantile of the temperature-0 avg_logprob of every window
+        cal = ctx.transcribe_long(recs, temperatures=(0.0,), logprob_threshold=None, compression_ratio_threshold=None,
+                                  no_speech_threshold=None, **kw)
+        lps = [sg["avg_logprob"] for o in cal for sg in {g["seek"]: g for g in o["segments"]}.values()]
+        extra = dict(logprob_threshold=float(np.quantile(lps, SHARE)), compression_ratio_threshold=None, no_speech_threshold=None)
+    modes = ["lockstep"] if FALLBACK == "lockstep" else ["lockstep", "deferred"]
+    res = {m: dict(wall_s=[]) for m in modes}
+    outs = {}
+    for m in modes:
+        ctx.transcribe_long(recs, fallback=m, **kw, **extra)     # warm-up of each
+    for _ in range(3):
+        for m in modes:
+            del calls[:]
+            del rounds[:]
+            t0 = time.perf_counter()
+            outs[m] = ctx.transcribe_long(recs, fallback=m, **kw, **extra)
+            res[m]["wall_s"].append(time.perf_counter() - t0)
+            res[m].update(rounds=len(rounds), decode_calls=len(calls), positions_stepped=sum(c[1] for c in calls),
+                          row_positions=sum(c[0] * c[1] for c in calls))
+    for m in modes:
+        res[m]["median_wall_s"] = float(np.median(res[m]["wall_s"]))
+        res[m]["audio_s_per_s"] = audio_s / res[m]["median_wall_s"]
+    ctx.transcribe_mel = inner
+    b._RoundRows = round_rows
+    strip = lambda out: [dict(o, windows=[{k: v for k, v in w.items() if k != "round"} for w in o["windows"]]) for o in out]  # noqa: E731
+    if len(modes) == 2:
+        assert strip(outs["lockstep"]) == strip(outs["deferred"])
+        res["deferred_over_lockstep"] = res["deferred"]["median_wall_s"] / res["lockstep"]["median_wall_s"]
+    temps = [w["temperatures"] for o in outs["lockstep"] for w in o["windows"]]
+    print(json.dumps(dict(model=name, recordings=N, audio_s=audio_s, share_asked=SHARE, thresholds=extra, windows=len(temps),
+                          windows_fell_back=sum(len(t) > 1 for t in temps), attempts=sum(len(t) for t in temps), **res)))
+
+
+def rows_position_probe():
+    P, new = 3, 64
+    d_mel, offs, T = ctx.logmel_long(recs, n_mels=dims["n_mels"], device=True)
+    rows = list(range(N))
+    mixed = [(0.0, 0.8, 0.0, 1.0)[i % 4] for i in rows]
+    variants = (("scalar", {}), ("map_one_pair", dict(row_temperatures=[0.8] * N, row_seeds=[5] * N)),
+                ("map_mixed", dict(row_temperatures=mixed, row_seeds=[5 + i for i in rows])))
+    out, profile = {}, {}
+    try:
+        for rules in (False, True):
+            if rules:
+                ctx.set_sampling_rules(50, 0.9, 0.0)
+            best = {}
+            for _ in range(4):
+                for label, k in variants:
+                    ctx.transcribe_mel(d_mel, offs[rows], T[rows], 0, [min(3000, int(t) - 3000) for t in T[rows]],
+                                       [SOT, 50259, TASK], new, eot=-1, no_speech_token=NS, temperature=0.8, seed=5,
+                                       mem=b.WM_MEM_DEVICE, **k)
+                    ms = float(ctx.last_stage_ms()[2]) / (P + new - 1)
+                    best[label] = ms if label not in best else min(best[label], ms)
+            out["rules_on" if rules else "rules_off"] = best
+            # per-launch HIP-event times of the two launches that read the table (eager launches: every launch bracketed by events)
+            ctx.profile_enable(True)
+            fam = {}
+            for label, k in variants:
+                for _ in range(2):
+                    ctx.profile_reset()
+                    ctx.transcribe_mel(d_mel, offs[rows], T[rows], 0, [min(3000, int(t) - 3000) for t in T[rows]],
+                                       [SOT, 50259, TASK], new, eot=-1, no_speech_token=NS, temperature=0.8, seed=5,
+                                       mem=b.WM_MEM_DEVICE, **k)
+                fam[label] = {q: round(v["ms"] / v["n"] * 1e3, 2) for q, v in ctx.profile().items()
+                              if isinstance(v, dict) and v.get("n") and ("logits" in q or "sample_trunc" in q)}
+            ctx.profile_enable(False)
+            profile["rules_on" if rules else "rules_off"] = fam
+    finally:
+        ctx.set_sampling_rules()
+        ctx.dev_free(d_mel)
+    print(json.dumps(dict(model=name, rows=N, positions=P + new - 1, decode_ms_per_position=out, profile_us_per_launch=profile)))
+
+
+if FALLBACK is not None:
+    fallback_probe()
+    sys.exit(0)
+if ROWS_POSITION:
+    rows_position_probe()
+    sys.exit(0)
 if CONDITION:
     condition_probe()
     sys.exit(0)
