@@ -1007,6 +1007,49 @@ WM_API int wm_resample_filter(int sample_rate, float *h, size_t cap, int *L, int
 WM_API int wm_resample_16k(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *elem_offsets,
                            const int32_t *n_channels, const int32_t *sample_rates, int R, float *out, wm_mem mem);
 
+/* ------------------------------------------------ multichannel audio: channel matrix, per-channel activity --- */
+/* wm_resample_16k with a CHANNEL MATRIX in place of the mean: recording r yields n_rows[r] output
+ * signals, signal (r, o) being the resampling of the recording mixed down under row o of its matrix.  The mixed sample of
+ * a frame x[0 .. C - 1] under a row w[0 .. C - 1], stated once:
+ *     m = w[0] * x[0]                          (one f32 rounding)
+ *     m = fmaf(w[c], x[c], m),  c = 1 .. C-1   (channel order)
+ * x is s / 32768 for WM_I16 and the sample itself for WM_F32.  Behind the mix the filter is wm_resample_16k's, unchanged: the
+ * same phase tables per rate, ONE f32 fma chain per output over its taps in ascending input order, and at 16000 Hz the
+ * bypass, which writes m itself.
+ *   pcm, pcm_dtype, elem_offsets, n_channels, sample_rates, R, mem, the supported rates: exactly as wm_resample_16k;
+ *   n_rows : i32 [R] (host), 1 .. 8: the output signals of recording r; their sum is at most 65535;
+ *   mix    : f32 (host): row o of recording r is n_channels[r] finite weights; the rows lie back to back in (r, o) order;
+ *   out    : f32, signal (r, o)'s wm_resample_out_len(frames_r, sample_rates[r]) samples, the signals back to back in (r, o)
+ *            order -- the pcm / sample_offsets layout of wm_logmel_long(..., WM_F32, ...) with sum(n_rows) recordings; same `mem`.
+ * A signal's bits depend on its own recording, rate and row only: not on the other rows or their order, the other
+ * recordings, the offset, the tile or the grid.  A one-hot row c equals wm_resample_16k on channel c as a mono recording
+ * (bit for bit behind a filter; at 16000 Hz as values: a -0.0 sample of a recording of two or more channels may come out
+ * +0.0), and for WM_I16 stereo the row (0.5, 0.5) equals wm_resample_16k's mean bit for bit.  One launch, one workgroup per
+ * (signal, tile of 1024 outputs), each reading the interleaved span of its tile; the tile limit, the return after the launch
+ * and the front-end-only context are wm_resample_16k's.  Profile family: "resample_mix".  Invalid: everything wm_resample_16k
+ * rejects, n_rows outside 1 .. 8, more than 65535 signals, a weight that is not finite, a null n_rows or mix with R > 0. */
+WM_API int wm_resample_16k_mix(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *elem_offsets,
+                               const int32_t *n_channels, const int32_t *sample_rates, int R, const int32_t *n_rows,
+                               const float *mix, float *out, wm_mem mem);
+/* Per-channel activity: the level of S 16 kHz f32 signals (wm_resample_16k_mix's output, where it lies), one value per mel
+ * frame of 10 ms.  Signal s = pcm16k[sample_offsets[s] .. sample_offsets[s + 1]) of N_s samples y gets ceil(N_s /
+ * WM_ACTIVITY_HOP) values, the signals' values packed back to back in signal order:
+ *     act[f] = sum |y[160 f + i]|   over i < 160 with 160 f + i < N_s        (f32)
+ * in THIS order, a function of the frame alone:
+ *     p[j] = ((|y[160 f + j]| + |y[160 f + 16 + j]|) + ...) + |y[160 f + 144 + j]|    j = 0 .. 15; ten terms, ascending; a term
+ *                                                                                    past N_s is +0
+ *     q[j] = p[j] + p[j + 8],  r[j] = q[j] + q[j + 4],  t[j] = r[j] + r[j + 2],  act[f] = t[0] + t[1]
+ * so a signal's values are bit-identical alone, among other signals and at any offset; a NaN sample makes its frame NaN and
+ * no other.  The terms are non-negative: |act - exact| <= 160 * 2^-24 * exact.
+ *   pcm16k : f32, mem-space selectable (with WM_MEM_HOST only pcm16k[sample_offsets[0] .. sample_offsets[S]) is copied);
+ *   sample_offsets : i64 [S + 1] (host), >= 0 and non-decreasing; S : 0 .. 65535; empty signals are legal (no value);
+ *   act_out : f32, same `mem`.
+ * A front-end-only context is enough.  One launch, one workgroup per (signal, tile of 64 frames); returns when the launch has
+ * finished (per-call tables, as wm_resample_16k); at most 2^24 - 1 tiles per call.  Profile family: "channel_activity".
+ * Invalid: negative or decreasing offsets, null pointers with S > 0. */
+#define WM_ACTIVITY_HOP 160   /* one value per mel frame: 10 ms */
+WM_API int wm_channel_activity(wm_ctx *ctx, const float *pcm16k, const int64_t *sample_offsets, int S, float *act_out, wm_mem mem);
+
 /* ------------------------------------------------ general RIFF/WAVE reader (host only) --- */
 /* Beside wm_wav_* (which keeps its strict 16 kHz mono 16-bit rule): any rate, 1 .. 8 channels; integer PCM (format 1) at
  * 8 bits (unsigned, (s - 128) / 128), 16 (s / 2^15), 24 (s / 2^23) and 32 (s / 2^31, computed in double, rounded once);

@@ -167,6 +167,8 @@ def load_library(path=None):
         "wm_wav_read_chunks": [vp, ip, ip, vp],
         "wm_resample_filter": [ip, vp, sz, vp, vp, vp],
         "wm_resample_16k": [vp, vp, ip, vp, vp, vp, ip, vp, ip],
+        "wm_resample_16k_mix": [vp, vp, ip, vp, vp, vp, ip, vp, vp, vp, ip],
+        "wm_channel_activity": [vp, vp, vp, ip, vp, ip],
         "wm_vad_energy": [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip],
         "wm_vad_segments": [vp, ctypes.c_int64, vp, vp, ip, vp, vp],
         "wm_audio_open": [ctypes.c_char_p, pp],
@@ -837,6 +839,134 @@ def _pack_interleaved(recordings, sample_rates):
     return pcm, offs, ch, np.array([int(x) for x in sample_rates], dtype=np.int32)
 
 
+# ---- multichannel audio: channel matrices, per-channel activity, the speaker of a span -------------
+ACTIVITY_HOP = 160            # WM_ACTIVITY_HOP: samples per activity value, one mel frame
+
+
+def channel_rows(kind, C):
+    """A channel matrix f32 [n_rows][C] for Context.resample_16k_mix.  "split": the identity, one signal per channel;
+    "mean": one row of float32(1.0 / C); an int c: the one-hot row of channel c."""
+    C = int(C)
+    if C < 1:
+        raise ValueError("channel_rows: C >= 1")
+    if isinstance(kind, str):
+        if kind == "split":
+            return np.eye(C, dtype=np.float32)
+        if kind == "mean":
+            return np.full((1, C), np.float32(1.0 / C), dtype=np.float32)
+        raise ValueError("channel_rows: 'split', 'mean' or a channel index, got %r" % (kind,))
+    if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or not 0 <= kind < C:
+        raise ValueError("channel_rows: 'split', 'mean' or a channel index 0 .. %d, got %r" % (C - 1, kind))
+    row = np.zeros((1, C), dtype=np.float32)
+    row[0, int(kind)] = 1.0
+    return row
+
+
+def _channel_ratio(ratio):
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.integer, np.floating)) or not math.isfinite(ratio) or ratio < 1:
+        raise ValueError("channel ratio: a finite number >= 1, got %r" % (ratio,))
+    return float(ratio)
+
+
+def speaker_by_channel(act, start, end, ratio=1.1):
+    """whisper.cpp's stereo --diarize rule for C channels.  act [C][F]: the channels' activity per 10 ms frame
+    (Context.channel_activity); [start, end): seconds.  The frames [floor(start * 100), ceil(end * 100)), cut to [0, F), are
+    summed per channel in f64; best = the first maximal channel; returns best when its sum is > 0 and strictly greater than
+    ratio times the largest other sum, else None -- also with fewer than 2 channels, an empty span or a NaN sum.  ratio:
+    finite and >= 1 (ValueError)."""
+    ratio = _channel_ratio(ratio)
+    C = len(act)
+    if C < 2:
+        return None
+    F = min(len(a) for a in act)
+    a, b = max(int(math.floor(start * 100.0)), 0), min(int(math.ceil(end * 100.0)), F)
+    if a >= b:
+        return None
+    sums = [float(np.sum(np.asarray(ch[a:b], dtype=np.float64))) for ch in act]
+    if any(s != s for s in sums):
+        return None
+    best = int(np.argmax(sums))   # (the first maximum)
+    other = max(s for c, s in enumerate(sums) if c != best)
+    return best if sums[best] > 0 and sums[best] > ratio * other else None
+
+
+def _pack_mix(mix, ch):
+    """The matrices of resample_16k_mix -- one [n_rows][C_r] per recording -- as (n_rows i32 [R], the rows back to back f32)."""
+    if len(mix) != len(ch):
+        raise ValueError("mix: one [n_rows][C] matrix per recording")
+    mats = [np.asarray(m, dtype=np.float32) for m in mix]
+    for r, m in enumerate(mats):
+        if m.ndim != 2 or m.shape[1] != int(ch[r]) or not 1 <= m.shape[0] <= 8:
+            raise ValueError("mix: recording %d needs [1 .. 8][%d] weights, got %r" % (r, int(ch[r]), m.shape))
+        if not np.all(np.isfinite(m)):
+            raise ValueError("mix: recording %d: a weight is not finite" % r)
+    rows = np.array([m.shape[0] for m in mats], dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in mats]) if mats else np.zeros(0, np.float32), dtype=np.float32)
+    return rows, flat
+
+
+def _channel_counts(recordings):
+    """channels of every recording of transcribe_long(channels=...): [n] is one channel, [n][C] are C"""
+    counts = []
+    for r in recordings:
+        shape = np.shape(r)
+        if len(shape) not in (1, 2) or (len(shape) == 2 and not 1 <= shape[1] <= 8):
+            raise ValueError("channels: a recording must be [n] or [n][C] with 1 .. 8 channels, got %r" % (shape,))
+        counts.append(int(shape[1]) if len(shape) == 2 else 1)
+    return counts
+
+
+def _per_channel(value, counts, per_recording):
+    """a per-recording list repeated per channel, in (recording, channel) order; anything else as it is"""
+    if not per_recording:
+        return value
+    if len(value) != len(counts):
+        raise ValueError("channels='split': a per-recording list has one entry per recording (%d), got %d" % (len(counts), len(value)))
+    return [value[r] for r, C in enumerate(counts) for _ in range(C)]
+
+
+def _split_arguments(counts, language, initial_prompt_tokens, clip_timestamps, recording_bias):
+    """transcribe_long(channels='split'): the arguments that are lists per recording, repeated per channel"""
+    nested = (list, tuple, np.ndarray)
+    ip, ct = initial_prompt_tokens, clip_timestamps
+    return (_per_channel(language, counts, language is not None and np.ndim(language) != 0),
+            _per_channel(ip, counts, ip is not None and len(ip) > 0 and all(isinstance(x, nested) for x in ip)),
+            _per_channel(ct, counts, ct is not None and not np.isscalar(ct) and len(ct) > 0
+                         and all(isinstance(x, nested + (str,)) for x in ct)),
+            _per_channel(recording_bias, counts, recording_bias is not None))
+
+
+def _split_results(out, counts):
+    """transcribe_long(channels='split'): per recording, `channels` -- its channels' results -- and `segments`, copies of all
+    their segments with `channel`, ordered by (start, channel)"""
+    res, i = [], 0
+    for C in counts:
+        chans = out[i:i + C]
+        i += C
+        segs = [dict(sg, channel=c) for c, ch in enumerate(chans) for sg in ch["segments"]]
+        segs.sort(key=lambda sg: (sg["start"], sg["channel"]))   # (stable: a channel's own order stays)
+        res.append(dict(channels=chans, segments=segs))
+    return res
+
+
+def _diarize_results(ctx, out, recordings, sample_rates, counts, ratio):
+    """transcribe_long(channels='diarize'): ONE wm_resample_16k_mix with identity rows, ONE wm_channel_activity over its device
+    output, the split signals freed; then `speaker` on every segment and word"""
+    d_sig, offs = ctx.resample_16k_mix(recordings, sample_rates, [channel_rows("split", C) for C in counts], device=True)
+    try:
+        act = ctx.channel_activity(d_sig, offs, device=True)
+    finally:
+        ctx.dev_free(d_sig)
+    i = 0
+    for rec, C in zip(out, counts):
+        act_r = act[i:i + C]
+        i += C
+        for sg in rec["segments"]:
+            sg["speaker"] = speaker_by_channel(act_r, sg["start"], sg["end"], ratio)
+            for w in sg.get("words", ()):
+                w["speaker"] = speaker_by_channel(act_r, w["start"], w["end"], ratio)
+
+
 # ---- long-form transcription: openai-whisper transcribe()'s seek loop ---------------------------------------------------
 HOP_SECONDS = 160 / 16000     # one mel frame
 INPUT_STRIDE = 2              # mel frames per encoder output frame (N_FRAMES // n_audio_ctx)
@@ -1430,9 +1560,12 @@ def _long_mel(o, R):
     ctx = o.ctx
     if o.sample_rates is None:
         return ctx.logmel_long(o.recordings, n_mels=o.n_mels, device=True)
-    if len(o.sample_rates) != R:
-        raise ValueError("sample_rates: one per recording")
-    d_pcm, pcm_offs = ctx.resample_16k(o.recordings, o.sample_rates, device=True)
+    if o.split:   # 27.: the identity matrix of every recording -- one signal per channel, R of them
+        d_pcm, pcm_offs = ctx.resample_16k_mix(o.recordings, o.sample_rates, [channel_rows("split", C) for C in o.counts], device=True)
+    else:
+        if len(o.sample_rates) != R:
+            raise ValueError("sample_rates: one per recording")
+        d_pcm, pcm_offs = ctx.resample_16k(o.recordings, o.sample_rates, device=True)
     try:
         return ctx.logmel_long_device(d_pcm, np.float32, pcm_offs, n_mels=o.n_mels)
     finally:
@@ -1594,7 +1727,8 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
                     hallucination_silence_threshold=None, carry_initial_prompt=False, vad=None, parallel_clips=None,
                     repetition_penalty=None, no_repeat_ngram_size=None, teacher_panel=None, sequence_bias=None, bad_words=None,
                     boost_phrases=None, phrase_boost=None, draft=None, draft_len=None, prompt_panel=None, recording_bias=None,
-                    top_k=None, top_p=None, min_p=None, alternatives=None, constraint=None, fallback="lockstep"):
+                    top_k=None, top_p=None, min_p=None, alternatives=None, constraint=None, fallback="lockstep", channels=None,
+                    channel_ratio=1.1):
     """openai-whisper transcribe() for recordings of any length, batched across the recordings.
     condition_on_previous_text defaults to False here (openai-whisper: True); see 5.  word_timestamps: see 6.
     clip_timestamps, hallucination_silence_threshold, carry_initial_prompt: see 10 - 12; at their defaults the function
@@ -1781,6 +1915,20 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
        temperature and seed, and the sample id does not depend on the round.  ValueError before any library call for any other
        value and for "deferred" together with best_of, beam_size, draft or reuse_encoder.  With "lockstep" the function makes
        exactly the calls it made before the argument existed.
+    27. channels (None; "split"; "diarize") / channel_ratio: multichannel recordings.  Both modes need sample_rates (the
+       interleaved path of 1.).  "split": ONE wm_resample_16k_mix call with identity rows (Context.resample_16k_mix) takes the
+       place of the wm_resample_16k call, and from the log-mel on every (recording, channel) is a recording of its own, in
+       (r, c) order: language, initial_prompt_tokens, clip_timestamps and recording_bias given per recording are repeated per
+       channel, recording_ids is one id per channel-recording (default 0 .. sum(C_r) - 1).  The run IS transcribe_long on the
+       list of the mono 16 kHz signals resample_16k_mix returns, with the same keywords, and works with every other option.
+       The result of recording r is a dict: `channels`, its channels' results as this function returns them, and `segments`,
+       copies of all their segments with `channel`, ordered by (start, channel).  "diarize": the decode is the channels=None
+       run call for call -- the mean is what the model hears --; behind it ONE wm_resample_16k_mix with identity rows and ONE
+       wm_channel_activity over its device output (the split signals are freed at once), and every segment -- with word
+       timestamps every word too -- gains speaker = speaker_by_channel(the recording's activity, start, end, channel_ratio): a
+       channel index or None; None everywhere for a mono recording.  ValueError before any library call: any other value of
+       channels, channels without sample_rates, a channel_ratio that is not finite and >= 1.  With None the function makes
+       exactly the calls it made before the arguments existed.
     With vad and parallel_clips at None the function makes exactly the calls it made before they existed.
     A recording's seek strictly grows from one of its windows to the next within a clip (asserted).
     initial_prompt_tokens: one flat list for all recordings, or one list per recording (a list of R lists, empty allowed:
@@ -1790,8 +1938,22 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     segments (openai-whisper's keys id seek start end tokens temperature avg_logprob compression_ratio no_speech_prob, plus
     text with a Vocab and words [{word, start, end, probability}] with word_timestamps), text (with a Vocab), seeks (the first frame of every decoded window) and windows (per window:
     seek, segment_size, the fallback steps' temperatures, skipped, prompt_len, prompt)."""
+    counts = None   # 27.: the channels of every recording (None: off)
+    channel_ratio = _channel_ratio(channel_ratio)
+    if channels is not None:
+        if channels not in ("split", "diarize"):
+            raise ValueError("channels: None, 'split' or 'diarize'")
+        if sample_rates is None:
+            raise ValueError("channels needs sample_rates: the recordings are interleaved at their own rates")
+        if len(sample_rates) != len(recordings):
+            raise ValueError("sample_rates: one per recording")
+        counts = _channel_counts(recordings)
+        if channels == "split":
+            language, initial_prompt_tokens, clip_timestamps, recording_bias = _split_arguments(
+                counts, language, initial_prompt_tokens, clip_timestamps, recording_bias)
+    split = channels == "split"
     o = _LongOptions(**locals())
-    R = len(recordings)
+    R = sum(counts) if split else len(recordings)   # (split: every channel is a recording from the log-mel on)
     o.early(R)
     sampling = sampling_rules_args(top_k, top_p, min_p)   # 23. (None: off)
     constraint_args(constraint)   # 25. (None: off)
@@ -1922,7 +2084,9 @@ def transcribe_long(ctx, recordings, *, sot, task, eot, timestamp_begin, no_spee
     if vocab is not None:
         for rec in out:
             rec["text"] = vocab.decode([t for sg in rec["segments"] for t in sg["tokens"] if t < eot])
-    return out
+    if channels == "diarize":   # 27.
+        _diarize_results(ctx, out, recordings, sample_rates, counts, channel_ratio)
+    return _split_results(out, counts) if split else out
 
 
 class Windows:
@@ -2086,6 +2250,68 @@ class Context:
             if d_pcm is not None:
                 self.dev_free(d_pcm)
         return d_out, out_offs
+
+    def resample_16k_mix(self, recordings, sample_rates, mix, device=False):
+        """wm_resample_16k_mix: resample_16k with a channel matrix.  mix: one [n_rows][C_r] array of finite weights per
+        recording (channel_rows makes the usual ones); recording r yields n_rows signals, signal (r, o) the recording mixed
+        under row o -- m = w[0] x[0], then fmaf(w[c], x[c], m) in channel order -- and resampled to 16 kHz.  One launch for
+        all of them.  Returns per recording a list of f32 arrays; device=True keeps the signals on the device and returns
+        (pointer, sample offsets i64 [sum(n_rows) + 1]), the signals in (r, o) order -- what logmel_long_device and
+        channel_activity read; free the pointer with dev_free."""
+        pcm, offs, ch, rates = _pack_interleaved(recordings, sample_rates)
+        rows, flat = _pack_mix(mix, ch)
+        R = len(ch)
+        frames = np.diff(offs) // np.maximum(ch, 1)
+        lens = [resample_out_len(int(n), int(sr)) for n, sr in zip(frames, rates)]
+        out_offs = np.zeros(int(rows.sum()) + 1, dtype=np.int64)
+        out_offs[1:] = np.cumsum(np.repeat(np.array(lens, dtype=np.int64), rows))
+        args = (_DTYPES[pcm.dtype], _ptr(offs), _ptr(ch), _ptr(rates), R, _ptr(rows), _ptr(flat))
+        if not device:
+            out = np.empty(max(int(out_offs[-1]), 1), dtype=np.float32)
+            _check(self.lib, self.lib.wm_resample_16k_mix(self.handle, _ptr(pcm), *args, _ptr(out), WM_MEM_HOST))
+            first = np.concatenate([[0], np.cumsum(rows)])
+            return [[out[out_offs[s]:out_offs[s + 1]] for s in range(first[r], first[r + 1])] for r in range(R)]
+        d_pcm = self.to_device(pcm) if pcm.nbytes else None
+        d_out = None
+        try:
+            d_out = self.dev_malloc(max(int(out_offs[-1]), 1) * 4)
+            _check(self.lib, self.lib.wm_resample_16k_mix(self.handle, d_pcm, *args, d_out, WM_MEM_DEVICE))
+            self.sync()
+        except Exception:
+            if d_out is not None:
+                self.dev_free(d_out)
+            raise
+        finally:
+            if d_pcm is not None:
+                self.dev_free(d_pcm)
+        return d_out, out_offs
+
+    def channel_activity(self, signals, offsets=None, device=False):
+        """wm_channel_activity: per signal, the f32 sum of |y| over every 160 samples (10 ms, one value per mel frame; the last
+        frame may be short).  signals: a list of 16 kHz f32 arrays -- or, with device=True, the device pointer and `offsets`,
+        the sample offsets i64 [S + 1], as resample_16k_mix(..., device=True) returns them (computed where the signals lie,
+        then downloaded).  Returns a list of f32 [ceil(N_s / 160)] on the host."""
+        if device:
+            offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        else:
+            sig = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+            offs = np.concatenate([[0], np.cumsum([s.size for s in sig])]).astype(np.int64)
+            pcm = np.ascontiguousarray(np.concatenate(sig) if sig else np.zeros(0, np.float32), dtype=np.float32)
+        S = len(offs) - 1
+        n = -(-np.diff(offs) // ACTIVITY_HOP)
+        out_offs = np.concatenate([[0], np.cumsum(np.maximum(n, 0))]).astype(np.int64)
+        total = max(int(out_offs[-1]), 1)
+        if not device:
+            act = np.empty(total, dtype=np.float32)
+            _check(self.lib, self.lib.wm_channel_activity(self.handle, _ptr(pcm), _ptr(offs), S, _ptr(act), WM_MEM_HOST))
+        else:
+            d_act = self.dev_malloc(total * 4)
+            try:
+                _check(self.lib, self.lib.wm_channel_activity(self.handle, signals, _ptr(offs), S, d_act, WM_MEM_DEVICE))
+                act = self.download(d_act, total, np.float32)
+            finally:
+                self.dev_free(d_act)
+        return [act[out_offs[s]:out_offs[s + 1]] for s in range(S)]
 
     def vad_energy(self, mel, mel_offs, T, n_frames, band, smooth=VAD_SMOOTH, device=False, raw=False, n_mels=None):
         """wm_vad_energy: the smoothed band energy of R recordings' log-mels in one launch.  mel: logmel_long's output --

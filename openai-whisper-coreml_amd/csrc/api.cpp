@@ -193,6 +193,7 @@ extern "C" void wm_destroy(wm_ctx *ctx) {
     wm_frontend_destroy(&ctx->fe);
     wm_resample_destroy(&ctx->rs);
     wm_vad_destroy(&ctx->vad);
+    wm_chanact_destroy(&ctx->chanact);
     ctx->prof.reset();
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -457,6 +458,87 @@ extern "C" int wm_resample_16k(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype,
                           ctx->stream));
     WM_TRY(wm_resample_run(&ctx->rs, &ctx->prof, ctx->stream, d_in, pcm_dtype, offs.data(), n_channels, sample_rates, R, (float *)d_out));
     WM_HIP(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    return WM_OK;
+} WM_API_CATCH
+
+// wm_resample_16k with a channel matrix: n_rows[r] signals per recording, each in wm_logmel_long's input layout
+extern "C" int wm_resample_16k_mix(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *elem_offsets,
+                                   const int32_t *n_channels, const int32_t *sample_rates, int R, const int32_t *n_rows,
+                                   const float *mix, float *out, wm_mem mem) try {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(R >= 0 && R <= 65535, WM_ERR_INVALID, "resample: R must be 0 .. 65535, got %d", R);
+    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32, WM_ERR_INVALID, "resample: pcm dtype must be WM_I16 / WM_F32");
+    if (R == 0) return WM_OK;
+    WM_REQUIRE(elem_offsets && n_channels && sample_rates, WM_ERR_INVALID, "resample: null elem_offsets / n_channels / sample_rates");
+    WM_REQUIRE(n_rows && mix, WM_ERR_INVALID, "resample_mix: null n_rows / mix");
+    int64_t n_out = 0, n_sig = 0;
+    const float *w = mix;
+    for (int r = 0; r < R; ++r) {
+        const int64_t len = elem_offsets[r + 1] - elem_offsets[r];
+        WM_REQUIRE(elem_offsets[r] >= 0 && len >= 0, WM_ERR_INVALID, "resample: elem_offsets must be >= 0 and non-decreasing (recording %d)", r);
+        WM_REQUIRE(n_channels[r] >= 1 && n_channels[r] <= WM_RS_MAX_CHANNELS, WM_ERR_INVALID,
+                   "resample: recording %d: %d channels (1 .. %d)", r, n_channels[r], WM_RS_MAX_CHANNELS);
+        WM_REQUIRE(len % n_channels[r] == 0, WM_ERR_INVALID, "resample: recording %d: %lld samples are no multiple of its %d channels",
+                   r, (long long)len, n_channels[r]);
+        const int64_t n = wm_resample_out_len(len / n_channels[r], sample_rates[r]);
+        WM_REQUIRE(n >= 0, WM_ERR_INVALID, "resample: recording %d: unsupported sample rate %d", r, sample_rates[r]);
+        WM_REQUIRE(n_rows[r] >= 1 && n_rows[r] <= WM_RS_MAX_CHANNELS, WM_ERR_INVALID, "resample_mix: recording %d: %d rows (1 .. %d)", r,
+                   n_rows[r], WM_RS_MAX_CHANNELS);
+        n_sig += n_rows[r];
+        WM_REQUIRE(n_sig <= 65535, WM_ERR_INVALID, "resample_mix: more than 65535 output signals");
+        for (int i = 0; i < n_rows[r] * n_channels[r]; ++i, ++w)
+            WM_REQUIRE(std::isfinite(*w), WM_ERR_INVALID, "resample_mix: recording %d: weight %d of its matrix is not finite", r, i);
+        n_out += n * n_rows[r];
+    }
+    if (n_out == 0) return WM_OK;
+    WM_REQUIRE(pcm && out, WM_ERR_INVALID, "resample: null pcm / out");
+    if (mem == WM_MEM_DEVICE)
+        return wm_resample_mix_run(&ctx->rs, &ctx->prof, ctx->stream, pcm, pcm_dtype, elem_offsets, n_channels, sample_rates, R, n_rows,
+                                   mix, out);
+    // host memory: only the samples the recordings span cross PCIe (offsets rebased to the first one)
+    std::vector<int64_t> offs(elem_offsets, elem_offsets + R + 1);
+    for (auto &o : offs) o -= elem_offsets[0];
+    const size_t in_b = (size_t)offs[R] * dtype_size(pcm_dtype);
+    const size_t out_b = (size_t)n_out * sizeof(float);
+    const size_t in_al = (in_b + 255) & ~(size_t)255;
+    WM_TRY(ensure_scratch(ctx, in_al + out_b));
+    char *d_in = (char *)ctx->fe.scratch, *d_out = d_in + in_al;
+    WM_HIP(hipMemcpyAsync(d_in, (const char *)pcm + (size_t)elem_offsets[0] * dtype_size(pcm_dtype), in_b, hipMemcpyHostToDevice,
+                          ctx->stream));
+    WM_TRY(wm_resample_mix_run(&ctx->rs, &ctx->prof, ctx->stream, d_in, pcm_dtype, offs.data(), n_channels, sample_rates, R, n_rows, mix,
+                               (float *)d_out));
+    WM_HIP(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    return WM_OK;
+} WM_API_CATCH
+
+// Per-channel activity of 16 kHz signals (channel_activity.hip): the sum of |y| per 160 samples
+extern "C" int wm_channel_activity(wm_ctx *ctx, const float *pcm16k, const int64_t *sample_offsets, int S, float *act_out,
+                                   wm_mem mem) try {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(S >= 0 && S <= 65535, WM_ERR_INVALID, "channel_activity: S must be 0 .. 65535, got %d", S);
+    if (S == 0) return WM_OK;
+    WM_REQUIRE(sample_offsets, WM_ERR_INVALID, "channel_activity: null sample_offsets");
+    int64_t n_out = 0;
+    for (int s = 0; s < S; ++s) {
+        WM_REQUIRE(sample_offsets[s] >= 0 && sample_offsets[s + 1] >= sample_offsets[s], WM_ERR_INVALID,
+                   "channel_activity: sample_offsets must be >= 0 and non-decreasing (signal %d)", s);
+        n_out += (sample_offsets[s + 1] - sample_offsets[s] + WM_ACTIVITY_HOP - 1) / WM_ACTIVITY_HOP;
+    }
+    if (n_out == 0) return WM_OK;
+    WM_REQUIRE(pcm16k && act_out, WM_ERR_INVALID, "channel_activity: null pcm16k / act_out");
+    if (mem == WM_MEM_DEVICE) return wm_chanact_run(&ctx->chanact, &ctx->prof, ctx->stream, pcm16k, sample_offsets, S, act_out);
+    // host memory: only the samples the signals span cross PCIe (offsets rebased to the first one)
+    std::vector<int64_t> offs(sample_offsets, sample_offsets + S + 1);
+    for (auto &o : offs) o -= sample_offsets[0];
+    const size_t in_b = (size_t)offs[S] * sizeof(float), out_b = (size_t)n_out * sizeof(float);
+    const size_t in_al = (in_b + 255) & ~(size_t)255;
+    WM_TRY(ensure_scratch(ctx, in_al + out_b));
+    char *d_in = (char *)ctx->fe.scratch, *d_out = d_in + in_al;
+    WM_HIP(hipMemcpyAsync(d_in, pcm16k + sample_offsets[0], in_b, hipMemcpyHostToDevice, ctx->stream));
+    WM_TRY(wm_chanact_run(&ctx->chanact, &ctx->prof, ctx->stream, (const float *)d_in, offs.data(), S, (float *)d_out));
+    WM_HIP(hipMemcpyAsync(act_out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
     WM_HIP(hipStreamSynchronize(ctx->stream));
     return WM_OK;
 } WM_API_CATCH

@@ -1,6 +1,7 @@
 // resample.hip -- audio at any sample rate -> 16 kHz mono f32 on the device: the filter (host, f64),
 // the polyphase kernel and its device-pointer core.  The C-ABI entry wm_resample_16k is in api.cpp beside wm_logmel_long,
-// whose input layout this produces.
+// whose input layout this produces.  Behind it the same filter with a CHANNEL MATRIX in front (DESIGN.md section 24,
+// wm_resample_16k_mix): resample_mix_kernel, one signal per (recording, matrix row).
 //
 // The filter.  For input rate sr: g = gcd(sr, 16000), L = 16000 / g, M = sr / g, mx = max(L, M), K = 32 mx.  The prototype
 // lives at the upsampled rate, j = -K .. K:
@@ -139,6 +140,53 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const S *__restric
     else rs_filter_tile<false>(rc, b.n0, k_base, rs_lds, out);
 }
 
+// ---- the channel matrix (wm_resample_16k_mix) ----
+// One output signal: a recording's geometry (out: the SIGNAL's first output sample) and its row of weights.
+struct RsSig {
+    RsRec rc;
+    float w[WM_RS_MAX_CHANNELS];
+};
+static_assert(sizeof(RsSig) == 96, "RsSig is copied to the device as is");
+
+// frame k under a row w: m = w[0] x[0] (one rounding), then m = fmaf(w[c], x[c], m) in channel order
+template <typename S>
+__device__ inline float rs_mix(const S *pcm, long long elem, int C, const float *w) {
+    const S *p = pcm + elem;
+    float m = w[0] * rs_sample(p);
+    for (int c = 1; c < C; ++c) m = fmaf(w[c], rs_sample(p + c), m);
+    return m;
+}
+
+// resample_kernel with the row's mix where the mean was: one workgroup per (signal, tile of RS_TILE outputs), each re-reading
+// the interleaved span of its tile.  The staged span and the fma chains are resample_kernel's, so a signal's bits are a
+// function of (recording, rate, row) alone.
+template <typename S>
+__global__ __launch_bounds__(RS_THREADS) void resample_mix_kernel(const S *__restrict__ pcm, const RsSig *__restrict__ sigs,
+                                                                  const RsBlk *__restrict__ blks, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+    const RsBlk b = blks[blockIdx.x];
+    const RsRec rc = sigs[b.rec].rc;
+    const float *w = sigs[b.rec].w;   // (a wave-uniform address: the weights come through the scalar cache)
+    if (rc.tab == nullptr) {   // 16 kHz: the mix alone
+#pragma unroll
+        for (int i = 0; i < RS_PER_LANE; ++i) {
+            const long long n = b.n0 + threadIdx.x + i * RS_THREADS;
+            if (n < rc.n_out) out[rc.out + n] = rs_mix(pcm, rc.in + n * rc.C, rc.C, w);
+        }
+        return;
+    }
+    const long long k_base = ceil_div_ll(b.n0 * rc.M - rc.K, rc.L);
+    const long long k_last = ceil_div_ll((b.n0 + RS_TILE - 1) * rc.M - rc.K, rc.L);
+    const int span = (int)(k_last - k_base) + rc.T4;
+    for (int i = threadIdx.x; i < span; i += RS_THREADS) {
+        const long long k = k_base + i;
+        rs_lds[i] = (k >= 0 && k < rc.n) ? rs_mix(pcm, rc.in + k * rc.C, rc.C, w) : 0.f;
+    }
+    __syncthreads();
+    if (rc.L == 1) rs_filter_tile<true>(rc, b.n0, k_base, rs_lds, out);
+    else rs_filter_tile<false>(rc, b.n0, k_base, rs_lds, out);
+}
+
 // floats of LDS a tile of this rate can need: (kf(n0 + RS_TILE - 1) - kf(n0)) + T4 <= ceil((RS_TILE - 1) M / L) + T4
 size_t rs_span_floats(int L, int M, int T4) { return (size_t)(((long long)(RS_TILE - 1) * M + L - 1) / L) + (size_t)T4; }
 }  // namespace
@@ -209,6 +257,71 @@ static int rs_filter(WmResampler *rs, hipStream_t stream, int sr, const WmRsFilt
     return WM_OK;
 }
 
+// Recording r's geometry (everything of RsRec but `out`) after the checks both entries share; *lds_floats grows to the span
+// a tile of its rate needs.
+static int rs_record(WmResampler *rs, hipStream_t stream, int r, const int64_t *offs, const int32_t *n_channels,
+                     const int32_t *sample_rates, RsRec *rec, size_t *lds_floats) {
+    const int64_t len = offs[r + 1] - offs[r];
+    const int C = n_channels[r], sr = sample_rates[r];
+    WM_REQUIRE(offs[r] >= 0 && len >= 0, WM_ERR_INVALID, "resample: recording %d: offsets [%lld, %lld) invalid", r,
+               (long long)offs[r], (long long)offs[r + 1]);
+    WM_REQUIRE(C >= 1 && C <= WM_RS_MAX_CHANNELS, WM_ERR_INVALID, "resample: recording %d: %d channels (1 .. %d)", r, C,
+               WM_RS_MAX_CHANNELS);
+    WM_REQUIRE(len % C == 0, WM_ERR_INVALID, "resample: recording %d: %lld samples are no multiple of its %d channels", r,
+               (long long)len, C);
+    const int64_t n_out = wm_resample_out_len(len / C, sr);
+    WM_REQUIRE(n_out >= 0, WM_ERR_INVALID, "resample: recording %d: unsupported sample rate %d", r, sr);
+    WM_REQUIRE(n_out <= (int64_t)1 << 30, WM_ERR_INVALID, "resample: recording %d: %lld output samples (0 .. 2^30)", r,
+               (long long)n_out);
+    RsRec &rc = *rec;
+    rc.in = offs[r];
+    rc.out = 0;
+    rc.n = len / C;
+    rc.n_out = n_out;
+    rc.C = C;
+    rc.pad = 0;
+    if (sr == WM_RS_TARGET_RATE) {
+        rc.tab = nullptr;
+        rc.L = rc.M = 1;
+        rc.K = rc.T4 = 0;
+    } else {
+        const WmRsFilter *f = nullptr;
+        WM_TRY(rs_filter(rs, stream, sr, &f));
+        rc.tab = f->d_tab;
+        rc.L = f->L;
+        rc.M = f->M;
+        rc.K = f->K;
+        rc.T4 = f->T4;
+        const size_t need = rs_span_floats(f->L, f->M, f->T4);
+        if (n_out > 0 && need > *lds_floats) *lds_floats = need;
+    }
+    return WM_OK;
+}
+
+// The call's tables on the device: rec_bytes of records (RsRec or RsSig), then the workgroup table; the copies are queued.
+static int rs_tables(WmResampler *rs, hipStream_t stream, const void *rec, size_t rec_bytes, const std::vector<RsBlk> &blk,
+                     const void *d_pcm, const float *d_out, size_t lds_floats, const void **d_rec, const RsBlk **d_blk) {
+    // (grid limit: blocks x 256 lanes stays below 2^32 -- 2^24 - 1 tiles are 298 hours of 16 kHz output)
+    WM_REQUIRE(blk.size() < ((size_t)1 << 24), WM_ERR_INVALID, "resample: %zu tiles of %d outputs in one call (at most 2^24 - 1)",
+               blk.size(), RS_TILE);
+    WM_REQUIRE(d_pcm && d_out, WM_ERR_INVALID, "resample: null pcm / out");
+    WM_REQUIRE(lds_floats * sizeof(float) <= 64 * 1024, WM_ERR_INVALID, "resample: tile span of %zu floats", lds_floats);
+    const size_t rec_b = (rec_bytes + 255) & ~(size_t)255, bytes = rec_b + sizeof(RsBlk) * blk.size();
+    if (rs->tab_bytes < bytes) {
+        WM_HIP(hipStreamSynchronize(stream));
+        if (rs->tab) WM_HIP(hipFree(rs->tab));
+        rs->tab = nullptr;
+        rs->tab_bytes = 0;
+        WM_HIP(hipMalloc(&rs->tab, bytes));
+        rs->tab_bytes = bytes;
+    }
+    *d_rec = rs->tab;
+    *d_blk = (const RsBlk *)((char *)rs->tab + rec_b);
+    WM_HIP(hipMemcpyAsync(rs->tab, rec, rec_bytes, hipMemcpyHostToDevice, stream));
+    WM_HIP(hipMemcpyAsync((void *)*d_blk, blk.data(), sizeof(RsBlk) * blk.size(), hipMemcpyHostToDevice, stream));
+    return WM_OK;
+}
+
 int wm_resample_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
                     const int64_t *offs, const int32_t *n_channels, const int32_t *sample_rates, int R, float *d_out) {
     WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32, WM_ERR_INVALID, "resample: pcm dtype must be WM_I16 / WM_F32");
@@ -220,62 +333,16 @@ int wm_resample_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const
     long long out = 0;
     size_t lds_floats = 0;
     for (int r = 0; r < R; ++r) {
-        const int64_t len = offs[r + 1] - offs[r];
-        const int C = n_channels[r], sr = sample_rates[r];
-        WM_REQUIRE(offs[r] >= 0 && len >= 0, WM_ERR_INVALID, "resample: recording %d: offsets [%lld, %lld) invalid", r,
-                   (long long)offs[r], (long long)offs[r + 1]);
-        WM_REQUIRE(C >= 1 && C <= WM_RS_MAX_CHANNELS, WM_ERR_INVALID, "resample: recording %d: %d channels (1 .. %d)", r, C,
-                   WM_RS_MAX_CHANNELS);
-        WM_REQUIRE(len % C == 0, WM_ERR_INVALID, "resample: recording %d: %lld samples are no multiple of its %d channels", r,
-                   (long long)len, C);
-        const int64_t n_out = wm_resample_out_len(len / C, sr);
-        WM_REQUIRE(n_out >= 0, WM_ERR_INVALID, "resample: recording %d: unsupported sample rate %d", r, sr);
-        WM_REQUIRE(n_out <= (int64_t)1 << 30, WM_ERR_INVALID, "resample: recording %d: %lld output samples (0 .. 2^30)", r,
-                   (long long)n_out);
-        RsRec &rc = rec[r];
-        rc.in = offs[r];
-        rc.out = out;
-        rc.n = len / C;
-        rc.n_out = n_out;
-        rc.C = C;
-        rc.pad = 0;
-        if (sr == WM_RS_TARGET_RATE) {
-            rc.tab = nullptr;
-            rc.L = rc.M = 1;
-            rc.K = rc.T4 = 0;
-        } else {
-            const WmRsFilter *f = nullptr;
-            WM_TRY(rs_filter(rs, stream, sr, &f));
-            rc.tab = f->d_tab;
-            rc.L = f->L;
-            rc.M = f->M;
-            rc.K = f->K;
-            rc.T4 = f->T4;
-            const size_t need = rs_span_floats(f->L, f->M, f->T4);
-            if (n_out > 0 && need > lds_floats) lds_floats = need;
-        }
-        out += n_out;
-        for (long long n0 = 0; n0 < n_out; n0 += RS_TILE) blk.push_back(RsBlk{r, 0, n0});
+        WM_TRY(rs_record(rs, stream, r, offs, n_channels, sample_rates, &rec[r], &lds_floats));
+        rec[r].out = out;
+        out += rec[r].n_out;
+        for (long long n0 = 0; n0 < rec[r].n_out; n0 += RS_TILE) blk.push_back(RsBlk{r, 0, n0});
     }
     if (blk.empty()) return WM_OK;
-    // (grid limit: blocks x 256 lanes stays below 2^32 -- 2^24 - 1 tiles are 298 hours of 16 kHz output)
-    WM_REQUIRE(blk.size() < ((size_t)1 << 24), WM_ERR_INVALID, "resample: %zu tiles of %d outputs in one call (at most 2^24 - 1)",
-               blk.size(), RS_TILE);
-    WM_REQUIRE(d_pcm && d_out, WM_ERR_INVALID, "resample: null pcm / out");
-    WM_REQUIRE(lds_floats * sizeof(float) <= 64 * 1024, WM_ERR_INVALID, "resample: tile span of %zu floats", lds_floats);
-    const size_t rec_b = (sizeof(RsRec) * R + 255) & ~(size_t)255, bytes = rec_b + sizeof(RsBlk) * blk.size();
-    if (rs->tab_bytes < bytes) {
-        WM_HIP(hipStreamSynchronize(stream));
-        if (rs->tab) WM_HIP(hipFree(rs->tab));
-        rs->tab = nullptr;
-        rs->tab_bytes = 0;
-        WM_HIP(hipMalloc(&rs->tab, bytes));
-        rs->tab_bytes = bytes;
-    }
-    const RsRec *d_rec = (const RsRec *)rs->tab;
-    const RsBlk *d_blk = (const RsBlk *)((char *)rs->tab + rec_b);
-    WM_HIP(hipMemcpyAsync(rs->tab, rec.data(), sizeof(RsRec) * R, hipMemcpyHostToDevice, stream));
-    WM_HIP(hipMemcpyAsync((void *)d_blk, blk.data(), sizeof(RsBlk) * blk.size(), hipMemcpyHostToDevice, stream));
+    const void *d_tab = nullptr;
+    const RsBlk *d_blk = nullptr;
+    WM_TRY(rs_tables(rs, stream, rec.data(), sizeof(RsRec) * R, blk, d_pcm, d_out, lds_floats, &d_tab, &d_blk));
+    const RsRec *d_rec = (const RsRec *)d_tab;
     {
         WmProfScope ps(prof, "resample", stream);
         const size_t lds = lds_floats * sizeof(float);
@@ -283,6 +350,54 @@ int wm_resample_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const
             resample_kernel<int16_t><<<(unsigned)blk.size(), RS_THREADS, lds, stream>>>((const int16_t *)d_pcm, d_rec, d_blk, d_out);
         else
             resample_kernel<float><<<(unsigned)blk.size(), RS_THREADS, lds, stream>>>((const float *)d_pcm, d_rec, d_blk, d_out);
+    }
+    WM_HIP(hipGetLastError());
+    // the tables are pageable host memory: the copies must have read them before they go out of scope
+    WM_HIP(hipStreamSynchronize(stream));
+    return WM_OK;
+}
+
+int wm_resample_mix_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
+                        const int64_t *offs, const int32_t *n_channels, const int32_t *sample_rates, int R, const int32_t *n_rows,
+                        const float *mix, float *d_out) {
+    WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32, WM_ERR_INVALID, "resample: pcm dtype must be WM_I16 / WM_F32");
+    WM_REQUIRE(R >= 0 && R <= 65535, WM_ERR_INVALID, "resample: R must be 0 .. 65535, got %d", R);
+    if (R == 0) return WM_OK;
+    WM_REQUIRE(offs && n_channels && sample_rates, WM_ERR_INVALID, "resample: null offsets / n_channels / sample_rates");
+    WM_REQUIRE(n_rows && mix, WM_ERR_INVALID, "resample_mix: null n_rows / mix");
+    std::vector<RsSig> sig;
+    std::vector<RsBlk> blk;
+    long long out = 0;
+    size_t lds_floats = 0;
+    const float *w = mix;
+    for (int r = 0; r < R; ++r) {
+        RsSig s;
+        WM_TRY(rs_record(rs, stream, r, offs, n_channels, sample_rates, &s.rc, &lds_floats));
+        WM_REQUIRE(n_rows[r] >= 1 && n_rows[r] <= WM_RS_MAX_CHANNELS, WM_ERR_INVALID, "resample_mix: recording %d: %d rows (1 .. %d)",
+                   r, n_rows[r], WM_RS_MAX_CHANNELS);
+        WM_REQUIRE(sig.size() + (size_t)n_rows[r] <= 65535, WM_ERR_INVALID, "resample_mix: more than 65535 output signals");
+        for (int o = 0; o < n_rows[r]; ++o, w += s.rc.C) {
+            for (int c = 0; c < WM_RS_MAX_CHANNELS; ++c) s.w[c] = c < s.rc.C ? w[c] : 0.f;
+            for (int c = 0; c < s.rc.C; ++c)
+                WM_REQUIRE(std::isfinite(w[c]), WM_ERR_INVALID, "resample_mix: recording %d, row %d: weight %d is not finite", r, o, c);
+            s.rc.out = out;
+            out += s.rc.n_out;
+            for (long long n0 = 0; n0 < s.rc.n_out; n0 += RS_TILE) blk.push_back(RsBlk{(int)sig.size(), 0, n0});
+            sig.push_back(s);
+        }
+    }
+    if (blk.empty()) return WM_OK;
+    const void *d_tab = nullptr;
+    const RsBlk *d_blk = nullptr;
+    WM_TRY(rs_tables(rs, stream, sig.data(), sizeof(RsSig) * sig.size(), blk, d_pcm, d_out, lds_floats, &d_tab, &d_blk));
+    const RsSig *d_sig = (const RsSig *)d_tab;
+    {
+        WmProfScope ps(prof, "resample_mix", stream);
+        const size_t lds = lds_floats * sizeof(float);
+        if (pcm_dtype == WM_I16)
+            resample_mix_kernel<int16_t><<<(unsigned)blk.size(), RS_THREADS, lds, stream>>>((const int16_t *)d_pcm, d_sig, d_blk, d_out);
+        else
+            resample_mix_kernel<float><<<(unsigned)blk.size(), RS_THREADS, lds, stream>>>((const float *)d_pcm, d_sig, d_blk, d_out);
     }
     WM_HIP(hipGetLastError());
     // the tables are pageable host memory: the copies must have read them before they go out of scope

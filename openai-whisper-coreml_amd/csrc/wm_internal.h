@@ -166,6 +166,22 @@ void wm_resample_destroy(WmResampler *rs);
 // sample_rates[r] Hz) -> d_out, its ceil(n L / M) samples after those of the recordings before it.  One launch.
 int wm_resample_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
                     const int64_t *offs, const int32_t *n_channels, const int32_t *sample_rates, int R, float *d_out);
+// Device-pointer core of wm_resample_16k_mix: the same with n_rows[r] output signals per recording, signal (r, o) under the
+// weights mix[row (r, o)] (n_rows, mix: host; the rows back to back) -> d_out, the signals in (r, o) order.  One launch.
+int wm_resample_mix_run(WmResampler *rs, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype,
+                        const int64_t *offs, const int32_t *n_channels, const int32_t *sample_rates, int R, const int32_t *n_rows,
+                        const float *mix, float *d_out);
+
+// ---------------------------------------------------------------- per-channel activity (channel_activity.hip) ----------
+constexpr int WM_CHANACT_TILE = 64;     // frames per workgroup
+struct WmChanAct {
+    void *tab = nullptr;                // signal and workgroup tables of a call
+    size_t tab_bytes = 0;
+};
+void wm_chanact_destroy(WmChanAct *ca);
+// Device-pointer core of wm_channel_activity: signal s = d_pcm[offs[s] .. offs[s + 1]) (offs: host) -> d_act, its
+// ceil(N_s / WM_ACTIVITY_HOP) values after those of the signals before it.  One launch.
+int wm_chanact_run(WmChanAct *ca, WmProfiler *prof, hipStream_t stream, const float *d_pcm, const int64_t *offs, int S, float *d_act);
 
 // ---------------------------------------------------------------- speech-activity energy (vad.hip) ----------
 constexpr int WM_VAD_MAX_SMOOTH = 31;
@@ -199,6 +215,7 @@ struct wm_ctx {
     WmFrontend fe;
     WmResampler rs;
     WmVad vad;
+    WmChanAct chanact;
     WmModel *model = nullptr;
     float stage_ms[3] = {0, 0, 0};
     std::vector<wm_ctx *> lanes;  // weight-sharing clones owned by this context (wm_transcribe_greedy)

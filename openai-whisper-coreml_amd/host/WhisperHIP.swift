@@ -352,6 +352,61 @@ struct Whisper {
         return result
     }
 
+    /// resample16k with a channel matrix (wm_resample_16k_mix, DESIGN.md section 24), host memory.  rows[r] is the number of
+    /// output signals of recording r and mix holds their weight rows back to back -- channels[r] weights each, in
+    /// (recording, row) order; the identity gives one signal per channel.  Returns the signals in (recording, row) order.
+    /// Not compiled in this repository (see the top of the file).
+    func resample16kMix(recordings: [[Float]], channels: [Int32], sampleRates: [Int32], rows: [Int32], mix: [Float]) throws -> [[Float]] {
+        typealias MixFn = @convention(c) (OpaquePointer, UnsafeRawPointer?, Int32, UnsafePointer<Int64>, UnsafePointer<Int32>,
+                                          UnsafePointer<Int32>, Int32, UnsafePointer<Int32>, UnsafePointer<Float>,
+                                          UnsafeMutablePointer<Float>, Int32) -> Int32
+        typealias OutLenFn = @convention(c) (Int64, Int32) -> Int64
+        let outLen: OutLenFn = try sym("wm_resample_out_len")
+        var offsets: [Int64] = [0]
+        for r in recordings { offsets.append(offsets.last! + Int64(r.count)) }
+        var lens: [Int] = []
+        for r in recordings.indices {
+            let n = outLen(Int64(recordings[r].count) / Int64(max(channels[r], 1)), sampleRates[r])
+            if n < 0 { throw WhisperError(description: "unsupported sample rate \(sampleRates[r])") }
+            lens += [Int](repeating: Int(n), count: Int(rows[r]))
+        }
+        let pcm = recordings.flatMap { $0 }
+        var out = [Float](repeating: 0, count: max(1, lens.reduce(0, +)))
+        let f: MixFn = try sym("wm_resample_16k_mix")
+        try pcm.withUnsafeBytes { p in
+            try check(f(ctx, p.baseAddress, 1 /* WM_F32 */, offsets, channels, sampleRates, Int32(recordings.count), rows, mix, &out, 0))
+        }
+        var result: [[Float]] = []
+        var at = 0
+        for n in lens {
+            result.append(Array(out[at..<at + n]))
+            at += n
+        }
+        return result
+    }
+
+    /// Per-channel activity (wm_channel_activity): per 16 kHz signal, the sum of |y| over every 160 samples -- one value per
+    /// mel frame --, host memory.  Returns one track of ceil(count / 160) values per signal.
+    /// Not compiled in this repository (see the top of the file).
+    func channelActivity(signals: [[Float]]) throws -> [[Float]] {
+        typealias ActivityFn = @convention(c) (OpaquePointer, UnsafePointer<Float>, UnsafePointer<Int64>, Int32,
+                                               UnsafeMutablePointer<Float>, Int32) -> Int32
+        var offsets: [Int64] = [0]
+        for s in signals { offsets.append(offsets.last! + Int64(s.count)) }
+        let lens = signals.map { ($0.count + 159) / 160 }
+        let pcm = signals.flatMap { $0 } + [0]   // (never empty: a base address to pass)
+        var out = [Float](repeating: 0, count: max(1, lens.reduce(0, +)))
+        let f: ActivityFn = try sym("wm_channel_activity")
+        try check(f(ctx, pcm, offsets, Int32(signals.count), &out, 0))
+        var result: [[Float]] = []
+        var at = 0
+        for n in lens {
+            result.append(Array(out[at..<at + n]))
+            at += n
+        }
+        return result
+    }
+
     /// wm_vad_params (include/whisper_mi355x.h), field for field; `VadParams.defaults()` is wm_vad_default_params.  The
     /// defaults are not validated on real speech.
     struct VadParams {
