@@ -451,7 +451,21 @@ WM_API int wmdbg_spec_round(int G, int w, const int32_t *accepted, const int32_t
 /* wmdbg_spec_round over n cases of one shape: in i32 [n][4][G] = accepted | live | eot_at | left, out i32 [n][1 + 5 G] = n |
  * live_out [G] | inc [G][4]; returns n (-1: bad arguments). */
 WM_API int wmdbg_spec_round_batch(int n, int G, int w, const int32_t *in, int32_t *out);
-/* Scoped to the NEXT wm_transcribe_mel_speculative call on ctx, which clears it whatever its outcome: the proposal for generated
+/* The next-call state of a transcribe call (csrc/tx_pending.h), on the CPU.
+ * wmdbg_pending_refusal: who serves which pending item.  pending: bits 1 budgets | 2 bias row map | 4 constraint row map |
+ *   8 sampling row map | 16 alternatives; the call: entry 0 plain | 1 mel | 2 ragged | 3 best-of | 4 beam, flags 1 greedy entry |
+ *   2 beam | 4 rows of a window set | 8 hypothesis-aligned | 16 speculative | 32 multi | 64 all-f32 path, n_cand.  Alternatives
+ *   are judged first; a caller masks `pending` to the items it answers for at that point.  Returns WM_OK (served) or
+ *   WM_ERR_STATE (-1: bad arguments) and writes the message ("" when served) to msg_out [msg_cap].
+ * wmdbg_pending_take: take() on a value of its own, armed with the items `bits` names, taken, the member armed again with
+ *   `again`.  out i32 [6] = bits armed | taken | left behind | the taken value's after the second arm | the member's then | the
+ *   taken value's budget (1: the first arm's; 0: none). */
+WM_API int wmdbg_pending_refusal(unsigned pending, int entry, unsigned flags, int n_cand, char *msg_out, int msg_cap);
+WM_API int wmdbg_pending_take(unsigned bits, unsigned again, int32_t *out);
+/* THE ONE-SHOTS' SCOPE (wmdbg_spec_script, wmdbg_align_capture, wmdbg_align_hyp, wmdbg_hyp_slots, wmdbg_beam_trace): each is
+ * armed for the NEXT transcribe call on ctx of ANY kind, which takes all of them whatever its outcome and reads the ones that
+ * are its own -- so arm one right in front of the call it is meant for: a plain transcribe call in between drops it. */
+/* Scoped to the NEXT transcribe call on ctx (above); wm_transcribe_mel_speculative reads it: the proposal for generated
  * index i of row b of that call is tokens[b * max_new + i] (B and max_new must be the call's; ids inside the vocabulary).  The
  * draft model still runs; only what the target is asked to verify changes, so tests and timings fix the acceptance pattern
  * exactly.  tokens is host memory that lives until that call returns; NULL clears the hook. */
@@ -524,10 +538,12 @@ WM_API int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, const
 /* Makes the NEXT wm_align or wm_align_mel call on ctx also return its cost matrix -- AFTER negation, i.e. x = -mean over heads, the matrix
  * the DTW runs on -- into matrix_out f32 [B][max_text + 1][1500] (0 outside each chunk's n + 1 rows x n_frames / 2 frames).
  * The next aligned transcribe call (wm_transcribe_mel_aligned, wm_transcribe_windows_aligned) is served the same way:
- * matrix_out f32 [B][max_new + 1][1500], 0 outside each row's len_b x M_b block. */
+ * matrix_out f32 [B][max_new + 1][1500], 0 outside each row's len_b x M_b block.  Whichever comes first takes it: a wm_align
+ * call, or a transcribe call of any kind (THE ONE-SHOTS' SCOPE above), which drops it when it is not an aligned one. */
 WM_API int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out);
 /* The aligned best-of / beam calls (wm_transcribe_mel_best_of_aligned, wm_transcribe_mel_beam_aligned and the window-set
- * pair), each for the NEXT aligned transcribe call on ctx only.  wmdbg_align_capture and wmdbg_beam_trace serve them too.
+ * pair), each for the NEXT transcribe call on ctx only, read when that call is an aligned one (THE ONE-SHOTS' SCOPE above).
+ * wmdbg_align_capture and wmdbg_beam_trace serve them too.
  * wmdbg_align_hyp: the call aligns hypothesis min(h, n_hyp - 1) of every window instead of best_out[b] (best-of: n_hyp =
  * best_of); best_out itself is the ranking's, as always.  For tests only.
  * wmdbg_hyp_slots: the call leaves the slot tables it aligned from in slots_out i32 [B][Tq], Tq = sot_tail + max_new - 1: entry t
@@ -586,7 +602,8 @@ WM_API double wmdbg_rank_score(double sum, int n_text, float length_penalty);
 /* Finalize: the live beams (sum > -inf) by descending sum, ties to the lower beam, into order_out [N]; returns their count
  * (-1: bad arguments).  Host only. */
 WM_API int wmdbg_beam_fill_order(int N, const float *sum, int32_t *order_out);
-/* Makes the NEXT wm_transcribe_mel_beam call on ctx also return, per window, generated index and beam, the beam's list and
+/* Makes the NEXT transcribe call on ctx, when it is a beam call (any other drops the hook: THE ONE-SHOTS' SCOPE above), also
+ * return, per window, generated index and beam, the beam's list and
  * its running sum BEFORE that step: trace_out f32 [B][max_new][beam_size][2 + 2 * (WM_MAX_BEAM + 1)], each record = entries
  * (i32 bits), sum, WM_MAX_BEAM + 1 token ids (i32 bits), WM_MAX_BEAM + 1 log-probs; zeros where no step ran.  That call
  * launches its positions eagerly. */

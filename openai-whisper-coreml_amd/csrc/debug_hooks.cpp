@@ -338,17 +338,46 @@ extern "C" int wmdbg_spec_round_batch(int n, int G, int w, const int32_t *in, in
     }
     return n;
 }
-// Scoped to the NEXT wm_transcribe_mel_speculative call on ctx (which clears it, whatever its outcome): the proposal for
-// generated index i of row b of that call is tokens[b * max_new + i].  `tokens` is host memory that lives until the call returns.
+// tx_pending.h on the CPU (documented at include/whisper_mi355x_debug.h): who serves which pending item, and take()
+extern "C" int wmdbg_pending_refusal(unsigned pending, int entry, unsigned flags, int n_cand, char *msg_out, int msg_cap) {
+    if (entry < WmCallKind::PLAIN || entry > WmCallKind::BEAM || !msg_out || msg_cap < 1) return -1;
+    WmCallKind k;
+    k.entry = (WmCallKind::Entry)entry; k.n_cand = n_cand; k.greedy_entry = flags & 1; k.beam = flags & 2; k.windows = flags & 4;
+    k.hyp = flags & 8; k.speculative = flags & 16; k.multi = flags & 32; k.f32_path = flags & 64;
+    const char *no = wm_pending_refusal(pending, k);
+    snprintf(msg_out, (size_t)msg_cap, "%s", no ? no : "");
+    return no ? WM_ERR_STATE : WM_OK;
+}
+extern "C" int wmdbg_pending_take(unsigned bits, unsigned again, int32_t *out) {
+    if (!out) return -1;
+    auto arm = [](WmPending &p, unsigned b, int v) {   // every list one entry of v
+        if (b & WM_PEND_BUDGETS) p.budgets.assign(1, v);
+        if (b & WM_PEND_BIAS_ROWS) p.bias_rows.assign(1, v);
+        if (b & WM_PEND_CST_ROWS) p.cst_rows.assign(1, v);
+        if (b & WM_PEND_SAMP_ROWS) { p.samp_T.assign(1, (float)v); p.samp_seed.assign(1, (uint64_t)v); }
+        if (b & WM_PEND_ALT) { p.alt_on = true; p.alt.n = v; }
+    };
+    WmPending member;
+    arm(member, bits, 1);
+    out[0] = (int32_t)member.bits();
+    const WmPending taken = member.take();   // (out[0]: before it; [1], [2]: what it returned and what it left)
+    out[1] = (int32_t)taken.bits(); out[2] = (int32_t)member.bits();
+    arm(member, again, 2);   // (the taken value is its own: it does not see this)
+    out[3] = (int32_t)taken.bits(); out[4] = (int32_t)member.bits(); out[5] = taken.budgets.empty() ? 0 : taken.budgets[0];
+    return 0;
+}
+// Scoped to the NEXT transcribe call on ctx, which takes it whatever its outcome; wm_transcribe_mel_speculative reads it: the proposal
+// for generated index i of row b of that call is tokens[b * max_new + i].  `tokens` is host memory that lives until the call returns.
 extern "C" int wmdbg_spec_script(wm_ctx *ctx, const int32_t *tokens, int B, int max_new) {
     WM_REQUIRE(ctx && ctx->model, WM_ERR_STATE, "wmdbg_spec_script: context has no model");
     WmModel *m = ctx->model;
-    m->spec_dbg_script = nullptr; m->spec_dbg_script_new = m->spec_dbg_script_rows = 0;
+    WmDebugShots &d = m->pending.dbg;
+    d.spec_script = nullptr; d.spec_script_new = d.spec_script_rows = 0;
     if (!tokens) return WM_OK;
     WM_REQUIRE(B >= 1 && max_new >= 1, WM_ERR_INVALID, "wmdbg_spec_script: B < 1 or max_new < 1");
     for (size_t i = 0; i < (size_t)B * max_new; ++i)
         WM_REQUIRE(tokens[i] >= 0 && tokens[i] < m->dims.n_vocab, WM_ERR_INVALID, "wmdbg_spec_script: token %d outside the vocabulary", tokens[i]);
-    m->spec_dbg_script = tokens; m->spec_dbg_script_new = max_new; m->spec_dbg_script_rows = B;
+    d.spec_script = tokens; d.spec_script_new = max_new; d.spec_script_rows = B;
     return WM_OK;
 }
 // The accept + commit launches of a speculative round alone (spec.hip), timestamp rules off: a group of G windows x w rows at
@@ -1124,27 +1153,19 @@ extern "C" int wmdbg_dtw(wm_ctx *ctx, const float *x, int B, const int32_t *N, c
     return WM_OK;
 }
 
-extern "C" int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out) {
+// the one-shots of the NEXT transcribe call on ctx (WmDebugShots, tx_pending.h): the hooks that arm one
+template <typename T>
+static int arm_shot(wm_ctx *ctx, bool ok, T WmDebugShots::*shot, T v) {
     WM_TRY(wm_ctx_make_current(ctx));
-    WM_REQUIRE(ctx->model && matrix_out, WM_ERR_INVALID, "bad args");
-    ctx->model->align_dbg_matrix = matrix_out;
+    WM_REQUIRE(ctx->model && ok, WM_ERR_INVALID, "bad args");
+    ctx->model->pending.dbg.*shot = v;
     return WM_OK;
 }
-
+extern "C" int wmdbg_align_capture(wm_ctx *ctx, float *matrix_out) { return arm_shot(ctx, matrix_out, &WmDebugShots::align_matrix, matrix_out); }
 // ---- the aligned best-of / beam calls (wm_transcribe_mel_beam_aligned) ----
-extern "C" int wmdbg_align_hyp(wm_ctx *ctx, int h) {
-    WM_TRY(wm_ctx_make_current(ctx));
-    WM_REQUIRE(ctx->model && h >= 0, WM_ERR_INVALID, "bad args");
-    ctx->model->align_dbg_hyp = h;
-    return WM_OK;
-}
-
-extern "C" int wmdbg_hyp_slots(wm_ctx *ctx, int32_t *slots_out) {
-    WM_TRY(wm_ctx_make_current(ctx));
-    WM_REQUIRE(ctx->model && slots_out, WM_ERR_INVALID, "bad args");
-    ctx->model->align_dbg_slots = slots_out;
-    return WM_OK;
-}
+extern "C" int wmdbg_align_hyp(wm_ctx *ctx, int h) { return arm_shot(ctx, h >= 0, &WmDebugShots::align_hyp, h); }
+extern "C" int wmdbg_hyp_slots(wm_ctx *ctx, int32_t *slots_out) { return arm_shot(ctx, slots_out, &WmDebugShots::align_slots, slots_out); }
+extern "C" int wmdbg_beam_trace(wm_ctx *ctx, float *trace_out) { return arm_shot(ctx, trace_out, &WmDebugShots::beam_trace, trace_out); }
 
 extern "C" int wmdbg_beam_ancestry(int N, int max_new, const int32_t *anc, int fin_n, const int32_t *fin_src, const int32_t *fin_len,
                                    int wsteps, const float *sum, int h, int S, int Tq, int32_t *slot) {
@@ -1309,13 +1330,6 @@ extern "C" double wmdbg_rank_score(double sum, int n_text, float length_penalty)
 extern "C" int wmdbg_beam_fill_order(int N, const float *sum, int32_t *order_out) {
     if (N < 1 || N > WM_MAX_BEAM || !sum || !order_out) return -1;
     return wm_beam_fill_order(N, sum, order_out);
-}
-
-extern "C" int wmdbg_beam_trace(wm_ctx *ctx, float *trace_out) {
-    WM_TRY(wm_ctx_make_current(ctx));
-    WM_REQUIRE(ctx->model && trace_out, WM_ERR_INVALID, "bad args");
-    ctx->model->beam_dbg_trace = trace_out;
-    return WM_OK;
 }
 
 // The partials a DE_LOGITS_X launch leaves for a row, restated on the host: per 16-id tile the best allowed text / timestamp

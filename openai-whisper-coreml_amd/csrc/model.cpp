@@ -318,7 +318,7 @@ int wm_model_set_sequence_bias(wm_ctx *ctx, const WmSbTable &t) {
     m->sb_on = ne > 0; m->sb_groups = ng; m->sb_entries = ne;
     // exclusive with the row tables: a table replaces them, the empty table clears both
     m->sbt_on = false; m->sbt_groups = m->sbt_entries = 0; m->sbt_tab_grp.clear();
-    m->bias_rows_host.clear();
+    m->pending.bias_rows.clear();
     return WM_OK;
 }
 
@@ -345,7 +345,7 @@ int wm_model_set_constraint(wm_ctx *ctx, const WmCstTable &t) {
         WM_HIP(hipStreamSynchronize(ctx->stream));   // (the table's vectors are the caller's)
     }
     m->cst_on = ns > 0; m->cst_states = ns; m->cst_edges = ne; m->cst_eot = ns ? t.eot : 0;
-    m->cst_rows_host.clear();
+    m->pending.cst_rows.clear();
     return WM_OK;
 }
 
@@ -388,7 +388,7 @@ int wm_model_set_sequence_bias_tables(wm_ctx *ctx, const WmSbPool &p) {
     }
     m->sbt_on = nt > 0; m->sbt_groups = ng; m->sbt_entries = ne;
     m->sbt_tab_grp = p.tab_grp;
-    m->bias_rows_host.clear();
+    m->pending.bias_rows.clear();
     return WM_OK;
 }
 

@@ -5,6 +5,7 @@
 #pragma once
 #include "wm_internal.h"
 #include "dec_launch.h"   // DecEpi, WM_DEC_MAXB, the launch plans
+#include "tx_pending.h"   // WmPending, WmDebugShots
 
 // ---------------------------------------------------------------- HBM layout ----------
 // All matrix weights are bf16 [N][K] row-major (PyTorch Linear layout: K contiguous), so
@@ -489,7 +490,9 @@ struct WmModel {
     // early stop (wm_transcribe_greedy with eot >= 0 or per-chunk token budgets): see WmStopDev
     int *ddone = nullptr, *dbudget = nullptr, *dlive = nullptr, *dnlive = nullptr;
     int *h_nlive = nullptr;     // pinned host ring: n_live after each burst of positions (the host polls it)
-    std::vector<int32_t> budget_host;  // wm_set_token_budgets: per-chunk budgets of the NEXT call (empty: none)
+    // What the setters arm for the NEXT transcribe call (and pending.dbg, the debug library's one-shots): ONE value that the call
+    // takes whole, in front of its checks (tx_pending.h).  Per call, not per context: wm_clone has nothing to copy.
+    WmPending pending;
     // Captured decode steps: one hipGraph of ONE position, and one of WM_BURST consecutive positions (the arg-max kernel
     // advances the device-side position, so consecutive positions do not depend on the host: 1/8 of the graph launches).
     // Everything a capture bakes into its kernel arguments is in the key (the shape and the WmDecodeMode it was captured
@@ -549,10 +552,8 @@ struct WmModel {
     float samp_p = 1.f, samp_minp = 0.f;
     bool samp_on() const { return samp_k > 0 || samp_p < 1.f || samp_minp > 0.f; }
     WmSampPar *dsamp_par = nullptr;
-    // alternatives (wm_request_alternatives): the request pending for the NEXT transcribe call, the device block a group's
-    // prefill writes and the group's output buffers [tok | lp | cnt | ent] (reserved and pad-filled at prefill, grow-only)
-    bool alt_pending = false;
-    wm_alternatives_out alt_req = {};
+    // alternatives (wm_request_alternatives): the device block a group's prefill writes and the group's output buffers
+    // [tok | lp | cnt | ent] (reserved and pad-filled at prefill, grow-only)
     WmAltPar *dalt_par = nullptr;
     WmDevBuf alt_ws;
     // sequence bias (wm_set_sequence_bias): the context's expanded table, and the device state allocated at full capacity when
@@ -568,31 +569,21 @@ struct WmModel {
     std::vector<int32_t> sbt_tab_grp;   // [n_tables + 1]
     WmSbDev dsbt = {};
     int *dsb_rng = nullptr;             // [WM_DEC_MAXB][2]
-    std::vector<int32_t> bias_rows_host;   // wm_set_bias_rows: the table of each row of the NEXT call (empty: none pending)
     // constraint (wm_set_constraint): the automaton's counts, and the device tables allocated at full capacity when first switched
     // on (dcst.par == null before that) -- never moved: the captured graphs hold the addresses; dcst.start is the group's row starts
     bool cst_on = false;
     int cst_states = 0, cst_edges = 0, cst_eot = 0;
     WmCstDev dcst = {};
-    std::vector<int32_t> cst_rows_host;    // wm_set_constraint_rows: the start state of each row of the NEXT call (empty: none pending)
-    // wm_set_sampling_rows: temperature and seed of each row of the NEXT call (empty: none pending; the two have one length)
-    std::vector<float> samp_rows_T;
-    std::vector<uint64_t> samp_rows_seed;
     // [2][WM_XIDS_CAND] per-row sample ids of the group (WmXPar::ids_on) | candidate words, and behind the two, at WM_XIDS_ROWS,
     // [WM_XIDS_CAND] WmXRow: the rows' (1 / T, seed) of wm_set_sampling_rows (wm_x_rows), uploaded at prefill like the ids
     unsigned *dx_ids = nullptr;
     WmMelWin *dmel_win = nullptr;  // [WM_DEC_MAXB] the group's mel windows (wm_transcribe_mel)
     int *dxkv_rows = nullptr;      // [WM_DEC_MAXB] the group's rows of a window set (wm_transcribe_windows): the gather's row map
-    // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..), the
-    // workspace of a call (grown on demand) and the debug library's one-shot cost-matrix capture (host, null in the product)
+    // wm_align: the alignment heads (empty: openai-whisper's default, every head of layers n_text_layer / 2 ..) and the
+    // workspace of a call (grown on demand)
     std::vector<int32_t> align_l, align_h;
     WmDevBuf align_ws;
     WmDevBuf acap_ws;   // an aligned transcribe group's capture buffer and alignment workspace (reserved at prefill, grow-only)
-    float *align_dbg_matrix = nullptr;
-    // debug library, one-shot each: the hypothesis the next aligned best-of / beam call aligns instead of best_out (-1: none),
-    // and where that call leaves its slot tables [B][Tq]
-    int align_dbg_hyp = -1;
-    int32_t *align_dbg_slots = nullptr;
     int teacher_panel = 1;   // wm_set_teacher_panel: positions per step of the teacher-forced passes (a launch policy: same bits)
     // wm_set_prompt_panel: positions per step of a transcribe group's prompt prefill (1: none -- every prompt position is an
     // ordinary step; a launch policy: same bits), and what the context's last group prefill enqueued (P0, slices, panel steps;
@@ -600,18 +591,14 @@ struct WmModel {
     int prompt_panel = 1;
     int last_prefill[3] = {0, 0, 0};
     // wm_transcribe_mel_beam: the group's beam state (WmBeamDev; allocated once at its largest size, so captured graphs keep
-    // their addresses) and the debug library's one-shot trace capture (host destination, null in the product) with its
-    // device buffer
+    // their addresses) and the device buffer of the debug library's trace capture
     WmDevBuf beam_ws;
-    float *beam_dbg_trace = nullptr;
     WmDevBuf beam_trace;
     bool beam_trace_on = false;   // the group decoding on this context right now writes its trace
-    // wm_transcribe_mel_speculative: the group's state (WmSpecDev), the pinned ring the host reads a round's (live windows,
-    // position) from, and the debug library's scoped proposal script (host, [B][max_new]; null in the product)
+    // wm_transcribe_mel_speculative: the group's state (WmSpecDev) and the pinned ring the host reads a round's (live windows,
+    // position) from
     WmDevBuf spec_ws;
     int *h_spec = nullptr;
-    const int32_t *spec_dbg_script = nullptr;
-    int spec_dbg_script_new = 0, spec_dbg_script_rows = 0;
     WmDevBuf pcm_stage;   // host-pointer staging of a decode group's PCM (wm_transcribe*, wm_align)
     WmDevBuf io_stage;    // staging for host-pointer model calls
 };

@@ -218,20 +218,20 @@ extern "C" int wm_set_sequence_bias_tables(wm_ctx *ctx, const int32_t *tokens, c
     WM_REQUIRE(n_tables == 0 || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
     return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { return wm_model_set_sequence_bias_tables(c, p); });
 } WM_API_CATCH
+// The two i32 row maps of WmModel::pending: a bad list; n == 0 drops the pending map; what must be in force; every value in
+// [-1, hi).  A refused call leaves the pending map as it was.
+static int set_row_map(std::vector<int32_t> *map, const char *who, const int32_t *v, int n, bool in_force, const char *needs,
+                       const char *what, int hi) {
+    WM_REQUIRE(n >= 0 && (n == 0 || v), WM_ERR_INVALID, "%s: bad list", who);
+    WM_REQUIRE(n == 0 || in_force, WM_ERR_STATE, "%s: the context has no %s", who, needs);
+    for (int i = 0; i < n; ++i) WM_REQUIRE(v[i] >= -1 && v[i] < hi, WM_ERR_INVALID, "%s: %s %d of row %d outside [-1, %d)", who, what, v[i], i, hi);
+    map->assign(v, v + n);
+    return WM_OK;
+}
 extern "C" int wm_set_bias_rows(wm_ctx *ctx, const int32_t *table_of_row, int n) try {
     WM_MODEL(ctx);
-    WM_REQUIRE(n >= 0 && (n == 0 || table_of_row), WM_ERR_INVALID, "set_bias_rows: bad list");
-    if (n == 0) {
-        m->bias_rows_host.clear();
-        return WM_OK;
-    }
-    WM_REQUIRE(m->sbt_on, WM_ERR_STATE, "set_bias_rows: the context has no sequence-bias tables (wm_set_sequence_bias_tables)");
-    const int nt = (int)m->sbt_tab_grp.size() - 1;
-    for (int i = 0; i < n; ++i)
-        WM_REQUIRE(table_of_row[i] >= -1 && table_of_row[i] < nt, WM_ERR_INVALID, "set_bias_rows: table %d of row %d outside [-1, %d)",
-                   table_of_row[i], i, nt);
-    m->bias_rows_host.assign(table_of_row, table_of_row + n);
-    return WM_OK;
+    return set_row_map(&m->pending.bias_rows, "set_bias_rows", table_of_row, n, m->sbt_on,
+                       "sequence-bias tables (wm_set_sequence_bias_tables)", "table", (int)m->sbt_tab_grp.size() - 1);
 } WM_API_CATCH
 extern "C" int wm_set_constraint(wm_ctx *ctx, const int32_t *edge_beg, const int32_t *edge_tok, const int32_t *edge_next,
                                  const int32_t *def_next, const uint8_t *accept, int n_states, int32_t eot) try {
@@ -244,22 +244,12 @@ extern "C" int wm_set_constraint(wm_ctx *ctx, const int32_t *edge_beg, const int
 } WM_API_CATCH
 extern "C" int wm_set_constraint_rows(wm_ctx *ctx, const int32_t *start_of_row, int n) try {
     WM_MODEL(ctx);
-    WM_REQUIRE(n >= 0 && (n == 0 || start_of_row), WM_ERR_INVALID, "set_constraint_rows: bad list");
-    if (n == 0) {
-        m->cst_rows_host.clear();
-        return WM_OK;
-    }
-    WM_REQUIRE(m->cst_on, WM_ERR_STATE, "set_constraint_rows: the context has no automaton (wm_set_constraint)");
-    for (int i = 0; i < n; ++i)
-        WM_REQUIRE(start_of_row[i] >= -1 && start_of_row[i] < m->cst_states, WM_ERR_INVALID,
-                   "set_constraint_rows: start state %d of row %d outside [-1, %d)", start_of_row[i], i, m->cst_states);
-    m->cst_rows_host.assign(start_of_row, start_of_row + n);
-    return WM_OK;
+    return set_row_map(&m->pending.cst_rows, "set_constraint_rows", start_of_row, n, m->cst_on, "automaton (wm_set_constraint)",
+                       "start state", m->cst_states);
 } WM_API_CATCH
 extern "C" int wm_set_sampling_rows(wm_ctx *ctx, const float *temperature, const uint64_t *seed, int n) try {
     WM_MODEL(ctx);
-    m->samp_rows_T.clear();   // whatever happens below, the map that was pending is gone
-    m->samp_rows_seed.clear();
+    m->pending.samp_T.clear(); m->pending.samp_seed.clear();   // whatever happens below, the map that was pending is gone
     WM_REQUIRE(n >= 0 && (n == 0 || (temperature && seed)), WM_ERR_INVALID, "set_sampling_rows: bad list");
     for (int i = 0; i < n; ++i) {
         const float T = temperature[i];
@@ -268,8 +258,7 @@ extern "C" int wm_set_sampling_rows(wm_ctx *ctx, const float *temperature, const
         WM_REQUIRE(T == 0.f || std::isfinite((float)(1.0 / (double)T)), WM_ERR_INVALID,
                    "set_sampling_rows: temperature %g of row %d is too small: 1 / T overflows", (double)T, i);
     }
-    m->samp_rows_T.assign(temperature, temperature + n);
-    m->samp_rows_seed.assign(seed, seed + n);
+    m->pending.samp_T.assign(temperature, temperature + n); m->pending.samp_seed.assign(seed, seed + n);
     return WM_OK;
 } WM_API_CATCH
 extern "C" int wm_set_teacher_panel(wm_ctx *ctx, int width) try {
@@ -581,22 +570,18 @@ extern "C" int wm_set_token_budgets(wm_ctx *ctx, const int32_t *budgets, int n) 
     WM_REQUIRE(n >= 0 && (n == 0 || budgets), WM_ERR_INVALID, "set_token_budgets: bad list");
     for (int i = 0; i < n; ++i)
         WM_REQUIRE(budgets[i] >= 1, WM_ERR_INVALID, "set_token_budgets: budget %d of chunk %d is < 1", budgets[i], i);
-    m->budget_host.assign(budgets, budgets + n);
+    m->pending.budgets.assign(budgets, budgets + n);
     return WM_OK;
 } WM_API_CATCH
 
 extern "C" int wm_request_alternatives(wm_ctx *ctx, const wm_alternatives_out *req) try {
     WM_MODEL(ctx);
-    if (!req) {
-        m->alt_pending = false;
-        return WM_OK;
-    }
+    if (!req) { m->pending.alt_on = false; return WM_OK; }   // (drops a pending request)
     WM_REQUIRE(req->n >= 1 && req->n <= WM_MAX_ALTERNATIVES, WM_ERR_INVALID, "request_alternatives: n %d outside [1, %d]", req->n,
                WM_MAX_ALTERNATIVES);
     WM_REQUIRE(req->tokens && req->logprobs, WM_ERR_INVALID, "request_alternatives: null tokens / logprobs");
     WM_REQUIRE(req->rows >= 1 && req->max_new >= 1, WM_ERR_INVALID, "request_alternatives: rows or max_new below 1");
-    m->alt_req = *req;
-    m->alt_pending = true;
+    m->pending.alt = *req; m->pending.alt_on = true;
     return WM_OK;
 } WM_API_CATCH
 
@@ -830,8 +815,7 @@ extern "C" int wm_align(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int B,
                         float *token_prob_out, wm_mem mem) try {
     WM_MODEL(ctx);
     AlignCall c;
-    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
-    m->align_dbg_matrix = nullptr;
+    c.dbg_matrix = std::exchange(m->pending.dbg.align_matrix, nullptr);   // the debug library's capture is for this call only
     WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
     WM_REQUIRE(pcm && sot_seq && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
     WM_REQUIRE(pcm_dtype == WM_I16 || pcm_dtype == WM_F32 || pcm_dtype == WM_F64, WM_ERR_INVALID, "bad pcm dtype");
@@ -850,8 +834,7 @@ extern "C" int wm_align_mel(wm_ctx *ctx, const float *mel, const int64_t *mel_ba
                             wm_mem mem) try {
     WM_MODEL(ctx);
     AlignCall c;
-    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
-    m->align_dbg_matrix = nullptr;
+    c.dbg_matrix = std::exchange(m->pending.dbg.align_matrix, nullptr);   // the debug library's capture is for this call only
     WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
     WM_REQUIRE(mel && mel_base && mel_len && seek && n_frames, WM_ERR_INVALID, "null mel / window pointer");
     WM_REQUIRE(sot_seqs && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
@@ -947,8 +930,7 @@ extern "C" int wm_align_windows(wm_ctx *ctx, const wm_windows *w, const int32_t 
                                 float *token_prob_out) try {
     WM_MODEL(ctx);
     AlignCall c;
-    c.dbg_matrix = m->align_dbg_matrix;   // the debug library's capture is for this call only
-    m->align_dbg_matrix = nullptr;
+    c.dbg_matrix = std::exchange(m->pending.dbg.align_matrix, nullptr);   // the debug library's capture is for this call only
     WM_REQUIRE(m->finalized, WM_ERR_STATE, "model weights not finalised (wm_finalize)");
     WM_REQUIRE(sot_seqs && n_text && start_frame_out && (max_text == 0 || text_tokens), WM_ERR_INVALID, "null pointer");
     WM_REQUIRE(B >= 1, WM_ERR_INVALID, "B < 1");

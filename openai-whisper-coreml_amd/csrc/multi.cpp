@@ -218,20 +218,19 @@ extern "C" int wm_multi_transcribe_greedy(wm_multi *m, const void *pcm, wm_dtype
     for (int r = 0; r < R; ++r)
         WM_REQUIRE(!m->ctx[r]->model || !m->ctx[r]->model->cst_on, WM_ERR_STATE,
                    "multi_transcribe_greedy does not support a constraint (device context %d has an automaton)", r);
-    {   // a request for alternatives pending on a device context is consumed and refused (its rows are the device's slice: not built)
-        bool alt = false;
+    {   // A request for alternatives or a sampling row map pending on a device context is consumed and refused (not built); the
+        // budgets stay for each worker's own wm_transcribe_greedy.  (The other row maps' setters need what was just refused.)
+        WmCallKind k;
+        k.greedy_entry = k.multi = true;
+        unsigned pending = 0;
         for (int r = 0; r < R; ++r)
-            if (m->ctx[r]->model && m->ctx[r]->model->alt_pending) { alt = true; m->ctx[r]->model->alt_pending = false; }
-        WM_REQUIRE(!alt, WM_ERR_STATE, "multi_transcribe_greedy does not serve alternatives (wm_request_alternatives)");
-    }
-    {   // a sampling row map pending on a device context likewise (wm_set_sampling_rows)
-        bool rows = false;
-        for (int r = 0; r < R; ++r)
-            if (m->ctx[r]->model && !m->ctx[r]->model->samp_rows_T.empty()) {
-                rows = true;
-                m->ctx[r]->model->samp_rows_T.clear(); m->ctx[r]->model->samp_rows_seed.clear();
+            if (WmModel *dm = m->ctx[r]->model) {
+                WmPending p = dm->pending.take();
+                dm->pending.budgets.swap(p.budgets);
+                pending |= p.bits();
             }
-        WM_REQUIRE(!rows, WM_ERR_STATE, "multi_transcribe_greedy takes no sampling row map (wm_set_sampling_rows)");
+        const char *no = wm_pending_refusal(pending, k);
+        WM_REQUIRE(!no, WM_ERR_STATE, "%s", no);
     }
     {   // every size that feeds an allocation below is checked against the model BEFORE any thread exists
         const wm_dims &D = m->ctx[0]->model->dims;

@@ -124,15 +124,10 @@ struct LaneJob {
 
 // A transcribe call: its rows (PCM chunks, mel windows or the rows of a window set), their prompts, what decodes them
 // (arg-max / sampling, best_of candidates, beams) and where the results go.
-struct TxCall {
-    enum Entry { PLAIN, MEL, RAGGED, BEST_OF, BEAM } entry = PLAIN;   // whose own checks run first
-    bool greedy_entry = false;   // wm_transcribe_greedy: no options, so no per-row ones either (wm_set_sampling_rows is refused)
+struct TxCall : WmCallKind {   // (tx_pending.h: the entry, greedy_entry, n_cand, beam, windows, hyp ...)
     WmAudioSrc src;
     TxPrompts prompts;
     int n_prompt = 0;   // the prompt length of a uniform call (a ragged call: TxCfg::n_prompt, found by validation)
-    int n_cand = 1;     // candidates per row (wm_transcribe_mel_best_of): every row decodes n_cand times over ONE encoder pass
-    // wm_transcribe_mel_beam: the n_cand rows of a window are its BEAMS (n_cand = beam width, 1 included)
-    bool beam = false;
     int max_cand = 0;
     float length_penalty = NAN;   // of the ranking step
     int B = 0, max_new = 0;
@@ -144,16 +139,12 @@ struct TxCall {
     int32_t *best_out = nullptr;      // [B], nullable: the ranking step's choice
     int32_t *n_hyp = nullptr;   // beam: [B]
     float *sums = nullptr;      // beam: [B][S]
-    float *trace = nullptr;     // beam, debug library: [B][max_new][n_cand][WM_BEAM_TRACE] (null in the product)
     // wm_transcribe_mel_aligned / wm_transcribe_windows_aligned: word-timestamp alignment from the decode's own queries
-    // hyp (the best-of and beam counterparts): a window decodes n_cand rows and aligns hypothesis best_out[b] alone
-    bool aligned = false, hyp = false;
+    bool aligned = false;
     int medfilt = 0;
     float qk_scale = 1.f;
     int32_t *start_out = nullptr;   // [B][max_new + 1]
-    float *dbg_matrix = nullptr;    // debug library: [B][max_new + 1][1500] (null in the product)
-    int dbg_hyp = -1;               // debug library: align hypothesis min(dbg_hyp, n_hyp - 1) instead (-1 in the product)
-    int32_t *dbg_slots = nullptr;   // debug library: the slot tables [B][Tq] (null in the product)
+    WmDebugShots dbg;   // debug library: the one-shots the call took, a beam call's trace and an aligned call's captures alone
     // hypotheses per window of the outputs: tokens_out [B][S][max_new]
     int out_stride() const { return beam ? std::max(n_cand, max_cand) : n_cand; }
     wm_mem mem = WM_MEM_HOST;
@@ -185,14 +176,10 @@ struct TxCfg {
     int sot_tail = 0;
     std::vector<int32_t> hl, hh;
     int max_group_rows = 0;
-    const int32_t *bias_rows = nullptr;   // row tables in force: the table of each row of the call [B] (wm_set_bias_rows), checked
-    const wm_alternatives_out *alt = nullptr;   // the call's alternatives request (wm_request_alternatives), checked; null: none
-    // a constraint in force: the start state of each row of the call [B] (wm_set_constraint_rows), checked; null: every row starts in 0
-    const int32_t *cst_rows = nullptr;
-    // a sampling row map in force (wm_set_sampling_rows) with at least one sampling row: temperature and seed of each row of the
-    // call [B], checked; null: opts->temperature and opts->seed hold for every row
-    const float *samp_T = nullptr;
-    const uint64_t *samp_seed = nullptr;
+    // What the call took (tx_take), checked: the row maps are [B] of the call where what they map is in force -- bias_rows with
+    // row tables; cst_rows with a constraint (empty: every row starts in 0); alt_on: the call's alternatives request.
+    const WmPending *pending = &wm_nothing_pending();
+    bool samp_rows = false;   // the sampling row map has a sampling row (else opts->temperature and opts->seed hold for every row)
 };
 
 // the tokens row `b` of the call may generate
@@ -218,8 +205,9 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     // (tx_validate turns the extended decode on with them; the bias and the constraint use the rules' bitmaps)
     j.mode.rep = m->rep_on || j.mode.sb || j.mode.cst;
     j.mode.trunc = m->samp_on() && xc.on && xc.par.sample != 0;   // temperature 0 ignores the sampling rules: today's launches
-    j.mode.srows = xc.on && cfg.samp_T != nullptr;   // (a row map: the launch is in the plan when any row of the CALL samples)
-    j.mode.alt = cfg.alt != nullptr;   // (tx_validate turned the extended decode on with it)
+    const WmPending &pend = *cfg.pending;
+    j.mode.srows = xc.on && cfg.samp_rows;   // (a row map: the launch is in the plan when any row of the CALL samples)
+    j.mode.alt = pend.alt_on;   // (tx_validate turned the extended decode on with it)
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
     if (call.aligned) {   // the capture buffer and the alignment workspace, reserved before anything is enqueued
@@ -237,7 +225,7 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
         }
         j.mode.acap = true; j.mode.acap_base = j.P - cfg.sot_tail; j.mode.acap_Tq = j.aw.Tq; j.mode.acap_J = J;
         j.mode.acap_q = (float *)((char *)m->acap_ws.p + j.aw.q);
-        if (call.dbg_matrix) WM_HIP(hipMemsetAsync((char *)m->acap_ws.p + j.aw.x, 0, (size_t)Cg * j.aw.n_ld * 1500 * 4, c->stream));
+        if (call.dbg.align_matrix) WM_HIP(hipMemsetAsync((char *)m->acap_ws.p + j.aw.x, 0, (size_t)Cg * j.aw.n_ld * 1500 * 4, c->stream));
     }
     const void *d_pcm;
     WM_TRY(wm_stage_pcm(c, call.src, j.b0, Cg, call.mem, &d_pcm));
@@ -265,8 +253,8 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
         if (j.mode.srows) {   // the rows' own 1 / T and keys, padded with arg-max rows like the ids (the epilogue's 16-row blocks)
             j.samp.assign(WM_XIDS_CAND, WmXRow{0.f, 0u, 0u, 0u});
             for (int r = 0; r < Bg; ++r) {
-                const float T = cfg.samp_T[j.b0 + r / N];
-                const uint64_t seed = cfg.samp_seed[j.b0 + r / N];
+                const float T = pend.samp_T[j.b0 + r / N];
+                const uint64_t seed = pend.samp_seed[j.b0 + r / N];
                 if (T > 0.f) j.samp[r] = WmXRow{(float)(1.0 / (double)T), (unsigned)seed, (unsigned)(seed >> 32), 0u};
             }
             WM_HIP(hipMemcpyAsync((void *)wm_x_rows(m->dx_ids), j.samp.data(), j.samp.size() * sizeof(WmXRow), hipMemcpyHostToDevice, c->stream));
@@ -290,12 +278,12 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     // reserved for this group and pad-filled here, so positions no workgroup writes (finished rows) read as pads
     if (j.mode.alt) {
         WM_REQUIRE(xc.on, WM_ERR_STATE, "alternatives need the extended decode");
-        WM_TRY(wm_model_alt_begin(c, Bg, call.max_new, cfg.alt->n, &j.apar));
+        WM_TRY(wm_model_alt_begin(c, Bg, call.max_new, pend.alt.n, &j.apar));
     }
     // sequence bias: the table was uploaded when it was set; its counts go with the group, so a captured graph replays for any table
     if (j.mode.sbt) {   // row tables: the pool was uploaded when it was set; the rows' group ranges go with the group likewise
-        WM_REQUIRE(cfg.bias_rows, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
-        wm_group_bias_rows(cfg.bias_rows, m->sbt_tab_grp.data(), (int)m->sbt_tab_grp.size() - 1, j.b0, Cg, N, &j.tab.sbr);
+        WM_REQUIRE(!pend.bias_rows.empty(), WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
+        wm_group_bias_rows(pend.bias_rows.data(), m->sbt_tab_grp.data(), (int)m->sbt_tab_grp.size() - 1, j.b0, Cg, N, &j.tab.sbr);
         WM_HIP(hipMemcpyAsync(m->dsb_rng, j.tab.sbr.data(), j.tab.sbr.size() * 4, hipMemcpyHostToDevice, c->stream));
     } else if (j.mode.sb) {
         j.sbpar.n_groups = m->sb_groups; j.sbpar.n_entries = m->sb_entries;
@@ -306,7 +294,7 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     if (j.mode.cst) {
         j.cpar.n_states = m->cst_states; j.cpar.n_edges = m->cst_edges; j.cpar.eot = m->cst_eot;
         j.cstart.resize(Bg);
-        for (int r = 0; r < Bg; ++r) j.cstart[r] = cfg.cst_rows ? cfg.cst_rows[j.b0 + r / N] : 0;
+        for (int r = 0; r < Bg; ++r) j.cstart[r] = pend.cst_rows.empty() ? 0 : pend.cst_rows[j.b0 + r / N];
         WM_HIP(hipMemcpyAsync((void *)m->dcst.par, &j.cpar, sizeof(WmCstPar), hipMemcpyHostToDevice, c->stream));
         WM_HIP(hipMemcpyAsync((void *)m->dcst.start, j.cstart.data(), (size_t)Bg * 4, hipMemcpyHostToDevice, c->stream));
     }
@@ -315,8 +303,8 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     if (call.beam) {   // beam state: nothing finished, every sum 0; a window's budget is its own max_new
         j.bbud.resize(Cg);
         for (int w = 0; w < Cg; ++w) j.bbud[w] = stop_budget(stop, j.b0 + w, j.bpar.max_new);
-        m->beam_trace_on = call.trace != nullptr;
-        if (call.trace) {
+        m->beam_trace_on = call.dbg.beam_trace != nullptr;
+        if (call.dbg.beam_trace) {
             const size_t bytes = (size_t)j.bpar.max_new * Bg * WM_BEAM_TRACE * 4;
             WM_TRY(m->beam_trace.reserve(c->stream, bytes));
             WM_HIP(hipMemsetAsync(m->beam_trace.p, 0, bytes, c->stream));
@@ -482,9 +470,9 @@ void beam_drain(const LaneJob &j, const TxCall &call) {
             call.sums[o] = -INFINITY;
         }
         if (no_speech_out) no_speech_out[W] = j.ns[(size_t)w * N];   // beam 0's
-        if (call.trace)     // [gi][row of the group] -> [window of the call][gi][beam]
+        if (call.dbg.beam_trace)     // [gi][row of the group] -> [window of the call][gi][beam]
             for (int gi = 0; gi < max_new; ++gi)
-                memcpy(call.trace + (((size_t)W * max_new + gi) * N) * WM_BEAM_TRACE,
+                memcpy(call.dbg.beam_trace + (((size_t)W * max_new + gi) * N) * WM_BEAM_TRACE,
                        j.btrace.data() + ((size_t)gi * j.Bg + (size_t)w * N) * WM_BEAM_TRACE, (size_t)N * WM_BEAM_TRACE * 4);
     }
 }
@@ -569,13 +557,25 @@ int entry_checks(const TxCall &call) {
     return WM_OK;
 }
 
+// What a call takes with it when it begins, in front of every check (tx_pending.h); it learns here whether it runs on the all-f32 path.
+WmPending tx_take(wm_ctx *ctx, TxCall &call) {
+    call.f32_path = ctx && ctx->dbg_hooks;
+    return ctx && ctx->model ? ctx->model->pending.take() : WmPending();
+}
+int tx_served(unsigned bits, const TxCall &call) {   // does the call serve the pending items `bits` names?
+    const char *no = wm_pending_refusal(bits, call);
+    WM_REQUIRE(!no, WM_ERR_STATE, "%s", no);
+    return WM_OK;
+}
+
 // The checks every transcribe call goes through, and what they make of it: the call's longest prompt, the early stop, the
-// extended decode.  budgets: the call's (wm_set_token_budgets), clamped to max_new here.  opts == null with both extra
-// outputs null is the greedy decode exactly.
-int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, TxCfg *cfg, const std::vector<int32_t> *bias_rows = nullptr,
-                const wm_alternatives_out *alt = nullptr, const std::vector<int32_t> *cst_rows = nullptr,
-                const std::vector<float> *samp_T = nullptr, const std::vector<uint64_t> *samp_seed = nullptr) {
+// extended decode.  pending: what the call took (tx_take) -- its budgets are clamped to max_new here, and cfg points into it.
+// opts == null with both extra outputs null is the greedy decode exactly.
+int tx_validate(wm_ctx *ctx, const TxCall &call, WmPending &pending, TxCfg *cfg) {
     WmModel *m = ctx->model;
+    cfg->pending = &pending;
+    std::vector<int32_t> &budgets = pending.budgets;
+    const wm_alternatives_out *alt = pending.alt_on ? &pending.alt : nullptr;
     const WmAudioSrc &src = call.src;
     const TxPrompts &p = call.prompts;
     const int B = call.B, max_new = call.max_new;
@@ -631,45 +631,39 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     WM_REQUIRE(!call.beam || T == 0.f, WM_ERR_INVALID, "beam search decodes at temperature 0 (got %g)", (double)T);
     // the call's sampling row map (wm_set_sampling_rows checked the values): opts->temperature and opts->seed are validated above
     // and not read below.  A map without a sampling row is the temperature-0 call.
-    const bool rows_map = samp_T != nullptr;
+    const std::vector<float> &samp_T = pending.samp_T;
+    const bool rows_map = !samp_T.empty();
     bool sampling = T > 0.f;
     if (rows_map) {
-        WM_REQUIRE((int)samp_T->size() == B && samp_seed && samp_seed->size() == samp_T->size(), WM_ERR_INVALID,
-                   "the sampling row map was set for %d rows, the call has %d", (int)samp_T->size(), B);
+        WM_REQUIRE((int)samp_T.size() == B && pending.samp_seed.size() == samp_T.size(), WM_ERR_INVALID,
+                   "the sampling row map was set for %d rows, the call has %d", (int)samp_T.size(), B);
         sampling = false;
-        for (int b = 0; b < B; ++b) sampling = sampling || (*samp_T)[b] > 0.f;
-        if (sampling) { cfg->samp_T = samp_T->data(); cfg->samp_seed = samp_seed->data(); }
+        for (int b = 0; b < B; ++b) sampling = sampling || samp_T[b] > 0.f;
+        cfg->samp_rows = sampling;
     }
     // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
     xc.on = sampling || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || m->cst_on || alt;
     if (alt) {   // the call's alternatives request (wm_request_alternatives checked n and the pointers)
-        WM_REQUIRE(!call.beam, WM_ERR_STATE, "alternatives are not served by beam-search calls");
-        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "alternatives are not supported by the all-f32 precision path");
+        WM_TRY(tx_served(WM_PEND_ALT, call));
         WM_REQUIRE(alt->rows == (int64_t)B * call.n_cand && alt->max_new == max_new, WM_ERR_INVALID,
                    "alternatives were requested for %lld rows x %d tokens, the call has %lld x %d", (long long)alt->rows, alt->max_new,
                    (long long)B * call.n_cand, max_new);
-        cfg->alt = alt;
     }
     WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
     WM_REQUIRE(!(m->sb_on || m->sbt_on) || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");
     WM_REQUIRE(!(m->samp_on() && sampling) || !ctx->dbg_hooks, WM_ERR_STATE, "the sampling rules are not supported by the all-f32 precision path");
+    // The two row maps' VALUES were checked by their setters against the context's tables / automaton, and whatever replaces those
+    // (wm_model_set_sequence_bias, .._tables, wm_model_set_constraint) clears the pending map of the context it changes; wm_clone
+    // starts without one.  So a map that arrives here fits what is in force on the CONTEXT: only its length is the call's.
     if (m->sbt_on) {   // row tables: the call's row map (wm_set_bias_rows), one entry per row of the call
-        WM_REQUIRE(bias_rows, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
-        WM_REQUIRE((int)bias_rows->size() == B, WM_ERR_INVALID, "the bias row map was set for %d rows, the call has %d", (int)bias_rows->size(), B);
-        const int nt = (int)m->sbt_tab_grp.size() - 1;
-        for (int b = 0; b < B; ++b)
-            WM_REQUIRE((*bias_rows)[b] >= -1 && (*bias_rows)[b] < nt, WM_ERR_INVALID, "bias row map: table %d of row %d outside [-1, %d)",
-                       (*bias_rows)[b], b, nt);
-        cfg->bias_rows = bias_rows->data();
+        const int n = (int)pending.bias_rows.size();
+        WM_REQUIRE(n, WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
+        WM_REQUIRE(n == B, WM_ERR_INVALID, "the bias row map was set for %d rows, the call has %d", n, B);
     }
     WM_REQUIRE(!m->cst_on || !ctx->dbg_hooks, WM_ERR_STATE, "the constraint is not supported by the all-f32 precision path");
-    if (m->cst_on && cst_rows) {   // the call's start states (wm_set_constraint_rows), one per row of the call; none: every row starts in 0
-        WM_REQUIRE((int)cst_rows->size() == B, WM_ERR_INVALID, "the constraint row map was set for %d rows, the call has %d", (int)cst_rows->size(), B);
-        for (int b = 0; b < B; ++b)
-            WM_REQUIRE((*cst_rows)[b] >= -1 && (*cst_rows)[b] < m->cst_states, WM_ERR_INVALID,
-                       "constraint row map: start state %d of row %d outside [-1, %d)", (*cst_rows)[b], b, m->cst_states);
-        cfg->cst_rows = cst_rows->data();
-    }
+    // the call's start states (wm_set_constraint_rows), one per row of the call; none: every row starts in 0
+    WM_REQUIRE(!m->cst_on || pending.cst_rows.empty() || (int)pending.cst_rows.size() == B, WM_ERR_INVALID,
+               "the constraint row map was set for %d rows, the call has %d", (int)pending.cst_rows.size(), B);
     xc.logprobs = call.logprobs_out;
     xc.no_speech = call.no_speech_out;
     const uint64_t seed = (opts && !rows_map) ? opts->seed : 0;
@@ -677,11 +671,11 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, std::vector<int32_t> &budgets, 
     xc.par.key1 = (unsigned)(seed >> 32);
     xc.par.sample = sampling ? 1 : 0;
     xc.par.inv_T = (T > 0.f && !rows_map) ? (float)(1.0 / (double)T) : 0.f;
-    xc.par.rows_on = cfg->samp_T ? 1 : 0;   // the rows' own 1 / T and keys: behind WmXDev::ids (lane_prefill)
+    xc.par.rows_on = cfg->samp_rows ? 1 : 0;  // the rows' own 1 / T and keys: behind WmXDev::ids (lane_prefill)
     xc.par.sot_pos = call.no_speech_out ? sot_index : -1;
     xc.par.ns_tok = ns_tok;
     const bool no_stop = g_wm_tuning.no_early_stop != 0;   // probes only: decode every position, truncate on the host
-    cfg->use_graph = !wm_graphs_off() && !ctx->prof.on && !call.trace;   // (a traced call bakes nothing into graphs)
+    cfg->use_graph = !wm_graphs_off() && !ctx->prof.on && !call.dbg.beam_trace;   // (a traced call bakes nothing into graphs)
     cfg->stop.on = !no_stop && (call.eot >= 0 || !budgets.empty());
     cfg->stop.eot = call.eot;
     cfg->stop.budgets = budgets.empty() ? nullptr : budgets.data();
@@ -831,7 +825,7 @@ int lane_fetch(TxRun &r, LaneJob &j) {
         WM_HIP(hipMemcpyAsync(j.acnt.data(), j.apar.cnt, np * 4, hipMemcpyDeviceToHost, j.c->stream));
         WM_HIP(hipMemcpyAsync(j.aent.data(), j.apar.ent, np * 4, hipMemcpyDeviceToHost, j.c->stream));
     }
-    if (call.beam) WM_TRY(beam_fetch(j, call.max_new, call.trace != nullptr));
+    if (call.beam) WM_TRY(beam_fetch(j, call.max_new, call.dbg.beam_trace != nullptr));
     j.state = LaneJob::DRAINING;
     return WM_OK;
 }
@@ -887,7 +881,7 @@ int lane_align(TxRun &r, LaneJob &j) {
         int h = 0;
         if (call.hyp) {
             h = call.best_out[W];
-            if (call.dbg_hyp >= 0) h = std::min(call.dbg_hyp, (call.beam ? call.n_hyp[W] : N) - 1);
+            if (call.dbg.align_hyp >= 0) h = std::min(call.dbg.align_hyp, (call.beam ? call.n_hyp[W] : N) - 1);
         }
         const int len = call.lens_out[(size_t)W * call.out_stride() + h];
         const int nf = call.src.windows ? call.src.set->n_frames[call.src.rows ? call.src.rows[W] : W] : call.src.n_frames[W];
@@ -911,8 +905,8 @@ int lane_align(TxRun &r, LaneJob &j) {
                 WM_REQUIRE(got == len || (got < 0 && len == 0), WM_ERR_STATE, "aligned beam group: window %d, hypothesis %d has %d tokens, its ancestry %d", W, h, len, got);
             }
         }
-        if (call.dbg_slots)
-            for (int t = 0; t < Tq; ++t) call.dbg_slots[(size_t)W * Tq + t] = N > 1 ? slots[(size_t)w * Tq + t] : 0;
+        if (call.dbg.align_slots)
+            for (int t = 0; t < Tq; ++t) call.dbg.align_slots[(size_t)W * Tq + t] = N > 1 ? slots[(size_t)w * Tq + t] : 0;
     }
     WM_HIP(hipEventRecord(j.tail_ev[0], c->stream));
     if (nmax >= 0) {
@@ -937,8 +931,8 @@ int lane_align(TxRun &r, LaneJob &j) {
         WM_TRY(wm_dtw(c, x, (long)n_ld * 1500, 1500, ints + 2 * Cg, ints + 3 * Cg, Cg, rows_max, mmax, (unsigned *)(ws + j.aw.tr), start, n_ld));
         j.astart.resize((size_t)Cg * n_ld);
         WM_HIP(hipMemcpyAsync(j.astart.data(), start, j.astart.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        if (call.dbg_matrix)
-            WM_HIP(hipMemcpyAsync(call.dbg_matrix + (size_t)j.b0 * n_ld * 1500, x, (size_t)Cg * n_ld * 1500 * 4, hipMemcpyDeviceToHost, c->stream));
+        if (call.dbg.align_matrix)
+            WM_HIP(hipMemcpyAsync(call.dbg.align_matrix + (size_t)j.b0 * n_ld * 1500, x, (size_t)Cg * n_ld * 1500 * 4, hipMemcpyDeviceToHost, c->stream));
     }
     WM_HIP(hipEventRecord(j.tail_ev[1], c->stream));
     j.state = LaneJob::ALIGNING;
@@ -961,7 +955,7 @@ int lane_finish(TxRun &r, LaneJob &j, bool *done) {
     } else {
         wm_group_rows_out(j.gen.data(), j.lp.data(), j.ns.data(), r.cfg.stop.budgets, call.eot, call.n_cand, j.b0, j.Bg, call.max_new,
                           call.tokens_out, call.lens_out, r.cfg.xc.logprobs, r.cfg.xc.no_speech);
-        if (const wm_alternatives_out *a = r.cfg.alt)   // by the row map and the lengths just written
+        if (const wm_alternatives_out *a = r.cfg.pending->alt_on ? &r.cfg.pending->alt : nullptr)   // by the row map and the lengths just written
             wm_group_alt_out(j.atok.data(), j.alp.data(), j.acnt.data(), j.aent.data(), a->n, call.n_cand, j.b0, j.Bg, call.max_new,
                              call.lens_out, a->tokens, a->logprobs, a->counts, a->entropy);
     }
@@ -1062,32 +1056,11 @@ int tx_rank(const TxCall &call) {
 
 // ---------------------------------------------------------------- the call ----
 int tx_transcribe(wm_ctx *ctx, TxCall &call) {
-    // per-chunk token budgets set for THIS call (wm_set_token_budgets) are consumed by it whatever happens next: a call
-    // that fails any check must not leave them armed for a later, unrelated call with the same B
-    std::vector<int32_t> budgets;
-    if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
-    // ... and so is the row map of the sequence-bias tables (wm_set_bias_rows)
-    std::vector<int32_t> bias_rows;
-    if (ctx && ctx->model) bias_rows.swap(ctx->model->bias_rows_host);
-    // ... and the start states of the constraint's rows (wm_set_constraint_rows)
-    std::vector<int32_t> cst_rows;
-    if (ctx && ctx->model) cst_rows.swap(ctx->model->cst_rows_host);
-    // ... and the request for alternatives (wm_request_alternatives)
-    wm_alternatives_out alt_req = {};
-    bool alt_on = false;
-    if (ctx && ctx->model) { alt_on = ctx->model->alt_pending; alt_req = ctx->model->alt_req; ctx->model->alt_pending = false; }
-    // ... and the temperature and seed of its rows (wm_set_sampling_rows)
-    std::vector<float> samp_T;
-    std::vector<uint64_t> samp_seed;
-    if (ctx && ctx->model) { samp_T.swap(ctx->model->samp_rows_T); samp_seed.swap(ctx->model->samp_rows_seed); }
-    if (!samp_T.empty()) {   // served by the plain, mel, ragged, window-set and aligned entries
-        WM_REQUIRE(!call.greedy_entry, WM_ERR_STATE, "wm_transcribe_greedy takes no sampling row map (wm_set_sampling_rows)");
-        // (wm_transcribe_windows is the best-of entry of a window set: one sample per row is the plain call)
-        const bool one_sample = call.entry == TxCall::BEST_OF && call.src.windows && call.n_cand == 1 && !call.hyp;
-        WM_REQUIRE((call.entry != TxCall::BEST_OF && call.entry != TxCall::BEAM) || one_sample, WM_ERR_STATE,
-                   "best-of and beam-search calls take no sampling row map (wm_set_sampling_rows)");
-        WM_REQUIRE(!ctx->dbg_hooks, WM_ERR_STATE, "a sampling row map is not supported by the all-f32 precision path");
-    }
+    // whatever was armed for THIS call is consumed by it: a failed check must not leave it armed for a later, unrelated call
+    WmPending pending = tx_take(ctx, call);
+    call.dbg = pending.dbg;
+    if (!call.beam) call.dbg.beam_trace = nullptr;   // (an aligned call's captures are read on its own paths alone)
+    WM_TRY(tx_served(pending.bits() & WM_PEND_SAMP_ROWS, call));   // (in front of the entry's own checks; alternatives: tx_validate)
     WM_TRY(entry_checks(call));
     WM_MODEL(ctx);
     std::vector<float> lp_own;   // best_out ranks by the log-probs whether or not the caller wants them
@@ -1096,8 +1069,7 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
         call.logprobs_out = lp_own.data();
     }
     TxCfg cfg;
-    WM_TRY(tx_validate(ctx, call, budgets, &cfg, bias_rows.empty() ? nullptr : &bias_rows, alt_on ? &alt_req : nullptr,
-                       cst_rows.empty() ? nullptr : &cst_rows, samp_T.empty() ? nullptr : &samp_T, samp_T.empty() ? nullptr : &samp_seed));
+    WM_TRY(tx_validate(ctx, call, pending, &cfg));
     // the plan: decode groups and lanes.  A masked clone that cannot be made switches the masks off and asks again.
     WmTxPlanIn pin;
     pin.B = call.B; pin.N = call.n_cand;
@@ -1117,7 +1089,7 @@ int tx_transcribe(wm_ctx *ctx, TxCall &call) {
     }
     if (call.aligned) {   // rows of a group that never ran (an error below) read "no alignment"
         std::fill(call.start_out, call.start_out + (size_t)call.B * (call.max_new + 1), -1);
-        if (call.dbg_matrix) memset(call.dbg_matrix, 0, (size_t)call.B * (call.max_new + 1) * 1500 * 4);
+        if (call.dbg.align_matrix) memset(call.dbg.align_matrix, 0, (size_t)call.B * (call.max_new + 1) * 1500 * 4);
     }
     WM_TRY(tx_run(ctx, call, cfg, plan, lanes));
     return tx_rank(call);
@@ -1131,7 +1103,7 @@ void mel_src(TxCall &call, const float *mel, const int64_t *mel_base, const int3
 }
 
 void set_src(TxCall &call, const wm_windows *w, const int32_t *rows) {
-    call.src.windows = true; call.src.set = w; call.src.rows = rows;
+    call.windows = call.src.windows = true; call.src.set = w; call.src.rows = rows;
     call.mem = WM_MEM_HOST;
 }
 
@@ -1153,29 +1125,20 @@ void best_of(TxCall &call, const int32_t *prompts, int prompt_stride, const int3
 
 // Beam search: the call of wm_transcribe_mel_best_of with the rows of a window as its BEAMS (TxCall::beam) -- the same groups,
 // the same prompt phase, one cross-K/V read per window; the generating positions close with the beam kernels (beam.hip)
-void beam(wm_ctx *ctx, TxCall &call, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len, int sot_tail,
+void beam(TxCall &call, const int32_t *prompts, int prompt_stride, const int32_t *prompt_len, int sot_tail,
           int beam_size, int max_candidates, float length_penalty, int32_t *n_hyp_out, float *sum_logprobs_out, int32_t *best_out) {
     call.entry = TxCall::BEAM;
     call.prompts = {prompts, prompt_stride, prompt_len, sot_tail, nullptr};
     call.n_prompt = prompt_stride;
     call.n_cand = beam_size; call.beam = true; call.max_cand = max_candidates; call.length_penalty = length_penalty;
     call.n_hyp = n_hyp_out; call.sums = sum_logprobs_out; call.best_out = best_out;
-    if (ctx && ctx->model) {   // the debug library's capture is for this call only
-        call.trace = ctx->model->beam_dbg_trace;
-        ctx->model->beam_dbg_trace = nullptr;
-    }
 }
 
-// the aligned calls: their three arguments, and the debug library's one-shot cost-matrix capture (for this call only)
+// the aligned calls: their three arguments
 // hyp: a best-of / beam counterpart, which aligns the hypothesis best_out names
-void aligned(wm_ctx *ctx, TxCall &call, int medfilt_width, float qk_scale, int32_t *start_frame_out, bool hyp = false) {
+void aligned(TxCall &call, int medfilt_width, float qk_scale, int32_t *start_frame_out, bool hyp = false) {
     call.aligned = true; call.medfilt = medfilt_width; call.qk_scale = qk_scale; call.start_out = start_frame_out;
     call.hyp = hyp;
-    if (ctx && ctx->model) {
-        WmModel *m = ctx->model;
-        call.dbg_matrix = m->align_dbg_matrix; call.dbg_hyp = m->align_dbg_hyp; call.dbg_slots = m->align_dbg_slots;
-        m->align_dbg_matrix = nullptr; m->align_dbg_hyp = -1; m->align_dbg_slots = nullptr;
-    }
 }
 
 // ---------------------------------------------------------------- speculative decoding ----
@@ -1233,8 +1196,8 @@ int spec_group(wm_ctx *ctx, const SpecCall &sc, const TxCall &call, const TxCfg 
     WM_TRY(lane_prefill(tj, call, cfg));
     WM_TRY(lane_prefill(dj, call, dcfg));
     const int P = tj.P;
-    if (m->spec_dbg_script) {   // debug library: the proposals come from the script (the draft still runs)
-        script.assign(m->spec_dbg_script + (size_t)b0 * max_new, m->spec_dbg_script + (size_t)(b0 + G) * max_new);
+    if (const int32_t *s = cfg.pending->dbg.spec_script) {   // debug library: the proposals come from the script (the draft still runs)
+        script.assign(s + (size_t)b0 * max_new, s + (size_t)(b0 + G) * max_new);
         WM_HIP(hipMemcpyAsync(script_area, script.data(), script.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         sp.script = script_area;
     }
@@ -1320,33 +1283,16 @@ int spec_group(wm_ctx *ctx, const SpecCall &sc, const TxCall &call, const TxCfg 
 }
 
 int tx_speculative(wm_ctx *ctx, const SpecCall &sc, TxCall &call) {
-    std::vector<int32_t> budgets;   // consumed by this call whatever happens next (tx_transcribe)
-    if (ctx && ctx->model) budgets.swap(ctx->model->budget_host);
-    if (ctx && ctx->model) ctx->model->bias_rows_host.clear();   // a pending row map likewise
-    if (ctx && ctx->model) ctx->model->cst_rows_host.clear();    // ... and the constraint's
-    bool samp_rows = false;   // ... and a sampling row map, which this call refuses below (it verifies the greedy choice)
-    if (ctx && ctx->model) {
-        samp_rows = !ctx->model->samp_rows_T.empty();
-        ctx->model->samp_rows_T.clear(); ctx->model->samp_rows_seed.clear();
-    }
-    bool alt_on = false;   // ... and a request for alternatives, which this call refuses below
-    if (ctx && ctx->model) { alt_on = ctx->model->alt_pending; ctx->model->alt_pending = false; }
-    const int32_t *dbg_script = nullptr;   // the debug library's script is for this call only
-    if (ctx && ctx->model) dbg_script = ctx->model->spec_dbg_script;
-    struct ScriptScope {
-        WmModel *m;
-        ~ScriptScope() { if (m) { m->spec_dbg_script = nullptr; m->spec_dbg_script_new = m->spec_dbg_script_rows = 0; } }
-    } script_scope{ctx && ctx->model ? ctx->model : nullptr};
+    WmPending pending = tx_take(ctx, call);   // (alternatives and a sampling row map are refused below: it verifies the greedy choice)
     WM_TRY(entry_checks(call));
     WM_MODEL(ctx);
     WM_TRY(spec_checks(ctx, sc, call));
-    WM_REQUIRE(!alt_on, WM_ERR_STATE, "alternatives are not served by speculative decoding");
-    WM_REQUIRE(!samp_rows, WM_ERR_STATE, "speculative decoding takes no sampling row map (wm_set_sampling_rows)");
+    WM_TRY(tx_served(pending.bits(), call));
     TxCfg cfg;
-    WM_TRY(tx_validate(ctx, call, budgets, &cfg));
-    WM_REQUIRE(!dbg_script || (m->spec_dbg_script_new == call.max_new && m->spec_dbg_script_rows == call.B), WM_ERR_INVALID,
-               "the proposal script was set for %d rows x %d tokens, the call has %d x %d", m->spec_dbg_script_rows,
-               m->spec_dbg_script_new, call.B, call.max_new);
+    WM_TRY(tx_validate(ctx, call, pending, &cfg));
+    const WmDebugShots &dbg = pending.dbg;
+    WM_REQUIRE(!dbg.spec_script || (dbg.spec_script_new == call.max_new && dbg.spec_script_rows == call.B), WM_ERR_INVALID,
+               "the proposal script was set for %d rows x %d tokens, the call has %d x %d", dbg.spec_script_rows, dbg.spec_script_new, call.B, call.max_new);
     // the accept kernel closes a row from the extended decode's partials and keeps the windows' stop state itself: both on
     // for every speculative call (a plain call without them gives the same tokens: DESIGN.md sections 4, 7)
     cfg.xc.on = true;
@@ -1449,7 +1395,7 @@ extern "C" int wm_transcribe_mel_beam(wm_ctx *ctx, const float *mel, const int64
                                       float *token_logprobs_out, float *no_speech_prob_out, int32_t *best_out, wm_mem mem) try {
     TxCall call;
     mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
-    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+    beam(call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
          sum_logprobs_out, best_out);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
     return tx_transcribe(ctx, call);
@@ -1463,7 +1409,7 @@ extern "C" int wm_transcribe_windows_beam(wm_ctx *ctx, const wm_windows *w, cons
                                           int32_t *best_out) try {
     TxCall call;
     set_src(call, w, rows);
-    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+    beam(call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
          sum_logprobs_out, best_out);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
     return tx_transcribe(ctx, call);
@@ -1483,7 +1429,7 @@ extern "C" int wm_transcribe_mel_aligned(wm_ctx *ctx, const float *mel, const in
     call.prompts = {prompts, prompt_stride, prompt_len, prompt_len ? sot_tail : 0, sample_ids};
     call.n_prompt = prompt_stride;
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
-    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out);
+    aligned(call, medfilt_width, qk_scale, start_frame_out);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
 
@@ -1497,7 +1443,7 @@ extern "C" int wm_transcribe_windows_aligned(wm_ctx *ctx, const wm_windows *w, c
     set_src(call, w, rows);
     best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, 1, NAN, nullptr);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
-    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out);
+    aligned(call, medfilt_width, qk_scale, start_frame_out);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
 
@@ -1515,7 +1461,7 @@ extern "C" int wm_transcribe_mel_best_of_aligned(wm_ctx *ctx, const float *mel, 
     mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
     best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of_n, length_penalty, best_out);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
-    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
+    aligned(call, medfilt_width, qk_scale, start_frame_out, true);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
 
@@ -1530,7 +1476,7 @@ extern "C" int wm_transcribe_windows_best_of_aligned(wm_ctx *ctx, const wm_windo
     set_src(call, w, rows);
     best_of(call, prompts, prompt_stride, prompt_len, sot_tail, sample_ids, best_of_n, length_penalty, best_out);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
-    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
+    aligned(call, medfilt_width, qk_scale, start_frame_out, true);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
 
@@ -1544,10 +1490,10 @@ extern "C" int wm_transcribe_mel_beam_aligned(wm_ctx *ctx, const float *mel, con
                                               int32_t *start_frame_out, wm_mem mem) try {
     TxCall call;
     mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
-    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+    beam(call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
          sum_logprobs_out, best_out);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
-    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
+    aligned(call, medfilt_width, qk_scale, start_frame_out, true);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
 
@@ -1560,10 +1506,10 @@ extern "C" int wm_transcribe_windows_beam_aligned(wm_ctx *ctx, const wm_windows 
                                                   int32_t *start_frame_out) try {
     TxCall call;
     set_src(call, w, rows);
-    beam(ctx, call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
+    beam(call, prompts, prompt_stride, prompt_len, sot_tail, beam_size, max_candidates, length_penalty, n_hyp_out,
          sum_logprobs_out, best_out);
     outputs(call, B, max_new, eot, opts, tokens_out, lens_out, token_logprobs_out, no_speech_prob_out);
-    aligned(ctx, call, medfilt_width, qk_scale, start_frame_out, true);
+    aligned(call, medfilt_width, qk_scale, start_frame_out, true);
     return tx_transcribe(ctx, call);
 } WM_API_CATCH
 
@@ -1575,7 +1521,7 @@ extern "C" int wm_transcribe_mel_speculative(wm_ctx *ctx, wm_ctx *draft, const f
                                              float *token_logprobs_out, float *no_speech_prob_out, wm_spec_stats *stats_out,
                                              wm_mem mem) try {
     TxCall call;
-    call.entry = TxCall::MEL;
+    call.entry = TxCall::MEL; call.speculative = true;
     mel_src(call, mel, mel_base, mel_len, seek, n_frames, mem);
     call.prompts = {prompts, n_prompt, nullptr, 0, nullptr};
     call.n_prompt = n_prompt;

@@ -234,6 +234,14 @@ def test_the_multi_device_entry_refuses_a_map(world, pkg):
         assert status_of(world, lambda: multi.transcribe_greedy(pcm, prompt, 6)) == WM_ERR_STATE
         t1, l1 = multi.transcribe_greedy(pcm, prompt, 6)          # consumed: the next call is the plain one
         assert same(t1, t0) and same(l1, l0)
+        # with a request for alternatives pending too, the entry answers for that one and has consumed both
+        multi.device_ctx(0).set_sampling_rows(TEMPS, SEEDS)
+        multi.device_ctx(0).request_alternatives(2, R, 6)
+        with pytest.raises(pkg.binding.WhisperError) as e:
+            multi.transcribe_greedy(pcm, prompt, 6)
+        assert e.value.status == WM_ERR_STATE and "does not serve alternatives" in str(e.value)
+        t2, l2 = multi.transcribe_greedy(pcm, prompt, 6)
+        assert same(t2, t0) and same(l2, l0)
     finally:
         multi.close()
 
