@@ -913,6 +913,40 @@ typedef struct wm_alternatives_out {
 } wm_alternatives_out;
 WM_API int wm_request_alternatives(wm_ctx *ctx, const wm_alternatives_out *req /* NULL: drop a pending request */);
 
+/* Given tokens: a row decodes a text the caller already has and returns its log-probs (CTranslate2's score_batch, Hugging Face's
+ * compute_transition_scores and forced decoder ids, openai-whisper's `prefix`; n-best rescoring, "which of these K commands was
+ * spoken", the log-prob and entropy of a reference transcript, resuming a hypothesis inside a window).  The table is armed for the
+ * NEXT transcribe call on the context and is consumed by it whatever happens, as wm_set_token_budgets; n = 0 drops a pending table.
+ * Row r is the call's hypothesis row: B rows, or B * best_of in the call's hypothesis order [B][best_of], as
+ * wm_request_alternatives counts them.
+ * At generated index gi < lens[r] the close takes tokens[r][gi] in place of its own choice; everything else is the call's:
+ *   - rule state follows the given token: the timestamp history, the repetition bitmaps, bias and constraint state, budgets, the
+ *     eot stop, the embedding of the next position;
+ *   - at gi >= lens[r] the row decodes freely; lens[r] = 0 is an ordinary row, so scored and decoded rows batch in one call;
+ *   - a caller who wants scoring alone sets budgets equal to lens (wm_set_token_budgets; per row of the CALL: the candidates of a
+ *     best-of window share theirs); a caller who wants openai-whisper's `prefix` with log-probs leaves them open.
+ * token_logprobs_out[r][gi] at a given position is v(tok) - norm:
+ *   - v is the stored logit after the repetition penalty and the sequence bias;
+ *   - norm is the normaliser of the decision the row would have made WITHOUT the table (under the timestamp rules: over the
+ *     admissible timestamps alone where the sum rule forces one): the normaliser of every other log-prob of the library, at
+ *     temperature 1, whatever the call's temperature, seed and sampling rules;
+ *   - if the given token is what the plain call chose, the bits are the plain call's;
+ *   - if the given token is not admissible -- outside the row's ranges, a text id where the sum rule forces a timestamp,
+ *     suppressed, banned, v equal to -INFINITY or NaN -- the log-prob is -INFINITY and the row goes on with the given token;
+ *   - a row with NOTHING admissible at a position (every allowed id suppressed) has no normaliser: there the call takes its existing
+ *     path (its fallback token, -INFINITY), and the table holds again from the next position.
+ * Alternatives of a given position (wm_request_alternatives) list what the model preferred; a given row of a sampling call never
+ * draws.  A group of ordinary rows inside a call with a table makes exactly the launches it makes without one.
+ * Served: wm_transcribe, _mel, _mel_ragged, _mel_best_of, wm_transcribe_windows and the *_aligned counterparts of the plain
+ * entries.  Refused with WM_ERR_STATE, the table consumed: the beam entries, the aligned best-of entries,
+ * wm_transcribe_mel_speculative, wm_multi_transcribe_greedy (a table pending on a device context), wm_transcribe_greedy (it has
+ * no log-prob output) and the all-f32 debug path.  WM_ERR_INVALID here: a token outside the vocabulary, a lens entry outside
+ * [0, stride], null pointers or stride < 1 with n > 0 (the pending table is dropped); from the call, the table still consumed: n
+ * other than the call's hypothesis rows, a lens entry above max_new.  Cost: one launch per position of a group that holds a
+ * given row, and that group's stored f32 logits row. */
+WM_API int wm_set_given_tokens(wm_ctx *ctx, const int32_t *tokens /* i32 [n][stride] */, int stride,
+                               const int32_t *lens /* i32 [n], 0 .. stride */, int n);
+
 /* ------------------------------------------------- all GPUs of the node, one host process --- */
 /* the Swift host dlopens ONE library in ONE process; wm_multi drives n GPUs from it.  Weights are
  * replicated (one wm_ctx per device: fetch each with wm_multi_device_ctx and fill it with wm_load_weights /

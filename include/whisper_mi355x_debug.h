@@ -176,6 +176,14 @@ WM_API int wmdbg_decode_close_trunc(wm_ctx *ctx, wmdbg_step *io, int top_k, floa
  * position -- the logits launch, the truncation launch when the rules are on ((0, 1, 0): no truncation launch) and some row
  * samples, and the close -- with the rows' table handed to the X-mode kernels.  Needs x_on; io->temperature and io->seed are not
  * read; row_T[b] == 0 is an arg-max row.  struct wmdbg_step is unchanged: the row arrays [io->B] are arguments. */
+/* wmdbg_decode_close_trunc's step with the given-tokens launch (wm_set_given_tokens, given.hip) last in front of the close: given
+ * i32 [B], -1: the row decodes freely; NULL: no such launch.  With (0, 1, 0), or at temperature 0, no truncation launch runs.
+ * Needs x_on.  Beside io's outputs: the rows' per-tile keys tilemax_out / key_ts_out u64 [B][n_tiles] (key_ts_out is written
+ * under timestamp rules alone) and winner values win_out f32 [B][n_tiles][2] as the launches in front of the close left them,
+ * n_tiles = (V + 15) / 16 -- so the rows the kernel must not touch compare byte for byte with the same step at given == NULL.
+ * A given id outside [-1, V) answers WM_ERR_INVALID and launches nothing. */
+WM_API int wmdbg_decode_close_given(wm_ctx *ctx, wmdbg_step *io, const int32_t *given, int top_k, float top_p, float min_p,
+                                    uint64_t *tilemax_out, uint64_t *key_ts_out, float *win_out);
 WM_API int wmdbg_decode_close_rows(wm_ctx *ctx, wmdbg_step *io, const float *row_T, const uint64_t *row_seed, int top_k, float top_p,
                                    float min_p);
 /* wmdbg_decode_close with the repetition rules on (wm_set_repetition_rules: penalty, ngram, and io->eot as the rules' eot, in
@@ -213,6 +221,11 @@ WM_API int wmdbg_sb_expand_tables(const int32_t *tokens, const int32_t *seq_offs
 /* The per-row group ranges a decode group uploads under row tables (tx_plan.cpp wm_group_bias_rows; the group-tables dump of
  * wmdbg_group_tables is left as it is): table_of_row i32 [B] of the call (wm_set_bias_rows), the group of windows [b0, b0 + Cg) x N
  * candidates, tab_grp [n_tables + 1] -> rng_out i32 [Cg * N][2] = (first group, end group) of each decoder row; (0, 0) for -1. */
+/* wm_group_given (tx_plan.h): the given-tokens table of the group of windows [b0, b0 + Cg) x N of a call whose table is lens
+ * i32 [rows] / tokens i32 [rows][stride].  Out: lens_out i32 [Cg * N], tok_out i32 [Cg * N][max(L, 1)] (tok_cap words of room), *L_out
+ * = L, the group's longest given text (0: no row of the group is given).  Host only. */
+WM_API int wmdbg_group_given(const int32_t *lens, const int32_t *tokens, int stride, int rows, int b0, int Cg, int N, int32_t *lens_out,
+                             int32_t *tok_out, int tok_cap, int32_t *L_out);
 WM_API int wmdbg_group_bias_rows(const int32_t *table_of_row, int B, const int32_t *tab_grp, int n_tables, int b0, int Cg, int N,
                                  int32_t *rng_out);
 /* The state kernel of the row tables alone (seqbias_rows.hip), as wmdbg_seqbias_state: the tables as for

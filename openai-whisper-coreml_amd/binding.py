@@ -277,6 +277,33 @@ def alternatives_arg(alternatives, beam_size=None, draft=None):
     return int(n)
 
 
+def given_arg(given, beam_size=None, draft=None):
+    """`given=` of the transcribe wrappers as wm_set_given_tokens' table: None (no table), or one id list per hypothesis row of
+    the call (B rows; B * best_of in the order [B][best_of]; an empty list or None: the row decodes freely).  Returns (tokens i32
+    [n][stride], lens i32 [n]).  ValueError -- before any library call -- for anything else, and together with beam search or a
+    draft model (neither serves a table)."""
+    if given is None:
+        return None
+    if beam_size is not None:
+        raise ValueError("given tokens are not served by beam search (beam_size)")
+    if draft is not None:
+        raise ValueError("given tokens are not served by speculative decoding (draft)")
+    try:
+        rows = [np.zeros(0, dtype=np.int64) if g is None else np.asarray(g).reshape(-1) for g in given]
+    except TypeError:
+        raise ValueError("given: one id list per hypothesis row (None: no table)")
+    if not rows:
+        raise ValueError("given: one id list per hypothesis row (None: no table)")
+    for r in rows:
+        if r.size and (not np.issubdtype(r.dtype, np.integer) or r.min() < 0 or r.max() > 0x7FFFFFFF):
+            raise ValueError("given: token ids are non-negative integers")
+    lens = np.array([r.size for r in rows], dtype=np.int32)
+    tok = np.zeros((len(rows), max(1, int(lens.max()))), dtype=np.int32)
+    for i, r in enumerate(rows):
+        tok[i, :r.size] = r
+    return tok, lens
+
+
 class Alternatives:
     """The arrays of one wm_request_alternatives request, filled by the transcribe call that consumes it: tokens i32 / logprobs
     f32 [rows][max_new][n] (-1 / 0 past counts and past a row's length), counts i32 [rows][max_new], entropy f32
@@ -442,6 +469,57 @@ def rank_candidates(tokens, lens, logprobs, eot, length_penalty=None):
                                        float("nan") if length_penalty is None else float(length_penalty), _ptr(best),
                                        _ptr(scores)))
     return best, scores
+
+
+def score_given(ctx, wset, rows, prompts, texts, eot, append_eot=True, length_penalty=None, alternatives=None):
+    """The log-probs of texts the caller already has (CTranslate2's score_batch; n-best rescoring, "which of these K commands was
+    spoken").  wset / rows: a Windows set and its rows (None: all) as for Context.transcribe_windows; prompts: one prompt for all,
+    or one per row; texts: per row a list of texts, each a list of token ids.  append_eot: eot is scored behind every text
+    (openai-whisper's sum_logprob includes it).  Every text is given whole with a token budget of its length, so nothing is
+    decoded beyond it.
+    Where every row has the same number K of texts this is ONE transcribe_windows_best_of(best_of=K) call at temperature 0 (a
+    given candidate never draws): the K texts of a window share one read of its cross-attention K/V per position; otherwise one
+    plain transcribe_windows call with the rows repeated.  Returns a SimpleNamespace: logprobs -- per row a list of f32 arrays,
+    one per text --, sum_logprob and avg_logprob (openai-whisper's: sum / (len(text) + 1)) f64 lists of the same shape, `best` i32
+    [rows] (the best-of call's ranking: wm_rank_candidates' rule under length_penalty; None on the plain path), `result` (the
+    call's own result) and, with alternatives=n, per row and text alt_tokens / alt_logprobs / alt_counts / entropy."""
+    n_alt = alternatives_arg(alternatives)
+    idx = list(range(len(wset))) if rows is None else [int(r) for r in np.asarray(rows).reshape(-1)]
+    if len(texts) != len(idx) or any(len(t) == 0 for t in texts):
+        raise ValueError("score_given: one non-empty list of texts per row")
+    tail = [int(eot)] if append_eot else []
+    given = [[[int(x) for x in t] + tail for t in ts] for ts in texts]
+    if any(len(g) == 0 for gs in given for g in gs):
+        raise ValueError("score_given: an empty text needs append_eot")
+    max_new = max(len(g) for gs in given for g in gs)
+    K = len(given[0])
+    same = all(len(gs) == K for gs in given)
+    pr = prompts
+    if not same and not (isinstance(prompts, np.ndarray) and prompts.ndim == 1) and np.ndim(prompts[0]) != 0:
+        pr = [prompts[w] for w, gs in enumerate(given) for _ in gs]   # a prompt per row: repeated with the row
+    flat = [g for gs in given for g in gs]
+    if same:
+        r = ctx.transcribe_windows_best_of(wset, idx, pr, max_new, K, eot=eot, temperature=0.0, length_penalty=length_penalty,
+                                           budgets=[max(len(g) for g in gs) for gs in given], alternatives=n_alt, given=flat)
+        lp = [[r.logprobs[w, k, :len(g)].copy() for k, g in enumerate(gs)] for w, gs in enumerate(given)]
+        alt = [[(w, k) for k in range(K)] for w in range(len(idx))]
+        best = r.best
+    else:
+        rep_rows = [idx[w] for w, gs in enumerate(given) for _ in gs]
+        r = ctx.transcribe_windows(wset, rep_rows, pr, max_new, eot=eot, budgets=[len(g) for g in flat], alternatives=n_alt,
+                                   given=flat)
+        at = iter(range(len(flat)))
+        alt = [[(next(at),) for _ in gs] for gs in given]
+        lp = [[r.logprobs[a[0], :len(g)].copy() for a, g in zip(al, gs)] for al, gs in zip(alt, given)]
+        best = None
+    out = types.SimpleNamespace(logprobs=lp, best=best, result=r)
+    out.sum_logprob = [[float(np.sum(a, dtype=np.float64)) for a in row] for row in lp]
+    out.avg_logprob = [[s_ / (len(t) + 1) for s_, t in zip(srow, ts)] for srow, ts in zip(out.sum_logprob, texts)]
+    if n_alt:
+        for name in ("alt_tokens", "alt_logprobs", "alt_counts", "entropy"):
+            a = getattr(r, name)
+            setattr(out, name, [[a[i][:len(g)] for i, g in zip(al, gs)] for al, gs in zip(alt, given)])
+    return out
 
 
 def n_text_tokens(toks, eot):
@@ -2684,6 +2762,27 @@ class Context:
         _check(self.lib, fn(self.handle, ctypes.byref(req)))
         return a
 
+    def set_given_tokens(self, given):
+        """Given tokens of the NEXT transcribe call on this context (wm_set_given_tokens; consumed by it whatever happens): one id
+        list per hypothesis row of that call (B, or B * best_of in the order [B][best_of]); the row takes them in place of its
+        own choices and returns their log-probs, and decodes freely behind them (an empty list: an ordinary row).  None or []
+        drops a pending table."""
+        if given is None or len(given) == 0:
+            self._put_given(None)
+        else:
+            self._put_given(given_arg(given))
+
+    def _put_given(self, table):
+        """wm_set_given_tokens on a checked table (given_arg); None: drop"""
+        fn = self.lib.wm_set_given_tokens
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        fn.restype = ctypes.c_int
+        if table is None:
+            _check(self.lib, fn(self.handle, None, 0, None, 0))
+            return
+        tok, lens = table
+        _check(self.lib, fn(self.handle, _ptr(tok), int(tok.shape[1]), _ptr(lens), int(lens.size)))
+
     def transcribe_greedy(self, pcm, prompt, max_new, eot=-1, mem=WM_MEM_HOST, pcm_dtype=None, B=None, budgets=None):
         """pcm: host array [B][480000] (int16/float32/float64), or a device pointer
         (c_void_p) with pcm_dtype and B given when mem == WM_MEM_DEVICE.  budgets: per-chunk token budgets
@@ -2706,11 +2805,12 @@ class Context:
         return toks, lens
 
     def transcribe_raw(self, pcm, prompt, max_new, eot=-1, opts=None, logprobs=True, no_speech=False, budgets=None,
-                       alternatives=None):
+                       alternatives=None, given=None):
         """wm_transcribe on host arrays: opts a wm_decode_opts or None (NULL); logprobs / no_speech request the two
         optional outputs.  Returns (tokens, lens, logprobs or None, no_speech_prob or None) -- and, with alternatives=n, the
-        call's Alternatives as a fifth element."""
+        call's Alternatives as a fifth element.  given: the call's given tokens (given_arg), armed right in front of the call."""
         n_alt = alternatives_arg(alternatives)
+        g = given_arg(given)
         if budgets is not None:
             self.set_token_budgets(budgets)
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
@@ -2721,6 +2821,8 @@ class Context:
         lp = np.empty((B, max_new), dtype=np.float32) if logprobs else None
         ns = np.empty(B, dtype=np.float32) if no_speech else None
         alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None   # (last: nothing can fail between it and the call)
+        if g is not None:
+            self._put_given(g)
         _check(self.lib, self.lib.wm_transcribe(self.handle, _ptr(pcm), _DTYPES[pcm.dtype], B, _ptr(prompt), len(prompt),
                                                 max_new, eot, ctypes.byref(opts) if opts is not None else None,
                                                 _ptr(toks), _ptr(lens), _ptr(lp) if lp is not None else None,
@@ -2728,15 +2830,17 @@ class Context:
         return (toks, lens, lp, ns) if alt is None else (toks, lens, lp, ns, alt)
 
     def transcribe(self, pcm, prompt, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1, sot_index=0,
-                   budgets=None, alternatives=None, row_temperatures=None, row_seeds=None):
+                   budgets=None, alternatives=None, row_temperatures=None, row_seeds=None, given=None):
         """wm_transcribe: greedy (temperature 0) or sampled decode with per-token log-probs and, with no_speech_token >= 0,
         openai-whisper's no_speech_prob.  alternatives=n: also the n best admissible tokens and the entropy of every generated
         position (request_alternatives).  row_temperatures / row_seeds (both or neither): a temperature and a seed per row
-        (set_sampling_rows in front of the call; temperature and seed are then not read).  Returns a TranscribeResult."""
+        (set_sampling_rows in front of the call; temperature and seed are then not read).  given: one id list per row that
+        the row decodes in place of its own choices, with their log-probs (set_given_tokens).  Returns a TranscribeResult."""
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         with self._rows_map(row_temperatures, row_seeds):
             toks, lens, lp, ns, *alt = self.transcribe_raw(pcm, prompt, max_new, eot, opts, logprobs=True,
-                                                           no_speech=no_speech_token >= 0, budgets=budgets, alternatives=alternatives)
+                                                           no_speech=no_speech_token >= 0, budgets=budgets, alternatives=alternatives,
+                                                           given=given)
         return self._with_alternatives(TranscribeResult(toks, lens, lp, ns, eot), alt)
 
     @contextlib.contextmanager
@@ -2816,7 +2920,7 @@ class Context:
 
     def transcribe_mel_raw(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, opts=None,
                            sample_ids=None, logprobs=True, no_speech=False, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
-                           sot_tail=None, alternatives=None):
+                           sot_tail=None, alternatives=None, given=None):
         """wm_transcribe_mel: mel is a host f32 array (mem WM_MEM_HOST) or a device pointer (WM_MEM_DEVICE); mel_base i64,
         mel_len / seek / n_frames i32 [B]; prompts [B][n_prompt]; sample_ids u32 [B] or None.  Returns (tokens, lens,
         logprobs or None, no_speech_prob or None).
@@ -2824,8 +2928,10 @@ class Context:
         wm_transcribe_mel_ragged with sot_tail (<|startoftranscript|> is the sot_tail-th token from the end of every
         prompt; default 1, opts.sot_index is not read).  A list of lists of ONE length without prompt_len stays
         wm_transcribe_mel; there a sot_tail, when given, replaces opts.sot_index by n_prompt - sot_tail.
-        alternatives=n: the call's Alternatives as a fifth element (request_alternatives)."""
+        alternatives=n: the call's Alternatives as a fifth element (request_alternatives).  given: the call's given tokens
+        (given_arg), armed right in front of the call."""
         n_alt = alternatives_arg(alternatives)
+        g = given_arg(given)
         if budgets is not None:
             self.set_token_budgets(budgets)
         head, B = self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem)
@@ -2838,6 +2944,8 @@ class Context:
         rest = (_ptr_or_null(ids), max_new, eot, ctypes.byref(opts) if opts is not None else None, _ptr(toks), _ptr(lens),
                 _ptr_or_null(lp), _ptr_or_null(ns), mem)
         alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None
+        if g is not None:
+            self._put_given(g)
         if plen is not None:
             _check(self.lib, self.lib.wm_transcribe_mel_ragged(*rows, _ptr(plen), 1 if sot_tail is None else int(sot_tail), *rest))
         else:
@@ -2869,21 +2977,23 @@ class Context:
 
     def transcribe_mel_best_of(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1, temperature=0.0,
                                seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None,
-                               prompt_len=None, sot_tail=None, length_penalty=None, alternatives=None):
+                               prompt_len=None, sot_tail=None, length_penalty=None, alternatives=None, given=None):
         """wm_transcribe_mel_best_of: transcribe_mel's arguments (uniform or ragged prompts as in transcribe_mel_raw) with
         best_of sampled candidates per row that share the row's encoder pass and cross-attention cache; length_penalty None
-        is openai-whisper's None.  alternatives=n: every candidate's alternatives and entropy.  Returns a BestOfResult."""
+        is openai-whisper's None.  alternatives=n: every candidate's alternatives and entropy.  given: B * best_of id lists in the
+        order [B][best_of] (set_given_tokens): a given candidate never draws.  Returns a BestOfResult."""
         return self._best_of_call(self.lib.wm_transcribe_mel_best_of,
                                   lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new,
                                   best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
-                                  sot_tail, length_penalty, alternatives=alternatives)
+                                  sot_tail, length_penalty, alternatives=alternatives, given=given)
 
     def _best_of_call(self, fn, rows, tail, prompts, max_new, best_of, eot, temperature, seed, no_speech_token, sot_index,
-                      sample_ids, budgets, prompt_len, sot_tail, length_penalty, aligned=None, alternatives=None):
+                      sample_ids, budgets, prompt_len, sot_tail, length_penalty, aligned=None, alternatives=None, given=None):
         """wm_transcribe_mel_best_of / wm_transcribe_windows, which differ in the arguments that name the rows -- rows() gives
         (them, B): _mel_rows, _window_rows -- and in the tail (mem).  aligned = (medfilt_width, qk_scale, capture_matrix): fn is
         the aligned counterpart, and the result carries start_frames (and matrix).  alternatives: None or n (every candidate's)."""
         n_alt = alternatives_arg(alternatives)
+        g = given_arg(given)   # (the aligned best-of wrappers take none: those entries refuse a table)
         opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
         if budgets is not None:
             self.set_token_budgets(budgets)
@@ -2898,6 +3008,8 @@ class Context:
         best = np.empty(B, dtype=np.int32)
         align_in, align_out, start, matrix = self._hyp_aligned_args(aligned, B, max_new)
         alt = self.request_alternatives(n_alt, B * max(N, 1), max_new) if n_alt else None
+        if g is not None:
+            self._put_given(g)
         _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
                             1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), N,
                             float("nan") if length_penalty is None else float(length_penalty), max_new, eot, ctypes.byref(opts),
@@ -2964,16 +3076,19 @@ class Context:
     def transcribe_mel(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                        no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
                        sot_tail=None, best_of=None, length_penalty=None, beam_size=None, patience=None, alternatives=None,
-                       row_temperatures=None, row_seeds=None):
+                       row_temperatures=None, row_seeds=None, given=None):
         """wm_transcribe_mel with log-probs (and no_speech_prob with no_speech_token >= 0).  Returns a TranscribeResult.
         row_temperatures / row_seeds (both or neither; not with best_of or beam_size): a temperature and a seed per row
         (set_sampling_rows in front of the call; temperature and seed are then not read).
         alternatives=n: also the n best admissible tokens and the entropy of every generated position (not with beam_size).
+        given: one id list per row (B * best_of with best_of) that the row decodes in place of its own choices (set_given_tokens;
+        not with beam_size).
         Prompts of different lengths (or prompt_len=) and sot_tail: see transcribe_mel_raw.
         best_of (None: one sample): transcribe_mel_best_of, and the result is its `selected` (with `candidate`).
         beam_size (None: no beam search; with patience): transcribe_mel_beam at temperature 0 -- sample_ids and the seed play
         no part -- and the result is its `selected` (with `hypothesis`)."""
         alternatives_arg(alternatives, beam_size if beam_size is not None else patience)
+        given_arg(given, beam_size if beam_size is not None else patience)
         win = (mel, mel_base, mel_len, seek, n_frames, prompts, max_new)
         common = dict(mem=mem, budgets=budgets, prompt_len=prompt_len, sot_tail=sot_tail)
         entry = dict(common, eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, length_penalty=length_penalty)
@@ -2984,12 +3099,12 @@ class Context:
             with self._rows_map(row_temperatures, row_seeds):
                 toks, lens, lp, ns, *alt = self.transcribe_mel_raw(
                     *win, eot, wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index)),
-                    sample_ids, logprobs=True, no_speech=no_speech_token >= 0, alternatives=alternatives, **common)
+                    sample_ids, logprobs=True, no_speech=no_speech_token >= 0, alternatives=alternatives, given=given, **common)
             return self._with_alternatives(TranscribeResult(toks, lens, lp, ns, eot), alt)
         return self._decode_entry(
             lambda: self.transcribe_mel_beam(*win, beam_size, patience=patience, **entry),
             lambda: self.transcribe_mel_best_of(*win, best_of, temperature=temperature, seed=seed, sample_ids=sample_ids,
-                                                alternatives=alternatives, **entry),
+                                                alternatives=alternatives, given=given, **entry),
             plain, temperature, best_of, beam_size, patience)
 
     @staticmethod
@@ -3033,12 +3148,12 @@ class Context:
 
     def transcribe_windows_best_of(self, windows, rows, prompts, max_new, best_of=1, eot=-1, temperature=0.0, seed=0,
                                    no_speech_token=-1, sot_index=0, sample_ids=None, budgets=None, prompt_len=None,
-                                   sot_tail=None, length_penalty=None, alternatives=None):
+                                   sot_tail=None, length_penalty=None, alternatives=None, given=None):
         """wm_transcribe_windows: transcribe_mel_best_of with rows of a Windows set (rows None: all of them, in order) in
         place of the mel windows.  Same bits.  Returns a BestOfResult."""
         return self._best_of_call(self.lib.wm_transcribe_windows, lambda: self._window_rows(windows, rows), (), prompts, max_new,
                                   best_of, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
-                                  sot_tail, length_penalty, alternatives=alternatives)
+                                  sot_tail, length_penalty, alternatives=alternatives, given=given)
 
     def transcribe_windows_beam(self, windows, rows, prompts, max_new, beam_size, eot=-1, patience=None, no_speech_token=-1,
                                 sot_index=0, budgets=None, prompt_len=None, sot_tail=None, length_penalty=None,
@@ -3051,18 +3166,19 @@ class Context:
     def transcribe_windows(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
                            sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, best_of=None,
                            length_penalty=None, beam_size=None, patience=None, alternatives=None, row_temperatures=None,
-                           row_seeds=None):
+                           row_seeds=None, given=None):
         """transcribe_mel with rows of a Windows set in place of the mel windows: the same bits, no encoder pass.  Returns a
-        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel; alternatives=n and row_temperatures /
+        TranscribeResult (best_of / beam_size: the `selected` one, as transcribe_mel; alternatives=n, given= and row_temperatures /
         row_seeds as there)."""
         alternatives_arg(alternatives, beam_size if beam_size is not None else patience)
+        given_arg(given, beam_size if beam_size is not None else patience)
         self._rows_entry(row_temperatures, row_seeds, best_of, beam_size, patience)
         common = dict(eot=eot, no_speech_token=no_speech_token, sot_index=sot_index, budgets=budgets, prompt_len=prompt_len,
                       sot_tail=sot_tail, length_penalty=length_penalty)
 
         def candidates(n):
             return self.transcribe_windows_best_of(windows, rows, prompts, max_new, n, temperature=temperature, seed=seed,
-                                                   sample_ids=sample_ids, alternatives=alternatives, **common)
+                                                   sample_ids=sample_ids, alternatives=alternatives, given=given, **common)
 
         def plain():   # (the set has no entry of its own for one sample: candidate 0 of N = 1)
             with self._rows_map(row_temperatures, row_seeds):
@@ -3080,9 +3196,10 @@ class Context:
 
     def _aligned_call(self, fn, rows, tail, prompts, max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids,
                       budgets, prompt_len, sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=None, row_temperatures=None,
-                      row_seeds=None):
+                      row_seeds=None, given=None):
         """wm_transcribe_mel_aligned / wm_transcribe_windows_aligned (rows, tail: as in _best_of_call)"""
         n_alt = alternatives_arg(alternatives)
+        g = given_arg(given)
         with self._rows_map(row_temperatures, row_seeds):
             opts = wm_decode_opts(float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, int(no_speech_token), int(sot_index))
             if budgets is not None:
@@ -3096,6 +3213,8 @@ class Context:
             start = np.empty((B, max_new + 1), dtype=np.int32)
             matrix = self._capture_matrix(B, max_new) if capture_matrix else None
             alt = self.request_alternatives(n_alt, B, max_new) if n_alt else None
+            if g is not None:
+                self._put_given(g)
             _check(self.lib, fn(self.handle, *head, B, _ptr(pr), pr.shape[1], _ptr_or_null(plen),
                                 1 if sot_tail is None else int(sot_tail), _ptr_or_null(ids), max_new, eot, ctypes.byref(opts),
                                 int(medfilt_width), float(qk_scale), _ptr(toks), _ptr(lens), _ptr(lp), _ptr_or_null(ns), _ptr(start),
@@ -3106,7 +3225,7 @@ class Context:
     def transcribe_mel_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, eot=-1, temperature=0.0, seed=0,
                                no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST, budgets=None, prompt_len=None,
                                sot_tail=None, medfilt_width=7, qk_scale=1.0, capture_matrix=False, alternatives=None,
-                               row_temperatures=None, row_seeds=None):
+                               row_temperatures=None, row_seeds=None, given=None):
         """wm_transcribe_mel_aligned: transcribe_mel (one sample per row; uniform or ragged prompts as in transcribe_mel_raw)
         whose decode also aligns what it generates, from its own cross-attention queries.  Tokens, lens, log-probs and
         no_speech_prob are transcribe_mel's bit for bit.  Returns an AlignedResult (start_frames; decode_alignment_text turns
@@ -3115,16 +3234,17 @@ class Context:
                                   lambda: self._mel_rows(mel, mel_base, mel_len, seek, n_frames, mem), (mem,), prompts, max_new, eot,
                                   temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len, sot_tail,
                                   medfilt_width, qk_scale, capture_matrix, alternatives=alternatives,
-                                  row_temperatures=row_temperatures, row_seeds=row_seeds)
+                                  row_temperatures=row_temperatures, row_seeds=row_seeds, given=given)
 
     def transcribe_windows_aligned(self, windows, rows, prompts, max_new, eot=-1, temperature=0.0, seed=0, no_speech_token=-1,
                                    sot_index=0, sample_ids=None, budgets=None, prompt_len=None, sot_tail=None, medfilt_width=7,
-                                   qk_scale=1.0, capture_matrix=False, alternatives=None, row_temperatures=None, row_seeds=None):
+                                   qk_scale=1.0, capture_matrix=False, alternatives=None, row_temperatures=None, row_seeds=None,
+                                   given=None):
         """wm_transcribe_windows_aligned: transcribe_mel_aligned with rows of a Windows set.  Same bits."""
         return self._aligned_call(self.lib.wm_transcribe_windows_aligned, lambda: self._window_rows(windows, rows), (), prompts,
                                   max_new, eot, temperature, seed, no_speech_token, sot_index, sample_ids, budgets, prompt_len,
                                   sot_tail, medfilt_width, qk_scale, capture_matrix, alternatives=alternatives,
-                                  row_temperatures=row_temperatures, row_seeds=row_seeds)
+                                  row_temperatures=row_temperatures, row_seeds=row_seeds, given=given)
 
     def transcribe_mel_best_of_aligned(self, mel, mel_base, mel_len, seek, n_frames, prompts, max_new, best_of, eot=-1,
                                        temperature=0.0, seed=0, no_speech_token=-1, sot_index=0, sample_ids=None, mem=WM_MEM_HOST,

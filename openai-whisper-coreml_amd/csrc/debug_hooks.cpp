@@ -356,6 +356,7 @@ extern "C" int wmdbg_pending_take(unsigned bits, unsigned again, int32_t *out) {
         if (b & WM_PEND_CST_ROWS) p.cst_rows.assign(1, v);
         if (b & WM_PEND_SAMP_ROWS) { p.samp_T.assign(1, (float)v); p.samp_seed.assign(1, (uint64_t)v); }
         if (b & WM_PEND_ALT) { p.alt_on = true; p.alt.n = v; }
+        if (b & WM_PEND_GIVEN) { p.given_lens.assign(1, v); p.given_tok.assign(1, v); p.given_stride = 1; }
     };
     WmPending member;
     arm(member, bits, 1);
@@ -2239,9 +2240,17 @@ static int shared_closes_run(wm_ctx *ctx, DevPool &pool, const wmdbg_step *io, c
 // cst (with rep): the constraint as well -- wm_constraint_state behind the other state launches, with the rows' starts
 // row_T / row_seed: temperature and seed per row (wm_set_sampling_rows) -- io->temperature and io->seed are not read, the X-mode
 // kernels are handed the rows' table
+// gv: the given-tokens launch last in front of the close (given == null: no launch), and the row's keys and winner values as
+// the launches in front of the close left them
+struct CloseGiven {
+    const int32_t *given;   // [B], -1: the row decodes freely
+    uint64_t *tilemax_out, *key_ts_out;   // [B][n_tiles] (key_ts_out: read with timestamp rules)
+    float *win_out;                       // [B][n_tiles][2]
+};
 static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty, int ngram, const WmSbTable *sbt = nullptr,
                             const CloseShared *sh = nullptr, const WmSampPar *trunc = nullptr, const WmCstTable *cst = nullptr,
-                            const int32_t *cst_starts = nullptr, const float *row_T = nullptr, const uint64_t *row_seed = nullptr) {
+                            const int32_t *cst_starts = nullptr, const float *row_T = nullptr, const uint64_t *row_seed = nullptr,
+                            const CloseGiven *gv = nullptr) {
     WM_TRY(wm_ctx_make_current(ctx));
     WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_decode_close: null");
     if (rep)
@@ -2430,6 +2439,25 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
         WM_TRY(wm_sample_truncate(ctx, a.out_f32, a.ldo, V, a.argmax, B, ts, xd, a.mask ? dmask : nullptr, mw, n_prompt, dpos, sp,
                                   rep ? a.rep.ban : nullptr, mw, dtr, nullptr));
     }
+    std::vector<int32_t> glen, gtok;
+    WmGivenPar gpar;
+    if (gv && gv->given) {   // as lane_prefill fills it: the table of a group whose rows are given up to this position
+        const int gi = pos + 1 - n_prompt, L = gi + 1 > 1 ? gi + 1 : 1;
+        glen.assign(B, 0); gtok.assign((size_t)B * L, 0);
+        for (int b = 0; b < B; ++b) {
+            if (gv->given[b] < 0) continue;
+            glen[b] = L;
+            for (int i = 0; i < L; ++i) gtok[(size_t)b * L + i] = gv->given[b];
+        }
+        int *dgl, *dgt;
+        const WmGivenPar *dgp;
+        WM_TRY(pool.get(&dgl, glen.data(), glen.size() * 4, s));
+        WM_TRY(pool.get(&dgt, gtok.data(), gtok.size() * 4, s));
+        gpar.stride = L; gpar.lens = dgl; gpar.tok = dgt;
+        WM_TRY(pool.get(&dgp, &gpar, sizeof(gpar), s));
+        WM_TRY(wm_given_tokens(ctx, a.out_f32, a.ldo, V, a.argmax, B, ts, xd, a.mask ? dmask : nullptr, mw, n_prompt, dpos, sp,
+                               rep ? a.rep.ban : nullptr, mw, dgp));
+    }
     // (ts, sp and xd are empty structs unless ts_mode, stop_on and x_on filled them)
     WM_TRY(wm_argmax_embed(ctx, a.argmax, n_tiles, B, dseq, dpos, n_prompt, dres, io->arg_first, n_ctx,
                            WmEmbedDev{dE, dpemb, K, dxn, dxbn, dstn, dmn}, ts, darr, io->fallback_tok, sp, xd, doff));
@@ -2445,6 +2473,11 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     if (io->ts_mode) {
         WM_HIP(hipMemcpyAsync(io->rng, ts.rng, (size_t)B * 16, hipMemcpyDeviceToHost, s));
         WM_HIP(hipMemcpyAsync(io->hist, ts.hist, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+    }
+    if (gv) {   // (the close reads these and writes none of them)
+        WM_HIP(hipMemcpyAsync(gv->tilemax_out, a.argmax, nt * 8, hipMemcpyDeviceToHost, s));
+        if (io->ts_mode) WM_HIP(hipMemcpyAsync(gv->key_ts_out, ts.key_ts, nt * 8, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(gv->win_out, xd.win, nt * 8, hipMemcpyDeviceToHost, s));
     }
     io->n_live = -1;
     if (io->stop_on) {
@@ -2504,6 +2537,24 @@ extern "C" int wmdbg_decode_close_trunc(wm_ctx *ctx, wmdbg_step *io, int top_k, 
     WM_REQUIRE(io->n_suppress_first == 0 || (io->mask_first != 0) == (io->pos == io->n_prompt - 1), WM_ERR_INVALID,
                "wmdbg_decode_close_trunc: mask_first must say whether this is position n_prompt - 1");
     return decode_close_run(ctx, io, false, 1.f, 0, nullptr, nullptr, &sp);
+}
+extern "C" int wmdbg_decode_close_given(wm_ctx *ctx, wmdbg_step *io, const int32_t *given, int top_k, float top_p, float min_p,
+                                         uint64_t *tilemax_out, uint64_t *key_ts_out, float *win_out) {
+    WM_REQUIRE(io && tilemax_out && key_ts_out && win_out, WM_ERR_INVALID, "wmdbg_decode_close_given: null");
+    WM_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p < 1.f, WM_ERR_INVALID,
+               "wmdbg_decode_close_given: top_k >= 0, top_p in (0, 1], min_p in [0, 1)");
+    WM_REQUIRE(io->x_on && io->B >= 1 && io->B <= WM_DEC_MAXB, WM_ERR_INVALID, "wmdbg_decode_close_given: needs x_on and 1 .. %d rows", WM_DEC_MAXB);
+    if (given)
+        for (int b = 0; b < io->B; ++b)
+            WM_REQUIRE(given[b] >= -1 && given[b] < io->V, WM_ERR_INVALID, "wmdbg_decode_close_given: row %d: id %d outside [-1, %d)", b,
+                       given[b], io->V);
+    // (the kernels take the first-position bitmap at position n_prompt - 1, the logits launch where mask_first says)
+    WM_REQUIRE(io->n_suppress_first == 0 || (io->mask_first != 0) == (io->pos == io->n_prompt - 1), WM_ERR_INVALID,
+               "wmdbg_decode_close_given: mask_first must say whether this is position n_prompt - 1");
+    const WmSampPar sp = {top_k, top_p, min_p};
+    const bool on = (top_k > 0 || top_p < 1.f || min_p > 0.f) && io->temperature > 0.f;
+    const CloseGiven gv = {given, tilemax_out, key_ts_out, win_out};
+    return decode_close_run(ctx, io, false, 1.f, 0, nullptr, nullptr, on ? &sp : nullptr, nullptr, nullptr, nullptr, nullptr, &gv);
 }
 extern "C" int wmdbg_decode_close_rows(wm_ctx *ctx, wmdbg_step *io, const float *row_T, const uint64_t *row_seed, int top_k,
                                         float top_p, float min_p) {
@@ -2645,6 +2696,21 @@ extern "C" int wmdbg_group_bias_rows(const int32_t *table_of_row, int B, const i
     std::vector<int32_t> r;
     wm_group_bias_rows(table_of_row, tab_grp, n_tables, b0, Cg, N, &r);
     std::copy(r.begin(), r.end(), rng_out);
+    return WM_OK;
+}
+
+extern "C" int wmdbg_group_given(const int32_t *lens, const int32_t *tokens, int stride, int rows, int b0, int Cg, int N, int32_t *lens_out,
+                                  int32_t *tok_out, int tok_cap, int32_t *L_out) {
+    WM_REQUIRE(lens && tokens && lens_out && tok_out && L_out && stride >= 1 && rows >= 1 && b0 >= 0 && Cg >= 1 && N >= 1 &&
+                   (int64_t)(b0 + Cg) * N <= rows && Cg * N <= WM_DEC_MAXB,
+               WM_ERR_INVALID, "wmdbg_group_given: bad geometry");
+    for (int r = 0; r < rows; ++r) WM_REQUIRE(lens[r] >= 0 && lens[r] <= stride, WM_ERR_INVALID, "wmdbg_group_given: lens[%d]", r);
+    std::vector<int32_t> gl, gt;
+    const int L = wm_group_given(lens, tokens, stride, b0, Cg, N, &gl, &gt);
+    WM_REQUIRE((int)gt.size() <= tok_cap, WM_ERR_INVALID, "wmdbg_group_given: %d words do not fit %d", (int)gt.size(), tok_cap);
+    std::copy(gl.begin(), gl.end(), lens_out);
+    std::copy(gt.begin(), gt.end(), tok_out);
+    *L_out = L;
     return WM_OK;
 }
 

@@ -81,6 +81,7 @@ static int alloc_decode_buffers(WmModel *m, hipStream_t s) {
     WM_TRY(dalloc(m, (void **)&m->dx_par, sizeof(WmXPar), s));
     WM_TRY(dalloc(m, (void **)&m->dsamp_par, sizeof(WmSampPar), s));
     WM_TRY(dalloc(m, (void **)&m->dalt_par, sizeof(WmAltPar), s));
+    WM_TRY(dalloc(m, (void **)&m->dgiven_par, sizeof(WmGivenPar), s));
     // (+16: the epilogue's padded 16-row blocks; second half: the rows' candidate words, WM_XIDS_CAND)
     WM_TRY(dalloc_t(m, &m->dx_ids, (size_t)WM_XIDS_WORDS, s));   // (third part: the sampling rows, WM_XIDS_ROWS)
     WM_TRY(dalloc_t(m, &m->dmel_win, (size_t)WM_DEC_MAXB, s));
@@ -463,6 +464,30 @@ int wm_model_alternatives(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &
                            rp.par ? rp.ban : nullptr, rp.words, m->dalt_par);
 }
 
+int wm_model_given_begin(wm_ctx *ctx, int rows, int stride, const int32_t *lens, const int32_t *tok, WmGivenPar *host_par) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && stride >= 1 && lens && tok, WM_ERR_INVALID, "given tokens: %d rows x %d tokens", rows,
+               stride);
+    const size_t nl = ((size_t)rows * 4 + 255) & ~(size_t)255, nt = (size_t)rows * stride * 4;
+    WM_TRY(m->given_ws.reserve(ctx->stream, nl + nt));
+    char *p = (char *)m->given_ws.p;
+    host_par->stride = stride; host_par->lens = (const int *)p; host_par->tok = (const int *)(p + nl);
+    WM_HIP(hipMemcpyAsync(p, lens, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipMemcpyAsync(p + nl, tok, nt, hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipMemcpyAsync(m->dgiven_par, host_par, sizeof(WmGivenPar), hipMemcpyHostToDevice, ctx->stream));
+    return WM_OK;
+}
+
+int wm_model_given_tokens(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(mode.given && mode.x && !mode.beam && mode.panel <= 1, WM_ERR_STATE, "given tokens: an extended-decode group without beams");
+    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
+    const WmRepDev rp = wm_model_rep_dev(m, mode);
+    return wm_given_tokens(ctx, m->dlogits, m->vpad, m->dims.n_vocab, m->dargmax, B, ts, wm_model_x_dev(m, mode),
+                           mode.mask ? m->dmask : nullptr, m->vpad / 32, n_prompt, m->dpos, wm_model_stop_dev(m, mode),
+                           rp.par ? rp.ban : nullptr, rp.words, m->dgiven_par);
+}
+
 WmTsDev wm_model_ts_dev(const WmModel *m) {
     WmTsDev t;
     memset(&t, 0, sizeof(t));
@@ -704,7 +729,8 @@ void wm_model_destroy(wm_ctx *ctx) {
     if (m->h_spec) (void)hipHostFree(m->h_spec);
     m->spec_ws.release();
     for (void *p : m->allocs) (void)hipFree(p);
-    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->acap_ws, &m->beam_ws, &m->beam_trace, &m->alt_ws}) b->release();
+    for (WmDevBuf *b : {&m->pcm_stage, &m->io_stage, &m->align_ws, &m->acap_ws, &m->beam_ws, &m->beam_trace, &m->alt_ws, &m->given_ws})
+        b->release();
     delete m;
     ctx->model = nullptr;
 }

@@ -153,6 +153,15 @@ struct WmSampPar {
     float top_p, min_p;
 };
 
+// Given tokens (wm_set_given_tokens; given.hip): one launch per position, last in front of the close, hands
+// the close the caller's token for the rows of the table.  The table lives in device memory (written at prefill), so a captured
+// position replays for any table.
+struct WmGivenPar {
+    int stride;       // tokens per row of the table (>= 1)
+    const int *lens;  // [rows] given tokens of each row, 0 .. stride (0: the row decodes freely)
+    const int *tok;   // [rows][stride]
+};
+
 // Top-n alternatives and entropy (wm_request_alternatives; alternatives.hip): one launch per position
 // between the logits product and the close lists a row's n best admissible ids with their log-probs and sums its entropy.  n
 // and the buffers live in device memory (WmAltPar, written at prefill), so a captured position replays for any request.
@@ -386,6 +395,9 @@ struct WmDecodeMode {
     // A request for alternatives is served (wm_request_alternatives): the logits launch stores the f32 row and wm_alternatives
     // runs between it and the close (in front of wm_sample_truncate).  Needs x.
     bool alt = false;
+    // The group holds a row with given tokens (wm_set_given_tokens): the logits launch stores the f32 row and wm_given_tokens runs
+    // last in front of the close.  Needs x.  A group of ordinary rows inside a call with a table does not set it.
+    bool given = false;
     // Temperature and seed are per row (wm_set_sampling_rows): the X-mode kernels read the rows' table behind WmModel::dx_ids.
     // Needs x.  The table's contents are uploaded at prefill; the key holds the flag, so a group with a table and one without
     // never share a captured graph.
@@ -403,7 +415,7 @@ struct WmDecodeMode {
     int acap_base = 0, acap_Tq = 0, acap_J = 0;
     float *acap_q = nullptr;
     bool operator==(const WmDecodeMode &o) const {
-        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && alt == o.alt && srows == o.srows && rep == o.rep && sb == o.sb && sbt == o.sbt && cst == o.cst && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
+        return acap == o.acap && acap_base == o.acap_base && acap_Tq == o.acap_Tq && acap_J == o.acap_J && acap_q == o.acap_q && panel == o.panel && trunc == o.trunc && alt == o.alt && given == o.given && srows == o.srows && rep == o.rep && sb == o.sb && sbt == o.sbt && cst == o.cst && n_cand == o.n_cand && beam == o.beam && mask == o.mask && ts == o.ts && x == o.x && off == o.off && stop == o.stop && budget == o.budget &&
                stop_eot == o.stop_eot && xattn_shared == o.xattn_shared;
     }
 };
@@ -556,6 +568,9 @@ struct WmModel {
     // [tok | lp | cnt | ent] (reserved and pad-filled at prefill, grow-only)
     WmAltPar *dalt_par = nullptr;
     WmDevBuf alt_ws;
+    // given tokens (wm_set_given_tokens): the device block a group's prefill writes and the group's table [lens | tok] (grow-only)
+    WmGivenPar *dgiven_par = nullptr;
+    WmDevBuf given_ws;
     // sequence bias (wm_set_sequence_bias): the context's expanded table, and the device state allocated at full capacity when
     // first switched on (dsb.par == null before that) -- never moved: the captured graphs hold the addresses
     bool sb_on = false;
@@ -664,6 +679,11 @@ int wm_model_sample_truncate(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMod
 int wm_model_alt_begin(wm_ctx *ctx, int rows, int max_new, int n, WmAltPar *host_par);
 // the alternatives launch of a position of a group with mode.alt, between wm_model_decode_step (want_logits) and the close
 int wm_model_alternatives(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode);
+// a group's prefill with mode.given: uploads the group's table -- lens [rows], tok [rows][stride], host memory that outlives the
+// stream's copies -- into given_ws and *host_par, with the addresses filled in, into the context's block
+int wm_model_given_begin(wm_ctx *ctx, int rows, int stride, const int32_t *lens, const int32_t *tok, WmGivenPar *host_par);
+// the given-tokens launch of a position of a group with mode.given: last in front of the close
+int wm_model_given_tokens(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode);
 // the device view of the sequence-bias state (par == null when mode.sb is false)
 WmSbDev wm_model_sb_dev(const WmModel *m, const WmDecodeMode &mode);
 // an expanded table (empty: off) -> this context's device table; the first non-empty one allocates the state
@@ -943,6 +963,15 @@ int wm_sample_truncate(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, 
 int wm_alternatives(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
                     const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
                     const WmStopDev &stop, const unsigned *ban, int ban_words, const WmAltPar *par);
+
+// given.hip (given tokens)
+// Per row (grid: rows) at a generated position gi < par->lens[row]: the row's per-tile keys (tilemax, ts.key_ts) and the winner
+// value of one tile are rewritten so that the close takes par->tok[row][gi], with the log-prob value - norm of the stored f32
+// logits [rows][ldo] under the row's own `forced` (-inf where the id is not admissible: beam_topk's test, row_list.h).  Rows with
+// stop.done set, prompt positions and rows with gi >= lens are not touched.  The log-sum-exp partials are read, never written.
+int wm_given_tokens(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, unsigned long long *tilemax, int rows, const WmTsDev &ts,
+                    const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr, const WmStopDev &stop,
+                    const unsigned *ban, int ban_words, const WmGivenPar *par);
 
 // repeat.hip (repetition rules)
 // Rebuild rows 0 .. B - 1 of rep.seen / rep.ban from the generated history of position *pos_ptr: tokens seq[(n_prompt + i) * B + b],

@@ -585,6 +585,26 @@ extern "C" int wm_request_alternatives(wm_ctx *ctx, const wm_alternatives_out *r
     return WM_OK;
 } WM_API_CATCH
 
+extern "C" int wm_set_given_tokens(wm_ctx *ctx, const int32_t *tokens, int stride, const int32_t *lens, int n) try {
+    WM_MODEL(ctx);
+    WmPending &p = m->pending;
+    p.given_lens.clear(); p.given_tok.clear(); p.given_stride = 0;   // whatever happens below, the table that was pending is gone
+    if (n == 0) return WM_OK;
+    WM_REQUIRE(n > 0 && stride >= 1 && tokens && lens, WM_ERR_INVALID, "set_given_tokens: bad table");
+    for (int r = 0; r < n; ++r) {
+        WM_REQUIRE(lens[r] >= 0 && lens[r] <= stride, WM_ERR_INVALID, "set_given_tokens: row %d has %d tokens, outside [0, %d]", r, lens[r],
+                   stride);
+        for (int i = 0; i < lens[r]; ++i) {
+            const int32_t t = tokens[(size_t)r * stride + i];
+            WM_REQUIRE(t >= 0 && t < m->dims.n_vocab, WM_ERR_INVALID, "set_given_tokens: row %d token %d: id %d outside the vocabulary", r, i, t);
+        }
+    }
+    p.given_lens.assign(lens, lens + n);
+    p.given_tok.assign(tokens, tokens + (size_t)n * stride);
+    p.given_stride = stride;
+    return WM_OK;
+} WM_API_CATCH
+
 // ---------------------------------------------------------------- word-level timestamps
 // openai-whisper's find_alignment (whisper/timing.py): a teacher-forced decoder pass that captures the alignment heads'
 // cross-attention queries, then the alignment kernels and DTW of align.hip.

@@ -96,6 +96,7 @@ struct LaneJob {
     std::vector<WmXRow> samp;      // its rows' temperatures and seeds, padded (wm_set_sampling_rows; likewise)
     WmSbPar sbpar = {};            // its sequence-bias table's counts (likewise)
     WmAltPar apar = {};            // its alternatives request: n and the lane's buffers (likewise)
+    WmGivenPar gpar = {};          // its given tokens: the group's table (likewise)
     WmCstPar cpar = {};            // its constraint automaton's counts (likewise)
     std::vector<int32_t> cstart;   // ... and its rows' start states [Bg] (likewise)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
@@ -208,6 +209,11 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     const WmPending &pend = *cfg.pending;
     j.mode.srows = xc.on && cfg.samp_rows;   // (a row map: the launch is in the plan when any row of the CALL samples)
     j.mode.alt = pend.alt_on;   // (tx_validate turned the extended decode on with it)
+    // given tokens: the group's rows of the call's table, by the hypothesis-row map; a group without a given row is an ordinary one
+    int given_L = 0;
+    if (!pend.given_lens.empty())
+        given_L = wm_group_given(pend.given_lens.data(), pend.given_tok.data(), pend.given_stride, j.b0, Cg, N, &j.tab.glen, &j.tab.gtok);
+    j.mode.given = given_L > 0;
     // the group's tables (pure: tx_plan.h), uploaded below: prompt tokens [P][Bg], a ragged call's offsets, budgets, sample ids
     j.P = wm_group_tables(call.prompts, cfg.n_prompt, j.mode.budget ? stop.budgets : nullptr, j.b0, Cg, N, WM_XIDS_CAND, xc.on, &j.tab);
     if (call.aligned) {   // the capture buffer and the alignment workspace, reserved before anything is enqueued
@@ -280,6 +286,11 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
         WM_REQUIRE(xc.on, WM_ERR_STATE, "alternatives need the extended decode");
         WM_TRY(wm_model_alt_begin(c, Bg, call.max_new, pend.alt.n, &j.apar));
     }
+    // given tokens: the group's table lives in device memory as well (the graph key holds `given` alone)
+    if (j.mode.given) {
+        WM_REQUIRE(xc.on, WM_ERR_STATE, "given tokens need the extended decode");
+        WM_TRY(wm_model_given_begin(c, Bg, given_L, j.tab.glen.data(), j.tab.gtok.data(), &j.gpar));
+    }
     // sequence bias: the table was uploaded when it was set; its counts go with the group, so a captured graph replays for any table
     if (j.mode.sbt) {   // row tables: the pool was uploaded when it was set; the rows' group ranges go with the group likewise
         WM_REQUIRE(!pend.bias_rows.empty(), WM_ERR_STATE, "sequence-bias tables are in force and the call has no row map (wm_set_bias_rows)");
@@ -345,7 +356,7 @@ int lane_prompt_panels(LaneJob &j, const TxCall &call, const wm_ctx *caller) {
 // gen (a beam group's generating positions): the step also stores the f32 logits and the beam kernels close it.
 int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) {
     WmAlignCap cap = {j.alayers.data(), mode.acap_q, mode.acap_Tq, mode.acap_J, mode.acap_base};   // an aligned group: every step captures
-    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen || mode.trunc || mode.alt, 0, j.c->model->dims.n_vocab - 1, mode.acap ? &cap : nullptr, mode, n_prompt));
+    WM_TRY(wm_model_decode_step(j.c, j.Bg, gen || mode.trunc || mode.alt || mode.given, 0, j.c->model->dims.n_vocab - 1, mode.acap ? &cap : nullptr, mode, n_prompt));
     if (gen) return wm_model_beam_close(j.c, j.Bg, n_prompt, mode);
     // alternatives: the row's list and entropy from the stored row and the partials as the logits launch left them -- in front of
     // the truncation, which rewrites the per-tile keys.  At a prompt position its workgroups return at once, as the truncation's.
@@ -355,6 +366,9 @@ int lane_position(LaneJob &j, const WmDecodeMode &mode, int n_prompt, bool gen) 
     // prompt position of such a group the row store is wasted and the truncation workgroups return at once (gi < 0): one
     // launch of the floor's cost per prompt position, paid so that no second graph shape exists.
     if (mode.trunc) WM_TRY(wm_model_sample_truncate(j.c, j.Bg, n_prompt, mode));
+    // given tokens: last in front of the close, so the alternatives list what the model preferred and a given row overrides a draw.
+    // At a prompt position, and for the group's free rows, its workgroups return at once.
+    if (mode.given) WM_TRY(wm_model_given_tokens(j.c, j.Bg, n_prompt, mode));
     return wm_model_close_step(j.c, j.Bg, n_prompt, true, nullptr, 0, mode);
 }
 
@@ -642,12 +656,23 @@ int tx_validate(wm_ctx *ctx, const TxCall &call, WmPending &pending, TxCfg *cfg)
         cfg->samp_rows = sampling;
     }
     // (the beam close reads the filtered partials; the repetition rules live in the extended epilogue)
-    xc.on = sampling || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || m->cst_on || alt;
+    const bool given = !pending.given_lens.empty();   // (a table without a given token changes no launch)
+    const bool given_any = std::any_of(pending.given_lens.begin(), pending.given_lens.end(), [](int32_t n) { return n > 0; });
+    xc.on = sampling || call.logprobs_out || call.no_speech_out || call.beam || m->rep_on || m->sb_on || m->sbt_on || m->cst_on || alt || given_any;
     if (alt) {   // the call's alternatives request (wm_request_alternatives checked n and the pointers)
         WM_TRY(tx_served(WM_PEND_ALT, call));
         WM_REQUIRE(alt->rows == (int64_t)B * call.n_cand && alt->max_new == max_new, WM_ERR_INVALID,
                    "alternatives were requested for %lld rows x %d tokens, the call has %lld x %d", (long long)alt->rows, alt->max_new,
                    (long long)B * call.n_cand, max_new);
+    }
+    if (given) {   // the call's given tokens (wm_set_given_tokens checked the ids and the lengths against the stride)
+        WM_TRY(tx_served(WM_PEND_GIVEN, call));
+        const int64_t rows = (int64_t)B * call.n_cand;
+        WM_REQUIRE((int64_t)pending.given_lens.size() == rows, WM_ERR_INVALID, "given tokens were set for %d rows, the call has %lld",
+                   (int)pending.given_lens.size(), (long long)rows);
+        for (int64_t r = 0; r < rows; ++r)
+            WM_REQUIRE(pending.given_lens[r] <= max_new, WM_ERR_INVALID, "row %lld: %d given tokens, the call generates at most %d",
+                       (long long)r, pending.given_lens[r], max_new);
     }
     WM_REQUIRE(!m->rep_on || !ctx->dbg_hooks, WM_ERR_STATE, "the repetition rules are not supported by the all-f32 precision path");
     WM_REQUIRE(!(m->sb_on || m->sbt_on) || !ctx->dbg_hooks, WM_ERR_STATE, "the sequence bias is not supported by the all-f32 precision path");

@@ -183,6 +183,22 @@ void wm_group_bias_rows(const int32_t *table_of_row, const int32_t *tab_grp, int
     }
 }
 
+int wm_group_given(const int32_t *lens, const int32_t *tok, int stride, int b0, int Cg, int N, std::vector<int32_t> *lens_out,
+                   std::vector<int32_t> *tok_out) {
+    const int Bg = Cg * N;
+    const size_t r0 = (size_t)b0 * N;
+    int L = 0;
+    for (int b = 0; b < Bg; ++b) L = std::max(L, (int)lens[r0 + b]);
+    lens_out->assign(lens + r0, lens + r0 + Bg);
+    tok_out->assign((size_t)Bg * std::max(L, 1), 0);
+    for (int b = 0; b < Bg; ++b)
+        for (int i = 0; i < L; ++i) {
+            const int n = lens[r0 + b];
+            if (n > 0) (*tok_out)[(size_t)b * L + i] = tok[(r0 + b) * stride + std::min(i, n - 1)];
+        }
+    return L;
+}
+
 void wm_group_rows_out(const int32_t *gen, const float *lp, const float *ns, const int32_t *budgets, int32_t eot, int N, int b0,
                        int Bg, int max_new, int32_t *tokens, int32_t *lens, float *logprobs, float *no_speech) {
     for (int b = 0; b < Bg; ++b) {   // [gi][row] -> [row of the call][candidate][gi]

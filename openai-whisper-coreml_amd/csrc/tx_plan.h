@@ -70,6 +70,7 @@ struct TxGroupTables {
     std::vector<int32_t> off;    // a ragged call: row offsets [Bg] = P - len
     std::vector<int32_t> bud;    // token budgets [Bg] (a call with budgets)
     std::vector<unsigned> ids;   // a candidate group: [2][ids_stride] window ids | candidate words; else the rows' sample ids [Bg]
+    std::vector<int32_t> glen, gtok;   // given tokens (wm_set_given_tokens): lens [Bg], tokens [Bg][L] (wm_group_given)
     std::vector<int32_t> sbr;    // row tables (wm_set_bias_rows): [Bg][2] (first group, end group) of each row's table in the pool
 };
 
@@ -88,6 +89,13 @@ int wm_group_tables(const TxPrompts &p, int n_prompt, const int32_t *budgets, in
 // is the caller's to refuse; here it reads as none.
 void wm_group_bias_rows(const int32_t *table_of_row, const int32_t *tab_grp, int n_tables, int b0, int Cg, int N,
                         std::vector<int32_t> *out);
+
+// The given tokens of the same group (wm_set_given_tokens): decoder row b is hypothesis row b0 * N + b of the call -- lens [B * N],
+// tok [B * N][stride] of the call.  lens_out [Bg], tok_out [Bg][L] with L = the group's longest given text (at least 1; the
+// tail of a shorter row repeats its last given token, a free row reads 0).  Returns L, or 0 when no row of the group is given:
+// such a group makes the launches of a call without a table.
+int wm_group_given(const int32_t *lens, const int32_t *tok, int stride, int b0, int Cg, int N, std::vector<int32_t> *lens_out,
+                   std::vector<int32_t> *tok_out);
 
 // ---------------------------------------------------------------- a group's outputs ----
 // The output rows of a finished plain (not beam) group from its fetched streams gen [max_new][Bg], lp [max_new][Bg] (read

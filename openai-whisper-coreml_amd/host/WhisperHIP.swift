@@ -297,6 +297,25 @@ struct Whisper {
         try check(f(ctx, temperatures.isEmpty ? nil : temperatures, seeds.isEmpty ? nil : seeds, Int32(temperatures.count)))
     }
 
+    /// Given tokens of the NEXT transcribe call on this context (wm_set_given_tokens; one list per hypothesis row of that call --
+    /// B, or B * best_of in the order [B][best_of] --, consumed by it): the row takes them in place of its own choices and
+    /// token_logprobs_out holds their log-probs; behind them it decodes freely, an empty list is an ordinary row.  [] drops a
+    /// pending table.  Not compiled in this repository (see the top of the file).
+    func setGivenTokens(_ rows: [[Int32]]) throws {
+        typealias GivenFn = @convention(c) (OpaquePointer, UnsafePointer<Int32>?, Int32, UnsafePointer<Int32>?, Int32) -> Int32
+        let f: GivenFn = try sym("wm_set_given_tokens")
+        if rows.isEmpty {
+            try check(f(ctx, nil, 0, nil, 0))
+            return
+        }
+        let stride = max(1, rows.map { $0.count }.max()!)
+        var tokens = [Int32](repeating: 0, count: rows.count * stride)
+        for (r, row) in rows.enumerated() {
+            for (i, t) in row.enumerated() { tokens[r * stride + i] = t }
+        }
+        try check(f(ctx, tokens, Int32(stride), rows.map { Int32($0.count) }, Int32(rows.count)))
+    }
+
     /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
     /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
     /// Not compiled in this repository (see the top of the file).
