@@ -947,6 +947,44 @@ WM_API int wm_request_alternatives(wm_ctx *ctx, const wm_alternatives_out *req /
 WM_API int wm_set_given_tokens(wm_ctx *ctx, const int32_t *tokens /* i32 [n][stride] */, int stride,
                                const int32_t *lens /* i32 [n], 0 .. stride */, int n);
 
+/* GIVEN PANELS: generated positions per decoder step over the GIVEN tokens of a transcribe call (wm_set_given_tokens).  A given
+ * text is known up front, so up to `width` of its positions can share one decoder step -- the weights streamed once, a window's
+ * cross-attention K/V read once -- each closed exactly as the one-position step closes it.
+ *   width : 1 .. WM_MAX_TEACHER_PANEL; 1 (the default) enqueues exactly the launches a call always enqueued.
+ * A context setting like wm_set_prompt_panel: not pending state, calls do not consume it; same inheritance as wm_set_suppress
+ * (wm_clone and the lanes of a call take it over).  WM_ERR_INVALID: width outside the range (the old width stays in force).
+ * A LAUNCH POLICY, NOT A NUMERICS SWITCH: tokens, lengths, token log-probs and no_speech_prob are bit-identical for every width,
+ * and the setting never makes a call fail.  THE RULE, per decode group of G rows with prompt length P:
+ *   SERVED GROUPS.  All of: the group holds a given row; it is a plain group (no best-of candidates, no beams) with uniform
+ *     prompts, the extended decode on and temperature 0 for every row (no row of a sampling row map samples; the sampling rules
+ *     are not read at temperature 0, as in every call); no
+ *     alternatives, repetition rules, sequence bias (single table or row tables), constraint or alignment capture; not the
+ *     all-f32 debug path and no debug hooks staged by the caller; and w = min(width, 128 / G) >= 2.  Timestamp rules, suppress
+ *     masks, budgets and the eot stop may be on or off.  Every other group steps one position at a time, exactly as without the
+ *     setting.
+ *   FIRST TOKEN.  Generated index 0 is always taken by the ordinary step at position P - 1 (the first-token suppress list,
+ *     max_initial_timestamp_index and the <|startoftranscript|> read of no_speech_prob live there; no panel meets them).
+ *   PHASE.  Lp = the largest L <= max_new with P + L - 1 < n_text_ctx such that for every row r and every gi in [1, L):
+ *     gi < lens[r] or gi >= min(budget[r], max_new) -- at every phase position each row is given, or already finished for a reason
+ *     the host knows.  Lp <= 1: no phase.  Otherwise generated indices [1, Lp) run as ceil((Lp - 1) / w) rounds, round at index
+ *     g0 of width min(w, Lp - g0), behind the ordinary step at P - 1; the group's ordinary steps (or captured graphs) continue from
+ *     position P + Lp - 1.  One round covers the whole group: no slices.
+ *   A ROUND at position pos (g0 = pos + 1 - P): the inputs tok[c][g0 + s - 1], s = 1 .. w - 1, are staged at positions pos + s and
+ *     the timestamp rules are replayed along them, so that row (c, s) sees the ranges after the tokens up to its own input; one
+ *     panel step over G x w rows with the stored f32 row (rows of finished windows are computed and ignored); per row the given
+ *     token's admissibility, value and log-prob by the arithmetic of the one-position step (the cases of wm_set_given_tokens apply
+ *     unchanged, a forced timestamp included; a row with NOTHING admissible takes the fallback token and -INFINITY as there, and --
+ *     the one exception to "the same bits" -- the later rows of that window in the SAME round were computed behind the table's
+ *     token, not the fallback); per window the commit -- its tokens and
+ *     log-probs up to its first eot (with the eot stop) or the end of its budget, pad and 0 behind, its rule state advanced along the
+ *     kept tokens, its done flag; the position advances by the round's width.  Behind the last round the step path's state
+ *     (rule state, done flags, the live list, the embedding of position P + Lp - 1) is what the one-position steps leave.
+ *   THE ONE EXCEPTION to "the same bits" is the nothing-admissible row named above: the round is not cut at that row.  It needs
+ *     every allowed id of a position suppressed (or NaN logits); under the timestamp rules eot stays allowed, so a caller who
+ *     does not suppress eot cannot meet it.
+ * The rounds run eagerly, not from captured graphs; no graph is dropped by this call. */
+WM_API int wm_set_given_panel(wm_ctx *ctx, int width);
+
 /* ------------------------------------------------- all GPUs of the node, one host process --- */
 /* the Swift host dlopens ONE library in ONE process; wm_multi drives n GPUs from it.  Weights are
  * replicated (one wm_ctx per device: fetch each with wm_multi_device_ctx and fill it with wm_load_weights /

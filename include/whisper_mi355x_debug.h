@@ -351,6 +351,58 @@ WM_API int wmdbg_prompt_panel_plan_batch(int n, const int32_t *in, int32_t *out)
 /* What the context's last decode-group prefill enqueued as prompt panels: out i32 [3] = P0, slices, panel steps (all slices).
  * All 0 when that group ran none (width 1, P0 < 2, a candidate / beam / speculative group). */
 WM_API int wmdbg_last_prompt_prefill(wm_ctx *ctx, int32_t *out);
+/* ---- given panels (wm_set_given_panel): the plan, and what the last group ran ---- */
+/* The given-panel plan of a decode group (host only, tx_plan.cpp wm_given_panel_plan): G rows (1 .. 128), the width (1 .. 8),
+ * lens i32 [G] the rows' given tokens, budgets i32 [G] or NULL, max_new, P prompt positions, n_text_ctx, and the group's mode as a
+ * bit word: 1 a given row, 2 candidates or beams, 4 ragged prompts, 8 extended decode, 16 sampling row map, 32 sampling rules in
+ * force at temperature > 0, 64 alternatives, 128 bias row tables, 256 sequence bias, 512 constraint, 1024 repetition-rule state,
+ * 2048 alignment capture, 4096 all-f32 path / debug hooks, 8192 temperature > 0.  out i32 [4] = reason (0: served; else the first
+ * test of the rule that failed, in the rule's order: 1 width 1, 2 no table, 3 candidates, 4 ragged, 5 no extended decode, 6 row
+ * map, 7 temperature, 8 alternatives, 9 row tables, 10 bias, 11 constraint, 12 repetition rules, 13 capture, 14 f32 / hooks,
+ * 15 min(width, 128 / G) < 2, 16 Lp <= 1), w, Lp, rounds.  _batch: n cases of 8 + 2 g_max words each -- G, width, max_new, P,
+ * n_text_ctx, bits, budgets given, 0, lens [g_max], budgets [g_max] -- out i32 [n][4]. */
+WM_API int wmdbg_given_panel_plan(int G, int width, const int32_t *lens, const int32_t *budgets, int max_new, int P, int n_text_ctx,
+                                  uint32_t bits, int32_t *out);
+WM_API int wmdbg_given_panel_plan_batch(int n, int g_max, const int32_t *in, int32_t *out);
+/* What the context's last decode group ran as given panels: out i32 [4] = first and last generated index of the phase, rounds,
+ * width w.  All 0 when that group ran none. */
+WM_API int wmdbg_last_given_panel(wm_ctx *ctx, int32_t *out);
+/* ... and of the context's lanes (wm_set_lanes): lane 0 is the context itself, lane k >= 1 its k-th clone, which ran the groups the
+ * scheduler handed it.  WM_ERR_INVALID for a lane the context does not have. */
+WM_API int wmdbg_last_given_panel_lane(wm_ctx *ctx, int lane, int32_t *out);
+/* ONE ROUND of a given-panel phase on caller-given state, the kernels of given_panel.hip alone: stage, the hook's own logits
+ * launch (final LayerNorm + tied-embedding product with the extended-decode epilogue over the G x w rows x, as
+ * wmdbg_decode_close builds it, under the ranges the stage left in the rows' slots), close, commit.  Row c * w + s is window c at
+ * position pos + s; pos >= n_prompt, pos + w < n_ctx, and the round's generated indices pos + 1 - n_prompt .. + w - 1 lie below
+ * max_new.  R = 128 entries per state buffer whatever G is: every buffer marked in/out goes up whole and comes down whole, so a
+ * caller's sentinels show what the kernels left alone.  ts_mode 0 or 2 (rng / hist as given); first / last: the phase's first /
+ * last round (first: the committed state is taken from hist / rng [G]; last: hist / rng get the [G] layout back). */
+typedef struct {
+    int32_t G, w, V, K, n_ctx, pos, n_prompt, max_new, first, last;
+    const float *x;             /* [G * w][K] the residual stream in front of the final LayerNorm */
+    const float *ln_g, *ln_b;   /* [K] */
+    const float *emb;           /* [V][K] token embedding (rounded to bf16) */
+    const float *bias;          /* [V] or NULL: added to the logits (places maxima) */
+    const int32_t *suppress;    /* ids suppressed at every position */
+    int32_t n_suppress, fallback_tok;
+    int32_t ts_mode, ts_begin, eot;
+    int32_t *hist, *rng;        /* in/out [R][4] the step path's slots: [G] committed in front of the first round, the rows' ranges after */
+    int32_t *chist, *crng;      /* in/out [R][4] the side area */
+    int32_t stop_on, stop_eot, pad_tok;
+    int32_t *done;              /* in/out [R] (stop_on) */
+    const int32_t *budget;      /* [G] or NULL */
+    int32_t *live_rows;         /* in/out [R] (stop_on) */
+    int32_t n_live;             /* in/out (stop_on) */
+    const int32_t *glens, *gtok;   /* the group's table: lens [G], tokens [G][stride] */
+    int32_t stride;
+    int32_t *seq;               /* in/out [n_ctx + 1][G] */
+    float *logprob;             /* in/out [max_new][G] */
+    int32_t *wtok;              /* in/out [R] the rows' tokens as the close left them */
+    float *wlp;                 /* in/out [R] */
+    float *logits;              /* out [G * w][V] the launch's f32 rows */
+    int32_t pos_out;
+} wmdbg_given_panel;
+WM_API int wmdbg_given_panel_round(wm_ctx *ctx, wmdbg_given_panel *io);
 /* The query capture of an alignment layer in a panel step: dq f32 [C * w][d], the layer's n_heads heads into slots slot0 .. of
  * cap f32 [C][Tq][J][64], pre-filled with the NaN bits WMDBG_SENTINEL_F32 (rows at positions >= Tq are not captured).
  * by_steps != 0: w step launches over the C windows instead. */

@@ -471,7 +471,7 @@ def rank_candidates(tokens, lens, logprobs, eot, length_penalty=None):
     return best, scores
 
 
-def score_given(ctx, wset, rows, prompts, texts, eot, append_eot=True, length_penalty=None, alternatives=None):
+def score_given(ctx, wset, rows, prompts, texts, eot, append_eot=True, length_penalty=None, alternatives=None, form=None):
     """The log-probs of texts the caller already has (CTranslate2's score_batch; n-best rescoring, "which of these K commands was
     spoken").  wset / rows: a Windows set and its rows (None: all) as for Context.transcribe_windows; prompts: one prompt for all,
     or one per row; texts: per row a list of texts, each a list of token ids.  append_eot: eot is scored behind every text
@@ -482,7 +482,12 @@ def score_given(ctx, wset, rows, prompts, texts, eot, append_eot=True, length_pe
     plain transcribe_windows call with the rows repeated.  Returns a SimpleNamespace: logprobs -- per row a list of f32 arrays,
     one per text --, sum_logprob and avg_logprob (openai-whisper's: sum / (len(text) + 1)) f64 lists of the same shape, `best` i32
     [rows] (the best-of call's ranking: wm_rank_candidates' rule under length_penalty; None on the plain path), `result` (the
-    call's own result) and, with alternatives=n, per row and text alt_tokens / alt_logprobs / alt_counts / entropy."""
+    call's own result) and, with alternatives=n, per row and text alt_tokens / alt_logprobs / alt_counts / entropy.
+    form: None keeps that choice; "rows" forces the plain call with the rows repeated -- the path Context.set_given_panel serves,
+    several positions of every text per decoder step --; "best_of" forces the best-of call and raises ValueError where the rows
+    do not all have the same number of texts."""
+    if form not in (None, "rows", "best_of"):
+        raise ValueError("score_given: form is None, 'rows' or 'best_of'")
     n_alt = alternatives_arg(alternatives)
     idx = list(range(len(wset))) if rows is None else [int(r) for r in np.asarray(rows).reshape(-1)]
     if len(texts) != len(idx) or any(len(t) == 0 for t in texts):
@@ -494,6 +499,10 @@ def score_given(ctx, wset, rows, prompts, texts, eot, append_eot=True, length_pe
     max_new = max(len(g) for gs in given for g in gs)
     K = len(given[0])
     same = all(len(gs) == K for gs in given)
+    if form == "best_of" and not same:
+        raise ValueError("score_given: form='best_of' needs the same number of texts for every row")
+    if form == "rows":
+        same = False
     pr = prompts
     if not same and not (isinstance(prompts, np.ndarray) and prompts.ndim == 1) and np.ndim(prompts[0]) != 0:
         pr = [prompts[w] for w, gs in enumerate(given) for _ in gs]   # a prompt per row: repeated with the row
@@ -2591,6 +2600,16 @@ class Context:
         self.lib.wm_set_prompt_panel.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self.lib.wm_set_prompt_panel.restype = ctypes.c_int
         _check(self.lib, self.lib.wm_set_prompt_panel(self.handle, int(n)))
+
+    def set_given_panel(self, n):
+        """wm_set_given_panel: generated positions per decoder step (1 .. MAX_TEACHER_PANEL; 1 = the default) over the given tokens
+        (given=, set_given_tokens) of a transcribe call.  A launch policy: every output is bit-identical for every width, and
+        no call fails because of it.  Served: plain temperature-0 groups with uniform prompts and no alternatives, repetition
+        rules, sequence bias or constraint; every other group steps one position at a time.  A context setting, not consumed by
+        calls; inherited by later clones and by the lanes of a call."""
+        self.lib.wm_set_given_panel.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.lib.wm_set_given_panel.restype = ctypes.c_int
+        _check(self.lib, self.lib.wm_set_given_panel(self.handle, int(n)))
 
     def set_teacher_panel(self, n):
         """wm_set_teacher_panel: positions per decoder step (1 .. MAX_TEACHER_PANEL; 1 = the default) of the teacher-forced passes

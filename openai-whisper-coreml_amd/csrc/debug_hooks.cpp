@@ -2036,6 +2036,39 @@ extern "C" int wmdbg_last_prompt_prefill(wm_ctx *ctx, int32_t *out) {
     return WM_OK;
 }
 
+// ------------------------------------------------------------------ given panels (wm_set_given_panel) ----
+extern "C" int wmdbg_given_panel_plan(int G, int width, const int32_t *lens, const int32_t *budgets, int max_new, int P, int n_text_ctx,
+                                      uint32_t bits, int32_t *out) {
+    WM_REQUIRE(out && lens && G >= 1 && G <= WM_DEC_MAXB && width >= 1 && width <= WM_MAX_TEACHER_PANEL && max_new >= 1 && P >= 1 &&
+                   n_text_ctx >= 1,
+               WM_ERR_INVALID, "wmdbg_given_panel_plan: bad arguments");
+    WmGivenPanelPlan pl;
+    wm_given_panel_plan(G, width, lens, budgets, max_new, P, n_text_ctx, bits, &pl);
+    out[0] = pl.reason; out[1] = pl.w; out[2] = pl.Lp; out[3] = pl.rounds;
+    return WM_OK;
+}
+extern "C" int wmdbg_given_panel_plan_batch(int n, int g_max, const int32_t *in, int32_t *out) {
+    WM_REQUIRE(n >= 0 && g_max >= 1 && g_max <= WM_DEC_MAXB && (n == 0 || (in && out)), WM_ERR_INVALID, "wmdbg_given_panel_plan_batch: bad arguments");
+    const size_t stride = 8 + 2 * (size_t)g_max;
+    for (int i = 0; i < n; ++i) {
+        const int32_t *c = in + stride * (size_t)i;
+        WM_REQUIRE(c[0] <= g_max, WM_ERR_INVALID, "wmdbg_given_panel_plan_batch: case %d has %d rows, the table holds %d", i, c[0], g_max);
+        WM_TRY(wmdbg_given_panel_plan(c[0], c[1], c + 8, c[6] ? c + 8 + g_max : nullptr, c[2], c[3], c[4], (uint32_t)c[5], out + 4 * (size_t)i));
+    }
+    return WM_OK;
+}
+extern "C" int wmdbg_last_given_panel(wm_ctx *ctx, int32_t *out) {
+    WM_REQUIRE(ctx && ctx->model && out, WM_ERR_INVALID, "wmdbg_last_given_panel: null pointer");
+    for (int i = 0; i < 4; ++i) out[i] = ctx->model->last_given_panel[i];
+    return WM_OK;
+}
+extern "C" int wmdbg_last_given_panel_lane(wm_ctx *ctx, int lane, int32_t *out) {
+    WM_REQUIRE(ctx && ctx->model && out, WM_ERR_INVALID, "wmdbg_last_given_panel_lane: null pointer");
+    WM_REQUIRE(lane >= 0 && lane <= (int)ctx->lanes.size(), WM_ERR_INVALID, "wmdbg_last_given_panel_lane: lane %d of %d", lane,
+               (int)ctx->lanes.size() + 1);
+    return wmdbg_last_given_panel(lane == 0 ? ctx : ctx->lanes[(size_t)lane - 1], out);
+}
+
 extern "C" int wmdbg_align_capture_panel(wm_ctx *ctx, const float *dq, int d, int C, int w, int pos, const int32_t *heads, int n_heads,
                                          int slot0, int Tq, int J, int by_steps, float *cap) {
     WM_TRY(wm_ctx_make_current(ctx));
@@ -2556,6 +2589,155 @@ extern "C" int wmdbg_decode_close_given(wm_ctx *ctx, wmdbg_step *io, const int32
     const CloseGiven gv = {given, tilemax_out, key_ts_out, win_out};
     return decode_close_run(ctx, io, false, 1.f, 0, nullptr, nullptr, on ? &sp : nullptr, nullptr, nullptr, nullptr, nullptr, &gv);
 }
+// One round of a given-panel phase on caller-given state (given_panel.hip): stage, the hook's own DE_LOGITS_X launch over the
+// G x w rows -- under the ranges the stage left in the rows' slots --, close and commit.  Every state buffer goes up whole (R =
+// WM_DEC_MAXB entries, whatever G is) and comes down whole.
+extern "C" int wmdbg_given_panel_round(wm_ctx *ctx, wmdbg_given_panel *io) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(io, WM_ERR_INVALID, "wmdbg_given_panel_round: null");
+    const int G = io->G, w = io->w, B = G * w, V = io->V, K = io->K, n_ctx = io->n_ctx, pos = io->pos, n_prompt = io->n_prompt;
+    constexpr int R = WM_DEC_MAXB;
+    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && B <= R && V >= 16 && K >= 64 && K % 64 == 0 && K <= 1280 && n_ctx >= 2 &&
+                   n_prompt >= 1 && pos >= n_prompt && pos + w < n_ctx && io->max_new >= 1 && pos + 1 - n_prompt + w <= io->max_new &&
+                   io->stride >= 1,
+               WM_ERR_INVALID, "wmdbg_given_panel_round: bad geometry");
+    WM_REQUIRE(io->x && io->ln_g && io->ln_b && io->emb && io->seq && io->logprob && io->wtok && io->wlp && io->logits && io->glens &&
+                   io->gtok && io->hist && io->rng && io->chist && io->crng && io->done && io->live_rows,
+               WM_ERR_INVALID, "wmdbg_given_panel_round: null pointer");
+    WM_REQUIRE(io->ts_mode == 0 || io->ts_mode == 2, WM_ERR_INVALID, "wmdbg_given_panel_round: ts_mode 0 or 2");
+    if (io->ts_mode)
+        WM_REQUIRE(io->ts_begin > 0 && io->ts_begin < V && io->eot >= 0 && io->eot < io->ts_begin, WM_ERR_INVALID,
+                   "wmdbg_given_panel_round: timestamp rules need 0 <= eot < ts_begin < V");
+    WM_REQUIRE(io->fallback_tok >= 0 && io->fallback_tok < V && io->pad_tok >= 0 && io->pad_tok < V && io->stop_eot < V, WM_ERR_INVALID,
+               "wmdbg_given_panel_round: fallback / pad / eot outside the vocabulary");
+    WM_REQUIRE(io->n_suppress >= 0 && (io->n_suppress == 0 || io->suppress), WM_ERR_INVALID, "wmdbg_given_panel_round: bad suppress list");
+    for (int c = 0; c < G; ++c) {
+        WM_REQUIRE(io->glens[c] >= 0 && io->glens[c] <= io->stride, WM_ERR_INVALID, "wmdbg_given_panel_round: lens[%d]", c);
+        for (int i = 0; i < io->glens[c]; ++i)
+            WM_REQUIRE(io->gtok[(size_t)c * io->stride + i] >= 0 && io->gtok[(size_t)c * io->stride + i] < V, WM_ERR_INVALID,
+                       "wmdbg_given_panel_round: given id of window %d outside the vocabulary", c);
+    }
+    for (int i = 0; i < (n_ctx + 1) * G; ++i)
+        WM_REQUIRE(io->seq[i] >= 0 && io->seq[i] < V, WM_ERR_INVALID, "wmdbg_given_panel_round: seq[%d] outside the vocabulary", i);
+    if (io->ts_mode)   // (the ranges are compared with ids, never indexed with; the history feeds ts_advance)
+        for (int i = 0; i < 4 * R; ++i)
+            WM_REQUIRE(io->rng[i] >= 0 && io->rng[i] <= V && io->crng[i] >= 0 && io->crng[i] <= V, WM_ERR_INVALID,
+                       "wmdbg_given_panel_round: rng[%d] outside [0, V]", i);
+    const int vpad = (V + 15) / 16 * 16, n_tiles = vpad / 16, mw = (vpad + 31) / 32;
+    std::vector<unsigned> mask((size_t)2 * mw, 0u);
+    for (int i = 0; i < io->n_suppress; ++i) {
+        WM_REQUIRE(io->suppress[i] >= 0 && io->suppress[i] < V, WM_ERR_INVALID, "wmdbg_given_panel_round: suppressed id %d", io->suppress[i]);
+        mask[io->suppress[i] >> 5] |= 1u << (io->suppress[i] & 31);
+    }
+    for (int i = 0; i < mw; ++i) mask[mw + i] = mask[i];
+    std::vector<bf16_t> e16, x16;
+    std::vector<float> st, mean;
+    tile_bf16(io->emb, (size_t)V, (size_t)K, e16);
+    stage_ln_rows(io->x, B, K, true, x16, st, mean);
+    const size_t nt = (size_t)B * n_tiles;
+    WmXPar xp;
+    memset(&xp, 0, sizeof(xp));
+    xp.sot_pos = -1; xp.ns_tok = -1; xp.n_prompt = n_prompt; xp.n_cand = 1;
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    DecGemvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.epi = DE_LOGITS_X; a.B = B; a.N = V; a.K = K; a.stats_parts = K / 16; a.ldo = vpad;
+    a.arg_first = 0; a.arg_last = V - 1;
+    const bf16_t *dE;
+    bf16_t *dEf;
+    float *dc1, *dc2;
+    const float *dg, *db, *dbias = nullptr;
+    WM_TRY(pool.get(&a.a, x16.data(), x16.size() * 2, s));
+    WM_TRY(pool.get(&dE, e16.data(), e16.size() * 2, s));
+    WM_TRY(pool.get(&dEf, nullptr, e16.size() * 2, s));
+    WM_TRY(pool.get(&dc1, nullptr, (size_t)vpad * 4, s));
+    WM_TRY(pool.get(&dc2, nullptr, (size_t)vpad * 4, s));
+    WM_TRY(pool.get(&dg, io->ln_g, (size_t)K * 4, s));
+    WM_TRY(pool.get(&db, io->ln_b, (size_t)K * 4, s));
+    if (io->bias) WM_TRY(pool.get(&dbias, io->bias, (size_t)V * 4, s));
+    WM_TRY(pool.get(&a.stats_in, st.data(), st.size() * 4, s));
+    WM_TRY(pool.get(&a.mean_in, mean.data(), (size_t)B * 4, s));
+    WM_TRY(pool.get(&a.mean_out, nullptr, (size_t)B * 4, s));
+    int *dpos;
+    const unsigned *dmask;
+    WM_TRY(pool.get(&dpos, &pos, 4, s));
+    WM_TRY(pool.get(&a.out_f32, nullptr, (size_t)B * vpad * 4, s));
+    WM_TRY(pool.get(&a.argmax, nullptr, nt * 8, s, 0xff));
+    WM_TRY(pool.get(&dmask, mask.data(), mask.size() * 4, s));
+    a.pos_ptr = dpos;
+    if (io->n_suppress > 0) { a.mask = dmask; a.mask_words = mw; a.mask_first_pos = -1; }
+    WmGivenPanelDev gp;
+    memset(&gp, 0, sizeof(gp));
+    if (io->ts_mode) {
+        WM_TRY(pool.get(&gp.ts.rng, io->rng, (size_t)R * 16, s));
+        WM_TRY(pool.get(&gp.ts.hist, io->hist, (size_t)R * 16, s));
+        WM_TRY(pool.get(&gp.ts.key_ts, nullptr, nt * 8, s, 0xff));
+        WM_TRY(pool.get(&gp.ts.lse, nullptr, nt * 8, s, 0xff));
+        gp.ts.ts_begin = io->ts_begin; gp.ts.eot = io->eot; gp.ts.n_vocab = V; gp.ts.max_initial = -1;
+    }
+    WM_TRY(pool.get(&gp.chist, io->chist, (size_t)R * 16, s));
+    WM_TRY(pool.get(&gp.crng, io->crng, (size_t)R * 16, s));
+    WM_TRY(pool.get(&gp.wtok, io->wtok, (size_t)R * 4, s));
+    WM_TRY(pool.get(&gp.wlp, io->wlp, (size_t)R * 4, s));
+    WM_TRY(pool.get(&gp.seq, io->seq, (size_t)(n_ctx + 1) * G * 4, s));
+    gp.pos = dpos; gp.max_new = io->max_new; gp.n_vocab = V;
+    WmGivenPar gpar;
+    int *dgl, *dgt;
+    WM_TRY(pool.get(&dgl, io->glens, (size_t)G * 4, s));
+    WM_TRY(pool.get(&dgt, io->gtok, (size_t)G * io->stride * 4, s));
+    gpar.stride = io->stride; gpar.lens = dgl; gpar.tok = dgt;
+    WM_TRY(pool.get(&gp.par, &gpar, sizeof(gpar), s));
+    WmXDev xd;
+    memset(&xd, 0, sizeof(xd));
+    WM_TRY(pool.get(&xd.par, &xp, sizeof(xp), s));
+    WM_TRY(pool.get(&xd.txt, nullptr, nt * 8, s, 0xff));
+    WM_TRY(pool.get(&xd.win, nullptr, nt * 8, s, 0xff));
+    WM_TRY(pool.get(&xd.all, nullptr, nt * 8, s, 0xff));
+    WM_TRY(pool.get(&xd.ns_v, nullptr, (size_t)B * 4, s, 0xff));
+    WM_TRY(pool.get(&xd.logprob, io->logprob, (size_t)io->max_new * G * 4, s));
+    WM_TRY(pool.get(&xd.nospeech, nullptr, (size_t)B * 4, s));
+    a.x = xd;
+    WmStopDev sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.pad_tok = io->pad_tok; sp.eot = -1;
+    if (io->stop_on) {
+        WM_TRY(pool.get(&sp.done, io->done, (size_t)R * 4, s));
+        WM_TRY(pool.get(&sp.live_rows, io->live_rows, (size_t)R * 4, s));
+        WM_TRY(pool.get(&sp.n_live, &io->n_live, 4, s));
+        if (io->budget) WM_TRY(pool.get(&sp.budget, io->budget, (size_t)G * 4, s));
+        sp.eot = io->stop_eot;
+    }
+    WM_TRY(wm_ln_fold(ctx, dE, dg, db, dbias, V, K, dEf, dc1, dc2));
+    a.W = dEf; a.c1 = dc1; a.c2 = dc2;
+    WM_TRY(wm_given_panel_stage(ctx, gp, sp, G, w, n_prompt, n_ctx, io->first != 0));
+    a.ts = gp.ts;   // (the rows' slots as the stage left them)
+    WM_TRY(wm_dec_gemv(ctx, a));
+    WM_TRY(wm_given_panel_close(ctx, a.out_f32, a.ldo, a.argmax, n_tiles, gp, xd, sp, io->n_suppress > 0 ? dmask : nullptr, mw, G, w,
+                                n_prompt, io->fallback_tok, io->last != 0));
+    std::vector<float> lg((size_t)B * vpad);
+    WM_HIP(hipMemcpyAsync(lg.data(), a.out_f32, lg.size() * 4, hipMemcpyDeviceToHost, s));
+    if (io->ts_mode) {
+        WM_HIP(hipMemcpyAsync(io->rng, gp.ts.rng, (size_t)R * 16, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->hist, gp.ts.hist, (size_t)R * 16, hipMemcpyDeviceToHost, s));
+    }
+    WM_HIP(hipMemcpyAsync(io->chist, gp.chist, (size_t)R * 16, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->crng, gp.crng, (size_t)R * 16, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->wtok, gp.wtok, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->wlp, gp.wlp, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->seq, gp.seq, (size_t)(n_ctx + 1) * G * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(io->logprob, xd.logprob, (size_t)io->max_new * G * 4, hipMemcpyDeviceToHost, s));
+    WM_HIP(hipMemcpyAsync(&io->pos_out, dpos, 4, hipMemcpyDeviceToHost, s));
+    if (io->stop_on) {
+        WM_HIP(hipMemcpyAsync(io->done, sp.done, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(io->live_rows, sp.live_rows, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(&io->n_live, sp.n_live, 4, hipMemcpyDeviceToHost, s));
+    }
+    WM_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) memcpy(io->logits + (size_t)b * V, lg.data() + (size_t)b * vpad, (size_t)V * 4);
+    return WM_OK;
+}
+
 extern "C" int wmdbg_decode_close_rows(wm_ctx *ctx, wmdbg_step *io, const float *row_T, const uint64_t *row_seed, int top_k,
                                         float top_p, float min_p) {
     WM_REQUIRE(io && row_T && row_seed, WM_ERR_INVALID, "wmdbg_decode_close_rows: null");

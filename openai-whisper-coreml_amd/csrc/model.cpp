@@ -469,8 +469,12 @@ int wm_model_given_begin(wm_ctx *ctx, int rows, int stride, const int32_t *lens,
     WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && stride >= 1 && lens && tok, WM_ERR_INVALID, "given tokens: %d rows x %d tokens", rows,
                stride);
     const size_t nl = ((size_t)rows * 4 + 255) & ~(size_t)255, nt = (size_t)rows * stride * 4;
-    WM_TRY(m->given_ws.reserve(ctx->stream, nl + nt));
+    // (behind the table: the side area of a given-panel phase -- committed history and ranges [R][4] each, the rows' tokens and
+    // log-probs [R] each)
+    const size_t side = (nl + nt + 255) & ~(size_t)255;
+    WM_TRY(m->given_ws.reserve(ctx->stream, side + (size_t)WM_DEC_MAXB * 10 * 4));
     char *p = (char *)m->given_ws.p;
+    m->dgiven_side = (int *)(p + side);
     host_par->stride = stride; host_par->lens = (const int *)p; host_par->tok = (const int *)(p + nl);
     WM_HIP(hipMemcpyAsync(p, lens, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
     WM_HIP(hipMemcpyAsync(p + nl, tok, nt, hipMemcpyHostToDevice, ctx->stream));
@@ -693,6 +697,7 @@ int wm_model_clone(wm_ctx *child, const wm_ctx *parent) {
     m->align_l = pm->align_l; m->align_h = pm->align_h;
     m->teacher_panel = pm->teacher_panel;
     m->prompt_panel = pm->prompt_panel;
+    m->given_panel = pm->given_panel;
     m->rep_on = pm->rep_on; m->rep_p = pm->rep_p; m->rep_n = pm->rep_n; m->rep_eot = pm->rep_eot;
     m->samp_k = pm->samp_k; m->samp_p = pm->samp_p; m->samp_minp = pm->samp_minp;
     if (m->rep_on || pm->sb_on || pm->sbt_on || pm->cst_on) WM_TRY(alloc_repetition_state(m, child->stream));
@@ -1311,6 +1316,56 @@ int wm_model_prompt_prefill(wm_ctx *ctx, int G, int P0, const WmDecodeMode &mode
     // *dpos == P0: the group's rows at that position (one row per window: embed_row, P0 >= 2)
     WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, 1, T, e, off0));
     m->last_prefill[0] = P0; m->last_prefill[1] = pl.slices; m->last_prefill[2] = pl.slices * pl.steps;
+    return WM_OK;
+}
+
+// ------------------------------------------------------------------ given panels (wm_set_given_panel)
+int wm_model_given_panel_dev(wm_ctx *ctx, int max_new, WmGivenPanelDev *out) {
+    WmModel *m = ctx->model;
+    WM_REQUIRE(m->dgiven_side, WM_ERR_STATE, "given panels: the group has no table (wm_model_given_begin)");
+    constexpr size_t R = WM_DEC_MAXB;
+    int *p = m->dgiven_side;
+    WmGivenPanelDev gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.seq = m->dseq; gp.pos = m->dpos; gp.ts = wm_model_ts_dev(m);
+    gp.chist = p; gp.crng = p + R * 4; gp.wtok = p + R * 8; gp.wlp = (float *)(p + R * 9);
+    gp.par = m->dgiven_par; gp.max_new = max_new; gp.n_vocab = m->dims.n_vocab;
+    *out = gp;
+    return WM_OK;
+}
+
+// A round: stage, the panel's embeddings, one step over G x w rows under the group's own mode with the f32 row stored (the pattern
+// of wm_model_spec_panel_step: the rows of frozen windows are computed and ignored, no live list), close + commit.  Eager.
+int wm_model_given_panel_phase(wm_ctx *ctx, int G, int w, int Lp, int n_prompt, int max_new, const WmDecodeMode &mode) {
+    WmModel *m = ctx->model;
+    const int T = m->dims.n_text_ctx, V = m->dims.n_vocab;
+    WM_TRY(panel_check(ctx, G, 0, G, w));
+    WM_REQUIRE(mode.given && mode.x && !mode.off && !mode.rep && !mode.sb && !mode.cst && !mode.alt && !mode.trunc && !mode.srows &&
+                   mode.n_cand <= 1 && !mode.beam && !mode.acap,
+               WM_ERR_STATE, "given panels: a plain temperature-0 extended-decode group with a table and no per-row rule state");
+    WM_REQUIRE(w >= 2 && Lp >= 2 && Lp <= max_new && n_prompt + Lp - 1 < T, WM_ERR_STATE, "given panels: nothing to run for %d rows up to index %d", G, Lp);
+    WmGivenPanelDev gp;
+    WM_TRY(wm_model_given_panel_dev(ctx, max_new, &gp));
+    if (!mode.ts) memset(&gp.ts, 0, sizeof(gp.ts));
+    WmDecodeMode pm = mode;
+    pm.stop = false; pm.budget = false; pm.stop_eot = -1;
+    const WmStopDev stop = wm_model_stop_dev(m, mode);
+    const WmXDev xd = wm_model_x_dev(m, mode);
+    const WmEmbedDev e = wm_model_embed_dev(m);
+    int rounds = 0;
+    for (int g0 = 1; g0 < Lp; g0 += w, ++rounds) {
+        const int wr = std::min(w, Lp - g0);
+        const bool last = g0 + wr >= Lp;
+        WM_TRY(wm_given_panel_stage(ctx, gp, stop, G, wr, n_prompt, T, g0 == 1));
+        WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, wr, T, e));
+        pm.panel = wr;
+        WM_TRY(decode_step_impl(ctx, G * wr, true, 0, V - 1, nullptr, pm, n_prompt, G, 0));
+        WM_TRY(wm_given_panel_close(ctx, m->dlogits, m->vpad, m->dargmax, m->vpad / 16, gp, xd, stop, mode.mask ? m->dmask : nullptr,
+                                    m->vpad / 32, G, wr, n_prompt, mode.ts ? m->ts_eot : 0, last));
+    }
+    // *dpos == n_prompt + Lp - 1: the group's rows at that position, as wm_model_prompt_prefill ends
+    WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, 1, T, e));
+    m->last_given_panel[0] = 1; m->last_given_panel[1] = Lp - 1; m->last_given_panel[2] = rounds; m->last_given_panel[3] = w;
     return WM_OK;
 }
 

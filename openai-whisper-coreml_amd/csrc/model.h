@@ -571,6 +571,7 @@ struct WmModel {
     // given tokens (wm_set_given_tokens): the device block a group's prefill writes and the group's table [lens | tok] (grow-only)
     WmGivenPar *dgiven_par = nullptr;
     WmDevBuf given_ws;
+    int *dgiven_side = nullptr;   // ... and behind the table the side area of a given-panel phase (wm_model_given_panel_dev), set with it
     // sequence bias (wm_set_sequence_bias): the context's expanded table, and the device state allocated at full capacity when
     // first switched on (dsb.par == null before that) -- never moved: the captured graphs hold the addresses
     bool sb_on = false;
@@ -605,6 +606,10 @@ struct WmModel {
     // all 0: none ran -- wmdbg_last_prompt_prefill)
     int prompt_panel = 1;
     int last_prefill[3] = {0, 0, 0};
+    // wm_set_given_panel: generated positions per step of a served group's given phase (1: none; a launch policy: same bits), and
+    // what the context's last group ran (first and last generated index, rounds, width; all 0: no phase -- wmdbg_last_given_panel)
+    int given_panel = 1;
+    int last_given_panel[4] = {0, 0, 0, 0};
     // wm_transcribe_mel_beam: the group's beam state (WmBeamDev; allocated once at its largest size, so captured graphs keep
     // their addresses) and the device buffer of the debug library's trace capture
     WmDevBuf beam_ws;
@@ -728,6 +733,14 @@ int wm_spec_commit(wm_ctx *ctx, const WmSpecDev &sp, const WmXDev &xd, const WmS
 // cache-only panel steps at the context's width, then *dpos = P0 and rows 0 .. G - 1 of dx / dxb / dstats / dmean hold the
 // embedding of position P0 as the close of step P0 - 1 would have left it.  P0 >= 2 and a width > 1 (the plan says so).
 int wm_model_prompt_prefill(wm_ctx *ctx, int G, int P0, const WmDecodeMode &mode);
+// Given panels (wm_set_given_panel, tx_plan.h wm_given_panel_plan): generated indices [1, Lp) of a served group of G rows, the
+// device position at n_prompt, as rounds of w positions (given_panel.hip); then *dpos = n_prompt + Lp - 1, the stop state, the
+// rules' state and rows 0 .. G - 1 of dx / dxb / dstats / dmean are what the plain steps would have left.  Needs the group's
+// table uploaded (wm_model_given_begin).
+struct WmGivenPanelDev;
+int wm_model_given_panel_phase(wm_ctx *ctx, int G, int w, int Lp, int n_prompt, int max_new, const WmDecodeMode &mode);
+// the device view of a group's given-panel state (the side area lives behind the table in given_ws)
+int wm_model_given_panel_dev(wm_ctx *ctx, int max_new, WmGivenPanelDev *out);
 int wm_model_embed_first(wm_ctx *ctx, int B, const WmDecodeMode &mode = WmDecodeMode());
 // arg-max reduce + write next token (positions >= n_prompt) + embed next position + advance *dpos
 int wm_model_close_step(wm_ctx *ctx, int B, int n_prompt, bool write_seq, int *result, int arg_first,
@@ -972,6 +985,35 @@ int wm_alternatives(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, con
 int wm_given_tokens(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, unsigned long long *tilemax, int rows, const WmTsDev &ts,
                     const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr, const WmStopDev &stop,
                     const unsigned *ban, int ban_words, const WmGivenPar *par);
+
+// given_panel.hip (given tokens in panels, wm_set_given_panel)
+// A round of a served group of G windows at position pos = *pos_ptr (generated index g0 = pos + 1 - n_prompt) closes w positions per
+// window: row c * w + s of the panel step is window c at position pos + s.  The windows' committed timestamp-rule state lives in
+// the side area (chist, crng) while the rounds run: the rng slots of WmTsDev are per ROW of the step (G x w).
+struct WmGivenPanelDev {
+    int *seq;          // the token buffer [n_text_ctx][G]
+    int *pos;          // the device position
+    WmTsDev ts;        // the timestamp rules (rng == null: off)
+    int *chist, *crng; // [G][4] committed history and ranges
+    int *wtok;         // [G x w] the rows' tokens as their close chose them
+    float *wlp;        // [G x w] and their log-probs
+    const WmGivenPar *par;   // the group's table
+    int max_new, n_vocab;
+};
+// STAGE (one workgroup, thread c owns window c): tokens tok[c][g0 + s - 1], s = 1 .. w - 1, go to positions pos + s of the token
+// buffer (a row without a token there -- finished by its budget -- gets stop.pad_tok) and the rules' ranges after the tokens up
+// to each row's own input go to the rows' rng slots.  first: the committed state is taken from ts.hist / ts.rng [G] first.
+int wm_given_panel_stage(wm_ctx *ctx, const WmGivenPanelDev &gp, const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx, bool first);
+// CLOSE (one workgroup per window, wave s closes row (c, s)) and COMMIT (one workgroup, thread c owns window c).  The close: per row
+// given_tokens_kernel's steps (`forced` from the partials, the admissibility of the one id, the hand-over into the row's keys)
+// and then the arg-max close's calls into dec_close.h on what the hand-over left.  The commit: a live window writes its tokens and
+// log-probs up to its first eot / the end of its budget and pads behind, advances its committed rule state and its done flag;
+// the position advances by w; the live list is rebuilt.  last: ts.hist / ts.rng get the [G] layout of the step path back.
+int wm_given_panel_close(wm_ctx *ctx, const float *logits, long ldo, unsigned long long *tilemax, int n_tiles, const WmGivenPanelDev &gp,
+                         const WmXDev &xd, const WmStopDev &stop, const unsigned *mask, int mask_words, int G, int w, int n_prompt,
+                         int fallback_tok, bool last);
+int wm_given_panel_commit(wm_ctx *ctx, const WmGivenPanelDev &gp, const WmXDev &xd, const WmStopDev &stop, int G, int w, int n_prompt,
+                          bool last);
 
 // repeat.hip (repetition rules)
 // Rebuild rows 0 .. B - 1 of rep.seen / rep.ban from the generated history of position *pos_ptr: tokens seq[(n_prompt + i) * B + b],

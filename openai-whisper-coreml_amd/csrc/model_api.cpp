@@ -275,6 +275,13 @@ extern "C" int wm_set_prompt_panel(wm_ctx *ctx, int width) try {
                WM_MAX_TEACHER_PANEL);
     return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { c->model->prompt_panel = width; return (int)WM_OK; });
 } WM_API_CATCH
+extern "C" int wm_set_given_panel(wm_ctx *ctx, int width) try {
+    WM_MODEL(ctx);
+    (void)m;
+    WM_REQUIRE(width >= 1 && width <= WM_MAX_TEACHER_PANEL, WM_ERR_INVALID, "set_given_panel: width %d outside [1, %d]", width,
+               WM_MAX_TEACHER_PANEL);
+    return wm_for_each_lane(ctx, true, [&](wm_ctx *c) { c->model->given_panel = width; return (int)WM_OK; });
+} WM_API_CATCH
 extern "C" int wm_set_lanes(wm_ctx *ctx, int n_lanes) try {
     WM_REQUIRE(ctx, WM_ERR_INVALID, "null context");
     WM_REQUIRE(n_lanes >= 0 && n_lanes <= 8, WM_ERR_INVALID, "set_lanes: 0 (default) .. 8");

@@ -13,6 +13,13 @@ struct RowAdmit {
     const unsigned *mrow, *brow;
 };
 
+// The same test for ONE id (the per-id test of row_list_local_best below): is n in the row's admissible set?
+__device__ __forceinline__ bool row_admits(const RowAdmit &a, int n) {
+    const bool in_text = !a.forced && n >= a.rng.x && n < a.rng.y, in_ts = n >= a.rng.z && n < a.rng.w;
+    const unsigned w = (a.mrow ? a.mrow[n >> 5] : 0u) | (a.brow ? a.brow[n >> 5] : 0u);
+    return n >= 0 && n < a.V && (in_text || in_ts) && !((w >> (n & 31)) & 1u);
+}
+
 // A thread's best admissible key below `bound`.  visit(n, v) sees every admissible id of the thread, ascending, with its
 // stored value: the pass that a caller's own per-id sums share with the scan.
 // A pass is latency-bound (one workgroup, ~51 ids per thread from L2): the loads of ROW_LIST_UNROLL ids -- value, suppress word,

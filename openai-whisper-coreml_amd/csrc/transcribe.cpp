@@ -97,6 +97,7 @@ struct LaneJob {
     WmSbPar sbpar = {};            // its sequence-bias table's counts (likewise)
     WmAltPar apar = {};            // its alternatives request: n and the lane's buffers (likewise)
     WmGivenPar gpar = {};          // its given tokens: the group's table (likewise)
+    WmGivenPanelPlan gplan;        // ... and their panel phase (wm_set_given_panel; WM_GP_SERVED: still to run, behind position P - 1)
     WmCstPar cpar = {};            // its constraint automaton's counts (likewise)
     std::vector<int32_t> cstart;   // ... and its rows' start states [Bg] (likewise)
     std::vector<float> lp, ns;     // its log-probs [max_new][Bg] and no-speech probabilities [Bg]
@@ -194,6 +195,8 @@ int lane_prefill(LaneJob &j, const TxCall &call, const TxCfg &cfg) {
     const XCfg &xc = cfg.xc;
     const int Bg = j.Bg, Cg = j.Cg, N = call.n_cand;   // decoder rows, encoder rows (windows), candidates per window
     m->last_prefill[0] = m->last_prefill[1] = m->last_prefill[2] = 0;   // (set again by this group's prompt panels, if it runs any)
+    for (int &v : m->last_given_panel) v = 0;                             // (... by its given panels)
+    j.gplan = WmGivenPanelPlan();
     // the mode of this group's decode: the lane's own context settings and the call's options, in this one place
     j.mode = WmDecodeMode();
     j.mode.mask = m->mask_on; j.mode.ts = m->ts_on; j.mode.x = xc.on; j.mode.off = call.prompts.len != nullptr;
@@ -350,6 +353,41 @@ int lane_prompt_panels(LaneJob &j, const TxCall &call, const wm_ctx *caller) {
     return WM_OK;
 }
 
+// Given panels (wm_set_given_panel): whether this group runs a phase, decided behind its prefill from the
+// group's mode, its rows' given lengths and budgets (tx_plan.h wm_given_panel_plan: pure).  The setting never makes a call fail:
+// a group the rule does not serve steps one position at a time.
+void lane_given_plan(LaneJob &j, const TxCall &call, const wm_ctx *caller) {
+    const WmModel *m = j.c->model;
+    const WmDecodeMode &md = j.mode;
+    unsigned bits = 0;
+    if (md.given) bits |= WM_GPB_GIVEN;
+    if (call.n_cand != 1 || call.beam) bits |= WM_GPB_CAND;
+    if (md.off) bits |= WM_GPB_OFF;
+    if (md.x) bits |= WM_GPB_X;
+    if (md.srows) bits |= WM_GPB_SROWS;
+    if (md.trunc) bits |= WM_GPB_TRUNC;
+    if (md.x && j.xpar.sample) bits |= WM_GPB_SAMPLE;
+    if (md.alt) bits |= WM_GPB_ALT;
+    if (md.sbt) bits |= WM_GPB_SBT;
+    if (md.sb) bits |= WM_GPB_SB;
+    if (md.cst) bits |= WM_GPB_CST;
+    if (md.rep) bits |= WM_GPB_REP;
+    if (md.acap) bits |= WM_GPB_ACAP;
+    if (call.f32_path || caller->dbg_hooks) bits |= WM_GPB_F32;
+    wm_given_panel_plan(j.Bg, m->given_panel, md.given ? j.tab.glen.data() : nullptr, md.budget ? j.tab.bud.data() : nullptr, call.max_new,
+                        j.P, m->dims.n_text_ctx, bits, &j.gplan);
+}
+
+// ... and the phase itself, enqueued eagerly behind the ordinary step at position P - 1 (which took generated index 0): generated
+// indices [1, Lp) in rounds; the group's ordinary steps or captured graphs continue from position P + Lp - 1.
+int lane_given_panels(LaneJob &j, int max_new, const WmDecodeMode &mode) {
+    const WmGivenPanelPlan pl = j.gplan;
+    j.gplan = WmGivenPanelPlan();   // (runs once)
+    WM_TRY(wm_model_given_panel_phase(j.c, j.Bg, pl.w, pl.Lp, j.P, max_new, mode));
+    j.t = j.P + pl.Lp - 1;
+    return WM_OK;
+}
+
 // One decoder position = 8 launches per layer + logits + arg-max/embed (which writes the next token, embeds the
 // next position and advances *dpos).  Nothing in it depends on host state, so it is captured ONCE into a
 // hipGraph per lane and replayed for every position -- and `burst` consecutive positions are captured as one more graph.
@@ -500,31 +538,38 @@ int lane_burst(LaneJob &j, int n_prompt, int n_steps, bool use_graph, bool share
     // a beam group: positions 0 .. n_prompt - 2 step through the prompt (the arg-max close), the others generate (the beam
     // close); a burst stays on one side
     const bool gen = j.mode.beam && j.t >= n_prompt - 1;
-    const int left = (j.mode.beam && !gen ? n_prompt - 1 : n_steps) - j.t;
-    const int k = left < K ? left : K;
     const int sh = shared ? 1 : 0;
     WmDecodeMode mode = j.mode;   // what every step of this burst, launched or captured, is handed
     mode.xattn_shared = shared;
-    WmModel::GraphSet *g = use_graph ? &m->graph_sets[j.gset] : nullptr;
-    WmGraph *g1 = g ? (gen ? g->b1 : g->g1) : nullptr, *gk = g ? (gen ? g->bk : g->gk) : nullptr;
-    int *burst = g ? (gen ? g->bburst : g->burst) : nullptr;
-    if (use_graph && k == K && K > 1) {
-        if (!gk[sh].e || burst[sh] != K) {
-            WM_TRY(capture_positions(j, mode, n_prompt, K, gen, &gk[sh]));
-            burst[sh] = K;
-        }
-        WM_HIP(hipGraphLaunch(gk[sh].e, c->stream));
+    // a group with a given-panel phase to run (never a beam group): a burst ends with the step at position n_prompt - 1, and the
+    // phase is the next burst
+    const bool phase = j.gplan.reason == WM_GP_SERVED;
+    if (phase && j.t == n_prompt) {
+        WM_TRY(lane_given_panels(j, n_steps - n_prompt + 1, mode));
     } else {
-        if (use_graph && !g1[sh].e) WM_TRY(capture_positions(j, mode, n_prompt, 1, gen, &g1[sh]));
-        for (int i = 0; i < k; ++i) {
-            if (use_graph) {
-                WM_HIP(hipGraphLaunch(g1[sh].e, c->stream));
-            } else {
-                WM_TRY(lane_position(j, mode, n_prompt, gen));
+        const int left = (j.mode.beam && !gen ? n_prompt - 1 : (phase ? n_prompt : n_steps)) - j.t;
+        const int k = left < K ? left : K;
+        WmModel::GraphSet *g = use_graph ? &m->graph_sets[j.gset] : nullptr;
+        WmGraph *g1 = g ? (gen ? g->b1 : g->g1) : nullptr, *gk = g ? (gen ? g->bk : g->gk) : nullptr;
+        int *burst = g ? (gen ? g->bburst : g->burst) : nullptr;
+        if (use_graph && k == K && K > 1) {
+            if (!gk[sh].e || burst[sh] != K) {
+                WM_TRY(capture_positions(j, mode, n_prompt, K, gen, &gk[sh]));
+                burst[sh] = K;
+            }
+            WM_HIP(hipGraphLaunch(gk[sh].e, c->stream));
+        } else {
+            if (use_graph && !g1[sh].e) WM_TRY(capture_positions(j, mode, n_prompt, 1, gen, &g1[sh]));
+            for (int i = 0; i < k; ++i) {
+                if (use_graph) {
+                    WM_HIP(hipGraphLaunch(g1[sh].e, c->stream));
+                } else {
+                    WM_TRY(lane_position(j, mode, n_prompt, gen));
+                }
             }
         }
+        j.t += k;
     }
-    j.t += k;
     if (j.mode.stop) {  // the live-row count after this burst, where the host can read it without touching the stream
         const int slot = j.bursts % WM_NLIVE_RING;
         WM_HIP(hipMemcpyAsync(m->h_nlive + slot, m->dnlive, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -792,6 +837,7 @@ int lane_start(TxRun &r, LaneJob &j) {
     j.bpar.max_cand = call.max_cand; j.bpar.max_new = call.max_new; j.bpar.eot = call.eot; j.bpar.pad = call.eot >= 0 ? call.eot : 0;
     WM_TRY(lane_prefill(j, call, r.cfg));
     WM_TRY(lane_prompt_panels(j, call, r.ctx));
+    lane_given_plan(j, call, r.ctx);
     if (r.cfg.use_graph) WM_TRY(lane_graph(j, j.P));
     j.state = LaneJob::DECODING;
     return WM_OK;

@@ -261,6 +261,41 @@ void wm_prompt_panel_plan(int G, int width, int P, int sot_pos, int acap_base, i
     out->steps = (P0 + out->w - 1) / out->w;
 }
 
+// ---------------------------------------------------------------- given panels ----
+void wm_given_panel_plan(int G, int width, const int32_t *lens, const int32_t *budgets, int max_new, int P, int n_text_ctx, unsigned bits,
+                         WmGivenPanelPlan *out) {
+    *out = WmGivenPanelPlan();
+    auto no = [&](int reason) { out->reason = reason; };
+    if (width <= 1) return no(WM_GP_WIDTH1);
+    if (!(bits & WM_GPB_GIVEN) || !lens) return no(WM_GP_NO_TABLE);
+    if (bits & WM_GPB_CAND) return no(WM_GP_CANDIDATES);
+    if (bits & WM_GPB_OFF) return no(WM_GP_RAGGED);
+    if (!(bits & WM_GPB_X)) return no(WM_GP_NO_X);
+    if (bits & WM_GPB_SROWS) return no(WM_GP_SAMP_ROWS);
+    if (bits & (WM_GPB_TRUNC | WM_GPB_SAMPLE)) return no(WM_GP_TRUNC);
+    if (bits & WM_GPB_ALT) return no(WM_GP_ALT);
+    if (bits & WM_GPB_SBT) return no(WM_GP_SB_TABLES);
+    if (bits & WM_GPB_SB) return no(WM_GP_SB);
+    if (bits & WM_GPB_CST) return no(WM_GP_CST);
+    if (bits & WM_GPB_REP) return no(WM_GP_REP);
+    if (bits & WM_GPB_ACAP) return no(WM_GP_ACAP);
+    if (bits & WM_GPB_F32) return no(WM_GP_F32);
+    if (G < 1) return no(WM_GP_NARROW);
+    const int wd = width > WM_PANEL_MAX_WIDTH ? WM_PANEL_MAX_WIDTH : width;
+    out->w = std::min(wd, WM_DEC_MAXB / G);
+    if (out->w < 2) return no(WM_GP_NARROW);
+    int L = std::min(max_new, n_text_ctx - P);
+    for (int r = 0; r < G; ++r) {
+        const int fin = budgets && budgets[r] < max_new ? budgets[r] : max_new;   // the row is finished from this index on
+        const int first_free = lens[r] > 1 ? lens[r] : 1;                       // the first index >= 1 that is not given
+        if (first_free < fin && first_free < L) L = first_free;
+    }
+    out->Lp = L < 0 ? 0 : L;
+    if (out->Lp <= 1) return no(WM_GP_NO_PHASE);
+    out->rounds = (out->Lp - 1 + out->w - 1) / out->w;
+    out->reason = WM_GP_SERVED;
+}
+
 // ---------------------------------------------------------------- the hooks' flat forms ----
 int wm_tx_plan_flat(const int32_t *in, int32_t *out, int32_t *cut, int cut_cap, int max_group_rows) {
     WmTxPlanIn pin;

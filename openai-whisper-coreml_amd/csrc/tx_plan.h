@@ -144,6 +144,49 @@ struct WmPromptPanelPlan {
 // cache.  width <= 1 or P0 < 2: no prefill (C = w = slices = steps = 0) -- the lane enqueues exactly what it always did.
 void wm_prompt_panel_plan(int G, int width, int P, int sot_pos, int acap_base, int knob, WmPromptPanelPlan *out);
 
+// ---------------------------------------------------------------- given panels ----
+// wm_set_given_panel: the positions of a plain decode group at which every row either decodes a given
+// token (wm_set_given_tokens) or is finished for a reason the host knows run as panel rounds of up to `width` positions per
+// decoder step, closed by given_panel.hip.  Why a group is not served, in the order the rule tests (the first that applies):
+enum WmGivenPanelReason {
+    WM_GP_SERVED = 0,
+    WM_GP_WIDTH1,      // the setting is at its default
+    WM_GP_NO_TABLE,    // no row of the group is given
+    WM_GP_CANDIDATES,  // a best-of or beam group
+    WM_GP_RAGGED,      // ragged prompts
+    WM_GP_NO_X,        // the extended decode is off
+    WM_GP_SAMP_ROWS,   // a sampling row map
+    WM_GP_TRUNC,       // temperature > 0 under the sampling rules
+    WM_GP_ALT,         // alternatives
+    WM_GP_SB_TABLES,   // sequence-bias row tables
+    WM_GP_SB,          // a sequence bias
+    WM_GP_CST,         // a constraint
+    WM_GP_REP,         // repetition rules
+    WM_GP_ACAP,        // an aligned group
+    WM_GP_F32,         // the all-f32 path, or debug hooks staged by the caller
+    WM_GP_NARROW,      // min(width, 128 / G) < 2
+    WM_GP_NO_PHASE,    // Lp <= 1: generated index 1 is neither given nor finished for some row
+    WM_GP_REASONS
+};
+// the mode of the group as the rule reads it (one bit each; wmdbg_given_panel_plan takes the same word)
+enum WmGivenPanelBits {
+    WM_GPB_GIVEN = 1 << 0, WM_GPB_CAND = 1 << 1, WM_GPB_OFF = 1 << 2, WM_GPB_X = 1 << 3, WM_GPB_SROWS = 1 << 4, WM_GPB_TRUNC = 1 << 5,
+    WM_GPB_ALT = 1 << 6, WM_GPB_SBT = 1 << 7, WM_GPB_SB = 1 << 8, WM_GPB_CST = 1 << 9, WM_GPB_REP = 1 << 10, WM_GPB_ACAP = 1 << 11,
+    WM_GPB_F32 = 1 << 12, WM_GPB_SAMPLE = 1 << 13
+};
+struct WmGivenPanelPlan {
+    int reason = WM_GP_WIDTH1;   // WM_GP_SERVED: the phase runs
+    int w = 0;                   // rows per window of a full round: min(width, 128 / G) (0: not served before the width was looked at)
+    int Lp = 0;                  // generated indices [1, Lp) are the phase (0 / 1: none)
+    int rounds = 0;              // ceil((Lp - 1) / w), the last one min(w, Lp - g0) wide
+};
+// The rule (include/whisper_mi355x.h states it in full).  G rows; lens [G]: the rows' given tokens; budgets [G] or null: the
+// rows' token budgets; P: the group's prompt positions; bits: WmGivenPanelBits (WM_GPB_SAMPLE: the call samples, temperature > 0).
+// Lp = the largest L <= max_new with P + L - 1 < n_text_ctx such that for every row r and every gi in [1, L): gi < lens[r] or
+// gi >= min(budget[r], max_new).
+void wm_given_panel_plan(int G, int width, const int32_t *lens, const int32_t *budgets, int max_new, int P, int n_text_ctx, unsigned bits,
+                         WmGivenPanelPlan *out);
+
 // ---------------------------------------------------------------- the hooks' flat forms ----
 // documented at wmdbg_tx_plan / wmdbg_group_tables / wmdbg_group_rows_out (include/whisper_mi355x_debug.h)
 constexpr int WM_TX_PLAN_IN = 12, WM_TX_PLAN_OUT = 8;

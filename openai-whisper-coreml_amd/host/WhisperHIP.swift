@@ -316,6 +316,15 @@ struct Whisper {
         try check(f(ctx, tokens, Int32(stride), rows.map { Int32($0.count) }, Int32(rows.count)))
     }
 
+    /// Generated positions per decoder step over the given tokens of a transcribe call (wm_set_given_panel; 1 ... 8, 1 = the
+    /// default).  A launch policy of the context, not consumed by calls: every output has the bits of width 1, and no call
+    /// fails because of it.  Not compiled in this repository (see the top of the file).
+    func setGivenPanel(_ width: Int32) throws {
+        typealias PanelFn = @convention(c) (OpaquePointer, Int32) -> Int32
+        let f: PanelFn = try sym("wm_set_given_panel")
+        try check(f(ctx, width))
+    }
+
     /// openai-whisper's whole-recording log-mel (wm_logmel_long; log_mel_spectrogram(audio, padding=480000)) of each
     /// recording, f32, host memory: recording r -> [nMels][(count + 480000) / 160] row-major.
     /// Not compiled in this repository (see the top of the file).

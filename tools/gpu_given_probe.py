@@ -9,6 +9,14 @@
            row for a group with a given row) and the arg-max close alone;
         3. score_given of 4 texts x 8 windows of 24 tokens through ONE best-of call against four plain window-set calls of 8
            rows each, alternating, three runs each after a warm-up of each.
+    python tools/gpu_given_probe.py panel [model]
+        Given panels (wm_set_given_panel): score_given of 4 texts x 8 windows of 24 tokens (+ eot) on
+        synthetic lively weights of `model` (default large-v2): form="rows" at widths 1 / 2 / 4 / 8 and form="best_of",
+        interleaved, three runs each after a warm-up of each, every result compared bit for bit with width 1; then one
+        profiled call (every launch bracketed by an event pair, so the bracketing bias is included) at widths 1 and 8: the
+        sum over all launches, the rounds, and the three panel launches alone.  On a tree without the setting (the parent
+        commit) the same two paths run as that tree has them: score_given's best-of call and the plain call with the rows
+        repeated.
 Prints one JSON line."""
 import json
 import os
@@ -97,6 +105,75 @@ def cost(name, rows, new):
     print(json.dumps(out))
 
 
+def panel(name):
+    from test_model_gpu import tones
+    dims = dict(b.MODEL_DIMS[name])
+    ctx = b.Context(dims)
+    ctx.init_synthetic(3, matrix_gain=W.lively_gain(dims))
+    ctx.finalize()
+    has = hasattr(ctx, "set_given_panel")
+    prompt = [50258, 50259, 50359]
+    eot, K, n_text = 50257, 4, 24
+    g = np.random.default_rng(7)
+    texts = [[[int(t) for t in g.integers(0, eot, n_text)] for _ in range(K)] for _ in range(8)]
+    mel = ctx.logmel(tones(8), out_dtype=np.float32)
+    out = dict(model=name, windows=8, texts=K, tokens=n_text + 1, given_panel=has)
+    with ctx.encode_windows(mel.reshape(-1), np.arange(8, dtype=np.int64) * dims["n_mels"] * 3000, 3000, 0, 3000) as ws:
+        def rows_call():   # the plain call with the rows repeated: what score_given(form="rows") makes
+            flat = [t + [eot] for ts in texts for t in ts]
+            return ctx.transcribe_windows(ws, [w_ for w_ in range(8) for _ in range(K)], prompt, n_text + 1, eot=eot,
+                                          budgets=[len(t) for t in flat], given=flat)
+
+        def at(width):
+            def f():
+                ctx.set_given_panel(width)
+                try:
+                    return rows_call()
+                finally:
+                    ctx.set_given_panel(1)
+            return f
+        runs = {"best_of": lambda: b.score_given(ctx, ws, None, prompt, texts, eot).result}
+        if has:
+            for width in (1, 2, 4, 8):
+                runs["rows_w%d" % width] = at(width)
+        else:
+            runs["rows_w1"] = rows_call
+        base = runs["rows_w1"]()
+        for k, f in runs.items():       # warm-up of each (graph capture), and the bits
+            r = f()
+            if k != "best_of":
+                assert np.array_equal(r.tokens, base.tokens) and np.array_equal(r.logprobs.view(np.uint32), base.logprobs.view(np.uint32)), k
+            else:
+                assert np.array_equal(r.logprobs.reshape(base.logprobs.shape).view(np.uint32), base.logprobs.view(np.uint32))
+        wall = {k: [] for k in runs}
+        for _ in range(3):
+            for k, f in runs.items():
+                t0 = time.perf_counter()
+                f()
+                wall[k].append(round(time.perf_counter() - t0, 5))
+        out["wall_s"] = wall
+        out["best_ms"] = {k: round(min(v) * 1e3, 2) for k, v in wall.items()}
+        if has:
+            ctx.profile_enable(True)
+            prof = {}
+            for width in (1, 8):
+                at(width)()
+                ctx.profile_reset()
+                at(width)()
+                pr = {q: v for q, v in ctx.profile().items() if isinstance(v, dict) and v.get("n")}
+                prof["w%d" % width] = dict(total_ms=round(sum(v["ms"] for v in pr.values()), 3), launches=int(sum(v["n"] for v in pr.values())),
+                                           panel_us_per_launch={q: round(v["ms"] / v["n"] * 1e3, 2) for q, v in pr.items() if "given_panel" in q},
+                                           rounds=int(pr.get("given_panel_stage", {}).get("n", 0)))
+            out["profile"] = prof
+            out["profile_overhead_us"] = ctx.profile_overhead_us()
+            ctx.profile_enable(False)
+    ctx.close()
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "panel":
+        panel(sys.argv[2] if len(sys.argv) > 2 else "large-v2")
+        sys.exit(0)
     cost(sys.argv[1] if len(sys.argv) > 1 else "large-v2", int(sys.argv[2]) if len(sys.argv) > 2 else 56,
          int(sys.argv[3]) if len(sys.argv) > 3 else 64)
