@@ -2,8 +2,8 @@
 // launch per position of a group with WmDecodeMode::alt, between the DE_LOGITS_X* product (which stored the f32 row, penalised
 // and biased, and left the per-tile partials) and the close -- in a group with the sampling rules BEFORE wm_sample_truncate,
 // which rewrites the per-tile keys.  One 16-wave workgroup per row:
-//   * `forced` and the normaliser from the partials through dec_close.h, exactly as beam_topk_kernel has them; the
-//     admissibility test and the descending-key list scan are row_list.h's, which that kernel calls too;
+//   * `forced` and the normaliser from the partials: stored_row.h's prologue, and its admissible set; the descending-key list
+//     scan is row_list.h's -- beam_topk_kernel calls all three too;
 //   * the entropy -sum p log p over the admissible ids shares the scan's first read of the row: thread t adds its ids
 //     ascending, then one fixed tree (a butterfly per wave, a butterfly over the 16 wave sums).  f32 adds commute, so every
 //     lane of a butterfly holds the same bits, and a row's bits depend on the row alone.
@@ -30,39 +30,16 @@ __global__ __launch_bounds__(1024) void alternatives_kernel(const float *__restr
     // workgroup-uniform: a prompt position, a position past the buffers, a row that is done (a window that has left: its rows
     // are done) -- the buffers keep the pads of the prefill
     if (gi < 0 || gi >= ap.max_new || ap.n < 1 || ap.n > WM_MAX_ALTERNATIVES || (done && done[b])) return;
-    const long rb = (long)b * n_tiles;
-    lse_row_segments(xd, rb, n_tiles, false, wave, 16, lane, seg_s);
-    {   // the best allowed text key of the row (decides the sum rule with the timestamps' log-sum-exp)
-        unsigned long long key = 0ull;
-        for (int t = threadIdx.x; t < n_tiles; t += 1024) {
-            const unsigned long long k = tilemax[rb + t];
-            key = k > key ? k : key;
-        }
-        key = key_max_xor<64>(key);
-        if (lane == 0) red_s[0][wave] = key;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f};
-        lse_row_total(seg_s, lane, lt, la);
-        unsigned long long key = lane < 16 ? red_s[0][lane] : 0ull;
-        key = __shfl(key_max_xor<16>(key), 0);
-        const RowChoice ch = row_choose(ts, b, n_tiles, lane, key, lt.m);   // (for `forced` and the normaliser)
+    // `forced` and the normaliser from the partials (the list scan below picks: ch.key is not used)
+    stored_row_prologue(ts, xd, tilemax, b, n_tiles, false, seg_s, red_s[0], [&](const RowChoice &ch, Lse lt, Lse) {
         const float norm = row_log_norm(ts, ch, lt);
         if (lane == 0) {
             norm_s = norm;
             forced_s = ch.forced ? 1 : 0;
         }
-    }
-    __syncthreads();
+    });
     const float norm = norm_s;
-    RowAdmit adm;
-    adm.V = V;
-    adm.rng = make_int4(0, V, 0, 0);
-    if (ts.rng) adm.rng = *(const int4 *)(ts.rng + b * 4);
-    adm.forced = forced_s != 0;
-    adm.mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
-    adm.brow = ban ? ban + (long)b * ban_words : nullptr;
+    const RowAdmit adm = row_admit_set(V, ts, mask, mask_words, ban, ban_words, b, pos, n_prompt, forced_s != 0);
     const long at = (long)gi * gridDim.x + b;   // [gi][row]
     int *tok = ap.tok + at * ap.n;
     float *lps = ap.lp + at * ap.n;
@@ -96,19 +73,12 @@ __global__ __launch_bounds__(1024) void alternatives_kernel(const float *__restr
 
 }  // namespace
 
-int wm_alternatives(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
-                    const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                    const WmStopDev &stop, const unsigned *ban, int ban_words, const WmAltPar *par) {
+int wm_alternatives(wm_ctx *ctx, const WmStoredRows &r, const WmAltPar *par) {
     WmProfScope ps(&ctx->prof, "alternatives", ctx->stream);
-    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && logits && tilemax && xd.par && xd.txt && par && pos_ptr, WM_ERR_INVALID,
-               "alternatives: bad group");
-    WM_REQUIRE(n_vocab >= 1 && ldo >= n_vocab, WM_ERR_INVALID, "alternatives: %d ids in rows of %ld", n_vocab, ldo);
-    WM_REQUIRE(!mask || (long)mask_words * 32 >= n_vocab, WM_ERR_INVALID, "alternatives: %d mask words do not cover %d ids", mask_words,
-               n_vocab);
-    WM_REQUIRE(!ban || (long)ban_words * 32 >= n_vocab, WM_ERR_INVALID, "alternatives: %d ban words do not cover %d ids", ban_words, n_vocab);
-    WM_REQUIRE(!ts.rng || (ts.key_ts && ts.lse && ts.ts_begin >= 0), WM_ERR_INVALID, "alternatives: incomplete timestamp-rule state");
-    alternatives_kernel<<<rows, 1024, 0, ctx->stream>>>(logits, ldo, n_vocab, (n_vocab + 15) / 16, tilemax, ts, xd, mask, mask_words,
-                                                        n_prompt, pos_ptr, stop.done, ban, ban_words, par);
+    WM_TRY(wm_stored_rows_check(r, "alternatives", false));
+    WM_REQUIRE(par, WM_ERR_INVALID, "alternatives: no parameters");
+    alternatives_kernel<<<r.rows, 1024, 0, ctx->stream>>>(r.logits, r.ldo, r.n_vocab, (r.n_vocab + 15) / 16, r.tilemax, r.ts, r.xd, r.mask,
+                                                          r.mask_words, r.n_prompt, r.pos_ptr, r.stop.done, r.ban, r.ban_words, par);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

@@ -8,7 +8,8 @@
 // A beam of width 1 must reproduce the greedy decode BIT FOR BIT (tokens, log-probs), so a row's close here is the
 // arithmetic of dec_kernels.hip's argmax_embed_body in its summation orders (16 fixed tile segments, one wave per row for
 // the merges and the embedding): both call the same functions of dec_close.h -- lse_row_segments, lse_row_total,
-// row_choose (with ts_row_merge inside), row_log_norm, row_no_speech, ts_advance, embed_row, live_list_rebuild -- and
+// row_choose (with ts_row_merge inside), row_log_norm, row_no_speech, ts_advance, embed_row, live_list_rebuild; the list
+// kernel's prologue and admissible set are stored_row.h's, shared with the other kernels on a stored row -- and
 // tests/test_beam_gpu.py (end to end) and tests/test_close_shared_gpu.py (on one step's partials) hold the closes to equal bits.
 #include "beam.h"
 #include "dec_close.h"
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
     __shared__ unsigned long long red_s[2][16];
     __shared__ float norm_s;
     __shared__ int forced_s;
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
     const int pos = *pos_ptr, gi = pos + 1 - n_prompt;
     const int K = bm.N + 1;
     const float my_sum = bm.sum[b];
@@ -41,44 +42,19 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float *__restrict
         }
         return;
     }
-    const long rb = (long)b * n_tiles;
     const bool sot = pos == xd.par->sot_pos;
-    lse_row_segments(xd, rb, n_tiles, sot, wave, 16, lane, seg_s);
-    {   // the best allowed text key of the row (decides the sum rule with the timestamps' log-sum-exp)
-        unsigned long long key = 0ull;
-        for (int t = threadIdx.x; t < n_tiles; t += 1024) {
-            const unsigned long long k = tilemax[rb + t];
-            key = k > key ? k : key;
-        }
-        key = key_max_xor<64>(key);
-        if (lane == 0) red_s[0][wave] = key;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f};
-        lse_row_total(seg_s, lane, lt, la);
-        unsigned long long key = lane < 16 ? red_s[0][lane] : 0ull;
-        key = __shfl(key_max_xor<16>(key), 0);
-        const RowChoice ch = row_choose(ts, b, n_tiles, lane, key, lt.m);   // (for `forced` and the normaliser: the list scan below picks)
+    // `forced` and the normaliser from the partials (the list scan below picks: ch.key is not used)
+    stored_row_prologue(ts, xd, tilemax, b, n_tiles, sot, seg_s, red_s[0], [&](const RowChoice &ch, Lse lt, Lse la) {
         const float norm = row_log_norm(ts, ch, lt);
         if (lane == 0) {
             norm_s = norm;
             forced_s = ch.forced ? 1 : 0;
             if (sot) xd.nospeech[b] = row_no_speech(xd, b, la);
         }
-    }
-    __syncthreads();
+    });
     const float norm = norm_s;
-    const bool forced = forced_s != 0;
     // the row's N + 1 best admissible ids in descending key order: the list scan of row_list.h
-    RowAdmit adm;
-    adm.V = V;
-    adm.rng = make_int4(0, V, 0, 0);
-    if (ts.rng) adm.rng = *(const int4 *)(ts.rng + b * 4);
-    adm.forced = forced;
-    adm.mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
-    // repetition rules: the row's no-repeat bitmap (the penalty is already in the stored logits)
-    adm.brow = ban ? ban + (long)b * ban_words : nullptr;
+    const RowAdmit adm = row_admit_set(V, ts, mask, mask_words, ban, ban_words, b, pos, n_prompt, forced_s != 0);
     const int count = row_list_scan(logits + (long)b * ldo, adm, K, norm, red_s, [](int, float) {},
                                     [&](int r, unsigned long long key, float lp) {
         bm.list_tok[b * WM_BEAM_LIST + r] = argmax_key_index(key);
@@ -262,15 +238,12 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(bf16_t *__restrict__ 
 
 }  // namespace
 
-int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
-                 const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                 const WmBeamDev &bm, const unsigned *ban, int ban_words) {
+int wm_beam_topk(wm_ctx *ctx, const WmStoredRows &r, const WmBeamDev &bm) {
     WmProfScope ps(&ctx->prof, "beam_topk", ctx->stream);
-    WM_REQUIRE(!ban || (long)ban_words * 32 >= n_vocab, WM_ERR_INVALID, "beam_topk: %d ban words do not cover %d ids", ban_words, n_vocab);
-    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && bm.N >= 1 && bm.N <= WM_MAX_BEAM && rows % bm.N == 0 && xd.par, WM_ERR_INVALID,
-               "beam_topk: bad group");
-    beam_topk_kernel<<<rows, 1024, 0, ctx->stream>>>(logits, ldo, n_vocab, (n_vocab + 15) / 16, tilemax, ts, xd, mask, mask_words,
-                                                     n_prompt, pos_ptr, bm, ban, ban_words);
+    WM_TRY(wm_stored_rows_check(r, "beam_topk", false));
+    WM_REQUIRE(bm.N >= 1 && bm.N <= WM_MAX_BEAM && r.rows % bm.N == 0, WM_ERR_INVALID, "beam_topk: bad group");
+    beam_topk_kernel<<<r.rows, 1024, 0, ctx->stream>>>(r.logits, r.ldo, r.n_vocab, (r.n_vocab + 15) / 16, r.tilemax, r.ts, r.xd, r.mask,
+                                                       r.mask_words, r.n_prompt, r.pos_ptr, bm, r.ban, r.ban_words);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

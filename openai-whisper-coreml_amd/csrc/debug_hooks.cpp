@@ -389,7 +389,8 @@ extern "C" int wmdbg_spec_accept(wm_ctx *ctx, int G, int w, int n_tiles, int pos
                                  int32_t *draft_seq_out, int32_t *pos_out) {
     WM_REQUIRE(ctx && tilemax && txt && win && seq && done && logprob_out && stats_out && round_out && acc_out && draft_seq_out && pos_out,
                WM_ERR_INVALID, "wmdbg_spec_accept: null pointer");
-    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB && n_tiles >= 1 && n_prompt >= 1 && max_new >= 1 &&
+    WM_TRY(wm_panel_shape_check(G, w, "wmdbg_spec_accept"));
+    WM_REQUIRE(n_tiles >= 1 && n_prompt >= 1 && max_new >= 1 &&
                    pos >= n_prompt && pos + w < n_ctx && pos + w <= n_prompt + max_new - 1 && n_ctx <= 4096,
                WM_ERR_INVALID, "wmdbg_spec_accept: bad geometry");
     for (int i = 0; i < G * w; ++i)
@@ -462,7 +463,8 @@ extern "C" int wmdbg_spec_kernel(wm_ctx *ctx, wmdbg_spec *io) {
                WM_ERR_INVALID, "wmdbg_spec_kernel: null pointer");
     const int G = io->G, w = io->w, cap = io->cap, n_ctx = io->n_ctx, n_prompt = io->n_prompt, max_new = io->max_new, pos = io->pos2[0];
     WM_REQUIRE(io->which >= 0 && io->which <= 2, WM_ERR_INVALID, "wmdbg_spec_kernel: which %d is not 0 .. 2", io->which);
-    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB && cap >= G && cap <= 2 * WM_DEC_MAXB &&
+    WM_TRY(wm_panel_shape_check(G, w, "wmdbg_spec_kernel"));
+    WM_REQUIRE(cap >= G && cap <= 2 * WM_DEC_MAXB &&
                    n_prompt >= 1 && n_prompt < n_ctx && n_ctx <= 4096 && max_new >= 1 && max_new <= 4096 && io->n_vocab >= 1,
                WM_ERR_INVALID, "wmdbg_spec_kernel: bad geometry");
     // the positions a kernel addresses the token buffers with: the staging stops at n_ctx by itself, the commit relies on its
@@ -1421,7 +1423,7 @@ extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V
     bm.N = N;
     const float *dlg;
     float *dtsl;
-    const unsigned long long *dkt;
+    unsigned long long *dkt;
     unsigned long long *dks;
     const unsigned *dmask;
     const int *dpos;
@@ -1443,7 +1445,7 @@ extern "C" int wmdbg_beam_topk(wm_ctx *ctx, const float *logits, int rows, int V
     WM_TRY(pool.get(&bm.list_tok, nullptr, (size_t)rows * L * 4, s));
     WM_TRY(pool.get(&bm.list_lp, nullptr, (size_t)rows * L * 4, s));
     // n_prompt 2 at position 0: not the first generated token, so the every-position bitmap applies
-    WM_TRY(wm_beam_topk(ctx, dlg, vpad, V, dkt, rows, ts, xd, dmask, mw, 2, dpos, bm));
+    WM_TRY(wm_beam_topk(ctx, WmStoredRows{dlg, vpad, V, dkt, rows, ts, xd, dmask, mw, 2, dpos, WmStopDev{}, nullptr, 0}, bm));
     WM_HIP(hipMemcpyAsync(list_n, bm.list_n, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(list_tok, bm.list_tok, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(list_lp, bm.list_lp, (size_t)rows * L * 4, hipMemcpyDeviceToHost, s));
@@ -1478,7 +1480,7 @@ extern "C" int wmdbg_alternatives(wm_ctx *ctx, const float *logits, int rows, in
     memset(&ap, 0, sizeof(ap));
     ap.n = n; ap.max_new = 1;
     const float *dlg;
-    const unsigned long long *dkt;
+    unsigned long long *dkt;
     const unsigned *dmask;
     const int *dpos;
     const WmAltPar *dpar;
@@ -1499,7 +1501,7 @@ extern "C" int wmdbg_alternatives(wm_ctx *ctx, const float *logits, int rows, in
     if (counts) WM_TRY(pool.get(&ap.cnt, counts, (size_t)rows * 4, s));
     if (entropy) WM_TRY(pool.get(&ap.ent, entropy, (size_t)rows * 4, s));
     WM_TRY(pool.get(&dpar, &ap, sizeof(ap), s));
-    WM_TRY(wm_alternatives(ctx, dlg, hp.vpad, V, dkt, rows, ts, xd, dmask, hp.mw, 2, dpos, WmStopDev{}, nullptr, 0, dpar));
+    WM_TRY(wm_alternatives(ctx, WmStoredRows{dlg, hp.vpad, V, dkt, rows, ts, xd, dmask, hp.mw, 2, dpos, WmStopDev{}, nullptr, 0}, dpar));
     WM_HIP(hipMemcpyAsync(tokens, ap.tok, (size_t)rows * n * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipMemcpyAsync(logprobs, ap.lp, (size_t)rows * n * 4, hipMemcpyDeviceToHost, s));
     if (counts) WM_HIP(hipMemcpyAsync(counts, ap.cnt, (size_t)rows * 4, hipMemcpyDeviceToHost, s));
@@ -1558,7 +1560,7 @@ extern "C" int wmdbg_sample_truncate(wm_ctx *ctx, const float *logits, int rows,
     WM_TRY(pool.get(&xd.par, &xp, sizeof(xp), s));
     WM_TRY(pool.get(&dpar, &spar, sizeof(spar), s));
     WM_TRY(pool.get(&ddbg, nullptr, (size_t)rows * 12, s, 0xff));
-    WM_TRY(wm_sample_truncate(ctx, dlg, hp.vpad, V, dkt, rows, ts, xd, dmask, hp.mw, 2, dpos, WmStopDev{}, nullptr, 0, dpar, ddbg));
+    WM_TRY(wm_sample_truncate(ctx, WmStoredRows{dlg, hp.vpad, V, dkt, rows, ts, xd, dmask, hp.mw, 2, dpos, WmStopDev{}, nullptr, 0}, dpar, ddbg));
     std::vector<int32_t> out((size_t)rows * 3);
     WM_HIP(hipMemcpyAsync(out.data(), ddbg, out.size() * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipStreamSynchronize(s));
@@ -2232,7 +2234,8 @@ static int shared_closes_run(wm_ctx *ctx, DevPool &pool, const wmdbg_step *io, c
     WM_TRY(pool.get(&bm.list_n, nullptr, (size_t)B * 4, s, 0xff));
     WM_TRY(pool.get(&bm.list_tok, nullptr, (size_t)B * L * 4, s, 0xff));
     WM_TRY(pool.get(&bm.list_lp, nullptr, (size_t)B * L * 4, s, 0xff));
-    WM_TRY(wm_beam_topk(ctx, a.out_f32, a.ldo, io->V, a.argmax, B, a.ts, bx, a.mask ? dmask : nullptr, mw, io->n_prompt, a.pos_ptr, bm));
+    WM_TRY(wm_beam_topk(ctx, WmStoredRows{a.out_f32, a.ldo, io->V, a.argmax, B, a.ts, bx, a.mask ? dmask : nullptr, mw, io->n_prompt, a.pos_ptr,
+                                           WmStopDev{}, nullptr, 0}, bm));
     // accept: the rows' ranges are the step's; the commit launch behind it advances scratch copies only
     WmSpecDev sp;
     memset(&sp, 0, sizeof(sp));
@@ -2466,11 +2469,12 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
     }
     WM_TRY(wm_dec_gemv(ctx, a));
     if (sh) WM_TRY(shared_closes_run(ctx, pool, io, *sh, a, dmask, mw));
+    const WmStoredRows stored{a.out_f32, a.ldo, V, a.argmax, B, ts, xd, a.mask ? dmask : nullptr, mw, n_prompt, dpos, sp,
+                              rep ? a.rep.ban : nullptr, mw};
     if (trunc) {
         const WmSampPar *dtr;
         WM_TRY(pool.get(&dtr, trunc, sizeof(*trunc), s));
-        WM_TRY(wm_sample_truncate(ctx, a.out_f32, a.ldo, V, a.argmax, B, ts, xd, a.mask ? dmask : nullptr, mw, n_prompt, dpos, sp,
-                                  rep ? a.rep.ban : nullptr, mw, dtr, nullptr));
+        WM_TRY(wm_sample_truncate(ctx, stored, dtr, nullptr));
     }
     std::vector<int32_t> glen, gtok;
     WmGivenPar gpar;
@@ -2488,8 +2492,7 @@ static int decode_close_run(wm_ctx *ctx, wmdbg_step *io, bool rep, float penalty
         WM_TRY(pool.get(&dgt, gtok.data(), gtok.size() * 4, s));
         gpar.stride = L; gpar.lens = dgl; gpar.tok = dgt;
         WM_TRY(pool.get(&dgp, &gpar, sizeof(gpar), s));
-        WM_TRY(wm_given_tokens(ctx, a.out_f32, a.ldo, V, a.argmax, B, ts, xd, a.mask ? dmask : nullptr, mw, n_prompt, dpos, sp,
-                               rep ? a.rep.ban : nullptr, mw, dgp));
+        WM_TRY(wm_given_tokens(ctx, stored, dgp));
     }
     // (ts, sp and xd are empty structs unless ts_mode, stop_on and x_on filled them)
     WM_TRY(wm_argmax_embed(ctx, a.argmax, n_tiles, B, dseq, dpos, n_prompt, dres, io->arg_first, n_ctx,
@@ -2713,8 +2716,8 @@ extern "C" int wmdbg_given_panel_round(wm_ctx *ctx, wmdbg_given_panel *io) {
     WM_TRY(wm_given_panel_stage(ctx, gp, sp, G, w, n_prompt, n_ctx, io->first != 0));
     a.ts = gp.ts;   // (the rows' slots as the stage left them)
     WM_TRY(wm_dec_gemv(ctx, a));
-    WM_TRY(wm_given_panel_close(ctx, a.out_f32, a.ldo, a.argmax, n_tiles, gp, xd, sp, io->n_suppress > 0 ? dmask : nullptr, mw, G, w,
-                                n_prompt, io->fallback_tok, io->last != 0));
+    WM_TRY(wm_given_panel_close(ctx, WmStoredRows{a.out_f32, a.ldo, V, a.argmax, B, gp.ts, xd, io->n_suppress > 0 ? dmask : nullptr, mw, n_prompt,
+                                                   gp.pos, sp, nullptr, 0}, gp, G, w, io->fallback_tok, io->last != 0));
     std::vector<float> lg((size_t)B * vpad);
     WM_HIP(hipMemcpyAsync(lg.data(), a.out_f32, lg.size() * 4, hipMemcpyDeviceToHost, s));
     if (io->ts_mode) {

@@ -1,9 +1,10 @@
 // dec_close.h -- device code shared by the kernels that CLOSE a decode position: the step-closing arg-max of the greedy /
-// sampling decode (dec_kernels.hip argmax_embed_body), the beam-search close (beam.hip) and the accept of a speculative
-// round (spec.hip).  First the small helpers (bf16 conversion, the packed (value, ~index) arg-max key and its butterfly
+// sampling decode (dec_kernels.hip argmax_embed_body), the beam-search close (beam.hip), the accept of a speculative
+// round (spec.hip) and the close of a given-panel round (given_panel.hip).  First the small helpers (bf16 conversion, the packed (value, ~index) arg-max key and its butterfly
 // maximum, the (max, sum exp) merge), then a row's close itself: the order-sensitive pieces whose bits make a beam of width 1
 // the greedy decode and a speculative decode the plain one, each stated here and nowhere else.  An edit to one of them is an
-// edit to all three closes (what holds them -- results, resources, time).
+// edit to all four closes (what holds them -- results, resources, time).  What the kernels BETWEEN the
+// logits launch and a close share is in stored_row.h, what the two panel rounds share in panel_rows.h (section 10a).
 #pragma once
 #include "model.h"
 
@@ -57,10 +58,10 @@ __device__ __forceinline__ Lse lse_load(const float *p) {
 }
 
 // ------------------------------------------------------------------ a row's close -------------------------------------
-// The order-sensitive pieces of a row's close, stated ONCE: argmax_embed_body, the beam kernels and spec_accept_kernel call
-// these, which is what makes a beam of width 1 the greedy decode and a verified round the plain steps bit for bit (16 fixed
-// tile segments, one wave per row for the merges, the decision and the embedding).  The callers keep their own guards (X,
-// generated position, finished row, <|startoftranscript|> position, context end).
+// The order-sensitive pieces of a row's close, stated ONCE: argmax_embed_body, the beam kernels, spec_accept_kernel and
+// given_panel_close_kernel call these, which is what makes a beam of width 1 the greedy decode and a verified round the plain
+// steps bit for bit (16 fixed tile segments, one wave per row for the merges, the decision and the embedding).  The callers
+// keep their own guards (X, generated position, finished row, <|startoftranscript|> position, context end).
 
 // One wave's share of a row's 16 FIXED tile segments of the WmXDev partials: segments pi, pi + P, ... of the row whose
 // partials start at tile index rb; seg[sg] = allowed text (m, s), unfiltered (m, s) -- the latter merged when `sot` only.
@@ -173,14 +174,17 @@ __device__ __forceinline__ float row_log_norm(const WmTsDev &ts, const RowChoice
     else if (ts.rng) al = lse_merge(lt, c.lts);
     return al.m + __logf(al.s);
 }
+// Where the winner value of id `tok` lies in WmXDev::win for the row whose partials start at tile index rb: [tile][text |
+// timestamp].  The logits epilogue's layout, read by row_logprob and written by a hand-over (stored_row.h row_hand_over).
+__device__ __forceinline__ long row_win_slot(const WmTsDev &ts, long rb, int tok) {
+    const int side = (ts.rng && tok >= ts.ts_begin) ? 1 : 0;
+    return (rb + (tok >> 4)) * 2 + side;
+}
 // log-prob of row b's winner under the filtered distribution; nothing admissible: -inf
 __device__ __forceinline__ float row_logprob(const WmTsDev &ts, const WmXDev &xd, int b, int n_tiles, const RowChoice &c, Lse lt) {
     const float norm = row_log_norm(ts, c, lt);
     float lp = -INFINITY;
-    if (c.key) {
-        const int tok = argmax_key_index(c.key), side = (ts.rng && tok >= ts.ts_begin) ? 1 : 0;
-        lp = xd.win[((long)b * n_tiles + (tok >> 4)) * 2 + side] - norm;
-    }
+    if (c.key) lp = xd.win[row_win_slot(ts, (long)b * n_tiles, argmax_key_index(c.key))] - norm;
     return lp;
 }
 // no_speech_prob of row b from the unfiltered (max, sum exp)

@@ -253,19 +253,30 @@ int wm_model_beam_begin(wm_ctx *ctx, const WmDecodeMode &mode, int rows, int win
     return WM_OK;
 }
 
+// The group's B rows as the kernels between the logits launch and the close see them (the device views of a mode that is off are
+// empty: wm_model_stop_dev, wm_model_x_dev, wm_model_rep_dev).
+static WmStoredRows wm_model_stored_rows(const WmModel *m, int B, int n_prompt, const WmDecodeMode &mode) {
+    const WmRepDev rp = wm_model_rep_dev(m, mode);
+    WmStoredRows r;
+    r.logits = m->dlogits; r.ldo = m->vpad; r.n_vocab = m->dims.n_vocab; r.tilemax = m->dargmax; r.rows = B;
+    r.ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
+    r.xd = wm_model_x_dev(m, mode);
+    r.mask = mode.mask ? m->dmask : nullptr; r.mask_words = m->vpad / 32;
+    r.n_prompt = n_prompt; r.pos_ptr = m->dpos;
+    r.stop = wm_model_stop_dev(m, mode);
+    r.ban = rp.par ? rp.ban : nullptr; r.ban_words = rp.words;
+    return r;
+}
+
 int wm_model_beam_close(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
     WmBeamDev bm;
     WM_TRY(wm_model_beam_dev(ctx, mode, &bm));
-    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
-    const WmStopDev sp = wm_model_stop_dev(m, mode);
-    const WmXDev xd = wm_model_x_dev(m, mode);
-    WM_REQUIRE(xd.par, WM_ERR_STATE, "beam close: the extended decode is off");
-    const WmRepDev rp = wm_model_rep_dev(m, mode);
-    WM_TRY(wm_beam_topk(ctx, m->dlogits, m->vpad, D.n_vocab, m->dargmax, B, ts, xd, mode.mask ? m->dmask : nullptr, m->vpad / 32,
-                        n_prompt, m->dpos, bm, rp.par ? rp.ban : nullptr, rp.words));
-    WM_TRY(wm_beam_select_step(ctx, B, m->dseq, m->dpos, n_prompt, wm_model_embed_dev(m), ts, sp, xd, mode.off ? m->doff : nullptr, bm));
+    const WmStoredRows r = wm_model_stored_rows(m, B, n_prompt, mode);
+    WM_REQUIRE(r.xd.par, WM_ERR_STATE, "beam close: the extended decode is off");
+    WM_TRY(wm_beam_topk(ctx, r, bm));
+    WM_TRY(wm_beam_select_step(ctx, B, m->dseq, m->dpos, n_prompt, wm_model_embed_dev(m), r.ts, r.stop, r.xd, mode.off ? m->doff : nullptr, bm));
     return wm_beam_reorder(ctx, m->skv, D.n_text_layer * 2, B, D.n_text_head, D.n_text_ctx, m->dpos, n_prompt, m->dseq,
                            m->dx_logprob, bm);
 }
@@ -430,11 +441,7 @@ int wm_model_set_sampling_rules(wm_ctx *ctx, int top_k, float top_p, float min_p
 int wm_model_sample_truncate(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
     WM_REQUIRE(mode.trunc && mode.x && !mode.beam && mode.panel <= 1, WM_ERR_STATE, "sampling rules: a sampling extended-decode group");
-    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
-    const WmRepDev rp = wm_model_rep_dev(m, mode);
-    return wm_sample_truncate(ctx, m->dlogits, m->vpad, m->dims.n_vocab, m->dargmax, B, ts, wm_model_x_dev(m, mode),
-                              mode.mask ? m->dmask : nullptr, m->vpad / 32, n_prompt, m->dpos, wm_model_stop_dev(m, mode),
-                              rp.par ? rp.ban : nullptr, rp.words, m->dsamp_par, nullptr);
+    return wm_sample_truncate(ctx, wm_model_stored_rows(m, B, n_prompt, mode), m->dsamp_par, nullptr);
 }
 
 int wm_model_alt_begin(wm_ctx *ctx, int rows, int max_new, int n, WmAltPar *host_par) {
@@ -457,11 +464,7 @@ int wm_model_alt_begin(wm_ctx *ctx, int rows, int max_new, int n, WmAltPar *host
 int wm_model_alternatives(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
     WM_REQUIRE(mode.alt && mode.x && !mode.beam && mode.panel <= 1, WM_ERR_STATE, "alternatives: an extended-decode group without beams");
-    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
-    const WmRepDev rp = wm_model_rep_dev(m, mode);
-    return wm_alternatives(ctx, m->dlogits, m->vpad, m->dims.n_vocab, m->dargmax, B, ts, wm_model_x_dev(m, mode),
-                           mode.mask ? m->dmask : nullptr, m->vpad / 32, n_prompt, m->dpos, wm_model_stop_dev(m, mode),
-                           rp.par ? rp.ban : nullptr, rp.words, m->dalt_par);
+    return wm_alternatives(ctx, wm_model_stored_rows(m, B, n_prompt, mode), m->dalt_par);
 }
 
 int wm_model_given_begin(wm_ctx *ctx, int rows, int stride, const int32_t *lens, const int32_t *tok, WmGivenPar *host_par) {
@@ -485,11 +488,7 @@ int wm_model_given_begin(wm_ctx *ctx, int rows, int stride, const int32_t *lens,
 int wm_model_given_tokens(wm_ctx *ctx, int B, int n_prompt, const WmDecodeMode &mode) {
     WmModel *m = ctx->model;
     WM_REQUIRE(mode.given && mode.x && !mode.beam && mode.panel <= 1, WM_ERR_STATE, "given tokens: an extended-decode group without beams");
-    const WmTsDev ts = mode.ts ? wm_model_ts_dev(m) : WmTsDev{};
-    const WmRepDev rp = wm_model_rep_dev(m, mode);
-    return wm_given_tokens(ctx, m->dlogits, m->vpad, m->dims.n_vocab, m->dargmax, B, ts, wm_model_x_dev(m, mode),
-                           mode.mask ? m->dmask : nullptr, m->vpad / 32, n_prompt, m->dpos, wm_model_stop_dev(m, mode),
-                           rp.par ? rp.ban : nullptr, rp.words, m->dgiven_par);
+    return wm_given_tokens(ctx, wm_model_stored_rows(m, B, n_prompt, mode), m->dgiven_par);
 }
 
 WmTsDev wm_model_ts_dev(const WmModel *m) {
@@ -1217,10 +1216,18 @@ void wm_model_panel_slices(int G, int width, int T, int *C, int *w) {
 
 static int panel_check(wm_ctx *ctx, int G, int c0, int C, int w) {
     WmModel *m = ctx->model;
-    WM_REQUIRE(m && w >= 1 && w <= WM_MAX_TEACHER_PANEL && C >= 1 && c0 >= 0 && c0 + C <= G && C * w <= WM_DEC_MAXB &&
-                   G <= m->cap_b && G <= m->cap_rows,
-               WM_ERR_INVALID, "panel: windows [%d, %d) of %d at width %d", c0, c0 + C, G, w);
+    WM_TRY(wm_panel_shape_check(C, w, "panel"));
+    WM_REQUIRE(m && c0 >= 0 && c0 + C <= G && G <= m->cap_b && G <= m->cap_rows, WM_ERR_INVALID,
+               "panel: windows [%d, %d) of %d at width %d", c0, c0 + C, G, w);
     return WM_OK;
+}
+
+// The mode of a panel step of width w inside a group's call: the group's own, with nothing that stops a row -- the rows of
+// frozen windows are computed and ignored, no live list; the round's commit kernel keeps the stop state.
+static WmDecodeMode panel_mode(const WmDecodeMode &mode, int w) {
+    WmDecodeMode pm = mode;
+    pm.panel = w; pm.stop = false; pm.budget = false; pm.stop_eot = -1;
+    return pm;
 }
 
 int wm_model_panel_embed(wm_ctx *ctx, int G, int c0, int C, int w) {
@@ -1255,9 +1262,7 @@ int wm_model_spec_panel_step(wm_ctx *ctx, int G, int w, const WmDecodeMode &mode
     WM_TRY(panel_check(ctx, G, 0, G, w));
     WM_REQUIRE(mode.x && !mode.off && !mode.rep && mode.n_cand <= 1 && !mode.beam && !mode.acap, WM_ERR_STATE,
                "speculative verify step: a plain extended-decode group");
-    WmDecodeMode pm = mode;   // the rows of frozen windows are computed and ignored: no live list
-    pm.panel = w; pm.stop = false; pm.budget = false; pm.stop_eot = -1;
-    return decode_step_impl(ctx, G * w, false, 0, ctx->model->dims.n_vocab - 1, nullptr, pm, n_prompt, G, 0);
+    return decode_step_impl(ctx, G * w, false, 0, ctx->model->dims.n_vocab - 1, nullptr, panel_mode(mode, w), n_prompt, G, 0);
 }
 
 int wm_model_spec_dev(wm_ctx *ctx, wm_ctx *draft, int max_new, WmSpecDev *out, int **script_area) {
@@ -1293,8 +1298,8 @@ int wm_model_prompt_prefill(wm_ctx *ctx, int G, int P0, const WmDecodeMode &mode
     WM_REQUIRE(pl.w >= 1 && pl.P0 == P0 && P0 < m->dims.n_text_ctx, WM_ERR_STATE, "prompt prefill: nothing to run for %d rows up to position %d",
                G, P0);
     WM_REQUIRE(mode.n_cand <= 1 && !mode.beam, WM_ERR_STATE, "prompt prefill: a plain decode group");
-    WmDecodeMode pm = mode;
-    pm.stop = false; pm.budget = false; pm.stop_eot = -1; pm.acap = false; pm.acap_base = pm.acap_Tq = pm.acap_J = 0; pm.acap_q = nullptr;
+    WmDecodeMode pm = panel_mode(mode, pl.w);   // (each step sets its own width below)
+    pm.acap = false; pm.acap_base = pm.acap_Tq = pm.acap_J = 0; pm.acap_q = nullptr;
     pm.rep = false; pm.sb = false; pm.sbt = false; pm.cst = false; pm.mask = false; pm.ts = false; pm.x = false;
     const int *off0 = mode.off ? m->doff : nullptr;
     const WmEmbedDev e = wm_model_embed_dev(m);
@@ -1347,21 +1352,17 @@ int wm_model_given_panel_phase(wm_ctx *ctx, int G, int w, int Lp, int n_prompt, 
     WmGivenPanelDev gp;
     WM_TRY(wm_model_given_panel_dev(ctx, max_new, &gp));
     if (!mode.ts) memset(&gp.ts, 0, sizeof(gp.ts));
-    WmDecodeMode pm = mode;
-    pm.stop = false; pm.budget = false; pm.stop_eot = -1;
-    const WmStopDev stop = wm_model_stop_dev(m, mode);
-    const WmXDev xd = wm_model_x_dev(m, mode);
+    WmStoredRows rows = wm_model_stored_rows(m, G * w, n_prompt, mode);   // (no ban rows: !mode.rep)
     const WmEmbedDev e = wm_model_embed_dev(m);
     int rounds = 0;
     for (int g0 = 1; g0 < Lp; g0 += w, ++rounds) {
         const int wr = std::min(w, Lp - g0);
         const bool last = g0 + wr >= Lp;
-        WM_TRY(wm_given_panel_stage(ctx, gp, stop, G, wr, n_prompt, T, g0 == 1));
+        WM_TRY(wm_given_panel_stage(ctx, gp, rows.stop, G, wr, n_prompt, T, g0 == 1));
         WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, wr, T, e));
-        pm.panel = wr;
-        WM_TRY(decode_step_impl(ctx, G * wr, true, 0, V - 1, nullptr, pm, n_prompt, G, 0));
-        WM_TRY(wm_given_panel_close(ctx, m->dlogits, m->vpad, m->dargmax, m->vpad / 16, gp, xd, stop, mode.mask ? m->dmask : nullptr,
-                                    m->vpad / 32, G, wr, n_prompt, mode.ts ? m->ts_eot : 0, last));
+        WM_TRY(decode_step_impl(ctx, G * wr, true, 0, V - 1, nullptr, panel_mode(mode, wr), n_prompt, G, 0));
+        rows.rows = G * wr;
+        WM_TRY(wm_given_panel_close(ctx, rows, gp, G, wr, mode.ts ? m->ts_eot : 0, last));
     }
     // *dpos == n_prompt + Lp - 1: the group's rows at that position, as wm_model_prompt_prefill ends
     WM_TRY(wm_dec_embed_panel(ctx, m->dseq, G, m->dpos, 0, G, 1, T, e));

@@ -941,14 +941,49 @@ int wm_ts_init(wm_ctx *ctx, const WmTsDev &ts, int B);
 int wm_range_softmax(wm_ctx *ctx, const float *logits, long ldo, int B, int first, int n, float *probs);
 int wm_fill_synthetic(wm_ctx *ctx, const WmTensor &t, uint32_t seed, int tensor_id, float gain);
 
+// The rows of a group as the kernels between the logits launch and the close see them (stored_row.h): the stored f32 logits
+// [rows][ldo] of n_vocab ids and the per-tile partials the DE_LOGITS_X* launch of the same position left (tilemax, xd, ts;
+// (n_vocab + 15) / 16 tiles per row), the suppress bitmap (mask, nullable: [2][mask_words], the first generated position's row
+// behind the every-position one), the device position, the stop state (done rows are skipped) and the rows' ban bitmaps (ban,
+// nullable: [rows][ban_words], WmRepDev::ban -- a banned id is not admissible).  wm_model_stored_rows builds it from a model.
+struct WmStoredRows {
+    const float *logits;
+    long ldo;
+    int n_vocab;
+    unsigned long long *tilemax;
+    int rows;
+    WmTsDev ts;
+    WmXDev xd;
+    const unsigned *mask;
+    int mask_words, n_prompt;
+    const int *pos_ptr;
+    WmStopDev stop;
+    const unsigned *ban;
+    int ban_words;
+};
+// what every stored-row entry point requires of it; needs_win: the kernel rewrites the winner values (xd.win)
+inline int wm_stored_rows_check(const WmStoredRows &r, const char *who, bool needs_win) {
+    WM_REQUIRE(r.rows >= 1 && r.rows <= WM_DEC_MAXB && r.logits && r.tilemax && r.xd.par && r.xd.txt && (!needs_win || r.xd.win) && r.pos_ptr,
+               WM_ERR_INVALID, "%s: bad group", who);
+    WM_REQUIRE(r.n_vocab >= 1 && r.ldo >= r.n_vocab, WM_ERR_INVALID, "%s: %d ids in rows of %ld", who, r.n_vocab, r.ldo);
+    WM_REQUIRE(!r.mask || (long)r.mask_words * 32 >= r.n_vocab, WM_ERR_INVALID, "%s: %d mask words do not cover %d ids", who, r.mask_words,
+               r.n_vocab);
+    WM_REQUIRE(!r.ban || (long)r.ban_words * 32 >= r.n_vocab, WM_ERR_INVALID, "%s: %d ban words do not cover %d ids", who, r.ban_words,
+               r.n_vocab);
+    WM_REQUIRE(!r.ts.rng || (r.ts.key_ts && r.ts.lse && r.ts.ts_begin >= 0), WM_ERR_INVALID, "%s: incomplete timestamp-rule state", who);
+    return WM_OK;
+}
+// the shape of a panel round: G windows x w positions are the rows of one step
+inline int wm_panel_shape_check(int G, int w, const char *what) {
+    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB, WM_ERR_INVALID, "%s: %d windows x %d rows", what, G, w);
+    return WM_OK;
+}
+
 // beam.hip (beam search)
-// Per row (grid: rows) the <= N + 1 best admissible tokens of the f32 logits [rows][ldo] with their log-probs under the
-// filtered distribution, from the partials the DE_LOGITS_X launch of the same position left (tilemax, xd, ts); rows of
-// windows that have left and dead beams get an empty list.  Also no_speech_prob when the position is par->sot_pos.
-// ban (nullable): the rows' no-repeat bitmaps [rows][ban_words] (WmRepDev::ban) -- a banned id is never listed.
-int wm_beam_topk(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
-                 const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                 const WmBeamDev &bm, const unsigned *ban = nullptr, int ban_words = 0);
+// Per row (grid: rows) the <= N + 1 best admissible tokens of the stored logits with their log-probs under the filtered
+// distribution; rows of windows that have left and dead beams get an empty list.  Also no_speech_prob when the position is
+// par->sot_pos.  (rows.stop is not read: a beam group's windows leave through bm.wdone.)
+int wm_beam_topk(wm_ctx *ctx, const WmStoredRows &rows, const WmBeamDev &bm);
 // Per window the selection (beam.h), finished records, the rows' new tokens / sums / sources / timestamp-rule state, the
 // early-stop flags and live list, the embedding of the next position and *pos_ptr += 1 (one workgroup).
 int wm_beam_select_step(wm_ctx *ctx, int rows, int *seq, int *pos_ptr, int n_prompt, const WmEmbedDev &e, const WmTsDev &ts,
@@ -959,32 +994,26 @@ int wm_beam_reorder(wm_ctx *ctx, bf16_t *skv, int L2, int rows, int H, int T, co
                     float *logprob, const WmBeamDev &bm);
 
 // sample_trunc.hip (sampling rules)
-// Per row (grid: rows) of a sampling group at a generated position: the kept set of *par over the admissible ids of the stored
-// f32 logits [rows][ldo] (beam_topk's admissibility: ranges, mask, ban; `forced` from the partials), the Gumbel-max draw over
-// it with the epilogue's Philox counters, and the row's per-tile keys (tilemax, ts.key_ts) and winner values (xd.win) rewritten
-// so that the close picks that id; the log-sum-exp partials are left alone.  Rows with stop.done set, prompt positions and
-// arg-max calls are skipped.  dbg (nullable, device): [rows][3] kept count, last kept id, drawn id.
-int wm_sample_truncate(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, unsigned long long *tilemax, int rows,
-                       const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                       const WmStopDev &stop, const unsigned *ban, int ban_words, const WmSampPar *par, int *dbg);
+// Per row (grid: rows) of a sampling group at a generated position: the kept set of *par over the row's admissible ids
+// (stored_row.h: ranges, mask, ban; `forced` from the partials), the Gumbel-max draw over it with the epilogue's Philox counters,
+// and the row's per-tile keys (tilemax, ts.key_ts) and winner values (xd.win) rewritten so that the close picks that id; the
+// log-sum-exp partials are left alone.  Rows with stop.done set, prompt positions and arg-max calls are skipped.  dbg
+// (nullable, device): [rows][3] kept count, last kept id, drawn id.
+int wm_sample_truncate(wm_ctx *ctx, const WmStoredRows &rows, const WmSampPar *par, int *dbg);
 
 // alternatives.hip (top-n alternatives and entropy)
-// Per row (grid: rows) at a generated position gi < par->max_new: the par->n best ids of the admissible set of the stored f32
-// logits [rows][ldo] in descending key order (beam_topk's admissibility and list scan: row_list.h; `forced` and the normaliser
-// from the partials) with log-probs value - norm, the count and the entropy, written at [gi][row] of par's buffers (cnt, ent
-// nullable).  Rows with stop.done set and prompt positions are skipped.  Reads the partials, writes par's buffers alone.
-int wm_alternatives(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, const unsigned long long *tilemax, int rows,
-                    const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                    const WmStopDev &stop, const unsigned *ban, int ban_words, const WmAltPar *par);
+// Per row (grid: rows) at a generated position gi < par->max_new: the par->n best ids of the row's admissible set in descending
+// key order (stored_row.h's admissibility, row_list.h's list scan; `forced` and the normaliser from the partials) with log-probs
+// value - norm, the count and the entropy, written at [gi][row] of par's buffers (cnt, ent nullable).  Rows with stop.done set
+// and prompt positions are skipped.  Reads the partials, writes par's buffers alone.
+int wm_alternatives(wm_ctx *ctx, const WmStoredRows &rows, const WmAltPar *par);
 
 // given.hip (given tokens)
 // Per row (grid: rows) at a generated position gi < par->lens[row]: the row's per-tile keys (tilemax, ts.key_ts) and the winner
-// value of one tile are rewritten so that the close takes par->tok[row][gi], with the log-prob value - norm of the stored f32
-// logits [rows][ldo] under the row's own `forced` (-inf where the id is not admissible: beam_topk's test, row_list.h).  Rows with
-// stop.done set, prompt positions and rows with gi >= lens are not touched.  The log-sum-exp partials are read, never written.
-int wm_given_tokens(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, unsigned long long *tilemax, int rows, const WmTsDev &ts,
-                    const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr, const WmStopDev &stop,
-                    const unsigned *ban, int ban_words, const WmGivenPar *par);
+// value of one tile are rewritten so that the close takes par->tok[row][gi], with the log-prob value - norm of the stored
+// logits under the row's own `forced` (-inf where the id is not admissible: stored_row.h row_admits).  Rows with stop.done set,
+// prompt positions and rows with gi >= lens are not touched.  The log-sum-exp partials are read, never written.
+int wm_given_tokens(wm_ctx *ctx, const WmStoredRows &rows, const WmGivenPar *par);
 
 // given_panel.hip (given tokens in panels, wm_set_given_panel)
 // A round of a served group of G windows at position pos = *pos_ptr (generated index g0 = pos + 1 - n_prompt) closes w positions per
@@ -1009,9 +1038,9 @@ int wm_given_panel_stage(wm_ctx *ctx, const WmGivenPanelDev &gp, const WmStopDev
 // and then the arg-max close's calls into dec_close.h on what the hand-over left.  The commit: a live window writes its tokens and
 // log-probs up to its first eot / the end of its budget and pads behind, advances its committed rule state and its done flag;
 // the position advances by w; the live list is rebuilt.  last: ts.hist / ts.rng get the [G] layout of the step path back.
-int wm_given_panel_close(wm_ctx *ctx, const float *logits, long ldo, unsigned long long *tilemax, int n_tiles, const WmGivenPanelDev &gp,
-                         const WmXDev &xd, const WmStopDev &stop, const unsigned *mask, int mask_words, int G, int w, int n_prompt,
-                         int fallback_tok, bool last);
+// rows: the G x w rows of the panel step (rows.rows == G * w, rows.ts == gp.ts; no ban rows: a served group has no per-row rule
+// state, and never the first generated position: the ordinary step takes it).
+int wm_given_panel_close(wm_ctx *ctx, const WmStoredRows &rows, const WmGivenPanelDev &gp, int G, int w, int fallback_tok, bool last);
 int wm_given_panel_commit(wm_ctx *ctx, const WmGivenPanelDev &gp, const WmXDev &xd, const WmStopDev &stop, int G, int w, int n_prompt,
                           bool last);
 

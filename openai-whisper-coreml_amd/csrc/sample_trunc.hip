@@ -1,17 +1,19 @@
 // sample_trunc.hip -- the sampling rules (wm_set_sampling_rules): top-k, top-p and min-p truncation of a
 // sampling row's distribution, one launch per generated position between the DE_LOGITS_X* product (which stored the f32 row,
 // penalised and biased, and left the per-tile partials) and the close.  One 16-wave workgroup per row:
-//   * `forced` from the partials through dec_close.h, as beam_topk_kernel has it; admissibility is that kernel's test;
+//   * `forced` and the best value from the partials, and the admissible set: stored_row.h, shared with the other stored-row kernels;
 //   * the cut: an LDS histogram (count and fixed-point mass per bin) over the top 11 bits of the order-preserving value word,
 //     a walk from the top bin, the bin of the cut refined on the next 11 and the last 10 bits, ties at the cut by lowest id;
 //   * the draw over the kept ids alone: philox.h's functions with the epilogue's counters, the epilogue's score and key;
-//   * the hand-over: the row's per-tile keys and winner values rewritten so that only the drawn id is left.  The log-sum-exp
-//     partials stay, so argmax_embed_body and dec_close.h run unchanged and the log-prob is the untruncated one.
+//   * the hand-over (stored_row.h row_hand_over): the row's per-tile keys and winner values rewritten so that only the drawn id
+//     is left.  The log-sum-exp partials stay, so argmax_embed_body and dec_close.h run unchanged and the log-prob is the
+//     untruncated one.
 // Everything order-dependent is integer: masses are u64 fixed point rint(m 2^40) (at most 131 072 terms <= 2^40), counts are
 // integers, keys are compared, so the kept set and the token depend on the row's values, ids and seed alone.
 #include "dec_close.h"
 #include "model.h"
 #include "philox.h"
+#include "stored_row.h"
 
 namespace {
 
@@ -21,46 +23,18 @@ constexpr int ST_COUNT = 0, ST_MASS = 1;
 // what a thread needs to walk row b: the stored values, the admissible set A and the mass of an id
 struct StRow {
     const float *lg;
-    int V;
-    int4 rng;
-    bool forced;
-    const unsigned *mrow, *brow;
+    RowAdmit adm;
     float vmax, inv_T;
-    // beam_topk_kernel's test: ranges, suppress words, ban words
-    __device__ __forceinline__ bool in_range(int n) const {
-        const bool in_text = !forced && n >= rng.x && n < rng.y, in_ts = n >= rng.z && n < rng.w;
-        return in_text || in_ts;
-    }
-    __device__ __forceinline__ bool admissible(int n) const {
-        if (!in_range(n) || (mrow && ((mrow[n >> 5] >> (n & 31)) & 1u))) return false;
-        return !(brow && ((brow[n >> 5] >> (n & 31)) & 1u));
-    }
     // m(n) = exp((v - vmax) inv_T), and its fixed-point form
     __device__ __forceinline__ float mass(float v) const { return v == vmax ? 1.f : __expf((v - vmax) * inv_T); }
     __device__ __forceinline__ unsigned long long mass_fix(float v) const { return __float2ull_rn(mass(v) * 1099511627776.f); }
 };
 // f(n, v, u) for every id of A whose value is above -inf (-inf and NaN are never kept); u = the value word of argmax_key
-// A pass is latency-bound (one workgroup, ~51 ids per thread from L2): the loads of ST_UNROLL ids -- value, suppress word, ban
-// word, none depending on another -- are requested together, then tested.
-constexpr int ST_UNROLL = 8;
 template <class F>
 __device__ __forceinline__ void st_for_each(const StRow &r, F f) {
-    for (int n0 = threadIdx.x; n0 < r.V; n0 += ST_THREADS * ST_UNROLL) {
-        float v[ST_UNROLL];
-        unsigned w[ST_UNROLL];
-#pragma unroll
-        for (int j = 0; j < ST_UNROLL; ++j) {
-            const int n = n0 + j * ST_THREADS, nc = n < r.V ? n : r.V - 1;   // (clamped: the test below drops it)
-            v[j] = r.lg[nc];
-            w[j] = (r.mrow ? r.mrow[nc >> 5] : 0u) | (r.brow ? r.brow[nc >> 5] : 0u);
-        }
-#pragma unroll
-        for (int j = 0; j < ST_UNROLL; ++j) {
-            const int n = n0 + j * ST_THREADS;
-            if (n >= r.V || !r.in_range(n) || ((w[j] >> (n & 31)) & 1u) || !(v[j] > -INFINITY)) continue;
-            f(n, v[j], (unsigned)(argmax_key(v[j], n) >> 32));
-        }
-    }
+    row_for_each_admitted(r.lg, r.adm, [&](int n, float v) {
+        if (v > -INFINITY) f(n, v, (unsigned)(argmax_key(v, n) >> 32));
+    });
 }
 
 struct StFound {
@@ -150,7 +124,7 @@ __device__ __forceinline__ StFound st_hist_find(StShared &s, bool desc, int mode
 // one ballot over the <= 64 ids of the bin
 __device__ __forceinline__ int st_tie_select(StShared &s, const StRow &r, unsigned u_cut, unsigned rth) {
     int sh = 0;
-    while (((r.V - 1) >> sh) >= ST_BINS) ++sh;   // (the launch checks V <= 64 ST_BINS)
+    while (((r.adm.V - 1) >> sh) >= ST_BINS) ++sh;   // (the launch checks V <= 64 ST_BINS)
     st_hist_clear(s);
     st_for_each(r, [&](int n, float, unsigned u) { if (u == u_cut) atomicAdd(&s.cnt[n >> sh], 1u); });
     __syncthreads();
@@ -160,7 +134,7 @@ __device__ __forceinline__ int st_tie_select(StShared &s, const StRow &r, unsign
     if (f.bin >= 0 && threadIdx.x < 64) {
         const int n = (f.bin << sh) + (int)threadIdx.x;
         bool is = false;
-        if ((int)threadIdx.x < (1 << sh) && n < r.V && r.admissible(n)) {
+        if ((int)threadIdx.x < (1 << sh) && n < r.adm.V && row_admits(r.adm, n)) {
             const float v = r.lg[n];
             is = v > -INFINITY && (unsigned)(argmax_key(v, n) >> 32) == u_cut;
         }
@@ -226,7 +200,7 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
     __shared__ float seg_s[16][4];
     __shared__ int forced_s;
     __shared__ float vmax_s;
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
     const int pos = *pos_ptr;
     const WmXPar xp = *xd.par;
     const WmSampPar sp = *par;
@@ -243,42 +217,18 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
         if (__float_as_uint(inv_T) == 0u) return;
     }
     const long rb = (long)b * n_tiles;
-    // `forced` (the sum rule) and the best value of A, from the partials: beam_topk_kernel's steps
-    lse_row_segments(xd, rb, n_tiles, false, wave, 16, lane, seg_s);
-    {
-        unsigned long long key = 0ull;
-        if (ts.rng) {   // (the best allowed text key: row_choose asks whether there is one)
-            for (int t = threadIdx.x; t < n_tiles; t += ST_THREADS) {
-                const unsigned long long k = tilemax[rb + t];
-                key = k > key ? k : key;
-            }
-            key = key_max_xor<64>(key);
-        }
-        if (lane == 0) s.red[wave] = key;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f};
-        lse_row_total(seg_s, lane, lt, la);
-        unsigned long long key = lane < 16 ? s.red[lane] : 0ull;
-        key = __shfl(key_max_xor<16>(key), 0);
-        const RowChoice ch = row_choose(ts, b, n_tiles, lane, key, lt.m);
+    // `forced` (the sum rule) and the best value of A, from the partials
+    stored_row_prologue(ts, xd, tilemax, b, n_tiles, false, seg_s, s.red, [&](const RowChoice &ch, Lse lt, Lse) {
         if (lane == 0) {
             forced_s = ch.forced ? 1 : 0;
-            vmax_s = ch.forced ? ch.lts.m : fmaxf(lt.m, ch.lts.m);   // (lts: (-1e30, 0) without timestamp rules)
+            vmax_s = row_best_value(ch, lt);
         }
-    }
-    __syncthreads();
+    });
     const bool forced = forced_s != 0;
     if (!(vmax_s > -1e30f)) return;   // nothing to keep: the close takes its existing path (uniform)
     StRow r;
     r.lg = logits + (long)b * ldo;
-    r.V = V;
-    r.rng = make_int4(0, V, 0, 0);
-    if (ts.rng) r.rng = *(const int4 *)(ts.rng + b * 4);
-    r.forced = forced;
-    r.mrow = mask ? mask + (pos == n_prompt - 1 ? mask_words : 0) : nullptr;
-    r.brow = ban ? ban + (long)b * ban_words : nullptr;
+    r.adm = row_admit_set(V, ts, mask, mask_words, ban, ban_words, b, pos, n_prompt, forced);
     r.vmax = vmax_s;
     r.inv_T = inv_T;
     // the cut
@@ -310,7 +260,7 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
     int kept = 0;
     const unsigned cw2 = xp.ids_on ? xd.ids[b] : (unsigned)(xp.chunk0 + b);
     const unsigned cw3 = xp.n_cand > 1 ? xd.ids[WM_XIDS_CAND + b] : 0u;
-    constexpr int QU = 2;   // quads in flight per thread: their loads are requested together (see st_for_each)
+    constexpr int QU = 2;   // quads in flight per thread: their loads are requested together (see row_for_each_admitted)
     for (int q0 = threadIdx.x; q0 * 4 < V; q0 += ST_THREADS * QU) {
         float vq[QU][4];
         unsigned wq[QU];
@@ -323,7 +273,7 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
                 vq[u][j] = r.lg[n < V ? n : V - 1];   // (clamped: dropped below)
             }
             const int wn = q * 4 < V ? q * 4 : V - 1;   // (the four ids of a quad share a bitmap word)
-            wq[u] = (r.mrow ? r.mrow[wn >> 5] : 0u) | (r.brow ? r.brow[wn >> 5] : 0u);
+            wq[u] = (r.adm.mrow ? r.adm.mrow[wn >> 5] : 0u) | (r.adm.brow ? r.adm.brow[wn >> 5] : 0u);
         }
 #pragma unroll
         for (int u = 0; u < QU; ++u) {
@@ -334,7 +284,7 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
             for (int j = 0; j < 4; ++j) {
                 const int n = q * 4 + j;
                 const float v = vq[u][j];
-                if (n >= V || !r.in_range(n) || ((wq[u] >> (n & 31)) & 1u) || !(v > -INFINITY)) continue;
+                if (n >= V || !row_in_ranges(r.adm, n) || ((wq[u] >> (n & 31)) & 1u) || !(v > -INFINITY)) continue;
                 const unsigned long long k = argmax_key(v, n);
                 if (k < cut || (sp.min_p > 0.f && !(r.mass(v) >= sp.min_p))) continue;
                 if (!have) {
@@ -357,36 +307,23 @@ __global__ __launch_bounds__(ST_THREADS) void sample_trunc_kernel(const float *_
     const unsigned long long win = st_block_max(s, best);
     const unsigned long long last = ~st_block_max(s, ~low);
     if (win == 0ull) return;   // (cannot happen: the best id of A is always kept)
-    // the hand-over: only the drawn id is left in the row's keys.  A timestamp drawn where the sum rule did not force one leaves
-    // the smallest key in the text keys, so that row_choose still sees admissible text below it (its decision reads lt.m).
-    const int tok = argmax_key_index(win), wt = tok >> 4;
-    const int side = (ts.rng && tok >= ts.ts_begin) ? 1 : 0;
-    const int t_first = ts.ts_begin >> 4;
-    for (int t = threadIdx.x; t < n_tiles; t += ST_THREADS) {
-        tilemax[rb + t] = (side == 0 && t == wt) ? win : ((side == 1 && !forced && t == 0) ? 1ull : 0ull);
-        if (ts.rng && t >= t_first) ts.key_ts[rb + t] = (side == 1 && t == wt) ? win : 0ull;
-    }
-    if (best == win) xd.win[(rb + wt) * 2 + side] = best_v;   // (keys carry the id: one thread)
+    // the hand-over: only the drawn id is left in the row's keys
+    const int tok = argmax_key_index(win);
+    row_hand_over(ts, tilemax, rb, n_tiles, forced, win, threadIdx.x, ST_THREADS);
+    if (best == win) xd.win[row_win_slot(ts, rb, tok)] = best_v;   // (keys carry the id: one thread)
     if (dbg && threadIdx.x == 0) { dbg[b * 3] = s.kept; dbg[b * 3 + 1] = argmax_key_index(last); dbg[b * 3 + 2] = tok; }
 }
 
 }  // namespace
 
-int wm_sample_truncate(wm_ctx *ctx, const float *logits, long ldo, int n_vocab, unsigned long long *tilemax, int rows,
-                       const WmTsDev &ts, const WmXDev &xd, const unsigned *mask, int mask_words, int n_prompt, const int *pos_ptr,
-                       const WmStopDev &stop, const unsigned *ban, int ban_words, const WmSampPar *par, int *dbg) {
+int wm_sample_truncate(wm_ctx *ctx, const WmStoredRows &r, const WmSampPar *par, int *dbg) {
     WmProfScope ps(&ctx->prof, "sample_trunc", ctx->stream);
-    WM_REQUIRE(rows >= 1 && rows <= WM_DEC_MAXB && logits && tilemax && xd.par && xd.txt && xd.win && par && pos_ptr, WM_ERR_INVALID,
-               "sample_truncate: bad group");
-    WM_REQUIRE(n_vocab >= 1 && n_vocab <= 64 * ST_BINS && ldo >= n_vocab, WM_ERR_INVALID, "sample_truncate: %d ids outside 1 .. %d",
-               n_vocab, 64 * ST_BINS);
-    WM_REQUIRE(!mask || (long)mask_words * 32 >= n_vocab, WM_ERR_INVALID, "sample_truncate: %d mask words do not cover %d ids", mask_words,
-               n_vocab);
-    WM_REQUIRE(!ban || (long)ban_words * 32 >= n_vocab, WM_ERR_INVALID, "sample_truncate: %d ban words do not cover %d ids", ban_words,
-               n_vocab);
-    WM_REQUIRE(!ts.rng || (ts.key_ts && ts.lse && ts.ts_begin >= 0), WM_ERR_INVALID, "sample_truncate: incomplete timestamp-rule state");
-    sample_trunc_kernel<<<rows, ST_THREADS, 0, ctx->stream>>>(logits, ldo, n_vocab, (n_vocab + 15) / 16, tilemax, ts, xd, mask, mask_words,
-                                                             n_prompt, pos_ptr, stop.done, ban, ban_words, par, dbg);
+    WM_TRY(wm_stored_rows_check(r, "sample_truncate", true));
+    WM_REQUIRE(par, WM_ERR_INVALID, "sample_truncate: no rules");
+    WM_REQUIRE(r.n_vocab <= 64 * ST_BINS, WM_ERR_INVALID, "sample_truncate: %d ids outside 1 .. %d", r.n_vocab, 64 * ST_BINS);
+    sample_trunc_kernel<<<r.rows, ST_THREADS, 0, ctx->stream>>>(r.logits, r.ldo, r.n_vocab, (r.n_vocab + 15) / 16, r.tilemax, r.ts, r.xd,
+                                                               r.mask, r.mask_words, r.n_prompt, r.pos_ptr, r.stop.done, r.ban, r.ban_words,
+                                                               par, dbg);
     WM_HIP(hipGetLastError());
     return WM_OK;
 }

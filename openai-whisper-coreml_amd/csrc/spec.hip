@@ -1,10 +1,10 @@
 // spec.hip -- the kernels of a speculative decode round (wm_transcribe_mel_speculative) around the
 // target's verify step: the draft's adoption of the first token, the staging of a round's proposals (with the replay of the
 // timestamp rules along them), the close of the verify step's rows (accept) and the group's lockstep cut (commit).
-// A row's close is the arg-max close of dec_kernels.hip argmax_embed_body<true>: the same calls into dec_close.h (segments,
-// totals, row_choose, row_logprob), by ONE wave per row, so winner, tie order, forced timestamps and log-prob are the plain
-// step's; the kernel itself holds only its tile-key maximum and the window's acceptance count.
-#include "dec_close.h"
+// A row's close is the one-wave close of panel_rows.h (the arg-max close of dec_kernels.hip argmax_embed_body<true>: the same
+// calls into dec_close.h), so winner, tie order, forced timestamps and log-prob are the plain step's; the accept kernel itself
+// holds only the window's acceptance count.  The committed-state load and store and the stage loop are panel_rows.h's too.
+#include "panel_rows.h"
 #include "spec_round.h"
 
 namespace {
@@ -17,17 +17,16 @@ __global__ void spec_adopt_kernel(WmSpecDev sp, int G, int n_prompt) {
     const int tok = sp.tseq[n_prompt * G + c];
     sp.dseq[n_prompt * G + c] = tok;
     sp.stats[c * 4 + 0] = 0; sp.stats[c * 4 + 1] = 0; sp.stats[c * 4 + 2] = 0; sp.stats[c * 4 + 3] = 0;
+    int hs[4];
     if (sp.tts.rng) {   // the target's committed state: what its first close left
-        *(int4 *)(sp.chist + c * 4) = *(const int4 *)(sp.tts.hist + c * 4);
-        *(int4 *)(sp.crng + c * 4) = *(const int4 *)(sp.tts.rng + c * 4);
+        const int4 r = panel_state_load(sp.tts.hist, sp.tts.rng, c, hs);
+        panel_state_store(sp.chist, sp.crng, c, hs, r);
     }
     if (sp.dts.rng) {   // (ts_init_kernel's history, advanced by the adopted token)
-        int hs[4] = {0, 0, 1, -1};
+        hs[0] = 0; hs[1] = 0; hs[2] = 1; hs[3] = -1;
         const int4 r = ts_advance(sp.dts, hs, tok);
-        *(int4 *)(sp.dts.rng + c * 4) = r;
-        *(int4 *)(sp.dts.hist + c * 4) = make_int4(hs[0], hs[1], hs[2], hs[3]);
-        *(int4 *)(sp.dcrng + c * 4) = r;
-        *(int4 *)(sp.dchist + c * 4) = make_int4(hs[0], hs[1], hs[2], hs[3]);
+        panel_state_store(sp.dts.hist, sp.dts.rng, c, hs, r);
+        panel_state_store(sp.dchist, sp.dcrng, c, hs, r);
     }
 }
 
@@ -39,20 +38,13 @@ __global__ void spec_stage_kernel(WmSpecDev sp, int G, int w, int n_prompt, int 
     if (c >= G) return;
     const int pos = *sp.tpos;
     int hs[4] = {0, 0, 0, 0};
-    if (sp.tts.rng) {
-        const int4 h = *(const int4 *)(sp.chist + c * 4);
-        hs[0] = h.x; hs[1] = h.y; hs[2] = h.z; hs[3] = h.w;
-        *(int4 *)(sp.tts.rng + (c * w) * 4) = *(const int4 *)(sp.crng + c * 4);
-    }
-    for (int s = 1; s < w; ++s) {
-        const int p = pos + s;
-        if (p >= n_ctx) break;
+    int4 rng = make_int4(0, 0, 0, 0);
+    if (sp.tts.rng) rng = panel_state_load(sp.chist, sp.crng, c, hs);
+    panel_stage_window(sp.tts, sp.tseq, G, c, w, pos, n_ctx, hs, rng, [&](int, int p) {
         const int gi = p - n_prompt;   // the proposal is generated token gi
-        int tok = (sp.script && gi >= 0 && gi < sp.max_new) ? sp.script[(long)c * sp.max_new + gi] : sp.dseq[p * G + c];
-        tok = tok < 0 ? 0 : (tok >= sp.n_vocab ? sp.n_vocab - 1 : tok);
-        sp.tseq[p * G + c] = tok;
-        if (sp.tts.rng) *(int4 *)(sp.tts.rng + (c * w + s) * 4) = ts_advance(sp.tts, hs, tok);
-    }
+        const int tok = (sp.script && gi >= 0 && gi < sp.max_new) ? sp.script[(long)c * sp.max_new + gi] : sp.dseq[p * G + c];
+        return tok < 0 ? 0 : (tok >= sp.n_vocab ? sp.n_vocab - 1 : tok);
+    });
 }
 
 // ACCEPT.  One workgroup per window, wave s closes row (c, s) = row c * w + s of the verify step.  Then the window's leading rows
@@ -65,25 +57,14 @@ __global__ __launch_bounds__(512) void spec_accept_kernel(const unsigned long lo
     const int lane = threadIdx.x & 63, s = threadIdx.x >> 6, c = blockIdx.x;
     const WmTsDev &ts = sp.tts;
     unsigned long long key = 0ull;
+    if (s < w) key = panel_close_begin(tilemax, xd, c * w + s, n_tiles, lane, seg_s[s]);   // wave-uniform
+    __syncthreads();   // (the barrier between the halves of the close: panel_rows.h)
     if (s < w) {   // wave-uniform
-        const int b = c * w + s;
-        const unsigned long long *row = tilemax + (long)b * n_tiles;
-        for (int t = lane; t < n_tiles; t += 64) {
-            const unsigned long long k = row[t];
-            key = k > key ? k : key;
-        }
-        key = key_max_xor<64>(key);
-        lse_row_segments(xd, (long)b * n_tiles, n_tiles, false, 0, 1, lane, seg_s[s]);
-    }
-    __syncthreads();   // lane 0 wrote the row's 16 segments, lanes 0 .. 15 read them: the barrier argmax_embed_body has here
-    if (s < w) {   // wave-uniform
-        const int b = c * w + s;
-        Lse lt{-1e30f, 0.f}, la{-1e30f, 0.f};
-        lse_row_total(seg_s[s], lane, lt, la);
-        const RowChoice ch = row_choose(ts, b, n_tiles, lane, key, lt.m);
+        Lse lt;
+        const PanelRowClose r = panel_close_end(ts, xd, c * w + s, n_tiles, lane, key, seg_s[s], lt, fallback_tok);
         if (lane == 0) {
-            tok_s[s] = ch.key ? argmax_key_index(ch.key) : fallback_tok;
-            lp_s[s] = row_logprob(ts, xd, b, n_tiles, ch, lt);
+            tok_s[s] = r.tok;
+            lp_s[s] = r.lp;
         }
     }
     __syncthreads();
@@ -144,11 +125,7 @@ __global__ __launch_bounds__(WM_DEC_MAXB) void spec_commit_kernel(WmSpecDev sp, 
         if (live) wm_spec_window_cut(n, a, eot_at, left, &m, &stops, &acc, &kept);
         int hs[4] = {0, 0, 0, 0};
         int4 rng = make_int4(0, 0, 0, 0);
-        if (sp.tts.rng) {
-            const int4 h = *(const int4 *)(sp.chist + c * 4);
-            hs[0] = h.x; hs[1] = h.y; hs[2] = h.z; hs[3] = h.w;
-            rng = *(const int4 *)(sp.crng + c * 4);
-        }
+        if (sp.tts.rng) rng = panel_state_load(sp.chist, sp.crng, c, hs);
         for (int i = 0; i < n; ++i) {
             const int tok = i < m ? sp.wtok[c * w + i] : stop.pad_tok;
             const float lp = i < m ? sp.wlp[c * w + i] : 0.f;
@@ -156,10 +133,7 @@ __global__ __launch_bounds__(WM_DEC_MAXB) void spec_commit_kernel(WmSpecDev sp, 
             if (g0 + i >= 0 && g0 + i < sp.max_new) xd.logprob[(long)(g0 + i) * G + c] = lp;
             if (sp.tts.rng && i < m) rng = ts_advance(sp.tts, hs, tok);
         }
-        if (sp.tts.rng && m > 0) {
-            *(int4 *)(sp.chist + c * 4) = make_int4(hs[0], hs[1], hs[2], hs[3]);
-            *(int4 *)(sp.crng + c * 4) = rng;
-        }
+        if (sp.tts.rng && m > 0) panel_state_store(sp.chist, sp.crng, c, hs, rng);
         if (live) {
             if (stops) stop.done[c] = 1;
             now_live = stops ? 0 : 1;
@@ -171,14 +145,11 @@ __global__ __launch_bounds__(WM_DEC_MAXB) void spec_commit_kernel(WmSpecDev sp, 
         // the draft: the token it continues from, and its rules' state behind the n tokens the group advanced by
         if (n > 0) sp.dseq[(pos + n) * G + c] = sp.tseq[(pos + n) * G + c];
         if (sp.dts.rng) {
-            const int4 h = *(const int4 *)(sp.dchist + c * 4);
-            int dh[4] = {h.x, h.y, h.z, h.w};
-            int4 dr = *(const int4 *)(sp.dcrng + c * 4);
+            int dh[4];
+            int4 dr = panel_state_load(sp.dchist, sp.dcrng, c, dh);
             for (int i = 0; i < n; ++i) dr = ts_advance(sp.dts, dh, sp.tseq[(pos + 1 + i) * G + c]);
-            *(int4 *)(sp.dts.hist + c * 4) = make_int4(dh[0], dh[1], dh[2], dh[3]);
-            *(int4 *)(sp.dts.rng + c * 4) = dr;
-            *(int4 *)(sp.dchist + c * 4) = make_int4(dh[0], dh[1], dh[2], dh[3]);
-            *(int4 *)(sp.dcrng + c * 4) = dr;
+            panel_state_store(sp.dts.hist, sp.dts.rng, c, dh, dr);
+            panel_state_store(sp.dchist, sp.dcrng, c, dh, dr);
         }
     }
     red_s[c] = now_live;
@@ -207,8 +178,7 @@ int wm_spec_adopt(wm_ctx *draft, const WmSpecDev &sp, int G, int n_prompt) {
 }
 
 int wm_spec_stage(wm_ctx *ctx, const WmSpecDev &sp, int G, int w, int n_prompt, int n_ctx) {
-    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB, WM_ERR_INVALID, "spec_stage: %d windows x %d rows",
-               G, w);
+    WM_TRY(wm_panel_shape_check(G, w, "spec_stage"));
     WmProfScope ps(&ctx->prof, "spec_stage", ctx->stream);
     spec_stage_kernel<<<1, WM_DEC_MAXB, 0, ctx->stream>>>(sp, G, w, n_prompt, n_ctx);
     WM_HIP(hipGetLastError());
@@ -217,8 +187,7 @@ int wm_spec_stage(wm_ctx *ctx, const WmSpecDev &sp, int G, int w, int n_prompt, 
 
 int wm_spec_accept(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, const WmSpecDev &sp, const WmXDev &xd,
                    const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx, int fallback_tok) {
-    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB, WM_ERR_INVALID, "spec_accept: %d windows x %d rows",
-               G, w);
+    WM_TRY(wm_panel_shape_check(G, w, "spec_accept"));
     WM_REQUIRE(xd.par && stop.done, WM_ERR_STATE, "spec_accept: needs the extended decode and the stop state");
     WmProfScope ps(&ctx->prof, "spec_accept", ctx->stream);
     spec_accept_kernel<<<G, 512, 0, ctx->stream>>>(tilemax, n_tiles, G, w, sp, xd, fallback_tok);
@@ -228,8 +197,7 @@ int wm_spec_accept(wm_ctx *ctx, const unsigned long long *tilemax, int n_tiles, 
 
 // the second launch of wm_spec_accept (which the product always makes through it; alone: the debug library's kernel tests)
 int wm_spec_commit(wm_ctx *ctx, const WmSpecDev &sp, const WmXDev &xd, const WmStopDev &stop, int G, int w, int n_prompt, int n_ctx) {
-    WM_REQUIRE(G >= 1 && w >= 1 && w <= WM_MAX_TEACHER_PANEL && G * w <= WM_DEC_MAXB, WM_ERR_INVALID, "spec_commit: %d windows x %d rows",
-               G, w);
+    WM_TRY(wm_panel_shape_check(G, w, "spec_commit"));
     WM_REQUIRE(xd.logprob && stop.done, WM_ERR_STATE, "spec_commit: needs the extended decode and the stop state");
     spec_commit_kernel<<<1, WM_DEC_MAXB, 0, ctx->stream>>>(sp, xd, stop, G, w, n_prompt, n_ctx);
     WM_HIP(hipGetLastError());
