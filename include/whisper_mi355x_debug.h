@@ -72,17 +72,32 @@ WM_API int wmdbg_encode_stem(wm_ctx *ctx, const float *mel, const int64_t *wins,
  * WMDBG_SENTINEL_BF16 before the launches; afterwards vt is zeroed, so that its pad columns 1500 .. 1535 are zero again as a
  * later encode expects. */
 WM_API int wmdbg_encode_layer_qkv(wm_ctx *ctx, int layer, const float *x, int B, float *xn_out, float *qk_out, float *vt_out);
+/* The whole of encoder layer `layer` on x f32 [B * 1500][d]: the LayerNorm + QKV launch as above, then the layer's other five
+ * launches by the function the encoder calls (attention, out-projection + residual, LayerNorm, fc1 + GELU, fc2 + residual).
+ * Out, each as its launch left it (bf16 widened / f32): att [B * 1500][d], x_mid [B * 1500][d] (the residual stream after the
+ * out-projection, copied aside before the LayerNorm), xn2 [B * 1500][d], hid [B * 1500][4 d], x_out [B * 1500][d].  xn, qk
+ * with the 64 rows behind it, att and hid hold WMDBG_SENTINEL_BF16 and the copy of x_mid WMDBG_SENTINEL_F32 before the
+ * launches; vt is zeroed before them (its pad columns are the attention kernel's contract), the 64 rows behind qk after them. */
+WM_API int wmdbg_encode_layer_tail(wm_ctx *ctx, int layer, const float *x, int B, float *att_out, float *x_mid_out,
+                                   float *xn2_out, float *hid_out, float *x_out);
+/* ln_post by the function the encoder calls, on x f32 [B * 1500][d]: xn [B * 1500][d] (bf16 widened), xa [B * 1500][d] f32; both
+ * hold their sentinels before the launch. */
+WM_API int wmdbg_encode_post(wm_ctx *ctx, const float *x, int B, float *xn_out, float *xa_out);
 /* wm_model_set_xa + wm_model_cross_kv on xa f32 [B][1500][d]: xkv f32 [L][2][B][H][1500][64] (L = n_text_layer; bf16 widened).
  * The model's whole cross-K/V allocation holds WMDBG_SENTINEL_BF16 before the launches; an element behind the B chunks' cache
  * that no longer does is WM_ERR_STATE. */
 WM_API int wmdbg_cross_kv(wm_ctx *ctx, const float *xa, int B, float *xkv_out);
 
-/* LayerNorm over the last axis (eps 1e-5): f32 result and the bf16 result widened to f32. */
+/* LayerNorm over the last axis (eps 1e-5): f32 result and the bf16 result widened to f32.  Either output may be null (not
+ * both): the kernel is then launched with that output null, as the encoder launches it. */
 WM_API int wmdbg_layernorm(wm_ctx *ctx, const float *x, const float *g, const float *b, int rows, int d,
                     float *out_f32, float *out_bf16_as_f32);
 /* Non-causal MHA, head_dim 64: q,k,v,out f32 [B][S][H*64]. */
 WM_API int wmdbg_enc_attention(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int S,
                         float *out);
+/* The same; flags & 1: the 64 rows behind the last chunk's keys, which the last K tile reads and the kernel masks, hold NaN. */
+WM_API int wmdbg_enc_attention_ex(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int S, int flags,
+                           float *out);
 /* Decode-step skinny GEMM (the DE_Q epilogue): out[B][N] = (ln_g ? LayerNorm(x) : x) . W[N][K]^T + bias; 1 <= B <= WM_DEC_MAXB
  * (128). */
 WM_API int wmdbg_dec_gemv(wm_ctx *ctx, const float *x, const float *ln_g, const float *ln_b, const float *W,

@@ -588,17 +588,20 @@ extern "C" int wmdbg_layernorm(wm_ctx *ctx, const float *x, const float *g, cons
     WM_TRY(wm_ctx_make_current(ctx));
     DevPool pool;
     hipStream_t s = ctx->stream;
+    WM_REQUIRE(x && g && b && rows >= 1 && d >= 1 && (out_f32 || out_bf16_as_f32), WM_ERR_INVALID, "wmdbg_layernorm: bad args");
     const float *dx, *dg, *db;
-    float *of;
-    bf16_t *ob;
+    float *of = nullptr;   // a null host output reaches wm_layernorm as a null output
+    bf16_t *ob = nullptr;
     WM_TRY(pool.get(&dx, x, (size_t)rows * d * 4, s));
     WM_TRY(pool.get(&dg, g, (size_t)d * 4, s));
     WM_TRY(pool.get(&db, b, (size_t)d * 4, s));
-    WM_TRY(pool.get(&of, nullptr, (size_t)rows * d * 4, s));
-    WM_TRY(pool.get(&ob, nullptr, (size_t)rows * d * 2, s));
+    if (out_f32) WM_TRY(pool.get(&of, nullptr, (size_t)rows * d * 4, s));
+    if (out_bf16_as_f32) WM_TRY(pool.get(&ob, nullptr, (size_t)rows * d * 2, s));
     WM_TRY(wm_layernorm(ctx, dx, dg, db, rows, d, ob, of));
-    WM_HIP(hipMemcpyAsync(out_f32, of, (size_t)rows * d * 4, hipMemcpyDeviceToHost, s));
-    return down_bf16(ob, (size_t)rows * d, out_bf16_as_f32, s);
+    if (out_f32) WM_HIP(hipMemcpyAsync(out_f32, of, (size_t)rows * d * 4, hipMemcpyDeviceToHost, s));
+    if (out_bf16_as_f32) return down_bf16(ob, (size_t)rows * d, out_bf16_as_f32, s);
+    WM_HIP(hipStreamSynchronize(s));
+    return WM_OK;
 }
 
 // The sampling noise of wm_transcribe as the device computes it (the DE_LOGITS_X epilogue's philox.h functions).
@@ -619,10 +622,19 @@ extern "C" int wmdbg_sample_noise(wm_ctx *ctx, uint64_t seed, int chunk, int gi,
 // Encoder attention on host q, k, v given as f32 [B][S][H*64] each (rounded to bf16 inside).
 extern "C" int wmdbg_enc_attention(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int S,
                                    float *out) {
+    return wmdbg_enc_attention_ex(ctx, q, k, v, B, H, S, 0, out);
+}
+
+// The same; flags & 1: the 64 rows behind the last chunk's in the staged query | key buffer -- what the last chunk's final K
+// tile reads behind key S - 1, as the encoder's m->qk has them behind row B * 1500 -- hold NaN instead of zeros.
+extern "C" int wmdbg_enc_attention_ex(wm_ctx *ctx, const float *q, const float *k, const float *v, int B, int H, int S,
+                                      int flags, float *out) {
     WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(q && k && v && out && B >= 1 && H >= 1 && S >= 1 && (flags & ~1) == 0, WM_ERR_INVALID, "wmdbg_enc_attention: bad args");
     const int d = H * 64, S_pad = ((S + 63) / 64) * 64;
     const size_t M = (size_t)B * S;
     std::vector<bf16_t> qk((M + 64) * 2 * d, 0), vt((size_t)B * H * 64 * S_pad, 0);
+    if (flags & 1) std::fill(qk.begin() + M * 2 * d, qk.end(), (bf16_t)0x7fc0);
     for (size_t mrow = 0; mrow < M; ++mrow)
         for (int j = 0; j < d; ++j) {
             qk[mrow * 2 * d + j] = f2bf(q[mrow * d + j] * WM_ENC_QSCALE);   // the kernel's contract: pre-scaled queries
@@ -3190,6 +3202,65 @@ extern "C" int wmdbg_encode_layer_qkv(wm_ctx *ctx, int layer, const float *x, in
     if (rc == WM_OK) rc = down_bf16(m->vt, vt_n, vt_out, s);
     // the pad columns 1500 .. 1535 of vt are zero in the product (zeroed at allocation, never written): as a later encode expects
     WM_HIP(hipMemsetAsync(m->vt, 0, vt_n * 2, s));
+    WM_HIP(hipStreamSynchronize(s));
+    return rc;
+}
+
+extern "C" int wmdbg_encode_layer_tail(wm_ctx *ctx, int layer, const float *x, int B, float *att_out, float *x_mid_out,
+                                       float *xn2_out, float *hid_out, float *x_out) {
+    WM_REQUIRE(x && att_out && x_mid_out && xn2_out && hid_out && x_out, WM_ERR_INVALID, "wmdbg_encode_layer_tail: null pointer");
+    WM_TRY(model_ready(ctx, B, "wmdbg_encode_layer_tail"));
+    WmModel *m = ctx->model;
+    WM_REQUIRE(layer >= 0 && layer < m->dims.n_audio_layer, WM_ERR_INVALID, "wmdbg_encode_layer_tail: layer %d out of range", layer);
+    const int d = m->dims.n_audio_state, H = m->dims.n_audio_head;
+    const size_t M = (size_t)B * 1500, vt_n = (size_t)B * H * 64 * 1536;
+    std::vector<bf16_t> s16;
+    std::vector<float> s32;
+    fill_bf16(s16, M * 4 * d);
+    fill_f32(s32, M * d);
+    DevPool pool;
+    hipStream_t s = ctx->stream;
+    float *dmid;
+    WM_TRY(pool.get(&dmid, s32.data(), M * d * 4, s));
+    // sentinels in everything the launches must write; vt is zeroed instead: its pad columns 1500 .. 1535 are the attention
+    // kernel's contract (zeroed at allocation, never written), and the live columns are all written by the QKV launch
+    WM_HIP(hipMemcpyAsync(m->x, x, M * d * 4, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->xn, s16.data(), M * d * 2, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->qk, s16.data(), (M + 64) * 2 * d * 2, hipMemcpyHostToDevice, s));   // and the 64 rows the last K tile over-reads
+    WM_HIP(hipMemcpyAsync(m->att, s16.data(), M * d * 2, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->hid, s16.data(), M * 4 * d * 2, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemsetAsync(m->vt, 0, vt_n * 2, s));
+    int rc = wm_model_encode_layer_qkv(ctx, layer, B);
+    if (rc == WM_OK) rc = wm_model_encode_layer_tail(ctx, layer, B, dmid);
+    if (rc == WM_OK) rc = down_bf16(m->att, M * d, att_out, s);
+    if (rc == WM_OK) rc = down_bf16(m->xn, M * d, xn2_out, s);
+    if (rc == WM_OK) rc = down_bf16(m->hid, M * 4 * d, hid_out, s);
+    if (rc == WM_OK) {
+        WM_HIP(hipMemcpyAsync(x_mid_out, dmid, M * d * 4, hipMemcpyDeviceToHost, s));
+        WM_HIP(hipMemcpyAsync(x_out, m->x, M * d * 4, hipMemcpyDeviceToHost, s));
+    }
+    WM_HIP(hipMemsetAsync(m->qk + M * 2 * d, 0, (size_t)64 * 2 * d * 2, s));   // the over-read rows as the allocation left them
+    WM_HIP(hipStreamSynchronize(s));
+    return rc;
+}
+
+extern "C" int wmdbg_encode_post(wm_ctx *ctx, const float *x, int B, float *xn_out, float *xa_out) {
+    WM_REQUIRE(x && xn_out && xa_out, WM_ERR_INVALID, "wmdbg_encode_post: null pointer");
+    WM_TRY(model_ready(ctx, B, "wmdbg_encode_post"));
+    WmModel *m = ctx->model;
+    const int d = m->dims.n_audio_state;
+    const size_t M = (size_t)B * 1500;
+    std::vector<bf16_t> s16;
+    std::vector<float> s32;
+    fill_bf16(s16, M * d);
+    fill_f32(s32, M * d);
+    hipStream_t s = ctx->stream;
+    WM_HIP(hipMemcpyAsync(m->x, x, M * d * 4, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->xn, s16.data(), M * d * 2, hipMemcpyHostToDevice, s));
+    WM_HIP(hipMemcpyAsync(m->xa_f32, s32.data(), M * d * 4, hipMemcpyHostToDevice, s));
+    int rc = wm_model_encode_post(ctx, B, nullptr);
+    if (rc == WM_OK) rc = down_bf16(m->xn, M * d, xn_out, s);
+    if (rc == WM_OK) WM_HIP(hipMemcpyAsync(xa_out, m->xa_f32, M * d * 4, hipMemcpyDeviceToHost, s));
     WM_HIP(hipStreamSynchronize(s));
     return rc;
 }

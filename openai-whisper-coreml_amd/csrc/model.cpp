@@ -990,23 +990,39 @@ int wm_model_encode_layer_qkv(wm_ctx *ctx, int layer, int B) {
     return wm_gemm(ctx, g);
 }
 
-int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out) {
-    WM_TRY(wm_model_encode_stem(ctx, d_mel, d_win, B));
+// The rest of the layer: attention over m->qk / m->vt into m->att, the out-projection onto the residual stream m->x, LayerNorm
+// into m->xn, fc1 + GELU into m->hid, fc2 onto m->x.  (Also run on its own by wmdbg_encode_layer_tail, which hands d_x_mid:
+// device f32 [B * 1500][d] that receives a copy of the residual stream between the out-projection and the LayerNorm -- the one
+// intermediate a later launch of the layer overwrites.  The encoder passes null: no copy.)
+int wm_model_encode_layer_tail(wm_ctx *ctx, int layer, int B, float *d_x_mid) {
     WmModel *m = ctx->model;
     const wm_dims &D = m->dims;
-    const int d = D.n_audio_state, H = D.n_audio_head, S = 1500;
-    const int M = B * S;
-    for (int i = 0; i < D.n_audio_layer; ++i) {
-        const EncLayerW &L = m->enc[i];
+    const int d = D.n_audio_state, H = D.n_audio_head, S = 1500, M = B * S;
+    const EncLayerW &L = m->enc[layer];
+    WM_TRY(wm_enc_attention(ctx, m->qk, m->vt, m->att, B, H, S, 1536, d));
+    WM_TRY(wm_gemm(ctx, plain_gemm(m->att, d, L.wo, L.bo, m->x, d, M, d, d, EPI_RESID_F32)));
+    if (d_x_mid) WM_HIP(hipMemcpyAsync(d_x_mid, m->x, (size_t)M * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    WM_TRY(wm_layernorm(ctx, m->x, L.ln2_g, L.ln2_b, M, d, m->xn, nullptr));
+    WM_TRY(wm_gemm(ctx, plain_gemm(m->xn, d, L.w1, L.b1, m->hid, 4 * d, M, 4 * d, d, EPI_GELU_BF16)));
+    return wm_gemm(ctx, plain_gemm(m->hid, 4 * d, L.w2, L.b2, m->x, d, M, d, 4 * d, EPI_RESID_F32));
+}
+
+// ln_post of the residual stream m->x: bf16 into m->xn (the cross-K/V product's operand), f32 into d_xa_out or m->xa_f32.
+// (Also run on its own by wmdbg_encode_post.)
+int wm_model_encode_post(wm_ctx *ctx, int B, float *d_xa_out) {
+    WmModel *m = ctx->model;
+    const int d = m->dims.n_audio_state, M = B * 1500;
+    return wm_layernorm(ctx, m->x, m->ln_post_g, m->ln_post_b, M, d, m->xn, d_xa_out ? d_xa_out : m->xa_f32);
+}
+
+int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out) {
+    WM_TRY(wm_model_encode_stem(ctx, d_mel, d_win, B));
+    const int n_layer = ctx->model->dims.n_audio_layer;
+    for (int i = 0; i < n_layer; ++i) {
         WM_TRY(wm_model_encode_layer_qkv(ctx, i, B));
-        WM_TRY(wm_enc_attention(ctx, m->qk, m->vt, m->att, B, H, S, 1536, d));
-        WM_TRY(wm_gemm(ctx, plain_gemm(m->att, d, L.wo, L.bo, m->x, d, M, d, d, EPI_RESID_F32)));
-        WM_TRY(wm_layernorm(ctx, m->x, L.ln2_g, L.ln2_b, M, d, m->xn, nullptr));
-        WM_TRY(wm_gemm(ctx, plain_gemm(m->xn, d, L.w1, L.b1, m->hid, 4 * d, M, 4 * d, d, EPI_GELU_BF16)));
-        WM_TRY(wm_gemm(ctx, plain_gemm(m->hid, 4 * d, L.w2, L.b2, m->x, d, M, d, 4 * d, EPI_RESID_F32)));
+        WM_TRY(wm_model_encode_layer_tail(ctx, i, B, nullptr));
     }
-    WM_TRY(wm_layernorm(ctx, m->x, m->ln_post_g, m->ln_post_b, M, d, m->xn, d_xa_out ? d_xa_out : m->xa_f32));
-    return WM_OK;
+    return wm_model_encode_post(ctx, B, d_xa_out);
 }
 
 int wm_model_set_xa(wm_ctx *ctx, const float *d_xa, int B) {

@@ -651,10 +651,13 @@ int wm_model_finalize(wm_ctx *ctx);
 int wm_model_encode_dev(wm_ctx *ctx, const float *d_mel, int B, float *d_xa_out /*nullable*/);
 // the same with row b's input the mel window d_win[b] (device, nullable: wm_model_encode_dev)
 int wm_model_encode_win(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B, float *d_xa_out /*nullable*/);
-// the two parts of wm_model_encode_win that the debug library also runs on their own: the stem (mel re-layout, conv1, conv2 ->
-// m->x) and one layer's LayerNorm + QKV launch (m->x -> m->xn, m->qk, m->vt)
+// the four parts of wm_model_encode_win, which the debug library also runs on their own: the stem (mel re-layout, conv1, conv2
+// -> m->x), one layer's LayerNorm + QKV launch (m->x -> m->xn, m->qk, m->vt), the rest of the layer (attention, out-projection,
+// LayerNorm, fc1, fc2 -> m->x; d_x_mid nullable: a copy of m->x after the out-projection) and ln_post (m->x -> m->xn, xa)
 int wm_model_encode_stem(wm_ctx *ctx, const float *d_mel, const WmMelWin *d_win, int B);
 int wm_model_encode_layer_qkv(wm_ctx *ctx, int layer, int B);
+int wm_model_encode_layer_tail(wm_ctx *ctx, int layer, int B, float *d_x_mid /*nullable*/);
+int wm_model_encode_post(wm_ctx *ctx, int B, float *d_xa_out /*nullable*/);
 int wm_model_cross_kv(wm_ctx *ctx, int B);                 // from m->xn (bf16 encoder output)
 int wm_model_set_xa(wm_ctx *ctx, const float *d_xa, int B);  // f32 xa -> m->xn (bf16)
 int wm_model_decode_begin(wm_ctx *ctx, int B);

@@ -1,8 +1,10 @@
 """The product's own encoder-side launches on a loaded model, stage by stage and element by element: the stem (mel re-layout,
 conv1, conv2 as wm_model_encode_win launches them, on the conv weights as wm_set_tensor packed them), one layer's LayerNorm +
-QKV launch (pre-scaled queries, keys, V^T in the attention kernel's column order) and the cross-K/V scatter, through
-wmdbg_encode_stem / wmdbg_encode_layer_qkv / wmdbg_cross_kv.  B = 3: the chunk boundaries at rows 1500 and 3000 (3000 and 6000
-for conv1) are no multiple of 64, 128 or 256.  References and bounds: tests/enc_gemm_ref.py (float64; delta = 2 K u S).
+QKV launch (pre-scaled queries, keys, V^T in the attention kernel's column order), the rest of the layer (attention, out-
+projection, LayerNorm, fc1 + GELU, fc2), ln_post and the cross-K/V scatter, through wmdbg_encode_stem / wmdbg_encode_layer_qkv /
+wmdbg_encode_layer_tail / wmdbg_encode_post / wmdbg_cross_kv.  B = 3: the chunk boundaries at rows 1500 and 3000 (3000 and 6000
+for conv1) are no multiple of 64, 128 or 256.  Every stage is measured on the DEVICE's own input to it.  References and bounds:
+tests/enc_gemm_ref.py (float64; delta = 2 K u S), tests/enc_attn_ref.py, tests/layernorm_ref.py.
 Whole-model rel-L2 (test_model_gpu.py) does not see one misplaced frame per chunk; these do."""
 import ctypes
 import importlib
@@ -14,7 +16,9 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import enc_attn_ref as E   # noqa: E402
 import enc_gemm_ref as R   # noqa: E402
+import layernorm_ref as L   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +55,8 @@ class Model:
         vp, ip = ctypes.c_void_p, ctypes.c_int
         c.lib.wmdbg_encode_stem.argtypes = [vp, vp, vp, ip, vp, vp, vp]
         c.lib.wmdbg_encode_layer_qkv.argtypes = [vp, ip, vp, ip, vp, vp, vp]
+        c.lib.wmdbg_encode_layer_tail.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, vp]
+        c.lib.wmdbg_encode_post.argtypes = [vp, vp, ip, vp, vp]
         c.lib.wmdbg_cross_kv.argtypes = [vp, vp, ip, vp]
         c.lib.wmdbg_set_gemm_tile.argtypes = [ctypes.c_int]
         c.lib.wmdbg_set_tuning.argtypes = [ctypes.c_char_p, ctypes.c_int]
@@ -86,6 +92,21 @@ class Model:
         st = self.ctx.lib.wmdbg_encode_layer_qkv(self.ctx.handle, layer, P(np.ascontiguousarray(x, np.float32)), n, P(xn), P(qk), P(vt))
         assert st == 0, self.ctx.lib.wm_last_error()
         return xn, qk, vt
+
+    def layer_tail(self, layer, x):
+        """-> att, x_mid, xn2, hid, x_out; NaN where the hook wrote nothing"""
+        n = len(x) // S
+        outs = [np.full((n * S, w), np.nan, np.float32) for w in (self.d, self.d, self.d, 4 * self.d, self.d)]
+        st = self.ctx.lib.wmdbg_encode_layer_tail(self.ctx.handle, layer, P(np.ascontiguousarray(x, np.float32)), n, *[P(o) for o in outs])
+        assert st == 0, self.ctx.lib.wm_last_error()
+        return outs
+
+    def post(self, x):
+        n = len(x) // S
+        xn, xa = (np.full((n * S, self.d), np.nan, np.float32) for _ in range(2))
+        st = self.ctx.lib.wmdbg_encode_post(self.ctx.handle, P(np.ascontiguousarray(x, np.float32)), n, P(xn), P(xa))
+        assert st == 0, self.ctx.lib.wm_last_error()
+        return xn, xa
 
     def cross_kv(self, xa):
         n = len(xa)
@@ -219,6 +240,66 @@ def test_layer_qkv_every_element_through_every_tile(model, layer):
         m.reset()
 
 
+def attention_operands(m, qk, vt):
+    """(pre-scaled queries, keys, values) [n][S][d] of the returned qk / vt: wm_att_vt_pos undone by enc_gemm_ref's restatement"""
+    n = len(qk) // S
+    qs, k = qk[:, :m.d].reshape(n, S, m.d), qk[:, m.d:].reshape(n, S, m.d)
+    v = vt[:, :, :, R.vt_pos(np.arange(S))].transpose(0, 3, 1, 2).reshape(n, S, m.d)
+    return qs, k, v
+
+
+@pytest.mark.parametrize("layer", [0, 1])
+def test_layer_tail_every_element_through_every_tile(model, layer):
+    """attention, out-projection + residual, LayerNorm, fc1 + GELU, fc2 + residual as wm_model_encode_layer_tail launches them"""
+    m = model
+    sd = m.sd
+    pre = "encoder.blocks.%d" % layer
+    M = B * S
+    Wo, W1, W2 = (R.bf16(sd[pre + k]) for k in (".attn.out.weight", ".mlp.0.weight", ".mlp.2.weight"))
+    g_o, g_1, g_2 = R.plain(M, m.d, m.d, R.EPI_RESID_F32), R.plain(M, 4 * m.d, m.d, R.EPI_GELU_BF16), R.plain(M, m.d, 4 * m.d, R.EPI_RESID_F32)
+    try:
+        outs, att_ref, first_qk = [], None, None
+        for tile, pipe in TILES:
+            m.tile(tile, pipe)
+            _, qk, vt = m.layer_qkv(layer, m.x)
+            att, x_mid, xn2, hid, x_out = m.layer_tail(layer, m.x)
+            if att_ref is None or not (np.array_equal(bits(qk), bits(first_qk[0])) and np.array_equal(bits(vt), bits(first_qk[1]))):
+                first_qk = (qk, vt)
+                qs, k, v = attention_operands(m, qk, vt)      # (no pad column among the 1500 live ones: all finite)
+                assert np.isfinite(v).all()
+                att_ref = E.restate(None, k, v, m.H, qs=qs)
+            within("att", att, att_ref.ref.reshape(M, m.d), att_ref.bound[0].reshape(M, m.d))
+            ref, Sb = R.values(g_o, att, Wo, sd[pre + ".attn.out.bias"], C0=m.x)
+            within("x_mid", x_mid, ref, R.bound(g_o, ref, Sb))
+            y, bnd = L.restate(x_mid, sd[pre + ".mlp_ln.weight"], sd[pre + ".mlp_ln.bias"])
+            lo, hi = L.bf16_bracket(y, bnd)
+            assert ((lo <= xn2) & (xn2 <= hi)).all(), ("xn2", np.argwhere(~((lo <= xn2) & (xn2 <= hi)))[:5])
+            ref, Sb = R.values(g_1, xn2, W1, sd[pre + ".mlp.0.bias"])
+            within("hid", hid, ref, R.bound(g_1, ref, Sb))
+            ref, Sb = R.values(g_2, hid, W2, sd[pre + ".mlp.2.bias"], C0=x_mid)
+            within("x_out", x_out, ref, R.bound(g_2, ref, Sb))
+            outs.append((att, x_mid, xn2, hid, x_out))
+        for o in outs[1:]:                                             # same accumulation order in every tile
+            assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(o, outs[0]))
+        # the hook leaves the buffers as a later encode expects them
+        assert np.isfinite(m.ctx.encode_mel(m.mel[:1])).all()
+    finally:
+        m.reset()
+
+
+def test_post_every_element(model):
+    """ln_post as wm_model_encode_post launches it (both outputs), on the residual stream and on one with an outlier column"""
+    m = model
+    g, b = m.sd["encoder.ln_post.weight"], m.sd["encoder.ln_post.bias"]
+    spike = m.x.copy()
+    spike[:, 5] *= 1e3
+    for name, x in (("xa", m.x), ("xa_spike", spike)):
+        xn, xa = m.post(x)
+        y, bnd = L.restate(x, g, b)
+        within(name, xa, y, bnd)
+        assert np.array_equal(bits(xn), bits(L.bf16(xa))), "ln_post: the bf16 output is not RNE of the f32 output"
+
+
 def test_cross_kv_every_element_through_every_tile(model):
     m = model
     sd = m.sd
@@ -257,6 +338,8 @@ def test_chunk_one_of_three_is_bit_identical_to_the_chunk_alone(model):
     xn1, qk1, vt1 = m.layer_qkv(1, m.x[S:2 * S])
     assert np.array_equal(bits(xn3[S:2 * S]), bits(xn1))
     assert np.array_equal(bits(qk3[S:2 * S]), bits(qk1)) and np.array_equal(bits(vt3[1]), bits(vt1[0]))
+    for a3, a1 in zip(m.layer_tail(1, m.x) + list(m.post(m.x)), m.layer_tail(1, m.x[S:2 * S]) + list(m.post(m.x[S:2 * S]))):
+        assert np.array_equal(bits(a3[S:2 * S]), bits(a1))
     xkv3 = m.cross_kv(m.xa)
     xkv1 = m.cross_kv(m.xa[1:2])          # (the model's cache is still sized for 3 chunks: the hook checks that rows 1, 2 stay untouched)
     assert np.array_equal(bits(xkv3[:, :, 1]), bits(xkv1[:, :, 0]))
