@@ -101,6 +101,57 @@ WM_API int wm_logmel(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, int n_chu
 WM_API int wm_logmel_long(wm_ctx *ctx, const void *pcm, wm_dtype pcm_dtype, const int64_t *sample_offsets, int R,
                           int n_mels, float *out, wm_mem mem);
 
+/* ---- live audio: a set of S streams whose appended samples become log-mel frames incrementally, on the device (DESIGN.md
+ * "Live streams").  A front-end-only context is enough.  Everything is enqueued on the context's stream, so pushes and
+ * windows are ordered.  Stream s has received N samples, an absolute i64 count; stream time has no limit.
+ *   frame t      : wm_logmel_long's frame t of a recording that begins where the stream began: centred at sample 160 t, it
+ *                  reads the samples [160 t - 200, 160 t + 200); an index n < 0 reads sample -n (torch center=True,
+ *                  reflect); a sample that has not arrived reads 0 -- no reflect at the live end, which is what
+ *                  wm_logmel_long computes for a recording that ends at N, because 480000 zeros follow it.
+ *   final_frames : F, the frames whose every sample has arrived, 160 t + 200 <= N (frame 0 reads sample 200: N >= 201); a prefix.
+ *   avail_frames : A, the frames that read at least one arrived sample: 0 for N = 0, else (N + 199) / 160 + 1.  Frames
+ *                  [F, A) are PROVISIONAL, at most 3; every push recomputes them until they are final.
+ *   first_kept   : K = max(0, A - capacity_frames); older frames are gone.
+ * The set keeps per stream, on the device: a ring of capacity_frames columns of the RAW values log10(max(mel, 1e-10)), before
+ * any normalisation; each frame's maximum over its mel rows; and a carry of the staged f32 samples (at most 399) that frames
+ * which are not final still need.  The carry holds values after conversion, and a frame's arithmetic sees its own 400
+ * samples alone: a frame does not depend on how the audio was split into pushes, nor on the dtype on either side of a split.
+ *
+ * wm_streams_create : S 1 .. 65535, n_mels 80 / 128, capacity_frames >= 3003 (a 3000-frame window and the provisional frames
+ *                     always fit).  WM_ERR_INVALID otherwise.
+ * wm_streams_free   : NULL: no-op; synchronises the context's stream.
+ * wm_streams_push   : appends pcm[sample_offsets[s] .. sample_offsets[s + 1]) to stream s, for all S streams at once.
+ *     pcm            : WM_I16 (x = s/32768) / WM_F32 / WM_F64, the conversions of the f32 fast path; mem-space selectable
+ *                      (with WM_MEM_HOST only pcm[sample_offsets[0] .. sample_offsets[S]) is copied); may be NULL when no
+ *                      stream gets a sample;
+ *     sample_offsets : i64 [S + 1] (host), >= 0 and non-decreasing; zero samples are legal, at most 2^30 per stream and call.
+ *   One launch of the f32 front-end kernel computes, for all streams, every frame that became final and the new provisional
+ *   frames; a push that brings more than capacity_frames frames computes only those that stay.  A second, small launch
+ *   moves the carries.  A push that fails validation changes nothing.
+ * wm_streams_reset  : stream s is empty again (N = 0); the others are untouched.
+ * wm_streams_frames : the counters N, F, A, K of every stream, i64 [S] each, any of them NULL.  Host only, no launch.
+ * wm_streams_window : row r = frames [first_frame[r], first_frame[r] + n_frames[r]) of stream stream[r]; K <= first,
+ *                     first + n <= A, n in 1 .. 3000; R in 1 .. 65535; several rows may name one stream.  The row's block
+ *                     [n_mels][n_frames] is written at out + out_base[r] (element offsets, i64 [R], host; >= 0) as
+ *                     (max(raw, gmax - 8) + 4) / 4 with gmax the maximum over exactly the row's frames -- the
+ *                     normalisation of a recording that is the window, the arithmetic of wm_logmel's second stage.  One
+ *                     launch for all rows, no atomics: deterministic.  out: f32, mem-space selectable.  The block is what
+ *                     wm_transcribe_mel, wm_windows_encode, wm_align_mel and wm_vad_energy take as `mel` with mel_base =
+ *                     out_base, mel_len = n_frames, seek = 0.  For first = 0 it is bit for bit wm_logmel_long's columns
+ *                     [0, A) of the samples so far.
+ * Errors: WM_ERR_INVALID for the ranges above, decreasing or negative offsets, a row outside [K, A), a stream index outside
+ * the set, null pointers; WM_ERR_STATE for a set used with a context on another device. */
+typedef struct wm_streams wm_streams;
+WM_API int wm_streams_create(wm_ctx *ctx, int S, int n_mels, int capacity_frames, wm_streams **out);
+WM_API int wm_streams_free(wm_ctx *ctx, wm_streams *set);
+WM_API int wm_streams_push(wm_ctx *ctx, wm_streams *set, const void *pcm, wm_dtype pcm_dtype, const int64_t *sample_offsets,
+                           wm_mem mem);
+WM_API int wm_streams_reset(wm_ctx *ctx, wm_streams *set, int s);
+WM_API int wm_streams_frames(const wm_streams *set, int64_t *samples, int64_t *final_frames, int64_t *avail_frames,
+                             int64_t *first_kept);
+WM_API int wm_streams_window(wm_ctx *ctx, wm_streams *set, int R, const int32_t *stream, const int64_t *first_frame,
+                             const int32_t *n_frames, float *out, const int64_t *out_base, wm_mem mem);
+
 /* --------------------------------------------------------- context / weight loading --- */
 
 /* Front-end-only context (no model): enough for wm_logmel. */

@@ -772,6 +772,14 @@ WM_API int wmdbg_beam_step_layout(int32_t *out4);
  * group_rows <= 128.  to_store != 0: group -> store (the rows must differ), else store -> group.  Synchronous. */
 WM_API int wmdbg_xkv_rows(wm_ctx *ctx, uint16_t *group, int group_rows, uint16_t *store, int64_t store_rows, const int32_t *rows,
                           int n_rows, int L, int H, int to_store);
+/* ---- live streams (wm_streams) ---- */
+/* An EMPTY stream s (N = 0: new or reset) believes that n_samples >= 0 of silence came before: N = n_samples, its carry is
+ * zeros, and no index is reflected because the stream is past its start.  No frame is computed: A reads as F and K as F until
+ * the next push, which computes the frames from F on.  Tests 64-bit stream time without pushing 2^33 samples. */
+WM_API int wmdbg_streams_set_position(wm_ctx *ctx, wm_streams *set, int s, int64_t n_samples);
+/* The smallest capacity_frames wm_streams_create accepts (the product: 3003), 64 .. 3003, so that the ring wrap can be tested on
+ * small rings; 0 restores the product's.  Process-wide.  Returns the value in force. */
+WM_API int wmdbg_streams_min_capacity(int capacity_frames);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,12 @@ def load_library(path=None):
         "wm_resample_16k_mix": [vp, vp, ip, vp, vp, vp, ip, vp, vp, vp, ip],
         "wm_channel_activity": [vp, vp, vp, ip, vp, ip],
         "wm_vad_energy": [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip],
+        "wm_streams_create": [vp, ip, ip, ip, pp],
+        "wm_streams_free": [vp, vp],
+        "wm_streams_push": [vp, vp, vp, ip, vp, ip],
+        "wm_streams_reset": [vp, vp, ip],
+        "wm_streams_frames": [vp, vp, vp, vp, vp],
+        "wm_streams_window": [vp, vp, ip, vp, vp, vp, vp, vp, ip],
         "wm_vad_segments": [vp, ctypes.c_int64, vp, vp, ip, vp, vp],
         "wm_audio_open": [ctypes.c_char_p, pp],
         "wm_audio_sample_rate": [vp],
@@ -190,6 +196,11 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
+    if hasattr(lib, "wmdbg_streams_set_position"):   # the debug library
+        lib.wmdbg_streams_set_position.argtypes = [vp, vp, ip, ctypes.c_int64]
+        lib.wmdbg_streams_set_position.restype = ctypes.c_int
+        lib.wmdbg_streams_min_capacity.argtypes = [ip]
+        lib.wmdbg_streams_min_capacity.restype = ctypes.c_int
     lib.wm_destroy.argtypes = [vp]
     lib.wm_destroy.restype = None
     lib.wm_windows_free.argtypes = [vp]
@@ -2195,6 +2206,95 @@ class Windows:
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle:
             self.lib.wm_windows_free(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def stream_frame_counts(n_samples, capacity_frames):
+    """The counters of a live stream that has received n_samples (wm_streams_frames): (final_frames F, avail_frames A,
+    first_kept K).  Frame t reads the samples [160 t - 200, 160 t + 200); frame 0's reflected half reads sample 200."""
+    n = int(n_samples)
+    final = 0 if n < 201 else (n - 200) // 160 + 1
+    avail = 0 if n <= 0 else (n + 199) // 160 + 1
+    return final, avail, max(0, avail - int(capacity_frames))
+
+
+class Streams:
+    """RAII wrapper over wm_streams: S live audio streams whose appended samples become log-mel frames incrementally on
+    the device (push), any window of which is normalised on demand (window).  A front-end-only context is enough.  Close
+    it (or leave its `with` block) before the context."""
+
+    def __init__(self, ctx, S, n_mels=80, capacity_frames=3003):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.S, self.n_mels, self.capacity_frames = int(S), int(n_mels), int(capacity_frames)
+        self.handle = ctypes.c_void_p()
+        _check(self.lib, self.lib.wm_streams_create(ctx.handle, self.S, self.n_mels, self.capacity_frames,
+                                                    ctypes.byref(self.handle)))
+
+    def push(self, pieces):
+        """wm_streams_push: pieces[s] = the new samples of stream s (1-D int16 / float32 / float64; one dtype per call) or
+        None for nothing.  One launch for all streams."""
+        if len(pieces) != self.S:
+            raise ValueError("push takes one entry per stream (%d), got %d" % (self.S, len(pieces)))
+        arrs = [np.ascontiguousarray(p).reshape(-1) for p in pieces if p is not None and len(p)]
+        dtype = arrs[0].dtype if arrs else np.dtype(np.float32)
+        if any(a.dtype != dtype for a in arrs) or dtype not in _DTYPES:
+            raise ValueError("the pieces of one push share one dtype of int16 / float32 / float64")
+        lens = [0 if p is None else len(p) for p in pieces]
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        pcm = np.concatenate(arrs) if arrs else np.zeros(1, dtype)
+        _check(self.lib, self.lib.wm_streams_push(self.ctx.handle, self.handle, _ptr(pcm), _DTYPES[pcm.dtype], _ptr(offs),
+                                                  WM_MEM_HOST))
+
+    def reset(self, s):
+        """wm_streams_reset: stream s is empty again."""
+        _check(self.lib, self.lib.wm_streams_reset(self.ctx.handle, self.handle, int(s)))
+
+    def frames(self):
+        """wm_streams_frames: (samples, final_frames, avail_frames, first_kept), i64 [S] each."""
+        out = [np.zeros(self.S, np.int64) for _ in range(4)]
+        _check(self.lib, self.lib.wm_streams_frames(self.handle, *[_ptr(o) for o in out]))
+        return tuple(out)
+
+    def window(self, rows, device=True):
+        """wm_streams_window: rows = (stream, first_frame, n_frames) triples, one launch for all of them.  Returns a list of
+        f32 [n_mels][n_frames] arrays with device=False; device=True keeps the blocks on the device, back to back: (pointer,
+        out_base i64 [R], n_frames i32 [R]) -- what transcribe_mel takes as (mel, mel_base, mel_len) with seek 0; free the
+        pointer with the context's dev_free."""
+        rows = [(int(s), int(f), int(n)) for s, f, n in rows]
+        R = len(rows)
+        stream = np.array([r[0] for r in rows], np.int32)
+        first = np.array([r[1] for r in rows], np.int64)
+        n = np.array([r[2] for r in rows], np.int32)
+        base = np.concatenate([[0], np.cumsum(np.maximum(n, 0).astype(np.int64) * self.n_mels)]).astype(np.int64)
+        if not device:
+            out = np.empty(max(int(base[-1]), 1), np.float32)
+            _check(self.lib, self.lib.wm_streams_window(self.ctx.handle, self.handle, R, _ptr(stream), _ptr(first), _ptr(n),
+                                                        _ptr(out), _ptr(base), WM_MEM_HOST))
+            return [out[base[r]:base[r + 1]].reshape(self.n_mels, n[r]) for r in range(R)]
+        d_out = self.ctx.dev_malloc(max(int(base[-1]), 1) * 4)
+        try:
+            _check(self.lib, self.lib.wm_streams_window(self.ctx.handle, self.handle, R, _ptr(stream), _ptr(first), _ptr(n),
+                                                        d_out, _ptr(base), WM_MEM_DEVICE))
+        except Exception:
+            self.ctx.dev_free(d_out)
+            raise
+        return d_out, base[:-1].copy(), n
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle:
+            self.lib.wm_streams_free(self.ctx.handle, self.handle)
             self.handle = ctypes.c_void_p()
 
     def __del__(self):

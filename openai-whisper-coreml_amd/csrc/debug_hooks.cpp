@@ -3294,3 +3294,27 @@ extern "C" int wmdbg_cross_kv(wm_ctx *ctx, const float *xa, int B, float *xkv_ou
     from_bf16(got, xkv_out);
     return WM_OK;
 }
+
+// ---------------------------------------------------------------- live streams (streams.cpp)
+#include "streams.h"
+
+extern "C" int wmdbg_streams_set_position(wm_ctx *ctx, wm_streams *st, int s, int64_t n_samples) {
+    WM_TRY(wm_ctx_make_current(ctx));
+    WM_REQUIRE(st != nullptr, WM_ERR_INVALID, "wmdbg_streams_set_position: null set");
+    WM_REQUIRE(st->device == ctx->device, WM_ERR_STATE, "wmdbg_streams_set_position: the set lives on another device");
+    WM_REQUIRE(s >= 0 && s < st->S, WM_ERR_INVALID, "wmdbg_streams_set_position: stream %d outside 0 .. %d", s, st->S - 1);
+    WM_REQUIRE(n_samples >= 0, WM_ERR_INVALID, "wmdbg_streams_set_position: negative position");
+    WM_REQUIRE(st->n[s] == 0, WM_ERR_STATE, "wmdbg_streams_set_position: stream %d is not empty", s);
+    WM_HIP(hipMemsetAsync(st->carry + (size_t)s * WM_STREAM_CARRY, 0, sizeof(float) * WM_STREAM_CARRY, ctx->stream));
+    st->n[s] = n_samples;
+    st->floor[s] = wm_stream_final(n_samples);
+    st->reflect[s] = n_samples == 0;
+    st->stale[s] = n_samples > 0;
+    return WM_OK;
+}
+
+extern "C" int wmdbg_streams_min_capacity(int capacity_frames) {
+    if (capacity_frames == 0) g_wm_stream_min_capacity = WM_STREAM_MIN_CAPACITY;
+    else if (capacity_frames >= WM_STREAM_FPB && capacity_frames <= WM_STREAM_MIN_CAPACITY) g_wm_stream_min_capacity = capacity_frames;
+    return g_wm_stream_min_capacity;
+}

@@ -28,6 +28,7 @@
 // ascending-k sum exactly) -> log10 -> store + per-chunk atomic max.
 // Kernel 2 (logmel_stage2): dynamic-range clamp + affine, in place.
 #include "wm_internal.h"
+#include "logmel_shared.h"
 
 #include <math.h>
 #include <string.h>
@@ -66,33 +67,6 @@ __device__ __forceinline__ int acc_row(double, int lane, int r) { return (lane >
 // times per lane; |error| <= 2e-7 relative, four orders below the path's 1e-4 gate (round 6; both f32 kernels share it)
 __device__ __forceinline__ float log10_t(float x) { return __builtin_amdgcn_logf(x) * 0.30102999566398120f; }
 __device__ __forceinline__ double log10_t(double x) { return log10(x); }
-
-// Monotone encodings so an unsigned atomicMax orders floating-point values.
-__device__ __forceinline__ unsigned long long enc_max(float v) {
-    unsigned u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return (unsigned long long)u;
-}
-__device__ __forceinline__ unsigned long long enc_max(double v) {
-    unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ void dec_max(unsigned long long e, float *out) {
-    unsigned u = (unsigned)e;
-    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    *out = __uint_as_float(u);
-}
-__device__ __forceinline__ void dec_max(unsigned long long e, double *out) {
-    unsigned long long u = (e & 0x8000000000000000ull) ? (e & 0x7fffffffffffffffull) : ~e;
-    *out = __longlong_as_double((long long)u);
-}
-
-template <typename T>
-__device__ __forceinline__ T load_sample(const void *pcm, int dtype, size_t idx) {
-    if (dtype == WM_I16) return (T)((const short *)pcm)[idx] * (T)(1.0 / 32768.0);
-    if (dtype == WM_F32) return (T)((const float *)pcm)[idx];
-    return (T)((const double *)pcm)[idx];
-}
 
 // LDS address of span sample p (p = local_frame * 160 + n): one pad word per 160 samples
 // so that the 16 frames a wave reads at the same n fall in different banks.
@@ -254,16 +228,27 @@ constexpr int BAND8 = 128 * (BW8 + 2);                  // band start / length /
 constexpr int LDS8_WORDS = MAIN8 + 2 * SLICE8 + 404 + W8 * 16 + BAND8;
 constexpr int LDS8_BYTES = LDS8_WORDS * 4;              // 76.5 KiB: two workgroups per CU
 
-// The staging rule is the template argument; the DFT, power, mel and log arithmetic below it is one code for both:
-//   LONG = false: chunk c = pcm[c * 480000, +480000), reflect-padded at both ends, 3000 frames, out [c][n_mels][3000];
-//   LONG = true : openai-whisper's log_mel_spectrogram(audio, padding=480000) -- recording r = its len_r samples followed by
+// The staging rule is the template argument; the DFT, power, mel and log arithmetic below it is one code for all three:
+//   Chunk : chunk c = pcm[c * 480000, +480000), reflect-padded at both ends, 3000 frames, out [c][n_mels][3000];
+//   Long  : openai-whisper's log_mel_spectrogram(audio, padding=480000) -- recording r = its len_r samples followed by
 //                 480000 zeros, reflect-padded by 200 at both ends (torch.stft center=True), T_r frames; workgroup ->
 //                 (recording, first frame) from lt.blk, out = recording r's [n_mels][T_r] block at lt.rec[r].out.
-template <bool LONG>
+//   Stream: a live stream (wm_streams_push) -- workgroup -> (stream, first sample, ring column, frame count) from lt.blk;
+//                 a sample comes from the stream's carry (the staged f32 samples below the old sample count), from the
+//                 new pcm behind it, is 0 where it has not arrived, and is reflected below the stream's first sample;
+//                 every index is relative to the carry's first sample, so absolute stream time never enters the kernel.
+//                 The frame goes to its column of the stream's ring of raw values, its maximum over the mel rows to
+//                 lt.fmax: no gmax atomic (the window kernel of streams.hip normalises).
+// One MFMA output row depends on its own input row alone, so a frame's bits do not depend on the rule, on the workgroup
+// or on the row it is computed in.
+enum class Stage { Chunk, Long, Stream };
+template <Stage RULE> struct StageTab { typedef WmLongTab type; };
+template <> struct StageTab<Stage::Stream> { typedef WmStreamTab type; };
+template <Stage RULE>
 __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     const void *__restrict__ pcm, int pcm_dtype, int n_mels, const float *__restrict__ tw, const float *__restrict__ win,
     const int *__restrict__ band_start, const int *__restrict__ band_len, const float *__restrict__ band_w,
-    float *__restrict__ out, unsigned long long *__restrict__ gmax, int blocks_per_chunk, WmLongTab lt) {
+    float *__restrict__ out, unsigned long long *__restrict__ gmax, int blocks_per_chunk, typename StageTab<RULE>::type lt) {
     extern __shared__ __attribute__((aligned(16))) float smem8[];
     float *xs = smem8;
     float(*pw)[16][PW8_STRIDE] = (float(*)[16][PW8_STRIDE])smem8;
@@ -276,7 +261,16 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     // [0, nsig); frames f0 .. f0 + 63 of nT, written to out[out0 + m * nT + frame]; its maximum goes to gmax[chunk]
     int chunk, f0, len, nsig, nT;
     size_t base, out0;
-    if (LONG) {
+    // Stream: span sample 0 relative to the carry, the carry's length, the ring column of the first frame
+    [[maybe_unused]] int s_first = 0, s_carry_len = 0, s_col0 = 0;
+    [[maybe_unused]] bool s_reflect = false;
+    if constexpr (RULE == Stage::Stream) {
+        const int4 bk = lt.blk[blockIdx.x];
+        const WmStreamRec r = lt.rec[bk.x];
+        chunk = bk.x; f0 = 0; s_first = bk.y; s_col0 = bk.z; nT = bk.w;
+        base = (size_t)r.pcm_base; out0 = (size_t)bk.x * n_mels * lt.cap; len = r.n_new; nsig = 0;
+        s_carry_len = r.carry_len; s_reflect = r.reflect != 0;
+    } else if constexpr (RULE == Stage::Long) {
         const int2 bk = lt.blk[blockIdx.x];
         const WmLongRec r = lt.rec[bk.x];
         chunk = bk.x; f0 = bk.y;
@@ -303,13 +297,31 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     const size_t chunk_base = base;
     constexpr int PER = 8, NPASS = (SPAN8 / PER + W8 * 64 - 1) / (W8 * 64);   // 1310 groups of 8 samples, 6 passes of 256 threads
     static_assert(SPAN8 % PER == 0, "the span is a whole number of 8-sample groups");
-    const int first = f0 * WM_HOP - 200;        // unpadded-chunk index of span sample 0
+    const int first = RULE == Stage::Stream ? s_first : f0 * WM_HOP - 200;   // unpadded-chunk index of span sample 0
     // (workgroup-uniform) no reflect, no masked frames, no zero tail -- and a span that starts 16-byte aligned (chunk offsets
     // and `first` are multiples of 16 bytes for int16 and f32; an odd base pointer or recording offset takes the gather path)
     const size_t esz = pcm_dtype == WM_I16 ? 2 : (pcm_dtype == WM_F32 ? 4 : 8);
-    const bool interior = first >= 0 && first + SPAN8 <= len && (((size_t)pcm + (chunk_base + first) * esz) & 15) == 0;
+    const bool interior = RULE != Stage::Stream && first >= 0 && first + SPAN8 <= len && (((size_t)pcm + (chunk_base + first) * esz) & 15) == 0;
     float v[NPASS][PER];
-    if (interior && pcm_dtype == WM_I16) {      // 16 bytes = 8 samples per load; first * 2 and chunk_base * 2 are multiples of 16
+    if constexpr (RULE == Stage::Stream) {      // carry below the old sample count, the new pcm from there, 0 past it
+        const float *carry = lt.carry + (size_t)chunk * WM_STREAM_CARRY;
+#pragma unroll
+        for (int ps = 0; ps < NPASS; ++ps) {
+            const int g = ps * W8 * 64 + tid;
+#pragma unroll
+            for (int u = 0; u < PER; ++u) {
+                int n = first + g * PER + u;                       // relative to the carry's first sample
+                const bool before = n < 0;                         // below the stream's first sample: a[-n] at its start,
+                if (before) n = -n;                                // silence for a stream that was placed past it
+                float x = 0.f;
+                if (!before || s_reflect) {
+                    if (n < s_carry_len) x = carry[n];
+                    else if (n - s_carry_len < len) x = load_sample<float>(pcm, pcm_dtype, chunk_base + (size_t)(n - s_carry_len));
+                }
+                v[ps][u] = x;
+            }
+        }
+    } else if (interior && pcm_dtype == WM_I16) {      // 16 bytes = 8 samples per load; first * 2 and chunk_base * 2 are multiples of 16
         const short *src = (const short *)pcm + chunk_base + first;
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
@@ -425,6 +437,8 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
     __syncthreads();
     const int frame = f0 + wave * 16 + (lane & 15);
     const bool live = frame < nT;
+    [[maybe_unused]] int s_col = 0;
+    if constexpr (RULE == Stage::Stream) s_col = (s_col0 + frame) % lt.cap;
     float vmax = -1e30f;
     for (int m = lane >> 4; m < n_mels; m += 4) {
         const int ks = bnd_i[m], kl = bnd_i[128 + m];
@@ -440,26 +454,26 @@ __global__ __launch_bounds__(W8 * 64, 2) void logmel_stage1_f32_lds(
         s = (s > 1e-10f) ? s : 1e-10f;
         const float v = log10_t(s);
         if (live) {
-            out[out0 + (size_t)m * nT + frame] = v;
+            if constexpr (RULE == Stage::Stream) out[out0 + (size_t)m * lt.cap + s_col] = v;
+            else out[out0 + (size_t)m * nT + frame] = v;
             vmax = (v > vmax) ? v : vmax;
         }
     }
+    if constexpr (RULE == Stage::Stream) {      // the frame's maximum over its mel rows: the four lanes that share lane & 15
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(vmax, off);
-        vmax = (o > vmax) ? o : vmax;
+        for (int off = 32; off >= 16; off >>= 1) {
+            const float o = __shfl_xor(vmax, off);
+            vmax = (o > vmax) ? o : vmax;
+        }
+        if (lane < 16 && live) lt.fmax[(size_t)chunk * lt.cap + s_col] = vmax;
+    } else {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float o = __shfl_xor(vmax, off);
+            vmax = (o > vmax) ? o : vmax;
+        }
+        if (lane == 0 && vmax > -1e29f) atomicMax(gmax + chunk, enc_max(vmax));
     }
-    if (lane == 0 && vmax > -1e29f) atomicMax(gmax + chunk, enc_max(vmax));
-}
-
-// the dynamic-range clamp and affine of one value (both stage-2 layouts)
-template <typename T>
-__device__ __forceinline__ T clamp_affine(T x, unsigned long long gm) {
-    T g;
-    dec_max(gm, &g);
-    const T fl = g - (T)8.0;
-    x = (x > fl) ? x : fl;         // x.max(gmax - 8.0)   lib.rs:96
-    return (x + (T)4.0) / (T)4.0;  // (.. + 4.0) / 4.0
 }
 
 template <typename T>
@@ -642,12 +656,12 @@ int wm_frontend_run(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const 
             int dev = 0;
             WM_HIP(hipGetDevice(&dev));
             if (!attr_set[dev & 63].load(std::memory_order_acquire)) {
-                WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
+                WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds<Stage::Chunk>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
                 attr_set[dev & 63].store(1, std::memory_order_release);
             }
             const int bpc = (WM_N_FRAMES + FPB8 - 1) / FPB8;
             WmProfScope ps(prof, "logmel_stage1_f32", stream);
-            logmel_stage1_f32_lds<false><<<n_chunks * bpc, W8 * 64, LDS8_BYTES, stream>>>(
+            logmel_stage1_f32_lds<Stage::Chunk><<<n_chunks * bpc, W8 * 64, LDS8_BYTES, stream>>>(
                 d_pcm, (int)pcm_dtype, n_mels, fe->cos32, fe->win32, fe->band_start[fi], fe->band_len[fi],
                 fe->band_w[fi], (float *)d_out, (unsigned long long *)fe->gmax, bpc, WmLongTab{});
         }
@@ -731,12 +745,12 @@ int wm_frontend_run_long(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, c
     int dev = 0;
     WM_HIP(hipGetDevice(&dev));
     if (!attr_set[dev & 63].load(std::memory_order_acquire)) {
-        WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
+        WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds<Stage::Long>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
         attr_set[dev & 63].store(1, std::memory_order_release);
     }
     {
         WmProfScope ps(prof, "logmel_long_stage1", stream);
-        logmel_stage1_f32_lds<true><<<(int)blk.size(), W8 * 64, LDS8_BYTES, stream>>>(
+        logmel_stage1_f32_lds<Stage::Long><<<(int)blk.size(), W8 * 64, LDS8_BYTES, stream>>>(
             d_pcm, (int)pcm_dtype, n_mels, fe->cos32, fe->win32, fe->band_start[fi], fe->band_len[fi], fe->band_w[fi],
             d_out, (unsigned long long *)fe->gmax, 0, lt);
     }
@@ -749,5 +763,26 @@ int wm_frontend_run_long(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, c
     WM_HIP(hipGetLastError());
     // the tables are pageable host memory: the copies must have read them before they go out of scope
     WM_HIP(hipStreamSynchronize(stream));
+    return WM_OK;
+}
+
+int wm_frontend_run_stream(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype, int n_mels,
+                           const WmStreamTab &tab, int n_blk, float *d_ring) {
+    WM_REQUIRE(fe->ready, WM_ERR_STATE, "front end not initialised");
+    const int fi = (n_mels == 80) ? 0 : 1;
+    WM_REQUIRE(fe->band_maxw[fi] <= BW8, WM_ERR_INVALID, "filterbank bands wider than %d bins", BW8);
+    if (n_blk == 0) return WM_OK;
+    static std::atomic<int> attr_set[64];
+    int dev = 0;
+    WM_HIP(hipGetDevice(&dev));
+    if (!attr_set[dev & 63].load(std::memory_order_acquire)) {
+        WM_HIP(hipFuncSetAttribute((const void *)logmel_stage1_f32_lds<Stage::Stream>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES));
+        attr_set[dev & 63].store(1, std::memory_order_release);
+    }
+    WmProfScope ps(prof, "logmel_stream_stage1", stream);
+    logmel_stage1_f32_lds<Stage::Stream><<<n_blk, W8 * 64, LDS8_BYTES, stream>>>(
+        d_pcm, (int)pcm_dtype, n_mels, fe->cos32, fe->win32, fe->band_start[fi], fe->band_len[fi], fe->band_w[fi], d_ring, nullptr, 0,
+        tab);
+    WM_HIP(hipGetLastError());
     return WM_OK;
 }

@@ -128,7 +128,32 @@ struct WmLongTab {
     const int2 *blk;
 };
 
+// wm_streams_push's geometry (frontend.hip, streams.hip): one record per stream of the set, one (stream, first span sample
+// relative to the carry, ring column of the first frame, frames) entry per workgroup of up to 64 frames.  Everything a
+// kernel sees is relative to the carry's first sample or to the ring: absolute stream time stays on the host, in 64 bits.
+constexpr int WM_STREAM_CARRY = 400;   // samples of a stream that frames which are not final still need: at most 399
+struct WmStreamRec {
+    long long pcm_base;  // first new sample of the stream in pcm
+    int carry_len;       // staged f32 samples held from earlier pushes (<= 399)
+    int n_new;           // new samples (0: the stream is not part of this push)
+    int reflect;         // the stream began at its sample 0: indices below it are reflected (else they read 0)
+    int shift;           // the next carry begins at this index of [carry | new samples]
+    int new_len;         // ... and holds this many samples (<= 399)
+    int pad;
+};
+struct WmStreamTab {
+    const WmStreamRec *rec;
+    const int4 *blk;
+    const float *carry;  // [S][WM_STREAM_CARRY]
+    float *fmax;         // [S][cap] a frame's maximum over its mel rows, by ring column
+    int cap;             // ring columns per stream
+};
+
 int wm_frontend_init(WmFrontend *fe, hipStream_t stream);
+// One launch of the f32 stage-1 kernel under the stream rule: n_blk workgroups of tab.blk, raw log10 values into
+// d_ring [S][n_mels][tab.cap], per-frame maxima into tab.fmax.
+int wm_frontend_run_stream(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const void *d_pcm, wm_dtype pcm_dtype, int n_mels,
+                           const WmStreamTab &tab, int n_blk, float *d_ring);
 void wm_frontend_destroy(WmFrontend *fe);
 // Device-pointer core: pcm [n][480000] (dtype) -> out [n][n_mels][3000] (f32 or f64).
 int wm_frontend_run(WmFrontend *fe, WmProfiler *prof, hipStream_t stream, const void *d_pcm,

@@ -349,6 +349,65 @@ struct Whisper {
         return result
     }
 
+    // ---- live streams (wm_streams_*): appended samples become log-mel frames incrementally on the device ----
+    typealias StreamsCreateFn = @convention(c) (OpaquePointer, Int32, Int32, Int32, UnsafeMutablePointer<OpaquePointer?>) -> Int32
+    typealias StreamsFreeFn = @convention(c) (OpaquePointer, OpaquePointer?) -> Int32
+    typealias StreamsPushFn = @convention(c) (OpaquePointer, OpaquePointer, UnsafeRawPointer?, Int32, UnsafePointer<Int64>,
+                                              Int32) -> Int32
+    typealias StreamsResetFn = @convention(c) (OpaquePointer, OpaquePointer, Int32) -> Int32
+    typealias StreamsFramesFn = @convention(c) (OpaquePointer, UnsafeMutablePointer<Int64>?, UnsafeMutablePointer<Int64>?,
+                                                UnsafeMutablePointer<Int64>?, UnsafeMutablePointer<Int64>?) -> Int32
+    typealias StreamsWindowFn = @convention(c) (OpaquePointer, OpaquePointer, Int32, UnsafePointer<Int32>, UnsafePointer<Int64>,
+                                                UnsafePointer<Int32>, UnsafeMutablePointer<Float>, UnsafePointer<Int64>,
+                                                Int32) -> Int32
+
+    /// A set of `count` live streams (wm_streams_create); free it with streamsFree before the context goes.
+    /// Not compiled in this repository (see the top of the file).
+    func streamsCreate(count: Int32, nMels: Int32 = 80, capacityFrames: Int32 = 3003) throws -> OpaquePointer {
+        var set: OpaquePointer?
+        let f: StreamsCreateFn = try sym("wm_streams_create")
+        try check(f(ctx, count, nMels, capacityFrames, &set))
+        return set!
+    }
+
+    func streamsFree(_ set: OpaquePointer) throws {
+        let f: StreamsFreeFn = try sym("wm_streams_free")
+        try check(f(ctx, set))
+    }
+
+    /// Appends pieces[s] (f32, 16 kHz; empty: nothing) to stream s: one launch for all streams (wm_streams_push).
+    func streamsPush(_ set: OpaquePointer, pieces: [[Float]]) throws {
+        var offsets: [Int64] = [0]
+        for p in pieces { offsets.append(offsets.last! + Int64(p.count)) }
+        let pcm = pieces.flatMap { $0 }
+        let f: StreamsPushFn = try sym("wm_streams_push")
+        try pcm.withUnsafeBytes { p in
+            try check(f(ctx, set, p.baseAddress, 1 /* WM_F32 */, offsets, 0))
+        }
+    }
+
+    func streamsReset(_ set: OpaquePointer, stream: Int32) throws {
+        let f: StreamsResetFn = try sym("wm_streams_reset")
+        try check(f(ctx, set, stream))
+    }
+
+    /// (samples, final frames, available frames, first kept frame) of each of the set's `count` streams (wm_streams_frames).
+    func streamsFrames(_ set: OpaquePointer, count: Int) throws -> (samples: [Int64], final: [Int64], avail: [Int64], firstKept: [Int64]) {
+        var n = [Int64](repeating: 0, count: count), fin = n, av = n, k = n
+        let f: StreamsFramesFn = try sym("wm_streams_frames")
+        try check(f(set, &n, &fin, &av, &k))
+        return (n, fin, av, k)
+    }
+
+    /// Frames [first, first + frames) of a stream, normalised as a recording that is the window (wm_streams_window), host
+    /// memory: [nMels][frames] row-major -- what the mel entries take with seek 0.
+    func streamsWindow(_ set: OpaquePointer, stream: Int32, first: Int64, frames: Int32, nMels: Int32 = 80) throws -> [Float] {
+        var out = [Float](repeating: 0, count: Int(nMels) * Int(frames))
+        let f: StreamsWindowFn = try sym("wm_streams_window")
+        try check(f(ctx, set, 1, [stream], [first], [frames], &out, [0], 0))
+        return out
+    }
+
     /// Recordings at their own sample rate and channel count -> 16 kHz mono f32 (wm_resample_16k: one launch, the polyphase
     /// Kaiser-sinc resampler of DESIGN.md section 12), host memory.  recordings[r] holds interleaved frames of channels[r]
     /// channels at sampleRates[r] Hz; the result feeds logMelLong as it is.
